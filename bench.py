@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the per-pixel Monte-Carlo sampling path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one frame of synthetic input (the seeded Shirley cover scene): every GPU renders
 its round-robin 8x8 tiles of the frame from the HBM-resident scene, one gather brings the tiles to GPU 0, GPU 0 assembles +
 quantises.  Inputs and outputs stay in HBM.
 
+A plain run sets up, warms up (W steps), times the K steps and prints the line: `value`, `ms_per_step` (wall time of one
+timed step) and the configuration.  --full adds what takes work of its own, all outside the timed region: the roofline
+object with the node-visit / exact-test counts (one more frame with the counting instantiation) and, at N = 1, the extra
+keys below (--no-extras / --no-e2e / --no-cpu-baseline drop parts of them).  --dump-outputs DIR writes what the caller of
+the timed path holds after the last timed step (dump_outputs).
+
   N = 1  BASELINE configs[2], the configuration the north star's target is quoted on: C3 = 1920x1080x256spp, cover scene
          n=50 (10 003 spheres), depth 50, BVH.  One frame in flight; `value` = samples / wall time of the K steps.  Extra keys
-         (outside the timed region): "pipelined" (two frames in flight), "c2" (configs[1]), "c4" (configs[3] on one GPU, the
-         N = 1 point of the strong-scaling curve), "cpu_baseline".
+         with --full (outside the timed region): "pipelined" (two frames in flight), "c2" (configs[1]), "c4" (configs[3] on
+         one GPU, the N = 1 point of the strong-scaling curve), "c5", "other_accel", the one-frame host, "cpu_baseline".
   N > 1  BASELINE configs[3]: C4 = 3840x2160x512spp cover scene n=11, STRONG scaling (the frame is fixed, its tiles are dealt
          round-robin over the N GPUs), the gather reported separately ("gather_ms").  Two launch forms, same arithmetic:
            * `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` (the driver's form): one process per GPU,
@@ -44,6 +50,8 @@ CONFIGS = {
     # ConstantMedium volumes, marble / image textures, a moving sphere, a rectangle light
     "FINAL": (500, 500, 128, 0, False, None),
 }
+DUMP_BUDGET = 64_000_000     # bytes, all files --dump-outputs writes together
+DUMP_SEED = 0x5EED0003       # the pixel sample of a frame too large for the budget
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8 TB/s
 L2_PEAK_GBS = 34500.0        # MI355X_MICROARCH.md: L2 aggregate ~34.5 TB/s
 SIMDS, CLOCK_GHZ = 1024, 2.4  # 256 CUs x 4 SIMDs; VALU issue peak = 1024 x 2.4e9 SIMD-cycles / s
@@ -256,6 +264,31 @@ def one_frame_host(r, flat, nx, ny, ns, precision, accel):
     return best
 
 
+def dump_outputs(path, outs):
+    """--dump-outputs: what the caller of the timed path holds after the last timed step, one .npy each -- linear.npy (the
+    averaged linear frame, float64), rgb8.npy (the quantised frame, as float32) and counters.npy (segments, pixels; float64).
+    A frame that does not fit DUMP_BUDGET is written as a fixed seeded sample of its pixels (the same for the same arguments):
+    linear / rgb8 are then (k, 3) and pixel_index.npy holds the k row-major pixel indices."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    ny, nx, _ = outs["linear"].shape
+    lin = outs["linear"].astype(np.float64)
+    q = outs["rgb8"].astype(np.float32)
+    cnt = outs["counters"].astype(np.float64)
+    header = 4 * 128  # one .npy header per file
+    idx_file = os.path.join(path, "pixel_index.npy")
+    if lin.nbytes + q.nbytes + cnt.nbytes + header > DUMP_BUDGET:
+        k = (DUMP_BUDGET - cnt.nbytes - header) // (3 * 8 + 3 * 4 + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(nx * ny, size=k, replace=False))
+        lin, q = lin.reshape(-1, 3)[idx], q.reshape(-1, 3)[idx]
+        np.save(idx_file, idx.astype(np.float64))
+    elif os.path.exists(idx_file):
+        os.remove(idx_file)  # left by an earlier dump of a larger frame
+    np.save(os.path.join(path, "linear.npy"), lin)
+    np.save(os.path.join(path, "rgb8.npy"), q)
+    np.save(os.path.join(path, "counters.npy"), cnt)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -263,9 +296,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS), help="default: C3 at --gpus 1, C4 at --gpus N > 1")
     ap.add_argument("--precision", default="f64", choices=["f64", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="N = 1: skip the one-frame-host figure (scene_create_ms / upload_bytes / end_to_end_ms); profiling runs use it so that every trace_kernel dispatch is a timed-workload launch")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1: skip the pipelined / C2 / C4 / other-accel extra measurements")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the roofline object and traversal counts and, at N = 1, "
+                                                        "the extras, the one-frame host and the CPU baseline (each outside the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's frame and counters to DIR/*.npy (at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full, N = 1: skip the one-frame-host figure (scene_create_ms / upload_bytes / end_to_end_ms); profiling runs use it so that every trace_kernel dispatch is a timed-workload launch")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, N = 1: skip the pipelined / C2 / C4 / other-accel extra measurements")
     ap.add_argument("--blocks-per-cu", type=int, default=0)
     ap.add_argument("--accel", default="bvh", choices=["flat", "bvh"], help="bvh = bvh-node descent (hitable.clj:97-123, what every reference scene builds); flat = Hitlist scan (hitable.clj:15-26)")
     ap.add_argument("--single", action="store_true", help="same as --no-extras")
@@ -339,7 +375,11 @@ def main():
             self.pl.set_option(k, v)
 
         def step(self, ns):
-            self.pl.step(ns, precision=args.precision)
+            self.last = self.pl.step(ns, precision=args.precision)
+
+        def outputs(self):  # rank 0 of the tile partition holds the frame
+            tr = self.last
+            return {"linear": tr.linear, "rgb8": tr.rgb8, "counters": tr.counters} if tr.rank == 0 else None
 
         def trace_ms(self):
             return self.pl.last_trace_ms()
@@ -381,6 +421,9 @@ def main():
         def step(self, ns):
             self.md.render_device(self.nx, self.ny, ns, self.lin, self.q, self.cnt, precision=args.precision)
 
+        def outputs(self):
+            return {"linear": self.lin, "rgb8": self.q, "counters": self.cnt}
+
         def trace_ms(self):
             per = self.md.last_trace_ms()
             self.per_replica = per  # every replica's (ms, launches) of the window: the line reports min / max, the roofline prices the slowest
@@ -406,7 +449,7 @@ def main():
         def gather_path(self):
             return self.md.last_gather_path()
 
-    def measure(drv, accel, steps, warmup, cfg_name, nx, ny, ns, n_prims, count=True):
+    def measure(drv, accel, steps, warmup, cfg_name, nx, ny, ns, n_prims, count=True, capture=False):
         drv.set_option("accel", 1 if accel == "bvh" else 0)
         drv.set_option("count_traversal", 0)
         for _ in range(max(warmup, drv.slots)):  # every slot allocates its sample workspace on its first frame: never in the timed region
@@ -419,6 +462,9 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         dt_local = dt
+        outs = None
+        if capture:  # the last timed step's results, before any later frame reuses the buffers
+            outs = {k: v.cpu().numpy() for k, v in (drv.outputs() or {}).items()} or None
         trace_ms, launches = drv.trace_ms()
         per_replica = list(getattr(drv, "per_replica", None) or [])  # in-library form: every replica's (ms, launches) of the timed window
         reduce_ms, reduce_launches = drv.reduce_ms()
@@ -437,7 +483,7 @@ def main():
         samples = nx * ny * ns
         counts = {"segments": seg_local if multi_proc else segments / (world if in_library else 1), "samples": samples / world, "pixels": nx * ny / world,
                   "aabb_tests": 0, "prim_tests": 0}
-        if count and accel == "bvh":  # one more frame with the counting instantiation (outside the timed region): node visits / leaf tests
+        if count and args.full and accel == "bvh":  # one more frame with the counting instantiation (outside the timed region): node visits / leaf tests
             drv.set_option("count_traversal", 1)
             drv.step(ns)
             barrier()
@@ -449,10 +495,11 @@ def main():
         launch_s = trace_ms / 1e3 / max(1, launches)
         res = {"value": round(samples / (dt / steps) / 1e6, 3), "ms_per_step": round(dt / steps * 1e3, 4), "segments": segments,
                "segments_per_sample": round(segments / samples, 4), "accel_ran": accel_ran,
-               "roofline": roofline(cfg_name, accel_ran, args.precision, n_prims, launch_s, launches_per_step, counts, share=1.0 / world),
                "trace_ms_per_step": round(trace_ms / max(1, steps), 4), "dt_local_ms": round(dt_local / steps * 1e3, 4), "segments_local": seg_local,
-               "per_replica": per_replica}
-        if reduce_launches:  # the one HBM-bound kernel of the path: the in-order per-pixel sample reduction (core.clj:52-53)
+               "per_replica": per_replica, "outputs": outs}
+        if args.full:
+            res["roofline"] = roofline(cfg_name, accel_ran, args.precision, n_prims, launch_s, launches_per_step, counts, share=1.0 / world)
+        if args.full and reduce_launches:  # the one HBM-bound kernel of the path: the in-order per-pixel sample reduction (core.clj:52-53)
             red_s = reduce_ms / 1e3 / reduce_launches
             red_bytes = (counts["samples"] * 24.0 + counts["pixels"] * 24.0 * (2 * launches_per_step - 1)) / launches_per_step  # samples read once; running sums written / re-read between passes
             res["roofline"]["reduce_kernel"] = {"bound": "hbm", "achieved": round(red_bytes / red_s / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -460,7 +507,7 @@ def main():
                                                 "bytes_per_launch": round(red_bytes), "share_of_step": round(reduce_ms / steps / (dt / steps * 1e3), 4),
                                                 "note": "reduce_kernel: one thread per pixel sums its samples in sample order (24 B each, coalesced 1536-B rows per tile and sample); "
                                                         "duration = HIP events from the trace kernel's end to the reduction's end on the launch stream"}
-        if count and accel == "bvh":
+        if count and args.full and accel == "bvh":
             res["aabb_tests_per_segment"] = round(counts["aabb_tests"] / max(1, counts["segments"]), 3)
             res["prim_tests_per_segment"] = round(counts["prim_tests"] / max(1, counts["segments"]), 3)
         if gather_ms is not None:
@@ -469,7 +516,7 @@ def main():
         return res
 
     drv = InLibrary(flat, nx, ny) if in_library else OneGpu(flat, nx, ny, max(1, args.frames_in_flight) if world == 1 else 1)
-    res = measure(drv, args.accel, args.steps, args.warmup, cfg, nx, ny, ns, n_prims)
+    res = measure(drv, args.accel, args.steps, args.warmup, cfg, nx, ny, ns, n_prims, capture=args.dump_outputs is not None)
 
     # ---- N > 1, one process per GPU: a line that proves what ran -- every rank reports its device, its own kernel time, segments and tiles --------------
     ranks_info = None
@@ -511,8 +558,9 @@ def main():
                        "depth": 50, "accel": args.accel, "accel_ran": res["accel_ran"], "frames_in_flight": drv.slots, "segments_per_sample": res["segments_per_sample"],
                        "launch_form": "one process per GPU (torch.distributed, RCCL gather)" if multi_proc else
                                       ("one host process, rtmi_render_multi_device (in-library ncclGather)" if in_library else "one GPU")},
-            "roofline": res["roofline"],
         }
+        if "roofline" in res:
+            out["roofline"] = res["roofline"]
         for k in ("aabb_tests_per_segment", "prim_tests_per_segment", "gather_ms", "gather_path"):
             if k in res:
                 out[k] = res[k]
@@ -530,8 +578,8 @@ def main():
         if rehearsal:
             out["rehearsal"] = True
             out["config"]["workload"] += " -- REHEARSAL: the %d replicas share %d device(s); control flow only, not a measurement" % (world, visible)
-    # ---- extras (N = 1 only, outside the timed region) -------------------------------------------------------------------
-    if world == 1 and extras and rank == 0:
+    # ---- extras (--full, N = 1 only, outside the timed region) ------------------------------------------------------------
+    if world == 1 and args.full and extras and rank == 0:
         if drv.slots == 1:
             two = OneGpu(flat, nx, ny, 2)
             p = measure(two, args.accel, max(2, min(args.steps, 5)), 2, cfg, nx, ny, ns, n_prims, count=False)
@@ -557,15 +605,17 @@ def main():
             o = measure(drv, other_accel, max(2, min(args.steps, 5)), 1, cfg, nx, ny, ns, n_prims)
             out["other_accel"] = {"accel": other_accel, "value": o["value"], "ms_per_step": o["ms_per_step"], "roofline": o["roofline"]}
     if rank == 0:
-        if world == 1 and not args.no_e2e:  # section 8(d): scene upload reported separately and included in an end-to-end figure
+        if world == 1 and args.full and not args.no_e2e:  # section 8(d): scene upload reported separately and included in an end-to-end figure
             drv_close = getattr(getattr(drv, "pl", None), "close", None)
             if drv_close:
                 drv_close()  # release the timed driver's workspace first: the one-frame host allocates its own
             e2e = one_frame_host(r, flat, nx, ny, ns, args.precision, args.accel)
             out["scene_create_ms"], out["upload_bytes"], out["end_to_end_ms"] = e2e["scene_create_ms"], e2e["upload_bytes"], e2e["end_to_end_ms"]
             out["one_frame_host"] = e2e
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, flat, nx, ny, ns)
+        if args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, res["outputs"])
         print(json.dumps(out), flush=True)
     if multi_proc:
         dist.barrier()

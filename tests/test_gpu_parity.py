@@ -598,9 +598,9 @@ def _bench(args, env=None, launcher=None, timeout=900):
 
 
 def test_bench_json_schema():
-    """bench.py prints ONE JSON line with the contract's keys (run as the driver runs it, tiny step counts): the N = 1 line is
-    the north-star configuration C3, one frame in flight, with a roofline object no fraction of which exceeds 1"""
-    d = _bench(["--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
+    """bench.py --full prints ONE JSON line with the contract's keys (tiny step counts): the N = 1 line is the north-star
+    configuration C3, one frame in flight, with a roofline object no fraction of which exceeds 1"""
+    d = _bench(["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["dtype"] == "f64" and d["vs_baseline"] is None and d["value"] > 100
@@ -630,9 +630,31 @@ def test_bench_json_schema():
 
 
 def test_bench_other_configs_and_flat():
-    d = _bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--config", "C2"])
+    d = _bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--config", "C2", "--full"])
     assert d["config"]["workload"].startswith("C2:") and d["other_accel"]["accel"] == "flat" and d["other_accel"]["value"] > 100
     assert d["other_accel"]["roofline"]["hbm"]["frac"] < 1
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) times the steps and prints the headline line only; --dump-outputs writes the last timed step's
+    frame and counters, which are those of the same frame rendered here through the same path"""
+    import bench
+    from raytrace_clj_amd import dist as rdist
+    d = _bench(["--config", "C1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert d["metric"] == "Msamples/sec (nx*ny*ns)" and d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] == pytest.approx(200 * 100 * 4 / d["ms_per_step"] / 1e3, rel=1e-2)
+    for k in ("roofline", "aabb_tests_per_segment", "pipelined", "c2", "c4", "c5", "other_accel", "scene_create_ms", "one_frame_host", "cpu_baseline"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ["counters.npy", "linear.npy", "rgb8.npy"]  # a 200x100 frame fits the budget whole
+    lin, q, cnt = (np.load(os.path.join(tmp_path, n + ".npy")) for n in ("linear", "rgb8", "counters"))
+    assert lin.dtype == np.float64 and q.dtype == np.float32 and cnt.dtype == np.float64 and lin.shape == q.shape == (100, 200, 3)
+    _, flat = bench.build_scene(r, "C1")
+    pl = rdist.FramePipeline(flat, 200, 100, 0, 1, 0, depth=1, options={"accel": 1})
+    tr = pl.step(4)
+    pl.sync()
+    assert np.array_equal(lin, tr.linear.cpu().numpy()) and np.array_equal(q, tr.rgb8.cpu().numpy().astype(np.float32))
+    assert np.array_equal(cnt, tr.counters.cpu().numpy().astype(np.float64)) and cnt[1] == 200 * 100
+    pl.close()
 
 
 def test_two_rank_control_flow_rehearsal():

@@ -348,6 +348,33 @@ def test_bench_roofline_object_is_consistent():
     assert "flat_scan_flops" in flat and flat["on_chip_fetch"]["frac"] < 1
 
 
+def test_bench_dump_outputs_fit_the_budget(tmp_path):
+    """bench.py --dump-outputs: a frame that fits is written whole; the C3 frame (1920x1080) is not, and becomes the same seeded pixel
+    sample in every run, the files together within 64 MB, in float32 / float64"""
+    import bench
+    rng = np.random.default_rng(5)
+    ny, nx = 1080, 1920
+    outs = {"linear": rng.random((ny, nx, 3)), "rgb8": rng.integers(0, 256, (ny, nx, 3), dtype=np.uint8), "counters": np.array([1430000000, nx * ny], np.int64)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), outs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["counters.npy", "linear.npy", "pixel_index.npy", "rgb8.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    for f in files:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes(), f
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    lin, q, cnt = (np.load(tmp_path / "a" / (n + ".npy")) for n in ("linear", "rgb8", "counters"))
+    assert idx.dtype == lin.dtype == cnt.dtype == np.float64 and q.dtype == np.float32
+    assert len(idx) > nx * ny // 2 and np.all(np.diff(idx) > 0) and lin.shape == q.shape == (len(idx), 3)
+    i = idx.astype(np.int64)
+    assert np.array_equal(lin, outs["linear"].reshape(-1, 3)[i]) and np.array_equal(q, outs["rgb8"].reshape(-1, 3)[i].astype(np.float32))
+    assert np.array_equal(cnt, outs["counters"].astype(np.float64))
+    small = {k: (v[:100, :200] if v.ndim == 3 else v) for k, v in outs.items()}
+    bench.dump_outputs(str(tmp_path / "a"), small)  # whole frame; the earlier sample's index does not stay behind
+    assert sorted(os.listdir(tmp_path / "a")) == ["counters.npy", "linear.npy", "rgb8.npy"]
+    assert np.array_equal(np.load(tmp_path / "a" / "linear.npy"), small["linear"])
+
+
 def test_half_outward_is_directed_rounding_to_half():
     """the tree's half-plane node records round every box plane OUTWARD to IEEE half (rtmi.hip: half_outward, integer arithmetic on the float's bits): against
     numpy's round-to-nearest half stepped to the neighbour on the required side -- one million floats over the whole half range and beyond, subnormals, signed
