@@ -742,6 +742,8 @@ __global__ void probe_arith_kernel(int n, const double *abc, double *out) {
 // =====================================================================================================
 // host side: C-ABI
 // =====================================================================================================
+#include "scene_build.h"
+
 namespace {
 
 thread_local std::string g_err;
@@ -862,14 +864,19 @@ namespace {
 bool ctx_ok(rtmi_ctx *c) { return c && c->magic == 0x52544d49u; }
 bool scene_ok(rtmi_scene *s) { return s && s->magic == 0x52545343u && ctx_ok(s->ctx); }
 
-template <typename T> int upload(rtmi_scene *s, const std::vector<T> &v, const T **out) {
+// one scene table: its host copy and the DevScene field that receives its device address
+struct Table {
+    const void *data; size_t bytes, elem; const void **field;
+    template <typename T> Table(const std::vector<T> &v, const T **f) : data(v.data()), bytes(v.size() * sizeof(T)), elem(sizeof(T)), field(reinterpret_cast<const void **>(f)) {}
+};
+int upload(rtmi_scene *s, const Table &t) { // (an empty table still gets one element)
     void *p = nullptr;
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    if (hipMalloc(&p, bytes) != hipSuccess) return fail(RTMI_E_NOMEM, "hipMalloc(%zu) failed", bytes);
+    const size_t alloc = std::max(t.bytes, t.elem);
+    if (hipMalloc(&p, alloc) != hipSuccess) return fail(RTMI_E_NOMEM, "hipMalloc(%zu) failed", alloc);
     s->allocs.push_back(p);
-    s->device_bytes += bytes;
-    if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = reinterpret_cast<const T *>(p);
+    s->device_bytes += alloc;
+    if (t.bytes) HIP_TRY(hipMemcpy(p, t.data, t.bytes, hipMemcpyHostToDevice));
+    *t.field = p;
     return RTMI_OK;
 }
 
@@ -927,6 +934,125 @@ int next_event_pair(rtmi_ctx *c, hipEvent_t *a, hipEvent_t *b) {
     return RTMI_OK;
 }
 
+// ---- which trace kernel a render launches --------------------------------------------------------------------------
+// The launch knobs, read once per render call (null: not set).  RTMI_FLAT_BELOW / RTMI_SUSPEND_LANES override the options of the same names;
+// RTMI_SPHERE_LDS_STASH=0 keeps the time-sliced sphere kernel's camera-ray stash in registers.
+struct LaunchKnobs { const char *flat_below, *suspend_lanes, *sphere_stash; };
+LaunchKnobs read_launch_knobs() { return {std::getenv("RTMI_FLAT_BELOW"), std::getenv("RTMI_SUSPEND_LANES"), std::getenv("RTMI_SPHERE_LDS_STASH")}; }
+
+// Dynamic LDS of a BVH kernel, per lane in words: `levels` stack columns, then `susp_words` of parked cursors (time-sliced instantiations), then
+// `stash_words` of camera-ray stash; susp_off / stash_off are where the last two begin (TraceParams)
+struct LdsLayout { int susp_off, stash_off; size_t bytes; };
+LdsLayout lds_layout(int levels, int susp_words, int stash_words) {
+    return {levels * RTMI_BVH_STRIDE, (levels + susp_words) * RTMI_BVH_STRIDE, (size_t)(levels + susp_words + stash_words) * kTraceBlock * sizeof(int)};
+}
+
+struct TracePlan {
+    void (*kern)(ScenePtr, TraceParams) = nullptr;
+    LdsLayout lds{RTMI_BVH_STACK * RTMI_BVH_STRIDE, 0, 0}; // (the sphere kernels' stack has the compile-time RTMI_BVH_STACK levels: immediate ds_ offsets)
+    int suspend_lanes = 0;
+    int accel = RTMI_ACCEL_BVH; // what runs: the request for the tree may be answered with the flat scan (rtmi_last_accel)
+};
+
+// The trace kernel of a render, its LDS layout and its time-slicing threshold.  multi / lds_bytes: the LDS tiling of the static spheres (lds_plan).
+template <typename R>
+TracePlan choose_trace_kernel(const rtmi_scene *s, const rtmi_ctx *c, const LaunchKnobs &k, bool multi, size_t lds_bytes) {
+    const DevScene &d = s->dev;
+    TracePlan p;
+    int variant = c->accel == RTMI_ACCEL_BVH ? SCAN_BVH : c->scan_variant;
+    // a tree over a handful of mixed-kind primitives costs more than scanning them: a Cornell box's 18 (six of them too big for the tree anyway)
+    // trace 8 % faster through the scalar-cache scan, the 3 - 8 of the small f3 / f4 scenes 3 - 10 %.  The two paths are bit-identical (tested
+    // scene by scene), so the request for the tree is answered with the scan -- unless the tree's traversal counters were asked for.
+    const int below = k.flat_below ? std::atoi(k.flat_below) : c->flat_below;
+    if (variant == SCAN_BVH && d.has_ext && !c->count_traversal && d.n_all < below) variant = SCAN_SGPR_CULL;
+    p.accel = variant == SCAN_BVH ? RTMI_ACCEL_BVH : RTMI_ACCEL_FLAT;
+    const bool bvh = variant == SCAN_BVH, count = c->count_traversal != 0;
+    p.suspend_lanes = c->suspend_lanes;
+    if (d.has_ext && !c->suspend_lanes_set) p.suspend_lanes = 12; // make-final, 20 frames each, thresholds 8 / 10 / 12 / 14: 16.22 - 16.30 / 16.16 - 16.21 / 16.12 - 16.20 / 16.21 - 16.22 ms
+    if (k.suspend_lanes) p.suspend_lanes = std::max(0, std::min(64, std::atoi(k.suspend_lanes)));
+    // Stack columns for THIS scene's tree (its depth is known) and the camera-ray stash: 11 words per entry, 17 when the rays' origins differ
+    const int levels = std::max(4, std::min(RTMI_BVH_STACK, s->bvh_depth + 2));
+    const int stash_words = d.cam_fixed_origin ? 11 : 17;
+    constexpr bool kExtLdsStash = RTMI_STASH && RTMI_EXT_LDS_STASH && !RTMI_EXT_NO_STASH;
+    if (d.has_ext && d.media_seq) { // a Hitlist world holding media (RTMI_MEDIA_HITLIST): its own instantiations, never time-sliced
+        const bool nar = d.media_seq == 2; // RTMI_MEDIA_NARROWED: Hitlists holding media below bvh-nodes (MSEQ = 2)
+        if (bvh && nar) p.kern = count ? trace_kernel<double, false, SCAN_BVH, true, true, false, 2> : trace_kernel<double, false, SCAN_BVH, true, false, false, 2>;
+        else if (bvh) p.kern = count ? trace_kernel<double, false, SCAN_BVH, true, true, false, 1> : trace_kernel<double, false, SCAN_BVH, true, false, false, 1>;
+        else p.kern = nar ? trace_kernel<double, false, SCAN_SGPR_CULL, true, false, true, 2> : trace_kernel<double, false, SCAN_SGPR_CULL, true, false, true, 1>;
+        p.lds = lds_layout(bvh ? levels : 0, 0, kExtLdsStash ? stash_words : 0);
+    } else if (d.has_ext) { // section 8(f3) scenes: FP64 kernels with the mixed-kind intersectors
+        // a Cornell box's 20-primitive tree loses 5 % to the time-slicing machinery, make-final's 3400 gain 8 %
+        const bool slice = bvh && s->bvh_node_count >= 128 && p.suspend_lanes > 0;
+        if (bvh && count) p.kern = slice ? trace_kernel<double, false, SCAN_BVH, true, true> : trace_kernel<double, false, SCAN_BVH, true, true, false>;
+        else if (bvh) p.kern = slice ? trace_kernel<double, false, SCAN_BVH, true> : trace_kernel<double, false, SCAN_BVH, true, false, false>;
+        else p.kern = trace_kernel<double, false, SCAN_SGPR_CULL, true>;
+        p.lds = lds_layout(bvh ? levels : 0, slice ? RTMI_BVH_SUSPEND_WORDS_EXT : 0, kExtLdsStash ? stash_words : 0);
+    } else if (bvh) {
+        // suspend_lanes = 0 or a small tree (< 128 inner nodes) selects the instantiation without the time-slicing machinery (the plain while-while loop);
+        // a scene with an entry grid always runs the time-sliced one (threshold 0 = never park early): the piecewise walk of long segments lives there
+        const bool slice = (p.suspend_lanes > 0 && s->bvh_node_count >= 128) || d.grid_n > 0;
+        p.lds.bytes = (size_t)(RTMI_BVH_STACK + RTMI_BVH_SUSPEND_WORDS) * kTraceBlock * sizeof(int); // stack columns + suspended cursors
+        // The time-sliced sphere kernel keeps its camera-ray stash in LDS too when the scene's tree leaves room for it beside the stack columns (a dead lane reads
+        // its entry with 6 ds_read instead of 11 ds_bpermute, and 14 VGPRs come free): C3 69.30 -> 68.76 ms, C2 3.067 -> 3.040 (RTMI_SPHERE_LDS_STASH=0: the
+        // register stash, which deeper trees -- more than 21 levels with their grid entries -- keep anyway: a fifth kilobyte-row would cost the fourth workgroup per CU)
+        const LdsLayout stash = lds_layout(levels, RTMI_BVH_SUSPEND_WORDS, stash_words);
+        if (slice) p.kern = count ? trace_kernel<R, false, SCAN_BVH, false, true> : trace_kernel<R, false, SCAN_BVH>;
+        else p.kern = count ? trace_kernel<R, false, SCAN_BVH, false, true, false> : trace_kernel<R, false, SCAN_BVH, false, false, false>;
+        if (slice && !count && !(k.sphere_stash && k.sphere_stash[0] == '0') && stash.bytes <= 40 * 1024) { p.kern = trace_kernel<R, false, SCAN_BVH, false, false, true, false, true>; p.lds = stash; } // four workgroups per CU still fit
+    } else if (variant == SCAN_SGPR_CULL) p.kern = trace_kernel<R, false, SCAN_SGPR_CULL>;
+    else if (variant == SCAN_SGPR) p.kern = trace_kernel<R, false, SCAN_SGPR>;
+    else {
+        p.kern = variant == SCAN_LDS_PIPE ? (multi ? trace_kernel<R, true, SCAN_LDS_PIPE> : trace_kernel<R, false, SCAN_LDS_PIPE>)
+                                          : (multi ? trace_kernel<R, true, SCAN_LDS_LITERAL> : trace_kernel<R, false, SCAN_LDS_LITERAL>);
+        p.lds.bytes = lds_bytes;
+    }
+    return p;
+}
+
+#ifdef RTMI_STAMPS
+// diagnostic build only (make stamps): the in-kernel phase stamps of the last trace launch, reported on stderr and cleared
+int report_phase_stamps(rtmi_ctx *c, hipStream_t st) {
+    const int grid_trace_dbg = c->last_grid;
+    HIP_TRY(hipStreamSynchronize(st));
+    unsigned long long h[3 * PH_SLOTS] = {0}, z[3 * PH_SLOTS] = {0};
+    HIP_TRY(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase), sizeof(h)));
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z)));
+    {
+        static unsigned long long wt[2][4096];
+        HIP_TRY(hipMemcpyFromSymbol(wt, HIP_SYMBOL(g_wg_t), sizeof(wt)));
+        const int g = std::min(4096, grid_trace_dbg);
+        unsigned long long t0 = ~0ull; for (int k = 0; k < g; ++k) t0 = std::min(t0, wt[0][k]);
+        std::vector<double> e(g), b(g); for (int k = 0; k < g; ++k) { e[k] = (wt[1][k] - t0) * 1e-5; b[k] = (wt[0][k] - t0) * 1e-5; }
+        std::sort(e.begin(), e.end()); std::sort(b.begin(), b.end());
+        fprintf(stderr, "[stamps] workgroup start (ms after first): median %.3f max %.3f | end: min %.3f p10 %.3f median %.3f p90 %.3f max %.3f (last pass, %d workgroups)\n",
+                b[g / 2], b[g - 1], e[0], e[g / 10], e[g / 2], e[g * 9 / 10], e[g - 1], g);
+    }
+    static const char *names[PH_N] = {"loop/tail", "refill: generate 64 camera rays", "refill: claim + deal", "bvh: ray setup / resume", "bvh: big primitives (exact)",
+                                      "bvh: descent (node visits)", "bvh: leaf exact tests", "bvh: loop control / park", "shade: hit record", "shade: |d| normalise",
+                                      "shade: rand-in-unit-sphere", "shade: material record + directions", "shade: texture", "shade: store / rest", "shade: sphere uv", "(stamp calibration)",
+                                      "bvh: grid entry / next piece of the walk", "media: chords, draws, log"};
+    // every interval begins with the bookkeeping of the stamp that opened it: subtract the cost of one stamp (PH_CAL: back-to-back stamps) per stamp
+    const double per_stamp = h[2 * PH_SLOTS + PH_CAL] ? (double)h[PH_CAL] / (double)h[2 * PH_SLOTS + PH_CAL] : 0.0;
+    double tk[PH_N], lk[PH_N], tot = 0, totl = 0, raw = 0;
+    for (int k = 0; k < PH_N; ++k) {
+        raw += (double)h[k];
+        const double t = (double)h[k], c = std::min(t, per_stamp * (double)h[2 * PH_SLOTS + k]);
+        tk[k] = k == PH_CAL ? 0.0 : t - c;
+        lk[k] = t > 0 ? (double)h[PH_SLOTS + k] * (tk[k] / t) : 0.0;
+        tot += tk[k]; totl += lk[k];
+    }
+    fprintf(stderr, "[phases] one stamp = %.0f ticks; stamps took %.1f %% of the %.4g wave-ticks of this (diagnostic) launch and are subtracted below\n", per_stamp, 100 * (raw - tot) / raw, raw);
+    fprintf(stderr, "[phases] %-36s %8s %8s %10s %10s %12s\n", "phase", "ticks %", "lanes", "masked %", "useful %", "stamps");
+    for (int k = 0; k < PH_N; ++k) {
+        if (!h[k] || k == PH_CAL) continue;
+        const double t = tk[k], l = lk[k];
+        fprintf(stderr, "[phases] %-36s %8.2f %8.1f %10.2f %10.2f %12llu\n", names[k], 100 * t / tot, t > 0 ? l / t : 0.0, 100 * (64 * t - l) / (64 * tot), 100 * l / (64 * tot), h[2 * PH_SLOTS + k]);
+    }
+    fprintf(stderr, "[phases] %-36s %8.2f %8.1f %10.2f %10.2f   (%.4g wave-ticks)\n", "total", 100.0, totl / tot, 100 * (64 * tot - totl) / (64 * tot), 100 * totl / (64 * tot), tot);
+    return RTMI_OK;
+}
+#endif
+
 template <typename R>
 int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t seed, int first, int stride, const int *rg, void *d_tiles_linear,
                       void *d_counters, hipStream_t st) {
@@ -980,7 +1106,8 @@ int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t
     int ppt, nptiles;
     size_t lds_bytes;
     lds_plan(c, s->dev.n_static, sizeof(R), &ppt, &nptiles, &lds_bytes);
-    const bool multi = nptiles > 1;
+    const TracePlan plan = choose_trace_kernel<R>(s, c, read_launch_knobs(), nptiles > 1, lds_bytes);
+    c->last_accel = plan.accel;
 
     for (int s_begin = 0; s_begin < ns; s_begin += s_per_pass) {
         const int s_count = std::min(s_per_pass, ns - s_begin);
@@ -1008,92 +1135,24 @@ int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t
         }
         tp.rx0 = std::max(rg[0], 0); tp.ry0 = std::max(rg[1], 0); tp.rx1 = std::min(rg[2], nx); tp.ry1 = std::min(rg[3], ny);
         tp.trav = reinterpret_cast<u64 *>(c->counters.p) + 3;
+        tp.suspend_lanes = plan.suspend_lanes; tp.susp_off = plan.lds.susp_off; tp.stash_off = plan.lds.stash_off;
         HIP_TRY(hipMemsetAsync(queue, 0, sizeof(unsigned), st));
-        int variant = c->accel == RTMI_ACCEL_BVH ? SCAN_BVH : c->scan_variant;
-        { // a tree over a handful of mixed-kind primitives costs more than scanning them: a Cornell box's 18 (six of them too big for the tree anyway)
-          // trace 8 % faster through the scalar-cache scan, the 3 - 8 of the small f3 / f4 scenes 3 - 10 %.  The two paths are bit-identical (tested
-          // scene by scene), so the request for the tree is answered with the scan -- unless the tree's traversal counters were asked for.
-            int below = c->flat_below;
-            if (const char *e = std::getenv("RTMI_FLAT_BELOW")) below = std::atoi(e);
-            if (variant == SCAN_BVH && s->dev.has_ext && !c->count_traversal && s->dev.n_all < below) variant = SCAN_SGPR_CULL;
-            c->last_accel = variant == SCAN_BVH ? RTMI_ACCEL_BVH : RTMI_ACCEL_FLAT;
-        }
-        void (*kern)(ScenePtr, TraceParams) = nullptr;
-        size_t dyn_lds = 0;
-        const size_t bvh_lds = (size_t)(RTMI_BVH_STACK + RTMI_BVH_SUSPEND_WORDS) * kTraceBlock * sizeof(int); // stack columns + suspended cursors
-        tp.suspend_lanes = c->suspend_lanes;
-        if (s->dev.has_ext && !c->suspend_lanes_set) tp.suspend_lanes = 12; // make-final, 20 frames each, thresholds 8 / 10 / 12 / 14: 16.22 - 16.30 / 16.16 - 16.21 / 16.12 - 16.20 / 16.21 - 16.22 ms
-        if (const char *e = std::getenv("RTMI_SUSPEND_LANES")) tp.suspend_lanes = std::max(0, std::min(64, std::atoi(e)));
-        // Mixed-kind kernels: LDS = stack columns for THIS scene's tree (its depth is known: the sphere kernels use the compile-time RTMI_BVH_STACK for their
-        // immediate ds_ offsets) + the parked cursors (time-sliced instantiation) + the camera-ray stash (11 words per entry, 17 when the rays' origins differ)
-        tp.susp_off = RTMI_BVH_STACK * RTMI_BVH_STRIDE; tp.stash_off = 0;
-        const char *lst_env = std::getenv("RTMI_SPHERE_LDS_STASH");
-        constexpr bool kExtLdsStash = RTMI_STASH && RTMI_EXT_LDS_STASH && !RTMI_EXT_NO_STASH;
-        const int ext_levels = std::max(4, std::min(RTMI_BVH_STACK, s->bvh_depth + 2));
-        const int stash_words = kExtLdsStash ? (s->dev.cam_fixed_origin ? 11 : 17) : 0;
-        auto ext_lds = [&](bool bvh, int susp_words) {
-            const int levels = bvh ? ext_levels : 0;
-            tp.susp_off = levels * RTMI_BVH_STRIDE;
-            tp.stash_off = (levels + susp_words) * RTMI_BVH_STRIDE;
-            return (size_t)(levels + susp_words + stash_words) * kTraceBlock * sizeof(int);
-        };
-        if (s->dev.has_ext && s->dev.media_seq) { // a Hitlist world holding media (RTMI_MEDIA_HITLIST): its own instantiations, never time-sliced
-            const bool nar = s->dev.media_seq == 2; // RTMI_MEDIA_NARROWED: Hitlists holding media below bvh-nodes (MSEQ = 2)
-            if (variant == SCAN_BVH) {
-                if (nar) kern = c->count_traversal ? trace_kernel<double, false, SCAN_BVH, true, true, false, 2> : trace_kernel<double, false, SCAN_BVH, true, false, false, 2>;
-                else kern = c->count_traversal ? trace_kernel<double, false, SCAN_BVH, true, true, false, 1> : trace_kernel<double, false, SCAN_BVH, true, false, false, 1>;
-                dyn_lds = ext_lds(true, 0);
-            } else { kern = nar ? trace_kernel<double, false, SCAN_SGPR_CULL, true, false, true, 2> : trace_kernel<double, false, SCAN_SGPR_CULL, true, false, true, 1>; dyn_lds = ext_lds(false, 0); }
-        } else if (s->dev.has_ext) { // section 8(f3) scenes: FP64 kernels with the mixed-kind intersectors
-            if (variant == SCAN_BVH) { // a Cornell box's 20-primitive tree loses 5 % to the time-slicing machinery, make-final's 3400 gain 8 %
-                const bool slice = s->bvh_node_count >= 128 && tp.suspend_lanes > 0;
-                if (c->count_traversal) kern = slice ? trace_kernel<double, false, SCAN_BVH, true, true> : trace_kernel<double, false, SCAN_BVH, true, true, false>;
-                else kern = slice ? trace_kernel<double, false, SCAN_BVH, true> : trace_kernel<double, false, SCAN_BVH, true, false, false>;
-                dyn_lds = ext_lds(true, slice ? RTMI_BVH_SUSPEND_WORDS_EXT : 0);
-            }
-            else { kern = trace_kernel<double, false, SCAN_SGPR_CULL, true>; dyn_lds = ext_lds(false, 0); }
-        } else
-        switch (variant) {
-        case SCAN_BVH: // suspend_lanes = 0 or a small tree (< 128 inner nodes) selects the instantiation without the time-slicing machinery (the plain while-while loop);
-                       // a scene with an entry grid always runs the time-sliced one (threshold 0 = never park early): the piecewise walk of long segments lives there
-            if ((tp.suspend_lanes > 0 && s->bvh_node_count >= 128) || s->dev.grid_n > 0) kern = c->count_traversal ? trace_kernel<R, false, SCAN_BVH, false, true> : trace_kernel<R, false, SCAN_BVH>;
-            else kern = c->count_traversal ? trace_kernel<R, false, SCAN_BVH, false, true, false> : trace_kernel<R, false, SCAN_BVH, false, false, false>;
-            dyn_lds = bvh_lds;
-            // The time-sliced sphere kernel keeps its camera-ray stash in LDS too when the scene's tree leaves room for it beside the stack columns (a dead lane reads
-            // its entry with 6 ds_read instead of 11 ds_bpermute, and 14 VGPRs come free): C3 69.30 -> 68.76 ms, C2 3.067 -> 3.040 (RTMI_SPHERE_LDS_STASH=0: the
-            // register stash, which deeper trees -- more than 21 levels with their grid entries -- keep anyway: a fifth kilobyte-row would cost the fourth workgroup per CU)
-            if (!(lst_env && lst_env[0] == '0') && !c->count_traversal && kern == (void (*)(ScenePtr, TraceParams))trace_kernel<R, false, SCAN_BVH>) {
-                const int levels = std::max(4, std::min(RTMI_BVH_STACK, s->bvh_depth + 2));
-                const int words = s->dev.cam_fixed_origin ? 11 : 17;
-                if ((size_t)(levels + RTMI_BVH_SUSPEND_WORDS + words) * kTraceBlock * sizeof(int) <= 40 * 1024) { // four workgroups per CU still fit
-                    kern = trace_kernel<R, false, SCAN_BVH, false, false, true, false, true>;
-                    tp.susp_off = levels * RTMI_BVH_STRIDE;
-                    tp.stash_off = (levels + RTMI_BVH_SUSPEND_WORDS) * RTMI_BVH_STRIDE;
-                    dyn_lds = (size_t)(levels + RTMI_BVH_SUSPEND_WORDS + words) * kTraceBlock * sizeof(int);
-                }
-            }
-            break;
-        case SCAN_SGPR_CULL: kern = trace_kernel<R, false, SCAN_SGPR_CULL>; break;
-        case SCAN_SGPR: kern = trace_kernel<R, false, SCAN_SGPR>; break;
-        case SCAN_LDS_PIPE: kern = multi ? trace_kernel<R, true, SCAN_LDS_PIPE> : trace_kernel<R, false, SCAN_LDS_PIPE>; dyn_lds = lds_bytes; break;
-        default: kern = multi ? trace_kernel<R, true, SCAN_LDS_LITERAL> : trace_kernel<R, false, SCAN_LDS_LITERAL>; dyn_lds = lds_bytes;
-        }
         // persistent launch: as many workgroups as stay resident (at most blocks_per_cu per CU); the queue feeds them
         int resident = 0;
         { // the occupancy query is a runtime call per launch and replica: asked once per (kernel, LDS bytes) and kept on the context
-            const std::pair<const void *, size_t> key(reinterpret_cast<const void *>(kern), dyn_lds);
+            const std::pair<const void *, size_t> key(reinterpret_cast<const void *>(plan.kern), plan.lds.bytes);
             auto it = c->occupancy.find(key);
             if (it == c->occupancy.end()) {
-                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kern, kTraceBlock, dyn_lds));
+                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, plan.kern, kTraceBlock, plan.lds.bytes));
                 c->occupancy.emplace(key, resident);
             } else resident = it->second;
         }
         const int grid_trace = std::max(1, c->cus * std::max(1, std::min(c->blocks_per_cu * (256 / kTraceBlock), resident)));
         if (c->last_grid != grid_trace && std::getenv("RTMI_DEBUG"))
             fprintf(stderr, "[rtmi] trace launch: %d workgroups of %d threads (%d resident per CU by the occupancy query, cap %d), %zu B LDS each\n",
-                    grid_trace, kTraceBlock, resident, c->blocks_per_cu * (256 / kTraceBlock), dyn_lds);
+                    grid_trace, kTraceBlock, resident, c->blocks_per_cu * (256 / kTraceBlock), plan.lds.bytes);
         c->last_grid = grid_trace;
-        hipLaunchKernelGGL(kern, dim3(grid_trace), dim3(kTraceBlock), dyn_lds, st, s->d_dev, tp);
+        hipLaunchKernelGGL(plan.kern, dim3(grid_trace), dim3(kTraceBlock), plan.lds.bytes, st, s->d_dev, tp);
         HIP_TRY(hipGetLastError());
         if (e1) HIP_TRY(hipEventRecord(e1, st));
         const long long npx = (long long)n_local * 64;
@@ -1109,647 +1168,9 @@ int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t
         }
     }
 #ifdef RTMI_STAMPS
-    {
-        const int grid_trace_dbg = c->last_grid;
-        HIP_TRY(hipStreamSynchronize(st));
-        unsigned long long h[3 * PH_SLOTS] = {0}, z[3 * PH_SLOTS] = {0};
-        HIP_TRY(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase), sizeof(h)));
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase), z, sizeof(z)));
-        {
-            static unsigned long long wt[2][4096];
-            HIP_TRY(hipMemcpyFromSymbol(wt, HIP_SYMBOL(g_wg_t), sizeof(wt)));
-            const int g = std::min(4096, grid_trace_dbg);
-            unsigned long long t0 = ~0ull; for (int k = 0; k < g; ++k) t0 = std::min(t0, wt[0][k]);
-            std::vector<double> e(g), b(g); for (int k = 0; k < g; ++k) { e[k] = (wt[1][k] - t0) * 1e-5; b[k] = (wt[0][k] - t0) * 1e-5; }
-            std::sort(e.begin(), e.end()); std::sort(b.begin(), b.end());
-            fprintf(stderr, "[stamps] workgroup start (ms after first): median %.3f max %.3f | end: min %.3f p10 %.3f median %.3f p90 %.3f max %.3f (last pass, %d workgroups)\n",
-                    b[g / 2], b[g - 1], e[0], e[g / 10], e[g / 2], e[g * 9 / 10], e[g - 1], g);
-        }
-        static const char *names[PH_N] = {"loop/tail", "refill: generate 64 camera rays", "refill: claim + deal", "bvh: ray setup / resume", "bvh: big primitives (exact)",
-                                          "bvh: descent (node visits)", "bvh: leaf exact tests", "bvh: loop control / park", "shade: hit record", "shade: |d| normalise",
-                                          "shade: rand-in-unit-sphere", "shade: material record + directions", "shade: texture", "shade: store / rest", "shade: sphere uv", "(stamp calibration)",
-                                          "bvh: grid entry / next piece of the walk", "media: chords, draws, log"};
-        // every interval begins with the bookkeeping of the stamp that opened it: subtract the cost of one stamp (PH_CAL: back-to-back stamps) per stamp
-        const double per_stamp = h[2 * PH_SLOTS + PH_CAL] ? (double)h[PH_CAL] / (double)h[2 * PH_SLOTS + PH_CAL] : 0.0;
-        double tk[PH_N], lk[PH_N], tot = 0, totl = 0, raw = 0;
-        for (int k = 0; k < PH_N; ++k) {
-            raw += (double)h[k];
-            const double t = (double)h[k], c = std::min(t, per_stamp * (double)h[2 * PH_SLOTS + k]);
-            tk[k] = k == PH_CAL ? 0.0 : t - c;
-            lk[k] = t > 0 ? (double)h[PH_SLOTS + k] * (tk[k] / t) : 0.0;
-            tot += tk[k]; totl += lk[k];
-        }
-        fprintf(stderr, "[phases] one stamp = %.0f ticks; stamps took %.1f %% of the %.4g wave-ticks of this (diagnostic) launch and are subtracted below\n", per_stamp, 100 * (raw - tot) / raw, raw);
-        fprintf(stderr, "[phases] %-36s %8s %8s %10s %10s %12s\n", "phase", "ticks %", "lanes", "masked %", "useful %", "stamps");
-        for (int k = 0; k < PH_N; ++k) {
-            if (!h[k] || k == PH_CAL) continue;
-            const double t = tk[k], l = lk[k];
-            fprintf(stderr, "[phases] %-36s %8.2f %8.1f %10.2f %10.2f %12llu\n", names[k], 100 * t / tot, t > 0 ? l / t : 0.0, 100 * (64 * t - l) / (64 * tot), 100 * l / (64 * tot), h[2 * PH_SLOTS + k]);
-        }
-        fprintf(stderr, "[phases] %-36s %8.2f %8.1f %10.2f %10.2f   (%.4g wave-ticks)\n", "total", 100.0, totl / tot, 100 * (64 * tot - totl) / (64 * tot), 100 * totl / (64 * tot), tot);
-    }
+    rc = report_phase_stamps(c, st);
 #endif
-    return RTMI_OK;
-}
-
-// ---- RTMI_ACCEL_BVH host build ----------------------------------------------------------------------------------------
-// Binned-SAH binary BVH over the primitives' boxes, one primitive per leaf, each node carrying its two children's boxes
-// (one 64-byte fetch per step).  Boxes are FLOAT, rounded outward and inflated by 2^-21 * obound (see slab_hit): the
-// traversal is only a conservative filter in front of the exact FP64 sphere test, so the tree's shape affects speed, never
-// results.  Primitives whose radius is a large fraction of the scene (sky dome, ground) are kept out of the tree.
-struct BvhBox { double lo[3], hi[3]; };
-struct BvhItem { BvhBox b; double cen[3]; int idx; };
-
-inline void box_grow(BvhBox &a, const BvhBox &b) { for (int k = 0; k < 3; ++k) { a.lo[k] = std::min(a.lo[k], b.lo[k]); a.hi[k] = std::max(a.hi[k], b.hi[k]); } }
-inline BvhBox box_empty() { BvhBox b; for (int k = 0; k < 3; ++k) { b.lo[k] = 1e300; b.hi[k] = -1e300; } return b; }
-inline double box_area(const BvhBox &b) { const double x = b.hi[0] - b.lo[0], y = b.hi[1] - b.lo[1], z = b.hi[2] - b.lo[2]; return x < 0 ? 0.0 : 2.0 * (x * y + y * z + z * x); }
-inline float f_down(double x) { float f = (float)x; if ((double)f > x) f = std::nextafterf(f, -INFINITY); return f; }
-inline float f_up(double x) { float f = (float)x; if ((double)f < x) f = std::nextafterf(f, INFINITY); return f; }
-
-#include <unistd.h> // getpid (the team below must not be used by a forked child)
-// Host-side scene preparation (the device's trees) runs on a small TEAM of threads created once per process and kept: on the GPU boxes of this pool creating a
-// thread costs ~0.3 ms, a team of 16 per call cost more than the 11 025 rectangle trees it built.  run(fn): the caller and every worker execute fn() once.
-static std::atomic<int> g_build_single{0}; // test hook (rtmi_test_build_tree): build on the calling thread only
-inline unsigned team_size() {
-    unsigned n = std::max(1u, std::min(8u, std::thread::hardware_concurrency()));
-    if (const char *e = std::getenv("RTMI_BUILD_THREADS")) n = (unsigned)std::max(1, std::min(64, std::atoi(e)));
-    return n;
-}
-inline unsigned build_threads() { return g_build_single.load() ? 1u : team_size(); }
-class WorkTeam {
-    std::vector<std::thread> th;
-    std::mutex mu, use_mu;
-    std::condition_variable cv, done_cv;
-    const std::function<void()> *fn = nullptr;
-    unsigned long gen = 0;
-    unsigned pending = 0;
-    bool stop = false;
-    pid_t owner;
-    void loop() {
-        unsigned long seen = 0;
-        for (;;) {
-            const std::function<void()> *f;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || gen != seen; });
-                if (stop) return;
-                seen = gen; f = fn;
-            }
-            (*f)();
-            { std::lock_guard<std::mutex> lk(mu); if (--pending == 0) done_cv.notify_all(); }
-        }
-    }
-public:
-    explicit WorkTeam(unsigned n) : owner(getpid()) { for (unsigned t = 1; t < n; ++t) th.emplace_back([this] { loop(); }); }
-    ~WorkTeam() { { std::lock_guard<std::mutex> lk(mu); stop = true; } cv.notify_all(); for (std::thread &t : th) t.join(); }
-    // one team per process, never destroyed (its threads wait on the condition variable until the process exits: no join in a static destructor, which a host
-    // that unloads libraries in its own order -- a JVM, an interpreter -- could run while they still wait); a forked child has the object but not the threads
-    static WorkTeam &get() { static WorkTeam *team = new WorkTeam(team_size()); return *team; }
-    void run(const std::function<void()> &f) {
-        std::unique_lock<std::mutex> use(use_mu, std::try_to_lock);
-        if (!use.owns_lock() || th.empty() || g_build_single.load() || getpid() != owner) { f(); return; } // the team is busy with another host thread's scene: this one builds alone
-        { std::lock_guard<std::mutex> lk(mu); fn = &f; pending = (unsigned)th.size(); ++gen; }
-        cv.notify_all();
-        f();
-        std::unique_lock<std::mutex> lk(mu);
-        done_cv.wait(lk, [&] { return pending == 0; });
-    }
-};
-// fn(begin, end) over [0, n) in blocks taken from a shared counter; `first` (optional) is one more job some thread of the team takes before the blocks
-template <typename F> void parallel_blocks(size_t n, size_t block, F fn, const std::function<void()> *first = nullptr) {
-    std::atomic<size_t> next{0};
-    std::atomic<bool> first_taken{first == nullptr};
-    const std::function<void()> worker = [&]() {
-        if (!first_taken.exchange(true)) (*first)();
-        for (size_t b = next.fetch_add(block); b < n; b = next.fetch_add(block)) fn(b, std::min(n, b + block));
-    };
-    if (n < 4 * block && !first) { worker(); return; }
-    WorkTeam::get().run(worker);
-}
-inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-struct BvhBuilder {
-    std::vector<BvhItem> items;
-    std::vector<float> nodes; // 16 floats per node
-    std::vector<char> moving; // by original primitive index
-    std::vector<char> box6;   // by original primitive index: the first of six rectangles that form a Box (one leaf: RTMI_LEAF_BOX)
-    double delta = 0.0;
-    const BvhBuilder *flags = nullptr; // a per-job builder (entry-grid rectangle trees) reads the flag vectors of the scene's builder instead of copying them
-    int leaf_code(int idx) const {
-        const BvhBuilder &f = flags ? *flags : *this;
-        return ~(idx | (f.moving[(size_t)idx] ? 0x40000000 : 0) | (!f.box6.empty() && f.box6[(size_t)idx] ? RTMI_LEAF_BOX : 0));
-    }
-    int sah_depth = 8, max_depth = 0;
-    double min_frac = 0.0;    // experiments: RTMI_BVH_MIN_FRAC = smallest share of a node's primitives a child may get (balance)
-    int sweep_max = 0;  // subtrees up to this many primitives: exact sweep SAH; above: 32 bins (build time)
-    int sah_levels = 1 << 20; // experiments: RTMI_BVH_SAH_LEVELS = number of top levels split by SAH (median below)
-    BvhBox bounds(int b, int e) const { BvhBox r = box_empty(); for (int i = b; i < e; ++i) box_grow(r, items[(size_t)i].b); return r; }
-    // node record (16 floats): l.lo.xy l.hi.xy | r.lo.xy r.hi.xy | l.lo.z l.hi.z r.lo.z r.hi.z | left, right, 0, 0
-    void put_box(int node, int side, const BvhBox &b) {
-        float *q = &nodes[(size_t)node * 16];
-        for (int k = 0; k < 2; ++k) { q[side * 4 + k] = f_down(b.lo[k] - delta); q[side * 4 + 2 + k] = f_up(b.hi[k] + delta); }
-        q[8 + side * 2] = f_down(b.lo[2] - delta); q[8 + side * 2 + 1] = f_up(b.hi[2] + delta);
-    }
-    void put_empty_box(int node, int side) {
-        float *q = &nodes[(size_t)node * 16];
-        for (int k = 0; k < 2; ++k) { q[side * 4 + k] = INFINITY; q[side * 4 + 2 + k] = -INFINITY; }
-        q[8 + side * 2] = INFINITY; q[8 + side * 2 + 1] = -INFINITY;
-    }
-    int build(int b, int e, int depth) { // returns the child code of the subtree over items [b, e): byte offset of the node, or a leaf code
-        max_depth = std::max(max_depth, depth);
-        if (e - b == 1) return leaf_code(items[(size_t)b].idx);
-        const int node = (int)(nodes.size() / 16);
-        nodes.resize(nodes.size() + 16, 0.0f);
-        // split: binned SAH (32 bins) over all three axes, the cheapest split wins; median split on the longest axis as the fallback
-        // (also beyond sah_depth, to bound the stack)
-        double clo[3] = {1e300, 1e300, 1e300}, chi[3] = {-1e300, -1e300, -1e300};
-        for (int i = b; i < e; ++i) for (int k = 0; k < 3; ++k) { clo[k] = std::min(clo[k], items[(size_t)i].cen[k]); chi[k] = std::max(chi[k], items[(size_t)i].cen[k]); }
-        int axis = 0;
-        for (int k = 1; k < 3; ++k) if (chi[k] - clo[k] > chi[axis] - clo[axis]) axis = k;
-        int mid = (b + e) / 2;
-        bool done = false;
-        // SAH wherever the subtree can still be finished by median splits within the stack's depth: depth + ceil(log2(count)) + 1
-        // levels at most (a global cap on the SAH depth left the deep, crowded parts of large scenes to median splits)
-        int lgc = 1;
-        while ((1 << lgc) < e - b) ++lgc;
-        if (depth + lgc + 1 < sah_depth && e - b > 2 && depth < sah_levels && e - b <= sweep_max) {
-            // exact sweep SAH: for each axis sort by centroid, try every split position (suffix boxes, then one forward pass)
-            double best = 1e300; int best_pos = -1;
-            const int n = e - b;
-            std::vector<BvhItem> tmp((size_t)n), best_order;
-            std::vector<double> suffix((size_t)n + 1);
-            for (int ax = 0; ax < 3; ++ax) {
-                if (!(chi[ax] - clo[ax] > 0)) continue;
-                std::copy(items.begin() + b, items.begin() + e, tmp.begin());
-                std::sort(tmp.begin(), tmp.end(), [&](const BvhItem &x, const BvhItem &y) { return x.cen[ax] < y.cen[ax] || (x.cen[ax] == y.cen[ax] && x.idx < y.idx); });
-                BvhBox acc = box_empty();
-                for (int i = n - 1; i > 0; --i) { box_grow(acc, tmp[(size_t)i].b); suffix[(size_t)i] = box_area(acc); }
-                acc = box_empty();
-                bool improved = false;
-                for (int i = 0; i < n - 1; ++i) { // left = [0, i], right = [i+1, n)
-                    box_grow(acc, tmp[(size_t)i].b);
-                    const double cost = box_area(acc) * (i + 1) + suffix[(size_t)i + 1] * (n - 1 - i);
-                    if (std::min(i + 1, n - 1 - i) < min_frac * n) continue;
-                    if (cost < best) { best = cost; best_pos = i + 1; improved = true; }
-                }
-                if (improved) best_order = tmp;
-            }
-            if (best_pos > 0) {
-                std::copy(best_order.begin(), best_order.end(), items.begin() + b);
-                mid = b + best_pos;
-                done = true;
-            }
-        } else if (depth + lgc + 1 < sah_depth && e - b > 2 && depth < sah_levels) {
-            const int NB = 32;
-            double best = 1e300; int best_k = -1, best_axis = -1;
-            for (int ax = 0; ax < 3; ++ax) {
-                const double ext = chi[ax] - clo[ax];
-                if (!(ext > 0)) continue;
-                // Only OCCUPIED bins matter: between two occupied bins the two sides of a split -- boxes and counts -- do not change, so every split position of
-                // such a run costs the same and the strict `cost < best` keeps the run's first, which is the occupied bin itself.  Walking the occupied bins (at
-                // most e - b of them) instead of all 32 gives the same split for a fraction of the work on the small sets of the entry grid's rectangle trees
-                // (3 - 14 primitives each, 11 025 trees at C3).
-                BvhBox bb[NB]; int cnt[NB];
-                unsigned occ = 0;
-                for (int i = b; i < e; ++i) {
-                    const int q = std::min(NB - 1, std::max(0, (int)((items[(size_t)i].cen[ax] - clo[ax]) / ext * NB)));
-                    if (!((occ >> q) & 1u)) { bb[q] = box_empty(); cnt[q] = 0; occ |= 1u << q; }
-                    box_grow(bb[q], items[(size_t)i].b); cnt[q]++;
-                }
-                int list[NB], m = 0;
-                for (int q = 0; q < NB; ++q) if ((occ >> q) & 1u) list[m++] = q;
-                BvhBox right[NB]; int rc[NB]; // right[j] / rc[j]: the occupied bins list[j], list[j + 1], ...
-                BvhBox acc = box_empty(); int n = 0;
-                for (int j = m - 1; j > 0; --j) { box_grow(acc, bb[list[j]]); n += cnt[list[j]]; right[j] = acc; rc[j] = n; }
-                acc = box_empty(); n = 0;
-                for (int j = 0; j + 1 < m; ++j) { // split after bin k = list[j]
-                    box_grow(acc, bb[list[j]]); n += cnt[list[j]];
-                    if (std::min(n, rc[j + 1]) < min_frac * (e - b)) continue;
-                    const double cost = box_area(acc) * n + box_area(right[j + 1]) * rc[j + 1];
-                    if (cost < best) { best = cost; best_k = list[j]; best_axis = ax; }
-                }
-            }
-            if (best_k >= 0) {
-                const double ext = chi[best_axis] - clo[best_axis], lo = clo[best_axis];
-                auto it = std::partition(items.begin() + b, items.begin() + e, [&](const BvhItem &x) {
-                    return std::min(NB - 1, std::max(0, (int)((x.cen[best_axis] - lo) / ext * NB))) <= best_k; });
-                mid = (int)(it - items.begin());
-                done = mid > b && mid < e;
-            }
-        }
-        if (!done) {
-            mid = (b + e) / 2;
-            std::nth_element(items.begin() + b, items.begin() + mid, items.begin() + e,
-                             [&](const BvhItem &x, const BvhItem &y) { return x.cen[axis] < y.cen[axis] || (x.cen[axis] == y.cen[axis] && x.idx < y.idx); });
-        }
-        const BvhBox lb = bounds(b, mid), rb = bounds(mid, e);
-        const int l = build(b, mid, depth + 1);
-        const int r = build(mid, e, depth + 1);
-        put_box(node, 0, lb);
-        put_box(node, 1, rb);
-        std::memcpy(&nodes[(size_t)node * 16 + 12], &l, 4);
-        std::memcpy(&nodes[(size_t)node * 16 + 13], &r, 4);
-        return node * 64;
-    }
-};
-
-// World-space box of primitive i in double (with a little slack): the local box of the innermost record, then each
-// instance wrapper's outward map applied to its 8 corners, innermost wrapper first (RotateY: hitable.clj:441-443; Translate: 396).
-// MovingSpheres: the sweep over the shutter interval.  Returns false when the primitive cannot be bounded.
-bool prim_world_box(int kind, const double *g, const int32_t *xf_kind, const double *xf_param, int xf_first, int xf_count,
-                    double t_lo, double t_hi, BvhBox &out) {
-    BvhBox b;
-    if (kind <= RTMI_PRIM_MOVING) {
-        const double r = std::fabs(g[3]);
-        if (kind == RTMI_PRIM_MOVING) {
-            const double f0 = (t_lo - g[7]) / (g[8] - g[7]), f1 = (t_hi - g[7]) / (g[8] - g[7]);
-            if (!std::isfinite(f0) || !std::isfinite(f1)) return false;
-            for (int k = 0; k < 3; ++k) {
-                const double a0 = g[k] * (1.0 - f0) + g[4 + k] * f0, a1 = g[k] * (1.0 - f1) + g[4 + k] * f1;
-                b.lo[k] = std::min(a0, a1) - r; b.hi[k] = std::max(a0, a1) + r;
-            }
-        } else for (int k = 0; k < 3; ++k) { b.lo[k] = g[k] - r; b.hi[k] = g[k] + r; }
-    } else if (kind <= RTMI_PRIM_RECT_YZ) {
-        const int ax = kind == RTMI_PRIM_RECT_XY ? 2 : (kind == RTMI_PRIM_RECT_XZ ? 1 : 0);
-        const int ua = kind == RTMI_PRIM_RECT_YZ ? 1 : 0, va = kind == RTMI_PRIM_RECT_XY ? 1 : 2;
-        b.lo[ua] = std::min(g[0], g[2]); b.hi[ua] = std::max(g[0], g[2]);
-        b.lo[va] = std::min(g[1], g[3]); b.hi[va] = std::max(g[1], g[3]);
-        b.lo[ax] = g[4]; b.hi[ax] = g[4];
-    } else {
-        for (int k = 0; k < 3; ++k) { b.lo[k] = std::min(g[k], std::min(g[3 + k], g[6 + k])); b.hi[k] = std::max(g[k], std::max(g[3 + k], g[6 + k])); }
-    }
-    if ((kind == RTMI_PRIM_SPHERE || kind == RTMI_PRIM_UVSPHERE) && xf_count > 0) {
-        // A sphere under Translate / RotateY wrappers is a sphere of the same radius about the mapped centre: its world box is centre +- r, not the box of the
-        // eight rotated corners of its local box (a RotateY of 15 degrees grows that one by a fifth per side -- half again the area -- and make-final's
-        // thousand spheres sit behind one).  The wrappers' own rounding moves a hit point by ~1e-13 of a coordinate; the slack below and the tree's 2^-21 obound cover it.
-        double c[3] = {g[0], g[1], g[2]};
-        const double r = std::fabs(g[3]);
-        for (int q = xf_count - 1; q >= 0; --q) {
-            const double *p = xf_param + (size_t)(xf_first + q) * 3;
-            if (xf_kind[xf_first + q] == RTMI_XFORM_TRANSLATE) { c[0] += p[0]; c[1] += p[1]; c[2] += p[2]; }
-            else { const double sn = p[0], cs = p[1]; const double rx = cs * c[0] + sn * c[2], rz = -(sn * c[0]) + cs * c[2]; c[0] = rx; c[2] = rz; }
-        }
-        for (int k = 0; k < 3; ++k) { const double pad = 1e-9 * (std::fabs(c[k]) + r) + 1e-12; b.lo[k] = c[k] - r - pad; b.hi[k] = c[k] + r + pad; }
-    } else
-    for (int q = xf_count - 1; q >= 0; --q) {
-        const double *p = xf_param + (size_t)(xf_first + q) * 3;
-        BvhBox nb = box_empty();
-        for (int c = 0; c < 8; ++c) {
-            double x = (c & 1) ? b.hi[0] : b.lo[0], y = (c & 2) ? b.hi[1] : b.lo[1], z = (c & 4) ? b.hi[2] : b.lo[2];
-            if (xf_kind[xf_first + q] == RTMI_XFORM_TRANSLATE) { x += p[0]; y += p[1]; z += p[2]; }
-            else { const double sn = p[0], cs = p[1]; const double rx = cs * x + sn * z, rz = -(sn * x) + cs * z; x = rx; z = rz; }
-            const double pt[3] = {x, y, z};
-            for (int k = 0; k < 3; ++k) { nb.lo[k] = std::min(nb.lo[k], pt[k]); nb.hi[k] = std::max(nb.hi[k], pt[k]); }
-        }
-        b = nb;
-    }
-    for (int k = 0; k < 3; ++k) {
-        if (!std::isfinite(b.lo[k]) || !std::isfinite(b.hi[k]) || std::fabs(b.lo[k]) > 1e15 || std::fabs(b.hi[k]) > 1e15) return false;
-        const double slack = 1e-9 * (std::fabs(b.lo[k]) + std::fabs(b.hi[k])) + 1e-12;
-        b.lo[k] -= slack; b.hi[k] += slack;
-    }
-    out = b;
-    return true;
-}
-
-// the IEEE half at or beyond x in the given direction (up: >= x, else <= x); beyond the half range: +-inf.  Integer arithmetic on the float's bits (directed
-// rounding of the magnitude: toward zero by truncation, away from zero by truncation + 1 when inexact): a host without F16C converts _Float16 in software, and a
-// scene's tree has twelve planes per node (C3: 1.4 million conversions there and back).  rtmi_test_half_outward exposes it to the CPU test against numpy.
-static uint16_t half_outward(float x, bool up) {
-    uint32_t u;
-    std::memcpy(&u, &x, 4);
-    const uint32_t sign = u >> 31, a = u & 0x7fffffffu;
-    if (a > 0x7f800000u) return (uint16_t)(0x7e00u | (sign << 15)); // NaN
-    const bool away = up != (sign != 0); // the magnitude rounds away from zero
-    uint32_t m;
-    bool inexact;
-    if (a >= 0x47800000u) { m = a == 0x7f800000u ? 0x7c00u : 0x7bffu; inexact = a != 0x7f800000u; } // >= 2^16: the largest half (65504) toward zero, inf away
-    else if (a >= 0x38800000u) { m = (((a >> 23) - 112u) << 10) | ((a & 0x7fffffu) >> 13); inexact = (a & 0x1fffu) != 0; } // normal halves: 2^-14 <= |x| < 2^16
-    else { const float sc = std::fabs(x) * 16777216.0f; m = (uint32_t)sc; inexact = (float)m != sc; } // half subnormals: units of 2^-24 (the scaling is exact)
-    if (inexact && away) m += 1; // (carries into the exponent: 0x03ff + 1 = the smallest normal, 0x7bff + 1 = inf)
-    return (uint16_t)(m | (sign << 15));
-}
-// fills d.bvh_* ; returns the node array to upload.  wbox[i] / bounded[i]: prim_world_box of every primitive.
-// box_first[i] != 0: primitives i .. i + 5 are the six faces of one Box (detected at scene creation) -- one leaf, unless the box is too large for the tree
-std::vector<float> build_bvh(DevScene &d, int n_prims, const int *prim_kind, const std::vector<BvhBox> &wbox, const std::vector<char> &bounded, const double *cam,
-                             bool want_grid, std::vector<int> &grid_cells, const std::vector<char> &box_first, int *out_depth = nullptr, const std::vector<BvhBox> *media_boxes = nullptr) {
-    BvhBuilder B;
-    struct DepthOut { BvhBuilder &b; int *o; ~DepthOut() { if (o) *o = b.max_depth; } } depth_out{B, out_depth};
-    std::vector<BvhItem> all;
-    double obound = 0.0;
-    for (int k = 0; k < 3; ++k) obound = std::max(obound, std::fabs(cam[k]));
-    for (int i = 0; i < n_prims; ++i) {
-        if (prim_kind[i] == RTMI_PRIM_MEDIUM) continue; // media are not surfaces (ext_medium_test)
-        BvhItem it; it.idx = i;
-        if (bounded[(size_t)i]) {
-            it.b = wbox[(size_t)i];
-            for (int k = 0; k < 3; ++k) it.cen[k] = 0.5 * (it.b.lo[k] + it.b.hi[k]);
-        } else { for (int k = 0; k < 3; ++k) { it.b.lo[k] = -1e15; it.b.hi[k] = 1e15; it.cen[k] = 0; } } // unbounded: goes to the big list below
-        for (int k = 0; k < 3; ++k) obound = std::max(obound, std::max(std::fabs(it.b.lo[k]), std::fabs(it.b.hi[k])));
-        all.push_back(it);
-    }
-    obound = std::min(obound, 1e15) * 1.001 + 1e-30;
-    d.n_big = 0;
-    B.box6.assign((size_t)std::max(n_prims, 1), 0);
-    for (size_t a = 0; a < all.size(); ++a) {
-        BvhItem it = all[a];
-        if (!box_first.empty() && box_first[(size_t)it.idx] && a + 5 < all.size() && all[a + 5].idx == it.idx + 5) { // a Box: the union of its six faces, if that fits the tree
-            BvhBox u = it.b;
-            bool ok = bounded[(size_t)it.idx] != 0;
-            for (int k = 1; k < 6; ++k) { box_grow(u, all[a + (size_t)k].b); ok = ok && bounded[(size_t)it.idx + (size_t)k]; }
-            const double uext = std::max(u.hi[0] - u.lo[0], std::max(u.hi[1] - u.lo[1], u.hi[2] - u.lo[2]));
-            if (ok && uext < 0.25 * obound) {
-                it.b = u;
-                for (int k = 0; k < 3; ++k) it.cen[k] = 0.5 * (u.lo[k] + u.hi[k]);
-                B.box6[(size_t)it.idx] = 1;
-                B.items.push_back(it);
-                a += 5;
-                continue;
-            }
-        }
-        const double ext = std::max(it.b.hi[0] - it.b.lo[0], std::max(it.b.hi[1] - it.b.lo[1], it.b.hi[2] - it.b.lo[2]));
-        if (ext >= 0.25 * obound && d.n_big < 16) d.big_idx[d.n_big++] = it.idx; // ascending index order
-        else B.items.push_back(it);
-    }
-    B.delta = obound * (1.0 / 2097152.0); // 2^-21 * obound
-    B.moving.assign((size_t)std::max(n_prims, 1), 0);
-    for (int i = 0; i < n_prims; ++i) B.moving[(size_t)i] = prim_kind[i] == RTMI_PRIM_MOVING;
-    d.bvh_obound = f_down(obound);
-    double cbound = 0.0;
-    for (const BvhItem &it : B.items) for (int k = 0; k < 3; ++k) cbound = std::max(cbound, std::max(std::fabs(it.b.lo[k]), std::fabs(it.b.hi[k])));
-    d.bvh_cbound = f_up(cbound);
-    std::vector<BvhItem> grid_items;
-    std::function<void()> whole_job; // the whole tree's build, when it is deferred to run beside the grid's jobs
-    if (B.items.empty()) d.bvh_root = RTMI_BVH_EMPTY;
-    else if (B.items.size() == 1) { // a lone primitive: a node whose right child is an empty box
-        B.nodes.assign(16, 0.0f);
-        B.put_box(0, 0, B.items[0].b);
-        B.put_empty_box(0, 1);
-        const int l = B.leaf_code(B.items[0].idx), r = l;
-        std::memcpy(&B.nodes[12], &l, 4); std::memcpy(&B.nodes[13], &r, 4);
-        d.bvh_root = 0;
-    } else {
-        int lg = 1;
-        while ((1u << lg) < B.items.size()) ++lg;
-        if (const char *e = std::getenv("RTMI_BVH_SAH_LEVELS")) B.sah_levels = std::atoi(e);
-        if (const char *e = std::getenv("RTMI_BVH_SWEEP_MAX")) B.sweep_max = std::atoi(e);
-        if (const char *e = std::getenv("RTMI_BVH_MIN_FRAC")) B.min_frac = std::atof(e);
-        B.sah_depth = RTMI_BVH_STACK - 2; // depth budget: a node at depth d over k primitives may use SAH while d + ceil(log2 k) + 1 < budget
-        (void)lg;
-        // The whole tree and the entry grid's rectangle trees are independent: when a grid will be tried, the whole tree is built on a thread of its own
-        // (into B.nodes, which the grid's jobs do not touch: they build into builders of their own and are appended after the join)
-        grid_items.assign(B.items.begin(), B.items.end()); // (build() reorders B.items: the grid works on a copy taken before)
-        auto build_whole = [&B, &d]() {
-            const double tb0 = now_ms();
-            d.bvh_root = B.build(0, (int)B.items.size(), 0);
-            if (std::getenv("RTMI_DEBUG")) fprintf(stderr, "[rtmi] build: whole tree over %zu primitives %.2f ms\n", B.items.size(), now_ms() - tb0);
-        };
-        if (want_grid && B.items.size() >= 256 && build_threads() > 1) whole_job = build_whole; // deferred: the team's first job, beside the grid's rectangle trees
-        else build_whole();
-    }
-    auto join_whole = [&]() {
-        if (whole_job) { whole_job(); whole_job = nullptr; } // (no grid was built after all: build it here)
-        if (d.bvh_root >= 0 && (B.max_depth >= RTMI_BVH_STACK - 1 || B.nodes.size() / 16 >= (1u << 25))) { // cannot happen by construction / node byte offsets are 31-bit
-            d.bvh_root = RTMI_BVH_EMPTY; d.n_big = 0; d.bvh_obound = -1.0f; // obound < 0: every ray takes the exact flat scan
-            B.nodes.clear();
-        }
-    };
-    // ---- entry grid: a BVH per x-z cell over the primitives whose boxes overlap the cell (DevScene::grid_*) -------------------------------------
-    d.grid_n = 0; d.grid_tall = RTMI_BVH_EMPTY; d.grid_kmax = 4; d.grid_walk = 0;
-    grid_cells.clear();
-    const char *grid_env = std::getenv("RTMI_GRID"); // "0": off; "n": n x n cells (experiments)
-    const double tg0 = now_ms();
-    struct GridTimer { double t0; ~GridTimer() { if (std::getenv("RTMI_DEBUG")) fprintf(stderr, "[rtmi] build: entry grid + node formats %.2f ms\n", now_ms() - t0); } } grid_timer{tg0};
-    if (want_grid && !(grid_env && grid_env[0] == '0') && grid_items.size() >= 256) { // (the whole tree may still be in the making: nothing below touches B.nodes / B.items before join_whole())
-        const size_t n_items = grid_items.size();
-        const std::vector<BvhItem> &world = grid_items; // (any order will do)
-        // the layer: every primitive except the few much taller than the typical one (the cover scene's three big spheres among 10 000 small ones)
-        std::vector<double> hts(n_items);
-        for (size_t i = 0; i < n_items; ++i) hts[i] = world[i].b.hi[1] - world[i].b.lo[1];
-        std::vector<double> sorted_h(hts);
-        std::nth_element(sorted_h.begin(), sorted_h.begin() + (long)(n_items / 2), sorted_h.end());
-        const double tall_h = 3.0 * sorted_h[n_items / 2] + 1e-300;
-        std::vector<BvhItem> layer, tall;
-        for (size_t i = 0; i < n_items; ++i) (hts[i] > tall_h ? tall : layer).push_back(world[i]);
-        BvhBox lb = box_empty();
-        for (const BvhItem &it : layer) box_grow(lb, it.b);
-        const double ex = lb.hi[0] - lb.lo[0], ez = lb.hi[2] - lb.lo[2], ey = lb.hi[1] - lb.lo[1];
-        // ~3.5 primitives per cell (C3: 53 x 53 cells, C2: 12 x 12).  Before long segments were walked in pieces (RTMI_GRID_CHUNK) ~10 per cell was best (C3, 16 .. 48
-        // cells per side: 84.1 / 82.3 / 83.3 ms: a finer grid sent more rays to the root of the whole tree); with the walk 32 / 40 / 48 / 56 / 64 / 72 cells: 77.2 / 76.2 /
-        // 76.4 / 76.1 / 76.7 / 78.5 ms, C2 7 / 10 / 14 / 20 cells: 3.39 / 3.37 / 3.33 / 3.49 ms
-        // ... and cells no smaller than ~4.5 x the layer's height: a ray crosses the layer over a horizontal distance of height / tan(elevation), so a
-        // taller layer (the moving cover scene: its spheres sweep up to 0.5 upwards, the layer is 0.9 instead of 0.4 high) at the same cell size means more
-        // cells per segment, i.e. more pieces (C2 moving, 6 / 8 / 10 / 12 / 16 cells per side: 3.55 / 3.60 / 3.68 / 3.75 / 4.01 ms; for the static scenes both
-        // rules give the same cell)
-        int G = (int)std::lround(std::min(std::sqrt((double)layer.size() / 3.5), std::min(ex, ez) / (4.5 * std::max(ey, 1e-300))));
-        if (grid_env && std::atoi(grid_env) > 1) G = std::atoi(grid_env);
-        G = std::max(2, std::min(G, 256)); // (90 000 spheres: 160 x 160 cells)
-        // worth it for a flat, wide layer of many primitives with few tall outliers
-        if (layer.size() >= 256 && tall.size() * 20 <= n_items && ex > 0 && ez > 0 && ey < 0.25 * std::min(ex, ez)) {
-            const double eps = 4.0 * B.delta; // cells claim the primitives whose (already inflated) boxes come this close; the device grows a ray's cell rectangle by its own position error
-            const double csx = ex / G, csz = ez / G;
-            std::vector<std::vector<int>> cell_items((size_t)G * G);
-            for (size_t i = 0; i < layer.size(); ++i) {
-                const BvhBox &b = layer[i].b;
-                const int i0 = std::max(0, std::min(G - 1, (int)std::floor((b.lo[0] - 2 * eps - lb.lo[0]) / csx))), i1 = std::max(0, std::min(G - 1, (int)std::floor((b.hi[0] + 2 * eps - lb.lo[0]) / csx)));
-                const int j0 = std::max(0, std::min(G - 1, (int)std::floor((b.lo[2] - 2 * eps - lb.lo[2]) / csz))), j1 = std::max(0, std::min(G - 1, (int)std::floor((b.hi[2] + 2 * eps - lb.lo[2]) / csz)));
-                for (int j = j0; j <= j1; ++j) for (int ii = i0; ii <= i1; ++ii) cell_items[(size_t)j * G + ii].push_back((int)i);
-            }
-            size_t claimed = 0;
-            for (const std::vector<int> &ci : cell_items) claimed += ci.size();
-            if (claimed > 4 * layer.size()) cell_items.clear(); // primitives that each span many cells (long sweeps, slabs): the per-cell trees would multiply them -- no grid
-            const int depth0 = 3; // stack entries a grid start may already hold: the rectangle's tree under the tall tree (+ margin)
-            auto subtree = [&](const std::vector<BvhItem> &its) -> int { // child code of a tree over `its`, appended to B.nodes
-                if (its.empty()) return RTMI_BVH_EMPTY;
-                const int b0 = (int)B.items.size();
-                B.items.insert(B.items.end(), its.begin(), its.end());
-                if (its.size() == 1) { // a lone primitive: a node whose right child is an empty box (a bare leaf code would skip the box test)
-                    const int node = (int)(B.nodes.size() / 16);
-                    B.nodes.resize(B.nodes.size() + 16, 0.0f);
-                    B.put_box(node, 0, its[0].b);
-                    B.put_empty_box(node, 1);
-                    const int l = B.leaf_code(its[0].idx);
-                    std::memcpy(&B.nodes[(size_t)node * 16 + 12], &l, 4); std::memcpy(&B.nodes[(size_t)node * 16 + 13], &l, 4);
-                    return node * 64;
-                }
-                return B.build(b0, b0 + (int)its.size(), depth0);
-            };
-            // One tree per RECTANGLE of cells a segment can touch -- 1 x 1, 2 x 1, 1 x 2, 2 x 2 (four families, each indexed by the rectangle's low corner:
-            // grid_cells[(wi + 2 wj) G G + j0 G + i0]) -- over the union of the cells' primitives: a segment starts at ONE root (no root per cell to push and
-            // to visit), and a primitive two cells of the rectangle share is in the tree once (it used to be tested exactly once per cell).
-            if (!cell_items.empty()) grid_cells.assign((size_t)4 * G * G, RTMI_BVH_EMPTY);
-            // The 4 G^2 rectangle trees (C3: 11 025 of them) are independent: every job builds its tree in a builder of its own, worker threads take jobs from a
-            // shared counter, and the results are appended to the node array IN JOB ORDER with their node offsets rebased -- the same array whatever the thread
-            // count (scene creation at C3: 59 ms single-threaded, most of it here).
-            if (!cell_items.empty()) {
-                struct RectTree { std::vector<float> nodes; int root = RTMI_BVH_EMPTY; int depth = 0; };
-                const size_t n_jobs = (size_t)4 * G * G;
-                std::vector<RectTree> trees(n_jobs);
-                auto job = [&](size_t jb) {
-                    const int fam = (int)(jb / ((size_t)G * G)), j = (int)((jb / (size_t)G) % (size_t)G), i = (int)(jb % (size_t)G);
-                    const int wi = fam & 1, wj = fam >> 1;
-                    if (j + wj >= G || i + wi >= G) return;
-                    std::vector<int> uni;
-                    for (int dj = 0; dj <= wj; ++dj) for (int di = 0; di <= wi; ++di) { const std::vector<int> &ci = cell_items[(size_t)(j + dj) * G + i + di]; uni.insert(uni.end(), ci.begin(), ci.end()); }
-                    std::sort(uni.begin(), uni.end());
-                    uni.erase(std::unique(uni.begin(), uni.end()), uni.end());
-                    if (uni.empty()) return;
-                    BvhBuilder L;
-                    L.flags = &B; L.delta = B.delta; L.sah_depth = B.sah_depth; L.min_frac = B.min_frac; L.sweep_max = B.sweep_max; L.sah_levels = B.sah_levels;
-                    for (int k : uni) L.items.push_back(layer[(size_t)k]);
-                    RectTree &T = trees[jb];
-                    if (L.items.size() == 1) { // a lone primitive: a node whose right child is an empty box (a bare leaf code would skip the box test)
-                        L.nodes.assign(16, 0.0f);
-                        L.put_box(0, 0, L.items[0].b);
-                        L.put_empty_box(0, 1);
-                        const int l = L.leaf_code(L.items[0].idx);
-                        std::memcpy(&L.nodes[12], &l, 4); std::memcpy(&L.nodes[13], &l, 4);
-                        T.root = 0; T.depth = depth0 + 1;
-                    } else { T.root = L.build(0, (int)L.items.size(), depth0); T.depth = L.max_depth; }
-                    T.nodes.swap(L.nodes);
-                };
-                const double tr0 = now_ms();
-                { // the whole tree (if deferred) is one more job of the same team
-                    const std::function<void()> first = whole_job;
-                    whole_job = nullptr;
-                    parallel_blocks(n_jobs, 16, [&](size_t b, size_t e) { for (size_t q = b; q < e; ++q) job(q); }, first ? &first : nullptr);
-                }
-                if (std::getenv("RTMI_DEBUG")) fprintf(stderr, "[rtmi] build: %zu rectangle trees on %u threads %.2f ms\n", n_jobs, build_threads(), now_ms() - tr0);
-                join_whole();
-                // append in job order, node offsets rebased: every job's place in the array is the sum of the sizes before it, so the copies run on the team too
-                std::vector<size_t> at(n_jobs + 1, B.nodes.size());
-                for (size_t jb = 0; jb < n_jobs; ++jb) { at[jb + 1] = at[jb] + trees[jb].nodes.size(); B.max_depth = std::max(B.max_depth, trees[jb].depth); }
-                B.nodes.resize(at[n_jobs]);
-                parallel_blocks(n_jobs, 64, [&](size_t b, size_t e) {
-                    for (size_t jb = b; jb < e; ++jb) {
-                        RectTree &T = trees[jb];
-                        if (T.root == RTMI_BVH_EMPTY) continue;
-                        const int base = (int)(at[jb] / 16) * 64;
-                        float *dst = &B.nodes[at[jb]];
-                        std::memcpy(dst, T.nodes.data(), T.nodes.size() * sizeof(float));
-                        for (size_t nd = 0; nd < T.nodes.size() / 16; ++nd) {
-                            int c[2];
-                            std::memcpy(c, dst + nd * 16 + 12, 8);
-                            for (int k = 0; k < 2; ++k) if (c[k] >= 0) c[k] += base; // inner node: byte offset of its record (leaf codes and RTMI_BVH_EMPTY are negative)
-                            std::memcpy(dst + nd * 16 + 12, c, 8);
-                        }
-                        grid_cells[jb] = T.root + base;
-                    }
-                });
-            }
-            join_whole();
-            if (d.bvh_root < 0) cell_items.clear(); // (the whole tree did not fit the stack: every ray takes the flat scan, no grid either)
-            if (!cell_items.empty()) d.grid_tall = subtree(tall);
-            if (cell_items.empty() || B.max_depth >= RTMI_BVH_STACK - 1 || B.nodes.size() / 16 >= (1u << 25)) { // too deep for the stack: no grid (the whole tree above stays valid)
-                grid_cells.clear(); d.grid_tall = RTMI_BVH_EMPTY;
-            } else {
-                d.grid_n = G;
-                if (const char *e = std::getenv("RTMI_GRID_KMAX")) d.grid_kmax = std::max(1, std::min(4, std::atoi(e)));
-                d.grid_walk = d.grid_kmax >= 4;
-                if (const char *e = std::getenv("RTMI_GRID_WALK")) d.grid_walk = d.grid_walk && e[0] != '0'; // (tests: the same grid without the piecewise walk)
-                d.grid_lo_x = (float)lb.lo[0]; d.grid_lo_z = (float)lb.lo[2];
-                d.grid_inv_x = (float)(1.0 / csx); d.grid_inv_z = (float)(1.0 / csz);
-                for (int k = 0; k < 3; ++k) { d.grid_box[k] = f_down(lb.lo[k] - B.delta - eps); d.grid_box[3 + k] = f_up(lb.hi[k] + B.delta + eps); }
-                d.grid_eps = 0.0f;
-                BvhBox tb = box_empty();
-                for (const BvhItem &it : tall) box_grow(tb, it.b);
-                for (int k = 0; k < 3; ++k) { d.grid_tall_box[k] = tall.empty() ? 0.0f : f_down(tb.lo[k] - B.delta - eps); d.grid_tall_box[3 + k] = tall.empty() ? 0.0f : f_up(tb.hi[k] + B.delta + eps); }
-                for (int k = 0; k < 3; ++k) { // what the device tests: {lo, hi} half pairs, rounded outward once more
-                    d.grid_box_h[k] = (unsigned)half_outward(d.grid_box[k], false) | ((unsigned)half_outward(d.grid_box[3 + k], true) << 16);
-                    d.grid_tall_box_h[k] = (unsigned)half_outward(d.grid_tall_box[k], false) | ((unsigned)half_outward(d.grid_tall_box[3 + k], true) << 16);
-                }
-            }
-        }
-    }
-    join_whole();
-    // ---- neighbourhood trees of the media (DevScene::mloc_*) ------------------------------------------------------------------------------------------------
-    d.n_mloc = 0;
-    // (measured on make-final: node visits per segment 10.2 -> 8.3, frame 17.43 vs 17.46 ms -- the segments it shortens finish early and wait for their wave's
-    // long ones; off unless RTMI_MLOC=1)
-    const char *mloc_env = std::getenv("RTMI_MLOC");
-    if (media_boxes && d.bvh_root >= 0 && mloc_env && mloc_env[0] == '1') {
-        const size_t n_tree = B.items.size(); // (the grid is never built for a scene with media: the items are the whole tree's)
-        std::vector<BvhItem> world(B.items.begin(), B.items.end());
-        for (const BvhBox &mb : *media_boxes) {
-            if (d.n_mloc >= 4) break;
-            BvhBox R = mb; // the boundary's box, a hundredth larger per side
-            for (int k = 0; k < 3; ++k) { const double pad = 0.01 * (mb.hi[k] - mb.lo[k]) + 4.0 * B.delta; R.lo[k] -= pad; R.hi[k] += pad; }
-            std::vector<BvhItem> its;
-            for (const BvhItem &it : world) { // every primitive with a surface point inside R: its box (the tree inflates it by delta once more) reaches into R
-                bool hit = true;
-                for (int k = 0; k < 3; ++k) hit = hit && it.b.hi[k] + 2.0 * B.delta >= R.lo[k] && it.b.lo[k] - 2.0 * B.delta <= R.hi[k];
-                if (hit) its.push_back(it);
-            }
-            if (its.size() * 2 > n_tree) continue; // a medium that holds most of the scene (make-final's haze): nothing to gain
-            int root = RTMI_BVH_EMPTY;
-            if (its.size() == 1) { // a lone primitive: a node whose right child is an empty box
-                const int node = (int)(B.nodes.size() / 16);
-                B.nodes.resize(B.nodes.size() + 16, 0.0f);
-                B.put_box(node, 0, its[0].b);
-                B.put_empty_box(node, 1);
-                const int l = B.leaf_code(its[0].idx);
-                std::memcpy(&B.nodes[(size_t)node * 16 + 12], &l, 4); std::memcpy(&B.nodes[(size_t)node * 16 + 13], &l, 4);
-                root = node * 64;
-            } else if (!its.empty()) {
-                const int b0 = (int)B.items.size();
-                B.items.insert(B.items.end(), its.begin(), its.end());
-                root = B.build(b0, b0 + (int)its.size(), 1);
-            }
-            if (B.max_depth >= RTMI_BVH_STACK - 1 || B.nodes.size() / 16 >= (1u << 25)) break; // (cannot happen: a subset of a tree that fitted)
-            d.mloc_root[d.n_mloc] = root;
-            for (int k = 0; k < 3; ++k) { d.mloc_box[d.n_mloc][k] = f_up(R.lo[k]); d.mloc_box[d.n_mloc][3 + k] = f_down(R.hi[k]); }
-            d.n_mloc++;
-        }
-    }
-    d.bvh_node16 = 0;
-    if (d.bvh_root != RTMI_BVH_EMPTY) { // 32-byte records (Node16) when rounding the planes to half costs little: 12 halves + 2 child codes
-        auto half_bits = [](float x, bool up) { return half_outward(x, up); };
-        auto half_val = [](uint16_t b) { // the half's value (integer decode: no software _Float16 conversion)
-            const int e = (b >> 10) & 31, m = b & 1023;
-            const double v = e == 0 ? std::ldexp((double)m, -24) : (e == 31 ? (m ? (double)NAN : (double)INFINITY) : std::ldexp((double)(1024 + m), e - 25));
-            return (b >> 15) ? -v : v;
-        };
-        std::vector<float> out(B.nodes.size() / 2, 0.0f);
-        double area32 = 0.0, area16 = 0.0;
-        const size_t n_nodes = B.nodes.size() / 16;
-        std::vector<double> part32((n_nodes + 2047) / 2048 + 1, 0.0), part16(part32.size(), 0.0); // per block, summed in block order: the same sums whatever the thread count
-        parallel_blocks(n_nodes, 2048, [&](size_t nb, size_t ne) {
-            double a32 = 0.0, a16 = 0.0;
-            for (size_t n = nb; n < ne; ++n) {
-                const float *q = &B.nodes[n * 16];
-                uint16_t h[12];
-                for (int side = 0; side < 2; ++side) {
-                    const float lo[3] = {q[side * 4], q[side * 4 + 1], q[8 + side * 2]}, hi[3] = {q[side * 4 + 2], q[side * 4 + 3], q[8 + side * 2 + 1]};
-                    double e32[3], e16[3];
-                    for (int k = 0; k < 3; ++k) {
-                        h[side * 6 + k * 2] = half_bits(lo[k], false); h[side * 6 + k * 2 + 1] = half_bits(hi[k], true);
-                        e32[k] = (double)hi[k] - lo[k]; e16[k] = half_val(h[side * 6 + k * 2 + 1]) - half_val(h[side * 6 + k * 2]);
-                    }
-                    if (e32[0] >= 0 && std::isfinite(e32[0] + e32[1] + e32[2])) { // (the lone primitive's empty sibling is +inf / -inf)
-                        a32 += e32[0] * e32[1] + e32[1] * e32[2] + e32[2] * e32[0];
-                        a16 += std::isfinite(e16[0] + e16[1] + e16[2]) ? e16[0] * e16[1] + e16[1] * e16[2] + e16[2] * e16[0] : INFINITY;
-                    }
-                }
-                int c[2];
-                std::memcpy(c, &q[12], 8);
-                for (int k = 0; k < 2; ++k) if (c[k] >= 0 && c[k] != RTMI_BVH_EMPTY) c[k] /= 2; // byte offsets of 32-byte records
-                std::memcpy(reinterpret_cast<char *>(&out[n * 8]), h, 24);
-                std::memcpy(reinterpret_cast<char *>(&out[n * 8]) + 24, c, 8);
-            }
-            part32[nb / 2048] = a32; part16[nb / 2048] = a16;
-        });
-        for (size_t k = 0; k < part32.size(); ++k) { area32 += part32[k]; area16 += part16[k]; }
-        const char *force = std::getenv("RTMI_NODE16"); // "0" / "1": override the choice (tests)
-        const bool use16 = force ? force[0] == '1' : (area16 <= 1.25 * area32);
-        if (use16) {
-            d.bvh_node16 = 1;
-            d.bvh_root = d.bvh_root >= 0 ? d.bvh_root / 2 : d.bvh_root;
-            for (int &c : grid_cells) if (c >= 0) c /= 2;
-            for (int k = 0; k < d.n_mloc; ++k) if (d.mloc_root[k] >= 0) d.mloc_root[k] /= 2;
-            if (d.grid_tall >= 0) d.grid_tall /= 2;
-            return out;
-        }
-    }
-    return B.nodes;
+    return rc;
 }
 
 int check_render_args(rtmi_scene *s, int nx, int ny, int ns, int depth, int precision) {
@@ -1770,6 +1191,7 @@ int check_render_args(rtmi_scene *s, int nx, int ny, int ns, int depth, int prec
 // calling thread alone.  out_hash = FNV-1a of the node array and the grid's root codes, out_info = {node records, depth, grid cells per side, big primitives}
 RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double *cam, int32_t threads, uint64_t *out_hash, int32_t *out_info, double *out_ms) {
     if (n <= 0 || !geom || !cam || !out_hash || !out_info || !out_ms) return fail(RTMI_E_ARG, "bad arguments");
+    const BuildKnobs knobs = read_build_knobs();
     std::vector<int> kind((size_t)n, RTMI_PRIM_SPHERE);
     std::vector<BvhBox> wbox((size_t)n);
     std::vector<char> bounded((size_t)n, 0), box_first((size_t)n, 0);
@@ -1782,7 +1204,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
     int depth = 0;
     g_build_single.store(threads == 1 ? 1 : 0);
     const double t0 = now_ms();
-    const std::vector<float> nodes = build_bvh(d, n, kind.data(), wbox, bounded, cam, true, grid_cells, box_first, &depth);
+    const std::vector<float> nodes = build_bvh(d, n, kind.data(), wbox, bounded, cam, true, grid_cells, box_first, knobs, &depth);
     *out_ms = now_ms() - t0;
     g_build_single.store(0);
     uint64_t h = 1469598103934665603ull;
@@ -1895,24 +1317,22 @@ static void fill_media_fast(rtmi_scene *s) {
         for (int j = 0; j < 5; ++j) q[1 + j] = it->second[(size_t)j];
     }
 }
-RTMI_EXPORT int rtmi_scene_create_ex(rtmi_ctx *c, int32_t n_prims, const int32_t *prim_kind, const double *prim_geom, const int32_t *prim_mat,
-                                     int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
-                                     int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
-                                     int32_t cam_kind, const double *cam, const int32_t *prim_flip, const int32_t *prim_xform,
-                                     int32_t n_xforms, const int32_t *xform_kind, const double *xform_param, rtmi_scene **out_scene) {
-    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
-    const double t_create0 = now_ms();
-    if (n_xforms < 0 || (n_xforms > 0 && (!xform_kind || !xform_param || !prim_xform))) return fail(RTMI_E_ARG, "xform arrays are NULL");
+namespace {
+// the checks of rtmi_scene_create_ex, in the order they are reported
+int check_scene_args(const SceneArrays &a, rtmi_scene **out_scene) {
+    const int n_prims = a.n_prims, n_mats = a.n_mats, n_tex = a.n_tex, n_xforms = a.n_xforms;
+    const int32_t *prim_kind = a.prim_kind, *prim_mat = a.prim_mat, *mat_kind = a.mat_kind, *mat_tex = a.mat_tex, *tex_kind = a.tex_kind, *tex_child = a.tex_child;
+    if (n_xforms < 0 || (n_xforms > 0 && (!a.xform_kind || !a.xform_param || !a.prim_xform))) return fail(RTMI_E_ARG, "xform arrays are NULL");
     for (int k = 0; k < n_xforms; ++k)
-        if (xform_kind[k] != RTMI_XFORM_TRANSLATE && xform_kind[k] != RTMI_XFORM_ROTATE_Y) return fail(RTMI_E_UNSUPPORTED, "xform %d: kind %d unsupported on GPU path", k, xform_kind[k]);
+        if (a.xform_kind[k] != RTMI_XFORM_TRANSLATE && a.xform_kind[k] != RTMI_XFORM_ROTATE_Y) return fail(RTMI_E_UNSUPPORTED, "xform %d: kind %d unsupported on GPU path", k, a.xform_kind[k]);
     if (!out_scene) return fail(RTMI_E_ARG, "out_scene is NULL");
     *out_scene = nullptr;
     if (n_prims < 0 || n_mats < 0 || n_tex < 0) return fail(RTMI_E_ARG, "negative count");
-    if (n_prims > 0 && (!prim_kind || !prim_geom || !prim_mat)) return fail(RTMI_E_ARG, "primitive arrays are NULL");
-    if (n_mats > 0 && (!mat_kind || !mat_tex || !mat_param)) return fail(RTMI_E_ARG, "material arrays are NULL");
-    if (n_tex > 0 && (!tex_kind || !tex_param || !tex_child)) return fail(RTMI_E_ARG, "texture arrays are NULL");
-    if (!cam) return fail(RTMI_E_ARG, "cam is NULL");
-    if (cam_kind != RTMI_CAM_PINHOLE && cam_kind != RTMI_CAM_THINLENS) return fail(RTMI_E_UNSUPPORTED, "camera kind %d unsupported on GPU path", cam_kind);
+    if (n_prims > 0 && (!prim_kind || !a.prim_geom || !prim_mat)) return fail(RTMI_E_ARG, "primitive arrays are NULL");
+    if (n_mats > 0 && (!mat_kind || !mat_tex || !a.mat_param)) return fail(RTMI_E_ARG, "material arrays are NULL");
+    if (n_tex > 0 && (!tex_kind || !a.tex_param || !tex_child)) return fail(RTMI_E_ARG, "texture arrays are NULL");
+    if (!a.cam) return fail(RTMI_E_ARG, "cam is NULL");
+    if (a.cam_kind != RTMI_CAM_PINHOLE && a.cam_kind != RTMI_CAM_THINLENS) return fail(RTMI_E_UNSUPPORTED, "camera kind %d unsupported on GPU path", a.cam_kind);
     // validate: this is where "unknown record type -> explicit unsupported error" surfaces
     for (int t = 0; t < n_tex; ++t) {
         if (tex_kind[t] < RTMI_TEX_CONSTANT || tex_kind[t] > RTMI_TEX_IMAGE) return fail(RTMI_E_UNSUPPORTED, "texture %d: kind %d unsupported on GPU path", t, tex_kind[t]);
@@ -1930,21 +1350,12 @@ RTMI_EXPORT int rtmi_scene_create_ex(rtmi_ctx *c, int32_t n_prims, const int32_t
         if (mat_kind[m] < RTMI_MAT_LAMBERTIAN || mat_kind[m] > RTMI_MAT_ISOTROPIC) return fail(RTMI_E_UNSUPPORTED, "material %d: kind %d unsupported on GPU path", m, mat_kind[m]);
         if (mat_kind[m] != RTMI_MAT_DIELECTRIC && (mat_tex[m] < 0 || mat_tex[m] >= n_tex)) return fail(RTMI_E_ARG, "material %d: texture index %d invalid", m, mat_tex[m]);
     }
-    std::vector<double> stat_geom, mov_geom, stat4_d;
-    std::vector<float> stat4_f;
-    bool has_ext = false, uses_perlin = false;
-    int n_world = 0, n_media = 0, media[16];
-    int max_image = -1;
-    for (int t = 0; t < n_tex; ++t) {
-        if (tex_kind[t] > RTMI_TEX_CHECKER) has_ext = true; // section 8(f4) textures live in the EXT kernels only
-        if (tex_kind[t] >= RTMI_TEX_PERLIN_NOISE && tex_kind[t] <= RTMI_TEX_MARBLE) uses_perlin = true;
+    for (int t = 0; t < n_tex; ++t)
         if (tex_kind[t] == RTMI_TEX_IMAGE) {
-            const double im = tex_param[(size_t)t * RTMI_TEX_STRIDE];
+            const double im = a.tex_param[(size_t)t * RTMI_TEX_STRIDE];
             if (!(im >= 0 && im < 1e6 && im == std::floor(im))) return fail(RTMI_E_ARG, "texture %d: image index invalid", t);
-            max_image = std::max(max_image, (int)im);
         }
-    }
-    std::vector<int> stat_orig, mov_orig, pk((size_t)n_prims), pm((size_t)n_prims);
+    int n_world = 0, n_media = 0;
     for (int i = 0; i < n_prims; ++i) {
         const int kind = prim_kind[i] & ~RTMI_PRIM_BOUNDARY;
         const bool is_boundary = (prim_kind[i] & RTMI_PRIM_BOUNDARY) != 0;
@@ -1953,361 +1364,61 @@ RTMI_EXPORT int rtmi_scene_create_ex(rtmi_ctx *c, int32_t n_prims, const int32_t
         if (!is_boundary && n_world != i) return fail(RTMI_E_ARG, "primitive %d: boundary primitives must come after all world primitives", i);
         if (!is_boundary) n_world = i + 1;
         if (prim_mat[i] < 0 || prim_mat[i] >= n_mats) return fail(RTMI_E_ARG, "primitive %d: material index %d invalid", i, prim_mat[i]);
-        pk[(size_t)i] = kind; pm[(size_t)i] = prim_mat[i];
-        if (mat_kind[prim_mat[i]] == RTMI_MAT_ISOTROPIC) has_ext = true; // Isotropic.scatter (shader.clj:129-138) is compiled into the EXT kernels only
         if (kind == RTMI_PRIM_MEDIUM) {
-            const double *mg = prim_geom + (size_t)i * RTMI_PRIM_STRIDE;
+            const double *mg = a.prim_geom + (size_t)i * RTMI_PRIM_STRIDE;
             const int fb = (int)mg[1], nb = (int)mg[2];
             if (!(mg[0] == mg[0]) || fb < 0 || nb <= 0 || fb + nb > n_prims) return fail(RTMI_E_ARG, "medium %d: boundary range [%d, %d) invalid", i, fb, fb + nb);
             for (int q = fb; q < fb + nb; ++q) if (!(prim_kind[q] & RTMI_PRIM_BOUNDARY)) return fail(RTMI_E_ARG, "medium %d: primitive %d is not flagged RTMI_PRIM_BOUNDARY", i, q);
             if (mat_kind[prim_mat[i]] != RTMI_MAT_ISOTROPIC) return fail(RTMI_E_ARG, "medium %d: the phase function must be RTMI_MAT_ISOTROPIC", i);
-            if (n_media >= 16) return fail(RTMI_E_UNSUPPORTED, "more than 16 ConstantMedium records in one scene");
-            media[n_media++] = i;
-            has_ext = true;
+            if (n_media++ >= 16) return fail(RTMI_E_UNSUPPORTED, "more than 16 ConstantMedium records in one scene");
             continue;
         }
-        if (is_boundary) { has_ext = true; continue; }
-        const double *g = prim_geom + (size_t)i * RTMI_PRIM_STRIDE;
-        const int xf_first = prim_xform ? prim_xform[2 * i] : 0, xf_count = prim_xform ? prim_xform[2 * i + 1] : 0;
+        if (is_boundary) continue;
+        const int xf_first = a.prim_xform ? a.prim_xform[2 * i] : 0, xf_count = a.prim_xform ? a.prim_xform[2 * i + 1] : 0;
         if (xf_count < 0 || xf_first < 0 || xf_first + xf_count > n_xforms) return fail(RTMI_E_ARG, "primitive %d: xform range [%d, %d) invalid", i, xf_first, xf_first + xf_count);
-        if (kind > RTMI_PRIM_MOVING || xf_count > 0 || (prim_flip && prim_flip[i])) { has_ext = true; continue; }
-        if (kind == RTMI_PRIM_MOVING) {
-            mov_geom.insert(mov_geom.end(), g, g + RTMI_PRIM_STRIDE);
-            mov_orig.push_back(i);
-        } else {
-            stat_geom.insert(stat_geom.end(), g, g + 4);
-            stat_orig.push_back(i);
-            // {cx, cy, cz, r*r}: hitable.clj:188 (* radius radius), one IEEE multiply in the precision the kernel computes in
-            const volatile double r2d = g[3] * g[3];
-            const volatile float rf = (float)g[3];
-            const volatile float r2f = rf * rf;
-            stat4_d.insert(stat4_d.end(), {g[0], g[1], g[2], (double)r2d});
-            stat4_f.insert(stat4_f.end(), {(float)g[0], (float)g[1], (float)g[2], (float)r2f});
-        }
     }
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_scene_create_ex(rtmi_ctx *c, int32_t n_prims, const int32_t *prim_kind, const double *prim_geom, const int32_t *prim_mat,
+                                     int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
+                                     int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
+                                     int32_t cam_kind, const double *cam, const int32_t *prim_flip, const int32_t *prim_xform,
+                                     int32_t n_xforms, const int32_t *xform_kind, const double *xform_param, rtmi_scene **out_scene) {
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    const double t_create0 = now_ms();
+    const SceneArrays a{n_prims, prim_kind, prim_geom, prim_mat, n_mats, mat_kind, mat_tex, mat_param, n_tex, tex_kind, tex_param, tex_child,
+                        cam_kind, cam, prim_flip, prim_xform, n_xforms, xform_kind, xform_param};
+    int rc = check_scene_args(a, out_scene);
+    if (rc) return rc;
+    const BuildKnobs knobs = read_build_knobs();
     HIP_TRY(hipSetDevice(c->device));
     rtmi_scene *s = new (std::nothrow) rtmi_scene();
     if (!s) return fail(RTMI_E_NOMEM, "out of host memory");
+    const PackedScene P = pack_scene(a, knobs);
     s->ctx = c; s->n_prims = n_prims; s->n_mats = n_mats; s->n_tex = n_tex;
-    s->uses_perlin = uses_perlin; s->max_image = max_image;
+    s->uses_perlin = P.uses_perlin; s->max_image = P.max_image; s->bvh_node_count = P.bvh_node_count; s->bvh_depth = P.bvh_depth;
+    s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of; s->dev = P.d;
     DevScene &d = s->dev;
-    d.n_static = (int)stat_orig.size(); d.n_moving = (int)mov_orig.size(); d.n_tex = n_tex; d.cam_kind = cam_kind;
-    std::memcpy(d.cam, cam, 24 * sizeof(double));
-    { // get-ray's origin is cam origin + lens offset; with aperture 0 the offset is (+-0, +-0, +-0) (camera.clj:39-44: lens-radius * rand-in-unit-disk), and
-      // x + (+-0) = x bit for bit for every x except -0 (whose sum with +0 is +0): then, and for the pinhole camera, all rays share one origin
-        bool fixed = cam_kind == RTMI_CAM_PINHOLE || cam[21] == 0.0;
-        for (int k = 0; k < 3; ++k) fixed = fixed && !(cam[k] == 0.0 && std::signbit(cam[k])) && std::isfinite(cam[k]);
-        for (int k = 12; k < 18; ++k) fixed = fixed && std::isfinite(cam[k]);
-        d.cam_fixed_origin = fixed ? 1 : 0;
-    }
-    std::vector<int> mk(mat_kind, mat_kind + n_mats), mt(mat_tex, mat_tex + n_mats), tk(tex_kind, tex_kind + n_tex), tc(tex_child, tex_child + 2 * (size_t)n_tex);
-    std::vector<double> mp(mat_param, mat_param + n_mats), tpv(tex_param, tex_param + (size_t)n_tex * RTMI_TEX_STRIDE);
-    int rc = RTMI_OK;
-    if (!rc) rc = upload(s, stat_geom, &d.stat_geom);
-    if (!rc) rc = upload(s, stat_orig, &d.stat_orig);
-    if (!stat_orig.empty()) { // pad to round_up(n,8)+8 records with copies of the last sphere (see scan_static_pipe)
-        const size_t n4 = (stat_orig.size() + 7) / 8 * 8 + 8;
-        const double ld[4] = {stat4_d[stat4_d.size() - 4], stat4_d[stat4_d.size() - 3], stat4_d[stat4_d.size() - 2], stat4_d[stat4_d.size() - 1]};
-        const float lf[4] = {stat4_f[stat4_f.size() - 4], stat4_f[stat4_f.size() - 3], stat4_f[stat4_f.size() - 2], stat4_f[stat4_f.size() - 1]};
-        while (stat4_d.size() < n4 * 4) stat4_d.insert(stat4_d.end(), ld, ld + 4);
-        while (stat4_f.size() < n4 * 4) stat4_f.insert(stat4_f.end(), lf, lf + 4);
-    }
-    // ---- scan variant SCAN_SGPR_CULL: all primitives in Hitlist order ----
-    // exact12[i] = c0.xyz, r*r, c1.xyz, t0, t1, moving?, r, 0 ; cull20 = FP32 bounding data per group of 4.
-    // A MovingSphere's cull entry bounds its sweep over the camera's shutter interval [t_lo, t_hi] (rays outside that
-    // interval bypass the cull, make_cull_ray): centre = midpoint of the two extreme centres, radius = r + half the
-    // distance between them, both inflated for the float rounding of the centre.
-    const double t_lo = cam_kind == RTMI_CAM_THINLENS ? std::min(cam[22], cam[23]) : 0.0;
-    const double t_hi = cam_kind == RTMI_CAM_THINLENS ? std::max(cam[22], cam[23]) : 0.0;
-    std::vector<double> exact12;
-    std::vector<float> cull_c, cull_r2, cull_w; // per primitive: centre (3), r2, w
-    std::vector<BvhBox> wbox((size_t)n_prims);
-    std::vector<char> bounded((size_t)n_prims, 0);
-    std::vector<int> ext_info;
-    std::vector<double> ext_xf;
-    for (int k = 0; k < n_xforms; ++k) {
-        const double *p = xform_param + (size_t)k * 3;
-        const double rec[4] = {xform_kind[k] == RTMI_XFORM_TRANSLATE ? 0.0 : 1.0, p[0], p[1], p[2]};
-        ext_xf.insert(ext_xf.end(), rec, rec + 4);
-    }
-    for (int i = 0; i < n_prims; ++i) {
-        const double *g = prim_geom + (size_t)i * RTMI_PRIM_STRIDE;
-        const int kind = prim_kind[i] & ~RTMI_PRIM_BOUNDARY;
-        const int xf_first = prim_xform ? prim_xform[2 * i] : 0, xf_count = prim_xform ? prim_xform[2 * i + 1] : 0;
-        const int info[4] = {kind, prim_flip ? (prim_flip[i] & 1) : 0, xf_first, xf_count};
-        ext_info.insert(ext_info.end(), info, info + 4);
-        if (kind == RTMI_PRIM_MEDIUM) { // not a surface: no box, a neutral cull entry (ext_prim_test ignores it), evaluated by ext_medium_test
-            exact12.insert(exact12.end(), {g[0], g[1], g[2], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0});
-            cull_c.insert(cull_c.end(), {0.0f, 0.0f, 0.0f});
-            cull_r2.push_back(0.0f);
-            cull_w.push_back(0.0f);
-            continue;
-        }
-        bounded[(size_t)i] = prim_world_box(kind, g, xform_kind, xform_param, xf_first, xf_count, t_lo, t_hi, wbox[(size_t)i]);
-        const bool moving = kind == RTMI_PRIM_MOVING;
-        const volatile double r2d = g[3] * g[3];
-        if (kind > RTMI_PRIM_MOVING || xf_count > 0) { // f3 primitive or instanced sphere: cull by the sphere around its world box
-            if (kind > RTMI_PRIM_MOVING) exact12.insert(exact12.end(), {g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], 0.0, 0.0, 0.0});
-            else exact12.insert(exact12.end(), {g[0], g[1], g[2], (double)r2d, g[4], g[5], g[6], g[7], g[8], moving ? 1.0 : 0.0, g[3], 0.0});
-            float cf[3] = {0, 0, 0};
-            double r2b = 3.0e38, w = 3.0e38;
-            if (bounded[(size_t)i]) {
-                const BvhBox &b = wbox[(size_t)i];
-                double slack = 0.0, rb2 = 0.0, cn = 0.0;
-                for (int k = 0; k < 3; ++k) {
-                    const double cm = 0.5 * (b.lo[k] + b.hi[k]);
-                    cf[k] = (float)cm;
-                    slack += std::fabs(cm - (double)cf[k]);
-                    rb2 += 0.25 * (b.hi[k] - b.lo[k]) * (b.hi[k] - b.lo[k]);
-                    cn += std::fabs((double)cf[k]);
-                }
-                const double rb = (std::sqrt(rb2) + slack + 1e-4) * (1.0 + 1e-6); // 1e-4: the reference's own rect/triangle bbox padding scale
-                r2b = rb * rb * (1.0 + 1e-6);
-                w = (2.0 * (cn + slack) * (cn + slack) + r2b) * 1.0001;
-                if (!std::isfinite(w) || w > 1e37) { w = 3.0e38; r2b = 3.0e38; }
-            }
-            cull_c.insert(cull_c.end(), cf, cf + 3);
-            cull_r2.push_back((float)std::min(r2b * (1.0 + 1e-6), 3.0e38));
-            cull_w.push_back((float)std::min(w, 3.0e38));
-            continue;
-        }
-        const double rec[12] = {g[0], g[1], g[2], (double)r2d, g[4], g[5], g[6], g[7], g[8], moving ? 1.0 : 0.0, g[3], 0.0};
-        exact12.insert(exact12.end(), rec, rec + 12);
-        double cm[3] = {g[0], g[1], g[2]}, rb = std::fabs(g[3]);
-        bool unbounded = false;
-        if (moving) {
-            const double f0 = (t_lo - g[7]) / (g[8] - g[7]), f1 = (t_hi - g[7]) / (g[8] - g[7]);
-            if (!std::isfinite(f0) || !std::isfinite(f1)) unbounded = true;
-            else {
-                double half2 = 0.0;
-                for (int k = 0; k < 3; ++k) {
-                    const double a0 = g[k] * (1.0 - f0) + g[4 + k] * f0, a1 = g[k] * (1.0 - f1) + g[4 + k] * f1;
-                    cm[k] = 0.5 * (a0 + a1);
-                    half2 += 0.25 * (a1 - a0) * (a1 - a0);
-                }
-                rb += std::sqrt(half2) * (1.0 + 1e-9);
-            }
-        }
-        float cf[3];
-        double slack = 0.0;
-        for (int k = 0; k < 3; ++k) { cf[k] = (float)cm[k]; slack += std::fabs(cm[k] - (double)cf[k]); }
-        if (moving) rb = (rb + slack) * (1.0 + 1e-6); // the bounding sphere is defined around the FLOAT centre
-        const double r2b = moving ? rb * rb * (1.0 + 1e-6) : (double)r2d;
-        const double cn = std::fabs((double)cf[0]) + std::fabs((double)cf[1]) + std::fabs((double)cf[2]) + slack;
-        double w = (2.0 * cn * cn + r2b) * 1.0001;
-        if (unbounded || !std::isfinite(w) || w > 1e37) w = 3.0e38; // tol = inf: always passes to the exact test
-        cull_c.insert(cull_c.end(), cf, cf + 3);
-        cull_r2.push_back(unbounded ? 3.0e38f : (float)std::min(r2b * (moving ? 1.0 + 1e-6 : 1.0), 3.0e38));
-        cull_w.push_back((float)w);
-    }
-    // Box = six consecutive rectangles RectXY z1, RectXY z0, RectXZ y1, RectXZ y0, RectYZ x1, RectYZ x0 over one (x0 y0 z0) - (x1 y1 z1) and one instance
-    // chain (hitable.clj:500-511, spliced in by the flattener): the tree gets one leaf for the six (ext_box_test); z0 goes to slot 5 of the first record
-    std::vector<char> box_first((size_t)std::max(n_prims, 1), 0);
-    if (const char *e = std::getenv("RTMI_BOX_LEAF"); e && e[0] == '1') // (measured: make-final 22.1 ms with box leaves against 21.2 without -- six face tests per leaf cost more than the 1.8 node visits they save; kept for experiments)
-    for (int i = 0; i + 5 < n_world; ++i) {
-        static const int want[6] = {RTMI_PRIM_RECT_XY, RTMI_PRIM_RECT_XY, RTMI_PRIM_RECT_XZ, RTMI_PRIM_RECT_XZ, RTMI_PRIM_RECT_YZ, RTMI_PRIM_RECT_YZ};
-        bool ok = true;
-        for (int k = 0; k < 6 && ok; ++k) {
-            ok = pk[(size_t)i + k] == want[k];
-            if (prim_xform) ok = ok && prim_xform[2 * (i + k)] == prim_xform[2 * i] && prim_xform[2 * (i + k) + 1] == prim_xform[2 * i + 1];
-        }
-        if (!ok) continue;
-        const double *q = prim_geom + (size_t)i * RTMI_PRIM_STRIDE;
-        const double x0 = q[0], y0 = q[1], x1 = q[2], y1 = q[3], z1 = q[4], z0 = q[RTMI_PRIM_STRIDE + 4];
-        const double expect[6][5] = {{x0, y0, x1, y1, z1}, {x0, y0, x1, y1, z0}, {x0, z0, x1, z1, y1}, {x0, z0, x1, z1, y0}, {y0, z0, y1, z1, x1}, {y0, z0, y1, z1, x0}};
-        for (int k = 0; k < 6 && ok; ++k) for (int c = 0; c < 5; ++c) ok = ok && std::memcmp(&q[(size_t)k * RTMI_PRIM_STRIDE + c], &expect[k][c], sizeof(double)) == 0; // bit for bit
-        if (!ok) continue;
-        box_first[(size_t)i] = 1;
-        exact12[(size_t)i * 12 + 5] = z0;
-        i += 5;
-    }
-    const size_t n_pad = n_prims > 0 ? ((size_t)n_prims + 7) / 8 * 8 + 8 : 0;
-    if (n_prims > 0) {
-        const std::vector<double> last12(exact12.begin() + (size_t)(n_prims - 1) * 12, exact12.begin() + (size_t)n_prims * 12);
-        exact12.resize((size_t)n_prims * 12);
-        for (size_t i = (size_t)n_prims; i < n_pad; ++i) {
-            exact12.insert(exact12.end(), last12.begin(), last12.end());
-            cull_c.push_back(cull_c[(size_t)(n_prims - 1) * 3]); cull_c.push_back(cull_c[(size_t)(n_prims - 1) * 3 + 1]); cull_c.push_back(cull_c[(size_t)(n_prims - 1) * 3 + 2]);
-            cull_r2.push_back(cull_r2[(size_t)n_prims - 1]);
-            cull_w.push_back(cull_w[(size_t)n_prims - 1]);
-        }
-    }
-    std::vector<float> cull20; // per group of 4 (padded) primitives: cx[4] cy[4] cz[4] r2[4] w[4]
-    for (size_t g = 0; g + 3 < n_pad; g += 4) {
-        float rec[20];
-        for (int k = 0; k < 4; ++k) {
-            rec[k] = cull_c[(g + k) * 3]; rec[4 + k] = cull_c[(g + k) * 3 + 1]; rec[8 + k] = cull_c[(g + k) * 3 + 2];
-            rec[12 + k] = cull_r2[g + k]; rec[16 + k] = cull_w[g + k];
-        }
-        cull20.insert(cull20.end(), rec, rec + 20);
-    }
-    d.n_all = n_world; d.cull_t_lo = t_lo; d.cull_t_hi = t_hi; // the scans walk the world; boundary primitives are reached only through their medium
-    d.n_media = n_media;
-    for (int k = 0; k < n_media; ++k) { d.media_idx[k] = media[k]; d.media_lo[k] = media[k]; }
-    s->host_kind = pk;
-    std::vector<int> grid_cells;
-    const double t_create1 = now_ms();
-    std::vector<BvhBox> media_boxes; // per ConstantMedium: the box of its boundary (if every boundary primitive can be bounded)
-    for (int k = 0; k < n_media; ++k) {
-        const double *mg = prim_geom + (size_t)media[k] * RTMI_PRIM_STRIDE;
-        const int fb = (int)mg[1], nb = (int)mg[2];
-        BvhBox u = box_empty();
-        bool ok = true;
-        for (int q = fb; q < fb + nb; ++q) { ok = ok && bounded[(size_t)q]; if (ok) box_grow(u, wbox[(size_t)q]); }
-        if (ok) media_boxes.push_back(u);
-    }
-    const std::vector<float> bvh_nodes = build_bvh(d, n_world, pk.data(), wbox, bounded, cam, !has_ext, grid_cells, box_first, &s->bvh_depth, &media_boxes);
-    s->bvh_node_count = (int)(bvh_nodes.size() / (d.bvh_node16 ? 8 : 16));
-    if (std::getenv("RTMI_DEBUG"))
-        fprintf(stderr, "[rtmi] tree: %d node records of %d bytes (%.2f MB), depth %d, %d big primitives, %d box leaves; entry grid %d x %d cells, %zu rectangle trees\n", s->bvh_node_count,
-                d.bvh_node16 ? 32 : 64, s->bvh_node_count * (d.bvh_node16 ? 32.0 : 64.0) / 1e6, s->bvh_depth, d.n_big, (int)std::count(box_first.begin(), box_first.end(), (char)1), d.grid_n, d.grid_n, grid_cells.size());
-    if (std::getenv("RTMI_DEBUG") && d.n_mloc) fprintf(stderr, "[rtmi] %d medium neighbourhood tree(s)\n", d.n_mloc);
-    const double t_create2 = now_ms();
-    if (!rc) rc = upload(s, bvh_nodes, &d.bvh_nodes);
-    if (!rc) rc = upload(s, grid_cells, &d.grid_cells);
-    std::vector<int> moving_all;
-    for (int i = 0; i < n_world; ++i) if (pk[(size_t)i] == RTMI_PRIM_MOVING) moving_all.push_back(i);
-    d.n_moving_all = (int)moving_all.size();
-    if (!rc) rc = upload(s, moving_all, &d.moving_all);
-    d.has_ext = has_ext ? 1 : 0;
-    { const char *e = std::getenv("RTMI_SMALL_SCAN"); d.small_scan = (has_ext && n_world <= RTMI_SMALL_SCAN_MAX && !(e && e[0] == '0')) ? 1 : 0; }
-    { // LeafRec (rtmi_device.h: ext_leaf_test): one 112-byte record per world primitive
-        std::vector<double> leaf_rec((size_t)std::max(n_prims, 1) * RTMI_LEAF_REC_DOUBLES, 0.0);
-        for (int i = 0; i < n_prims; ++i) {
-            double *q = &leaf_rec[(size_t)i * RTMI_LEAF_REC_DOUBLES];
-            const int kind = pk[(size_t)i];
-            const int xf_first = prim_xform ? prim_xform[2 * i] : 0, xf_count = prim_xform ? prim_xform[2 * i + 1] : 0;
-            int hdr[4] = {kind | ((prim_flip && (prim_flip[i] & 1)) ? 0x100 : 0), 0, 0, 0}; // bit 8: FlipNormals parity (resolve_hit_ext)
-            const bool simple = (kind == RTMI_PRIM_SPHERE || kind == RTMI_PRIM_UVSPHERE || (kind >= RTMI_PRIM_RECT_XY && kind <= RTMI_PRIM_RECT_YZ)) && xf_count <= 2;
-            if (!simple) hdr[1] = 1; // generic: ext_prim_test
-            else {
-                for (int c = 0; c < 5; ++c) q[2 + c] = exact12[(size_t)i * 12 + c]; // sphere: c r*r (slot 4 unused) | rectangle: u0 v0 u1 v1 k
-                for (int k = 0; k < xf_count; ++k) {
-                    const double *xp = xform_param + (size_t)(xf_first + k) * 3;
-                    hdr[2 + k] = xform_kind[xf_first + k] == RTMI_XFORM_TRANSLATE ? 1 : 2;
-                    q[7 + 3 * k] = xp[0]; q[8 + 3 * k] = xp[1]; q[9 + 3 * k] = xp[2];
-                }
-                if (box_first[(size_t)i]) q[13] = exact12[(size_t)i * 12 + 5]; // z0 of the Box whose first face this rectangle is
-            }
-            std::memcpy(q, hdr, sizeof hdr);
-        }
-        if (!rc) rc = upload(s, leaf_rec, &d.leaf_rec);
-    }
-    ext_info.insert(ext_info.end(), {RTMI_PRIM_MEDIUM, 0, 0, 0}); // one record past the end: scan_small_ext requests primitive i + 1's records while it tests primitive i
-    if (!rc) rc = upload(s, ext_info, &d.ext_info);
-    if (!rc) rc = upload(s, ext_xf, &d.ext_xf);
-    if (!rc) rc = upload(s, cull20, &d.cull20);
-    if (!rc) rc = upload(s, exact12, &d.exact12);
-    if (!rc) rc = upload(s, stat4_d, &d.stat4_d);
-    if (!rc) rc = upload(s, stat4_f, &d.stat4_f);
-    if (!rc) rc = upload(s, mov_geom, &d.mov_geom);
-    if (!rc) rc = upload(s, mov_orig, &d.mov_orig);
-    { // device copy of prim_kind: + RTMI_PRIM_NEEDS_U / _V where a UVSphere's material texture reads that coordinate (texture.clj: UVGradient --
-      // per coordinate: a gradient whose corner colours do not vary along u never reads u --, ImageMap, through Checkerboard / FlipTexture
-      // children); Constant, Checkerboard itself and the Perlin family read p only
-        std::vector<char> uses((size_t)std::max(n_tex, 1), 0); // bit 0: reads u, bit 1: reads v
-        bool changed = true;
-        for (int pass = 0; pass <= n_tex && changed; ++pass) { // children may come after their parents: iterate to the fixed point (a pass that changes nothing ends it:
-            changed = false;                                  // one texture per sphere made the unconditional n_tex passes 5.8 of the 6.4 s a 90 000-sphere scene took to create)
-            for (int t = 0; t < n_tex; ++t) {
-                const int k = tex_kind[t];
-                char u = k == RTMI_TEX_IMAGE ? 3 : 0;
-                if (k == RTMI_TEX_UVGRADIENT) { // co cu cv cuv: a = cu (1-u) + co u, b = cuv (1-u) + cv u, out = b (1-v) + a v  (texture.clj:26-34)
-                    const double *tp = tex_param + (size_t)t * RTMI_TEX_STRIDE;
-                    bool var_u = false, var_v = false;
-                    // "does not vary" is a comparison of BITS (memcmp), not of values: only then is the lerp of the two colours at u = 1/2 the colour itself
-                    // whatever it holds (c/2 + c/2 = c exactly; +0 against -0, or two different NaNs, count as varying and keep the real coordinate)
-                    auto same = [&](int a, int b) { return std::memcmp(&tp[a], &tp[b], sizeof(double)) == 0; };
-                    for (int c = 0; c < 3; ++c) {
-                        var_u = var_u || !same(c, 3 + c) || !same(6 + c, 9 + c);     // co != cu or cv != cuv
-                        var_v = var_v || !same(c, 6 + c) || !same(3 + c, 9 + c);     // co != cv or cu != cuv
-                    }
-                    u = (char)((var_u ? 1 : 0) | (var_v ? 2 : 0));
-                }
-                if (k == RTMI_TEX_CHECKER || k == RTMI_TEX_FLIP_U || k == RTMI_TEX_FLIP_V)
-                    for (int c = 0; c < (k == RTMI_TEX_CHECKER ? 2 : 1); ++c) {
-                        const int ch = tex_child[2 * (size_t)t + c];
-                        if (ch >= 0 && ch < n_tex) u |= uses[(size_t)ch];
-                    }
-                if (uses[(size_t)t] != u) { uses[(size_t)t] = u; changed = true; }
-            }
-        }
-        std::vector<int> pk_dev(pk);
-        for (int i = 0; i < n_prims; ++i)
-            if (pk[(size_t)i] == RTMI_PRIM_UVSPHERE) {
-                const int m = pm[(size_t)i], t = (m >= 0 && m < n_mats) ? mat_tex[m] : -1;
-                const int bits = (t < 0 || t >= n_tex) ? 3 : uses[(size_t)t];
-                if (bits & 1) pk_dev[(size_t)i] |= RTMI_PRIM_NEEDS_U;
-                if (bits & 2) pk_dev[(size_t)i] |= RTMI_PRIM_NEEDS_V;
-            } else if (pk[(size_t)i] >= RTMI_PRIM_RECT_XY && pk[(size_t)i] <= RTMI_PRIM_TRIANGLE) {
-                // a rectangle's uv is two IEEE divisions per hit (hitable.clj:283-284), a triangle's a second Moeller-Trumbore: computed only where the material's
-                // texture reads uv at all (both coordinates then: no coordinate is ever replaced here, so nothing deviates) -- a Cornell box's walls never do
-                const int m = pm[(size_t)i], t = (m >= 0 && m < n_mats) ? mat_tex[m] : -1;
-                if (t < 0 || t >= n_tex || uses[(size_t)t]) pk_dev[(size_t)i] |= RTMI_PRIM_NEEDS_UV;
-            }
-        if (!rc) rc = upload(s, pk_dev, &d.prim_kind);
-        std::vector<int> km((size_t)std::max(n_prims, 1) * 2, 0);
-        for (int i = 0; i < n_prims; ++i) { km[2 * (size_t)i] = pk_dev[(size_t)i]; km[2 * (size_t)i + 1] = pm[(size_t)i]; }
-        if (!rc) rc = upload(s, km, &d.prim_km);
-        std::vector<double> mrec((size_t)std::max(n_mats, 1) * 12, 0.0), mgrad((size_t)std::max(n_mats, 1) * 12, 0.0);
-        for (int m = 0; m < n_mats; ++m) {
-            MatRec r;
-            std::memset(&r, 0, sizeof(r));
-            r.mat_kind = mat_kind[m]; r.tex = mat_tex[m]; r.param = mat_param[m];
-            if (mat_kind[m] == RTMI_MAT_DIELECTRIC) { // one IEEE operation each, as the kernel would evaluate them per scatter
-                const volatile double ri = mat_param[m];
-                const volatile double inv = 1.0 / ri, num = 1.0 - ri, den = 1.0 + ri;
-                const volatile double q = num / den;
-                const volatile double r0 = q * q;
-                r.inv_ri = inv; r.r0 = r0;
-            }
-            r.tex_kind = (r.tex >= 0 && r.tex < n_tex) ? tex_kind[r.tex] : -1;
-            if (r.tex_kind == RTMI_TEX_CONSTANT) { const double *tp = tex_param + (size_t)r.tex * RTMI_TEX_STRIDE; r.r = tp[0]; r.g = tp[1]; r.b = tp[2]; }
-            if (r.tex_kind == RTMI_TEX_UVGRADIENT) { // texture.clj:26-34: co cu cv cuv travel with the material
-                std::memcpy(&mgrad[(size_t)m * 12], tex_param + (size_t)r.tex * RTMI_TEX_STRIDE, 12 * sizeof(double));
-                r.tex_kind = RTMI_TEX_GRADIENT_REC;
-            }
-            if (r.tex_kind == RTMI_TEX_CHECKER) { // both children Constant: the whole texture fits the record
-                const int c0 = tex_child[2 * (size_t)r.tex], c1 = tex_child[2 * (size_t)r.tex + 1];
-                if (c0 >= 0 && c0 < n_tex && c1 >= 0 && c1 < n_tex && tex_kind[c0] == RTMI_TEX_CONSTANT && tex_kind[c1] == RTMI_TEX_CONSTANT) {
-                    const double *t0 = tex_param + (size_t)c0 * RTMI_TEX_STRIDE, *t1 = tex_param + (size_t)c1 * RTMI_TEX_STRIDE;
-                    r.tex_kind = RTMI_TEX_CHECKER2;
-                    r.scale = tex_param[(size_t)r.tex * RTMI_TEX_STRIDE];
-                    r.r = t0[0]; r.g = t0[1]; r.b = t0[2]; r.c1r = t1[0]; r.c1g = t1[1]; r.c1b = t1[2];
-                }
-            }
-            static_assert(sizeof(MatRec) == 96, "MatRec is twelve doubles");
-            std::memcpy(&mrec[(size_t)m * 12], &r, sizeof(r));
-        }
-        if (!rc) rc = upload(s, mrec, &d.mat_rec);
-        if (!rc) rc = upload(s, mgrad, &d.mat_grad);
-    }
-    if (!rc) rc = upload(s, pm, &d.prim_mat);
-    if (!rc) rc = upload(s, mk, &d.mat_kind);
-    if (!rc) rc = upload(s, mt, &d.mat_tex);
-    if (!rc) rc = upload(s, mp, &d.mat_param);
-    if (!rc) rc = upload(s, tk, &d.tex_kind);
-    if (!rc) rc = upload(s, tpv, &d.tex_param);
-    if (!rc) rc = upload(s, tc, &d.tex_child);
-    for (int k = 0; k < n_media; ++k) { // media whose boundary is one plain sphere, neither under wrappers: their operands go into the descriptor (media_fast)
-        const int m = media[k];
-        const int fb = (int)prim_geom[(size_t)m * RTMI_PRIM_STRIDE + 1], nb = (int)prim_geom[(size_t)m * RTMI_PRIM_STRIDE + 2];
-        if (nb != 1 || fb < 0 || fb >= n_prims) continue;
-        if (pk[(size_t)fb] != RTMI_PRIM_SPHERE && pk[(size_t)fb] != RTMI_PRIM_UVSPHERE) continue;
-        if (prim_xform && (prim_xform[2 * m + 1] != 0 || prim_xform[2 * fb + 1] != 0)) continue;
-        s->media_fast_of[m] = {exact12[(size_t)m * 12], exact12[(size_t)fb * 12], exact12[(size_t)fb * 12 + 1], exact12[(size_t)fb * 12 + 2], exact12[(size_t)fb * 12 + 3]};
-    }
+    const Table tables[] = { // (uploaded in this order, as they always were)
+        {P.stat_geom, &d.stat_geom}, {P.stat_orig, &d.stat_orig}, {P.bvh_nodes, &d.bvh_nodes}, {P.grid_cells, &d.grid_cells}, {P.moving_all, &d.moving_all},
+        {P.leaf_rec, &d.leaf_rec}, {P.ext_info, &d.ext_info}, {P.ext_xf, &d.ext_xf}, {P.cull20, &d.cull20}, {P.exact12, &d.exact12}, {P.stat4_d, &d.stat4_d},
+        {P.stat4_f, &d.stat4_f}, {P.mov_geom, &d.mov_geom}, {P.mov_orig, &d.mov_orig}, {P.prim_kind, &d.prim_kind}, {P.prim_km, &d.prim_km},
+        {P.mat_rec, &d.mat_rec}, {P.mat_grad, &d.mat_grad}, {P.prim_mat, &d.prim_mat}, {P.mat_kind, &d.mat_kind}, {P.mat_tex, &d.mat_tex},
+        {P.mat_param, &d.mat_param}, {P.tex_kind, &d.tex_kind}, {P.tex_param, &d.tex_param}, {P.tex_child, &d.tex_child}};
+    for (const Table &t : tables) if ((rc = upload(s, t))) break;
     fill_media_fast(s);
     if (!rc) {
         std::vector<DevScene> one(1, d);
         const DevScene *dp = nullptr;
-        rc = upload(s, one, &dp);
+        rc = upload(s, Table(one, &dp));
         s->d_dev = (ScenePtr)dp;
     }
     if (rc) { rtmi_scene_destroy(s); return rc; }
-    if (std::getenv("RTMI_DEBUG"))
-        fprintf(stderr, "[rtmi] scene create: records %.2f ms, trees %.2f ms, tables + upload (%zu allocations, %.2f MB) %.2f ms\n", t_create1 - t_create0, t_create2 - t_create1,
-                s->allocs.size(), (double)s->device_bytes / 1e6, now_ms() - t_create2);
+    if (knobs.debug)
+        fprintf(stderr, "[rtmi] scene create: records %.2f ms, trees %.2f ms, tables + upload (%zu allocations, %.2f MB) %.2f ms\n", P.t_tree0 - t_create0, P.t_tree1 - P.t_tree0,
+                s->allocs.size(), (double)s->device_bytes / 1e6, now_ms() - P.t_tree1);
     {
         rtmi_scene::Args &A = s->args;
         A.prim_kind.assign(prim_kind, prim_kind + n_prims); A.prim_mat.assign(prim_mat, prim_mat + n_prims);
@@ -2347,8 +1458,8 @@ RTMI_EXPORT int rtmi_scene_set_perlin(rtmi_scene *s, const double *vectors, cons
     HIP_TRY(hipSetDevice(s->ctx->device));
     std::vector<double> v(vectors, vectors + 768);
     std::vector<int> p(perm, perm + 768);
-    int rc = upload(s, v, &s->dev.perlin_vec);
-    if (!rc) rc = upload(s, p, &s->dev.perlin_perm);
+    int rc = upload(s, Table(v, &s->dev.perlin_vec));
+    if (!rc) rc = upload(s, Table(p, &s->dev.perlin_perm));
     if (rc) return rc;
     s->have_perlin = true;
     s->args.perlin_vec = v; s->args.perm.assign(perm, perm + 768);
@@ -2416,9 +1527,9 @@ RTMI_EXPORT int rtmi_scene_set_images(rtmi_scene *s, int32_t n_images, const int
     }
     HIP_TRY(hipSetDevice(s->ctx->device));
     std::vector<unsigned char> px(rgb, rgb + total);
-    int rc = upload(s, whv, &s->dev.image_wh);
-    if (!rc) rc = upload(s, off, &s->dev.image_off);
-    if (!rc) rc = upload(s, px, &s->dev.image_rgb);
+    int rc = upload(s, Table(whv, &s->dev.image_wh));
+    if (!rc) rc = upload(s, Table(off, &s->dev.image_off));
+    if (!rc) rc = upload(s, Table(px, &s->dev.image_rgb));
     if (rc) return rc;
     s->dev.n_images = n_images;
     s->args.image_wh = whv; s->args.image_rgb = px;
@@ -2898,6 +2009,38 @@ struct Tmp { // scoped device temporaries for the (synchronous) probe entry poin
 #define PROBE_EPILOGUE()                      \
     HIP_TRY(hipGetLastError());               \
     HIP_TRY(hipStreamSynchronize(c->stream));
+
+// the two probe kernels that trace like a render: Family::kernel<R, VARIANT, EXT, MSEQ>() is the instantiation
+struct ProbeHit { template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_hit_kernel<R, V, EXT, MSEQ>; } };
+struct ProbePaths { template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_kernel<R, V, EXT, MSEQ>; } };
+
+// The probe instantiation the scene and the context select (precision x mixed kinds x media_seq x accel / scan_variant) and its dynamic LDS:
+// launch(kernel, lds_bytes, prims_per_tile, n_ptiles).  Mixed-kind scenes have FP64 kernels only (the entries refuse RTMI_F32 for them).
+template <typename Family, typename R, typename Launch> void with_probe_kernel(const rtmi_scene *s, Launch launch) {
+    const rtmi_ctx *c = s->ctx;
+    int ppt, npt;
+    size_t lds;
+    lds_plan(c, s->dev.n_static, sizeof(R), &ppt, &npt, &lds);
+    const size_t bvh_lds = (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16;
+    const bool bvh = c->accel == RTMI_ACCEL_BVH;
+    if constexpr (std::is_same<R, double>::value) {
+        if (s->dev.has_ext) { // (operands in the order the kernels were always instantiated in: the device code's inlining follows that order)
+            const int seq = s->dev.media_seq;
+            if (bvh) launch(seq != 2 ? (seq ? Family::template kernel<double, SCAN_BVH, true, 1>() : Family::template kernel<double, SCAN_BVH, true>())
+                                     : Family::template kernel<double, SCAN_BVH, true, 2>(), bvh_lds, ppt, npt);
+            else launch(seq != 2 ? (seq ? Family::template kernel<double, SCAN_SGPR_CULL, true, 1>() : Family::template kernel<double, SCAN_SGPR_CULL, true>())
+                                 : Family::template kernel<double, SCAN_SGPR_CULL, true, 2>(), (size_t)64, ppt, npt);
+            return;
+        }
+    }
+    switch (bvh ? SCAN_BVH : c->scan_variant) {
+    case SCAN_BVH: launch(Family::template kernel<R, SCAN_BVH>(), std::max(lds, bvh_lds), ppt, npt); break;
+    case SCAN_SGPR_CULL: launch(Family::template kernel<R, SCAN_SGPR_CULL>(), lds, ppt, npt); break;
+    case SCAN_SGPR: launch(Family::template kernel<R, SCAN_SGPR>(), lds, ppt, npt); break;
+    case SCAN_LDS_PIPE: launch(Family::template kernel<R, SCAN_LDS_PIPE>(), lds, ppt, npt); break;
+    default: launch(Family::template kernel<R, SCAN_LDS_LITERAL>(), lds, ppt, npt);
+    }
+}
 } // namespace
 
 RTMI_EXPORT int rtmi_probe_hit(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, double t_min, double t_max, double *out) {
@@ -2907,31 +2050,11 @@ RTMI_EXPORT int rtmi_probe_hit(rtmi_scene *s, int32_t precision, int32_t n, cons
     double *d_rays = (double *)tmp.up(rays, (size_t)n * 7 * sizeof(double));
     double *d_out = (double *)tmp.alloc((size_t)n * 11 * sizeof(double));
     if (!d_rays || !d_out) return fail(RTMI_E_NOMEM, "probe buffers");
-    int ppt, npt; size_t lds;
-    if (precision == RTMI_F64) {
-        lds_plan(c, s->dev.n_static, sizeof(double), &ppt, &npt, &lds);
-        if (s->dev.has_ext) {
-            const int seq = s->dev.media_seq;
-            if (c->accel == RTMI_ACCEL_BVH) hipLaunchKernelGGL((seq == 2 ? probe_hit_kernel<double, SCAN_BVH, true, 2> : seq ? probe_hit_kernel<double, SCAN_BVH, true, 1> : probe_hit_kernel<double, SCAN_BVH, true>), dim3(grid), dim3(kBlock), (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out);
-            else hipLaunchKernelGGL((seq == 2 ? probe_hit_kernel<double, SCAN_SGPR_CULL, true, 2> : seq ? probe_hit_kernel<double, SCAN_SGPR_CULL, true, 1> : probe_hit_kernel<double, SCAN_SGPR_CULL, true>), dim3(grid), dim3(kBlock), 64, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out);
-        } else
-        switch (c->accel == RTMI_ACCEL_BVH ? SCAN_BVH : c->scan_variant) {
-        case SCAN_BVH: hipLaunchKernelGGL((probe_hit_kernel<double, SCAN_BVH>), dim3(grid), dim3(kBlock), std::max(lds, (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16), c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out); break;
-        case SCAN_SGPR_CULL: hipLaunchKernelGGL((probe_hit_kernel<double, SCAN_SGPR_CULL>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out); break;
-        case SCAN_SGPR: hipLaunchKernelGGL((probe_hit_kernel<double, SCAN_SGPR>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out); break;
-        case SCAN_LDS_PIPE: hipLaunchKernelGGL((probe_hit_kernel<double, SCAN_LDS_PIPE>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out); break;
-        default: hipLaunchKernelGGL((probe_hit_kernel<double, SCAN_LDS_LITERAL>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out);
-        }
-    } else {
-        lds_plan(c, s->dev.n_static, sizeof(float), &ppt, &npt, &lds);
-        switch (c->accel == RTMI_ACCEL_BVH ? SCAN_BVH : c->scan_variant) {
-        case SCAN_BVH: hipLaunchKernelGGL((probe_hit_kernel<float, SCAN_BVH>), dim3(grid), dim3(kBlock), std::max(lds, (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16), c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out); break;
-        case SCAN_SGPR_CULL: hipLaunchKernelGGL((probe_hit_kernel<float, SCAN_SGPR_CULL>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out); break;
-        case SCAN_SGPR: hipLaunchKernelGGL((probe_hit_kernel<float, SCAN_SGPR>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out); break;
-        case SCAN_LDS_PIPE: hipLaunchKernelGGL((probe_hit_kernel<float, SCAN_LDS_PIPE>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out); break;
-        default: hipLaunchKernelGGL((probe_hit_kernel<float, SCAN_LDS_LITERAL>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out);
-        }
-    }
+    auto run = [&](auto kern, size_t lds, int ppt, int npt) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out);
+    };
+    if (precision == RTMI_F64) with_probe_kernel<ProbeHit, double>(s, run);
+    else with_probe_kernel<ProbeHit, float>(s, run);
     PROBE_EPILOGUE()
     HIP_TRY(hipMemcpy(out, d_out, (size_t)n * 11 * sizeof(double), hipMemcpyDeviceToHost));
     return RTMI_OK;
@@ -2952,31 +2075,11 @@ RTMI_EXPORT int rtmi_probe_paths(rtmi_scene *s, int32_t precision, int32_t n, co
     double *d_log = log ? (double *)tmp.alloc(log_bytes) : nullptr;
     if (!d_rays || !d_keys || !d_rgb || !d_nseg || !d_nlog || (log && !d_log)) return fail(RTMI_E_NOMEM, "probe buffers");
     if (d_log) HIP_TRY(hipMemset(d_log, 0, log_bytes));
-    int ppt, npt; size_t lds;
-    if (precision == RTMI_F64) {
-        lds_plan(c, s->dev.n_static, sizeof(double), &ppt, &npt, &lds);
-        if (s->dev.has_ext) {
-            const int seq = s->dev.media_seq;
-            if (c->accel == RTMI_ACCEL_BVH) hipLaunchKernelGGL((seq == 2 ? probe_paths_kernel<double, SCAN_BVH, true, 2> : seq ? probe_paths_kernel<double, SCAN_BVH, true, 1> : probe_paths_kernel<double, SCAN_BVH, true>), dim3(grid), dim3(kBlock), (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog);
-            else hipLaunchKernelGGL((seq == 2 ? probe_paths_kernel<double, SCAN_SGPR_CULL, true, 2> : seq ? probe_paths_kernel<double, SCAN_SGPR_CULL, true, 1> : probe_paths_kernel<double, SCAN_SGPR_CULL, true>), dim3(grid), dim3(kBlock), 64, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog);
-        } else
-        switch (c->accel == RTMI_ACCEL_BVH ? SCAN_BVH : c->scan_variant) {
-        case SCAN_BVH: hipLaunchKernelGGL((probe_paths_kernel<double, SCAN_BVH>), dim3(grid), dim3(kBlock), std::max(lds, (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16), c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog); break;
-        case SCAN_SGPR_CULL: hipLaunchKernelGGL((probe_paths_kernel<double, SCAN_SGPR_CULL>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog); break;
-        case SCAN_SGPR: hipLaunchKernelGGL((probe_paths_kernel<double, SCAN_SGPR>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog); break;
-        case SCAN_LDS_PIPE: hipLaunchKernelGGL((probe_paths_kernel<double, SCAN_LDS_PIPE>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog); break;
-        default: hipLaunchKernelGGL((probe_paths_kernel<double, SCAN_LDS_LITERAL>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog);
-        }
-    } else {
-        lds_plan(c, s->dev.n_static, sizeof(float), &ppt, &npt, &lds);
-        switch (c->accel == RTMI_ACCEL_BVH ? SCAN_BVH : c->scan_variant) {
-        case SCAN_BVH: hipLaunchKernelGGL((probe_paths_kernel<float, SCAN_BVH>), dim3(grid), dim3(kBlock), std::max(lds, (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16), c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog); break;
-        case SCAN_SGPR_CULL: hipLaunchKernelGGL((probe_paths_kernel<float, SCAN_SGPR_CULL>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog); break;
-        case SCAN_SGPR: hipLaunchKernelGGL((probe_paths_kernel<float, SCAN_SGPR>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog); break;
-        case SCAN_LDS_PIPE: hipLaunchKernelGGL((probe_paths_kernel<float, SCAN_LDS_PIPE>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog); break;
-        default: hipLaunchKernelGGL((probe_paths_kernel<float, SCAN_LDS_LITERAL>), dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog);
-        }
-    }
+    auto run = [&](auto kern, size_t lds, int ppt, int npt) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog);
+    };
+    if (precision == RTMI_F64) with_probe_kernel<ProbePaths, double>(s, run);
+    else with_probe_kernel<ProbePaths, float>(s, run);
     PROBE_EPILOGUE()
     HIP_TRY(hipMemcpy(out_rgb, d_rgb, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_nseg) HIP_TRY(hipMemcpy(out_nseg, d_nseg, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost));

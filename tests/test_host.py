@@ -376,7 +376,7 @@ def test_bench_dump_outputs_fit_the_budget(tmp_path):
 
 
 def test_half_outward_is_directed_rounding_to_half():
-    """the tree's half-plane node records round every box plane OUTWARD to IEEE half (rtmi.hip: half_outward, integer arithmetic on the float's bits): against
+    """the tree's half-plane node records round every box plane OUTWARD to IEEE half (scene_build.h: half_outward, integer arithmetic on the float's bits): against
     numpy's round-to-nearest half stepped to the neighbour on the required side -- one million floats over the whole half range and beyond, subnormals, signed
     zeros, ties, the overflow threshold, infinities.  Host arithmetic only."""
     L = _ffi.lib()
