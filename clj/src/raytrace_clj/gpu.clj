@@ -322,6 +322,35 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn render-progressive
+  "Render scene {:camera :world} progressively on GPU `device` (rtmi_render_progressive): chunks of `chunk` samples up to ns, and after
+  each chunk (on-chunk m) with m = what `render` returns for ns = k (bit for bit) plus :samples k and :stderr (double-array, per pixel the
+  largest channel's standard error of the mean; ##Inf at k = 1).  The arrays are refilled by the next chunk: copy what must outlive it.
+  on-chunk returning :stop ends the render early.  Returns the last m."
+  [scene nx ny ns chunk on-chunk & {:keys [depth seed device precision] :or {depth 50 seed 0x5eed0002 device 0 precision 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        npx  (* nx ny)
+        lin  (double-array (* 3 npx))
+        rgb  (byte-array (* 3 npx))
+        err  (double-array npx)
+        cnt  (long-array 2)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (loop [k 0]
+            (let [n (min chunk (- ns k))]
+              (check (call-int "rtmi_render_progressive" scn (int nx) (int ny) (int k) (int n) (int depth) (long seed) (int precision)
+                               (int 0) (int 0) (int nx) (int ny) lin rgb err cnt))
+              (let [k' (+ k n)
+                    m  {:samples k' :rgb8 rgb :linear lin :stderr err :total-rays (aget cnt 0) :total-pixels (aget cnt 1)}]
+                (if (and (not= :stop (on-chunk m)) (< k' ns))
+                  (recur k')
+                  m))))
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn render-multi
   "The same on every GPU in `devices` from this one JVM (rtmi_render_multi): one context per device, the scene created on
   the first (Perlin tables, ImageMap pixels and media calls included) and cloned onto the others (rtmi_scene_clone), the 8x8

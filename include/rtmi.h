@@ -201,6 +201,39 @@ int rtmi_render_tiles_device(rtmi_scene *scene, int32_t nx, int32_t ny, int32_t 
                              void *d_tiles_linear, void *d_out_counters, void *stream);
 int32_t rtmi_local_tiles(int32_t nx, int32_t ny, int32_t tile_first, int32_t tile_stride);
 
+/* ---- progressive rendering: one frame refined over calls (a preview while it renders, a time budget, more samples later) ----
+ * A context holds at most one progressive frame (two frames at once: two contexts): per-pixel running sums and noise state in HBM, the
+ * cumulative counters, and the key it was started with.  rtmi_render_progressive*(..., s_first, s_count, ...) adds samples
+ * [s_first, s_first + s_count) of every pixel; with k = s_first + s_count the call returns
+ *   out_linear / out_rgb8: the mean over samples [0, k), BIT-IDENTICAL to what rtmi_render / rtmi_render_device return with ns = k and the same
+ *                          scene, nx, ny, depth, seed, precision and region -- for F64 and F32, every scene kind, any sequence of chunk sizes and
+ *                          however option "workspace_bytes" splits a call into passes (every draw is keyed by (seed, pixel, sample), not by ns,
+ *                          and the sums are folded in sample order exactly as the one-shot reduction folds them);
+ *   out_stderr:            one double per pixel (pixel order of out_linear): for k >= 2 the largest of the three channels' standard error of
+ *                          the mean, sqrt(var_c / k), var_c the unbiased sample variance of the channel's k sample values (accumulated in double
+ *                          with Welford's update whatever the precision: exactly 0 when all samples of a pixel are equal); +inf for k = 1;
+ *   out_counters:          {total-rays of samples [0, k), total-pixels}, equal to rtmi_render(ns = k)'s.
+ * Every output may be NULL.
+ * s_first == 0 starts a new frame (any previous one is discarded).  s_first > 0 must equal the k the context holds and the key must match,
+ * else RTMI_E_STATE and rtmi_last_error names what differs.  The key: the scene's identity (a creation serial: a new scene allocated at a
+ * destroyed scene's address does not match), its revision (every rtmi_scene_set_* call changes it), nx, ny, depth, seed, precision and region.
+ * Options the image does not depend on ("accel", "suspend_lanes", "flat_below", "scan_variant", "workspace_bytes", "blocks_per_cu") may change
+ * between calls, and one-shot renders on the same context may come in between: the frame has buffers of its own.
+ * A call that fails before it launches anything (argument checks, a mismatched key, the test_fail_next_render hook) leaves the frame as it
+ * was; a call that fails after it launched anything drops it (k = 0): a later continuation is refused rather than allowed to produce a wrong
+ * image.  s_count <= 0, s_first < 0 or s_first + s_count beyond int32: RTMI_E_ARG; the other argument errors are rtmi_render's.
+ * Like the workspace, the frame belongs to one stream at a time.  RTMI_FLAG_TIMING covers progressive calls too (the "reduce" interval is the
+ * fold of each pass into the frame); rtmi_shutdown frees the frame. */
+/* host buffers, output region [x0,x1) x [y0,y1) as rtmi_render */
+int rtmi_render_progressive(rtmi_scene *scene, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                            int32_t precision, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                            double *out_linear, uint8_t *out_rgb8, double *out_stderr, uint64_t *out_counters);
+/* device buffers, the whole frame, launched on `stream` with rtmi_render_device's stream semantics; asynchronous */
+int rtmi_render_progressive_device(rtmi_scene *scene, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                   int32_t precision, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_counters, void *stream);
+int rtmi_progressive_samples(rtmi_ctx *ctx, int32_t *samples); /* k of the context's progressive frame, 0 = none */
+int rtmi_progressive_release(rtmi_ctx *ctx);                   /* drop the frame and free its buffers */
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

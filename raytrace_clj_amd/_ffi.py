@@ -26,6 +26,7 @@ SYMBOLS = [
     "rtmi_sample_key", "rtmi_test_half_outward", "rtmi_test_build_tree", "rtmi_probe_arith", "rtmi_probe_math", "rtmi_probe_math2", "rtmi_last_traversal_counters",
     "rtmi_scene_clone", "rtmi_render_multi", "rtmi_render_multi_device", "rtmi_last_gather_ms",
     "rtmi_last_gather_path", "rtmi_rccl_probe", "rtmi_stream_idle", "rtmi_last_passes", "rtmi_last_accel",
+    "rtmi_render_progressive", "rtmi_render_progressive_device", "rtmi_progressive_samples", "rtmi_progressive_release",
 ]
 
 F64, F32 = 0, 1
@@ -102,6 +103,10 @@ def lib():
     L.rtmi_stream_idle.argtypes = [vp, C.POINTER(i32)]
     L.rtmi_last_passes.argtypes = [vp, C.POINTER(i32)]
     L.rtmi_last_accel.argtypes = [vp, C.POINTER(i32)]
+    L.rtmi_render_progressive.argtypes = [vp, i32, i32, i32, i32, i32, u64, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.rtmi_render_progressive_device.argtypes = [vp, i32, i32, i32, i32, i32, u64, i32, vp, vp, vp, vp, vp]
+    L.rtmi_progressive_samples.argtypes = [vp, C.POINTER(i32)]
+    L.rtmi_progressive_release.argtypes = [vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

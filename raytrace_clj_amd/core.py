@@ -67,6 +67,16 @@ class Context:
         check(_ffi.lib().rtmi_last_reduce_ms(self.handle, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def progressive_samples(self):
+        """k of the context's progressive frame (samples [0, k) it holds), 0 = none"""
+        k = C.c_int32()
+        check(_ffi.lib().rtmi_progressive_samples(self.handle, C.byref(k)))
+        return k.value
+
+    def progressive_release(self):
+        """drop the context's progressive frame and free its buffers"""
+        check(_ffi.lib().rtmi_progressive_release(self.handle))
+
     def last_traversal_counters(self):
         """(AABB slab tests, exact primitive tests) of the last render; needs set_option("count_traversal", 1) before it
         (metrics.clj:10 aabb.intersection.total, for the device's own tree)"""
@@ -165,6 +175,38 @@ class DeviceScene:
                       seed=RENDER_SEED, precision="f64", stream=None):
         check(_ffi.lib().rtmi_render_device(self.handle, nx, ny, ns, depth, seed, _PRECISION[precision],
                                             ptr(out_linear), ptr(out_rgb8), ptr(out_counters), ptr(stream)))
+
+    # ---- progressive rendering: the context's one progressive frame, refined over calls ---------------------------------
+    def render_progressive(self, nx, ny, s_first, s_count, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", region=None):
+        """Add samples [s_first, s_first + s_count) to the context's progressive frame (s_first = 0 starts one) -> (linear, rgb8, stderr [h,w],
+        counters) after k = s_first + s_count samples: linear, rgb8 and counters equal render(ns = k) bit for bit; stderr = per pixel the largest
+        channel's standard error of the mean (inf at k = 1)."""
+        x0, y0, x1, y1 = region if region is not None else (0, 0, nx, ny)
+        lin = np.zeros((max(y1 - y0, 0), max(x1 - x0, 0), 3), np.float64)
+        q = np.zeros(lin.shape, np.uint8)
+        err = np.zeros(lin.shape[:2], np.float64)
+        cnt = np.zeros(2, np.uint64)
+        check(_ffi.lib().rtmi_render_progressive(self.handle, nx, ny, s_first, s_count, depth, seed, _PRECISION[precision], x0, y0, x1, y1,
+                                                 ptr(lin), ptr(q), ptr(err), ptr(cnt)))
+        return lin, q, err, cnt
+
+    def render_progressive_device(self, nx, ny, s_first, s_count, out_linear=None, out_rgb8=None, out_stderr=None, out_counters=None,
+                                  depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", stream=None):
+        """render_progressive for the whole frame into HBM-resident buffers (asynchronous, render_device's stream semantics)"""
+        check(_ffi.lib().rtmi_render_progressive_device(self.handle, nx, ny, s_first, s_count, depth, seed, _PRECISION[precision],
+                                                        ptr(out_linear), ptr(out_rgb8), ptr(out_stderr), ptr(out_counters), ptr(stream)))
+
+    def refine(self, nx, ny, ns, chunk, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", region=None):
+        """Render progressively in chunks of `chunk` samples up to ns: yields (k, linear, rgb8, stderr, counters) after every chunk.  The
+        caller may stop early; the frame after k samples is render(ns = k)'s."""
+        if chunk <= 0 or ns <= 0:
+            raise ValueError("ns and chunk must be > 0")
+        k = 0
+        while k < ns:
+            n = min(chunk, ns - k)
+            lin, q, err, cnt = self.render_progressive(nx, ny, k, n, depth, seed, precision, region)
+            k += n
+            yield k, lin, q, err, cnt
 
     def render_tiles_device(self, nx, ny, ns, tile_first, tile_stride, out_tiles, out_counters=None, depth=DEFAULT_DEPTH,
                             seed=RENDER_SEED, precision="f64", stream=None):
@@ -369,12 +411,59 @@ SCENES = {  # the scene choices of core.clj:82-90 (there: commented-out lines; h
 }
 
 
+def _progressive_flags(argv):
+    """-> (positional arguments, chunk, budget, noise): the optional flags --chunk K, --budget SECONDS, --noise EPS, checked here, before any
+    device work (None when absent)"""
+    import math
+    rest, flags = [], {}
+    conv = {"--chunk": int, "--budget": float, "--noise": float}
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        key, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") else (a, None)
+        if key not in conv:
+            rest.append(a)
+            i += 1
+            continue
+        if val is None:
+            if i + 1 >= len(argv):
+                raise SystemExit("%s needs a value" % key)
+            val = argv[i + 1]
+            i += 1
+        i += 1
+        try:
+            v = conv[key](val)
+        except ValueError:
+            raise SystemExit("%s %r is not a number" % (key, val))
+        if key == "--chunk" and v <= 0:
+            raise SystemExit("--chunk must be a positive number of samples (got %d)" % v)
+        if key != "--chunk" and not (math.isfinite(v) and v >= 0):
+            raise SystemExit("%s must be a finite number >= 0 (got %r)" % (key, val))
+        flags[key] = v
+    return rest, flags.get("--chunk"), flags.get("--budget"), flags.get("--noise")
+
+
+def _show_progress(tstart, k, ns):
+    """display.clj:20-24 after a chunk: elapsed, percent done, ETA"""
+    elapsed = time.time() - tstart
+    pct = k / ns
+    print("%.2fs, %d%%, ETA %.2fs" % (elapsed, int(100.0 * pct), elapsed * (1 - pct) / pct), flush=True)
+    return elapsed
+
+
 def main(argv=None):
     """lein-run compatible: `name nx ny ns [win|scene]` (core.clj:73-80).  The reference picks its scene by editing the
     source (core.clj:82-90); here the 5th argument names it (default: the cover scene; "true"/"win", the reference's
-    window switch, is accepted and ignored -- there is no display on this path)."""
+    window switch, is accepted and ignored -- there is no display on this path).
+    Optional flags: --chunk K renders the frame progressively in chunks of K samples and prints the reference's progress line
+    (display.clj:20-24) after each; --budget SECONDS stops after the first chunk that ends past the budget; --noise EPS stops after the
+    first chunk at which 99 % of the pixels have a standard error <= EPS (--budget / --noise alone: chunks of 16).  ns stays the cap; the
+    image after k samples is the one-shot render's with ns = k."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
+    argv, chunk, budget, noise = _progressive_flags(argv)
+    if chunk is None and (budget is not None or noise is not None):
+        chunk = 16
     name = argv[0] if len(argv) > 0 else "render.png"  # core.clj:76
     nx = int(argv[1]) if len(argv) > 1 else 200
     ny = int(argv[2]) if len(argv) > 2 else 100
@@ -384,9 +473,26 @@ def main(argv=None):
         raise SystemExit("unknown scene %r; one of %s" % (which, ", ".join(sorted(SCENES))))
     tstart = time.time()
     sc = SCENES[which](scenes, nx, ny)
-    lin, rgb8, cnt = render(sc, nx, ny, nr)
-    elapsed = time.time() - tstart
-    print("%.2fs, %d%%, ETA %.2fs" % (elapsed, 100, 0.0))  # display.clj:20-24
+    if chunk is None:
+        lin, rgb8, cnt = render(sc, nx, ny, nr)
+        elapsed = time.time() - tstart
+        print("%.2fs, %d%%, ETA %.2fs" % (elapsed, 100, 0.0))  # display.clj:20-24
+    else:
+        ds = DeviceScene(sc)
+        try:
+            for k, lin, rgb8, err, cnt in ds.refine(nx, ny, nr, chunk):
+                elapsed = _show_progress(tstart, k, nr)
+                why = None
+                if budget is not None and elapsed > budget:
+                    why = "budget %gs" % budget
+                elif noise is not None and np.mean(err <= noise) >= 0.99:
+                    why = "noise %g" % noise
+                if why and k < nr:
+                    print("stopped at %d of %d samples (%s)" % (k, nr, why))
+                    break
+        finally:
+            ds.ctx.progressive_release()
+            ds.close()
     print("total-rays %d total-pixels %d" % (int(cnt[0]), int(cnt[1])))  # metrics.clj:8-9
     if name.lower().endswith(".ppm"):
         save_ppm(name, rgb8)

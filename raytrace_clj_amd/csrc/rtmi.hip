@@ -784,6 +784,113 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
 
+// ---- progressive frame kernels (rtmi_render_progressive*) ----------------------------------------------------------------------------------------
+// The frame's state is tile-major like c->accum: element l + 64 k of local tile t (pixel (l + 64 k) / 3 of the tile, channel (l + 64 k) % 3) sits at
+// t * 192 + l + 64 k in three arrays: the running sum of the samples in R (what reduce_kernel keeps between passes), and, in double whatever R is,
+// Welford's running mean and M2 of the same samples (the noise estimate; the image never reads them).
+
+// One pass of the sample buffer, samples [s_begin, s_begin + s_count), folded into the state: the sums with reduce_kernel's fold (same order, the
+// first sample of the frame is the start value), the noise state with Welford's update.  Lane l of a tile's wave owns elements l, l + 64, l + 128
+// of the tile's row, so every load is contiguous.  Elements outside the region keep 0.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) progressive_fold_kernel(const R *__restrict__ samples, R *__restrict__ sums, double *__restrict__ mean,
+                                                                  double *__restrict__ m2, const int *__restrict__ tile_ids, int tiles_x, int n_local_tiles,
+                                                                  int s_begin, int s_count, u64 *counters, u64 n_valid_pixels, int rx0, int ry0, int rx1, int ry1) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid == 0) counters[1] = n_valid_pixels; // metrics total-pixels, core.clj:47
+    if (gid >= (long long)n_local_tiles * 64) return;
+    const int tile_local = (int)(gid >> 6), l = (int)(gid & 63);
+    const int gtile = tile_ids[tile_local];
+    const int tx = (gtile % tiles_x) * RTMI_TILE, ty = (gtile / tiles_x) * RTMI_TILE;
+    R acc[3];
+    double mu[3], q[3];
+    bool valid[3];
+    const size_t tile_base = (size_t)tile_local * 192;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int p = (l + 64 * k) / 3;
+        const int x = tx + (p & 7), y = ty + (p >> 3);
+        valid[k] = x >= rx0 && x < rx1 && y >= ry0 && y < ry1;
+        const bool carry = valid[k] && s_begin > 0;
+        const size_t o = tile_base + l + 64 * k;
+        acc[k] = carry ? sums[o] : R(0);
+        mu[k] = carry ? mean[o] : 0.0;
+        q[k] = carry ? m2[o] : 0.0;
+    }
+    const R *row = samples + (size_t)tile_local * s_count * 192 + l;
+    for (int s = 0; s < s_count; ++s, row += 192) {
+        const R v[3] = {row[0], row[64], row[128]};
+        if (s_begin + s == 0) { // the fold starts FROM the first sample (not 0 + first)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { acc[k] = v[k]; mu[k] = (double)v[k]; q[k] = 0.0; }
+        } else {
+            const double n = (double)(s_begin + s + 1);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                acc[k] = acc[k] + v[k];
+                const double x = (double)v[k], d = x - mu[k];
+                mu[k] = mu[k] + d / n;
+                q[k] = q[k] + d * (x - mu[k]); // >= 0 up to rounding; exactly 0 while every sample is equal
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const size_t o = tile_base + l + 64 * k;
+        sums[o] = valid[k] ? acc[k] : R(0);
+        mean[o] = valid[k] ? mu[k] : 0.0;
+        m2[o] = valid[k] ? q[k] : 0.0;
+    }
+}
+
+// The state after k samples -> the dense region [x0, x0 + w) x [y0, y0 + h) of the frame (its local tiles are the window [tx0, tx0 + wtx) x ..., row-major):
+// out_linear = the mean as reduce_kernel's last pass computes it, out_rgb8 = assemble_kernel<double>'s quantiser of that mean, out_stderr = per pixel the
+// largest of the three channels' standard errors of the mean, sqrt((M2 / (k - 1)) / k) (+inf for k = 1).  Any output may be null.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) progressive_resolve_kernel(const R *__restrict__ sums, const double *__restrict__ m2, int k, int tx0, int ty0,
+                                                                     int wtx, int x0, int y0, int w, int h, double *__restrict__ out_linear,
+                                                                     unsigned char *__restrict__ out_rgb8, double *__restrict__ out_stderr) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)w * h) return;
+    const int x = x0 + (int)(gid % w), y = y0 + (int)(gid / w);
+    const int t = (y / RTMI_TILE - ty0) * wtx + (x / RTMI_TILE - tx0);
+    const int l = (y % RTMI_TILE) * RTMI_TILE + (x % RTMI_TILE);
+    const size_t e = ((size_t)t * 64 + l) * 3;
+    double err = k > 1 ? 0.0 : INFINITY;
+    for (int c = 0; c < 3; ++c) {
+        const double m = (double)(sums[e + c] * (R(1.0) / (R)k)); // reduce_kernel's last pass
+        if (out_linear) out_linear[gid * 3 + c] = m;
+        if (out_rgb8) { // assemble_kernel<double>
+            const double q = Real<double>::sqrt_(m) * 255.99;
+            unsigned char o = 0;
+            if (q == q) { const double mq = q < 255.99 ? q : 255.99; o = (unsigned char)(int)mq; }
+            out_rgb8[gid * 3 + c] = o;
+        }
+        if (k > 1) {
+            const double se = ::sqrt((m2[e + c] / (double)(k - 1)) / (double)k);
+            err = se > err ? se : err;
+        }
+    }
+    if (out_stderr) out_stderr[gid] = err;
+}
+
+// What a progressive frame was started with: a continuation must match it field for field
+struct ProgKey {
+    uint64_t scene_serial = 0, scene_revision = 0, seed = 0;
+    int nx = 0, ny = 0, depth = 0, precision = 0;
+    int rg[4] = {0, 0, 0, 0};
+};
+
+// A context's progressive frame (rtmi_render_progressive*): the state progressive_fold_kernel keeps (sums in the precision of the frame, Welford
+// mean / M2 in double), the cumulative metrics counters, and the key; k = samples [0, k) it holds (0 = no frame).  Its own buffers: a one-shot
+// render on the same context in between does not touch it.
+struct ProgFrame {
+    DevBuf sums, mean, m2, counters;
+    ProgKey key;
+    int k = 0;
+    void release() { sums.release(); mean.release(); m2.release(); counters.release(); k = 0; }
+};
+
 } // namespace
 
 struct rtmi_ctx {
@@ -828,6 +935,7 @@ struct rtmi_ctx {
     int suspend_lanes = 8;        // option "suspend_lanes": threshold of the time-sliced BVH traversal (0 = plain while-while loop); 6 .. 12 within 0.4 % (C3 69.3 / 69.2 / 69.5 ms at 6 / 10 / 12; 18: 70.7, 24: 73.6)
     hipStream_t last_stream = nullptr; // stream of the most recent render (rtmi_last_traversal_counters synchronises on it)
     long long tile_valid_pixels = 0;
+    ProgFrame prog; // at most one progressive frame per context
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     int events_used = 0;
@@ -846,6 +954,8 @@ struct rtmi_scene {
     bool uses_perlin = false; // a Perlin texture is present: rtmi_scene_set_perlin must have been called before rendering
     int max_image = -1;       // highest ImageMap index: rtmi_scene_set_images must cover it
     bool have_perlin = false;
+    uint64_t serial = 0;      // creation serial (a scene created at a destroyed scene's address is still another scene: progressive frame key)
+    uint64_t revision = 0;    // incremented by every rtmi_scene_set_* call that changes the scene
     std::vector<int> host_kind; // primitive kinds (boundary flag removed), for argument checks
     std::map<int, std::array<double, 5>> media_fast_of; // medium primitive -> {density, c.xyz, r*r} when it and its boundary are one plain sphere without wrappers (DevScene::media_fast)
     // the caller's arrays, copied at creation (the library keeps no host POINTERS): what rtmi_scene_clone replicates
@@ -863,6 +973,7 @@ namespace {
 
 bool ctx_ok(rtmi_ctx *c) { return c && c->magic == 0x52544d49u; }
 bool scene_ok(rtmi_scene *s) { return s && s->magic == 0x52545343u && ctx_ok(s->ctx); }
+std::atomic<uint64_t> g_scene_serial{0}; // rtmi_scene::serial
 
 // one scene table: its host copy and the DevScene field that receives its device address
 struct Table {
@@ -1053,9 +1164,13 @@ int report_phase_stamps(rtmi_ctx *c, hipStream_t st) {
 }
 #endif
 
+// The sample passes of a render: samples [s_first, s_end) of every pixel of the local tiles, as many per pass as the sample buffer holds, each pass one
+// trace launch followed by its fold.  A one-shot render (prog = null) runs samples [0, ns) and reduce_kernel folds them into c->accum and, on the last
+// pass, the mean into d_tiles_linear.  A progressive call (prog = the context's frame) folds them into the frame with progressive_fold_kernel; the trace
+// kernel counts its rays into the frame's counters.  A progressive call that fails once it got past the test hook has dropped its frame (k = 0).
 template <typename R>
-int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t seed, int first, int stride, const int *rg, void *d_tiles_linear,
-                      void *d_counters, hipStream_t st) {
+int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int depth, uint64_t seed, int first, int stride, const int *rg, void *d_tiles_linear,
+                  void *d_counters, hipStream_t st, ProgFrame *prog) {
     rtmi_ctx *c = s->ctx;
     int n_local = 0;
     const int whole[4] = {0, 0, nx, ny};
@@ -1064,15 +1179,31 @@ int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t
     if (rc) return rc;
     c->last_stream = st;
     if (c->fail_next_render) { c->fail_next_render = 0; return fail(RTMI_E_DEVICE, "render failed (injected by the test hook test_fail_next_render)"); }
+    if (prog) { // from here on the frame is being changed: it only holds samples again once this call has succeeded
+        prog->k = 0;
+        const size_t elems = (size_t)std::max(n_local, 1) * 192;
+        if (s_first == 0) {
+            rc = prog->sums.ensure(elems * sizeof(R));
+            if (!rc) rc = prog->mean.ensure(elems * sizeof(double));
+            if (!rc) rc = prog->m2.ensure(elems * sizeof(double));
+            if (!rc) rc = prog->counters.ensure(2 * sizeof(u64));
+            if (rc) return rc;
+            HIP_TRY(hipMemsetAsync(prog->counters.p, 0, 2 * sizeof(u64), st));
+        } else if (prog->sums.bytes < elems * sizeof(R) || prog->m2.bytes < elems * sizeof(double)) {
+            return fail(RTMI_E_STATE, "progressive frame buffers do not match the frame"); // (the key check makes this unreachable)
+        }
+        d_counters = prog->counters.p;
+    }
     rc = c->counters.ensure(8 * sizeof(u64)); // [0..1] the metrics when the caller passes no buffer, [2] the work-queue head, [3..4] traversal counters
     if (rc) return rc;
-    if (d_counters) HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(u64), st));
+    if (d_counters && !prog) HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(u64), st));
     HIP_TRY(hipMemsetAsync(reinterpret_cast<u64 *>(c->counters.p) + 3, 0, 2 * sizeof(u64), st));
     if (n_local == 0) return RTMI_OK;
     u64 *cnt = d_counters ? reinterpret_cast<u64 *>(d_counters) : reinterpret_cast<u64 *>(c->counters.p);
     unsigned *queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 2);
 
     // sample-buffer passes: samples [s_begin, s_begin+s_count) of every local pixel per pass
+    const int ns = s_end - s_first; // samples this call renders
     const size_t per_sample = (size_t)n_local * 64 * 3 * sizeof(R);
     int s_per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(ns, c->workspace_bytes / (int64_t)per_sample));
     // the work queue is indexed with 32 bits: items per pass (+ one claim per wave past the end) must stay below 2^32
@@ -1099,7 +1230,7 @@ int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t
         }
     }
     c->last_passes = (ns + s_per_pass - 1) / s_per_pass;
-    if (s_per_pass < ns) {
+    if (!prog && s_per_pass < ns) {
         rc = c->accum.ensure((size_t)n_local * 64 * 3 * sizeof(R));
         if (rc) return rc;
     }
@@ -1109,8 +1240,8 @@ int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t
     const TracePlan plan = choose_trace_kernel<R>(s, c, read_launch_knobs(), nptiles > 1, lds_bytes);
     c->last_accel = plan.accel;
 
-    for (int s_begin = 0; s_begin < ns; s_begin += s_per_pass) {
-        const int s_count = std::min(s_per_pass, ns - s_begin);
+    for (int s_begin = s_first; s_begin < s_end; s_begin += s_per_pass) {
+        const int s_count = std::min(s_per_pass, s_end - s_begin);
         TraceParams tp;
         tp.nx = nx; tp.ny = ny; tp.depth = depth; tp.seed = seed; tp.tiles_x = tiles_x_of(nx);
         tp.n_local_tiles = n_local; tp.tile_ids = reinterpret_cast<const int *>(c->tile_ids.p);
@@ -1156,10 +1287,16 @@ int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t
         HIP_TRY(hipGetLastError());
         if (e1) HIP_TRY(hipEventRecord(e1, st));
         const long long npx = (long long)n_local * 64;
-        hipLaunchKernelGGL((reduce_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                           reinterpret_cast<const R *>(c->samples.p), reinterpret_cast<R *>(c->accum.p),
-                           reinterpret_cast<double *>(d_tiles_linear), reinterpret_cast<const int *>(c->tile_ids.p), tiles_x_of(nx), nx, ny,
-                           n_local, s_begin, s_count, ns, d_counters ? cnt : nullptr, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1);
+        if (prog)
+            hipLaunchKernelGGL((progressive_fold_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                               reinterpret_cast<const R *>(c->samples.p), reinterpret_cast<R *>(prog->sums.p), reinterpret_cast<double *>(prog->mean.p),
+                               reinterpret_cast<double *>(prog->m2.p), reinterpret_cast<const int *>(c->tile_ids.p), tiles_x_of(nx), n_local,
+                               s_begin, s_count, cnt, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1);
+        else
+            hipLaunchKernelGGL((reduce_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                               reinterpret_cast<const R *>(c->samples.p), reinterpret_cast<R *>(c->accum.p),
+                               reinterpret_cast<double *>(d_tiles_linear), reinterpret_cast<const int *>(c->tile_ids.p), tiles_x_of(nx), nx, ny,
+                               n_local, s_begin, s_count, ns, d_counters ? cnt : nullptr, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1);
         HIP_TRY(hipGetLastError());
         if (e1) { // timing: the reduction is the interval from the trace kernel's end event to this one
             const size_t k = (size_t)c->events_used - 1;
@@ -1170,7 +1307,14 @@ int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t
 #ifdef RTMI_STAMPS
     rc = report_phase_stamps(c, st);
 #endif
+    if (!rc && prog) prog->k = s_end;
     return rc;
+}
+
+template <typename R>
+int render_tiles_impl(rtmi_scene *s, int nx, int ny, int ns, int depth, uint64_t seed, int first, int stride, const int *rg, void *d_tiles_linear,
+                      void *d_counters, hipStream_t st) {
+    return render_passes<R>(s, nx, ny, 0, ns, depth, seed, first, stride, rg, d_tiles_linear, d_counters, st, nullptr);
 }
 
 int check_render_args(rtmi_scene *s, int nx, int ny, int ns, int depth, int precision) {
@@ -1219,7 +1363,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 204; } // 204: rtmi_probe_math2 (explicit slot count; rtmi_probe_math writes 8 values per triple again)
+RTMI_EXPORT int rtmi_version(void) { return 205; } // 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -1257,6 +1401,7 @@ RTMI_EXPORT int rtmi_shutdown(rtmi_ctx *c) {
     { unsigned long long h[200]; if (hipMemcpyFromSymbol(h, HIP_SYMBOL(rtmi::g_hist), sizeof h) == hipSuccess) { for (int k = 0; k < 3; ++k) { fprintf(stderr, "HIST%d", k); for (int i = 0; i <= 64; ++i) fprintf(stderr, " %llu", h[64 * k + i]); fprintf(stderr, "\n"); } } }
 #endif
     c->samples.release(); c->accum.release(); c->tiles.release(); c->tile_ids.release(); c->counters.release(); c->scratch_lin.release(); c->multi.release();
+    c->prog.release();
     for (hipEvent_t e : {c->ev_done, c->ev_g0, c->ev_g1}) if (e) (void)hipEventDestroy(e);
     if (c->ev_consumed) { (void)hipSetDevice(c->ev_consumed_device); (void)hipEventDestroy(c->ev_consumed); (void)hipSetDevice(c->device); }
     for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -1398,6 +1543,7 @@ RTMI_EXPORT int rtmi_scene_create_ex(rtmi_ctx *c, int32_t n_prims, const int32_t
     if (!s) return fail(RTMI_E_NOMEM, "out of host memory");
     const PackedScene P = pack_scene(a, knobs);
     s->ctx = c; s->n_prims = n_prims; s->n_mats = n_mats; s->n_tex = n_tex;
+    s->serial = ++g_scene_serial;
     s->uses_perlin = P.uses_perlin; s->max_image = P.max_image; s->bvh_node_count = P.bvh_node_count; s->bvh_depth = P.bvh_depth;
     s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of; s->dev = P.d;
     DevScene &d = s->dev;
@@ -1456,6 +1602,7 @@ RTMI_EXPORT int rtmi_scene_set_perlin(rtmi_scene *s, const double *vectors, cons
         }
     }
     HIP_TRY(hipSetDevice(s->ctx->device));
+    s->revision++;
     std::vector<double> v(vectors, vectors + 768);
     std::vector<int> p(perm, perm + 768);
     int rc = upload(s, Table(v, &s->dev.perlin_vec));
@@ -1473,6 +1620,7 @@ RTMI_EXPORT int rtmi_scene_set_media_calls(rtmi_scene *s, int32_t n_calls, const
         if (calls[k] < 0 || calls[k] >= s->n_prims || s->host_kind[(size_t)calls[k]] != RTMI_PRIM_MEDIUM) return fail(RTMI_E_ARG, "calls[%d] = %d is not a medium primitive", k, calls[k]);
     if (s->dev.media_seq == 1)
         for (int k = 1; k < n_calls; ++k) if (calls[k] <= calls[k - 1]) return fail(RTMI_E_ARG, "RTMI_MEDIA_HITLIST: the media must be called once each, in ascending primitive (= list) order");
+    s->revision++;
     if (s->dev.media_seq == 2) { s->dev.media_seq = 0; s->args.media_mode = 0; } // a plain call sequence replaces a narrowed one
     s->dev.n_media = n_calls;
     for (int k = 0; k < n_calls; ++k) { s->dev.media_idx[k] = calls[k]; s->dev.media_lo[k] = calls[k]; }
@@ -1491,6 +1639,7 @@ RTMI_EXPORT int rtmi_scene_set_media_calls_narrowed(rtmi_scene *s, int32_t n_cal
         if (k > 0 && narrow_from[k] < calls[k] && narrow_from[k] == narrow_from[k - 1] && calls[k] <= calls[k - 1])
             return fail(RTMI_E_ARG, "calls %d and %d share a narrowing Hitlist and must come in list order", k - 1, k);
     }
+    s->revision++;
     s->dev.n_media = n_calls;
     bool any = false;
     for (int k = 0; k < n_calls; ++k) { s->dev.media_idx[k] = calls[k]; s->dev.media_lo[k] = narrow_from[k]; any = any || narrow_from[k] < calls[k]; }
@@ -1507,6 +1656,7 @@ RTMI_EXPORT int rtmi_scene_set_media_mode(rtmi_scene *s, int32_t mode) {
     if (mode == RTMI_MEDIA_HITLIST)
         for (int k = 1; k < s->dev.n_media; ++k)
             if (s->dev.media_idx[k] <= s->dev.media_idx[k - 1]) return fail(RTMI_E_ARG, "RTMI_MEDIA_HITLIST: the media must be called once each, in ascending primitive (= list) order");
+    s->revision++;
     s->dev.media_seq = mode == RTMI_MEDIA_HITLIST ? 1 : 0;
     s->args.media_mode = mode;
     HIP_TRY(hipSetDevice(s->ctx->device));
@@ -1526,6 +1676,7 @@ RTMI_EXPORT int rtmi_scene_set_images(rtmi_scene *s, int32_t n_images, const int
         total += (long long)wh[2 * i] * wh[2 * i + 1] * 3;
     }
     HIP_TRY(hipSetDevice(s->ctx->device));
+    s->revision++;
     std::vector<unsigned char> px(rgb, rgb + total);
     int rc = upload(s, Table(whv, &s->dev.image_wh));
     if (!rc) rc = upload(s, Table(off, &s->dev.image_off));
@@ -1636,6 +1787,127 @@ RTMI_EXPORT int rtmi_render(rtmi_scene *s, int32_t nx, int32_t ny, int32_t ns, i
     if (out_linear) HIP_TRY(hipMemcpy(out_linear, d_lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_q, npx * 3, hipMemcpyDeviceToHost));
     if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---- progressive rendering: a frame refined over calls ----------------------------------------------------------------
+namespace {
+// the checks of a progressive call; failing one leaves the context's frame as it was
+int check_progressive_args(rtmi_scene *s, int nx, int ny, int s_first, int s_count, int depth, int precision) {
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    if (s_first < 0 || s_count <= 0) return fail(RTMI_E_ARG, "s_first must be >= 0 and s_count > 0 (got %d, %d)", s_first, s_count);
+    if ((long long)s_first + s_count > INT32_MAX) return fail(RTMI_E_ARG, "s_first + s_count = %d + %d overflows int32", s_first, s_count);
+    return check_render_args(s, nx, ny, s_count, depth, precision);
+}
+
+ProgKey progressive_key(const rtmi_scene *s, int nx, int ny, int depth, uint64_t seed, int precision, const int *rg) {
+    ProgKey k;
+    k.scene_serial = s->serial; k.scene_revision = s->revision; k.seed = seed;
+    k.nx = nx; k.ny = ny; k.depth = depth; k.precision = precision;
+    for (int i = 0; i < 4; ++i) k.rg[i] = rg[i];
+    return k;
+}
+
+// s_first > 0 continues the context's frame: it must hold exactly s_first samples of the same key
+int check_continuation(const rtmi_ctx *c, const ProgKey &k, int s_first) {
+    if (s_first == 0) return RTMI_OK;
+    const ProgFrame &f = c->prog;
+    const ProgKey &a = f.key;
+    if (f.k == 0) return fail(RTMI_E_STATE, "s_first = %d continues a progressive frame, but the context holds none (s_first = 0 starts one)", s_first);
+    if (s_first != f.k) return fail(RTMI_E_STATE, "s_first = %d, but the context's progressive frame holds samples [0, %d)", s_first, f.k);
+    if (k.scene_serial != a.scene_serial) return fail(RTMI_E_STATE, "the progressive frame was started with another scene");
+    if (k.scene_revision != a.scene_revision) return fail(RTMI_E_STATE, "the scene was changed (rtmi_scene_set_*) after the progressive frame was started");
+    if (k.nx != a.nx || k.ny != a.ny) return fail(RTMI_E_STATE, "nx x ny = %d x %d, the progressive frame is %d x %d", k.nx, k.ny, a.nx, a.ny);
+    if (k.depth != a.depth) return fail(RTMI_E_STATE, "depth = %d, the progressive frame was started with %d", k.depth, a.depth);
+    if (k.seed != a.seed) return fail(RTMI_E_STATE, "seed = %llu, the progressive frame was started with %llu", (unsigned long long)k.seed, (unsigned long long)a.seed);
+    if (k.precision != a.precision) return fail(RTMI_E_STATE, "precision = %d, the progressive frame was started with %d", k.precision, a.precision);
+    if (std::memcmp(k.rg, a.rg, sizeof k.rg))
+        return fail(RTMI_E_STATE, "region [%d,%d)x[%d,%d), the progressive frame was started with [%d,%d)x[%d,%d)", k.rg[0], k.rg[2], k.rg[1], k.rg[3], a.rg[0], a.rg[2], a.rg[1], a.rg[3]);
+    return RTMI_OK;
+}
+
+// Adds samples [s_first, s_first + s_count) to the context's frame (s_first = 0: a new frame), then resolves the state into the region's outputs
+// (device pointers, any may be null) and copies the cumulative counters to d_cnt, all on `st`.
+template <typename R>
+int render_progressive_impl(rtmi_scene *s, const ProgKey &key, int s_first, int s_count, double *d_lin, unsigned char *d_q, double *d_err, void *d_cnt,
+                            hipStream_t st) {
+    ProgFrame &f = s->ctx->prog;
+    int rc = render_passes<R>(s, key.nx, key.ny, s_first, s_first + s_count, key.depth, key.seed, 0, 1, key.rg, nullptr, nullptr, st, &f);
+    if (rc) return rc;
+    f.key = key;
+    const int x0 = key.rg[0], y0 = key.rg[1], w = key.rg[2] - x0, h = key.rg[3] - y0;
+    const int tx0 = x0 / RTMI_TILE, ty0 = y0 / RTMI_TILE, wtx = (key.rg[2] + RTMI_TILE - 1) / RTMI_TILE - tx0; // the local tiles of the region: this window, row-major
+    const long long npx = (long long)w * h;
+    hipError_t e = hipSuccess;
+    if (d_lin || d_q || d_err) {
+        hipLaunchKernelGGL((progressive_resolve_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                           reinterpret_cast<const R *>(f.sums.p), reinterpret_cast<const double *>(f.m2.p), f.k, tx0, ty0, wtx, x0, y0, w, h, d_lin, d_q, d_err);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && d_cnt) e = hipMemcpyAsync(d_cnt, f.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) { f.k = 0; return fail(RTMI_E_DEVICE, "progressive resolve: %s", hipGetErrorString(e)); }
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_progressive_device(rtmi_scene *s, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                               int32_t precision, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_counters, void *stream) {
+    int rc = check_progressive_args(s, nx, ny, s_first, s_count, depth, precision);
+    if (rc) return rc;
+    const int whole[4] = {0, 0, nx, ny};
+    const ProgKey key = progressive_key(s, nx, ny, depth, seed, precision, whole);
+    rc = check_continuation(s->ctx, key, s_first);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
+    double *lin = reinterpret_cast<double *>(d_out_linear), *err = reinterpret_cast<double *>(d_out_stderr);
+    unsigned char *q = reinterpret_cast<unsigned char *>(d_out_rgb8);
+    if (precision == RTMI_F64) return render_progressive_impl<double>(s, key, s_first, s_count, lin, q, err, d_out_counters, st);
+    return render_progressive_impl<float>(s, key, s_first, s_count, lin, q, err, d_out_counters, st);
+}
+
+RTMI_EXPORT int rtmi_render_progressive(rtmi_scene *s, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                        int32_t precision, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                                        double *out_linear, uint8_t *out_rgb8, double *out_stderr, uint64_t *out_counters) {
+    int rc = check_progressive_args(s, nx, ny, s_first, s_count, depth, precision);
+    if (rc) return rc;
+    if (x0 < 0 || y0 < 0 || x1 > nx || y1 > ny || x1 <= x0 || y1 <= y0) return fail(RTMI_E_ARG, "region [%d,%d)x[%d,%d) outside %dx%d", x0, x1, y0, y1, nx, ny);
+    const int rg[4] = {x0, y0, x1, y1};
+    const ProgKey key = progressive_key(s, nx, ny, depth, seed, precision, rg);
+    rtmi_ctx *c = s->ctx;
+    rc = check_continuation(c, key, s_first);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npx = (size_t)(x1 - x0) * (size_t)(y1 - y0);
+    rc = c->scratch_lin.ensure(npx * 3 * sizeof(double) + npx * sizeof(double) + npx * 3 + 64);
+    if (rc) return rc;
+    char *base = reinterpret_cast<char *>(c->scratch_lin.p);
+    double *d_lin = reinterpret_cast<double *>(base), *d_err = reinterpret_cast<double *>(base + npx * 3 * sizeof(double));
+    unsigned char *d_q = reinterpret_cast<unsigned char *>(base + npx * 4 * sizeof(double));
+    hipStream_t st = c->stream;
+    if (precision == RTMI_F64) rc = render_progressive_impl<double>(s, key, s_first, s_count, d_lin, d_q, d_err, nullptr, st);
+    else rc = render_progressive_impl<float>(s, key, s_first, s_count, d_lin, d_q, d_err, nullptr, st);
+    if (rc) return rc;
+    hipError_t e = hipStreamSynchronize(st);
+    if (e == hipSuccess && out_linear) e = hipMemcpy(out_linear, d_lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_rgb8) e = hipMemcpy(out_rgb8, d_q, npx * 3, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_stderr) e = hipMemcpy(out_stderr, d_err, npx * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_counters) e = hipMemcpy(out_counters, c->prog.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { c->prog.k = 0; return fail(RTMI_E_DEVICE, "progressive render: %s", hipGetErrorString(e)); }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_progressive_samples(rtmi_ctx *c, int32_t *samples) {
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    if (samples) *samples = c->prog.k;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_progressive_release(rtmi_ctx *c) {
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->prog.release();
     return RTMI_OK;
 }
 
