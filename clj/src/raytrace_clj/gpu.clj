@@ -351,6 +351,44 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn render-adaptive
+  "Render scene {:camera :world} adaptively on GPU `device` (rtmi_render_adaptive): a first round of :first-round samples (default: chunk), then
+  rounds of `chunk` samples up to ns per pixel.  After every round each 8x8 tile whose pixels all have a standard error <= eps stops taking
+  samples; the render ends when no tile is active or at ns.  After each round (on-round m), m = {:samples k :rgb8 :linear :stderr
+  :pixel-samples (int-array, the samples behind every pixel) :total-rays :total-pixels :active-tiles :total-tiles}; a pixel whose tile holds n
+  samples equals `render` with ns = n there, bit for bit.  The arrays are refilled by the next round.  on-round returning :stop ends the
+  render early.  Returns the last m."
+  [scene nx ny ns chunk eps on-round & {:keys [first-round depth seed device precision] :or {depth 50 seed 0x5eed0002 device 0 precision 0}}]
+  (let [f     (flatten-scene scene)
+        ctx   (PointerByReference.)
+        npx   (* nx ny)
+        lin   (double-array (* 3 npx))
+        rgb   (byte-array (* 3 npx))
+        err   (double-array npx)
+        smp   (int-array npx)
+        cnt   (long-array 2)
+        act   (int-array 1)
+        tot   (int-array 1)
+        pxs   (long-array 1)
+        head  (or first-round chunk)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (loop [k 0]
+            (let [n (min (if (zero? k) head chunk) (- ns k))]
+              (check (call-int "rtmi_render_adaptive" scn (int nx) (int ny) (int k) (int n) (double eps) (int depth) (long seed) (int precision)
+                               (int 0) (int 0) (int nx) (int ny) lin rgb err smp cnt))
+              (check (call-int "rtmi_adaptive_status" (.getValue ctx) act tot pxs))
+              (let [k' (+ k n)
+                    m  {:samples k' :rgb8 rgb :linear lin :stderr err :pixel-samples smp :total-rays (aget cnt 0) :total-pixels (aget cnt 1)
+                        :active-tiles (aget act 0) :total-tiles (aget tot 0)}]
+                (if (and (not= :stop (on-round m)) (< k' ns) (pos? (aget act 0)))
+                  (recur k')
+                  m))))
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn render-multi
   "The same on every GPU in `devices` from this one JVM (rtmi_render_multi): one context per device, the scene created on
   the first (Perlin tables, ImageMap pixels and media calls included) and cloned onto the others (rtmi_scene_clone), the 8x8

@@ -234,6 +234,50 @@ int rtmi_render_progressive_device(rtmi_scene *scene, int32_t nx, int32_t ny, in
 int rtmi_progressive_samples(rtmi_ctx *ctx, int32_t *samples); /* k of the context's progressive frame, 0 = none */
 int rtmi_progressive_release(rtmi_ctx *ctx);                   /* drop the frame and free its buffers */
 
+/* ---- adaptive sampling: the progressive frame stops refining 8x8 tiles whose noise is below eps ----
+ * The context's one progressive frame keeps per-tile state: for every local tile t the number of samples it holds, n_t, and whether the tile
+ * is still ACTIVE.  A frame started by rtmi_render_progressive is the special case where every tile is active with n_t = k.
+ * rtmi_render_adaptive*(..., s_first, s_count, eps, ...) does two things, in this order:
+ *   1. it adds samples [s_first, s_first + s_count) to every tile that is active when the call starts: the ordinary trace launches (the same
+ *      kernel choice, pass loop and "workspace_bytes" splitting) over the compacted list of active tiles, in ascending tile order.  Retired
+ *      tiles are not traced, folded or touched;
+ *   2. it then retires tiles: with k = s_first + s_count an active tile is RETIRED if k >= 2 and every pixel of the tile that lies inside the
+ *      image and the region passes: the value rtmi_render_progressive would report in out_stderr after k samples -- per channel
+ *      sqrt((M2 / (k - 1)) / k), the resolve's own expression -- is <= eps.  It is compared as se <= eps: a NaN fails and the tile stays
+ *      active.  Retirement is permanent for the life of the frame.  A tile retired by this call keeps the samples this call gave it (n_t = k).
+ * Outputs, each of which may be NULL:
+ *   out_linear / out_rgb8: per pixel the mean over its tile's samples [0, n_t), BIT-IDENTICAL to what rtmi_render returns for that pixel with
+ *                          ns = n_t and the same scene, nx, ny, depth, seed, precision and region (every draw is keyed by (seed, pixel, sample),
+ *                          never by ns: a tile that stopped at n samples holds what the one-shot render with ns = n computes for its pixels);
+ *   out_stderr:            as rtmi_render_progressive's, with n_t in place of k;
+ *   out_samples:           n_t per pixel, int32, pixel order of out_stderr;
+ *   out_counters:          {ray segments of all samples traced into the frame so far, total-pixels of the region}.
+ * s_first == 0 starts a new frame (any previous one is discarded).  s_first > 0 must equal the frame's k, the number of samples OFFERED so far
+ * (rtmi_progressive_samples), and the key must match as for rtmi_render_progressive, else RTMI_E_STATE and rtmi_last_error names what differs.
+ * eps is not part of the key and may change between calls; eps < 0, NaN or infinite: RTMI_E_ARG; eps == 0 retires only tiles whose samples are
+ * all equal.  rtmi_render_adaptive may continue a frame that rtmi_render_progressive started.  rtmi_render_progressive with s_first > 0 on a
+ * frame that has a retired tile returns RTMI_E_STATE (its "equals ns = k" promise cannot hold there) and leaves the frame untouched.  A call
+ * that starts with no active tile launches no trace: RTMI_OK, k advanced, the outputs resolved.  Failures are the progressive call's: before
+ * anything launched the frame stays as it was, after a launch it is dropped.  RTMI_FLAG_TIMING covers these calls; rtmi_progressive_release
+ * and rtmi_shutdown free the per-tile state with the frame.  One-shot renders on the same context may come in between: the frame keeps its own
+ * tile lists. */
+/* host buffers, output region [x0,x1) x [y0,y1) as rtmi_render */
+int rtmi_render_adaptive(rtmi_scene *scene, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, double eps,
+                         int32_t depth, uint64_t seed, int32_t precision, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                         double *out_linear, uint8_t *out_rgb8, double *out_stderr, int32_t *out_samples, uint64_t *out_counters);
+/* device buffers, the whole frame, launched on `stream` with rtmi_render_device's stream semantics.  Unlike rtmi_render_progressive_device this
+ * call synchronises the stream once, at its end: the host needs the length of the next active list to size the next launch and to answer
+ * rtmi_adaptive_status. */
+int rtmi_render_adaptive_device(rtmi_scene *scene, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, double eps,
+                                int32_t depth, uint64_t seed, int32_t precision,
+                                void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_samples, void *d_out_counters, void *stream);
+/* tiles still active, local tiles of the frame, sum over the region's pixels of n_t; zeros without a frame.  Host state only: no device access. */
+int rtmi_adaptive_status(rtmi_ctx *ctx, int32_t *active_tiles, int32_t *total_tiles, int64_t *pixel_samples);
+/* The active list itself: out_count = tiles still active; with out_tiles != NULL (capacity >= that count, else RTMI_E_ARG) their global tile
+ * indices (row-major over ceil(nx/8) x ceil(ny/8)), in ASCENDING order -- the order the next call traces them in.  Copies the list from the
+ * device (an adaptive call has synchronised its stream when it returns).  Without a frame: 0 and RTMI_OK. */
+int rtmi_adaptive_active_tiles(rtmi_ctx *ctx, int32_t capacity, int32_t *out_tiles, int32_t *out_count);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

@@ -27,6 +27,7 @@ SYMBOLS = [
     "rtmi_scene_clone", "rtmi_render_multi", "rtmi_render_multi_device", "rtmi_last_gather_ms",
     "rtmi_last_gather_path", "rtmi_rccl_probe", "rtmi_stream_idle", "rtmi_last_passes", "rtmi_last_accel",
     "rtmi_render_progressive", "rtmi_render_progressive_device", "rtmi_progressive_samples", "rtmi_progressive_release",
+    "rtmi_render_adaptive", "rtmi_render_adaptive_device", "rtmi_adaptive_status", "rtmi_adaptive_active_tiles",
 ]
 
 F64, F32 = 0, 1
@@ -107,6 +108,10 @@ def lib():
     L.rtmi_render_progressive_device.argtypes = [vp, i32, i32, i32, i32, i32, u64, i32, vp, vp, vp, vp, vp]
     L.rtmi_progressive_samples.argtypes = [vp, C.POINTER(i32)]
     L.rtmi_progressive_release.argtypes = [vp]
+    L.rtmi_render_adaptive.argtypes = [vp, i32, i32, i32, i32, dbl, i32, u64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.rtmi_render_adaptive_device.argtypes = [vp, i32, i32, i32, i32, dbl, i32, u64, i32, vp, vp, vp, vp, vp, vp]
+    L.rtmi_adaptive_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
+    L.rtmi_adaptive_active_tiles.argtypes = [vp, i32, vp, C.POINTER(i32)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

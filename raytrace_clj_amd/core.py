@@ -77,6 +77,22 @@ class Context:
         """drop the context's progressive frame and free its buffers"""
         check(_ffi.lib().rtmi_progressive_release(self.handle))
 
+    def adaptive_status(self):
+        """(tiles still active, local tiles of the frame, sum over the region's pixels of the samples their tile holds) of the context's
+        progressive frame; zeros without one.  Host state only."""
+        a, t, n = C.c_int32(), C.c_int32(), C.c_int64()
+        check(_ffi.lib().rtmi_adaptive_status(self.handle, C.byref(a), C.byref(t), C.byref(n)))
+        return a.value, t.value, n.value
+
+    def adaptive_active_tiles(self):
+        """global tile indices (row-major over the 8x8 tiles of the frame) of the tiles still active, int32, ascending"""
+        n = C.c_int32()
+        check(_ffi.lib().rtmi_adaptive_active_tiles(self.handle, 0, None, C.byref(n)))
+        out = np.zeros(n.value, np.int32)
+        if n.value:
+            check(_ffi.lib().rtmi_adaptive_active_tiles(self.handle, n.value, ptr(out), C.byref(n)))
+        return out
+
     def last_traversal_counters(self):
         """(AABB slab tests, exact primitive tests) of the last render; needs set_option("count_traversal", 1) before it
         (metrics.clj:10 aabb.intersection.total, for the device's own tree)"""
@@ -207,6 +223,45 @@ class DeviceScene:
             lin, q, err, cnt = self.render_progressive(nx, ny, k, n, depth, seed, precision, region)
             k += n
             yield k, lin, q, err, cnt
+
+    # ---- adaptive sampling: the frame's 8x8 tiles stop taking samples once their noise is below eps -----------------------------
+    def render_adaptive(self, nx, ny, s_first, s_count, eps, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", region=None):
+        """Add samples [s_first, s_first + s_count) to the active tiles of the context's progressive frame, then retire every tile whose
+        pixels all have a standard error <= eps after k = s_first + s_count >= 2 samples -> (linear, rgb8, stderr [h,w], samples int32 [h,w],
+        counters).  A pixel whose tile holds n samples equals render(ns = n) there bit for bit; counters[0] = the segments traced so far."""
+        x0, y0, x1, y1 = region if region is not None else (0, 0, nx, ny)
+        lin = np.zeros((max(y1 - y0, 0), max(x1 - x0, 0), 3), np.float64)
+        q = np.zeros(lin.shape, np.uint8)
+        err = np.zeros(lin.shape[:2], np.float64)
+        smp = np.zeros(lin.shape[:2], np.int32)
+        cnt = np.zeros(2, np.uint64)
+        check(_ffi.lib().rtmi_render_adaptive(self.handle, nx, ny, s_first, s_count, float(eps), depth, seed, _PRECISION[precision], x0, y0, x1, y1,
+                                              ptr(lin), ptr(q), ptr(err), ptr(smp), ptr(cnt)))
+        return lin, q, err, smp, cnt
+
+    def render_adaptive_device(self, nx, ny, s_first, s_count, eps, out_linear=None, out_rgb8=None, out_stderr=None, out_samples=None,
+                               out_counters=None, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", stream=None):
+        """render_adaptive for the whole frame into HBM-resident buffers (render_device's stream semantics; synchronises the stream once, at the
+        end of the call: the host reads the number of tiles still active)"""
+        check(_ffi.lib().rtmi_render_adaptive_device(self.handle, nx, ny, s_first, s_count, float(eps), depth, seed, _PRECISION[precision],
+                                                     ptr(out_linear), ptr(out_rgb8), ptr(out_stderr), ptr(out_samples), ptr(out_counters), ptr(stream)))
+
+    def refine_adaptive(self, nx, ny, ns, chunk, eps, first=None, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", region=None):
+        """Render adaptively up to ns samples per pixel: a first round of `first` samples (default: chunk; the guard against retiring a tile on
+        two lucky samples), then rounds of `chunk`; yields (k, linear, rgb8, stderr, samples, counters, active tiles) after every round and ends
+        when no tile is active or k reaches ns."""
+        first = chunk if first is None else first
+        if chunk <= 0 or ns <= 0 or first <= 0:
+            raise ValueError("ns, chunk and first must be > 0")
+        k = 0
+        while k < ns:
+            n = min(first if k == 0 else chunk, ns - k)
+            lin, q, err, smp, cnt = self.render_adaptive(nx, ny, k, n, eps, depth, seed, precision, region)
+            k += n
+            active = self.ctx.adaptive_status()[0]
+            yield k, lin, q, err, smp, cnt, active
+            if active == 0:
+                break
 
     def render_tiles_device(self, nx, ny, ns, tile_first, tile_stride, out_tiles, out_counters=None, depth=DEFAULT_DEPTH,
                             seed=RENDER_SEED, precision="f64", stream=None):
@@ -412,11 +467,11 @@ SCENES = {  # the scene choices of core.clj:82-90 (there: commented-out lines; h
 
 
 def _progressive_flags(argv):
-    """-> (positional arguments, chunk, budget, noise): the optional flags --chunk K, --budget SECONDS, --noise EPS, checked here, before any
-    device work (None when absent)"""
+    """-> (positional arguments, chunk, budget, noise, adaptive): the optional flags --chunk K, --budget SECONDS, --noise EPS, --adaptive EPS,
+    checked here, before any device work (None when absent)"""
     import math
     rest, flags = [], {}
-    conv = {"--chunk": int, "--budget": float, "--noise": float}
+    conv = {"--chunk": int, "--budget": float, "--noise": float, "--adaptive": float}
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -440,7 +495,9 @@ def _progressive_flags(argv):
         if key != "--chunk" and not (math.isfinite(v) and v >= 0):
             raise SystemExit("%s must be a finite number >= 0 (got %r)" % (key, val))
         flags[key] = v
-    return rest, flags.get("--chunk"), flags.get("--budget"), flags.get("--noise")
+    if "--adaptive" in flags and "--noise" in flags:
+        raise SystemExit("--adaptive and --noise are two stopping rules: give one of them")
+    return rest, flags.get("--chunk"), flags.get("--budget"), flags.get("--noise"), flags.get("--adaptive")
 
 
 def _show_progress(tstart, k, ns):
@@ -458,11 +515,14 @@ def main(argv=None):
     Optional flags: --chunk K renders the frame progressively in chunks of K samples and prints the reference's progress line
     (display.clj:20-24) after each; --budget SECONDS stops after the first chunk that ends past the budget; --noise EPS stops after the
     first chunk at which 99 % of the pixels have a standard error <= EPS (--budget / --noise alone: chunks of 16).  ns stays the cap; the
-    image after k samples is the one-shot render's with ns = k."""
+    image after k samples is the one-shot render's with ns = k.
+    --adaptive EPS samples adaptively instead (refine_adaptive, rounds of --chunk, default 16): an 8x8 tile stops taking samples once all its
+    pixels have a standard error <= EPS, and the run ends when no tile is left or at ns; every tile equals the one-shot render with the
+    samples it took.  --budget applies; --noise does not combine with it."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
-    argv, chunk, budget, noise = _progressive_flags(argv)
-    if chunk is None and (budget is not None or noise is not None):
+    argv, chunk, budget, noise, adaptive = _progressive_flags(argv)
+    if chunk is None and (budget is not None or noise is not None or adaptive is not None):
         chunk = 16
     name = argv[0] if len(argv) > 0 else "render.png"  # core.clj:76
     nx = int(argv[1]) if len(argv) > 1 else 200
@@ -477,6 +537,19 @@ def main(argv=None):
         lin, rgb8, cnt = render(sc, nx, ny, nr)
         elapsed = time.time() - tstart
         print("%.2fs, %d%%, ETA %.2fs" % (elapsed, 100, 0.0))  # display.clj:20-24
+    elif adaptive is not None:
+        ds = DeviceScene(sc)
+        try:
+            for k, lin, rgb8, err, smp, cnt, active in ds.refine_adaptive(nx, ny, nr, chunk, adaptive):
+                elapsed = _show_progress(tstart, k, nr)
+                if budget is not None and elapsed > budget and k < nr and active:
+                    print("stopped at %d of %d samples (budget %gs)" % (k, nr, budget))
+                    break
+            active, total, pixel_samples = ds.ctx.adaptive_status()
+            print("samples: mean %.2f of %d per pixel, %d of %d tiles converged" % (pixel_samples / max(int(cnt[1]), 1), nr, total - active, total))
+        finally:
+            ds.ctx.progressive_release()
+            ds.close()
     else:
         ds = DeviceScene(sc)
         try:

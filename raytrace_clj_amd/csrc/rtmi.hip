@@ -874,6 +874,163 @@ __global__ void __launch_bounds__(kBlock) progressive_resolve_kernel(const R *__
     if (out_stderr) out_stderr[gid] = err;
 }
 
+// ---- adaptive frame kernels (rtmi_render_adaptive*) -----------------------------------------------------------------------------------------------
+// An adaptive call traces only the frame's active tiles.  The active list is two parallel arrays in ascending tile order: act_tiles[i] = global tile
+// (what the trace kernel takes as tile_ids, so sample-buffer tile i holds entry i's samples) and act_slots[i] = the tile's local tile number, i.e.
+// where its state sits (slot * 192) and what the resolve indexes.  n_t[slot] = samples the tile holds.
+
+// progressive_fold_kernel behind the indirection: the wave of entry i folds sample-buffer tile i into the state at act_slots[i] * 192, same element
+// ownership, same arithmetic.  On the call's last pass (`last`) it also decides: k = s_begin + s_count, the tile stays active (keep[i] = 1) if k < 2
+// or any element of a valid pixel fails se <= eps, se = sqrt((M2 / (k - 1)) / k) as the resolve computes it (a NaN fails); n_t[slot] = k.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) adaptive_fold_kernel(const R *__restrict__ samples, R *__restrict__ sums, double *__restrict__ mean,
+                                                               double *__restrict__ m2, const int *__restrict__ act_tiles, const int *__restrict__ act_slots,
+                                                               int tiles_x, int n_active, int s_begin, int s_count, u64 *counters, u64 n_valid_pixels, int rx0,
+                                                               int ry0, int rx1, int ry1, int last, double eps, int *__restrict__ keep, int *__restrict__ n_t) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid == 0) counters[1] = n_valid_pixels; // metrics total-pixels, core.clj:47
+    if (gid >= (long long)n_active * 64) return; // (whole waves: kBlock is a multiple of 64)
+    const int entry = (int)(gid >> 6), l = (int)(gid & 63);
+    const int gtile = act_tiles[entry], slot = act_slots[entry];
+    const int tx = (gtile % tiles_x) * RTMI_TILE, ty = (gtile / tiles_x) * RTMI_TILE;
+    R acc[3];
+    double mu[3], q[3];
+    bool valid[3];
+    const size_t tile_base = (size_t)slot * 192;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int p = (l + 64 * k) / 3;
+        const int x = tx + (p & 7), y = ty + (p >> 3);
+        valid[k] = x >= rx0 && x < rx1 && y >= ry0 && y < ry1;
+        const bool carry = valid[k] && s_begin > 0;
+        const size_t o = tile_base + l + 64 * k;
+        acc[k] = carry ? sums[o] : R(0);
+        mu[k] = carry ? mean[o] : 0.0;
+        q[k] = carry ? m2[o] : 0.0;
+    }
+    const R *row = samples + (size_t)entry * s_count * 192 + l;
+    for (int s = 0; s < s_count; ++s, row += 192) {
+        const R v[3] = {row[0], row[64], row[128]};
+        if (s_begin + s == 0) { // the fold starts FROM the first sample (not 0 + first)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { acc[k] = v[k]; mu[k] = (double)v[k]; q[k] = 0.0; }
+        } else {
+            const double n = (double)(s_begin + s + 1);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                acc[k] = acc[k] + v[k];
+                const double x = (double)v[k], d = x - mu[k];
+                mu[k] = mu[k] + d / n;
+                q[k] = q[k] + d * (x - mu[k]);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const size_t o = tile_base + l + 64 * k;
+        sums[o] = valid[k] ? acc[k] : R(0);
+        mean[o] = valid[k] ? mu[k] : 0.0;
+        m2[o] = valid[k] ? q[k] : 0.0;
+    }
+    if (!last) return;
+    const int kk = s_begin + s_count;
+    bool noisy = false;
+    if (kk > 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double se = ::sqrt((q[k] / (double)(kk - 1)) / (double)kk); // progressive_resolve_kernel's expression
+            noisy = noisy || (valid[k] && !(se <= eps));
+        }
+    }
+    const u64 any = __ballot(noisy);
+    if (l == 0) { keep[entry] = (kk < 2 || any != 0ull) ? 1 : 0; n_t[slot] = kk; }
+}
+
+// Ordered compaction of the active list, one workgroup of kCompactBlock threads walking the n entries in strides of its size: entry i survives if
+// keep[i] != 0 (keep = null: all survive) and goes to position (survivors before i), so ascending tile order is kept and the result does not depend
+// on timing: ballot + popcount give a lane its rank within the wave, an LDS table of the waves' counts the wave's offset within the stride, a
+// register the running total.  in_slots = null: the identity (the start of a frame: in_tiles = the render's tile list; init_n_t >= 0 then also
+// sets n_t[i]).  meta = {survivors, their pixels inside the image and the region}; ints suffice, a frame has at most 2^30 pixels.
+constexpr int kCompactBlock = 1024;
+__global__ void __launch_bounds__(kCompactBlock) adaptive_compact_kernel(const int *__restrict__ keep, const int *__restrict__ in_tiles,
+                                                                         const int *__restrict__ in_slots, int n, int *__restrict__ out_tiles,
+                                                                         int *__restrict__ out_slots, int *__restrict__ meta, int init_n_t,
+                                                                         int *__restrict__ n_t, int tiles_x, int rx0, int ry0, int rx1, int ry1) {
+    __shared__ int wave_count[kCompactBlock / 64];
+    __shared__ int wave_pixels[kCompactBlock / 64];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int base = 0, pixels = 0;
+    for (int i0 = 0; i0 < n; i0 += kCompactBlock) {
+        const int i = i0 + tid;
+        const bool in = i < n;
+        const bool live = in && (!keep || keep[i] != 0);
+        const u64 mask = __ballot(live);
+        const int rank = (int)__popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_count[wave] = (int)__popcll(mask);
+        __syncthreads();
+        int offset = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kCompactBlock / 64; ++w) {
+            const int cw = wave_count[w];
+            offset += w < wave ? cw : 0;
+            total += cw;
+        }
+        if (live) {
+            const int g = in_tiles[i], slot = in_slots ? in_slots[i] : i;
+            const int o = base + offset + rank;
+            out_tiles[o] = g;
+            out_slots[o] = slot;
+            const int px0 = (g % tiles_x) * RTMI_TILE, py0 = (g / tiles_x) * RTMI_TILE;
+            const int ax0 = max(px0, rx0), ay0 = max(py0, ry0), ax1 = min(px0 + RTMI_TILE, rx1), ay1 = min(py0 + RTMI_TILE, ry1);
+            pixels += (ax1 > ax0 && ay1 > ay0) ? (ax1 - ax0) * (ay1 - ay0) : 0;
+        }
+        if (in && init_n_t >= 0) n_t[i] = init_n_t;
+        base += total;
+        __syncthreads(); // wave_count is rewritten by the next stride
+    }
+    for (int d = 32; d > 0; d >>= 1) pixels += __shfl_down(pixels, d, 64);
+    if (lane == 0) wave_pixels[wave] = pixels;
+    __syncthreads();
+    if (tid == 0) {
+        int sum = 0;
+        for (int w = 0; w < kCompactBlock / 64; ++w) sum += wave_pixels[w];
+        meta[0] = base;
+        meta[1] = sum;
+    }
+}
+
+// progressive_resolve_kernel with k read per tile: n_t[t] samples behind every pixel of local tile t; out_samples = that count per pixel.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) adaptive_resolve_kernel(const R *__restrict__ sums, const double *__restrict__ m2, const int *__restrict__ n_t,
+                                                                  int tx0, int ty0, int wtx, int x0, int y0, int w, int h, double *__restrict__ out_linear,
+                                                                  unsigned char *__restrict__ out_rgb8, double *__restrict__ out_stderr,
+                                                                  int *__restrict__ out_samples) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)w * h) return;
+    const int x = x0 + (int)(gid % w), y = y0 + (int)(gid / w);
+    const int t = (y / RTMI_TILE - ty0) * wtx + (x / RTMI_TILE - tx0);
+    const int l = (y % RTMI_TILE) * RTMI_TILE + (x % RTMI_TILE);
+    const size_t e = ((size_t)t * 64 + l) * 3;
+    const int k = n_t[t];
+    double err = k > 1 ? 0.0 : INFINITY;
+    for (int c = 0; c < 3; ++c) {
+        const double m = (double)(sums[e + c] * (R(1.0) / (R)k)); // reduce_kernel's last pass
+        if (out_linear) out_linear[gid * 3 + c] = m;
+        if (out_rgb8) { // assemble_kernel<double>
+            const double q = Real<double>::sqrt_(m) * 255.99;
+            unsigned char o = 0;
+            if (q == q) { const double mq = q < 255.99 ? q : 255.99; o = (unsigned char)(int)mq; }
+            out_rgb8[gid * 3 + c] = o;
+        }
+        if (k > 1) {
+            const double se = ::sqrt((m2[e + c] / (double)(k - 1)) / (double)k);
+            err = se > err ? se : err;
+        }
+    }
+    if (out_stderr) out_stderr[gid] = err;
+    if (out_samples) out_samples[gid] = k;
+}
+
 // What a progressive frame was started with: a continuation must match it field for field
 struct ProgKey {
     uint64_t scene_serial = 0, scene_revision = 0, seed = 0;
@@ -884,11 +1041,30 @@ struct ProgKey {
 // A context's progressive frame (rtmi_render_progressive*): the state progressive_fold_kernel keeps (sums in the precision of the frame, Welford
 // mean / M2 in double), the cumulative metrics counters, and the key; k = samples [0, k) it holds (0 = no frame).  Its own buffers: a one-shot
 // render on the same context in between does not touch it.
+// Per-tile state (rtmi_render_adaptive*): n_tiles local tiles of valid_pixels pixels inside the image and the region.  While `adaptive` is false every
+// tile is active with n_t = k and the arrays below are not in use (rtmi_render_progressive* never reads them); the first adaptive call fills them.
+// The active list is its own pair of arrays (c->tile_ids is rewritten by any other render on the context), double-buffered: the compaction reads
+// list `cur` and writes the other.  n_active, active_pixels and pixel_samples mirror the device's state on the host.
 struct ProgFrame {
     DevBuf sums, mean, m2, counters;
+    DevBuf act_tiles[2], act_slots[2], n_t, keep, meta;
     ProgKey key;
     int k = 0;
-    void release() { sums.release(); mean.release(); m2.release(); counters.release(); k = 0; }
+    bool adaptive = false;
+    int cur = 0, n_tiles = 0, n_active = 0;
+    long long valid_pixels = 0, active_pixels = 0, pixel_samples = 0;
+    void release() {
+        sums.release(); mean.release(); m2.release(); counters.release();
+        for (int i = 0; i < 2; ++i) { act_tiles[i].release(); act_slots[i].release(); }
+        n_t.release(); keep.release(); meta.release();
+        k = 0; adaptive = false; cur = n_tiles = n_active = 0; valid_pixels = active_pixels = pixel_samples = 0;
+    }
+};
+
+// what an adaptive call adds to the sample passes of a progressive one
+struct AdaptiveCall {
+    double eps = 0.0;
+    int k_before = 0; // the frame's k when the call started
 };
 
 } // namespace
@@ -1170,7 +1346,7 @@ int report_phase_stamps(rtmi_ctx *c, hipStream_t st) {
 // kernel counts its rays into the frame's counters.  A progressive call that fails once it got past the test hook has dropped its frame (k = 0).
 template <typename R>
 int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int depth, uint64_t seed, int first, int stride, const int *rg, void *d_tiles_linear,
-                  void *d_counters, hipStream_t st, ProgFrame *prog) {
+                  void *d_counters, hipStream_t st, ProgFrame *prog, const AdaptiveCall *ad = nullptr) {
     rtmi_ctx *c = s->ctx;
     int n_local = 0;
     const int whole[4] = {0, 0, nx, ny};
@@ -1193,12 +1369,34 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
             return fail(RTMI_E_STATE, "progressive frame buffers do not match the frame"); // (the key check makes this unreachable)
         }
         d_counters = prog->counters.p;
+        if (s_first == 0 || !ad) prog->adaptive = false; // a new frame, or a uniform continuation (no tile retired: the entries checked): every tile active, n_t = k
+        prog->n_tiles = n_local; prog->valid_pixels = c->tile_valid_pixels;
+        if (ad && !prog->adaptive) { // the per-tile state of a frame whose tiles all hold ad->k_before samples (0: a new frame) and are all active
+            const size_t ints = (size_t)std::max(n_local, 1) * sizeof(int);
+            for (int i = 0; i < 2 && !rc; ++i) { rc = prog->act_tiles[i].ensure(ints); if (!rc) rc = prog->act_slots[i].ensure(ints); }
+            if (!rc) rc = prog->n_t.ensure(ints);
+            if (!rc) rc = prog->keep.ensure(ints);
+            if (!rc) rc = prog->meta.ensure(2 * sizeof(int));
+            if (rc) return rc;
+            prog->cur = 0;
+            hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kCompactBlock), 0, st, (const int *)nullptr, reinterpret_cast<const int *>(c->tile_ids.p),
+                               (const int *)nullptr, n_local, reinterpret_cast<int *>(prog->act_tiles[0].p), reinterpret_cast<int *>(prog->act_slots[0].p),
+                               reinterpret_cast<int *>(prog->meta.p), ad->k_before, reinterpret_cast<int *>(prog->n_t.p), tiles_x_of(nx), std::max(rg[0], 0),
+                               std::max(rg[1], 0), std::min(rg[2], nx), std::min(rg[3], ny));
+            HIP_TRY(hipGetLastError());
+            prog->adaptive = true;
+            prog->n_active = n_local; prog->active_pixels = c->tile_valid_pixels;
+            prog->pixel_samples = c->tile_valid_pixels * (long long)ad->k_before;
+        }
     }
     rc = c->counters.ensure(8 * sizeof(u64)); // [0..1] the metrics when the caller passes no buffer, [2] the work-queue head, [3..4] traversal counters
     if (rc) return rc;
     if (d_counters && !prog) HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(u64), st));
     HIP_TRY(hipMemsetAsync(reinterpret_cast<u64 *>(c->counters.p) + 3, 0, 2 * sizeof(u64), st));
     if (n_local == 0) return RTMI_OK;
+    if (ad) n_local = prog->n_active; // an adaptive call traces and folds the frame's active list, not the render's tile list
+    if (n_local == 0) { prog->k = s_end; c->last_passes = 0; return RTMI_OK; } // every tile has retired: nothing to trace, k advances
+    const int *tile_list = ad ? reinterpret_cast<const int *>(prog->act_tiles[prog->cur].p) : reinterpret_cast<const int *>(c->tile_ids.p);
     u64 *cnt = d_counters ? reinterpret_cast<u64 *>(d_counters) : reinterpret_cast<u64 *>(c->counters.p);
     unsigned *queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 2);
 
@@ -1244,7 +1442,7 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
         const int s_count = std::min(s_per_pass, s_end - s_begin);
         TraceParams tp;
         tp.nx = nx; tp.ny = ny; tp.depth = depth; tp.seed = seed; tp.tiles_x = tiles_x_of(nx);
-        tp.n_local_tiles = n_local; tp.tile_ids = reinterpret_cast<const int *>(c->tile_ids.p);
+        tp.n_local_tiles = n_local; tp.tile_ids = tile_list;
         tp.s_begin = s_begin; tp.s_count = s_count; tp.samples = c->samples.p; tp.counters = cnt;
         tp.prims_per_tile = (c->scan_variant >= SCAN_SGPR || s->dev.has_ext) ? 0 : ppt; tp.n_ptiles = nptiles;
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1287,7 +1485,13 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
         HIP_TRY(hipGetLastError());
         if (e1) HIP_TRY(hipEventRecord(e1, st));
         const long long npx = (long long)n_local * 64;
-        if (prog)
+        if (ad)
+            hipLaunchKernelGGL((adaptive_fold_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                               reinterpret_cast<const R *>(c->samples.p), reinterpret_cast<R *>(prog->sums.p), reinterpret_cast<double *>(prog->mean.p),
+                               reinterpret_cast<double *>(prog->m2.p), tile_list, reinterpret_cast<const int *>(prog->act_slots[prog->cur].p), tiles_x_of(nx),
+                               n_local, s_begin, s_count, cnt, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1, s_begin + s_count == s_end ? 1 : 0,
+                               ad->eps, reinterpret_cast<int *>(prog->keep.p), reinterpret_cast<int *>(prog->n_t.p));
+        else if (prog)
             hipLaunchKernelGGL((progressive_fold_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                                reinterpret_cast<const R *>(c->samples.p), reinterpret_cast<R *>(prog->sums.p), reinterpret_cast<double *>(prog->mean.p),
                                reinterpret_cast<double *>(prog->m2.p), reinterpret_cast<const int *>(c->tile_ids.p), tiles_x_of(nx), n_local,
@@ -1307,6 +1511,15 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
 #ifdef RTMI_STAMPS
     rc = report_phase_stamps(c, st);
 #endif
+    if (!rc && ad) { // retire: the next active list, in tile order, and its length for the host
+        const int nxt = 1 - prog->cur;
+        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kCompactBlock), 0, st, reinterpret_cast<const int *>(prog->keep.p), tile_list,
+                           reinterpret_cast<const int *>(prog->act_slots[prog->cur].p), n_local, reinterpret_cast<int *>(prog->act_tiles[nxt].p),
+                           reinterpret_cast<int *>(prog->act_slots[nxt].p), reinterpret_cast<int *>(prog->meta.p), -1, (int *)nullptr, tiles_x_of(nx),
+                           std::max(rg[0], 0), std::max(rg[1], 0), std::min(rg[2], nx), std::min(rg[3], ny));
+        HIP_TRY(hipGetLastError());
+        prog->cur = nxt;
+    }
     if (!rc && prog) prog->k = s_end;
     return rc;
 }
@@ -1363,7 +1576,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 205; } // 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 206; } // 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -1826,6 +2039,15 @@ int check_continuation(const rtmi_ctx *c, const ProgKey &k, int s_first) {
     return RTMI_OK;
 }
 
+// rtmi_render_progressive* cannot continue a frame in which a tile has retired: its image would not be render(ns = k)'s
+int check_no_tile_retired(const rtmi_ctx *c, int s_first) {
+    const ProgFrame &f = c->prog;
+    if (s_first > 0 && f.k > 0 && f.adaptive && f.n_active < f.n_tiles)
+        return fail(RTMI_E_STATE, "%d of the frame's %d tiles have retired (rtmi_render_adaptive): continue it with rtmi_render_adaptive, or start a new frame with s_first = 0",
+                    f.n_tiles - f.n_active, f.n_tiles);
+    return RTMI_OK;
+}
+
 // Adds samples [s_first, s_first + s_count) to the context's frame (s_first = 0: a new frame), then resolves the state into the region's outputs
 // (device pointers, any may be null) and copies the cumulative counters to d_cnt, all on `st`.
 template <typename R>
@@ -1857,6 +2079,7 @@ RTMI_EXPORT int rtmi_render_progressive_device(rtmi_scene *s, int32_t nx, int32_
     const int whole[4] = {0, 0, nx, ny};
     const ProgKey key = progressive_key(s, nx, ny, depth, seed, precision, whole);
     rc = check_continuation(s->ctx, key, s_first);
+    if (!rc) rc = check_no_tile_retired(s->ctx, s_first);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(s->ctx->device));
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
@@ -1876,6 +2099,7 @@ RTMI_EXPORT int rtmi_render_progressive(rtmi_scene *s, int32_t nx, int32_t ny, i
     const ProgKey key = progressive_key(s, nx, ny, depth, seed, precision, rg);
     rtmi_ctx *c = s->ctx;
     rc = check_continuation(c, key, s_first);
+    if (!rc) rc = check_no_tile_retired(c, s_first);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const size_t npx = (size_t)(x1 - x0) * (size_t)(y1 - y0);
@@ -1908,6 +2132,128 @@ RTMI_EXPORT int rtmi_progressive_release(rtmi_ctx *c) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->prog.release();
+    return RTMI_OK;
+}
+
+// ---- adaptive sampling: the frame's tiles stop taking samples once their noise is below eps -------------------------------------------------
+namespace {
+int check_adaptive_args(rtmi_scene *s, int nx, int ny, int s_first, int s_count, double eps, int depth, int precision) {
+    int rc = check_progressive_args(s, nx, ny, s_first, s_count, depth, precision);
+    if (rc) return rc;
+    if (!(eps >= 0.0) || std::isinf(eps)) return fail(RTMI_E_ARG, "eps must be a finite number >= 0 (got %g)", eps);
+    return RTMI_OK;
+}
+
+// Adds samples [s_first, s_first + s_count) to the active tiles of the context's frame, retires the tiles that pass eps, resolves the frame into
+// the region's outputs (device pointers, any may be null), copies the cumulative counters to d_cnt and synchronises `st`: the host reads the
+// length of the next active list.
+template <typename R>
+int render_adaptive_impl(rtmi_scene *s, const ProgKey &key, int s_first, int s_count, double eps, double *d_lin, unsigned char *d_q, double *d_err,
+                         int *d_smp, void *d_cnt, hipStream_t st) {
+    ProgFrame &f = s->ctx->prog;
+    AdaptiveCall ad;
+    ad.eps = eps; ad.k_before = s_first;
+    int rc = render_passes<R>(s, key.nx, key.ny, s_first, s_first + s_count, key.depth, key.seed, 0, 1, key.rg, nullptr, nullptr, st, &f, &ad);
+    if (rc) return rc;
+    f.key = key;
+    const int x0 = key.rg[0], y0 = key.rg[1], w = key.rg[2] - x0, h = key.rg[3] - y0;
+    const int tx0 = x0 / RTMI_TILE, ty0 = y0 / RTMI_TILE, wtx = (key.rg[2] + RTMI_TILE - 1) / RTMI_TILE - tx0;
+    const long long npx = (long long)w * h;
+    hipError_t e = hipSuccess;
+    if (d_lin || d_q || d_err || d_smp) {
+        hipLaunchKernelGGL((adaptive_resolve_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                           reinterpret_cast<const R *>(f.sums.p), reinterpret_cast<const double *>(f.m2.p), reinterpret_cast<const int *>(f.n_t.p), tx0, ty0, wtx,
+                           x0, y0, w, h, d_lin, d_q, d_err, d_smp);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && d_cnt) e = hipMemcpyAsync(d_cnt, f.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToDevice, st);
+    int meta[2] = {f.n_active, (int)f.active_pixels}; // both fit an int: check_render_args refuses frames above 2^30 pixels
+    const bool traced = f.n_active > 0; // (the list this call started with: no trace, no compaction, meta unchanged)
+    if (e == hipSuccess && traced) e = hipMemcpyAsync(meta, f.meta.p, sizeof meta, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { f.k = 0; return fail(RTMI_E_DEVICE, "adaptive resolve: %s", hipGetErrorString(e)); }
+    f.pixel_samples += f.active_pixels * (long long)s_count; // the tiles active when the call started took its samples
+    f.n_active = meta[0]; f.active_pixels = meta[1];
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_adaptive_device(rtmi_scene *s, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, double eps, int32_t depth,
+                                            uint64_t seed, int32_t precision, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr,
+                                            void *d_out_samples, void *d_out_counters, void *stream) {
+    int rc = check_adaptive_args(s, nx, ny, s_first, s_count, eps, depth, precision);
+    if (rc) return rc;
+    const int whole[4] = {0, 0, nx, ny};
+    const ProgKey key = progressive_key(s, nx, ny, depth, seed, precision, whole);
+    rc = check_continuation(s->ctx, key, s_first);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
+    double *lin = reinterpret_cast<double *>(d_out_linear), *err = reinterpret_cast<double *>(d_out_stderr);
+    unsigned char *q = reinterpret_cast<unsigned char *>(d_out_rgb8);
+    int *smp = reinterpret_cast<int *>(d_out_samples);
+    if (precision == RTMI_F64) return render_adaptive_impl<double>(s, key, s_first, s_count, eps, lin, q, err, smp, d_out_counters, st);
+    return render_adaptive_impl<float>(s, key, s_first, s_count, eps, lin, q, err, smp, d_out_counters, st);
+}
+
+RTMI_EXPORT int rtmi_render_adaptive(rtmi_scene *s, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, double eps, int32_t depth, uint64_t seed,
+                                     int32_t precision, int32_t x0, int32_t y0, int32_t x1, int32_t y1, double *out_linear, uint8_t *out_rgb8,
+                                     double *out_stderr, int32_t *out_samples, uint64_t *out_counters) {
+    int rc = check_adaptive_args(s, nx, ny, s_first, s_count, eps, depth, precision);
+    if (rc) return rc;
+    if (x0 < 0 || y0 < 0 || x1 > nx || y1 > ny || x1 <= x0 || y1 <= y0) return fail(RTMI_E_ARG, "region [%d,%d)x[%d,%d) outside %dx%d", x0, x1, y0, y1, nx, ny);
+    const int rg[4] = {x0, y0, x1, y1};
+    const ProgKey key = progressive_key(s, nx, ny, depth, seed, precision, rg);
+    rtmi_ctx *c = s->ctx;
+    rc = check_continuation(c, key, s_first);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npx = (size_t)(x1 - x0) * (size_t)(y1 - y0);
+    rc = c->scratch_lin.ensure(npx * 3 * sizeof(double) + npx * sizeof(double) + npx * sizeof(int) + npx * 3 + 64);
+    if (rc) return rc;
+    char *base = reinterpret_cast<char *>(c->scratch_lin.p);
+    double *d_lin = reinterpret_cast<double *>(base), *d_err = reinterpret_cast<double *>(base + npx * 3 * sizeof(double));
+    int *d_smp = reinterpret_cast<int *>(base + npx * 4 * sizeof(double));
+    unsigned char *d_q = reinterpret_cast<unsigned char *>(base + npx * 4 * sizeof(double) + npx * sizeof(int));
+    hipStream_t st = c->stream;
+    if (precision == RTMI_F64) rc = render_adaptive_impl<double>(s, key, s_first, s_count, eps, d_lin, d_q, d_err, d_smp, nullptr, st);
+    else rc = render_adaptive_impl<float>(s, key, s_first, s_count, eps, d_lin, d_q, d_err, d_smp, nullptr, st);
+    if (rc) return rc;
+    hipError_t e = hipSuccess; // (the stream is synchronised)
+    if (out_linear) e = hipMemcpy(out_linear, d_lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_rgb8) e = hipMemcpy(out_rgb8, d_q, npx * 3, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_stderr) e = hipMemcpy(out_stderr, d_err, npx * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_samples) e = hipMemcpy(out_samples, d_smp, npx * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_counters) e = hipMemcpy(out_counters, c->prog.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { c->prog.k = 0; return fail(RTMI_E_DEVICE, "adaptive render: %s", hipGetErrorString(e)); }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_adaptive_status(rtmi_ctx *c, int32_t *active_tiles, int32_t *total_tiles, int64_t *pixel_samples) {
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    const ProgFrame &f = c->prog;
+    const bool have = f.k > 0;
+    if (active_tiles) *active_tiles = !have ? 0 : f.adaptive ? f.n_active : f.n_tiles;
+    if (total_tiles) *total_tiles = have ? f.n_tiles : 0;
+    if (pixel_samples) *pixel_samples = !have ? 0 : f.adaptive ? f.pixel_samples : f.valid_pixels * (long long)f.k;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_adaptive_active_tiles(rtmi_ctx *c, int32_t capacity, int32_t *out_tiles, int32_t *out_count) {
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    ProgFrame &f = c->prog;
+    const int n = f.k <= 0 ? 0 : f.adaptive ? f.n_active : f.n_tiles;
+    if (out_count) *out_count = n;
+    if (!out_tiles || n == 0) return RTMI_OK;
+    if (capacity < n) return fail(RTMI_E_ARG, "capacity = %d, the frame has %d active tiles", capacity, n);
+    HIP_TRY(hipSetDevice(c->device));
+    if (f.adaptive) { // the frame's own list, as the last compaction left it (every adaptive call ends with its stream synchronised)
+        HIP_TRY(hipMemcpy(out_tiles, f.act_tiles[f.cur].p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    } else { // a uniform frame: every tile of the region, in tile order
+        const int tx_n = tiles_x_of(f.key.nx), tx0 = f.key.rg[0] / RTMI_TILE, ty0 = f.key.rg[1] / RTMI_TILE;
+        const int wtx = (f.key.rg[2] + RTMI_TILE - 1) / RTMI_TILE - tx0;
+        for (int i = 0; i < n; ++i) out_tiles[i] = (ty0 + i / wtx) * tx_n + tx0 + i % wtx;
+    }
     return RTMI_OK;
 }
 
