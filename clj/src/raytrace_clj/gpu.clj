@@ -389,6 +389,46 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn render-features
+  "First-hit feature buffers of scene {:camera :world} on GPU `device` (rtmi_render_features): per pixel the mean over the first segments of
+  render samples 0 .. na-1 of albedo rgb, normal xyz, depth and coverage.  Returns {:features double-array [ny][nx][8] (row 0 = top)
+  :feature-rays :total-pixels}.  seed must be the seed of the frame the features belong to."
+  [scene nx ny na & {:keys [seed device precision] :or {seed 0x5eed0002 device 0 precision 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        ft   (double-array (* 8 nx ny))
+        cnt  (long-array 2)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_features" scn (int nx) (int ny) (int na) (long seed) (int precision)
+                           (int 0) (int 0) (int nx) (int ny) ft cnt))
+          {:features ft :feature-rays (aget cnt 0) :total-pixels (aget cnt 1)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
+(defn denoise
+  "Edge-aware a-trous filter (rtmi_denoise) of a frame: linear [ny][nx][3] (:linear of render / render-adaptive), stderr [ny][nx] (:stderr)
+  and features [ny][nx][8] (:features of render-features), `iterations` passes (0 .. 8).  A sigma of 0 switches its term off.  Returns
+  {:linear :rgb8 :stderr} of the filtered frame.  (A frame without a noise estimate or without features: pass NULL for it to rtmi_denoise.)"
+  [nx ny linear stderr features & {:keys [iterations sigma-c sigma-n sigma-a sigma-d device]
+                                   :or {iterations 5 sigma-c 4.0 sigma-n 0.5 sigma-a 0.2 sigma-d 0.2 device 0}}]
+  (let [ctx  (PointerByReference.)
+        npx  (* nx ny)
+        lin  (double-array linear)
+        se   (double-array stderr)
+        ft   (double-array features)
+        out  (double-array (* 3 npx))
+        rgb  (byte-array (* 3 npx))
+        err  (double-array npx)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (check (call-int "rtmi_denoise" (.getValue ctx) (int nx) (int ny) lin se ft (int iterations) (double sigma-c) (double sigma-n)
+                       (double sigma-a) (double sigma-d) out rgb err))
+      {:linear out :rgb8 rgb :stderr err}
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn render-multi
   "The same on every GPU in `devices` from this one JVM (rtmi_render_multi): one context per device, the scene created on
   the first (Perlin tables, ImageMap pixels and media calls included) and cloned onto the others (rtmi_scene_clone), the 8x8

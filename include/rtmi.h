@@ -278,6 +278,71 @@ int rtmi_adaptive_status(rtmi_ctx *ctx, int32_t *active_tiles, int32_t *total_ti
  * device (an adaptive call has synchronised its stream when it returns).  Without a frame: 0 and RTMI_OK. */
 int rtmi_adaptive_active_tiles(rtmi_ctx *ctx, int32_t capacity, int32_t *out_tiles, int32_t *out_count);
 
+/* ---- first-hit feature buffers: per-pixel albedo, normal, depth and coverage of a frame (what an edge-aware filter reads) ----
+ * out_features: [rows][cols][RTMI_FEATURES] doubles, row 0 = top, of the region (host form) or the whole frame (device form):
+ *   channels 0-2 albedo rgb, 3-5 normal xyz, 6 depth, 7 coverage.
+ * Each channel is the mean over the pixel's feature samples s = 0 .. na-1.  Feature sample s is the FIRST SEGMENT of the path render sample s
+ * traces: the stream keyed (seed, j*nx+i, s), the same two jitter draws and camera draws, the same hit? of the world with t-min 0.001 and
+ * t-max Float/MAX_VALUE, the media evaluated as the render evaluates them (they draw from the sample's stream; a medium's scattering point is a
+ * hit).  On a hit:
+ *   normal   = the hit record's :normal as the reference stores it (hitable.clj) -- not flipped toward the ray; the mean is not renormalised;
+ *   depth    = sqrt((p - o) . (p - o)), p the hit record's :p, o the ray's origin, the dot product folded from the left ((x x + y y) + z z), every
+ *              operation correctly rounded in the precision of the call;
+ *   coverage = 1;
+ *   albedo   = (sample texture u v p) at the hit record's uv and p, BOTH uv coordinates evaluated (the trace kernel's shortcut for textures that
+ *              do not read one is not taken): Lambertian, Metal, Isotropic: their albedo texture; DiffuseLight: its emission texture;
+ *              Dielectric: (1 1 1).  No scatter draw is made.
+ * On a miss all eight values are 0.  The fold is the frame's: in the precision R of the call, in sample order starting FROM sample 0, then
+ * sum * (R(1) / R(na)), widened to double.
+ * out_counters (may be NULL): {feature rays = pixels * na, pixels} of the region.
+ * The result does not depend on options "accel", "suspend_lanes", "flat_below", "scan_variant" or on the region, and the calls do not touch the
+ * context's progressive frame or its one-shot workspace.  Errors: na <= 0: RTMI_E_ARG; the others are rtmi_render's (RTMI_F32 on a mixed-kind
+ * scene: RTMI_E_UNSUPPORTED). */
+#define RTMI_FEATURES 8
+/* host buffers, output region [x0,x1) x [y0,y1) as rtmi_render */
+int rtmi_render_features(rtmi_scene *scene, int32_t nx, int32_t ny, int32_t na, uint64_t seed, int32_t precision,
+                         int32_t x0, int32_t y0, int32_t x1, int32_t y1, double *out_features, uint64_t *out_counters);
+/* device buffers, the whole frame, launched on `stream` with rtmi_render_device's stream semantics; asynchronous */
+int rtmi_render_features_device(rtmi_scene *scene, int32_t nx, int32_t ny, int32_t na, uint64_t seed, int32_t precision,
+                                void *d_out_features, void *d_out_counters, void *stream);
+
+/* ---- edge-aware denoiser: an a-trous wavelet filter guided by the noise estimate and the feature buffers ----
+ * A pure image operation in FP64 (-ffp-contract=off, no libm call in the weights): it reads no scene and no progressive frame, so it serves
+ * one-shot, progressive, adaptive and multi-device frames alike.
+ *   linear_in[ny][nx][3]      the frame (the mean before sqrt);
+ *   stderr_in[ny][nx]         standard error of the mean per pixel (out_stderr of the progressive / adaptive calls), may be NULL;
+ *   features_in[ny][nx][8]    rtmi_render_features' result, may be NULL;
+ *   iterations                0 .. 8 passes; pass i = 0, 1, ... uses tap distance step = 2^i;
+ *   sigma_c, _n, _a, _d       edge-stopping widths of colour, normal, albedo and depth; 0 switches the term off (decided per launch, not by arithmetic).
+ * State per pixel: the colour c (3 channels) and V, the variance of the mean: V = se * se at the start (0 when stderr_in is NULL).  One pass
+ * computes, for every centre pixel p, over the taps q = p + step * (dx, dy), dy = -2 .. 2 (outer loop), dx = -2 .. 2 (inner loop), with
+ * h = {1/16, 1/4, 3/8, 1/4, 1/16} indexed by dy + 2 / dx + 2, E = 2^-200, and sums folded from the left in that tap order, every operation one
+ * IEEE double operation as written:
+ *   a tap outside the image is skipped; a tap any of whose three colour values is not finite is skipped;
+ *   x = 0
+ *   x = x + (((c_p - c_q)_r^2 + (c_p - c_q)_g^2) + (c_p - c_q)_b^2) / ((sigma_c * sigma_c) * (V_p + V_q) + E)    if stderr_in and sigma_c > 0
+ *   x = x + (((n_p - n_q)_x^2 + (n_p - n_q)_y^2) + (n_p - n_q)_z^2) / (sigma_n * sigma_n)                        if features_in and sigma_n > 0
+ *   x = x + (((a_p - a_q)_r^2 + (a_p - a_q)_g^2) + (a_p - a_q)_b^2) / (sigma_a * sigma_a)                        if features_in and sigma_a > 0
+ *   x = x + ((d_p - d_q) * (d_p - d_q)) / ((sigma_d * sigma_d) * m + E),  m = d_q * d_q if d_q * d_q > d_p * d_p else d_p * d_p
+ *                                                                                                                if features_in and sigma_d > 0
+ *   the tap is skipped if x is NaN;    r = 1 / (1 + x);    w = (h[dy] * h[dx]) * ((r * r) * (r * r));    the tap is skipped if w is 0 or NaN;
+ *   W = W + w;    S_ch = S_ch + w * c_q,ch;    T = T + (w * w) * V_q
+ * and then c'_p = S_ch / W, V'_p = T / (W * W).  A centre pixel whose own colour is not finite, or for which no tap was taken (W = 0), is passed
+ * through unchanged (c and V).  A pixel with se = +inf (one sample) has V = +inf: its colour term is 0 -- no colour edge -- and 0 * inf never occurs.
+ * The features are not filtered.  Outputs, each may be NULL: out_linear = c after the last pass; out_rgb8 = rtmi_render's quantiser of it;
+ * out_stderr = sqrt(V) after the last pass.  iterations = 0 copies linear_in and stderr_in (0 where NULL) bit for bit.
+ * The passes ping-pong between two sets of planes the context owns (its denoise workspace: 8 planes of nx * ny doubles, 15 with features).
+ * Errors, reported before anything is launched (and before the handle is examined): nx or ny <= 0, iterations outside 0 .. 8, a negative or NaN
+ * sigma, linear_in NULL: RTMI_E_ARG. */
+/* host buffers */
+int rtmi_denoise(rtmi_ctx *ctx, int32_t nx, int32_t ny, const double *linear_in, const double *stderr_in, const double *features_in,
+                 int32_t iterations, double sigma_c, double sigma_n, double sigma_a, double sigma_d,
+                 double *out_linear, uint8_t *out_rgb8, double *out_stderr);
+/* device buffers, launched on `stream` with rtmi_render_device's stream semantics; asynchronous.  The input and output buffers may be the same. */
+int rtmi_denoise_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, const void *d_linear_in, const void *d_stderr_in, const void *d_features_in,
+                        int32_t iterations, double sigma_c, double sigma_n, double sigma_a, double sigma_d,
+                        void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *stream);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

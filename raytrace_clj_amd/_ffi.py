@@ -28,6 +28,7 @@ SYMBOLS = [
     "rtmi_last_gather_path", "rtmi_rccl_probe", "rtmi_stream_idle", "rtmi_last_passes", "rtmi_last_accel",
     "rtmi_render_progressive", "rtmi_render_progressive_device", "rtmi_progressive_samples", "rtmi_progressive_release",
     "rtmi_render_adaptive", "rtmi_render_adaptive_device", "rtmi_adaptive_status", "rtmi_adaptive_active_tiles",
+    "rtmi_render_features", "rtmi_render_features_device", "rtmi_denoise", "rtmi_denoise_device",
 ]
 
 F64, F32 = 0, 1
@@ -36,6 +37,7 @@ FLAG_TIMING = 1
 GATHER_PATHS = {0: "none", 1: "same-device", 2: "peer-copy", 3: "rccl"}
 SEG_REC = 12
 TILE = 8
+FEATURES = 8  # doubles per pixel of rtmi_render_features: albedo rgb, normal xyz, depth, coverage
 
 
 class RtmiError(RuntimeError):
@@ -112,6 +114,10 @@ def lib():
     L.rtmi_render_adaptive_device.argtypes = [vp, i32, i32, i32, i32, dbl, i32, u64, i32, vp, vp, vp, vp, vp, vp]
     L.rtmi_adaptive_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
     L.rtmi_adaptive_active_tiles.argtypes = [vp, i32, vp, C.POINTER(i32)]
+    L.rtmi_render_features.argtypes = [vp, i32, i32, i32, u64, i32, i32, i32, i32, i32, vp, vp]
+    L.rtmi_render_features_device.argtypes = [vp, i32, i32, i32, u64, i32, vp, vp, vp]
+    L.rtmi_denoise.argtypes = [vp, i32, i32, vp, vp, vp, i32, dbl, dbl, dbl, dbl, vp, vp, vp]
+    L.rtmi_denoise_device.argtypes = [vp, i32, i32, vp, vp, vp, i32, dbl, dbl, dbl, dbl, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

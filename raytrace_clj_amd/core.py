@@ -28,6 +28,14 @@ T_MAX = 3.4028234663852886e38  # Float/MAX_VALUE, core.clj:25
 DEFAULT_DEPTH = 50              # core.clj:20,45
 RENDER_SEED = 0x5EED0002
 
+# the denoiser's defaults: chosen by a grid over the small cover scene and the Cornell box at 16 spp
+DENOISE_ITERATIONS = 5
+DENOISE_SIGMA_C = 4.0
+DENOISE_SIGMA_N = 0.5
+DENOISE_SIGMA_A = 0.2
+DENOISE_SIGMA_D = 0.2
+FEATURE_SAMPLES = 4
+
 _PRECISION = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 
 
@@ -92,6 +100,35 @@ class Context:
         if n.value:
             check(_ffi.lib().rtmi_adaptive_active_tiles(self.handle, n.value, ptr(out), C.byref(n)))
         return out
+
+    # ---- the edge-aware denoiser: a pure image operation (rtmi_denoise*) ---------------------------------------------------------
+    def denoise(self, linear, stderr=None, features=None, iterations=DENOISE_ITERATIONS, sigma_c=DENOISE_SIGMA_C, sigma_n=DENOISE_SIGMA_N,
+                sigma_a=DENOISE_SIGMA_A, sigma_d=DENOISE_SIGMA_D):
+        """A-trous wavelet filter of a frame [h,w,3] guided by its standard error [h,w] (render_progressive / render_adaptive) and its feature
+        buffers [h,w,8] (render_features), either of which may be None -> (linear, rgb8, stderr) after `iterations` passes.  A sigma of 0
+        switches its term off; iterations = 0 returns the input."""
+        lin = np.ascontiguousarray(linear, np.float64)
+        if lin.ndim != 3 or lin.shape[2] != 3:
+            raise ValueError("linear must be [h, w, 3]")
+        h, w = lin.shape[:2]
+        se = None if stderr is None else np.ascontiguousarray(stderr, np.float64)
+        ft = None if features is None else np.ascontiguousarray(features, np.float64)
+        if se is not None and se.shape != (h, w):
+            raise ValueError("stderr must be [h, w]")
+        if ft is not None and ft.shape != (h, w, _ffi.FEATURES):
+            raise ValueError("features must be [h, w, %d]" % _ffi.FEATURES)
+        out, q, err = np.zeros_like(lin), np.zeros(lin.shape, np.uint8), np.zeros((h, w), np.float64)
+        check(_ffi.lib().rtmi_denoise(self.handle, w, h, ptr(lin), ptr(se), ptr(ft), int(iterations), float(sigma_c), float(sigma_n),
+                                      float(sigma_a), float(sigma_d), ptr(out), ptr(q), ptr(err)))
+        return out, q, err
+
+    def denoise_device(self, nx, ny, linear, stderr=None, features=None, out_linear=None, out_rgb8=None, out_stderr=None,
+                       iterations=DENOISE_ITERATIONS, sigma_c=DENOISE_SIGMA_C, sigma_n=DENOISE_SIGMA_N, sigma_a=DENOISE_SIGMA_A,
+                       sigma_d=DENOISE_SIGMA_D, stream=None):
+        """denoise on HBM-resident buffers (torch tensors or raw device pointers), asynchronous, render_device's stream semantics"""
+        check(_ffi.lib().rtmi_denoise_device(self.handle, nx, ny, ptr(linear), ptr(stderr), ptr(features), int(iterations), float(sigma_c),
+                                             float(sigma_n), float(sigma_a), float(sigma_d), ptr(out_linear), ptr(out_rgb8), ptr(out_stderr),
+                                             ptr(stream)))
 
     def last_traversal_counters(self):
         """(AABB slab tests, exact primitive tests) of the last render; needs set_option("count_traversal", 1) before it
@@ -262,6 +299,32 @@ class DeviceScene:
             yield k, lin, q, err, smp, cnt, active
             if active == 0:
                 break
+
+    # ---- first-hit feature buffers and the denoised frame ------------------------------------------------------------------------------
+    def render_features(self, nx, ny, na=FEATURE_SAMPLES, seed=RENDER_SEED, precision="f64", region=None):
+        """-> (features float64 [h,w,8] = albedo rgb, normal xyz, depth, coverage: the mean over the first segments of render samples 0 .. na-1,
+        counters {feature rays, pixels})"""
+        x0, y0, x1, y1 = region if region is not None else (0, 0, nx, ny)
+        ft = np.zeros((max(y1 - y0, 0), max(x1 - x0, 0), _ffi.FEATURES), np.float64)
+        cnt = np.zeros(2, np.uint64)
+        check(_ffi.lib().rtmi_render_features(self.handle, nx, ny, na, seed, _PRECISION[precision], x0, y0, x1, y1, ptr(ft), ptr(cnt)))
+        return ft, cnt
+
+    def render_features_device(self, nx, ny, na, out_features, out_counters=None, seed=RENDER_SEED, precision="f64", stream=None):
+        """render_features for the whole frame into HBM-resident buffers (asynchronous, render_device's stream semantics)"""
+        check(_ffi.lib().rtmi_render_features_device(self.handle, nx, ny, na, seed, _PRECISION[precision], ptr(out_features), ptr(out_counters),
+                                                     ptr(stream)))
+
+    def render_denoised(self, nx, ny, ns, na=FEATURE_SAMPLES, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", **denoise):
+        """One frame of ns samples with its noise estimate (render_progressive), its features (render_features, na samples) and the filtered frame
+        (Context.denoise; keyword arguments: iterations, sigma_c, sigma_n, sigma_a, sigma_d) ->
+        ((linear, rgb8, stderr, counters), features, (linear, rgb8, stderr) filtered).  The raw frame equals render(ns)."""
+        try:
+            raw = self.render_progressive(nx, ny, 0, ns, depth, seed, precision)
+        finally:
+            self.ctx.progressive_release()
+        ft, _ = self.render_features(nx, ny, na, seed, precision)
+        return raw, ft, self.ctx.denoise(raw[0], raw[2], ft, **denoise)
 
     def render_tiles_device(self, nx, ny, ns, tile_first, tile_stride, out_tiles, out_counters=None, depth=DEFAULT_DEPTH,
                             seed=RENDER_SEED, precision="f64", stream=None):
@@ -500,6 +563,68 @@ def _progressive_flags(argv):
     return rest, flags.get("--chunk"), flags.get("--budget"), flags.get("--noise"), flags.get("--adaptive")
 
 
+def _denoise_flags(argv):
+    """-> (the other arguments, iterations, feature samples): --denoise [ITERATIONS] (an integer right after it, or --denoise=K, is its value;
+    default DENOISE_ITERATIONS) and --feature-samples N, checked here, before any device work (None when absent)"""
+    import re
+    rest, iterations, na = [], None, None
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        key, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") else (a, None)
+        i += 1
+        if key == "--denoise":
+            if val is None and i < len(argv) and re.fullmatch(r"[+-]?[0-9]+", argv[i]):
+                val = argv[i]
+                i += 1
+            try:
+                iterations = DENOISE_ITERATIONS if val is None else int(val)
+            except ValueError:
+                raise SystemExit("--denoise %r is not a number of passes" % val)
+            if not 0 <= iterations <= 8:
+                raise SystemExit("--denoise takes 0 to 8 passes (got %d)" % iterations)
+        elif key == "--feature-samples":
+            if val is None:
+                if i >= len(argv):
+                    raise SystemExit("--feature-samples needs a value")
+                val = argv[i]
+                i += 1
+            try:
+                na = int(val)
+            except ValueError:
+                raise SystemExit("--feature-samples %r is not a number" % val)
+            if na <= 0:
+                raise SystemExit("--feature-samples must be a positive number of samples (got %d)" % na)
+        else:
+            rest.append(a)
+    if na is not None and iterations is None:
+        raise SystemExit("--feature-samples belongs to --denoise")
+    return rest, iterations, na
+
+
+def _denoised_name(name):
+    """x.png -> x.denoised.png: the filtered image is written next to the unfiltered one"""
+    import os
+    root, ext = os.path.splitext(name)
+    return root + ".denoised" + ext
+
+
+def _denoise_frame(ds, nx, ny, lin, err, iterations, na):
+    """the filtered 8-bit frame of a run with --denoise: the features of the frame, then the filter with the default sigmas"""
+    ft, _ = ds.render_features(nx, ny, FEATURE_SAMPLES if na is None else na)
+    return ds.ctx.denoise(lin, err, ft, iterations=iterations)[1]
+
+
+def _save_image(name, rgb8):
+    if name.lower().endswith(".ppm"):
+        save_ppm(name, rgb8)
+    elif name.lower().endswith(".npy"):
+        np.save(name, rgb8)
+    else:
+        save_png(name, rgb8)
+    print("wrote", name)  # core.clj:113
+
+
 def _show_progress(tstart, k, ns):
     """display.clj:20-24 after a chunk: elapsed, percent done, ETA"""
     elapsed = time.time() - tstart
@@ -518,9 +643,13 @@ def main(argv=None):
     image after k samples is the one-shot render's with ns = k.
     --adaptive EPS samples adaptively instead (refine_adaptive, rounds of --chunk, default 16): an 8x8 tile stops taking samples once all its
     pixels have a standard error <= EPS, and the run ends when no tile is left or at ns; every tile equals the one-shot render with the
-    samples it took.  --budget applies; --noise does not combine with it."""
+    samples it took.  --budget applies; --noise does not combine with it.
+    --denoise [ITERATIONS] also writes the frame filtered by the edge-aware denoiser (Context.denoise, default sigmas, ITERATIONS passes, default
+    5) next to the unfiltered one, as name.denoised.ext; --feature-samples N sets the samples of its feature buffers (default 4).  It works with
+    every mode above; the unfiltered file and the progress lines are what they are without it."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
+    argv, dn_iterations, dn_samples = _denoise_flags(argv)
     argv, chunk, budget, noise, adaptive = _progressive_flags(argv)
     if chunk is None and (budget is not None or noise is not None or adaptive is not None):
         chunk = 16
@@ -533,10 +662,21 @@ def main(argv=None):
         raise SystemExit("unknown scene %r; one of %s" % (which, ", ".join(sorted(SCENES))))
     tstart = time.time()
     sc = SCENES[which](scenes, nx, ny)
-    if chunk is None:
+    filtered = None
+    if chunk is None and dn_iterations is None:
         lin, rgb8, cnt = render(sc, nx, ny, nr)
         elapsed = time.time() - tstart
         print("%.2fs, %d%%, ETA %.2fs" % (elapsed, 100, 0.0))  # display.clj:20-24
+    elif chunk is None:  # the one-shot frame through the progressive call: the same image, and the noise estimate the filter reads
+        ds = DeviceScene(sc)
+        try:
+            lin, rgb8, err, cnt = ds.render_progressive(nx, ny, 0, nr)
+            elapsed = time.time() - tstart
+            print("%.2fs, %d%%, ETA %.2fs" % (elapsed, 100, 0.0))  # display.clj:20-24
+            filtered = _denoise_frame(ds, nx, ny, lin, err, dn_iterations, dn_samples)
+        finally:
+            ds.ctx.progressive_release()
+            ds.close()
     elif adaptive is not None:
         ds = DeviceScene(sc)
         try:
@@ -547,6 +687,8 @@ def main(argv=None):
                     break
             active, total, pixel_samples = ds.ctx.adaptive_status()
             print("samples: mean %.2f of %d per pixel, %d of %d tiles converged" % (pixel_samples / max(int(cnt[1]), 1), nr, total - active, total))
+            if dn_iterations is not None:
+                filtered = _denoise_frame(ds, nx, ny, lin, err, dn_iterations, dn_samples)
         finally:
             ds.ctx.progressive_release()
             ds.close()
@@ -563,17 +705,15 @@ def main(argv=None):
                 if why and k < nr:
                     print("stopped at %d of %d samples (%s)" % (k, nr, why))
                     break
+            if dn_iterations is not None:
+                filtered = _denoise_frame(ds, nx, ny, lin, err, dn_iterations, dn_samples)
         finally:
             ds.ctx.progressive_release()
             ds.close()
     print("total-rays %d total-pixels %d" % (int(cnt[0]), int(cnt[1])))  # metrics.clj:8-9
-    if name.lower().endswith(".ppm"):
-        save_ppm(name, rgb8)
-    elif name.lower().endswith(".npy"):
-        np.save(name, rgb8)
-    else:
-        save_png(name, rgb8)
-    print("wrote", name)  # core.clj:113
+    _save_image(name, rgb8)
+    if filtered is not None:
+        _save_image(_denoised_name(name), filtered)
     return 0
 
 

@@ -1031,6 +1031,183 @@ __global__ void __launch_bounds__(kBlock) adaptive_resolve_kernel(const R *__res
     if (out_samples) out_samples[gid] = k;
 }
 
+// ---- first-hit feature pass (rtmi_render_features*) -------------------------------------------------------------------------------------------
+// One wave per 8x8 tile of the window of tiles that covers the region, one lane per pixel, four waves per workgroup (the LDS stack columns of the
+// probe kernels: column = threadIdx.x).  Lane l loops over the feature samples s = 0 .. na-1 of its pixel: the first segment of the path render
+// sample s traces -- start_sample (same key, jitter and camera draws), intersect_world with t-min 0.001 (media draw from the sample's stream as in
+// the render), resolve_any with both uv coordinates, tex_sample of the material's texture -- and folds the eight values into running sums in
+// registers, in sample order, starting FROM sample 0.  No sample buffer, no reduction pass: HBM sees the 64 bytes per pixel of the result.
+struct FeatureParams {
+    int nx, ny, na;
+    u64 seed;
+    int tx0, ty0, wtx, n_tiles; // the window of tiles, row-major
+    int rx0, ry0, rx1, ry1;     // output region (row 0 = top)
+    double *out;                // [ry1 - ry0][rx1 - rx0][8]
+    u64 *counters;              // [0] += feature rays, [1] += pixels
+};
+
+template <typename R, int VARIANT, bool EXT = false, int MSEQ = 0>
+__global__ void __launch_bounds__(kBlock) feature_kernel(ScenePtr scp, FeatureParams fp) {
+    static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the feature pass does not run them");
+    SceneRef sc = *scp;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    Prim4<R> *lds = reinterpret_cast<Prim4<R> *>(smem);
+    const int lane = threadIdx.x & 63;
+    const int tile = (int)((blockIdx.x * (unsigned)kBlock + threadIdx.x) >> 6); // wave-uniform
+    const bool in_grid = tile < fp.n_tiles;
+    const int tcol = in_grid ? tile % fp.wtx : 0, trow = in_grid ? tile / fp.wtx : 0;
+    const int x = (fp.tx0 + tcol) * RTMI_TILE + (lane & 7), y = (fp.ty0 + trow) * RTMI_TILE + (lane >> 3);
+    const bool active = in_grid && x >= fp.rx0 && x < fp.rx1 && y >= fp.ry0 && y < fp.ry1;
+    TraceParams tp;
+    tp.seed = fp.seed; tp.nx = fp.nx; tp.ny = fp.ny; tp.depth = 0;
+    const R tmin = R(0.001), tmax = Real<R>::tmax();
+    R acc[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) acc[c] = R(0);
+    for (int s = 0; s < fp.na; ++s) {
+        Path<R> P;
+        P.ox = P.oy = P.oz = P.dx = P.dy = P.dz = P.time = R(0);
+        P.ar = P.ag = P.ab = R(0);
+        seed_stream(P, 0ull, 0u); P.depth = 0;
+        if (active) start_sample<R>(sc, tp, x, fp.ny - 1 - y, s, P); // j = ny-1-y (core.clj:105)
+        const R ox = P.ox, oy = P.oy, oz = P.oz;
+        R best_t; int best_i;
+        intersect_world<R, false, VARIANT, EXT, false, false, MSEQ>(sc, lds, 0, 1, P, active, tmin, tmax, best_t, best_i);
+        R f[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) f[c] = R(0);
+        if (active && best_i >= 0) {
+            HitRec<R> h;
+            resolve_any<R, EXT>(sc, P, best_t, best_i, h, true);
+            const int mk = sc.mat_kind[h.mat];
+            if (mk == RTMI_MAT_DIELECTRIC) f[0] = f[1] = f[2] = R(1);
+            else tex_sample<R, EXT>(sc, sc.mat_tex[h.mat], h.u, h.v, h.px, h.py, h.pz, f[0], f[1], f[2]);
+            f[3] = h.nx; f[4] = h.ny; f[5] = h.nz;
+            const R ex = h.px - ox, ey = h.py - oy, ez = h.pz - oz;
+            f[6] = Real<R>::sqrt_(dot3(ex, ey, ez, ex, ey, ez));
+            f[7] = R(1);
+        }
+        if (s == 0) { // the fold starts FROM the first sample (not 0 + first)
+#pragma unroll
+            for (int c = 0; c < 8; ++c) acc[c] = f[c];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) acc[c] = acc[c] + f[c];
+        }
+    }
+    const u64 live = __ballot(active);
+    if (lane == 0 && live) {
+        atomicAdd(fp.counters, (u64)__popcll(live) * (u64)fp.na);
+        atomicAdd(fp.counters + 1, (u64)__popcll(live));
+    }
+    if (!active) return;
+    const R inv = R(1.0) / (R)fp.na; // the frame's mean: sum * (1 / n)
+    double *o = fp.out + ((size_t)(y - fp.ry0) * (size_t)(fp.rx1 - fp.rx0) + (size_t)(x - fp.rx0)) * 8;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[c] = (double)(acc[c] * inv);
+}
+
+// ---- edge-aware denoiser (rtmi_denoise*): an a-trous wavelet filter over planar FP64 images -----------------------------------------------------
+// Planes of nx * ny doubles: colour r, g, b and the variance of the mean V (two sets: a pass reads one and writes the other), then normal xyz,
+// albedo rgb and depth (read only).  Lanes run along x: every tap of a wave is one contiguous run per plane.
+constexpr int kDnState = 4, kDnFeat = 7;
+constexpr double kDnTiny = 0x1p-200; // E of rtmi.h
+
+// interleaved inputs -> planes.  V = se * se (0 without stderr_in)
+__global__ void __launch_bounds__(kBlock) denoise_load_kernel(const double *__restrict__ lin, const double *__restrict__ se, const double *__restrict__ feat,
+                                                              size_t n, double *__restrict__ state, double *__restrict__ fplanes) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    state[p] = lin[3 * p]; state[n + p] = lin[3 * p + 1]; state[2 * n + p] = lin[3 * p + 2];
+    double v = 0.0;
+    if (se) { const double e = se[p]; v = e * e; }
+    state[3 * n + p] = v;
+    if (feat) {
+        const double *f = feat + 8 * p;
+        fplanes[p] = f[3]; fplanes[n + p] = f[4]; fplanes[2 * n + p] = f[5];
+        fplanes[3 * n + p] = f[0]; fplanes[4 * n + p] = f[1]; fplanes[5 * n + p] = f[2];
+        fplanes[6 * n + p] = f[6];
+    }
+}
+
+// One pass with tap distance `step`.  use_c / use_n / use_a / use_d are launch-uniform: a term that is off is not evaluated.  s*2 = sigma squared.
+__global__ void __launch_bounds__(kBlock) denoise_pass_kernel(const double *__restrict__ in, double *__restrict__ out, const double *__restrict__ fp,
+                                                              int nx, int ny, int step, int use_c, int use_n, int use_a, int use_d,
+                                                              double sc2, double sn2, double sa2, double sd2) {
+    const int x = (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = (int)(blockIdx.y * (kBlock / 64) + (threadIdx.x >> 6));
+    if (x >= nx || y >= ny) return;
+    const size_t n = (size_t)nx * (size_t)ny, p = (size_t)y * (size_t)nx + (size_t)x;
+    const double c0 = in[p], c1 = in[n + p], c2 = in[2 * n + p], vp = in[3 * n + p];
+    const double big = __builtin_inf();
+    const bool centre_ok = ::fabs(c0) < big && ::fabs(c1) < big && ::fabs(c2) < big; // finite: neither inf nor NaN
+    double n0 = 0, n1 = 0, n2 = 0, a0 = 0, a1 = 0, a2 = 0, dp = 0;
+    if (use_n) { n0 = fp[p]; n1 = fp[n + p]; n2 = fp[2 * n + p]; }
+    if (use_a) { a0 = fp[3 * n + p]; a1 = fp[4 * n + p]; a2 = fp[5 * n + p]; }
+    if (use_d) dp = fp[6 * n + p];
+    double sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, sv = 0.0;
+    if (centre_ok) {
+        for (int dy = -2; dy <= 2; ++dy) {
+            const int qy = y + dy * step;
+            if (qy < 0 || qy >= ny) continue; // (wave-uniform)
+            const double hy = dy == 0 ? 0.375 : ((dy == 1 || dy == -1) ? 0.25 : 0.0625);
+            for (int dx = -2; dx <= 2; ++dx) {
+                const int qx = x + dx * step;
+                if (qx < 0 || qx >= nx) continue;
+                const double hx = dx == 0 ? 0.375 : ((dx == 1 || dx == -1) ? 0.25 : 0.0625);
+                const size_t q = (size_t)qy * (size_t)nx + (size_t)qx;
+                const double q0 = in[q], q1 = in[n + q], q2 = in[2 * n + q], vq = in[3 * n + q];
+                if (!(::fabs(q0) < big && ::fabs(q1) < big && ::fabs(q2) < big)) continue;
+                double xx = 0.0;
+                if (use_c) {
+                    const double e0 = c0 - q0, e1 = c1 - q1, e2 = c2 - q2;
+                    xx = xx + ((e0 * e0 + e1 * e1) + e2 * e2) / (sc2 * (vp + vq) + kDnTiny);
+                }
+                if (use_n) {
+                    const double e0 = n0 - fp[q], e1 = n1 - fp[n + q], e2 = n2 - fp[2 * n + q];
+                    xx = xx + ((e0 * e0 + e1 * e1) + e2 * e2) / sn2;
+                }
+                if (use_a) {
+                    const double e0 = a0 - fp[3 * n + q], e1 = a1 - fp[4 * n + q], e2 = a2 - fp[5 * n + q];
+                    xx = xx + ((e0 * e0 + e1 * e1) + e2 * e2) / sa2;
+                }
+                if (use_d) {
+                    const double dq = fp[6 * n + q], e = dp - dq, pp = dp * dp, qq = dq * dq;
+                    xx = xx + (e * e) / (sd2 * (qq > pp ? qq : pp) + kDnTiny);
+                }
+                if (xx != xx) continue;
+                const double r = 1.0 / (1.0 + xx);
+                const double w = (hy * hx) * ((r * r) * (r * r));
+                if (!(w > 0.0)) continue; // 0 (x = +inf) or NaN
+                sw = sw + w;
+                s0 = s0 + w * q0; s1 = s1 + w * q1; s2 = s2 + w * q2;
+                sv = sv + (w * w) * vq;
+            }
+        }
+    }
+    if (sw != 0.0) { // (never with a non-finite centre)
+        out[p] = s0 / sw; out[n + p] = s1 / sw; out[2 * n + p] = s2 / sw; out[3 * n + p] = sv / (sw * sw);
+    } else { out[p] = c0; out[n + p] = c1; out[2 * n + p] = c2; out[3 * n + p] = vp; }
+}
+
+// planes -> interleaved outputs.  se_copy != null: out_stderr copies it (iterations = 0); else sqrt(V) (V = 0 without stderr_in)
+__global__ void __launch_bounds__(kBlock) denoise_store_kernel(const double *__restrict__ state, size_t n, const double *__restrict__ se_copy,
+                                                               double *__restrict__ out_linear, unsigned char *__restrict__ out_rgb8,
+                                                               double *__restrict__ out_stderr) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    for (int c = 0; c < 3; ++c) {
+        const double m = state[(size_t)c * n + p];
+        if (out_linear) out_linear[3 * p + c] = m;
+        if (out_rgb8) { // assemble_kernel<double>
+            const double q = Real<double>::sqrt_(m) * 255.99;
+            unsigned char o = 0;
+            if (q == q) { const double mq = q < 255.99 ? q : 255.99; o = (unsigned char)(int)mq; }
+            out_rgb8[3 * p + c] = o;
+        }
+    }
+    if (out_stderr) out_stderr[p] = se_copy ? se_copy[p] : ::sqrt(state[3 * n + p]);
+}
+
 // What a progressive frame was started with: a continuation must match it field for field
 struct ProgKey {
     uint64_t scene_serial = 0, scene_revision = 0, seed = 0;
@@ -1112,6 +1289,8 @@ struct rtmi_ctx {
     hipStream_t last_stream = nullptr; // stream of the most recent render (rtmi_last_traversal_counters synchronises on it)
     long long tile_valid_pixels = 0;
     ProgFrame prog; // at most one progressive frame per context
+    DevBuf feat_out, feat_cnt; // rtmi_render_features*: the host form's result, the counters nobody asked for
+    DevBuf dn_planes, dn_io;   // rtmi_denoise*: the filter's planes (two colour + variance sets, the feature planes), the host form's buffers
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     int events_used = 0;
@@ -1576,7 +1755,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 206; } // 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 207; } // 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -1615,6 +1794,7 @@ RTMI_EXPORT int rtmi_shutdown(rtmi_ctx *c) {
 #endif
     c->samples.release(); c->accum.release(); c->tiles.release(); c->tile_ids.release(); c->counters.release(); c->scratch_lin.release(); c->multi.release();
     c->prog.release();
+    c->feat_out.release(); c->feat_cnt.release(); c->dn_planes.release(); c->dn_io.release();
     for (hipEvent_t e : {c->ev_done, c->ev_g0, c->ev_g1}) if (e) (void)hipEventDestroy(e);
     if (c->ev_consumed) { (void)hipSetDevice(c->ev_consumed_device); (void)hipEventDestroy(c->ev_consumed); (void)hipSetDevice(c->device); }
     for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -2833,4 +3013,162 @@ RTMI_EXPORT int rtmi_probe_math2(rtmi_ctx *c, int32_t n, const double *abc, doub
 // the entry as first published: EIGHT values per triple (version 203 wrote nine into the same signature; hosts built against either header get eight again)
 RTMI_EXPORT int rtmi_probe_math(rtmi_ctx *c, int32_t n, const double *abc, double tmin, double tmax, double *out) {
     return rtmi_probe_math2(c, n, abc, tmin, tmax, 8, out);
+}
+
+// ---- first-hit feature buffers (rtmi_render_features*) -----------------------------------------------------------------------------------------
+namespace {
+// feature_kernel's instantiations are chosen where the probe kernels' are (with_probe_kernel); the LDS-staged scans (scan_variant 0 / 1) need
+// workgroup barriers and are answered with the scalar-cache scan, which finds the same hit
+struct FeaturePass {
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return feature_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MSEQ>; }
+};
+
+int check_feature_args(rtmi_scene *s, int nx, int ny, int na, int precision) {
+    if (na <= 0) return fail(RTMI_E_ARG, "na must be > 0 (got %d)", na);
+    if (nx <= 0 || ny <= 0) return fail(RTMI_E_ARG, "nx, ny must be > 0 (got %d %d)", nx, ny);
+    return check_render_args(s, nx, ny, na, 0, precision);
+}
+
+// the region rg = {x0, y0, x1, y1} of the frame's features into d_out[y1 - y0][x1 - x0][8], the counters into d_cnt[2]; all on `st`
+template <typename R>
+int render_features_impl(rtmi_scene *s, int nx, int ny, int na, uint64_t seed, const int *rg, double *d_out, u64 *d_cnt, hipStream_t st) {
+    rtmi_ctx *c = s->ctx;
+    FeatureParams fp;
+    fp.nx = nx; fp.ny = ny; fp.na = na; fp.seed = seed;
+    fp.tx0 = rg[0] / RTMI_TILE; fp.ty0 = rg[1] / RTMI_TILE;
+    fp.wtx = (rg[2] + RTMI_TILE - 1) / RTMI_TILE - fp.tx0;
+    fp.n_tiles = fp.wtx * ((rg[3] + RTMI_TILE - 1) / RTMI_TILE - fp.ty0);
+    fp.rx0 = rg[0]; fp.ry0 = rg[1]; fp.rx1 = rg[2]; fp.ry1 = rg[3];
+    fp.out = d_out; fp.counters = d_cnt;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(u64), st));
+    const size_t lds = c->accel == RTMI_ACCEL_BVH ? (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16 : (size_t)64; // the traversal's stack columns
+    const unsigned grid = (unsigned)((fp.n_tiles + kBlock / 64 - 1) / (kBlock / 64));
+    with_probe_kernel<FeaturePass, R>(s, [&](auto kern, size_t, int, int) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, s->d_dev, fp); });
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_features_device(rtmi_scene *s, int32_t nx, int32_t ny, int32_t na, uint64_t seed, int32_t precision,
+                                            void *d_out_features, void *d_out_counters, void *stream) {
+    int rc = check_feature_args(s, nx, ny, na, precision);
+    if (rc) return rc;
+    if (!d_out_features) return fail(RTMI_E_ARG, "d_out_features is NULL");
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    if (!d_out_counters) {
+        rc = c->feat_cnt.ensure(2 * sizeof(u64));
+        if (rc) return rc;
+        d_out_counters = c->feat_cnt.p;
+    }
+    const int whole[4] = {0, 0, nx, ny};
+    if (precision == RTMI_F64) return render_features_impl<double>(s, nx, ny, na, seed, whole, reinterpret_cast<double *>(d_out_features), reinterpret_cast<u64 *>(d_out_counters), st);
+    return render_features_impl<float>(s, nx, ny, na, seed, whole, reinterpret_cast<double *>(d_out_features), reinterpret_cast<u64 *>(d_out_counters), st);
+}
+
+RTMI_EXPORT int rtmi_render_features(rtmi_scene *s, int32_t nx, int32_t ny, int32_t na, uint64_t seed, int32_t precision,
+                                     int32_t x0, int32_t y0, int32_t x1, int32_t y1, double *out_features, uint64_t *out_counters) {
+    int rc = check_feature_args(s, nx, ny, na, precision);
+    if (rc) return rc;
+    if (x0 < 0 || y0 < 0 || x1 > nx || y1 > ny || x1 <= x0 || y1 <= y0) return fail(RTMI_E_ARG, "region [%d,%d)x[%d,%d) outside %dx%d", x0, x1, y0, y1, nx, ny);
+    if (!out_features) return fail(RTMI_E_ARG, "out_features is NULL");
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npx = (size_t)(x1 - x0) * (size_t)(y1 - y0);
+    rc = c->feat_out.ensure(npx * 8 * sizeof(double) + 2 * sizeof(u64));
+    if (rc) return rc;
+    double *d_out = reinterpret_cast<double *>(c->feat_out.p);
+    u64 *d_cnt = reinterpret_cast<u64 *>(d_out + npx * 8);
+    const int rg[4] = {x0, y0, x1, y1};
+    hipStream_t st = c->stream;
+    if (precision == RTMI_F64) rc = render_features_impl<double>(s, nx, ny, na, seed, rg, d_out, d_cnt, st);
+    else rc = render_features_impl<float>(s, nx, ny, na, seed, rg, d_out, d_cnt, st);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(out_features, d_out, npx * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---- edge-aware denoiser (rtmi_denoise*) ---------------------------------------------------------------------------------------------------------
+namespace {
+// the argument checks of both entries, before the handle is looked at: they need no device
+int check_denoise_args(int nx, int ny, const void *lin, int iterations, double sigma_c, double sigma_n, double sigma_a, double sigma_d) {
+    if (nx <= 0 || ny <= 0) return fail(RTMI_E_ARG, "nx, ny must be > 0 (got %d %d)", nx, ny);
+    if ((long long)nx * ny > (1ll << 30)) return fail(RTMI_E_ARG, "frame too large");
+    if (iterations < 0 || iterations > 8) return fail(RTMI_E_ARG, "iterations must be 0..8 (got %d)", iterations);
+    const double sg[4] = {sigma_c, sigma_n, sigma_a, sigma_d};
+    for (int k = 0; k < 4; ++k)
+        if (!(sg[k] >= 0.0)) return fail(RTMI_E_ARG, "sigma_%c must be >= 0 and not NaN (got %g)", "cnad"[k], sg[k]);
+    if (!lin) return fail(RTMI_E_ARG, "linear_in is NULL");
+    return RTMI_OK;
+}
+
+int denoise_impl(rtmi_ctx *c, int nx, int ny, const double *d_lin, const double *d_se, const double *d_feat, int iterations, double sigma_c,
+                 double sigma_n, double sigma_a, double sigma_d, double *d_out_lin, unsigned char *d_out_q, double *d_out_se, hipStream_t st) {
+    const size_t n = (size_t)nx * (size_t)ny;
+    int rc = c->dn_planes.ensure((2 * kDnState + (d_feat ? kDnFeat : 0)) * n * sizeof(double));
+    if (rc) return rc;
+    double *state[2] = {reinterpret_cast<double *>(c->dn_planes.p), reinterpret_cast<double *>(c->dn_planes.p) + kDnState * n};
+    double *fplanes = d_feat ? state[1] + kDnState * n : nullptr;
+    const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(denoise_load_kernel, dim3(blocks), dim3(kBlock), 0, st, d_lin, d_se, d_feat, n, state[0], fplanes);
+    HIP_TRY(hipGetLastError());
+    const int use_c = d_se && sigma_c > 0.0, use_n = d_feat && sigma_n > 0.0, use_a = d_feat && sigma_a > 0.0, use_d = d_feat && sigma_d > 0.0;
+    int cur = 0;
+    for (int i = 0; i < iterations; ++i, cur = 1 - cur) {
+        hipLaunchKernelGGL(denoise_pass_kernel, dim3((unsigned)((nx + 63) / 64), (unsigned)((ny + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st,
+                           state[cur], state[1 - cur], fplanes, nx, ny, 1 << i, use_c, use_n, use_a, use_d, sigma_c * sigma_c, sigma_n * sigma_n,
+                           sigma_a * sigma_a, sigma_d * sigma_d);
+        HIP_TRY(hipGetLastError());
+    }
+    if (d_out_lin || d_out_q || d_out_se) {
+        hipLaunchKernelGGL(denoise_store_kernel, dim3(blocks), dim3(kBlock), 0, st, state[cur], n, iterations == 0 ? d_se : (const double *)nullptr, d_out_lin,
+                           d_out_q, d_out_se);
+        HIP_TRY(hipGetLastError());
+    }
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_denoise_device(rtmi_ctx *c, int32_t nx, int32_t ny, const void *d_linear_in, const void *d_stderr_in, const void *d_features_in,
+                                    int32_t iterations, double sigma_c, double sigma_n, double sigma_a, double sigma_d,
+                                    void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *stream) {
+    int rc = check_denoise_args(nx, ny, d_linear_in, iterations, sigma_c, sigma_n, sigma_a, sigma_d);
+    if (rc) return rc;
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    return denoise_impl(c, nx, ny, reinterpret_cast<const double *>(d_linear_in), reinterpret_cast<const double *>(d_stderr_in),
+                        reinterpret_cast<const double *>(d_features_in), iterations, sigma_c, sigma_n, sigma_a, sigma_d,
+                        reinterpret_cast<double *>(d_out_linear), reinterpret_cast<unsigned char *>(d_out_rgb8), reinterpret_cast<double *>(d_out_stderr), st);
+}
+
+RTMI_EXPORT int rtmi_denoise(rtmi_ctx *c, int32_t nx, int32_t ny, const double *linear_in, const double *stderr_in, const double *features_in,
+                             int32_t iterations, double sigma_c, double sigma_n, double sigma_a, double sigma_d,
+                             double *out_linear, uint8_t *out_rgb8, double *out_stderr) {
+    int rc = check_denoise_args(nx, ny, linear_in, iterations, sigma_c, sigma_n, sigma_a, sigma_d);
+    if (rc) return rc;
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)nx * (size_t)ny;
+    // in: linear 3n, stderr n, features 8n doubles; out: linear 3n, stderr n doubles, rgb8 3n bytes
+    rc = c->dn_io.ensure(16 * n * sizeof(double) + 3 * n);
+    if (rc) return rc;
+    double *d_lin = reinterpret_cast<double *>(c->dn_io.p), *d_se = d_lin + 3 * n, *d_feat = d_se + n, *d_olin = d_feat + 8 * n, *d_ose = d_olin + 3 * n;
+    unsigned char *d_oq = reinterpret_cast<unsigned char *>(d_ose + n);
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(d_lin, linear_in, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+    if (stderr_in) HIP_TRY(hipMemcpy(d_se, stderr_in, n * sizeof(double), hipMemcpyHostToDevice));
+    if (features_in) HIP_TRY(hipMemcpy(d_feat, features_in, 8 * n * sizeof(double), hipMemcpyHostToDevice));
+    rc = denoise_impl(c, nx, ny, d_lin, stderr_in ? d_se : nullptr, features_in ? d_feat : nullptr, iterations, sigma_c, sigma_n, sigma_a, sigma_d,
+                      out_linear ? d_olin : nullptr, out_rgb8 ? d_oq : nullptr, out_stderr ? d_ose : nullptr, st);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out_linear) HIP_TRY(hipMemcpy(out_linear, d_olin, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_oq, 3 * n, hipMemcpyDeviceToHost));
+    if (out_stderr) HIP_TRY(hipMemcpy(out_stderr, d_ose, n * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
 }
