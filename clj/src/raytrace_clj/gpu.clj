@@ -429,6 +429,76 @@
       {:linear out :rgb8 rgb :stderr err}
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn adaptive-retire
+  "Retire the active tiles of context `ctx`'s progressive frame whose pixels all pass noise <= eps (rtmi_adaptive_retire; a NaN fails): `noise`
+  holds [ny][nx] doubles of the whole frame, row 0 = top -- :stderr of `denoise` as it is.  Adds no samples.  Returns the number of tiles this
+  call retired.  The device form (rtmi_adaptive_retire_device) takes an HBM pointer and a stream instead: see adaptive-retire-device."
+  [ctx nx ny noise eps]
+  (let [m   (double-array noise)
+        out (int-array 1)]
+    (check (call-int "rtmi_adaptive_retire" ctx (int nx) (int ny) m (double eps) out))
+    (aget out 0)))
+
+(defn adaptive-retire-device
+  "adaptive-retire on a map resident in HBM: `d-noise` and `stream` are com.sun.jna.Pointer (stream nil = the context's own stream).  The call
+  synchronises the stream once, at its end.  (The one device-buffer entry this file binds: the conformance reader has no category for device
+  pointers, so the call is made on the Function itself, with the same coercions as every call-int form.)"
+  [ctx nx ny ^Pointer d-noise eps ^Pointer stream]
+  (let [out (int-array 1)]
+    (check (.invokeInt (cfn "rtmi_adaptive_retire_device") (object-array [ctx (int nx) (int ny) d-noise (double eps) out stream])))
+    (aget out 0)))
+
+(defn render-adaptive-denoised
+  "Render scene {:camera :world} adaptively on GPU `device` for a frame that is denoised anyway: the feature buffers once (:feature-samples,
+  default 4), then rounds as in render-adaptive; per round rtmi_render_adaptive with the raw rule at eps 0 (only tiles whose samples are all
+  equal retire), rtmi_denoise of the frame with its standard error and the features (:iterations, :sigma-c ... as `denoise`), and
+  rtmi_adaptive_retire of the tiles whose FILTERED standard error is <= eps everywhere.  After each round (on-round m), m = what render-adaptive
+  passes (with :active-tiles taken after the retirement) plus :denoised {:linear :rgb8 :stderr}.  The arrays are refilled by the next round.
+  on-round returning :stop ends the render early.  Returns the last m."
+  [scene nx ny ns chunk eps on-round & {:keys [first-round feature-samples iterations sigma-c sigma-n sigma-a sigma-d depth seed device precision]
+                                        :or {feature-samples 4 iterations 5 sigma-c 4.0 sigma-n 0.5 sigma-a 0.2 sigma-d 0.2
+                                             depth 50 seed 0x5eed0002 device 0 precision 0}}]
+  (let [f     (flatten-scene scene)
+        ctx   (PointerByReference.)
+        npx   (* nx ny)
+        lin   (double-array (* 3 npx))
+        rgb   (byte-array (* 3 npx))
+        err   (double-array npx)
+        smp   (int-array npx)
+        cnt   (long-array 2)
+        ft    (double-array (* 8 npx))
+        fcnt  (long-array 2)
+        flin  (double-array (* 3 npx))
+        frgb  (byte-array (* 3 npx))
+        ferr  (double-array npx)
+        ret   (int-array 1)
+        act   (int-array 1)
+        tot   (int-array 1)
+        pxs   (long-array 1)
+        head  (or first-round chunk)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_features" scn (int nx) (int ny) (int feature-samples) (long seed) (int precision)
+                           (int 0) (int 0) (int nx) (int ny) ft fcnt))
+          (loop [k 0]
+            (let [n (min (if (zero? k) head chunk) (- ns k))]
+              (check (call-int "rtmi_render_adaptive" scn (int nx) (int ny) (int k) (int n) (double 0.0) (int depth) (long seed) (int precision)
+                               (int 0) (int 0) (int nx) (int ny) lin rgb err smp cnt))
+              (check (call-int "rtmi_denoise" (.getValue ctx) (int nx) (int ny) lin err ft (int iterations) (double sigma-c) (double sigma-n)
+                               (double sigma-a) (double sigma-d) flin frgb ferr))
+              (check (call-int "rtmi_adaptive_retire" (.getValue ctx) (int nx) (int ny) ferr (double eps) ret))
+              (check (call-int "rtmi_adaptive_status" (.getValue ctx) act tot pxs))
+              (let [k' (+ k n)
+                    m  {:samples k' :rgb8 rgb :linear lin :stderr err :pixel-samples smp :total-rays (aget cnt 0) :total-pixels (aget cnt 1)
+                        :active-tiles (aget act 0) :total-tiles (aget tot 0) :denoised {:linear flin :rgb8 frgb :stderr ferr}}]
+                (if (and (not= :stop (on-round m)) (< k' ns) (pos? (aget act 0)))
+                  (recur k')
+                  m))))
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn render-multi
   "The same on every GPU in `devices` from this one JVM (rtmi_render_multi): one context per device, the scene created on
   the first (Perlin tables, ImageMap pixels and media calls included) and cloned onto the others (rtmi_scene_clone), the 8x8

@@ -278,6 +278,28 @@ int rtmi_adaptive_status(rtmi_ctx *ctx, int32_t *active_tiles, int32_t *total_ti
  * device (an adaptive call has synchronised its stream when it returns).  Without a frame: 0 and RTMI_OK. */
 int rtmi_adaptive_active_tiles(rtmi_ctx *ctx, int32_t capacity, int32_t *out_tiles, int32_t *out_count);
 
+/* ---- retiring tiles by a noise map the caller supplies (a filtered estimate, a relative or display-space error, a region-of-interest mask) ----
+ * rtmi_adaptive_retire*(ctx, nx, ny, noise, eps, out_retired) acts on the context's one progressive frame and only on its per-tile state: it adds
+ * no samples and leaves k, every n_t, the sums, the noise state, the counters and the key as they are.
+ *   noise: [ny][nx] doubles of the WHOLE frame, row 0 = top, whatever the frame's region -- the layout of rtmi_denoise's out_stderr, whose device
+ *          buffer can be handed to the device form as it is.  nx and ny must be the frame's.
+ * An ACTIVE tile is RETIRED if every pixel of it that lies inside the image and the frame's region passes noise <= eps.  The comparison is
+ * written exactly so: a NaN fails, +inf fails, -inf and negative values pass.  Pixels outside the region (and of tiles that are not active) are
+ * not read.  There is no k >= 2 rule here: the caller owns the criterion.  Retirement is permanent for the life of the frame, as above; the
+ * active list stays in ascending tile order.  out_retired (may be NULL) receives the number of tiles this call retired.
+ * A frame started by rtmi_render_progressive is converted exactly as the first rtmi_render_adaptive call converts it: every tile active, n_t = k.
+ * Afterwards rtmi_render_adaptive* behaves as documented (it traces the tiles still active), rtmi_adaptive_status and
+ * rtmi_adaptive_active_tiles reflect the result, and rtmi_render_progressive with s_first > 0 is refused with RTMI_E_STATE once a tile has
+ * retired -- and still allowed if nothing has.
+ * Errors: noise NULL, eps negative, NaN or infinite, nx or ny <= 0: RTMI_E_ARG, reported before the handle is examined.  No frame, or nx / ny not
+ * the frame's: RTMI_E_STATE, rtmi_last_error names what differs.  A failure before anything is launched leaves the frame as it was, a failure
+ * after a launch drops it.  A call on a frame with no active tile launches nothing: RTMI_OK, 0 retired. */
+/* host buffer */
+int rtmi_adaptive_retire(rtmi_ctx *ctx, int32_t nx, int32_t ny, const double *noise, double eps, int32_t *out_retired);
+/* device buffer, launched on `stream` with rtmi_render_device's stream semantics.  Like rtmi_render_adaptive_device it synchronises the stream
+ * once, at its end: the host mirrors the length of the active list. */
+int rtmi_adaptive_retire_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, const void *d_noise, double eps, int32_t *out_retired, void *stream);
+
 /* ---- first-hit feature buffers: per-pixel albedo, normal, depth and coverage of a frame (what an edge-aware filter reads) ----
  * out_features: [rows][cols][RTMI_FEATURES] doubles, row 0 = top, of the region (host form) or the whole frame (device form):
  *   channels 0-2 albedo rgb, 3-5 normal xyz, 6 depth, 7 coverage.

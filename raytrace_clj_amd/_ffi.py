@@ -29,6 +29,7 @@ SYMBOLS = [
     "rtmi_render_progressive", "rtmi_render_progressive_device", "rtmi_progressive_samples", "rtmi_progressive_release",
     "rtmi_render_adaptive", "rtmi_render_adaptive_device", "rtmi_adaptive_status", "rtmi_adaptive_active_tiles",
     "rtmi_render_features", "rtmi_render_features_device", "rtmi_denoise", "rtmi_denoise_device",
+    "rtmi_adaptive_retire", "rtmi_adaptive_retire_device",
 ]
 
 F64, F32 = 0, 1
@@ -114,7 +115,9 @@ def lib():
     L.rtmi_render_adaptive_device.argtypes = [vp, i32, i32, i32, i32, dbl, i32, u64, i32, vp, vp, vp, vp, vp, vp]
     L.rtmi_adaptive_status.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
     L.rtmi_adaptive_active_tiles.argtypes = [vp, i32, vp, C.POINTER(i32)]
-    L.rtmi_render_features.argtypes = [vp, i32, i32, i32, u64, i32, i32, i32, i32, i32, vp, vp]
+    L.rtmi_adaptive_retire.argtypes = [vp, i32, i32, vp, dbl, C.POINTER(i32)]
+    L.rtmi_adaptive_retire_device.argtypes = [vp, i32, i32, vp, dbl, C.POINTER(i32), vp]
+    L.rtmi_render_features.argtypes =[vp, i32, i32, i32, u64, i32, i32, i32, i32, i32, vp, vp]
     L.rtmi_render_features_device.argtypes = [vp, i32, i32, i32, u64, i32, vp, vp, vp]
     L.rtmi_denoise.argtypes = [vp, i32, i32, vp, vp, vp, i32, dbl, dbl, dbl, dbl, vp, vp, vp]
     L.rtmi_denoise_device.argtypes = [vp, i32, i32, vp, vp, vp, i32, dbl, dbl, dbl, dbl, vp, vp, vp, vp]

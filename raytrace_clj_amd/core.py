@@ -101,6 +101,24 @@ class Context:
             check(_ffi.lib().rtmi_adaptive_active_tiles(self.handle, n.value, ptr(out), C.byref(n)))
         return out
 
+    def adaptive_retire(self, noise, eps):
+        """Retire the active tiles of the context's progressive frame whose pixels inside the frame's region all pass noise <= eps (a NaN
+        fails) -> the number of tiles this call retired.  noise: [ny, nx] float64 of the WHOLE frame, row 0 = top -- denoise's stderr as it
+        is.  No samples are added; the frame's sums, sample counts and counters stay as they are."""
+        m = np.ascontiguousarray(noise, np.float64)
+        if m.ndim != 2:
+            raise ValueError("noise must be [ny, nx]")
+        n = C.c_int32()
+        check(_ffi.lib().rtmi_adaptive_retire(self.handle, m.shape[1], m.shape[0], ptr(m), float(eps), C.byref(n)))
+        return n.value
+
+    def adaptive_retire_device(self, nx, ny, noise, eps, stream=None):
+        """adaptive_retire on an HBM-resident map (a torch tensor or a raw device pointer; render_device's stream semantics; synchronises the
+        stream once, at the end of the call: the host reads the number of tiles still active) -> the number of tiles retired"""
+        n = C.c_int32()
+        check(_ffi.lib().rtmi_adaptive_retire_device(self.handle, nx, ny, ptr(noise), float(eps), C.byref(n), ptr(stream)))
+        return n.value
+
     # ---- the edge-aware denoiser: a pure image operation (rtmi_denoise*) ---------------------------------------------------------
     def denoise(self, linear, stderr=None, features=None, iterations=DENOISE_ITERATIONS, sigma_c=DENOISE_SIGMA_C, sigma_n=DENOISE_SIGMA_N,
                 sigma_a=DENOISE_SIGMA_A, sigma_d=DENOISE_SIGMA_D):
@@ -325,6 +343,32 @@ class DeviceScene:
             self.ctx.progressive_release()
         ft, _ = self.render_features(nx, ny, na, seed, precision)
         return raw, ft, self.ctx.denoise(raw[0], raw[2], ft, **denoise)
+
+    def refine_adaptive_denoised(self, nx, ny, ns, chunk, eps, first=None, na=FEATURE_SAMPLES, iterations=DENOISE_ITERATIONS,
+                                 sigma_c=DENOISE_SIGMA_C, sigma_n=DENOISE_SIGMA_N, sigma_a=DENOISE_SIGMA_A, sigma_d=DENOISE_SIGMA_D,
+                                 depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64"):
+        """Adaptive sampling steered by the noise estimate of the DENOISED frame: for a frame that will be filtered anyway, a tile stops taking
+        samples once the filter has cleaned it.  The feature buffers are rendered once (na samples); then per round: render_adaptive with the raw
+        rule at eps 0 (it retires only tiles whose samples are all equal), denoise of the frame with its standard error and the features,
+        adaptive_retire of the tiles whose filtered standard error is <= eps everywhere.  Yields (k, linear, rgb8, stderr, samples, counters,
+        active tiles after the retirement, filtered linear, filtered rgb8, filtered stderr) after every round and ends at ns or when no tile is
+        active, like refine_adaptive.  Whole frame only (the filter is a whole-frame operation).  Every tile of the unfiltered frame equals
+        render(ns = the samples it holds); the filtered frame is denoise of that frame."""
+        first = chunk if first is None else first
+        if chunk <= 0 or ns <= 0 or first <= 0:
+            raise ValueError("ns, chunk and first must be > 0")
+        ft, _ = self.render_features(nx, ny, na, seed, precision)
+        k = 0
+        while k < ns:
+            n = min(first if k == 0 else chunk, ns - k)
+            lin, q, err, smp, cnt = self.render_adaptive(nx, ny, k, n, 0.0, depth, seed, precision)
+            k += n
+            flt, fq, ferr = self.ctx.denoise(lin, err, ft, iterations, sigma_c, sigma_n, sigma_a, sigma_d)
+            self.ctx.adaptive_retire(ferr, eps)
+            active = self.ctx.adaptive_status()[0]
+            yield k, lin, q, err, smp, cnt, active, flt, fq, ferr
+            if active == 0:
+                break
 
     def render_tiles_device(self, nx, ny, ns, tile_first, tile_stride, out_tiles, out_counters=None, depth=DEFAULT_DEPTH,
                             seed=RENDER_SEED, precision="f64", stream=None):
@@ -602,6 +646,37 @@ def _denoise_flags(argv):
     return rest, iterations, na
 
 
+def _adaptive_denoised_flags(argv):
+    """-> (the other arguments, eps): --adaptive-denoised EPS, checked here, before any device work (None when absent).  It is a stopping rule
+    of its own: it does not combine with --adaptive or --noise."""
+    import math
+    rest, eps = [], None
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        key, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") else (a, None)
+        i += 1
+        if key != "--adaptive-denoised":
+            rest.append(a)
+            continue
+        if val is None:
+            if i >= len(argv):
+                raise SystemExit("--adaptive-denoised needs a value")
+            val = argv[i]
+            i += 1
+        try:
+            eps = float(val)
+        except ValueError:
+            raise SystemExit("--adaptive-denoised %r is not a number" % val)
+        if not (math.isfinite(eps) and eps >= 0):
+            raise SystemExit("--adaptive-denoised must be a finite number >= 0 (got %r)" % val)
+    if eps is not None:
+        for other in ("--adaptive", "--noise"):
+            if any(a.split("=", 1)[0] == other for a in rest):
+                raise SystemExit("--adaptive-denoised and %s are two stopping rules: give one of them" % other)
+    return rest, eps
+
+
 def _denoised_name(name):
     """x.png -> x.denoised.png: the filtered image is written next to the unfiltered one"""
     import os
@@ -646,12 +721,19 @@ def main(argv=None):
     samples it took.  --budget applies; --noise does not combine with it.
     --denoise [ITERATIONS] also writes the frame filtered by the edge-aware denoiser (Context.denoise, default sigmas, ITERATIONS passes, default
     5) next to the unfiltered one, as name.denoised.ext; --feature-samples N sets the samples of its feature buffers (default 4).  It works with
-    every mode above; the unfiltered file and the progress lines are what they are without it."""
+    every mode above; the unfiltered file and the progress lines are what they are without it.
+    --adaptive-denoised EPS samples adaptively for a frame that is filtered anyway (refine_adaptive_denoised, rounds of --chunk, default 16):
+    after every round the frame is denoised and an 8x8 tile stops taking samples once the FILTERED standard error of all its pixels is <= EPS.
+    It writes name.ext unfiltered and name.denoised.ext, prints the "samples: mean ..." line, implies --denoise with the defaults unless
+    --denoise / --feature-samples are given, obeys --budget and does not combine with --adaptive or --noise."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
+    argv, adaptive_denoised = _adaptive_denoised_flags(argv)
+    if adaptive_denoised is not None and not any(a.split("=", 1)[0] == "--denoise" for a in argv):
+        argv.append("--denoise")  # implied, with the default passes; --feature-samples then belongs to it
     argv, dn_iterations, dn_samples = _denoise_flags(argv)
     argv, chunk, budget, noise, adaptive = _progressive_flags(argv)
-    if chunk is None and (budget is not None or noise is not None or adaptive is not None):
+    if chunk is None and (budget is not None or noise is not None or adaptive is not None or adaptive_denoised is not None):
         chunk = 16
     name = argv[0] if len(argv) > 0 else "render.png"  # core.clj:76
     nx = int(argv[1]) if len(argv) > 1 else 200
@@ -674,6 +756,21 @@ def main(argv=None):
             elapsed = time.time() - tstart
             print("%.2fs, %d%%, ETA %.2fs" % (elapsed, 100, 0.0))  # display.clj:20-24
             filtered = _denoise_frame(ds, nx, ny, lin, err, dn_iterations, dn_samples)
+        finally:
+            ds.ctx.progressive_release()
+            ds.close()
+    elif adaptive_denoised is not None:
+        ds = DeviceScene(sc)
+        try:
+            na = FEATURE_SAMPLES if dn_samples is None else dn_samples
+            for k, lin, rgb8, err, smp, cnt, active, flt, filtered, ferr in ds.refine_adaptive_denoised(nx, ny, nr, chunk, adaptive_denoised, na=na,
+                                                                                                      iterations=dn_iterations):
+                elapsed = _show_progress(tstart, k, nr)
+                if budget is not None and elapsed > budget and k < nr and active:
+                    print("stopped at %d of %d samples (budget %gs)" % (k, nr, budget))
+                    break
+            active, total, pixel_samples = ds.ctx.adaptive_status()
+            print("samples: mean %.2f of %d per pixel, %d of %d tiles converged" % (pixel_samples / max(int(cnt[1]), 1), nr, total - active, total))
         finally:
             ds.ctx.progressive_release()
             ds.close()

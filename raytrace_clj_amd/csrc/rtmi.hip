@@ -1031,6 +1031,28 @@ __global__ void __launch_bounds__(kBlock) adaptive_resolve_kernel(const R *__res
     if (out_samples) out_samples[gid] = k;
 }
 
+// rtmi_adaptive_retire*: the decision of adaptive_fold_kernel's last pass taken on a noise map the caller supplies.  One wave per entry of the active
+// list, lane l = pixel l of the entry's 8x8 tile: the wave reads eight 64-byte row segments of the whole-frame map [ny][nx] at the tile's place in the
+// IMAGE (act_tiles: the global tile; act_slots, the tile's place in the frame's state, is not needed here), only where the pixel lies inside the
+// region clipped to the image.  keep[entry] = 1 if any such pixel fails noise <= eps (a NaN fails).  adaptive_compact_kernel follows.
+__global__ void __launch_bounds__(kBlock) adaptive_retire_kernel(const double *__restrict__ noise, const int *__restrict__ act_tiles, int n_active,
+                                                                 int tiles_x, int nx, int rx0, int ry0, int rx1, int ry1, double eps,
+                                                                 int *__restrict__ keep) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)n_active * 64) return; // (whole waves: kBlock is a multiple of 64)
+    const int entry = (int)(gid >> 6), l = (int)(gid & 63);
+    const int gtile = act_tiles[entry];
+    const int x = (gtile % tiles_x) * RTMI_TILE + (l & 7), y = (gtile / tiles_x) * RTMI_TILE + (l >> 3);
+    const bool valid = x >= rx0 && x < rx1 && y >= ry0 && y < ry1; // rx1 <= nx, ry1 <= ny: the load below stays inside the map
+    bool noisy = false;
+    if (valid) {
+        const double v = noise[(size_t)y * (size_t)nx + (size_t)x];
+        noisy = !(v <= eps);
+    }
+    const u64 any = __ballot(noisy);
+    if (l == 0) keep[entry] = any != 0ull ? 1 : 0;
+}
+
 // ---- first-hit feature pass (rtmi_render_features*) -------------------------------------------------------------------------------------------
 // One wave per 8x8 tile of the window of tiles that covers the region, one lane per pixel, four waves per workgroup (the LDS stack columns of the
 // probe kernels: column = threadIdx.x).  Lane l loops over the feature samples s = 0 .. na-1 of its pixel: the first segment of the path render
@@ -1755,7 +1777,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 207; } // 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 208; } // 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -2435,6 +2457,105 @@ RTMI_EXPORT int rtmi_adaptive_active_tiles(rtmi_ctx *c, int32_t capacity, int32_
         for (int i = 0; i < n; ++i) out_tiles[i] = (ty0 + i / wtx) * tx_n + tx0 + i % wtx;
     }
     return RTMI_OK;
+}
+
+// ---- retiring tiles by a noise map the caller supplies (rtmi_adaptive_retire*) -------------------------------------------------------------------
+namespace {
+int check_retire_args(int nx, int ny, const void *noise, double eps) {
+    if (nx <= 0 || ny <= 0) return fail(RTMI_E_ARG, "nx, ny must be > 0 (got %d %d)", nx, ny);
+    if (!noise) return fail(RTMI_E_ARG, "noise is NULL");
+    if (!(eps >= 0.0) || std::isinf(eps)) return fail(RTMI_E_ARG, "eps must be a finite number >= 0 (got %g)", eps);
+    return RTMI_OK;
+}
+
+int check_retire_frame(const rtmi_ctx *c, int nx, int ny) {
+    const ProgFrame &f = c->prog;
+    if (f.k == 0) return fail(RTMI_E_STATE, "the context holds no progressive frame to retire tiles of (rtmi_render_adaptive or rtmi_render_progressive with s_first = 0 starts one)");
+    if (nx != f.key.nx || ny != f.key.ny) return fail(RTMI_E_STATE, "nx x ny = %d x %d, the progressive frame is %d x %d", nx, ny, f.key.nx, f.key.ny);
+    return RTMI_OK;
+}
+
+// Retires the active tiles of the context's frame whose pixels all pass d_noise <= eps (a device pointer to the whole-frame map) and synchronises
+// `st`: the host reads the length of the next active list.  Nothing but the active list, its length and its pixel count changes.
+int adaptive_retire_impl(rtmi_ctx *c, const double *d_noise, double eps, int32_t *out_retired, hipStream_t st) {
+    ProgFrame &f = c->prog;
+    const int nx = f.key.nx, ny = f.key.ny;
+    const int rx0 = std::max(f.key.rg[0], 0), ry0 = std::max(f.key.rg[1], 0), rx1 = std::min(f.key.rg[2], nx), ry1 = std::min(f.key.rg[3], ny);
+    if (!f.adaptive) { // a uniform frame: the per-tile state as the first adaptive call builds it, every tile active with n_t = k
+        int n_local = 0;
+        int rc = ensure_tile_ids(c, nx, ny, 0, 1, f.key.rg, st, &n_local); // (another render on the context may have rewritten its tile list)
+        const size_t ints = (size_t)std::max(n_local, 1) * sizeof(int);
+        for (int i = 0; i < 2 && !rc; ++i) { rc = f.act_tiles[i].ensure(ints); if (!rc) rc = f.act_slots[i].ensure(ints); }
+        if (!rc) rc = f.n_t.ensure(ints);
+        if (!rc) rc = f.keep.ensure(ints);
+        if (!rc) rc = f.meta.ensure(2 * sizeof(int));
+        if (rc) return rc;
+        if (n_local != f.n_tiles) return fail(RTMI_E_STATE, "progressive frame buffers do not match the frame"); // (unreachable: the key is the frame's own)
+        f.cur = 0;
+        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kCompactBlock), 0, st, (const int *)nullptr, reinterpret_cast<const int *>(c->tile_ids.p),
+                           (const int *)nullptr, n_local, reinterpret_cast<int *>(f.act_tiles[0].p), reinterpret_cast<int *>(f.act_slots[0].p),
+                           reinterpret_cast<int *>(f.meta.p), f.k, reinterpret_cast<int *>(f.n_t.p), tiles_x_of(nx), rx0, ry0, rx1, ry1);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { f.k = 0; return fail(RTMI_E_DEVICE, "adaptive retire: %s", hipGetErrorString(e)); }
+        f.adaptive = true;
+        f.n_active = n_local; f.active_pixels = f.valid_pixels;
+        f.pixel_samples = f.valid_pixels * (long long)f.k;
+    }
+    if (out_retired) *out_retired = 0;
+    if (f.n_active == 0) return RTMI_OK; // nothing to decide, nothing launched
+    const int n = f.n_active, nxt = 1 - f.cur;
+    const int *tile_list = reinterpret_cast<const int *>(f.act_tiles[f.cur].p);
+    hipLaunchKernelGGL(adaptive_retire_kernel, dim3((unsigned)(((long long)n * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_noise, tile_list, n,
+                       tiles_x_of(nx), nx, rx0, ry0, rx1, ry1, eps, reinterpret_cast<int *>(f.keep.p));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kCompactBlock), 0, st, reinterpret_cast<const int *>(f.keep.p), tile_list,
+                           reinterpret_cast<const int *>(f.act_slots[f.cur].p), n, reinterpret_cast<int *>(f.act_tiles[nxt].p),
+                           reinterpret_cast<int *>(f.act_slots[nxt].p), reinterpret_cast<int *>(f.meta.p), -1, (int *)nullptr, tiles_x_of(nx), rx0, ry0,
+                           rx1, ry1);
+        e = hipGetLastError();
+    }
+    int meta[2] = {0, 0};
+    if (e == hipSuccess) e = hipMemcpyAsync(meta, f.meta.p, sizeof meta, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { f.k = 0; return fail(RTMI_E_DEVICE, "adaptive retire: %s", hipGetErrorString(e)); }
+    f.cur = nxt;
+    f.n_active = meta[0]; f.active_pixels = meta[1];
+    if (out_retired) *out_retired = n - meta[0];
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_adaptive_retire_device(rtmi_ctx *c, int32_t nx, int32_t ny, const void *d_noise, double eps, int32_t *out_retired, void *stream) {
+    int rc = check_retire_args(nx, ny, d_noise, eps);
+    if (rc) return rc;
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    rc = check_retire_frame(c, nx, ny);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    return adaptive_retire_impl(c, reinterpret_cast<const double *>(d_noise), eps, out_retired, st);
+}
+
+RTMI_EXPORT int rtmi_adaptive_retire(rtmi_ctx *c, int32_t nx, int32_t ny, const double *noise, double eps, int32_t *out_retired) {
+    int rc = check_retire_args(nx, ny, noise, eps);
+    if (rc) return rc;
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    rc = check_retire_frame(c, nx, ny);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const ProgFrame &f = c->prog;
+    if (f.adaptive && f.n_active == 0) { // nothing to decide: no upload, no launch
+        if (out_retired) *out_retired = 0;
+        return RTMI_OK;
+    }
+    const size_t n = (size_t)nx * (size_t)ny;
+    rc = c->dn_io.ensure(n * sizeof(double)); // the host forms' staging buffer for maps of the frame's size
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(c->dn_io.p, noise, n * sizeof(double), hipMemcpyHostToDevice));
+    return adaptive_retire_impl(c, reinterpret_cast<const double *>(c->dn_io.p), eps, out_retired, st);
 }
 
 // ---- one host process, several GPUs (the reference's host is ONE JVM: core.clj:100-108) ---------------------------------

@@ -1,6 +1,6 @@
 """Adaptive sampling on the GPU, measured: what it buys and what it costs when it buys nothing.
 
-    python scripts/gpu_adaptive.py [--out DIR] [step ...]      steps: buys-C3 buys-FINAL cost-C3 kernels (default: all, in this order)
+    python scripts/gpu_adaptive.py [--out DIR] [step ...]      steps: buys-C3 buys-FINAL cost-C3 kernels denoised (default: all, in this order)
 
 Every step is a child process of its own under a time limit; the first one that fails (or runs out of time) ends the run, nothing is started after
 it.  Each step writes DIR/<step>.json.  Times are device events on one stream around the whole sequence of calls of a variant, after a warm-up,
@@ -11,7 +11,12 @@ median of 5, with the compared variants alternated in the same process.
   buys-FINAL  make-final 500x500, first 32, chunk 32, cap 128: the same
   cost-C3     C3 as 4 x 64 with eps = 0 (no tile retires: checked) against refine 4 x 64, the progressive path; the progressive run is
               measured twice per repetition, the difference of its two medians is its own spread
-  kernels     rocprofv3 --kernel-trace --stats over one adaptive C3 run: time per call of the three adaptive kernels"""
+  kernels     rocprofv3 --kernel-trace --stats over one adaptive C3 run: time per call of the three adaptive kernels
+  denoised    adaptive sampling steered by the denoised frame's noise estimate, two children: (1) C3: one
+              rtmi_adaptive_retire_device call (kernel + compaction + synchronise) next to the adaptive round it follows; then the Cornell box
+              600x600 and C3, first 64, chunk 64, cap 256, eps = the median per-tile maximum of the first round's filtered noise: time and
+              pixel-samples of render_adaptive -> denoise -> adaptive_retire against uniform-at-cap + denoise and against the raw criterion
+              at the same eps; (2) rocprofv3 --kernel-trace --stats over one such C3 run, in a run of its own: adaptive_retire_kernel's line"""
 import argparse
 import csv
 import glob
@@ -25,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-STEPS = {"buys-C3": 420, "buys-FINAL": 300, "cost-C3": 300, "kernels": 300}  # step -> time limit in seconds
+STEPS = {"buys-C3": 420, "buys-FINAL": 300, "cost-C3": 300, "kernels": 300, "denoised": 540}  # step -> time limit in seconds
 REPS = 5
 
 
@@ -34,6 +39,9 @@ def _scene(which):
     if which == "C3":
         nx, ny = 1920, 1080
         return r.scene.make_random_scene(nx, ny, 50, False, mix=(0.8, 0.95)), nx, ny, 64, 64, 256
+    if which == "CB":
+        nx, ny = 600, 600
+        return r.scene.make_cornell_box(nx, ny), nx, ny, 64, 64, 256
     nx, ny = 500, 500
     return r.scene.make_final(nx, ny), nx, ny, 32, 32, 128
 
@@ -78,6 +86,51 @@ class Bench:
             self.ds.render_adaptive_device(self.nx, self.ny, k, n, eps, self.lin, self.q, self.err, self.spp, self.cnt, stream=self.stream)
             if self.ctx.adaptive_status()[0] == 0:
                 break
+
+    def filter_buffers(self):
+        """the buffers of the adaptive-denoised loop: the features (rendered here, once) and the filtered frame"""
+        t, nx, ny = self.torch, self.nx, self.ny
+        with t.cuda.stream(self.side):
+            self.ft = t.zeros((ny, nx, 8), dtype=t.float64, device="cuda")
+            self.flin = t.zeros((ny, nx, 3), dtype=t.float64, device="cuda")
+            self.fq = t.zeros((ny, nx, 3), dtype=t.uint8, device="cuda")
+            self.ferr = t.zeros((ny, nx), dtype=t.float64, device="cuda")
+        self.ds.render_features_device(nx, ny, self.core.FEATURE_SAMPLES, self.ft, None, stream=self.stream)
+        self.side.synchronize()
+
+    def denoise(self):
+        self.ctx.denoise_device(self.nx, self.ny, self.lin, self.err, self.ft, self.flin, self.fq, self.ferr, stream=self.stream)
+
+    def uniform_denoised(self):
+        """uniform at the cap with its noise estimate, then the filter: the existing path"""
+        self.ds.render_progressive_device(self.nx, self.ny, 0, self.cap, self.lin, self.q, self.err, self.cnt, stream=self.stream)
+        self.denoise()
+
+    def adaptive_then_denoise(self, eps):
+        """the raw criterion, the frame filtered once at the end"""
+        self.adaptive(eps)
+        self.denoise()
+
+    def adaptive_denoised(self, eps):
+        """one stream, no host copy: render_adaptive (raw rule at eps 0) -> denoise -> adaptive_retire on the filtered noise plane"""
+        for k, n in self.rounds():
+            self.ds.render_adaptive_device(self.nx, self.ny, k, n, 0.0, self.lin, self.q, self.err, self.spp, self.cnt, stream=self.stream)
+            self.denoise()
+            self.ctx.adaptive_retire_device(self.nx, self.ny, self.ferr, eps, stream=self.stream)
+            if self.ctx.adaptive_status()[0] == 0:
+                break
+
+    def first_round_filtered_tile_noise(self):
+        """per-tile maxima of the filtered noise plane after the first round of a uniform frame"""
+        import numpy as np
+        self.ds.render_progressive_device(self.nx, self.ny, 0, self.first, self.lin, None, self.err, None, stream=self.stream)
+        self.denoise()
+        self.side.synchronize()
+        e = self.ferr.cpu().numpy()
+        ty, tx = (self.ny + 7) // 8, (self.nx + 7) // 8
+        pad = np.full((ty * 8, tx * 8), -np.inf)
+        pad[:self.ny, :self.nx] = e
+        return pad.reshape(ty, 8, tx, 8).max(axis=(1, 3)).ravel()
 
     def timed(self, fn):
         t = self.torch
@@ -158,6 +211,79 @@ def step_cost():
         b.close()
 
 
+def step_retire_cost():
+    """C3: the first adaptive round (64 samples, the raw rule at eps 0) and the rtmi_adaptive_retire_device call that follows it, on a filtered
+    noise plane computed once; every repetition starts a new frame, so the retire call does the same work each time"""
+    import numpy as np
+    b = Bench("C3")
+    try:
+        b.filter_buffers()
+        noise = b.first_round_filtered_tile_noise()
+        eps = float(np.quantile(noise[np.isfinite(noise)], 0.5))
+        t = b.torch
+        rounds, retires, retired = [], [], []
+        for rep in range(REPS + 1):  # the first repetition is the warm-up
+            ev = [t.cuda.Event(enable_timing=True) for _ in range(3)]
+            with t.cuda.stream(b.side):
+                ev[0].record(b.side)
+                b.ds.render_adaptive_device(b.nx, b.ny, 0, b.first, 0.0, b.lin, b.q, b.err, b.spp, b.cnt, stream=b.stream)
+                ev[1].record(b.side)
+                n = b.ctx.adaptive_retire_device(b.nx, b.ny, b.ferr, eps, stream=b.stream)
+                ev[2].record(b.side)
+            b.side.synchronize()
+            if rep:
+                rounds.append(ev[0].elapsed_time(ev[1]))
+                retires.append(ev[1].elapsed_time(ev[2]))
+                retired.append(n)
+        return {"scene": "C3", "eps": eps, "tiles": int(noise.size), "tiles_retired_per_call": retired, "adaptive_round_64spp": _summary(rounds),
+                "retire_call": _summary(retires)}
+    finally:
+        b.close()
+
+
+def step_denoised_buys(which):
+    import numpy as np
+    b = Bench(which)
+    try:
+        b.filter_buffers()
+        noise = b.first_round_filtered_tile_noise()
+        eps = float(np.quantile(noise[np.isfinite(noise)], 0.5))
+        samples = {}
+
+        def run(name, fn):
+            def go():
+                fn()
+                samples[name] = b.ctx.adaptive_status()
+            return go
+
+        ms = b.alternate({"uniform_cap_denoise": run("uniform_cap_denoise", b.uniform_denoised),
+                          "adaptive_raw_then_denoise": run("adaptive_raw_then_denoise", lambda: b.adaptive_then_denoise(eps)),
+                          "adaptive_denoised": run("adaptive_denoised", lambda: b.adaptive_denoised(eps))})
+        full = b.nx * b.ny * b.cap
+        out = {"scene": which, "nx": b.nx, "ny": b.ny, "first": b.first, "chunk": b.chunk, "cap": b.cap, "eps": eps, "tiles": int(noise.size)}
+        for name in ms:
+            active, total, pixel_samples = samples[name]
+            out[name] = dict(_summary(ms[name]), share_of_pixel_samples=pixel_samples / full, tiles_active_at_end=active)
+        return out
+    finally:
+        b.close()
+
+
+def step_denoised_profiled_run():
+    """what `denoised` runs under rocprofv3: one warm-up and one adaptive-denoised C3 run at the median eps"""
+    import numpy as np
+    b = Bench("C3")
+    try:
+        b.filter_buffers()
+        noise = b.first_round_filtered_tile_noise()
+        eps = float(np.quantile(noise[np.isfinite(noise)], 0.5))
+        for _ in range(2):
+            b.adaptive_denoised(eps)
+        b.side.synchronize()
+    finally:
+        b.close()
+
+
 def step_profiled_run():
     """what `kernels` runs under rocprofv3: one warm-up and one adaptive C3 run at the median eps"""
     import numpy as np
@@ -172,16 +298,16 @@ def step_profiled_run():
         b.close()
 
 
-def step_kernels(out_dir, limit):
-    d = os.path.join(out_dir, "kernel_trace")
+def step_kernels(out_dir, limit, child_step="profiled-run", sub="kernel_trace", keep=("adaptive_", "trace_kernel")):
+    d = os.path.join(out_dir, sub)
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "adaptive", "--output-format", "csv", "--", "timeout", "-k", "10", str(max(30, limit - 30)), sys.executable, os.path.abspath(__file__),
-           "--child", "profiled-run", "--out", out_dir]
+           "--child", child_step, "--out", out_dir]
     subprocess.run(cmd, check=True, timeout=limit, cwd=ROOT)
     rows = []
     for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
         for row in csv.DictReader(open(path)):
             name = row.get("Name") or row.get("KernelName") or ""
-            if "adaptive_" in name or "trace_kernel" in name:
+            if any(k in name for k in keep):
                 rows.append({"kernel": name.split("(")[0][:120], "calls": int(row["Calls"]), "total_ms": float(row["TotalDurationNs"]) * 1e-6,
                              "average_ms": float(row["AverageNs"]) * 1e-6})
     assert rows, "no kernel statistics found under %s" % d
@@ -192,7 +318,13 @@ def child(step, out_dir):
     if step == "profiled-run":
         step_profiled_run()
         return
-    res = step_buys(step.split("-")[1]) if step.startswith("buys-") else step_cost()
+    if step == "denoised-profiled-run":
+        step_denoised_profiled_run()
+        return
+    if step == "denoised":
+        res = {"retire_cost": step_retire_cost(), "buys": [step_denoised_buys("CB"), step_denoised_buys("C3")]}
+    else:
+        res = step_buys(step.split("-")[1]) if step.startswith("buys-") else step_cost()
     with open(os.path.join(out_dir, step + ".json"), "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
@@ -220,6 +352,11 @@ def main():
                 print(json.dumps(res))
             else:
                 subprocess.run([sys.executable, os.path.abspath(__file__), "--child", step, "--out", a.out], check=True, timeout=STEPS[step], cwd=ROOT)
+                if step == "denoised":  # the new kernel's line, from a profiled run of its own
+                    res = step_kernels(a.out, 300, "denoised-profiled-run", "kernel_trace_denoised", ("adaptive_", "denoise_", "trace_kernel"))
+                    with open(os.path.join(a.out, "denoised_kernels.json"), "w") as f:
+                        json.dump(res, f, indent=1)
+                    print(json.dumps(res))
         except (subprocess.CalledProcessError, subprocess.TimeoutExpired, AssertionError) as e:
             print("step %s failed: %s -- stopping, nothing else is started" % (step, e), flush=True)
             return 1
