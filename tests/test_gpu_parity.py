@@ -1077,6 +1077,10 @@ def test_f32_precision_matches_f32_oracle(oracle_f32, cover11_moving):
     ds = core.DeviceScene(f)
     got, exp = ds.probe_hit(rays, precision="f32"), oracle_f32.probe_hit(f, rays)
     assert np.array_equal(got[:, :9], exp[:, :9]), "f32 geometry is bit-exact too (IEEE float + - * / sqrt, no contraction)"
+    hit = exp[:, 0] == 1  # uv: atan2f / asinf, ocml vs glibc -- twice the float oracle's own 1.81 * 2^-24 against FP64 and the two divisions (tests/test_gpu_f32.py)
+    uv_err = float(np.abs(got[hit, 9:11] - exp[hit, 9:11]).max())
+    print("f32 uv err %.3g (%.2f * 2^-24)" % (uv_err, uv_err * 2.0 ** 24))
+    assert uv_err <= 6 * 2.0 ** -24 and np.any(exp[hit, 9:11] != 0), uv_err
     n = 4096
     keys = np.array([sample_key(5, i, 0) for i in range(n)], np.uint64)
     uv = np.random.default_rng(3).random((n, 2))
