@@ -524,6 +524,48 @@
           (finally (doseq [s scenes] (call-int "rtmi_scene_destroy" s)))))
       (finally (doseq [c ctxs] (call-int "rtmi_shutdown" c))))))
 
+(defn render-multi-adaptive
+  "render-adaptive on every GPU in `devices` from this one JVM (rtmi_render_multi_adaptive): contexts and scene replicas as in render-multi, the
+  8x8 tiles of the ONE frame dealt round-robin, every replica refining its own tiles, one gather of the tile records per round, assembled on the
+  first device.  Rounds, on-round, m and the return value are render-adaptive's (:active-tiles and :total-tiles summed over the devices);
+  :retire false gives the progressive rule (no tile retires, eps is not read).  Every array is bit-identical to render-adaptive's on one GPU."
+  [scene nx ny ns chunk eps on-round & {:keys [first-round retire depth seed devices precision]
+                                        :or {retire true depth 50 seed 0x5eed0002 devices [0] precision 0}}]
+  (let [f     (flatten-scene scene)
+        npx   (* nx ny)
+        lin   (double-array (* 3 npx))
+        rgb   (byte-array (* 3 npx))
+        err   (double-array npx)
+        smp   (int-array npx)
+        cnt   (long-array 2)
+        act   (int-array 1)
+        tot   (int-array 1)
+        pxs   (long-array 1)
+        head  (or first-round chunk)
+        ctxs  (mapv (fn [d] (let [ctx (PointerByReference.)] (check (call-int "rtmi_init" (int d) (int 0) ctx)) (.getValue ctx))) devices)]
+    (try
+      (let [scn0   (create-scene! (first ctxs) f)
+            clones (mapv (fn [c] (let [scn (PointerByReference.)] (check (call-int "rtmi_scene_clone" scn0 c scn)) (.getValue scn)))
+                         (rest ctxs))
+            scenes (into [scn0] clones)
+            handles (into-array com.sun.jna.Pointer scenes)
+            status (fn [] (reduce (fn [[a t] c] (check (call-int "rtmi_adaptive_status" c act tot pxs)) [(+ a (aget act 0)) (+ t (aget tot 0))])
+                                  [0 0] ctxs))]
+        (try
+          (loop [k 0]
+            (let [n (min (if (zero? k) head chunk) (- ns k))]
+              (check (call-int "rtmi_render_multi_adaptive" (int (count scenes)) handles (int nx) (int ny) (int k) (int n) (int (if retire 1 0))
+                               (double eps) (int depth) (long seed) (int precision) lin rgb err smp cnt))
+              (let [k'              (+ k n)
+                    [active total]  (status)
+                    m  {:samples k' :rgb8 rgb :linear lin :stderr err :pixel-samples smp :total-rays (aget cnt 0) :total-pixels (aget cnt 1)
+                        :active-tiles active :total-tiles total}]
+                (if (and (not= :stop (on-round m)) (< k' ns) (pos? active))
+                  (recur k')
+                  m))))
+          (finally (doseq [s scenes] (call-int "rtmi_scene_destroy" s)))))
+      (finally (doseq [c ctxs] (call-int "rtmi_shutdown" c))))))
+
 (defn save-ppm
   "imagez `save` (core.clj:112) has no PPM writer; binary P6 written here"
   [filename ^bytes rgb8 nx ny]

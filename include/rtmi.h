@@ -370,6 +370,40 @@ int rtmi_denoise_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, const void *d_lin
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,
                          const void *d_gathered, void *d_out_linear, void *d_out_rgb8, void *stream);
 
+/* ---- progressive and adaptive frames on dealt tiles: the per-device primitive of a frame refined on several GPUs ----
+ * rtmi_render_adaptive_tiles_device is to rtmi_render_progressive* / rtmi_render_adaptive* what rtmi_render_tiles_device is to rtmi_render: the
+ * context's one progressive frame covers the DEALT tiles tile_first, tile_first + tile_stride, ... (global row-major tile indices over
+ * ceil(nx/8) x ceil(ny/8); rtmi_local_tiles of them; local tile k is global tile tile_first + k * tile_stride), its region is the whole image,
+ * and the call writes tile records instead of a dense frame.
+ *   The dealing is part of the frame's key.  The entries above are the dealing (0, 1): a whole-frame (0, 1) frame may be continued by either
+ *   family; a continuation with another dealing is RTMI_E_STATE and rtmi_last_error names both dealings.
+ *   retire = 0: rtmi_render_progressive's semantics on those tiles -- samples [s_first, s_first + s_count) to every tile, no tile retires, eps is
+ *               not read; refused with RTMI_E_STATE (frame untouched) if a tile of the frame has retired.
+ *   retire = 1: rtmi_render_adaptive's two steps with eps (trace the active tiles, then retire those whose pixels all pass se <= eps at k >= 2),
+ *               under the same argument rules.
+ *   d_tiles_rec[k][64][RTMI_PROG_REC] doubles, may be NULL: local tile k, pixel l = row * 8 + column of the tile.  With n_t the samples the tile holds:
+ *               values 0-2 the mean over samples [0, n_t), computed with the resolve's own expression sums * (R(1) / R(n_t)) in the precision R of
+ *               the frame and widened to double; value 3 the standard error exactly as rtmi_render_adaptive's out_stderr defines it (+inf for
+ *               n_t = 1); value 4 n_t as a double.  Pixels outside the image hold five zeros.
+ *   d_out_counters, may be NULL: {ray segments traced into this frame so far, pixels of the dealt tiles that lie inside the image}.
+ * Like rtmi_render_adaptive_device the call synchronises the stream once, at its end, for either value of retire.
+ * rtmi_progressive_samples, rtmi_adaptive_status, rtmi_adaptive_active_tiles (global tile indices, ascending), rtmi_adaptive_retire* (the map is
+ * still the WHOLE frame's [ny][nx]; only the frame's own active tiles are read) and rtmi_progressive_release work on a dealt frame as they do on
+ * a whole one.  A rank dealt no tile (tile_first beyond the last tile) holds an empty frame that still counts its samples.
+ * Errors: tile_first < 0, tile_stride <= 0, s_first < 0, s_count <= 0, retire outside {0, 1}, with retire = 1 an eps that is negative, NaN or
+ * infinite: RTMI_E_ARG, reported before the handle is examined; the others are the progressive calls'.  A failure before anything is launched
+ * leaves the frame as it was; a failure after a launch drops it. */
+#define RTMI_PROG_REC 5   /* doubles per pixel of a progressive tile record: mean r, g, b, stderr, samples */
+int rtmi_render_adaptive_tiles_device(rtmi_scene *scene, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count,
+                                      int32_t retire, double eps, int32_t depth, uint64_t seed, int32_t precision,
+                                      int32_t tile_first, int32_t tile_stride, void *d_tiles_rec, void *d_out_counters, void *stream);
+/* After the gather of such records: d_gathered_rec[r][k][64][RTMI_PROG_REC] (r < world, k < tiles_per_rank as for rtmi_assemble_device, rank r's
+ * k-th tile is global tile r + k*world; slots past the last tile are ignored) -> the dense frame.  Outputs, each of which may be NULL:
+ * linear [ny][nx][3] doubles, rgb8 (assemble_device's quantiser on the mean: the double one, whatever the frame's precision), stderr [ny][nx]
+ * doubles, samples [ny][nx] int32.  Asynchronous on `stream` (rtmi_render_device's stream semantics). */
+int rtmi_assemble_progressive_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,
+                                     const void *d_gathered_rec, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_samples, void *stream);
+
 /* ---- one host process, several GPUs ---------------------------------------------------------------
  * The reference's host is ONE JVM whose render loop fans out over a thread pool (cp/upmap, core.clj:100-108); the same
  * single process reaches the 8 GPUs of a node through these entries: one context per device (rtmi_init), the scene
@@ -395,6 +429,27 @@ int rtmi_render_multi(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t 
  * renders on its own context stream). */
 int rtmi_render_multi_device(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t ny, int32_t ns, int32_t depth, uint64_t seed,
                              int32_t precision, void *d_out_linear, void *d_out_rgb8, void *d_out_counters);
+/* One progressive / adaptive frame refined on n devices: every replica r calls rtmi_render_adaptive_tiles_device's work with the dealing (r, n)
+ * on its own context stream (the launches of the replicas overlap), ONE gather -- the paths and RTMI_MULTI_GATHER values above: same-device
+ * copies, peer copies, the grouped ncclGather with its count scaled to the larger record; n = 1 launches none -- moves the records to replica 0's
+ * device, and replica 0 assembles.  Outputs as rtmi_render_adaptive's for the whole frame, each may be NULL; out_counters = {ray segments
+ * summed over the replicas, pixels of the frame}.  retire and eps as for rtmi_render_adaptive_tiles_device.
+ * For every n, either gather path, F64 and F32, sphere-only and mixed-kind scenes, any sequence of chunk sizes and any "workspace_bytes" split,
+ * out_linear, out_rgb8, out_stderr, out_samples and out_counters[0] are BIT-IDENTICAL to what one context returns from rtmi_render_adaptive for
+ * the whole frame after the same calls (with retire = 0: from rtmi_render_progressive), and the union of the replicas' active lists
+ * (rtmi_adaptive_active_tiles on each context) is that context's active list: pixels are independent, every draw is keyed by (seed, global pixel,
+ * sample), and a tile retires on its own pixels alone.
+ * The argument checks and the continuation checks of ALL replicas run before the first launch: a mismatch on any replica (RTMI_E_STATE, the text
+ * names the replica) leaves every frame as it was.  A failure after a launch drops the frame on EVERY replica -- a later s_first > 0 is refused
+ * on the whole set -- and every stream touched so far is synchronised before the call returns.  Both forms return with every replica's stream
+ * synchronised (the host mirrors every replica's active list), so rtmi_adaptive_status / rtmi_adaptive_retire* may follow on each context. */
+int rtmi_render_multi_adaptive(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count,
+                               int32_t retire, double eps, int32_t depth, uint64_t seed, int32_t precision,
+                               double *out_linear, uint8_t *out_rgb8, double *out_stderr, int32_t *out_samples, uint64_t *out_counters);
+/* The same, outputs resident on replica 0's device. */
+int rtmi_render_multi_adaptive_device(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count,
+                                      int32_t retire, double eps, int32_t depth, uint64_t seed, int32_t precision,
+                                      void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_samples, void *d_out_counters);
 /* How the last rtmi_render_multi* on replica 0's context moved the replicas' records to replica 0's device. */
 enum { RTMI_GATHER_NONE = 0,        /* one replica: nothing to move */
        RTMI_GATHER_SAME_DEVICE = 1, /* replicas share replica 0's device (rehearsal on a one-GPU host): device-to-device copies */

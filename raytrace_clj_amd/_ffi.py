@@ -30,6 +30,7 @@ SYMBOLS = [
     "rtmi_render_adaptive", "rtmi_render_adaptive_device", "rtmi_adaptive_status", "rtmi_adaptive_active_tiles",
     "rtmi_render_features", "rtmi_render_features_device", "rtmi_denoise", "rtmi_denoise_device",
     "rtmi_adaptive_retire", "rtmi_adaptive_retire_device",
+    "rtmi_render_adaptive_tiles_device", "rtmi_assemble_progressive_device", "rtmi_render_multi_adaptive", "rtmi_render_multi_adaptive_device",
 ]
 
 F64, F32 = 0, 1
@@ -38,6 +39,7 @@ FLAG_TIMING = 1
 GATHER_PATHS = {0: "none", 1: "same-device", 2: "peer-copy", 3: "rccl"}
 SEG_REC = 12
 TILE = 8
+PROG_REC = 5  # doubles per pixel of a progressive tile record: mean rgb, stderr, samples
 FEATURES = 8  # doubles per pixel of rtmi_render_features: albedo rgb, normal xyz, depth, coverage
 
 
@@ -121,6 +123,10 @@ def lib():
     L.rtmi_render_features_device.argtypes = [vp, i32, i32, i32, u64, i32, vp, vp, vp]
     L.rtmi_denoise.argtypes = [vp, i32, i32, vp, vp, vp, i32, dbl, dbl, dbl, dbl, vp, vp, vp]
     L.rtmi_denoise_device.argtypes = [vp, i32, i32, vp, vp, vp, i32, dbl, dbl, dbl, dbl, vp, vp, vp, vp]
+    L.rtmi_render_adaptive_tiles_device.argtypes = [vp, i32, i32, i32, i32, i32, dbl, i32, u64, i32, i32, i32, vp, vp, vp]
+    L.rtmi_assemble_progressive_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.rtmi_render_multi_adaptive.argtypes = [i32, C.POINTER(vp), i32, i32, i32, i32, i32, dbl, i32, u64, i32, vp, vp, vp, vp, vp]
+    L.rtmi_render_multi_adaptive_device.argtypes = [i32, C.POINTER(vp), i32, i32, i32, i32, i32, dbl, i32, u64, i32, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

@@ -112,6 +112,13 @@ class Context:
         check(_ffi.lib().rtmi_adaptive_retire(self.handle, m.shape[1], m.shape[0], ptr(m), float(eps), C.byref(n)))
         return n.value
 
+    def assemble_progressive_device(self, nx, ny, world, tiles_per_rank, gathered_rec, out_linear=None, out_rgb8=None, out_stderr=None,
+                                    out_samples=None, stream=None):
+        """gathered tile records [world, tiles_per_rank, 64, 5] (rank r's k-th tile is global tile r + k * world) -> the dense frame: linear,
+        rgb8, stderr [ny, nx] float64, samples [ny, nx] int32, HBM-resident, each may be None; asynchronous, render_device's stream semantics"""
+        check(_ffi.lib().rtmi_assemble_progressive_device(self.handle, nx, ny, world, tiles_per_rank, ptr(gathered_rec), ptr(out_linear),
+                                                          ptr(out_rgb8), ptr(out_stderr), ptr(out_samples), ptr(stream)))
+
     def adaptive_retire_device(self, nx, ny, noise, eps, stream=None):
         """adaptive_retire on an HBM-resident map (a torch tensor or a raw device pointer; render_device's stream semantics; synchronises the
         stream once, at the end of the call: the host reads the number of tiles still active) -> the number of tiles retired"""
@@ -374,6 +381,16 @@ class DeviceScene:
                             seed=RENDER_SEED, precision="f64", stream=None):
         check(_ffi.lib().rtmi_render_tiles_device(self.handle, nx, ny, ns, depth, seed, _PRECISION[precision],
                                                   tile_first, tile_stride, ptr(out_tiles), ptr(out_counters), ptr(stream)))
+
+    def render_adaptive_tiles_device(self, nx, ny, s_first, s_count, retire, eps, tile_first, tile_stride, out_tiles_rec=None, out_counters=None,
+                                     depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", stream=None):
+        """The per-device primitive of a progressive / adaptive frame on several GPUs: samples [s_first, s_first + s_count) into the context's
+        frame over the dealt tiles tile_first, tile_first + tile_stride, ... (retire: render_adaptive's two steps with eps, else
+        render_progressive's one), the tiles' records [local tiles, 64, 5] float64 (mean rgb, stderr, samples) into out_tiles_rec and
+        {segments so far, pixels of the dealt tiles} into out_counters, both HBM-resident.  Synchronises the stream once, at its end."""
+        check(_ffi.lib().rtmi_render_adaptive_tiles_device(self.handle, nx, ny, s_first, s_count, int(retire), float(eps), depth, seed,
+                                                           _PRECISION[precision], tile_first, tile_stride, ptr(out_tiles_rec), ptr(out_counters),
+                                                           ptr(stream)))
 
     # ---- probes ------------------------------------------------------------------------------------------
     def probe_hit(self, rays, t_min=T_MIN, t_max=T_MAX, precision="f64"):

@@ -1053,6 +1053,71 @@ __global__ void __launch_bounds__(kBlock) adaptive_retire_kernel(const double *_
     if (l == 0) keep[entry] = any != 0ull ? 1 : 0;
 }
 
+// ---- dealt progressive frames (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*) ------------------
+// The frame's local tiles are the dealt tiles first, first + stride, ...: local slot t holds global tile first + t * stride, so no rectangular window
+// describes them.  The resolve therefore writes tile RECORDS, rec[t][64][RTMI_PROG_REC]: what adaptive_resolve_kernel computes per pixel -- the mean
+// sums * (R(1) / R(n_t)) widened to double, the largest channel's standard error (+inf for n_t = 1), n_t -- in tile order, the layout a gather moves.
+// n_t = null: a uniform frame, every tile holds k samples.  One thread per pixel of the n_slots record slots; slots past the frame's n_local tiles
+// (the padding of a gathered record) and pixels outside the image hold five zeros.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) progressive_record_kernel(const R *__restrict__ sums, const double *__restrict__ m2, const int *__restrict__ n_t,
+                                                                    int k_uniform, int first, int stride, int tiles_x, int nx, int ny, int n_local,
+                                                                    int n_slots, double *__restrict__ rec) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)n_slots * 64) return;
+    const int t = (int)(gid >> 6), l = (int)(gid & 63);
+    double *o = rec + (size_t)gid * RTMI_PROG_REC;
+    bool inside = false;
+    if (t < n_local) {
+        const long long gtile = (long long)first + (long long)t * stride; // < tiles of the frame: t < n_local
+        const int x = (int)(gtile % tiles_x) * RTMI_TILE + (l & 7), y = (int)(gtile / tiles_x) * RTMI_TILE + (l >> 3);
+        inside = x < nx && y < ny;
+    }
+    if (!inside) {
+#pragma unroll
+        for (int c = 0; c < RTMI_PROG_REC; ++c) o[c] = 0.0;
+        return;
+    }
+    const size_t e = (size_t)gid * 3;
+    const int k = n_t ? n_t[t] : k_uniform;
+    double err = k > 1 ? 0.0 : INFINITY;
+    for (int c = 0; c < 3; ++c) {
+        o[c] = (double)(sums[e + c] * (R(1.0) / (R)k)); // reduce_kernel's last pass
+        if (k > 1) {
+            const double se = ::sqrt((m2[e + c] / (double)(k - 1)) / (double)k); // progressive_resolve_kernel's expression
+            err = se > err ? se : err;
+        }
+    }
+    o[3] = err;
+    o[4] = (double)k;
+}
+
+// gathered[r][k][64][RTMI_PROG_REC] (rank r's k-th tile is global tile r + k * world; rank_stride = doubles per rank record) -> the dense frame:
+// assemble_kernel<double> for the mean (the same quantiser), the standard error and the sample count beside it.  Any output may be null.
+__global__ void __launch_bounds__(kBlock) assemble_progressive_kernel(const double *__restrict__ gathered, int world, size_t rank_stride, int tiles_x,
+                                                                      int nx, int ny, double *__restrict__ out_linear, unsigned char *__restrict__ out_rgb8,
+                                                                      double *__restrict__ out_stderr, int *__restrict__ out_samples) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)nx * ny) return;
+    const int x = (int)(gid % nx), y = (int)(gid / nx);
+    const int gtile = (y / RTMI_TILE) * tiles_x + (x / RTMI_TILE);
+    const int r = gtile % world, k = gtile / world;
+    const int l = (y % RTMI_TILE) * RTMI_TILE + (x % RTMI_TILE);
+    const double *p = gathered + (size_t)r * rank_stride + ((size_t)k * 64 + l) * RTMI_PROG_REC;
+    for (int c = 0; c < 3; ++c) {
+        const double m = p[c];
+        if (out_linear) out_linear[gid * 3 + c] = m;
+        if (out_rgb8) { // assemble_kernel<double>
+            const double q = Real<double>::sqrt_(m) * 255.99;
+            unsigned char o = 0;
+            if (q == q) { const double mq = q < 255.99 ? q : 255.99; o = (unsigned char)(int)mq; }
+            out_rgb8[gid * 3 + c] = o;
+        }
+    }
+    if (out_stderr) out_stderr[gid] = p[3];
+    if (out_samples) out_samples[gid] = (int)p[4];
+}
+
 // ---- first-hit feature pass (rtmi_render_features*) -------------------------------------------------------------------------------------------
 // One wave per 8x8 tile of the window of tiles that covers the region, one lane per pixel, four waves per workgroup (the LDS stack columns of the
 // probe kernels: column = threadIdx.x).  Lane l loops over the feature samples s = 0 .. na-1 of its pixel: the first segment of the path render
@@ -1235,6 +1300,7 @@ struct ProgKey {
     uint64_t scene_serial = 0, scene_revision = 0, seed = 0;
     int nx = 0, ny = 0, depth = 0, precision = 0;
     int rg[4] = {0, 0, 0, 0};
+    int first = 0, stride = 1; // the dealing: the frame's local tiles are the global tiles first, first + stride, ... ((0, 1): every tile of the region)
 };
 
 // A context's progressive frame (rtmi_render_progressive*): the state progressive_fold_kernel keeps (sums in the precision of the frame, Welford
@@ -1252,10 +1318,14 @@ struct ProgFrame {
     bool adaptive = false;
     int cur = 0, n_tiles = 0, n_active = 0;
     long long valid_pixels = 0, active_pixels = 0, pixel_samples = 0;
+    int *meta_host = nullptr;  // pinned copy of `meta`: a dealt call's copy-back must not block the host while the other replicas are launched
+    bool meta_pending = false; // a dealt call traced tiles: meta_host holds the next active list's length once its stream is synchronised
     void release() {
         sums.release(); mean.release(); m2.release(); counters.release();
         for (int i = 0; i < 2; ++i) { act_tiles[i].release(); act_slots[i].release(); }
         n_t.release(); keep.release(); meta.release();
+        if (meta_host) (void)hipHostFree(meta_host);
+        meta_host = nullptr; meta_pending = false;
         k = 0; adaptive = false; cur = n_tiles = n_active = 0; valid_pixels = active_pixels = pixel_samples = 0;
     }
 };
@@ -1594,7 +1664,7 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
     if (rc) return rc;
     if (d_counters && !prog) HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(u64), st));
     HIP_TRY(hipMemsetAsync(reinterpret_cast<u64 *>(c->counters.p) + 3, 0, 2 * sizeof(u64), st));
-    if (n_local == 0) return RTMI_OK;
+    if (n_local == 0) { if (prog) { prog->k = s_end; c->last_passes = 0; } return RTMI_OK; } // (a dealt frame on a rank beyond the last tile: an empty frame that still counts its calls)
     if (ad) n_local = prog->n_active; // an adaptive call traces and folds the frame's active list, not the render's tile list
     if (n_local == 0) { prog->k = s_end; c->last_passes = 0; return RTMI_OK; } // every tile has retired: nothing to trace, k advances
     const int *tile_list = ad ? reinterpret_cast<const int *>(prog->act_tiles[prog->cur].p) : reinterpret_cast<const int *>(c->tile_ids.p);
@@ -1777,7 +1847,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 208; } // 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 209; } // 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -2238,6 +2308,8 @@ int check_continuation(const rtmi_ctx *c, const ProgKey &k, int s_first) {
     if (k.precision != a.precision) return fail(RTMI_E_STATE, "precision = %d, the progressive frame was started with %d", k.precision, a.precision);
     if (std::memcmp(k.rg, a.rg, sizeof k.rg))
         return fail(RTMI_E_STATE, "region [%d,%d)x[%d,%d), the progressive frame was started with [%d,%d)x[%d,%d)", k.rg[0], k.rg[2], k.rg[1], k.rg[3], a.rg[0], a.rg[2], a.rg[1], a.rg[3]);
+    if (k.first != a.first || k.stride != a.stride)
+        return fail(RTMI_E_STATE, "tile dealing (first %d, stride %d), the progressive frame was started with the dealing (first %d, stride %d)", k.first, k.stride, a.first, a.stride);
     return RTMI_OK;
 }
 
@@ -2451,6 +2523,8 @@ RTMI_EXPORT int rtmi_adaptive_active_tiles(rtmi_ctx *c, int32_t capacity, int32_
     HIP_TRY(hipSetDevice(c->device));
     if (f.adaptive) { // the frame's own list, as the last compaction left it (every adaptive call ends with its stream synchronised)
         HIP_TRY(hipMemcpy(out_tiles, f.act_tiles[f.cur].p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    } else if (f.key.first != 0 || f.key.stride != 1) { // a uniform dealt frame (its region is the whole image): the dealing itself
+        for (int i = 0; i < n; ++i) out_tiles[i] = f.key.first + i * f.key.stride;
     } else { // a uniform frame: every tile of the region, in tile order
         const int tx_n = tiles_x_of(f.key.nx), tx0 = f.key.rg[0] / RTMI_TILE, ty0 = f.key.rg[1] / RTMI_TILE;
         const int wtx = (f.key.rg[2] + RTMI_TILE - 1) / RTMI_TILE - tx0;
@@ -2483,7 +2557,7 @@ int adaptive_retire_impl(rtmi_ctx *c, const double *d_noise, double eps, int32_t
     const int rx0 = std::max(f.key.rg[0], 0), ry0 = std::max(f.key.rg[1], 0), rx1 = std::min(f.key.rg[2], nx), ry1 = std::min(f.key.rg[3], ny);
     if (!f.adaptive) { // a uniform frame: the per-tile state as the first adaptive call builds it, every tile active with n_t = k
         int n_local = 0;
-        int rc = ensure_tile_ids(c, nx, ny, 0, 1, f.key.rg, st, &n_local); // (another render on the context may have rewritten its tile list)
+        int rc = ensure_tile_ids(c, nx, ny, f.key.first, f.key.stride, f.key.rg, st, &n_local); // (another render on the context may have rewritten its tile list)
         const size_t ints = (size_t)std::max(n_local, 1) * sizeof(int);
         for (int i = 0; i < 2 && !rc; ++i) { rc = f.act_tiles[i].ensure(ints); if (!rc) rc = f.act_slots[i].ensure(ints); }
         if (!rc) rc = f.n_t.ensure(ints);
@@ -2822,6 +2896,330 @@ RTMI_EXPORT int rtmi_render_multi(int32_t n, rtmi_scene *const *scenes, int32_t 
     if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_q, npx * 3, hipMemcpyDeviceToHost));
     if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
     for (int r = 1; r < n; ++r) { HIP_TRY(hipSetDevice(scenes[r]->ctx->device)); HIP_TRY(hipStreamSynchronize(scenes[r]->ctx->stream)); scenes[r]->ctx->consume_pending = false; }
+    return RTMI_OK;
+}
+
+// ---- progressive and adaptive frames on dealt tiles: the per-device primitive, the assemble, the one-process driver -------------------------------
+namespace {
+// the checks of a dealt call that need no frame; failing one leaves every frame as it was
+int check_adaptive_tiles_args(rtmi_scene *s, int nx, int ny, int s_first, int s_count, int retire, double eps, int depth, int precision, int tile_first,
+                              int tile_stride) {
+    if (tile_first < 0 || tile_stride <= 0) return fail(RTMI_E_ARG, "tile_first must be >= 0 and tile_stride > 0 (got %d, %d)", tile_first, tile_stride);
+    if (s_first < 0 || s_count <= 0) return fail(RTMI_E_ARG, "s_first must be >= 0 and s_count > 0 (got %d, %d)", s_first, s_count);
+    if (retire != 0 && retire != 1) return fail(RTMI_E_ARG, "retire must be 0 or 1 (got %d)", retire);
+    if (retire && (!(eps >= 0.0) || std::isinf(eps))) return fail(RTMI_E_ARG, "eps must be a finite number >= 0 (got %g)", eps);
+    return check_progressive_args(s, nx, ny, s_first, s_count, depth, precision);
+}
+
+ProgKey dealt_key(const rtmi_scene *s, int nx, int ny, int depth, uint64_t seed, int precision, int tile_first, int tile_stride) {
+    const int whole[4] = {0, 0, nx, ny};
+    ProgKey k = progressive_key(s, nx, ny, depth, seed, precision, whole);
+    k.first = tile_first; k.stride = tile_stride;
+    return k;
+}
+
+int check_dealt_continuation(const rtmi_ctx *c, const ProgKey &key, int s_first, int retire) {
+    int rc = check_continuation(c, key, s_first);
+    if (!rc && !retire) rc = check_no_tile_retired(c, s_first);
+    return rc;
+}
+
+// Enqueues on `st`: samples [s_first, s_first + s_count) into the context's dealt frame (retire: rtmi_render_adaptive's two steps, else
+// rtmi_render_progressive's one), the records of its local tiles into d_rec[n_slots][64][RTMI_PROG_REC] (n_slots >= the local tiles: the rest is
+// zeroed), the cumulative counters into d_cnt, and the copy-back of the next active list's length.  Nothing waits: dealt_finish does.
+template <typename R>
+int dealt_launch(rtmi_scene *s, const ProgKey &key, int s_first, int s_count, int retire, double eps, double *d_rec, int n_slots, void *d_cnt,
+                 hipStream_t st) {
+    ProgFrame &f = s->ctx->prog;
+    if (!f.meta_host && hipHostMalloc(reinterpret_cast<void **>(&f.meta_host), 2 * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+        f.meta_host = nullptr;
+        (void)hipGetLastError();
+        return fail(RTMI_E_NOMEM, "hipHostMalloc(%zu bytes) failed", 2 * sizeof(int));
+    }
+    f.meta_pending = false;
+    AdaptiveCall ad;
+    ad.eps = eps; ad.k_before = s_first;
+    int rc = render_passes<R>(s, key.nx, key.ny, s_first, s_first + s_count, key.depth, key.seed, key.first, key.stride, key.rg, nullptr, nullptr, st, &f,
+                              retire ? &ad : nullptr);
+    if (rc) return rc;
+    f.key = key;
+    hipError_t e = hipSuccess;
+    if (d_rec && n_slots > 0) {
+        const long long npx = (long long)n_slots * 64;
+        hipLaunchKernelGGL((progressive_record_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                           reinterpret_cast<const R *>(f.sums.p), reinterpret_cast<const double *>(f.m2.p),
+                           f.adaptive ? reinterpret_cast<const int *>(f.n_t.p) : (const int *)nullptr, f.k, key.first, key.stride, tiles_x_of(key.nx), key.nx,
+                           key.ny, f.n_tiles, n_slots, d_rec);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && d_cnt) e = hipMemcpyAsync(d_cnt, f.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToDevice, st);
+    const bool traced = retire && f.n_active > 0; // (the list this call started with: no trace, no compaction, meta unchanged)
+    if (e == hipSuccess && traced) e = hipMemcpyAsync(f.meta_host, f.meta.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) { f.k = 0; return fail(RTMI_E_DEVICE, "dealt resolve: %s", hipGetErrorString(e)); }
+    f.meta_pending = traced;
+    return RTMI_OK;
+}
+
+// Waits for `st` and brings the host's mirror of the frame's per-tile state up to date (render_adaptive_impl's last lines).
+int dealt_finish(rtmi_ctx *c, int s_count, int retire, hipStream_t st) {
+    ProgFrame &f = c->prog;
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { f.k = 0; f.meta_pending = false; return fail(RTMI_E_DEVICE, "dealt render: %s", hipGetErrorString(e)); }
+    if (retire) {
+        f.pixel_samples += f.active_pixels * (long long)s_count; // the tiles active when the call started took its samples
+        if (f.meta_pending) { f.n_active = f.meta_host[0]; f.active_pixels = f.meta_host[1]; }
+    }
+    f.meta_pending = false;
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_adaptive_tiles_device(rtmi_scene *s, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t retire, double eps,
+                                                  int32_t depth, uint64_t seed, int32_t precision, int32_t tile_first, int32_t tile_stride,
+                                                  void *d_tiles_rec, void *d_out_counters, void *stream) {
+    int rc = check_adaptive_tiles_args(s, nx, ny, s_first, s_count, retire, eps, depth, precision, tile_first, tile_stride);
+    if (rc) return rc;
+    const ProgKey key = dealt_key(s, nx, ny, depth, seed, precision, tile_first, tile_stride);
+    rc = check_dealt_continuation(s->ctx, key, s_first, retire);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
+    const int n_slots = rtmi_local_tiles(nx, ny, tile_first, tile_stride);
+    double *rec = reinterpret_cast<double *>(d_tiles_rec);
+    if (precision == RTMI_F64) rc = dealt_launch<double>(s, key, s_first, s_count, retire, eps, rec, n_slots, d_out_counters, st);
+    else rc = dealt_launch<float>(s, key, s_first, s_count, retire, eps, rec, n_slots, d_out_counters, st);
+    if (rc) return rc;
+    return dealt_finish(s->ctx, s_count, retire, st);
+}
+
+RTMI_EXPORT int rtmi_assemble_progressive_device(rtmi_ctx *c, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank, const void *d_gathered_rec,
+                                                 void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_samples, void *stream) {
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    if (nx <= 0 || ny <= 0 || world <= 0 || tiles_per_rank <= 0 || !d_gathered_rec) return fail(RTMI_E_ARG, "bad assemble arguments");
+    if ((long long)nx * ny > (1ll << 30)) return fail(RTMI_E_ARG, "frame too large");
+    const int ntiles = tiles_x_of(nx) * tiles_y_of(ny);
+    if ((long long)world * tiles_per_rank < ntiles) return fail(RTMI_E_ARG, "world*tiles_per_rank (%d*%d) does not cover %d tiles", world, tiles_per_rank, ntiles);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    const long long npx = (long long)nx * ny;
+    hipLaunchKernelGGL(assemble_progressive_kernel, dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                       reinterpret_cast<const double *>(d_gathered_rec), world, (size_t)tiles_per_rank * 64 * RTMI_PROG_REC, tiles_x_of(nx), nx, ny,
+                       reinterpret_cast<double *>(d_out_linear), reinterpret_cast<unsigned char *>(d_out_rgb8), reinterpret_cast<double *>(d_out_stderr),
+                       reinterpret_cast<int *>(d_out_samples));
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+
+namespace {
+// How a multi-device call moves the replicas' records to replica 0's device: rtmi_render_multi_device's rules (RTMI_MULTI_GATHER, the library's
+// communicator sets, the fall-back to copies), decided before anything is launched.
+struct GatherPlan {
+    bool use_rccl = false;
+    std::vector<ncclComm_t> *comms = nullptr;
+    std::vector<int> devs;
+};
+
+int plan_gather(int n, rtmi_scene *const *scenes, GatherPlan &g) {
+    g.devs.resize((size_t)n);
+    bool distinct = true;
+    for (int r = 0; r < n; ++r) {
+        g.devs[(size_t)r] = scenes[r]->ctx->device;
+        for (int q = 0; q < r; ++q) distinct = distinct && g.devs[(size_t)q] != g.devs[(size_t)r];
+    }
+    const char *force = std::getenv("RTMI_MULTI_GATHER");
+    const bool want_copy = force && !std::strcmp(force, "copy"), want_rccl = force && !std::strcmp(force, "rccl");
+    if (want_rccl && !distinct) return fail(RTMI_E_ARG, "RTMI_MULTI_GATHER=rccl needs replicas on distinct devices (RCCL refuses one device twice in a communicator)");
+    g.use_rccl = distinct && !want_copy && (want_rccl || (n > 1 && !g_rccl_failed));
+    if (!g.use_rccl) return RTMI_OK;
+    std::string why;
+    if (!rccl_load()) why = g_rccl.err;
+    else {
+        auto it = g_comms.find(g.devs);
+        if (it == g_comms.end()) {
+            std::vector<ncclComm_t> cs((size_t)n);
+            const ncclResult_t e = g_rccl.CommInitAll(cs.data(), n, g.devs.data());
+            if (e != ncclSuccess) why = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(e);
+            else it = g_comms.emplace(g.devs, std::move(cs)).first;
+        }
+        if (why.empty()) g.comms = &it->second;
+    }
+    if (!why.empty()) {
+        if (want_rccl) return fail(RTMI_E_DEVICE, "multi-device gather: %s", why.c_str());
+        fprintf(stderr, "[rtmi] multi-device gather falls back to hipMemcpyPeerAsync: %s\n", why.c_str());
+        g_rccl_failed = true;
+        g.use_rccl = false;
+    }
+    return RTMI_OK;
+}
+
+// ONE gather of `words` 8-byte words per replica: recs[r] (on replica r's device, written on its context stream; with copies its ev_done is recorded
+// behind the writes) -> gathered[r] on replica 0's device.  recs[0] = gathered: replica 0's record is in place.
+int enqueue_gather(int n, rtmi_scene *const *scenes, const GatherPlan &g, const std::vector<char *> &recs, char *gathered, size_t words) {
+    rtmi_ctx *c0 = scenes[0]->ctx;
+    HIP_TRY(hipSetDevice(c0->device));
+    int rc = ensure_event(&c0->ev_g0);
+    if (!rc) rc = ensure_event(&c0->ev_g1);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c0->ev_g0, c0->stream));
+    if (g.use_rccl) {
+        ncclResult_t e = g_rccl.GroupStart();
+        for (int r = 0; r < n && e == ncclSuccess; ++r) {
+            (void)hipSetDevice(scenes[r]->ctx->device);
+            e = g_rccl.Gather(recs[(size_t)r], r == 0 ? gathered : nullptr, words, ncclUint64, 0, (*g.comms)[(size_t)r], scenes[r]->ctx->stream);
+        }
+        const ncclResult_t e2 = g_rccl.GroupEnd();
+        (void)hipSetDevice(c0->device);
+        if (e == ncclSuccess) e = e2;
+        if (e != ncclSuccess) { // this communicator set is not trusted again: later calls gather by copies
+            const int code = fail(RTMI_E_DEVICE, "ncclGather: %s", g_rccl.GetErrorString(e));
+            rccl_give_up(g.devs);
+            return code;
+        }
+        c0->last_gather_path = RTMI_GATHER_RCCL;
+    } else {
+        bool peer = false;
+        for (int r = 1; r < n; ++r) {
+            rtmi_ctx *cr = scenes[r]->ctx;
+            char *dst = gathered + (size_t)r * words * 8;
+            HIP_TRY(hipStreamWaitEvent(c0->stream, cr->ev_done, 0));
+            if (cr->device == c0->device) HIP_TRY(hipMemcpyAsync(dst, recs[(size_t)r], words * 8, hipMemcpyDeviceToDevice, c0->stream));
+            else { peer = true; HIP_TRY(hipMemcpyPeerAsync(dst, c0->device, recs[(size_t)r], cr->device, words * 8, c0->stream)); }
+            // replica r's NEXT render into its record waits for this copy (its stream is not otherwise ordered with replica 0's)
+            if (cr->ev_consumed && cr->ev_consumed_device != c0->device) { (void)hipSetDevice(cr->ev_consumed_device); (void)hipEventDestroy(cr->ev_consumed); cr->ev_consumed = nullptr; HIP_TRY(hipSetDevice(c0->device)); }
+            if (!cr->ev_consumed) { HIP_TRY(hipEventCreateWithFlags(&cr->ev_consumed, hipEventDisableTiming)); cr->ev_consumed_device = c0->device; }
+            HIP_TRY(hipEventRecord(cr->ev_consumed, c0->stream));
+            cr->consume_pending = true;
+        }
+        c0->last_gather_path = n == 1 ? RTMI_GATHER_NONE : (peer ? RTMI_GATHER_PEER_COPY : RTMI_GATHER_SAME_DEVICE);
+    }
+    HIP_TRY(hipEventRecord(c0->ev_g1, c0->stream));
+    c0->have_gather = true;
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_multi_adaptive_device(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count,
+                                                  int32_t retire, double eps, int32_t depth, uint64_t seed, int32_t precision, void *d_out_linear,
+                                                  void *d_out_rgb8, void *d_out_stderr, void *d_out_samples, void *d_out_counters) {
+    if (n <= 0 || n > 64 || !scenes) return fail(RTMI_E_ARG, "n must be 1..64 and scenes non-NULL");
+    // every check of every replica comes before the first launch: a refusal leaves every frame as it was
+    for (int r = 0; r < n; ++r) {
+        int rc = check_adaptive_tiles_args(scenes[r], nx, ny, s_first, s_count, retire, eps, depth, precision, r, n);
+        if (rc) return rc;
+        for (int q = 0; q < r; ++q)
+            if (scenes[q]->ctx == scenes[r]->ctx) return fail(RTMI_E_ARG, "replicas %d and %d share a context (a context is not re-entrant: one per replica)", q, r);
+        if (scenes[r]->n_prims != scenes[0]->n_prims) return fail(RTMI_E_ARG, "replica %d is not a clone of replica 0", r);
+    }
+    std::vector<ProgKey> keys((size_t)n);
+    for (int r = 0; r < n; ++r) {
+        keys[(size_t)r] = dealt_key(scenes[r], nx, ny, depth, seed, precision, r, n);
+        const int rc = check_dealt_continuation(scenes[r]->ctx, keys[(size_t)r], s_first, retire);
+        if (rc) { const std::string why = g_err; return fail(rc, "replica %d: %s", r, why.c_str()); }
+    }
+    std::lock_guard<std::mutex> lock(g_multi_mu);
+    DeviceGuard guard;
+    GatherPlan plan;
+    int rc = plan_gather(n, scenes, plan);
+    if (rc) return rc;
+    const int ntiles = tiles_x_of(nx) * tiles_y_of(ny);
+    const int per = (ntiles + n - 1) / n;                             // every replica's record is padded to this many tiles
+    const size_t tile_words = (size_t)per * 64 * RTMI_PROG_REC;       // doubles of a record's tiles
+    const size_t rec = tile_words + 2;                                // 8-byte words per record: the tiles + the two metrics counters
+    rtmi_ctx *c0 = scenes[0]->ctx;
+    const int k_before0 = c0->prog.k;
+    // An error once a frame has been touched drops the frame of EVERY replica (some hold the new samples, some do not: no continuation can be
+    // right), and does not return with work in flight on streams the caller believes idle.
+    int launched = 0;
+    auto bail = [&](int code, bool drop) {
+        const std::string keep = g_err;
+        for (int r = 0; r < launched; ++r) { (void)hipSetDevice(scenes[r]->ctx->device); (void)hipStreamSynchronize(scenes[r]->ctx->stream); }
+        (void)hipSetDevice(c0->device); (void)hipStreamSynchronize(c0->stream);
+        if (drop) for (int r = 0; r < n; ++r) { scenes[r]->ctx->prog.k = 0; scenes[r]->ctx->prog.meta_pending = false; }
+        g_err = keep;
+        return code;
+    };
+#define HIP_BAIL(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return bail(fail(RTMI_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)), launched > 0); } while (0)
+    // 1. every replica adds the samples to its dealt tiles (r, r + n, ...) on its own device and stream and resolves them straight into its record
+    HIP_TRY(hipSetDevice(c0->device));
+    rc = c0->multi.ensure((size_t)n * rec * 8);
+    if (rc) return rc;
+    char *gathered = reinterpret_cast<char *>(c0->multi.p);
+    std::vector<char *> recs((size_t)n);
+    for (int r = 0; r < n; ++r) {
+        rtmi_ctx *cr = scenes[r]->ctx;
+        HIP_BAIL(hipSetDevice(cr->device));
+        if (r == 0) recs[0] = gathered; // in place: replica 0's record is the first of the gathered buffer
+        else { rc = cr->multi.ensure(rec * 8); if (rc) return bail(rc, true); recs[(size_t)r] = reinterpret_cast<char *>(cr->multi.p); }
+        char *buf = recs[(size_t)r];
+        if (cr->consume_pending) { // the previous call's copy out of this record (on another replica 0's stream) must have read it
+            HIP_BAIL(hipStreamWaitEvent(cr->stream, cr->ev_consumed, 0));
+            cr->consume_pending = false;
+        }
+        if (precision == RTMI_F64) rc = dealt_launch<double>(scenes[r], keys[(size_t)r], s_first, s_count, retire, eps, reinterpret_cast<double *>(buf), per, buf + tile_words * 8, cr->stream);
+        else rc = dealt_launch<float>(scenes[r], keys[(size_t)r], s_first, s_count, retire, eps, reinterpret_cast<double *>(buf), per, buf + tile_words * 8, cr->stream);
+        // replica 0 refused before it touched its frame (the test hook, an allocation): nothing has changed anywhere
+        if (rc) { launched = r + 1; return bail(rc, !(r == 0 && c0->prog.k == k_before0 && k_before0 > 0)); }
+        launched = r + 1;
+        if (!plan.use_rccl && r > 0) { rc = ensure_event(&cr->ev_done); if (rc) return bail(rc, true); HIP_BAIL(hipEventRecord(cr->ev_done, cr->stream)); }
+    }
+    // 2. ONE gather to replica 0's device (n = 1 without RTMI_MULTI_GATHER=rccl: nothing to move)
+    rc = enqueue_gather(n, scenes, plan, recs, gathered, rec);
+    if (rc) return bail(rc, true);
+    // 3. replica 0 un-tiles, quantises and sums the counters
+    HIP_BAIL(hipSetDevice(c0->device));
+    if (d_out_linear || d_out_rgb8 || d_out_stderr || d_out_samples) {
+        const long long npx = (long long)nx * ny;
+        hipLaunchKernelGGL(assemble_progressive_kernel, dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, c0->stream,
+                           reinterpret_cast<const double *>(gathered), n, rec, tiles_x_of(nx), nx, ny, reinterpret_cast<double *>(d_out_linear),
+                           reinterpret_cast<unsigned char *>(d_out_rgb8), reinterpret_cast<double *>(d_out_stderr), reinterpret_cast<int *>(d_out_samples));
+        HIP_BAIL(hipGetLastError());
+    }
+    if (d_out_counters) {
+        hipLaunchKernelGGL(sum_counters_kernel, dim3(1), dim3(64), 0, c0->stream, reinterpret_cast<const u64 *>(gathered), n, rec, tile_words,
+                           reinterpret_cast<u64 *>(d_out_counters));
+        HIP_BAIL(hipGetLastError());
+    }
+#undef HIP_BAIL
+    // 4. the host's mirror of every replica's tile state; replica 0 last: its stream carries the gather and the assemble
+    for (int r = n - 1; r >= 0; --r) {
+        rtmi_ctx *cr = scenes[r]->ctx;
+        if (hipSetDevice(cr->device) != hipSuccess) return bail(fail(RTMI_E_DEVICE, "hipSetDevice(%d) failed", cr->device), true);
+        rc = dealt_finish(cr, s_count, retire, cr->stream);
+        if (rc) return bail(rc, true);
+    }
+    for (int r = 1; r < n; ++r) scenes[r]->ctx->consume_pending = false; // replica 0's stream is idle: the copies out of the records are done
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_render_multi_adaptive(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t retire,
+                                           double eps, int32_t depth, uint64_t seed, int32_t precision, double *out_linear, uint8_t *out_rgb8,
+                                           double *out_stderr, int32_t *out_samples, uint64_t *out_counters) {
+    if (n <= 0 || !scenes || !scene_ok(scenes[0])) return fail(RTMI_E_ARG, "bad replica list");
+    if (nx <= 0 || ny <= 0 || (long long)nx * ny > (1ll << 30)) return fail(RTMI_E_ARG, "nx, ny must be > 0 and the frame at most 2^30 pixels (got %d %d)", nx, ny);
+    DeviceGuard guard;
+    rtmi_ctx *c0 = scenes[0]->ctx;
+    HIP_TRY(hipSetDevice(c0->device));
+    const size_t npx = (size_t)nx * (size_t)ny;
+    int rc = c0->scratch_lin.ensure(npx * 4 * sizeof(double) + npx * sizeof(int) + 2 * sizeof(u64) + npx * 3 + 64);
+    if (rc) return rc;
+    char *base = reinterpret_cast<char *>(c0->scratch_lin.p);
+    double *d_lin = reinterpret_cast<double *>(base), *d_err = reinterpret_cast<double *>(base + npx * 3 * sizeof(double));
+    u64 *d_cnt = reinterpret_cast<u64 *>(base + npx * 4 * sizeof(double));
+    int *d_smp = reinterpret_cast<int *>(base + npx * 4 * sizeof(double) + 2 * sizeof(u64));
+    unsigned char *d_q = reinterpret_cast<unsigned char *>(base + npx * 4 * sizeof(double) + 2 * sizeof(u64) + npx * sizeof(int));
+    rc = rtmi_render_multi_adaptive_device(n, scenes, nx, ny, s_first, s_count, retire, eps, depth, seed, precision, d_lin, d_q, d_err, d_smp, d_cnt);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c0->device)); // (every replica's stream is synchronised)
+    hipError_t e = hipSuccess;
+    if (out_linear) e = hipMemcpy(out_linear, d_lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_rgb8) e = hipMemcpy(out_rgb8, d_q, npx * 3, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_stderr) e = hipMemcpy(out_stderr, d_err, npx * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_samples) e = hipMemcpy(out_samples, d_smp, npx * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_counters) e = hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        for (int r = 0; r < n; ++r) scenes[r]->ctx->prog.k = 0;
+        return fail(RTMI_E_DEVICE, "multi-device adaptive render: %s", hipGetErrorString(e));
+    }
     return RTMI_OK;
 }
 

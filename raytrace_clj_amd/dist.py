@@ -7,6 +7,7 @@ import torch
 import torch.distributed as dist
 
 from . import _ffi
+from . import core
 from .core import Context, DeviceScene, check
 
 TILE = _ffi.TILE
@@ -28,7 +29,8 @@ def local_tile_ids(nx, ny, rank, world):
 
 
 def gather_tiles(local_tiles, world, rank, dst=0, group=None):
-    """local_tiles: [tiles_per_rank, 64, 3] float64 on this rank's device -> on dst: [world, tiles_per_rank, 64, 3]."""
+    """local_tiles: [tiles_per_rank, 64, 3] float64 on this rank's device -> on dst: [world, tiles_per_rank, 64, 3]
+    (any trailing shape: the progressive tile records are [tiles_per_rank, 64, 5])."""
     if world == 1:
         return local_tiles.unsqueeze(0)
     if HOST_STAGED_GATHER:
@@ -91,6 +93,35 @@ class TileRenderer:
             check(_ffi.lib().rtmi_assemble_device(self.ds.ctx.handle, self.nx, self.ny, self.world, self.per, _ffi.ptr(gathered),
                                                   _ffi.ptr(self.linear), _ffi.ptr(self.rgb8), _ffi.ptr(stream)))
 
+    def step_adaptive(self, s_first, s_count, retire, eps=0.0, depth=50, seed=0x5EED0002, precision="f64"):
+        """One refinement of the frame dealt over the ranks: samples [s_first, s_first + s_count) into this rank's tiles (retire: the adaptive
+        rule with eps, else none retires) -> gather of the tile records -> (rank 0) assemble into self.linear, self.rgb8, self.stderr,
+        self.samples.  Ordered with torch's current stream as step() is; the render call synchronises its stream once (the host mirrors the
+        rank's active list: self.ds.ctx.adaptive_status() / adaptive_active_tiles() describe this rank's tiles)."""
+        if getattr(self, "local_rec", None) is None:
+            self.local_rec = torch.zeros((self.per, 64, _ffi.PROG_REC), dtype=torch.float64, device=self.dev)
+            if self.rank == 0:
+                self.stderr = torch.zeros((self.ny, self.nx), dtype=torch.float64, device=self.dev)
+                self.samples = torch.zeros((self.ny, self.nx), dtype=torch.int32, device=self.dev)
+        cur = torch.cuda.current_stream(self.dev)
+        if cur.cuda_stream != 0:
+            return self._step_adaptive(cur.cuda_stream, s_first, s_count, retire, eps, depth, seed, precision)
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.dev)
+        self._side.wait_stream(cur)
+        with torch.cuda.stream(self._side):
+            self._step_adaptive(self._side.cuda_stream, s_first, s_count, retire, eps, depth, seed, precision)
+        cur.wait_stream(self._side)
+
+    def _step_adaptive(self, stream, s_first, s_count, retire, eps, depth, seed, precision):
+        # (the primitive writes this rank's local tiles only: the padding slot of local_rec, if any, keeps its zeros)
+        self.ds.render_adaptive_tiles_device(self.nx, self.ny, s_first, s_count, retire, eps, self.rank, self.world, self.local_rec, self.counters,
+                                             depth, seed, precision, stream)
+        gathered = gather_tiles(self.local_rec, self.world, self.rank)
+        if self.rank == 0:
+            self.ds.ctx.assemble_progressive_device(self.nx, self.ny, self.world, self.per, gathered, self.linear, self.rgb8, self.stderr,
+                                                    self.samples, stream)
+
 
     def last_gather_ms(self):
         """milliseconds the last step's gather took on this rank's stream (the transfer plus the wait for the slowest rank)"""
@@ -134,6 +165,112 @@ class MultiDevice:
         """outputs: device pointers / torch tensors on devices[0]; asynchronous on replica 0's context stream"""
         check(_ffi.lib().rtmi_render_multi_device(self.n, self._arr, nx, ny, ns, depth, seed, {"f64": 0, "f32": 1}[precision],
                                                   _ffi.ptr(out_linear), _ffi.ptr(out_rgb8), _ffi.ptr(out_counters)))
+
+    # ---- one progressive / adaptive frame refined on all replicas (rtmi_render_multi_adaptive): DeviceScene's drivers, same defaults, same shapes ----
+    def render_multi_adaptive(self, nx, ny, s_first, s_count, retire, eps=0.0, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED, precision="f64"):
+        """host buffers: samples [s_first, s_first + s_count) into the frame dealt over the replicas (retire: the adaptive rule with eps, else
+        the progressive one) -> (linear, rgb8, stderr [ny,nx], samples int32 [ny,nx], counters)"""
+        import numpy as np
+        lin, q = np.zeros((ny, nx, 3)), np.zeros((ny, nx, 3), np.uint8)
+        err, smp, cnt = np.zeros((ny, nx)), np.zeros((ny, nx), np.int32), np.zeros(2, np.uint64)
+        check(_ffi.lib().rtmi_render_multi_adaptive(self.n, self._arr, nx, ny, s_first, s_count, int(retire), float(eps), depth, seed,
+                                                    {"f64": 0, "f32": 1}[precision], _ffi.ptr(lin), _ffi.ptr(q), _ffi.ptr(err), _ffi.ptr(smp),
+                                                    _ffi.ptr(cnt)))
+        return lin, q, err, smp, cnt
+
+    def render_progressive(self, nx, ny, s_first, s_count, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED, precision="f64"):
+        """DeviceScene.render_progressive for the whole frame, its tiles dealt over the replicas -> (linear, rgb8, stderr, counters), bit for bit
+        the single context's"""
+        lin, q, err, _, cnt = self.render_multi_adaptive(nx, ny, s_first, s_count, 0, 0.0, depth, seed, precision)
+        return lin, q, err, cnt
+
+    def refine(self, nx, ny, ns, chunk, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED, precision="f64"):
+        """DeviceScene.refine on all replicas: yields (k, linear, rgb8, stderr, counters) after every chunk"""
+        if chunk <= 0 or ns <= 0:
+            raise ValueError("ns and chunk must be > 0")
+        k = 0
+        while k < ns:
+            n = min(chunk, ns - k)
+            lin, q, err, cnt = self.render_progressive(nx, ny, k, n, depth, seed, precision)
+            k += n
+            yield k, lin, q, err, cnt
+
+    def render_adaptive(self, nx, ny, s_first, s_count, eps, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED, precision="f64"):
+        """DeviceScene.render_adaptive for the whole frame, its tiles dealt over the replicas -> (linear, rgb8, stderr, samples, counters), bit
+        for bit the single context's"""
+        return self.render_multi_adaptive(nx, ny, s_first, s_count, 1, eps, depth, seed, precision)
+
+    def render_adaptive_device(self, nx, ny, s_first, s_count, eps, out_linear=None, out_rgb8=None, out_stderr=None, out_samples=None,
+                               out_counters=None, retire=True, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED, precision="f64"):
+        """the same with the outputs resident on devices[0] (rtmi_render_multi_adaptive_device; retire=False: the progressive rule); returns with
+        every replica's stream synchronised"""
+        check(_ffi.lib().rtmi_render_multi_adaptive_device(self.n, self._arr, nx, ny, s_first, s_count, int(bool(retire)), float(eps), depth, seed,
+                                                           {"f64": 0, "f32": 1}[precision], _ffi.ptr(out_linear), _ffi.ptr(out_rgb8),
+                                                           _ffi.ptr(out_stderr), _ffi.ptr(out_samples), _ffi.ptr(out_counters)))
+
+    def adaptive_status(self):
+        """(tiles still active, tiles of the frame, sum over the pixels of the samples their tile holds), summed over the replicas"""
+        a, t, n = 0, 0, 0
+        for ctx in self.ctxs:
+            x, y, z = ctx.adaptive_status()
+            a, t, n = a + x, t + y, n + z
+        return a, t, n
+
+    def adaptive_active_tiles(self):
+        """global tile indices of the tiles still active on any replica, int32, ascending"""
+        import numpy as np
+        return np.sort(np.concatenate([ctx.adaptive_active_tiles() for ctx in self.ctxs])).astype(np.int32)
+
+    def adaptive_retire(self, noise, eps):
+        """Context.adaptive_retire with the whole-frame map on every replica (each reads its own active tiles) -> tiles retired in all"""
+        return sum(ctx.adaptive_retire(noise, eps) for ctx in self.ctxs)
+
+    def progressive_samples(self):
+        """k of the frame (the replicas agree; 0 = none)"""
+        ks = {ctx.progressive_samples() for ctx in self.ctxs}
+        return ks.pop() if len(ks) == 1 else 0
+
+    def progressive_release(self):
+        for ctx in self.ctxs:
+            ctx.progressive_release()
+
+    def refine_adaptive(self, nx, ny, ns, chunk, eps, first=None, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED, precision="f64"):
+        """DeviceScene.refine_adaptive on all replicas: yields (k, linear, rgb8, stderr, samples, counters, active tiles) after every round and
+        ends when no tile is active anywhere or k reaches ns"""
+        first = chunk if first is None else first
+        if chunk <= 0 or ns <= 0 or first <= 0:
+            raise ValueError("ns, chunk and first must be > 0")
+        k = 0
+        while k < ns:
+            n = min(first if k == 0 else chunk, ns - k)
+            lin, q, err, smp, cnt = self.render_adaptive(nx, ny, k, n, eps, depth, seed, precision)
+            k += n
+            active = self.adaptive_status()[0]
+            yield k, lin, q, err, smp, cnt, active
+            if active == 0:
+                break
+
+    def refine_adaptive_denoised(self, nx, ny, ns, chunk, eps, first=None, na=core.FEATURE_SAMPLES, iterations=core.DENOISE_ITERATIONS,
+                                 sigma_c=core.DENOISE_SIGMA_C, sigma_n=core.DENOISE_SIGMA_N, sigma_a=core.DENOISE_SIGMA_A,
+                                 sigma_d=core.DENOISE_SIGMA_D, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED, precision="f64"):
+        """DeviceScene.refine_adaptive_denoised on all replicas: the features and the filter run on replica 0 over the assembled frame, the
+        filtered noise map retires tiles on every replica.  Yields (k, linear, rgb8, stderr, samples, counters, active tiles after the
+        retirement, filtered linear, filtered rgb8, filtered stderr) after every round."""
+        first = chunk if first is None else first
+        if chunk <= 0 or ns <= 0 or first <= 0:
+            raise ValueError("ns, chunk and first must be > 0")
+        ft, _ = self.scenes[0].render_features(nx, ny, na, seed, precision)
+        k = 0
+        while k < ns:
+            n = min(first if k == 0 else chunk, ns - k)
+            lin, q, err, smp, cnt = self.render_adaptive(nx, ny, k, n, 0.0, depth, seed, precision)
+            k += n
+            flt, fq, ferr = self.ctxs[0].denoise(lin, err, ft, iterations, sigma_c, sigma_n, sigma_a, sigma_d)
+            self.adaptive_retire(ferr, eps)
+            active = self.adaptive_status()[0]
+            yield k, lin, q, err, smp, cnt, active, flt, fq, ferr
+            if active == 0:
+                break
 
     def sync(self):
         """wait for every replica (a multi render is complete when replica 0's stream is; the others finished before the gather)"""
