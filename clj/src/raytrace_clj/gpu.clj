@@ -322,6 +322,42 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn set-camera
+  "Give the live scene `scn` (the Pointer create-scene! returned) another camera record (PinholeCamera / ThinLensCamera) without a new
+  scene: every render afterwards is, bit for bit, the render of a scene created with that camera.  Returns true when the library had to
+  rebuild its trees (the scene holds MovingSpheres and the camera's shutter [t0, t1] lies outside the interval the scene was built for),
+  false when only the camera changed.  A progressive frame started before the call is not continued (start a new one: s-first 0)."
+  [scn camera]
+  (let [row     (camera-row camera)
+        cam     (double-array (:cam row))
+        rebuilt (int-array 1)]
+    (check (call-int "rtmi_scene_set_camera" scn (int (:kind row)) cam rebuilt))
+    (= 1 (aget rebuilt 0))))
+
+(defn render-views
+  "Render scene {:camera :world} once per camera record of `cameras` -- a turntable, a fly-through, a shutter sweep -- from ONE device
+  scene: the world is flattened, built and uploaded once, every view only moves the camera (set-camera).  Returns a vector of render's
+  maps, one per camera, each equal to (render (assoc scene :camera c) ...)."
+  [scene cameras nx ny ns & {:keys [depth seed device precision] :or {depth 50 seed 0x5eed0002 device 0 precision 0}}]
+  (let [f   (flatten-scene scene)
+        ctx (PointerByReference.)
+        npx (* nx ny)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (mapv (fn [camera]
+                  (let [lin (double-array (* 3 npx))
+                        rgb (byte-array (* 3 npx))
+                        cnt (long-array 2)]
+                    (set-camera scn camera)
+                    (check (call-int "rtmi_render" scn (int nx) (int ny) (int ns) (int depth) (long seed) (int precision)
+                                     (int 0) (int 0) (int nx) (int ny) lin rgb cnt))
+                    {:rgb8 rgb :linear lin :total-rays (aget cnt 0) :total-pixels (aget cnt 1)}))
+                cameras)
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn render-progressive
   "Render scene {:camera :world} progressively on GPU `device` (rtmi_render_progressive): chunks of `chunk` samples up to ns, and after
   each chunk (on-chunk m) with m = what `render` returns for ns = k (bit for bit) plus :samples k and :stderr (double-array, per pixel the

@@ -166,6 +166,38 @@ int rtmi_scene_set_media_mode(rtmi_scene *scene, int32_t mode);
  * contiguous in the flattened order; calls that share a narrowing list come in list order.  Replaces both calls above for such worlds; still unsupported: a
  * bvh-node BETWEEN a narrowing Hitlist and its medium, a medium inside a medium's boundary. */
 int rtmi_scene_set_media_calls_narrowed(rtmi_scene *scene, int32_t n_calls, const int32_t *calls, const int32_t *narrow_from);
+/* ---- the camera of a live scene: another viewpoint or shutter without a new scene (a turntable, a fly-through, a shutter sweep, a drag of the mouse) ----
+ * The promise: after either set call has succeeded, every entry that reads the scene -- rtmi_render*, the tiles, progressive, adaptive and multi forms,
+ * rtmi_render_features* and the probes -- returns, BIT FOR BIT, what it returns for a scene freshly created from the same arrays (and the same
+ * rtmi_scene_set_* calls) with this camera: frame, 8-bit frame, standard error, samples, features and the ray counters.  Only the traversal counters of
+ * rtmi_last_traversal_counters may differ: they describe the tree, and the tree may differ (it is a conservative filter in front of the exact tests; a
+ * fresh scene takes |camera origin| into the bound its boxes are inflated by, and sweeps its MovingSphere boxes over its own camera's shutter).
+ * Shutter interval of a camera: RTMI_CAM_PINHOLE [0, 0] (camera.clj:16: its rays carry time 0); RTMI_CAM_THINLENS [min(t0, t1), max(t0, t1)].  The camera
+ * FITS if the scene holds no RTMI_PRIM_MOVING primitive, or if its interval lies inside the interval the scene was built for (the creating camera's, or the
+ * last rebuild's; rtmi_scene_camera reports it).  The origin never matters: a ray that starts beyond the tree's bound moves the box planes out itself.
+ *   The camera fits: only the camera changes -- in the descriptor in HBM, in the host's mirror of it and in the arguments rtmi_scene_clone replays.  No table
+ *     is allocated, freed or uploaded again, rtmi_scene_device_bytes is unchanged and the built interval stays as built.
+ *   It does not fit (rtmi_scene_set_camera only): rays outside the built interval would bypass the swept bounds and test every MovingSphere exactly --
+ *     correct, and ruinous -- so the call rebuilds: the trees and tables are built for the new camera from the arrays the scene keeps, uploaded beside the old
+ *     ones and only then swapped in; the old ones are freed after the context's stream has been synchronised.  The Perlin tables, the images, the media call
+ *     sequence (a narrowed one too) and the media mode stay.  The handle and the scene's identity (the progressive key's serial) stay; on any failure the scene
+ *     is exactly as before.  *out_rebuilt (may be NULL) = 1 on this path, 0 on the other.
+ * Both forms change the scene's revision on success, always (the bytes are not compared): a progressive frame started before the call is refused its
+ * continuation with RTMI_E_STATE, s_first = 0 starts a new one.
+ * rtmi_scene_set_camera synchronises the context's stream first, like every rtmi_scene_set_* call.
+ * rtmi_scene_set_camera_stream never waits for the host: the 24 doubles and the two ints travel as the arguments of a one-wave kernel that stores them into
+ * the descriptor on `stream` (rtmi_render_device's stream semantics: NULL = the context's own stream).  A render queued on that stream before the call sees
+ * the old camera, one queued after it the new one.  The host's mirror changes at once: what a render decides at enqueue time (the width of its camera-ray
+ * stash) agrees with what its kernels will read.  If the camera does not fit: RTMI_E_UNSUPPORTED, rtmi_last_error names both intervals, nothing changes and
+ * nothing is launched.  A scene's camera belongs to one stream at a time, like the workspace: renders of the scene that are still queued on ANOTHER stream
+ * when either form is called are not ordered with it.
+ * Errors of the two set forms, reported before the handle is examined: cam NULL: RTMI_E_ARG; cam_kind neither RTMI_CAM_PINHOLE nor RTMI_CAM_THINLENS:
+ * RTMI_E_UNSUPPORTED.  Then a bad handle: RTMI_E_STATE.  Non-finite camera values are accepted, as creation accepts them. */
+int rtmi_scene_set_camera(rtmi_scene *scene, int32_t cam_kind, const double *cam, int32_t *out_rebuilt);
+int rtmi_scene_set_camera_stream(rtmi_scene *scene, int32_t cam_kind, const double *cam, void *stream);
+/* The camera the scene renders with now (cam_kind, cam[24]) and the shutter interval its MovingSphere bounds were built for.  Every output may be NULL.
+ * Host state only: no device access. */
+int rtmi_scene_camera(rtmi_scene *scene, int32_t *cam_kind, double *cam, double *built_t_lo, double *built_t_hi);
 /* HBM bytes the scene occupies (everything its creation uploaded: records, tree, tables) -- bench.py's `upload_bytes` */
 int rtmi_scene_device_bytes(rtmi_scene *scene, int64_t *out_bytes);
 int rtmi_scene_destroy(rtmi_scene *scene);

@@ -31,6 +31,7 @@ SYMBOLS = [
     "rtmi_render_features", "rtmi_render_features_device", "rtmi_denoise", "rtmi_denoise_device",
     "rtmi_adaptive_retire", "rtmi_adaptive_retire_device",
     "rtmi_render_adaptive_tiles_device", "rtmi_assemble_progressive_device", "rtmi_render_multi_adaptive", "rtmi_render_multi_adaptive_device",
+    "rtmi_scene_set_camera", "rtmi_scene_set_camera_stream", "rtmi_scene_camera",
 ]
 
 F64, F32 = 0, 1
@@ -127,6 +128,9 @@ def lib():
     L.rtmi_assemble_progressive_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.rtmi_render_multi_adaptive.argtypes = [i32, C.POINTER(vp), i32, i32, i32, i32, i32, dbl, i32, u64, i32, vp, vp, vp, vp, vp]
     L.rtmi_render_multi_adaptive_device.argtypes = [i32, C.POINTER(vp), i32, i32, i32, i32, i32, dbl, i32, u64, i32, vp, vp, vp, vp, vp]
+    L.rtmi_scene_set_camera.argtypes = [vp, i32, vp, C.POINTER(i32)]
+    L.rtmi_scene_set_camera_stream.argtypes = [vp, i32, vp, vp]
+    L.rtmi_scene_camera.argtypes = [vp, C.POINTER(i32), vp, C.POINTER(dbl), C.POINTER(dbl)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

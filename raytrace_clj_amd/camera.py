@@ -73,3 +73,45 @@ def thin_lens_camera(*, lookfrom, lookat, vup, vfov, aspect, aperture, focus_dis
     lleft = lookfrom - ((u * (fd * hw) + v * (fd * hh)) + w * fd)
     return ThinLensCamera(lookfrom, lleft, u * ((2.0 * fd) * hw), v * ((2.0 * fd) * hh), u, v, w,
                           float(aperture), float(t0), float(t1))
+
+
+# ---- moving the camera of a live scene (DeviceScene.set_camera): the reference has no such operation, a new view is a new record ----
+_POINTS = ("origin", "lleft")
+_VECTORS = ("horiz", "vert", "u", "v", "w")
+
+
+def rotate_y(camera, angle, pivot):
+    """The same record type turned rigidly by `angle` radians about the vertical axis through `pivot`: x' = c x + s z, z' = -s x + c z
+    (RotateY's outward map, hitable.clj:441-443), the points (origin, lleft) about the pivot, the vectors (horiz, vert, u, v, w) about the
+    origin; aperture and shutter are kept.  An angle whose sine is 0 and cosine 1 is the identity: the arrays are copied bit for bit."""
+    s, c = math.sin(float(angle)), math.cos(float(angle))
+    pivot = np.asarray(pivot, np.float64)
+    identity = s == 0.0 and c == 1.0
+
+    def turn(a, about):  # the height is copied, never computed
+        x, z = a[0] - about[0], a[2] - about[2]
+        return np.array([(c * x + s * z) + about[0], a[1], (-(s * x) + c * z) + about[2]], np.float64)
+
+    fields = {}
+    for name in _POINTS + _VECTORS:
+        if not hasattr(camera, name):
+            continue
+        a = np.asarray(getattr(camera, name), np.float64)
+        fields[name] = a.copy() if identity else turn(a, pivot if name in _POINTS else np.zeros(3))
+    if isinstance(camera, ThinLensCamera):
+        return ThinLensCamera(aperture=camera.aperture, t0=camera.t0, t1=camera.t1, **fields)
+    if isinstance(camera, PinholeCamera):
+        return PinholeCamera(**fields)
+    raise TypeError("rotate_y: %s is not a camera record" % type(camera).__name__)
+
+
+def view_pivot(camera):
+    """A point on the camera's look-at axis, from the record alone: the centre of its image plane, lleft + horiz / 2 + vert / 2 (the
+    focus point origin - focus-dist * w of a thin lens: the look-at point itself when the lens is focused on it)."""
+    return np.asarray(camera.lleft, np.float64) + 0.5 * np.asarray(camera.horiz, np.float64) + 0.5 * np.asarray(camera.vert, np.float64)
+
+
+def orbit(camera, n, pivot=None):
+    """n views of a turntable: view k is `camera` turned by k * 360 / n degrees about the vertical axis through `pivot` (default: view_pivot)"""
+    pivot = view_pivot(camera) if pivot is None else np.asarray(pivot, np.float64)
+    return [rotate_y(camera, 2.0 * math.pi * k / n, pivot) for k in range(n)]

@@ -237,6 +237,49 @@ class DeviceScene:
             _ffi.lib().rtmi_scene_destroy(self.handle)
             self.handle = None
 
+    # ---- the camera of the live scene (rtmi_scene_set_camera*): another viewpoint or shutter without a new scene -------------------------
+    def set_camera(self, camera, stream=None):
+        """Give the live scene another camera: a Camera record or a (cam_kind, cam24) pair -> rebuilt (bool).  Every render afterwards equals,
+        bit for bit, the render of a scene created fresh with that camera.  stream=None: the host form -- it waits for the context's stream,
+        and if the scene holds MovingSpheres and the camera's shutter interval lies outside the one the scene was built for it rebuilds the
+        trees (True).  With a stream (a hipStream_t handle or torch stream; 0 = the context's own) the camera travels in stream order and the
+        host is never waited for: renders queued before it keep the old camera; a shutter that does not fit raises RtmiError -3."""
+        kind, c = camera if isinstance(camera, tuple) else fl.flatten_camera(camera)
+        c = np.ascontiguousarray(c, np.float64)
+        if c.shape != (24,):
+            raise ValueError("cam must hold 24 doubles")
+        if stream is not None:
+            handle = getattr(stream, "cuda_stream", stream)
+            check(_ffi.lib().rtmi_scene_set_camera_stream(self.handle, int(kind), ptr(c), ptr(int(handle)) if handle else None))
+            return False
+        rebuilt = C.c_int32()
+        check(_ffi.lib().rtmi_scene_set_camera(self.handle, int(kind), ptr(c), C.byref(rebuilt)))
+        return bool(rebuilt.value)
+
+    def camera_info(self):
+        """-> {"cam_kind", "cam" (24 doubles), "built_t_lo", "built_t_hi"}: the camera the scene renders with now and the shutter interval its
+        trees were built for (a camera whose interval lies inside it never rebuilds).  Host state only."""
+        kind, lo, hi = C.c_int32(), C.c_double(), C.c_double()
+        c = np.zeros(24, np.float64)
+        check(_ffi.lib().rtmi_scene_camera(self.handle, C.byref(kind), ptr(c), C.byref(lo), C.byref(hi)))
+        return {"cam_kind": kind.value, "cam": c, "built_t_lo": lo.value, "built_t_hi": hi.value}
+
+    def render_views(self, cameras, nx, ny, ns, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", stream=None, out_rgb8=None):
+        """One frame per camera, queued back to back: for every view the stream form of set_camera, then render_device into its slice of ONE
+        [V, ny, nx, 3] float64 device tensor (out_rgb8: an optional [V, ny, nx, 3] uint8 device tensor for the 8-bit frames), and ONE
+        synchronisation at the end -> the tensor.  stream=None: the context's own stream.  The scene keeps the last camera."""
+        import torch
+        cameras = list(cameras)
+        dev = torch.device("cuda", self.ctx.device)
+        out = torch.empty((len(cameras), ny, nx, 3), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)  # (the allocator may have zero-filled or recycled on torch's stream; nothing of torch's is queued after this)
+        handle = 0 if stream is None else getattr(stream, "cuda_stream", stream)
+        for k, camera in enumerate(cameras):
+            self.set_camera(camera, stream=handle)
+            self.render_device(nx, ny, ns, out[k], None if out_rgb8 is None else out_rgb8[k], None, depth, seed, precision, handle or None)
+        torch.cuda.synchronize(dev)
+        return out
+
     # ---- the hot path, host buffers (what the JNA host calls) ---------------------------------------
     def render(self, nx, ny, ns, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", region=None):
         """-> (linear float64 [h,w,3] = per-pixel mean before sqrt, rgb8 uint8 [h,w,3], counters {total-rays,total-pixels})"""
@@ -694,6 +737,69 @@ def _adaptive_denoised_flags(argv):
     return rest, eps
 
 
+def _orbit_flags(argv):
+    """-> (the other arguments, views): --orbit N, checked here, before any device work (None when absent).  An orbit is a set of one-shot
+    frames of one live scene: it combines with --denoise and with none of the progressive / adaptive modes."""
+    rest, views = [], None
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        key, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") else (a, None)
+        i += 1
+        if key != "--orbit":
+            rest.append(a)
+            continue
+        if val is None:
+            if i >= len(argv):
+                raise SystemExit("--orbit needs a value")
+            val = argv[i]
+            i += 1
+        try:
+            views = int(val)
+        except ValueError:
+            raise SystemExit("--orbit %r is not a number of views" % val)
+        if views <= 0:
+            raise SystemExit("--orbit must be a positive number of views (got %d)" % views)
+    if views is not None:
+        for other in ("--chunk", "--budget", "--noise", "--adaptive", "--adaptive-denoised"):
+            if any(a.split("=", 1)[0] == other for a in rest):
+                raise SystemExit("--orbit renders one-shot frames: it does not combine with %s" % other)
+    return rest, views
+
+
+def _orbit_name(name, k):
+    """x.png -> x_007.png: view k of an orbit"""
+    import os
+    root, ext = os.path.splitext(name)
+    return "%s_%03d%s" % (root, k, ext)
+
+
+def _render_orbit(sc, name, nx, ny, nr, views, dn_iterations, dn_samples, tstart):
+    """--orbit: `views` frames of ONE device scene, view k turned by k * 360 / views degrees about the vertical axis through the scene's
+    look-at point (sc["lookat"] when the scene gives one, else the centre of the camera's image plane, which lies on the look-at axis);
+    only the camera moves between the frames (DeviceScene.set_camera).  Writes name_000.ext ... and, with --denoise, name_000.denoised.ext ..."""
+    pivot = sc.get("lookat") if isinstance(sc, dict) else None
+    ds = DeviceScene(sc)
+    rays = pixels = 0
+    try:
+        for k, camera in enumerate(cam.orbit(sc["camera"], views, pivot)):
+            ds.set_camera(camera)
+            if dn_iterations is None:
+                lin, rgb8, cnt = ds.render(nx, ny, nr)
+            else:
+                lin, rgb8, err, cnt = ds.render_progressive(nx, ny, 0, nr)
+            _show_progress(tstart, k + 1, views)
+            _save_image(_orbit_name(name, k), rgb8)
+            if dn_iterations is not None:
+                _save_image(_denoised_name(_orbit_name(name, k)), _denoise_frame(ds, nx, ny, lin, err, dn_iterations, dn_samples))
+            rays, pixels = rays + int(cnt[0]), pixels + int(cnt[1])
+    finally:
+        ds.ctx.progressive_release()
+        ds.close()
+    print("total-rays %d total-pixels %d" % (rays, pixels))  # metrics.clj:8-9, summed over the views
+    return 0
+
+
 def _denoised_name(name):
     """x.png -> x.denoised.png: the filtered image is written next to the unfiltered one"""
     import os
@@ -742,9 +848,13 @@ def main(argv=None):
     --adaptive-denoised EPS samples adaptively for a frame that is filtered anyway (refine_adaptive_denoised, rounds of --chunk, default 16):
     after every round the frame is denoised and an 8x8 tile stops taking samples once the FILTERED standard error of all its pixels is <= EPS.
     It writes name.ext unfiltered and name.denoised.ext, prints the "samples: mean ..." line, implies --denoise with the defaults unless
-    --denoise / --feature-samples are given, obeys --budget and does not combine with --adaptive or --noise."""
+    --denoise / --feature-samples are given, obeys --budget and does not combine with --adaptive or --noise.
+    --orbit N renders N one-shot views of the scene, view k turned by k * 360 / N degrees about the vertical axis through the scene's look-at
+    point, from ONE device scene whose camera moves between the frames (DeviceScene.set_camera); it writes name_000.ext, name_001.ext, ...,
+    works with --denoise (name_000.denoised.ext, ...) and does not combine with the progressive and adaptive modes."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
+    argv, orbit_views = _orbit_flags(argv)
     argv, adaptive_denoised = _adaptive_denoised_flags(argv)
     if adaptive_denoised is not None and not any(a.split("=", 1)[0] == "--denoise" for a in argv):
         argv.append("--denoise")  # implied, with the default passes; --feature-samples then belongs to it
@@ -761,6 +871,8 @@ def main(argv=None):
         raise SystemExit("unknown scene %r; one of %s" % (which, ", ".join(sorted(SCENES))))
     tstart = time.time()
     sc = SCENES[which](scenes, nx, ny)
+    if orbit_views is not None:
+        return _render_orbit(sc, name, nx, ny, nr, orbit_views, dn_iterations, dn_samples, tstart)
     filtered = None
     if chunk is None and dn_iterations is None:
         lin, rgb8, cnt = render(sc, nx, ny, nr)

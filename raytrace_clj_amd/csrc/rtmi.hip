@@ -1393,7 +1393,9 @@ struct rtmi_scene {
     rtmi_ctx *ctx = nullptr;
     DevScene dev{};             // host copy of the descriptor
     ScenePtr d_dev = nullptr;   // the descriptor in HBM (what the kernels read)
-    std::vector<void *> allocs;
+    std::vector<void *> allocs;       // the descriptor and what rtmi_scene_set_perlin / _images uploaded
+    std::vector<void *> table_allocs; // the tables pack_scene built (records, trees, cull entries): what a camera whose shutter does not fit replaces
+    size_t table_bytes = 0;           // bytes of table_allocs (part of device_bytes)
     size_t device_bytes = 0;  // HBM the scene occupies = what its creation uploads (rtmi_scene_device_bytes)
     int n_prims = 0, n_mats = 0, n_tex = 0;
     int bvh_node_count = 0;   // inner nodes of the device's tree
@@ -1404,6 +1406,7 @@ struct rtmi_scene {
     uint64_t serial = 0;      // creation serial (a scene created at a destroyed scene's address is still another scene: progressive frame key)
     uint64_t revision = 0;    // incremented by every rtmi_scene_set_* call that changes the scene
     std::vector<int> host_kind; // primitive kinds (boundary flag removed), for argument checks
+    bool has_moving = false;    // a RTMI_PRIM_MOVING primitive is present: the trees and cull entries hold for the shutter interval [dev.cull_t_lo, dev.cull_t_hi] only
     std::map<int, std::array<double, 5>> media_fast_of; // medium primitive -> {density, c.xyz, r*r} when it and its boundary are one plain sphere without wrappers (DevScene::media_fast)
     // the caller's arrays, copied at creation (the library keeps no host POINTERS): what rtmi_scene_clone replicates
     struct Args {
@@ -1427,14 +1430,26 @@ struct Table {
     const void *data; size_t bytes, elem; const void **field;
     template <typename T> Table(const std::vector<T> &v, const T **f) : data(v.data()), bytes(v.size() * sizeof(T)), elem(sizeof(T)), field(reinterpret_cast<const void **>(f)) {}
 };
-int upload(rtmi_scene *s, const Table &t) { // (an empty table still gets one element)
+int upload_to(std::vector<void *> &allocs, size_t &bytes, const Table &t) { // (an empty table still gets one element)
     void *p = nullptr;
     const size_t alloc = std::max(t.bytes, t.elem);
     if (hipMalloc(&p, alloc) != hipSuccess) return fail(RTMI_E_NOMEM, "hipMalloc(%zu) failed", alloc);
-    s->allocs.push_back(p);
-    s->device_bytes += alloc;
+    allocs.push_back(p);
+    bytes += alloc;
     if (t.bytes) HIP_TRY(hipMemcpy(p, t.data, t.bytes, hipMemcpyHostToDevice));
     *t.field = p;
+    return RTMI_OK;
+}
+int upload(rtmi_scene *s, const Table &t) { return upload_to(s->allocs, s->device_bytes, t); }
+// The tables of a packed scene, uploaded in the order they always were; their device addresses go into d (= the descriptor that P.d was copied to).
+int upload_tables(const PackedScene &P, DevScene &d, std::vector<void *> &allocs, size_t &bytes) {
+    const Table tables[] = {
+        {P.stat_geom, &d.stat_geom}, {P.stat_orig, &d.stat_orig}, {P.bvh_nodes, &d.bvh_nodes}, {P.grid_cells, &d.grid_cells}, {P.moving_all, &d.moving_all},
+        {P.leaf_rec, &d.leaf_rec}, {P.ext_info, &d.ext_info}, {P.ext_xf, &d.ext_xf}, {P.cull20, &d.cull20}, {P.exact12, &d.exact12}, {P.stat4_d, &d.stat4_d},
+        {P.stat4_f, &d.stat4_f}, {P.mov_geom, &d.mov_geom}, {P.mov_orig, &d.mov_orig}, {P.prim_kind, &d.prim_kind}, {P.prim_km, &d.prim_km},
+        {P.mat_rec, &d.mat_rec}, {P.mat_grad, &d.mat_grad}, {P.prim_mat, &d.prim_mat}, {P.mat_kind, &d.mat_kind}, {P.mat_tex, &d.mat_tex},
+        {P.mat_param, &d.mat_param}, {P.tex_kind, &d.tex_kind}, {P.tex_param, &d.tex_param}, {P.tex_child, &d.tex_child}};
+    for (const Table &t : tables) { const int rc = upload_to(allocs, bytes, t); if (rc) return rc; }
     return RTMI_OK;
 }
 
@@ -1847,7 +1862,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 209; } // 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 210; } // 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -1936,17 +1951,18 @@ RTMI_EXPORT int rtmi_scene_create(rtmi_ctx *c, int32_t n_prims, const int32_t *p
 }
 
 // DevScene::media_fast follows the media call sequence
-static void fill_media_fast(rtmi_scene *s) {
+static void fill_media_fast(DevScene &d, const std::map<int, std::array<double, 5>> &media_fast_of) {
     for (int k = 0; k < 8; ++k) {
-        double *q = s->dev.media_fast[k];
+        double *q = d.media_fast[k];
         for (int j = 0; j < 8; ++j) q[j] = 0.0;
-        if (k >= s->dev.n_media) continue;
-        const auto it = s->media_fast_of.find(s->dev.media_idx[k]);
-        if (it == s->media_fast_of.end()) continue;
+        if (k >= d.n_media) continue;
+        const auto it = media_fast_of.find(d.media_idx[k]);
+        if (it == media_fast_of.end()) continue;
         q[0] = 1.0;
         for (int j = 0; j < 5; ++j) q[1 + j] = it->second[(size_t)j];
     }
 }
+static void fill_media_fast(rtmi_scene *s) { fill_media_fast(s->dev, s->media_fast_of); }
 namespace {
 // the checks of rtmi_scene_create_ex, in the order they are reported
 int check_scene_args(const SceneArrays &a, rtmi_scene **out_scene) {
@@ -2031,14 +2047,10 @@ RTMI_EXPORT int rtmi_scene_create_ex(rtmi_ctx *c, int32_t n_prims, const int32_t
     s->serial = ++g_scene_serial;
     s->uses_perlin = P.uses_perlin; s->max_image = P.max_image; s->bvh_node_count = P.bvh_node_count; s->bvh_depth = P.bvh_depth;
     s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of; s->dev = P.d;
+    for (int k : s->host_kind) s->has_moving = s->has_moving || k == RTMI_PRIM_MOVING;
     DevScene &d = s->dev;
-    const Table tables[] = { // (uploaded in this order, as they always were)
-        {P.stat_geom, &d.stat_geom}, {P.stat_orig, &d.stat_orig}, {P.bvh_nodes, &d.bvh_nodes}, {P.grid_cells, &d.grid_cells}, {P.moving_all, &d.moving_all},
-        {P.leaf_rec, &d.leaf_rec}, {P.ext_info, &d.ext_info}, {P.ext_xf, &d.ext_xf}, {P.cull20, &d.cull20}, {P.exact12, &d.exact12}, {P.stat4_d, &d.stat4_d},
-        {P.stat4_f, &d.stat4_f}, {P.mov_geom, &d.mov_geom}, {P.mov_orig, &d.mov_orig}, {P.prim_kind, &d.prim_kind}, {P.prim_km, &d.prim_km},
-        {P.mat_rec, &d.mat_rec}, {P.mat_grad, &d.mat_grad}, {P.prim_mat, &d.prim_mat}, {P.mat_kind, &d.mat_kind}, {P.mat_tex, &d.mat_tex},
-        {P.mat_param, &d.mat_param}, {P.tex_kind, &d.tex_kind}, {P.tex_param, &d.tex_param}, {P.tex_child, &d.tex_child}};
-    for (const Table &t : tables) if ((rc = upload(s, t))) break;
+    rc = upload_tables(P, d, s->table_allocs, s->table_bytes);
+    s->device_bytes += s->table_bytes;
     fill_media_fast(s);
     if (!rc) {
         std::vector<DevScene> one(1, d);
@@ -2049,7 +2061,7 @@ RTMI_EXPORT int rtmi_scene_create_ex(rtmi_ctx *c, int32_t n_prims, const int32_t
     if (rc) { rtmi_scene_destroy(s); return rc; }
     if (knobs.debug)
         fprintf(stderr, "[rtmi] scene create: records %.2f ms, trees %.2f ms, tables + upload (%zu allocations, %.2f MB) %.2f ms\n", P.t_tree0 - t_create0, P.t_tree1 - P.t_tree0,
-                s->allocs.size(), (double)s->device_bytes / 1e6, now_ms() - P.t_tree1);
+                s->allocs.size() + s->table_allocs.size(), (double)s->device_bytes / 1e6, now_ms() - P.t_tree1);
     {
         rtmi_scene::Args &A = s->args;
         A.prim_kind.assign(prim_kind, prim_kind + n_prims); A.prim_mat.assign(prim_mat, prim_mat + n_prims);
@@ -2172,6 +2184,133 @@ RTMI_EXPORT int rtmi_scene_set_images(rtmi_scene *s, int32_t n_images, const int
     return reupload_descriptor(s);
 }
 
+// ---- the camera of a live scene (rtmi_scene_set_camera*) ---------------------------------------------------------------------------------------
+namespace {
+// What a camera move changes in the descriptor: the last three fields of DevScene, one contiguous range
+constexpr size_t kCamOffset = offsetof(DevScene, cam_kind), kCamBytes = sizeof(DevScene) - offsetof(DevScene, cam_kind);
+static_assert(offsetof(DevScene, cam_fixed_origin) == offsetof(DevScene, cam_kind) + sizeof(int) && offsetof(DevScene, cam) == offsetof(DevScene, cam_kind) + 2 * sizeof(int) &&
+              kCamBytes == 2 * sizeof(int) + 24 * sizeof(double), "cam_kind, cam_fixed_origin and cam[24] end the descriptor");
+struct CameraArgs { double cam[24]; int cam_kind, cam_fixed_origin; };
+
+// One wave, in stream order: lane l < 24 stores cam[l], lanes 24 and 25 the two ints.  Plain vector stores; the renders queued behind it on the stream read the
+// descriptor through the scalar cache, which every kernel launch invalidates.  No LDS, no scratch.
+__global__ void __launch_bounds__(64) set_camera_kernel(DevScene *d, CameraArgs a) {
+    const int l = (int)threadIdx.x;
+    if (l < 24) d->cam[l] = a.cam[l];
+    else if (l == 24) d->cam_kind = a.cam_kind;
+    else if (l == 25) d->cam_fixed_origin = a.cam_fixed_origin;
+}
+
+// the argument errors of both set forms, reported before the handle is examined
+int check_camera_args(int cam_kind, const double *cam) {
+    if (!cam) return fail(RTMI_E_ARG, "cam is NULL");
+    if (cam_kind != RTMI_CAM_PINHOLE && cam_kind != RTMI_CAM_THINLENS) return fail(RTMI_E_UNSUPPORTED, "camera kind %d unsupported on GPU path", cam_kind);
+    return RTMI_OK;
+}
+// The camera FITS the built scene: no MovingSphere, or its shutter interval lies inside the interval the swept bounds were built for
+bool camera_fits(const rtmi_scene *s, int cam_kind, const double *cam, double *t_lo, double *t_hi) {
+    camera_shutter(cam_kind, cam, *t_lo, *t_hi);
+    return !s->has_moving || (*t_lo >= s->dev.cull_t_lo && *t_hi <= s->dev.cull_t_hi);
+}
+// the host's half of a camera move: the mirror of the descriptor (launch decisions read it) and the arguments a clone replays
+void adopt_camera(rtmi_scene *s, int cam_kind, const double *cam) {
+    s->dev.cam_kind = cam_kind;
+    std::memcpy(s->dev.cam, cam, 24 * sizeof(double));
+    s->dev.cam_fixed_origin = camera_fixed_origin(cam_kind, cam);
+    s->args.cam.assign(cam, cam + 24); s->args.cam_kind = cam_kind;
+    s->revision++;
+}
+// The slow path: the staged build with the new camera from the arrays the scene keeps, new tables uploaded beside the old ones, then the swap.
+// Until the swap nothing of the scene has changed; a failure frees what was uploaded and leaves it as it was.
+int rebuild_for_camera(rtmi_scene *s, int cam_kind, const double *cam) {
+    const rtmi_scene::Args &A = s->args;
+    const SceneArrays a{s->n_prims, A.prim_kind.data(), A.prim_geom.data(), A.prim_mat.data(), s->n_mats, A.mat_kind.data(), A.mat_tex.data(), A.mat_param.data(),
+                        s->n_tex, A.tex_kind.data(), A.tex_param.data(), A.tex_child.data(), cam_kind, cam,
+                        A.prim_flip.empty() ? nullptr : A.prim_flip.data(), A.prim_xform.empty() ? nullptr : A.prim_xform.data(),
+                        (int)A.xform_kind.size(), A.xform_kind.empty() ? nullptr : A.xform_kind.data(), A.xform_param.empty() ? nullptr : A.xform_param.data()};
+    const PackedScene P = pack_scene(a, read_build_knobs());
+    DevScene nd = P.d;
+    std::vector<void *> fresh;
+    size_t fresh_bytes = 0;
+    int rc = upload_tables(P, nd, fresh, fresh_bytes);
+    if (!rc) {
+        // what the rtmi_scene_set_* calls gave the scene (kept in Args for the clones) stays: the Perlin tables and the images where they are in HBM, the media
+        // call sequence -- a narrowed one too -- and the media mode as the descriptor holds them
+        const DevScene &o = s->dev;
+        nd.perlin_vec = o.perlin_vec; nd.perlin_perm = o.perlin_perm;
+        nd.n_images = o.n_images; nd.image_wh = o.image_wh; nd.image_off = o.image_off; nd.image_rgb = o.image_rgb;
+        nd.n_media = o.n_media; nd.media_seq = o.media_seq;
+        std::memcpy(nd.media_idx, o.media_idx, sizeof nd.media_idx); std::memcpy(nd.media_lo, o.media_lo, sizeof nd.media_lo);
+        fill_media_fast(nd, P.media_fast_of);
+        hipError_t e = hipStreamSynchronize(s->ctx->stream); // the renders in flight read the old tables
+        if (e == hipSuccess) e = hipMemcpy((void *)s->d_dev, &nd, sizeof(DevScene), hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = fail(RTMI_E_DEVICE, "rtmi_scene_set_camera: %s", hipGetErrorString(e));
+    }
+    if (rc) { for (void *p : fresh) (void)hipFree(p); return rc; }
+    for (void *p : s->table_allocs) (void)hipFree(p); // (the stream was synchronised above and nothing has been launched since)
+    s->table_allocs.swap(fresh);
+    s->device_bytes = s->device_bytes - s->table_bytes + fresh_bytes;
+    s->table_bytes = fresh_bytes;
+    s->dev = nd;
+    s->uses_perlin = P.uses_perlin; s->max_image = P.max_image; s->bvh_node_count = P.bvh_node_count; s->bvh_depth = P.bvh_depth;
+    s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of;
+    s->args.cam.assign(cam, cam + 24); s->args.cam_kind = cam_kind;
+    s->revision++;
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_scene_set_camera(rtmi_scene *s, int32_t cam_kind, const double *cam, int32_t *out_rebuilt) {
+    int rc = check_camera_args(cam_kind, cam);
+    if (rc) return rc;
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    double c24[24], t_lo, t_hi; // (a copy: the caller may hand back what rtmi_scene_camera gave it, or anything else that the call itself overwrites)
+    std::memcpy(c24, cam, sizeof c24);
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    if (!camera_fits(s, cam_kind, c24, &t_lo, &t_hi)) {
+        rc = rebuild_for_camera(s, cam_kind, c24);
+        if (!rc && out_rebuilt) *out_rebuilt = 1;
+        return rc;
+    }
+    struct { int cam_kind, cam_fixed_origin; double cam[24]; } rec; // the descriptor's last three fields as they lie in it
+    static_assert(sizeof rec == kCamBytes, "the camera range of the descriptor");
+    rec.cam_kind = cam_kind; rec.cam_fixed_origin = camera_fixed_origin(cam_kind, c24);
+    std::memcpy(rec.cam, c24, sizeof c24);
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    HIP_TRY(hipMemcpy((char *)(void *)s->d_dev + kCamOffset, &rec, kCamBytes, hipMemcpyHostToDevice));
+    adopt_camera(s, cam_kind, c24);
+    if (out_rebuilt) *out_rebuilt = 0;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_scene_set_camera_stream(rtmi_scene *s, int32_t cam_kind, const double *cam, void *stream) {
+    int rc = check_camera_args(cam_kind, cam);
+    if (rc) return rc;
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    CameraArgs a;
+    std::memcpy(a.cam, cam, sizeof a.cam);
+    a.cam_kind = cam_kind; a.cam_fixed_origin = camera_fixed_origin(cam_kind, a.cam);
+    double t_lo, t_hi;
+    if (!camera_fits(s, cam_kind, a.cam, &t_lo, &t_hi))
+        return fail(RTMI_E_UNSUPPORTED, "the camera's shutter interval [%g, %g] lies outside the interval [%g, %g] the scene's MovingSphere bounds were built for: "
+                                        "rtmi_scene_set_camera rebuilds them, the stream form does not", t_lo, t_hi, s->dev.cull_t_lo, s->dev.cull_t_hi);
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = stream ? (hipStream_t)stream : s->ctx->stream;
+    hipLaunchKernelGGL(set_camera_kernel, dim3(1), dim3(64), 0, st, (DevScene *)(void *)s->d_dev, a);
+    HIP_TRY(hipGetLastError());
+    adopt_camera(s, cam_kind, a.cam); // at once: the launch decisions of the renders queued behind the kernel (the stash's width) are taken at enqueue time
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_scene_camera(rtmi_scene *s, int32_t *cam_kind, double *cam, double *built_t_lo, double *built_t_hi) {
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    if (cam_kind) *cam_kind = s->dev.cam_kind;
+    if (cam) std::memcpy(cam, s->dev.cam, 24 * sizeof(double));
+    if (built_t_lo) *built_t_lo = s->dev.cull_t_lo;
+    if (built_t_hi) *built_t_hi = s->dev.cull_t_hi;
+    return RTMI_OK;
+}
+
 RTMI_EXPORT int rtmi_scene_device_bytes(rtmi_scene *s, int64_t *out_bytes) {
     if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
     if (!out_bytes) return fail(RTMI_E_ARG, "out_bytes is NULL");
@@ -2183,6 +2322,7 @@ RTMI_EXPORT int rtmi_scene_destroy(rtmi_scene *s) {
     if (!s || s->magic != 0x52545343u) return fail(RTMI_E_STATE, "invalid scene handle");
     if (ctx_ok(s->ctx)) { (void)hipSetDevice(s->ctx->device); (void)hipStreamSynchronize(s->ctx->stream); }
     for (void *p : s->allocs) (void)hipFree(p);
+    for (void *p : s->table_allocs) (void)hipFree(p);
     s->magic = 0;
     delete s;
     return RTMI_OK;

@@ -674,6 +674,21 @@ std::vector<char> texture_uv_use(const SceneArrays &a) {
     return uses;
 }
 
+// DevScene::cam_fixed_origin of a camera (pack_scene, rtmi_scene_set_camera*): get-ray's origin is cam origin + lens offset; with aperture 0 the offset is
+// (+-0, +-0, +-0) (camera.clj:39-44: lens-radius * rand-in-unit-disk), and x + (+-0) = x bit for bit for every x except -0 (whose sum with +0 is +0): then, and
+// for the pinhole camera, all rays share one origin
+inline int camera_fixed_origin(int cam_kind, const double *cam) {
+    bool fixed = cam_kind == RTMI_CAM_PINHOLE || cam[21] == 0.0;
+    for (int k = 0; k < 3; ++k) fixed = fixed && !(cam[k] == 0.0 && std::signbit(cam[k])) && std::isfinite(cam[k]);
+    for (int k = 12; k < 18; ++k) fixed = fixed && std::isfinite(cam[k]);
+    return fixed ? 1 : 0;
+}
+// The shutter interval of a camera: the times its rays carry (camera.clj:16: a pinhole ray has time 0; camera.clj:48: a thin lens draws t0 + (t1 - t0) * rand)
+inline void camera_shutter(int cam_kind, const double *cam, double &t_lo, double &t_hi) {
+    t_lo = cam_kind == RTMI_CAM_THINLENS ? std::min(cam[22], cam[23]) : 0.0;
+    t_hi = cam_kind == RTMI_CAM_THINLENS ? std::max(cam[22], cam[23]) : 0.0;
+}
+
 // The caller's (checked) arrays -> every device table of the scene, in host memory.  Pure host code: the same arrays and knobs give the same bytes.
 PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
     PackedScene P;
@@ -690,13 +705,7 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
     }
     d.n_tex = a.n_tex; d.cam_kind = a.cam_kind;
     std::memcpy(d.cam, cam, 24 * sizeof(double));
-    { // get-ray's origin is cam origin + lens offset; with aperture 0 the offset is (+-0, +-0, +-0) (camera.clj:39-44: lens-radius * rand-in-unit-disk), and
-      // x + (+-0) = x bit for bit for every x except -0 (whose sum with +0 is +0): then, and for the pinhole camera, all rays share one origin
-        bool fixed = a.cam_kind == RTMI_CAM_PINHOLE || cam[21] == 0.0;
-        for (int k = 0; k < 3; ++k) fixed = fixed && !(cam[k] == 0.0 && std::signbit(cam[k])) && std::isfinite(cam[k]);
-        for (int k = 12; k < 18; ++k) fixed = fixed && std::isfinite(cam[k]);
-        d.cam_fixed_origin = fixed ? 1 : 0;
-    }
+    d.cam_fixed_origin = camera_fixed_origin(a.cam_kind, cam);
     for (int k = 0; k < a.n_xforms; ++k) {
         const double *p = a.xform_param + (size_t)k * 3;
         const double rec[4] = {a.xform_kind[k] == RTMI_XFORM_TRANSLATE ? 0.0 : 1.0, p[0], p[1], p[2]};
@@ -707,8 +716,8 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
     // multiply in the precision the kernel computes in).  exact12[i] = c0.xyz, r*r, c1.xyz, t0, t1, moving?, r, 0 and the FP32 cull entry of scan variant
     // SCAN_SGPR_CULL: a MovingSphere's bounds its sweep over the camera's shutter interval [t_lo, t_hi] (rays outside that interval bypass the cull, make_cull_ray):
     // centre = midpoint of the two extreme centres, radius = r + half the distance between them, both inflated for the float rounding of the centre.
-    const double t_lo = a.cam_kind == RTMI_CAM_THINLENS ? std::min(cam[22], cam[23]) : 0.0;
-    const double t_hi = a.cam_kind == RTMI_CAM_THINLENS ? std::max(cam[22], cam[23]) : 0.0;
+    double t_lo, t_hi;
+    camera_shutter(a.cam_kind, cam, t_lo, t_hi);
     std::vector<float> cull; // per primitive: centre (3), r2, w
     std::vector<BvhBox> wbox((size_t)n_prims);
     std::vector<char> bounded((size_t)n_prims, 0);

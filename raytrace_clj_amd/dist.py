@@ -153,6 +153,10 @@ class MultiDevice:
         for ctx in self.ctxs:
             ctx.set_option(name, value)
 
+    def set_camera(self, camera):
+        """DeviceScene.set_camera (the host form) on every replica -> True if any replica rebuilt its trees (they all do, or none)"""
+        return any([s.set_camera(camera) for s in self.scenes])
+
     def render(self, nx, ny, ns, depth=50, seed=0x5EED0002, precision="f64"):
         """host buffers: (linear [ny,nx,3] float64, rgb8, counters)"""
         import numpy as np
@@ -324,11 +328,15 @@ class FramePipeline:
         for ctx, _, _, _ in self.slots:
             ctx.set_option(name, value)
 
-    def step(self, ns, **kw):
-        """enqueue one frame on the next slot; returns that slot's TileRenderer (its buffers are valid after sync())"""
+    def step(self, ns, camera=None, **kw):
+        """enqueue one frame on the next slot; returns that slot's TileRenderer (its buffers are valid after sync()).  camera: the slot's own
+        scene takes it in stream order before its frame (DeviceScene.set_camera's stream form: the host is not waited for, and the frames
+        still in flight on the other slots keep their cameras -- every slot has a scene of its own)."""
         ctx, ds, tr, stream = self.slots[self.next]
         self.next = (self.next + 1) % len(self.slots)
         if tr.world == 1 and len(self.slots) > 1:
+            if camera is not None:
+                ds.set_camera(camera, stream=0)
             # one GPU, several frames in flight: every slot runs on its CONTEXT'S OWN stream (stream = NULL in the C-ABI).  The HIP
             # runtime deals streams to a few hardware queues in creation order; the contexts' streams are created back to back and
             # land on different queues, whereas extra torch streams were seen to share one queue (kernels of two frames then
@@ -336,6 +344,8 @@ class FramePipeline:
             tr._step(None, ns, kw.get("depth", 50), kw.get("seed", 0x5EED0002), kw.get("precision", "f64"))
             return tr
         with torch.cuda.stream(stream):
+            if camera is not None:
+                ds.set_camera(camera, stream=stream.cuda_stream)
             tr.step(ns, **kw)
         return tr
 
