@@ -784,114 +784,40 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
 
-// ---- progressive frame kernels (rtmi_render_progressive*) ----------------------------------------------------------------------------------------
+// ---- progressive and adaptive frame kernels (rtmi_render_progressive*, rtmi_render_adaptive*) ----------------------------------------------------
 // The frame's state is tile-major like c->accum: element l + 64 k of local tile t (pixel (l + 64 k) / 3 of the tile, channel (l + 64 k) % 3) sits at
 // t * 192 + l + 64 k in three arrays: the running sum of the samples in R (what reduce_kernel keeps between passes), and, in double whatever R is,
 // Welford's running mean and M2 of the same samples (the noise estimate; the image never reads them).
-
-// One pass of the sample buffer, samples [s_begin, s_begin + s_count), folded into the state: the sums with reduce_kernel's fold (same order, the
-// first sample of the frame is the start value), the noise state with Welford's update.  Lane l of a tile's wave owns elements l, l + 64, l + 128
-// of the tile's row, so every load is contiguous.  Elements outside the region keep 0.
-template <typename R>
-__global__ void __launch_bounds__(kBlock) progressive_fold_kernel(const R *__restrict__ samples, R *__restrict__ sums, double *__restrict__ mean,
-                                                                  double *__restrict__ m2, const int *__restrict__ tile_ids, int tiles_x, int n_local_tiles,
-                                                                  int s_begin, int s_count, u64 *counters, u64 n_valid_pixels, int rx0, int ry0, int rx1, int ry1) {
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid == 0) counters[1] = n_valid_pixels; // metrics total-pixels, core.clj:47
-    if (gid >= (long long)n_local_tiles * 64) return;
-    const int tile_local = (int)(gid >> 6), l = (int)(gid & 63);
-    const int gtile = tile_ids[tile_local];
-    const int tx = (gtile % tiles_x) * RTMI_TILE, ty = (gtile / tiles_x) * RTMI_TILE;
-    R acc[3];
-    double mu[3], q[3];
-    bool valid[3];
-    const size_t tile_base = (size_t)tile_local * 192;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int p = (l + 64 * k) / 3;
-        const int x = tx + (p & 7), y = ty + (p >> 3);
-        valid[k] = x >= rx0 && x < rx1 && y >= ry0 && y < ry1;
-        const bool carry = valid[k] && s_begin > 0;
-        const size_t o = tile_base + l + 64 * k;
-        acc[k] = carry ? sums[o] : R(0);
-        mu[k] = carry ? mean[o] : 0.0;
-        q[k] = carry ? m2[o] : 0.0;
-    }
-    const R *row = samples + (size_t)tile_local * s_count * 192 + l;
-    for (int s = 0; s < s_count; ++s, row += 192) {
-        const R v[3] = {row[0], row[64], row[128]};
-        if (s_begin + s == 0) { // the fold starts FROM the first sample (not 0 + first)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { acc[k] = v[k]; mu[k] = (double)v[k]; q[k] = 0.0; }
-        } else {
-            const double n = (double)(s_begin + s + 1);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                acc[k] = acc[k] + v[k];
-                const double x = (double)v[k], d = x - mu[k];
-                mu[k] = mu[k] + d / n;
-                q[k] = q[k] + d * (x - mu[k]); // >= 0 up to rounding; exactly 0 while every sample is equal
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const size_t o = tile_base + l + 64 * k;
-        sums[o] = valid[k] ? acc[k] : R(0);
-        mean[o] = valid[k] ? mu[k] : 0.0;
-        m2[o] = valid[k] ? q[k] : 0.0;
-    }
-}
-
-// The state after k samples -> the dense region [x0, x0 + w) x [y0, y0 + h) of the frame (its local tiles are the window [tx0, tx0 + wtx) x ..., row-major):
-// out_linear = the mean as reduce_kernel's last pass computes it, out_rgb8 = assemble_kernel<double>'s quantiser of that mean, out_stderr = per pixel the
-// largest of the three channels' standard errors of the mean, sqrt((M2 / (k - 1)) / k) (+inf for k = 1).  Any output may be null.
-template <typename R>
-__global__ void __launch_bounds__(kBlock) progressive_resolve_kernel(const R *__restrict__ sums, const double *__restrict__ m2, int k, int tx0, int ty0,
-                                                                     int wtx, int x0, int y0, int w, int h, double *__restrict__ out_linear,
-                                                                     unsigned char *__restrict__ out_rgb8, double *__restrict__ out_stderr) {
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= (long long)w * h) return;
-    const int x = x0 + (int)(gid % w), y = y0 + (int)(gid / w);
-    const int t = (y / RTMI_TILE - ty0) * wtx + (x / RTMI_TILE - tx0);
-    const int l = (y % RTMI_TILE) * RTMI_TILE + (x % RTMI_TILE);
-    const size_t e = ((size_t)t * 64 + l) * 3;
-    double err = k > 1 ? 0.0 : INFINITY;
-    for (int c = 0; c < 3; ++c) {
-        const double m = (double)(sums[e + c] * (R(1.0) / (R)k)); // reduce_kernel's last pass
-        if (out_linear) out_linear[gid * 3 + c] = m;
-        if (out_rgb8) { // assemble_kernel<double>
-            const double q = Real<double>::sqrt_(m) * 255.99;
-            unsigned char o = 0;
-            if (q == q) { const double mq = q < 255.99 ? q : 255.99; o = (unsigned char)(int)mq; }
-            out_rgb8[gid * 3 + c] = o;
-        }
-        if (k > 1) {
-            const double se = ::sqrt((m2[e + c] / (double)(k - 1)) / (double)k);
-            err = se > err ? se : err;
-        }
-    }
-    if (out_stderr) out_stderr[gid] = err;
-}
-
-// ---- adaptive frame kernels (rtmi_render_adaptive*) -----------------------------------------------------------------------------------------------
 // An adaptive call traces only the frame's active tiles.  The active list is two parallel arrays in ascending tile order: act_tiles[i] = global tile
 // (what the trace kernel takes as tile_ids, so sample-buffer tile i holds entry i's samples) and act_slots[i] = the tile's local tile number, i.e.
 // where its state sits (slot * 192) and what the resolve indexes.  n_t[slot] = samples the tile holds.
 
-// progressive_fold_kernel behind the indirection: the wave of entry i folds sample-buffer tile i into the state at act_slots[i] * 192, same element
-// ownership, same arithmetic.  On the call's last pass (`last`) it also decides: k = s_begin + s_count, the tile stays active (keep[i] = 1) if k < 2
-// or any element of a valid pixel fails se <= eps, se = sqrt((M2 / (k - 1)) / k) as the resolve computes it (a NaN fails); n_t[slot] = k.
-template <typename R>
-__global__ void __launch_bounds__(kBlock) adaptive_fold_kernel(const R *__restrict__ samples, R *__restrict__ sums, double *__restrict__ mean,
-                                                               double *__restrict__ m2, const int *__restrict__ act_tiles, const int *__restrict__ act_slots,
-                                                               int tiles_x, int n_active, int s_begin, int s_count, u64 *counters, u64 n_valid_pixels, int rx0,
-                                                               int ry0, int rx1, int ry1, int last, double eps, int *__restrict__ keep, int *__restrict__ n_t) {
+// what the retiring fold takes beside the uniform one's arguments (an empty one for the uniform fold, which reads none of it)
+struct FoldRetire {
+    const int *act_slots = nullptr;
+    int last = 0; // the call's last pass: decide
+    double eps = 0.0;
+    int *keep = nullptr, *n_t = nullptr;
+};
+
+// One pass of the sample buffer, samples [s_begin, s_begin + s_count), folded into the state: the sums with reduce_kernel's fold (same order, the
+// first sample of the frame is the start value), the noise state with Welford's update.  The wave of entry i of `tiles` folds sample-buffer tile i;
+// lane l owns elements l, l + 64, l + 128 of the tile's row, so every load is contiguous.  Elements outside the region keep 0.
+// RETIRE = false (a progressive call): `tiles` is the render's tile list and entry i's state sits at i * 192.
+// RETIRE = true (an adaptive call): `tiles` is the active list and the state sits at rt.act_slots[i] * 192, same element ownership, same arithmetic.
+// On the call's last pass (rt.last) the wave also decides: k = s_begin + s_count, the tile stays active (keep[i] = 1) if k < 2 or any element of a
+// valid pixel fails se <= eps, se = sqrt((M2 / (k - 1)) / k) as the resolve computes it, on the M2 in registers (a NaN fails); n_t[slot] = k.
+template <typename R, bool RETIRE>
+__global__ void __launch_bounds__(kBlock) frame_fold_kernel(const R *__restrict__ samples, R *__restrict__ sums, double *__restrict__ mean,
+                                                            double *__restrict__ m2, const int *__restrict__ tiles, int tiles_x, int n_entries, int s_begin,
+                                                            int s_count, u64 *counters, u64 n_valid_pixels, int rx0, int ry0, int rx1, int ry1, FoldRetire rt) {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid == 0) counters[1] = n_valid_pixels; // metrics total-pixels, core.clj:47
-    if (gid >= (long long)n_active * 64) return; // (whole waves: kBlock is a multiple of 64)
+    if (gid >= (long long)n_entries * 64) return; // (whole waves: kBlock is a multiple of 64)
     const int entry = (int)(gid >> 6), l = (int)(gid & 63);
-    const int gtile = act_tiles[entry], slot = act_slots[entry];
+    const int gtile = tiles[entry];
+    int slot = entry;
+    if constexpr (RETIRE) slot = rt.act_slots[entry];
     const int tx = (gtile % tiles_x) * RTMI_TILE, ty = (gtile / tiles_x) * RTMI_TILE;
     R acc[3];
     double mu[3], q[3];
@@ -921,7 +847,7 @@ __global__ void __launch_bounds__(kBlock) adaptive_fold_kernel(const R *__restri
                 acc[k] = acc[k] + v[k];
                 const double x = (double)v[k], d = x - mu[k];
                 mu[k] = mu[k] + d / n;
-                q[k] = q[k] + d * (x - mu[k]);
+                q[k] = q[k] + d * (x - mu[k]); // >= 0 up to rounding; exactly 0 while every sample is equal
             }
         }
     }
@@ -932,18 +858,71 @@ __global__ void __launch_bounds__(kBlock) adaptive_fold_kernel(const R *__restri
         mean[o] = valid[k] ? mu[k] : 0.0;
         m2[o] = valid[k] ? q[k] : 0.0;
     }
-    if (!last) return;
-    const int kk = s_begin + s_count;
-    bool noisy = false;
-    if (kk > 1) {
+    if constexpr (RETIRE) {
+        if (!rt.last) return;
+        const int kk = s_begin + s_count;
+        bool noisy = false;
+        if (kk > 1) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const double se = ::sqrt((q[k] / (double)(kk - 1)) / (double)kk); // progressive_resolve_kernel's expression
-            noisy = noisy || (valid[k] && !(se <= eps));
+            for (int k = 0; k < 3; ++k) {
+                const double se = ::sqrt((q[k] / (double)(kk - 1)) / (double)kk); // pixel_estimate's expression
+                noisy = noisy || (valid[k] && !(se <= rt.eps));
+            }
+        }
+        const u64 any = __ballot(noisy);
+        if (l == 0) { rt.keep[entry] = (kk < 2 || any != 0ull) ? 1 : 0; rt.n_t[slot] = kk; }
+    }
+}
+
+// What the state says about one pixel after k samples: m = the three means as reduce_kernel's last pass computes them, sums * (R(1) / R(k)),
+// widened to double; err = the largest of the three channels' standard errors of the mean, sqrt((M2 / (k - 1)) / k) (+inf for k <= 1; a NaN
+// standard error does not replace the running maximum).  e = the element index of the pixel's first channel.
+struct PixelEstimate { double m[3], err; int k; };
+template <typename R>
+__device__ inline PixelEstimate pixel_estimate(const R *__restrict__ sums, const double *__restrict__ m2, size_t e, int k) {
+    PixelEstimate p;
+    p.k = k;
+    p.err = k > 1 ? 0.0 : INFINITY;
+    for (int c = 0; c < 3; ++c) {
+        p.m[c] = (double)(sums[e + c] * (R(1.0) / (R)k)); // reduce_kernel's last pass
+        if (k > 1) {
+            const double se = ::sqrt((m2[e + c] / (double)(k - 1)) / (double)k);
+            p.err = se > p.err ? se : p.err;
         }
     }
-    const u64 any = __ballot(noisy);
-    if (l == 0) { keep[entry] = (kk < 2 || any != 0ull) ? 1 : 0; n_t[slot] = kk; }
+    return p;
+}
+
+// The 8-bit quantiser of a linear mean, in double for both precisions: the one copy below the kernel section.  assemble_kernel and
+// assemble_region_kernel above keep their own (their text is part of the hashed kernel section); test_gpu_frame_exact.py pins all copies
+// against each other.
+__device__ inline unsigned char quantise8(double m) {
+    const double q = Real<double>::sqrt_(m) * 255.99;
+    unsigned char o = 0;
+    if (q == q) { const double mq = q < 255.99 ? q : 255.99; o = (unsigned char)(int)mq; }
+    return o;
+}
+
+// The state -> the dense region [x0, x0 + w) x [y0, y0 + h) of the frame (its local tiles are the window [tx0, tx0 + wtx) x ..., row-major): per pixel
+// pixel_estimate with k = n_t[t] samples behind every pixel of local tile t (n_t = null: a uniform frame, k_uniform everywhere).  out_linear = the
+// mean, out_rgb8 = quantise8 of it, out_stderr = the error, out_samples = k.  Any output may be null.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) frame_resolve_kernel(const R *__restrict__ sums, const double *__restrict__ m2, const int *__restrict__ n_t,
+                                                               int k_uniform, int tx0, int ty0, int wtx, int x0, int y0, int w, int h,
+                                                               double *__restrict__ out_linear, unsigned char *__restrict__ out_rgb8,
+                                                               double *__restrict__ out_stderr, int *__restrict__ out_samples) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)w * h) return;
+    const int x = x0 + (int)(gid % w), y = y0 + (int)(gid / w);
+    const int t = (y / RTMI_TILE - ty0) * wtx + (x / RTMI_TILE - tx0);
+    const int l = (y % RTMI_TILE) * RTMI_TILE + (x % RTMI_TILE);
+    const PixelEstimate p = pixel_estimate(sums, m2, ((size_t)t * 64 + l) * 3, n_t ? n_t[t] : k_uniform);
+    for (int c = 0; c < 3; ++c) {
+        if (out_linear) out_linear[gid * 3 + c] = p.m[c];
+        if (out_rgb8) out_rgb8[gid * 3 + c] = quantise8(p.m[c]);
+    }
+    if (out_stderr) out_stderr[gid] = p.err;
+    if (out_samples) out_samples[gid] = p.k;
 }
 
 // Ordered compaction of the active list, one workgroup of kCompactBlock threads walking the n entries in strides of its size: entry i survives if
@@ -999,39 +978,7 @@ __global__ void __launch_bounds__(kCompactBlock) adaptive_compact_kernel(const i
     }
 }
 
-// progressive_resolve_kernel with k read per tile: n_t[t] samples behind every pixel of local tile t; out_samples = that count per pixel.
-template <typename R>
-__global__ void __launch_bounds__(kBlock) adaptive_resolve_kernel(const R *__restrict__ sums, const double *__restrict__ m2, const int *__restrict__ n_t,
-                                                                  int tx0, int ty0, int wtx, int x0, int y0, int w, int h, double *__restrict__ out_linear,
-                                                                  unsigned char *__restrict__ out_rgb8, double *__restrict__ out_stderr,
-                                                                  int *__restrict__ out_samples) {
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= (long long)w * h) return;
-    const int x = x0 + (int)(gid % w), y = y0 + (int)(gid / w);
-    const int t = (y / RTMI_TILE - ty0) * wtx + (x / RTMI_TILE - tx0);
-    const int l = (y % RTMI_TILE) * RTMI_TILE + (x % RTMI_TILE);
-    const size_t e = ((size_t)t * 64 + l) * 3;
-    const int k = n_t[t];
-    double err = k > 1 ? 0.0 : INFINITY;
-    for (int c = 0; c < 3; ++c) {
-        const double m = (double)(sums[e + c] * (R(1.0) / (R)k)); // reduce_kernel's last pass
-        if (out_linear) out_linear[gid * 3 + c] = m;
-        if (out_rgb8) { // assemble_kernel<double>
-            const double q = Real<double>::sqrt_(m) * 255.99;
-            unsigned char o = 0;
-            if (q == q) { const double mq = q < 255.99 ? q : 255.99; o = (unsigned char)(int)mq; }
-            out_rgb8[gid * 3 + c] = o;
-        }
-        if (k > 1) {
-            const double se = ::sqrt((m2[e + c] / (double)(k - 1)) / (double)k);
-            err = se > err ? se : err;
-        }
-    }
-    if (out_stderr) out_stderr[gid] = err;
-    if (out_samples) out_samples[gid] = k;
-}
-
-// rtmi_adaptive_retire*: the decision of adaptive_fold_kernel's last pass taken on a noise map the caller supplies.  One wave per entry of the active
+// rtmi_adaptive_retire*: the decision of the retiring frame_fold_kernel's last pass taken on a noise map the caller supplies.  One wave per entry of the active
 // list, lane l = pixel l of the entry's 8x8 tile: the wave reads eight 64-byte row segments of the whole-frame map [ny][nx] at the tile's place in the
 // IMAGE (act_tiles: the global tile; act_slots, the tile's place in the frame's state, is not needed here), only where the pixel lies inside the
 // region clipped to the image.  keep[entry] = 1 if any such pixel fails noise <= eps (a NaN fails).  adaptive_compact_kernel follows.
@@ -1055,8 +1002,8 @@ __global__ void __launch_bounds__(kBlock) adaptive_retire_kernel(const double *_
 
 // ---- dealt progressive frames (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*) ------------------
 // The frame's local tiles are the dealt tiles first, first + stride, ...: local slot t holds global tile first + t * stride, so no rectangular window
-// describes them.  The resolve therefore writes tile RECORDS, rec[t][64][RTMI_PROG_REC]: what adaptive_resolve_kernel computes per pixel -- the mean
-// sums * (R(1) / R(n_t)) widened to double, the largest channel's standard error (+inf for n_t = 1), n_t -- in tile order, the layout a gather moves.
+// describes them.  The resolve therefore writes tile RECORDS, rec[t][64][RTMI_PROG_REC]: pixel_estimate's three means, its error and its k, the
+// values frame_resolve_kernel writes per pixel, in tile order, the layout a gather moves.
 // n_t = null: a uniform frame, every tile holds k samples.  One thread per pixel of the n_slots record slots; slots past the frame's n_local tiles
 // (the padding of a gathered record) and pixels outside the image hold five zeros.
 template <typename R>
@@ -1078,22 +1025,14 @@ __global__ void __launch_bounds__(kBlock) progressive_record_kernel(const R *__r
         for (int c = 0; c < RTMI_PROG_REC; ++c) o[c] = 0.0;
         return;
     }
-    const size_t e = (size_t)gid * 3;
-    const int k = n_t ? n_t[t] : k_uniform;
-    double err = k > 1 ? 0.0 : INFINITY;
-    for (int c = 0; c < 3; ++c) {
-        o[c] = (double)(sums[e + c] * (R(1.0) / (R)k)); // reduce_kernel's last pass
-        if (k > 1) {
-            const double se = ::sqrt((m2[e + c] / (double)(k - 1)) / (double)k); // progressive_resolve_kernel's expression
-            err = se > err ? se : err;
-        }
-    }
-    o[3] = err;
-    o[4] = (double)k;
+    const PixelEstimate p = pixel_estimate(sums, m2, (size_t)gid * 3, n_t ? n_t[t] : k_uniform);
+    for (int c = 0; c < 3; ++c) o[c] = p.m[c];
+    o[3] = p.err;
+    o[4] = (double)p.k;
 }
 
 // gathered[r][k][64][RTMI_PROG_REC] (rank r's k-th tile is global tile r + k * world; rank_stride = doubles per rank record) -> the dense frame:
-// assemble_kernel<double> for the mean (the same quantiser), the standard error and the sample count beside it.  Any output may be null.
+// assemble_kernel<double> for the mean (quantise8), the standard error and the sample count beside it.  Any output may be null.
 __global__ void __launch_bounds__(kBlock) assemble_progressive_kernel(const double *__restrict__ gathered, int world, size_t rank_stride, int tiles_x,
                                                                       int nx, int ny, double *__restrict__ out_linear, unsigned char *__restrict__ out_rgb8,
                                                                       double *__restrict__ out_stderr, int *__restrict__ out_samples) {
@@ -1107,12 +1046,7 @@ __global__ void __launch_bounds__(kBlock) assemble_progressive_kernel(const doub
     for (int c = 0; c < 3; ++c) {
         const double m = p[c];
         if (out_linear) out_linear[gid * 3 + c] = m;
-        if (out_rgb8) { // assemble_kernel<double>
-            const double q = Real<double>::sqrt_(m) * 255.99;
-            unsigned char o = 0;
-            if (q == q) { const double mq = q < 255.99 ? q : 255.99; o = (unsigned char)(int)mq; }
-            out_rgb8[gid * 3 + c] = o;
-        }
+        if (out_rgb8) out_rgb8[gid * 3 + c] = quantise8(m);
     }
     if (out_stderr) out_stderr[gid] = p[3];
     if (out_samples) out_samples[gid] = (int)p[4];
@@ -1285,12 +1219,7 @@ __global__ void __launch_bounds__(kBlock) denoise_store_kernel(const double *__r
     for (int c = 0; c < 3; ++c) {
         const double m = state[(size_t)c * n + p];
         if (out_linear) out_linear[3 * p + c] = m;
-        if (out_rgb8) { // assemble_kernel<double>
-            const double q = Real<double>::sqrt_(m) * 255.99;
-            unsigned char o = 0;
-            if (q == q) { const double mq = q < 255.99 ? q : 255.99; o = (unsigned char)(int)mq; }
-            out_rgb8[3 * p + c] = o;
-        }
+        if (out_rgb8) out_rgb8[3 * p + c] = quantise8(m);
     }
     if (out_stderr) out_stderr[p] = se_copy ? se_copy[p] : ::sqrt(state[3 * n + p]);
 }
@@ -1303,7 +1232,7 @@ struct ProgKey {
     int first = 0, stride = 1; // the dealing: the frame's local tiles are the global tiles first, first + stride, ... ((0, 1): every tile of the region)
 };
 
-// A context's progressive frame (rtmi_render_progressive*): the state progressive_fold_kernel keeps (sums in the precision of the frame, Welford
+// A context's progressive frame (rtmi_render_progressive*): the state frame_fold_kernel keeps (sums in the precision of the frame, Welford
 // mean / M2 in double), the cumulative metrics counters, and the key; k = samples [0, k) it holds (0 = no frame).  Its own buffers: a one-shot
 // render on the same context in between does not touch it.
 // Per-tile state (rtmi_render_adaptive*): n_tiles local tiles of valid_pixels pixels inside the image and the region.  While `adaptive` is false every
@@ -1626,69 +1555,73 @@ int report_phase_stamps(rtmi_ctx *c, hipStream_t st) {
 }
 #endif
 
-// The sample passes of a render: samples [s_first, s_end) of every pixel of the local tiles, as many per pass as the sample buffer holds, each pass one
-// trace launch followed by its fold.  A one-shot render (prog = null) runs samples [0, ns) and reduce_kernel folds them into c->accum and, on the last
-// pass, the mean into d_tiles_linear.  A progressive call (prog = the context's frame) folds them into the frame with progressive_fold_kernel; the trace
-// kernel counts its rays into the frame's counters.  A progressive call that fails once it got past the test hook has dropped its frame (k = 0).
-template <typename R>
-int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int depth, uint64_t seed, int first, int stride, const int *rg, void *d_tiles_linear,
-                  void *d_counters, hipStream_t st, ProgFrame *prog, const AdaptiveCall *ad = nullptr) {
-    rtmi_ctx *c = s->ctx;
-    int n_local = 0;
-    const int whole[4] = {0, 0, nx, ny};
-    if (!rg) rg = whole;
-    int rc = ensure_tile_ids(c, nx, ny, first, stride, rg, st, &n_local);
-    if (rc) return rc;
-    c->last_stream = st;
-    if (c->fail_next_render) { c->fail_next_render = 0; return fail(RTMI_E_DEVICE, "render failed (injected by the test hook test_fail_next_render)"); }
-    if (prog) { // from here on the frame is being changed: it only holds samples again once this call has succeeded
-        prog->k = 0;
-        const size_t elems = (size_t)std::max(n_local, 1) * 192;
-        if (s_first == 0) {
-            rc = prog->sums.ensure(elems * sizeof(R));
-            if (!rc) rc = prog->mean.ensure(elems * sizeof(double));
-            if (!rc) rc = prog->m2.ensure(elems * sizeof(double));
-            if (!rc) rc = prog->counters.ensure(2 * sizeof(u64));
-            if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(prog->counters.p, 0, 2 * sizeof(u64), st));
-        } else if (prog->sums.bytes < elems * sizeof(R) || prog->m2.bytes < elems * sizeof(double)) {
-            return fail(RTMI_E_STATE, "progressive frame buffers do not match the frame"); // (the key check makes this unreachable)
-        }
-        d_counters = prog->counters.p;
-        if (s_first == 0 || !ad) prog->adaptive = false; // a new frame, or a uniform continuation (no tile retired: the entries checked): every tile active, n_t = k
-        prog->n_tiles = n_local; prog->valid_pixels = c->tile_valid_pixels;
-        if (ad && !prog->adaptive) { // the per-tile state of a frame whose tiles all hold ad->k_before samples (0: a new frame) and are all active
-            const size_t ints = (size_t)std::max(n_local, 1) * sizeof(int);
-            for (int i = 0; i < 2 && !rc; ++i) { rc = prog->act_tiles[i].ensure(ints); if (!rc) rc = prog->act_slots[i].ensure(ints); }
-            if (!rc) rc = prog->n_t.ensure(ints);
-            if (!rc) rc = prog->keep.ensure(ints);
-            if (!rc) rc = prog->meta.ensure(2 * sizeof(int));
-            if (rc) return rc;
-            prog->cur = 0;
-            hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kCompactBlock), 0, st, (const int *)nullptr, reinterpret_cast<const int *>(c->tile_ids.p),
-                               (const int *)nullptr, n_local, reinterpret_cast<int *>(prog->act_tiles[0].p), reinterpret_cast<int *>(prog->act_slots[0].p),
-                               reinterpret_cast<int *>(prog->meta.p), ad->k_before, reinterpret_cast<int *>(prog->n_t.p), tiles_x_of(nx), std::max(rg[0], 0),
-                               std::max(rg[1], 0), std::min(rg[2], nx), std::min(rg[3], ny));
-            HIP_TRY(hipGetLastError());
-            prog->adaptive = true;
-            prog->n_active = n_local; prog->active_pixels = c->tile_valid_pixels;
-            prog->pixel_samples = c->tile_valid_pixels * (long long)ad->k_before;
-        }
-    }
-    rc = c->counters.ensure(8 * sizeof(u64)); // [0..1] the metrics when the caller passes no buffer, [2] the work-queue head, [3..4] traversal counters
-    if (rc) return rc;
-    if (d_counters && !prog) HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(u64), st));
-    HIP_TRY(hipMemsetAsync(reinterpret_cast<u64 *>(c->counters.p) + 3, 0, 2 * sizeof(u64), st));
-    if (n_local == 0) { if (prog) { prog->k = s_end; c->last_passes = 0; } return RTMI_OK; } // (a dealt frame on a rank beyond the last tile: an empty frame that still counts its calls)
-    if (ad) n_local = prog->n_active; // an adaptive call traces and folds the frame's active list, not the render's tile list
-    if (n_local == 0) { prog->k = s_end; c->last_passes = 0; return RTMI_OK; } // every tile has retired: nothing to trace, k advances
-    const int *tile_list = ad ? reinterpret_cast<const int *>(prog->act_tiles[prog->cur].p) : reinterpret_cast<const int *>(c->tile_ids.p);
-    u64 *cnt = d_counters ? reinterpret_cast<u64 *>(d_counters) : reinterpret_cast<u64 *>(c->counters.p);
-    unsigned *queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 2);
+// f(double{}) or f(float{}): a call's precision selects the instantiation
+template <typename F> auto with_real(int precision, F f) { return precision == RTMI_F64 ? f(double{}) : f(float{}); }
 
-    // sample-buffer passes: samples [s_begin, s_begin+s_count) of every local pixel per pass
-    const int ns = s_end - s_first; // samples this call renders
-    const size_t per_sample = (size_t)n_local * 64 * 3 * sizeof(R);
+// the output region rg = {x0, y0, x1, y1} clipped to the image
+struct Region { int x0, y0, x1, y1; };
+Region clip_region(const int *rg, int nx, int ny) { return {std::max(rg[0], 0), std::max(rg[1], 0), std::min(rg[2], nx), std::min(rg[3], ny)}; }
+
+// adaptive_compact_kernel on `st`.  tile_ids != null: the identity over a render's n tiles into list 0, n_t = init_n_t everywhere (the start of the
+// per-tile state); tile_ids = null: the n entries of the frame's current list, filtered by `keep`, into the other list.  The list written is current.
+hipError_t launch_compact(ProgFrame &f, const int *tile_ids, int n, int init_n_t, int tiles_x, const Region &r, hipStream_t st) {
+    const bool start = tile_ids != nullptr;
+    const int to = start ? 0 : 1 - f.cur;
+    hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kCompactBlock), 0, st, start ? nullptr : reinterpret_cast<const int *>(f.keep.p),
+                       start ? tile_ids : reinterpret_cast<const int *>(f.act_tiles[f.cur].p),
+                       start ? nullptr : reinterpret_cast<const int *>(f.act_slots[f.cur].p), n, reinterpret_cast<int *>(f.act_tiles[to].p),
+                       reinterpret_cast<int *>(f.act_slots[to].p), reinterpret_cast<int *>(f.meta.p), start ? init_n_t : -1,
+                       start ? reinterpret_cast<int *>(f.n_t.p) : nullptr, tiles_x, r.x0, r.y0, r.x1, r.y1);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) f.cur = to;
+    return e;
+}
+
+// The per-tile state of a frame whose n_local tiles (tile_ids, the context's tile list) all hold k samples and are all active: the arrays, the
+// identity compaction with n_t = k, the host's mirror.  A launch failure is reported as "`what`: ..." with RTMI_E_DEVICE.
+int ensure_tile_state(ProgFrame &f, const int *tile_ids, int n_local, int k, int tiles_x, const Region &r, hipStream_t st, const char *what) {
+    const size_t ints = (size_t)std::max(n_local, 1) * sizeof(int);
+    int rc = RTMI_OK;
+    for (int i = 0; i < 2 && !rc; ++i) { rc = f.act_tiles[i].ensure(ints); if (!rc) rc = f.act_slots[i].ensure(ints); }
+    if (!rc) rc = f.n_t.ensure(ints);
+    if (!rc) rc = f.keep.ensure(ints);
+    if (!rc) rc = f.meta.ensure(2 * sizeof(int));
+    if (rc) return rc;
+    const hipError_t e = launch_compact(f, tile_ids, n_local, k, tiles_x, r, st);
+    if (e != hipSuccess) return fail(RTMI_E_DEVICE, "%s: %s", what, hipGetErrorString(e));
+    f.adaptive = true;
+    f.n_active = n_local; f.active_pixels = f.valid_pixels;
+    f.pixel_samples = f.valid_pixels * (long long)k;
+    return RTMI_OK;
+}
+
+// render_passes, step 1 (progressive and adaptive calls): the frame for this call.  A new frame (s_first = 0) gets its buffers, real_bytes per sum,
+// and zeroed counters; a continuation's are checked; an adaptive call (ad) on a frame without per-tile state builds it.  From here on the frame is
+// being changed: it only holds samples again (k > 0) once the call has succeeded.
+int prepare_frame(rtmi_ctx *c, ProgFrame *prog, const AdaptiveCall *ad, int n_local, int s_first, size_t real_bytes, int tiles_x, const Region &r,
+                  hipStream_t st) {
+    prog->k = 0;
+    const size_t elems = (size_t)std::max(n_local, 1) * 192;
+    if (s_first == 0) {
+        int rc = prog->sums.ensure(elems * real_bytes);
+        if (!rc) rc = prog->mean.ensure(elems * sizeof(double));
+        if (!rc) rc = prog->m2.ensure(elems * sizeof(double));
+        if (!rc) rc = prog->counters.ensure(2 * sizeof(u64));
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(prog->counters.p, 0, 2 * sizeof(u64), st));
+    } else if (prog->sums.bytes < elems * real_bytes || prog->m2.bytes < elems * sizeof(double)) {
+        return fail(RTMI_E_STATE, "progressive frame buffers do not match the frame"); // (the key check makes this unreachable)
+    }
+    if (s_first == 0 || !ad) prog->adaptive = false; // a new frame, or a uniform continuation (no tile retired: the entries checked): every tile active, n_t = k
+    prog->n_tiles = n_local; prog->valid_pixels = c->tile_valid_pixels;
+    if (ad && !prog->adaptive) // the per-tile state of a frame whose tiles all hold ad->k_before samples (0: a new frame) and are all active
+        return ensure_tile_state(*prog, reinterpret_cast<const int *>(c->tile_ids.p), n_local, ad->k_before, tiles_x, r, st, "hipGetLastError()");
+    return RTMI_OK;
+}
+
+// render_passes, step 2: how many of the call's ns samples of n_local tiles one pass takes, and a sample buffer that holds them.
+int size_sample_passes(rtmi_ctx *c, int n_local, int ns, size_t real_bytes, int *out_s_per_pass) {
+    const size_t per_sample = (size_t)n_local * 64 * 3 * real_bytes;
     int s_per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(ns, c->workspace_bytes / (int64_t)per_sample));
     // the work queue is indexed with 32 bits: items per pass (+ one claim per wave past the end) must stay below 2^32
     while (s_per_pass > 1 && (long long)n_local * s_per_pass * 64 >= 0xf0000000ll) s_per_pass /= 2;
@@ -1705,6 +1638,7 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
             s_per_pass = std::min(s_per_pass, fit);
         }
         for (;;) {
+            int rc;
             if (c->fail_allocs > 0) { c->fail_allocs--; c->samples.release(); rc = fail(RTMI_E_NOMEM, "hipMalloc(%zu bytes) failed (injected by the test hook)", per_sample * (size_t)s_per_pass); }
             else rc = c->samples.ensure(per_sample * (size_t)s_per_pass);
             if (!rc) break;
@@ -1713,6 +1647,123 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
             s_per_pass = (s_per_pass + 1) / 2;
         }
     }
+    *out_s_per_pass = s_per_pass;
+    return RTMI_OK;
+}
+
+// render_passes, step 3: one trace launch on `st`.  tp holds what the call fixes; the pass adds its samples [s_begin, s_begin + s_count), the
+// claim size and a zeroed queue head.  *out_e1 = the timing event behind the kernel (null: not timed).
+int launch_trace_pass(rtmi_scene *s, const TracePlan &plan, TraceParams &tp, int s_begin, int s_count, hipStream_t st, hipEvent_t *out_e1) {
+    rtmi_ctx *c = s->ctx;
+    tp.s_begin = s_begin; tp.s_count = s_count;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if ((c->flags & RTMI_FLAG_TIMING) && c->events_used < 8192) {
+        const int rc = next_event_pair(c, &e0, &e1);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(e0, st));
+    }
+    tp.total_items = (unsigned)((long long)tp.n_local_tiles * s_count * 64);
+    { // claim size: one global atomic per claim -- 256 items on small launches (a short tail matters more), up to 1024 when a wave has
+      // thousands of claims ahead of it (C3: 129 000 items per wave)
+        const long long per_wave = (long long)tp.total_items / std::max(1, c->cus * 16);
+        // (mixed-kind scenes: 192 -- their launches are short and end in a long die-off of deep paths through the media; make-final 64 / 128 / 192 / 256 / 320 / 384 / 512 items:
+        // 18.2 / 17.3 / 17.1 - 17.2 / 17.4 - 17.5 / 17.9 / 18.3 / 19.4 ms, the Cornell box indifferent)
+        unsigned qb = s->dev.has_ext ? 192u : kQueueBlock;
+        while (qb < 1024u && per_wave >= (long long)qb * 128) qb *= 2;
+        if (const char *e = std::getenv("RTMI_QUEUE_BLOCK_RT")) qb = std::max(64, std::atoi(e) / 64 * 64);
+        tp.qblock = qb;
+    }
+    HIP_TRY(hipMemsetAsync(tp.queue, 0, sizeof(unsigned), st));
+    // persistent launch: as many workgroups as stay resident (at most blocks_per_cu per CU); the queue feeds them
+    int resident = 0;
+    { // the occupancy query is a runtime call per launch and replica: asked once per (kernel, LDS bytes) and kept on the context
+        const std::pair<const void *, size_t> key(reinterpret_cast<const void *>(plan.kern), plan.lds.bytes);
+        auto it = c->occupancy.find(key);
+        if (it == c->occupancy.end()) {
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, plan.kern, kTraceBlock, plan.lds.bytes));
+            c->occupancy.emplace(key, resident);
+        } else resident = it->second;
+    }
+    const int grid_trace = std::max(1, c->cus * std::max(1, std::min(c->blocks_per_cu * (256 / kTraceBlock), resident)));
+    if (c->last_grid != grid_trace && std::getenv("RTMI_DEBUG"))
+        fprintf(stderr, "[rtmi] trace launch: %d workgroups of %d threads (%d resident per CU by the occupancy query, cap %d), %zu B LDS each\n",
+                grid_trace, kTraceBlock, resident, c->blocks_per_cu * (256 / kTraceBlock), plan.lds.bytes);
+    c->last_grid = grid_trace;
+    hipLaunchKernelGGL(plan.kern, dim3(grid_trace), dim3(kTraceBlock), plan.lds.bytes, st, s->d_dev, tp);
+    HIP_TRY(hipGetLastError());
+    if (e1) HIP_TRY(hipEventRecord(e1, st));
+    *out_e1 = e1;
+    return RTMI_OK;
+}
+
+// render_passes, step 4: the fold of the pass tp traced.  A one-shot render (prog = null): reduce_kernel into c->accum and, on the last of the ns
+// samples, the mean into d_tiles_linear; a progressive call: frame_fold_kernel into the frame; an adaptive one (ad): its retiring instantiation,
+// which decides on the pass that ends at s_end.  Timed (e1): the fold is the interval from the trace kernel's end event to one recorded here.
+template <typename R>
+int launch_fold(rtmi_ctx *c, const TraceParams &tp, int ns, int s_end, void *d_tiles_linear, bool count_pixels, ProgFrame *prog, const AdaptiveCall *ad,
+                hipEvent_t e1, hipStream_t st) {
+    const long long npx = (long long)tp.n_local_tiles * 64;
+    const dim3 grid((unsigned)((npx + kBlock - 1) / kBlock));
+    const R *samples = reinterpret_cast<const R *>(c->samples.p);
+    if (ad) {
+        FoldRetire rt;
+        rt.act_slots = reinterpret_cast<const int *>(prog->act_slots[prog->cur].p);
+        rt.last = tp.s_begin + tp.s_count == s_end ? 1 : 0; rt.eps = ad->eps;
+        rt.keep = reinterpret_cast<int *>(prog->keep.p); rt.n_t = reinterpret_cast<int *>(prog->n_t.p);
+        hipLaunchKernelGGL((frame_fold_kernel<R, true>), grid, dim3(kBlock), 0, st, samples, reinterpret_cast<R *>(prog->sums.p),
+                           reinterpret_cast<double *>(prog->mean.p), reinterpret_cast<double *>(prog->m2.p), tp.tile_ids, tp.tiles_x, tp.n_local_tiles,
+                           tp.s_begin, tp.s_count, tp.counters, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1, rt);
+    } else if (prog)
+        hipLaunchKernelGGL((frame_fold_kernel<R, false>), grid, dim3(kBlock), 0, st, samples, reinterpret_cast<R *>(prog->sums.p),
+                           reinterpret_cast<double *>(prog->mean.p), reinterpret_cast<double *>(prog->m2.p), tp.tile_ids, tp.tiles_x, tp.n_local_tiles,
+                           tp.s_begin, tp.s_count, tp.counters, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1, FoldRetire{});
+    else
+        hipLaunchKernelGGL((reduce_kernel<R>), grid, dim3(kBlock), 0, st, samples, reinterpret_cast<R *>(c->accum.p),
+                           reinterpret_cast<double *>(d_tiles_linear), tp.tile_ids, tp.tiles_x, tp.nx, tp.ny, tp.n_local_tiles, tp.s_begin, tp.s_count, ns,
+                           count_pixels ? tp.counters : nullptr, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1);
+    HIP_TRY(hipGetLastError());
+    if (e1) {
+        const size_t k = (size_t)c->events_used - 1;
+        while (c->events_r.size() <= k) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->events_r.push_back(e); }
+        HIP_TRY(hipEventRecord(c->events_r[k], st));
+    }
+    return RTMI_OK;
+}
+
+// The sample passes of a render: samples [s_first, s_end) of every pixel of the local tiles, as many per pass as the sample buffer holds, each pass one
+// trace launch followed by its fold.  A one-shot render (prog = null) runs samples [0, ns) and reduce_kernel folds them into c->accum and, on the last
+// pass, the mean into d_tiles_linear.  A progressive call (prog = the context's frame) folds them into the frame with frame_fold_kernel; the trace
+// kernel counts its rays into the frame's counters.  An adaptive call (ad) traces and folds the frame's active list and ends with the compaction that
+// retires tiles.  A progressive call that fails once it got past the test hook has dropped its frame (k = 0).
+template <typename R>
+int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int depth, uint64_t seed, int first, int stride, const int *rg, void *d_tiles_linear,
+                  void *d_counters, hipStream_t st, ProgFrame *prog, const AdaptiveCall *ad = nullptr) {
+    rtmi_ctx *c = s->ctx;
+    int n_local = 0;
+    const int whole[4] = {0, 0, nx, ny};
+    if (!rg) rg = whole;
+    const Region region = clip_region(rg, nx, ny);
+    int rc = ensure_tile_ids(c, nx, ny, first, stride, rg, st, &n_local);
+    if (rc) return rc;
+    c->last_stream = st;
+    if (c->fail_next_render) { c->fail_next_render = 0; return fail(RTMI_E_DEVICE, "render failed (injected by the test hook test_fail_next_render)"); }
+    if (prog) {
+        rc = prepare_frame(c, prog, ad, n_local, s_first, sizeof(R), tiles_x_of(nx), region, st);
+        if (rc) return rc;
+        d_counters = prog->counters.p;
+    }
+    rc = c->counters.ensure(8 * sizeof(u64)); // [0..1] the metrics when the caller passes no buffer, [2] the work-queue head, [3..4] traversal counters
+    if (rc) return rc;
+    if (d_counters && !prog) HIP_TRY(hipMemsetAsync(d_counters, 0, 2 * sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(reinterpret_cast<u64 *>(c->counters.p) + 3, 0, 2 * sizeof(u64), st));
+    if (n_local == 0) { if (prog) { prog->k = s_end; c->last_passes = 0; } return RTMI_OK; } // (a dealt frame on a rank beyond the last tile: an empty frame that still counts its calls)
+    if (ad) n_local = prog->n_active; // an adaptive call traces and folds the frame's active list, not the render's tile list
+    if (n_local == 0) { prog->k = s_end; c->last_passes = 0; return RTMI_OK; } // every tile has retired: nothing to trace, k advances
+
+    const int ns = s_end - s_first; // samples this call renders
+    int s_per_pass = 0;
+    rc = size_sample_passes(c, n_local, ns, sizeof(R), &s_per_pass);
+    if (rc) return rc;
     c->last_passes = (ns + s_per_pass - 1) / s_per_pass;
     if (!prog && s_per_pass < ns) {
         rc = c->accum.ensure((size_t)n_local * 64 * 3 * sizeof(R));
@@ -1724,88 +1775,28 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
     const TracePlan plan = choose_trace_kernel<R>(s, c, read_launch_knobs(), nptiles > 1, lds_bytes);
     c->last_accel = plan.accel;
 
+    TraceParams tp; // what every pass of the call shares; launch_trace_pass adds the pass
+    tp.nx = nx; tp.ny = ny; tp.depth = depth; tp.seed = seed; tp.tiles_x = tiles_x_of(nx);
+    tp.n_local_tiles = n_local;
+    tp.tile_ids = ad ? reinterpret_cast<const int *>(prog->act_tiles[prog->cur].p) : reinterpret_cast<const int *>(c->tile_ids.p);
+    tp.samples = c->samples.p;
+    tp.counters = d_counters ? reinterpret_cast<u64 *>(d_counters) : reinterpret_cast<u64 *>(c->counters.p);
+    tp.prims_per_tile = (c->scan_variant >= SCAN_SGPR || s->dev.has_ext) ? 0 : ppt; tp.n_ptiles = nptiles;
+    tp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 2);
+    tp.rx0 = region.x0; tp.ry0 = region.y0; tp.rx1 = region.x1; tp.ry1 = region.y1;
+    tp.trav = reinterpret_cast<u64 *>(c->counters.p) + 3;
+    tp.suspend_lanes = plan.suspend_lanes; tp.susp_off = plan.lds.susp_off; tp.stash_off = plan.lds.stash_off;
     for (int s_begin = s_first; s_begin < s_end; s_begin += s_per_pass) {
-        const int s_count = std::min(s_per_pass, s_end - s_begin);
-        TraceParams tp;
-        tp.nx = nx; tp.ny = ny; tp.depth = depth; tp.seed = seed; tp.tiles_x = tiles_x_of(nx);
-        tp.n_local_tiles = n_local; tp.tile_ids = tile_list;
-        tp.s_begin = s_begin; tp.s_count = s_count; tp.samples = c->samples.p; tp.counters = cnt;
-        tp.prims_per_tile = (c->scan_variant >= SCAN_SGPR || s->dev.has_ext) ? 0 : ppt; tp.n_ptiles = nptiles;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if ((c->flags & RTMI_FLAG_TIMING) && c->events_used < 8192) {
-            rc = next_event_pair(c, &e0, &e1);
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(e0, st));
-        }
-        tp.queue = queue; tp.total_items = (unsigned)((long long)n_local * s_count * 64);
-        { // claim size: one global atomic per claim -- 256 items on small launches (a short tail matters more), up to 1024 when a wave has
-          // thousands of claims ahead of it (C3: 129 000 items per wave)
-            const long long per_wave = (long long)tp.total_items / std::max(1, c->cus * 16);
-            // (mixed-kind scenes: 192 -- their launches are short and end in a long die-off of deep paths through the media; make-final 64 / 128 / 192 / 256 / 320 / 384 / 512 items:
-            // 18.2 / 17.3 / 17.1 - 17.2 / 17.4 - 17.5 / 17.9 / 18.3 / 19.4 ms, the Cornell box indifferent)
-            unsigned qb = s->dev.has_ext ? 192u : kQueueBlock;
-            while (qb < 1024u && per_wave >= (long long)qb * 128) qb *= 2;
-            if (const char *e = std::getenv("RTMI_QUEUE_BLOCK_RT")) qb = std::max(64, std::atoi(e) / 64 * 64);
-            tp.qblock = qb;
-        }
-        tp.rx0 = std::max(rg[0], 0); tp.ry0 = std::max(rg[1], 0); tp.rx1 = std::min(rg[2], nx); tp.ry1 = std::min(rg[3], ny);
-        tp.trav = reinterpret_cast<u64 *>(c->counters.p) + 3;
-        tp.suspend_lanes = plan.suspend_lanes; tp.susp_off = plan.lds.susp_off; tp.stash_off = plan.lds.stash_off;
-        HIP_TRY(hipMemsetAsync(queue, 0, sizeof(unsigned), st));
-        // persistent launch: as many workgroups as stay resident (at most blocks_per_cu per CU); the queue feeds them
-        int resident = 0;
-        { // the occupancy query is a runtime call per launch and replica: asked once per (kernel, LDS bytes) and kept on the context
-            const std::pair<const void *, size_t> key(reinterpret_cast<const void *>(plan.kern), plan.lds.bytes);
-            auto it = c->occupancy.find(key);
-            if (it == c->occupancy.end()) {
-                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, plan.kern, kTraceBlock, plan.lds.bytes));
-                c->occupancy.emplace(key, resident);
-            } else resident = it->second;
-        }
-        const int grid_trace = std::max(1, c->cus * std::max(1, std::min(c->blocks_per_cu * (256 / kTraceBlock), resident)));
-        if (c->last_grid != grid_trace && std::getenv("RTMI_DEBUG"))
-            fprintf(stderr, "[rtmi] trace launch: %d workgroups of %d threads (%d resident per CU by the occupancy query, cap %d), %zu B LDS each\n",
-                    grid_trace, kTraceBlock, resident, c->blocks_per_cu * (256 / kTraceBlock), plan.lds.bytes);
-        c->last_grid = grid_trace;
-        hipLaunchKernelGGL(plan.kern, dim3(grid_trace), dim3(kTraceBlock), plan.lds.bytes, st, s->d_dev, tp);
-        HIP_TRY(hipGetLastError());
-        if (e1) HIP_TRY(hipEventRecord(e1, st));
-        const long long npx = (long long)n_local * 64;
-        if (ad)
-            hipLaunchKernelGGL((adaptive_fold_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                               reinterpret_cast<const R *>(c->samples.p), reinterpret_cast<R *>(prog->sums.p), reinterpret_cast<double *>(prog->mean.p),
-                               reinterpret_cast<double *>(prog->m2.p), tile_list, reinterpret_cast<const int *>(prog->act_slots[prog->cur].p), tiles_x_of(nx),
-                               n_local, s_begin, s_count, cnt, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1, s_begin + s_count == s_end ? 1 : 0,
-                               ad->eps, reinterpret_cast<int *>(prog->keep.p), reinterpret_cast<int *>(prog->n_t.p));
-        else if (prog)
-            hipLaunchKernelGGL((progressive_fold_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                               reinterpret_cast<const R *>(c->samples.p), reinterpret_cast<R *>(prog->sums.p), reinterpret_cast<double *>(prog->mean.p),
-                               reinterpret_cast<double *>(prog->m2.p), reinterpret_cast<const int *>(c->tile_ids.p), tiles_x_of(nx), n_local,
-                               s_begin, s_count, cnt, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1);
-        else
-            hipLaunchKernelGGL((reduce_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                               reinterpret_cast<const R *>(c->samples.p), reinterpret_cast<R *>(c->accum.p),
-                               reinterpret_cast<double *>(d_tiles_linear), reinterpret_cast<const int *>(c->tile_ids.p), tiles_x_of(nx), nx, ny,
-                               n_local, s_begin, s_count, ns, d_counters ? cnt : nullptr, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1);
-        HIP_TRY(hipGetLastError());
-        if (e1) { // timing: the reduction is the interval from the trace kernel's end event to this one
-            const size_t k = (size_t)c->events_used - 1;
-            while (c->events_r.size() <= k) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->events_r.push_back(e); }
-            HIP_TRY(hipEventRecord(c->events_r[k], st));
-        }
+        hipEvent_t e1 = nullptr;
+        rc = launch_trace_pass(s, plan, tp, s_begin, std::min(s_per_pass, s_end - s_begin), st, &e1);
+        if (!rc) rc = launch_fold<R>(c, tp, ns, s_end, d_tiles_linear, d_counters != nullptr, prog, ad, e1, st);
+        if (rc) return rc;
     }
 #ifdef RTMI_STAMPS
     rc = report_phase_stamps(c, st);
 #endif
-    if (!rc && ad) { // retire: the next active list, in tile order, and its length for the host
-        const int nxt = 1 - prog->cur;
-        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kCompactBlock), 0, st, reinterpret_cast<const int *>(prog->keep.p), tile_list,
-                           reinterpret_cast<const int *>(prog->act_slots[prog->cur].p), n_local, reinterpret_cast<int *>(prog->act_tiles[nxt].p),
-                           reinterpret_cast<int *>(prog->act_slots[nxt].p), reinterpret_cast<int *>(prog->meta.p), -1, (int *)nullptr, tiles_x_of(nx),
-                           std::max(rg[0], 0), std::max(rg[1], 0), std::min(rg[2], nx), std::min(rg[3], ny));
-        HIP_TRY(hipGetLastError());
-        prog->cur = nxt;
-    }
+    if (!rc && ad) // retire: the next active list, in tile order, and its length for the host
+        HIP_TRY(launch_compact(*prog, nullptr, n_local, -1, tiles_x_of(nx), region, st));
     if (!rc && prog) prog->k = s_end;
     return rc;
 }
@@ -1826,6 +1817,41 @@ int check_render_args(rtmi_scene *s, int nx, int ny, int ns, int depth, int prec
     if (s->max_image >= s->dev.n_images) return fail(RTMI_E_STATE, "the scene holds an ImageMap with index %d: call rtmi_scene_set_images first", s->max_image);
     return RTMI_OK;
 }
+
+// The host forms' staging: device planes for npx pixels carved out of c->scratch_lin -- linear [npx][3] doubles, stderr [npx] doubles, the two
+// metrics counters, samples [npx] ints, rgb8 [npx][3] bytes, in that order, so every plane is aligned to its element size.  linear and rgb8
+// always; the others where wanted (else null).  copy_back brings every plane the caller gave a host array for back; the stream is idle by then.
+struct HostStage {
+    size_t npx = 0;
+    double *lin = nullptr, *err = nullptr;
+    u64 *cnt = nullptr;
+    int *smp = nullptr;
+    unsigned char *q = nullptr;
+    int ensure(rtmi_ctx *c, size_t n, bool want_err, bool want_cnt, bool want_smp) {
+        const size_t b_lin = n * 3 * sizeof(double), b_err = want_err ? n * sizeof(double) : 0, b_cnt = want_cnt ? 2 * sizeof(u64) : 0;
+        const size_t b_smp = want_smp ? n * sizeof(int) : 0;
+        const int rc = c->scratch_lin.ensure(b_lin + b_err + b_cnt + b_smp + n * 3 + 64);
+        if (rc) return rc;
+        char *base = reinterpret_cast<char *>(c->scratch_lin.p);
+        npx = n;
+        lin = reinterpret_cast<double *>(base);
+        err = want_err ? reinterpret_cast<double *>(base + b_lin) : nullptr;
+        cnt = want_cnt ? reinterpret_cast<u64 *>(base + b_lin + b_err) : nullptr;
+        smp = want_smp ? reinterpret_cast<int *>(base + b_lin + b_err + b_cnt) : nullptr;
+        q = reinterpret_cast<unsigned char *>(base + b_lin + b_err + b_cnt + b_smp);
+        return RTMI_OK;
+    }
+    // d_cnt: where the call's counters are (this stage's plane, or a frame's own)
+    hipError_t copy_back(double *out_linear, uint8_t *out_rgb8, double *out_stderr, int32_t *out_samples, uint64_t *out_counters, const void *d_cnt) const {
+        hipError_t e = hipSuccess;
+        if (out_linear) e = hipMemcpy(out_linear, lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out_rgb8) e = hipMemcpy(out_rgb8, q, npx * 3, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out_stderr) e = hipMemcpy(out_stderr, err, npx * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out_samples) e = hipMemcpy(out_samples, smp, npx * sizeof(int), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out_counters) e = hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost);
+        return e;
+    }
+};
 
 } // namespace
 
@@ -2343,8 +2369,7 @@ RTMI_EXPORT int rtmi_render_tiles_device(rtmi_scene *s, int32_t nx, int32_t ny, 
     if (!d_tiles_linear) return fail(RTMI_E_ARG, "d_tiles_linear is NULL");
     HIP_TRY(hipSetDevice(s->ctx->device));
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
-    if (precision == RTMI_F64) return render_tiles_impl<double>(s, nx, ny, ns, depth, seed, tile_first, tile_stride, nullptr, d_tiles_linear, d_out_counters, st);
-    return render_tiles_impl<float>(s, nx, ny, ns, depth, seed, tile_first, tile_stride, nullptr, d_tiles_linear, d_out_counters, st);
+    return with_real(precision, [&](auto r) { return render_tiles_impl<decltype(r)>(s, nx, ny, ns, depth, seed, tile_first, tile_stride, nullptr, d_tiles_linear, d_out_counters, st); });
 }
 
 RTMI_EXPORT int rtmi_assemble_device(rtmi_ctx *c, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank, const void *d_gathered,
@@ -2394,24 +2419,18 @@ RTMI_EXPORT int rtmi_render(rtmi_scene *s, int32_t nx, int32_t ny, int32_t ns, i
     const size_t npx = (size_t)w * h;
     rc = c->tiles.ensure((size_t)nwin * 64 * 3 * sizeof(double));
     if (rc) return rc;
-    rc = c->scratch_lin.ensure(npx * 3 * sizeof(double) + npx * 3 + 2 * sizeof(u64) + 64);
+    HostStage stage;
+    rc = stage.ensure(c, npx, false, true, false);
     if (rc) return rc;
-    char *base = reinterpret_cast<char *>(c->scratch_lin.p);
-    double *d_lin = reinterpret_cast<double *>(base);
-    u64 *d_cnt = reinterpret_cast<u64 *>(base + npx * 3 * sizeof(double));
-    unsigned char *d_q = reinterpret_cast<unsigned char *>(base + npx * 3 * sizeof(double) + 2 * sizeof(u64));
     const int rg[4] = {x0, y0, x1, y1};
     hipStream_t st = c->stream;
-    if (precision == RTMI_F64) rc = render_tiles_impl<double>(s, nx, ny, ns, depth, seed, 0, 1, rg, c->tiles.p, d_cnt, st);
-    else rc = render_tiles_impl<float>(s, nx, ny, ns, depth, seed, 0, 1, rg, c->tiles.p, d_cnt, st);
+    rc = with_real(precision, [&](auto r) { return render_tiles_impl<decltype(r)>(s, nx, ny, ns, depth, seed, 0, 1, rg, c->tiles.p, stage.cnt, st); });
     if (rc) return rc;
     hipLaunchKernelGGL((assemble_region_kernel<double>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       reinterpret_cast<const double *>(c->tiles.p), tx0, ty0, wtx, x0, y0, w, h, d_lin, d_q);
+                       reinterpret_cast<const double *>(c->tiles.p), tx0, ty0, wtx, x0, y0, w, h, stage.lin, stage.q);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    if (out_linear) HIP_TRY(hipMemcpy(out_linear, d_lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_q, npx * 3, hipMemcpyDeviceToHost));
-    if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
+    HIP_TRY(stage.copy_back(out_linear, out_rgb8, nullptr, nullptr, out_counters, stage.cnt));
     return RTMI_OK;
 }
 
@@ -2462,6 +2481,20 @@ int check_no_tile_retired(const rtmi_ctx *c, int s_first) {
     return RTMI_OK;
 }
 
+// The frame's state resolved into the dense outputs of its region (device pointers, any may be null; none: nothing is launched), on `st`.
+// per_tile: every local tile with its own sample count n_t (an adaptive frame); else the frame's k everywhere.
+template <typename R>
+hipError_t resolve_frame(const ProgFrame &f, const ProgKey &key, bool per_tile, double *d_lin, unsigned char *d_q, double *d_err, int *d_smp, hipStream_t st) {
+    if (!d_lin && !d_q && !d_err && !d_smp) return hipSuccess;
+    const int x0 = key.rg[0], y0 = key.rg[1], w = key.rg[2] - x0, h = key.rg[3] - y0;
+    const int tx0 = x0 / RTMI_TILE, ty0 = y0 / RTMI_TILE, wtx = (key.rg[2] + RTMI_TILE - 1) / RTMI_TILE - tx0; // the local tiles of the region: this window, row-major
+    const long long npx = (long long)w * h;
+    hipLaunchKernelGGL((frame_resolve_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, reinterpret_cast<const R *>(f.sums.p),
+                       reinterpret_cast<const double *>(f.m2.p), per_tile ? reinterpret_cast<const int *>(f.n_t.p) : (const int *)nullptr, f.k, tx0, ty0, wtx,
+                       x0, y0, w, h, d_lin, d_q, d_err, d_smp);
+    return hipGetLastError();
+}
+
 // Adds samples [s_first, s_first + s_count) to the context's frame (s_first = 0: a new frame), then resolves the state into the region's outputs
 // (device pointers, any may be null) and copies the cumulative counters to d_cnt, all on `st`.
 template <typename R>
@@ -2471,15 +2504,7 @@ int render_progressive_impl(rtmi_scene *s, const ProgKey &key, int s_first, int 
     int rc = render_passes<R>(s, key.nx, key.ny, s_first, s_first + s_count, key.depth, key.seed, 0, 1, key.rg, nullptr, nullptr, st, &f);
     if (rc) return rc;
     f.key = key;
-    const int x0 = key.rg[0], y0 = key.rg[1], w = key.rg[2] - x0, h = key.rg[3] - y0;
-    const int tx0 = x0 / RTMI_TILE, ty0 = y0 / RTMI_TILE, wtx = (key.rg[2] + RTMI_TILE - 1) / RTMI_TILE - tx0; // the local tiles of the region: this window, row-major
-    const long long npx = (long long)w * h;
-    hipError_t e = hipSuccess;
-    if (d_lin || d_q || d_err) {
-        hipLaunchKernelGGL((progressive_resolve_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                           reinterpret_cast<const R *>(f.sums.p), reinterpret_cast<const double *>(f.m2.p), f.k, tx0, ty0, wtx, x0, y0, w, h, d_lin, d_q, d_err);
-        e = hipGetLastError();
-    }
+    hipError_t e = resolve_frame<R>(f, key, false, d_lin, d_q, d_err, nullptr, st);
     if (e == hipSuccess && d_cnt) e = hipMemcpyAsync(d_cnt, f.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess) { f.k = 0; return fail(RTMI_E_DEVICE, "progressive resolve: %s", hipGetErrorString(e)); }
     return RTMI_OK;
@@ -2499,8 +2524,7 @@ RTMI_EXPORT int rtmi_render_progressive_device(rtmi_scene *s, int32_t nx, int32_
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
     double *lin = reinterpret_cast<double *>(d_out_linear), *err = reinterpret_cast<double *>(d_out_stderr);
     unsigned char *q = reinterpret_cast<unsigned char *>(d_out_rgb8);
-    if (precision == RTMI_F64) return render_progressive_impl<double>(s, key, s_first, s_count, lin, q, err, d_out_counters, st);
-    return render_progressive_impl<float>(s, key, s_first, s_count, lin, q, err, d_out_counters, st);
+    return with_real(precision, [&](auto r) { return render_progressive_impl<decltype(r)>(s, key, s_first, s_count, lin, q, err, d_out_counters, st); });
 }
 
 RTMI_EXPORT int rtmi_render_progressive(rtmi_scene *s, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
@@ -2516,21 +2540,14 @@ RTMI_EXPORT int rtmi_render_progressive(rtmi_scene *s, int32_t nx, int32_t ny, i
     if (!rc) rc = check_no_tile_retired(c, s_first);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t npx = (size_t)(x1 - x0) * (size_t)(y1 - y0);
-    rc = c->scratch_lin.ensure(npx * 3 * sizeof(double) + npx * sizeof(double) + npx * 3 + 64);
+    HostStage stage;
+    rc = stage.ensure(c, (size_t)(x1 - x0) * (size_t)(y1 - y0), true, false, false);
     if (rc) return rc;
-    char *base = reinterpret_cast<char *>(c->scratch_lin.p);
-    double *d_lin = reinterpret_cast<double *>(base), *d_err = reinterpret_cast<double *>(base + npx * 3 * sizeof(double));
-    unsigned char *d_q = reinterpret_cast<unsigned char *>(base + npx * 4 * sizeof(double));
     hipStream_t st = c->stream;
-    if (precision == RTMI_F64) rc = render_progressive_impl<double>(s, key, s_first, s_count, d_lin, d_q, d_err, nullptr, st);
-    else rc = render_progressive_impl<float>(s, key, s_first, s_count, d_lin, d_q, d_err, nullptr, st);
+    rc = with_real(precision, [&](auto r) { return render_progressive_impl<decltype(r)>(s, key, s_first, s_count, stage.lin, stage.q, stage.err, nullptr, st); });
     if (rc) return rc;
     hipError_t e = hipStreamSynchronize(st);
-    if (e == hipSuccess && out_linear) e = hipMemcpy(out_linear, d_lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_rgb8) e = hipMemcpy(out_rgb8, d_q, npx * 3, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_stderr) e = hipMemcpy(out_stderr, d_err, npx * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_counters) e = hipMemcpy(out_counters, c->prog.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = stage.copy_back(out_linear, out_rgb8, out_stderr, nullptr, out_counters, c->prog.counters.p);
     if (e != hipSuccess) { c->prog.k = 0; return fail(RTMI_E_DEVICE, "progressive render: %s", hipGetErrorString(e)); }
     return RTMI_OK;
 }
@@ -2570,16 +2587,7 @@ int render_adaptive_impl(rtmi_scene *s, const ProgKey &key, int s_first, int s_c
     int rc = render_passes<R>(s, key.nx, key.ny, s_first, s_first + s_count, key.depth, key.seed, 0, 1, key.rg, nullptr, nullptr, st, &f, &ad);
     if (rc) return rc;
     f.key = key;
-    const int x0 = key.rg[0], y0 = key.rg[1], w = key.rg[2] - x0, h = key.rg[3] - y0;
-    const int tx0 = x0 / RTMI_TILE, ty0 = y0 / RTMI_TILE, wtx = (key.rg[2] + RTMI_TILE - 1) / RTMI_TILE - tx0;
-    const long long npx = (long long)w * h;
-    hipError_t e = hipSuccess;
-    if (d_lin || d_q || d_err || d_smp) {
-        hipLaunchKernelGGL((adaptive_resolve_kernel<R>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                           reinterpret_cast<const R *>(f.sums.p), reinterpret_cast<const double *>(f.m2.p), reinterpret_cast<const int *>(f.n_t.p), tx0, ty0, wtx,
-                           x0, y0, w, h, d_lin, d_q, d_err, d_smp);
-        e = hipGetLastError();
-    }
+    hipError_t e = resolve_frame<R>(f, key, true, d_lin, d_q, d_err, d_smp, st);
     if (e == hipSuccess && d_cnt) e = hipMemcpyAsync(d_cnt, f.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToDevice, st);
     int meta[2] = {f.n_active, (int)f.active_pixels}; // both fit an int: check_render_args refuses frames above 2^30 pixels
     const bool traced = f.n_active > 0; // (the list this call started with: no trace, no compaction, meta unchanged)
@@ -2606,8 +2614,7 @@ RTMI_EXPORT int rtmi_render_adaptive_device(rtmi_scene *s, int32_t nx, int32_t n
     double *lin = reinterpret_cast<double *>(d_out_linear), *err = reinterpret_cast<double *>(d_out_stderr);
     unsigned char *q = reinterpret_cast<unsigned char *>(d_out_rgb8);
     int *smp = reinterpret_cast<int *>(d_out_samples);
-    if (precision == RTMI_F64) return render_adaptive_impl<double>(s, key, s_first, s_count, eps, lin, q, err, smp, d_out_counters, st);
-    return render_adaptive_impl<float>(s, key, s_first, s_count, eps, lin, q, err, smp, d_out_counters, st);
+    return with_real(precision, [&](auto r) { return render_adaptive_impl<decltype(r)>(s, key, s_first, s_count, eps, lin, q, err, smp, d_out_counters, st); });
 }
 
 RTMI_EXPORT int rtmi_render_adaptive(rtmi_scene *s, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, double eps, int32_t depth, uint64_t seed,
@@ -2622,23 +2629,13 @@ RTMI_EXPORT int rtmi_render_adaptive(rtmi_scene *s, int32_t nx, int32_t ny, int3
     rc = check_continuation(c, key, s_first);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t npx = (size_t)(x1 - x0) * (size_t)(y1 - y0);
-    rc = c->scratch_lin.ensure(npx * 3 * sizeof(double) + npx * sizeof(double) + npx * sizeof(int) + npx * 3 + 64);
+    HostStage stage;
+    rc = stage.ensure(c, (size_t)(x1 - x0) * (size_t)(y1 - y0), true, false, true);
     if (rc) return rc;
-    char *base = reinterpret_cast<char *>(c->scratch_lin.p);
-    double *d_lin = reinterpret_cast<double *>(base), *d_err = reinterpret_cast<double *>(base + npx * 3 * sizeof(double));
-    int *d_smp = reinterpret_cast<int *>(base + npx * 4 * sizeof(double));
-    unsigned char *d_q = reinterpret_cast<unsigned char *>(base + npx * 4 * sizeof(double) + npx * sizeof(int));
     hipStream_t st = c->stream;
-    if (precision == RTMI_F64) rc = render_adaptive_impl<double>(s, key, s_first, s_count, eps, d_lin, d_q, d_err, d_smp, nullptr, st);
-    else rc = render_adaptive_impl<float>(s, key, s_first, s_count, eps, d_lin, d_q, d_err, d_smp, nullptr, st);
+    rc = with_real(precision, [&](auto r) { return render_adaptive_impl<decltype(r)>(s, key, s_first, s_count, eps, stage.lin, stage.q, stage.err, stage.smp, nullptr, st); });
     if (rc) return rc;
-    hipError_t e = hipSuccess; // (the stream is synchronised)
-    if (out_linear) e = hipMemcpy(out_linear, d_lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_rgb8) e = hipMemcpy(out_rgb8, d_q, npx * 3, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_stderr) e = hipMemcpy(out_stderr, d_err, npx * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_samples) e = hipMemcpy(out_samples, d_smp, npx * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_counters) e = hipMemcpy(out_counters, c->prog.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToHost);
+    const hipError_t e = stage.copy_back(out_linear, out_rgb8, out_stderr, out_samples, out_counters, c->prog.counters.p); // (the stream is synchronised)
     if (e != hipSuccess) { c->prog.k = 0; return fail(RTMI_E_DEVICE, "adaptive render: %s", hipGetErrorString(e)); }
     return RTMI_OK;
 }
@@ -2694,46 +2691,26 @@ int check_retire_frame(const rtmi_ctx *c, int nx, int ny) {
 int adaptive_retire_impl(rtmi_ctx *c, const double *d_noise, double eps, int32_t *out_retired, hipStream_t st) {
     ProgFrame &f = c->prog;
     const int nx = f.key.nx, ny = f.key.ny;
-    const int rx0 = std::max(f.key.rg[0], 0), ry0 = std::max(f.key.rg[1], 0), rx1 = std::min(f.key.rg[2], nx), ry1 = std::min(f.key.rg[3], ny);
+    const Region r = clip_region(f.key.rg, nx, ny);
     if (!f.adaptive) { // a uniform frame: the per-tile state as the first adaptive call builds it, every tile active with n_t = k
         int n_local = 0;
         int rc = ensure_tile_ids(c, nx, ny, f.key.first, f.key.stride, f.key.rg, st, &n_local); // (another render on the context may have rewritten its tile list)
-        const size_t ints = (size_t)std::max(n_local, 1) * sizeof(int);
-        for (int i = 0; i < 2 && !rc; ++i) { rc = f.act_tiles[i].ensure(ints); if (!rc) rc = f.act_slots[i].ensure(ints); }
-        if (!rc) rc = f.n_t.ensure(ints);
-        if (!rc) rc = f.keep.ensure(ints);
-        if (!rc) rc = f.meta.ensure(2 * sizeof(int));
         if (rc) return rc;
         if (n_local != f.n_tiles) return fail(RTMI_E_STATE, "progressive frame buffers do not match the frame"); // (unreachable: the key is the frame's own)
-        f.cur = 0;
-        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kCompactBlock), 0, st, (const int *)nullptr, reinterpret_cast<const int *>(c->tile_ids.p),
-                           (const int *)nullptr, n_local, reinterpret_cast<int *>(f.act_tiles[0].p), reinterpret_cast<int *>(f.act_slots[0].p),
-                           reinterpret_cast<int *>(f.meta.p), f.k, reinterpret_cast<int *>(f.n_t.p), tiles_x_of(nx), rx0, ry0, rx1, ry1);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { f.k = 0; return fail(RTMI_E_DEVICE, "adaptive retire: %s", hipGetErrorString(e)); }
-        f.adaptive = true;
-        f.n_active = n_local; f.active_pixels = f.valid_pixels;
-        f.pixel_samples = f.valid_pixels * (long long)f.k;
+        rc = ensure_tile_state(f, reinterpret_cast<const int *>(c->tile_ids.p), n_local, f.k, tiles_x_of(nx), r, st, "adaptive retire");
+        if (rc) { if (rc == RTMI_E_DEVICE) f.k = 0; return rc; } // (a failed launch drops the frame, a failed allocation does not)
     }
     if (out_retired) *out_retired = 0;
     if (f.n_active == 0) return RTMI_OK; // nothing to decide, nothing launched
-    const int n = f.n_active, nxt = 1 - f.cur;
-    const int *tile_list = reinterpret_cast<const int *>(f.act_tiles[f.cur].p);
-    hipLaunchKernelGGL(adaptive_retire_kernel, dim3((unsigned)(((long long)n * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_noise, tile_list, n,
-                       tiles_x_of(nx), nx, rx0, ry0, rx1, ry1, eps, reinterpret_cast<int *>(f.keep.p));
+    const int n = f.n_active;
+    hipLaunchKernelGGL(adaptive_retire_kernel, dim3((unsigned)(((long long)n * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_noise,
+                       reinterpret_cast<const int *>(f.act_tiles[f.cur].p), n, tiles_x_of(nx), nx, r.x0, r.y0, r.x1, r.y1, eps, reinterpret_cast<int *>(f.keep.p));
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kCompactBlock), 0, st, reinterpret_cast<const int *>(f.keep.p), tile_list,
-                           reinterpret_cast<const int *>(f.act_slots[f.cur].p), n, reinterpret_cast<int *>(f.act_tiles[nxt].p),
-                           reinterpret_cast<int *>(f.act_slots[nxt].p), reinterpret_cast<int *>(f.meta.p), -1, (int *)nullptr, tiles_x_of(nx), rx0, ry0,
-                           rx1, ry1);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch_compact(f, nullptr, n, -1, tiles_x_of(nx), r, st);
     int meta[2] = {0, 0};
     if (e == hipSuccess) e = hipMemcpyAsync(meta, f.meta.p, sizeof meta, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { f.k = 0; return fail(RTMI_E_DEVICE, "adaptive retire: %s", hipGetErrorString(e)); }
-    f.cur = nxt;
     f.n_active = meta[0]; f.active_pixels = meta[1];
     if (out_retired) *out_retired = n - meta[0];
     return RTMI_OK;
@@ -2878,6 +2855,97 @@ RTMI_EXPORT int rtmi_rccl_probe(const char *soname) {
     return RTMI_OK;
 }
 
+namespace {
+// How a multi-device call moves the replicas' records to replica 0's device, decided before anything is launched: RCCL whenever the replicas sit
+// on distinct devices (n > 1); copies when they share a device (RCCL refuses duplicate devices in one communicator).  RTMI_MULTI_GATHER = "copy":
+// never RCCL; "rccl": RCCL or an error -- no silent substitution -- and also for n = 1 (a one-rank communicator: the whole path -- dlopen,
+// ncclCommInitAll, grouped in-place ncclGather -- on a one-GPU host).  The library owns its communicators: one set per device list, created on
+// first use, kept for the process; without a usable RCCL the gather falls back to peer copies (same result, ordered with events), once and for all.
+struct GatherPlan {
+    bool use_rccl = false;
+    std::vector<ncclComm_t> *comms = nullptr;
+    std::vector<int> devs;
+};
+
+int plan_gather(int n, rtmi_scene *const *scenes, GatherPlan &g) {
+    g.devs.resize((size_t)n);
+    bool distinct = true;
+    for (int r = 0; r < n; ++r) {
+        g.devs[(size_t)r] = scenes[r]->ctx->device;
+        for (int q = 0; q < r; ++q) distinct = distinct && g.devs[(size_t)q] != g.devs[(size_t)r];
+    }
+    const char *force = std::getenv("RTMI_MULTI_GATHER");
+    const bool want_copy = force && !std::strcmp(force, "copy"), want_rccl = force && !std::strcmp(force, "rccl");
+    if (want_rccl && !distinct) return fail(RTMI_E_ARG, "RTMI_MULTI_GATHER=rccl needs replicas on distinct devices (RCCL refuses one device twice in a communicator)");
+    g.use_rccl = distinct && !want_copy && (want_rccl || (n > 1 && !g_rccl_failed));
+    if (!g.use_rccl) return RTMI_OK;
+    std::string why;
+    if (!rccl_load()) why = g_rccl.err;
+    else {
+        auto it = g_comms.find(g.devs);
+        if (it == g_comms.end()) {
+            std::vector<ncclComm_t> cs((size_t)n);
+            const ncclResult_t e = g_rccl.CommInitAll(cs.data(), n, g.devs.data());
+            if (e != ncclSuccess) why = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(e);
+            else it = g_comms.emplace(g.devs, std::move(cs)).first;
+        }
+        if (why.empty()) g.comms = &it->second;
+    }
+    if (!why.empty()) {
+        if (want_rccl) return fail(RTMI_E_DEVICE, "multi-device gather: %s", why.c_str());
+        fprintf(stderr, "[rtmi] multi-device gather falls back to hipMemcpyPeerAsync: %s\n", why.c_str());
+        g_rccl_failed = true;
+        g.use_rccl = false;
+    }
+    return RTMI_OK;
+}
+
+// ONE gather of `words` 8-byte words per replica: recs[r] (on replica r's device, written on its context stream; with copies its ev_done is recorded
+// behind the writes) -> gathered[r] on replica 0's device.  recs[0] = gathered: replica 0's record is in place.
+int enqueue_gather(int n, rtmi_scene *const *scenes, const GatherPlan &g, const std::vector<char *> &recs, char *gathered, size_t words) {
+    rtmi_ctx *c0 = scenes[0]->ctx;
+    HIP_TRY(hipSetDevice(c0->device));
+    int rc = ensure_event(&c0->ev_g0);
+    if (!rc) rc = ensure_event(&c0->ev_g1);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c0->ev_g0, c0->stream));
+    if (g.use_rccl) {
+        ncclResult_t e = g_rccl.GroupStart();
+        for (int r = 0; r < n && e == ncclSuccess; ++r) {
+            (void)hipSetDevice(scenes[r]->ctx->device);
+            e = g_rccl.Gather(recs[(size_t)r], r == 0 ? gathered : nullptr, words, ncclUint64, 0, (*g.comms)[(size_t)r], scenes[r]->ctx->stream);
+        }
+        const ncclResult_t e2 = g_rccl.GroupEnd();
+        (void)hipSetDevice(c0->device);
+        if (e == ncclSuccess) e = e2;
+        if (e != ncclSuccess) { // this communicator set is not trusted again: later calls gather by copies
+            const int code = fail(RTMI_E_DEVICE, "ncclGather: %s", g_rccl.GetErrorString(e));
+            rccl_give_up(g.devs);
+            return code;
+        }
+        c0->last_gather_path = RTMI_GATHER_RCCL;
+    } else {
+        bool peer = false;
+        for (int r = 1; r < n; ++r) {
+            rtmi_ctx *cr = scenes[r]->ctx;
+            char *dst = gathered + (size_t)r * words * 8;
+            HIP_TRY(hipStreamWaitEvent(c0->stream, cr->ev_done, 0));
+            if (cr->device == c0->device) HIP_TRY(hipMemcpyAsync(dst, recs[(size_t)r], words * 8, hipMemcpyDeviceToDevice, c0->stream));
+            else { peer = true; HIP_TRY(hipMemcpyPeerAsync(dst, c0->device, recs[(size_t)r], cr->device, words * 8, c0->stream)); }
+            // replica r's NEXT render into its record waits for this copy (its stream is not otherwise ordered with replica 0's)
+            if (cr->ev_consumed && cr->ev_consumed_device != c0->device) { (void)hipSetDevice(cr->ev_consumed_device); (void)hipEventDestroy(cr->ev_consumed); cr->ev_consumed = nullptr; HIP_TRY(hipSetDevice(c0->device)); }
+            if (!cr->ev_consumed) { HIP_TRY(hipEventCreateWithFlags(&cr->ev_consumed, hipEventDisableTiming)); cr->ev_consumed_device = c0->device; }
+            HIP_TRY(hipEventRecord(cr->ev_consumed, c0->stream));
+            cr->consume_pending = true;
+        }
+        c0->last_gather_path = n == 1 ? RTMI_GATHER_NONE : (peer ? RTMI_GATHER_PEER_COPY : RTMI_GATHER_SAME_DEVICE);
+    }
+    HIP_TRY(hipEventRecord(c0->ev_g1, c0->stream));
+    c0->have_gather = true;
+    return RTMI_OK;
+}
+} // namespace
+
 RTMI_EXPORT int rtmi_render_multi_device(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t ny, int32_t ns, int32_t depth, uint64_t seed,
                                          int32_t precision, void *d_out_linear, void *d_out_rgb8, void *d_out_counters) {
     if (n <= 0 || n > 64 || !scenes) return fail(RTMI_E_ARG, "n must be 1..64 and scenes non-NULL");
@@ -2890,44 +2958,13 @@ RTMI_EXPORT int rtmi_render_multi_device(int32_t n, rtmi_scene *const *scenes, i
     }
     std::lock_guard<std::mutex> lock(g_multi_mu);
     DeviceGuard guard;
+    GatherPlan plan;
+    int rc = plan_gather(n, scenes, plan);
+    if (rc) return rc;
     const int ntiles = tiles_x_of(nx) * tiles_y_of(ny);
     const int per = (ntiles + n - 1) / n;                  // every replica's record is padded to this many tiles
     const size_t rec = (size_t)per * 192 + 2;              // 8-byte words per record: tiles [per][64][3] doubles + the two metrics counters
     rtmi_ctx *c0 = scenes[0]->ctx;
-    std::vector<int> devs((size_t)n);
-    bool distinct = true;
-    for (int r = 0; r < n; ++r) {
-        devs[(size_t)r] = scenes[r]->ctx->device;
-        for (int q = 0; q < r; ++q) distinct = distinct && devs[(size_t)q] != devs[(size_t)r];
-    }
-    // Which gather: RCCL whenever the replicas sit on distinct devices (n > 1); copies when they share a device (RCCL refuses duplicate
-    // devices in one communicator).  RTMI_MULTI_GATHER = "copy": never RCCL; "rccl": RCCL or an error -- no silent substitution -- and also
-    // for n = 1 (a one-rank communicator: the whole path -- dlopen, ncclCommInitAll, grouped in-place ncclGather -- on a one-GPU host).
-    const char *force = std::getenv("RTMI_MULTI_GATHER");
-    const bool want_copy = force && !std::strcmp(force, "copy"), want_rccl = force && !std::strcmp(force, "rccl");
-    if (want_rccl && !distinct) return fail(RTMI_E_ARG, "RTMI_MULTI_GATHER=rccl needs replicas on distinct devices (RCCL refuses one device twice in a communicator)");
-    bool use_rccl = distinct && !want_copy && (want_rccl || (n > 1 && !g_rccl_failed));
-    std::vector<ncclComm_t> *comms = nullptr;
-    if (use_rccl) { // the library owns its communicators: one set per device list, created on first use, kept for the process
-        std::string why;
-        if (!rccl_load()) why = g_rccl.err;
-        else {
-            auto it = g_comms.find(devs);
-            if (it == g_comms.end()) {
-                std::vector<ncclComm_t> cs((size_t)n);
-                const ncclResult_t e = g_rccl.CommInitAll(cs.data(), n, devs.data());
-                if (e != ncclSuccess) why = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(e);
-                else it = g_comms.emplace(devs, std::move(cs)).first;
-            }
-            if (why.empty()) comms = &it->second;
-        }
-        if (!why.empty()) { // no usable RCCL: the gather falls back to peer copies (same result, ordered with events), once and for all
-            if (want_rccl) return fail(RTMI_E_DEVICE, "multi-device gather: %s", why.c_str());
-            fprintf(stderr, "[rtmi] multi-device gather falls back to hipMemcpyPeerAsync: %s\n", why.c_str());
-            g_rccl_failed = true;
-            use_rccl = false;
-        }
-    }
     // From here on work is enqueued on the replicas' streams.  An error after the first launch must not return with kernels still in
     // flight on streams the caller believes idle (it may destroy the contexts next): bail() waits for every stream touched so far.
     int launched = 0;
@@ -2941,7 +2978,7 @@ RTMI_EXPORT int rtmi_render_multi_device(int32_t n, rtmi_scene *const *scenes, i
 #define HIP_BAIL(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return bail(fail(RTMI_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_))); } while (0)
     // 1. every replica renders its tiles (r, r+n, ...) on its own device and stream, straight into its record
     HIP_TRY(hipSetDevice(c0->device));
-    int rc = c0->multi.ensure((size_t)n * rec * 8);
+    rc = c0->multi.ensure((size_t)n * rec * 8);
     if (rc) return rc;
     char *gathered = reinterpret_cast<char *>(c0->multi.p);
     std::vector<char *> recs((size_t)n);
@@ -2955,49 +2992,14 @@ RTMI_EXPORT int rtmi_render_multi_device(int32_t n, rtmi_scene *const *scenes, i
             HIP_BAIL(hipStreamWaitEvent(cr->stream, cr->ev_consumed, 0));
             cr->consume_pending = false;
         }
-        launched = r + 1;
-        if (precision == RTMI_F64) rc = render_tiles_impl<double>(scenes[r], nx, ny, ns, depth, seed, r, n, nullptr, buf, buf + (size_t)per * 192 * 8, cr->stream);
-        else rc = render_tiles_impl<float>(scenes[r], nx, ny, ns, depth, seed, r, n, nullptr, buf, buf + (size_t)per * 192 * 8, cr->stream);
+        launched = r + 1; // before the render: one that fails part-way is waited for
+        rc = with_real(precision, [&](auto real) { return render_tiles_impl<decltype(real)>(scenes[r], nx, ny, ns, depth, seed, r, n, nullptr, buf, buf + (size_t)per * 192 * 8, cr->stream); });
         if (rc) return bail(rc);
-        if (!use_rccl && r > 0) { rc = ensure_event(&cr->ev_done); if (rc) return bail(rc); HIP_BAIL(hipEventRecord(cr->ev_done, cr->stream)); }
+        if (!plan.use_rccl && r > 0) { rc = ensure_event(&cr->ev_done); if (rc) return bail(rc); HIP_BAIL(hipEventRecord(cr->ev_done, cr->stream)); }
     }
     // 2. ONE gather to replica 0's device
-    HIP_BAIL(hipSetDevice(c0->device));
-    rc = ensure_event(&c0->ev_g0); if (!rc) rc = ensure_event(&c0->ev_g1);
+    rc = enqueue_gather(n, scenes, plan, recs, gathered, rec);
     if (rc) return bail(rc);
-    HIP_BAIL(hipEventRecord(c0->ev_g0, c0->stream));
-    if (use_rccl) {
-        ncclResult_t e = g_rccl.GroupStart();
-        for (int r = 0; r < n && e == ncclSuccess; ++r) {
-            (void)hipSetDevice(scenes[r]->ctx->device); // (a communicator knows its device; older RCCLs still want it current for calls inside a group)
-            e = g_rccl.Gather(recs[(size_t)r], r == 0 ? gathered : nullptr, rec, ncclUint64, 0, (*comms)[(size_t)r], scenes[r]->ctx->stream);
-        }
-        const ncclResult_t e2 = g_rccl.GroupEnd();
-        (void)hipSetDevice(c0->device);
-        if (e == ncclSuccess) e = e2;
-        if (e != ncclSuccess) { // this communicator set is not trusted again: later calls gather by copies
-            const int code = fail(RTMI_E_DEVICE, "ncclGather: %s", g_rccl.GetErrorString(e));
-            rccl_give_up(devs);
-            return bail(code);
-        }
-        c0->last_gather_path = RTMI_GATHER_RCCL;
-    } else {
-        bool peer = false;
-        for (int r = 1; r < n; ++r) { // replicas sharing a device (rehearsal on a one-GPU host), RTMI_MULTI_GATHER=copy, or no usable RCCL: copies on replica 0's stream
-            rtmi_ctx *cr = scenes[r]->ctx;
-            HIP_BAIL(hipStreamWaitEvent(c0->stream, cr->ev_done, 0));
-            if (cr->device == c0->device) HIP_BAIL(hipMemcpyAsync(gathered + (size_t)r * rec * 8, recs[(size_t)r], rec * 8, hipMemcpyDeviceToDevice, c0->stream));
-            else { peer = true; HIP_BAIL(hipMemcpyPeerAsync(gathered + (size_t)r * rec * 8, c0->device, recs[(size_t)r], cr->device, rec * 8, c0->stream)); }
-            // replica r's NEXT render into its record waits for this copy (its stream is not otherwise ordered with replica 0's)
-            if (cr->ev_consumed && cr->ev_consumed_device != c0->device) { (void)hipSetDevice(cr->ev_consumed_device); (void)hipEventDestroy(cr->ev_consumed); cr->ev_consumed = nullptr; HIP_BAIL(hipSetDevice(c0->device)); }
-            if (!cr->ev_consumed) { HIP_BAIL(hipEventCreateWithFlags(&cr->ev_consumed, hipEventDisableTiming)); cr->ev_consumed_device = c0->device; }
-            HIP_BAIL(hipEventRecord(cr->ev_consumed, c0->stream));
-            cr->consume_pending = true;
-        }
-        c0->last_gather_path = n == 1 ? RTMI_GATHER_NONE : (peer ? RTMI_GATHER_PEER_COPY : RTMI_GATHER_SAME_DEVICE);
-    }
-    HIP_BAIL(hipEventRecord(c0->ev_g1, c0->stream));
-    c0->have_gather = true;
     // 3. replica 0 un-tiles, quantises and sums the counters
     if (d_out_linear || d_out_rgb8) {
         const long long npx = (long long)nx * ny;
@@ -3021,20 +3023,14 @@ RTMI_EXPORT int rtmi_render_multi(int32_t n, rtmi_scene *const *scenes, int32_t 
     DeviceGuard guard;
     rtmi_ctx *c0 = scenes[0]->ctx;
     HIP_TRY(hipSetDevice(c0->device));
-    const size_t npx = (size_t)nx * (size_t)ny;
-    int rc = c0->scratch_lin.ensure(npx * 3 * sizeof(double) + npx * 3 + 2 * sizeof(u64) + 64);
+    HostStage stage;
+    int rc = stage.ensure(c0, (size_t)nx * (size_t)ny, false, true, false);
     if (rc) return rc;
-    char *base = reinterpret_cast<char *>(c0->scratch_lin.p);
-    double *d_lin = reinterpret_cast<double *>(base);
-    u64 *d_cnt = reinterpret_cast<u64 *>(base + npx * 3 * sizeof(double));
-    unsigned char *d_q = reinterpret_cast<unsigned char *>(base + npx * 3 * sizeof(double) + 2 * sizeof(u64));
-    rc = rtmi_render_multi_device(n, scenes, nx, ny, ns, depth, seed, precision, d_lin, d_q, d_cnt);
+    rc = rtmi_render_multi_device(n, scenes, nx, ny, ns, depth, seed, precision, stage.lin, stage.q, stage.cnt);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c0->device));
     HIP_TRY(hipStreamSynchronize(c0->stream)); // ordered after every replica's render through the gather
-    if (out_linear) HIP_TRY(hipMemcpy(out_linear, d_lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_q, npx * 3, hipMemcpyDeviceToHost));
-    if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
+    HIP_TRY(stage.copy_back(out_linear, out_rgb8, nullptr, nullptr, out_counters, stage.cnt));
     for (int r = 1; r < n; ++r) { HIP_TRY(hipSetDevice(scenes[r]->ctx->device)); HIP_TRY(hipStreamSynchronize(scenes[r]->ctx->stream)); scenes[r]->ctx->consume_pending = false; }
     return RTMI_OK;
 }
@@ -3126,8 +3122,7 @@ RTMI_EXPORT int rtmi_render_adaptive_tiles_device(rtmi_scene *s, int32_t nx, int
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
     const int n_slots = rtmi_local_tiles(nx, ny, tile_first, tile_stride);
     double *rec = reinterpret_cast<double *>(d_tiles_rec);
-    if (precision == RTMI_F64) rc = dealt_launch<double>(s, key, s_first, s_count, retire, eps, rec, n_slots, d_out_counters, st);
-    else rc = dealt_launch<float>(s, key, s_first, s_count, retire, eps, rec, n_slots, d_out_counters, st);
+    rc = with_real(precision, [&](auto r) { return dealt_launch<decltype(r)>(s, key, s_first, s_count, retire, eps, rec, n_slots, d_out_counters, st); });
     if (rc) return rc;
     return dealt_finish(s->ctx, s_count, retire, st);
 }
@@ -3149,94 +3144,6 @@ RTMI_EXPORT int rtmi_assemble_progressive_device(rtmi_ctx *c, int32_t nx, int32_
     HIP_TRY(hipGetLastError());
     return RTMI_OK;
 }
-
-namespace {
-// How a multi-device call moves the replicas' records to replica 0's device: rtmi_render_multi_device's rules (RTMI_MULTI_GATHER, the library's
-// communicator sets, the fall-back to copies), decided before anything is launched.
-struct GatherPlan {
-    bool use_rccl = false;
-    std::vector<ncclComm_t> *comms = nullptr;
-    std::vector<int> devs;
-};
-
-int plan_gather(int n, rtmi_scene *const *scenes, GatherPlan &g) {
-    g.devs.resize((size_t)n);
-    bool distinct = true;
-    for (int r = 0; r < n; ++r) {
-        g.devs[(size_t)r] = scenes[r]->ctx->device;
-        for (int q = 0; q < r; ++q) distinct = distinct && g.devs[(size_t)q] != g.devs[(size_t)r];
-    }
-    const char *force = std::getenv("RTMI_MULTI_GATHER");
-    const bool want_copy = force && !std::strcmp(force, "copy"), want_rccl = force && !std::strcmp(force, "rccl");
-    if (want_rccl && !distinct) return fail(RTMI_E_ARG, "RTMI_MULTI_GATHER=rccl needs replicas on distinct devices (RCCL refuses one device twice in a communicator)");
-    g.use_rccl = distinct && !want_copy && (want_rccl || (n > 1 && !g_rccl_failed));
-    if (!g.use_rccl) return RTMI_OK;
-    std::string why;
-    if (!rccl_load()) why = g_rccl.err;
-    else {
-        auto it = g_comms.find(g.devs);
-        if (it == g_comms.end()) {
-            std::vector<ncclComm_t> cs((size_t)n);
-            const ncclResult_t e = g_rccl.CommInitAll(cs.data(), n, g.devs.data());
-            if (e != ncclSuccess) why = std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(e);
-            else it = g_comms.emplace(g.devs, std::move(cs)).first;
-        }
-        if (why.empty()) g.comms = &it->second;
-    }
-    if (!why.empty()) {
-        if (want_rccl) return fail(RTMI_E_DEVICE, "multi-device gather: %s", why.c_str());
-        fprintf(stderr, "[rtmi] multi-device gather falls back to hipMemcpyPeerAsync: %s\n", why.c_str());
-        g_rccl_failed = true;
-        g.use_rccl = false;
-    }
-    return RTMI_OK;
-}
-
-// ONE gather of `words` 8-byte words per replica: recs[r] (on replica r's device, written on its context stream; with copies its ev_done is recorded
-// behind the writes) -> gathered[r] on replica 0's device.  recs[0] = gathered: replica 0's record is in place.
-int enqueue_gather(int n, rtmi_scene *const *scenes, const GatherPlan &g, const std::vector<char *> &recs, char *gathered, size_t words) {
-    rtmi_ctx *c0 = scenes[0]->ctx;
-    HIP_TRY(hipSetDevice(c0->device));
-    int rc = ensure_event(&c0->ev_g0);
-    if (!rc) rc = ensure_event(&c0->ev_g1);
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(c0->ev_g0, c0->stream));
-    if (g.use_rccl) {
-        ncclResult_t e = g_rccl.GroupStart();
-        for (int r = 0; r < n && e == ncclSuccess; ++r) {
-            (void)hipSetDevice(scenes[r]->ctx->device);
-            e = g_rccl.Gather(recs[(size_t)r], r == 0 ? gathered : nullptr, words, ncclUint64, 0, (*g.comms)[(size_t)r], scenes[r]->ctx->stream);
-        }
-        const ncclResult_t e2 = g_rccl.GroupEnd();
-        (void)hipSetDevice(c0->device);
-        if (e == ncclSuccess) e = e2;
-        if (e != ncclSuccess) { // this communicator set is not trusted again: later calls gather by copies
-            const int code = fail(RTMI_E_DEVICE, "ncclGather: %s", g_rccl.GetErrorString(e));
-            rccl_give_up(g.devs);
-            return code;
-        }
-        c0->last_gather_path = RTMI_GATHER_RCCL;
-    } else {
-        bool peer = false;
-        for (int r = 1; r < n; ++r) {
-            rtmi_ctx *cr = scenes[r]->ctx;
-            char *dst = gathered + (size_t)r * words * 8;
-            HIP_TRY(hipStreamWaitEvent(c0->stream, cr->ev_done, 0));
-            if (cr->device == c0->device) HIP_TRY(hipMemcpyAsync(dst, recs[(size_t)r], words * 8, hipMemcpyDeviceToDevice, c0->stream));
-            else { peer = true; HIP_TRY(hipMemcpyPeerAsync(dst, c0->device, recs[(size_t)r], cr->device, words * 8, c0->stream)); }
-            // replica r's NEXT render into its record waits for this copy (its stream is not otherwise ordered with replica 0's)
-            if (cr->ev_consumed && cr->ev_consumed_device != c0->device) { (void)hipSetDevice(cr->ev_consumed_device); (void)hipEventDestroy(cr->ev_consumed); cr->ev_consumed = nullptr; HIP_TRY(hipSetDevice(c0->device)); }
-            if (!cr->ev_consumed) { HIP_TRY(hipEventCreateWithFlags(&cr->ev_consumed, hipEventDisableTiming)); cr->ev_consumed_device = c0->device; }
-            HIP_TRY(hipEventRecord(cr->ev_consumed, c0->stream));
-            cr->consume_pending = true;
-        }
-        c0->last_gather_path = n == 1 ? RTMI_GATHER_NONE : (peer ? RTMI_GATHER_PEER_COPY : RTMI_GATHER_SAME_DEVICE);
-    }
-    HIP_TRY(hipEventRecord(c0->ev_g1, c0->stream));
-    c0->have_gather = true;
-    return RTMI_OK;
-}
-} // namespace
 
 RTMI_EXPORT int rtmi_render_multi_adaptive_device(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count,
                                                   int32_t retire, double eps, int32_t depth, uint64_t seed, int32_t precision, void *d_out_linear,
@@ -3295,8 +3202,7 @@ RTMI_EXPORT int rtmi_render_multi_adaptive_device(int32_t n, rtmi_scene *const *
             HIP_BAIL(hipStreamWaitEvent(cr->stream, cr->ev_consumed, 0));
             cr->consume_pending = false;
         }
-        if (precision == RTMI_F64) rc = dealt_launch<double>(scenes[r], keys[(size_t)r], s_first, s_count, retire, eps, reinterpret_cast<double *>(buf), per, buf + tile_words * 8, cr->stream);
-        else rc = dealt_launch<float>(scenes[r], keys[(size_t)r], s_first, s_count, retire, eps, reinterpret_cast<double *>(buf), per, buf + tile_words * 8, cr->stream);
+        rc = with_real(precision, [&](auto real) { return dealt_launch<decltype(real)>(scenes[r], keys[(size_t)r], s_first, s_count, retire, eps, reinterpret_cast<double *>(buf), per, buf + tile_words * 8, cr->stream); });
         // replica 0 refused before it touched its frame (the test hook, an allocation): nothing has changed anywhere
         if (rc) { launched = r + 1; return bail(rc, !(r == 0 && c0->prog.k == k_before0 && k_before0 > 0)); }
         launched = r + 1;
@@ -3339,23 +3245,13 @@ RTMI_EXPORT int rtmi_render_multi_adaptive(int32_t n, rtmi_scene *const *scenes,
     DeviceGuard guard;
     rtmi_ctx *c0 = scenes[0]->ctx;
     HIP_TRY(hipSetDevice(c0->device));
-    const size_t npx = (size_t)nx * (size_t)ny;
-    int rc = c0->scratch_lin.ensure(npx * 4 * sizeof(double) + npx * sizeof(int) + 2 * sizeof(u64) + npx * 3 + 64);
+    HostStage stage;
+    int rc = stage.ensure(c0, (size_t)nx * (size_t)ny, true, true, true);
     if (rc) return rc;
-    char *base = reinterpret_cast<char *>(c0->scratch_lin.p);
-    double *d_lin = reinterpret_cast<double *>(base), *d_err = reinterpret_cast<double *>(base + npx * 3 * sizeof(double));
-    u64 *d_cnt = reinterpret_cast<u64 *>(base + npx * 4 * sizeof(double));
-    int *d_smp = reinterpret_cast<int *>(base + npx * 4 * sizeof(double) + 2 * sizeof(u64));
-    unsigned char *d_q = reinterpret_cast<unsigned char *>(base + npx * 4 * sizeof(double) + 2 * sizeof(u64) + npx * sizeof(int));
-    rc = rtmi_render_multi_adaptive_device(n, scenes, nx, ny, s_first, s_count, retire, eps, depth, seed, precision, d_lin, d_q, d_err, d_smp, d_cnt);
+    rc = rtmi_render_multi_adaptive_device(n, scenes, nx, ny, s_first, s_count, retire, eps, depth, seed, precision, stage.lin, stage.q, stage.err, stage.smp, stage.cnt);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c0->device)); // (every replica's stream is synchronised)
-    hipError_t e = hipSuccess;
-    if (out_linear) e = hipMemcpy(out_linear, d_lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_rgb8) e = hipMemcpy(out_rgb8, d_q, npx * 3, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_stderr) e = hipMemcpy(out_stderr, d_err, npx * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_samples) e = hipMemcpy(out_samples, d_smp, npx * sizeof(int), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_counters) e = hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost);
+    const hipError_t e = stage.copy_back(out_linear, out_rgb8, out_stderr, out_samples, out_counters, stage.cnt);
     if (e != hipSuccess) {
         for (int r = 0; r < n; ++r) scenes[r]->ctx->prog.k = 0;
         return fail(RTMI_E_DEVICE, "multi-device adaptive render: %s", hipGetErrorString(e));
@@ -3510,8 +3406,7 @@ RTMI_EXPORT int rtmi_probe_hit(rtmi_scene *s, int32_t precision, int32_t n, cons
     auto run = [&](auto kern, size_t lds, int ppt, int npt) {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out);
     };
-    if (precision == RTMI_F64) with_probe_kernel<ProbeHit, double>(s, run);
-    else with_probe_kernel<ProbeHit, float>(s, run);
+    with_real(precision, [&](auto r) { with_probe_kernel<ProbeHit, decltype(r)>(s, run); });
     PROBE_EPILOGUE()
     HIP_TRY(hipMemcpy(out, d_out, (size_t)n * 11 * sizeof(double), hipMemcpyDeviceToHost));
     return RTMI_OK;
@@ -3535,8 +3430,7 @@ RTMI_EXPORT int rtmi_probe_paths(rtmi_scene *s, int32_t precision, int32_t n, co
     auto run = [&](auto kern, size_t lds, int ppt, int npt) {
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog);
     };
-    if (precision == RTMI_F64) with_probe_kernel<ProbePaths, double>(s, run);
-    else with_probe_kernel<ProbePaths, float>(s, run);
+    with_real(precision, [&](auto r) { with_probe_kernel<ProbePaths, decltype(r)>(s, run); });
     PROBE_EPILOGUE()
     HIP_TRY(hipMemcpy(out_rgb, d_rgb, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (out_nseg) HIP_TRY(hipMemcpy(out_nseg, d_nseg, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost));
@@ -3552,8 +3446,7 @@ RTMI_EXPORT int rtmi_probe_camera(rtmi_scene *s, int32_t precision, int32_t n, c
     u64 *d_keys = (u64 *)tmp.up(keys, (size_t)n * sizeof(u64));
     double *d_out = (double *)tmp.alloc((size_t)n * 8 * sizeof(double));
     if (!d_uv || !d_keys || !d_out) return fail(RTMI_E_NOMEM, "probe buffers");
-    if (precision == RTMI_F64) hipLaunchKernelGGL((probe_camera_kernel<double>), dim3(grid), dim3(kBlock), 0, c->stream, s->d_dev, n, d_uv, d_keys, d_out);
-    else hipLaunchKernelGGL((probe_camera_kernel<float>), dim3(grid), dim3(kBlock), 0, c->stream, s->d_dev, n, d_uv, d_keys, d_out);
+    with_real(precision, [&](auto r) { hipLaunchKernelGGL((probe_camera_kernel<decltype(r)>), dim3(grid), dim3(kBlock), 0, c->stream, s->d_dev, n, d_uv, d_keys, d_out); });
     PROBE_EPILOGUE()
     HIP_TRY(hipMemcpy(out, d_out, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost));
     return RTMI_OK;
@@ -3606,8 +3499,7 @@ RTMI_EXPORT int rtmi_probe_rng(rtmi_ctx *c, int32_t precision, uint64_t key, uin
     double *d_real = (double *)tmp.alloc((size_t)n * sizeof(double));
     if (!d_bits || !d_real) return fail(RTMI_E_NOMEM, "probe buffers");
     const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    if (precision == RTMI_F64) hipLaunchKernelGGL((probe_rng_kernel<double>), dim3(grid), dim3(kBlock), 0, c->stream, (u64)key, (u64)d0, n, d_bits, d_real);
-    else hipLaunchKernelGGL((probe_rng_kernel<float>), dim3(grid), dim3(kBlock), 0, c->stream, (u64)key, (u64)d0, n, d_bits, d_real);
+    with_real(precision, [&](auto r) { hipLaunchKernelGGL((probe_rng_kernel<decltype(r)>), dim3(grid), dim3(kBlock), 0, c->stream, (u64)key, (u64)d0, n, d_bits, d_real); });
     PROBE_EPILOGUE()
     HIP_TRY(hipMemcpy(out_bits, d_bits, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_real, d_real, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
@@ -3722,8 +3614,7 @@ RTMI_EXPORT int rtmi_render_features_device(rtmi_scene *s, int32_t nx, int32_t n
         d_out_counters = c->feat_cnt.p;
     }
     const int whole[4] = {0, 0, nx, ny};
-    if (precision == RTMI_F64) return render_features_impl<double>(s, nx, ny, na, seed, whole, reinterpret_cast<double *>(d_out_features), reinterpret_cast<u64 *>(d_out_counters), st);
-    return render_features_impl<float>(s, nx, ny, na, seed, whole, reinterpret_cast<double *>(d_out_features), reinterpret_cast<u64 *>(d_out_counters), st);
+    return with_real(precision, [&](auto r) { return render_features_impl<decltype(r)>(s, nx, ny, na, seed, whole, reinterpret_cast<double *>(d_out_features), reinterpret_cast<u64 *>(d_out_counters), st); });
 }
 
 RTMI_EXPORT int rtmi_render_features(rtmi_scene *s, int32_t nx, int32_t ny, int32_t na, uint64_t seed, int32_t precision,
@@ -3741,8 +3632,7 @@ RTMI_EXPORT int rtmi_render_features(rtmi_scene *s, int32_t nx, int32_t ny, int3
     u64 *d_cnt = reinterpret_cast<u64 *>(d_out + npx * 8);
     const int rg[4] = {x0, y0, x1, y1};
     hipStream_t st = c->stream;
-    if (precision == RTMI_F64) rc = render_features_impl<double>(s, nx, ny, na, seed, rg, d_out, d_cnt, st);
-    else rc = render_features_impl<float>(s, nx, ny, na, seed, rg, d_out, d_cnt, st);
+    rc = with_real(precision, [&](auto r) { return render_features_impl<decltype(r)>(s, nx, ny, na, seed, rg, d_out, d_cnt, st); });
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     HIP_TRY(hipMemcpy(out_features, d_out, npx * 8 * sizeof(double), hipMemcpyDeviceToHost));

@@ -298,7 +298,7 @@ def step_profiled_run():
         b.close()
 
 
-def step_kernels(out_dir, limit, child_step="profiled-run", sub="kernel_trace", keep=("adaptive_", "trace_kernel")):
+def step_kernels(out_dir, limit, child_step="profiled-run", sub="kernel_trace", keep=("adaptive_", "frame_", "trace_kernel")):
     d = os.path.join(out_dir, sub)
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "adaptive", "--output-format", "csv", "--", "timeout", "-k", "10", str(max(30, limit - 30)), sys.executable, os.path.abspath(__file__),
            "--child", child_step, "--out", out_dir]
@@ -353,7 +353,7 @@ def main():
             else:
                 subprocess.run([sys.executable, os.path.abspath(__file__), "--child", step, "--out", a.out], check=True, timeout=STEPS[step], cwd=ROOT)
                 if step == "denoised":  # the new kernel's line, from a profiled run of its own
-                    res = step_kernels(a.out, 300, "denoised-profiled-run", "kernel_trace_denoised", ("adaptive_", "denoise_", "trace_kernel"))
+                    res = step_kernels(a.out, 300, "denoised-profiled-run", "kernel_trace_denoised", ("adaptive_", "frame_", "denoise_", "trace_kernel"))
                     with open(os.path.join(a.out, "denoised_kernels.json"), "w") as f:
                         json.dump(res, f, indent=1)
                     print(json.dumps(res))

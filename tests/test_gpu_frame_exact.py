@@ -1,5 +1,5 @@
-"""The back half of a frame on the device, bit for bit: reduce_kernel, assemble_kernel, assemble_region_kernel, progressive_fold_kernel and
-progressive_resolve_kernel against references that are not the device.
+"""The back half of a frame on the device, bit for bit: reduce_kernel, assemble_kernel, assemble_region_kernel, frame_fold_kernel and
+frame_resolve_kernel against references that are not the device.
 
   * Scenes whose colours never touch libm (frame_reference.py) must equal oracle.render EXACTLY -- linear, rgb8, both counters -- through every
     path that folds or assembles: tree and flat scan, one sample pass and many, an unaligned region, tiles dealt over 1..8 ranks and assembled,
@@ -105,7 +105,7 @@ def _check_fold(o, name, nx, ny, ns, lin, what, region=None):
 
 
 def _check_stderr(err, smp, k, what, region=None):
-    """progressive_resolve_kernel's noise plane against the two-pass reference.
+    """frame_resolve_kernel's noise plane against the two-pass reference.
 
     The bound.  The device keeps Welford's M2 in double, the reference is two-pass; with S the exact sum of squared deviations of a channel's k
     samples, M the largest |sample| of the pixel, u = eps / 2:
@@ -346,7 +346,7 @@ def _light_colours(precision):
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
 def test_quantiser_behind_region_and_progressive_renders(request, ctx, precision):
-    """assemble_region_kernel and progressive_resolve_kernel have no entry of their own: a world that is one constant light of colour c has every
+    """assemble_region_kernel and frame_resolve_kernel have no entry of their own: a world that is one constant light of colour c has every
     sample equal to c, so the mean is (c + ... + c) * (1 / ns) in the frame's precision"""
     o = _oracle(request, precision)
     R = fr.REAL[precision]

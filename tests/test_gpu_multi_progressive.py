@@ -103,6 +103,37 @@ def test_progressive_equals_oracle_and_single_context(request, closing, name, pr
     assert md.progressive_samples() == 0 and md.adaptive_status() == (0, 0, 0)
 
 
+# ---- one-shot renders in between: the same gather, records and hand-off events on the same contexts --------------------------------------------
+@pytest.mark.parametrize("n", [2, 3])
+@pytest.mark.parametrize("name,precision", CASES[:2], ids=["%s-%s" % c for c in CASES[:2]])
+def test_one_shot_multi_renders_between_progressive_calls(closing, name, precision, n):
+    """rtmi_render_multi and rtmi_render_multi_adaptive share plan_gather / enqueue_gather, c->multi and the ev_consumed hand-off: a one-shot render
+    between two calls of a dealt progressive frame leaves the frame alone, and each is bit for bit what one context computes after the same calls."""
+    md, one = _multi(closing, name, [0] * n), _Single(name)
+    closing(one)
+
+    def one_shot():
+        lin, q, cnt = md.render(NX, NY, 4, precision=precision, **KW)
+        slin, sq, scnt = one.ds.render(NX, NY, 4, precision=precision, **KW)
+        for a, b, label in ((lin, slin, "linear"), (q, sq, "rgb8"), (cnt, scnt, "counters")):
+            assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), ("one-shot", n, label)
+        assert md.last_gather_path() == "same-device"
+
+    def progressive(s_first, s_count):
+        lin, q, err, smp, cnt = md.render_multi_adaptive(NX, NY, s_first, s_count, 0, precision=precision, **KW)
+        slin, sq, serr, scnt = one.ds.render_progressive(NX, NY, s_first, s_count, precision=precision, **KW)
+        k = s_first + s_count
+        _eq((lin, q, err), (slin, sq, serr), "n=%d k=%d vs rtmi_render_progressive" % (n, k))
+        assert np.array_equal(cnt, scnt) and smp.dtype == np.int32 and (smp == k).all()
+        assert md.progressive_samples() == one.ctx.progressive_samples() == k
+        assert md.last_gather_path() == "same-device"
+
+    one_shot()
+    progressive(0, 2)
+    one_shot()
+    progressive(2, 3)  # a one-shot render does not touch the frame: the continuation is accepted and right
+
+
 # ---- retire = 1: the adaptive frame ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [2, 3])
 @pytest.mark.parametrize("name,precision", CASES, ids=["%s-%s" % c for c in CASES])
