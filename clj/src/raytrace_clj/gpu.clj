@@ -465,6 +465,41 @@
       {:linear out :rgb8 rgb :stderr err}
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn reproject
+  "Temporal accumulation (rtmi_reproject): blend the previous view's result into the current frame where both see the same surface.
+  `prev` = {:cam-kind :cam :linear :weight :stderr :features} -- the camera the history was seen with (:cam-kind / :cam of flatten-scene),
+  its colour [ny][nx][3], the samples accumulated behind every pixel [ny][nx] (doubles), its standard error [ny][nx] and the previous view's
+  features [ny][nx][8]; `cur` = {:cam-kind :cam :linear :stderr :features} of the current frame, `cur-weight` its samples per pixel.
+  :max-history caps the weight a history may count for (Double/POSITIVE_INFINITY = no cap); a sigma of 0 switches its test off.
+  Returns {:linear :rgb8 :weight :stderr :counters [pixels, pixels that took history]}: feed :linear, :weight and :stderr back as the next
+  call's `prev`, with the current features and camera.  (A frame without a noise estimate: pass NULL for both stderr planes and for
+  out_stderr to rtmi_reproject.)"
+  [nx ny prev cur cur-weight & {:keys [max-history sigma-d sigma-n sigma-a device]
+                                :or {max-history 8.0 sigma-d 0.1 sigma-n 0.0 sigma-a 0.0 device 0}}]
+  (let [ctx  (PointerByReference.)
+        npx  (* nx ny)
+        pcam (double-array (:cam prev))
+        ccam (double-array (:cam cur))
+        plin (double-array (:linear prev))
+        pw   (double-array (:weight prev))
+        pse  (double-array (:stderr prev))
+        pft  (double-array (:features prev))
+        clin (double-array (:linear cur))
+        cse  (double-array (:stderr cur))
+        cft  (double-array (:features cur))
+        out  (double-array (* 3 npx))
+        rgb  (byte-array (* 3 npx))
+        wgt  (double-array npx)
+        err  (double-array npx)
+        cnt  (long-array 2)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (check (call-int "rtmi_reproject" (.getValue ctx) (int nx) (int ny) (int (:cam-kind prev)) pcam (int (:cam-kind cur)) ccam
+                       plin pw pse pft clin cse cft (double cur-weight) (double max-history) (double sigma-d) (double sigma-n)
+                       (double sigma-a) out rgb wgt err cnt))
+      {:linear out :rgb8 rgb :weight wgt :stderr err :counters (vec cnt)}
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn adaptive-retire
   "Retire the active tiles of context `ctx`'s progressive frame whose pixels all pass noise <= eps (rtmi_adaptive_retire; a NaN fails): `noise`
   holds [ny][nx] doubles of the whole frame, row 0 = top -- :stderr of `denoise` as it is.  Adds no samples.  Returns the number of tiles this

@@ -397,6 +397,66 @@ int rtmi_denoise_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, const void *d_lin
                         int32_t iterations, double sigma_c, double sigma_n, double sigma_a, double sigma_d,
                         void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *stream);
 
+/* ---- temporal accumulation: the previous frame reprojected into a moved camera and blended with the current one ----
+ * A pure image operation in FP64 (-ffp-contract=off; sqrt, floor and / are the only functions, all correctly rounded) plus two cameras: it reads no
+ * scene, no progressive frame and no workspace of another call, so it serves one-shot, progressive, denoised and multi-device frames alike.  All
+ * planes are [ny][nx] row-major, row 0 = top.
+ *   prev_cam_kind, prev_cam[24] / cur_cam_kind, cur_cam[24]   the cameras of the history and of the current frame (rtmi_scene_create's layout).  For
+ *                             both kinds only origin o, lleft l, horiz h and vert v (cam[0..11]) are read: a thin lens is reprojected through its lens
+ *                             centre; aperture, u, v, w and the shutter are ignored.  Below the previous camera's are primed.
+ *   prev_linear[ny][nx][3]    the history's colour;   prev_weight[ny][nx]  the samples accumulated behind it, as doubles;
+ *   prev_stderr[ny][nx]       its standard error, may be NULL;   prev_features[ny][nx][8]  rtmi_render_features' result of the previous view;
+ *   cur_linear, cur_stderr (may be NULL), cur_features   the same of the current frame;   cur_weight  the samples of the current frame (ns), one
+ *                             scalar for all pixels (a frame with per-pixel sample counts is not served);
+ *   max_history               cap of the history's weight, may be +inf;   sigma_d, sigma_n, sigma_a  tolerances of the depth, normal and albedo tests
+ *                             of a tap; 0 switches the test off (decided per launch, not by arithmetic).
+ * Once per call, on the host:  a = l' - o';  n = h' x v' = (h'y v'z - h'z v'y, h'z v'x - h'x v'z, h'x v'y - h'y v'x);  nn = (nx nx + ny ny) + nz nz;
+ * A = (ax nx + ay ny) + az nz.  Every dot product here and below is folded from the left like these two, every cross product is written like n, and
+ * every operation is one IEEE double operation as written.
+ * Per pixel, column i, row y, j = ny-1-y, f = cur_features[y][i], c = cur_linear[y][i]:
+ *   1. world point:   u = (i + 0.5) / nx;  v = (j + 0.5) / ny;  d = ((l + u h) + v v) - o per component;  L = sqrt(d . d);  s = f[6] / L;
+ *                     P = o + s d per component.
+ *   2. into the previous camera:   q = P - o';  D = q . n;  t = A / D;  reject unless t > 0 (a NaN rejects);  X = t q - a per component;
+ *                     u' = ((X x v') . n) / nn;  v' = ((h' x X) . n) / nn;  fx = u' nx - 0.5;  fy = (ny - 1) - (v' ny - 0.5);
+ *                     reject unless -1 < fx < nx and -1 < fy < ny;  dist = sqrt(q . q).
+ *   3. taps:          x0 = floor(fx), y0 = floor(fy), ax = fx - x0, ay = fy - y0; four taps in the order (ty, tx) = (0,0), (0,1), (1,0), (1,1) at
+ *                     pixel g = (x0 + tx, y0 + ty) of the history, weight b = (tx ? ax : 1 - ax) * (ty ? ay : 1 - ay).  A tap is ACCEPTED iff it
+ *                     lies inside the image; b > 0; prev_features[g][7] == 1; prev_weight[g] is finite and > 0; the three values of prev_linear[g]
+ *                     are finite; prev_stderr[g] (if prev_stderr is given) is not NaN;
+ *                       if sigma_d > 0:  dq = prev_features[g][6], e = dq - dist, m = dq > dist ? dq : dist, (e e) <= (sigma_d sigma_d) (m m);
+ *                       if sigma_n > 0:  e = f[3..5] - prev_features[g][3..5] per component, (e . e) <= sigma_n sigma_n;
+ *                       if sigma_a > 0:  the same over channels 0..2 with sigma_a
+ *                     (each comparison as written: a NaN fails).  Accepted taps fold from the left, starting from 0:
+ *                       W = W + b;  S_ch = S_ch + b prev_linear[g][ch];  N = N + b prev_weight[g];  T = T + b (prev_stderr[g] prev_stderr[g]).
+ *   4. the pixel TAKES HISTORY iff f[7] == 1, its own three colour values c are finite, it was not rejected in 2 and W != 0.
+ *      It does not:   out_linear = c and out_stderr = cur_stderr, bit for bit;  out_weight = cur_weight.
+ *      It does:       c_h = S / W per channel;  n_h = N / W, then n_h = max_history if n_h > max_history;  V_h = T / W;  w = n_h + cur_weight;
+ *                     out_linear = (n_h c_h + cur_weight c) / w per channel;  out_weight = w;
+ *                     V = ((n_h n_h) V_h + (cur_weight cur_weight) (cur_stderr cur_stderr)) / (w w);  out_stderr = sqrt(V)
+ *                     (a one-sample frame has stderr +inf and gives +inf; both weights are positive, so 0 * inf does not occur).
+ * Outputs, each may be NULL: out_linear [ny][nx][3]; out_rgb8 = rtmi_render's quantiser of it; out_weight [ny][nx]; out_stderr [ny][nx], written only
+ * when BOTH stderr inputs are given (else passing it is RTMI_E_ARG); out_counters = {pixels, pixels that took history}.
+ * The history is gathered from neighbours: no output may be the same pointer as a prev_* input.  The cur_* inputs are read pointwise: outputs may
+ * alias them.  The limits are those of the inputs: depth is a mean over jittered feature samples, so pixels on a silhouette are approximate; shading
+ * that depends on the view (metal, glass) and anything that moves is held back by max_history alone; pixels whose coverage is not 1 never take history.
+ * Errors, reported before anything is launched and before the handle is examined (they need no device): nx or ny <= 0; a NULL camera; NULL
+ * prev_linear, prev_weight, prev_features, cur_linear or cur_features; cur_weight not finite or <= 0; max_history NaN or <= 0; a negative or NaN sigma;
+ * out_stderr without both stderr inputs; an output equal to a prev_* input: RTMI_E_ARG.  A camera kind other than RTMI_CAM_PINHOLE /
+ * RTMI_CAM_THINLENS: RTMI_E_UNSUPPORTED.  Then a bad handle: RTMI_E_STATE. */
+/* host buffers */
+int rtmi_reproject(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t prev_cam_kind, const double *prev_cam, int32_t cur_cam_kind, const double *cur_cam,
+                   const double *prev_linear, const double *prev_weight, const double *prev_stderr, const double *prev_features,
+                   const double *cur_linear, const double *cur_stderr, const double *cur_features, double cur_weight,
+                   double max_history, double sigma_d, double sigma_n, double sigma_a,
+                   double *out_linear, uint8_t *out_rgb8, double *out_weight, double *out_stderr, uint64_t *out_counters);
+/* device buffers, launched on `stream` with rtmi_render_device's stream semantics; asynchronous.  The two cameras are HOST arrays: they and the
+ * constants computed from them travel as kernel arguments. */
+int rtmi_reproject_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t prev_cam_kind, const double *prev_cam, int32_t cur_cam_kind, const double *cur_cam,
+                          const void *d_prev_linear, const void *d_prev_weight, const void *d_prev_stderr, const void *d_prev_features,
+                          const void *d_cur_linear, const void *d_cur_stderr, const void *d_cur_features, double cur_weight,
+                          double max_history, double sigma_d, double sigma_n, double sigma_a,
+                          void *d_out_linear, void *d_out_rgb8, void *d_out_weight, void *d_out_stderr, void *d_out_counters, void *stream);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

@@ -32,6 +32,7 @@ SYMBOLS = [
     "rtmi_adaptive_retire", "rtmi_adaptive_retire_device",
     "rtmi_render_adaptive_tiles_device", "rtmi_assemble_progressive_device", "rtmi_render_multi_adaptive", "rtmi_render_multi_adaptive_device",
     "rtmi_scene_set_camera", "rtmi_scene_set_camera_stream", "rtmi_scene_camera",
+    "rtmi_reproject", "rtmi_reproject_device",
 ]
 
 F64, F32 = 0, 1
@@ -131,6 +132,8 @@ def lib():
     L.rtmi_scene_set_camera.argtypes = [vp, i32, vp, C.POINTER(i32)]
     L.rtmi_scene_set_camera_stream.argtypes = [vp, i32, vp, vp]
     L.rtmi_scene_camera.argtypes = [vp, C.POINTER(i32), vp, C.POINTER(dbl), C.POINTER(dbl)]
+    L.rtmi_reproject.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 5
+    L.rtmi_reproject_device.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 6
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

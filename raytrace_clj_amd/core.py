@@ -36,6 +36,12 @@ DENOISE_SIGMA_A = 0.2
 DENOISE_SIGMA_D = 0.2
 FEATURE_SAMPLES = 4
 
+# temporal accumulation's defaults: chosen by a grid over the Cornell box and the small cover scene at 4 spp per view
+REPROJECT_MAX_HISTORY = 8.0
+REPROJECT_SIGMA_D = 0.1
+REPROJECT_SIGMA_N = 0.0
+REPROJECT_SIGMA_A = 0.0
+
 _PRECISION = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 
 
@@ -155,6 +161,50 @@ class Context:
                                              float(sigma_n), float(sigma_a), float(sigma_d), ptr(out_linear), ptr(out_rgb8), ptr(out_stderr),
                                              ptr(stream)))
 
+    # ---- temporal accumulation: the previous frame reprojected into a moved camera (rtmi_reproject*) -------------------------------------
+    def reproject(self, prev_camera, cur_camera, prev_linear, prev_weight, prev_stderr, prev_features, cur_linear, cur_stderr, cur_features,
+                  cur_weight, max_history=REPROJECT_MAX_HISTORY, sigma_d=REPROJECT_SIGMA_D, sigma_n=REPROJECT_SIGMA_N, sigma_a=REPROJECT_SIGMA_A):
+        """Blend a history (colour [h,w,3], accumulated samples [h,w], standard error [h,w] or None, the features [h,w,8] and the camera it was
+        seen with) into the current frame (colour, standard error or None, features, camera, its samples cur_weight): every pixel whose world
+        point is found in the history -- same surface by depth / normal / albedo within the sigmas, 0 = test off -- becomes the weighted mean of
+        both, the history's weight capped at max_history -> (linear, rgb8, weight, stderr or None, counters {pixels, pixels that took history}).
+        Cameras: Camera records or (cam_kind, cam24) pairs."""
+        (pk, pc), (ck, cc) = _camera_pair(prev_camera), _camera_pair(cur_camera)
+        cl = np.ascontiguousarray(cur_linear, np.float64)
+        if cl.ndim != 3 or cl.shape[2] != 3:
+            raise ValueError("cur_linear must be [h, w, 3]")
+        h, w = cl.shape[:2]
+        shapes = {"prev_linear": (h, w, 3), "prev_weight": (h, w), "prev_stderr": (h, w), "prev_features": (h, w, _ffi.FEATURES),
+                  "cur_stderr": (h, w), "cur_features": (h, w, _ffi.FEATURES)}
+        given = {"prev_linear": prev_linear, "prev_weight": prev_weight, "prev_stderr": prev_stderr, "prev_features": prev_features,
+                 "cur_stderr": cur_stderr, "cur_features": cur_features}
+        a = {}
+        for name, v in given.items():
+            a[name] = None if v is None else np.ascontiguousarray(v, np.float64)
+            if a[name] is not None and a[name].shape != shapes[name]:
+                raise ValueError("%s must be %s" % (name, list(shapes[name])))
+        both = a["prev_stderr"] is not None and a["cur_stderr"] is not None
+        out, q, wt = np.zeros_like(cl), np.zeros(cl.shape, np.uint8), np.zeros((h, w), np.float64)
+        err = np.zeros((h, w), np.float64) if both else None
+        cnt = np.zeros(2, np.uint64)
+        check(_ffi.lib().rtmi_reproject(self.handle, w, h, pk, ptr(pc), ck, ptr(cc), ptr(a["prev_linear"]), ptr(a["prev_weight"]),
+                                        ptr(a["prev_stderr"]), ptr(a["prev_features"]), ptr(cl), ptr(a["cur_stderr"]), ptr(a["cur_features"]),
+                                        float(cur_weight), float(max_history), float(sigma_d), float(sigma_n), float(sigma_a),
+                                        ptr(out), ptr(q), ptr(wt), ptr(err), ptr(cnt)))
+        return out, q, wt, err, cnt
+
+    def reproject_device(self, nx, ny, prev_camera, cur_camera, prev_linear, prev_weight, prev_stderr, prev_features, cur_linear, cur_stderr,
+                         cur_features, cur_weight, out_linear=None, out_rgb8=None, out_weight=None, out_stderr=None, out_counters=None,
+                         max_history=REPROJECT_MAX_HISTORY, sigma_d=REPROJECT_SIGMA_D, sigma_n=REPROJECT_SIGMA_N, sigma_a=REPROJECT_SIGMA_A,
+                         stream=None):
+        """reproject on HBM-resident buffers (torch tensors or raw device pointers), asynchronous, render_device's stream semantics; the cameras
+        stay host values.  Outputs may alias the cur_* buffers, never the prev_* ones."""
+        (pk, pc), (ck, cc) = _camera_pair(prev_camera), _camera_pair(cur_camera)
+        check(_ffi.lib().rtmi_reproject_device(self.handle, nx, ny, pk, ptr(pc), ck, ptr(cc), ptr(prev_linear), ptr(prev_weight), ptr(prev_stderr),
+                                               ptr(prev_features), ptr(cur_linear), ptr(cur_stderr), ptr(cur_features), float(cur_weight),
+                                               float(max_history), float(sigma_d), float(sigma_n), float(sigma_a), ptr(out_linear), ptr(out_rgb8),
+                                               ptr(out_weight), ptr(out_stderr), ptr(out_counters), ptr(stream)))
+
     def last_traversal_counters(self):
         """(AABB slab tests, exact primitive tests) of the last render; needs set_option("count_traversal", 1) before it
         (metrics.clj:10 aabb.intersection.total, for the device's own tree)"""
@@ -166,6 +216,15 @@ class Context:
         if self.handle:
             _ffi.lib().rtmi_shutdown(self.handle)
             self.handle = None
+
+
+def _camera_pair(camera):
+    """a Camera record or a (cam_kind, cam24) pair -> (int kind, float64 [24])"""
+    kind, c = camera if isinstance(camera, tuple) else fl.flatten_camera(camera)
+    c = np.ascontiguousarray(c, np.float64)
+    if c.shape != (24,):
+        raise ValueError("cam must hold 24 doubles")
+    return int(kind), c
 
 
 _default_ctx = None
@@ -475,6 +534,96 @@ class DeviceScene:
         return out
 
 
+class TemporalAccumulator:
+    """Frames of a moving camera that build on each other: every step renders ns samples of the new view and blends the previous result into it
+    where the previous view saw the same surface (Context.reproject_device).  The history -- colour, accumulated samples, standard error, the
+    features and the camera of the last view -- stays in HBM (torch tensors on the scene's device).
+    step(camera) queues, on one stream (stream=: a hipStream_t handle or torch stream; default the context's own) and with ONE synchronisation at
+    its end: the stream form of set_camera,
+    render_progressive_device(s_first = 0, s_count = ns), render_features_device(na), reproject_device and, with denoise= (True for the library's
+    defaults or a dict of Context.denoise_device's iterations / sigma_* arguments), denoise_device of the OUTPUT with its standard error and the
+    new features; the history is never filtered.  Step k renders with seed + k: with one seed a still camera would add the same samples again.
+    The first step, reset() and a step with another nx, ny or precision start without history.  The context's progressive frame is used.
+    Limits: depth is the mean over jittered feature samples, so silhouette pixels are approximate; shading that depends on the view (metal, glass)
+    and anything that moves is held back by max_history alone; pixels whose coverage is not 1 never take history."""
+
+    def __init__(self, scene, nx, ny, ns, na=FEATURE_SAMPLES, max_history=REPROJECT_MAX_HISTORY, sigma_d=REPROJECT_SIGMA_D,
+                 sigma_n=REPROJECT_SIGMA_N, sigma_a=REPROJECT_SIGMA_A, denoise=None, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", stream=None):
+        if nx <= 0 or ny <= 0 or ns <= 0 or na <= 0:
+            raise ValueError("nx, ny, ns and na must be > 0")
+        self.scene, self.ns, self.na = scene, int(ns), int(na)
+        self.max_history, self.sigma_d, self.sigma_n, self.sigma_a = float(max_history), float(sigma_d), float(sigma_n), float(sigma_a)
+        self.denoise = None if denoise is None or denoise is False else ({} if denoise is True else dict(denoise))
+        self.depth, self.seed = depth, int(seed)
+        self.stream = 0 if stream is None else int(getattr(stream, "cuda_stream", stream))  # 0: the context's own stream
+        self.nx = self.ny = self.precision = None
+        self._shape(int(nx), int(ny), precision)
+
+    def _shape(self, nx, ny, precision):
+        import torch
+        dev = torch.device("cuda", self.scene.ctx.device)
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.nx, self.ny, self.precision = nx, ny, precision
+        # two sets of history planes (a step reads one and writes the other), the current frame, the 8-bit frames, the filtered output
+        self._lin = [torch.empty((ny, nx, 3), **f64) for _ in range(2)]
+        self._w = [torch.empty((ny, nx), **f64) for _ in range(2)]
+        self._se = [torch.empty((ny, nx), **f64) for _ in range(2)]
+        self._ft = [torch.empty((ny, nx, _ffi.FEATURES), **f64) for _ in range(2)]
+        self._cur_lin, self._cur_se = torch.empty((ny, nx, 3), **f64), torch.empty((ny, nx), **f64)
+        self._raw_q, self._q = (torch.empty((ny, nx, 3), dtype=torch.uint8, device=dev) for _ in range(2))
+        self._cnt = torch.zeros(4, dtype=torch.int64, device=dev)  # {pixels, pixels with history}, {rays, pixels} of the render
+        if self.denoise is not None:
+            self._dn = (torch.empty((ny, nx, 3), **f64), torch.empty((ny, nx, 3), dtype=torch.uint8, device=dev), torch.empty((ny, nx), **f64))
+        self.reset()
+
+    def reset(self):
+        """forget the history: the next step returns its own frame (the seed sequence goes on)"""
+        self._cam, self._cur = None, 0
+        self.steps = getattr(self, "steps", 0)
+        self.raw_rgb8 = self.accumulated = None
+
+    def step(self, camera, nx=None, ny=None, precision=None):
+        """-> (linear [ny,nx,3], rgb8, stderr [ny,nx], weight [ny,nx] = samples behind every pixel, share of the pixels that took history): device
+        tensors owned by the accumulator -- rgb8 is overwritten by the next step, the others by the one after it -- filtered if denoise= was
+        given (then .accumulated holds the unfiltered four).  .raw_rgb8 is the 8-bit frame of this view's ns samples alone, .rays its
+        {total-rays, total-pixels}."""
+        import torch
+        nx, ny, precision = nx or self.nx, ny or self.ny, precision or self.precision
+        if (nx, ny, precision) != (self.nx, self.ny, self.precision):
+            self._shape(int(nx), int(ny), precision)
+        ds, ctx, dev = self.scene, self.scene.ctx, torch.device("cuda", self.scene.ctx.device)
+        cam_pair = _camera_pair(camera)
+        old, new = self._cur, 1 - self._cur
+        first = self._cam is None
+        if first:
+            self._w[new].fill_(float(self.ns))
+        torch.cuda.synchronize(dev)  # (the allocator or the fill ran on torch's stream; nothing of torch's is queued after this)
+        seed = self.seed + self.steps
+        lin, se = (self._lin[new], self._se[new]) if first else (self._cur_lin, self._cur_se)
+        st = self.stream or None
+        ds.set_camera(cam_pair, stream=self.stream)
+        ds.render_progressive_device(nx, ny, 0, self.ns, lin, self._raw_q, se, self._cnt[2:], self.depth, seed, precision, st)
+        ds.render_features_device(nx, ny, self.na, self._ft[new], None, seed, precision, st)
+        if not first:
+            ctx.reproject_device(nx, ny, self._cam, cam_pair, self._lin[old], self._w[old], self._se[old], self._ft[old], lin, se, self._ft[new],
+                                 float(self.ns), self._lin[new], self._q, self._w[new], self._se[new], self._cnt[:2], self.max_history,
+                                 self.sigma_d, self.sigma_n, self.sigma_a, st)
+        q = self._raw_q if first else self._q
+        self.accumulated = (self._lin[new], q, self._se[new], self._w[new])
+        out = self.accumulated
+        if self.denoise is not None:
+            ctx.denoise_device(nx, ny, self._lin[new], self._se[new], self._ft[new], self._dn[0], self._dn[1], self._dn[2], stream=st, **self.denoise)
+            out = (self._dn[0], self._dn[1], self._dn[2], self._w[new])
+        torch.cuda.synchronize(dev)
+        cnt = self._cnt.cpu().numpy().astype(np.uint64)
+        self.rays = cnt[2:]
+        self.raw_rgb8 = self._raw_q
+        self._cam, self._cur = cam_pair, new
+        self.steps += 1
+        share = 0.0 if first else float(cnt[1]) / float(cnt[0])
+        return out[0], out[1], out[2], out[3], share
+
+
 def probe_rng(key, d0, n, precision="f64", ctx=None):
     ctx = ctx or default_context()
     bits, real = np.zeros(n, np.uint64), np.zeros(n, np.float64)
@@ -767,11 +916,72 @@ def _orbit_flags(argv):
     return rest, views
 
 
+def _accumulate_flags(argv, orbit_views=None):
+    """-> (the other arguments, max_history): --accumulate [MAX_HISTORY] (a number right after it, or --accumulate=M, is its value; "inf" = no cap;
+    default REPROJECT_MAX_HISTORY), checked here, before any device work (None when absent).  It belongs to --orbit: the views of an orbit build
+    on each other."""
+    import math
+    import re
+    rest, cap = [], None
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        key, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") else (a, None)
+        i += 1
+        if key != "--accumulate":
+            rest.append(a)
+            continue
+        if val is None and i < len(argv) and re.fullmatch(r"[+-]?([0-9]+\.?[0-9]*([eE][+-]?[0-9]+)?|\.[0-9]+|inf|nan)", argv[i]):
+            val = argv[i]
+            i += 1
+        try:
+            cap = REPROJECT_MAX_HISTORY if val is None else float(val)
+        except ValueError:
+            raise SystemExit("--accumulate %r is not a number of samples" % val)
+        if math.isnan(cap) or cap <= 0:
+            raise SystemExit("--accumulate takes the cap of the history's weight in samples, > 0 or inf (got %r)" % val)
+    if cap is not None and orbit_views is None:
+        raise SystemExit("--accumulate belongs to --orbit")
+    return rest, cap
+
+
+def _accumulated_name(name):
+    """x_007.png -> x_007.acc.png: the accumulated frame is written next to the view's own"""
+    import os
+    root, ext = os.path.splitext(name)
+    return root + ".acc" + ext
+
+
 def _orbit_name(name, k):
     """x.png -> x_007.png: view k of an orbit"""
     import os
     root, ext = os.path.splitext(name)
     return "%s_%03d%s" % (root, k, ext)
+
+
+def _render_orbit_accumulated(sc, name, nx, ny, nr, views, dn_iterations, dn_samples, max_history, tstart):
+    """--orbit with --accumulate: the views through ONE TemporalAccumulator.  Writes name_000.ext ... (every view's own nr samples; view k is
+    rendered with seed RENDER_SEED + k), name_000.acc.ext ... (the accumulated frames) and, with --denoise, name_000.acc.denoised.ext ..."""
+    pivot = sc.get("lookat") if isinstance(sc, dict) else None
+    ds = DeviceScene(sc)
+    rays = pixels = 0
+    try:
+        dn = None if dn_iterations is None else {"iterations": dn_iterations}
+        acc = TemporalAccumulator(ds, nx, ny, nr, na=FEATURE_SAMPLES if dn_samples is None else dn_samples, max_history=max_history, denoise=dn)
+        for k, camera in enumerate(cam.orbit(sc["camera"], views, pivot)):
+            lin, rgb8, err, weight, share = acc.step(camera)
+            _show_progress(tstart, k + 1, views)
+            print("history on %.1f%% of the pixels, %.1f samples behind a pixel on average" % (100.0 * share, float(weight.mean())))
+            _save_image(_orbit_name(name, k), acc.raw_rgb8.cpu().numpy())
+            _save_image(_accumulated_name(_orbit_name(name, k)), acc.accumulated[1].cpu().numpy())
+            if dn is not None:
+                _save_image(_denoised_name(_accumulated_name(_orbit_name(name, k))), rgb8.cpu().numpy())
+            rays, pixels = rays + int(acc.rays[0]), pixels + int(acc.rays[1])
+    finally:
+        ds.ctx.progressive_release()
+        ds.close()
+    print("total-rays %d total-pixels %d" % (rays, pixels))  # metrics.clj:8-9, summed over the views
+    return 0
 
 
 def _render_orbit(sc, name, nx, ny, nr, views, dn_iterations, dn_samples, tstart):
@@ -851,10 +1061,15 @@ def main(argv=None):
     --denoise / --feature-samples are given, obeys --budget and does not combine with --adaptive or --noise.
     --orbit N renders N one-shot views of the scene, view k turned by k * 360 / N degrees about the vertical axis through the scene's look-at
     point, from ONE device scene whose camera moves between the frames (DeviceScene.set_camera); it writes name_000.ext, name_001.ext, ...,
-    works with --denoise (name_000.denoised.ext, ...) and does not combine with the progressive and adaptive modes."""
+    works with --denoise (name_000.denoised.ext, ...) and does not combine with the progressive and adaptive modes.
+    --accumulate [MAX_HISTORY] belongs to --orbit: the views build on each other (TemporalAccumulator: the previous view's result is reprojected
+    into the next camera and blended where both see the same surface; MAX_HISTORY caps the samples a history may count for, default 8, inf =
+    no cap).  View k is rendered with seed RENDER_SEED + k; it writes name_000.ext (the view's own samples), name_000.acc.ext (accumulated) and,
+    with --denoise, name_000.acc.denoised.ext."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
     argv, orbit_views = _orbit_flags(argv)
+    argv, accumulate = _accumulate_flags(argv, orbit_views)
     argv, adaptive_denoised = _adaptive_denoised_flags(argv)
     if adaptive_denoised is not None and not any(a.split("=", 1)[0] == "--denoise" for a in argv):
         argv.append("--denoise")  # implied, with the default passes; --feature-samples then belongs to it
@@ -871,6 +1086,8 @@ def main(argv=None):
         raise SystemExit("unknown scene %r; one of %s" % (which, ", ".join(sorted(SCENES))))
     tstart = time.time()
     sc = SCENES[which](scenes, nx, ny)
+    if accumulate is not None:
+        return _render_orbit_accumulated(sc, name, nx, ny, nr, orbit_views, dn_iterations, dn_samples, accumulate, tstart)
     if orbit_views is not None:
         return _render_orbit(sc, name, nx, ny, nr, orbit_views, dn_iterations, dn_samples, tstart)
     filtered = None

@@ -1224,6 +1224,118 @@ __global__ void __launch_bounds__(kBlock) denoise_store_kernel(const double *__r
     if (out_stderr) out_stderr[p] = se_copy ? se_copy[p] : ::sqrt(state[3 * n + p]);
 }
 
+// ---- temporal accumulation (rtmi_reproject*): the previous frame gathered through both cameras and blended with the current one -----------------------
+// One thread per pixel, lanes along x (denoise_pass_kernel's launch shape).  It reads the interleaved buffers as the callers hold them and writes every
+// output, the 8-bit frame included: one launch per call.  The cameras and the constants the host computes from the previous one are kernel arguments.
+struct ReprojectParams {
+    int nx, ny;
+    int use_d, use_n, use_a;              // launch-uniform: a test that is off is not evaluated and its values are not loaded
+    double co[3], cl[3], ch[3], cv[3];    // current camera: origin, lleft, horiz, vert
+    double po[3], ph[3], pv[3];           // previous camera: origin, horiz, vert
+    double a[3], n[3], nn, A;             // a = l' - o', n = h' x v', nn = n . n, A = a . n (rtmi.h)
+    double cur_weight, max_history, sd2, sn2, sa2; // s*2 = sigma squared
+    const double *prev_lin, *prev_w, *prev_se, *prev_feat;
+    const double *cur_lin, *cur_se, *cur_feat;    // (no __restrict__: the outputs may alias the current frame's buffers)
+    double *out_lin; unsigned char *out_q; double *out_w, *out_se;
+    u64 *counters;                        // [0] = pixels, [1] += pixels that took history; may be null
+};
+
+__global__ void __launch_bounds__(kBlock) reproject_kernel(ReprojectParams rp) {
+    const int x = (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = (int)(blockIdx.y * (kBlock / 64) + (threadIdx.x >> 6));
+    const bool inside = x < rp.nx && y < rp.ny;
+    bool took = false;
+    if (inside) {
+        const double big = __builtin_inf();
+        const size_t p = (size_t)y * (size_t)rp.nx + (size_t)x;
+        const double c0 = rp.cur_lin[3 * p], c1 = rp.cur_lin[3 * p + 1], c2 = rp.cur_lin[3 * p + 2];
+        const double se_c = rp.cur_se ? rp.cur_se[p] : 0.0;
+        const double *f = rp.cur_feat + 8 * p;
+        const double depth = f[6];
+        double n0 = 0, n1 = 0, n2 = 0, a0 = 0, a1 = 0, a2 = 0;
+        if (rp.use_n) { n0 = f[3]; n1 = f[4]; n2 = f[5]; }
+        if (rp.use_a) { a0 = f[0]; a1 = f[1]; a2 = f[2]; }
+        bool ok = f[7] == 1.0 && ::fabs(c0) < big && ::fabs(c1) < big && ::fabs(c2) < big;
+        // the world point and its place in the previous frame: every lane computes (a pixel that is not `ok` computes on whatever it holds and
+        // its result is not used), so that the loads of the four taps below do not wait behind a chain of branches
+        const double u = ((double)x + 0.5) / (double)rp.nx, v = ((double)(rp.ny - 1 - y) + 0.5) / (double)rp.ny;
+        const double d0 = ((rp.cl[0] + u * rp.ch[0]) + v * rp.cv[0]) - rp.co[0];
+        const double d1 = ((rp.cl[1] + u * rp.ch[1]) + v * rp.cv[1]) - rp.co[1];
+        const double d2 = ((rp.cl[2] + u * rp.ch[2]) + v * rp.cv[2]) - rp.co[2];
+        const double len = ::sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+        const double s = depth / len;
+        const double q0 = (rp.co[0] + s * d0) - rp.po[0], q1 = (rp.co[1] + s * d1) - rp.po[1], q2 = (rp.co[2] + s * d2) - rp.po[2];
+        const double t = rp.A / ((q0 * rp.n[0] + q1 * rp.n[1]) + q2 * rp.n[2]);
+        ok = ok && t > 0.0;
+        const double X0 = t * q0 - rp.a[0], X1 = t * q1 - rp.a[1], X2 = t * q2 - rp.a[2];
+        const double up = (((X1 * rp.pv[2] - X2 * rp.pv[1]) * rp.n[0] + (X2 * rp.pv[0] - X0 * rp.pv[2]) * rp.n[1]) +
+                           (X0 * rp.pv[1] - X1 * rp.pv[0]) * rp.n[2]) / rp.nn;
+        const double vp = (((rp.ph[1] * X2 - rp.ph[2] * X1) * rp.n[0] + (rp.ph[2] * X0 - rp.ph[0] * X2) * rp.n[1]) +
+                           (rp.ph[0] * X1 - rp.ph[1] * X0) * rp.n[2]) / rp.nn;
+        double fx = up * (double)rp.nx - 0.5, fy = (double)(rp.ny - 1) - (vp * (double)rp.ny - 0.5);
+        ok = ok && fx > -1.0 && fx < (double)rp.nx && fy > -1.0 && fy < (double)rp.ny; // (a NaN fails)
+        if (!ok) { fx = 0.0; fy = 0.0; }                                               // (the conversions below are in range)
+        const double dist = ::sqrt((q0 * q0 + q1 * q1) + q2 * q2);
+        const double flx = ::floor(fx), fly = ::floor(fy), ax = fx - flx, ay = fy - fly;
+        const int x0 = (int)flx, y0 = (int)fly;
+        double sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, sn = 0.0, st = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int tx = k & 1, ty = k >> 1, gx = x0 + tx, gy = y0 + ty;
+            bool acc = ok && gx >= 0 && gx < rp.nx && gy >= 0 && gy < rp.ny;
+            // a tap outside the image reads the nearest pixel inside (and is not accepted): every address below is in bounds for every lane
+            const int cx = gx < 0 ? 0 : (gx >= rp.nx ? rp.nx - 1 : gx), cy = gy < 0 ? 0 : (gy >= rp.ny ? rp.ny - 1 : gy);
+            const size_t g = (size_t)cy * (size_t)rp.nx + (size_t)cx;
+            const double *fq = rp.prev_feat + 8 * g;
+            const double covq = fq[7], wq = rp.prev_w[g];
+            const double p0 = rp.prev_lin[3 * g], p1 = rp.prev_lin[3 * g + 1], p2 = rp.prev_lin[3 * g + 2];
+            const double b = (tx ? ax : 1.0 - ax) * (ty ? ay : 1.0 - ay);
+            acc = acc && b > 0.0 && covq == 1.0 && wq > 0.0 && wq < big && ::fabs(p0) < big && ::fabs(p1) < big && ::fabs(p2) < big;
+            double seq = 0.0;
+            if (rp.prev_se) { seq = rp.prev_se[g]; acc = acc && seq == seq; }
+            if (rp.use_d) {
+                const double dq = fq[6], e = dq - dist, m = dq > dist ? dq : dist;
+                acc = acc && e * e <= rp.sd2 * (m * m);
+            }
+            if (rp.use_n) {
+                const double e0 = n0 - fq[3], e1 = n1 - fq[4], e2 = n2 - fq[5];
+                acc = acc && (e0 * e0 + e1 * e1) + e2 * e2 <= rp.sn2;
+            }
+            if (rp.use_a) {
+                const double e0 = a0 - fq[0], e1 = a1 - fq[1], e2 = a2 - fq[2];
+                acc = acc && (e0 * e0 + e1 * e1) + e2 * e2 <= rp.sa2;
+            }
+            if (acc) {
+                sw = sw + b;
+                s0 = s0 + b * p0; s1 = s1 + b * p1; s2 = s2 + b * p2;
+                sn = sn + b * wq;
+                st = st + b * (seq * seq);
+            }
+        }
+        double o0 = c0, o1 = c1, o2 = c2, ow = rp.cur_weight, ose = se_c;
+        if (sw != 0.0) {
+            took = true;
+            double nh = sn / sw;
+            if (nh > rp.max_history) nh = rp.max_history;
+            const double w = nh + rp.cur_weight, cw = rp.cur_weight;
+            o0 = (nh * (s0 / sw) + cw * c0) / w; o1 = (nh * (s1 / sw) + cw * c1) / w; o2 = (nh * (s2 / sw) + cw * c2) / w;
+            ow = w;
+            if (rp.out_se) ose = ::sqrt(((nh * nh) * (st / sw) + (cw * cw) * (se_c * se_c)) / (w * w));
+        }
+        if (rp.out_lin) { rp.out_lin[3 * p] = o0; rp.out_lin[3 * p + 1] = o1; rp.out_lin[3 * p + 2] = o2; }
+        if (rp.out_q) { rp.out_q[3 * p] = quantise8(o0); rp.out_q[3 * p + 1] = quantise8(o1); rp.out_q[3 * p + 2] = quantise8(o2); }
+        if (rp.out_w) rp.out_w[p] = ow;
+        if (rp.out_se) rp.out_se[p] = ose;
+    }
+    // The counters.  Every pixel of the frame is visited, so the first is nx * ny: one lane stores it.  The second takes one atomic per wave that
+    // found history.  (Two atomics per wave, as feature_kernel counts, were 0.67 ms of a 0.82 ms call at 1920 x 1080: 32 400 waves adding to one
+    // cache line wait for each other, and this kernel is too short to hide it.  DESIGN.md section 7h.)
+    if (rp.counters) {
+        const u64 hist = __ballot(took);
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) rp.counters[0] = (u64)rp.nx * (u64)rp.ny;
+        if ((threadIdx.x & 63u) == 0 && hist) atomicAdd(rp.counters + 1, (u64)__popcll(hist));
+    }
+}
+
 // What a progressive frame was started with: a continuation must match it field for field
 struct ProgKey {
     uint64_t scene_serial = 0, scene_revision = 0, seed = 0;
@@ -1312,6 +1424,7 @@ struct rtmi_ctx {
     ProgFrame prog; // at most one progressive frame per context
     DevBuf feat_out, feat_cnt; // rtmi_render_features*: the host form's result, the counters nobody asked for
     DevBuf dn_planes, dn_io;   // rtmi_denoise*: the filter's planes (two colour + variance sets, the feature planes), the host form's buffers
+    DevBuf rp_io;              // rtmi_reproject: the host form's buffers (the device form owns nothing)
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     int events_used = 0;
@@ -1888,7 +2001,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 210; } // 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 211; } // 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -1927,7 +2040,7 @@ RTMI_EXPORT int rtmi_shutdown(rtmi_ctx *c) {
 #endif
     c->samples.release(); c->accum.release(); c->tiles.release(); c->tile_ids.release(); c->counters.release(); c->scratch_lin.release(); c->multi.release();
     c->prog.release();
-    c->feat_out.release(); c->feat_cnt.release(); c->dn_planes.release(); c->dn_io.release();
+    c->feat_out.release(); c->feat_cnt.release(); c->dn_planes.release(); c->dn_io.release(); c->rp_io.release();
     for (hipEvent_t e : {c->ev_done, c->ev_g0, c->ev_g1}) if (e) (void)hipEventDestroy(e);
     if (c->ev_consumed) { (void)hipSetDevice(c->ev_consumed_device); (void)hipEventDestroy(c->ev_consumed); (void)hipSetDevice(c->device); }
     for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -3719,5 +3832,129 @@ RTMI_EXPORT int rtmi_denoise(rtmi_ctx *c, int32_t nx, int32_t ny, const double *
     if (out_linear) HIP_TRY(hipMemcpy(out_linear, d_olin, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
     if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_oq, 3 * n, hipMemcpyDeviceToHost));
     if (out_stderr) HIP_TRY(hipMemcpy(out_stderr, d_ose, n * sizeof(double), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---- temporal accumulation (rtmi_reproject*) -----------------------------------------------------------------------------------------------------------
+namespace {
+// the argument checks of both entries, before the handle is looked at: they need no device
+int check_reproject_args(int nx, int ny, int prev_cam_kind, const double *prev_cam, int cur_cam_kind, const double *cur_cam, const void *prev_lin,
+                         const void *prev_w, const void *prev_se, const void *prev_feat, const void *cur_lin, const void *cur_se, const void *cur_feat,
+                         double cur_weight, double max_history, double sigma_d, double sigma_n, double sigma_a, const void *out_lin, const void *out_q,
+                         const void *out_w, const void *out_se, const void *out_cnt) {
+    if (nx <= 0 || ny <= 0) return fail(RTMI_E_ARG, "nx, ny must be > 0 (got %d %d)", nx, ny);
+    if ((long long)nx * ny > (1ll << 30)) return fail(RTMI_E_ARG, "frame too large");
+    if (!prev_cam) return fail(RTMI_E_ARG, "prev_cam is NULL");
+    if (!cur_cam) return fail(RTMI_E_ARG, "cur_cam is NULL");
+    const struct { const void *p; const char *name; } need[5] = {{prev_lin, "prev_linear"}, {prev_w, "prev_weight"}, {prev_feat, "prev_features"},
+                                                                 {cur_lin, "cur_linear"}, {cur_feat, "cur_features"}};
+    for (const auto &a : need)
+        if (!a.p) return fail(RTMI_E_ARG, "%s is NULL", a.name);
+    if (!(cur_weight > 0.0 && cur_weight < __builtin_inf())) return fail(RTMI_E_ARG, "cur_weight must be finite and > 0 (got %g)", cur_weight);
+    if (!(max_history > 0.0)) return fail(RTMI_E_ARG, "max_history must be > 0 and not NaN (got %g)", max_history);
+    const double sg[3] = {sigma_d, sigma_n, sigma_a};
+    for (int k = 0; k < 3; ++k)
+        if (!(sg[k] >= 0.0)) return fail(RTMI_E_ARG, "sigma_%c must be >= 0 and not NaN (got %g)", "dna"[k], sg[k]);
+    if (out_se && !(prev_se && cur_se)) return fail(RTMI_E_ARG, "out_stderr needs both prev_stderr and cur_stderr");
+    const struct { const void *p; const char *name; } outs[5] = {{out_lin, "out_linear"}, {out_q, "out_rgb8"}, {out_w, "out_weight"},
+                                                                 {out_se, "out_stderr"}, {out_cnt, "out_counters"}};
+    const struct { const void *p; const char *name; } prevs[4] = {{prev_lin, "prev_linear"}, {prev_w, "prev_weight"}, {prev_se, "prev_stderr"},
+                                                                  {prev_feat, "prev_features"}};
+    for (const auto &o : outs)
+        for (const auto &q : prevs)
+            if (o.p && o.p == q.p) return fail(RTMI_E_ARG, "%s is %s: the history is gathered from neighbours and cannot be overwritten in place", o.name, q.name);
+    for (int kind : {prev_cam_kind, cur_cam_kind})
+        if (kind != RTMI_CAM_PINHOLE && kind != RTMI_CAM_THINLENS) return fail(RTMI_E_UNSUPPORTED, "camera kind %d unsupported on GPU path", kind);
+    return RTMI_OK;
+}
+
+// the launch: every pointer a device pointer, the cameras host arrays
+int reproject_impl(int nx, int ny, const double *prev_cam, const double *cur_cam, const double *prev_lin, const double *prev_w, const double *prev_se,
+                   const double *prev_feat, const double *cur_lin, const double *cur_se, const double *cur_feat, double cur_weight, double max_history,
+                   double sigma_d, double sigma_n, double sigma_a, double *out_lin, unsigned char *out_q, double *out_w, double *out_se, u64 *out_cnt,
+                   hipStream_t st) {
+    ReprojectParams rp;
+    rp.nx = nx; rp.ny = ny;
+    rp.use_d = sigma_d > 0.0; rp.use_n = sigma_n > 0.0; rp.use_a = sigma_a > 0.0;
+    double pl[3];
+    for (int k = 0; k < 3; ++k) {
+        rp.co[k] = cur_cam[k]; rp.cl[k] = cur_cam[3 + k]; rp.ch[k] = cur_cam[6 + k]; rp.cv[k] = cur_cam[9 + k];
+        rp.po[k] = prev_cam[k]; pl[k] = prev_cam[3 + k]; rp.ph[k] = prev_cam[6 + k]; rp.pv[k] = prev_cam[9 + k];
+        rp.a[k] = pl[k] - rp.po[k];
+    }
+    rp.n[0] = rp.ph[1] * rp.pv[2] - rp.ph[2] * rp.pv[1];
+    rp.n[1] = rp.ph[2] * rp.pv[0] - rp.ph[0] * rp.pv[2];
+    rp.n[2] = rp.ph[0] * rp.pv[1] - rp.ph[1] * rp.pv[0];
+    rp.nn = (rp.n[0] * rp.n[0] + rp.n[1] * rp.n[1]) + rp.n[2] * rp.n[2];
+    rp.A = (rp.a[0] * rp.n[0] + rp.a[1] * rp.n[1]) + rp.a[2] * rp.n[2];
+    rp.cur_weight = cur_weight; rp.max_history = max_history;
+    rp.sd2 = sigma_d * sigma_d; rp.sn2 = sigma_n * sigma_n; rp.sa2 = sigma_a * sigma_a;
+    rp.prev_lin = prev_lin; rp.prev_w = prev_w; rp.prev_se = prev_se; rp.prev_feat = prev_feat;
+    rp.cur_lin = cur_lin; rp.cur_se = cur_se; rp.cur_feat = cur_feat;
+    rp.out_lin = out_lin; rp.out_q = out_q; rp.out_w = out_w; rp.out_se = out_se; rp.counters = out_cnt;
+    if (out_cnt) HIP_TRY(hipMemsetAsync(out_cnt, 0, 2 * sizeof(u64), st));
+    hipLaunchKernelGGL(reproject_kernel, dim3((unsigned)((nx + 63) / 64), (unsigned)((ny + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, rp);
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_reproject_device(rtmi_ctx *c, int32_t nx, int32_t ny, int32_t prev_cam_kind, const double *prev_cam, int32_t cur_cam_kind,
+                                      const double *cur_cam, const void *d_prev_linear, const void *d_prev_weight, const void *d_prev_stderr,
+                                      const void *d_prev_features, const void *d_cur_linear, const void *d_cur_stderr, const void *d_cur_features,
+                                      double cur_weight, double max_history, double sigma_d, double sigma_n, double sigma_a, void *d_out_linear,
+                                      void *d_out_rgb8, void *d_out_weight, void *d_out_stderr, void *d_out_counters, void *stream) {
+    int rc = check_reproject_args(nx, ny, prev_cam_kind, prev_cam, cur_cam_kind, cur_cam, d_prev_linear, d_prev_weight, d_prev_stderr, d_prev_features,
+                                  d_cur_linear, d_cur_stderr, d_cur_features, cur_weight, max_history, sigma_d, sigma_n, sigma_a, d_out_linear, d_out_rgb8,
+                                  d_out_weight, d_out_stderr, d_out_counters);
+    if (rc) return rc;
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    auto D = [](const void *p) { return reinterpret_cast<const double *>(p); };
+    return reproject_impl(nx, ny, prev_cam, cur_cam, D(d_prev_linear), D(d_prev_weight), D(d_prev_stderr), D(d_prev_features), D(d_cur_linear),
+                          D(d_cur_stderr), D(d_cur_features), cur_weight, max_history, sigma_d, sigma_n, sigma_a, reinterpret_cast<double *>(d_out_linear),
+                          reinterpret_cast<unsigned char *>(d_out_rgb8), reinterpret_cast<double *>(d_out_weight), reinterpret_cast<double *>(d_out_stderr),
+                          reinterpret_cast<u64 *>(d_out_counters), st);
+}
+
+RTMI_EXPORT int rtmi_reproject(rtmi_ctx *c, int32_t nx, int32_t ny, int32_t prev_cam_kind, const double *prev_cam, int32_t cur_cam_kind,
+                               const double *cur_cam, const double *prev_linear, const double *prev_weight, const double *prev_stderr,
+                               const double *prev_features, const double *cur_linear, const double *cur_stderr, const double *cur_features,
+                               double cur_weight, double max_history, double sigma_d, double sigma_n, double sigma_a, double *out_linear,
+                               uint8_t *out_rgb8, double *out_weight, double *out_stderr, uint64_t *out_counters) {
+    int rc = check_reproject_args(nx, ny, prev_cam_kind, prev_cam, cur_cam_kind, cur_cam, prev_linear, prev_weight, prev_stderr, prev_features, cur_linear,
+                                  cur_stderr, cur_features, cur_weight, max_history, sigma_d, sigma_n, sigma_a, out_linear, out_rgb8, out_weight, out_stderr,
+                                  out_counters);
+    if (rc) return rc;
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)nx * (size_t)ny;
+    // in: two frames of linear 3n, stderr n, features 8n doubles and the history's weight n; out: linear 3n, weight n, stderr n doubles, the counters, rgb8 3n bytes
+    rc = c->rp_io.ensure(30 * n * sizeof(double) + 2 * sizeof(u64) + 3 * n);
+    if (rc) return rc;
+    double *d_plin = reinterpret_cast<double *>(c->rp_io.p), *d_pw = d_plin + 3 * n, *d_pse = d_pw + n, *d_pft = d_pse + n, *d_clin = d_pft + 8 * n,
+           *d_cse = d_clin + 3 * n, *d_cft = d_cse + n, *d_olin = d_cft + 8 * n, *d_ow = d_olin + 3 * n, *d_ose = d_ow + n;
+    u64 *d_cnt = reinterpret_cast<u64 *>(d_ose + n);
+    unsigned char *d_oq = reinterpret_cast<unsigned char *>(d_cnt + 2);
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(d_plin, prev_linear, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pw, prev_weight, n * sizeof(double), hipMemcpyHostToDevice));
+    if (prev_stderr) HIP_TRY(hipMemcpy(d_pse, prev_stderr, n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pft, prev_features, 8 * n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_clin, cur_linear, 3 * n * sizeof(double), hipMemcpyHostToDevice));
+    if (cur_stderr) HIP_TRY(hipMemcpy(d_cse, cur_stderr, n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_cft, cur_features, 8 * n * sizeof(double), hipMemcpyHostToDevice));
+    rc = reproject_impl(nx, ny, prev_cam, cur_cam, d_plin, d_pw, prev_stderr ? d_pse : nullptr, d_pft, d_clin, cur_stderr ? d_cse : nullptr, d_cft, cur_weight,
+                        max_history, sigma_d, sigma_n, sigma_a, out_linear ? d_olin : nullptr, out_rgb8 ? d_oq : nullptr, out_weight ? d_ow : nullptr,
+                        out_stderr ? d_ose : nullptr, out_counters ? d_cnt : nullptr, st);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out_linear) HIP_TRY(hipMemcpy(out_linear, d_olin, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_oq, 3 * n, hipMemcpyDeviceToHost));
+    if (out_weight) HIP_TRY(hipMemcpy(out_weight, d_ow, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_stderr) HIP_TRY(hipMemcpy(out_stderr, d_ose, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
