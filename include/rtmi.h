@@ -200,6 +200,9 @@ int rtmi_scene_set_camera_stream(rtmi_scene *scene, int32_t cam_kind, const doub
 int rtmi_scene_camera(rtmi_scene *scene, int32_t *cam_kind, double *cam, double *built_t_lo, double *built_t_hi);
 /* HBM bytes the scene occupies (everything its creation uploaded: records, tree, tables) -- bench.py's `upload_bytes` */
 int rtmi_scene_device_bytes(rtmi_scene *scene, int64_t *out_bytes);
+/* The device's tree as the scene was built with it: out_info[4] = node records, depth of the deepest leaf, entry-grid cells per side (0: no grid),
+ * big primitives kept out of the tree -- the four numbers rtmi_test_build_tree reports.  Host state only: no device access. */
+int rtmi_scene_tree_info(const rtmi_scene *scene, int32_t *out_info);
 int rtmi_scene_destroy(rtmi_scene *scene);
 
 /* ---- the hot path --------------------------------------------------------------------------- */

@@ -33,6 +33,7 @@ SYMBOLS = [
     "rtmi_render_adaptive_tiles_device", "rtmi_assemble_progressive_device", "rtmi_render_multi_adaptive", "rtmi_render_multi_adaptive_device",
     "rtmi_scene_set_camera", "rtmi_scene_set_camera_stream", "rtmi_scene_camera",
     "rtmi_reproject", "rtmi_reproject_device",
+    "rtmi_scene_tree_info",
 ]
 
 F64, F32 = 0, 1
@@ -132,6 +133,7 @@ def lib():
     L.rtmi_scene_set_camera.argtypes = [vp, i32, vp, C.POINTER(i32)]
     L.rtmi_scene_set_camera_stream.argtypes = [vp, i32, vp, vp]
     L.rtmi_scene_camera.argtypes = [vp, C.POINTER(i32), vp, C.POINTER(dbl), C.POINTER(dbl)]
+    L.rtmi_scene_tree_info.argtypes = [vp, vp]
     L.rtmi_reproject.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 5
     L.rtmi_reproject_device.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 6
     for name in SYMBOLS:

@@ -323,6 +323,13 @@ class DeviceScene:
         check(_ffi.lib().rtmi_scene_camera(self.handle, C.byref(kind), ptr(c), C.byref(lo), C.byref(hi)))
         return {"cam_kind": kind.value, "cam": c, "built_t_lo": lo.value, "built_t_hi": hi.value}
 
+    def tree_info(self):
+        """-> (node records, depth of the deepest leaf, entry-grid cells per side, big primitives kept out of the tree) of the device's tree as
+        the scene was built with it: what the launch decisions are taken from.  Host state only."""
+        info = np.zeros(4, np.int32)
+        check(_ffi.lib().rtmi_scene_tree_info(self.handle, ptr(info)))
+        return tuple(int(v) for v in info)
+
     def render_views(self, cameras, nx, ny, ns, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", stream=None, out_rgb8=None):
         """One frame per camera, queued back to back: for every view the stream form of set_camera, then render_device into its slice of ONE
         [V, ny, nx, 3] float64 device tensor (out_rgb8: an optional [V, ny, nx, 3] uint8 device tensor for the 8-bit frames), and ONE

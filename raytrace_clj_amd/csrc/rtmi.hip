@@ -2001,7 +2001,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 211; } // 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 212; } // 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -2447,6 +2447,13 @@ RTMI_EXPORT int rtmi_scene_camera(rtmi_scene *s, int32_t *cam_kind, double *cam,
     if (cam) std::memcpy(cam, s->dev.cam, 24 * sizeof(double));
     if (built_t_lo) *built_t_lo = s->dev.cull_t_lo;
     if (built_t_hi) *built_t_hi = s->dev.cull_t_hi;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_scene_tree_info(const rtmi_scene *s, int32_t *out_info) {
+    if (!scene_ok(const_cast<rtmi_scene *>(s))) return fail(RTMI_E_STATE, "invalid scene handle");
+    if (!out_info) return fail(RTMI_E_ARG, "out_info is NULL");
+    out_info[0] = s->bvh_node_count; out_info[1] = s->bvh_depth; out_info[2] = s->dev.grid_n; out_info[3] = s->dev.n_big;
     return RTMI_OK;
 }
 

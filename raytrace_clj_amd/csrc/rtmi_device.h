@@ -849,7 +849,10 @@ __device__ inline CullRay make_cull_ray(const Path<double> &P, double a, double 
     const float on = (fabsf(c.ox) + fabsf(c.oy)) + fabsf(c.oz);
     const float ku = 64.0f * 5.9604645e-08f; // 64 * 2^-24
     c.A1 = ku * c.a * 1.0001f;
-    c.A0 = c.A1 * (2.0f * on * on);
+    // ... + an ABSOLUTE floor: the bound above is relative, and below ~1e-19 (squares below FLT_MIN) the float evaluation loses its relative
+    // precision -- every operation then errs by up to half a denormal ulp (2^-150; 2^-126 if denormals were flushed), a q carries a times the four
+    // of q.  16 * 2^-126 (1 + a) = 2^-122 (1 + a) bounds that; at scene scales it is nothing (a chain of spheres shrinking to 1e-47 lost grazing hits)
+    c.A0 = c.A1 * (2.0f * on * on) + 7.5231638e-37f * (1.0f + c.a); // 2^-120 (1 + a)
     const bool safe = (on < 1e15f) && (c.a > 1e-30f) && (c.a < 1e30f) && (a > 1e-30) && (a < 1e30) && (P.time >= t_lo) && (P.time <= t_hi);
     if (!safe) { // NaN compares false too
         c.ox = c.oy = c.oz = c.dx = c.dy = c.dz = 0.0f; c.a = 0.0f; c.A1 = 0.0f; c.A0 = 3.0e38f;
