@@ -358,6 +358,49 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn set-materials
+  "Give the live scene `scn` (the Pointer create-scene! returned for the flattened scene `flat`) other materials and textures without a
+  new scene: `edited` is a scene {:camera :world} with the same primitives, or its flatten-scene map; its material and texture tables and
+  its primitive-to-material assignment replace the scene's, the geometry and the camera stay.  Every render afterwards is, bit for bit, the
+  render of a scene created from the edited arrays.  Returns true when the library had to rebuild the scene (the edit changes the number
+  of materials or textures, or brings the first Perlin / ImageMap / Isotropic use into a scene of plain spheres -- the Perlin tables and
+  images the scene already has stay), false when only the tables were rewritten where they lie.  A progressive frame started before the
+  call is not continued (start a new one: s-first 0)."
+  [scn flat edited]
+  (let [e       (if (contains? edited :world) (flatten-scene edited) edited)
+        rebuilt (int-array 1)]
+    (when (not= (:n-prims e) (:n-prims flat))
+      (throw (ex-info "set-materials: the edit has another primitive count" {:edit (:n-prims e) :scene (:n-prims flat)})))
+    (check (call-int "rtmi_scene_set_materials" scn
+                     (int (:n-mats e)) (:mat-kind e) (:mat-tex e) (:mat-param e)
+                     (int (:n-tex e)) (:tex-kind e) (:tex-param e) (:tex-child e)
+                     (:prim-mat e) rebuilt))
+    (= 1 (aget rebuilt 0))))
+
+(defn render-materials
+  "Render scene {:camera :world} once per entry of `edits` -- scenes with the same primitives, or flatten-scene maps: a colour picker, a
+  material library -- from ONE device scene: the world is flattened, built and uploaded once, every entry only rewrites the material
+  tables (set-materials).  Returns a vector of render's maps plus :rebuilt, one per entry, each equal to (render entry ...)."
+  [scene edits nx ny ns & {:keys [depth seed device precision] :or {depth 50 seed 0x5eed0002 device 0 precision 0}}]
+  (let [f   (flatten-scene scene)
+        ctx (PointerByReference.)
+        npx (* nx ny)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (mapv (fn [edited]
+                  (let [lin     (double-array (* 3 npx))
+                        rgb     (byte-array (* 3 npx))
+                        cnt     (long-array 2)
+                        rebuilt (set-materials scn f edited)]
+                    (check (call-int "rtmi_render" scn (int nx) (int ny) (int ns) (int depth) (long seed) (int precision)
+                                     (int 0) (int 0) (int nx) (int ny) lin rgb cnt))
+                    {:rgb8 rgb :linear lin :total-rays (aget cnt 0) :total-pixels (aget cnt 1) :rebuilt rebuilt}))
+                edits)
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn render-progressive
   "Render scene {:camera :world} progressively on GPU `device` (rtmi_render_progressive): chunks of `chunk` samples up to ns, and after
   each chunk (on-chunk m) with m = what `render` returns for ns = k (bit for bit) plus :samples k and :stderr (double-array, per pixel the

@@ -126,3 +126,18 @@
     (is (= (* 40 20 3) (count (:rgb8 out))))
     (is (= 800 (:total-pixels out)))
     (is (pos? (:total-rays out)))))
+
+(deftest ^:gpu set-materials-follows-the-edit
+  ;; ONE device scene, two entries: the scene's own tables (an edit that changes nothing) and the same tables with the first parameter of texture 0
+  ;; changed (a colour component, a gradient corner or a checker's scale: visible either way).  Neither rebuilds; the first frame is gpu/render's.
+  (let [fx  (fixture "two_spheres")
+        sc  (with-seeded-rand fx (scene/make-two-spheres (:nx fx) (:ny fx)))
+        f   (gpu/flatten-scene sc)
+        e   (assoc f :tex-param (let [a (aclone ^doubles (:tex-param f))] (aset a 0 0.25) a))
+        [before after] (gpu/render-materials sc [f e] (:nx fx) (:ny fx) 4)
+        own (gpu/render sc (:nx fx) (:ny fx) 4)]
+    (is (= (vec (:rgb8 before)) (vec (:rgb8 own))))
+    (is (= (:total-rays before) (:total-rays own)))
+    (is (false? (:rebuilt before)))
+    (is (false? (:rebuilt after)))
+    (is (not= (vec (:rgb8 after)) (vec (:rgb8 before))))))

@@ -198,6 +198,48 @@ int rtmi_scene_set_camera_stream(rtmi_scene *scene, int32_t cam_kind, const doub
 /* The camera the scene renders with now (cam_kind, cam[24]) and the shutter interval its MovingSphere bounds were built for.  Every output may be NULL.
  * Host state only: no device access. */
 int rtmi_scene_camera(rtmi_scene *scene, int32_t *cam_kind, double *cam, double *built_t_lo, double *built_t_hi);
+/* ---- the materials and textures of a live scene: a wall's colour, a lamp's power, a metal's fuzz, glass in place of a diffuse ball, a checker's scale ----
+ * Both calls take WHOLE tables with the layout rtmi_scene_create takes (the reference's records: shader.clj:29,46,76,114,129 Lambertian, Metal, Dielectric,
+ * DiffuseLight, Isotropic; texture.clj:14-133 Constant ... ImageMap) and prim_mat: n_prims entries (the scene's primitive count; the `material` field of
+ * hitable.clj's records), or NULL: the assignment stays as it is.  The geometry, the instancing records and the camera are the scene's.
+ * The promise: after either call has succeeded, every entry that reads the scene -- rtmi_render*, the tiles, progressive, adaptive and multi forms,
+ * rtmi_render_features* and the probes -- returns, BIT FOR BIT, what it returns for a scene freshly created from the edited arrays with the same camera and the
+ * same rtmi_scene_set_* calls: frame, 8-bit frame, standard error, samples, features and the ray counters, in RTMI_F64 and RTMI_F32.  It holds by
+ * construction: creation and the edit pack the material tables with one function.
+ * Materials and textures reach the device through eleven tables (the material records with a dielectric's precomputed 1/ri and r0, the gradient corners,
+ * the kinds, texture indices and parameters of the materials, the kinds, parameters and children of the textures, the primitives' materials and their kinds
+ * with the RTMI_PRIM_NEEDS_U / _V / _UV bits); the trees, the entry grid and every other table read geometry only.  The edit FITS if n_mats and n_tex are the
+ * scene's and the scene keeps its kernels: a section 8(f4) texture (above RTMI_TEX_CHECKER) or a used RTMI_MAT_ISOTROPIC material neither appears in a scene
+ * that the sphere kernels render nor disappears from one that had nothing else to need the EXT kernels.
+ *   The edit fits: only the eleven tables are written, where they lie, with the host's mirror of them and the arguments rtmi_scene_clone and a camera rebuild
+ *     replay.  No table is allocated or freed, rtmi_scene_device_bytes and rtmi_scene_tree_info are unchanged, and the traversal counters equal a fresh
+ *     scene's too (the tree is untouched).  *out_rebuilt (may be NULL) = 0.
+ *   It does not fit (rtmi_scene_set_materials only): the scene is rebuilt from the arrays it keeps with the edited ones in their place, as for a camera that
+ *     does not fit: uploaded beside the old tables, swapped, the old ones freed after the context's stream has been synchronised.  The Perlin tables, the
+ *     images, the media call sequence and the media mode stay, the handle and the scene's identity stay; on any failure the scene is exactly as before.
+ *     *out_rebuilt = 1.
+ * A Perlin texture without rtmi_scene_set_perlin, or an ImageMap beyond the images given, is reported when rendering (RTMI_E_STATE), as for a fresh scene.
+ * Both forms change the scene's revision on success, always: a progressive or adaptive frame started before the call is refused its continuation with
+ * RTMI_E_STATE, s_first = 0 starts a new one.
+ * rtmi_scene_set_materials synchronises the context's stream first, like every rtmi_scene_set_* call, then copies the tables that changed.
+ * rtmi_scene_set_materials_stream never waits for the host, and the caller's arrays are free again when it returns: the host packs the new tables, compares
+ * them row by row with its mirror, and only the changed rows travel, as the arguments of a one-wave kernel on `stream` (rtmi_render_device's stream semantics)
+ * -- one launch per batch that fits the kernel-argument space, none if nothing changed.  A render queued on that stream before the call sees the old materials,
+ * one queued after it the new ones; the host's mirror changes at once.  It is for the few records an interactive edit touches: more than
+ * RTMI_EDIT_STREAM_MAX_BYTES of changed rows, or an edit that does not fit: RTMI_E_UNSUPPORTED, rtmi_last_error names the reason, nothing changes and nothing
+ * is launched -- rtmi_scene_set_materials does both.  The scene's tables belong to one stream at a time, like its camera.
+ * Errors of the two forms, in this order: a negative count or a NULL array (prim_mat excepted): RTMI_E_ARG; a bad handle: RTMI_E_STATE; then creation's
+ * checks with creation's codes -- the kind ranges (RTMI_E_UNSUPPORTED), texture, child and image indices, prim_mat out of range, a medium whose material is
+ * not RTMI_MAT_ISOTROPIC (RTMI_E_ARG).  Any failure leaves the scene exactly as it was. */
+#define RTMI_EDIT_STREAM_MAX_BYTES 32768 /* changed row payload one rtmi_scene_set_materials_stream call carries */
+int rtmi_scene_set_materials(rtmi_scene *scene,
+                             int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
+                             int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
+                             const int32_t *prim_mat, int32_t *out_rebuilt);
+int rtmi_scene_set_materials_stream(rtmi_scene *scene,
+                                    int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
+                                    int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
+                                    const int32_t *prim_mat, void *stream);
 /* HBM bytes the scene occupies (everything its creation uploaded: records, tree, tables) -- bench.py's `upload_bytes` */
 int rtmi_scene_device_bytes(rtmi_scene *scene, int64_t *out_bytes);
 /* The device's tree as the scene was built with it: out_info[4] = node records, depth of the deepest leaf, entry-grid cells per side (0: no grid),
@@ -623,6 +665,16 @@ int rtmi_test_build_tree(int32_t n, const double *geom, const double *cam, int32
  * library's team of build threads, or with threads = 1 on the calling thread alone; out_hash = FNV-1a of the node array and the grid's root codes (the same
  * for any thread count), out_info[4] = node records, depth, grid cells per side, big primitives; out_ms = the build's wall time */
 int rtmi_test_half_outward(double x, int32_t up); /* x: a float value (host scalars are doubles at this boundary) */
+/* test hook, host code only (no device): the eleven material tables of rtmi_scene_create_ex's arrays, packed as rtmi_scene_set_materials* packs an edit
+ * (through_creation = 0: only prim_kind, prim_mat and the material and texture tables are read, the other arrays may be NULL) or as creation packs them
+ * (through_creation = 1: after creation's checks, as part of the whole scene).  out_hash = FNV-1a of the tables (equal for both: one packer),
+ * out_facts[3] = the materials' share of has_ext, uses_perlin, max_image.  The errors are those of the path taken. */
+int rtmi_test_pack_materials(int32_t n_prims, const int32_t *prim_kind, const double *prim_geom, const int32_t *prim_mat,
+                             int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
+                             int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
+                             int32_t cam_kind, const double *cam, const int32_t *prim_flip, const int32_t *prim_xform,
+                             int32_t n_xforms, const int32_t *xform_kind, const double *xform_param, int32_t through_creation,
+                             uint64_t *out_hash, int32_t *out_facts);
 
 #ifdef __cplusplus
 }

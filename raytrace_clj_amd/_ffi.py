@@ -34,6 +34,7 @@ SYMBOLS = [
     "rtmi_scene_set_camera", "rtmi_scene_set_camera_stream", "rtmi_scene_camera",
     "rtmi_reproject", "rtmi_reproject_device",
     "rtmi_scene_tree_info",
+    "rtmi_scene_set_materials", "rtmi_scene_set_materials_stream", "rtmi_test_pack_materials",
 ]
 
 F64, F32 = 0, 1
@@ -44,6 +45,7 @@ SEG_REC = 12
 TILE = 8
 PROG_REC = 5  # doubles per pixel of a progressive tile record: mean rgb, stderr, samples
 FEATURES = 8  # doubles per pixel of rtmi_render_features: albedo rgb, normal xyz, depth, coverage
+EDIT_STREAM_MAX_BYTES = 32768  # RTMI_EDIT_STREAM_MAX_BYTES: changed row payload one rtmi_scene_set_materials_stream call carries
 
 
 class RtmiError(RuntimeError):
@@ -134,6 +136,9 @@ def lib():
     L.rtmi_scene_set_camera_stream.argtypes = [vp, i32, vp, vp]
     L.rtmi_scene_camera.argtypes = [vp, C.POINTER(i32), vp, C.POINTER(dbl), C.POINTER(dbl)]
     L.rtmi_scene_tree_info.argtypes = [vp, vp]
+    L.rtmi_scene_set_materials.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, C.POINTER(i32)]
+    L.rtmi_scene_set_materials_stream.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.rtmi_test_pack_materials.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
     L.rtmi_reproject.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 5
     L.rtmi_reproject_device.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 6
     for name in SYMBOLS:

@@ -315,6 +315,38 @@ class DeviceScene:
         check(_ffi.lib().rtmi_scene_set_camera(self.handle, int(kind), ptr(c), C.byref(rebuilt)))
         return bool(rebuilt.value)
 
+    # ---- the materials of the live scene (rtmi_scene_set_materials*): other surfaces without a new scene ------------------------------
+    def set_materials(self, scene_or_flat, stream=None):
+        """Give the live scene other materials and textures: a FlatScene, or a scene (flattened here; its camera is not read) with the same
+        primitives -> rebuilt (bool).  Its material and texture tables and its prim_mat replace the scene's; geometry, instancing and camera stay.
+        Every render afterwards equals, bit for bit, the render of a scene created fresh from the edited arrays.  An edit that keeps the material
+        and texture counts and the scene's kernels (no first Perlin / ImageMap / Isotropic use in a scene of plain spheres, no last one removed)
+        rewrites the tables where they lie (False); any other rebuilds the scene behind the same handle (True) -- a new Perlin texture or image
+        then still needs its tables, as at creation (rtmi_scene_set_perlin / _images; rendering raises RtmiError -5 until then).
+        With a stream (a hipStream_t handle or torch stream; 0 = the context's own) only the changed rows travel, in stream order, and the host
+        is never waited for: renders queued before keep the old materials.  An edit that would rebuild, or more than
+        _ffi.EDIT_STREAM_MAX_BYTES of changed rows, raises RtmiError -3 and changes nothing.  ValueError if the primitive count differs.
+        self.flat is replaced by a copy that holds the new arrays (clones share the old one and keep it)."""
+        import copy
+        f = scene_or_flat if isinstance(scene_or_flat, fl.FlatScene) else fl.flatten(scene_or_flat)
+        if len(f.prim_mat) != len(self.flat.prim_kind):
+            raise ValueError("the edit has %d primitives, the scene %d" % (len(f.prim_mat), len(self.flat.prim_kind)))
+        mk, mt, mp, tk, tp, tc, pm = (np.ascontiguousarray(a, dt) for a, dt in (
+            (f.mat_kind, np.int32), (f.mat_tex, np.int32), (f.mat_param, np.float64), (f.tex_kind, np.int32), (f.tex_param, np.float64),
+            (f.tex_child, np.int32), (f.prim_mat, np.int32)))
+        args = (self.handle, len(mk), ptr(mk), ptr(mt), ptr(mp), len(tk), ptr(tk), ptr(tp), ptr(tc), ptr(pm))
+        rebuilt = C.c_int32()
+        if stream is not None:
+            handle = getattr(stream, "cuda_stream", stream)
+            check(_ffi.lib().rtmi_scene_set_materials_stream(*args, ptr(int(handle)) if handle else None))
+        else:
+            check(_ffi.lib().rtmi_scene_set_materials(*args, C.byref(rebuilt)))
+        flat = copy.copy(self.flat)
+        flat.mat_kind, flat.mat_tex, flat.mat_param, flat.tex_kind, flat.tex_param, flat.tex_child, flat.prim_mat = (
+            mk.copy(), mt.copy(), mp.copy(), tk.copy(), tp.reshape(-1, fl.TEX_STRIDE).copy(), tc.reshape(-1, 2).copy(), pm.copy())
+        self.flat = flat
+        return bool(rebuilt.value)
+
     def camera_info(self):
         """-> {"cam_kind", "cam" (24 doubles), "built_t_lo", "built_t_hi"}: the camera the scene renders with now and the shutter interval its
         trees were built for (a camera whose interval lies inside it never rebuilds).  Host state only."""
@@ -589,11 +621,14 @@ class TemporalAccumulator:
         self.steps = getattr(self, "steps", 0)
         self.raw_rgb8 = self.accumulated = None
 
-    def step(self, camera, nx=None, ny=None, precision=None):
+    def step(self, camera, nx=None, ny=None, precision=None, materials=None):
         """-> (linear [ny,nx,3], rgb8, stderr [ny,nx], weight [ny,nx] = samples behind every pixel, share of the pixels that took history): device
         tensors owned by the accumulator -- rgb8 is overwritten by the next step, the others by the one after it -- filtered if denoise= was
         given (then .accumulated holds the unfiltered four).  .raw_rgb8 is the 8-bit frame of this view's ns samples alone, .rays its
-        {total-rays, total-pixels}."""
+        {total-rays, total-pixels}.
+        materials= (a FlatScene or scene, as DeviceScene.set_materials takes it) edits the scene's materials in stream order before this frame
+        (the stream form: an edit that would rebuild raises RtmiError -3 before anything is queued).  Such a step starts WITHOUT history
+        (share 0), like the first: the colours accumulated so far describe other surfaces.  The step after it takes history again."""
         import torch
         nx, ny, precision = nx or self.nx, ny or self.ny, precision or self.precision
         if (nx, ny, precision) != (self.nx, self.ny, self.precision):
@@ -601,13 +636,15 @@ class TemporalAccumulator:
         ds, ctx, dev = self.scene, self.scene.ctx, torch.device("cuda", self.scene.ctx.device)
         cam_pair = _camera_pair(camera)
         old, new = self._cur, 1 - self._cur
-        first = self._cam is None
+        first = self._cam is None or materials is not None
         if first:
             self._w[new].fill_(float(self.ns))
         torch.cuda.synchronize(dev)  # (the allocator or the fill ran on torch's stream; nothing of torch's is queued after this)
         seed = self.seed + self.steps
         lin, se = (self._lin[new], self._se[new]) if first else (self._cur_lin, self._cur_se)
         st = self.stream or None
+        if materials is not None:
+            ds.set_materials(materials, stream=self.stream)
         ds.set_camera(cam_pair, stream=self.stream)
         ds.render_progressive_device(nx, ny, 0, self.ns, lin, self._raw_q, se, self._cnt[2:], self.depth, seed, precision, st)
         ds.render_features_device(nx, ny, self.na, self._ft[new], None, seed, precision, st)

@@ -1450,6 +1450,8 @@ struct rtmi_scene {
     std::vector<int> host_kind; // primitive kinds (boundary flag removed), for argument checks
     bool has_moving = false;    // a RTMI_PRIM_MOVING primitive is present: the trees and cull entries hold for the shutter interval [dev.cull_t_lo, dev.cull_t_hi] only
     std::map<int, std::array<double, 5>> media_fast_of; // medium primitive -> {density, c.xyz, r*r} when it and its boundary are one plain sphere without wrappers (DevScene::media_fast)
+    PackedMaterials mat;   // host copy of the eleven material tables as they lie in HBM: what rtmi_scene_set_materials_stream compares an edit with, row by row
+    bool geom_ext = false; // the geometry's share of dev.has_ext (PackedScene::geom_ext): an edit of the materials fits if it leaves dev.has_ext as it is
     // the caller's arrays, copied at creation (the library keeps no host POINTERS): what rtmi_scene_clone replicates
     struct Args {
         std::vector<int32_t> prim_kind, prim_mat, mat_kind, mat_tex, tex_kind, tex_child, prim_flip, prim_xform, xform_kind, perm, media_calls, media_lo, image_wh;
@@ -1488,9 +1490,9 @@ int upload_tables(const PackedScene &P, DevScene &d, std::vector<void *> &allocs
     const Table tables[] = {
         {P.stat_geom, &d.stat_geom}, {P.stat_orig, &d.stat_orig}, {P.bvh_nodes, &d.bvh_nodes}, {P.grid_cells, &d.grid_cells}, {P.moving_all, &d.moving_all},
         {P.leaf_rec, &d.leaf_rec}, {P.ext_info, &d.ext_info}, {P.ext_xf, &d.ext_xf}, {P.cull20, &d.cull20}, {P.exact12, &d.exact12}, {P.stat4_d, &d.stat4_d},
-        {P.stat4_f, &d.stat4_f}, {P.mov_geom, &d.mov_geom}, {P.mov_orig, &d.mov_orig}, {P.prim_kind, &d.prim_kind}, {P.prim_km, &d.prim_km},
-        {P.mat_rec, &d.mat_rec}, {P.mat_grad, &d.mat_grad}, {P.prim_mat, &d.prim_mat}, {P.mat_kind, &d.mat_kind}, {P.mat_tex, &d.mat_tex},
-        {P.mat_param, &d.mat_param}, {P.tex_kind, &d.tex_kind}, {P.tex_param, &d.tex_param}, {P.tex_child, &d.tex_child}};
+        {P.stat4_f, &d.stat4_f}, {P.mov_geom, &d.mov_geom}, {P.mov_orig, &d.mov_orig}, {P.M.prim_kind, &d.prim_kind}, {P.M.prim_km, &d.prim_km},
+        {P.M.mat_rec, &d.mat_rec}, {P.M.mat_grad, &d.mat_grad}, {P.M.prim_mat, &d.prim_mat}, {P.M.mat_kind, &d.mat_kind}, {P.M.mat_tex, &d.mat_tex},
+        {P.M.mat_param, &d.mat_param}, {P.M.tex_kind, &d.tex_kind}, {P.M.tex_param, &d.tex_param}, {P.M.tex_child, &d.tex_child}};
     for (const Table &t : tables) { const int rc = upload_to(allocs, bytes, t); if (rc) return rc; }
     return RTMI_OK;
 }
@@ -2001,7 +2003,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 212; } // 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 213; } // 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -2103,22 +2105,11 @@ static void fill_media_fast(DevScene &d, const std::map<int, std::array<double, 
 }
 static void fill_media_fast(rtmi_scene *s) { fill_media_fast(s->dev, s->media_fast_of); }
 namespace {
-// the checks of rtmi_scene_create_ex, in the order they are reported
-int check_scene_args(const SceneArrays &a, rtmi_scene **out_scene) {
-    const int n_prims = a.n_prims, n_mats = a.n_mats, n_tex = a.n_tex, n_xforms = a.n_xforms;
-    const int32_t *prim_kind = a.prim_kind, *prim_mat = a.prim_mat, *mat_kind = a.mat_kind, *mat_tex = a.mat_tex, *tex_kind = a.tex_kind, *tex_child = a.tex_child;
-    if (n_xforms < 0 || (n_xforms > 0 && (!a.xform_kind || !a.xform_param || !a.prim_xform))) return fail(RTMI_E_ARG, "xform arrays are NULL");
-    for (int k = 0; k < n_xforms; ++k)
-        if (a.xform_kind[k] != RTMI_XFORM_TRANSLATE && a.xform_kind[k] != RTMI_XFORM_ROTATE_Y) return fail(RTMI_E_UNSUPPORTED, "xform %d: kind %d unsupported on GPU path", k, a.xform_kind[k]);
-    if (!out_scene) return fail(RTMI_E_ARG, "out_scene is NULL");
-    *out_scene = nullptr;
-    if (n_prims < 0 || n_mats < 0 || n_tex < 0) return fail(RTMI_E_ARG, "negative count");
-    if (n_prims > 0 && (!prim_kind || !a.prim_geom || !prim_mat)) return fail(RTMI_E_ARG, "primitive arrays are NULL");
-    if (n_mats > 0 && (!mat_kind || !mat_tex || !a.mat_param)) return fail(RTMI_E_ARG, "material arrays are NULL");
-    if (n_tex > 0 && (!tex_kind || !a.tex_param || !tex_child)) return fail(RTMI_E_ARG, "texture arrays are NULL");
-    if (!a.cam) return fail(RTMI_E_ARG, "cam is NULL");
-    if (a.cam_kind != RTMI_CAM_PINHOLE && a.cam_kind != RTMI_CAM_THINLENS) return fail(RTMI_E_UNSUPPORTED, "camera kind %d unsupported on GPU path", a.cam_kind);
-    // validate: this is where "unknown record type -> explicit unsupported error" surfaces
+// The checks of the material and texture tables, shared by rtmi_scene_create_ex and rtmi_scene_set_materials*: the kind ranges, the texture and child indices, the
+// image indices.  This is where "unknown record type -> explicit unsupported error" surfaces
+int check_material_tables(const SceneArrays &a) {
+    const int n_mats = a.n_mats, n_tex = a.n_tex;
+    const int32_t *mat_kind = a.mat_kind, *mat_tex = a.mat_tex, *tex_kind = a.tex_kind, *tex_child = a.tex_child;
     for (int t = 0; t < n_tex; ++t) {
         if (tex_kind[t] < RTMI_TEX_CONSTANT || tex_kind[t] > RTMI_TEX_IMAGE) return fail(RTMI_E_UNSUPPORTED, "texture %d: kind %d unsupported on GPU path", t, tex_kind[t]);
         if (tex_kind[t] == RTMI_TEX_FLIP_U || tex_kind[t] == RTMI_TEX_FLIP_V) {
@@ -2140,6 +2131,34 @@ int check_scene_args(const SceneArrays &a, rtmi_scene **out_scene) {
             const double im = a.tex_param[(size_t)t * RTMI_TEX_STRIDE];
             if (!(im >= 0 && im < 1e6 && im == std::floor(im))) return fail(RTMI_E_ARG, "texture %d: image index invalid", t);
         }
+    return RTMI_OK;
+}
+// ... and of primitive i's material: its index, and (after the index: it reads the material) the phase function of a medium
+int check_prim_material(const SceneArrays &a, int i) {
+    if (a.prim_mat[i] < 0 || a.prim_mat[i] >= a.n_mats) return fail(RTMI_E_ARG, "primitive %d: material index %d invalid", i, a.prim_mat[i]);
+    return RTMI_OK;
+}
+int check_medium_material(const SceneArrays &a, int i) {
+    if (a.mat_kind[a.prim_mat[i]] != RTMI_MAT_ISOTROPIC) return fail(RTMI_E_ARG, "medium %d: the phase function must be RTMI_MAT_ISOTROPIC", i);
+    return RTMI_OK;
+}
+// the checks of rtmi_scene_create_ex, in the order they are reported
+int check_scene_args(const SceneArrays &a, rtmi_scene **out_scene) {
+    const int n_prims = a.n_prims, n_mats = a.n_mats, n_tex = a.n_tex, n_xforms = a.n_xforms;
+    const int32_t *prim_kind = a.prim_kind, *prim_mat = a.prim_mat, *mat_kind = a.mat_kind, *mat_tex = a.mat_tex, *tex_kind = a.tex_kind, *tex_child = a.tex_child;
+    if (n_xforms < 0 || (n_xforms > 0 && (!a.xform_kind || !a.xform_param || !a.prim_xform))) return fail(RTMI_E_ARG, "xform arrays are NULL");
+    for (int k = 0; k < n_xforms; ++k)
+        if (a.xform_kind[k] != RTMI_XFORM_TRANSLATE && a.xform_kind[k] != RTMI_XFORM_ROTATE_Y) return fail(RTMI_E_UNSUPPORTED, "xform %d: kind %d unsupported on GPU path", k, a.xform_kind[k]);
+    if (!out_scene) return fail(RTMI_E_ARG, "out_scene is NULL");
+    *out_scene = nullptr;
+    if (n_prims < 0 || n_mats < 0 || n_tex < 0) return fail(RTMI_E_ARG, "negative count");
+    if (n_prims > 0 && (!prim_kind || !a.prim_geom || !prim_mat)) return fail(RTMI_E_ARG, "primitive arrays are NULL");
+    if (n_mats > 0 && (!mat_kind || !mat_tex || !a.mat_param)) return fail(RTMI_E_ARG, "material arrays are NULL");
+    if (n_tex > 0 && (!tex_kind || !a.tex_param || !tex_child)) return fail(RTMI_E_ARG, "texture arrays are NULL");
+    if (!a.cam) return fail(RTMI_E_ARG, "cam is NULL");
+    if (a.cam_kind != RTMI_CAM_PINHOLE && a.cam_kind != RTMI_CAM_THINLENS) return fail(RTMI_E_UNSUPPORTED, "camera kind %d unsupported on GPU path", a.cam_kind);
+    int rc = check_material_tables(a);
+    if (rc) return rc;
     int n_world = 0, n_media = 0;
     for (int i = 0; i < n_prims; ++i) {
         const int kind = prim_kind[i] & ~RTMI_PRIM_BOUNDARY;
@@ -2148,13 +2167,13 @@ int check_scene_args(const SceneArrays &a, rtmi_scene **out_scene) {
         if (is_boundary && kind == RTMI_PRIM_MEDIUM) return fail(RTMI_E_UNSUPPORTED, "primitive %d: a medium inside a medium's boundary is unsupported", i);
         if (!is_boundary && n_world != i) return fail(RTMI_E_ARG, "primitive %d: boundary primitives must come after all world primitives", i);
         if (!is_boundary) n_world = i + 1;
-        if (prim_mat[i] < 0 || prim_mat[i] >= n_mats) return fail(RTMI_E_ARG, "primitive %d: material index %d invalid", i, prim_mat[i]);
+        if ((rc = check_prim_material(a, i)) != RTMI_OK) return rc;
         if (kind == RTMI_PRIM_MEDIUM) {
             const double *mg = a.prim_geom + (size_t)i * RTMI_PRIM_STRIDE;
             const int fb = (int)mg[1], nb = (int)mg[2];
             if (!(mg[0] == mg[0]) || fb < 0 || nb <= 0 || fb + nb > n_prims) return fail(RTMI_E_ARG, "medium %d: boundary range [%d, %d) invalid", i, fb, fb + nb);
             for (int q = fb; q < fb + nb; ++q) if (!(prim_kind[q] & RTMI_PRIM_BOUNDARY)) return fail(RTMI_E_ARG, "medium %d: primitive %d is not flagged RTMI_PRIM_BOUNDARY", i, q);
-            if (mat_kind[prim_mat[i]] != RTMI_MAT_ISOTROPIC) return fail(RTMI_E_ARG, "medium %d: the phase function must be RTMI_MAT_ISOTROPIC", i);
+            if ((rc = check_medium_material(a, i)) != RTMI_OK) return rc;
             if (n_media++ >= 16) return fail(RTMI_E_UNSUPPORTED, "more than 16 ConstantMedium records in one scene");
             continue;
         }
@@ -2181,15 +2200,16 @@ RTMI_EXPORT int rtmi_scene_create_ex(rtmi_ctx *c, int32_t n_prims, const int32_t
     HIP_TRY(hipSetDevice(c->device));
     rtmi_scene *s = new (std::nothrow) rtmi_scene();
     if (!s) return fail(RTMI_E_NOMEM, "out of host memory");
-    const PackedScene P = pack_scene(a, knobs);
+    PackedScene P = pack_scene(a, knobs);
     s->ctx = c; s->n_prims = n_prims; s->n_mats = n_mats; s->n_tex = n_tex;
     s->serial = ++g_scene_serial;
-    s->uses_perlin = P.uses_perlin; s->max_image = P.max_image; s->bvh_node_count = P.bvh_node_count; s->bvh_depth = P.bvh_depth;
-    s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of; s->dev = P.d;
+    s->uses_perlin = P.M.uses_perlin; s->max_image = P.M.max_image; s->bvh_node_count = P.bvh_node_count; s->bvh_depth = P.bvh_depth;
+    s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of; s->dev = P.d; s->geom_ext = P.geom_ext;
     for (int k : s->host_kind) s->has_moving = s->has_moving || k == RTMI_PRIM_MOVING;
     DevScene &d = s->dev;
     rc = upload_tables(P, d, s->table_allocs, s->table_bytes);
     s->device_bytes += s->table_bytes;
+    s->mat = std::move(P.M); // (uploaded: the scene keeps the host copy)
     fill_media_fast(s);
     if (!rc) {
         std::vector<DevScene> one(1, d);
@@ -2359,15 +2379,19 @@ void adopt_camera(rtmi_scene *s, int cam_kind, const double *cam) {
     s->args.cam.assign(cam, cam + 24); s->args.cam_kind = cam_kind;
     s->revision++;
 }
-// The slow path: the staged build with the new camera from the arrays the scene keeps, new tables uploaded beside the old ones, then the swap.
-// Until the swap nothing of the scene has changed; a failure frees what was uploaded and leaves it as it was.
-int rebuild_for_camera(rtmi_scene *s, int cam_kind, const double *cam) {
+// The arrays the scene keeps, as pack_scene takes them: what a rebuild starts from.  The callers replace the camera, or the materials, by their own.
+SceneArrays kept_arrays(const rtmi_scene *s) {
     const rtmi_scene::Args &A = s->args;
-    const SceneArrays a{s->n_prims, A.prim_kind.data(), A.prim_geom.data(), A.prim_mat.data(), s->n_mats, A.mat_kind.data(), A.mat_tex.data(), A.mat_param.data(),
-                        s->n_tex, A.tex_kind.data(), A.tex_param.data(), A.tex_child.data(), cam_kind, cam,
-                        A.prim_flip.empty() ? nullptr : A.prim_flip.data(), A.prim_xform.empty() ? nullptr : A.prim_xform.data(),
-                        (int)A.xform_kind.size(), A.xform_kind.empty() ? nullptr : A.xform_kind.data(), A.xform_param.empty() ? nullptr : A.xform_param.data()};
-    const PackedScene P = pack_scene(a, read_build_knobs());
+    return SceneArrays{s->n_prims, A.prim_kind.data(), A.prim_geom.data(), A.prim_mat.data(), s->n_mats, A.mat_kind.data(), A.mat_tex.data(), A.mat_param.data(),
+                       s->n_tex, A.tex_kind.data(), A.tex_param.data(), A.tex_child.data(), A.cam_kind, A.cam.data(),
+                       A.prim_flip.empty() ? nullptr : A.prim_flip.data(), A.prim_xform.empty() ? nullptr : A.prim_xform.data(),
+                       (int)A.xform_kind.size(), A.xform_kind.empty() ? nullptr : A.xform_kind.data(), A.xform_param.empty() ? nullptr : A.xform_param.data()};
+}
+// The slow path of a camera or material edit: the staged build from `a` (the arrays the scene keeps, with the edited ones in their place), new tables uploaded
+// beside the old ones, then the swap.  Until the swap nothing of the scene has changed; a failure frees what was uploaded and leaves it as it was.  The caller
+// adopts the edited arrays into rtmi_scene::Args afterwards (`a` may point into them) and bumps the revision.
+int rebuild_scene(rtmi_scene *s, const SceneArrays &a, const char *what) {
+    PackedScene P = pack_scene(a, read_build_knobs());
     DevScene nd = P.d;
     std::vector<void *> fresh;
     size_t fresh_bytes = 0;
@@ -2383,7 +2407,7 @@ int rebuild_for_camera(rtmi_scene *s, int cam_kind, const double *cam) {
         fill_media_fast(nd, P.media_fast_of);
         hipError_t e = hipStreamSynchronize(s->ctx->stream); // the renders in flight read the old tables
         if (e == hipSuccess) e = hipMemcpy((void *)s->d_dev, &nd, sizeof(DevScene), hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = fail(RTMI_E_DEVICE, "rtmi_scene_set_camera: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = fail(RTMI_E_DEVICE, "%s: %s", what, hipGetErrorString(e));
     }
     if (rc) { for (void *p : fresh) (void)hipFree(p); return rc; }
     for (void *p : s->table_allocs) (void)hipFree(p); // (the stream was synchronised above and nothing has been launched since)
@@ -2391,8 +2415,16 @@ int rebuild_for_camera(rtmi_scene *s, int cam_kind, const double *cam) {
     s->device_bytes = s->device_bytes - s->table_bytes + fresh_bytes;
     s->table_bytes = fresh_bytes;
     s->dev = nd;
-    s->uses_perlin = P.uses_perlin; s->max_image = P.max_image; s->bvh_node_count = P.bvh_node_count; s->bvh_depth = P.bvh_depth;
-    s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of;
+    s->uses_perlin = P.M.uses_perlin; s->max_image = P.M.max_image; s->bvh_node_count = P.bvh_node_count; s->bvh_depth = P.bvh_depth;
+    s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of; s->mat = std::move(P.M); s->geom_ext = P.geom_ext;
+    s->n_mats = a.n_mats; s->n_tex = a.n_tex;
+    return RTMI_OK;
+}
+int rebuild_for_camera(rtmi_scene *s, int cam_kind, const double *cam) {
+    SceneArrays a = kept_arrays(s);
+    a.cam_kind = cam_kind; a.cam = cam;
+    const int rc = rebuild_scene(s, a, "rtmi_scene_set_camera");
+    if (rc) return rc;
     s->args.cam.assign(cam, cam + 24); s->args.cam_kind = cam_kind;
     s->revision++;
     return RTMI_OK;
@@ -2447,6 +2479,208 @@ RTMI_EXPORT int rtmi_scene_camera(rtmi_scene *s, int32_t *cam_kind, double *cam,
     if (cam) std::memcpy(cam, s->dev.cam, 24 * sizeof(double));
     if (built_t_lo) *built_t_lo = s->dev.cull_t_lo;
     if (built_t_hi) *built_t_hi = s->dev.cull_t_hi;
+    return RTMI_OK;
+}
+
+// ---- the materials and textures of a live scene (rtmi_scene_set_materials*) --------------------------------------------------------------------
+namespace {
+// One of the eleven tables that read the materials: its host copy in a PackedMaterials, its place in HBM, the bytes of one row
+struct MatTable { const void *host; size_t bytes, row; const void *dev; };
+constexpr int kMatTables = 11;
+std::array<MatTable, kMatTables> material_tables(const PackedMaterials &M, const DevScene &d) {
+    auto tab = [](const auto &v, size_t row_elems, const void *dev) { return MatTable{v.data(), v.size() * sizeof(v[0]), row_elems * sizeof(v[0]), dev}; };
+    return {tab(M.mat_rec, 12, d.mat_rec), tab(M.mat_grad, 12, d.mat_grad), tab(M.mat_kind, 1, d.mat_kind), tab(M.mat_tex, 1, d.mat_tex),
+            tab(M.mat_param, 1, d.mat_param), tab(M.tex_kind, 1, d.tex_kind), tab(M.tex_param, RTMI_TEX_STRIDE, d.tex_param), tab(M.tex_child, 2, d.tex_child),
+            tab(M.prim_mat, 1, d.prim_mat), tab(M.prim_kind, 1, d.prim_kind), tab(M.prim_km, 2, d.prim_km)};
+}
+
+// The changed rows of a stream edit travel as kernel arguments: up to kPatchRows rows and kPatchWords 32-bit words of payload per launch (the argument space is
+// 4 KiB).  Every table's rows are whole 32-bit words and 4-byte aligned in HBM.
+constexpr int kPatchRows = 64, kPatchWords = 704;
+struct PatchRow { unsigned *dst; unsigned short src, n; unsigned pad; }; // n words from word[src] to dst
+struct PatchArgs { PatchRow row[kPatchRows]; unsigned word[kPatchWords]; int n_rows, pad; };
+static_assert(sizeof(PatchArgs) <= 4096, "one launch's rows fit the kernel-argument space");
+static_assert(RTMI_EDIT_STREAM_MAX_BYTES % 4 == 0 && 96 / 4 <= kPatchWords, "the largest row (MatRec, a texture's parameters: twelve doubles) fits one launch");
+
+// One wave, in stream order: lane l stores row l, word by word.  Plain vector stores; the launch boundary orders them for the renders queued behind it on the
+// stream (they read the tables through caches every kernel launch invalidates).  No LDS, no scratch.
+__global__ void __launch_bounds__(64) set_materials_kernel(PatchArgs a) {
+    const int l = (int)threadIdx.x;
+    if (l >= a.n_rows) return;
+    unsigned *dst = a.row[l].dst;
+    const int src = a.row[l].src, n = a.row[l].n;
+    for (int k = 0; k < n; ++k) dst[k] = a.word[src + k];
+}
+
+// the argument errors of both set forms, reported before the handle is examined
+int check_material_arrays(int n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param, int n_tex, const int32_t *tex_kind,
+                          const double *tex_param, const int32_t *tex_child) {
+    if (n_mats < 0 || n_tex < 0) return fail(RTMI_E_ARG, "negative count");
+    if (n_mats > 0 && (!mat_kind || !mat_tex || !mat_param)) return fail(RTMI_E_ARG, "material arrays are NULL");
+    if (n_tex > 0 && (!tex_kind || !tex_param || !tex_child)) return fail(RTMI_E_ARG, "texture arrays are NULL");
+    return RTMI_OK;
+}
+// the checks creation applies to the materials, on the scene's arrays with the edited ones in their place
+int check_material_edit(const SceneArrays &a) {
+    int rc = check_material_tables(a);
+    for (int i = 0; i < a.n_prims && !rc; ++i) {
+        rc = check_prim_material(a, i);
+        if (!rc && (a.prim_kind[i] & ~RTMI_PRIM_BOUNDARY) == RTMI_PRIM_MEDIUM) rc = check_medium_material(a, i);
+    }
+    return rc;
+}
+// The edit FITS the built scene: the tables keep their sizes and the scene keeps its kernels (dev.has_ext, and through it the entry grid and the small scan).
+// why (optional): the reason it does not
+bool materials_fit(const rtmi_scene *s, const SceneArrays &a, const PackedMaterials &M, std::string *why) {
+    char buf[160] = "";
+    const int has_ext = (s->geom_ext || M.has_ext) ? 1 : 0;
+    if (a.n_mats != s->n_mats) snprintf(buf, sizeof buf, "the edit has %d materials, the scene %d", a.n_mats, s->n_mats);
+    else if (a.n_tex != s->n_tex) snprintf(buf, sizeof buf, "the edit has %d textures, the scene %d", a.n_tex, s->n_tex);
+    else if (has_ext != s->dev.has_ext)
+        snprintf(buf, sizeof buf, "the edit %s a texture or material that only the EXT kernels hold (has_ext %d -> %d)", has_ext ? "brings in" : "removes the last use of", s->dev.has_ext, has_ext);
+    else {
+        const auto was = material_tables(s->mat, s->dev), now = material_tables(M, s->dev);
+        for (int t = 0; t < kMatTables; ++t) if (was[(size_t)t].bytes != now[(size_t)t].bytes) snprintf(buf, sizeof buf, "table %d changes its size", t); // (cannot happen: the counts are equal)
+    }
+    if (why) *why = buf;
+    return buf[0] == 0;
+}
+// the host's half of an edit: the mirror of the tables, the facts the render checks read, and the arguments a clone or a camera rebuild replays
+void adopt_materials(rtmi_scene *s, const SceneArrays &a, PackedMaterials *M) {
+    rtmi_scene::Args &A = s->args;
+    if (M) { s->uses_perlin = M->uses_perlin; s->max_image = M->max_image; s->mat = std::move(*M); } // (a rebuild has done this itself)
+    if (a.prim_mat != A.prim_mat.data()) A.prim_mat.assign(a.prim_mat, a.prim_mat + a.n_prims);
+    A.mat_kind.assign(a.mat_kind, a.mat_kind + a.n_mats); A.mat_tex.assign(a.mat_tex, a.mat_tex + a.n_mats); A.mat_param.assign(a.mat_param, a.mat_param + a.n_mats);
+    A.tex_kind.assign(a.tex_kind, a.tex_kind + a.n_tex); A.tex_param.assign(a.tex_param, a.tex_param + (size_t)a.n_tex * RTMI_TEX_STRIDE);
+    A.tex_child.assign(a.tex_child, a.tex_child + 2 * (size_t)a.n_tex);
+    s->revision++;
+}
+// both forms up to the decision: the checks in the order they are reported, the scene's arrays with the edit in their place, the packed tables
+int prepare_material_edit(rtmi_scene *s, int n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param, int n_tex, const int32_t *tex_kind,
+                          const double *tex_param, const int32_t *tex_child, const int32_t *prim_mat, SceneArrays &a, PackedMaterials &M) {
+    int rc = check_material_arrays(n_mats, mat_kind, mat_tex, mat_param, n_tex, tex_kind, tex_param, tex_child);
+    if (rc) return rc;
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    a = kept_arrays(s);
+    a.n_mats = n_mats; a.mat_kind = mat_kind; a.mat_tex = mat_tex; a.mat_param = mat_param;
+    a.n_tex = n_tex; a.tex_kind = tex_kind; a.tex_param = tex_param; a.tex_child = tex_child;
+    if (prim_mat) a.prim_mat = prim_mat;
+    rc = check_material_edit(a);
+    if (rc) return rc;
+    M = pack_materials(a);
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_scene_set_materials(rtmi_scene *s, int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
+                                         int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
+                                         const int32_t *prim_mat, int32_t *out_rebuilt) {
+    SceneArrays a;
+    PackedMaterials M;
+    int rc = prepare_material_edit(s, n_mats, mat_kind, mat_tex, mat_param, n_tex, tex_kind, tex_param, tex_child, prim_mat, a, M);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    if (!materials_fit(s, a, M, nullptr)) {
+        rc = rebuild_scene(s, a, "rtmi_scene_set_materials");
+        if (rc) return rc;
+        adopt_materials(s, a, nullptr);
+        if (out_rebuilt) *out_rebuilt = 1;
+        return RTMI_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    const auto was = material_tables(s->mat, s->dev), now = material_tables(M, s->dev);
+    for (int t = 0; t < kMatTables; ++t) { // each table where it lies; a table the edit leaves as it is does not travel
+        const MatTable &o = was[(size_t)t], &n = now[(size_t)t];
+        if (n.bytes == 0 || std::memcmp(o.host, n.host, n.bytes) == 0) continue;
+        HIP_TRY(hipMemcpy(const_cast<void *>(n.dev), n.host, n.bytes, hipMemcpyHostToDevice));
+    }
+    adopt_materials(s, a, &M);
+    if (out_rebuilt) *out_rebuilt = 0;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_scene_set_materials_stream(rtmi_scene *s, int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
+                                                int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
+                                                const int32_t *prim_mat, void *stream) {
+    SceneArrays a;
+    PackedMaterials M;
+    int rc = prepare_material_edit(s, n_mats, mat_kind, mat_tex, mat_param, n_tex, tex_kind, tex_param, tex_child, prim_mat, a, M);
+    if (rc) return rc;
+    std::string why;
+    if (!materials_fit(s, a, M, &why))
+        return fail(RTMI_E_UNSUPPORTED, "%s: rtmi_scene_set_materials rebuilds the scene for such an edit, the stream form does not", why.c_str());
+    // the rows that differ from the mirror, batched into launches
+    const auto was = material_tables(s->mat, s->dev), now = material_tables(M, s->dev);
+    std::vector<PatchArgs> batches;
+    size_t payload = 0;
+    int words_used = 0;
+    for (int t = 0; t < kMatTables; ++t) {
+        const MatTable &o = was[(size_t)t], &n = now[(size_t)t];
+        const char *ob = (const char *)o.host, *nb = (const char *)n.host;
+        for (size_t off = 0; off + n.row <= n.bytes; off += n.row) {
+            if (std::memcmp(ob + off, nb + off, n.row) == 0) continue;
+            payload += n.row;
+            if (payload > RTMI_EDIT_STREAM_MAX_BYTES)
+                return fail(RTMI_E_UNSUPPORTED, "the edit changes more than RTMI_EDIT_STREAM_MAX_BYTES = %d bytes of table rows: rtmi_scene_set_materials copies whole tables, "
+                                                "the stream form is for the few records an interactive edit touches", RTMI_EDIT_STREAM_MAX_BYTES);
+            const int nw = (int)(n.row / 4);
+            if (batches.empty() || batches.back().n_rows == kPatchRows || words_used + nw > kPatchWords) {
+                batches.emplace_back();
+                std::memset(&batches.back(), 0, sizeof(PatchArgs));
+                words_used = 0;
+            }
+            PatchArgs &b = batches.back();
+            PatchRow &r = b.row[b.n_rows++];
+            r.dst = reinterpret_cast<unsigned *>(const_cast<char *>((const char *)n.dev + off));
+            r.src = (unsigned short)words_used; r.n = (unsigned short)nw;
+            std::memcpy(&b.word[words_used], nb + off, n.row);
+            words_used += nw;
+        }
+    }
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = stream ? (hipStream_t)stream : s->ctx->stream;
+    for (const PatchArgs &b : batches) {
+        hipLaunchKernelGGL(set_materials_kernel, dim3(1), dim3(64), 0, st, b);
+        HIP_TRY(hipGetLastError());
+    }
+    adopt_materials(s, a, &M); // at once, like the camera's mirror: the render checks (Perlin table, images) of the calls queued behind the kernel read it
+    return RTMI_OK;
+}
+
+// test hook, host code only (no device): the eleven material tables of the given arrays as rtmi_scene_set_materials* packs them (through_creation = 0: only the
+// primitive kinds and materials and the material and texture tables are read, the other arrays may be NULL) or as rtmi_scene_create_ex does (1: through its
+// checks and pack_scene).  out_hash = FNV-1a of the tables, out_facts = {the materials' share of has_ext, uses_perlin, max_image}
+RTMI_EXPORT int rtmi_test_pack_materials(int32_t n_prims, const int32_t *prim_kind, const double *prim_geom, const int32_t *prim_mat,
+                                         int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
+                                         int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
+                                         int32_t cam_kind, const double *cam, const int32_t *prim_flip, const int32_t *prim_xform,
+                                         int32_t n_xforms, const int32_t *xform_kind, const double *xform_param, int32_t through_creation,
+                                         uint64_t *out_hash, int32_t *out_facts) {
+    if (!out_hash || !out_facts) return fail(RTMI_E_ARG, "bad arguments");
+    const SceneArrays a{n_prims, prim_kind, prim_geom, prim_mat, n_mats, mat_kind, mat_tex, mat_param, n_tex, tex_kind, tex_param, tex_child,
+                        cam_kind, cam, prim_flip, prim_xform, n_xforms, xform_kind, xform_param};
+    PackedMaterials M;
+    if (through_creation) {
+        rtmi_scene *none = nullptr;
+        const int rc = check_scene_args(a, &none);
+        if (rc) return rc;
+        M = pack_scene(a, read_build_knobs()).M;
+    } else {
+        int rc = check_material_arrays(n_mats, mat_kind, mat_tex, mat_param, n_tex, tex_kind, tex_param, tex_child);
+        if (!rc && (n_prims < 0 || (n_prims > 0 && (!prim_kind || !prim_mat)))) rc = fail(RTMI_E_ARG, "primitive arrays are NULL");
+        if (!rc) rc = check_material_edit(a);
+        if (rc) return rc;
+        M = pack_materials(a);
+    }
+    uint64_t h = 1469598103934665603ull;
+    DevScene none{};
+    for (const MatTable &t : material_tables(M, none)) {
+        const unsigned char *q = (const unsigned char *)t.host;
+        for (size_t k = 0; k < t.bytes; ++k) { h ^= q[k]; h *= 1099511628211ull; }
+        h ^= (uint64_t)t.bytes; h *= 1099511628211ull;
+    }
+    *out_hash = h;
+    out_facts[0] = M.has_ext ? 1 : 0; out_facts[1] = M.uses_perlin ? 1 : 0; out_facts[2] = M.max_image;
     return RTMI_OK;
 }
 

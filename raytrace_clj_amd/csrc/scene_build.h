@@ -620,16 +620,28 @@ struct SceneArrays {
     int n_xforms; const int32_t *xform_kind; const double *xform_param;
 };
 
+// The material half of a scene: the eleven device tables that read the materials, the textures and their assignment to the primitives (each named after its
+// DevScene field), and the three host facts that depend on them.  pack_materials builds it -- for pack_scene, and for rtmi_scene_set_materials*, which
+// rewrites these tables where they lie: one packer, so an edited scene holds the bytes a fresh one would.  Everything else of a scene reads geometry only.
+struct PackedMaterials {
+    std::vector<double> mat_rec, mat_grad, mat_param, tex_param;
+    std::vector<int> prim_kind, prim_km, prim_mat, mat_kind, mat_tex, tex_kind, tex_child;
+    bool has_ext = false; // the materials' share of DevScene::has_ext: a section 8(f4) texture, or a primitive whose material is Isotropic
+    bool uses_perlin = false;
+    int max_image = -1;
+};
+
 // What a scene uploads, as host tables (each named after its DevScene field), plus what rtmi_scene keeps on the host.
 struct PackedScene {
     DevScene d{}; // scalar fields; the table pointers stay null until the upload
-    std::vector<double> stat_geom, stat4_d, exact12, ext_xf, leaf_rec, mov_geom, mat_rec, mat_grad, mat_param, tex_param;
+    std::vector<double> stat_geom, stat4_d, exact12, ext_xf, leaf_rec, mov_geom;
     std::vector<float> stat4_f, bvh_nodes, cull20;
-    std::vector<int> stat_orig, grid_cells, moving_all, ext_info, mov_orig, prim_kind, prim_km, prim_mat, mat_kind, mat_tex, tex_kind, tex_child;
+    std::vector<int> stat_orig, grid_cells, moving_all, ext_info, mov_orig;
+    PackedMaterials M;
     std::vector<int> host_kind; // primitive kinds, boundary flag removed
     std::map<int, std::array<double, 5>> media_fast_of;
-    int bvh_node_count = 0, bvh_depth = 0, max_image = -1;
-    bool uses_perlin = false;
+    int bvh_node_count = 0, bvh_depth = 0;
+    bool geom_ext = false; // the geometry's share of DevScene::has_ext: a primitive the sphere kernels do not hold (d.has_ext = geom_ext || M.has_ext)
     double t_tree0 = 0.0, t_tree1 = 0.0; // now_ms() around the tree build (RTMI_DEBUG)
 };
 
@@ -689,6 +701,75 @@ inline void camera_shutter(int cam_kind, const double *cam, double &t_lo, double
     t_hi = cam_kind == RTMI_CAM_THINLENS ? std::max(cam[22], cam[23]) : 0.0;
 }
 
+// The material half of pack_scene.  Of `a` it reads the primitive count, kinds and materials and the material and texture tables -- no geometry, no camera.
+PackedMaterials pack_materials(const SceneArrays &a) {
+    PackedMaterials M;
+    const int n_prims = a.n_prims;
+    for (int t = 0; t < a.n_tex; ++t) {
+        if (a.tex_kind[t] > RTMI_TEX_CHECKER) M.has_ext = true; // section 8(f4) textures live in the EXT kernels only
+        if (a.tex_kind[t] >= RTMI_TEX_PERLIN_NOISE && a.tex_kind[t] <= RTMI_TEX_MARBLE) M.uses_perlin = true;
+        if (a.tex_kind[t] == RTMI_TEX_IMAGE) M.max_image = std::max(M.max_image, (int)a.tex_param[(size_t)t * RTMI_TEX_STRIDE]);
+    }
+    for (int i = 0; i < n_prims; ++i)
+        if (a.mat_kind[a.prim_mat[i]] == RTMI_MAT_ISOTROPIC) M.has_ext = true; // Isotropic.scatter (shader.clj:129-138) is compiled into the EXT kernels only
+    // device copy of prim_kind: + RTMI_PRIM_NEEDS_U / _V where a UVSphere's material texture reads that coordinate; + RTMI_PRIM_NEEDS_UV where a rectangle's or
+    // a triangle's does (its uv is two IEEE divisions per hit (hitable.clj:283-284), a triangle's a second Moeller-Trumbore: computed only where the material's
+    // texture reads uv at all -- both coordinates then: no coordinate is ever replaced here, so nothing deviates --; a Cornell box's walls never do)
+    const std::vector<char> uses = texture_uv_use(a);
+    M.prim_mat.assign(a.prim_mat, a.prim_mat + n_prims);
+    M.prim_kind.resize((size_t)n_prims);
+    for (int i = 0; i < n_prims; ++i) {
+        const int kind = a.prim_kind[i] & ~RTMI_PRIM_BOUNDARY;
+        M.prim_kind[(size_t)i] = kind;
+        const int m = M.prim_mat[(size_t)i], t = (m >= 0 && m < a.n_mats) ? a.mat_tex[m] : -1;
+        if (kind == RTMI_PRIM_UVSPHERE) {
+            const int bits = (t < 0 || t >= a.n_tex) ? 3 : uses[(size_t)t];
+            if (bits & 1) M.prim_kind[(size_t)i] |= RTMI_PRIM_NEEDS_U;
+            if (bits & 2) M.prim_kind[(size_t)i] |= RTMI_PRIM_NEEDS_V;
+        } else if (kind >= RTMI_PRIM_RECT_XY && kind <= RTMI_PRIM_TRIANGLE) {
+            if (t < 0 || t >= a.n_tex || uses[(size_t)t]) M.prim_kind[(size_t)i] |= RTMI_PRIM_NEEDS_UV;
+        }
+    }
+    M.prim_km.assign((size_t)std::max(n_prims, 1) * 2, 0);
+    for (int i = 0; i < n_prims; ++i) { M.prim_km[2 * (size_t)i] = M.prim_kind[(size_t)i]; M.prim_km[2 * (size_t)i + 1] = M.prim_mat[(size_t)i]; }
+    // MatRec (rtmi_device.h) of every material, and the four corner colours of those whose texture is a UVGradient
+    M.mat_rec.assign((size_t)std::max(a.n_mats, 1) * 12, 0.0);
+    M.mat_grad.assign((size_t)std::max(a.n_mats, 1) * 12, 0.0);
+    for (int m = 0; m < a.n_mats; ++m) {
+        MatRec r;
+        std::memset(&r, 0, sizeof(r));
+        r.mat_kind = a.mat_kind[m]; r.tex = a.mat_tex[m]; r.param = a.mat_param[m];
+        if (a.mat_kind[m] == RTMI_MAT_DIELECTRIC) { // one IEEE operation each, as the kernel would evaluate them per scatter
+            const volatile double ri = a.mat_param[m];
+            const volatile double inv = 1.0 / ri, num = 1.0 - ri, den = 1.0 + ri;
+            const volatile double q = num / den;
+            const volatile double r0 = q * q;
+            r.inv_ri = inv; r.r0 = r0;
+        }
+        r.tex_kind = (r.tex >= 0 && r.tex < a.n_tex) ? a.tex_kind[r.tex] : -1;
+        if (r.tex_kind == RTMI_TEX_CONSTANT) { const double *tp = a.tex_param + (size_t)r.tex * RTMI_TEX_STRIDE; r.r = tp[0]; r.g = tp[1]; r.b = tp[2]; }
+        if (r.tex_kind == RTMI_TEX_UVGRADIENT) { // texture.clj:26-34: co cu cv cuv travel with the material
+            std::memcpy(&M.mat_grad[(size_t)m * 12], a.tex_param + (size_t)r.tex * RTMI_TEX_STRIDE, 12 * sizeof(double));
+            r.tex_kind = RTMI_TEX_GRADIENT_REC;
+        }
+        if (r.tex_kind == RTMI_TEX_CHECKER) { // both children Constant: the whole texture fits the record
+            const int c0 = a.tex_child[2 * (size_t)r.tex], c1 = a.tex_child[2 * (size_t)r.tex + 1];
+            if (c0 >= 0 && c0 < a.n_tex && c1 >= 0 && c1 < a.n_tex && a.tex_kind[c0] == RTMI_TEX_CONSTANT && a.tex_kind[c1] == RTMI_TEX_CONSTANT) {
+                const double *t0 = a.tex_param + (size_t)c0 * RTMI_TEX_STRIDE, *t1 = a.tex_param + (size_t)c1 * RTMI_TEX_STRIDE;
+                r.tex_kind = RTMI_TEX_CHECKER2;
+                r.scale = a.tex_param[(size_t)r.tex * RTMI_TEX_STRIDE];
+                r.r = t0[0]; r.g = t0[1]; r.b = t0[2]; r.c1r = t1[0]; r.c1g = t1[1]; r.c1b = t1[2];
+            }
+        }
+        static_assert(sizeof(MatRec) == 96, "MatRec is twelve doubles");
+        std::memcpy(&M.mat_rec[(size_t)m * 12], &r, sizeof(r));
+    }
+    M.mat_kind.assign(a.mat_kind, a.mat_kind + a.n_mats); M.mat_tex.assign(a.mat_tex, a.mat_tex + a.n_mats); M.mat_param.assign(a.mat_param, a.mat_param + a.n_mats);
+    M.tex_kind.assign(a.tex_kind, a.tex_kind + a.n_tex); M.tex_child.assign(a.tex_child, a.tex_child + 2 * (size_t)a.n_tex);
+    M.tex_param.assign(a.tex_param, a.tex_param + (size_t)a.n_tex * RTMI_TEX_STRIDE);
+    return M;
+}
+
 // The caller's (checked) arrays -> every device table of the scene, in host memory.  Pure host code: the same arrays and knobs give the same bytes.
 PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
     PackedScene P;
@@ -696,13 +777,8 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
     std::memset(&d, 0, sizeof d); // (padding included: the descriptor is uploaded as bytes)
     const int n_prims = a.n_prims;
     const double *cam = a.cam;
-    bool has_ext = false;
+    P.M = pack_materials(a);
     int n_world = 0, n_media = 0, media[16];
-    for (int t = 0; t < a.n_tex; ++t) {
-        if (a.tex_kind[t] > RTMI_TEX_CHECKER) has_ext = true; // section 8(f4) textures live in the EXT kernels only
-        if (a.tex_kind[t] >= RTMI_TEX_PERLIN_NOISE && a.tex_kind[t] <= RTMI_TEX_MARBLE) P.uses_perlin = true;
-        if (a.tex_kind[t] == RTMI_TEX_IMAGE) P.max_image = std::max(P.max_image, (int)a.tex_param[(size_t)t * RTMI_TEX_STRIDE]);
-    }
     d.n_tex = a.n_tex; d.cam_kind = a.cam_kind;
     std::memcpy(d.cam, cam, 24 * sizeof(double));
     d.cam_fixed_origin = camera_fixed_origin(a.cam_kind, cam);
@@ -732,16 +808,15 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
         P.ext_info.insert(P.ext_info.end(), info, info + 4);
         pk[(size_t)i] = kind;
         if (!is_boundary) n_world = i + 1;
-        if (a.mat_kind[a.prim_mat[i]] == RTMI_MAT_ISOTROPIC) has_ext = true; // Isotropic.scatter (shader.clj:129-138) is compiled into the EXT kernels only
         if (kind == RTMI_PRIM_MEDIUM) { // not a surface: no box, a neutral cull entry (ext_prim_test ignores it), evaluated by ext_medium_test
             media[n_media++] = i;
-            has_ext = true;
+            P.geom_ext = true;
             P.exact12.insert(P.exact12.end(), {g[0], g[1], g[2], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0});
             cull.insert(cull.end(), {0.0f, 0.0f, 0.0f, 0.0f, 0.0f});
             continue;
         }
         const bool sphere_kernels = !is_boundary && kind <= RTMI_PRIM_MOVING && xf_count == 0 && !(a.prim_flip && a.prim_flip[i]);
-        if (!sphere_kernels) has_ext = true;
+        if (!sphere_kernels) P.geom_ext = true;
         bounded[(size_t)i] = prim_world_box(kind, g, a.xform_kind, a.xform_param, xf_first, xf_count, t_lo, t_hi, wbox[(size_t)i]);
         const bool moving = kind == RTMI_PRIM_MOVING;
         const volatile double r2d = g[3] * g[3];
@@ -805,6 +880,7 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
         cull.insert(cull.end(), {cf[0], cf[1], cf[2], unbounded ? 3.0e38f : (float)std::min(r2b * (moving ? 1.0 + 1e-6 : 1.0), 3.0e38), (float)w});
     }
     d.n_static = (int)P.stat_orig.size(); d.n_moving = (int)P.mov_orig.size();
+    const bool has_ext = P.geom_ext || P.M.has_ext;
     pad_last(P.stat4_d, 4); // (see scan_static_pipe)
     pad_last(P.stat4_f, 4);
     // Box = six consecutive rectangles RectXY z1, RectXY z0, RectXZ y1, RectXZ y0, RectYZ x1, RectYZ x0 over one (x0 y0 z0) - (x1 y1 z1) and one instance
@@ -879,59 +955,6 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
         std::memcpy(q, hdr, sizeof hdr);
     }
     P.ext_info.insert(P.ext_info.end(), {RTMI_PRIM_MEDIUM, 0, 0, 0}); // one record past the end: scan_small_ext requests primitive i + 1's records while it tests primitive i
-    // device copy of prim_kind: + RTMI_PRIM_NEEDS_U / _V where a UVSphere's material texture reads that coordinate; + RTMI_PRIM_NEEDS_UV where a rectangle's or
-    // a triangle's does (its uv is two IEEE divisions per hit (hitable.clj:283-284), a triangle's a second Moeller-Trumbore: computed only where the material's
-    // texture reads uv at all -- both coordinates then: no coordinate is ever replaced here, so nothing deviates --; a Cornell box's walls never do)
-    const std::vector<char> uses = texture_uv_use(a);
-    P.prim_mat.assign(a.prim_mat, a.prim_mat + n_prims);
-    P.prim_kind = pk;
-    for (int i = 0; i < n_prims; ++i) {
-        const int m = P.prim_mat[(size_t)i], t = (m >= 0 && m < a.n_mats) ? a.mat_tex[m] : -1;
-        if (pk[(size_t)i] == RTMI_PRIM_UVSPHERE) {
-            const int bits = (t < 0 || t >= a.n_tex) ? 3 : uses[(size_t)t];
-            if (bits & 1) P.prim_kind[(size_t)i] |= RTMI_PRIM_NEEDS_U;
-            if (bits & 2) P.prim_kind[(size_t)i] |= RTMI_PRIM_NEEDS_V;
-        } else if (pk[(size_t)i] >= RTMI_PRIM_RECT_XY && pk[(size_t)i] <= RTMI_PRIM_TRIANGLE) {
-            if (t < 0 || t >= a.n_tex || uses[(size_t)t]) P.prim_kind[(size_t)i] |= RTMI_PRIM_NEEDS_UV;
-        }
-    }
-    P.prim_km.assign((size_t)std::max(n_prims, 1) * 2, 0);
-    for (int i = 0; i < n_prims; ++i) { P.prim_km[2 * (size_t)i] = P.prim_kind[(size_t)i]; P.prim_km[2 * (size_t)i + 1] = P.prim_mat[(size_t)i]; }
-    // MatRec (rtmi_device.h) of every material, and the four corner colours of those whose texture is a UVGradient
-    P.mat_rec.assign((size_t)std::max(a.n_mats, 1) * 12, 0.0);
-    P.mat_grad.assign((size_t)std::max(a.n_mats, 1) * 12, 0.0);
-    for (int m = 0; m < a.n_mats; ++m) {
-        MatRec r;
-        std::memset(&r, 0, sizeof(r));
-        r.mat_kind = a.mat_kind[m]; r.tex = a.mat_tex[m]; r.param = a.mat_param[m];
-        if (a.mat_kind[m] == RTMI_MAT_DIELECTRIC) { // one IEEE operation each, as the kernel would evaluate them per scatter
-            const volatile double ri = a.mat_param[m];
-            const volatile double inv = 1.0 / ri, num = 1.0 - ri, den = 1.0 + ri;
-            const volatile double q = num / den;
-            const volatile double r0 = q * q;
-            r.inv_ri = inv; r.r0 = r0;
-        }
-        r.tex_kind = (r.tex >= 0 && r.tex < a.n_tex) ? a.tex_kind[r.tex] : -1;
-        if (r.tex_kind == RTMI_TEX_CONSTANT) { const double *tp = a.tex_param + (size_t)r.tex * RTMI_TEX_STRIDE; r.r = tp[0]; r.g = tp[1]; r.b = tp[2]; }
-        if (r.tex_kind == RTMI_TEX_UVGRADIENT) { // texture.clj:26-34: co cu cv cuv travel with the material
-            std::memcpy(&P.mat_grad[(size_t)m * 12], a.tex_param + (size_t)r.tex * RTMI_TEX_STRIDE, 12 * sizeof(double));
-            r.tex_kind = RTMI_TEX_GRADIENT_REC;
-        }
-        if (r.tex_kind == RTMI_TEX_CHECKER) { // both children Constant: the whole texture fits the record
-            const int c0 = a.tex_child[2 * (size_t)r.tex], c1 = a.tex_child[2 * (size_t)r.tex + 1];
-            if (c0 >= 0 && c0 < a.n_tex && c1 >= 0 && c1 < a.n_tex && a.tex_kind[c0] == RTMI_TEX_CONSTANT && a.tex_kind[c1] == RTMI_TEX_CONSTANT) {
-                const double *t0 = a.tex_param + (size_t)c0 * RTMI_TEX_STRIDE, *t1 = a.tex_param + (size_t)c1 * RTMI_TEX_STRIDE;
-                r.tex_kind = RTMI_TEX_CHECKER2;
-                r.scale = a.tex_param[(size_t)r.tex * RTMI_TEX_STRIDE];
-                r.r = t0[0]; r.g = t0[1]; r.b = t0[2]; r.c1r = t1[0]; r.c1g = t1[1]; r.c1b = t1[2];
-            }
-        }
-        static_assert(sizeof(MatRec) == 96, "MatRec is twelve doubles");
-        std::memcpy(&P.mat_rec[(size_t)m * 12], &r, sizeof(r));
-    }
-    P.mat_kind.assign(a.mat_kind, a.mat_kind + a.n_mats); P.mat_tex.assign(a.mat_tex, a.mat_tex + a.n_mats); P.mat_param.assign(a.mat_param, a.mat_param + a.n_mats);
-    P.tex_kind.assign(a.tex_kind, a.tex_kind + a.n_tex); P.tex_child.assign(a.tex_child, a.tex_child + 2 * (size_t)a.n_tex);
-    P.tex_param.assign(a.tex_param, a.tex_param + (size_t)a.n_tex * RTMI_TEX_STRIDE);
     for (int k = 0; k < n_media; ++k) { // media whose boundary is one plain sphere, neither under wrappers: their operands go into the descriptor (media_fast)
         const int m = media[k];
         const int fb = (int)a.prim_geom[(size_t)m * RTMI_PRIM_STRIDE + 1], nb = (int)a.prim_geom[(size_t)m * RTMI_PRIM_STRIDE + 2];

@@ -157,6 +157,28 @@ class MultiDevice:
         """DeviceScene.set_camera (the host form) on every replica -> True if any replica rebuilt its trees (they all do, or none)"""
         return any([s.set_camera(camera) for s in self.scenes])
 
+    def set_materials(self, scene_or_flat):
+        """DeviceScene.set_materials (the host form) on every replica -> True if the replicas rebuilt (they all do, or none).  The argument
+        and fit checks of ALL replicas run before the first write: a bad edit raises and leaves every replica as it was."""
+        from . import flatten as fl
+        f = scene_or_flat if isinstance(scene_or_flat, fl.FlatScene) else fl.flatten(scene_or_flat)
+        for s in self.scenes:
+            if len(f.prim_mat) != len(s.flat.prim_kind):
+                raise ValueError("the edit has %d primitives, the scene %d" % (len(f.prim_mat), len(s.flat.prim_kind)))
+        # the replicas are clones: they hold the same arrays, so the library's checks (creation's, on the scene's arrays with the edit in their
+        # place) and its fit decision give one answer for all of them.  The host-only hook runs those checks without touching a scene.
+        import numpy as np
+        g = self.scenes[0].flat
+        arrs = [np.ascontiguousarray(a, dt) for a, dt in (
+            (g.prim_kind, np.int32), (f.prim_mat, np.int32), (f.mat_kind, np.int32), (f.mat_tex, np.int32), (f.mat_param, np.float64),
+            (f.tex_kind, np.int32), (f.tex_param, np.float64), (f.tex_child, np.int32))]
+        pk, pm, mk, mt, mp, tk, tp, tc = arrs
+        h, facts = np.zeros(1, np.uint64), np.zeros(3, np.int32)
+        p = _ffi.ptr
+        check(_ffi.lib().rtmi_test_pack_materials(len(pk), p(pk), None, p(pm), len(mk), p(mk), p(mt), p(mp), len(tk), p(tk), p(tp), p(tc),
+                                                  0, None, None, None, 0, None, None, 0, p(h), p(facts)))
+        return any([s.set_materials(f) for s in self.scenes])
+
     def render(self, nx, ny, ns, depth=50, seed=0x5EED0002, precision="f64"):
         """host buffers: (linear [ny,nx,3] float64, rgb8, counters)"""
         import numpy as np
