@@ -377,6 +377,28 @@
                      (:prim-mat e) rebuilt))
     (= 1 (aget rebuilt 0))))
 
+(defn set-geometry
+  "Move the primitives of the live scene `scn` (the Pointer create-scene! returned for the flattened scene `flat`) without a new scene:
+  `edited` is a scene {:camera :world} with the same structure, or its flatten-scene map; its primitive geometry and the parameters of its
+  Translate / RotateY records replace the scene's, the materials and the camera stay.  Every result afterwards is, bit for bit, that of a
+  scene created from the edited arrays; the device refits the trees it has.  Counts, kinds, flips and the instance structure are not
+  editable (ex-info).  :rebuild true asks for a fresh tree.  Returns {:rebuilt :displaced :nodes-refit :launches}: whether the library
+  rebuilt the scene (the edit did not fit the built trees), how many primitives left their entry-grid cells and are now tested by every
+  ray first (a rebuild brings them home), the node records refit and the launches that took.  A progressive frame started before the call
+  is not continued (start a new one: s-first 0)."
+  [scn flat edited & {:keys [rebuild] :or {rebuild false}}]
+  (let [e    (if (contains? edited :world) (flatten-scene edited) edited)
+        info (int-array 4)]
+    (when (or (not= (:n-prims e) (:n-prims flat)) (not= (:n-xforms e) (:n-xforms flat)))
+      (throw (ex-info "set-geometry: a changed count is a new scene" {:edit [(:n-prims e) (:n-xforms e)] :scene [(:n-prims flat) (:n-xforms flat)]})))
+    (doseq [k [:prim-kind :prim-flip :prim-xform :xform-kind]]
+      (when (not= (seq (k e)) (seq (k flat)))
+        (throw (ex-info "set-geometry: kinds, flips and instance structure are not editable (a new scene)" {:array k}))))
+    (check (call-int "rtmi_scene_set_geometry" scn
+                     (int (:n-prims e)) (:prim-geom e) (int (:n-xforms e)) (:xform-param e)
+                     (int (if rebuild 1 0)) info))
+    {:rebuilt (= 1 (aget info 0)) :displaced (aget info 1) :nodes-refit (aget info 2) :launches (aget info 3)}))
+
 (defn render-materials
   "Render scene {:camera :world} once per entry of `edits` -- scenes with the same primitives, or flatten-scene maps: a colour picker, a
   material library -- from ONE device scene: the world is flattened, built and uploaded once, every entry only rewrites the material

@@ -240,6 +240,45 @@ int rtmi_scene_set_materials_stream(rtmi_scene *scene,
                                     int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
                                     int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
                                     const int32_t *prim_mat, void *stream);
+/* ---- the geometry of a live scene: a sphere dragged, a radius shrunk, a Cornell block nudged or turned, a rectangle or a triangle's vertex moved ----
+ * prim_geom is the WHOLE table, n_prims rows of RTMI_PRIM_STRIDE doubles as rtmi_scene_create_ex takes it, xform_param the whole table of n_xforms rows of three
+ * (a Translate's offset, a RotateY's sin and cos), or NULL: it stays.  STRUCTURE is not editable: the counts, the kinds (boundary flag included), prim_flip,
+ * prim_xform and xform_kind are the scene's and no arguments of this call; another n_prims or n_xforms than the scene's is RTMI_E_ARG (a changed count or kind
+ * is a new scene).  The materials and the camera are the scene's.
+ * The promise: after the call has succeeded every RESULT -- frame, 8-bit frame, standard error, samples, features, probes and the ray counter, in RTMI_F64 and
+ * RTMI_F32 -- is BIT FOR BIT that of a scene freshly created from the edited arrays with the same camera and rtmi_scene_set_* calls.  The closest hit does not
+ * depend on the tree, so the edited scene keeps the tree it has: rtmi_last_traversal_counters and rtmi_scene_tree_info describe that tree and may differ from a
+ * fresh scene's.
+ * mode 0: in place if the edit fits, else a rebuild; mode 1: always a rebuild (how a host asks for a fresh tree).  The edit FITS if
+ *   - the scene has no Box leaves and no media neighbourhood trees (the experiment knobs RTMI_BOX_LEAF, RTMI_MLOC);
+ *   - every RTMI_PRIM_MEDIUM row is bit-equal to the scene's, and no primitive changes between boundable and not (non-finite values, a MovingSphere with
+ *     time0 = time1);
+ *   - every boundable world primitive's new world box (MovingSpheres: swept over the shutter interval the scene was BUILT for) has |coordinate| <= the bound
+ *     the trees were built with (DevScene::bvh_obound), and every tree primitive's box lies within the trees' coordinate bound (bvh_cbound);
+ *   - after displacement (below) the list of big primitives, which every ray tests exactly before the tree, holds at most 16 entries.
+ * In place: the context's stream is synchronised; the geometry tables whose bytes changed (packed by the function that packs them at creation) are copied where
+ * they lie, with the descriptor if its big list or a medium's fast operands changed; then the node array is REFIT on the context's stream, topology kept:
+ * one launch of refit_kernel per node height, lowest first, every box the union of its children's (a leaf: the primitive's box rounded as the builder rounds
+ * it; the node of a tree over one primitive keeps its empty right side).  The builder's rounding is monotone, so these are the planes it would emit for the same topology over the new boxes.  The renders queued on the
+ * context's stream afterwards see the new scene; the call does not wait for the refit (a render on ANOTHER stream must: any host-form rtmi_scene_set_* call
+ * synchronises the context's stream first -- the scene's tables belong to one stream at a time).  The first in-place edit after a build allocates the refit plan (node
+ * indices by height) and one box per world primitive, counted by rtmi_scene_device_bytes; later edits allocate nothing.
+ * DISPLACEMENT: where an entry grid was built, a primitive registered in grid cells (the layer) whose new box reaches a cell it was not registered in or
+ * leaves the layer's box, and a tall primitive whose box leaves the tall primitives' box, leaves the trees -- its leaves get the empty box -- and joins the
+ * big list (kept in ascending index order): one more exact test per segment, what one dragged object costs.  It is judged against the range the BUILD gave
+ * the primitive, never against a later edit (shrinking and growing back stays home); once displaced, a primitive stays so until a rebuild; nothing is
+ * re-classified.  Scenes without a grid never displace.
+ * A rebuild goes behind the same handle like a camera's or a material edit's (the old tables serve until the swap) and forgets every displacement; so does a
+ * rebuild by rtmi_scene_set_camera or rtmi_scene_set_materials.
+ * out_info[4] (may be NULL) = rebuilt 0 / 1, displaced primitives now in the big list, node records refit, refit launches.
+ * Success always changes the scene's revision: a progressive or adaptive frame is not continued.  Errors, in this order: a negative count, a NULL prim_geom, a
+ * mode other than 0 / 1: RTMI_E_ARG; a bad handle: RTMI_E_STATE; other counts than the scene's: RTMI_E_ARG; then creation's checks of the same arrays with
+ * creation's codes (a medium's density NaN or its boundary range invalid: RTMI_E_ARG).  A failed call leaves the scene, revision included, as it was. */
+int rtmi_scene_set_geometry(rtmi_scene *scene, int32_t n_prims, const double *prim_geom, int32_t n_xforms, const double *xform_param,
+                            int32_t mode, int32_t *out_info);
+/* Device time of the refit launches of the scene's last in-place rtmi_scene_set_geometry, by events on the context's stream; waits for them.  Needs a
+ * context created with RTMI_FLAG_TIMING; RTMI_E_STATE if there is no such edit since the scene's last build. */
+int rtmi_scene_last_refit_ms(rtmi_scene *scene, double *out_ms);
 /* HBM bytes the scene occupies (everything its creation uploaded: records, tree, tables) -- bench.py's `upload_bytes` */
 int rtmi_scene_device_bytes(rtmi_scene *scene, int64_t *out_bytes);
 /* The device's tree as the scene was built with it: out_info[4] = node records, depth of the deepest leaf, entry-grid cells per side (0: no grid),
@@ -675,6 +714,28 @@ int rtmi_test_pack_materials(int32_t n_prims, const int32_t *prim_kind, const do
                              int32_t cam_kind, const double *cam, const int32_t *prim_flip, const int32_t *prim_xform,
                              int32_t n_xforms, const int32_t *xform_kind, const double *xform_param, int32_t through_creation,
                              uint64_t *out_hash, int32_t *out_facts);
+/* test hook, host code only (no device): the geometry tables of rtmi_scene_create_ex's arrays -- stat_geom, stat4_d, stat4_f, exact12, cull20, leaf_rec,
+ * ext_xf, mov_geom, media_fast_of, every primitive's bounded flag and world box -- as creation packs them (through_creation = 1) or as
+ * rtmi_scene_set_geometry packs an edit (0), both after creation's checks.  out_hash = FNV-1a of them (equal for both: one packer). */
+int rtmi_test_pack_geometry(int32_t n_prims, const int32_t *prim_kind, const double *prim_geom, const int32_t *prim_mat,
+                            int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
+                            int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
+                            int32_t cam_kind, const double *cam, const int32_t *prim_flip, const int32_t *prim_xform,
+                            int32_t n_xforms, const int32_t *xform_kind, const double *xform_param, int32_t through_creation, uint64_t *out_hash);
+/* test hook, host code only (no device): the trees of geometry 0 as creation builds them (every surface one grey Lambertian, every medium Isotropic), then steps 1 .. n_steps - 1 as
+ * rtmi_scene_set_geometry (mode 0) applies them -- the same fit and displacement rules, a rebuild where a step does not fit -- with the refit done by the
+ * host's reference of refit_kernel's rule.  geoms[n_steps][n_prims][RTMI_PRIM_STRIDE], xforms[n_steps][n_xforms][3] (NULL with n_xforms = 0).  The state
+ * after the last step: out_nodes (if *out_bytes <= capacity) the node array, out_info[10] = node16, bvh_root, grid_tall, grid cells per side, n_big,
+ * displaced, rebuilt by the last step, node records, refit launches, steps that rebuilt since step 0; out_big[16] (may be NULL) the big list; out_cells
+ * (may be NULL) up to cells_capacity of the grid's 4 G G root codes; out_leaf_box (may be NULL) [n_world][6] floats lo.xyz hi.xyz, the leaf boxes of the last
+ * in-place step ((+inf, -inf): not in the trees). */
+int rtmi_test_refit(int32_t n_prims, const int32_t *prim_kind, const int32_t *prim_flip, const int32_t *prim_xform, int32_t n_xforms, const int32_t *xform_kind,
+                    int32_t cam_kind, const double *cam, int32_t n_steps, const double *geoms, const double *xforms,
+                    void *out_nodes, int64_t capacity, int64_t *out_bytes, int32_t *out_info, int32_t *out_big,
+                    int32_t *out_cells, int64_t cells_capacity, void *out_leaf_box);
+int rtmi_test_refit_half(double x, int32_t up); /* rtmi_test_half_outward by the integer form the refit uses on the device */
+/* test hook: the scene's node array as it lies in HBM, after the work queued on the context's stream; *out_bytes = its size, copied if <= capacity */
+int rtmi_test_scene_nodes(rtmi_scene *scene, void *buf, int64_t capacity, int64_t *out_bytes);
 
 #ifdef __cplusplus
 }

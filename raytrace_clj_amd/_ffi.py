@@ -35,6 +35,7 @@ SYMBOLS = [
     "rtmi_reproject", "rtmi_reproject_device",
     "rtmi_scene_tree_info",
     "rtmi_scene_set_materials", "rtmi_scene_set_materials_stream", "rtmi_test_pack_materials",
+    "rtmi_scene_set_geometry", "rtmi_scene_last_refit_ms", "rtmi_test_pack_geometry", "rtmi_test_refit", "rtmi_test_refit_half", "rtmi_test_scene_nodes",
 ]
 
 F64, F32 = 0, 1
@@ -139,6 +140,12 @@ def lib():
     L.rtmi_scene_set_materials.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, C.POINTER(i32)]
     L.rtmi_scene_set_materials_stream.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.rtmi_test_pack_materials.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
+    L.rtmi_scene_set_geometry.argtypes = [vp, i32, vp, i32, vp, i32, vp]
+    L.rtmi_scene_last_refit_ms.argtypes = [vp, C.POINTER(dbl)]
+    L.rtmi_test_pack_geometry.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp]
+    L.rtmi_test_refit.argtypes = [i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
+    L.rtmi_test_refit_half.argtypes = [C.c_double, i32]
+    L.rtmi_test_scene_nodes.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.rtmi_reproject.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 5
     L.rtmi_reproject_device.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 6
     for name in SYMBOLS:

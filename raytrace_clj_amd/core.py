@@ -347,6 +347,54 @@ class DeviceScene:
         self.flat = flat
         return bool(rebuilt.value)
 
+    # ---- the geometry of the live scene (rtmi_scene_set_geometry): primitives moved without a new scene ----------------------------------
+    def _geometry_arrays(self, scene_or_flat):
+        """the edit's prim_geom and xform_param, after the structure checks: ValueError unless counts, kinds, flips and instance chains are the scene's"""
+        f = scene_or_flat if isinstance(scene_or_flat, fl.FlatScene) else fl.flatten(scene_or_flat)
+        g = self.flat
+        if len(f.prim_kind) != len(g.prim_kind):
+            raise ValueError("the edit has %d primitives, the scene %d: a changed count is a new scene" % (len(f.prim_kind), len(g.prim_kind)))
+        xk_f, xk_g = np.asarray(getattr(f, "xform_kind", np.zeros(0)), np.int32), np.asarray(getattr(g, "xform_kind", np.zeros(0)), np.int32)
+        if len(xk_f) != len(xk_g):
+            raise ValueError("the edit has %d instance records, the scene %d: a changed count is a new scene" % (len(xk_f), len(xk_g)))
+        n = len(g.prim_kind)
+        for name, shape in (("prim_kind", (n,)), ("prim_flip", (n,)), ("prim_xform", (n, 2)), ("xform_kind", (len(xk_g),))):
+            a = np.asarray(getattr(f, name, np.zeros(shape)), np.int32).reshape(shape)
+            b = np.asarray(getattr(g, name, np.zeros(shape)), np.int32).reshape(shape)
+            if not np.array_equal(a, b):
+                raise ValueError("the edit's %s differs from the scene's: kinds, flips and instance structure are not editable (a new scene)" % name)
+        pg = np.ascontiguousarray(f.prim_geom, np.float64).reshape(n, -1)
+        xp = np.ascontiguousarray(getattr(f, "xform_param", np.zeros((0, 3))), np.float64).reshape(-1, 3)
+        return pg, xp
+
+    def set_geometry(self, scene_or_flat, mode="auto"):
+        """Move the live scene's primitives: a FlatScene, or a scene (flattened here; its camera and materials are not read) with the same
+        structure -> info = {"rebuilt", "displaced", "nodes_refit", "launches"}.  Its prim_geom and xform_param replace the scene's.  Every
+        result afterwards (frames, features, probes, ray counter) equals, bit for bit, that of a scene created fresh from the edited arrays; the
+        tree keeps its topology and is refit on the device, so the traversal counters and tree_info() may differ.  mode "auto": in place if
+        the edit fits the built trees (see rtmi.h), else a rebuild behind the same handle; "rebuild": always a fresh tree.  A primitive that
+        leaves the entry-grid cells it was built into is displaced into the list of primitives every ray tests first ("displaced": how many
+        are there now); a rebuild brings them home.  ValueError, before the library is touched, if counts, kinds, flips or the instance
+        structure differ.  self.flat is replaced by a copy that holds the new arrays (clones share the old one and keep it)."""
+        import copy
+        if mode not in ("auto", "rebuild"):
+            raise ValueError("mode must be 'auto' or 'rebuild'")
+        pg, xp = self._geometry_arrays(scene_or_flat)
+        info = np.zeros(4, np.int32)
+        check(_ffi.lib().rtmi_scene_set_geometry(self.handle, len(pg), ptr(pg), len(xp), ptr(xp) if len(xp) else None, 1 if mode == "rebuild" else 0, ptr(info)))
+        flat = copy.copy(self.flat)
+        flat.prim_geom = pg.copy()
+        if len(xp):
+            flat.xform_param = xp.copy()
+        self.flat = flat
+        return {"rebuilt": bool(info[0]), "displaced": int(info[1]), "nodes_refit": int(info[2]), "launches": int(info[3])}
+
+    def last_refit_ms(self):
+        """device time of the refit launches of the last in-place set_geometry (a Context(timing=True); waits for them)"""
+        ms = C.c_double()
+        check(_ffi.lib().rtmi_scene_last_refit_ms(self.handle, C.byref(ms)))
+        return ms.value
+
     def camera_info(self):
         """-> {"cam_kind", "cam" (24 doubles), "built_t_lo", "built_t_hi"}: the camera the scene renders with now and the shutter interval its
         trees were built for (a camera whose interval lies inside it never rebuilds).  Host state only."""
@@ -621,14 +669,16 @@ class TemporalAccumulator:
         self.steps = getattr(self, "steps", 0)
         self.raw_rgb8 = self.accumulated = None
 
-    def step(self, camera, nx=None, ny=None, precision=None, materials=None):
+    def step(self, camera, nx=None, ny=None, precision=None, materials=None, geometry=None):
         """-> (linear [ny,nx,3], rgb8, stderr [ny,nx], weight [ny,nx] = samples behind every pixel, share of the pixels that took history): device
         tensors owned by the accumulator -- rgb8 is overwritten by the next step, the others by the one after it -- filtered if denoise= was
         given (then .accumulated holds the unfiltered four).  .raw_rgb8 is the 8-bit frame of this view's ns samples alone, .rays its
         {total-rays, total-pixels}.
         materials= (a FlatScene or scene, as DeviceScene.set_materials takes it) edits the scene's materials in stream order before this frame
         (the stream form: an edit that would rebuild raises RtmiError -3 before anything is queued).  Such a step starts WITHOUT history
-        (share 0), like the first: the colours accumulated so far describe other surfaces.  The step after it takes history again."""
+        (share 0), like the first: the colours accumulated so far describe other surfaces.  The step after it takes history again.
+        geometry= (as DeviceScene.set_geometry takes it, mode "auto") moves the scene's primitives before this frame; that step starts without
+        history too: the reprojection assumes a static world."""
         import torch
         nx, ny, precision = nx or self.nx, ny or self.ny, precision or self.precision
         if (nx, ny, precision) != (self.nx, self.ny, self.precision):
@@ -636,13 +686,16 @@ class TemporalAccumulator:
         ds, ctx, dev = self.scene, self.scene.ctx, torch.device("cuda", self.scene.ctx.device)
         cam_pair = _camera_pair(camera)
         old, new = self._cur, 1 - self._cur
-        first = self._cam is None or materials is not None
+        first = self._cam is None or materials is not None or geometry is not None
         if first:
             self._w[new].fill_(float(self.ns))
         torch.cuda.synchronize(dev)  # (the allocator or the fill ran on torch's stream; nothing of torch's is queued after this)
         seed = self.seed + self.steps
         lin, se = (self._lin[new], self._se[new]) if first else (self._cur_lin, self._cur_se)
         st = self.stream or None
+        if geometry is not None:
+            ds.set_geometry(geometry)  # the refit is queued on the context's stream ...
+            ds.set_camera(cam_pair)    # ... which the camera's host form waits for: this frame may render on another stream
         if materials is not None:
             ds.set_materials(materials, stream=self.stream)
         ds.set_camera(cam_pair, stream=self.stream)

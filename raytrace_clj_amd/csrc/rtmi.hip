@@ -1452,6 +1452,21 @@ struct rtmi_scene {
     std::map<int, std::array<double, 5>> media_fast_of; // medium primitive -> {density, c.xyz, r*r} when it and its boundary are one plain sphere without wrappers (DevScene::media_fast)
     PackedMaterials mat;   // host copy of the eleven material tables as they lie in HBM: what rtmi_scene_set_materials_stream compares an edit with, row by row
     bool geom_ext = false; // the geometry's share of dev.has_ext (PackedScene::geom_ext): an edit of the materials fits if it leaves dev.has_ext as it is
+    TreeBuild tree;        // what the trees in HBM were built with: rtmi_scene_set_geometry judges every edit against it
+    // rtmi_scene_set_geometry: made by the first edit after a build, dropped by every rebuild (whoever asked for it)
+    struct GeoEdit {
+        bool ready = false;
+        PackedScene tab;             // host copy of the geometry tables as they lie in HBM (P.d, P.M and the trees are not used)
+        GeomExtras X;                // ... and the world boxes they were packed with
+        std::vector<char> displaced; // per world primitive: it left its place in the trees and joined the big list
+        std::vector<int> level_off;  // refit plan: the nodes of height h are order[level_off[h] .. level_off[h + 1])
+        std::vector<float> leaf_box; // [n_world][6], host side of d_leaf_box
+        int *d_order = nullptr;      // node indices sorted by height
+        float *d_leaf_box = nullptr;
+        size_t bytes = 0;            // of the two device tables (part of device_bytes)
+        hipEvent_t ev0 = nullptr, ev1 = nullptr; // RTMI_FLAG_TIMING: around the refit launches of the last in-place edit (rtmi_scene_last_refit_ms)
+        bool timed = false;
+    } geo;
     // the caller's arrays, copied at creation (the library keeps no host POINTERS): what rtmi_scene_clone replicates
     struct Args {
         std::vector<int32_t> prim_kind, prim_mat, mat_kind, mat_tex, tex_kind, tex_child, prim_flip, prim_xform, xform_kind, perm, media_calls, media_lo, image_wh;
@@ -2003,7 +2018,7 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 213; } // 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 214; } // 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -2204,7 +2219,7 @@ RTMI_EXPORT int rtmi_scene_create_ex(rtmi_ctx *c, int32_t n_prims, const int32_t
     s->ctx = c; s->n_prims = n_prims; s->n_mats = n_mats; s->n_tex = n_tex;
     s->serial = ++g_scene_serial;
     s->uses_perlin = P.M.uses_perlin; s->max_image = P.M.max_image; s->bvh_node_count = P.bvh_node_count; s->bvh_depth = P.bvh_depth;
-    s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of; s->dev = P.d; s->geom_ext = P.geom_ext;
+    s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of; s->dev = P.d; s->geom_ext = P.geom_ext; s->tree = std::move(P.tree);
     for (int k : s->host_kind) s->has_moving = s->has_moving || k == RTMI_PRIM_MOVING;
     DevScene &d = s->dev;
     rc = upload_tables(P, d, s->table_allocs, s->table_bytes);
@@ -2390,6 +2405,14 @@ SceneArrays kept_arrays(const rtmi_scene *s) {
 // The slow path of a camera or material edit: the staged build from `a` (the arrays the scene keeps, with the edited ones in their place), new tables uploaded
 // beside the old ones, then the swap.  Until the swap nothing of the scene has changed; a failure frees what was uploaded and leaves it as it was.  The caller
 // adopts the edited arrays into rtmi_scene::Args afterwards (`a` may point into them) and bumps the revision.
+void drop_geometry_edit(rtmi_scene *s) {
+    if (s->geo.d_order) (void)hipFree(s->geo.d_order);
+    if (s->geo.d_leaf_box) (void)hipFree(s->geo.d_leaf_box);
+    if (s->geo.ev0) (void)hipEventDestroy(s->geo.ev0);
+    if (s->geo.ev1) (void)hipEventDestroy(s->geo.ev1);
+    s->device_bytes -= s->geo.bytes;
+    s->geo = rtmi_scene::GeoEdit();
+}
 int rebuild_scene(rtmi_scene *s, const SceneArrays &a, const char *what) {
     PackedScene P = pack_scene(a, read_build_knobs());
     DevScene nd = P.d;
@@ -2418,6 +2441,8 @@ int rebuild_scene(rtmi_scene *s, const SceneArrays &a, const char *what) {
     s->uses_perlin = P.M.uses_perlin; s->max_image = P.M.max_image; s->bvh_node_count = P.bvh_node_count; s->bvh_depth = P.bvh_depth;
     s->host_kind = P.host_kind; s->media_fast_of = P.media_fast_of; s->mat = std::move(P.M); s->geom_ext = P.geom_ext;
     s->n_mats = a.n_mats; s->n_tex = a.n_tex;
+    s->tree = std::move(P.tree);
+    drop_geometry_edit(s); // the trees are new: nothing is displaced, and the refit plan was the old node array's
     return RTMI_OK;
 }
 int rebuild_for_camera(rtmi_scene *s, int cam_kind, const double *cam) {
@@ -2684,6 +2709,483 @@ RTMI_EXPORT int rtmi_test_pack_materials(int32_t n_prims, const int32_t *prim_ki
     return RTMI_OK;
 }
 
+// ---- the geometry of a live scene (rtmi_scene_set_geometry) ------------------------------------------------------------------------------------
+// The trees keep their topology; every box plane is recomputed bottom-up from the leaves.  BvhBuilder::put_box and half_outward are monotone, so a
+// union of rounded boxes is the rounded union: for the same topology the refit writes the planes the builder would.
+namespace {
+// Box planes travel as BITS (a float's, or a half's) and are compared by a key that orders them like their values, -0 below +0; nothing here needs libm.
+__host__ __device__ inline int refit_key32(unsigned u) { const int v = (int)u; return v ^ ((v >> 31) & 0x7fffffff); }
+__host__ __device__ inline int refit_key16(unsigned h) { const int v = (int)(short)(unsigned short)h; return v ^ ((v >> 31) & 0x7fff); }
+// half_outward (scene_build.h) on a float's bits, subnormal halves included in integer arithmetic: the same half for every input (rtmi_test_refit_half)
+__host__ __device__ inline unsigned refit_half_outward(unsigned u, bool up) {
+    const unsigned sign = u >> 31, a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return 0x7e00u | (sign << 15); // NaN
+    const bool away = up != (sign != 0);
+    unsigned m;
+    bool inexact;
+    if (a >= 0x47800000u) { m = a == 0x7f800000u ? 0x7c00u : 0x7bffu; inexact = a != 0x7f800000u; }
+    else if (a >= 0x38800000u) { m = (((a >> 23) - 112u) << 10) | ((a & 0x7fffffu) >> 13); inexact = (a & 0x1fffu) != 0; }
+    else { // half subnormals, units of 2^-24: |x| = mant 2^(e - 150), so m = mant >> (126 - e)
+        const unsigned e = a >> 23, mant = (a & 0x7fffffu) | 0x800000u, sh = 126u - e;
+        if (e == 0 || sh >= 25u) { m = 0; inexact = a != 0; }
+        else { m = mant >> sh; inexact = (mant & ((1u << sh) - 1u)) != 0; }
+    }
+    if (inexact && away) m += 1;
+    return m | (sign << 15);
+}
+// record layouts (BvhBuilder::put_box; Node16): plane (side, axis k, hi) of a record's words, and the words of its two child codes
+template <bool H> __host__ __device__ inline unsigned refit_get(const unsigned *w, int side, int k, int hi) {
+    if (H) { const int h = side * 6 + k * 2 + hi; return (w[h >> 1] >> ((h & 1) * 16)) & 0xffffu; }
+    return k < 2 ? w[side * 4 + hi * 2 + k] : w[8 + side * 2 + hi];
+}
+template <bool H> __host__ __device__ inline void refit_put(unsigned *w, int side, int k, int hi, unsigned v) {
+    if (H) { const int h = side * 6 + k * 2 + hi; w[h >> 1] = (h & 1) ? ((w[h >> 1] & 0xffffu) | (v << 16)) : ((w[h >> 1] & 0xffff0000u) | v); }
+    else w[k < 2 ? side * 4 + hi * 2 + k : 8 + side * 2 + hi] = v;
+}
+template <bool H> __host__ __device__ inline void refit_load(const unsigned *p, unsigned *w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint4 *q = reinterpret_cast<const uint4 *>(p);
+#pragma unroll
+    for (int k = 0; k < (H ? 2 : 4); ++k) { const uint4 v = q[k]; w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
+#else
+    for (int k = 0; k < (H ? 8 : 16); ++k) w[k] = p[k];
+#endif
+}
+// One node: both boxes from its children -- RTMI_BVH_EMPTY, or the right side of a lone primitive's node: the empty box; a leaf: leaf_box[primitive] (the moving and Box bits masked off, as the traversal
+// does), through half_outward for half records; an inner child: the union of that record's two boxes, refit before (its height is lower).  The child codes are
+// read, never written.  nodes: the whole array as 32-bit words.
+template <bool H> __host__ __device__ inline void refit_node(unsigned *nodes, const float *leaf_box, int n) {
+    constexpr int REC = H ? 8 : 16, CODE = H ? 6 : 12; // words per record, word of the left child code
+    unsigned own[16], out[12];
+    refit_load<H>(nodes + (size_t)n * REC, own);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) out[k] = own[k];
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+        const int code = (int)own[CODE + side];
+        unsigned lo[3], hi[3];
+        if (code >= 0) {
+            unsigned ch[16];
+            refit_load<H>(nodes + (size_t)code / 4, ch);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const unsigned l0 = refit_get<H>(ch, 0, k, 0), l1 = refit_get<H>(ch, 1, k, 0), h0 = refit_get<H>(ch, 0, k, 1), h1 = refit_get<H>(ch, 1, k, 1);
+                if (H) { lo[k] = refit_key16(l1) < refit_key16(l0) ? l1 : l0; hi[k] = refit_key16(h1) > refit_key16(h0) ? h1 : h0; }
+                else { lo[k] = refit_key32(l1) < refit_key32(l0) ? l1 : l0; hi[k] = refit_key32(h1) > refit_key32(h0) ? h1 : h0; }
+            }
+        } else {
+            unsigned fl[3] = {0x7f800000u, 0x7f800000u, 0x7f800000u}, fh[3] = {0xff800000u, 0xff800000u, 0xff800000u}; // +inf, -inf
+            // (a tree over ONE primitive, BvhBuilder::lone, names its leaf on both sides and gives the right side the empty box: no build puts a leaf twice otherwise)
+            if (code != RTMI_BVH_EMPTY && !(side == 1 && code == (int)own[CODE])) {
+                const unsigned *b = reinterpret_cast<const unsigned *>(leaf_box) + (size_t)(~code & 0x1fffffff) * 6;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { fl[k] = b[k]; fh[k] = b[3 + k]; }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { lo[k] = H ? refit_half_outward(fl[k], false) : fl[k]; hi[k] = H ? refit_half_outward(fh[k], true) : fh[k]; }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { refit_put<H>(out, side, k, 0, lo[k]); refit_put<H>(out, side, k, 1, hi[k]); }
+    }
+    unsigned *dst = nodes + (size_t)n * REC;
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint4 *q = reinterpret_cast<uint4 *>(dst);
+    q[0] = make_uint4(out[0], out[1], out[2], out[3]);
+    if (H) *reinterpret_cast<uint2 *>(dst + 4) = make_uint2(out[4], out[5]);
+    else { q[1] = make_uint4(out[4], out[5], out[6], out[7]); q[2] = make_uint4(out[8], out[9], out[10], out[11]); }
+#else
+    for (int k = 0; k < (H ? 6 : 12); ++k) dst[k] = out[k];
+#endif
+}
+
+// One launch per height, lowest first, in stream order: thread i refits node order[i].  The nodes of one height read only records of lower heights (written by
+// earlier launches) and their own child codes (never written): the launch boundary is the only ordering.  Plain vector stores, no LDS, no atomics.
+struct RefitArgs { unsigned *nodes; const float *leaf_box; const int *order; int count, node16; };
+__global__ void __launch_bounds__(256) refit_kernel(RefitArgs a) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= a.count) return;
+    const int n = a.order[i];
+    if (a.node16) refit_node<true>(a.nodes, a.leaf_box, n);
+    else refit_node<false>(a.nodes, a.leaf_box, n);
+}
+
+// The refit plan of a node array: every node's height (0: no inner child), the node indices sorted by height.  It also proves what the kernel relies on: every
+// inner child is a record of the array BEHIND its parent (BvhBuilder::build allocates a node before it recurses; the rectangle trees are rebased as blocks), and
+// every leaf names a world primitive.  false: the array is not of that form (the edit rebuilds).
+bool make_refit_plan(const unsigned *w, int n_nodes, bool node16, int n_world, std::vector<int> &order, std::vector<int> &level_off) {
+    const int rec = node16 ? 8 : 16, code_at = node16 ? 6 : 12;
+    std::vector<int> height((size_t)n_nodes, 0);
+    int top = -1;
+    for (int n = n_nodes - 1; n >= 0; --n) {
+        int h = 0;
+        for (int side = 0; side < 2; ++side) {
+            const int c = (int)w[(size_t)n * rec + code_at + side];
+            if (c == RTMI_BVH_EMPTY) continue;
+            if (c < 0) { if ((~c & 0x1fffffff) >= n_world) return false; continue; }
+            const int ci = c / (rec * 4);
+            if (c % (rec * 4) != 0 || ci <= n || ci >= n_nodes) return false;
+            h = std::max(h, height[(size_t)ci] + 1);
+        }
+        height[(size_t)n] = h;
+        top = std::max(top, h);
+    }
+    level_off.assign((size_t)top + 2, 0);
+    for (int n = 0; n < n_nodes; ++n) level_off[(size_t)height[(size_t)n] + 1]++;
+    for (size_t h = 1; h < level_off.size(); ++h) level_off[h] += level_off[h - 1];
+    order.resize((size_t)n_nodes);
+    std::vector<int> at(level_off.begin(), level_off.end() - 1);
+    for (int n = 0; n < n_nodes; ++n) order[(size_t)at[(size_t)height[(size_t)n]]++] = n;
+    return true;
+}
+// the host's refit, level by level as the device runs it: the reference the kernel is compared with (rtmi_test_refit)
+void refit_host(unsigned *w, bool node16, const float *leaf_box, const std::vector<int> &order) {
+    for (int n : order) { if (node16) refit_node<true>(w, leaf_box, n); else refit_node<false>(w, leaf_box, n); }
+}
+
+// What an edit of the geometry does to a built scene (see rtmi.h).  The built state: the TreeBuild record, the descriptor's rounded bounds, the kinds, the
+// geometry and bounded flags in HBM, who is displaced already.  The edit: its arrays and their world boxes (packed with the BUILT shutter interval).
+struct GeoVerdict {
+    bool fits = false;
+    std::string why;
+    std::vector<char> displaced;
+    int n_displaced = 0, n_big = 0, big_idx[16] = {0};
+    std::vector<float> leaf_box;
+};
+GeoVerdict judge_geometry(const TreeBuild &T, const DevScene &d, const std::vector<int> &kind, int n_world, const double *geom_was, const std::vector<char> &bounded_was,
+                          const double *geom_now, const GeomExtras &X, const std::vector<char> &displaced_was) {
+    GeoVerdict V;
+    char buf[200] = "";
+    const int n_prims = (int)kind.size();
+    const double ob = (double)d.bvh_obound, cb = (double)d.bvh_cbound;
+    V.displaced = displaced_was;
+    V.displaced.resize((size_t)std::max(n_world, 1), 0);
+    V.leaf_box.assign((size_t)std::max(n_world, 1) * 6, 0.0f);
+    if (T.box_leaves) snprintf(buf, sizeof buf, "the tree holds Box leaves (RTMI_BOX_LEAF)");
+    else if (d.n_mloc) snprintf(buf, sizeof buf, "the scene has media neighbourhood trees (RTMI_MLOC)");
+    for (int i = 0; i < n_prims && !buf[0]; ++i) {
+        if (kind[(size_t)i] == RTMI_PRIM_MEDIUM) {
+            if (std::memcmp(geom_was + (size_t)i * RTMI_PRIM_STRIDE, geom_now + (size_t)i * RTMI_PRIM_STRIDE, RTMI_PRIM_STRIDE * sizeof(double)) != 0)
+                snprintf(buf, sizeof buf, "medium %d changes (its density and boundary range are structure)", i);
+            continue;
+        }
+        if (X.bounded[(size_t)i] != bounded_was[(size_t)i]) { snprintf(buf, sizeof buf, "primitive %d %s be bounded", i, X.bounded[(size_t)i] ? "can now" : "can no longer"); break; }
+        if (i >= n_world) continue; // boundary primitives are in no tree
+        const unsigned char cls = T.cls[(size_t)i];
+        const BvhBox b = tree_item_box(X.bounded[(size_t)i] != 0, X.wbox[(size_t)i]);
+        float *lbx = &V.leaf_box[(size_t)i * 6];
+        for (int k = 0; k < 3; ++k) { lbx[k] = INFINITY; lbx[3 + k] = -INFINITY; }
+        if (X.bounded[(size_t)i])
+            for (int k = 0; k < 3 && !buf[0]; ++k)
+                if (!(std::fabs(b.lo[k]) <= ob && std::fabs(b.hi[k]) <= ob)) snprintf(buf, sizeof buf, "primitive %d leaves the bound %g the trees were built for", i, ob);
+        if (buf[0] || !(cls & TB_ITEM)) continue;
+        for (int k = 0; k < 3 && !buf[0]; ++k)
+            if (!(std::fabs(b.lo[k]) <= cb && std::fabs(b.hi[k]) <= cb)) snprintf(buf, sizeof buf, "tree primitive %d leaves the bound %g of the boxes in the tree", i, cb);
+        if (buf[0]) break;
+        if (T.grid && !V.displaced[(size_t)i]) {
+            bool out = false;
+            if (cls & TB_LAYER) {
+                int r[4];
+                grid_cell_range(b, T.lb, T.G, T.csx, T.csz, T.eps, r);
+                const int *c = &T.cell[(size_t)i * 4];
+                out = r[0] < c[0] || r[1] > c[1] || r[2] < c[2] || r[3] > c[3];
+                for (int k = 0; k < 3; ++k) out = out || !(b.lo[k] >= T.lb.lo[k] && b.hi[k] <= T.lb.hi[k]);
+            } else if (cls & TB_TALL)
+                for (int k = 0; k < 3; ++k) out = out || !(b.lo[k] >= T.tb.lo[k] && b.hi[k] <= T.tb.hi[k]);
+            if (out) V.displaced[(size_t)i] = 1;
+        }
+        if (!V.displaced[(size_t)i]) // BvhBuilder::put_box
+            for (int k = 0; k < 3; ++k) { lbx[k] = f_down(b.lo[k] - T.delta); lbx[3 + k] = f_up(b.hi[k] + T.delta); }
+    }
+    if (!buf[0]) { // the big list: the build's and the displaced, ascending
+        int total = 0;
+        for (int i = 0; i < n_world; ++i) {
+            const bool big = (T.cls[(size_t)i] & TB_BIG) || V.displaced[(size_t)i];
+            if (V.displaced[(size_t)i]) V.n_displaced++;
+            if (!big) continue;
+            if (total < 16) V.big_idx[total] = i;
+            total++;
+        }
+        V.n_big = std::min(total, 16);
+        if (total > 16) snprintf(buf, sizeof buf, "%d displaced primitives: the big list would hold %d entries, it has 16", V.n_displaced, total);
+    }
+    V.why = buf;
+    V.fits = buf[0] == 0;
+    return V;
+}
+
+// the geometry tables that lie in HBM where an edit rewrites them: host copy in a PackedScene, place in the descriptor
+struct GeoTable { const void *host; size_t bytes; const void *dev; };
+constexpr int kGeoTables = 8;
+std::array<GeoTable, kGeoTables> geometry_tables(const PackedScene &P, const DevScene &d) {
+    auto tab = [](const auto &v, const void *dev) { return GeoTable{v.data(), v.size() * sizeof(v[0]), dev}; };
+    return {tab(P.stat_geom, d.stat_geom), tab(P.stat4_d, d.stat4_d), tab(P.stat4_f, d.stat4_f), tab(P.exact12, d.exact12), tab(P.cull20, d.cull20),
+            tab(P.leaf_rec, d.leaf_rec), tab(P.ext_xf, d.ext_xf), tab(P.mov_geom, d.mov_geom)};
+}
+uint64_t hash_geometry(const PackedScene &P, const GeomExtras &X) {
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&](const void *p, size_t bytes) { const unsigned char *q = (const unsigned char *)p; for (size_t k = 0; k < bytes; ++k) { h ^= q[k]; h *= 1099511628211ull; } h ^= (uint64_t)bytes; h *= 1099511628211ull; };
+    DevScene none{};
+    for (const GeoTable &t : geometry_tables(P, none)) mix(t.host, t.bytes);
+    for (const auto &kv : P.media_fast_of) { mix(&kv.first, sizeof(int)); mix(kv.second.data(), 5 * sizeof(double)); }
+    mix(X.bounded.data(), X.bounded.size());
+    for (size_t i = 0; i < X.wbox.size(); ++i) if (X.bounded[i]) mix(&X.wbox[i], sizeof(BvhBox));
+    return h;
+}
+void pack_geometry_only(const SceneArrays &a, double t_lo, double t_hi, PackedScene &P, GeomExtras &X) {
+    std::memset(&P.d, 0, sizeof P.d);
+    pack_geometry(a, read_build_knobs().box_leaf, t_lo, t_hi, P, X);
+}
+// the first edit after a build: the mirror of the tables, the refit plan and the two device tables that go with it
+int prepare_geometry_edit(rtmi_scene *s) {
+    rtmi_scene::GeoEdit &g = s->geo;
+    if (g.ready) return RTMI_OK;
+    const DevScene &d = s->dev;
+    pack_geometry_only(kept_arrays(s), d.cull_t_lo, d.cull_t_hi, g.tab, g.X);
+    g.displaced.assign((size_t)std::max(d.n_all, 1), 0);
+    g.leaf_box.assign((size_t)std::max(d.n_all, 1) * 6, 0.0f);
+    std::vector<int> order;
+    const int n_nodes = d.bvh_root == RTMI_BVH_EMPTY && !d.grid_n ? 0 : s->bvh_node_count;
+    if (n_nodes > 0) {
+        std::vector<unsigned> w((size_t)n_nodes * (d.bvh_node16 ? 8 : 16));
+        HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+        HIP_TRY(hipMemcpy(w.data(), d.bvh_nodes, w.size() * 4, hipMemcpyDeviceToHost));
+        if (!make_refit_plan(w.data(), n_nodes, d.bvh_node16 != 0, d.n_all, order, g.level_off)) return fail(RTMI_E_STATE, "the scene's node array is not in parent-before-child order");
+    }
+    const size_t ob = std::max(order.size(), (size_t)1) * sizeof(int), lb = g.leaf_box.size() * sizeof(float);
+    if (hipMalloc((void **)&g.d_order, ob) != hipSuccess || hipMalloc((void **)&g.d_leaf_box, lb) != hipSuccess) {
+        if (g.d_order) (void)hipFree(g.d_order);
+        g = rtmi_scene::GeoEdit();
+        return fail(RTMI_E_NOMEM, "hipMalloc(%zu) failed", ob + lb);
+    }
+    g.bytes = ob + lb;
+    s->device_bytes += g.bytes;
+    if (!order.empty()) HIP_TRY(hipMemcpy(g.d_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (s->ctx->flags & RTMI_FLAG_TIMING) { HIP_TRY(hipEventCreate(&g.ev0)); HIP_TRY(hipEventCreate(&g.ev1)); }
+    g.ready = true;
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_scene_set_geometry(rtmi_scene *s, int32_t n_prims, const double *prim_geom, int32_t n_xforms, const double *xform_param, int32_t mode, int32_t *out_info) {
+    if (n_prims < 0 || n_xforms < 0) return fail(RTMI_E_ARG, "negative count");
+    if (n_prims > 0 && !prim_geom) return fail(RTMI_E_ARG, "primitive arrays are NULL");
+    if (mode != 0 && mode != 1) return fail(RTMI_E_ARG, "mode must be 0 (in place if the edit fits) or 1 (rebuild)");
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    if (n_prims != s->n_prims || n_xforms != (int)s->args.xform_kind.size())
+        return fail(RTMI_E_ARG, "the edit has %d primitives and %d instance records, the scene %d and %d: a changed count or kind is a new scene", n_prims, n_xforms, s->n_prims,
+                    (int)s->args.xform_kind.size());
+    SceneArrays a = kept_arrays(s);
+    a.prim_geom = prim_geom;
+    if (xform_param && n_xforms > 0) a.xform_param = xform_param;
+    rtmi_scene *none = nullptr;
+    int rc = check_scene_args(a, &none); // creation's checks of the same arrays, with its codes
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    int info[4] = {0, 0, 0, 0};
+    PackedScene P;
+    GeomExtras X;
+    GeoVerdict V;
+    if (mode == 0) {
+        rc = prepare_geometry_edit(s);
+        if (rc) return rc;
+        pack_geometry_only(a, s->dev.cull_t_lo, s->dev.cull_t_hi, P, X);
+        V = judge_geometry(s->tree, s->dev, s->host_kind, s->dev.n_all, s->args.prim_geom.data(), s->geo.X.bounded, prim_geom, X, s->geo.displaced);
+    }
+    rtmi_scene::Args &A = s->args;
+    auto adopt = [&]() { // (after the last use of `a`, which may point into the arrays replaced here)
+        if (prim_geom != A.prim_geom.data()) A.prim_geom.assign(prim_geom, prim_geom + (size_t)n_prims * RTMI_PRIM_STRIDE);
+        if (xform_param && n_xforms > 0 && xform_param != A.xform_param.data()) A.xform_param.assign(xform_param, xform_param + 3 * (size_t)n_xforms);
+        s->revision++;
+    };
+    if (!V.fits) {
+        rc = rebuild_scene(s, a, "rtmi_scene_set_geometry");
+        if (rc) return rc;
+        adopt();
+        info[0] = 1;
+        if (out_info) std::memcpy(out_info, info, sizeof info);
+        return RTMI_OK;
+    }
+    rtmi_scene::GeoEdit &g = s->geo;
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    const auto was = geometry_tables(g.tab, s->dev), now = geometry_tables(P, s->dev);
+    for (int t = 0; t < kGeoTables; ++t) { // each table where it lies; a table the edit leaves as it is does not travel
+        const GeoTable &o = was[(size_t)t], &n = now[(size_t)t];
+        if (o.bytes != n.bytes) return fail(RTMI_E_STATE, "geometry table %d changes its size", t); // (cannot happen: kinds, flips and chains are the scene's)
+        if (n.bytes == 0 || std::memcmp(o.host, n.host, n.bytes) == 0) continue;
+        HIP_TRY(hipMemcpy(const_cast<void *>(n.dev), n.host, n.bytes, hipMemcpyHostToDevice));
+    }
+    DevScene nd = s->dev;
+    nd.n_big = V.n_big;
+    for (int k = 0; k < 16; ++k) nd.big_idx[k] = k < V.n_big ? V.big_idx[k] : 0;
+    fill_media_fast(nd, P.media_fast_of);
+    if (std::memcmp(&nd, &s->dev, sizeof nd) != 0) HIP_TRY(hipMemcpy((void *)s->d_dev, &nd, sizeof(DevScene), hipMemcpyHostToDevice));
+    const int n_nodes = g.level_off.empty() ? 0 : g.level_off.back();
+    if (n_nodes > 0) {
+        HIP_TRY(hipMemcpy(g.d_leaf_box, V.leaf_box.data(), V.leaf_box.size() * sizeof(float), hipMemcpyHostToDevice));
+        if (g.ev0) HIP_TRY(hipEventRecord(g.ev0, s->ctx->stream));
+        for (size_t h = 0; h + 1 < g.level_off.size(); ++h) {
+            const int count = g.level_off[h + 1] - g.level_off[h];
+            if (count <= 0) continue;
+            const RefitArgs ra{reinterpret_cast<unsigned *>(const_cast<void *>((const void *)nd.bvh_nodes)), g.d_leaf_box, g.d_order + g.level_off[h], count, nd.bvh_node16};
+            hipLaunchKernelGGL(refit_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s->ctx->stream, ra);
+            HIP_TRY(hipGetLastError());
+            info[3]++;
+        }
+        info[2] = n_nodes;
+        if (g.ev1) { HIP_TRY(hipEventRecord(g.ev1, s->ctx->stream)); g.timed = true; }
+    }
+    s->dev = nd;
+    s->media_fast_of = P.media_fast_of;
+    g.leaf_box.swap(V.leaf_box);
+    g.displaced.swap(V.displaced);
+    g.tab = std::move(P);
+    g.X = std::move(X);
+    adopt();
+    info[1] = V.n_displaced;
+    if (out_info) std::memcpy(out_info, info, sizeof info);
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_scene_last_refit_ms(rtmi_scene *s, double *out_ms) {
+    if (!out_ms) return fail(RTMI_E_ARG, "out_ms is NULL");
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    if (!s->geo.timed) return fail(RTMI_E_STATE, "no timed refit: the context needs RTMI_FLAG_TIMING and the scene an in-place rtmi_scene_set_geometry since its last build");
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    HIP_TRY(hipEventSynchronize(s->geo.ev1));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->geo.ev0, s->geo.ev1));
+    *out_ms = (double)ms;
+    return RTMI_OK;
+}
+
+// test hook, host code only (no device): the geometry tables of the given arrays as creation packs them (through_creation = 1: its checks, then pack_scene) or
+// as rtmi_scene_set_geometry does (0: pack_geometry alone, with the camera's shutter interval).  out_hash = FNV-1a of stat_geom, stat4_d, stat4_f, exact12,
+// cull20, leaf_rec, ext_xf, mov_geom, media_fast_of and every primitive's bounded flag and world box.
+RTMI_EXPORT int rtmi_test_pack_geometry(int32_t n_prims, const int32_t *prim_kind, const double *prim_geom, const int32_t *prim_mat,
+                                        int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, const double *mat_param,
+                                        int32_t n_tex, const int32_t *tex_kind, const double *tex_param, const int32_t *tex_child,
+                                        int32_t cam_kind, const double *cam, const int32_t *prim_flip, const int32_t *prim_xform,
+                                        int32_t n_xforms, const int32_t *xform_kind, const double *xform_param, int32_t through_creation, uint64_t *out_hash) {
+    if (!out_hash) return fail(RTMI_E_ARG, "bad arguments");
+    const SceneArrays a{n_prims, prim_kind, prim_geom, prim_mat, n_mats, mat_kind, mat_tex, mat_param, n_tex, tex_kind, tex_param, tex_child,
+                        cam_kind, cam, prim_flip, prim_xform, n_xforms, xform_kind, xform_param};
+    rtmi_scene *none = nullptr;
+    const int rc = check_scene_args(a, &none);
+    if (rc) return rc;
+    double t_lo, t_hi;
+    camera_shutter(cam_kind, cam, t_lo, t_hi);
+    if (through_creation) {
+        // (pack_scene keeps no world boxes: they are recomputed here by the function it calls)
+        const PackedScene P = pack_scene(a, read_build_knobs());
+        PackedScene Q;
+        GeomExtras X;
+        pack_geometry_only(a, t_lo, t_hi, Q, X);
+        *out_hash = hash_geometry(P, X);
+    } else {
+        PackedScene P;
+        GeomExtras X;
+        pack_geometry_only(a, t_lo, t_hi, P, X);
+        *out_hash = hash_geometry(P, X);
+    }
+    return RTMI_OK;
+}
+
+// test hook, host code only (no device): the trees of geometry 0 as creation builds them, then n_steps - 1 edits as rtmi_scene_set_geometry applies them, the
+// refit done by the host's reference (refit_host).  geoms = [n_steps][n_prims][RTMI_PRIM_STRIDE], xforms = [n_steps][n_xforms][3] (NULL with n_xforms = 0); the
+// scene's surfaces are one grey Lambertian, its media Isotropic: every primitive goes through the kernels its geometry asks for.  Outputs, all of the state after the last step: the node array,
+// out_info = {node16, bvh_root, grid_tall, grid cells per side, n_big, displaced, rebuilt by the last step, node records, refit launches, steps that rebuilt},
+// out_big[16], the 4 G G root codes of the grid (up to cells_capacity), leaf_box [n_world][6] of the last in-place step (optional).
+RTMI_EXPORT int rtmi_test_refit(int32_t n_prims, const int32_t *prim_kind, const int32_t *prim_flip, const int32_t *prim_xform, int32_t n_xforms, const int32_t *xform_kind,
+                                int32_t cam_kind, const double *cam, int32_t n_steps, const double *geoms, const double *xforms,
+                                void *out_nodes, int64_t capacity, int64_t *out_bytes, int32_t *out_info, int32_t *out_big,
+                                int32_t *out_cells, int64_t cells_capacity, void *out_leaf_box) {
+    if (n_prims <= 0 || !prim_kind || !cam || n_steps < 1 || !geoms || !out_bytes || !out_info || n_xforms < 0 || (n_xforms > 0 && (!xforms || !xform_kind || !prim_xform)))
+        return fail(RTMI_E_ARG, "bad arguments");
+    const BuildKnobs K = read_build_knobs();
+    std::vector<int32_t> mat((size_t)n_prims, 0); // a grey Lambertian; the media scatter by material 1
+    for (int i = 0; i < n_prims; ++i) mat[(size_t)i] = (prim_kind[i] & ~RTMI_PRIM_BOUNDARY) == RTMI_PRIM_MEDIUM ? 1 : 0;
+    const int32_t mk[2] = {RTMI_MAT_LAMBERTIAN, RTMI_MAT_ISOTROPIC}, mt[2] = {0, 0}, tk = RTMI_TEX_CONSTANT, tc[2] = {-1, -1};
+    const double mp[2] = {0.0, 0.0}, tp[RTMI_TEX_STRIDE] = {0.5, 0.5, 0.5};
+    auto arrays = [&](int step) {
+        return SceneArrays{n_prims, prim_kind, geoms + (size_t)step * n_prims * RTMI_PRIM_STRIDE, mat.data(), 2, mk, mt, mp, 1, &tk, tp, tc, cam_kind, cam, prim_flip, prim_xform,
+                           n_xforms, xform_kind, n_xforms ? xforms + (size_t)step * n_xforms * 3 : nullptr};
+    };
+    PackedScene S; // the scene: its trees, its tables
+    GeomExtras SX;
+    std::vector<char> displaced;
+    std::vector<int> order, level_off;
+    std::vector<float> leaf_box;
+    int n_nodes = 0, displaced_n = 0, rebuilt_last = 0, rebuilds = 0, launches = 0;
+    const double *geom_was = nullptr;
+    auto build = [&](int step) -> int {
+        const SceneArrays a = arrays(step);
+        rtmi_scene *none = nullptr;
+        const int rc = check_scene_args(a, &none);
+        if (rc) return rc;
+        S = PackedScene();
+        std::memset(&S.d, 0, sizeof S.d);
+        double t_lo, t_hi;
+        camera_shutter(cam_kind, cam, t_lo, t_hi);
+        pack_geometry(a, K.box_leaf, t_lo, t_hi, S, SX);
+        build_trees(a, K, S.geom_ext, SX, S);
+        S.bvh_node_count = (int)(S.bvh_nodes.size() / (S.d.bvh_node16 ? 8 : 16));
+        n_nodes = S.d.bvh_root == RTMI_BVH_EMPTY && !S.d.grid_n ? 0 : S.bvh_node_count;
+        displaced.assign((size_t)std::max(S.d.n_all, 1), 0);
+        leaf_box.assign((size_t)std::max(S.d.n_all, 1) * 6, 0.0f);
+        displaced_n = 0; launches = 0;
+        order.clear(); level_off.clear();
+        geom_was = a.prim_geom;
+        if (n_nodes > 0 && !make_refit_plan(reinterpret_cast<const unsigned *>(S.bvh_nodes.data()), n_nodes, S.d.bvh_node16 != 0, S.d.n_all, order, level_off))
+            return fail(RTMI_E_STATE, "the node array is not in parent-before-child order");
+        return RTMI_OK;
+    };
+    int rc = build(0);
+    if (rc) return rc;
+    for (int step = 1; step < n_steps; ++step) {
+        const SceneArrays a = arrays(step);
+        rtmi_scene *none = nullptr;
+        if ((rc = check_scene_args(a, &none)) != RTMI_OK) return rc;
+        PackedScene P;
+        GeomExtras X;
+        pack_geometry_only(a, S.d.cull_t_lo, S.d.cull_t_hi, P, X);
+        GeoVerdict V = judge_geometry(S.tree, S.d, S.host_kind, S.d.n_all, geom_was, SX.bounded, a.prim_geom, X, displaced);
+        rebuilt_last = V.fits ? 0 : 1;
+        if (!V.fits) { rebuilds++; if ((rc = build(step)) != RTMI_OK) return rc; continue; }
+        if (n_nodes > 0) refit_host(reinterpret_cast<unsigned *>(S.bvh_nodes.data()), S.d.bvh_node16 != 0, V.leaf_box.data(), order);
+        launches = 0;
+        for (size_t h = 0; h + 1 < level_off.size(); ++h) launches += level_off[h + 1] > level_off[h];
+        S.d.n_big = V.n_big;
+        for (int k = 0; k < 16; ++k) S.d.big_idx[k] = k < V.n_big ? V.big_idx[k] : 0;
+        displaced.swap(V.displaced); leaf_box.swap(V.leaf_box); displaced_n = V.n_displaced;
+        SX = std::move(X);
+        geom_was = a.prim_geom;
+    }
+    const int64_t bytes = (int64_t)(S.bvh_nodes.size() * sizeof(float));
+    *out_bytes = bytes;
+    if (out_nodes && bytes <= capacity) std::memcpy(out_nodes, S.bvh_nodes.data(), (size_t)bytes);
+    const int32_t info[10] = {S.d.bvh_node16, S.d.bvh_root, S.d.grid_tall, S.d.grid_n, S.d.n_big, displaced_n, rebuilt_last, S.bvh_node_count, launches, rebuilds};
+    std::memcpy(out_info, info, sizeof info);
+    if (out_big) for (int k = 0; k < 16; ++k) out_big[k] = S.d.big_idx[k];
+    if (out_cells) std::memcpy(out_cells, S.grid_cells.data(), (size_t)std::min<int64_t>(cells_capacity, (int64_t)S.grid_cells.size()) * sizeof(int));
+    if (out_leaf_box) std::memcpy(out_leaf_box, leaf_box.data(), (size_t)S.d.n_all * 6 * sizeof(float));
+    return RTMI_OK;
+}
+// ... and refit_half_outward against half_outward, the function it was ported from
+RTMI_EXPORT int rtmi_test_refit_half(double x, int32_t up) { const float f = (float)x; unsigned u; std::memcpy(&u, &f, 4); return (int)refit_half_outward(u, up != 0); }
+
+// test hook: the scene's node array as it lies in HBM (after the work queued on the context's stream); *out_bytes = its size, copied if it fits `capacity`
+RTMI_EXPORT int rtmi_test_scene_nodes(rtmi_scene *s, void *buf, int64_t capacity, int64_t *out_bytes) {
+    if (!out_bytes) return fail(RTMI_E_ARG, "out_bytes is NULL");
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    const int64_t bytes = (int64_t)s->bvh_node_count * (s->dev.bvh_node16 ? 32 : 64);
+    *out_bytes = bytes;
+    if (!buf || bytes > capacity || bytes == 0) return RTMI_OK;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    HIP_TRY(hipMemcpy(buf, s->dev.bvh_nodes, (size_t)bytes, hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
 RTMI_EXPORT int rtmi_scene_tree_info(const rtmi_scene *s, int32_t *out_info) {
     if (!scene_ok(const_cast<rtmi_scene *>(s))) return fail(RTMI_E_STATE, "invalid scene handle");
     if (!out_info) return fail(RTMI_E_ARG, "out_info is NULL");
@@ -2703,6 +3205,10 @@ RTMI_EXPORT int rtmi_scene_destroy(rtmi_scene *s) {
     if (ctx_ok(s->ctx)) { (void)hipSetDevice(s->ctx->device); (void)hipStreamSynchronize(s->ctx->stream); }
     for (void *p : s->allocs) (void)hipFree(p);
     for (void *p : s->table_allocs) (void)hipFree(p);
+    if (s->geo.d_order) (void)hipFree(s->geo.d_order);
+    if (s->geo.d_leaf_box) (void)hipFree(s->geo.d_leaf_box);
+    if (s->geo.ev0) (void)hipEventDestroy(s->geo.ev0);
+    if (s->geo.ev1) (void)hipEventDestroy(s->geo.ev1);
     s->magic = 0;
     delete s;
     return RTMI_OK;

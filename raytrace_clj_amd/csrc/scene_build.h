@@ -322,11 +322,35 @@ static uint16_t half_outward(float x, bool up) {
     if (inexact && away) m += 1; // (carries into the exponent: 0x03ff + 1 = the smallest normal, 0x7bff + 1 = inf)
     return (uint16_t)(m | (sign << 15));
 }
+// What the trees of a scene were built with, kept by the scene: rtmi_scene_set_geometry judges an edit against it (never against a later edit).
+enum { TB_ITEM = 1, TB_BIG = 2, TB_TALL = 4, TB_LAYER = 8, TB_UNBOUNDED = 16 };
+struct TreeBuild {
+    double obound = 0.0, cbound = 0.0, delta = 0.0; // unrounded (DevScene holds f_down(obound), f_up(cbound))
+    std::vector<unsigned char> cls;                 // per world primitive: TB_* bits (tall / layer only where the entry grid was built)
+    bool box_leaves = false;                        // a Box went into the tree as one leaf (RTMI_BOX_LEAF)
+    bool grid = false;                              // the entry grid was built: lb .. cell hold
+    BvhBox lb{}, tb{};                              // the layer's box, the tall primitives' box
+    int G = 0;
+    double csx = 0.0, csz = 0.0, eps = 0.0;
+    std::vector<int> cell;                          // per world primitive: i0 i1 j0 j1, the cells a layer primitive was registered in
+};
+// the range of grid cells a layer primitive's box is registered in (build_bvh, and the displacement rule of rtmi_scene_set_geometry)
+inline void grid_cell_range(const BvhBox &b, const BvhBox &lb, int G, double csx, double csz, double eps, int r[4]) {
+    r[0] = std::max(0, std::min(G - 1, (int)std::floor((b.lo[0] - 2 * eps - lb.lo[0]) / csx))); r[1] = std::max(0, std::min(G - 1, (int)std::floor((b.hi[0] + 2 * eps - lb.lo[0]) / csx)));
+    r[2] = std::max(0, std::min(G - 1, (int)std::floor((b.lo[2] - 2 * eps - lb.lo[2]) / csz))); r[3] = std::max(0, std::min(G - 1, (int)std::floor((b.hi[2] + 2 * eps - lb.lo[2]) / csz)));
+}
+// the box build_bvh gives a world primitive: its world box, or everything for one that cannot be bounded
+inline BvhBox tree_item_box(bool bounded, const BvhBox &wbox) {
+    if (bounded) return wbox;
+    BvhBox b;
+    for (int k = 0; k < 3; ++k) { b.lo[k] = -1e15; b.hi[k] = 1e15; }
+    return b;
+}
 // fills d.bvh_* ; returns the node array to upload.  wbox[i] / bounded[i]: prim_world_box of every primitive.
 // box_first[i] != 0: primitives i .. i + 5 are the six faces of one Box (detected at scene creation) -- one leaf, unless the box is too large for the tree
 std::vector<float> build_bvh(DevScene &d, int n_prims, const int *prim_kind, const std::vector<BvhBox> &wbox, const std::vector<char> &bounded, const double *cam,
                              bool want_grid, std::vector<int> &grid_cells, const std::vector<char> &box_first, const BuildKnobs &K, int *out_depth = nullptr,
-                             const std::vector<BvhBox> *media_boxes = nullptr) {
+                             const std::vector<BvhBox> *media_boxes = nullptr, TreeBuild *rec = nullptr) {
     BvhBuilder B;
     struct DepthOut { BvhBuilder &b; int *o; ~DepthOut() { if (o) *o = b.max_depth; } } depth_out{B, out_depth};
     std::vector<BvhItem> all;
@@ -372,6 +396,16 @@ std::vector<float> build_bvh(DevScene &d, int n_prims, const int *prim_kind, con
     double cbound = 0.0;
     for (const BvhItem &it : B.items) for (int k = 0; k < 3; ++k) cbound = std::max(cbound, std::max(std::fabs(it.b.lo[k]), std::fabs(it.b.hi[k])));
     d.bvh_cbound = f_up(cbound);
+    if (rec) {
+        *rec = TreeBuild();
+        rec->obound = obound; rec->cbound = cbound; rec->delta = B.delta;
+        rec->cls.assign((size_t)std::max(n_prims, 1), 0);
+        rec->cell.assign((size_t)std::max(n_prims, 1) * 4, 0);
+        for (int i = 0; i < n_prims; ++i) if (prim_kind[i] != RTMI_PRIM_MEDIUM && !bounded[(size_t)i]) rec->cls[(size_t)i] |= TB_UNBOUNDED;
+        for (int k = 0; k < d.n_big; ++k) rec->cls[(size_t)d.big_idx[k]] |= TB_BIG;
+        for (const BvhItem &it : B.items) rec->cls[(size_t)it.idx] |= TB_ITEM;
+        for (char c : B.box6) rec->box_leaves = rec->box_leaves || c;
+    }
     std::vector<BvhItem> grid_items;
     std::function<void()> whole_job; // the whole tree's build, when it is deferred to run beside the grid's jobs
     if (B.items.empty()) d.bvh_root = RTMI_BVH_EMPTY;
@@ -432,9 +466,10 @@ std::vector<float> build_bvh(DevScene &d, int n_prims, const int *prim_kind, con
             const double csx = ex / G, csz = ez / G;
             std::vector<std::vector<int>> cell_items((size_t)G * G);
             for (size_t i = 0; i < layer.size(); ++i) {
-                const BvhBox &b = layer[i].b;
-                const int i0 = std::max(0, std::min(G - 1, (int)std::floor((b.lo[0] - 2 * eps - lb.lo[0]) / csx))), i1 = std::max(0, std::min(G - 1, (int)std::floor((b.hi[0] + 2 * eps - lb.lo[0]) / csx)));
-                const int j0 = std::max(0, std::min(G - 1, (int)std::floor((b.lo[2] - 2 * eps - lb.lo[2]) / csz))), j1 = std::max(0, std::min(G - 1, (int)std::floor((b.hi[2] + 2 * eps - lb.lo[2]) / csz)));
+                int cr[4];
+                grid_cell_range(layer[i].b, lb, G, csx, csz, eps, cr);
+                const int i0 = cr[0], i1 = cr[1], j0 = cr[2], j1 = cr[3];
+                if (rec) std::memcpy(&rec->cell[(size_t)layer[i].idx * 4], cr, sizeof cr);
                 for (int j = j0; j <= j1; ++j) for (int ii = i0; ii <= i1; ++ii) cell_items[(size_t)j * G + ii].push_back((int)i);
             }
             size_t claimed = 0;
@@ -520,6 +555,11 @@ std::vector<float> build_bvh(DevScene &d, int n_prims, const int *prim_kind, con
                 d.grid_eps = 0.0f;
                 BvhBox tb = box_empty();
                 for (const BvhItem &it : tall) box_grow(tb, it.b);
+                if (rec) {
+                    rec->grid = true; rec->lb = lb; rec->tb = tb; rec->G = G; rec->csx = csx; rec->csz = csz; rec->eps = eps;
+                    for (const BvhItem &it : layer) rec->cls[(size_t)it.idx] |= TB_LAYER;
+                    for (const BvhItem &it : tall) rec->cls[(size_t)it.idx] |= TB_TALL;
+                }
                 for (int k = 0; k < 3; ++k) { d.grid_tall_box[k] = tall.empty() ? 0.0f : f_down(tb.lo[k] - B.delta - eps); d.grid_tall_box[3 + k] = tall.empty() ? 0.0f : f_up(tb.hi[k] + B.delta + eps); }
                 for (int k = 0; k < 3; ++k) { // what the device tests: {lo, hi} half pairs, rounded outward once more
                     d.grid_box_h[k] = (unsigned)half_outward(d.grid_box[k], false) | ((unsigned)half_outward(d.grid_box[3 + k], true) << 16);
@@ -641,6 +681,7 @@ struct PackedScene {
     std::vector<int> host_kind; // primitive kinds, boundary flag removed
     std::map<int, std::array<double, 5>> media_fast_of;
     int bvh_node_count = 0, bvh_depth = 0;
+    TreeBuild tree;        // what build_bvh was given and decided (rtmi_scene_set_geometry)
     bool geom_ext = false; // the geometry's share of DevScene::has_ext: a primitive the sphere kernels do not hold (d.has_ext = geom_ext || M.has_ext)
     double t_tree0 = 0.0, t_tree1 = 0.0; // now_ms() around the tree build (RTMI_DEBUG)
 };
@@ -770,18 +811,20 @@ PackedMaterials pack_materials(const SceneArrays &a) {
     return M;
 }
 
-// The caller's (checked) arrays -> every device table of the scene, in host memory.  Pure host code: the same arrays and knobs give the same bytes.
-PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
-    PackedScene P;
-    DevScene &d = P.d;
-    std::memset(&d, 0, sizeof d); // (padding included: the descriptor is uploaded as bytes)
-    const int n_prims = a.n_prims;
-    const double *cam = a.cam;
-    P.M = pack_materials(a);
+// What the geometry half of a scene hands to the tree build: every primitive's world box, and the Boxes found among the rectangles
+struct GeomExtras {
+    std::vector<BvhBox> wbox;
+    std::vector<char> bounded, box_first;
     int n_world = 0, n_media = 0, media[16];
-    d.n_tex = a.n_tex; d.cam_kind = a.cam_kind;
-    std::memcpy(d.cam, cam, 24 * sizeof(double));
-    d.cam_fixed_origin = camera_fixed_origin(a.cam_kind, cam);
+};
+// The geometry half of pack_scene, trees excluded: stat_geom, stat4_d, stat4_f, exact12, cull20, leaf_rec, ext_xf, mov_geom and media_fast_of (with the index
+// tables that go with them) and the per-primitive wbox / bounded.  Of `a` it reads the primitives' kinds, geometry, flips and instance chains -- no material, no
+// camera: the shutter interval [t_lo, t_hi] the MovingSphere bounds hold for is an argument (creation: the camera's; rtmi_scene_set_geometry: the built one).
+// Writes the geometry fields of P.d (n_static, n_moving, n_all, cull_t_*, n_media, media_idx, media_lo, n_moving_all) and nothing else of it.
+void pack_geometry(const SceneArrays &a, bool box_leaf, double t_lo, double t_hi, PackedScene &P, GeomExtras &X) {
+    DevScene &d = P.d;
+    const int n_prims = a.n_prims;
+    int &n_world = X.n_world, &n_media = X.n_media, *media = X.media;
     for (int k = 0; k < a.n_xforms; ++k) {
         const double *p = a.xform_param + (size_t)k * 3;
         const double rec[4] = {a.xform_kind[k] == RTMI_XFORM_TRANSLATE ? 0.0 : 1.0, p[0], p[1], p[2]};
@@ -792,11 +835,11 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
     // multiply in the precision the kernel computes in).  exact12[i] = c0.xyz, r*r, c1.xyz, t0, t1, moving?, r, 0 and the FP32 cull entry of scan variant
     // SCAN_SGPR_CULL: a MovingSphere's bounds its sweep over the camera's shutter interval [t_lo, t_hi] (rays outside that interval bypass the cull, make_cull_ray):
     // centre = midpoint of the two extreme centres, radius = r + half the distance between them, both inflated for the float rounding of the centre.
-    double t_lo, t_hi;
-    camera_shutter(a.cam_kind, cam, t_lo, t_hi);
     std::vector<float> cull; // per primitive: centre (3), r2, w
-    std::vector<BvhBox> wbox((size_t)n_prims);
-    std::vector<char> bounded((size_t)n_prims, 0);
+    std::vector<BvhBox> &wbox = X.wbox;
+    std::vector<char> &bounded = X.bounded;
+    wbox.assign((size_t)n_prims, BvhBox{});
+    bounded.assign((size_t)n_prims, 0);
     std::vector<int> &pk = P.host_kind;
     pk.resize((size_t)n_prims);
     for (int i = 0; i < n_prims; ++i) {
@@ -880,13 +923,13 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
         cull.insert(cull.end(), {cf[0], cf[1], cf[2], unbounded ? 3.0e38f : (float)std::min(r2b * (moving ? 1.0 + 1e-6 : 1.0), 3.0e38), (float)w});
     }
     d.n_static = (int)P.stat_orig.size(); d.n_moving = (int)P.mov_orig.size();
-    const bool has_ext = P.geom_ext || P.M.has_ext;
     pad_last(P.stat4_d, 4); // (see scan_static_pipe)
     pad_last(P.stat4_f, 4);
     // Box = six consecutive rectangles RectXY z1, RectXY z0, RectXZ y1, RectXZ y0, RectYZ x1, RectYZ x0 over one (x0 y0 z0) - (x1 y1 z1) and one instance
     // chain (hitable.clj:500-511, spliced in by the flattener): the tree gets one leaf for the six (ext_box_test); z0 goes to slot 5 of the first record
-    std::vector<char> box_first((size_t)std::max(n_prims, 1), 0);
-    if (K.box_leaf) // (measured: make-final 22.1 ms with box leaves against 21.2 without -- six face tests per leaf cost more than the 1.8 node visits they save; kept for experiments)
+    std::vector<char> &box_first = X.box_first;
+    box_first.assign((size_t)std::max(n_prims, 1), 0);
+    if (box_leaf) // (measured: make-final 22.1 ms with box leaves against 21.2 without -- six face tests per leaf cost more than the 1.8 node visits they save; kept for experiments)
     for (int i = 0; i + 5 < n_world; ++i) {
         static const int want[6] = {RTMI_PRIM_RECT_XY, RTMI_PRIM_RECT_XY, RTMI_PRIM_RECT_XZ, RTMI_PRIM_RECT_XZ, RTMI_PRIM_RECT_YZ, RTMI_PRIM_RECT_YZ};
         bool ok = true;
@@ -912,28 +955,8 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
     d.n_all = n_world; d.cull_t_lo = t_lo; d.cull_t_hi = t_hi; // the scans walk the world; boundary primitives are reached only through their medium
     d.n_media = n_media;
     for (int k = 0; k < n_media; ++k) { d.media_idx[k] = media[k]; d.media_lo[k] = media[k]; }
-    // ---- the trees ----
-    P.t_tree0 = now_ms();
-    std::vector<BvhBox> media_boxes; // per ConstantMedium: the box of its boundary (if every boundary primitive can be bounded)
-    for (int k = 0; k < n_media; ++k) {
-        const double *mg = a.prim_geom + (size_t)media[k] * RTMI_PRIM_STRIDE;
-        const int fb = (int)mg[1], nb = (int)mg[2];
-        BvhBox u = box_empty();
-        bool ok = true;
-        for (int q = fb; q < fb + nb; ++q) { ok = ok && bounded[(size_t)q]; if (ok) box_grow(u, wbox[(size_t)q]); }
-        if (ok) media_boxes.push_back(u);
-    }
-    P.bvh_nodes = build_bvh(d, n_world, pk.data(), wbox, bounded, cam, !has_ext, P.grid_cells, box_first, K, &P.bvh_depth, &media_boxes);
-    P.bvh_node_count = (int)(P.bvh_nodes.size() / (d.bvh_node16 ? 8 : 16));
-    if (K.debug)
-        fprintf(stderr, "[rtmi] tree: %d node records of %d bytes (%.2f MB), depth %d, %d big primitives, %d box leaves; entry grid %d x %d cells, %zu rectangle trees\n", P.bvh_node_count,
-                d.bvh_node16 ? 32 : 64, P.bvh_node_count * (d.bvh_node16 ? 32.0 : 64.0) / 1e6, P.bvh_depth, d.n_big, (int)std::count(box_first.begin(), box_first.end(), (char)1), d.grid_n, d.grid_n, P.grid_cells.size());
-    if (K.debug && d.n_mloc) fprintf(stderr, "[rtmi] %d medium neighbourhood tree(s)\n", d.n_mloc);
-    P.t_tree1 = now_ms();
     for (int i = 0; i < n_world; ++i) if (pk[(size_t)i] == RTMI_PRIM_MOVING) P.moving_all.push_back(i);
     d.n_moving_all = (int)P.moving_all.size();
-    d.has_ext = has_ext ? 1 : 0;
-    d.small_scan = (has_ext && n_world <= RTMI_SMALL_SCAN_MAX && K.small_scan) ? 1 : 0;
     // LeafRec (rtmi_device.h: ext_leaf_test): one 112-byte record per world primitive
     P.leaf_rec.assign((size_t)std::max(n_prims, 1) * RTMI_LEAF_REC_DOUBLES, 0.0);
     for (int i = 0; i < n_prims; ++i) {
@@ -964,6 +987,56 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
         const double *e = &P.exact12[0];
         P.media_fast_of[m] = {e[(size_t)m * 12], e[(size_t)fb * 12], e[(size_t)fb * 12 + 1], e[(size_t)fb * 12 + 2], e[(size_t)fb * 12 + 3]};
     }
+}
+
+// The tree step of pack_scene: the device's trees over the world primitives of a packed geometry (P.bvh_nodes, P.grid_cells, the bvh_* / grid_* / mloc_* fields
+// of P.d, P.tree).  has_ext: the scene takes the EXT kernels, which use no entry grid.
+void build_trees(const SceneArrays &a, const BuildKnobs &K, bool has_ext, const GeomExtras &X, PackedScene &P) {
+    DevScene &d = P.d;
+    const double *cam = a.cam;
+    const std::vector<BvhBox> &wbox = X.wbox;
+    const std::vector<char> &bounded = X.bounded, &box_first = X.box_first;
+    const std::vector<int> &pk = P.host_kind;
+    const int n_world = X.n_world, n_media = X.n_media, *media = X.media;
+    // ---- the trees ----
+    P.t_tree0 = now_ms();
+    std::vector<BvhBox> media_boxes; // per ConstantMedium: the box of its boundary (if every boundary primitive can be bounded)
+    for (int k = 0; k < n_media; ++k) {
+        const double *mg = a.prim_geom + (size_t)media[k] * RTMI_PRIM_STRIDE;
+        const int fb = (int)mg[1], nb = (int)mg[2];
+        BvhBox u = box_empty();
+        bool ok = true;
+        for (int q = fb; q < fb + nb; ++q) { ok = ok && bounded[(size_t)q]; if (ok) box_grow(u, wbox[(size_t)q]); }
+        if (ok) media_boxes.push_back(u);
+    }
+    P.bvh_nodes = build_bvh(d, n_world, pk.data(), wbox, bounded, cam, !has_ext, P.grid_cells, box_first, K, &P.bvh_depth, &media_boxes, &P.tree);
+    P.bvh_node_count = (int)(P.bvh_nodes.size() / (d.bvh_node16 ? 8 : 16));
+    if (K.debug)
+        fprintf(stderr, "[rtmi] tree: %d node records of %d bytes (%.2f MB), depth %d, %d big primitives, %d box leaves; entry grid %d x %d cells, %zu rectangle trees\n", P.bvh_node_count,
+                d.bvh_node16 ? 32 : 64, P.bvh_node_count * (d.bvh_node16 ? 32.0 : 64.0) / 1e6, P.bvh_depth, d.n_big, (int)std::count(box_first.begin(), box_first.end(), (char)1), d.grid_n, d.grid_n, P.grid_cells.size());
+    if (K.debug && d.n_mloc) fprintf(stderr, "[rtmi] %d medium neighbourhood tree(s)\n", d.n_mloc);
+    P.t_tree1 = now_ms();
+}
+
+// The caller's (checked) arrays -> every device table of the scene, in host memory.  Pure host code: the same arrays and knobs give the same bytes.
+PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
+    PackedScene P;
+    DevScene &d = P.d;
+    std::memset(&d, 0, sizeof d); // (padding included: the descriptor is uploaded as bytes)
+    const double *cam = a.cam;
+    P.M = pack_materials(a);
+    d.n_tex = a.n_tex; d.cam_kind = a.cam_kind;
+    std::memcpy(d.cam, cam, 24 * sizeof(double));
+    d.cam_fixed_origin = camera_fixed_origin(a.cam_kind, cam);
+    double t_lo, t_hi;
+    camera_shutter(a.cam_kind, cam, t_lo, t_hi);
+    GeomExtras X;
+    pack_geometry(a, K.box_leaf, t_lo, t_hi, P, X);
+    const int n_world = X.n_world;
+    const bool has_ext = P.geom_ext || P.M.has_ext;
+    build_trees(a, K, has_ext, X, P);
+    d.has_ext = has_ext ? 1 : 0;
+    d.small_scan = (has_ext && n_world <= RTMI_SMALL_SCAN_MAX && K.small_scan) ? 1 : 0;
     return P;
 }
 

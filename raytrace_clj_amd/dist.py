@@ -179,6 +179,29 @@ class MultiDevice:
                                                   0, None, None, None, 0, None, None, 0, p(h), p(facts)))
         return any([s.set_materials(f) for s in self.scenes])
 
+    def set_geometry(self, scene_or_flat, mode="auto"):
+        """DeviceScene.set_geometry on every replica -> the first replica's info (the replicas are clones built from the same arrays: after the
+        same sequence of edits they decide alike).  The structure checks of ALL replicas, and creation's checks of the edited arrays, run before
+        the first replica is written: a bad edit raises and leaves every replica as it was."""
+        import numpy as np
+        if mode not in ("auto", "rebuild"):
+            raise ValueError("mode must be 'auto' or 'rebuild'")
+        pairs = [s._geometry_arrays(scene_or_flat) for s in self.scenes]
+        g, (pg, xp) = self.scenes[0].flat, pairs[0]
+        a = lambda x, dt: np.ascontiguousarray(x, dt)
+        n = len(g.prim_kind)
+        pk, pm = a(g.prim_kind, np.int32), a(g.prim_mat, np.int32)
+        mk, mt, mp = a(g.mat_kind, np.int32), a(g.mat_tex, np.int32), a(g.mat_param, np.float64)
+        tk, tp, tc = a(g.tex_kind, np.int32), a(g.tex_param, np.float64), a(g.tex_child, np.int32)
+        c24 = a(g.cam, np.float64)
+        flip, xf = a(getattr(g, "prim_flip", np.zeros(n)), np.int32), a(getattr(g, "prim_xform", np.zeros((n, 2))), np.int32)
+        xk = a(getattr(g, "xform_kind", np.zeros(0)), np.int32)
+        h = np.zeros(1, np.uint64)
+        p = _ffi.ptr
+        check(_ffi.lib().rtmi_test_pack_geometry(n, p(pk), p(pg), p(pm), len(mk), p(mk), p(mt), p(mp), len(tk), p(tk), p(tp), p(tc), int(g.cam_kind), p(c24),
+                                                 p(flip), p(xf), len(xk), p(xk), p(xp) if len(xk) else None, 0, p(h)))
+        return [s.set_geometry(scene_or_flat, mode) for s in self.scenes][0]
+
     def render(self, nx, ny, ns, depth=50, seed=0x5EED0002, precision="f64"):
         """host buffers: (linear [ny,nx,3] float64, rgb8, counters)"""
         import numpy as np
