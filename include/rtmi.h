@@ -703,6 +703,9 @@ int rtmi_test_build_tree(int32_t n, const double *geom, const double *cam, int32
 /* ^ test hook, host code only: the device's tree and entry grid over n spheres (geom[n][4] = cx cy cz r) exactly as rtmi_scene_create builds them -- on the
  * library's team of build threads, or with threads = 1 on the calling thread alone; out_hash = FNV-1a of the node array and the grid's root codes (the same
  * for any thread count), out_info[4] = node records, depth, grid cells per side, big primitives; out_ms = the build's wall time */
+int rtmi_test_camera_fixed(int32_t cam_kind, const double *cam);
+/* ^ test hook, host arithmetic only (no device): bit 0 = every ray of the camera cam[24] starts at cam[0..2] bit for bit (the stash carries no origins), bit 1 = a
+ * thin lens whose offset changes no bit of a ray's direction either (the wave-wide refill only counts the lens disk's draws) */
 int rtmi_test_half_outward(double x, int32_t up); /* x: a float value (host scalars are doubles at this boundary) */
 /* test hook, host code only (no device): the eleven material tables of rtmi_scene_create_ex's arrays, packed as rtmi_scene_set_materials* packs an edit
  * (through_creation = 0: only prim_kind, prim_mat and the material and texture tables are read, the other arrays may be NULL) or as creation packs them

@@ -23,7 +23,7 @@ SYMBOLS = [
     "rtmi_device_info", "rtmi_scene_create", "rtmi_scene_create_ex", "rtmi_scene_set_perlin", "rtmi_scene_set_images", "rtmi_scene_set_media_calls", "rtmi_scene_set_media_mode", "rtmi_scene_set_media_calls_narrowed", "rtmi_scene_device_bytes", "rtmi_scene_destroy", "rtmi_render", "rtmi_render_device",
     "rtmi_render_tiles_device", "rtmi_local_tiles", "rtmi_assemble_device", "rtmi_last_trace_ms", "rtmi_last_reduce_ms", "rtmi_probe_hit",
     "rtmi_probe_paths", "rtmi_probe_camera", "rtmi_probe_texture", "rtmi_probe_scatter", "rtmi_probe_rng",
-    "rtmi_sample_key", "rtmi_test_half_outward", "rtmi_test_build_tree", "rtmi_probe_arith", "rtmi_probe_math", "rtmi_probe_math2", "rtmi_last_traversal_counters",
+    "rtmi_sample_key", "rtmi_test_half_outward", "rtmi_test_camera_fixed", "rtmi_test_build_tree", "rtmi_probe_arith", "rtmi_probe_math", "rtmi_probe_math2", "rtmi_last_traversal_counters",
     "rtmi_scene_clone", "rtmi_render_multi", "rtmi_render_multi_device", "rtmi_last_gather_ms",
     "rtmi_last_gather_path", "rtmi_rccl_probe", "rtmi_stream_idle", "rtmi_last_passes", "rtmi_last_accel",
     "rtmi_render_progressive", "rtmi_render_progressive_device", "rtmi_progressive_samples", "rtmi_progressive_release",
@@ -103,6 +103,7 @@ def lib():
     L.rtmi_probe_arith.argtypes = [vp, i32, vp, vp]
     L.rtmi_test_build_tree.argtypes = [i32, vp, vp, i32, vp, vp, vp]
     L.rtmi_test_half_outward.argtypes = [C.c_double, i32]
+    L.rtmi_test_camera_fixed.argtypes = [i32, vp]
     L.rtmi_probe_math.argtypes = [vp, i32, vp, C.c_double, C.c_double, vp]
     L.rtmi_probe_math2.argtypes = [vp, i32, vp, C.c_double, C.c_double, i32, vp]
     L.rtmi_last_traversal_counters.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]

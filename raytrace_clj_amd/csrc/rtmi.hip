@@ -87,6 +87,8 @@ struct TraceParams {
     u64 *trav;             // COUNT instantiations: [0] += AABB slab tests (metrics aabb.intersection.total, hitable.clj:39), [1] += exact primitive tests
     int susp_off;          // mixed-kind (EXT) BVH kernels: word offset of the parked cursors in LDS = stack levels of THIS scene's tree x RTMI_BVH_STRIDE
     int stash_off;         // mixed-kind kernels: word offset of the camera-ray stash in LDS (behind the stack and the parked cursors; 0 for the scan)
+    double rnx, rny;       // RN(1 / nx), RN(1 / ny): the FP64 kernels divide the jittered pixel coordinates through div_const
+    int fixed_rays;        // thin lens whose offset (+-0, +-0, +-0) changes no bit of a ray's origin or direction (camera_fixed_rays): the lens disk loop only counts its draws
 };
 #ifndef RTMI_QUEUE_BLOCK
 #define RTMI_QUEUE_BLOCK 256
@@ -277,9 +279,54 @@ template <typename R> __device__ inline void start_sample(SceneRef sc, const Tra
     seed_stream(P, sample_key(tp.seed, (u64)j * (u64)tp.nx + (u64)i, (u64)s), 0u);
     const R u = ((R)(float)i + next_uniform(P)) / (R)tp.nx;
     const R v = ((R)(float)j + next_uniform(P)) / (R)tp.ny;
+    RTMI_PH(PH_GEN_KEY)
     get_ray<R>(sc, u, v, P);
     P.ar = P.ag = P.ab = R(1);
     P.depth = tp.depth;
+}
+
+// (i + u) / nx of start_sample: nx is a launch constant, so the FP64 kernels take the correctly rounded quotient from div_const (rn = RN(1 / n), one host
+// division per launch; 0 <= x <= n < 2^31, so no operand is scaled and Markstein's correction applies); the FP32 kernels keep their division
+__device__ inline double pixel_quot(double x, int n, double rn) { return div_const(x, (double)n, rn); }
+__device__ inline float pixel_quot(float x, int n, double) { return x / (float)n; }
+
+#ifndef RTMI_GEN_PLAIN
+#define RTMI_GEN_PLAIN 0 // 1: the stash refills generate with start_sample under the item mask, as before the wave-wide routine (A/B and the stamps' "before")
+#endif
+// What a wave keeps between the generations of one tile: a claim is qblock / 64 consecutive chunks = the same 64 pixels, samples s, s + 1, ...,
+// so the tile's origin (wave-uniform) and each lane's inner pixel hash mix64(seed ^ GOLD (pix + 1)) are computed when the tile changes only.
+// KEEP = false (the instantiations that stand at their register limit): nothing is carried, every generation recomputes them.
+struct GenTile { int tile, x0, y0; u64 hpix; };
+// One generation: chunk (wave-uniform) = 64 consecutive work items = sample s of the 64 pixels of one tile, lane l its pixel l.  The WHOLE wave calls
+// (wave-uniform control flow); returns whether the lane's item lies inside the image and region -- the others come along as helpers of the
+// cooperative disk sampler and their Q is never read.  Per lane the same stream and the same operations as start_sample.
+template <typename R, bool KEEP> __device__ inline bool generate_camera_rays(SceneRef sc, const TraceParams &tp, unsigned chunk, int lane, GenTile &g, Path<R> &Q) {
+    const int tile_local = (int)(chunk / (unsigned)tp.s_count);
+    const int s = tp.s_begin + (int)(chunk - (unsigned)tile_local * (unsigned)tp.s_count);
+#if RTMI_GEN_PLAIN
+    const int gtile = tp.tile_ids[tile_local];
+    const int x = (gtile % tp.tiles_x) * RTMI_TILE + (lane & 7), y = (gtile / tp.tiles_x) * RTMI_TILE + (lane >> 3);
+    const bool has = x >= tp.rx0 && x < tp.rx1 && y >= tp.ry0 && y < tp.ry1;
+    if (has) start_sample<R>(sc, tp, x, tp.ny - 1 - y, s, Q);
+    return has;
+#else
+    if (!KEEP || tile_local != g.tile) { // wave-uniform
+        const int gtile = tp.tile_ids[tile_local];
+        g.x0 = (gtile % tp.tiles_x) * RTMI_TILE; g.y0 = (gtile / tp.tiles_x) * RTMI_TILE;
+        const int i = g.x0 + (lane & 7), j = tp.ny - 1 - (g.y0 + (lane >> 3));
+        g.hpix = mix64(tp.seed ^ (RTMI_GOLD * ((u64)j * (u64)tp.nx + (u64)i + 1)));
+        g.tile = tile_local;
+    }
+    const int x = g.x0 + (lane & 7), y = g.y0 + (lane >> 3), j = tp.ny - 1 - y; // j = ny-1-y (core.clj:105)
+    const bool has = x >= tp.rx0 && x < tp.rx1 && y >= tp.ry0 && y < tp.ry1;
+    seed_stream(Q, mix64(g.hpix + 0xD1B54A32D192ED03ULL * ((u64)s + 1)), 0u); // = sample_key(seed, j nx + x, s)
+    const R ju = next_uniform(Q), jv = next_uniform(Q);
+    const R u = pixel_quot((R)(float)x + ju, tp.nx, tp.rnx);
+    const R v = pixel_quot((R)(float)j + jv, tp.ny, tp.rny);
+    RTMI_PH(PH_GEN_KEY)
+    get_ray_wave<R>(sc, tp.fixed_rays != 0, has, u, v, Q);
+    return has;
+#endif
 }
 
 // SLICE: time-sliced BVH traversal (section 5.1b of DESIGN.md); the plain instantiation is kept for scenes whose tree is too small to gain
@@ -318,6 +365,8 @@ __global__ void __launch_bounds__(kTraceBlock, EXT ? ((MSEQ != 0 || COUNT) ? 3 :
     u64 st_rs = 0;
     unsigned st_item = 0xffffffffu;
     unsigned s_head = 64u; // wave-uniform: entries [s_head, 64) are unclaimed
+    constexpr bool KEEP = LST; // the per-tile invariants cost two VGPRs across the path loop: kept where the kernel has them to spare (profiles/camera_rays_resources.txt)
+    GenTile gen = {-1, 0, 0, 0ull};
     unsigned nrays = 0;
     unsigned ntrav[2] = {0u, 0u};
     const R tmin = R(0.001), tmax = Real<R>::tmax();
@@ -342,19 +391,12 @@ __global__ void __launch_bounds__(kTraceBlock, EXT ? ((MSEQ != 0 || COUNT) ? 3 :
                     w_cur = base;
                     w_end = min(base + tp.qblock, total_items);
                 }
-                const unsigned m = w_cur + (unsigned)lane;
+                const unsigned m = w_cur + (unsigned)lane; // (w_cur is a multiple of 64: lane l holds pixel l of chunk w_cur / 64)
+                Path<R> Q;
+                const bool has = generate_camera_rays<R, KEEP>(sc, tp, w_cur >> 6, lane, gen, Q);
                 w_cur += 64u;
-                const unsigned chunk = m >> 6;
-                const int l = (int)(m & 63u);
-                const int tile_local = (int)(chunk / (unsigned)tp.s_count);
-                const int s = tp.s_begin + (int)(chunk - (unsigned)tile_local * (unsigned)tp.s_count);
-                const int gtile = tp.tile_ids[tile_local];
-                const int x = (gtile % tp.tiles_x) * RTMI_TILE + (l & 7);
-                const int y = (gtile / tp.tiles_x) * RTMI_TILE + (l >> 3);
                 unsigned item = 0xffffffffu; // (an item outside the image / region: an empty entry; work items are 32-bit UNSIGNED -- C4 has 2.1e9 per pass)
-                if (x >= tp.rx0 && x < tp.rx1 && y >= tp.ry0 && y < tp.ry1) {
-                    Path<R> Q;
-                    start_sample<R>(sc, tp, x, tp.ny - 1 - y, s, Q); // j = ny-1-y (core.clj:105)
+                if (has) {
                     int w0, w1;
                     best_to_words<R>(Q.dx, w0, w1); lst[lane] = w0; lst[kTraceBlock + lane] = w1;
                     best_to_words<R>(Q.dy, w0, w1); lst[2 * kTraceBlock + lane] = w0; lst[3 * kTraceBlock + lane] = w1;
@@ -412,19 +454,12 @@ __global__ void __launch_bounds__(kTraceBlock, EXT ? ((MSEQ != 0 || COUNT) ? 3 :
                     w_cur = base;
                     w_end = min(base + tp.qblock, total_items); // total_items and qblock are multiples of 64
                 }
-                const unsigned m = w_cur + (unsigned)lane;
+                const unsigned m = w_cur + (unsigned)lane; // (w_cur is a multiple of 64: lane l holds pixel l of chunk w_cur / 64)
+                Path<R> Q;
+                const bool has = generate_camera_rays<R, KEEP>(sc, tp, w_cur >> 6, lane, gen, Q);
                 w_cur += 64u;
-                const unsigned chunk = m >> 6;
-                const int l = (int)(m & 63u);
-                const int tile_local = (int)(chunk / (unsigned)tp.s_count);
-                const int s = tp.s_begin + (int)(chunk - (unsigned)tile_local * (unsigned)tp.s_count);
-                const int gtile = tp.tile_ids[tile_local];
-                const int x = (gtile % tp.tiles_x) * RTMI_TILE + (l & 7);
-                const int y = (gtile / tp.tiles_x) * RTMI_TILE + (l >> 3);
                 st_item = 0xffffffffu; // an item outside the image / region: an empty entry
-                if (x >= tp.rx0 && x < tp.rx1 && y >= tp.ry0 && y < tp.ry1) {
-                    Path<R> Q;
-                    start_sample<R>(sc, tp, x, tp.ny - 1 - y, s, Q); // j = ny-1-y (core.clj:105)
+                if (has) {
                     st_ox = Q.ox; st_oy = Q.oy; st_oz = Q.oz; st_dx = Q.dx; st_dy = Q.dy; st_dz = Q.dz; st_time = Q.time; st_rs = Q.rs;
                     st_item = m;
                     RTMI_PH(PH_REFILL_GEN)
@@ -1659,10 +1694,11 @@ int report_phase_stamps(rtmi_ctx *c, hipStream_t st) {
         fprintf(stderr, "[stamps] workgroup start (ms after first): median %.3f max %.3f | end: min %.3f p10 %.3f median %.3f p90 %.3f max %.3f (last pass, %d workgroups)\n",
                 b[g / 2], b[g - 1], e[0], e[g / 10], e[g / 2], e[g * 9 / 10], e[g - 1], g);
     }
-    static const char *names[PH_N] = {"loop/tail", "refill: generate 64 camera rays", "refill: claim + deal", "bvh: ray setup / resume", "bvh: big primitives (exact)",
+    static const char *names[PH_N] = {"loop/tail", "refill: generate (stash write)", "refill: claim + deal", "bvh: ray setup / resume", "bvh: big primitives (exact)",
                                       "bvh: descent (node visits)", "bvh: leaf exact tests", "bvh: loop control / park", "shade: hit record", "shade: |d| normalise",
                                       "shade: rand-in-unit-sphere", "shade: material record + directions", "shade: texture", "shade: store / rest", "shade: sphere uv", "(stamp calibration)",
-                                      "bvh: grid entry / next piece of the walk", "media: chords, draws, log"};
+                                      "bvh: grid entry / next piece of the walk", "media: chords, draws, log", "generate: key, jitter, u v", "generate: lens disk rounds",
+                                      "generate: camera arithmetic"};
     // every interval begins with the bookkeeping of the stamp that opened it: subtract the cost of one stamp (PH_CAL: back-to-back stamps) per stamp
     const double per_stamp = h[2 * PH_SLOTS + PH_CAL] ? (double)h[PH_CAL] / (double)h[2 * PH_SLOTS + PH_CAL] : 0.0;
     double tk[PH_N], lk[PH_N], tot = 0, totl = 0, raw = 0;
@@ -1916,6 +1952,7 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
     tp.rx0 = region.x0; tp.ry0 = region.y0; tp.rx1 = region.x1; tp.ry1 = region.y1;
     tp.trav = reinterpret_cast<u64 *>(c->counters.p) + 3;
     tp.suspend_lanes = plan.suspend_lanes; tp.susp_off = plan.lds.susp_off; tp.stash_off = plan.lds.stash_off;
+    tp.rnx = 1.0 / (double)nx; tp.rny = 1.0 / (double)ny; tp.fixed_rays = camera_fixed_rays(s->dev.cam_kind, s->dev.cam_fixed_origin, s->dev.cam);
     for (int s_begin = s_first; s_begin < s_end; s_begin += s_per_pass) {
         hipEvent_t e1 = nullptr;
         rc = launch_trace_pass(s, plan, tp, s_begin, std::min(s_per_pass, s_end - s_begin), st, &e1);
@@ -2014,6 +2051,10 @@ RTMI_EXPORT int rtmi_test_build_tree(int32_t n, const double *geom, const double
     *out_hash = h;
     out_info[0] = (int32_t)(nodes.size() / (d.bvh_node16 ? 8 : 16)); out_info[1] = depth; out_info[2] = d.grid_n; out_info[3] = d.n_big;
     return RTMI_OK;
+}
+RTMI_EXPORT int rtmi_test_camera_fixed(int32_t cam_kind, const double *cam) { // test hook (host arithmetic only: no device needed)
+    const int o = camera_fixed_origin(cam_kind, cam);
+    return o | (camera_fixed_rays(cam_kind, o, cam) << 1);
 }
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }

@@ -127,8 +127,8 @@ __host__ __device__ inline u64 draw_bits(u64 key, u64 d) { return mix64(key + RT
 // cycles) and as lane-ticks = ticks x the lanes active AT the stamp.  A stamp therefore sits at the END of the code it names, inside
 // the divergent region if that code runs under a lane mask (a region no lane enters executes no stamp: its few scalar cycles fall to
 // the next stamp).  Accumulators live in LDS, one row per wave, updated by the wave's first active lane; flushed once per launch.
-enum { PH_LOOP = 0, PH_REFILL_GEN, PH_REFILL_DEAL, PH_BVH_SETUP, PH_BIG, PH_DESCENT, PH_LEAF, PH_BVH_POST, PH_HITREC, PH_DNORM, PH_SAMPLER, PH_DIRS, PH_TEXTURE, PH_STORE, PH_UV, PH_CAL, PH_GRID, PH_MEDIA, PH_N }; // PH_CAL: back-to-back stamps = the cost of a stamp, subtracted per stamp on the host
-#define PH_SLOTS 20
+enum { PH_LOOP = 0, PH_REFILL_GEN, PH_REFILL_DEAL, PH_BVH_SETUP, PH_BIG, PH_DESCENT, PH_LEAF, PH_BVH_POST, PH_HITREC, PH_DNORM, PH_SAMPLER, PH_DIRS, PH_TEXTURE, PH_STORE, PH_UV, PH_CAL, PH_GRID, PH_MEDIA, PH_GEN_KEY, PH_GEN_DISK, PH_GEN_CAM, PH_N }; // PH_CAL: back-to-back stamps = the cost of a stamp, subtracted per stamp on the host
+#define PH_SLOTS 24
 __shared__ unsigned long long g_ph[4][3 * PH_SLOTS + 2]; // [wave]: ticks[PH_SLOTS], lane-ticks[PH_SLOTS], stamps[PH_SLOTS], last stamp, unused
 __device__ inline void ph_stamp(int k, unsigned lane_trips = 0, unsigned trips = 0) { // trips > 0: book lane_trips / trips lanes per tick instead of the stamp's own mask (loops that count their lanes per trip)
     __builtin_amdgcn_sched_barrier(0);
@@ -488,7 +488,77 @@ template <typename R> __device__ inline void rand_in_unit_disk(Path<R> &P, R &x,
     for (;;) {
         x = next_symmetric(P);
         y = next_symmetric(P);
+        RTMI_PH(PH_GEN_DISK) // one round: the stamps of this phase per generation are the wave's rounds
         if (!(dot3(x, y, R(0), x, y, R(0)) >= R(1.0))) return;
+    }
+}
+// The same for the lanes with `need`, evaluated cooperatively when the whole wave is here, as rand_in_unit_sphere_wave (every lane of the
+// wave calls; the lanes without `need` help).  Acceptance is pi/4: in the plain loop 64 lanes take ~3.6 rounds until the unluckiest accepts.
+// Here ONE ordinary round, then the n lanes still pending (~14) get K = 64/n candidates each at once: candidate c of a victim is draws
+// 2c+1, 2c+2 after its position; it takes its first accepted one and advances by exactly the draws the sequential loop would have consumed.
+// counts_only (wave-uniform): the caller needs the stream position alone (the lens radius is zero: get_ray_wave), so no value travels back.
+// The two samplers derive the lane split differently: rand_in_unit_sphere_wave keeps its arithmetic form (its schedule is not this change's to touch).
+// (The sphere sampler's (unsigned)(65536.0f / n) and 64 / n are an IEEE float division and a reciprocal sequence on the vector unit, 21 of this round's
+// 110 instructions: here both come from a table.)
+// kCoopSplit[n] = M | K << 20 with K = 64 / n and M = 65536 / n + 1, so that (L M) >> 16 = L / n for L < 64: how 64 lanes split into K candidates for each of n
+// victims (n is wave-uniform: one scalar load where the compiler's own uniform divisions are ~20 vector instructions)
+struct CoopSplit { unsigned v[65]; };
+constexpr CoopSplit make_coop_split() {
+    CoopSplit t{};
+    for (unsigned n = 1; n <= 64; ++n) t.v[n] = (65536u / n + 1u) | ((64u / n) << 20);
+    return t;
+}
+constexpr bool coop_split_divides(const CoopSplit &t) {
+    for (unsigned n = 1; n <= 64; ++n)
+        for (unsigned L = 0; L < 64; ++L) if (((L * (t.v[n] & 0xfffffu)) >> 16) != L / n) return false;
+    return true;
+}
+static_assert(coop_split_divides(make_coop_split()), "(L M) >> 16 = L / n");
+__device__ __constant__ const CoopSplit kCoopSplit = make_coop_split();
+#ifndef RTMI_COOP_DISK
+#define RTMI_COOP_DISK 1
+#endif
+template <typename R> __device__ inline void rand_in_unit_disk_wave(Path<R> &P, bool need, bool counts_only, R &x, R &y) {
+    if (!RTMI_COOP_DISK || __ballot(1) != ~0ull) { // part of the wave is elsewhere (it cannot help): the plain loop
+        if (need) rand_in_unit_disk(P, x, y);
+        return;
+    }
+    const int lane = threadIdx.x & 63;
+    bool pending = need;
+    if (pending) {
+        x = next_symmetric(P); y = next_symmetric(P);
+        pending = dot3(x, y, R(0), x, y, R(0)) >= R(1.0);
+    }
+    RTMI_PH(PH_GEN_DISK)
+    u64 rem = __ballot(pending);
+    while (rem) { // wave-uniform
+        const int n = __popcll(rem);
+        const unsigned split = kCoopSplit.v[n];
+        const int K = (int)(split >> 20);
+        const int vrank = __popcll(rem & ((1ull << lane) - 1ull));
+        const int dest = pending ? vrank : n + (lane - vrank); // victims to the front (by rank): lane i < n then knows victim i
+        const int tbl = __builtin_amdgcn_ds_permute(dest << 2, lane);
+        const int c = (int)(((unsigned)lane * (split & 0xfffffu)) >> 16), j = lane - c * n; // this lane: candidate c = lane / n of victim j = lane % n
+        const int vic = __builtin_amdgcn_ds_bpermute(j << 2, tbl);
+        const u64 rs_c = __shfl(P.rs, vic) + RTMI_GOLD * (u64)(2 * c);
+        const R cx = Real<R>::symmetric(mix64(rs_c + RTMI_GOLD)), cy = Real<R>::symmetric(mix64(rs_c + 2ull * RTMI_GOLD));
+        const u64 acc = __ballot(c < K && !(dot3(cx, cy, R(0), cx, cy, R(0)) >= R(1.0)));
+        const u64 sm = kStrideMask[n]; // the lanes that hold one victim's candidates, relative to its rank: bits 0, n, 2n, ..., (K-1) n
+        const u64 mine = pending ? ((acc >> vrank) & sm) : 0ull;
+        const int first = mine ? __ffsll((long long)mine) - 1 : 0;
+        if (!counts_only) {
+            const int src = mine ? vrank + first : lane;
+            const R fx = __shfl(cx, src), fy = __shfl(cy, src);
+            if (mine) { x = fx; y = fy; }
+        }
+        if (pending) {
+            const unsigned used = mine ? 2u * (unsigned)(__popcll(sm & ((1ull << first) - 1ull)) + 1) : 2u * (unsigned)K;
+            P.rs += RTMI_GOLD * (u64)used;
+            P.ctr += used;
+            if (mine) pending = false;
+        }
+        RTMI_PH(PH_GEN_DISK) // a cooperative round: every lane evaluates a candidate
+        rem = __ballot(pending);
     }
 }
 
@@ -510,6 +580,7 @@ template <typename R> __device__ inline void get_ray(SceneRef sc, R s, R t, Path
     }
     const R lens_radius = (R)c[21] / R(2.0);
     R rx, ry;
+    RTMI_PH(PH_GEN_CAM)
     rand_in_unit_disk(P, rx, ry); // consumed even when aperture = 0
     rx = lens_radius * rx; ry = lens_radius * ry;
     const R offx = (R)c[12] * rx + (R)c[15] * ry;
@@ -519,6 +590,40 @@ template <typename R> __device__ inline void get_ray(SceneRef sc, R s, R t, Path
     P.dx = dx + (-offx); P.dy = dy + (-offy); P.dz = dz + (-offz);
     const R t0 = (R)c[22], t1 = (R)c[23];
     P.time = t0 + (t1 - t0) * next_uniform(P);
+    RTMI_PH(PH_GEN_CAM)
+}
+// get_ray for a whole wave (the trace kernels' stash refill; every lane calls, the lanes without an item -- !has -- help the disk sampler and
+// their ray is never read).  The same operations in the same order per lane.  fixed_rays (wave-uniform, TraceParams): the lens radius is +-0 and
+// neither the origin nor the direction before the lens offset can be -0, so adding the offset (+-0, +-0, +-0) changes no bit of either: only
+// the disk loop's draw count is needed.
+template <typename R> __device__ inline void get_ray_wave(SceneRef sc, bool fixed_rays, bool has, R s, R t, Path<R> &P) {
+    unsigned long long cam_addr = (unsigned long long)(&sc.cam[0]);
+    asm volatile("" : "+s"(cam_addr)); // (as get_ray: the camera's loads stay at their use site)
+    const __attribute__((address_space(4))) double *c = (const __attribute__((address_space(4))) double *)cam_addr;
+    const R ox = (R)c[0], oy = (R)c[1], oz = (R)c[2];
+    R dx = (((R)c[3] + (R)c[6] * s) + (R)c[9] * t) + (-ox);
+    R dy = (((R)c[4] + (R)c[7] * s) + (R)c[10] * t) + (-oy);
+    R dz = (((R)c[5] + (R)c[8] * s) + (R)c[11] * t) + (-oz);
+    if (sc.cam_kind == RTMI_CAM_PINHOLE) {
+        P.ox = ox; P.oy = oy; P.oz = oz; P.dx = dx; P.dy = dy; P.dz = dz; P.time = R(0);
+        return;
+    }
+    RTMI_PH(PH_GEN_CAM)
+    R rx = R(0), ry = R(0);
+    rand_in_unit_disk_wave(P, has, fixed_rays, rx, ry);
+    if (fixed_rays) { P.ox = ox; P.oy = oy; P.oz = oz; P.dx = dx; P.dy = dy; P.dz = dz; }
+    else {
+        const R lens_radius = (R)c[21] / R(2.0);
+        rx = lens_radius * rx; ry = lens_radius * ry;
+        const R offx = (R)c[12] * rx + (R)c[15] * ry;
+        const R offy = (R)c[13] * rx + (R)c[16] * ry;
+        const R offz = (R)c[14] * rx + (R)c[17] * ry;
+        P.ox = ox + offx; P.oy = oy + offy; P.oz = oz + offz;
+        P.dx = dx + (-offx); P.dy = dy + (-offy); P.dz = dz + (-offz);
+    }
+    const R t0 = (R)c[22], t1 = (R)c[23];
+    P.time = t0 + (t1 - t0) * next_uniform(P);
+    RTMI_PH(PH_GEN_CAM)
 }
 
 // Sign of sin(x) without evaluating the sine (Checkerboard only needs (neg? (* sin sin sin)), texture.clj:47-48).

@@ -730,10 +730,20 @@ std::vector<char> texture_uv_use(const SceneArrays &a) {
 // DevScene::cam_fixed_origin of a camera (pack_scene, rtmi_scene_set_camera*): get-ray's origin is cam origin + lens offset; with aperture 0 the offset is
 // (+-0, +-0, +-0) (camera.clj:39-44: lens-radius * rand-in-unit-disk), and x + (+-0) = x bit for bit for every x except -0 (whose sum with +0 is +0): then, and
 // for the pinhole camera, all rays share one origin
+// (a component may be neither -0 nor infinite in EITHER precision: the FP32 kernels read (float)cam[k], and a tiny negative double is -0.0f there)
+inline bool camera_component_plain(double v) { return std::isfinite(v) && std::isfinite((float)v) && !(std::signbit(v) && (float)v == 0.0f); }
 inline int camera_fixed_origin(int cam_kind, const double *cam) {
     bool fixed = cam_kind == RTMI_CAM_PINHOLE || cam[21] == 0.0;
-    for (int k = 0; k < 3; ++k) fixed = fixed && !(cam[k] == 0.0 && std::signbit(cam[k])) && std::isfinite(cam[k]);
-    for (int k = 12; k < 18; ++k) fixed = fixed && std::isfinite(cam[k]);
+    for (int k = 0; k < 3; ++k) fixed = fixed && camera_component_plain(cam[k]);
+    for (int k = 12; k < 18; ++k) fixed = fixed && std::isfinite(cam[k]) && std::isfinite((float)cam[k]);
+    return fixed ? 1 : 0;
+}
+// TraceParams::fixed_rays of a thin-lens camera with a fixed origin: the lens offset (+-0, +-0, +-0) is also subtracted from the direction (camera.clj:44-46), which
+// it changes only where the direction before it is -0.  That is lleft + s horiz + t vert - origin, a left fold of sums: a sum is -0 only when both terms are,
+// so a lower-left corner without a -0 component rules it out and the wave-wide refill may skip the disk's values and keep their draw count.
+inline int camera_fixed_rays(int cam_kind, int fixed_origin, const double *cam) {
+    bool fixed = cam_kind == RTMI_CAM_THINLENS && fixed_origin;
+    for (int k = 3; k < 6; ++k) fixed = fixed && camera_component_plain(cam[k]);
     return fixed ? 1 : 0;
 }
 // The shutter interval of a camera: the times its rays carry (camera.clj:16: a pinhole ray has time 0; camera.clj:48: a thin lens draws t0 + (t1 - t0) * rand)
