@@ -509,6 +509,53 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+;; the render stream's keys (rtmi_sample_key), restated: 64-bit wrapping arithmetic
+(def ^:private stream-gold (unchecked-long 0x9E3779B97F4A7C15N))
+(def ^:private stream-mul (unchecked-long 0xD6E8FEB86659FD93N))
+(def ^:private stream-step (unchecked-long 0xD1B54A32D192ED03N))
+
+(defn- mix64 [z]
+  (let [z (bit-xor z (unsigned-bit-shift-right z 32))
+        z (unchecked-multiply z stream-mul)
+        z (bit-xor z (unsigned-bit-shift-right z 32))
+        z (unchecked-multiply z stream-mul)]
+    (bit-xor z (unsigned-bit-shift-right z 32))))
+
+(defn sample-key
+  "Stream key of (seed, pixel, sample) as a long: rtmi_sample_key."
+  [seed pixel sample]
+  (mix64 (unchecked-add (mix64 (bit-xor (unchecked-long seed) (unchecked-multiply stream-gold (unchecked-inc (long pixel)))))
+                        (unchecked-multiply stream-step (unchecked-inc (long sample))))))
+
+(defn render-rays
+  "Paths from caller-supplied rays of scene {:camera :world} on GPU `device` (rtmi_render_rays): `rays` holds 7 doubles per ray (origin,
+  direction, time), (* n-groups group) of them, ray r of group g at row (+ (* g group) r); the scene's camera is not read.  `keys` (longs, one
+  per ray) key the rays' streams; without them ray r of group g is keyed (sample-key seed g (+ first-ray r)).  Every stream starts at draw
+  `ctr0` (2 for a caller whose jitter took draws 0 and 1).  Returns {:mean double-array [n-groups][3], the group's rays folded in row order as a
+  frame folds a pixel's samples, :stderr double-array [n-groups], :rays double-array [n][3], :state double-array [n-groups][10] (the groups'
+  running records: pass it back as `state` with `first-ray` = the rays every group holds to continue them), :segments, :total-rays}."
+  [scene rays n-groups group & {:keys [keys seed ctr0 depth device precision first-ray state]
+                                :or {seed 0x5eed0002 ctr0 0 depth 50 device 0 precision 0 first-ray 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        n    (* n-groups group)
+        rs   (double-array rays)
+        ks   (long-array (or keys (for [g (range n-groups) r (range group)] (sample-key seed g (+ first-ray r)))))
+        st   (double-array (or state (* 10 n-groups)))
+        mean (double-array (* 3 n-groups))
+        err  (double-array n-groups)
+        out  (double-array (* 3 n))
+        cnt  (long-array 2)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_rays" scn (int precision) (int n-groups) (int group) (int first-ray) rs ks (long seed) (int ctr0)
+                           (int depth) st mean err out cnt))
+          {:mean mean :stderr err :rays out :state st :segments (aget cnt 0) :total-rays (aget cnt 1)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn denoise
   "Edge-aware a-trous filter (rtmi_denoise) of a frame: linear [ny][nx][3] (:linear of render / render-adaptive), stderr [ny][nx] (:stderr)
   and features [ny][nx][8] (:features of render-features), `iterations` passes (0 .. 8).  A sigma of 0 switches its term off.  Returns

@@ -541,6 +541,43 @@ int rtmi_reproject_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t prev_ca
                           double max_history, double sigma_d, double sigma_n, double sigma_a,
                           void *d_out_linear, void *d_out_rgb8, void *d_out_weight, void *d_out_stderr, void *d_out_counters, void *stream);
 
+/* ---- caller-supplied rays: every camera model, baker and probe the two built-in cameras are not ----
+ * n = n_groups * group rays, each 7 doubles {o.xyz, d.xyz, time} in the row layout of rtmi_probe_paths; ray r of group g is row g * group + r.
+ * Each ray is one path of `color` (core.clj:17-41): hit? of the world with t-min 0.001, then scatter / emitted, up to `depth`; attenuation starts
+ * at 1.  The operations are rtmi_probe_paths' on the same ray, key, ctr0 and depth, bit for bit; rays are not validated (a non-finite ray yields
+ * what the device functions yield for it and never runs past depth + 1 segments).
+ *   keys != NULL: row k's stream is keyed keys[k].  keys == NULL: it is keyed rtmi_sample_key(seed, g, g_first + r).  Either way the stream
+ *     starts at draw ctr0 (a caller that took its jitter from draws 0 and 1 of that stream passes ctr0 = 2, as a camera path continues).
+ *   out_rays (may be NULL): [n][3] doubles, the radiance of each ray.
+ *   out_mean: [n_groups][3] doubles.  The group's rays summed IN ROW ORDER in the precision R of the call, starting FROM the first ray (not 0 +
+ *     first), then sum * (R(1) / R(count)), widened to double: the frame's fold.
+ *   out_stderr: [n_groups] doubles, rtmi_render_progressive's out_stderr with "pixel" read as "group": Welford's update in double whatever the
+ *     precision, the largest channel's sqrt((M2 / (count - 1)) / count); exactly 0 when all samples are equal, +inf for count == 1.
+ *   out_counters (may be NULL): {segments traced by this call (the sum of the paths' segment counts = total-rays of metrics.clj), rays n}.
+ *   state (may be NULL): in/out, [n_groups][RTMI_RAYS_REC] doubles, the group's running record:
+ *       [0..2] the sums (in R, widened to double), [3..5] Welford's mean per channel, [6..8] Welford's M2 per channel, [9] count.
+ *     g_first == 0 starts the records; g_first > 0 continues them and must equal every record's count: the host form checks this (RTMI_E_STATE,
+ *     state untouched), the device form does not read back -- it is the caller's contract.  With a state, out_mean and out_stderr are those over
+ *     rays [0, g_first + group) of each group, and for any split of a group's rays into consecutive chunks the mean, the stderr and the sum of
+ *     the calls' counters are bit-identical to one call with all of them.  Without a state g_first only offsets the derived keys.
+ * n must fit the 32-bit work items of the kernels: n <= 2^31 - 64 (else RTMI_E_ARG); n_groups == 0 succeeds and launches nothing.
+ * RTMI_F32: sphere worlds only (a mixed-kind scene: RTMI_E_UNSUPPORTED), as the probes.
+ * Errors, in this order: n_groups < 0, group <= 0, g_first < 0, depth < 0 or an overflow (n, g_first + group): RTMI_E_ARG; rays NULL, or
+ * out_mean / out_stderr NULL with n_groups > 0: RTMI_E_ARG; a bad handle: RTMI_E_STATE; a bad precision: RTMI_E_ARG.
+ * The result does not depend on the scene's camera, on options "accel", "flat_below", "suspend_lanes", "blocks_per_cu" or "workspace_bytes" (which
+ * may split the call into passes of whole groups).  The calls do not touch the context's progressive or adaptive frame, nor the scene's
+ * revision.  RTMI_FLAG_TIMING covers them: rtmi_last_trace_ms / rtmi_last_reduce_ms report the trace and fold intervals as for a render. */
+#define RTMI_RAYS_REC 10
+/* host buffers; synchronous */
+int rtmi_render_rays(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first,
+                     const double *rays, const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth,
+                     double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters);
+/* every pointer a device pointer; asynchronous on `stream` with rtmi_render_device's stream semantics.  Allocates nothing once the context's
+ * workspace has grown to size; without d_out_rays the per-ray radiance lives in that workspace. */
+int rtmi_render_rays_device(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first,
+                            const void *d_rays, const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth,
+                            void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

@@ -36,6 +36,7 @@ SYMBOLS = [
     "rtmi_scene_tree_info",
     "rtmi_scene_set_materials", "rtmi_scene_set_materials_stream", "rtmi_test_pack_materials",
     "rtmi_scene_set_geometry", "rtmi_scene_last_refit_ms", "rtmi_test_pack_geometry", "rtmi_test_refit", "rtmi_test_refit_half", "rtmi_test_scene_nodes",
+    "rtmi_render_rays", "rtmi_render_rays_device",
 ]
 
 F64, F32 = 0, 1
@@ -46,6 +47,7 @@ SEG_REC = 12
 TILE = 8
 PROG_REC = 5  # doubles per pixel of a progressive tile record: mean rgb, stderr, samples
 FEATURES = 8  # doubles per pixel of rtmi_render_features: albedo rgb, normal xyz, depth, coverage
+RAYS_REC = 10  # doubles per group record of rtmi_render_rays: sums rgb, Welford mean rgb, Welford M2 rgb, count
 EDIT_STREAM_MAX_BYTES = 32768  # RTMI_EDIT_STREAM_MAX_BYTES: changed row payload one rtmi_scene_set_materials_stream call carries
 
 
@@ -149,6 +151,8 @@ def lib():
     L.rtmi_test_scene_nodes.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.rtmi_reproject.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 5
     L.rtmi_reproject_device.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 6
+    L.rtmi_render_rays.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, vp, vp, vp, vp, vp]
+    L.rtmi_render_rays_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, vp, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

@@ -115,3 +115,59 @@ def orbit(camera, n, pivot=None):
     """n views of a turntable: view k is `camera` turned by k * 360 / n degrees about the vertical axis through `pivot` (default: view_pivot)"""
     pivot = view_pivot(camera) if pivot is None else np.asarray(pivot, np.float64)
     return [rotate_y(camera, 2.0 * math.pi * k / n, pivot) for k in range(n)]
+
+
+# ---- ray generators for DeviceScene.render_rays / render_with: camera models the device does not have, as rays ----
+# A generator returns (rays [nx * ny * s_count, 7] float64, ctr0) for samples [s_first, s_first + s_count) of an nx x ny image, grouped per pixel:
+# group g = j * nx + i in the reference's coordinates (j = 0 is the bottom row), ray r of the group is sample s_first + r.  Its jitter is draws 0
+# and 1 of the stream keyed sample_key(seed, j * nx + i, s) -- the key render_rays derives for that row when it is given none -- so ctr0 = 2: the
+# path continues the stream where the generator stopped, as a camera path does.
+def _pixel_samples(nx, ny, s_first, s_count, seed):
+    from . import util
+    if nx <= 0 or ny <= 0 or s_first < 0 or s_count <= 0:
+        raise ValueError("nx, ny, s_count must be > 0 and s_first >= 0")
+    pix, ss = (a.ravel() for a in np.meshgrid(np.arange(nx * ny), np.arange(s_first, s_first + s_count), indexing="ij"))
+    keys = util.sample_keys(seed, pix, ss)
+    u = ((pix % nx).astype(np.float64) + util.draw_uniforms(keys, 0)) / np.float64(nx)
+    v = ((pix // nx).astype(np.float64) + util.draw_uniforms(keys, 1)) / np.float64(ny)
+    return u, v
+
+
+def _rays(origin, direction, time):
+    n = len(direction)
+    rays = np.empty((n, 7), np.float64)
+    rays[:, 0:3] = origin
+    rays[:, 3:6] = direction
+    rays[:, 6] = time
+    return rays, 2
+
+
+def panorama_rays(nx, ny, s_first, s_count, *, lookfrom, lookat, vup, seed=0x5EED0002, time=0.0):
+    """Equirectangular panorama: the full sphere seen from `lookfrom`.  Longitude (u - 1/2) * 2 pi about the axis `vup`, latitude (v - 1/2) * pi:
+    the top row (j = ny - 1) closes on +vup, the bottom row on -vup, and the centre column is the meridian through lookat - lookfrom (the centre
+    pixel looks along it when vup is perpendicular to it).  Directions are unit vectors up to rounding.  Time: no draw is made, as the pinhole
+    camera makes none; every ray carries `time` (default 0.0, the pinhole camera's)."""
+    lookfrom, lookat, vup = (np.asarray(x, np.float64) for x in (lookfrom, lookat, vup))
+    up = _normalise(vup)
+    d = lookat - lookfrom
+    fwd = _normalise(d - up * ((d[0] * up[0] + d[1] * up[1]) + d[2] * up[2]))
+    right = _cross(fwd, up)
+    u, v = _pixel_samples(nx, ny, s_first, s_count, seed)
+    lon, lat = (u - 0.5) * (2.0 * math.pi), (v - 0.5) * math.pi
+    cl = np.cos(lat)
+    direction = (cl * np.cos(lon))[:, None] * fwd + (cl * np.sin(lon))[:, None] * right + np.sin(lat)[:, None] * up
+    return _rays(lookfrom, direction, float(time))
+
+
+def orthographic_rays(nx, ny, s_first, s_count, *, lookfrom, lookat, vup, width, seed=0x5EED0002, time=0.0):
+    """Orthographic view: parallel rays along lookat - lookfrom (a unit vector) from a window of `width` x `width * ny / nx` centred on `lookfrom`
+    in the plane through it perpendicular to that direction; the window's axes are the pinhole camera's u and v (camera.clj:18-33).  Time: no
+    draw is made; every ray carries `time` (default 0.0, the pinhole camera's)."""
+    lookfrom, lookat, vup = (np.asarray(x, np.float64) for x in (lookfrom, lookat, vup))
+    w = _normalise(lookfrom - lookat)
+    cu = _normalise(_cross(vup, w))
+    cv = _cross(w, cu)
+    height = float(width) * ny / nx
+    u, v = _pixel_samples(nx, ny, s_first, s_count, seed)
+    origin = lookfrom + ((u - 0.5) * float(width))[:, None] * cu + ((v - 0.5) * height)[:, None] * cv
+    return _rays(origin, np.broadcast_to(-w, (len(u), 3)), float(time))

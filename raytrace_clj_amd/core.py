@@ -581,6 +581,60 @@ class DeviceScene:
                                                            _PRECISION[precision], tile_first, tile_stride, ptr(out_tiles_rec), ptr(out_counters),
                                                            ptr(stream)))
 
+    # ---- caller-supplied rays: panoramas, orthographic views, bakers, probes ------------------------------------------------------------
+    def render_rays(self, rays, group=1, keys=None, seed=RENDER_SEED, ctr0=0, depth=DEFAULT_DEPTH, precision="f64", first=0, state=None,
+                    return_rays=False):
+        """One path per ray: rays [n_groups * group, 7] = origin, direction, time; ray r of group g is row g * group + r.  Its stream is keyed
+        keys[row], or sample_key(seed, g, first + r) without keys, and starts at draw ctr0.  -> (mean [n_groups, 3] = the group's rays folded in
+        row order as a frame folds a pixel's samples, stderr [n_groups] = render_progressive's noise estimate per group, counters {segments traced,
+        rays}, rays' radiance [n, 3] or None).  state ([n_groups, RAYS_REC] float64, updated in place; first = 0 starts it, first > 0 continues
+        it and must be the rays every group already holds): mean and stderr are then over all rays so far, and any split of a group's rays into
+        consecutive calls gives the bits of one call."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+        group = int(group)
+        if group <= 0 or len(rays) % group:
+            raise ValueError("%d rays are not whole groups of %d" % (len(rays), group))
+        n_groups = len(rays) // group
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+            if len(keys) != len(rays):
+                raise ValueError("%d keys for %d rays" % (len(keys), len(rays)))
+        if state is not None and (not isinstance(state, np.ndarray) or state.dtype != np.float64 or not state.flags.c_contiguous
+                                  or state.shape != (n_groups, _ffi.RAYS_REC)):
+            raise ValueError("state must be a C-contiguous float64 array [n_groups, %d]" % _ffi.RAYS_REC)
+        mean, err, cnt = np.zeros((n_groups, 3), np.float64), np.zeros(n_groups, np.float64), np.zeros(2, np.uint64)
+        out = np.zeros((len(rays), 3), np.float64) if return_rays else None
+        check(_ffi.lib().rtmi_render_rays(self.handle, _PRECISION[precision], n_groups, group, int(first), ptr(rays), ptr(keys), int(seed), int(ctr0),
+                                          int(depth), ptr(state), ptr(mean), ptr(err), ptr(out), ptr(cnt)))
+        return mean, err, cnt, out
+
+    def render_rays_device(self, n_groups, group, rays, out_mean, out_stderr, keys=None, seed=RENDER_SEED, ctr0=0, depth=DEFAULT_DEPTH,
+                           precision="f64", first=0, state=None, out_rays=None, out_counters=None, stream=None):
+        """render_rays on HBM-resident buffers (torch tensors or raw device pointers; asynchronous, render_device's stream semantics).  A state's
+        count is the caller's contract: it is not read back."""
+        check(_ffi.lib().rtmi_render_rays_device(self.handle, _PRECISION[precision], int(n_groups), int(group), int(first), ptr(rays), ptr(keys), int(seed),
+                                                 int(ctr0), int(depth), ptr(state), ptr(out_mean), ptr(out_stderr), ptr(out_rays), ptr(out_counters),
+                                                 ptr(stream)))
+
+    def render_with(self, generator, nx, ny, ns, chunk, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", **generator_args):
+        """An nx x ny x ns image through a ray generator of camera.py (generator(nx, ny, s_first, s_count, seed=, **generator_args) -> (rays,
+        ctr0), grouped per pixel): chunks of `chunk` samples per pixel folded into one state, keys derived from (seed, pixel, sample) ->
+        (linear [ny, nx, 3] = the per-pixel mean, rgb8 = the frame's 8-bit quantiser of it (Context.denoise with no pass), stderr [ny, nx], counters
+        summed over the chunks); row 0 = top.  The result does not depend on `chunk`."""
+        if chunk <= 0 or ns <= 0:
+            raise ValueError("ns and chunk must be > 0")
+        state = np.zeros((nx * ny, _ffi.RAYS_REC), np.float64)
+        total = np.zeros(2, np.uint64)
+        k = 0
+        while k < ns:
+            n = min(chunk, ns - k)
+            rays, ctr0 = generator(nx, ny, k, n, seed=seed, **generator_args)
+            mean, err, cnt, _ = self.render_rays(rays, group=n, seed=seed, ctr0=ctr0, depth=depth, precision=precision, first=k, state=state)
+            total += cnt
+            k += n
+        lin = np.ascontiguousarray(mean.reshape(ny, nx, 3)[::-1])  # group j * nx + i, j = 0 at the bottom
+        return lin, self.ctx.denoise(lin, iterations=0)[1], np.ascontiguousarray(err.reshape(ny, nx)[::-1]), total
+
     # ---- probes ------------------------------------------------------------------------------------------
     def probe_hit(self, rays, t_min=T_MIN, t_max=T_MAX, precision="f64"):
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
@@ -1162,9 +1216,13 @@ def main(argv=None):
     --accumulate [MAX_HISTORY] belongs to --orbit: the views build on each other (TemporalAccumulator: the previous view's result is reprojected
     into the next camera and blended where both see the same surface; MAX_HISTORY caps the samples a history may count for, default 8, inf =
     no cap).  View k is rendered with seed RENDER_SEED + k; it writes name_000.ext (the view's own samples), name_000.acc.ext (accumulated) and,
-    with --denoise, name_000.acc.denoised.ext."""
+    with --denoise, name_000.acc.denoised.ext.
+    --panorama renders the full sphere around the scene's camera position as an equirectangular image of 2 ny x ny pixels (nx is ignored): rays
+    from camera.panorama_rays through DeviceScene.render_with, ns samples per pixel in chunks of 16.  It does not combine with the other modes."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
+    panorama = "--panorama" in argv
+    argv = [x for x in argv if x != "--panorama"]
     argv, orbit_views = _orbit_flags(argv)
     argv, accumulate = _accumulate_flags(argv, orbit_views)
     argv, adaptive_denoised = _adaptive_denoised_flags(argv)
@@ -1172,6 +1230,8 @@ def main(argv=None):
         argv.append("--denoise")  # implied, with the default passes; --feature-samples then belongs to it
     argv, dn_iterations, dn_samples = _denoise_flags(argv)
     argv, chunk, budget, noise, adaptive = _progressive_flags(argv)
+    if panorama and any(x is not None for x in (chunk, budget, noise, adaptive, dn_iterations, orbit_views, accumulate, adaptive_denoised)):
+        raise SystemExit("--panorama does not combine with the other modes")
     if chunk is None and (budget is not None or noise is not None or adaptive is not None or adaptive_denoised is not None):
         chunk = 16
     name = argv[0] if len(argv) > 0 else "render.png"  # core.clj:76
@@ -1188,7 +1248,18 @@ def main(argv=None):
     if orbit_views is not None:
         return _render_orbit(sc, name, nx, ny, nr, orbit_views, dn_iterations, dn_samples, tstart)
     filtered = None
-    if chunk is None and dn_iterations is None:
+    if panorama:
+        nx = 2 * ny
+        camera = sc["camera"]
+        ds = DeviceScene(sc)
+        try:
+            lin, rgb8, err, cnt = ds.render_with(cam.panorama_rays, nx, ny, nr, min(nr, 16), lookfrom=camera.origin, lookat=cam.view_pivot(camera),
+                                                 vup=camera.vert)
+        finally:
+            ds.close()
+        cnt = (cnt[0], nx * ny)  # the summary line counts pixels; render_with counts rays
+        print("%.2fs, %d%%, ETA %.2fs" % (time.time() - tstart, 100, 0.0))  # display.clj:20-24
+    elif chunk is None and dn_iterations is None:
         lin, rgb8, cnt = render(sc, nx, ny, nr)
         elapsed = time.time() - tstart
         print("%.2fs, %d%%, ETA %.2fs" % (elapsed, 100, 0.0))  # display.clj:20-24

@@ -1163,6 +1163,144 @@ __global__ void __launch_bounds__(kBlock) feature_kernel(ScenePtr scp, FeaturePa
     for (int c = 0; c < 8; ++c) o[c] = (double)(acc[c] * inv);
 }
 
+// ---- caller-supplied rays (rtmi_render_rays*) ------------------------------------------------------------------------------------------------
+// A work item is one ray = one path.  Persistent waves over one queue, trace_kernel's plain refill loop: a wave claims qblock consecutive items with
+// one atomic and deals them to its dead lanes in lane order; a dead lane loads the 7 doubles of its row and its key (or derives it), seeds its
+// stream and runs probe_paths_kernel's trip -- intersect_world without time-slicing, so a long segment walks its entry-grid pieces, then
+// shade_segment -- next to the live lanes' trips.  The loop is wave-level (no workgroup barrier), hence the scans that need none, as feature_kernel.
+// Which lane traces a ray never affects the result: the stream is a function of the ray's key only.  A pass covers rows [row0, row0 + total_items):
+// rays, keys and samples are the pass's own (already offset), row0 only enters the derived keys.
+struct RaysParams {
+    const double *rays;   // [total_items][7]
+    const u64 *keys;      // [total_items], or null: sample_key(seed, g, g_first + r) of row row0 + m = g * group + r
+    double *samples;      // [total_items][3]
+    u64 seed;
+    unsigned ctr0;
+    int depth;
+    unsigned group, g_first, row0;
+    unsigned total_items; // <= 2^31 - 64: a claim past the end cannot wrap the queue head
+    unsigned qblock;      // items a wave claims per queue access
+    unsigned *queue;      // zeroed before the launch
+    u64 *counters;        // [0] += segments
+};
+
+template <typename R, int VARIANT, bool EXT = false, int MSEQ = 0>
+__global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WAVES) : RTMI_MIN_WAVES) rays_kernel(ScenePtr scp, RaysParams rp) {
+    static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the refill loop is per wave");
+    SceneRef sc = *scp;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    Prim4<R> *lds = reinterpret_cast<Prim4<R> *>(smem);
+    const int lane = threadIdx.x & 63;
+    const unsigned total_items = rp.total_items;
+    unsigned w_cur = 0, w_end = 0; // this wave's claimed range [w_cur, w_end): wave-uniform
+    Path<R> P;
+    P.ox = P.oy = P.oz = P.dx = P.dy = P.dz = P.time = R(0);
+    P.ar = P.ag = P.ab = R(0);
+    seed_stream(P, 0ull, 0u); P.depth = 0;
+    bool alive = false;
+    bool exhausted = (total_items == 0);
+    unsigned out_item = 0;
+    unsigned nseg = 0;
+    const R tmin = R(0.001), tmax = Real<R>::tmax();
+    for (;;) {
+        while (!exhausted) { // every lane of the wave takes part: the loop conditions are wave-uniform
+            const u64 dead = __ballot(!alive);
+            if (dead == 0) break;
+            if (w_cur == w_end) {
+                unsigned base = 0;
+                if (lane == 0) base = atomicAdd(rp.queue, rp.qblock);
+                base = __builtin_amdgcn_readfirstlane(base);
+                if (base >= total_items) { exhausted = true; break; }
+                w_cur = base;
+                w_end = min(base + rp.qblock, total_items);
+            }
+            const unsigned avail = w_end - w_cur;
+            const unsigned rank = (unsigned)__popcll(dead & ((1ull << lane) - 1ull));
+            if (!alive && rank < avail) {
+                const unsigned m = w_cur + rank; // < total_items
+                load_ray<R>(rp.rays + (size_t)m * 7, P);
+                u64 key;
+                if (rp.keys) key = rp.keys[m];
+                else { const unsigned row = rp.row0 + m, g = row / rp.group; key = sample_key(rp.seed, (u64)g, (u64)rp.g_first + (u64)(row - g * rp.group)); }
+                seed_stream(P, key, rp.ctr0); P.depth = rp.depth;
+                out_item = m;
+                alive = true;
+            }
+            w_cur += min((unsigned)__popcll(dead), avail);
+        }
+        if (!__any(alive ? 1 : 0)) break;
+        R best_t; int best_i;
+        intersect_world<R, true, VARIANT, EXT, false, false, MSEQ>(sc, lds, 0, 1, P, alive, tmin, tmax, best_t, best_i);
+        if (alive) {
+            ++nseg;
+            R emit[3];
+            alive = shade_segment<R, EXT>(sc, P, best_t, best_i, nullptr, emit);
+            if (!alive) {
+                double *out = rp.samples + (size_t)out_item * 3;
+                out[0] = (double)emit[0]; out[1] = (double)emit[1]; out[2] = (double)emit[2];
+            }
+        }
+    }
+    // segments: wave reduction, one atomic per wave
+    unsigned n = nseg;
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off);
+    if (lane == 0 && n) atomicAdd(rp.counters, (u64)n);
+}
+
+// One lane per group (consecutive lanes, consecutive groups), looping over the group's rows in order: the sums with reduce_kernel's fold in R (the
+// first ray of the group is the start value), the noise state with frame_fold_kernel's Welford update in double (restated: that kernel's update is
+// part of its body), then pixel_estimate's mean and standard error over count = first + group rays.  state (may be null): the records, read when
+// first > 0 and written back; without one first is 0.  samples holds groups [g0, g0 + n_groups) of the call; mean, se and state are the call's.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) rays_fold_kernel(const double *__restrict__ samples, int g0, int n_groups, int group, int first,
+                                                           double *__restrict__ state, double *__restrict__ mean, double *__restrict__ se,
+                                                           u64 *counters, u64 n_rays) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid == 0 && counters) counters[1] = n_rays;
+    if (gid >= n_groups) return;
+    const size_t g = (size_t)g0 + (size_t)gid;
+    R acc[3] = {R(0), R(0), R(0)};
+    double mu[3] = {0.0, 0.0, 0.0}, q[3] = {0.0, 0.0, 0.0};
+    double *rec = state ? state + g * RTMI_RAYS_REC : nullptr;
+    if (rec && first > 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { acc[k] = (R)rec[k]; mu[k] = rec[3 + k]; q[k] = rec[6 + k]; }
+    }
+    const double *row = samples + (size_t)gid * (size_t)group * 3;
+    for (int s = 0; s < group; ++s, row += 3) {
+        const R v[3] = {(R)row[0], (R)row[1], (R)row[2]};
+        if (first + s == 0) { // the fold starts FROM the first ray (not 0 + first)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { acc[k] = v[k]; mu[k] = (double)v[k]; q[k] = 0.0; }
+        } else {
+            const double n = (double)(first + s + 1);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                acc[k] = acc[k] + v[k];
+                const double x = (double)v[k], d = x - mu[k];
+                mu[k] = mu[k] + d / n;
+                q[k] = q[k] + d * (x - mu[k]);
+            }
+        }
+    }
+    const int count = first + group;
+    if (rec) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { rec[k] = (double)acc[k]; rec[3 + k] = mu[k]; rec[6 + k] = q[k]; }
+        rec[9] = (double)count;
+    }
+    double err = count > 1 ? 0.0 : INFINITY;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        mean[g * 3 + k] = (double)(acc[k] * (R(1.0) / (R)count));
+        if (count > 1) {
+            const double e = ::sqrt((q[k] / (double)(count - 1)) / (double)count);
+            err = e > err ? e : err;
+        }
+    }
+    se[g] = err;
+}
+
 // ---- edge-aware denoiser (rtmi_denoise*): an a-trous wavelet filter over planar FP64 images -----------------------------------------------------
 // Planes of nx * ny doubles: colour r, g, b and the variance of the mean V (two sets: a pass reads one and writes the other), then normal xyz,
 // albedo rgb and depth (read only).  Lanes run along x: every tap of a wave is one contiguous run per plane.
@@ -1460,6 +1598,7 @@ struct rtmi_ctx {
     DevBuf feat_out, feat_cnt; // rtmi_render_features*: the host form's result, the counters nobody asked for
     DevBuf dn_planes, dn_io;   // rtmi_denoise*: the filter's planes (two colour + variance sets, the feature planes), the host form's buffers
     DevBuf rp_io;              // rtmi_reproject: the host form's buffers (the device form owns nothing)
+    DevBuf rays_ws, rays_io;   // rtmi_render_rays*: the per-ray radiance nobody asked for (one pass of it), the host form's buffers
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     int events_used = 0;
@@ -2059,7 +2198,7 @@ RTMI_EXPORT int rtmi_test_camera_fixed(int32_t cam_kind, const double *cam) { //
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 214; } // 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 215; } // 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -2098,7 +2237,7 @@ RTMI_EXPORT int rtmi_shutdown(rtmi_ctx *c) {
 #endif
     c->samples.release(); c->accum.release(); c->tiles.release(); c->tile_ids.release(); c->counters.release(); c->scratch_lin.release(); c->multi.release();
     c->prog.release();
-    c->feat_out.release(); c->feat_cnt.release(); c->dn_planes.release(); c->dn_io.release(); c->rp_io.release();
+    c->feat_out.release(); c->feat_cnt.release(); c->dn_planes.release(); c->dn_io.release(); c->rp_io.release(); c->rays_ws.release(); c->rays_io.release();
     for (hipEvent_t e : {c->ev_done, c->ev_g0, c->ev_g1}) if (e) (void)hipEventDestroy(e);
     if (c->ev_consumed) { (void)hipSetDevice(c->ev_consumed_device); (void)hipEventDestroy(c->ev_consumed); (void)hipSetDevice(c->device); }
     for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -4743,6 +4882,167 @@ RTMI_EXPORT int rtmi_reproject(rtmi_ctx *c, int32_t nx, int32_t ny, int32_t prev
     if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_oq, 3 * n, hipMemcpyDeviceToHost));
     if (out_weight) HIP_TRY(hipMemcpy(out_weight, d_ow, n * sizeof(double), hipMemcpyDeviceToHost));
     if (out_stderr) HIP_TRY(hipMemcpy(out_stderr, d_ose, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---- caller-supplied rays (rtmi_render_rays*) ---------------------------------------------------------------------------------------------------
+namespace {
+// rays_kernel's instantiations are chosen where the probe kernels' are (with_probe_kernel); the LDS-staged scans (scan_variant 0 / 1) need
+// workgroup barriers and are answered with the scalar-cache scan, which finds the same hit (as the feature pass)
+struct RaysPass {
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MSEQ>; }
+};
+
+constexpr long long kRaysMax = (1ll << 31) - 64; // rays per call: 32-bit work items, and a claim past the end must not wrap the queue head
+
+// the argument checks of both entries, in the header's order
+int check_rays_args(rtmi_scene *s, int precision, int n_groups, int group, int g_first, int depth, const void *rays, const void *mean, const void *se) {
+    if (n_groups < 0 || group <= 0 || g_first < 0 || depth < 0)
+        return fail(RTMI_E_ARG, "n_groups, g_first, depth must be >= 0 and group > 0 (got %d %d %d %d)", n_groups, g_first, depth, group);
+    if ((long long)n_groups * group > kRaysMax) return fail(RTMI_E_ARG, "n_groups * group = %lld rays exceed 2^31 - 64", (long long)n_groups * group);
+    if ((long long)g_first + group > INT32_MAX) return fail(RTMI_E_ARG, "g_first + group = %d + %d overflows int32", g_first, group);
+    if (n_groups > 0 && !rays) return fail(RTMI_E_ARG, "rays is NULL");
+    if (n_groups > 0 && (!mean || !se)) return fail(RTMI_E_ARG, "out_mean / out_stderr is NULL");
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    if (precision != RTMI_F64 && precision != RTMI_F32) return fail(RTMI_E_ARG, "precision must be RTMI_F64 or RTMI_F32");
+    if (precision == RTMI_F32 && s->dev.has_ext) return fail(RTMI_E_UNSUPPORTED, "rectangles / triangles / instances / procedural textures are traced by the FP64 kernels only");
+    if (s->uses_perlin && !s->have_perlin) return fail(RTMI_E_STATE, "the scene holds a Perlin texture: call rtmi_scene_set_perlin first");
+    if (s->max_image >= s->dev.n_images) return fail(RTMI_E_STATE, "the scene holds an ImageMap with index %d: call rtmi_scene_set_images first", s->max_image);
+    return RTMI_OK;
+}
+
+// The launches, all on `st`, every pointer a device pointer: passes of whole groups, each one rays_kernel launch followed by its fold.  With
+// d_out_rays the call is one pass into it; without, a pass holds as many groups as option "workspace_bytes" allows (at least one) in c->rays_ws.
+template <typename R>
+int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
+                     double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
+    rtmi_ctx *c = s->ctx;
+    int rc = c->counters.ensure(8 * sizeof(u64)); // [0..1] the counters when the caller passes no buffer, [2] the work-queue head
+    if (rc) return rc;
+    if (!d_cnt) d_cnt = reinterpret_cast<u64 *>(c->counters.p);
+    int per_pass = n_groups;
+    if (!d_out_rays) {
+        const int64_t group_bytes = (int64_t)group * 3 * (int64_t)sizeof(double);
+        per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(n_groups, c->workspace_bytes / group_bytes));
+        rc = c->rays_ws.ensure((size_t)per_pass * (size_t)group_bytes);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(u64), st));
+    RaysParams rp;
+    rp.seed = seed; rp.ctr0 = ctr0; rp.depth = depth;
+    rp.group = (unsigned)group; rp.g_first = (unsigned)g_first;
+    rp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 2);
+    rp.counters = d_cnt;
+    const size_t lds = c->accel == RTMI_ACCEL_BVH ? (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16 : (size_t)64; // the traversal's stack columns
+    const u64 n_rays = (u64)n_groups * (u64)group;
+    with_probe_kernel<RaysPass, R>(s, [&](auto kern, size_t, int, int) {
+        rc = [&]() -> int {
+            int resident = 0;
+            { // asked once per (kernel, LDS bytes) and kept on the context, as the trace launch does
+                const std::pair<const void *, size_t> key(reinterpret_cast<const void *>(kern), lds);
+                auto it = c->occupancy.find(key);
+                if (it == c->occupancy.end()) {
+                    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kern, kBlock, lds));
+                    c->occupancy.emplace(key, resident);
+                } else resident = it->second;
+            }
+            const long long persistent = (long long)c->cus * std::max(1, std::min(c->blocks_per_cu, resident));
+            for (int g0 = 0; g0 < n_groups; g0 += per_pass) {
+                const int ng = std::min(per_pass, n_groups - g0);
+                const size_t row0 = (size_t)g0 * (size_t)group;
+                const long long items = (long long)ng * group;
+                rp.rays = d_rays + row0 * 7;
+                rp.keys = d_keys ? d_keys + row0 : nullptr;
+                rp.samples = d_out_rays ? d_out_rays + row0 * 3 : reinterpret_cast<double *>(c->rays_ws.p);
+                rp.row0 = (unsigned)row0; rp.total_items = (unsigned)items;
+                { // claim size: short claims on small launches (the tail matters), longer ones when a wave has many ahead of it
+                    const long long per_wave = items / std::max(1, c->cus * 16);
+                    unsigned qb = 64u;
+                    while (qb < 1024u && per_wave >= (long long)qb * 16) qb *= 2;
+                    rp.qblock = qb;
+                }
+                hipEvent_t e0 = nullptr, e1 = nullptr;
+                if ((c->flags & RTMI_FLAG_TIMING) && c->events_used < 8192) {
+                    const int rce = next_event_pair(c, &e0, &e1);
+                    if (rce) return rce;
+                    HIP_TRY(hipEventRecord(e0, st));
+                }
+                HIP_TRY(hipMemsetAsync(rp.queue, 0, sizeof(unsigned), st));
+                const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(persistent, (items + kBlock - 1) / kBlock));
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, s->d_dev, rp);
+                HIP_TRY(hipGetLastError());
+                if (e1) HIP_TRY(hipEventRecord(e1, st));
+                hipLaunchKernelGGL((rays_fold_kernel<R>), dim3((unsigned)((ng + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rp.samples, g0, ng, group,
+                                   d_state ? g_first : 0, d_state, d_mean, d_se, d_cnt, n_rays);
+                HIP_TRY(hipGetLastError());
+                if (e1) {
+                    const size_t k = (size_t)c->events_used - 1;
+                    while (c->events_r.size() <= k) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->events_r.push_back(e); }
+                    HIP_TRY(hipEventRecord(c->events_r[k], st));
+                }
+            }
+            return RTMI_OK;
+        }();
+    });
+    return rc;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_rays_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const void *d_rays,
+                                        const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth, void *d_state, void *d_out_mean,
+                                        void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream) {
+    int rc = check_rays_args(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr);
+    if (rc) return rc;
+    if (n_groups == 0) return RTMI_OK;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    return with_real(precision, [&](auto r) {
+        return render_rays_impl<decltype(r)>(s, n_groups, group, g_first, reinterpret_cast<const double *>(d_rays), reinterpret_cast<const u64 *>(d_keys), seed,
+                                             ctr0, depth, reinterpret_cast<double *>(d_state), reinterpret_cast<double *>(d_out_mean),
+                                             reinterpret_cast<double *>(d_out_stderr), reinterpret_cast<double *>(d_out_rays),
+                                             reinterpret_cast<u64 *>(d_out_counters), st);
+    });
+}
+
+RTMI_EXPORT int rtmi_render_rays(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const double *rays,
+                                 const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth, double *state, double *out_mean, double *out_stderr,
+                                 double *out_rays, uint64_t *out_counters) {
+    int rc = check_rays_args(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr);
+    if (rc) return rc;
+    if (n_groups == 0) return RTMI_OK;
+    if (state && g_first > 0)
+        for (int g = 0; g < n_groups; ++g)
+            if (state[(size_t)g * RTMI_RAYS_REC + 9] != (double)g_first)
+                return fail(RTMI_E_STATE, "group %d's record holds %g rays, g_first is %d", g, state[(size_t)g * RTMI_RAYS_REC + 9], g_first);
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)n_groups * (size_t)group, ng = (size_t)n_groups;
+    // in: rays 7n doubles, keys n; in/out: the records; out: mean 3 ng, stderr ng doubles, the counters, the radiance 3n doubles where asked for
+    const size_t words = 7 * n + (keys ? n : 0) + (state ? ng * RTMI_RAYS_REC : 0) + 4 * ng + 2 + (out_rays ? 3 * n : 0);
+    rc = c->rays_io.ensure(words * sizeof(double));
+    if (rc) return rc;
+    double *d_rays = reinterpret_cast<double *>(c->rays_io.p);
+    u64 *d_keys = reinterpret_cast<u64 *>(d_rays + 7 * n);
+    double *d_state = reinterpret_cast<double *>(d_keys + (keys ? n : 0)), *d_mean = d_state + (state ? ng * RTMI_RAYS_REC : 0), *d_se = d_mean + 3 * ng;
+    u64 *d_cnt = reinterpret_cast<u64 *>(d_se + ng);
+    double *d_out = reinterpret_cast<double *>(d_cnt + 2);
+    hipStream_t st = c->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(d_rays, rays, 7 * n * sizeof(double), hipMemcpyHostToDevice));
+    if (keys) HIP_TRY(hipMemcpy(d_keys, keys, n * sizeof(u64), hipMemcpyHostToDevice));
+    if (state && g_first > 0) HIP_TRY(hipMemcpy(d_state, state, ng * RTMI_RAYS_REC * sizeof(double), hipMemcpyHostToDevice));
+    rc = with_real(precision, [&](auto r) {
+        return render_rays_impl<decltype(r)>(s, n_groups, group, g_first, d_rays, keys ? d_keys : nullptr, seed, ctr0, depth, state ? d_state : nullptr, d_mean,
+                                             d_se, out_rays ? d_out : nullptr, d_cnt, st);
+    });
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (state) HIP_TRY(hipMemcpy(state, d_state, ng * RTMI_RAYS_REC * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_mean, d_mean, 3 * ng * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_stderr, d_se, ng * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_rays) HIP_TRY(hipMemcpy(out_rays, d_out, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
     if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
     return RTMI_OK;
 }

@@ -78,3 +78,28 @@ def sample_key(seed, pixel, sample):
 def draw_bits(key, d):
     m, g = SplitMix64.MASK, SplitMix64.GOLD
     return mix64((key + g * (d + 1)) & m)
+
+
+# ---- the render stream over arrays (numpy uint64; the scalar functions above, element-wise) ----
+def _mix64_np(z):
+    s, mul = np.uint64(32), np.uint64(0xD6E8FEB86659FD93)
+    z = z ^ (z >> s)
+    z = z * mul
+    z = z ^ (z >> s)
+    z = z * mul
+    return z ^ (z >> s)
+
+
+def sample_keys(seed, pixel, sample):
+    """sample_key over arrays of pixel indices and sample numbers -> uint64 array"""
+    with np.errstate(over="ignore"):
+        pixel, sample = np.asarray(pixel, np.uint64), np.asarray(sample, np.uint64)
+        gold, step, one = np.uint64(SplitMix64.GOLD), np.uint64(0xD1B54A32D192ED03), np.uint64(1)
+        return _mix64_np(_mix64_np(np.uint64(seed) ^ (gold * (pixel + one))) + step * (sample + one))
+
+
+def draw_uniforms(keys, d):
+    """draw number d of every stream as the FP64 uniform in [0, 1) the device draws: the top 53 bits of draw_bits(key, d) * 2^-53"""
+    with np.errstate(over="ignore"):
+        z = _mix64_np(np.asarray(keys, np.uint64) + np.uint64(SplitMix64.GOLD) * np.uint64(d + 1))
+    return (z >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
