@@ -776,6 +776,10 @@ int rtmi_test_refit(int32_t n_prims, const int32_t *prim_kind, const int32_t *pr
 int rtmi_test_refit_half(double x, int32_t up); /* rtmi_test_half_outward by the integer form the refit uses on the device */
 /* test hook: the scene's node array as it lies in HBM, after the work queued on the context's stream; *out_bytes = its size, copied if <= capacity */
 int rtmi_test_scene_nodes(rtmi_scene *scene, void *buf, int64_t capacity, int64_t *out_bytes);
+/* test hook, host code only (no device): where the host forms' staging puts n planes of elem_bytes[i] * counts[i] bytes each, by the code that lays out
+ * every host form's device buffers (present[i] = 0: an optional array the caller left out).  out_offsets[i] = the plane's first byte (UINT64_MAX for an
+ * absent plane), *out_total = the bytes the staging buffer needs */
+int rtmi_test_stage_layout(int32_t n, const uint64_t *elem_bytes, const uint64_t *counts, const int32_t *present, uint64_t *out_offsets, uint64_t *out_total);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@ SYMBOLS = [
     "rtmi_scene_set_materials", "rtmi_scene_set_materials_stream", "rtmi_test_pack_materials",
     "rtmi_scene_set_geometry", "rtmi_scene_last_refit_ms", "rtmi_test_pack_geometry", "rtmi_test_refit", "rtmi_test_refit_half", "rtmi_test_scene_nodes",
     "rtmi_render_rays", "rtmi_render_rays_device",
+    "rtmi_test_stage_layout",
 ]
 
 F64, F32 = 0, 1
@@ -153,6 +154,7 @@ def lib():
     L.rtmi_reproject_device.argtypes = [vp, i32, i32, i32, vp, i32, vp] + [vp] * 7 + [dbl] * 5 + [vp] * 6
     L.rtmi_render_rays.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, vp, vp, vp, vp, vp]
     L.rtmi_render_rays_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, vp, vp, vp, vp, vp, vp]
+    L.rtmi_test_stage_layout.argtypes = [i32, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

@@ -9,6 +9,7 @@ reference's positional CLI `name nx ny ns` (core.clj:73-80) and the progress/sum
 hit / scatter / emitted / sample / get_ray are the protocol entry points (hitable.clj:7-10,
 shader.clj:22-24, texture.clj:8-9, camera.clj:5-6): each runs the SAME device function the render
 kernel uses, for one call, through the probe entry points of the C-ABI.  Nothing here computes on the CPU."""
+import copy
 import ctypes as C
 import sys
 import time
@@ -237,6 +238,31 @@ def default_context():
     return _default_ctx
 
 
+MATERIAL_FIELDS = ("mat_kind", "mat_tex", "mat_param", "tex_kind", "tex_param", "tex_child", "prim_mat")  # what set_materials replaces
+
+
+def scene_arrays(f, **edit):
+    """A FlatScene as rtmi.h's SceneArrays -> (arrays, args): the contiguous arrays by field name and the 19 C arguments made of them, n_prims
+    first, xform_param last.  edit: arrays that stand in for the FlatScene's own (an edit, marshalled with the rest of the scene it applies to).
+    A scene without the instancing arrays -- one assembled by hand, or with them at another length -- gets "no flips, no instances".
+    `arrays` owns the memory `args` points into: keep it while the arguments are in use."""
+    def field(name, dt, *default):
+        return np.ascontiguousarray(edit[name] if name in edit else getattr(f, name, *default), dt)
+    a = {name: field(name, dt) for name, dt in (
+        ("prim_kind", np.int32), ("prim_geom", np.float64), ("prim_mat", np.int32), ("mat_kind", np.int32), ("mat_tex", np.int32),
+        ("mat_param", np.float64), ("tex_kind", np.int32), ("tex_param", np.float64), ("tex_child", np.int32), ("cam", np.float64))}
+    n = len(a["prim_kind"])
+    for name, dt, shape in (("prim_flip", np.int32, n), ("prim_xform", np.int32, (n, 2)), ("xform_kind", np.int32, 0), ("xform_param", np.float64, (0, 3))):
+        a[name] = field(name, dt, np.zeros(shape))
+    if len(a["prim_flip"]) != n or len(a["prim_xform"]) != n:
+        a["prim_flip"], a["prim_xform"] = np.zeros(n, np.int32), np.zeros((n, 2), np.int32)
+    p = {name: ptr(v) for name, v in a.items()}
+    args = (n, p["prim_kind"], p["prim_geom"], p["prim_mat"], len(a["mat_kind"]), p["mat_kind"], p["mat_tex"], p["mat_param"],
+            len(a["tex_kind"]), p["tex_kind"], p["tex_param"], p["tex_child"], int(f.cam_kind), p["cam"],
+            p["prim_flip"], p["prim_xform"], len(a["xform_kind"]), p["xform_kind"], p["xform_param"])
+    return a, args
+
+
 class DeviceScene:
     """A flattened scene resident in HBM (rtmi_scene)."""
 
@@ -244,23 +270,9 @@ class DeviceScene:
         self.ctx = ctx or default_context()
         self.flat = scene if isinstance(scene, fl.FlatScene) else fl.flatten(scene, camera)
         f = self.flat
-        keep = [np.ascontiguousarray(a, dt) for a, dt in (
-            (f.prim_kind, np.int32), (f.prim_geom, np.float64), (f.prim_mat, np.int32),
-            (f.mat_kind, np.int32), (f.mat_tex, np.int32), (f.mat_param, np.float64),
-            (f.tex_kind, np.int32), (f.tex_param, np.float64), (f.tex_child, np.int32), (f.cam, np.float64))]
         h = C.c_void_p()
-        n = len(keep[0])
-        flip = np.ascontiguousarray(getattr(f, "prim_flip", np.zeros(n)), np.int32)
-        xform = np.ascontiguousarray(getattr(f, "prim_xform", np.zeros((n, 2))), np.int32)
-        xk = np.ascontiguousarray(getattr(f, "xform_kind", np.zeros(0)), np.int32)
-        xp = np.ascontiguousarray(getattr(f, "xform_param", np.zeros((0, 3))), np.float64)
-        if len(flip) != n or len(xform) != n:  # a FlatScene assembled by hand without the instancing arrays
-            flip, xform = np.zeros(n, np.int32), np.zeros((n, 2), np.int32)
-        check(_ffi.lib().rtmi_scene_create_ex(
-            self.ctx.handle, n, ptr(keep[0]), ptr(keep[1]), ptr(keep[2]),
-            len(keep[3]), ptr(keep[3]), ptr(keep[4]), ptr(keep[5]),
-            len(keep[6]), ptr(keep[6]), ptr(keep[7]), ptr(keep[8]), int(f.cam_kind), ptr(keep[9]),
-            ptr(flip), ptr(xform), len(xk), ptr(xk), ptr(xp), C.byref(h)))
+        keep, args = scene_arrays(f)
+        check(_ffi.lib().rtmi_scene_create_ex(self.ctx.handle, *args, C.byref(h)))
         self.handle = h
         if getattr(f, "perlin_vectors", None) is not None:  # perlin.clj:6-17 tables (seeded)
             vec = np.ascontiguousarray(f.perlin_vectors, np.float64)
@@ -327,14 +339,11 @@ class DeviceScene:
         is never waited for: renders queued before keep the old materials.  An edit that would rebuild, or more than
         _ffi.EDIT_STREAM_MAX_BYTES of changed rows, raises RtmiError -3 and changes nothing.  ValueError if the primitive count differs.
         self.flat is replaced by a copy that holds the new arrays (clones share the old one and keep it)."""
-        import copy
         f = scene_or_flat if isinstance(scene_or_flat, fl.FlatScene) else fl.flatten(scene_or_flat)
         if len(f.prim_mat) != len(self.flat.prim_kind):
             raise ValueError("the edit has %d primitives, the scene %d" % (len(f.prim_mat), len(self.flat.prim_kind)))
-        mk, mt, mp, tk, tp, tc, pm = (np.ascontiguousarray(a, dt) for a, dt in (
-            (f.mat_kind, np.int32), (f.mat_tex, np.int32), (f.mat_param, np.float64), (f.tex_kind, np.int32), (f.tex_param, np.float64),
-            (f.tex_child, np.int32), (f.prim_mat, np.int32)))
-        args = (self.handle, len(mk), ptr(mk), ptr(mt), ptr(mp), len(tk), ptr(tk), ptr(tp), ptr(tc), ptr(pm))
+        a, all_args = scene_arrays(self.flat, **{name: getattr(f, name) for name in MATERIAL_FIELDS})
+        args = (self.handle,) + all_args[4:12] + (all_args[3],)  # n_mats + 3 arrays, n_tex + 3 arrays, prim_mat
         rebuilt = C.c_int32()
         if stream is not None:
             handle = getattr(stream, "cuda_stream", stream)
@@ -342,8 +351,9 @@ class DeviceScene:
         else:
             check(_ffi.lib().rtmi_scene_set_materials(*args, C.byref(rebuilt)))
         flat = copy.copy(self.flat)
-        flat.mat_kind, flat.mat_tex, flat.mat_param, flat.tex_kind, flat.tex_param, flat.tex_child, flat.prim_mat = (
-            mk.copy(), mt.copy(), mp.copy(), tk.copy(), tp.reshape(-1, fl.TEX_STRIDE).copy(), tc.reshape(-1, 2).copy(), pm.copy())
+        for name in MATERIAL_FIELDS:
+            setattr(flat, name, a[name].copy())
+        flat.tex_param, flat.tex_child = flat.tex_param.reshape(-1, fl.TEX_STRIDE), flat.tex_child.reshape(-1, 2)
         self.flat = flat
         return bool(rebuilt.value)
 
@@ -376,7 +386,6 @@ class DeviceScene:
         leaves the entry-grid cells it was built into is displaced into the list of primitives every ray tests first ("displaced": how many
         are there now); a rebuild brings them home.  ValueError, before the library is touched, if counts, kinds, flips or the instance
         structure differ.  self.flat is replaced by a copy that holds the new arrays (clones share the old one and keep it)."""
-        import copy
         if mode not in ("auto", "rebuild"):
             raise ValueError("mode must be 'auto' or 'rebuild'")
         pg, xp = self._geometry_arrays(scene_or_flat)

@@ -1567,7 +1567,8 @@ struct rtmi_ctx {
     int scan_variant = SCAN_SGPR_CULL;
     int max_lds_bytes = 64 * 1024 - 64; // static-sphere LDS tile budget per workgroup
     // workspace
-    DevBuf samples, accum, tiles, tile_ids, counters, scratch_lin;
+    DevBuf samples, accum, tiles, tile_ids, counters;
+    DevBuf io;    // every host form's staging (HostIo): idle between calls, each of which ends with the stream synchronised
     DevBuf multi; // rtmi_render_multi*: this replica's record (tiles + counters); on replica 0 the gathered records of all replicas
     hipEvent_t ev_done = nullptr, ev_g0 = nullptr, ev_g1 = nullptr; // multi-device: render finished / gather interval on replica 0
     bool have_gather = false;
@@ -1595,10 +1596,9 @@ struct rtmi_ctx {
     hipStream_t last_stream = nullptr; // stream of the most recent render (rtmi_last_traversal_counters synchronises on it)
     long long tile_valid_pixels = 0;
     ProgFrame prog; // at most one progressive frame per context
-    DevBuf feat_out, feat_cnt; // rtmi_render_features*: the host form's result, the counters nobody asked for
-    DevBuf dn_planes, dn_io;   // rtmi_denoise*: the filter's planes (two colour + variance sets, the feature planes), the host form's buffers
-    DevBuf rp_io;              // rtmi_reproject: the host form's buffers (the device form owns nothing)
-    DevBuf rays_ws, rays_io;   // rtmi_render_rays*: the per-ray radiance nobody asked for (one pass of it), the host form's buffers
+    DevBuf feat_cnt;  // rtmi_render_features_device: the counters nobody asked for
+    DevBuf dn_planes; // rtmi_denoise*: the filter's planes (two colour + variance sets, the feature planes)
+    DevBuf rays_ws;   // rtmi_render_rays*: the per-ray radiance nobody asked for (one pass of it)
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     int events_used = 0;
@@ -1737,6 +1737,45 @@ int next_event_pair(rtmi_ctx *c, hipEvent_t *a, hipEvent_t *b) {
     *a = c->events[(size_t)c->events_used].first;
     *b = c->events[(size_t)c->events_used].second;
     c->events_used++;
+    return RTMI_OK;
+}
+
+// RTMI_FLAG_TIMING: the interval of one launch on `st`.  open_timed records its first event; *e1 = the event the caller records behind the kernel
+// (null: not timed).  close_timed_fold records the event behind the fold that follows that kernel (rtmi_last_reduce_ms).
+int open_timed(rtmi_ctx *c, hipStream_t st, hipEvent_t *e1) {
+    hipEvent_t e0 = nullptr;
+    *e1 = nullptr;
+    if (!(c->flags & RTMI_FLAG_TIMING) || c->events_used >= 8192) return RTMI_OK;
+    const int rc = next_event_pair(c, &e0, e1);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(e0, st));
+    return RTMI_OK;
+}
+int close_timed_fold(rtmi_ctx *c, hipStream_t st) {
+    const size_t k = (size_t)c->events_used - 1;
+    while (c->events_r.size() <= k) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->events_r.push_back(e); }
+    HIP_TRY(hipEventRecord(c->events_r[k], st));
+    return RTMI_OK;
+}
+
+// Workgroups of `block` threads and lds_bytes of dynamic LDS that stay resident per CU.  The occupancy query is a runtime call per launch and
+// replica: asked once per (kernel, LDS bytes) and kept on the context.
+int resident_blocks(rtmi_ctx *c, const void *kern, int block, size_t lds_bytes, int *resident) {
+    const std::pair<const void *, size_t> key(kern, lds_bytes);
+    auto it = c->occupancy.find(key);
+    if (it == c->occupancy.end()) {
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(resident, kern, block, lds_bytes));
+        c->occupancy.emplace(key, *resident);
+    } else *resident = it->second;
+    return RTMI_OK;
+}
+
+// the stream of a call: the caller's, or the context's own
+hipStream_t stream_of(const rtmi_ctx *c, void *stream) { return stream ? reinterpret_cast<hipStream_t>(stream) : c->stream; }
+
+// the output region [x0, x1) x [y0, y1) of a host form must lie inside the frame and hold a pixel
+int check_region(int nx, int ny, int x0, int y0, int x1, int y1) {
+    if (x0 < 0 || y0 < 0 || x1 > nx || y1 > ny || x1 <= x0 || y1 <= y0) return fail(RTMI_E_ARG, "region [%d,%d)x[%d,%d) outside %dx%d", x0, x1, y0, y1, nx, ny);
     return RTMI_OK;
 }
 
@@ -1961,12 +2000,9 @@ int size_sample_passes(rtmi_ctx *c, int n_local, int ns, size_t real_bytes, int 
 int launch_trace_pass(rtmi_scene *s, const TracePlan &plan, TraceParams &tp, int s_begin, int s_count, hipStream_t st, hipEvent_t *out_e1) {
     rtmi_ctx *c = s->ctx;
     tp.s_begin = s_begin; tp.s_count = s_count;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if ((c->flags & RTMI_FLAG_TIMING) && c->events_used < 8192) {
-        const int rc = next_event_pair(c, &e0, &e1);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(e0, st));
-    }
+    hipEvent_t e1 = nullptr;
+    int rc = open_timed(c, st, &e1);
+    if (rc) return rc;
     tp.total_items = (unsigned)((long long)tp.n_local_tiles * s_count * 64);
     { // claim size: one global atomic per claim -- 256 items on small launches (a short tail matters more), up to 1024 when a wave has
       // thousands of claims ahead of it (C3: 129 000 items per wave)
@@ -1981,14 +2017,8 @@ int launch_trace_pass(rtmi_scene *s, const TracePlan &plan, TraceParams &tp, int
     HIP_TRY(hipMemsetAsync(tp.queue, 0, sizeof(unsigned), st));
     // persistent launch: as many workgroups as stay resident (at most blocks_per_cu per CU); the queue feeds them
     int resident = 0;
-    { // the occupancy query is a runtime call per launch and replica: asked once per (kernel, LDS bytes) and kept on the context
-        const std::pair<const void *, size_t> key(reinterpret_cast<const void *>(plan.kern), plan.lds.bytes);
-        auto it = c->occupancy.find(key);
-        if (it == c->occupancy.end()) {
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, plan.kern, kTraceBlock, plan.lds.bytes));
-            c->occupancy.emplace(key, resident);
-        } else resident = it->second;
-    }
+    rc = resident_blocks(c, reinterpret_cast<const void *>(plan.kern), kTraceBlock, plan.lds.bytes, &resident);
+    if (rc) return rc;
     const int grid_trace = std::max(1, c->cus * std::max(1, std::min(c->blocks_per_cu * (256 / kTraceBlock), resident)));
     if (c->last_grid != grid_trace && std::getenv("RTMI_DEBUG"))
         fprintf(stderr, "[rtmi] trace launch: %d workgroups of %d threads (%d resident per CU by the occupancy query, cap %d), %zu B LDS each\n",
@@ -2027,12 +2057,7 @@ int launch_fold(rtmi_ctx *c, const TraceParams &tp, int ns, int s_end, void *d_t
                            reinterpret_cast<double *>(d_tiles_linear), tp.tile_ids, tp.tiles_x, tp.nx, tp.ny, tp.n_local_tiles, tp.s_begin, tp.s_count, ns,
                            count_pixels ? tp.counters : nullptr, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1);
     HIP_TRY(hipGetLastError());
-    if (e1) {
-        const size_t k = (size_t)c->events_used - 1;
-        while (c->events_r.size() <= k) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->events_r.push_back(e); }
-        HIP_TRY(hipEventRecord(c->events_r[k], st));
-    }
-    return RTMI_OK;
+    return e1 ? close_timed_fold(c, st) : RTMI_OK;
 }
 
 // The sample passes of a render: samples [s_first, s_end) of every pixel of the local tiles, as many per pass as the sample buffer holds, each pass one
@@ -2124,38 +2149,63 @@ int check_render_args(rtmi_scene *s, int nx, int ny, int ns, int depth, int prec
     return RTMI_OK;
 }
 
-// The host forms' staging: device planes for npx pixels carved out of c->scratch_lin -- linear [npx][3] doubles, stderr [npx] doubles, the two
-// metrics counters, samples [npx] ints, rgb8 [npx][3] bytes, in that order, so every plane is aligned to its element size.  linear and rgb8
-// always; the others where wanted (else null).  copy_back brings every plane the caller gave a host array for back; the stream is idle by then.
-struct HostStage {
-    size_t npx = 0;
+// The host forms' staging.  A call names its planes -- element count and the host arrays to copy from (`up`) and to (`down`), either or both null --
+// then reserve() lays them out in c->io, every plane on a multiple of 16 bytes whatever the order, and hands out the device pointers.  A plane that
+// is not present takes no space and its device pointer is null: what the *_impl functions take for "not given".  upload() and download() synchronise
+// the context's stream once and copy every present plane that has a host array on that side; they return the first HIP error, so each entry keeps
+// its own failure action.
+struct IoPlane { size_t elem, count; bool present; const void *up; void *down; void **dev; size_t off; };
+
+// where each plane starts (IoPlane::off); returns the bytes the arena needs
+size_t io_layout(IoPlane *pl, int n) {
+    size_t at = 0;
+    for (int i = 0; i < n; ++i) { pl[i].off = at; if (pl[i].present) at += (pl[i].elem * pl[i].count + 15) & ~(size_t)15; }
+    return at;
+}
+
+struct HostIo {
+    rtmi_ctx *c;
+    IoPlane pl[16]; // (rtmi_reproject names twelve)
+    int n = 0;
+    explicit HostIo(rtmi_ctx *ctx) : c(ctx) {}
+    template <typename T> void plane(T **dev, size_t count, bool present, const void *up, void *down) { pl[n++] = {sizeof(T), count, present, up, down, reinterpret_cast<void **>(dev), 0}; }
+    template <typename T> void in(T **dev, size_t count, const void *host) { plane(dev, count, host != nullptr, host, nullptr); } // an input, optional
+    template <typename T> void out(T **dev, size_t count, void *host) { plane(dev, count, host != nullptr, nullptr, host); }     // an output, optional
+    template <typename T> void work(T **dev, size_t count, void *host) { plane(dev, count, true, nullptr, host); } // the device side needs it; copied back where asked for
+    int reserve() {
+        const int rc = c->io.ensure(io_layout(pl, n));
+        for (int i = 0; i < n && !rc; ++i) *pl[i].dev = pl[i].present ? static_cast<char *>(c->io.p) + pl[i].off : nullptr;
+        return rc;
+    }
+    hipError_t copy(bool up) const {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        for (int i = 0; i < n && e == hipSuccess; ++i) {
+            const IoPlane &p = pl[i];
+            if (p.present && up && p.up) e = hipMemcpy(*p.dev, p.up, p.elem * p.count, hipMemcpyHostToDevice);
+            if (p.present && !up && p.down) e = hipMemcpy(p.down, *p.dev, p.elem * p.count, hipMemcpyDeviceToHost);
+        }
+        return e;
+    }
+    hipError_t upload() const { return copy(true); }
+    hipError_t download() const { return copy(false); }
+    // the entries without a failure action of their own: reserve() and upload() before the launches, download() behind them
+    int stage() { const int rc = reserve(); if (rc) return rc; HIP_TRY(upload()); return RTMI_OK; }
+    int finish() const { HIP_TRY(hipGetLastError()); HIP_TRY(download()); return RTMI_OK; }
+};
+
+// The planes of the frame host forms, for npx pixels: linear [npx][3] doubles and rgb8 [npx][3] bytes always; stderr [npx] doubles, the two metrics
+// counters and samples [npx] ints where wanted (else null).  Each comes back to the host array the caller gave for it.  (A progressive frame keeps
+// its counters in its own buffer: those forms want no plane and copy from there.)
+struct FramePlanes {
     double *lin = nullptr, *err = nullptr;
     u64 *cnt = nullptr;
     int *smp = nullptr;
     unsigned char *q = nullptr;
-    int ensure(rtmi_ctx *c, size_t n, bool want_err, bool want_cnt, bool want_smp) {
-        const size_t b_lin = n * 3 * sizeof(double), b_err = want_err ? n * sizeof(double) : 0, b_cnt = want_cnt ? 2 * sizeof(u64) : 0;
-        const size_t b_smp = want_smp ? n * sizeof(int) : 0;
-        const int rc = c->scratch_lin.ensure(b_lin + b_err + b_cnt + b_smp + n * 3 + 64);
-        if (rc) return rc;
-        char *base = reinterpret_cast<char *>(c->scratch_lin.p);
-        npx = n;
-        lin = reinterpret_cast<double *>(base);
-        err = want_err ? reinterpret_cast<double *>(base + b_lin) : nullptr;
-        cnt = want_cnt ? reinterpret_cast<u64 *>(base + b_lin + b_err) : nullptr;
-        smp = want_smp ? reinterpret_cast<int *>(base + b_lin + b_err + b_cnt) : nullptr;
-        q = reinterpret_cast<unsigned char *>(base + b_lin + b_err + b_cnt + b_smp);
-        return RTMI_OK;
-    }
-    // d_cnt: where the call's counters are (this stage's plane, or a frame's own)
-    hipError_t copy_back(double *out_linear, uint8_t *out_rgb8, double *out_stderr, int32_t *out_samples, uint64_t *out_counters, const void *d_cnt) const {
-        hipError_t e = hipSuccess;
-        if (out_linear) e = hipMemcpy(out_linear, lin, npx * 3 * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && out_rgb8) e = hipMemcpy(out_rgb8, q, npx * 3, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && out_stderr) e = hipMemcpy(out_stderr, err, npx * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && out_samples) e = hipMemcpy(out_samples, smp, npx * sizeof(int), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && out_counters) e = hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost);
-        return e;
+    int reserve(HostIo &io, size_t npx, bool want_err, bool want_cnt, bool want_smp, double *out_linear, uint8_t *out_rgb8, double *out_stderr,
+                int32_t *out_samples, uint64_t *out_counters) {
+        io.work(&lin, npx * 3, out_linear); io.plane(&err, npx, want_err, nullptr, out_stderr); io.plane(&cnt, 2, want_cnt, nullptr, out_counters);
+        io.plane(&smp, npx, want_smp, nullptr, out_samples); io.work(&q, npx * 3, out_rgb8);
+        return io.reserve();
     }
 };
 
@@ -2196,6 +2246,16 @@ RTMI_EXPORT int rtmi_test_camera_fixed(int32_t cam_kind, const double *cam) { //
     return o | (camera_fixed_rays(cam_kind, o, cam) << 1);
 }
 RTMI_EXPORT int rtmi_test_half_outward(double x, int32_t up) { return (int)half_outward((float)x, up != 0); } // test hook (host arithmetic only: no device needed)
+// test hook, host code only (no device): where HostIo puts n planes of elem_bytes[i] * counts[i] bytes (present[i] = 0: the caller left the plane out).
+// out_offsets[i] = the plane's first byte in the arena (UINT64_MAX for an absent plane), out_total = the bytes the arena needs
+RTMI_EXPORT int rtmi_test_stage_layout(int32_t n, const uint64_t *elem_bytes, const uint64_t *counts, const int32_t *present, uint64_t *out_offsets, uint64_t *out_total) {
+    if (n < 0 || (n && (!elem_bytes || !counts || !present || !out_offsets)) || !out_total) return fail(RTMI_E_ARG, "bad arguments");
+    std::vector<IoPlane> pl((size_t)n);
+    for (int i = 0; i < n; ++i) pl[(size_t)i] = {(size_t)elem_bytes[i], (size_t)counts[i], present[i] != 0, nullptr, nullptr, nullptr, 0};
+    *out_total = io_layout(pl.data(), n);
+    for (int i = 0; i < n; ++i) out_offsets[i] = pl[(size_t)i].present ? pl[(size_t)i].off : UINT64_MAX;
+    return RTMI_OK;
+}
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
 RTMI_EXPORT int rtmi_version(void) { return 215; } // 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
@@ -2235,9 +2295,9 @@ RTMI_EXPORT int rtmi_shutdown(rtmi_ctx *c) {
 #ifdef RTMI_HIST
     { unsigned long long h[200]; if (hipMemcpyFromSymbol(h, HIP_SYMBOL(rtmi::g_hist), sizeof h) == hipSuccess) { for (int k = 0; k < 3; ++k) { fprintf(stderr, "HIST%d", k); for (int i = 0; i <= 64; ++i) fprintf(stderr, " %llu", h[64 * k + i]); fprintf(stderr, "\n"); } } }
 #endif
-    c->samples.release(); c->accum.release(); c->tiles.release(); c->tile_ids.release(); c->counters.release(); c->scratch_lin.release(); c->multi.release();
+    c->samples.release(); c->accum.release(); c->tiles.release(); c->tile_ids.release(); c->counters.release(); c->io.release(); c->multi.release();
     c->prog.release();
-    c->feat_out.release(); c->feat_cnt.release(); c->dn_planes.release(); c->dn_io.release(); c->rp_io.release(); c->rays_ws.release(); c->rays_io.release();
+    c->feat_cnt.release(); c->dn_planes.release(); c->rays_ws.release();
     for (hipEvent_t e : {c->ev_done, c->ev_g0, c->ev_g1}) if (e) (void)hipEventDestroy(e);
     if (c->ev_consumed) { (void)hipSetDevice(c->ev_consumed_device); (void)hipEventDestroy(c->ev_consumed); (void)hipSetDevice(c->device); }
     for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -3408,7 +3468,7 @@ RTMI_EXPORT int rtmi_render_tiles_device(rtmi_scene *s, int32_t nx, int32_t ny, 
     if (tile_first < 0 || tile_stride <= 0) return fail(RTMI_E_ARG, "tile_first must be >= 0 and tile_stride > 0");
     if (!d_tiles_linear) return fail(RTMI_E_ARG, "d_tiles_linear is NULL");
     HIP_TRY(hipSetDevice(s->ctx->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
+    hipStream_t st = stream_of(s->ctx, stream);
     return with_real(precision, [&](auto r) { return render_tiles_impl<decltype(r)>(s, nx, ny, ns, depth, seed, tile_first, tile_stride, nullptr, d_tiles_linear, d_out_counters, st); });
 }
 
@@ -3419,7 +3479,7 @@ RTMI_EXPORT int rtmi_assemble_device(rtmi_ctx *c, int32_t nx, int32_t ny, int32_
     const int ntiles = tiles_x_of(nx) * tiles_y_of(ny);
     if ((long long)world * tiles_per_rank < ntiles) return fail(RTMI_E_ARG, "world*tiles_per_rank (%d*%d) does not cover %d tiles", world, tiles_per_rank, ntiles);
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     const long long npx = (long long)nx * ny;
     // the 8-bit quantiser always runs in double on the double mean: both precisions share it
     hipLaunchKernelGGL((assemble_kernel<double>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
@@ -3447,8 +3507,8 @@ RTMI_EXPORT int rtmi_render_device(rtmi_scene *s, int32_t nx, int32_t ny, int32_
 RTMI_EXPORT int rtmi_render(rtmi_scene *s, int32_t nx, int32_t ny, int32_t ns, int32_t depth, uint64_t seed, int32_t precision,
                             int32_t x0, int32_t y0, int32_t x1, int32_t y1, double *out_linear, uint8_t *out_rgb8, uint64_t *out_counters) {
     int rc = check_render_args(s, nx, ny, ns, depth, precision);
+    if (!rc) rc = check_region(nx, ny, x0, y0, x1, y1);
     if (rc) return rc;
-    if (x0 < 0 || y0 < 0 || x1 > nx || y1 > ny || x1 <= x0 || y1 <= y0) return fail(RTMI_E_ARG, "region [%d,%d)x[%d,%d) outside %dx%d", x0, x1, y0, y1, nx, ny);
     rtmi_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     // only the 8x8 tiles that intersect the region are rendered, and only the region's pixels in them are traced: both
@@ -3459,19 +3519,17 @@ RTMI_EXPORT int rtmi_render(rtmi_scene *s, int32_t nx, int32_t ny, int32_t ns, i
     const size_t npx = (size_t)w * h;
     rc = c->tiles.ensure((size_t)nwin * 64 * 3 * sizeof(double));
     if (rc) return rc;
-    HostStage stage;
-    rc = stage.ensure(c, npx, false, true, false);
+    HostIo io(c);
+    FramePlanes d;
+    rc = d.reserve(io, npx, false, true, false, out_linear, out_rgb8, nullptr, nullptr, out_counters);
     if (rc) return rc;
     const int rg[4] = {x0, y0, x1, y1};
     hipStream_t st = c->stream;
-    rc = with_real(precision, [&](auto r) { return render_tiles_impl<decltype(r)>(s, nx, ny, ns, depth, seed, 0, 1, rg, c->tiles.p, stage.cnt, st); });
+    rc = with_real(precision, [&](auto r) { return render_tiles_impl<decltype(r)>(s, nx, ny, ns, depth, seed, 0, 1, rg, c->tiles.p, d.cnt, st); });
     if (rc) return rc;
     hipLaunchKernelGGL((assemble_region_kernel<double>), dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       reinterpret_cast<const double *>(c->tiles.p), tx0, ty0, wtx, x0, y0, w, h, stage.lin, stage.q);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(stage.copy_back(out_linear, out_rgb8, nullptr, nullptr, out_counters, stage.cnt));
-    return RTMI_OK;
+                       reinterpret_cast<const double *>(c->tiles.p), tx0, ty0, wtx, x0, y0, w, h, d.lin, d.q);
+    return io.finish();
 }
 
 // ---- progressive rendering: a frame refined over calls ----------------------------------------------------------------
@@ -3561,7 +3619,7 @@ RTMI_EXPORT int rtmi_render_progressive_device(rtmi_scene *s, int32_t nx, int32_
     if (!rc) rc = check_no_tile_retired(s->ctx, s_first);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(s->ctx->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
+    hipStream_t st = stream_of(s->ctx, stream);
     double *lin = reinterpret_cast<double *>(d_out_linear), *err = reinterpret_cast<double *>(d_out_stderr);
     unsigned char *q = reinterpret_cast<unsigned char *>(d_out_rgb8);
     return with_real(precision, [&](auto r) { return render_progressive_impl<decltype(r)>(s, key, s_first, s_count, lin, q, err, d_out_counters, st); });
@@ -3571,8 +3629,8 @@ RTMI_EXPORT int rtmi_render_progressive(rtmi_scene *s, int32_t nx, int32_t ny, i
                                         int32_t precision, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
                                         double *out_linear, uint8_t *out_rgb8, double *out_stderr, uint64_t *out_counters) {
     int rc = check_progressive_args(s, nx, ny, s_first, s_count, depth, precision);
+    if (!rc) rc = check_region(nx, ny, x0, y0, x1, y1);
     if (rc) return rc;
-    if (x0 < 0 || y0 < 0 || x1 > nx || y1 > ny || x1 <= x0 || y1 <= y0) return fail(RTMI_E_ARG, "region [%d,%d)x[%d,%d) outside %dx%d", x0, x1, y0, y1, nx, ny);
     const int rg[4] = {x0, y0, x1, y1};
     const ProgKey key = progressive_key(s, nx, ny, depth, seed, precision, rg);
     rtmi_ctx *c = s->ctx;
@@ -3580,14 +3638,15 @@ RTMI_EXPORT int rtmi_render_progressive(rtmi_scene *s, int32_t nx, int32_t ny, i
     if (!rc) rc = check_no_tile_retired(c, s_first);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    HostStage stage;
-    rc = stage.ensure(c, (size_t)(x1 - x0) * (size_t)(y1 - y0), true, false, false);
+    HostIo io(c);
+    FramePlanes d;
+    rc = d.reserve(io, (size_t)(x1 - x0) * (size_t)(y1 - y0), true, false, false, out_linear, out_rgb8, out_stderr, nullptr, nullptr);
     if (rc) return rc;
     hipStream_t st = c->stream;
-    rc = with_real(precision, [&](auto r) { return render_progressive_impl<decltype(r)>(s, key, s_first, s_count, stage.lin, stage.q, stage.err, nullptr, st); });
+    rc = with_real(precision, [&](auto r) { return render_progressive_impl<decltype(r)>(s, key, s_first, s_count, d.lin, d.q, d.err, nullptr, st); });
     if (rc) return rc;
-    hipError_t e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = stage.copy_back(out_linear, out_rgb8, out_stderr, nullptr, out_counters, c->prog.counters.p);
+    hipError_t e = io.download();
+    if (e == hipSuccess && out_counters) e = hipMemcpy(out_counters, c->prog.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToHost);
     if (e != hipSuccess) { c->prog.k = 0; return fail(RTMI_E_DEVICE, "progressive render: %s", hipGetErrorString(e)); }
     return RTMI_OK;
 }
@@ -3650,7 +3709,7 @@ RTMI_EXPORT int rtmi_render_adaptive_device(rtmi_scene *s, int32_t nx, int32_t n
     rc = check_continuation(s->ctx, key, s_first);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(s->ctx->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
+    hipStream_t st = stream_of(s->ctx, stream);
     double *lin = reinterpret_cast<double *>(d_out_linear), *err = reinterpret_cast<double *>(d_out_stderr);
     unsigned char *q = reinterpret_cast<unsigned char *>(d_out_rgb8);
     int *smp = reinterpret_cast<int *>(d_out_samples);
@@ -3661,21 +3720,23 @@ RTMI_EXPORT int rtmi_render_adaptive(rtmi_scene *s, int32_t nx, int32_t ny, int3
                                      int32_t precision, int32_t x0, int32_t y0, int32_t x1, int32_t y1, double *out_linear, uint8_t *out_rgb8,
                                      double *out_stderr, int32_t *out_samples, uint64_t *out_counters) {
     int rc = check_adaptive_args(s, nx, ny, s_first, s_count, eps, depth, precision);
+    if (!rc) rc = check_region(nx, ny, x0, y0, x1, y1);
     if (rc) return rc;
-    if (x0 < 0 || y0 < 0 || x1 > nx || y1 > ny || x1 <= x0 || y1 <= y0) return fail(RTMI_E_ARG, "region [%d,%d)x[%d,%d) outside %dx%d", x0, x1, y0, y1, nx, ny);
     const int rg[4] = {x0, y0, x1, y1};
     const ProgKey key = progressive_key(s, nx, ny, depth, seed, precision, rg);
     rtmi_ctx *c = s->ctx;
     rc = check_continuation(c, key, s_first);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    HostStage stage;
-    rc = stage.ensure(c, (size_t)(x1 - x0) * (size_t)(y1 - y0), true, false, true);
+    HostIo io(c);
+    FramePlanes d;
+    rc = d.reserve(io, (size_t)(x1 - x0) * (size_t)(y1 - y0), true, false, true, out_linear, out_rgb8, out_stderr, out_samples, nullptr);
     if (rc) return rc;
     hipStream_t st = c->stream;
-    rc = with_real(precision, [&](auto r) { return render_adaptive_impl<decltype(r)>(s, key, s_first, s_count, eps, stage.lin, stage.q, stage.err, stage.smp, nullptr, st); });
+    rc = with_real(precision, [&](auto r) { return render_adaptive_impl<decltype(r)>(s, key, s_first, s_count, eps, d.lin, d.q, d.err, d.smp, nullptr, st); });
     if (rc) return rc;
-    const hipError_t e = stage.copy_back(out_linear, out_rgb8, out_stderr, out_samples, out_counters, c->prog.counters.p); // (the stream is synchronised)
+    hipError_t e = io.download(); // (the stream is synchronised already)
+    if (e == hipSuccess && out_counters) e = hipMemcpy(out_counters, c->prog.counters.p, 2 * sizeof(u64), hipMemcpyDeviceToHost);
     if (e != hipSuccess) { c->prog.k = 0; return fail(RTMI_E_DEVICE, "adaptive render: %s", hipGetErrorString(e)); }
     return RTMI_OK;
 }
@@ -3764,7 +3825,7 @@ RTMI_EXPORT int rtmi_adaptive_retire_device(rtmi_ctx *c, int32_t nx, int32_t ny,
     rc = check_retire_frame(c, nx, ny);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return adaptive_retire_impl(c, reinterpret_cast<const double *>(d_noise), eps, out_retired, st);
 }
 
@@ -3780,13 +3841,12 @@ RTMI_EXPORT int rtmi_adaptive_retire(rtmi_ctx *c, int32_t nx, int32_t ny, const 
         if (out_retired) *out_retired = 0;
         return RTMI_OK;
     }
-    const size_t n = (size_t)nx * (size_t)ny;
-    rc = c->dn_io.ensure(n * sizeof(double)); // the host forms' staging buffer for maps of the frame's size
+    HostIo io(c);
+    double *d_noise;
+    io.in(&d_noise, (size_t)nx * (size_t)ny, noise);
+    rc = io.stage();
     if (rc) return rc;
-    hipStream_t st = c->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(c->dn_io.p, noise, n * sizeof(double), hipMemcpyHostToDevice));
-    return adaptive_retire_impl(c, reinterpret_cast<const double *>(c->dn_io.p), eps, out_retired, st);
+    return adaptive_retire_impl(c, d_noise, eps, out_retired, c->stream);
 }
 
 // ---- one host process, several GPUs (the reference's host is ONE JVM: core.clj:100-108) ---------------------------------
@@ -4063,14 +4123,14 @@ RTMI_EXPORT int rtmi_render_multi(int32_t n, rtmi_scene *const *scenes, int32_t 
     DeviceGuard guard;
     rtmi_ctx *c0 = scenes[0]->ctx;
     HIP_TRY(hipSetDevice(c0->device));
-    HostStage stage;
-    int rc = stage.ensure(c0, (size_t)nx * (size_t)ny, false, true, false);
+    HostIo io(c0);
+    FramePlanes d;
+    int rc = d.reserve(io, (size_t)nx * (size_t)ny, false, true, false, out_linear, out_rgb8, nullptr, nullptr, out_counters);
     if (rc) return rc;
-    rc = rtmi_render_multi_device(n, scenes, nx, ny, ns, depth, seed, precision, stage.lin, stage.q, stage.cnt);
+    rc = rtmi_render_multi_device(n, scenes, nx, ny, ns, depth, seed, precision, d.lin, d.q, d.cnt);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c0->device));
-    HIP_TRY(hipStreamSynchronize(c0->stream)); // ordered after every replica's render through the gather
-    HIP_TRY(stage.copy_back(out_linear, out_rgb8, nullptr, nullptr, out_counters, stage.cnt));
+    HIP_TRY(io.download()); // replica 0's stream is ordered after every replica's render through the gather
     for (int r = 1; r < n; ++r) { HIP_TRY(hipSetDevice(scenes[r]->ctx->device)); HIP_TRY(hipStreamSynchronize(scenes[r]->ctx->stream)); scenes[r]->ctx->consume_pending = false; }
     return RTMI_OK;
 }
@@ -4159,7 +4219,7 @@ RTMI_EXPORT int rtmi_render_adaptive_tiles_device(rtmi_scene *s, int32_t nx, int
     rc = check_dealt_continuation(s->ctx, key, s_first, retire);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(s->ctx->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : s->ctx->stream;
+    hipStream_t st = stream_of(s->ctx, stream);
     const int n_slots = rtmi_local_tiles(nx, ny, tile_first, tile_stride);
     double *rec = reinterpret_cast<double *>(d_tiles_rec);
     rc = with_real(precision, [&](auto r) { return dealt_launch<decltype(r)>(s, key, s_first, s_count, retire, eps, rec, n_slots, d_out_counters, st); });
@@ -4175,7 +4235,7 @@ RTMI_EXPORT int rtmi_assemble_progressive_device(rtmi_ctx *c, int32_t nx, int32_
     const int ntiles = tiles_x_of(nx) * tiles_y_of(ny);
     if ((long long)world * tiles_per_rank < ntiles) return fail(RTMI_E_ARG, "world*tiles_per_rank (%d*%d) does not cover %d tiles", world, tiles_per_rank, ntiles);
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     const long long npx = (long long)nx * ny;
     hipLaunchKernelGGL(assemble_progressive_kernel, dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
                        reinterpret_cast<const double *>(d_gathered_rec), world, (size_t)tiles_per_rank * 64 * RTMI_PROG_REC, tiles_x_of(nx), nx, ny,
@@ -4285,13 +4345,14 @@ RTMI_EXPORT int rtmi_render_multi_adaptive(int32_t n, rtmi_scene *const *scenes,
     DeviceGuard guard;
     rtmi_ctx *c0 = scenes[0]->ctx;
     HIP_TRY(hipSetDevice(c0->device));
-    HostStage stage;
-    int rc = stage.ensure(c0, (size_t)nx * (size_t)ny, true, true, true);
+    HostIo io(c0);
+    FramePlanes d;
+    int rc = d.reserve(io, (size_t)nx * (size_t)ny, true, true, true, out_linear, out_rgb8, out_stderr, out_samples, out_counters);
     if (rc) return rc;
-    rc = rtmi_render_multi_adaptive_device(n, scenes, nx, ny, s_first, s_count, retire, eps, depth, seed, precision, stage.lin, stage.q, stage.err, stage.smp, stage.cnt);
+    rc = rtmi_render_multi_adaptive_device(n, scenes, nx, ny, s_first, s_count, retire, eps, depth, seed, precision, d.lin, d.q, d.err, d.smp, d.cnt);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(c0->device)); // (every replica's stream is synchronised)
-    const hipError_t e = stage.copy_back(out_linear, out_rgb8, out_stderr, out_samples, out_counters, stage.cnt);
+    const hipError_t e = io.download();
     if (e != hipSuccess) {
         for (int r = 0; r < n; ++r) scenes[r]->ctx->prog.k = 0;
         return fail(RTMI_E_DEVICE, "multi-device adaptive render: %s", hipGetErrorString(e));
@@ -4384,28 +4445,32 @@ RTMI_EXPORT int rtmi_last_reduce_ms(rtmi_ctx *c, double *ms, int32_t *launches) 
 
 // ---- probes ---------------------------------------------------------------------------------------------
 namespace {
-struct Tmp { // scoped device temporaries for the (synchronous) probe entry points
-    std::vector<void *> ptrs;
-    ~Tmp() { for (void *p : ptrs) (void)hipFree(p); }
-    void *alloc(size_t bytes) { void *p = nullptr; if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr; ptrs.push_back(p); return p; }
-    void *up(const void *src, size_t bytes) { void *p = alloc(bytes); if (p && src && bytes) if (hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr; return p; }
-};
-#define PROBE_PROLOGUE(scene_)                                                             \
-    if (!scene_ok(scene_)) return fail(RTMI_E_STATE, "invalid scene handle");             \
-    if (precision != RTMI_F64 && precision != RTMI_F32) return fail(RTMI_E_ARG, "bad precision"); \
-    if (n < 0) return fail(RTMI_E_ARG, "n < 0");                                           \
-    if (n == 0) return RTMI_OK;                                                            \
-    rtmi_ctx *c = (scene_)->ctx;                                                           \
-    HIP_TRY(hipSetDevice(c->device));                                                      \
-    Tmp tmp;                                                                               \
-    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-#define PROBE_EPILOGUE()                      \
-    HIP_TRY(hipGetLastError());               \
-    HIP_TRY(hipStreamSynchronize(c->stream));
+// What every probe of a scene checks first; then the scene's device is current.  n = 0 passes: the caller returns RTMI_OK at once.
+int probe_begin(rtmi_scene *s, int precision, int n) {
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    if (precision != RTMI_F64 && precision != RTMI_F32) return fail(RTMI_E_ARG, "bad precision");
+    if (n < 0) return fail(RTMI_E_ARG, "n < 0");
+    if (n > 0) HIP_TRY(hipSetDevice(s->ctx->device));
+    return RTMI_OK;
+}
+// A probe once its planes are named: the inputs go up, launch(stream, grid) starts the kernel over n items, the outputs come back.
+template <typename Launch> int probe_run(HostIo &io, int n, Launch launch) {
+    const int rc = io.stage();
+    if (rc) return rc;
+    launch(io.c->stream, dim3((unsigned)((n + kBlock - 1) / kBlock)));
+    return io.finish();
+}
 
-// the two probe kernels that trace like a render: Family::kernel<R, VARIANT, EXT, MSEQ>() is the instantiation
-struct ProbeHit { template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_hit_kernel<R, V, EXT, MSEQ>; } };
-struct ProbePaths { template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_kernel<R, V, EXT, MSEQ>; } };
+// the two probe kernels that trace like a render: Family::kernel<R, VARIANT, EXT, MSEQ>() is the instantiation.  wave_level: the family has no
+// LDS-staged scan (no workgroup barriers), so its only dynamic LDS is the traversal's stack columns
+struct ProbeHit {
+    static constexpr bool wave_level = false;
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_hit_kernel<R, V, EXT, MSEQ>; }
+};
+struct ProbePaths {
+    static constexpr bool wave_level = false;
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_kernel<R, V, EXT, MSEQ>; }
+};
 
 // The probe instantiation the scene and the context select (precision x mixed kinds x media_seq x accel / scan_variant) and its dynamic LDS:
 // launch(kernel, lds_bytes, prims_per_tile, n_ptiles).  Mixed-kind scenes have FP64 kernels only (the entries refuse RTMI_F32 for them).
@@ -4414,7 +4479,8 @@ template <typename Family, typename R, typename Launch> void with_probe_kernel(c
     int ppt, npt;
     size_t lds;
     lds_plan(c, s->dev.n_static, sizeof(R), &ppt, &npt, &lds);
-    const size_t bvh_lds = (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16;
+    if (Family::wave_level) lds = 64;
+    const size_t bvh_lds = (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16; // the traversal's stack columns
     const bool bvh = c->accel == RTMI_ACCEL_BVH;
     if constexpr (std::is_same<R, double>::value) {
         if (s->dev.has_ext) { // (operands in the order the kernels were always instantiated in: the device code's inlining follows that order)
@@ -4437,96 +4503,87 @@ template <typename Family, typename R, typename Launch> void with_probe_kernel(c
 } // namespace
 
 RTMI_EXPORT int rtmi_probe_hit(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, double t_min, double t_max, double *out) {
-    PROBE_PROLOGUE(s)
+    const int rc = probe_begin(s, precision, n);
+    if (rc || n == 0) return rc;
     if (!rays || !out) return fail(RTMI_E_ARG, "NULL array");
     if (precision == RTMI_F32 && s->dev.has_ext) return fail(RTMI_E_UNSUPPORTED, "rectangles / triangles / instances are FP64 only");
-    double *d_rays = (double *)tmp.up(rays, (size_t)n * 7 * sizeof(double));
-    double *d_out = (double *)tmp.alloc((size_t)n * 11 * sizeof(double));
-    if (!d_rays || !d_out) return fail(RTMI_E_NOMEM, "probe buffers");
-    auto run = [&](auto kern, size_t lds, int ppt, int npt) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out);
-    };
-    with_real(precision, [&](auto r) { with_probe_kernel<ProbeHit, decltype(r)>(s, run); });
-    PROBE_EPILOGUE()
-    HIP_TRY(hipMemcpy(out, d_out, (size_t)n * 11 * sizeof(double), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    HostIo io(s->ctx);
+    double *d_rays, *d_out;
+    io.in(&d_rays, (size_t)n * 7, rays); io.out(&d_out, (size_t)n * 11, out);
+    return probe_run(io, n, [&](hipStream_t st, dim3 grid) {
+        auto run = [&](auto kern, size_t lds, int ppt, int npt) { hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, s->d_dev, ppt, npt, n, d_rays, t_min, t_max, d_out); };
+        with_real(precision, [&](auto r) { with_probe_kernel<ProbeHit, decltype(r)>(s, run); });
+    });
 }
 
 RTMI_EXPORT int rtmi_probe_paths(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
                                  double *out_rgb, uint64_t *out_nseg, double *log, int32_t max_seg, int32_t *out_nlog) {
-    PROBE_PROLOGUE(s)
+    const int rc = probe_begin(s, precision, n);
+    if (rc || n == 0) return rc;
     if (!rays || !keys || !out_rgb) return fail(RTMI_E_ARG, "NULL array");
     if (log && max_seg <= 0) return fail(RTMI_E_ARG, "log given but max_seg <= 0");
     if (precision == RTMI_F32 && s->dev.has_ext) return fail(RTMI_E_UNSUPPORTED, "rectangles / triangles / instances are FP64 only");
-    double *d_rays = (double *)tmp.up(rays, (size_t)n * 7 * sizeof(double));
-    u64 *d_keys = (u64 *)tmp.up(keys, (size_t)n * sizeof(u64));
-    double *d_rgb = (double *)tmp.alloc((size_t)n * 3 * sizeof(double));
-    u64 *d_nseg = (u64 *)tmp.alloc((size_t)n * sizeof(u64));
-    int *d_nlog = (int *)tmp.alloc((size_t)n * sizeof(int));
-    const size_t log_bytes = log ? (size_t)n * max_seg * RTMI_SEG_REC * sizeof(double) : 0;
-    double *d_log = log ? (double *)tmp.alloc(log_bytes) : nullptr;
-    if (!d_rays || !d_keys || !d_rgb || !d_nseg || !d_nlog || (log && !d_log)) return fail(RTMI_E_NOMEM, "probe buffers");
-    if (d_log) HIP_TRY(hipMemset(d_log, 0, log_bytes));
-    auto run = [&](auto kern, size_t lds, int ppt, int npt) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, c->stream, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog);
-    };
-    with_real(precision, [&](auto r) { with_probe_kernel<ProbePaths, decltype(r)>(s, run); });
-    PROBE_EPILOGUE()
-    HIP_TRY(hipMemcpy(out_rgb, d_rgb, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_nseg) HIP_TRY(hipMemcpy(out_nseg, d_nseg, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost));
-    if (out_nlog) HIP_TRY(hipMemcpy(out_nlog, d_nlog, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    if (log) HIP_TRY(hipMemcpy(log, d_log, log_bytes, hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    HostIo io(s->ctx);
+    double *d_rays, *d_rgb, *d_log;
+    u64 *d_keys, *d_nseg;
+    int *d_nlog;
+    const size_t log_words = log ? (size_t)n * max_seg * RTMI_SEG_REC : 0;
+    io.in(&d_rays, (size_t)n * 7, rays); io.in(&d_keys, (size_t)n, keys); io.out(&d_rgb, (size_t)n * 3, out_rgb);
+    io.work(&d_nseg, (size_t)n, out_nseg); io.work(&d_nlog, (size_t)n, out_nlog); io.out(&d_log, log_words, log);
+    return probe_run(io, n, [&](hipStream_t st, dim3 grid) {
+        if (d_log && hipMemset(d_log, 0, log_words * sizeof(double)) != hipSuccess) return; // (probe_run reports the error)
+        auto run = [&](auto kern, size_t lds, int ppt, int npt) {
+            hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, s->d_dev, ppt, npt, n, d_rays, d_keys, (u64)ctr0, depth, d_rgb, d_nseg, d_log, max_seg, d_nlog);
+        };
+        with_real(precision, [&](auto r) { with_probe_kernel<ProbePaths, decltype(r)>(s, run); });
+    });
 }
 
 RTMI_EXPORT int rtmi_probe_camera(rtmi_scene *s, int32_t precision, int32_t n, const double *uv, const uint64_t *keys, double *out) {
-    PROBE_PROLOGUE(s)
+    const int rc = probe_begin(s, precision, n);
+    if (rc || n == 0) return rc;
     if (!uv || !keys || !out) return fail(RTMI_E_ARG, "NULL array");
-    double *d_uv = (double *)tmp.up(uv, (size_t)n * 2 * sizeof(double));
-    u64 *d_keys = (u64 *)tmp.up(keys, (size_t)n * sizeof(u64));
-    double *d_out = (double *)tmp.alloc((size_t)n * 8 * sizeof(double));
-    if (!d_uv || !d_keys || !d_out) return fail(RTMI_E_NOMEM, "probe buffers");
-    with_real(precision, [&](auto r) { hipLaunchKernelGGL((probe_camera_kernel<decltype(r)>), dim3(grid), dim3(kBlock), 0, c->stream, s->d_dev, n, d_uv, d_keys, d_out); });
-    PROBE_EPILOGUE()
-    HIP_TRY(hipMemcpy(out, d_out, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    HostIo io(s->ctx);
+    double *d_uv, *d_out;
+    u64 *d_keys;
+    io.in(&d_uv, (size_t)n * 2, uv); io.in(&d_keys, (size_t)n, keys); io.out(&d_out, (size_t)n * 8, out);
+    return probe_run(io, n, [&](hipStream_t st, dim3 grid) {
+        with_real(precision, [&](auto r) { hipLaunchKernelGGL((probe_camera_kernel<decltype(r)>), grid, dim3(kBlock), 0, st, s->d_dev, n, d_uv, d_keys, d_out); });
+    });
 }
 
 RTMI_EXPORT int rtmi_probe_texture(rtmi_scene *s, int32_t precision, int32_t tex, int32_t n, const double *uvp, double *out) {
-    PROBE_PROLOGUE(s)
+    const int rc = probe_begin(s, precision, n);
+    if (rc || n == 0) return rc;
     if (!uvp || !out) return fail(RTMI_E_ARG, "NULL array");
     if (tex < 0 || tex >= s->n_tex) return fail(RTMI_E_ARG, "texture index %d out of range", tex);
-    double *d_in = (double *)tmp.up(uvp, (size_t)n * 5 * sizeof(double));
-    double *d_out = (double *)tmp.alloc((size_t)n * 3 * sizeof(double));
-    if (!d_in || !d_out) return fail(RTMI_E_NOMEM, "probe buffers");
-    if (s->dev.has_ext) {
-        if (precision != RTMI_F64) return fail(RTMI_E_UNSUPPORTED, "procedural / image textures are FP64 only");
-        hipLaunchKernelGGL((probe_texture_kernel<double, true>), dim3(grid), dim3(kBlock), 0, c->stream, s->d_dev, tex, n, d_in, d_out);
-    } else if (precision == RTMI_F64) hipLaunchKernelGGL((probe_texture_kernel<double>), dim3(grid), dim3(kBlock), 0, c->stream, s->d_dev, tex, n, d_in, d_out);
-    else hipLaunchKernelGGL((probe_texture_kernel<float>), dim3(grid), dim3(kBlock), 0, c->stream, s->d_dev, tex, n, d_in, d_out);
-    PROBE_EPILOGUE()
-    HIP_TRY(hipMemcpy(out, d_out, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    if (s->dev.has_ext && precision != RTMI_F64) return fail(RTMI_E_UNSUPPORTED, "procedural / image textures are FP64 only");
+    HostIo io(s->ctx);
+    double *d_in, *d_out;
+    io.in(&d_in, (size_t)n * 5, uvp); io.out(&d_out, (size_t)n * 3, out);
+    return probe_run(io, n, [&](hipStream_t st, dim3 grid) {
+        if (s->dev.has_ext) hipLaunchKernelGGL((probe_texture_kernel<double, true>), grid, dim3(kBlock), 0, st, s->d_dev, tex, n, d_in, d_out);
+        else if (precision == RTMI_F64) hipLaunchKernelGGL((probe_texture_kernel<double>), grid, dim3(kBlock), 0, st, s->d_dev, tex, n, d_in, d_out);
+        else hipLaunchKernelGGL((probe_texture_kernel<float>), grid, dim3(kBlock), 0, st, s->d_dev, tex, n, d_in, d_out);
+    });
 }
 
 RTMI_EXPORT int rtmi_probe_scatter(rtmi_scene *s, int32_t precision, int32_t mat, int32_t n, const double *rays, const double *hits,
                                    const uint64_t *keys, double *out) {
-    PROBE_PROLOGUE(s)
+    const int rc = probe_begin(s, precision, n);
+    if (rc || n == 0) return rc;
     if (!rays || !hits || !keys || !out) return fail(RTMI_E_ARG, "NULL array");
     if (mat < 0 || mat >= s->n_mats) return fail(RTMI_E_ARG, "material index %d out of range", mat);
-    double *d_rays = (double *)tmp.up(rays, (size_t)n * 7 * sizeof(double));
-    double *d_hits = (double *)tmp.up(hits, (size_t)n * 8 * sizeof(double));
-    u64 *d_keys = (u64 *)tmp.up(keys, (size_t)n * sizeof(u64));
-    double *d_out = (double *)tmp.alloc((size_t)n * 9 * sizeof(double));
-    if (!d_rays || !d_hits || !d_keys || !d_out) return fail(RTMI_E_NOMEM, "probe buffers");
-    if (s->dev.has_ext) {
-        if (precision != RTMI_F64) return fail(RTMI_E_UNSUPPORTED, "procedural / image textures are FP64 only");
-        hipLaunchKernelGGL((probe_scatter_kernel<double, true>), dim3(grid), dim3(kBlock), 0, c->stream, s->d_dev, mat, n, d_rays, d_hits, d_keys, d_out);
-    } else if (precision == RTMI_F64) hipLaunchKernelGGL((probe_scatter_kernel<double>), dim3(grid), dim3(kBlock), 0, c->stream, s->d_dev, mat, n, d_rays, d_hits, d_keys, d_out);
-    else hipLaunchKernelGGL((probe_scatter_kernel<float>), dim3(grid), dim3(kBlock), 0, c->stream, s->d_dev, mat, n, d_rays, d_hits, d_keys, d_out);
-    PROBE_EPILOGUE()
-    HIP_TRY(hipMemcpy(out, d_out, (size_t)n * 9 * sizeof(double), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    if (s->dev.has_ext && precision != RTMI_F64) return fail(RTMI_E_UNSUPPORTED, "procedural / image textures are FP64 only");
+    HostIo io(s->ctx);
+    double *d_rays, *d_hits, *d_out;
+    u64 *d_keys;
+    io.in(&d_rays, (size_t)n * 7, rays); io.in(&d_hits, (size_t)n * 8, hits); io.in(&d_keys, (size_t)n, keys); io.out(&d_out, (size_t)n * 9, out);
+    return probe_run(io, n, [&](hipStream_t st, dim3 grid) {
+        if (s->dev.has_ext) hipLaunchKernelGGL((probe_scatter_kernel<double, true>), grid, dim3(kBlock), 0, st, s->d_dev, mat, n, d_rays, d_hits, d_keys, d_out);
+        else if (precision == RTMI_F64) hipLaunchKernelGGL((probe_scatter_kernel<double>), grid, dim3(kBlock), 0, st, s->d_dev, mat, n, d_rays, d_hits, d_keys, d_out);
+        else hipLaunchKernelGGL((probe_scatter_kernel<float>), grid, dim3(kBlock), 0, st, s->d_dev, mat, n, d_rays, d_hits, d_keys, d_out);
+    });
 }
 
 RTMI_EXPORT int rtmi_probe_rng(rtmi_ctx *c, int32_t precision, uint64_t key, uint64_t d0, int32_t n, uint64_t *out_bits, double *out_real) {
@@ -4534,16 +4591,13 @@ RTMI_EXPORT int rtmi_probe_rng(rtmi_ctx *c, int32_t precision, uint64_t key, uin
     if (precision != RTMI_F64 && precision != RTMI_F32) return fail(RTMI_E_ARG, "bad precision");
     if (n <= 0 || !out_bits || !out_real) return fail(RTMI_E_ARG, "bad arguments");
     HIP_TRY(hipSetDevice(c->device));
-    Tmp tmp;
-    u64 *d_bits = (u64 *)tmp.alloc((size_t)n * sizeof(u64));
-    double *d_real = (double *)tmp.alloc((size_t)n * sizeof(double));
-    if (!d_bits || !d_real) return fail(RTMI_E_NOMEM, "probe buffers");
-    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    with_real(precision, [&](auto r) { hipLaunchKernelGGL((probe_rng_kernel<decltype(r)>), dim3(grid), dim3(kBlock), 0, c->stream, (u64)key, (u64)d0, n, d_bits, d_real); });
-    PROBE_EPILOGUE()
-    HIP_TRY(hipMemcpy(out_bits, d_bits, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_real, d_real, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    HostIo io(c);
+    u64 *d_bits;
+    double *d_real;
+    io.out(&d_bits, (size_t)n, out_bits); io.out(&d_real, (size_t)n, out_real);
+    return probe_run(io, n, [&](hipStream_t st, dim3 grid) {
+        with_real(precision, [&](auto r) { hipLaunchKernelGGL((probe_rng_kernel<decltype(r)>), grid, dim3(kBlock), 0, st, (u64)key, (u64)d0, n, d_bits, d_real); });
+    });
 }
 
 // the path's own FP64 helpers (rtmi_device.h): square root with the wave-uniform fast path, the table-driven atan2 / asin and the uv
@@ -4574,15 +4628,10 @@ RTMI_EXPORT int rtmi_probe_arith(rtmi_ctx *c, int32_t n, const double *abc, doub
     if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
     if (n <= 0 || !abc || !out) return fail(RTMI_E_ARG, "bad arguments");
     HIP_TRY(hipSetDevice(c->device));
-    Tmp tmp;
-    double *d_in = (double *)tmp.up(abc, (size_t)n * 3 * sizeof(double));
-    double *d_out = (double *)tmp.alloc((size_t)n * 3 * sizeof(double));
-    if (!d_in || !d_out) return fail(RTMI_E_NOMEM, "probe buffers");
-    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(probe_arith_kernel, dim3(grid), dim3(kBlock), 0, c->stream, n, d_in, d_out);
-    PROBE_EPILOGUE()
-    HIP_TRY(hipMemcpy(out, d_out, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    HostIo io(c);
+    double *d_in, *d_out;
+    io.in(&d_in, (size_t)n * 3, abc); io.out(&d_out, (size_t)n * 3, out);
+    return probe_run(io, n, [&](hipStream_t st, dim3 grid) { hipLaunchKernelGGL(probe_arith_kernel, grid, dim3(kBlock), 0, st, n, d_in, d_out); });
 }
 
 // n_slots values per triple (1 .. RTMI_PROBE_MATH_SLOTS): the caller states how many its buffer holds per triple
@@ -4591,15 +4640,10 @@ RTMI_EXPORT int rtmi_probe_math2(rtmi_ctx *c, int32_t n, const double *abc, doub
     if (n <= 0 || !abc || !out) return fail(RTMI_E_ARG, "bad arguments");
     if (n_slots < 1 || n_slots > RTMI_PROBE_MATH_SLOTS) return fail(RTMI_E_ARG, "n_slots must be 1..%d", RTMI_PROBE_MATH_SLOTS);
     HIP_TRY(hipSetDevice(c->device));
-    Tmp tmp;
-    double *d_in = (double *)tmp.up(abc, (size_t)n * 3 * sizeof(double));
-    double *d_out = (double *)tmp.alloc((size_t)n * (size_t)n_slots * sizeof(double));
-    if (!d_in || !d_out) return fail(RTMI_E_NOMEM, "probe buffers");
-    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(probe_math_kernel, dim3(grid), dim3(kBlock), 0, c->stream, n, d_in, tmin, tmax, (int)n_slots, d_out);
-    PROBE_EPILOGUE()
-    HIP_TRY(hipMemcpy(out, d_out, (size_t)n * (size_t)n_slots * sizeof(double), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    HostIo io(c);
+    double *d_in, *d_out;
+    io.in(&d_in, (size_t)n * 3, abc); io.out(&d_out, (size_t)n * (size_t)n_slots, out);
+    return probe_run(io, n, [&](hipStream_t st, dim3 grid) { hipLaunchKernelGGL(probe_math_kernel, grid, dim3(kBlock), 0, st, n, d_in, tmin, tmax, (int)n_slots, d_out); });
 }
 // the entry as first published: EIGHT values per triple (version 203 wrote nine into the same signature; hosts built against either header get eight again)
 RTMI_EXPORT int rtmi_probe_math(rtmi_ctx *c, int32_t n, const double *abc, double tmin, double tmax, double *out) {
@@ -4611,6 +4655,7 @@ namespace {
 // feature_kernel's instantiations are chosen where the probe kernels' are (with_probe_kernel); the LDS-staged scans (scan_variant 0 / 1) need
 // workgroup barriers and are answered with the scalar-cache scan, which finds the same hit
 struct FeaturePass {
+    static constexpr bool wave_level = true;
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return feature_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MSEQ>; }
 };
 
@@ -4623,7 +4668,6 @@ int check_feature_args(rtmi_scene *s, int nx, int ny, int na, int precision) {
 // the region rg = {x0, y0, x1, y1} of the frame's features into d_out[y1 - y0][x1 - x0][8], the counters into d_cnt[2]; all on `st`
 template <typename R>
 int render_features_impl(rtmi_scene *s, int nx, int ny, int na, uint64_t seed, const int *rg, double *d_out, u64 *d_cnt, hipStream_t st) {
-    rtmi_ctx *c = s->ctx;
     FeatureParams fp;
     fp.nx = nx; fp.ny = ny; fp.na = na; fp.seed = seed;
     fp.tx0 = rg[0] / RTMI_TILE; fp.ty0 = rg[1] / RTMI_TILE;
@@ -4632,9 +4676,8 @@ int render_features_impl(rtmi_scene *s, int nx, int ny, int na, uint64_t seed, c
     fp.rx0 = rg[0]; fp.ry0 = rg[1]; fp.rx1 = rg[2]; fp.ry1 = rg[3];
     fp.out = d_out; fp.counters = d_cnt;
     HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(u64), st));
-    const size_t lds = c->accel == RTMI_ACCEL_BVH ? (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16 : (size_t)64; // the traversal's stack columns
     const unsigned grid = (unsigned)((fp.n_tiles + kBlock / 64 - 1) / (kBlock / 64));
-    with_probe_kernel<FeaturePass, R>(s, [&](auto kern, size_t, int, int) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, s->d_dev, fp); });
+    with_probe_kernel<FeaturePass, R>(s, [&](auto kern, size_t lds, int, int) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, s->d_dev, fp); });
     HIP_TRY(hipGetLastError());
     return RTMI_OK;
 }
@@ -4647,7 +4690,7 @@ RTMI_EXPORT int rtmi_render_features_device(rtmi_scene *s, int32_t nx, int32_t n
     if (!d_out_features) return fail(RTMI_E_ARG, "d_out_features is NULL");
     rtmi_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     if (!d_out_counters) {
         rc = c->feat_cnt.ensure(2 * sizeof(u64));
         if (rc) return rc;
@@ -4660,24 +4703,21 @@ RTMI_EXPORT int rtmi_render_features_device(rtmi_scene *s, int32_t nx, int32_t n
 RTMI_EXPORT int rtmi_render_features(rtmi_scene *s, int32_t nx, int32_t ny, int32_t na, uint64_t seed, int32_t precision,
                                      int32_t x0, int32_t y0, int32_t x1, int32_t y1, double *out_features, uint64_t *out_counters) {
     int rc = check_feature_args(s, nx, ny, na, precision);
+    if (!rc) rc = check_region(nx, ny, x0, y0, x1, y1);
     if (rc) return rc;
-    if (x0 < 0 || y0 < 0 || x1 > nx || y1 > ny || x1 <= x0 || y1 <= y0) return fail(RTMI_E_ARG, "region [%d,%d)x[%d,%d) outside %dx%d", x0, x1, y0, y1, nx, ny);
     if (!out_features) return fail(RTMI_E_ARG, "out_features is NULL");
     rtmi_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t npx = (size_t)(x1 - x0) * (size_t)(y1 - y0);
-    rc = c->feat_out.ensure(npx * 8 * sizeof(double) + 2 * sizeof(u64));
+    HostIo io(c);
+    double *d_out;
+    u64 *d_cnt;
+    io.out(&d_out, (size_t)(x1 - x0) * (size_t)(y1 - y0) * 8, out_features); io.work(&d_cnt, 2, out_counters);
+    rc = io.reserve();
     if (rc) return rc;
-    double *d_out = reinterpret_cast<double *>(c->feat_out.p);
-    u64 *d_cnt = reinterpret_cast<u64 *>(d_out + npx * 8);
     const int rg[4] = {x0, y0, x1, y1};
     hipStream_t st = c->stream;
     rc = with_real(precision, [&](auto r) { return render_features_impl<decltype(r)>(s, nx, ny, na, seed, rg, d_out, d_cnt, st); });
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(out_features, d_out, npx * 8 * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    return rc ? rc : io.finish();
 }
 
 // ---- edge-aware denoiser (rtmi_denoise*) ---------------------------------------------------------------------------------------------------------
@@ -4728,7 +4768,7 @@ RTMI_EXPORT int rtmi_denoise_device(rtmi_ctx *c, int32_t nx, int32_t ny, const v
     if (rc) return rc;
     if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return denoise_impl(c, nx, ny, reinterpret_cast<const double *>(d_linear_in), reinterpret_cast<const double *>(d_stderr_in),
                         reinterpret_cast<const double *>(d_features_in), iterations, sigma_c, sigma_n, sigma_a, sigma_d,
                         reinterpret_cast<double *>(d_out_linear), reinterpret_cast<unsigned char *>(d_out_rgb8), reinterpret_cast<double *>(d_out_stderr), st);
@@ -4742,24 +4782,14 @@ RTMI_EXPORT int rtmi_denoise(rtmi_ctx *c, int32_t nx, int32_t ny, const double *
     if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)nx * (size_t)ny;
-    // in: linear 3n, stderr n, features 8n doubles; out: linear 3n, stderr n doubles, rgb8 3n bytes
-    rc = c->dn_io.ensure(16 * n * sizeof(double) + 3 * n);
-    if (rc) return rc;
-    double *d_lin = reinterpret_cast<double *>(c->dn_io.p), *d_se = d_lin + 3 * n, *d_feat = d_se + n, *d_olin = d_feat + 8 * n, *d_ose = d_olin + 3 * n;
-    unsigned char *d_oq = reinterpret_cast<unsigned char *>(d_ose + n);
-    hipStream_t st = c->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(d_lin, linear_in, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    if (stderr_in) HIP_TRY(hipMemcpy(d_se, stderr_in, n * sizeof(double), hipMemcpyHostToDevice));
-    if (features_in) HIP_TRY(hipMemcpy(d_feat, features_in, 8 * n * sizeof(double), hipMemcpyHostToDevice));
-    rc = denoise_impl(c, nx, ny, d_lin, stderr_in ? d_se : nullptr, features_in ? d_feat : nullptr, iterations, sigma_c, sigma_n, sigma_a, sigma_d,
-                      out_linear ? d_olin : nullptr, out_rgb8 ? d_oq : nullptr, out_stderr ? d_ose : nullptr, st);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (out_linear) HIP_TRY(hipMemcpy(out_linear, d_olin, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_oq, 3 * n, hipMemcpyDeviceToHost));
-    if (out_stderr) HIP_TRY(hipMemcpy(out_stderr, d_ose, n * sizeof(double), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    HostIo io(c);
+    double *d_lin, *d_se, *d_feat, *d_olin, *d_ose;
+    unsigned char *d_oq;
+    io.in(&d_lin, 3 * n, linear_in); io.in(&d_se, n, stderr_in); io.in(&d_feat, 8 * n, features_in);
+    io.out(&d_olin, 3 * n, out_linear); io.out(&d_oq, 3 * n, out_rgb8); io.out(&d_ose, n, out_stderr);
+    rc = io.stage();
+    if (!rc) rc = denoise_impl(c, nx, ny, d_lin, d_se, d_feat, iterations, sigma_c, sigma_n, sigma_a, sigma_d, d_olin, d_oq, d_ose, c->stream);
+    return rc ? rc : io.finish();
 }
 
 // ---- temporal accumulation (rtmi_reproject*) -----------------------------------------------------------------------------------------------------------
@@ -4837,7 +4867,7 @@ RTMI_EXPORT int rtmi_reproject_device(rtmi_ctx *c, int32_t nx, int32_t ny, int32
     if (rc) return rc;
     if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     auto D = [](const void *p) { return reinterpret_cast<const double *>(p); };
     return reproject_impl(nx, ny, prev_cam, cur_cam, D(d_prev_linear), D(d_prev_weight), D(d_prev_stderr), D(d_prev_features), D(d_cur_linear),
                           D(d_cur_stderr), D(d_cur_features), cur_weight, max_history, sigma_d, sigma_n, sigma_a, reinterpret_cast<double *>(d_out_linear),
@@ -4857,33 +4887,17 @@ RTMI_EXPORT int rtmi_reproject(rtmi_ctx *c, int32_t nx, int32_t ny, int32_t prev
     if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)nx * (size_t)ny;
-    // in: two frames of linear 3n, stderr n, features 8n doubles and the history's weight n; out: linear 3n, weight n, stderr n doubles, the counters, rgb8 3n bytes
-    rc = c->rp_io.ensure(30 * n * sizeof(double) + 2 * sizeof(u64) + 3 * n);
-    if (rc) return rc;
-    double *d_plin = reinterpret_cast<double *>(c->rp_io.p), *d_pw = d_plin + 3 * n, *d_pse = d_pw + n, *d_pft = d_pse + n, *d_clin = d_pft + 8 * n,
-           *d_cse = d_clin + 3 * n, *d_cft = d_cse + n, *d_olin = d_cft + 8 * n, *d_ow = d_olin + 3 * n, *d_ose = d_ow + n;
-    u64 *d_cnt = reinterpret_cast<u64 *>(d_ose + n);
-    unsigned char *d_oq = reinterpret_cast<unsigned char *>(d_cnt + 2);
-    hipStream_t st = c->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(d_plin, prev_linear, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_pw, prev_weight, n * sizeof(double), hipMemcpyHostToDevice));
-    if (prev_stderr) HIP_TRY(hipMemcpy(d_pse, prev_stderr, n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_pft, prev_features, 8 * n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_clin, cur_linear, 3 * n * sizeof(double), hipMemcpyHostToDevice));
-    if (cur_stderr) HIP_TRY(hipMemcpy(d_cse, cur_stderr, n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_cft, cur_features, 8 * n * sizeof(double), hipMemcpyHostToDevice));
-    rc = reproject_impl(nx, ny, prev_cam, cur_cam, d_plin, d_pw, prev_stderr ? d_pse : nullptr, d_pft, d_clin, cur_stderr ? d_cse : nullptr, d_cft, cur_weight,
-                        max_history, sigma_d, sigma_n, sigma_a, out_linear ? d_olin : nullptr, out_rgb8 ? d_oq : nullptr, out_weight ? d_ow : nullptr,
-                        out_stderr ? d_ose : nullptr, out_counters ? d_cnt : nullptr, st);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (out_linear) HIP_TRY(hipMemcpy(out_linear, d_olin, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, d_oq, 3 * n, hipMemcpyDeviceToHost));
-    if (out_weight) HIP_TRY(hipMemcpy(out_weight, d_ow, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_stderr) HIP_TRY(hipMemcpy(out_stderr, d_ose, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    HostIo io(c);
+    double *d_plin, *d_pw, *d_pse, *d_pft, *d_clin, *d_cse, *d_cft, *d_olin, *d_ow, *d_ose;
+    unsigned char *d_oq;
+    u64 *d_cnt;
+    io.in(&d_plin, 3 * n, prev_linear); io.in(&d_pw, n, prev_weight); io.in(&d_pse, n, prev_stderr); io.in(&d_pft, 8 * n, prev_features);
+    io.in(&d_clin, 3 * n, cur_linear); io.in(&d_cse, n, cur_stderr); io.in(&d_cft, 8 * n, cur_features);
+    io.out(&d_olin, 3 * n, out_linear); io.out(&d_oq, 3 * n, out_rgb8); io.out(&d_ow, n, out_weight); io.out(&d_ose, n, out_stderr); io.out(&d_cnt, 2, out_counters);
+    rc = io.stage();
+    if (!rc) rc = reproject_impl(nx, ny, prev_cam, cur_cam, d_plin, d_pw, d_pse, d_pft, d_clin, d_cse, d_cft, cur_weight, max_history, sigma_d, sigma_n, sigma_a,
+                                 d_olin, d_oq, d_ow, d_ose, d_cnt, c->stream);
+    return rc ? rc : io.finish();
 }
 
 // ---- caller-supplied rays (rtmi_render_rays*) ---------------------------------------------------------------------------------------------------
@@ -4891,6 +4905,7 @@ namespace {
 // rays_kernel's instantiations are chosen where the probe kernels' are (with_probe_kernel); the LDS-staged scans (scan_variant 0 / 1) need
 // workgroup barriers and are answered with the scalar-cache scan, which finds the same hit (as the feature pass)
 struct RaysPass {
+    static constexpr bool wave_level = true;
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MSEQ>; }
 };
 
@@ -4934,19 +4949,12 @@ int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const 
     rp.group = (unsigned)group; rp.g_first = (unsigned)g_first;
     rp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 2);
     rp.counters = d_cnt;
-    const size_t lds = c->accel == RTMI_ACCEL_BVH ? (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16 : (size_t)64; // the traversal's stack columns
     const u64 n_rays = (u64)n_groups * (u64)group;
-    with_probe_kernel<RaysPass, R>(s, [&](auto kern, size_t, int, int) {
+    with_probe_kernel<RaysPass, R>(s, [&](auto kern, size_t lds, int, int) {
         rc = [&]() -> int {
             int resident = 0;
-            { // asked once per (kernel, LDS bytes) and kept on the context, as the trace launch does
-                const std::pair<const void *, size_t> key(reinterpret_cast<const void *>(kern), lds);
-                auto it = c->occupancy.find(key);
-                if (it == c->occupancy.end()) {
-                    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, kern, kBlock, lds));
-                    c->occupancy.emplace(key, resident);
-                } else resident = it->second;
-            }
+            const int rco = resident_blocks(c, reinterpret_cast<const void *>(kern), kBlock, lds, &resident);
+            if (rco) return rco;
             const long long persistent = (long long)c->cus * std::max(1, std::min(c->blocks_per_cu, resident));
             for (int g0 = 0; g0 < n_groups; g0 += per_pass) {
                 const int ng = std::min(per_pass, n_groups - g0);
@@ -4962,12 +4970,9 @@ int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const 
                     while (qb < 1024u && per_wave >= (long long)qb * 16) qb *= 2;
                     rp.qblock = qb;
                 }
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if ((c->flags & RTMI_FLAG_TIMING) && c->events_used < 8192) {
-                    const int rce = next_event_pair(c, &e0, &e1);
-                    if (rce) return rce;
-                    HIP_TRY(hipEventRecord(e0, st));
-                }
+                hipEvent_t e1 = nullptr;
+                const int rce = open_timed(c, st, &e1);
+                if (rce) return rce;
                 HIP_TRY(hipMemsetAsync(rp.queue, 0, sizeof(unsigned), st));
                 const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(persistent, (items + kBlock - 1) / kBlock));
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, s->d_dev, rp);
@@ -4976,11 +4981,7 @@ int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const 
                 hipLaunchKernelGGL((rays_fold_kernel<R>), dim3((unsigned)((ng + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rp.samples, g0, ng, group,
                                    d_state ? g_first : 0, d_state, d_mean, d_se, d_cnt, n_rays);
                 HIP_TRY(hipGetLastError());
-                if (e1) {
-                    const size_t k = (size_t)c->events_used - 1;
-                    while (c->events_r.size() <= k) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); c->events_r.push_back(e); }
-                    HIP_TRY(hipEventRecord(c->events_r[k], st));
-                }
+                if (e1) { const int rcf = close_timed_fold(c, st); if (rcf) return rcf; }
             }
             return RTMI_OK;
         }();
@@ -4997,7 +4998,7 @@ RTMI_EXPORT int rtmi_render_rays_device(rtmi_scene *s, int32_t precision, int32_
     if (n_groups == 0) return RTMI_OK;
     rtmi_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
+    hipStream_t st = stream_of(c, stream);
     return with_real(precision, [&](auto r) {
         return render_rays_impl<decltype(r)>(s, n_groups, group, g_first, reinterpret_cast<const double *>(d_rays), reinterpret_cast<const u64 *>(d_keys), seed,
                                              ctr0, depth, reinterpret_cast<double *>(d_state), reinterpret_cast<double *>(d_out_mean),
@@ -5019,30 +5020,16 @@ RTMI_EXPORT int rtmi_render_rays(rtmi_scene *s, int32_t precision, int32_t n_gro
     rtmi_ctx *c = s->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)n_groups * (size_t)group, ng = (size_t)n_groups;
-    // in: rays 7n doubles, keys n; in/out: the records; out: mean 3 ng, stderr ng doubles, the counters, the radiance 3n doubles where asked for
-    const size_t words = 7 * n + (keys ? n : 0) + (state ? ng * RTMI_RAYS_REC : 0) + 4 * ng + 2 + (out_rays ? 3 * n : 0);
-    rc = c->rays_io.ensure(words * sizeof(double));
+    HostIo io(c);
+    double *d_rays, *d_state, *d_mean, *d_se, *d_out;
+    u64 *d_keys, *d_cnt;
+    io.in(&d_rays, 7 * n, rays); io.in(&d_keys, n, keys);
+    io.plane(&d_state, ng * RTMI_RAYS_REC, state != nullptr, g_first > 0 ? state : nullptr, state); // a first chunk (g_first = 0) reads no records
+    io.out(&d_mean, 3 * ng, out_mean); io.out(&d_se, ng, out_stderr); io.work(&d_cnt, 2, out_counters); io.out(&d_out, 3 * n, out_rays);
+    rc = io.stage();
     if (rc) return rc;
-    double *d_rays = reinterpret_cast<double *>(c->rays_io.p);
-    u64 *d_keys = reinterpret_cast<u64 *>(d_rays + 7 * n);
-    double *d_state = reinterpret_cast<double *>(d_keys + (keys ? n : 0)), *d_mean = d_state + (state ? ng * RTMI_RAYS_REC : 0), *d_se = d_mean + 3 * ng;
-    u64 *d_cnt = reinterpret_cast<u64 *>(d_se + ng);
-    double *d_out = reinterpret_cast<double *>(d_cnt + 2);
-    hipStream_t st = c->stream;
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(d_rays, rays, 7 * n * sizeof(double), hipMemcpyHostToDevice));
-    if (keys) HIP_TRY(hipMemcpy(d_keys, keys, n * sizeof(u64), hipMemcpyHostToDevice));
-    if (state && g_first > 0) HIP_TRY(hipMemcpy(d_state, state, ng * RTMI_RAYS_REC * sizeof(double), hipMemcpyHostToDevice));
     rc = with_real(precision, [&](auto r) {
-        return render_rays_impl<decltype(r)>(s, n_groups, group, g_first, d_rays, keys ? d_keys : nullptr, seed, ctr0, depth, state ? d_state : nullptr, d_mean,
-                                             d_se, out_rays ? d_out : nullptr, d_cnt, st);
+        return render_rays_impl<decltype(r)>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out, d_cnt, c->stream);
     });
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (state) HIP_TRY(hipMemcpy(state, d_state, ng * RTMI_RAYS_REC * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_mean, d_mean, 3 * ng * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_stderr, d_se, ng * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_rays) HIP_TRY(hipMemcpy(out_rays, d_out, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_counters) HIP_TRY(hipMemcpy(out_counters, d_cnt, 2 * sizeof(u64), hipMemcpyDeviceToHost));
-    return RTMI_OK;
+    return rc ? rc : io.finish();
 }

@@ -3,11 +3,15 @@ tiled-coords chunks, core.clj:59-71, become device tiles), every rank renders it
 and ONE gather (RCCL over xGMI when the backend is nccl) brings the tile-major buffers to rank 0, which un-tiles and
 quantises them on its GPU.  Pixels are independent and the stream key is the global pixel index, so the image does not
 depend on the partition."""
+import ctypes as C
+
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from . import _ffi
 from . import core
+from . import flatten as fl
 from .core import Context, DeviceScene, check
 
 TILE = _ffi.TILE
@@ -145,7 +149,6 @@ class MultiDevice:
                 ctx.set_option(k, v)
             self.ctxs.append(ctx)
             self.scenes.append(DeviceScene(flat_scene, ctx=ctx) if not self.scenes else self.scenes[0].clone(ctx))
-        import ctypes as C
         self._arr = (C.c_void_p * len(self.scenes))(*[s.handle for s in self.scenes])
         self.n = len(self.scenes)
 
@@ -160,51 +163,31 @@ class MultiDevice:
     def set_materials(self, scene_or_flat):
         """DeviceScene.set_materials (the host form) on every replica -> True if the replicas rebuilt (they all do, or none).  The argument
         and fit checks of ALL replicas run before the first write: a bad edit raises and leaves every replica as it was."""
-        from . import flatten as fl
         f = scene_or_flat if isinstance(scene_or_flat, fl.FlatScene) else fl.flatten(scene_or_flat)
         for s in self.scenes:
             if len(f.prim_mat) != len(s.flat.prim_kind):
                 raise ValueError("the edit has %d primitives, the scene %d" % (len(f.prim_mat), len(s.flat.prim_kind)))
         # the replicas are clones: they hold the same arrays, so the library's checks (creation's, on the scene's arrays with the edit in their
         # place) and its fit decision give one answer for all of them.  The host-only hook runs those checks without touching a scene.
-        import numpy as np
-        g = self.scenes[0].flat
-        arrs = [np.ascontiguousarray(a, dt) for a, dt in (
-            (g.prim_kind, np.int32), (f.prim_mat, np.int32), (f.mat_kind, np.int32), (f.mat_tex, np.int32), (f.mat_param, np.float64),
-            (f.tex_kind, np.int32), (f.tex_param, np.float64), (f.tex_child, np.int32))]
-        pk, pm, mk, mt, mp, tk, tp, tc = arrs
+        keep, args = core.scene_arrays(self.scenes[0].flat, **{name: getattr(f, name) for name in core.MATERIAL_FIELDS})
         h, facts = np.zeros(1, np.uint64), np.zeros(3, np.int32)
-        p = _ffi.ptr
-        check(_ffi.lib().rtmi_test_pack_materials(len(pk), p(pk), None, p(pm), len(mk), p(mk), p(mt), p(mp), len(tk), p(tk), p(tp), p(tc),
-                                                  0, None, None, None, 0, None, None, 0, p(h), p(facts)))
+        check(_ffi.lib().rtmi_test_pack_materials(*args, 0, _ffi.ptr(h), _ffi.ptr(facts)))
         return any([s.set_materials(f) for s in self.scenes])
 
     def set_geometry(self, scene_or_flat, mode="auto"):
         """DeviceScene.set_geometry on every replica -> the first replica's info (the replicas are clones built from the same arrays: after the
         same sequence of edits they decide alike).  The structure checks of ALL replicas, and creation's checks of the edited arrays, run before
         the first replica is written: a bad edit raises and leaves every replica as it was."""
-        import numpy as np
         if mode not in ("auto", "rebuild"):
             raise ValueError("mode must be 'auto' or 'rebuild'")
-        pairs = [s._geometry_arrays(scene_or_flat) for s in self.scenes]
-        g, (pg, xp) = self.scenes[0].flat, pairs[0]
-        a = lambda x, dt: np.ascontiguousarray(x, dt)
-        n = len(g.prim_kind)
-        pk, pm = a(g.prim_kind, np.int32), a(g.prim_mat, np.int32)
-        mk, mt, mp = a(g.mat_kind, np.int32), a(g.mat_tex, np.int32), a(g.mat_param, np.float64)
-        tk, tp, tc = a(g.tex_kind, np.int32), a(g.tex_param, np.float64), a(g.tex_child, np.int32)
-        c24 = a(g.cam, np.float64)
-        flip, xf = a(getattr(g, "prim_flip", np.zeros(n)), np.int32), a(getattr(g, "prim_xform", np.zeros((n, 2))), np.int32)
-        xk = a(getattr(g, "xform_kind", np.zeros(0)), np.int32)
+        pg, xp = [s._geometry_arrays(scene_or_flat) for s in self.scenes][0]
+        keep, args = core.scene_arrays(self.scenes[0].flat, prim_geom=pg, xform_param=xp)
         h = np.zeros(1, np.uint64)
-        p = _ffi.ptr
-        check(_ffi.lib().rtmi_test_pack_geometry(n, p(pk), p(pg), p(pm), len(mk), p(mk), p(mt), p(mp), len(tk), p(tk), p(tp), p(tc), int(g.cam_kind), p(c24),
-                                                 p(flip), p(xf), len(xk), p(xk), p(xp) if len(xk) else None, 0, p(h)))
+        check(_ffi.lib().rtmi_test_pack_geometry(*args, 0, _ffi.ptr(h)))
         return [s.set_geometry(scene_or_flat, mode) for s in self.scenes][0]
 
     def render(self, nx, ny, ns, depth=50, seed=0x5EED0002, precision="f64"):
         """host buffers: (linear [ny,nx,3] float64, rgb8, counters)"""
-        import numpy as np
         lin, q, cnt = np.zeros((ny, nx, 3)), np.zeros((ny, nx, 3), np.uint8), np.zeros(2, np.uint64)
         check(_ffi.lib().rtmi_render_multi(self.n, self._arr, nx, ny, ns, depth, seed, {"f64": 0, "f32": 1}[precision],
                                            _ffi.ptr(lin), _ffi.ptr(q), _ffi.ptr(cnt)))
@@ -219,7 +202,6 @@ class MultiDevice:
     def render_multi_adaptive(self, nx, ny, s_first, s_count, retire, eps=0.0, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED, precision="f64"):
         """host buffers: samples [s_first, s_first + s_count) into the frame dealt over the replicas (retire: the adaptive rule with eps, else
         the progressive one) -> (linear, rgb8, stderr [ny,nx], samples int32 [ny,nx], counters)"""
-        import numpy as np
         lin, q = np.zeros((ny, nx, 3)), np.zeros((ny, nx, 3), np.uint8)
         err, smp, cnt = np.zeros((ny, nx)), np.zeros((ny, nx), np.int32), np.zeros(2, np.uint64)
         check(_ffi.lib().rtmi_render_multi_adaptive(self.n, self._arr, nx, ny, s_first, s_count, int(retire), float(eps), depth, seed,
@@ -267,7 +249,6 @@ class MultiDevice:
 
     def adaptive_active_tiles(self):
         """global tile indices of the tiles still active on any replica, int32, ascending"""
-        import numpy as np
         return np.sort(np.concatenate([ctx.adaptive_active_tiles() for ctx in self.ctxs])).astype(np.int32)
 
     def adaptive_retire(self, noise, eps):
@@ -327,14 +308,12 @@ class MultiDevice:
             torch.cuda.synchronize(ctx.device)
 
     def last_gather_ms(self):
-        import ctypes as C
         ms = C.c_double()
         check(_ffi.lib().rtmi_last_gather_ms(self.ctxs[0].handle, C.byref(ms)))
         return ms.value
 
     def last_gather_path(self):
         """"none" | "same-device" | "peer-copy" | "rccl": how the last render moved the replicas' records to replica 0 (rtmi_last_gather_path)"""
-        import ctypes as C
         p = C.c_int32(-1)
         check(_ffi.lib().rtmi_last_gather_path(self.ctxs[0].handle, C.byref(p)))
         return _ffi.GATHER_PATHS[p.value]

@@ -10,7 +10,7 @@ then the median of 5, by the library's own events (RTMI_FLAG_TIMING):
 
   rays    rtmi_render_rays_device on those rays, HBM-resident, no per-ray output: trace (rays_kernel) and fold (rays_fold_kernel) ms
   frame   rtmi_render_device of the same frame: trace and reduce ms
-  probe   rtmi_probe_paths on the same rays and keys from host arrays: WALL time -- it allocates, uploads 64 bytes per ray and reads 36 back per call
+  probe   rtmi_probe_paths on the same rays and keys from host arrays: WALL time -- it uploads 64 bytes per ray and reads 36 back per call
 
   scenes: C3 = the cover scene with 10 001 spheres; glass = the cover scene n = 11 with choose-mat at (0.1, 0.2): four of five small spheres glass
 The child also states whether every ray's radiance is the probe's and whether the means of `rays` are the frame's linear image, bit for bit."""
