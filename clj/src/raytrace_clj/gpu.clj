@@ -556,6 +556,69 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn query-hits
+  "The closest hit of every caller-supplied ray of scene {:camera :world} on GPU `device` (rtmi_query_hits): `rays` holds 7 doubles per ray
+  (origin, direction, time), `n` of them; the scene's camera is not read.  Every ray takes (t-min, t-max), or its own pair of `t-range`
+  (2 doubles per ray).  `keys` (longs, one per ray) key the streams a ConstantMedium draws from, each starting at draw `ctr0`; without them every
+  ray is keyed 0.  Returns {:hits double-array [n][12] = hit?, prim, t, p xyz, normal xyz, u, v, material (zeros on a miss), :rays n,
+  :rays-hit}."
+  [scene rays n & {:keys [keys t-range t-min t-max ctr0 device precision]
+                   :or {t-min 0.001 t-max 3.4028234663852886e38 ctr0 0 device 0 precision 0}}]
+  (let [f   (flatten-scene scene)
+        ctx (PointerByReference.)
+        rs  (double-array rays)
+        tr  (double-array (or t-range (mapcat (fn [_] [t-min t-max]) (range n))))
+        ks  (long-array (or keys n))
+        out (double-array (* 12 n))
+        cnt (long-array 2)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_query_hits" scn (int precision) (int n) rs tr (double t-min) (double t-max) ks (int (if keys ctr0 0)) out cnt))
+          {:hits out :rays (aget cnt 0) :rays-hit (aget cnt 1)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
+(defn occluded
+  "Is anything hit within each ray's range (rtmi_query_occluded)?  (* n-groups group) rays as for query-hits, ray r of group g at row
+  (+ (* g group) r).  The search leaves at the first primitive that accepts the ray.  Returns {:occluded byte-array [n], 1 where query-hits
+  would report a hit, :count int-array [n-groups] = occluded rays per group, :rays n, :rays-occluded}."
+  [scene rays n-groups group & {:keys [keys t-range t-min t-max ctr0 device precision]
+                                :or {t-min 0.001 t-max 3.4028234663852886e38 ctr0 0 device 0 precision 0}}]
+  (let [f     (flatten-scene scene)
+        ctx   (PointerByReference.)
+        n     (* n-groups group)
+        rs    (double-array rays)
+        tr    (double-array (or t-range (mapcat (fn [_] [t-min t-max]) (range n))))
+        ks    (long-array (or keys n))
+        flags (byte-array n)
+        per   (int-array n-groups)
+        cnt   (long-array 2)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_query_occluded" scn (int precision) (int n-groups) (int group) rs tr (double t-min) (double t-max) ks
+                           (int (if keys ctr0 0)) flags per cnt))
+          {:occluded flags :count per :rays (aget cnt 0) :rays-occluded (aget cnt 1)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
+(defn pick
+  "What lies under pixel (column i, row j from the top) of an nx x ny view of scene {:camera :world}: nil, or {:prim :material :t :p :normal
+  :uv} of the closest hit of the ray from the camera's origin (a thin lens: its lens centre) through the pixel's centre -- u = (i + 1/2) / nx,
+  v = (ny - 1 - j + 1/2) / ny, direction lleft + u horiz + v vert - origin in get-ray's operation order."
+  [scene nx ny i j & {:keys [device] :or {device 0}}]
+  (let [cam (vec (:cam (camera-row (:camera scene))))
+        u   (/ (+ (double i) 0.5) (double nx))
+        v   (/ (+ (- (double (dec ny)) (double j)) 0.5) (double ny))
+        dir (fn [k] (+ (+ (+ (cam (+ 3 k)) (* (cam (+ 6 k)) u)) (* (cam (+ 9 k)) v)) (- (cam k))))
+        ray [(cam 0) (cam 1) (cam 2) (dir 0) (dir 1) (dir 2) (if (= 0 (:kind (camera-row (:camera scene)))) 0.0 (cam 22))]
+        h   (vec (:hits (query-hits scene ray 1 :device device)))]
+    (when-not (zero? (h 0))
+      {:prim (long (h 1)) :material (long (h 11)) :t (h 2) :p (subvec h 3 6) :normal (subvec h 6 9) :uv (subvec h 9 11)})))
+
 (defn denoise
   "Edge-aware a-trous filter (rtmi_denoise) of a frame: linear [ny][nx][3] (:linear of render / render-adaptive), stderr [ny][nx] (:stderr)
   and features [ny][nx][8] (:features of render-features), `iterations` passes (0 .. 8).  A sigma of 0 switches its term off.  Returns

@@ -578,6 +578,56 @@ int rtmi_render_rays_device(rtmi_scene *scene, int32_t precision, int32_t n_grou
                             const void *d_rays, const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth,
                             void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream);
 
+/* ---- closest-hit and any-hit queries on caller-supplied rays: picking, snapping, first hits of a baker, shadow / ambient-occlusion / line-of-sight rays ----
+ * n rays, each 7 doubles {o.xyz, d.xyz, time} in the row layout of rtmi_probe_hit and rtmi_render_rays; rays are not validated (a non-finite ray yields
+ * what the device functions yield for it: both calls return).
+ *   t_range (may be NULL): [n][2] doubles, ray k's own (t-min, t-max) -- a shadow ray ends at its light, an ambient-occlusion ray at its radius.
+ *     NULL: every ray takes the scalars t_min, t_max (which are ignored otherwise).
+ *   keys, ctr0: the stream a ConstantMedium draws from inside hit?.  keys == NULL: every ray is keyed 0 and starts at draw 0, as rtmi_probe_hit's
+ *     (ctr0 is ignored); else ray k's stream is keyed keys[k] and starts at draw ctr0.  Scenes without media never read it.
+ * rtmi_query_hits: hit? of the world (closest hit) per ray.
+ *   out_hits: [n][RTMI_HIT_REC] doubles.  [0..10] = {hit?, prim, t, p.xyz, normal.xyz, u, v}: bit for bit what rtmi_probe_hit writes for ray k with that ray's
+ *     (t-min, t-max) and the same stream; [11] = the hit primitive's material index.  All zeros on a miss.
+ *   out_counters (may be NULL): {rays, rays that hit}.
+ * rtmi_query_occluded: is ANY primitive hit within the ray's range?  n = n_groups * group rays, ray r of group g is row g * group + r (rtmi_render_rays).
+ *   out_occluded (may be NULL): [n] bytes, 1 iff rtmi_query_hits would report a hit for ray k, else 0.
+ *   out_count (may be NULL): [n_groups] int32, the number of occluded rays of group g (integers: exact in any order); zeroed by the call.
+ *   out_counters (may be NULL): {rays, occluded rays}.
+ *   Only the flag is promised, and it does not depend on the order primitives are visited in.  A primitive ACCEPTS a ray when it has a root in
+ *   (t-min, t-max): for rectangles and triangles t-min <= t <= t-max (hitable.clj:278, 564), for spheres t-min < t < t-max, the second root taken when
+ *   the first is not above t-min (hitable.clj:195-203).  The closest-hit search hands every primitive the closest t so far as its t-max
+ *   (hitable.clj:20), which is the INITIAL t-max until the first acceptance and afterwards only rejects candidates that are not closer: it reports a
+ *   hit iff some primitive accepts the ray against the initial t-max.  The any-hit search tests primitives against the initial t-max and leaves at the
+ *   first acceptance, so whichever primitive it meets first it reports the same flag.  The arithmetic of a test does not depend on the order either: the
+ *   sphere roots' division takes its fast form (make_quot) by the ray's own a, t-min and t-max.  The conservative boxes of the trees are cut at the same
+ *   t-max in both searches.  Worlds that hold a ConstantMedium: with media_seq == 0 the media are asked first, against the caller's interval as the
+ *   closest-hit search asks them, and the surfaces leave early; the Hitlist forms (RTMI_MEDIA_HITLIST / _NARROWED), whose media see the surfaces'
+ *   closest hit, run the closest-hit search unchanged and report its flag.
+ * n <= 2^31 - 64 (else RTMI_E_ARG); n == 0 / n_groups == 0 succeeds and launches nothing.  RTMI_F32: sphere worlds only (RTMI_E_UNSUPPORTED), as the probes.
+ * Errors, in this order: n < 0, n_groups < 0, group <= 0 or an overflow of n: RTMI_E_ARG; rays NULL, or out_hits NULL, with n > 0: RTMI_E_ARG; a bad
+ * handle: RTMI_E_STATE; a bad precision: RTMI_E_ARG.
+ * Results do not depend on options "accel", "flat_below", "suspend_lanes", "scan_variant", "blocks_per_cu" or "workspace_bytes".  The calls touch neither
+ * the context's progressive or adaptive frame nor the scene's revision.  RTMI_FLAG_TIMING covers them: the trace interval of rtmi_last_trace_ms is the
+ * query kernel (the fold interval is empty).  Option "count_traversal" = 1: the FP64 sphere-tree kernels of both calls add their AABB and primitive
+ * tests to what rtmi_last_traversal_counters reads; every other family (flat scans, RTMI_F32, mixed-kind scenes) ignores the option for these calls and
+ * leaves those counters at zero. */
+#define RTMI_HIT_REC 12
+/* host buffers; synchronous */
+int rtmi_query_hits(rtmi_scene *scene, int32_t precision, int32_t n, const double *rays, const double *t_range, double t_min, double t_max,
+                    const uint64_t *keys, uint32_t ctr0, double *out_hits, uint64_t *out_counters);
+/* every pointer a device pointer; asynchronous on `stream` with rtmi_render_device's stream semantics.  Allocates nothing once the context's
+ * workspace has grown to size. */
+int rtmi_query_hits_device(rtmi_scene *scene, int32_t precision, int32_t n, const void *d_rays, const void *d_t_range, double t_min, double t_max,
+                           const void *d_keys, uint32_t ctr0, void *d_out_hits, void *d_out_counters, void *stream);
+/* host buffers; synchronous */
+int rtmi_query_occluded(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, const double *rays, const double *t_range,
+                        double t_min, double t_max, const uint64_t *keys, uint32_t ctr0,
+                        uint8_t *out_occluded, int32_t *out_count, uint64_t *out_counters);
+/* device buffers, as rtmi_query_hits_device */
+int rtmi_query_occluded_device(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, const void *d_rays, const void *d_t_range,
+                               double t_min, double t_max, const void *d_keys, uint32_t ctr0,
+                               void *d_out_occluded, void *d_out_count, void *d_out_counters, void *stream);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

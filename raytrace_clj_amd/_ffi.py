@@ -38,6 +38,7 @@ SYMBOLS = [
     "rtmi_scene_set_geometry", "rtmi_scene_last_refit_ms", "rtmi_test_pack_geometry", "rtmi_test_refit", "rtmi_test_refit_half", "rtmi_test_scene_nodes",
     "rtmi_render_rays", "rtmi_render_rays_device",
     "rtmi_test_stage_layout",
+    "rtmi_query_hits", "rtmi_query_hits_device", "rtmi_query_occluded", "rtmi_query_occluded_device",
 ]
 
 F64, F32 = 0, 1
@@ -48,6 +49,7 @@ SEG_REC = 12
 TILE = 8
 PROG_REC = 5  # doubles per pixel of a progressive tile record: mean rgb, stderr, samples
 FEATURES = 8  # doubles per pixel of rtmi_render_features: albedo rgb, normal xyz, depth, coverage
+HIT_REC = 12  # doubles per ray of rtmi_query_hits: hit?, prim, t, p xyz, normal xyz, u, v, material
 RAYS_REC = 10  # doubles per group record of rtmi_render_rays: sums rgb, Welford mean rgb, Welford M2 rgb, count
 EDIT_STREAM_MAX_BYTES = 32768  # RTMI_EDIT_STREAM_MAX_BYTES: changed row payload one rtmi_scene_set_materials_stream call carries
 
@@ -155,6 +157,10 @@ def lib():
     L.rtmi_render_rays.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, vp, vp, vp, vp, vp]
     L.rtmi_render_rays_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, vp, vp, vp, vp, vp, vp]
     L.rtmi_test_stage_layout.argtypes = [i32, vp, vp, vp, vp, vp]
+    L.rtmi_query_hits.argtypes = [vp, i32, i32, vp, vp, dbl, dbl, vp, C.c_uint32, vp, vp]
+    L.rtmi_query_hits_device.argtypes = [vp, i32, i32, vp, vp, dbl, dbl, vp, C.c_uint32, vp, vp, vp]
+    L.rtmi_query_occluded.argtypes = [vp, i32, i32, i32, vp, vp, dbl, dbl, vp, C.c_uint32, vp, vp, vp]
+    L.rtmi_query_occluded_device.argtypes = [vp, i32, i32, i32, vp, vp, dbl, dbl, vp, C.c_uint32, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

@@ -171,3 +171,31 @@ def orthographic_rays(nx, ny, s_first, s_count, *, lookfrom, lookat, vup, width,
     u, v = _pixel_samples(nx, ny, s_first, s_count, seed)
     origin = lookfrom + ((u - 0.5) * float(width))[:, None] * cu + ((v - 0.5) * height)[:, None] * cv
     return _rays(origin, np.broadcast_to(-w, (len(u), 3)), float(time))
+
+
+# ---- secondary rays for DeviceScene.occluded / ambient_occlusion: not a camera, a hemisphere over every surface point ----
+def hemisphere_rays(points, normals, n_dirs, first=0, seed=0x5EED0002, time=0.0):
+    """n_dirs rays from each of `points` [n, 3] into the hemisphere about `normals` [n, 3] (any length > 0; the rays leave on the normal's side),
+    cosine-weighted by Malley's method: a uniform point of the unit disk (radius sqrt(xi0), angle 2 pi xi1) lifted onto the hemisphere, in an
+    orthonormal frame about the normal.  Ray r of point g is row g * n_dirs + r and takes draws 0 and 1 of the stream keyed
+    sample_key(seed, g, first + r): numpy only, so any split of a point's directions over `first` gives the rays of one call.  Directions are unit
+    vectors up to rounding with normal . direction = sqrt(1 - xi0) > 0.  -> rays [n * n_dirs, 7] float64, every ray carrying `time`."""
+    from . import util
+    points, normals = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(normals, np.float64).reshape(-1, 3)
+    n_dirs, first = int(n_dirs), int(first)
+    if len(points) != len(normals) or n_dirs <= 0 or first < 0:
+        raise ValueError("points and normals must pair up, n_dirs > 0 and first >= 0")
+    g, r = (a.ravel() for a in np.meshgrid(np.arange(len(points)), np.arange(first, first + n_dirs), indexing="ij"))
+    keys = util.sample_keys(seed, g, r)
+    xi0, xi1 = util.draw_uniforms(keys, 0), util.draw_uniforms(keys, 1)
+    rad, phi = np.sqrt(xi0), (2.0 * math.pi) * xi1
+    x, y, z = rad * np.cos(phi), rad * np.sin(phi), np.sqrt(1.0 - xi0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        n = normals / np.sqrt((normals * normals).sum(axis=1))[:, None]
+        # the frame: the coordinate axis least aligned with the normal, made perpendicular to it
+        axis = np.where((np.abs(n[:, 0]) < 0.5)[:, None], np.array([1.0, 0.0, 0.0]), np.array([0.0, 1.0, 0.0]))
+        t = np.cross(axis, n)
+        t = t / np.sqrt((t * t).sum(axis=1))[:, None]
+    b = np.cross(n, t)
+    direction = x[:, None] * t[g] + y[:, None] * b[g] + z[:, None] * n[g]
+    return _rays(points[g], direction, float(time))[0]

@@ -644,6 +644,123 @@ class DeviceScene:
         lin = np.ascontiguousarray(mean.reshape(ny, nx, 3)[::-1])  # group j * nx + i, j = 0 at the bottom
         return lin, self.ctx.denoise(lin, iterations=0)[1], np.ascontiguousarray(err.reshape(ny, nx)[::-1]), total
 
+    # ---- closest-hit and any-hit queries: picking, first hits, shadow / ambient-occlusion / line-of-sight rays --------------------------------
+    @staticmethod
+    def _query_inputs(rays, t_range, keys):
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+        if t_range is not None:
+            t_range = np.ascontiguousarray(t_range, np.float64).reshape(-1, 2)
+            if len(t_range) != len(rays):
+                raise ValueError("%d ranges for %d rays" % (len(t_range), len(rays)))
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+            if len(keys) != len(rays):
+                raise ValueError("%d keys for %d rays" % (len(keys), len(rays)))
+        return rays, t_range, keys
+
+    def query_hits(self, rays, t_min=T_MIN, t_max=T_MAX, t_range=None, keys=None, ctr0=0, precision="f64", return_counters=False):
+        """The closest hit of every ray: rays [n, 7] = origin, direction, time -> [n, HIT_REC] float64 = hit?, prim, t, p xyz, normal xyz, u, v
+        (probe_hit's record, bit for bit) and the hit primitive's material; zeros on a miss.  t_range [n, 2]: each ray's own (t-min, t-max) in place
+        of the scalars.  keys (with ctr0): the streams a ConstantMedium draws from; None keys every ray 0, as probe_hit.  return_counters: also
+        {rays, rays that hit}."""
+        rays, t_range, keys = self._query_inputs(rays, t_range, keys)
+        out, cnt = np.zeros((len(rays), _ffi.HIT_REC), np.float64), np.zeros(2, np.uint64)
+        check(_ffi.lib().rtmi_query_hits(self.handle, _PRECISION[precision], len(rays), ptr(rays), ptr(t_range), float(t_min), float(t_max), ptr(keys),
+                                         int(ctr0), ptr(out), ptr(cnt)))
+        return (out, cnt) if return_counters else out
+
+    def query_hits_device(self, n, rays, out_hits, t_min=T_MIN, t_max=T_MAX, t_range=None, keys=None, ctr0=0, precision="f64", out_counters=None,
+                          stream=None):
+        """query_hits on HBM-resident buffers (torch tensors or raw device pointers; asynchronous, render_device's stream semantics)"""
+        check(_ffi.lib().rtmi_query_hits_device(self.handle, _PRECISION[precision], int(n), ptr(rays), ptr(t_range), float(t_min), float(t_max), ptr(keys),
+                                                int(ctr0), ptr(out_hits), ptr(out_counters), ptr(stream)))
+
+    def occluded(self, rays, group=1, t_min=T_MIN, t_max=T_MAX, t_range=None, keys=None, ctr0=0, precision="f64"):
+        """Is anything hit within each ray's range?  rays [n_groups * group, 7], ray r of group g is row g * group + r -> (flags uint8 [n] = 1 where
+        query_hits would report a hit, counts int32 [n_groups] = occluded rays per group, counters {rays, occluded rays}).  The search leaves at
+        the first primitive that accepts the ray instead of looking for the nearest."""
+        rays, t_range, keys = self._query_inputs(rays, t_range, keys)
+        group = int(group)
+        if group <= 0 or len(rays) % group:
+            raise ValueError("%d rays are not whole groups of %d" % (len(rays), group))
+        n_groups = len(rays) // group
+        flags, counts, cnt = np.zeros(len(rays), np.uint8), np.zeros(n_groups, np.int32), np.zeros(2, np.uint64)
+        check(_ffi.lib().rtmi_query_occluded(self.handle, _PRECISION[precision], n_groups, group, ptr(rays), ptr(t_range), float(t_min), float(t_max),
+                                             ptr(keys), int(ctr0), ptr(flags), ptr(counts), ptr(cnt)))
+        return flags, counts, cnt
+
+    def occluded_device(self, n_groups, group, rays, out_occluded=None, out_count=None, t_min=T_MIN, t_max=T_MAX, t_range=None, keys=None, ctr0=0,
+                        precision="f64", out_counters=None, stream=None):
+        """occluded on HBM-resident buffers (uint8 flags, int32 counts; either may be None); asynchronous, render_device's stream semantics"""
+        check(_ffi.lib().rtmi_query_occluded_device(self.handle, _PRECISION[precision], int(n_groups), int(group), ptr(rays), ptr(t_range), float(t_min),
+                                                    float(t_max), ptr(keys), int(ctr0), ptr(out_occluded), ptr(out_count), ptr(out_counters),
+                                                    ptr(stream)))
+
+    def pixel_centre_rays(self, nx, ny, columns=None, rows=None):
+        """The rays through pixel centres from the camera's origin (a thin lens: its lens centre, at shutter time t0): u = (i + 1/2) / nx, v =
+        (ny - 1 - j + 1/2) / ny for column i and row j from the top, direction lleft + u horiz + v vert - origin in get-ray's operation order
+        (step 1 of rtmi_reproject).  columns / rows: paired index arrays; default every pixel, row-major from the top -> rays [n, 7]."""
+        info = self.camera_info()
+        c = info["cam"]
+        if columns is None:
+            rows, columns = (a.ravel() for a in np.meshgrid(np.arange(ny), np.arange(nx), indexing="ij"))
+        i, j = np.asarray(columns, np.float64).ravel(), np.asarray(rows, np.float64).ravel()
+        u, v = (i + 0.5) / np.float64(nx), ((np.float64(ny - 1) - j) + 0.5) / np.float64(ny)
+        rays = np.empty((len(u), 7), np.float64)
+        rays[:, 0:3] = c[0:3]
+        rays[:, 3:6] = ((c[3:6] + c[6:9] * u[:, None]) + c[9:12] * v[:, None]) + (-c[0:3])
+        rays[:, 6] = 0.0 if info["cam_kind"] == 0 else c[22]
+        return rays
+
+    def pick(self, nx, ny, i, j):
+        """What lies under pixel (column i, row j from the top) of an nx x ny view: None, or {"prim", "material", "t", "p", "normal", "uv"} of the
+        closest hit of the ray through the pixel's centre (pixel_centre_rays)."""
+        if not (0 <= i < nx and 0 <= j < ny):
+            raise ValueError("pixel (%d, %d) outside %d x %d" % (i, j, nx, ny))
+        h = self.query_hits(self.pixel_centre_rays(nx, ny, [i], [j]))[0]
+        if h[0] == 0.0:
+            return None
+        return {"prim": int(h[1]), "material": int(h[11]), "t": float(h[2]), "p": h[3:6].copy(), "normal": h[6:9].copy(), "uv": h[9:11].copy()}
+
+    def ambient_occlusion(self, nx, ny, n_dirs, radius, seed=RENDER_SEED, chunk=None):
+        """Ambient occlusion of the view: [ny, nx] float64 visibility, row 0 = top.  The first hits of the pixel-centre rays (query_hits_device), then
+        n_dirs cosine-weighted rays per hit (camera.hemisphere_rays; point g = pixel j * nx + i, j from the top) from the hit point into the hemisphere
+        on the viewer's side of the surface, t-range (0.001, radius), through occluded_device with one group per pixel: 1 - occluded / n_dirs, and
+        1 where the primary ray missed.  chunk: directions per any-hit call (default all n_dirs); the result does not depend on it."""
+        import torch
+
+        from . import camera as cam
+        if nx <= 0 or ny <= 0 or n_dirs <= 0:
+            raise ValueError("nx, ny, n_dirs must be > 0")
+        n = nx * ny
+        dev = torch.device("cuda", self.ctx.device)
+        primary = self.pixel_centre_rays(nx, ny)
+        d_rays = torch.from_numpy(primary).to(dev)
+        d_hits = torch.zeros((n, _ffi.HIT_REC), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)  # (uploads and fills ran on torch's stream; nothing of torch's is queued after this)
+        self.query_hits_device(n, d_rays, d_hits)
+        torch.cuda.synchronize(dev)  # (a device-wide wait: the context's stream included)
+        hits = d_hits.cpu().numpy()
+        hit = hits[:, 0] != 0.0
+        normals = hits[:, 6:9].copy()
+        away = (normals * primary[:, 3:6]).sum(axis=1) > 0.0  # the normal points away from the viewer: take the other side
+        normals[away] = -normals[away]
+        normals[~hit] = (0.0, 1.0, 0.0)  # (a missed pixel's rays are traced and ignored: every group keeps its place)
+        chunk = n_dirs if chunk is None else max(1, int(chunk))
+        occluded = np.zeros(n, np.int64)
+        for first in range(0, n_dirs, chunk):
+            m = min(chunk, n_dirs - first)
+            rays = cam.hemisphere_rays(hits[:, 3:6], normals, m, first=first, seed=seed, time=primary[0, 6])
+            d_sec = torch.from_numpy(rays).to(dev)
+            d_count = torch.zeros(n, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize(dev)
+            self.occluded_device(n, m, d_sec, out_count=d_count, t_min=T_MIN, t_max=float(radius))
+            torch.cuda.synchronize(dev)
+            occluded += d_count.cpu().numpy()
+        vis = 1.0 - occluded.astype(np.float64) / float(n_dirs)
+        vis[~hit] = 1.0
+        return vis.reshape(ny, nx)
+
     # ---- probes ------------------------------------------------------------------------------------------
     def probe_hit(self, rays, t_min=T_MIN, t_max=T_MAX, precision="f64"):
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
@@ -1170,6 +1287,48 @@ def _render_orbit(sc, name, nx, ny, nr, views, dn_iterations, dn_samples, tstart
     return 0
 
 
+def _ao_flags(argv):
+    """-> (the other arguments, (directions, radius) or None): --ao N [RADIUS] (a number right after N, or --ao=N, is taken; default radius 1.0),
+    checked here, before any device work"""
+    import re
+    rest, ao = [], None
+    number = r"[+]?([0-9]+\.?[0-9]*|\.[0-9]+)([eE][+-]?[0-9]+)?"
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        key, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") else (a, None)
+        i += 1
+        if key != "--ao":
+            rest.append(a)
+            continue
+        if val is None:
+            if i >= len(argv):
+                raise SystemExit("--ao needs a number of directions")
+            val = argv[i]
+            i += 1
+        try:
+            n_dirs = int(val)
+        except ValueError:
+            raise SystemExit("--ao %r is not a number of directions" % val)
+        if n_dirs <= 0:
+            raise SystemExit("--ao takes a positive number of directions (got %d)" % n_dirs)
+        radius = 1.0
+        if i < len(argv) and re.fullmatch(number, argv[i]):
+            radius = float(argv[i])
+            i += 1
+        if not radius > 0.0:
+            raise SystemExit("--ao takes a positive radius (got %g)" % radius)
+        ao = (n_dirs, radius)
+    return rest, ao
+
+
+def _ao_name(name):
+    """x.png -> x.ao.png: the visibility map is written next to the frame"""
+    import os
+    root, ext = os.path.splitext(name)
+    return root + ".ao" + ext
+
+
 def _denoised_name(name):
     """x.png -> x.denoised.png: the filtered image is written next to the unfiltered one"""
     import os
@@ -1227,12 +1386,17 @@ def main(argv=None):
     no cap).  View k is rendered with seed RENDER_SEED + k; it writes name_000.ext (the view's own samples), name_000.acc.ext (accumulated) and,
     with --denoise, name_000.acc.denoised.ext.
     --panorama renders the full sphere around the scene's camera position as an equirectangular image of 2 ny x ny pixels (nx is ignored): rays
-    from camera.panorama_rays through DeviceScene.render_with, ns samples per pixel in chunks of 16.  It does not combine with the other modes."""
+    from camera.panorama_rays through DeviceScene.render_with, ns samples per pixel in chunks of 16.  It does not combine with the other modes.
+    --ao N [RADIUS] also writes the view's ambient occlusion (DeviceScene.ambient_occlusion: N cosine-weighted any-hit rays of length RADIUS, default
+    1.0, from the first hit under every pixel centre) as a grey image, name.ao.ext, beside the frame.  It does not combine with --orbit or --panorama."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
+    argv, ao = _ao_flags(argv)
     panorama = "--panorama" in argv
     argv = [x for x in argv if x != "--panorama"]
     argv, orbit_views = _orbit_flags(argv)
+    if ao is not None and (panorama or orbit_views is not None):
+        raise SystemExit("--ao does not combine with --orbit or --panorama")
     argv, accumulate = _accumulate_flags(argv, orbit_views)
     argv, adaptive_denoised = _adaptive_denoised_flags(argv)
     if adaptive_denoised is not None and not any(a.split("=", 1)[0] == "--denoise" for a in argv):
@@ -1334,6 +1498,14 @@ def main(argv=None):
     _save_image(name, rgb8)
     if filtered is not None:
         _save_image(_denoised_name(name), filtered)
+    if ao is not None:
+        ds = DeviceScene(sc)
+        try:
+            vis = ds.ambient_occlusion(nx, ny, ao[0], ao[1])
+        finally:
+            ds.close()
+        grey = np.floor(255.0 * vis + 0.5).astype(np.uint8)
+        _save_image(_ao_name(name), np.ascontiguousarray(np.repeat(grey[:, :, None], 3, axis=2)))
     return 0
 
 

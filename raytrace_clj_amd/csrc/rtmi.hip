@@ -120,12 +120,16 @@ template <> __device__ inline const double *stat4_of<double>(SceneRef sc) { retu
 template <> __device__ inline const float *stat4_of<float>(SceneRef sc) { return sc.stat4_f; }
 
 // the FP32 cull exists for the FP64 path only; RTMI_F32 falls back to the plain scalar-cache scan
+// ANY (the any-hit queries): the scans may stop once every lane holds a hit, and a lane that holds one skips the moving spheres
+template <bool ANY = false>
 __device__ inline void scan_cull_dispatch(SceneRef sc, const Path<double> &P, double a, double tmin, double &best_t, int &best_i) {
-    scan_all_cull(sc, P, a, tmin, best_t, best_i);
+    scan_all_cull<ANY>(sc, P, a, tmin, best_t, best_i);
 }
+template <bool ANY = false>
 __device__ inline void scan_cull_dispatch(SceneRef sc, const Path<float> &P, float a, float tmin, float &best_t, int &best_i) {
-    scan_static_pipe<float, false>(ScalarPrims<float>(sc.stat4_f), sc.n_static, 0, P, a, tmin, best_t, best_i);
+    scan_static_pipe<float, false, ANY>(ScalarPrims<float>(sc.stat4_f), sc.n_static, 0, P, a, tmin, best_t, best_i);
     if (best_i >= 0) best_i = sc.stat_orig[best_i];
+    if (ANY && best_i >= 0) return;
     if (sc.n_moving > 0) {
         int best_orig = best_i >= 0 ? best_i : 0x7fffffff, scan_i = -1;
         scan_moving<float>(sc, P, a, tmin, best_t, scan_i, best_orig);
@@ -138,7 +142,10 @@ __device__ inline void scan_cull_dispatch(SceneRef sc, const Path<float> &P, flo
 // MULTI (LDS variants only): the static spheres do not fit one LDS tile; every thread of the workgroup must call this.
 // section 8(f3) scenes (FP64 only): BVH or culled flat scan over mixed primitive kinds with the any-order tie rule
 // MSEQ: the instantiations for RTMI_MEDIA_HITLIST (1) and RTMI_MEDIA_NARROWED (2) worlds (their own kernels: the plain mixed-kind kernels keep their registers)
-template <bool SLICED = false, bool COUNT = false, int MSEQ = 0>
+// ANY (the any-hit queries, MSEQ = 0 only -- the media_seq worlds run the closest-hit search as it is): only best_i >= 0 is wanted.  The media come first
+// and see the caller's interval whatever the surfaces do; a lane one of them hits is done, the others scan the surfaces against the initial t-max
+// and leave at the first accepted primitive (scan_bvh_ext).
+template <bool SLICED = false, bool COUNT = false, int MSEQ = 0, bool ANY = false>
 __device__ inline void intersect_ext(SceneRef sc, int *stack, bool bvh, Path<double> &P, bool active, double tmin, double tmax, double &best_t, int &best_i,
                                      bool *mid = nullptr, int min_lanes = 0, unsigned *cnt = nullptr, int susp_off = RTMI_BVH_STACK * RTMI_BVH_STRIDE) {
     best_t = tmax; best_i = -1;
@@ -202,28 +209,31 @@ __device__ inline void intersect_ext(SceneRef sc, int *stack, bool bvh, Path<dou
         for (int k = 0; k < sc.n_media; ++k) ext_medium_test(sc, sc.media_idx[k], P, tmin, tmax, H, chord, COUNT ? cnt : nullptr, nullptr, k);
         RTMI_PH(PH_MEDIA)
     }
+    if (ANY && H.any()) { best_i = ext_winner(H); best_t = H.t; return; }
     if (bvh) {
         if (SLICED) {
             const bool done = scan_bvh_ext<true, COUNT>(sc, stack, P, a, tmin, H, stack + susp_off, *mid, min_lanes, cnt);
             *mid = !done;
             if (!done) return;
-        } else scan_bvh_ext<false, COUNT>(sc, stack, P, a, tmin, H, nullptr, false, 0, cnt);
-    } else if (sc.small_scan) scan_small_ext(sc, P, tmin, H); // (wave-uniform)
-    else scan_all_cull_ext(sc, P, a, tmin, H);
+        } else scan_bvh_ext<false, COUNT, ANY>(sc, stack, P, a, tmin, H, nullptr, false, 0, cnt);
+    } else if (sc.small_scan) scan_small_ext<ANY>(sc, P, tmin, H); // (wave-uniform)
+    else scan_all_cull_ext<ANY>(sc, P, a, tmin, H);
     RTMI_PH(PH_BVH_POST)
     best_i = ext_winner(H);
     if (best_i >= 0) best_t = H.t;
 }
-template <bool SLICED = false, bool COUNT = false, int MSEQ = 0>
+template <bool SLICED = false, bool COUNT = false, int MSEQ = 0, bool ANY = false>
 __device__ inline void intersect_ext(SceneRef, int *, bool, Path<float> &, bool, float, float tmax, float &best_t, int &best_i, bool * = nullptr, int = 0, unsigned * = nullptr, int = 0) { best_t = tmax; best_i = -1; }
 
 // NOGRID: the plain (not time-sliced) RENDER kernel -- never launched on a scene with an entry grid, so it carries no code for one (the probe
 // kernels, also not time-sliced, do: they walk a long segment's pieces in a loop of their own)
-template <typename R, bool MULTI, int VARIANT, bool EXT = false, bool COUNT = false, bool SLICED = false, int MSEQ = 0, bool NOGRID = false>
+// ANY (query_kernel's any-hit instantiations; never SLICED, never the LDS-staged scans): best_i >= 0 iff the closest-hit search would find a hit; which
+// primitive and which t is arbitrary
+template <typename R, bool MULTI, int VARIANT, bool EXT = false, bool COUNT = false, bool SLICED = false, int MSEQ = 0, bool NOGRID = false, bool ANY = false>
 __device__ inline void intersect_world(SceneRef sc, Prim4<R> *lds, int prims_per_tile, int n_ptiles, Path<R> &P,
                                        bool active, R tmin, R tmax, R &best_t, int &best_i, unsigned *cnt = nullptr, bool *mid = nullptr, int min_lanes = 0,
                                        int susp_off = RTMI_BVH_STACK * RTMI_BVH_STRIDE) {
-    if (EXT) { intersect_ext<SLICED, COUNT, MSEQ>(sc, reinterpret_cast<int *>(lds), VARIANT == SCAN_BVH, P, active, tmin, tmax, best_t, best_i, mid, min_lanes, cnt, susp_off); return; }
+    if (EXT) { intersect_ext<SLICED, COUNT, MSEQ, ANY && MSEQ == 0>(sc, reinterpret_cast<int *>(lds), VARIANT == SCAN_BVH, P, active, tmin, tmax, best_t, best_i, mid, min_lanes, cnt, susp_off); return; }
     best_t = tmax;
     best_i = -1;
     const R a = dot3(P.dx, P.dy, P.dz, P.dx, P.dy, P.dz);
@@ -234,16 +244,16 @@ __device__ inline void intersect_world(SceneRef sc, Prim4<R> *lds, int prims_per
                 const bool done = scan_bvh<R, COUNT, true>(sc, stack, P, a, tmin, best_t, best_i, [&]() { scan_cull_dispatch(sc, P, a, tmin, best_t, best_i); }, cnt,
                                                            stack + susp_off, *mid, min_lanes);
                 *mid = !done;
-            } else scan_bvh<R, COUNT, false, !NOGRID>(sc, stack, P, a, tmin, best_t, best_i, [&]() { scan_cull_dispatch(sc, P, a, tmin, best_t, best_i); }, cnt);
+            } else scan_bvh<R, COUNT, false, !NOGRID, ANY>(sc, stack, P, a, tmin, best_t, best_i, [&]() { scan_cull_dispatch<ANY>(sc, P, a, tmin, best_t, best_i); }, cnt);
         }
         return;
     }
     if (VARIANT == SCAN_SGPR_CULL) { // all primitives, original order; returns the original index
-        if (active) scan_cull_dispatch(sc, P, a, tmin, best_t, best_i);
+        if (active) scan_cull_dispatch<ANY>(sc, P, a, tmin, best_t, best_i);
         return;
     }
     if (VARIANT == SCAN_SGPR) {
-        if (active) scan_static_pipe<R, false>(ScalarPrims<R>(stat4_of<R>(sc)), sc.n_static, 0, P, a, tmin, best_t, best_i);
+        if (active) scan_static_pipe<R, false, ANY>(ScalarPrims<R>(stat4_of<R>(sc)), sc.n_static, 0, P, a, tmin, best_t, best_i);
     } else if (!MULTI) {
         if (active) {
             if (VARIANT == SCAN_LDS_PIPE) scan_static_pipe<R, true>(LdsPrims<R>{lds}, sc.n_static, 0, P, a, tmin, best_t, best_i);
@@ -266,7 +276,7 @@ __device__ inline void intersect_world(SceneRef sc, Prim4<R> *lds, int prims_per
     // moving spheres, with ties resolved by original index (first in Hitlist order wins, hitable.clj:20)
     if (active) {
         if (best_i >= 0) best_i = sc.stat_orig[best_i];
-        if (sc.n_moving > 0) {
+        if (sc.n_moving > 0 && !(ANY && best_i >= 0)) {
             int best_orig = best_i >= 0 ? best_i : 0x7fffffff, scan_i = -1;
             scan_moving<R>(sc, P, a, tmin, best_t, scan_i, best_orig);
             if (scan_i >= 0) best_i = best_orig;
@@ -1301,6 +1311,101 @@ __global__ void __launch_bounds__(kBlock) rays_fold_kernel(const double *__restr
     se[g] = err;
 }
 
+// ---- closest-hit and any-hit queries on caller-supplied rays (rtmi_query_hits*, rtmi_query_occluded*) ------------------------------------------------
+// A work item is one ray = one hit? of the world (probe_hit_kernel's trip), so every lane is free again after every trip: persistent waves over one queue with
+// rays_kernel's claim -- qblock (a multiple of 64) consecutive items per atomic --, of which the wave takes 64 consecutive rays per trip, lane order = row order.
+// ANY = false: the record of probe_hit_kernel (resolve_any with every uv) plus the material.  ANY = true: the flag alone, found by the searches that leave at
+// the first accepted primitive (intersect_world<..., ANY>); group counts are popcounts over each run of lanes that share a group -- rows are consecutive, so a
+// group is one run per wave -- added with one atomic per run.  COUNT (<double, SCAN_BVH, EXT = false> only): the traversal counters of option "count_traversal".
+struct QueryParams {
+    const double *rays;    // [total_items][7]
+    const double *t_range; // [total_items][2], or null: every ray takes tmin, tmax
+    const u64 *keys;       // [total_items], or null: every stream is keyed 0
+    double tmin, tmax;
+    unsigned ctr0;
+    unsigned group;        // ANY with count: rays per group
+    unsigned total_items;  // <= 2^31 - 64: a claim past the end cannot wrap the queue head
+    unsigned qblock;       // items a wave claims per queue access, a multiple of 64
+    unsigned *queue;       // zeroed before the launch
+    double *hits;          // ANY = false: [total_items][RTMI_HIT_REC]
+    unsigned char *occluded; // ANY = true: [total_items], or null
+    int *count;            // ANY = true: [ceil(total_items / group)], zeroed before the launch, or null
+    u64 *counters;         // [0] += rays, [1] += rays that hit; zeroed before the launch
+    u64 *trav;             // COUNT: [0] += AABB tests, [1] += primitive tests
+};
+
+template <typename R, int VARIANT, bool EXT = false, int MSEQ = 0, bool ANY = false, bool COUNT = false>
+__global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WAVES) : RTMI_MIN_WAVES) query_kernel(ScenePtr scp, QueryParams qp) {
+    static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the claim loop is per wave");
+    static_assert(!COUNT || (VARIANT == SCAN_BVH && !EXT && sizeof(R) == sizeof(double)), "traversal counters: the FP64 sphere tree only");
+    SceneRef sc = *scp;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    Prim4<R> *lds = reinterpret_cast<Prim4<R> *>(smem);
+    const int lane = threadIdx.x & 63;
+    const unsigned total_items = qp.total_items;
+    unsigned w_cur = 0, w_end = 0; // this wave's claimed range [w_cur, w_end): wave-uniform
+    unsigned n_rays = 0, n_hit = 0; // wave-uniform tallies
+    unsigned ntrav[2] = {0u, 0u};
+    for (;;) {
+        if (w_cur == w_end) {
+            unsigned base = 0;
+            if (lane == 0) base = atomicAdd(qp.queue, qp.qblock);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base >= total_items) break;
+            w_cur = base;
+            w_end = min(base + qp.qblock, total_items);
+        }
+        const unsigned m = w_cur + (unsigned)lane;
+        const bool active = m < w_end;
+        w_cur = min(w_cur + 64u, w_end);
+        const unsigned row = active ? m : 0u; // (an idle lane loads row 0 and traces nothing)
+        Path<R> P;
+        load_ray<R>(qp.rays + (size_t)row * 7, P);
+        if (qp.keys) seed_stream(P, qp.keys[row], qp.ctr0);
+        R tmin = (R)qp.tmin, tmax = (R)qp.tmax;
+        if (qp.t_range) { const double *q = qp.t_range + (size_t)row * 2; tmin = (R)q[0]; tmax = (R)q[1]; }
+        R best_t; int best_i;
+        intersect_world<R, true, VARIANT, EXT, COUNT, false, MSEQ, false, ANY>(sc, lds, 0, 1, P, active, tmin, tmax, best_t, best_i, COUNT ? ntrav : nullptr);
+        const bool hit = active && best_i >= 0;
+        const u64 hit_mask = __ballot(hit);
+        n_rays += (unsigned)__popcll(__ballot(active));
+        n_hit += (unsigned)__popcll(hit_mask);
+        if (ANY) {
+            if (active && qp.occluded) qp.occluded[m] = hit ? 1 : 0;
+            if (qp.count) {
+                const unsigned g = row / qp.group;
+                const unsigned g_prev = (unsigned)__shfl_up((int)g, 1);
+                const bool head = active && (lane == 0 || g != g_prev); // the first lane of its group's run in this wave
+                const u64 heads = __ballot(head);
+                if (head) {
+                    const u64 later = lane == 63 ? 0ull : heads >> (lane + 1);
+                    const int end = later ? lane + 1 + (__ffsll((long long)later) - 1) : 64; // where the next run begins (idle lanes hold no hit)
+                    const u64 run = (end == 64 ? ~0ull : (1ull << end) - 1ull) & ~((1ull << lane) - 1ull);
+                    const int k = __popcll(hit_mask & run);
+                    if (k) atomicAdd(qp.count + g, k);
+                }
+            }
+        } else if (active) {
+            double *o = qp.hits + (size_t)m * RTMI_HIT_REC;
+            if (best_i < 0) {
+#pragma unroll
+                for (int c = 0; c < RTMI_HIT_REC; ++c) o[c] = 0.0;
+            } else {
+                HitRec<R> h;
+                resolve_any<R, EXT>(sc, P, best_t, best_i, h);
+                o[0] = 1.0; o[1] = h.orig; o[2] = h.t; o[3] = h.px; o[4] = h.py; o[5] = h.pz;
+                o[6] = h.nx; o[7] = h.ny; o[8] = h.nz; o[9] = h.u; o[10] = h.v; o[11] = h.mat;
+            }
+        }
+    }
+    if (lane == 0 && n_rays) { atomicAdd(qp.counters, (u64)n_rays); if (n_hit) atomicAdd(qp.counters + 1, (u64)n_hit); }
+    if (COUNT) {
+        u64 a = ntrav[0], b = ntrav[1];
+        for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
+        if (lane == 0) { atomicAdd(qp.trav, a); atomicAdd(qp.trav + 1, b); }
+    }
+}
+
 // ---- edge-aware denoiser (rtmi_denoise*): an a-trous wavelet filter over planar FP64 images -----------------------------------------------------
 // Planes of nx * ny doubles: colour r, g, b and the variance of the mean V (two sets: a pass reads one and writes the other), then normal xyz,
 // albedo rgb and depth (read only).  Lanes run along x: every tap of a wave is one contiguous run per plane.
@@ -2258,7 +2363,7 @@ RTMI_EXPORT int rtmi_test_stage_layout(int32_t n, const uint64_t *elem_bytes, co
 }
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 215; } // 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 216; } // 216: closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*); 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -4474,14 +4579,15 @@ struct ProbePaths {
 
 // The probe instantiation the scene and the context select (precision x mixed kinds x media_seq x accel / scan_variant) and its dynamic LDS:
 // launch(kernel, lds_bytes, prims_per_tile, n_ptiles).  Mixed-kind scenes have FP64 kernels only (the entries refuse RTMI_F32 for them).
-template <typename Family, typename R, typename Launch> void with_probe_kernel(const rtmi_scene *s, Launch launch) {
+// force_flat: answer a request for the tree with the flat scan (the queries' use of option "flat_below"; the scans find the same hits).
+template <typename Family, typename R, typename Launch> void with_probe_kernel(const rtmi_scene *s, Launch launch, bool force_flat = false) {
     const rtmi_ctx *c = s->ctx;
     int ppt, npt;
     size_t lds;
     lds_plan(c, s->dev.n_static, sizeof(R), &ppt, &npt, &lds);
     if (Family::wave_level) lds = 64;
     const size_t bvh_lds = (size_t)RTMI_BVH_STACK * kBlock * sizeof(int) + 16; // the traversal's stack columns
-    const bool bvh = c->accel == RTMI_ACCEL_BVH;
+    const bool bvh = c->accel == RTMI_ACCEL_BVH && !force_flat;
     if constexpr (std::is_same<R, double>::value) {
         if (s->dev.has_ext) { // (operands in the order the kernels were always instantiated in: the device code's inlining follows that order)
             const int seq = s->dev.media_seq;
@@ -5030,6 +5136,155 @@ RTMI_EXPORT int rtmi_render_rays(rtmi_scene *s, int32_t precision, int32_t n_gro
     if (rc) return rc;
     rc = with_real(precision, [&](auto r) {
         return render_rays_impl<decltype(r)>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out, d_cnt, c->stream);
+    });
+    return rc ? rc : io.finish();
+}
+
+// ---- closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*) --------------------------------------------------------------------
+namespace {
+// query_kernel's instantiations are chosen where the probe kernels' are (with_probe_kernel), the LDS-staged scans answered with the scalar-cache scan as
+// for rays_kernel.  COUNT (option "count_traversal") exists for the FP64 sphere tree only: every other family runs the kernel it always runs.
+template <bool ANY, bool COUNT> struct QueryPass {
+    static constexpr bool wave_level = true;
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() {
+        constexpr int W = V < SCAN_SGPR ? (int)SCAN_SGPR : V;
+        return query_kernel<R, W, EXT, MSEQ, ANY, COUNT && W == SCAN_BVH && !EXT && std::is_same<R, double>::value>;
+    }
+};
+
+// the argument checks of the four entries, in the header's order; out: the array a call cannot do without (null when it has none)
+int check_query_args(rtmi_scene *s, int precision, long long n, bool dims_ok, const void *rays, bool out_ok) {
+    if (!dims_ok) return fail(RTMI_E_ARG, "n, n_groups must be >= 0 and group > 0");
+    if (n > kRaysMax) return fail(RTMI_E_ARG, "%lld rays exceed 2^31 - 64", n);
+    if (n > 0 && !rays) return fail(RTMI_E_ARG, "rays is NULL");
+    if (n > 0 && !out_ok) return fail(RTMI_E_ARG, "out_hits is NULL");
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    if (precision != RTMI_F64 && precision != RTMI_F32) return fail(RTMI_E_ARG, "precision must be RTMI_F64 or RTMI_F32");
+    if (precision == RTMI_F32 && s->dev.has_ext) return fail(RTMI_E_UNSUPPORTED, "rectangles / triangles / instances are FP64 only");
+    return RTMI_OK;
+}
+
+// The launch, on `st`, every pointer a device pointer: counters (and group counts) zeroed, then one query_kernel over the n rays.
+template <typename R, bool ANY>
+int query_impl(rtmi_scene *s, int n, int n_groups, int group, const double *d_rays, const double *d_range, double t_min, double t_max, const u64 *d_keys,
+               unsigned ctr0, double *d_hits, unsigned char *d_occ, int *d_count, u64 *d_cnt, hipStream_t st) {
+    rtmi_ctx *c = s->ctx;
+    int rc = c->counters.ensure(8 * sizeof(u64)); // [0..1] the counters when the caller passes no buffer, [2] the work-queue head, [3..4] traversal counters
+    if (rc) return rc;
+    if (!d_cnt) d_cnt = reinterpret_cast<u64 *>(c->counters.p);
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(u64), st));
+    if (ANY && d_count) HIP_TRY(hipMemsetAsync(d_count, 0, (size_t)n_groups * sizeof(int), st));
+    const bool count = c->count_traversal != 0;
+    if (count) {
+        HIP_TRY(hipMemsetAsync(reinterpret_cast<u64 *>(c->counters.p) + 3, 0, 2 * sizeof(u64), st));
+        c->last_stream = st;
+    }
+    QueryParams qp;
+    qp.rays = d_rays; qp.t_range = d_range; qp.keys = d_keys; qp.tmin = t_min; qp.tmax = t_max; qp.ctr0 = ctr0;
+    qp.group = (unsigned)std::max(1, group); qp.total_items = (unsigned)n;
+    qp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 2);
+    qp.hits = d_hits; qp.occluded = d_occ; qp.count = d_count; qp.counters = d_cnt;
+    qp.trav = reinterpret_cast<u64 *>(c->counters.p) + 3;
+    { // claim size: as rays_kernel's
+        const long long per_wave = (long long)n / std::max(1, c->cus * 16);
+        unsigned qb = 64u;
+        while (qb < 1024u && per_wave >= (long long)qb * 16) qb *= 2;
+        qp.qblock = qb;
+    }
+    auto run = [&](auto kern, size_t lds, int, int) {
+        rc = [&]() -> int {
+            int resident = 0;
+            const int rco = resident_blocks(c, reinterpret_cast<const void *>(kern), kBlock, lds, &resident);
+            if (rco) return rco;
+            const long long persistent = (long long)c->cus * std::max(1, std::min(c->blocks_per_cu, resident));
+            hipEvent_t e1 = nullptr;
+            const int rce = open_timed(c, st, &e1);
+            if (rce) return rce;
+            HIP_TRY(hipMemsetAsync(qp.queue, 0, sizeof(unsigned), st));
+            const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(persistent, ((long long)n + kBlock - 1) / kBlock));
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, s->d_dev, qp);
+            HIP_TRY(hipGetLastError());
+            if (e1) { HIP_TRY(hipEventRecord(e1, st)); return close_timed_fold(c, st); } // (no fold follows: an empty fold interval)
+            return RTMI_OK;
+        }();
+    };
+    // a tree over a handful of mixed-kind primitives costs more than scanning them (choose_trace_kernel): the same shortcut, the same knobs
+    const LaunchKnobs knobs = read_launch_knobs();
+    const bool flat = s->dev.has_ext && !count && s->dev.n_all < (knobs.flat_below ? std::atoi(knobs.flat_below) : c->flat_below);
+    if (count) with_probe_kernel<QueryPass<ANY, true>, R>(s, run);
+    else with_probe_kernel<QueryPass<ANY, false>, R>(s, run, flat);
+    return rc;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_query_hits_device(rtmi_scene *s, int32_t precision, int32_t n, const void *d_rays, const void *d_t_range, double t_min, double t_max,
+                                       const void *d_keys, uint32_t ctr0, void *d_out_hits, void *d_out_counters, void *stream) {
+    const int rc = check_query_args(s, precision, n, n >= 0, d_rays, d_out_hits != nullptr);
+    if (rc || n == 0) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream_of(c, stream);
+    return with_real(precision, [&](auto r) {
+        return query_impl<decltype(r), false>(s, n, 0, 1, reinterpret_cast<const double *>(d_rays), reinterpret_cast<const double *>(d_t_range), t_min, t_max,
+                                              reinterpret_cast<const u64 *>(d_keys), ctr0, reinterpret_cast<double *>(d_out_hits), nullptr, nullptr,
+                                              reinterpret_cast<u64 *>(d_out_counters), st);
+    });
+}
+
+RTMI_EXPORT int rtmi_query_hits(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, const double *t_range, double t_min, double t_max,
+                                const uint64_t *keys, uint32_t ctr0, double *out_hits, uint64_t *out_counters) {
+    int rc = check_query_args(s, precision, n, n >= 0, rays, out_hits != nullptr);
+    if (rc || n == 0) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HostIo io(c);
+    double *d_rays, *d_range, *d_hits;
+    u64 *d_keys, *d_cnt;
+    io.in(&d_rays, (size_t)n * 7, rays); io.in(&d_range, (size_t)n * 2, t_range); io.in(&d_keys, (size_t)n, keys);
+    io.out(&d_hits, (size_t)n * RTMI_HIT_REC, out_hits); io.work(&d_cnt, 2, out_counters);
+    rc = io.stage();
+    if (rc) return rc;
+    rc = with_real(precision, [&](auto r) {
+        return query_impl<decltype(r), false>(s, n, 0, 1, d_rays, d_range, t_min, t_max, d_keys, ctr0, d_hits, nullptr, nullptr, d_cnt, c->stream);
+    });
+    return rc ? rc : io.finish();
+}
+
+RTMI_EXPORT int rtmi_query_occluded_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, const void *d_rays, const void *d_t_range,
+                                           double t_min, double t_max, const void *d_keys, uint32_t ctr0, void *d_out_occluded, void *d_out_count,
+                                           void *d_out_counters, void *stream) {
+    const long long n = (long long)n_groups * group;
+    const int rc = check_query_args(s, precision, n, n_groups >= 0 && group > 0, d_rays, true);
+    if (rc || n_groups == 0) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream_of(c, stream);
+    return with_real(precision, [&](auto r) {
+        return query_impl<decltype(r), true>(s, (int)n, n_groups, group, reinterpret_cast<const double *>(d_rays), reinterpret_cast<const double *>(d_t_range),
+                                             t_min, t_max, reinterpret_cast<const u64 *>(d_keys), ctr0, nullptr, reinterpret_cast<unsigned char *>(d_out_occluded),
+                                             reinterpret_cast<int *>(d_out_count), reinterpret_cast<u64 *>(d_out_counters), st);
+    });
+}
+
+RTMI_EXPORT int rtmi_query_occluded(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, const double *rays, const double *t_range,
+                                    double t_min, double t_max, const uint64_t *keys, uint32_t ctr0, uint8_t *out_occluded, int32_t *out_count,
+                                    uint64_t *out_counters) {
+    const long long n = (long long)n_groups * group;
+    int rc = check_query_args(s, precision, n, n_groups >= 0 && group > 0, rays, true);
+    if (rc || n_groups == 0) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HostIo io(c);
+    double *d_rays, *d_range;
+    u64 *d_keys, *d_cnt;
+    unsigned char *d_occ;
+    int *d_count;
+    io.in(&d_rays, (size_t)n * 7, rays); io.in(&d_range, (size_t)n * 2, t_range); io.in(&d_keys, (size_t)n, keys);
+    io.out(&d_occ, (size_t)n, out_occluded); io.out(&d_count, (size_t)n_groups, out_count); io.work(&d_cnt, 2, out_counters);
+    rc = io.stage();
+    if (rc) return rc;
+    rc = with_real(precision, [&](auto r) {
+        return query_impl<decltype(r), true>(s, (int)n, n_groups, group, d_rays, d_range, t_min, t_max, d_keys, ctr0, nullptr, d_occ, d_count, d_cnt, c->stream);
     });
     return rc ? rc : io.finish();
 }

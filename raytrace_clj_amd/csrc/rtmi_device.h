@@ -912,7 +912,9 @@ __device__ inline void test_group(const Group4<R> &G, int g, int last, int idx_b
     }
 }
 
-template <typename R, bool CLAMP, typename Src>
+// ANY (the any-hit queries, query_kernel): the scan may stop at the first accepted root -- wave-uniform indices, so it stops when EVERY lane of the
+// wave holds one.  Which primitive a lane then reports is arbitrary; that it holds one is not (see scan_bvh).
+template <typename R, bool CLAMP, bool ANY = false, typename Src>
 __device__ inline void scan_static_pipe(const Src &src, int n, int idx_base, const Path<R> &P, R a, R tmin, R &best_t, int &best_i) {
     if (n <= 0) return;
     const int last = n - 1;
@@ -923,6 +925,7 @@ __device__ inline void scan_static_pipe(const Src &src, int n, int idx_base, con
         test_group<R>(A, g, last, idx_base, P, a, tmin, behind_ok, best_t, best_i);
         A = load_group<R, CLAMP>(src, g + 8, last);
         test_group<R>(B, g + 4, last, idx_base, P, a, tmin, behind_ok, best_t, best_i);
+        if (ANY && __all(best_i >= 0)) break;
     }
 }
 
@@ -1026,6 +1029,7 @@ __device__ inline void cull_test_group(const CullGroup &G, int g, int last, cons
 }
 
 // the culled scan over ALL primitives in Hitlist order; best_i is the ORIGINAL primitive index
+template <bool ANY = false>
 __device__ inline void scan_all_cull(SceneRef sc, const Path<double> &P, double a, double tmin, double &best_t, int &best_i) {
     const int n = sc.n_all;
     if (n <= 0) return;
@@ -1040,6 +1044,7 @@ __device__ inline void scan_all_cull(SceneRef sc, const Path<double> &P, double 
         cull_test_group(A, g, last, exact12, P, c, a, tmin, behind_ok, best_t, best_i);
         A = load_cull_group(cull20, (g >> 2) + 2);
         cull_test_group(B, g + 4, last, exact12, P, c, a, tmin, behind_ok, best_t, best_i);
+        if (ANY && __all(best_i >= 0)) break; // (wave-uniform, as scan_static_pipe)
     }
 }
 
@@ -1203,7 +1208,9 @@ __device__ inline BvhCursor bvh_cursor_at_root(SceneRef sc, int *stack) { return
 // of the unfinished lanes, as soon as fewer than min_lanes lanes still have nodes to visit (checked after each exact-test phase,
 // so every call makes progress): the caller lets the finished lanes move on and calls again with the same cursors and stack
 // columns.  Per lane the visiting order is the same depth-first order either way.  min_lanes = 0: plain while-while.
-template <bool NODE16, bool COUNT, bool SLICE, typename Leaf, typename BestHi>
+// ANY (the any-hit queries): leaf(code) returns whether the lane now holds an accepted hit; such a lane leaves the traversal at once (its cursor is
+// RTMI_BVH_EMPTY: the caller starts its next ray from the root of its stack column).  Default false: leaf's result, if any, is not looked at.
+template <bool NODE16, bool COUNT, bool SLICE, bool ANY = false, typename Leaf, typename BestHi>
 __device__ inline void bvh_traverse_fmt(SceneRef sc, const BvhRay &r, BvhCursor &cur, int min_lanes, Leaf leaf, BestHi best, unsigned *cnt) {
     int node = cur.node;
     if (node == RTMI_BVH_EMPTY) return;
@@ -1294,9 +1301,12 @@ __device__ inline void bvh_traverse_fmt(SceneRef sc, const BvhRay &r, BvhCursor 
             { const int c = __popcll(__ballot(1)); if ((threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(&g_hist[64 + c], 1ull); }
 #endif
             if (COUNT) cnt[1] += 1;
-            leaf(node);
+            bool leave = false;
+            if constexpr (ANY) leave = leaf(node);
+            else leaf(node);
             best_hi = best();
             node = tos; top -= stride; tos = *top;
+            if (ANY && leave) { node = RTMI_BVH_EMPTY; tos = RTMI_BVH_EMPTY; }
             RTMI_PH(PH_LEAF)
         }
         if (SLICE && __popcll(__ballot(node != RTMI_BVH_EMPTY)) < min_lanes) break; // wave-uniform
@@ -1393,10 +1403,10 @@ __device__ inline float bvh_grid_entry(SceneRef sc, const BvhRay &r, float ox, f
 }
 
 // one loop per record format (a format test inside the loop costs 5 %)
-template <bool COUNT = false, bool SLICE = false, typename Leaf, typename BestHi>
+template <bool COUNT = false, bool SLICE = false, bool ANY = false, typename Leaf, typename BestHi>
 __device__ inline void bvh_traverse(SceneRef sc, const BvhRay &r, BvhCursor &cur, int min_lanes, Leaf leaf, BestHi best, unsigned *cnt = nullptr) {
-    if (sc.bvh_node16) bvh_traverse_fmt<true, COUNT, SLICE>(sc, r, cur, min_lanes, leaf, best, cnt);
-    else bvh_traverse_fmt<false, COUNT, SLICE>(sc, r, cur, min_lanes, leaf, best, cnt);
+    if (sc.bvh_node16) bvh_traverse_fmt<true, COUNT, SLICE, ANY>(sc, r, cur, min_lanes, leaf, best, cnt);
+    else bvh_traverse_fmt<false, COUNT, SLICE, ANY>(sc, r, cur, min_lanes, leaf, best, cnt);
 }
 
 // what a suspended lane keeps between two calls of scan_bvh (time-sliced traversal): LDS, one column per thread like the stack
@@ -1414,7 +1424,12 @@ template <> __device__ inline float best_from_words<float>(int w0, int) { return
 // cursor and closest hit so far are then in susp (RTMI_BVH_SUSPEND_WORDS columns of blockDim.x words) -- and the caller passes
 // resume = true on the next call with the SAME ray; best_t / best_i are only final when the function returns true.
 // CHUNK = false: the instantiation for scenes WITHOUT an entry grid (the plain render kernel: it is never launched on a scene that has one)
-template <typename R, bool COUNT = false, bool SLICE = false, bool CHUNK = true, typename Flat>
+// ANY (the any-hit queries; never with SLICE): only WHETHER a primitive has an accepted root is wanted, so the lane returns at the first one -- after
+// the big primitives, after any leaf, after any piece of the grid walk, in the exact MovingSphere pass.  The answer does not depend on the visiting
+// order: until the first acceptance best_t is the caller's t-max, so every test before it ran against the INITIAL interval, and the closest-hit search
+// finds a hit iff some primitive has a root in that interval (a running t-max only ever rejects non-minimal candidates).  The boxes are cut at
+// float_above(best_t) = the initial t-max as well, and make_quot's fast path is decided by a, t-min and the initial t-max: the same for both searches.
+template <typename R, bool COUNT = false, bool SLICE = false, bool CHUNK = true, bool ANY = false, typename Flat>
 __device__ inline bool scan_bvh(SceneRef sc, int *stack, const Path<R> &P, R a, R tmin, R &best_t, int &best_i, Flat flat, unsigned *cnt = nullptr,
                                 int *susp = nullptr, bool resume = false, int min_lanes = 0) {
     constexpr bool WALK = CHUNK && RTMI_GRID_CHUNK;
@@ -1452,11 +1467,14 @@ __device__ inline bool scan_bvh(SceneRef sc, int *stack, const Path<R> &P, R a, 
     RTMI_PH(PH_BVH_SETUP)
     if (!(SLICE && resume)) { // 1. the big primitives (sky dome, ground, ...): exact test, ascending Hitlist index
         if (COUNT) cnt[1] += (unsigned)sc.n_big;
-        for (int k = 0; k < sc.n_big; ++k) exact_prim_test<R>(exact12, sc.big_idx[k], sc.big_idx[k], P, qa, tmin, behind_ok, best_t, best_i);
+        for (int k = 0; k < sc.n_big; ++k) {
+            exact_prim_test<R>(exact12, sc.big_idx[k], sc.big_idx[k], P, qa, tmin, behind_ok, best_t, best_i);
+            if (ANY && best_i >= 0) return true;
+        }
         RTMI_PH(PH_BIG)
     }
     // 2. the tree
-    auto leaf = [&](int code) { exact_prim_test_lane<R>(exact12, code, P, qa, tmin, behind_ok, best_t, best_i); };
+    auto leaf = [&](int code) { exact_prim_test_lane<R>(exact12, code, P, qa, tmin, behind_ok, best_t, best_i); return best_i >= 0; };
     auto best = [&]() { return float_above((double)best_t); };
     const float e_rel = sizeof(R) == sizeof(float) ? 4.0e-3f + 1.0f / 65536.0f : 1.0f / 65536.0f;
     bool enter = CHUNK && sc.grid_n && (!(SLICE && resume) || reenter), first = !reenter;
@@ -1466,7 +1484,8 @@ __device__ inline bool scan_bvh(SceneRef sc, int *stack, const Path<R> &P, R a, 
             t_split = bvh_grid_entry(sc, r, (float)P.ox, (float)P.oy, (float)P.oz, (float)P.dx, (float)P.dy, (float)P.dz, best(), e_rel, cur, t_from, first);
             RTMI_PH(PH_GRID)
         }
-        bvh_traverse<COUNT, SLICE>(sc, r, cur, min_lanes, leaf, best, cnt);
+        bvh_traverse<COUNT, SLICE, ANY>(sc, r, cur, min_lanes, leaf, best, cnt);
+        if (ANY && best_i >= 0) return true; // (the ordered walk ends at the first piece that holds a hit, wherever in the piece it lies)
         if (SLICE && cur.node != RTMI_BVH_EMPTY) { // suspended
             int w0, w1;
             best_to_words<R>(best_t, w0, w1);
@@ -1491,7 +1510,10 @@ __device__ inline bool scan_bvh(SceneRef sc, int *stack, const Path<R> &P, R a, 
     }
     // 3. a ray outside the shutter interval: the MovingSphere boxes were built for [t_lo, t_hi], so test every moving sphere exactly
     if (!r.time_ok)
-        for (int k = 0; k < sc.n_moving_all; ++k) exact_prim_test_lane<R>(exact12, ~(sc.moving_all[k] | 0x40000000), P, qa, tmin, behind_ok, best_t, best_i);
+        for (int k = 0; k < sc.n_moving_all; ++k) {
+            exact_prim_test_lane<R>(exact12, ~(sc.moving_all[k] | 0x40000000), P, qa, tmin, behind_ok, best_t, best_i);
+            if (ANY && best_i >= 0) break;
+        }
     return true;
 }
 
@@ -1735,6 +1757,8 @@ __device__ inline SmallRec small_rec(SceneRef sc, int i) {
     r.g4 = ext_ld<true>(sc.exact12, gi + 4);
     return r;
 }
+// ANY (the any-hit queries): the scan stops once every lane of the wave holds a hit (the indices are wave-uniform); see scan_bvh_ext.
+template <bool ANY = false>
 __device__ inline void scan_small_ext(SceneRef sc, const Path<double> &P, double tmin, ExtHit &H, int lo = 0, int hi = 0x7fffffff) {
     const int n = min(sc.n_all, hi);
     int cf = -1, cc = -1; // the chain the cached local ray belongs to
@@ -1754,6 +1778,7 @@ __device__ inline void scan_small_ext(SceneRef sc, const Path<double> &P, double
         const SmallRec rec = small_rec(sc, i); // info and the first five geometry slots (a rectangle's whole record) requested together: one wait per primitive, not two
         const int4 info = rec.info;
 #endif
+        if (ANY && __all(H.any())) break;
         if (info.x == RTMI_PRIM_MEDIUM) continue;
         if (info.z != cf || info.w != cc) { // (wave-uniform)
             cf = info.z; cc = info.w;
@@ -1960,12 +1985,14 @@ __device__ inline void ext_leaf_test(SceneRef sc, int idx, bool box, const Path<
 
 // the flat scan (FP32 cull + exact test) over all primitives
 // [lo, hi): only the primitives of this index range (RTMI_MEDIA_HITLIST scans the list in pieces, between its media); default: all
+template <bool ANY = false>
 __device__ inline void scan_all_cull_ext(SceneRef sc, const Path<double> &P, double a, double tmin, ExtHit &H, int lo = 0, int hi = 0x7fffffff) {
     const int n = min(sc.n_all, hi);
     if (n <= 0) return;
     const int last = n - 1;
     const CullRay c = make_cull_ray(P, a, sc.cull_t_lo, sc.cull_t_hi);
     for (int g = lo & ~3; g < n; g += 4) {
+        if (ANY && __all(H.any())) break; // (any-hit queries: wave-uniform, as scan_small_ext)
         const CullGroup G = load_cull_group(sc.cull20, g >> 2);
         const float d0 = cull_disc(G, 0, c), d1 = cull_disc(G, 1, c), d2 = cull_disc(G, 2, c), d3 = cull_disc(G, 3, c);
         if (fmaxf(fmaxf(d0, d1), fmaxf(d2, d3)) >= 0.0f) {
@@ -1982,7 +2009,10 @@ __device__ inline float ext_best_hi(const ExtHit &H) { return float_above(H.t); 
 // Time-sliced like scan_bvh (susp: RTMI_BVH_SUSPEND_WORDS_EXT columns behind the stack; returns false when the lane's traversal was
 // suspended): the mixed-kind scenes need it most -- make-final's descent trips ran at 12.7 of 64 lanes, 66 % of them below 8.
 #define RTMI_BVH_SUSPEND_WORDS_EXT 7 // node, tos, top, H.t (2 words), H.F, H.W   (no hit yet <=> H.F = 0x7fffffff)
-template <bool SLICE = false, bool COUNT = false>
+// ANY (the any-hit queries; never with SLICE): the lane returns after the first primitive that sets H.  Until then H.t is the caller's t-max, so every
+// test before it ran against the initial interval -- rectangles and triangles with t <= t-max (hitable.clj:278, 564), spheres with t < t-max (:195),
+// exactly the first comparison each kind makes in the closest-hit search, which therefore finds a hit iff one of these tests accepts.
+template <bool SLICE = false, bool COUNT = false, bool ANY = false>
 __device__ inline bool scan_bvh_ext(SceneRef sc, int *stack, const Path<double> &P, double a, double tmin, ExtHit &H, int *susp = nullptr, bool resume = false,
                                     int min_lanes = 0, unsigned *cnt = nullptr, int lo = 0, int hi = 0x7fffffff) {
     const BvhRay r = make_bvh_ray(sc, P, a, tmin);
@@ -1995,10 +2025,13 @@ __device__ inline bool scan_bvh_ext(SceneRef sc, int *stack, const Path<double> 
         H.t = __hiloint2double(sw[4 * stride], sw[3 * stride]);
         H.F = sw[5 * stride]; H.W = sw[6 * stride];
     } else {
-        if (!r.ok) { if (COUNT) cnt[1] += (unsigned)sc.n_all; scan_all_cull_ext(sc, P, a, tmin, H, lo, hi); return true; }
+        if (!r.ok) { if (COUNT) cnt[1] += (unsigned)sc.n_all; scan_all_cull_ext<ANY>(sc, P, a, tmin, H, lo, hi); return true; }
         RTMI_PH(PH_BVH_SETUP)
         if (COUNT) cnt[1] += (unsigned)sc.n_big;
-        for (int k = 0; k < sc.n_big; ++k) if (sc.big_idx[k] >= lo && sc.big_idx[k] < hi) ext_prim_test<true>(sc, sc.big_idx[k], P, tmin, H);
+        for (int k = 0; k < sc.n_big; ++k) {
+            if (sc.big_idx[k] >= lo && sc.big_idx[k] < hi) ext_prim_test<true>(sc, sc.big_idx[k], P, tmin, H);
+            if (ANY && H.any()) return true;
+        }
         cur = bvh_cursor_at_root(sc, stack);
         if (sc.n_mloc > 0 && !sc.media_seq && lo == 0 && H.t < 1e30) { // (wave-uniform) a bounded segment: does it lie inside a medium's neighbourhood?
             const float ox = (float)P.ox, oy = (float)P.oy, oz = (float)P.oz, tb = (float)H.t;
@@ -2024,9 +2057,11 @@ __device__ inline bool scan_bvh_ext(SceneRef sc, int *stack, const Path<double> 
             else ext_prim_test<false>(sc, idx, P, tmin, H);
 #endif
         }
+        return H.any();
     };
     auto best = [&]() { return ext_best_hi(H); };
-    bvh_traverse<COUNT, SLICE>(sc, r, cur, min_lanes, leaf, best, cnt);
+    bvh_traverse<COUNT, SLICE, ANY>(sc, r, cur, min_lanes, leaf, best, cnt);
+    if (ANY && H.any()) return true;
     if (SLICE && cur.node != RTMI_BVH_EMPTY) { // suspended
         sw[0] = cur.node; sw[stride] = cur.tos;
         sw[2 * stride] = (int)(reinterpret_cast<char *>(cur.top) - reinterpret_cast<char *>(stack));
@@ -2036,7 +2071,10 @@ __device__ inline bool scan_bvh_ext(SceneRef sc, int *stack, const Path<double> 
     }
     if (!r.time_ok) { // e.g. after Isotropic.scatter, which sets the ray's time to the hit's t (shader.clj:136)
         if (COUNT) cnt[1] += (unsigned)sc.n_moving_all;
-        for (int k = 0; k < sc.n_moving_all; ++k) if (sc.moving_all[k] >= lo && sc.moving_all[k] < hi) ext_prim_test<true>(sc, sc.moving_all[k], P, tmin, H);
+        for (int k = 0; k < sc.n_moving_all; ++k) {
+            if (sc.moving_all[k] >= lo && sc.moving_all[k] < hi) ext_prim_test<true>(sc, sc.moving_all[k], P, tmin, H);
+            if (ANY && H.any()) break;
+        }
     }
     return true;
 }
