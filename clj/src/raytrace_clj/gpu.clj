@@ -605,6 +605,84 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn occlusion-hemisphere
+  "n-dirs cosine-weighted occlusion rays from each of n-points hit records, generated on the device (rtmi_occlusion_hemisphere): `hits` holds
+  12 doubles per point as query-hits returns them, `view` the 7 doubles of the ray that found each point (its direction picks the side of the
+  surface, its time is the new rays'); `view` is required here (7 * n-points doubles -- the C entry's NULL form is not bound).  Direction k of point g draws from the stream keyed (sample-key seed g (+ first k)).  Returns
+  {:occluded byte-array [n], :count int-array [n-points], :out-rays double-array [n][7] (zeros where a point yields no ray), :rays, :rays-occluded}."
+  [scene hits view n-points n-dirs & {:keys [first seed t-min t-max device precision]
+                                      :or {first 0 seed 0x5EED0002 t-min 0.001 t-max 3.4028234663852886e38 device 0 precision 0}}]
+  (let [f     (flatten-scene scene)
+        ctx   (PointerByReference.)
+        n     (* n-points n-dirs)
+        hs    (double-array hits)
+        vw    (double-array view)
+        flags (byte-array n)
+        per   (int-array n-points)
+        out   (double-array (* 7 n))
+        cnt   (long-array 2)]
+    (when-not (and (= (alength hs) (* 12 n-points)) (= (alength vw) (* 7 n-points)))
+      (throw (IllegalArgumentException. "hits must hold 12 and view 7 doubles per point")))
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_occlusion_hemisphere" scn (int precision) (int n-points) hs vw (int n-dirs) (int first) (long seed) (double 0.0)
+                           (double t-min) (double t-max) flags per out cnt))
+          {:occluded flags :count per :out-rays out :rays (aget cnt 0) :rays-occluded (aget cnt 1)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
+(defn occlusion-targets
+  "One occlusion ray from each of n-points hit records towards each of n-targets points, generated on the device (rtmi_occlusion_targets):
+  `targets` holds 3 doubles per target, `hits` and `view` as for occlusion-hemisphere (of `view` only the time is read; required as there).  The direction is
+  target - point, so (t-min, t-max) = (0.001, 0.999) asks \"up to the light\".  Returns what occlusion-hemisphere returns, one group per point."
+  [scene hits view n-points targets n-targets & {:keys [t-min t-max device precision] :or {t-min 0.001 t-max 0.999 device 0 precision 0}}]
+  (let [f     (flatten-scene scene)
+        ctx   (PointerByReference.)
+        n     (* n-points n-targets)
+        hs    (double-array hits)
+        vw    (double-array view)
+        tg    (double-array targets)
+        flags (byte-array n)
+        per   (int-array n-points)
+        out   (double-array (* 7 n))
+        cnt   (long-array 2)]
+    (when-not (and (= (alength hs) (* 12 n-points)) (= (alength vw) (* 7 n-points)) (= (alength tg) (* 3 n-targets)))
+      (throw (IllegalArgumentException. "hits must hold 12 and view 7 doubles per point, targets 3 per target")))
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_occlusion_targets" scn (int precision) (int n-points) hs vw (int n-targets) tg (double 0.0) (double t-min)
+                           (double t-max) flags per out cnt))
+          {:occluded flags :count per :out-rays out :rays (aget cnt 0) :rays-occluded (aget cnt 1)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
+(defn ambient-occlusion
+  "Ambient occlusion of the nx x ny view of scene {:camera :world}, the whole pass on the device (rtmi_ambient_occlusion): the first hits of the
+  pixel-centre rays, n-dirs cosine-weighted rays per hit on the viewer's side with t-range (0.001, radius), visibility = 1 - occluded / n-dirs
+  and 1 where the primary ray missed.  Returns {:visibility double-array [ny * nx] (row 0 = top), :count int-array, :hits double-array
+  [ny * nx][12], :rays, :rays-occluded}; `first` offsets the directions, so a caller accumulates :count over calls."
+  [scene nx ny n-dirs radius & {:keys [first seed device precision] :or {first 0 seed 0x5EED0002 device 0 precision 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        n    (* nx ny)
+        vis  (double-array n)
+        per  (int-array n)
+        hits (double-array (* 12 n))
+        cnt  (long-array 2)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_ambient_occlusion" scn (int precision) (int nx) (int ny) (int n-dirs) (int first) (double radius) (long seed)
+                           vis per hits cnt))
+          {:visibility vis :count per :hits hits :rays (aget cnt 0) :rays-occluded (aget cnt 1)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn pick
   "What lies under pixel (column i, row j from the top) of an nx x ny view of scene {:camera :world}: nil, or {:prim :material :t :p :normal
   :uv} of the closest hit of the ray from the camera's origin (a thin lens: its lens centre) through the pixel's centre -- u = (i + 1/2) / nx,

@@ -628,6 +628,70 @@ int rtmi_query_occluded_device(rtmi_scene *scene, int32_t precision, int32_t n_g
                                double t_min, double t_max, const void *d_keys, uint32_t ctr0,
                                void *d_out_occluded, void *d_out_count, void *d_out_counters, void *stream);
 
+/* ---- occlusion rays generated on the device: ambient occlusion, shadow rays, lines of sight from points the device already holds ----
+ * The points are rtmi_query_hits' records: hits = [n_points][RTMI_HIT_REC], rec = one of them.  Item m = g * n_dirs + k (g * n_targets + k) is ray k of
+ * point g; the any-hit query of rtmi_query_occluded runs over the n_points * n_dirs (n_targets) items with one group per point, but a lane builds its ray
+ * in registers from its point's record instead of reading seven doubles.  Every ray is built in FP64 whatever the precision and is then converted as a
+ * ray read from memory is, so RTMI_F32 differs from RTMI_F64 exactly where it does in rtmi_query_occluded.  The rays' streams (what a ConstantMedium
+ * draws from) are keyed 0, as with keys == NULL there.
+ *   view (may be NULL): [n_points][7] doubles, the ray that found each point (what rtmi_query_hits was given).
+ *   out_occluded (may be NULL): [n] bytes; out_count (may be NULL): [n_points] int32, zeroed by the call; out_counters (may be NULL): {rays generated,
+ *     occluded rays}.  A point that yields no ray (below) traces nothing: its flags and its count are 0 and it adds nothing to the counters.
+ *   out_rays (may be NULL): [n][7] doubles, the rays as generated; the rows of a point that yields no ray are zeros.
+ *
+ * THE HEMISPHERE RULE (rtmi_occlusion_hemisphere): n_dirs cosine-weighted directions about each point's normal, by Malley's method driven by the
+ * reference's rand-in-unit-disk rejection loop (util.clj:32-41) -- built from + - * / sqrt alone, so a host restates it bit for bit (no cos, no sin).
+ * Every product, sum and quotient below is one IEEE double operation in the order written; dot3(a, b) = (ax*bx + ay*by) + az*bz.
+ *   1. p = rec[3:6], n = rec[6:9].  The point yields no ray if rec[0] == 0, if any of the six values is not finite, or if dot3(n, n) is not > 0.
+ *   2. Side: with a view array, w = view[g][3:6]; if dot3(n, w) > 0, negate each component of n.  Without one, n stays as it is.  The ray's time is
+ *      view[g][6], or the call's `time` argument without a view array.
+ *   3. nn = n / sqrt(dot3(n, n)), component by component.
+ *   4. Tangent: if |nn.x| < 0.5 then t = (+0.0, -nn.z, nn.y), else t = (nn.z, +0.0, -nn.x).  Then t = t / sqrt(dot3(t, t)), component by component.
+ *   5. b = (nn.y*t.z - nn.z*t.y, nn.z*t.x - nn.x*t.z, nn.x*t.y - nn.y*t.x).
+ *   6. Disk point: the stream is keyed rtmi_sample_key(seed, g, first + k) and starts at draw 0.  Candidate c is (x, y) = (2*u(2c) - 1, 2*u(2c+1) - 1),
+ *      u(d) = the FP64 uniform of draw d (the top 53 bits of the draw, times 2^-53).  Take the first candidate for which (x*x + y*y) + 0*0 >= 1 is false.
+ *   7. z = sqrt(1 - (x*x + y*y)).  Direction = (x*t + y*b) + z*nn per component.  Origin = p.
+ *   Any split of a point's directions over `first` therefore gives the rays of one call.
+ * THE TARGETS RULE (rtmi_occlusion_targets): origin p, direction targets[k] - p per component (targets = [n_targets][3] doubles), time as in step 2.
+ *   "No ray" is as in step 1, but the normal is not read.  The t-range is the call's scalars: "up to the light" is (0.001, 1 - 0.001).
+ * rtmi_ambient_occlusion: the whole pass for an nx x ny view of the scene's camera on one stream, without a host round trip and without a buffer of
+ *   nx * ny * n_dirs rays.  (a) the closest hits (t-range (0.001, FLT_MAX)) of the pixel-centre rays, pixel m = j * nx + i row-major from the top (j = 0):
+ *   origin cam[0:3], direction ((lleft + horiz*u) + vert*v) + (-origin) per component with u = (i + 1/2) / nx, v = ((ny - 1 - j) + 1/2) / ny, time 0 for
+ *   the pinhole camera and t0 for the thin lens -- built on the device from the camera the scene holds there, so the call follows
+ *   rtmi_scene_set_camera_stream in stream order; (b) the hemisphere rule over those records with the pixel-centre rays as the view array, directions
+ *   [first, first + n_dirs), t-range (0.001, radius); (c) out_visibility[m] = 1 - count[m] / n_dirs (doubles), and 1 where the primary ray missed.
+ *   out_visibility: [ny * nx] doubles; out_count (may be NULL): [ny * nx] int32 occluded directions of this call -- with `first` a caller accumulates
+ *   directions over calls; out_hits (may be NULL): [ny * nx][RTMI_HIT_REC], the records of (a); out_counters (may be NULL): those of (b).
+ * n_points * n_dirs, n_points * n_targets, nx * ny * n_dirs <= 2^31 - 64 (else RTMI_E_ARG); n_points == 0 (nx * ny == 0) succeeds and launches nothing.
+ * RTMI_F32: sphere worlds only (RTMI_E_UNSUPPORTED), as the queries.
+ * Errors, in this order: n_points < 0 (nx, ny < 0), n_dirs / n_targets <= 0, first < 0, radius not > 0, or an overflow: RTMI_E_ARG; hits, targets or
+ * out_visibility NULL with work to do: RTMI_E_ARG; a bad handle: RTMI_E_STATE; a bad precision: RTMI_E_ARG.
+ * Options, frames, revision and RTMI_FLAG_TIMING: as the queries (rtmi_ambient_occlusion's trace interval is its two query launches). */
+/* host buffers; synchronous */
+int rtmi_occlusion_hemisphere(rtmi_scene *scene, int32_t precision, int32_t n_points, const double *hits, const double *view, int32_t n_dirs, int32_t first,
+                              uint64_t seed, double time, double t_min, double t_max,
+                              uint8_t *out_occluded, int32_t *out_count, double *out_rays, uint64_t *out_counters);
+/* every pointer a device pointer; asynchronous on `stream` with rtmi_render_device's stream semantics.  Allocates nothing once the context's
+ * workspace has grown to size. */
+int rtmi_occlusion_hemisphere_device(rtmi_scene *scene, int32_t precision, int32_t n_points, const void *d_hits, const void *d_view, int32_t n_dirs,
+                                     int32_t first, uint64_t seed, double time, double t_min, double t_max,
+                                     void *d_out_occluded, void *d_out_count, void *d_out_rays, void *d_out_counters, void *stream);
+/* host buffers; synchronous */
+int rtmi_occlusion_targets(rtmi_scene *scene, int32_t precision, int32_t n_points, const double *hits, const double *view, int32_t n_targets,
+                           const double *targets, double time, double t_min, double t_max,
+                           uint8_t *out_occluded, int32_t *out_count, double *out_rays, uint64_t *out_counters);
+/* device buffers, as rtmi_occlusion_hemisphere_device */
+int rtmi_occlusion_targets_device(rtmi_scene *scene, int32_t precision, int32_t n_points, const void *d_hits, const void *d_view, int32_t n_targets,
+                                  const void *d_targets, double time, double t_min, double t_max,
+                                  void *d_out_occluded, void *d_out_count, void *d_out_rays, void *d_out_counters, void *stream);
+/* host buffers; synchronous */
+int rtmi_ambient_occlusion(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t n_dirs, int32_t first, double radius, uint64_t seed,
+                           double *out_visibility, int32_t *out_count, double *out_hits, uint64_t *out_counters);
+/* every pointer a device pointer; asynchronous on `stream`.  Allocates nothing once the context's workspace has grown to size; without d_out_hits /
+ * d_out_count the records and the counts live in that workspace. */
+int rtmi_ambient_occlusion_device(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t n_dirs, int32_t first, double radius, uint64_t seed,
+                                  void *d_out_visibility, void *d_out_count, void *d_out_hits, void *d_out_counters, void *stream);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

@@ -39,6 +39,8 @@ SYMBOLS = [
     "rtmi_render_rays", "rtmi_render_rays_device",
     "rtmi_test_stage_layout",
     "rtmi_query_hits", "rtmi_query_hits_device", "rtmi_query_occluded", "rtmi_query_occluded_device",
+    "rtmi_occlusion_hemisphere", "rtmi_occlusion_hemisphere_device", "rtmi_occlusion_targets", "rtmi_occlusion_targets_device",
+    "rtmi_ambient_occlusion", "rtmi_ambient_occlusion_device",
 ]
 
 F64, F32 = 0, 1
@@ -161,6 +163,12 @@ def lib():
     L.rtmi_query_hits_device.argtypes = [vp, i32, i32, vp, vp, dbl, dbl, vp, C.c_uint32, vp, vp, vp]
     L.rtmi_query_occluded.argtypes = [vp, i32, i32, i32, vp, vp, dbl, dbl, vp, C.c_uint32, vp, vp, vp]
     L.rtmi_query_occluded_device.argtypes = [vp, i32, i32, i32, vp, vp, dbl, dbl, vp, C.c_uint32, vp, vp, vp, vp]
+    L.rtmi_occlusion_hemisphere.argtypes = [vp, i32, i32, vp, vp, i32, i32, u64, dbl, dbl, dbl, vp, vp, vp, vp]
+    L.rtmi_occlusion_hemisphere_device.argtypes = [vp, i32, i32, vp, vp, i32, i32, u64, dbl, dbl, dbl, vp, vp, vp, vp, vp]
+    L.rtmi_occlusion_targets.argtypes = [vp, i32, i32, vp, vp, i32, vp, dbl, dbl, dbl, vp, vp, vp, vp]
+    L.rtmi_occlusion_targets_device.argtypes = [vp, i32, i32, vp, vp, i32, vp, dbl, dbl, dbl, vp, vp, vp, vp, vp]
+    L.rtmi_ambient_occlusion.argtypes = [vp, i32, i32, i32, i32, i32, dbl, u64, vp, vp, vp, vp]
+    L.rtmi_ambient_occlusion_device.argtypes = [vp, i32, i32, i32, i32, i32, dbl, u64, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

@@ -199,3 +199,41 @@ def hemisphere_rays(points, normals, n_dirs, first=0, seed=0x5EED0002, time=0.0)
     b = np.cross(n, t)
     direction = x[:, None] * t[g] + y[:, None] * b[g] + z[:, None] * n[g]
     return _rays(points[g], direction, float(time))[0]
+
+
+def hemisphere_rays_disk(points, normals, n_dirs, first=0, seed=0x5EED0002, time=0.0):
+    """hemisphere_rays with the sampler the device runs (include/rtmi.h, "the hemisphere rule", steps 3 - 7): the same signature and row order, the
+    same cosine weighting by Malley's method, but the uniform point of the unit disk comes from the reference's rand-in-unit-disk rejection loop
+    (util.clj:32-41) instead of a radius and an angle -- no cos, no sin, only + - * / sqrt, every one a single IEEE operation in the header's
+    order, so rtmi_occlusion_hemisphere's out_rays equal these rows bit for bit.  Ray r of point g takes candidates (draws 2c, 2c + 1 as 2 u - 1)
+    of the stream keyed sample_key(seed, g, first + r) until one lies inside the disk.  -> rays [n * n_dirs, 7] float64, every ray carrying `time`."""
+    from . import util
+    points, normals = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(normals, np.float64).reshape(-1, 3)
+    n_dirs, first = int(n_dirs), int(first)
+    if len(points) != len(normals) or n_dirs <= 0 or first < 0:
+        raise ValueError("points and normals must pair up, n_dirs > 0 and first >= 0")
+    g, r = (a.ravel() for a in np.meshgrid(np.arange(len(points)), np.arange(first, first + n_dirs), indexing="ij"))
+    keys = util.sample_keys(seed, g, r)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        nx, ny, nz = normals[:, 0], normals[:, 1], normals[:, 2]
+        length = np.sqrt((nx * nx + ny * ny) + nz * nz)                               # 3. nn = n / sqrt(dot3(n, n))
+        nx, ny, nz = nx / length, ny / length, nz / length
+        small = np.abs(nx) < 0.5                                                        # 4. the tangent
+        zero = np.zeros(len(nx))
+        tx, ty, tz = np.where(small, zero, nz), np.where(small, -nz, zero), np.where(small, ny, -nx)
+        tl = np.sqrt((tx * tx + ty * ty) + tz * tz)
+        tx, ty, tz = tx / tl, ty / tl, tz / tl
+        bx, by, bz = ny * tz - nz * ty, nz * tx - nx * tz, nx * ty - ny * tx            # 5. b = nn x t
+        x, y = np.zeros(len(keys)), np.zeros(len(keys))                                 # 6. the first candidate inside the disk
+        pending, c = np.arange(len(keys)), 0
+        while len(pending):
+            cx = 2.0 * util.draw_uniforms(keys[pending], 2 * c) - 1.0
+            cy = 2.0 * util.draw_uniforms(keys[pending], 2 * c + 1) - 1.0
+            inside = ~(((cx * cx + cy * cy) + 0.0 * 0.0) >= 1.0)
+            x[pending[inside]], y[pending[inside]] = cx[inside], cy[inside]
+            pending, c = pending[~inside], c + 1
+        z = np.sqrt(1.0 - (x * x + y * y))                                              # 7. lifted onto the hemisphere
+        dx = (x * tx[g] + y * bx[g]) + z * nx[g]
+        dy = (x * ty[g] + y * by[g]) + z * ny[g]
+        dz = (x * tz[g] + y * bz[g]) + z * nz[g]
+    return _rays(points[g], np.stack([dx, dy, dz], axis=1), float(time))[0]

@@ -761,6 +761,76 @@ class DeviceScene:
         vis[~hit] = 1.0
         return vis.reshape(ny, nx)
 
+    # ---- occlusion rays generated on the device (rtmi_occlusion_hemisphere*, rtmi_occlusion_targets*, rtmi_ambient_occlusion*) --------------------
+    @staticmethod
+    def _occlusion_inputs(hits, view):
+        hits = np.ascontiguousarray(hits, np.float64).reshape(-1, _ffi.HIT_REC)
+        if view is not None:
+            view = np.ascontiguousarray(view, np.float64).reshape(-1, 7)
+            if len(view) != len(hits):
+                raise ValueError("%d view rays for %d points" % (len(view), len(hits)))
+        return hits, view
+
+    def occlusion_hemisphere(self, hits, n_dirs, view=None, first=0, seed=RENDER_SEED, time=0.0, t_min=T_MIN, t_max=T_MAX, precision="f64",
+                             return_rays=False):
+        """n_dirs cosine-weighted rays from every point of hits [n, HIT_REC] (query_hits' records), generated on the device by the hemisphere rule of
+        include/rtmi.h (camera.hemisphere_rays_disk restates it) and put through the any-hit search.  view [n, 7]: the rays that found the points
+        -- the new rays leave on their side of the surface and carry their time; None: the normal's side and `time`.  A missed record or a
+        non-finite one yields no ray.  -> (flags uint8 [n * n_dirs], counts int32 [n], counters {rays generated, occluded rays}), and the rays
+        [n * n_dirs, 7] with return_rays."""
+        hits, view = self._occlusion_inputs(hits, view)
+        n, m = len(hits), len(hits) * int(n_dirs)
+        flags, counts, cnt = np.zeros(max(m, 0), np.uint8), np.zeros(n, np.int32), np.zeros(2, np.uint64)
+        rays = np.zeros((max(m, 0), 7), np.float64) if return_rays else None
+        check(_ffi.lib().rtmi_occlusion_hemisphere(self.handle, _PRECISION[precision], n, ptr(hits), ptr(view), int(n_dirs), int(first), int(seed),
+                                                   float(time), float(t_min), float(t_max), ptr(flags), ptr(counts), ptr(rays), ptr(cnt)))
+        return (flags, counts, cnt, rays) if return_rays else (flags, counts, cnt)
+
+    def occlusion_hemisphere_device(self, n_points, hits, n_dirs, view=None, first=0, seed=RENDER_SEED, time=0.0, t_min=T_MIN, t_max=T_MAX,
+                                    out_occluded=None, out_count=None, out_rays=None, out_counters=None, precision="f64", stream=None):
+        """occlusion_hemisphere on HBM-resident buffers (hits as query_hits_device wrote them; every output may be None); asynchronous,
+        render_device's stream semantics"""
+        check(_ffi.lib().rtmi_occlusion_hemisphere_device(self.handle, _PRECISION[precision], int(n_points), ptr(hits), ptr(view), int(n_dirs), int(first),
+                                                          int(seed), float(time), float(t_min), float(t_max), ptr(out_occluded), ptr(out_count),
+                                                          ptr(out_rays), ptr(out_counters), ptr(stream)))
+
+    def occlusion_targets(self, hits, targets, view=None, time=0.0, t_min=T_MIN, t_max=1.0 - T_MIN, precision="f64", return_rays=False):
+        """One ray from every point of hits [n, HIT_REC] towards each of targets [k, 3] (lights, observers), generated on the device: origin the point,
+        direction target - point, so the default range (0.001, 1 - 0.001) asks "up to the target".  view [n, 7]: only its times are read.
+        -> (flags uint8 [n * k], counts int32 [n], counters), and the rays with return_rays."""
+        hits, view = self._occlusion_inputs(hits, view)
+        targets = np.ascontiguousarray(targets, np.float64).reshape(-1, 3)
+        n, k = len(hits), len(targets)
+        flags, counts, cnt = np.zeros(n * k, np.uint8), np.zeros(n, np.int32), np.zeros(2, np.uint64)
+        rays = np.zeros((n * k, 7), np.float64) if return_rays else None
+        check(_ffi.lib().rtmi_occlusion_targets(self.handle, _PRECISION[precision], n, ptr(hits), ptr(view), k, ptr(targets), float(time), float(t_min),
+                                                float(t_max), ptr(flags), ptr(counts), ptr(rays), ptr(cnt)))
+        return (flags, counts, cnt, rays) if return_rays else (flags, counts, cnt)
+
+    def occlusion_targets_device(self, n_points, hits, n_targets, targets, view=None, time=0.0, t_min=T_MIN, t_max=1.0 - T_MIN, out_occluded=None,
+                                 out_count=None, out_rays=None, out_counters=None, precision="f64", stream=None):
+        """occlusion_targets on HBM-resident buffers; asynchronous, render_device's stream semantics"""
+        check(_ffi.lib().rtmi_occlusion_targets_device(self.handle, _PRECISION[precision], int(n_points), ptr(hits), ptr(view), int(n_targets), ptr(targets),
+                                                       float(time), float(t_min), float(t_max), ptr(out_occluded), ptr(out_count), ptr(out_rays),
+                                                       ptr(out_counters), ptr(stream)))
+
+    def ambient_occlusion_device(self, nx, ny, n_dirs, radius, seed=RENDER_SEED, first=0, precision="f64", out_visibility=None, out_count=None,
+                                 out_hits=None, out_counters=None, stream=None):
+        """Ambient occlusion of the view, the whole pass on the device (rtmi_ambient_occlusion*): first hits of the pixel-centre rays, n_dirs rays per
+        hit by the hemisphere rule on the viewer's side, t-range (0.001, radius), visibility = 1 - occluded / n_dirs and 1 where the primary ray
+        missed -- no ray is downloaded, built on the host or uploaded.  The same estimate as ambient_occlusion from other directions (the disk
+        sampler's, not the angle's).  Without out_visibility: the host form -> [ny, nx] float64, row 0 = top.  With it (HBM-resident buffers;
+        out_count int32 [ny * nx], out_hits [ny * nx, HIT_REC] and out_counters may be None): asynchronous on `stream`, returns None.  first:
+        directions [first, first + n_dirs) -- a caller accumulates out_count over calls."""
+        if out_visibility is None:
+            vis = np.zeros((max(ny, 0), max(nx, 0)), np.float64)
+            check(_ffi.lib().rtmi_ambient_occlusion(self.handle, _PRECISION[precision], int(nx), int(ny), int(n_dirs), int(first), float(radius), int(seed),
+                                                    ptr(vis), ptr(out_count), ptr(out_hits), ptr(out_counters)))
+            return vis
+        check(_ffi.lib().rtmi_ambient_occlusion_device(self.handle, _PRECISION[precision], int(nx), int(ny), int(n_dirs), int(first), float(radius), int(seed),
+                                                       ptr(out_visibility), ptr(out_count), ptr(out_hits), ptr(out_counters), ptr(stream)))
+        return None
+
     # ---- probes ------------------------------------------------------------------------------------------
     def probe_hit(self, rays, t_min=T_MIN, t_max=T_MAX, precision="f64"):
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
@@ -1287,9 +1357,9 @@ def _render_orbit(sc, name, nx, ny, nr, views, dn_iterations, dn_samples, tstart
     return 0
 
 
-def _ao_flags(argv):
+def _ao_flags(argv, flag="--ao"):
     """-> (the other arguments, (directions, radius) or None): --ao N [RADIUS] (a number right after N, or --ao=N, is taken; default radius 1.0),
-    checked here, before any device work"""
+    checked here, before any device work.  flag: the same for --ao-device."""
     import re
     rest, ao = [], None
     number = r"[+]?([0-9]+\.?[0-9]*|\.[0-9]+)([eE][+-]?[0-9]+)?"
@@ -1298,26 +1368,26 @@ def _ao_flags(argv):
         a = argv[i]
         key, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") else (a, None)
         i += 1
-        if key != "--ao":
+        if key != flag:
             rest.append(a)
             continue
         if val is None:
             if i >= len(argv):
-                raise SystemExit("--ao needs a number of directions")
+                raise SystemExit("%s needs a number of directions" % flag)
             val = argv[i]
             i += 1
         try:
             n_dirs = int(val)
         except ValueError:
-            raise SystemExit("--ao %r is not a number of directions" % val)
+            raise SystemExit("%s %r is not a number of directions" % (flag, val))
         if n_dirs <= 0:
-            raise SystemExit("--ao takes a positive number of directions (got %d)" % n_dirs)
+            raise SystemExit("%s takes a positive number of directions (got %d)" % (flag, n_dirs))
         radius = 1.0
         if i < len(argv) and re.fullmatch(number, argv[i]):
             radius = float(argv[i])
             i += 1
         if not radius > 0.0:
-            raise SystemExit("--ao takes a positive radius (got %g)" % radius)
+            raise SystemExit("%s takes a positive radius (got %g)" % (flag, radius))
         ao = (n_dirs, radius)
     return rest, ao
 
@@ -1388,10 +1458,16 @@ def main(argv=None):
     --panorama renders the full sphere around the scene's camera position as an equirectangular image of 2 ny x ny pixels (nx is ignored): rays
     from camera.panorama_rays through DeviceScene.render_with, ns samples per pixel in chunks of 16.  It does not combine with the other modes.
     --ao N [RADIUS] also writes the view's ambient occlusion (DeviceScene.ambient_occlusion: N cosine-weighted any-hit rays of length RADIUS, default
-    1.0, from the first hit under every pixel centre) as a grey image, name.ao.ext, beside the frame.  It does not combine with --orbit or --panorama."""
+    1.0, from the first hit under every pixel centre) as a grey image, name.ao.ext, beside the frame.  It does not combine with --orbit or --panorama.
+    --ao-device N [RADIUS] writes the same kind of image through DeviceScene.ambient_occlusion_device: the rays are generated on the device (the disk
+    sampler's directions, not --ao's: the same estimate from other rays).  It takes the place of --ao."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
     argv, ao = _ao_flags(argv)
+    argv, ao_device = _ao_flags(argv, "--ao-device")
+    if ao is not None and ao_device is not None:
+        raise SystemExit("--ao and --ao-device write the same file: give one of them")
+    ao_on_device, ao = ao_device is not None, ao_device if ao_device is not None else ao
     panorama = "--panorama" in argv
     argv = [x for x in argv if x != "--panorama"]
     argv, orbit_views = _orbit_flags(argv)
@@ -1501,7 +1577,7 @@ def main(argv=None):
     if ao is not None:
         ds = DeviceScene(sc)
         try:
-            vis = ds.ambient_occlusion(nx, ny, ao[0], ao[1])
+            vis = ds.ambient_occlusion_device(nx, ny, ao[0], ao[1]) if ao_on_device else ds.ambient_occlusion(nx, ny, ao[0], ao[1])
         finally:
             ds.close()
         grey = np.floor(255.0 * vis + 0.5).astype(np.uint8)

@@ -1332,10 +1332,82 @@ struct QueryParams {
     int *count;            // ANY = true: [ceil(total_items / group)], zeroed before the launch, or null
     u64 *counters;         // [0] += rays, [1] += rays that hit; zeroed before the launch
     u64 *trav;             // COUNT: [0] += AABB tests, [1] += primitive tests
+    // generated sources (SRC != SRC_MEMORY; never read by the memory source): the points, what is known of the rays that found them, and the stream
+    const double *src_hits;    // [n_points][RTMI_HIT_REC]: rtmi_query_hits' records
+    const double *src_view;    // [n_points][7]: the ray that found each point (its direction picks the side, its time is the new ray's), or null
+    const double *src_targets; // SRC_TARGETS: [group][3]
+    double *out_rays;          // [total_items][7]: the rays as generated (FP64), zeros where a point yields none; or null
+    u64 src_seed;              // SRC_HEMISPHERE: the stream of direction k of point g is keyed sample_key(src_seed, g, src_first + k)
+    double src_time;           // the rays' time without a view array
+    unsigned src_first;
+    unsigned src_nx, src_ny;   // the view of SRC_PIXEL and of src_view_camera
+    unsigned src_view_camera;  // SRC_HEMISPHERE, no view array: point g is pixel g of the src_nx x src_ny view and its view ray that pixel's centre ray, built again
 };
 
-template <typename R, int VARIANT, bool EXT = false, int MSEQ = 0, bool ANY = false, bool COUNT = false>
+// Where a lane's ray comes from.  SRC_MEMORY: row m of qp.rays.  The others build it in registers, in FP64 whatever R is, by the rules of rtmi.h
+// (rtmi_occlusion_hemisphere, rtmi_occlusion_targets, rtmi_ambient_occlusion): every product, sum and quotient one IEEE operation in the header's order,
+// so that numpy restates them bit for bit; the seven doubles then go through load_ray as if they had been read.
+enum { SRC_MEMORY = 0, SRC_HEMISPHERE = 1, SRC_TARGETS = 2, SRC_PIXEL = 3 };
+
+// pixel m of an nx x ny view, row-major from the top, through its centre from the camera the scene holds on the device (DeviceScene.pixel_centre_rays)
+__device__ inline void pixel_centre_ray(SceneRef sc, unsigned m, unsigned nx, unsigned ny, double *q) {
+    unsigned long long cam_addr = (unsigned long long)(&sc.cam[0]);
+    asm volatile("" : "+s"(cam_addr)); // (as get_ray: the camera's loads stay at their use site)
+    const __attribute__((address_space(4))) double *c = (const __attribute__((address_space(4))) double *)cam_addr;
+    const unsigned j = m / nx, i = m - j * nx;
+    const double u = ((double)i + 0.5) / (double)nx, v = (((double)(ny - 1u) - (double)j) + 0.5) / (double)ny;
+    q[0] = c[0]; q[1] = c[1]; q[2] = c[2];
+    q[3] = ((c[3] + c[6] * u) + c[9] * v) + (-c[0]);
+    q[4] = ((c[4] + c[7] * u) + c[10] * v) + (-c[1]);
+    q[5] = ((c[5] + c[8] * u) + c[11] * v) + (-c[2]);
+    q[6] = sc.cam_kind == RTMI_CAM_PINHOLE ? 0.0 : c[22];
+}
+
+// The ray of item m of a generated source -> q[7]; false: its point yields none (q is zeros).  Every lane of the wave calls (the disk sampler is
+// cooperative); a lane past the end of the queue passes in_range = false and m = 0.
+template <int SRC> __device__ inline bool generate_ray(SceneRef sc, const QueryParams &qp, bool in_range, unsigned m, double *q) {
+    if (SRC == SRC_PIXEL) { pixel_centre_ray(sc, m, qp.src_nx, qp.src_ny, q); return in_range; }
+    const double big = __builtin_inf();
+    const unsigned g = m / qp.group, k = m - g * qp.group;
+    const double *rec = qp.src_hits + (size_t)g * RTMI_HIT_REC;
+    const double px = rec[3], py = rec[4], pz = rec[5];
+    bool ok = in_range && rec[0] != 0.0 && ::fabs(px) < big && ::fabs(py) < big && ::fabs(pz) < big; // finite: neither inf nor NaN
+    double time = qp.src_time, wx = 0.0, wy = 0.0, wz = 0.0;
+    bool sided = false;
+    if (qp.src_view) { const double *w = qp.src_view + (size_t)g * 7; wx = w[3]; wy = w[4]; wz = w[5]; time = w[6]; sided = true; }
+    else if (SRC == SRC_HEMISPHERE && qp.src_view_camera) { double w[7]; pixel_centre_ray(sc, g, qp.src_nx, qp.src_ny, w); wx = w[3]; wy = w[4]; wz = w[5]; time = w[6]; sided = true; }
+    double dx, dy, dz;
+    if (SRC == SRC_TARGETS) {
+        const double *tg = qp.src_targets + (size_t)k * 3;
+        dx = tg[0] - px; dy = tg[1] - py; dz = tg[2] - pz;
+    } else {
+        double nx = rec[6], ny = rec[7], nz = rec[8];
+        const double len2 = dot3(nx, ny, nz, nx, ny, nz);
+        ok = ok && ::fabs(nx) < big && ::fabs(ny) < big && ::fabs(nz) < big && len2 > 0.0;
+        // step 6 before steps 2 - 5 (no operation changes): the wave is still whole here, as the cooperative rounds need it
+        Path<double> G; // the generator's own stream; the ray's (what a ConstantMedium draws from) is load_ray's
+        seed_stream(G, sample_key(qp.src_seed, (u64)g, (u64)qp.src_first + (u64)k), 0u);
+        double x = 0.0, y = 0.0;
+        rand_in_unit_disk_wave<double>(G, ok, false, x, y); // Malley: a uniform point of the unit disk, lifted onto the hemisphere
+        if (sided && dot3(nx, ny, nz, wx, wy, wz) > 0.0) { nx = -nx; ny = -ny; nz = -nz; } // the normal points away from the viewer: the other side
+        const double len = ::sqrt(len2);
+        nx = nx / len; ny = ny / len; nz = nz / len;
+        double tx, ty, tz; // the frame: the coordinate axis least aligned with the normal, crossed with it
+        if (::fabs(nx) < 0.5) { tx = 0.0; ty = -nz; tz = ny; } else { tx = nz; ty = 0.0; tz = -nx; }
+        const double tl = ::sqrt(dot3(tx, ty, tz, tx, ty, tz));
+        tx = tx / tl; ty = ty / tl; tz = tz / tl;
+        const double bx = ny * tz - nz * ty, by = nz * tx - nx * tz, bz = nx * ty - ny * tx;
+        const double z = ::sqrt(1.0 - (x * x + y * y));
+        dx = (x * tx + y * bx) + z * nx; dy = (x * ty + y * by) + z * ny; dz = (x * tz + y * bz) + z * nz;
+    }
+    q[0] = ok ? px : 0.0; q[1] = ok ? py : 0.0; q[2] = ok ? pz : 0.0;
+    q[3] = ok ? dx : 0.0; q[4] = ok ? dy : 0.0; q[5] = ok ? dz : 0.0; q[6] = ok ? time : 0.0;
+    return ok;
+}
+
+template <typename R, int VARIANT, bool EXT = false, int MSEQ = 0, bool ANY = false, bool COUNT = false, int SRC = SRC_MEMORY>
 __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WAVES) : RTMI_MIN_WAVES) query_kernel(ScenePtr scp, QueryParams qp) {
+    static_assert(SRC == SRC_MEMORY || (SRC == SRC_PIXEL) != ANY, "the pixel-centre source feeds the closest-hit search, the point sources the any-hit search");
     static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the claim loop is per wave");
     static_assert(!COUNT || (VARIANT == SCAN_BVH && !EXT && sizeof(R) == sizeof(double)), "traversal counters: the FP64 sphere tree only");
     SceneRef sc = *scp;
@@ -1356,11 +1428,22 @@ __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WA
             w_end = min(base + qp.qblock, total_items);
         }
         const unsigned m = w_cur + (unsigned)lane;
-        const bool active = m < w_end;
+        const bool in_range = m < w_end;
+        bool active = in_range;
         w_cur = min(w_cur + 64u, w_end);
-        const unsigned row = active ? m : 0u; // (an idle lane loads row 0 and traces nothing)
+        const unsigned row = in_range ? m : 0u; // (an idle lane loads row 0 and traces nothing)
         Path<R> P;
-        load_ray<R>(qp.rays + (size_t)row * 7, P);
+        if (SRC == SRC_MEMORY) load_ray<R>(qp.rays + (size_t)row * 7, P);
+        else { // a point that yields no ray: an idle lane for this trip, its flag 0
+            double q[7];
+            active = generate_ray<SRC>(sc, qp, in_range, row, q);
+            if (in_range && qp.out_rays) {
+                double *o = qp.out_rays + (size_t)m * 7;
+#pragma unroll
+                for (int c = 0; c < 7; ++c) o[c] = q[c];
+            }
+            load_ray<R>(q, P);
+        }
         if (qp.keys) seed_stream(P, qp.keys[row], qp.ctr0);
         R tmin = (R)qp.tmin, tmax = (R)qp.tmax;
         if (qp.t_range) { const double *q = qp.t_range + (size_t)row * 2; tmin = (R)q[0]; tmax = (R)q[1]; }
@@ -1371,7 +1454,7 @@ __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WA
         n_rays += (unsigned)__popcll(__ballot(active));
         n_hit += (unsigned)__popcll(hit_mask);
         if (ANY) {
-            if (active && qp.occluded) qp.occluded[m] = hit ? 1 : 0;
+            if (in_range && qp.occluded) qp.occluded[m] = hit ? 1 : 0;
             if (qp.count) {
                 const unsigned g = row / qp.group;
                 const unsigned g_prev = (unsigned)__shfl_up((int)g, 1);
@@ -1704,6 +1787,7 @@ struct rtmi_ctx {
     DevBuf feat_cnt;  // rtmi_render_features_device: the counters nobody asked for
     DevBuf dn_planes; // rtmi_denoise*: the filter's planes (two colour + variance sets, the feature planes)
     DevBuf rays_ws;   // rtmi_render_rays*: the per-ray radiance nobody asked for (one pass of it)
+    DevBuf occ_ws;    // rtmi_ambient_occlusion*: the first-hit records and the per-pixel counts nobody asked for
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     int events_used = 0;
@@ -2363,7 +2447,7 @@ RTMI_EXPORT int rtmi_test_stage_layout(int32_t n, const uint64_t *elem_bytes, co
 }
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 216; } // 216: closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*); 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 217; } // 217: occlusion rays generated on the device (rtmi_occlusion_hemisphere*, rtmi_occlusion_targets*, rtmi_ambient_occlusion*); 216: closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*); 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -2402,7 +2486,7 @@ RTMI_EXPORT int rtmi_shutdown(rtmi_ctx *c) {
 #endif
     c->samples.release(); c->accum.release(); c->tiles.release(); c->tile_ids.release(); c->counters.release(); c->io.release(); c->multi.release();
     c->prog.release();
-    c->feat_cnt.release(); c->dn_planes.release(); c->rays_ws.release();
+    c->feat_cnt.release(); c->dn_planes.release(); c->rays_ws.release(); c->occ_ws.release();
     for (hipEvent_t e : {c->ev_done, c->ev_g0, c->ev_g1}) if (e) (void)hipEventDestroy(e);
     if (c->ev_consumed) { (void)hipSetDevice(c->ev_consumed_device); (void)hipEventDestroy(c->ev_consumed); (void)hipSetDevice(c->device); }
     for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -5144,11 +5228,11 @@ RTMI_EXPORT int rtmi_render_rays(rtmi_scene *s, int32_t precision, int32_t n_gro
 namespace {
 // query_kernel's instantiations are chosen where the probe kernels' are (with_probe_kernel), the LDS-staged scans answered with the scalar-cache scan as
 // for rays_kernel.  COUNT (option "count_traversal") exists for the FP64 sphere tree only: every other family runs the kernel it always runs.
-template <bool ANY, bool COUNT> struct QueryPass {
+template <bool ANY, bool COUNT, int SRC = SRC_MEMORY> struct QueryPass {
     static constexpr bool wave_level = true;
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() {
         constexpr int W = V < SCAN_SGPR ? (int)SCAN_SGPR : V;
-        return query_kernel<R, W, EXT, MSEQ, ANY, COUNT && W == SCAN_BVH && !EXT && std::is_same<R, double>::value>;
+        return query_kernel<R, W, EXT, MSEQ, ANY, COUNT && W == SCAN_BVH && !EXT && std::is_same<R, double>::value, SRC>;
     }
 };
 
@@ -5164,10 +5248,11 @@ int check_query_args(rtmi_scene *s, int precision, long long n, bool dims_ok, co
     return RTMI_OK;
 }
 
-// The launch, on `st`, every pointer a device pointer: counters (and group counts) zeroed, then one query_kernel over the n rays.
-template <typename R, bool ANY>
+// The launch, on `st`, every pointer a device pointer: counters (and group counts) zeroed, then one query_kernel over the n rays.  gen: the src_* fields
+// and out_rays of a generated source (SRC != SRC_MEMORY, which reads no d_rays).
+template <typename R, bool ANY, int SRC = SRC_MEMORY>
 int query_impl(rtmi_scene *s, int n, int n_groups, int group, const double *d_rays, const double *d_range, double t_min, double t_max, const u64 *d_keys,
-               unsigned ctr0, double *d_hits, unsigned char *d_occ, int *d_count, u64 *d_cnt, hipStream_t st) {
+               unsigned ctr0, double *d_hits, unsigned char *d_occ, int *d_count, u64 *d_cnt, hipStream_t st, const QueryParams *gen = nullptr) {
     rtmi_ctx *c = s->ctx;
     int rc = c->counters.ensure(8 * sizeof(u64)); // [0..1] the counters when the caller passes no buffer, [2] the work-queue head, [3..4] traversal counters
     if (rc) return rc;
@@ -5179,7 +5264,7 @@ int query_impl(rtmi_scene *s, int n, int n_groups, int group, const double *d_ra
         HIP_TRY(hipMemsetAsync(reinterpret_cast<u64 *>(c->counters.p) + 3, 0, 2 * sizeof(u64), st));
         c->last_stream = st;
     }
-    QueryParams qp;
+    QueryParams qp = gen ? *gen : QueryParams{};
     qp.rays = d_rays; qp.t_range = d_range; qp.keys = d_keys; qp.tmin = t_min; qp.tmax = t_max; qp.ctr0 = ctr0;
     qp.group = (unsigned)std::max(1, group); qp.total_items = (unsigned)n;
     qp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 2);
@@ -5211,8 +5296,8 @@ int query_impl(rtmi_scene *s, int n, int n_groups, int group, const double *d_ra
     // a tree over a handful of mixed-kind primitives costs more than scanning them (choose_trace_kernel): the same shortcut, the same knobs
     const LaunchKnobs knobs = read_launch_knobs();
     const bool flat = s->dev.has_ext && !count && s->dev.n_all < (knobs.flat_below ? std::atoi(knobs.flat_below) : c->flat_below);
-    if (count) with_probe_kernel<QueryPass<ANY, true>, R>(s, run);
-    else with_probe_kernel<QueryPass<ANY, false>, R>(s, run, flat);
+    if (count) with_probe_kernel<QueryPass<ANY, true, SRC>, R>(s, run);
+    else with_probe_kernel<QueryPass<ANY, false, SRC>, R>(s, run, flat);
     return rc;
 }
 } // namespace
@@ -5286,5 +5371,182 @@ RTMI_EXPORT int rtmi_query_occluded(rtmi_scene *s, int32_t precision, int32_t n_
     rc = with_real(precision, [&](auto r) {
         return query_impl<decltype(r), true>(s, (int)n, n_groups, group, d_rays, d_range, t_min, t_max, d_keys, ctr0, nullptr, d_occ, d_count, d_cnt, c->stream);
     });
+    return rc ? rc : io.finish();
+}
+
+// ---- occlusion rays generated on the device (rtmi_occlusion_hemisphere*, rtmi_occlusion_targets*, rtmi_ambient_occlusion*) -------------------------
+// query_kernel with a generated source: the points are rtmi_query_hits' records already in HBM, a ray is a few operations on its point's record, and no
+// ray ever crosses the bus or lies in HBM unless the caller asks for it (out_rays).
+namespace {
+// visibility = 1 - occluded / n_dirs, and 1 where the primary ray missed
+__global__ void __launch_bounds__(kBlock) ao_resolve_kernel(const double *__restrict__ hits, const int *__restrict__ count, int n, int n_dirs, double *__restrict__ vis) {
+    const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (p >= n) return;
+    vis[p] = hits[(size_t)p * RTMI_HIT_REC] != 0.0 ? 1.0 - (double)count[p] / (double)n_dirs : 1.0;
+}
+
+// the argument checks of the point entries, in the header's order; per_point = n_dirs / n_targets
+int check_occlusion_args(rtmi_scene *s, int precision, int n_points, int per_point, int first, const void *hits, bool targets_ok) {
+    if (n_points < 0 || per_point <= 0 || first < 0)
+        return fail(RTMI_E_ARG, "n_points, first must be >= 0 and n_dirs / n_targets > 0 (got %d %d %d)", n_points, first, per_point);
+    const long long n = (long long)n_points * per_point;
+    if (n > kRaysMax) return fail(RTMI_E_ARG, "%lld rays exceed 2^31 - 64", n);
+    if (n > 0 && !hits) return fail(RTMI_E_ARG, "hits is NULL");
+    if (n > 0 && !targets_ok) return fail(RTMI_E_ARG, "targets is NULL");
+    return check_query_args(s, precision, 0, true, nullptr, true); // the handle, the precision, RTMI_F32 on a mixed-kind scene
+}
+
+template <int SRC>
+int occlusion_impl(rtmi_scene *s, int precision, int n_points, int per_point, const QueryParams &gen, double t_min, double t_max, unsigned char *d_occ,
+                   int *d_count, u64 *d_cnt, hipStream_t st) {
+    return with_real(precision, [&](auto r) {
+        return query_impl<decltype(r), true, SRC>(s, n_points * per_point, n_points, per_point, nullptr, nullptr, t_min, t_max, nullptr, 0u, nullptr, d_occ,
+                                                  d_count, d_cnt, st, &gen);
+    });
+}
+
+QueryParams point_source(const double *d_hits, const double *d_view, const double *d_targets, int first, u64 seed, double time, double *d_out_rays) {
+    QueryParams g{};
+    g.src_hits = d_hits; g.src_view = d_view; g.src_targets = d_targets; g.src_first = (unsigned)first; g.src_seed = seed; g.src_time = time;
+    g.out_rays = d_out_rays;
+    return g;
+}
+
+int check_ao_args(rtmi_scene *s, int precision, int nx, int ny, int n_dirs, int first, double radius, const void *vis) {
+    if (nx < 0 || ny < 0 || n_dirs <= 0 || first < 0) return fail(RTMI_E_ARG, "nx, ny, first must be >= 0 and n_dirs > 0 (got %d %d %d %d)", nx, ny, first, n_dirs);
+    if (!(radius > 0.0)) return fail(RTMI_E_ARG, "radius must be > 0 (got %g)", radius);
+    const long long n = (long long)nx * ny;
+    if (n > kRaysMax || n * n_dirs > kRaysMax) return fail(RTMI_E_ARG, "%lld pixels x %d rays exceed 2^31 - 64", n, n_dirs);
+    if (n > 0 && !vis) return fail(RTMI_E_ARG, "out_visibility is NULL");
+    return check_query_args(s, precision, 0, true, nullptr, true); // the handle, the precision, RTMI_F32 on a mixed-kind scene
+}
+
+// The whole pass on `st`: the first hits of the pixel-centre rays, n_dirs hemisphere rays per hit on the viewer's side (the pixel-centre ray is built
+// again from the camera, not kept), the resolve.  d_hits / d_count null: in the context's workspace.
+template <typename R>
+int ao_impl(rtmi_scene *s, int nx, int ny, int n_dirs, int first, double radius, u64 seed, double *d_vis, int *d_count, double *d_hits, u64 *d_cnt,
+            hipStream_t st) {
+    rtmi_ctx *c = s->ctx;
+    const size_t n = (size_t)nx * (size_t)ny, hit_bytes = n * RTMI_HIT_REC * sizeof(double);
+    if (!d_hits || !d_count) {
+        const int rc = c->occ_ws.ensure(hit_bytes + n * sizeof(int));
+        if (rc) return rc;
+        if (!d_hits) d_hits = reinterpret_cast<double *>(c->occ_ws.p);
+        if (!d_count) d_count = reinterpret_cast<int *>(static_cast<char *>(c->occ_ws.p) + hit_bytes);
+    }
+    QueryParams g{};
+    g.src_nx = (unsigned)nx; g.src_ny = (unsigned)ny;
+    int rc = query_impl<R, false, SRC_PIXEL>(s, (int)n, 0, 1, nullptr, nullptr, 0.001, 3.4028234663852886e38, nullptr, 0u, d_hits, nullptr, nullptr, nullptr, st, &g);
+    if (rc) return rc;
+    g.src_hits = d_hits; g.src_first = (unsigned)first; g.src_seed = seed; g.src_view_camera = 1u;
+    rc = query_impl<R, true, SRC_HEMISPHERE>(s, (int)(n * (size_t)n_dirs), (int)n, n_dirs, nullptr, nullptr, 0.001, radius, nullptr, 0u, nullptr, nullptr, d_count,
+                                             d_cnt, st, &g);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ao_resolve_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_hits, d_count, (int)n, n_dirs, d_vis);
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_occlusion_hemisphere_device(rtmi_scene *s, int32_t precision, int32_t n_points, const void *d_hits, const void *d_view, int32_t n_dirs,
+                                                 int32_t first, uint64_t seed, double time, double t_min, double t_max, void *d_out_occluded,
+                                                 void *d_out_count, void *d_out_rays, void *d_out_counters, void *stream) {
+    const int rc = check_occlusion_args(s, precision, n_points, n_dirs, first, d_hits, true);
+    if (rc || n_points == 0) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    return occlusion_impl<SRC_HEMISPHERE>(s, precision, n_points, n_dirs,
+                                          point_source(reinterpret_cast<const double *>(d_hits), reinterpret_cast<const double *>(d_view), nullptr, first, seed, time,
+                                                       reinterpret_cast<double *>(d_out_rays)),
+                                          t_min, t_max, reinterpret_cast<unsigned char *>(d_out_occluded), reinterpret_cast<int *>(d_out_count),
+                                          reinterpret_cast<u64 *>(d_out_counters), stream_of(c, stream));
+}
+
+RTMI_EXPORT int rtmi_occlusion_hemisphere(rtmi_scene *s, int32_t precision, int32_t n_points, const double *hits, const double *view, int32_t n_dirs,
+                                          int32_t first, uint64_t seed, double time, double t_min, double t_max, uint8_t *out_occluded, int32_t *out_count,
+                                          double *out_rays, uint64_t *out_counters) {
+    int rc = check_occlusion_args(s, precision, n_points, n_dirs, first, hits, true);
+    if (rc || n_points == 0) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t np = (size_t)n_points, n = np * (size_t)n_dirs;
+    HostIo io(c);
+    double *d_hits, *d_view, *d_rays;
+    u64 *d_cnt;
+    unsigned char *d_occ;
+    int *d_count;
+    io.in(&d_hits, np * RTMI_HIT_REC, hits); io.in(&d_view, np * 7, view);
+    io.out(&d_occ, n, out_occluded); io.out(&d_count, np, out_count); io.out(&d_rays, n * 7, out_rays); io.work(&d_cnt, 2, out_counters);
+    rc = io.stage();
+    if (rc) return rc;
+    rc = occlusion_impl<SRC_HEMISPHERE>(s, precision, n_points, n_dirs, point_source(d_hits, d_view, nullptr, first, seed, time, d_rays), t_min, t_max, d_occ,
+                                        d_count, d_cnt, c->stream);
+    return rc ? rc : io.finish();
+}
+
+RTMI_EXPORT int rtmi_occlusion_targets_device(rtmi_scene *s, int32_t precision, int32_t n_points, const void *d_hits, const void *d_view, int32_t n_targets,
+                                              const void *d_targets, double time, double t_min, double t_max, void *d_out_occluded, void *d_out_count,
+                                              void *d_out_rays, void *d_out_counters, void *stream) {
+    const int rc = check_occlusion_args(s, precision, n_points, n_targets, 0, d_hits, d_targets != nullptr);
+    if (rc || n_points == 0) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    return occlusion_impl<SRC_TARGETS>(s, precision, n_points, n_targets,
+                                       point_source(reinterpret_cast<const double *>(d_hits), reinterpret_cast<const double *>(d_view),
+                                                    reinterpret_cast<const double *>(d_targets), 0, 0ull, time, reinterpret_cast<double *>(d_out_rays)),
+                                       t_min, t_max, reinterpret_cast<unsigned char *>(d_out_occluded), reinterpret_cast<int *>(d_out_count),
+                                       reinterpret_cast<u64 *>(d_out_counters), stream_of(c, stream));
+}
+
+RTMI_EXPORT int rtmi_occlusion_targets(rtmi_scene *s, int32_t precision, int32_t n_points, const double *hits, const double *view, int32_t n_targets,
+                                       const double *targets, double time, double t_min, double t_max, uint8_t *out_occluded, int32_t *out_count,
+                                       double *out_rays, uint64_t *out_counters) {
+    int rc = check_occlusion_args(s, precision, n_points, n_targets, 0, hits, targets != nullptr);
+    if (rc || n_points == 0) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t np = (size_t)n_points, n = np * (size_t)n_targets;
+    HostIo io(c);
+    double *d_hits, *d_view, *d_targets, *d_rays;
+    u64 *d_cnt;
+    unsigned char *d_occ;
+    int *d_count;
+    io.in(&d_hits, np * RTMI_HIT_REC, hits); io.in(&d_view, np * 7, view); io.in(&d_targets, (size_t)n_targets * 3, targets);
+    io.out(&d_occ, n, out_occluded); io.out(&d_count, np, out_count); io.out(&d_rays, n * 7, out_rays); io.work(&d_cnt, 2, out_counters);
+    rc = io.stage();
+    if (rc) return rc;
+    rc = occlusion_impl<SRC_TARGETS>(s, precision, n_points, n_targets, point_source(d_hits, d_view, d_targets, 0, 0ull, time, d_rays), t_min, t_max, d_occ,
+                                     d_count, d_cnt, c->stream);
+    return rc ? rc : io.finish();
+}
+
+RTMI_EXPORT int rtmi_ambient_occlusion_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t n_dirs, int32_t first, double radius,
+                                              uint64_t seed, void *d_out_visibility, void *d_out_count, void *d_out_hits, void *d_out_counters, void *stream) {
+    const int rc = check_ao_args(s, precision, nx, ny, n_dirs, first, radius, d_out_visibility);
+    if (rc || nx == 0 || ny == 0) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream_of(c, stream);
+    return with_real(precision, [&](auto r) {
+        return ao_impl<decltype(r)>(s, nx, ny, n_dirs, first, radius, seed, reinterpret_cast<double *>(d_out_visibility), reinterpret_cast<int *>(d_out_count),
+                                    reinterpret_cast<double *>(d_out_hits), reinterpret_cast<u64 *>(d_out_counters), st);
+    });
+}
+
+RTMI_EXPORT int rtmi_ambient_occlusion(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t n_dirs, int32_t first, double radius, uint64_t seed,
+                                       double *out_visibility, int32_t *out_count, double *out_hits, uint64_t *out_counters) {
+    int rc = check_ao_args(s, precision, nx, ny, n_dirs, first, radius, out_visibility);
+    if (rc || nx == 0 || ny == 0) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)nx * (size_t)ny;
+    HostIo io(c);
+    double *d_vis, *d_hits;
+    u64 *d_cnt;
+    int *d_count;
+    io.out(&d_vis, n, out_visibility); io.out(&d_count, n, out_count); io.out(&d_hits, n * RTMI_HIT_REC, out_hits); io.work(&d_cnt, 2, out_counters);
+    rc = io.stage();
+    if (rc) return rc;
+    rc = with_real(precision, [&](auto r) { return ao_impl<decltype(r)>(s, nx, ny, n_dirs, first, radius, seed, d_vis, d_count, d_hits, d_cnt, c->stream); });
     return rc ? rc : io.finish();
 }
