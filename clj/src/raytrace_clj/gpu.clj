@@ -683,6 +683,81 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn scene-lights
+  "The primitives of scene {:camera :world} a light sample can be placed on (rtmi_scene_lights), in primitive order, as a vector of indices
+  into the flattened primitive list: spheres and axis-aligned rectangles without a Translate / RotateY chain whose material is a DiffuseLight
+  over a Constant texture.  Moving, triangle, instanced, gradient and image emitters are left out; that is no error."
+  [scene & {:keys [device] :or {device 0}}]
+  (let [f     (flatten-scene scene)
+        ctx   (PointerByReference.)
+        prims (int-array 32)
+        cnt   (int-array 1)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_scene_lights" scn (int 32) prims cnt))
+          (vec (take (min 32 (aget cnt 0)) prims))
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
+(defn direct-irradiance
+  "The direct irradiance at each of n-points hit records (rtmi_direct_irradiance): n-samples points on each of the lights `lights` (primitive
+  indices out of scene-lights, at most 32; required here -- the C entry's NULL form, all eligible lights, is not bound), one shadow ray each,
+  weighted by both cosines, the inverse square and the light's area.  `hits` holds 12 doubles per point as query-hits returns them, `view` the
+  7 doubles of the ray that found each point (required, as for occlusion-hemisphere).  Item (g * n-samples + k) * n-lights + l draws from the
+  stream keyed (sample-key seed (+ (* g n-lights) l) (+ first k)).  Returns {:irradiance double-array [n-points][3], :contrib double-array
+  [items][3], :occluded byte-array [items], :out-rays double-array [items][7], :rays, :rays-occluded}."
+  [scene hits view n-points lights n-samples & {:keys [first seed lambert-only device precision]
+                                                 :or {first 0 seed 0x5EED0002 lambert-only false device 0 precision 0}}]
+  (let [f       (flatten-scene scene)
+        ctx     (PointerByReference.)
+        lp      (int-array lights)
+        nl      (alength lp)
+        n       (* n-points n-samples nl)
+        hs      (double-array hits)
+        vw      (double-array view)
+        state   (double-array (* 4 n-points))
+        irr     (double-array (* 3 n-points))
+        contrib (double-array (* 3 n))
+        flags   (byte-array n)
+        out     (double-array (* 7 n))
+        cnt     (long-array 2)]
+    (when-not (and (= (alength hs) (* 12 n-points)) (= (alength vw) (* 7 n-points)))
+      (throw (IllegalArgumentException. "hits must hold 12 and view 7 doubles per point")))
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_direct_irradiance" scn (int precision) (int n-points) hs vw (int nl) lp (int n-samples) (int first) (long seed)
+                           (double 0.0) (int (if lambert-only 1 0)) state irr contrib flags out cnt))
+          {:irradiance irr :contrib contrib :occluded flags :out-rays out :rays (aget cnt 0) :rays-occluded (aget cnt 1)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
+(defn render-direct
+  "The nx x ny view of scene {:camera :world} lit directly, the whole pass on the device (rtmi_render_direct): the first hits of the
+  pixel-centre rays, n-samples shadow rays per hit towards every light of scene-lights, then per pixel: an emitter shows its emission, a
+  Lambertian surface albedo * E / pi, anything else and a miss is black.  Returns {:linear double-array [ny * nx][3] (row 0 = top), :rgb8
+  byte-array, :hits double-array [ny * nx][12], :rays, :rays-occluded}."
+  [scene nx ny n-samples & {:keys [seed device precision] :or {seed 0x5EED0002 device 0 precision 0}}]
+  (let [f     (flatten-scene scene)
+        ctx   (PointerByReference.)
+        n     (* nx ny)
+        state (double-array (* 4 n))
+        lin   (double-array (* 3 n))
+        rgb8  (byte-array (* 3 n))
+        hits  (double-array (* 12 n))
+        cnt   (long-array 2)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_direct" scn (int precision) (int nx) (int ny) (int n-samples) (int 0) (long seed) state lin rgb8 hits cnt))
+          {:linear lin :rgb8 rgb8 :hits hits :rays (aget cnt 0) :rays-occluded (aget cnt 1)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn pick
   "What lies under pixel (column i, row j from the top) of an nx x ny view of scene {:camera :world}: nil, or {:prim :material :t :p :normal
   :uv} of the closest hit of the ray from the camera's origin (a thin lens: its lens centre) through the pixel's centre -- u = (i + 1/2) / nx,

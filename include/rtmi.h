@@ -692,6 +692,89 @@ int rtmi_ambient_occlusion(rtmi_scene *scene, int32_t precision, int32_t nx, int
 int rtmi_ambient_occlusion_device(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t n_dirs, int32_t first, double radius, uint64_t seed,
                                   void *d_out_visibility, void *d_out_count, void *d_out_hits, void *d_out_counters, void *stream);
 
+/* ---- direct lighting from first hits: the scene's area lights sampled on the device (a lit preview, a lightmap's direct term) ----
+ * THE LIGHTS.  rtmi_scene_lights lists, in primitive order, the primitives a light sample can be placed on.  A primitive is ELIGIBLE when
+ *   - its kind is RTMI_PRIM_SPHERE or RTMI_PRIM_UVSPHERE with radius > 0, or RTMI_PRIM_RECT_XY / XZ / YZ with both extents non-zero (a1 != a0, b1 != b0);
+ *   - it does not carry RTMI_PRIM_BOUNDARY;
+ *   - its Translate / RotateY chain is empty (FlipNormals wrappers do not matter: DiffuseLight's emitted is two-sided, shader.clj:118);
+ *   - its material is RTMI_MAT_DIFFUSE_LIGHT and that material's texture is RTMI_TEX_CONSTANT.
+ * Everything else -- a MovingSphere, a triangle, an instanced lamp, a gradient or image emitter such as the cover scene's sky dome -- is simply not a light
+ * for these calls; it is no error, and it still occludes and still shows its emission where a primary ray of rtmi_render_direct hits it.
+ * The list is read from the host-side tables the scene keeps, at call time: it follows every rtmi_scene_set_materials* and rtmi_scene_set_geometry call made
+ * before.  out_prims: `capacity` entries (may be NULL with capacity 0), the first min(count, capacity) eligible primitives; *out_count: all of them.
+ * Host state only: no device access.  Errors: capacity < 0, out_count NULL, out_prims NULL with capacity > 0: RTMI_E_ARG; a bad handle: RTMI_E_STATE.
+ * rtmi_test_scene_lights: test hook, host code only (no device, no handle): the same function over the flat arrays (prim_xform may be NULL: no chains).
+ *
+ * THE ITEMS.  Points are rtmi_query_hits' records, as for the occlusion calls above.  Item m = (g * n_samples + k) * n_lights + l is sample k of point g
+ * towards light l; a point's group is its n_samples * n_lights consecutive items.  light_prims (a HOST array in both forms): the n_lights primitives to
+ * sample, each eligible (else RTMI_E_ARG), at most RTMI_DIRECT_MAX_LIGHTS; NULL: all eligible primitives, n_lights is then not read.  The light table --
+ * per light {kind, 5 geometry doubles, area, Le.rgb}, Le = the constant texture's colour -- travels in stream order as the arguments of a one-wave kernel:
+ * the host is never waited for.
+ * THE LIGHT RULE, operation by operation as the hemisphere rule: every product, sum, difference and quotient is one IEEE double operation in the order written,
+ * only + - * / sqrt occur, dot3(a, b) = (ax*bx + ay*by) + az*bz.
+ *   1. Steps 1 - 3 of the hemisphere rule give p, the viewer-side unit normal nn, the ray's time and "the point yields no ray".  With lambert_only != 0 a point
+ *      also yields no ray unless rec[11] is a material index of the scene and mat_kind[rec[11]] == RTMI_MAT_LAMBERTIAN.
+ *   2. The stream of item (g, k, l) is keyed rtmi_sample_key(seed, g * n_lights + l, first + k) and starts at draw 0; u(d) = the FP64 uniform of draw d.
+ *   3. Rectangle light (prim_geom = a0, b0, a1, b1, kk): the in-plane point (a0 + u(0)*(a1 - a0), b0 + u(1)*(b1 - b0)) with kk on the axis, i.e. q = (a, b, kk)
+ *      for RTMI_PRIM_RECT_XY, (a, kk, b) for RECT_XZ, (kk, a, b) for RECT_YZ; s = the axis' unit vector (0, 0, 1) / (0, 1, 0) / (1, 0, 0);
+ *      area = |(a1 - a0)*(b1 - b0)|.
+ *   4. Sphere light (c, r): take the disk point (x, y) of hemisphere-rule step 6 from this stream, S = x*x + y*y, root = sqrt(1 - S),
+ *      s = ((2*x)*root, (2*y)*root, 1 - 2*S) (Marsaglia: uniform on the sphere), q = c + r*s per component, area = FOURPI*(r*r), FOURPI = 0x1.921fb54442d18p+3.
+ *      With e = p - c: if dot3(e, e) > r*r and dot3(s, d) > 0 (d of step 5) the item yields no ray -- the far side seen from outside; a point inside the sphere
+ *      (under a constant sky dome) sees all of it.
+ *   5. d = q - p per component, d2 = dot3(d, d), cp = dot3(nn, d), cl = |dot3(s, d)|.  The item yields no ray unless d2 > 0, cp > 0 and cl > 0 (a NaN fails).
+ *      w = ((cp*cl) / (d2*d2)) * area: both cosines and the inverse square in one quotient, no sqrt.
+ *   6. The ray: origin p, direction d, the time of step 1, t-range (0.001, 1 - 0.001) -- "up to the light": the light's own surface at t = 1 is outside it.
+ *   7. After the any-hit search the item's contribution is three doubles: Le * w per channel if the ray was built and is not occluded, else +0.0.
+ * Rays and weights are FP64 whatever the precision; RTMI_F32 differs from RTMI_F64 exactly where rtmi_query_occluded does.
+ * THE FOLD.  One lane per point sums the point's contributions in item order in double, starting FROM the first item (not 0 + first), then
+ * E = sum * (1.0 / (double)samples), samples = every sample k taken so far, those that built no ray included.  state (may be NULL): [n_points][RTMI_DIRECT_REC]
+ * doubles {sum.rgb, samples}, read when first > 0 and written back: it continues a point over calls under rtmi_render_rays' contract -- any split of a point's
+ * samples into consecutive chunks gives the bits of one call (the host form checks state[g][3] == first: RTMI_E_STATE).  Without a state samples = n_samples.
+ * The contributions live in the context's workspace, 24 bytes per item, in passes of whole points under option "workspace_bytes"; with out_contrib the call
+ * is one pass into it.
+ *   out_irradiance: [n_points][3]; out_contrib (may be NULL): [items][3]; out_occluded (may be NULL): [items] bytes; out_rays (may be NULL): [items][7], zeros
+ *   where no ray was built; out_counters (may be NULL): {rays built, occluded rays}.
+ * Zero lights (an empty list, or NULL and nothing eligible) succeeds: without a state it writes zeros to out_irradiance and out_counters and launches
+ * nothing (rtmi_render_direct: none of the light passes).  With a state, in the host and the device forms alike, the fold runs over groups of no items:
+ * every sample counts as one that built no ray -- the sums carry over (zeros when first == 0), samples becomes first + n_samples and
+ * E = sum * (1.0 / samples), so a state split over calls continues on a scene without lights as on any other.  n_points == 0 succeeds and does nothing.
+ * rtmi_render_direct: the whole pass for an nx x ny view on one stream, as rtmi_ambient_occlusion: (a) its first hits of the pixel-centre rays; (b) the light
+ *   rule over those records with the pixel-centre rays as the view, all eligible lights, lambert_only = 1; (c) the resolve, per pixel: a first hit on
+ *   RTMI_MAT_DIFFUSE_LIGHT: its texture at the record's (u, v, p) (Texture.sample, whatever the texture); on RTMI_MAT_LAMBERTIAN: (albedo * E) * INV_PI per
+ *   channel, albedo = its texture at the record, INV_PI = 0x1.45f306dc9c883p-2; anything else, or a miss: zeros (the reference's black miss; specular
+ *   transport is not direct light).  The textures are evaluated in the call's precision, E and the product in double.  out_rgb8 (may be NULL): the frame's
+ *   quantiser of out_linear (sqrt, x 255.99, min, trunc, NaN -> 0).  out_linear: [ny * nx][3], row 0 = top; out_hits (may be NULL): the records of (a);
+ *   state (may be NULL): [ny * nx][RTMI_DIRECT_REC]; out_counters (may be NULL): those of (b).
+ * Errors, in this order: n_points < 0 (nx, ny < 0), n_samples <= 0, first < 0, n_lights < 0 or > RTMI_DIRECT_MAX_LIGHTS with a list: RTMI_E_ARG; hits,
+ * out_irradiance (out_linear) NULL with work to do: RTMI_E_ARG; a bad handle: RTMI_E_STATE; a bad precision: RTMI_E_ARG; RTMI_F32 on a mixed-kind scene:
+ * RTMI_E_UNSUPPORTED; rtmi_render_direct* only, whose resolve samples textures: a Perlin texture without rtmi_scene_set_perlin, or an ImageMap beyond the
+ * images given: RTMI_E_STATE, as rtmi_render; a listed primitive that is out of range or not eligible, more than RTMI_DIRECT_MAX_LIGHTS eligible primitives without a list, more than
+ * 2^31 - 64 items: RTMI_E_ARG.  A failed call launches nothing.  Options, frames, revision and RTMI_FLAG_TIMING: as the occlusion calls (neither entry
+ * touches the progressive or adaptive frame or the scene's revision; the trace interval covers the query launches, the fold interval the fold). */
+#define RTMI_DIRECT_REC 4         /* doubles per point of a direct-lighting state: sum rgb, samples */
+#define RTMI_DIRECT_MAX_LIGHTS 32 /* lights one call samples */
+int rtmi_scene_lights(rtmi_scene *scene, int32_t capacity, int32_t *out_prims, int32_t *out_count);
+int rtmi_test_scene_lights(int32_t n_prims, const int32_t *prim_kind, const double *prim_geom, const int32_t *prim_mat,
+                           int32_t n_mats, const int32_t *mat_kind, const int32_t *mat_tex, int32_t n_tex, const int32_t *tex_kind,
+                           const int32_t *prim_xform, int32_t capacity, int32_t *out_prims, int32_t *out_count);
+/* host buffers; synchronous */
+int rtmi_direct_irradiance(rtmi_scene *scene, int32_t precision, int32_t n_points, const double *hits, const double *view, int32_t n_lights,
+                           const int32_t *light_prims, int32_t n_samples, int32_t first, uint64_t seed, double time, int32_t lambert_only, double *state,
+                           double *out_irradiance, double *out_contrib, uint8_t *out_occluded, double *out_rays, uint64_t *out_counters);
+/* every d_ pointer a device pointer (light_prims stays a host array); asynchronous on `stream` with rtmi_render_device's stream semantics.  Allocates nothing
+ * once the context's workspace has grown to size. */
+int rtmi_direct_irradiance_device(rtmi_scene *scene, int32_t precision, int32_t n_points, const void *d_hits, const void *d_view, int32_t n_lights,
+                                  const int32_t *light_prims, int32_t n_samples, int32_t first, uint64_t seed, double time, int32_t lambert_only,
+                                  void *d_state, void *d_out_irradiance, void *d_out_contrib, void *d_out_occluded, void *d_out_rays, void *d_out_counters,
+                                  void *stream);
+/* host buffers; synchronous */
+int rtmi_render_direct(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t n_samples, int32_t first, uint64_t seed, double *state,
+                       double *out_linear, uint8_t *out_rgb8, double *out_hits, uint64_t *out_counters);
+/* every pointer a device pointer; asynchronous on `stream`; without d_out_hits the records live in the context's workspace */
+int rtmi_render_direct_device(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t n_samples, int32_t first, uint64_t seed, void *d_state,
+                              void *d_out_linear, void *d_out_rgb8, void *d_out_hits, void *d_out_counters, void *stream);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

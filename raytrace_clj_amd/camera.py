@@ -237,3 +237,82 @@ def hemisphere_rays_disk(points, normals, n_dirs, first=0, seed=0x5EED0002, time
         dy = (x * ty[g] + y * by[g]) + z * ny[g]
         dz = (x * tz[g] + y * bz[g]) + z * nz[g]
     return _rays(points[g], np.stack([dx, dy, dz], axis=1), float(time))[0]
+
+
+LIGHT_REC = 10  # doubles per light of a light table: kind, 5 geometry doubles, area, Le rgb
+FOURPI = float.fromhex("0x1.921fb54442d18p+3")
+
+
+def light_table(flat, prims):
+    """The light table rtmi_direct_irradiance builds for the primitives `prims` of a FlatScene (each out of DeviceScene.lights()) -> [n, LIGHT_REC]:
+    the primitive's kind; a sphere's centre and radius and 0, or a rectangle's a0, b0, a1, b1, k; the area FOURPI * (r * r) or
+    |(a1 - a0) * (b1 - b0)|; Le = the colour of the DiffuseLight's Constant texture."""
+    prims = np.asarray(prims, np.int64).reshape(-1)
+    kind = np.asarray(flat.prim_kind, np.int64)[prims]
+    geom = np.asarray(flat.prim_geom, np.float64).reshape(-1, 9)[prims]
+    tex = np.asarray(flat.mat_tex, np.int64)[np.asarray(flat.prim_mat, np.int64)[prims]]
+    sphere = kind <= 1
+    table = np.zeros((len(prims), LIGHT_REC), np.float64)
+    table[:, 0] = kind
+    table[:, 1:5] = geom[:, 0:4]
+    table[:, 5] = np.where(sphere, 0.0, geom[:, 4])
+    table[:, 6] = np.where(sphere, FOURPI * (geom[:, 3] * geom[:, 3]), np.abs((geom[:, 2] - geom[:, 0]) * (geom[:, 3] - geom[:, 1])))
+    table[:, 7:10] = np.asarray(flat.tex_param, np.float64).reshape(-1, 12)[tex, 0:3]
+    return table
+
+
+def light_samples(points, normals, lights, n_samples, first=0, seed=0x5EED0002, time=0.0):
+    """The shadow rays and weights the device builds towards area lights (include/rtmi.h, "the light rule", steps 2 - 6), every operation a single
+    IEEE operation in the header's order, so rtmi_direct_irradiance's out_rays equal these rows bit for bit.  points, normals [n, 3]: the shaded
+    points and their normals on the viewer's side (any length; the rule normalises them); lights [n_lights, LIGHT_REC] (light_table).  Item
+    (g * n_samples + k) * n_lights + l is sample first + k of point g on light l, its stream keyed sample_key(seed, g * n_lights + l, first + k):
+    a rectangle takes draws 0 and 1 as in-plane coordinates, a sphere the rejection loop's disk point mapped onto the sphere by Marsaglia's method.
+    -> (rays [items, 7] from the point to the sampled point, so t = 1 is the light; weights [items] = cos cos' area / d^2 as
+    ((cp * cl) / (d2 * d2)) * area; built [items] bool: False where the light is behind the point, edge-on, or turns its far side -- those rows
+    are zeros).  The irradiance estimate of a point is the mean over k of the sum over l of Le * weight * visibility."""
+    from . import util
+    points, normals = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(normals, np.float64).reshape(-1, 3)
+    lights = np.asarray(lights, np.float64).reshape(-1, LIGHT_REC)
+    n_samples, first, nl = int(n_samples), int(first), len(lights)
+    if len(points) != len(normals) or n_samples <= 0 or first < 0:
+        raise ValueError("points and normals must pair up, n_samples > 0 and first >= 0")
+    g, k, l = (a.ravel() for a in np.meshgrid(np.arange(len(points)), np.arange(first, first + n_samples), np.arange(nl), indexing="ij"))
+    keys = util.sample_keys(seed, g * nl + l, k)                                        # 2. the item's stream
+    kind = lights[l, 0].astype(np.int64)
+    sphere = kind <= 1
+    g0, g1, g2, g3, g4, area = (lights[l, c] for c in range(1, 7))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        nx, ny, nz = normals[:, 0], normals[:, 1], normals[:, 2]
+        length = np.sqrt((nx * nx + ny * ny) + nz * nz)                               # (step 3 of the hemisphere rule)
+        nx, ny, nz = (nx / length)[g], (ny / length)[g], (nz / length)[g]
+        px, py, pz = points[g, 0], points[g, 1], points[g, 2]
+        a = g0 + util.draw_uniforms(keys, 0) * (g2 - g0)                                # 3. a rectangle: draws 0 and 1
+        b = g1 + util.draw_uniforms(keys, 1) * (g3 - g1)
+        x, y = np.zeros(len(keys)), np.zeros(len(keys))                                 # 4. a sphere: the first candidate inside the disk
+        pending, c = np.flatnonzero(sphere), 0
+        while len(pending):
+            cx = 2.0 * util.draw_uniforms(keys[pending], 2 * c) - 1.0
+            cy = 2.0 * util.draw_uniforms(keys[pending], 2 * c + 1) - 1.0
+            inside = ~(((cx * cx + cy * cy) + 0.0 * 0.0) >= 1.0)
+            x[pending[inside]], y[pending[inside]] = cx[inside], cy[inside]
+            pending, c = pending[~inside], c + 1
+        S = x * x + y * y
+        root = np.sqrt(1.0 - S)
+        sx = np.where(sphere, (2.0 * x) * root, np.where(kind == 5, 1.0, 0.0))
+        sy = np.where(sphere, (2.0 * y) * root, np.where(kind == 4, 1.0, 0.0))
+        sz = np.where(sphere, 1.0 - 2.0 * S, np.where(kind == 3, 1.0, 0.0))
+        qx = np.where(sphere, g0 + g3 * sx, np.where(kind == 5, g4, a))
+        qy = np.where(sphere, g1 + g3 * sy, np.where(kind == 3, b, np.where(kind == 4, g4, a)))
+        qz = np.where(sphere, g2 + g3 * sz, np.where(kind == 3, g4, b))
+        dx, dy, dz = qx - px, qy - py, qz - pz                                          # 5. the geometry term
+        d2 = (dx * dx + dy * dy) + dz * dz
+        cp = (nx * dx + ny * dy) + nz * dz
+        sd = (sx * dx + sy * dy) + sz * dz
+        cl = np.abs(sd)
+        ex, ey, ez = px - g0, py - g1, pz - g2
+        far = sphere & (((ex * ex + ey * ey) + ez * ez) > g3 * g3) & (sd > 0.0)           # the far side of a sphere seen from outside
+        built = ~far & (d2 > 0.0) & (cp > 0.0) & (cl > 0.0)
+        w = ((cp * cl) / (d2 * d2)) * area
+    rays = _rays(points[g], np.stack([dx, dy, dz], axis=1), float(time))[0]            # 6. origin p, direction d: t = 1 is the light
+    rays[~built] = 0.0
+    return rays, np.where(built, w, 0.0), built

@@ -831,6 +831,82 @@ class DeviceScene:
                                                        ptr(out_visibility), ptr(out_count), ptr(out_hits), ptr(out_counters), ptr(stream)))
         return None
 
+    # ---- direct lighting from first hits: the scene's area lights sampled on the device (rtmi_scene_lights, rtmi_direct_irradiance*, rtmi_render_direct*)
+    def lights(self):
+        """The primitives a light sample can be placed on, in primitive order (int32): spheres and axis-aligned rectangles without a Translate /
+        RotateY chain whose material is a DiffuseLight over a Constant texture.  Read from the tables the scene keeps: it follows set_materials
+        and set_geometry.  Moving, triangle, instanced, gradient and image emitters are not lights for these calls (they still occlude and show)."""
+        count = C.c_int32()
+        check(_ffi.lib().rtmi_scene_lights(self.handle, 0, None, C.byref(count)))
+        prims = np.zeros(count.value, np.int32)
+        check(_ffi.lib().rtmi_scene_lights(self.handle, len(prims), ptr(prims), C.byref(count)))
+        return prims
+
+    def _direct_lights(self, lights):
+        """-> (the int32 list or None = all eligible, its length, the lights the call will sample)"""
+        if lights is None:
+            return None, 0, len(self.lights())
+        lights = np.ascontiguousarray(lights, np.int32).reshape(-1)
+        n = len(lights)
+        return (lights if n else np.zeros(1, np.int32)), n, n  # (an empty list is still a list: its pointer must not be NULL)
+
+    def direct_irradiance(self, hits, n_samples, view=None, lights=None, first=0, seed=RENDER_SEED, time=0.0, lambert_only=False, state=None,
+                          precision="f64", return_items=False):
+        """The direct irradiance at every point of hits [n, HIT_REC] (query_hits' records): n_samples points on each light (lights: primitive
+        indices out of self.lights(); None: all of them), one shadow ray each, weighted by both cosines, the inverse square and the light's area
+        -- the light rule of include/rtmi.h, which camera.light_samples restates.  view [n, 7]: the rays that found the points (they pick the
+        side and the time).  lambert_only: only points on a Lambertian material are lit.  state ([n, DIRECT_REC] float64, updated in place;
+        first = 0 starts it, first > 0 continues it): the estimate is then over all samples so far, and any split gives the bits of one call.
+        -> (E [n, 3], counters {rays built, occluded rays}); with return_items also the per-item contributions [items, 3], flags uint8 [items]
+        and rays [items, 7], item (g * n_samples + k) * n_lights + l."""
+        hits, view = self._occlusion_inputs(hits, view)
+        lights, n_listed, n_lights = self._direct_lights(lights)
+        n = len(hits)
+        items = n * max(int(n_samples), 0) * n_lights
+        if state is not None and (not isinstance(state, np.ndarray) or state.dtype != np.float64 or not state.flags.c_contiguous
+                                  or state.shape != (n, _ffi.DIRECT_REC)):
+            raise ValueError("state must be a C-contiguous float64 array [n_points, %d]" % _ffi.DIRECT_REC)
+        E, cnt = np.zeros((n, 3), np.float64), np.zeros(2, np.uint64)
+        contrib, flags, rays = ((np.zeros((items, 3), np.float64), np.zeros(items, np.uint8), np.zeros((items, 7), np.float64)) if return_items
+                                else (None, None, None))
+        check(_ffi.lib().rtmi_direct_irradiance(self.handle, _PRECISION[precision], n, ptr(hits), ptr(view), n_listed, ptr(lights), int(n_samples),
+                                                int(first), int(seed), float(time), int(bool(lambert_only)), ptr(state), ptr(E), ptr(contrib), ptr(flags),
+                                                ptr(rays), ptr(cnt)))
+        return (E, cnt, contrib, flags, rays) if return_items else (E, cnt)
+
+    def direct_irradiance_device(self, n_points, hits, n_samples, out_irradiance, view=None, lights=None, first=0, seed=RENDER_SEED, time=0.0,
+                                 lambert_only=False, state=None, out_contrib=None, out_occluded=None, out_rays=None, out_counters=None,
+                                 precision="f64", stream=None):
+        """direct_irradiance on HBM-resident buffers (hits as query_hits_device wrote them; lights stays a host list); asynchronous,
+        render_device's stream semantics.  A state's sample count is the caller's contract: it is not read back."""
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        check(_ffi.lib().rtmi_direct_irradiance_device(self.handle, _PRECISION[precision], int(n_points), ptr(hits), ptr(view), n_listed, ptr(lights),
+                                                       int(n_samples), int(first), int(seed), float(time), int(bool(lambert_only)), ptr(state),
+                                                       ptr(out_irradiance), ptr(out_contrib), ptr(out_occluded), ptr(out_rays), ptr(out_counters),
+                                                       ptr(stream)))
+
+    def render_direct(self, nx, ny, n_samples, first=0, seed=RENDER_SEED, state=None, precision="f64", return_hits=False):
+        """The view lit directly, the whole pass on the device (rtmi_render_direct): first hits of the pixel-centre rays, n_samples shadow rays per
+        hit and eligible light, then per pixel: an emitter shows its emission, a Lambertian surface albedo * E / pi, anything else and a miss is
+        black (specular transport is not direct light).  state ([ny * nx, DIRECT_REC], in place) continues the estimate over calls through `first`.
+        -> (linear [ny, nx, 3], rgb8 [ny, nx, 3], counters {shadow rays built, occluded}), and the first-hit records [ny * nx, HIT_REC] with
+        return_hits; row 0 = top."""
+        n = max(nx, 0) * max(ny, 0)
+        lin, rgb8, cnt = np.zeros((max(ny, 0), max(nx, 0), 3), np.float64), np.zeros((max(ny, 0), max(nx, 0), 3), np.uint8), np.zeros(2, np.uint64)
+        hits = np.zeros((n, _ffi.HIT_REC), np.float64) if return_hits else None
+        if state is not None and (not isinstance(state, np.ndarray) or state.dtype != np.float64 or not state.flags.c_contiguous
+                                  or state.shape != (n, _ffi.DIRECT_REC)):
+            raise ValueError("state must be a C-contiguous float64 array [ny * nx, %d]" % _ffi.DIRECT_REC)
+        check(_ffi.lib().rtmi_render_direct(self.handle, _PRECISION[precision], int(nx), int(ny), int(n_samples), int(first), int(seed), ptr(state), ptr(lin),
+                                            ptr(rgb8), ptr(hits), ptr(cnt)))
+        return (lin, rgb8, cnt, hits) if return_hits else (lin, rgb8, cnt)
+
+    def render_direct_device(self, nx, ny, n_samples, out_linear, out_rgb8=None, out_hits=None, out_counters=None, first=0, seed=RENDER_SEED, state=None,
+                             precision="f64", stream=None):
+        """render_direct on HBM-resident buffers (out_linear float64 [ny * nx, 3]; the others may be None); asynchronous on `stream`"""
+        check(_ffi.lib().rtmi_render_direct_device(self.handle, _PRECISION[precision], int(nx), int(ny), int(n_samples), int(first), int(seed), ptr(state),
+                                                   ptr(out_linear), ptr(out_rgb8), ptr(out_hits), ptr(out_counters), ptr(stream)))
+
     # ---- probes ------------------------------------------------------------------------------------------
     def probe_hit(self, rays, t_min=T_MIN, t_max=T_MAX, precision="f64"):
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
@@ -1399,6 +1475,38 @@ def _ao_name(name):
     return root + ".ao" + ext
 
 
+def _direct_flags(argv):
+    """-> (the other arguments, samples or None): --direct N or --direct=N, checked here, before any device work"""
+    rest, samples = [], None
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        key, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") else (a, None)
+        i += 1
+        if key != "--direct":
+            rest.append(a)
+            continue
+        if val is None:
+            if i >= len(argv):
+                raise SystemExit("--direct needs a number of samples per light")
+            val = argv[i]
+            i += 1
+        try:
+            samples = int(val)
+        except ValueError:
+            raise SystemExit("--direct %r is not a number of samples" % val)
+        if samples <= 0:
+            raise SystemExit("--direct takes a positive number of samples (got %d)" % samples)
+    return rest, samples
+
+
+def _direct_name(name):
+    """x.png -> x.direct.png: the directly lit view is written next to the frame"""
+    import os
+    root, ext = os.path.splitext(name)
+    return root + ".direct" + ext
+
+
 def _denoised_name(name):
     """x.png -> x.denoised.png: the filtered image is written next to the unfiltered one"""
     import os
@@ -1460,9 +1568,12 @@ def main(argv=None):
     --ao N [RADIUS] also writes the view's ambient occlusion (DeviceScene.ambient_occlusion: N cosine-weighted any-hit rays of length RADIUS, default
     1.0, from the first hit under every pixel centre) as a grey image, name.ao.ext, beside the frame.  It does not combine with --orbit or --panorama.
     --ao-device N [RADIUS] writes the same kind of image through DeviceScene.ambient_occlusion_device: the rays are generated on the device (the disk
-    sampler's directions, not --ao's: the same estimate from other rays).  It takes the place of --ao."""
+    sampler's directions, not --ao's: the same estimate from other rays).  It takes the place of --ao.
+    --direct N also writes the view lit directly (DeviceScene.render_direct: N shadow rays per first hit towards every area light the scene holds,
+    sampled on the device) as name.direct.ext, beside the frame.  It does not combine with --orbit or --panorama."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
+    argv, direct = _direct_flags(argv)
     argv, ao = _ao_flags(argv)
     argv, ao_device = _ao_flags(argv, "--ao-device")
     if ao is not None and ao_device is not None:
@@ -1473,6 +1584,8 @@ def main(argv=None):
     argv, orbit_views = _orbit_flags(argv)
     if ao is not None and (panorama or orbit_views is not None):
         raise SystemExit("--ao does not combine with --orbit or --panorama")
+    if direct is not None and (panorama or orbit_views is not None):
+        raise SystemExit("--direct does not combine with --orbit or --panorama")
     argv, accumulate = _accumulate_flags(argv, orbit_views)
     argv, adaptive_denoised = _adaptive_denoised_flags(argv)
     if adaptive_denoised is not None and not any(a.split("=", 1)[0] == "--denoise" for a in argv):
@@ -1582,6 +1695,13 @@ def main(argv=None):
             ds.close()
         grey = np.floor(255.0 * vis + 0.5).astype(np.uint8)
         _save_image(_ao_name(name), np.ascontiguousarray(np.repeat(grey[:, :, None], 3, axis=2)))
+    if direct is not None:
+        ds = DeviceScene(sc)
+        try:
+            lit = ds.render_direct(nx, ny, direct)[1]
+        finally:
+            ds.close()
+        _save_image(_direct_name(name), lit)
     return 0
 
 

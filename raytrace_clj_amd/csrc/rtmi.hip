@@ -1342,12 +1342,22 @@ struct QueryParams {
     unsigned src_first;
     unsigned src_nx, src_ny;   // the view of SRC_PIXEL and of src_view_camera
     unsigned src_view_camera;  // SRC_HEMISPHERE, no view array: point g is pixel g of the src_nx x src_ny view and its view ray that pixel's centre ray, built again
+    // SRC_LIGHT (never read by another source): item m = (g * n_samples + k) * src_n_lights + l of the pass, whose first point is point src_g0 of the call
+    const double *src_lights;  // [src_n_lights][kLightRec]: kind, 5 geometry doubles, area, Le.rgb
+    double *contrib;           // [total_items][3]: Le * w where the ray was built and is not occluded, else +0.0; or null
+    unsigned src_n_lights;
+    unsigned src_g0;           // enters the key and the pixel of src_view_camera; src_hits, src_view, out_rays, occluded and contrib are the pass's own
+    unsigned src_n_mats;       // src_lambert: a record whose material index is outside [0, src_n_mats) yields no ray
+    unsigned src_lambert;      // only points on a RTMI_MAT_LAMBERTIAN material yield rays
 };
+constexpr int kLightRec = 10;
 
 // Where a lane's ray comes from.  SRC_MEMORY: row m of qp.rays.  The others build it in registers, in FP64 whatever R is, by the rules of rtmi.h
 // (rtmi_occlusion_hemisphere, rtmi_occlusion_targets, rtmi_ambient_occlusion): every product, sum and quotient one IEEE operation in the header's order,
 // so that numpy restates them bit for bit; the seven doubles then go through load_ray as if they had been read.
-enum { SRC_MEMORY = 0, SRC_HEMISPHERE = 1, SRC_TARGETS = 2, SRC_PIXEL = 3 };
+// SRC_LIGHT: towards a sampled point of an area light, by the light rule of rtmi.h (rtmi_direct_irradiance); the lane writes the sample's
+// contribution before the search and zeroes it behind the search if the ray is occluded.
+enum { SRC_MEMORY = 0, SRC_HEMISPHERE = 1, SRC_TARGETS = 2, SRC_PIXEL = 3, SRC_LIGHT = 4 };
 
 // pixel m of an nx x ny view, row-major from the top, through its centre from the camera the scene holds on the device (DeviceScene.pixel_centre_rays)
 __device__ inline void pixel_centre_ray(SceneRef sc, unsigned m, unsigned nx, unsigned ny, double *q) {
@@ -1405,6 +1415,76 @@ template <int SRC> __device__ inline bool generate_ray(SceneRef sc, const QueryP
     return ok;
 }
 
+// SRC_LIGHT: the shadow ray of item m = (g * n_samples + k) * n_lights + l -> q[7] and c[3] = Le * w, w = ((cp cl) / d2^2) area, what the item contributes if
+// the ray reaches its light; false: the item yields no ray (q and c are zeros).  Every lane of the wave calls: a sphere light's disk point comes from the
+// cooperative sampler, and a wave holds lights of both kinds -- so every lane enters the disk rounds, the sphere lanes with `need`, and the two uniforms of
+// a rectangle are read off the key (draws 0 and 1) without a stream.  As in generate_ray the rounds stand before the frame is built (no operation changes).
+__device__ inline bool generate_light_ray(SceneRef sc, const QueryParams &qp, bool in_range, unsigned m, double *q, double *c) {
+    const double big = __builtin_inf();
+    const unsigned nl = qp.src_n_lights;
+    const unsigned g = m / qp.group, r = m - g * qp.group, k = r / nl, l = r - k * nl;
+    const unsigned gg = qp.src_g0 + g; // the point's index in the call
+    const double *rec = qp.src_hits + (size_t)g * RTMI_HIT_REC;
+    const double *L = qp.src_lights + (size_t)l * kLightRec;
+    const int kind = (int)L[0];
+    const bool sphere = kind == RTMI_PRIM_SPHERE || kind == RTMI_PRIM_UVSPHERE;
+    bool ok;
+    {
+        const double ax = rec[3], ay = rec[4], az = rec[5], bx = rec[6], by = rec[7], bz = rec[8];
+        ok = in_range && rec[0] != 0.0 && ::fabs(ax) < big && ::fabs(ay) < big && ::fabs(az) < big // finite: neither inf nor NaN
+             && ::fabs(bx) < big && ::fabs(by) < big && ::fabs(bz) < big && dot3(bx, by, bz, bx, by, bz) > 0.0;
+    }
+    if (qp.src_lambert) {
+        const double mf = rec[11];
+        const bool known = ok && mf >= 0.0 && mf < (double)qp.src_n_mats;
+        ok = known && sc.mat_kind[known ? (int)mf : 0] == RTMI_MAT_LAMBERTIAN;
+    }
+    Path<double> G; // the sampler's own stream; the ray's (what a ConstantMedium draws from) is load_ray's
+    const u64 key = sample_key(qp.src_seed, (u64)gg * (u64)nl + (u64)l, (u64)qp.src_first + (u64)k);
+    seed_stream(G, key, 0u);
+    double x = 0.0, y = 0.0;
+    rand_in_unit_disk_wave<double>(G, ok && sphere, false, x, y);
+    // Only the verdict, the disk point and the key cross the cooperative rounds: the record and the light are read again behind them (the fence keeps
+    // the compiler from holding thirty doubles in registers through the rounds instead).
+    asm volatile("" ::: "memory");
+    const double u0 = Real<double>::uniform(mix64(key + RTMI_GOLD)), u1 = Real<double>::uniform(mix64(key + 2ull * RTMI_GOLD)); // draws 0 and 1
+    const double px = rec[3], py = rec[4], pz = rec[5];
+    double nx = rec[6], ny = rec[7], nz = rec[8];
+    const double len2 = dot3(nx, ny, nz, nx, ny, nz);
+    const double g0 = L[1], g1 = L[2], g2 = L[3], g3 = L[4], g4 = L[5], area = L[6];
+    double time = qp.src_time, wx = 0.0, wy = 0.0, wz = 0.0;
+    bool sided = false;
+    if (qp.src_view) { const double *v = qp.src_view + (size_t)g * 7; wx = v[3]; wy = v[4]; wz = v[5]; time = v[6]; sided = true; }
+    else if (qp.src_view_camera) { double v[7]; pixel_centre_ray(sc, gg, qp.src_nx, qp.src_ny, v); wx = v[3]; wy = v[4]; wz = v[5]; time = v[6]; sided = true; }
+    if (sided && dot3(nx, ny, nz, wx, wy, wz) > 0.0) { nx = -nx; ny = -ny; nz = -nz; } // the normal points away from the viewer: the other side
+    const double len = ::sqrt(len2);
+    nx = nx / len; ny = ny / len; nz = nz / len;
+    double qx, qy, qz, sx, sy, sz;
+    if (sphere) { // Marsaglia: a uniform point of the unit disk -> a uniform point of the unit sphere
+        const double S = x * x + y * y, root = ::sqrt(1.0 - S);
+        sx = (2.0 * x) * root; sy = (2.0 * y) * root; sz = 1.0 - 2.0 * S;
+        qx = g0 + g3 * sx; qy = g1 + g3 * sy; qz = g2 + g3 * sz;
+    } else {
+        const double a = g0 + u0 * (g2 - g0), b = g1 + u1 * (g3 - g1);
+        sx = kind == RTMI_PRIM_RECT_YZ ? 1.0 : 0.0; sy = kind == RTMI_PRIM_RECT_XZ ? 1.0 : 0.0; sz = kind == RTMI_PRIM_RECT_XY ? 1.0 : 0.0;
+        if (kind == RTMI_PRIM_RECT_XY) { qx = a; qy = b; qz = g4; }
+        else if (kind == RTMI_PRIM_RECT_XZ) { qx = a; qy = g4; qz = b; }
+        else { qx = g4; qy = a; qz = b; }
+    }
+    const double dx = qx - px, dy = qy - py, dz = qz - pz;
+    const double d2 = dot3(dx, dy, dz, dx, dy, dz), cp = dot3(nx, ny, nz, dx, dy, dz), sd = dot3(sx, sy, sz, dx, dy, dz), cl = ::fabs(sd);
+    if (sphere) { // the far side of a sphere seen from outside
+        const double ex = px - g0, ey = py - g1, ez = pz - g2;
+        if (dot3(ex, ey, ez, ex, ey, ez) > g3 * g3 && sd > 0.0) ok = false;
+    }
+    ok = ok && d2 > 0.0 && cp > 0.0 && cl > 0.0;
+    const double w = ((cp * cl) / (d2 * d2)) * area;
+    c[0] = ok ? L[7] * w : 0.0; c[1] = ok ? L[8] * w : 0.0; c[2] = ok ? L[9] * w : 0.0;
+    q[0] = ok ? px : 0.0; q[1] = ok ? py : 0.0; q[2] = ok ? pz : 0.0;
+    q[3] = ok ? dx : 0.0; q[4] = ok ? dy : 0.0; q[5] = ok ? dz : 0.0; q[6] = ok ? time : 0.0;
+    return ok;
+}
+
 template <typename R, int VARIANT, bool EXT = false, int MSEQ = 0, bool ANY = false, bool COUNT = false, int SRC = SRC_MEMORY>
 __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WAVES) : RTMI_MIN_WAVES) query_kernel(ScenePtr scp, QueryParams qp) {
     static_assert(SRC == SRC_MEMORY || (SRC == SRC_PIXEL) != ANY, "the pixel-centre source feeds the closest-hit search, the point sources the any-hit search");
@@ -1436,7 +1516,12 @@ __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WA
         if (SRC == SRC_MEMORY) load_ray<R>(qp.rays + (size_t)row * 7, P);
         else { // a point that yields no ray: an idle lane for this trip, its flag 0
             double q[7];
-            active = generate_ray<SRC>(sc, qp, in_range, row, q);
+            if constexpr (SRC == SRC_LIGHT) {
+                // the contribution of a ray that reaches its light is written now (no weight is alive across the search), +0.0 where no ray is built
+                double c[3];
+                active = generate_light_ray(sc, qp, in_range, row, q, c);
+                if (in_range && qp.contrib) { double *o = qp.contrib + (size_t)m * 3; o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; }
+            } else active = generate_ray<SRC>(sc, qp, in_range, row, q);
             if (in_range && qp.out_rays) {
                 double *o = qp.out_rays + (size_t)m * 7;
 #pragma unroll
@@ -1455,6 +1540,10 @@ __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WA
         n_hit += (unsigned)__popcll(hit_mask);
         if (ANY) {
             if (in_range && qp.occluded) qp.occluded[m] = hit ? 1 : 0;
+            if (SRC == SRC_LIGHT && hit && qp.contrib) { // step 7 of the light rule: an occluded ray takes its contribution back
+                double *o = qp.contrib + (size_t)m * 3;
+                o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
+            }
             if (qp.count) {
                 const unsigned g = row / qp.group;
                 const unsigned g_prev = (unsigned)__shfl_up((int)g, 1);
@@ -1788,6 +1877,7 @@ struct rtmi_ctx {
     DevBuf dn_planes; // rtmi_denoise*: the filter's planes (two colour + variance sets, the feature planes)
     DevBuf rays_ws;   // rtmi_render_rays*: the per-ray radiance nobody asked for (one pass of it)
     DevBuf occ_ws;    // rtmi_ambient_occlusion*: the first-hit records and the per-pixel counts nobody asked for
+    DevBuf direct_ws; // rtmi_direct_irradiance*, rtmi_render_direct*: the light table, then the records and irradiance nobody asked for, then one pass of contributions
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     int events_used = 0;
@@ -2447,7 +2537,7 @@ RTMI_EXPORT int rtmi_test_stage_layout(int32_t n, const uint64_t *elem_bytes, co
 }
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 217; } // 217: occlusion rays generated on the device (rtmi_occlusion_hemisphere*, rtmi_occlusion_targets*, rtmi_ambient_occlusion*); 216: closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*); 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 218; } // 218: direct lighting from the scene's area lights (rtmi_scene_lights, rtmi_direct_irradiance*, rtmi_render_direct*); 217: occlusion rays generated on the device (rtmi_occlusion_hemisphere*, rtmi_occlusion_targets*, rtmi_ambient_occlusion*); 216: closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*); 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -2486,7 +2576,7 @@ RTMI_EXPORT int rtmi_shutdown(rtmi_ctx *c) {
 #endif
     c->samples.release(); c->accum.release(); c->tiles.release(); c->tile_ids.release(); c->counters.release(); c->io.release(); c->multi.release();
     c->prog.release();
-    c->feat_cnt.release(); c->dn_planes.release(); c->rays_ws.release(); c->occ_ws.release();
+    c->feat_cnt.release(); c->dn_planes.release(); c->rays_ws.release(); c->occ_ws.release(); c->direct_ws.release();
     for (hipEvent_t e : {c->ev_done, c->ev_g0, c->ev_g1}) if (e) (void)hipEventDestroy(e);
     if (c->ev_consumed) { (void)hipSetDevice(c->ev_consumed_device); (void)hipEventDestroy(c->ev_consumed); (void)hipSetDevice(c->device); }
     for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -5252,12 +5342,13 @@ int check_query_args(rtmi_scene *s, int precision, long long n, bool dims_ok, co
 // and out_rays of a generated source (SRC != SRC_MEMORY, which reads no d_rays).
 template <typename R, bool ANY, int SRC = SRC_MEMORY>
 int query_impl(rtmi_scene *s, int n, int n_groups, int group, const double *d_rays, const double *d_range, double t_min, double t_max, const u64 *d_keys,
-               unsigned ctr0, double *d_hits, unsigned char *d_occ, int *d_count, u64 *d_cnt, hipStream_t st, const QueryParams *gen = nullptr) {
+               unsigned ctr0, double *d_hits, unsigned char *d_occ, int *d_count, u64 *d_cnt, hipStream_t st, const QueryParams *gen = nullptr,
+               bool keep_counters = false) { // keep_counters: a later pass of one call adds to what its earlier passes counted
     rtmi_ctx *c = s->ctx;
     int rc = c->counters.ensure(8 * sizeof(u64)); // [0..1] the counters when the caller passes no buffer, [2] the work-queue head, [3..4] traversal counters
     if (rc) return rc;
     if (!d_cnt) d_cnt = reinterpret_cast<u64 *>(c->counters.p);
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(u64), st));
+    if (!keep_counters) HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(u64), st));
     if (ANY && d_count) HIP_TRY(hipMemsetAsync(d_count, 0, (size_t)n_groups * sizeof(int), st));
     const bool count = c->count_traversal != 0;
     if (count) {
@@ -5548,5 +5639,364 @@ RTMI_EXPORT int rtmi_ambient_occlusion(rtmi_scene *s, int32_t precision, int32_t
     rc = io.stage();
     if (rc) return rc;
     rc = with_real(precision, [&](auto r) { return ao_impl<decltype(r)>(s, nx, ny, n_dirs, first, radius, seed, d_vis, d_count, d_hits, d_cnt, c->stream); });
+    return rc ? rc : io.finish();
+}
+
+// ---- direct lighting from first hits (rtmi_scene_lights, rtmi_direct_irradiance*, rtmi_render_direct*) -------------------------------------------------
+// query_kernel with SRC_LIGHT: a lane places a point on an area light, builds the shadow ray towards it and writes the item's contribution Le * w at once;
+// after the any-hit search an occluded ray takes its contribution back (zeros), so no weight is alive across the search.  direct_fold_kernel sums a point's contributions in item order.  Which primitives are lights is read off
+// the host-side tables the scene keeps (they follow every edit), and the table of the lights a call samples travels as kernel arguments.
+namespace {
+// the header's eligibility rule for primitive i of the flat arrays
+bool light_eligible(const SceneArrays &a, int i) {
+    const int kind = a.prim_kind[i];
+    const double *g = a.prim_geom + (size_t)i * RTMI_PRIM_STRIDE;
+    if (kind == RTMI_PRIM_SPHERE || kind == RTMI_PRIM_UVSPHERE) { if (!(g[3] > 0.0)) return false; }
+    else if (kind == RTMI_PRIM_RECT_XY || kind == RTMI_PRIM_RECT_XZ || kind == RTMI_PRIM_RECT_YZ) { // both extents non-zero (a NaN is no extent)
+        const double ea = g[2] - g[0], eb = g[3] - g[1];
+        if (!(ea < 0.0 || ea > 0.0) || !(eb < 0.0 || eb > 0.0)) return false;
+    }
+    else return false; // (a RTMI_PRIM_BOUNDARY primitive has another kind value and ends here)
+    if (a.prim_xform && a.prim_xform[2 * (size_t)i + 1] != 0) return false;
+    const int m = a.prim_mat[i];
+    if (m < 0 || m >= a.n_mats || a.mat_kind[m] != RTMI_MAT_DIFFUSE_LIGHT) return false;
+    const int t = a.mat_tex[m];
+    return t >= 0 && t < a.n_tex && a.tex_kind[t] == RTMI_TEX_CONSTANT;
+}
+int list_lights(const SceneArrays &a, int capacity, int32_t *out_prims, int32_t *out_count) {
+    int n = 0;
+    for (int i = 0; i < a.n_prims; ++i)
+        if (light_eligible(a, i)) { if (n < capacity) out_prims[n] = i; ++n; }
+    *out_count = n;
+    return RTMI_OK;
+}
+
+struct LightTable { double rec[RTMI_DIRECT_MAX_LIGHTS * kLightRec]; int n, pad; };
+// one wave stores the table where the query kernels queued behind it read it
+__global__ void __launch_bounds__(64) set_lights_kernel(LightTable t, double *dst) {
+    for (int i = (int)threadIdx.x; i < t.n * kLightRec; i += 64) dst[i] = t.rec[i];
+}
+
+// the lights of a call: the listed primitives, each eligible, or all eligible ones
+int make_light_table(const rtmi_scene *s, int n_lights, const int32_t *light_prims, LightTable &T) {
+    const SceneArrays a = kept_arrays(s);
+    int32_t all[RTMI_DIRECT_MAX_LIGHTS];
+    if (!light_prims) {
+        int32_t count = 0;
+        list_lights(a, RTMI_DIRECT_MAX_LIGHTS, all, &count);
+        if (count > RTMI_DIRECT_MAX_LIGHTS) return fail(RTMI_E_ARG, "the scene holds %d eligible lights, a call samples at most %d: pass a list", count, RTMI_DIRECT_MAX_LIGHTS);
+        n_lights = count; light_prims = all;
+    }
+    T.n = n_lights; T.pad = 0;
+    for (int l = 0; l < n_lights; ++l) {
+        const int i = light_prims[l];
+        if (i < 0 || i >= a.n_prims || !light_eligible(a, i)) return fail(RTMI_E_ARG, "light_prims[%d] = %d is not an eligible light (rtmi_scene_lights)", l, i);
+        const double *g = a.prim_geom + (size_t)i * RTMI_PRIM_STRIDE, *col = a.tex_param + (size_t)a.mat_tex[a.prim_mat[i]] * RTMI_TEX_STRIDE;
+        double *r = T.rec + (size_t)l * kLightRec;
+        const int kind = a.prim_kind[i];
+        const bool sphere = kind == RTMI_PRIM_SPHERE || kind == RTMI_PRIM_UVSPHERE;
+        r[0] = (double)kind;
+        r[1] = g[0]; r[2] = g[1]; r[3] = g[2]; r[4] = g[3]; r[5] = sphere ? 0.0 : g[4];
+        r[6] = sphere ? 0x1.921fb54442d18p+3 * (g[3] * g[3]) : std::fabs((g[2] - g[0]) * (g[3] - g[1]));
+        r[7] = col[0]; r[8] = col[1]; r[9] = col[2];
+    }
+    return RTMI_OK;
+}
+
+// One lane per point of the pass (points [g0, g0 + n) of the call): the point's contributions in item order, starting FROM the first item of its first
+// sample, then E = sum * (1 / samples).  state (may be null): {sum.rgb, samples}, read when first > 0 and written back; without one first is 0.
+__global__ void __launch_bounds__(kBlock) direct_fold_kernel(const double *__restrict__ contrib, int g0, int n, int group, int first, int n_samples,
+                                                             double *__restrict__ state, double *__restrict__ E) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= n) return;
+    const size_t g = (size_t)g0 + (size_t)gid;
+    double acc[3] = {0.0, 0.0, 0.0};
+    double *rec = state ? state + g * RTMI_DIRECT_REC : nullptr;
+    if (rec && first > 0) { acc[0] = rec[0]; acc[1] = rec[1]; acc[2] = rec[2]; }
+    const double *row = contrib + (size_t)gid * (size_t)group * 3;
+    for (int i = 0; i < group; ++i, row += 3) {
+        if (first == 0 && i == 0) { acc[0] = row[0]; acc[1] = row[1]; acc[2] = row[2]; }
+        else { acc[0] = acc[0] + row[0]; acc[1] = acc[1] + row[1]; acc[2] = acc[2] + row[2]; }
+    }
+    const int samples = first + n_samples;
+    if (rec) { rec[0] = acc[0]; rec[1] = acc[1]; rec[2] = acc[2]; rec[3] = (double)samples; }
+    const double inv = 1.0 / (double)samples;
+    E[g * 3] = acc[0] * inv; E[g * 3 + 1] = acc[1] * inv; E[g * 3 + 2] = acc[2] * inv;
+}
+
+// rtmi_render_direct's resolve: emitters show their emission, Lambertian surfaces (albedo * E) * INV_PI, everything else and a miss black
+template <typename R, bool EXT>
+__global__ void __launch_bounds__(kBlock) direct_resolve_kernel(ScenePtr scp, const double *__restrict__ hits, const double *__restrict__ E, int n, int n_mats,
+                                                                double *__restrict__ out_linear, unsigned char *__restrict__ out_rgb8) {
+    SceneRef sc = *scp;
+    const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (p >= n) return;
+    const double *rec = hits + (size_t)p * RTMI_HIT_REC;
+    double o[3] = {0.0, 0.0, 0.0};
+    const double mf = rec[11];
+    if (rec[0] != 0.0 && mf >= 0.0 && mf < (double)n_mats) {
+        const int mat = (int)mf, mk = sc.mat_kind[mat];
+        if (mk == RTMI_MAT_DIFFUSE_LIGHT || mk == RTMI_MAT_LAMBERTIAN) {
+            R r, g, b;
+            tex_sample<R, EXT>(sc, sc.mat_tex[mat], (R)rec[9], (R)rec[10], (R)rec[3], (R)rec[4], (R)rec[5], r, g, b);
+            if (mk == RTMI_MAT_DIFFUSE_LIGHT) { o[0] = (double)r; o[1] = (double)g; o[2] = (double)b; }
+            else {
+                const double inv_pi = 0x1.45f306dc9c883p-2;
+                o[0] = ((double)r * E[(size_t)p * 3]) * inv_pi; o[1] = ((double)g * E[(size_t)p * 3 + 1]) * inv_pi; o[2] = ((double)b * E[(size_t)p * 3 + 2]) * inv_pi;
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (out_linear) out_linear[(size_t)p * 3 + c] = o[c];
+        if (out_rgb8) out_rgb8[(size_t)p * 3 + c] = quantise8(o[c]);
+    }
+}
+
+// what both entries check first, in the header's order; n_points = nx * ny for the whole pass
+int check_direct_args(rtmi_scene *s, int precision, long long n_points, bool dims_ok, int n_samples, int first, int n_lights, bool listed, const void *hits,
+                      const void *out) {
+    if (!dims_ok || n_samples <= 0 || first < 0) return fail(RTMI_E_ARG, "n_points (nx, ny), first must be >= 0 and n_samples > 0 (got %lld %d %d)", n_points, first, n_samples);
+    if (listed && (n_lights < 0 || n_lights > RTMI_DIRECT_MAX_LIGHTS)) return fail(RTMI_E_ARG, "n_lights must be in [0, %d] (got %d)", RTMI_DIRECT_MAX_LIGHTS, n_lights);
+    if (n_points > kRaysMax) return fail(RTMI_E_ARG, "%lld points exceed 2^31 - 64", n_points);
+    if (n_points > 0 && !hits) return fail(RTMI_E_ARG, "hits is NULL");
+    if (n_points > 0 && !out) return fail(RTMI_E_ARG, "out_irradiance / out_linear is NULL");
+    return check_query_args(s, precision, 0, true, nullptr, true); // the handle, the precision, RTMI_F32 on a mixed-kind scene
+}
+// rtmi_render_direct*'s resolve samples textures: what rtmi_render refuses for their tables, it refuses
+int check_direct_textures(const rtmi_scene *s) {
+    if (s->uses_perlin && !s->have_perlin) return fail(RTMI_E_STATE, "the scene holds a Perlin texture: call rtmi_scene_set_perlin first");
+    if (s->max_image >= s->dev.n_images) return fail(RTMI_E_STATE, "the scene holds an ImageMap with index %d: call rtmi_scene_set_images first", s->max_image);
+    return RTMI_OK;
+}
+int check_direct_items(long long n_points, int n_samples, int n_lights) {
+    if ((long long)n_samples * n_lights > kRaysMax || n_points * n_samples * n_lights > kRaysMax)
+        return fail(RTMI_E_ARG, "%lld points x %d samples x %d lights exceed 2^31 - 64 items", n_points, n_samples, n_lights);
+    return RTMI_OK;
+}
+
+struct DirectView { const double *d_view; bool camera; int nx, ny; }; // the rays that found the points: an array, the pixel-centre rays built again, or none
+
+// bytes of c->direct_ws: the light table, then whatever the caller lets the context hold, then one pass of contributions
+constexpr size_t kLightTableBytes = sizeof(double) * RTMI_DIRECT_MAX_LIGHTS * kLightRec;
+
+// The launches of the light passes on `st`, every pointer a device pointer: the table, then passes of whole points, each one query_kernel launch and its fold.
+// d_contrib: the caller's [items][3] (one pass into it) or null: ws_contrib holds per_pass points.
+template <typename R>
+int direct_impl(rtmi_scene *s, int n_points, const double *d_hits, const DirectView &view, const LightTable &T, int n_samples, int first, u64 seed, double time,
+                int lambert_only, double *d_state, double *d_E, double *d_contrib, unsigned char *d_occ, double *d_rays, u64 *d_cnt, double *ws_contrib,
+                int per_pass, hipStream_t st) {
+    rtmi_ctx *c = s->ctx;
+    double *d_lights = reinterpret_cast<double *>(c->direct_ws.p);
+    hipLaunchKernelGGL(set_lights_kernel, dim3(1), dim3(64), 0, st, T, d_lights);
+    HIP_TRY(hipGetLastError());
+    const int group = n_samples * T.n;
+    QueryParams g{};
+    g.src_lights = d_lights; g.src_n_lights = (unsigned)T.n; g.src_n_mats = (unsigned)s->n_mats; g.src_lambert = lambert_only ? 1u : 0u;
+    g.src_first = (unsigned)first; g.src_seed = seed; g.src_time = time;
+    g.src_view_camera = view.camera ? 1u : 0u; g.src_nx = (unsigned)view.nx; g.src_ny = (unsigned)view.ny;
+    for (int g0 = 0; g0 < n_points; g0 += per_pass) {
+        const int ng = std::min(per_pass, n_points - g0);
+        const size_t row0 = (size_t)g0 * (size_t)group;
+        g.src_g0 = (unsigned)g0;
+        g.src_hits = d_hits + (size_t)g0 * RTMI_HIT_REC;
+        g.src_view = view.d_view ? view.d_view + (size_t)g0 * 7 : nullptr;
+        g.out_rays = d_rays ? d_rays + row0 * 7 : nullptr;
+        g.contrib = d_contrib ? d_contrib + row0 * 3 : ws_contrib;
+        const int pairs_before = c->events_used; // RTMI_FLAG_TIMING: did this launch open an interval of its own? (none past the 8192nd)
+        int rc = query_impl<R, true, SRC_LIGHT>(s, ng * group, ng, group, nullptr, nullptr, 0.001, 1.0 - 0.001, nullptr, 0u, nullptr, d_occ ? d_occ + row0 : nullptr,
+                                                nullptr, d_cnt, st, &g, g0 > 0);
+        if (rc) return rc;
+        const bool timed = c->events_used > pairs_before;
+        hipLaunchKernelGGL(direct_fold_kernel, dim3((unsigned)((ng + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g.contrib, g0, ng, group, d_state ? first : 0,
+                           n_samples, d_state, d_E);
+        HIP_TRY(hipGetLastError());
+        if (timed) { rc = close_timed_fold(c, st); if (rc) return rc; } // its fold interval ends behind the fold (query_impl closed an empty one)
+    }
+    return RTMI_OK;
+}
+
+// points of one pass and the bytes of its contributions in the workspace (none with the caller's out_contrib)
+int direct_pass(const rtmi_ctx *c, int n_points, int group, bool own_contrib, size_t *bytes) {
+    if (own_contrib) { *bytes = 0; return n_points; }
+    const int64_t point_bytes = (int64_t)group * 3 * (int64_t)sizeof(double);
+    const int per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(n_points, c->workspace_bytes / point_bytes));
+    *bytes = (size_t)per_pass * (size_t)point_bytes;
+    return per_pass;
+}
+
+// Zero lights: nothing to sample.  Without a state the irradiance is zeros and nothing is launched.  With one, the fold runs over groups of no items: a
+// point's sums carry over (zeros for a first chunk), its samples grow by n_samples and E = sum * (1 / samples), as if every sample had built no ray.
+int direct_nothing(double *d_state, double *d_E, int n_points, int first, int n_samples, u64 *d_cnt, hipStream_t st) {
+    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(u64), st));
+    if (!d_state) { HIP_TRY(hipMemsetAsync(d_E, 0, (size_t)n_points * 3 * sizeof(double), st)); return RTMI_OK; }
+    hipLaunchKernelGGL(direct_fold_kernel, dim3((unsigned)((n_points + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, static_cast<const double *>(nullptr), 0, n_points,
+                       0, first, n_samples, d_state, d_E);
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+
+int direct_irradiance_impl(rtmi_scene *s, int precision, int n_points, const double *d_hits, const double *d_view, const LightTable &T, int n_samples, int first,
+                           u64 seed, double time, int lambert_only, double *d_state, double *d_E, double *d_contrib, unsigned char *d_occ, double *d_rays,
+                           u64 *d_cnt, hipStream_t st) {
+    rtmi_ctx *c = s->ctx;
+    if (T.n == 0) return direct_nothing(d_state, d_E, n_points, first, n_samples, d_cnt, st);
+    size_t pass_bytes = 0;
+    const int per_pass = direct_pass(c, n_points, n_samples * T.n, d_contrib != nullptr, &pass_bytes);
+    const int rc = c->direct_ws.ensure(kLightTableBytes + pass_bytes);
+    if (rc) return rc;
+    double *ws_contrib = reinterpret_cast<double *>(static_cast<char *>(c->direct_ws.p) + kLightTableBytes);
+    const DirectView view{d_view, false, 0, 0};
+    return with_real(precision, [&](auto r) {
+        return direct_impl<decltype(r)>(s, n_points, d_hits, view, T, n_samples, first, seed, time, lambert_only, d_state, d_E, d_contrib, d_occ, d_rays, d_cnt,
+                                        ws_contrib, per_pass, st);
+    });
+}
+
+// The whole pass on `st`: the first hits of the pixel-centre rays, the light passes with those rays (built again from the camera) as the view, the resolve.
+// d_hits null: the records live in the context's workspace, as the irradiance does.
+template <typename R>
+int render_direct_impl(rtmi_scene *s, int nx, int ny, const LightTable &T, int n_samples, int first, u64 seed, double *d_state, double *d_lin, unsigned char *d_q,
+                       double *d_hits, u64 *d_cnt, hipStream_t st) {
+    rtmi_ctx *c = s->ctx;
+    const size_t n = (size_t)nx * (size_t)ny, hit_bytes = d_hits ? 0 : n * RTMI_HIT_REC * sizeof(double), e_bytes = n * 3 * sizeof(double);
+    size_t pass_bytes = 0;
+    const int per_pass = T.n ? direct_pass(c, (int)n, n_samples * T.n, false, &pass_bytes) : 0;
+    int rc = c->direct_ws.ensure(kLightTableBytes + hit_bytes + e_bytes + pass_bytes);
+    if (rc) return rc;
+    char *ws = static_cast<char *>(c->direct_ws.p) + kLightTableBytes;
+    if (!d_hits) d_hits = reinterpret_cast<double *>(ws);
+    double *d_E = reinterpret_cast<double *>(ws + hit_bytes), *ws_contrib = reinterpret_cast<double *>(ws + hit_bytes + e_bytes);
+    QueryParams g{};
+    g.src_nx = (unsigned)nx; g.src_ny = (unsigned)ny;
+    rc = query_impl<R, false, SRC_PIXEL>(s, (int)n, 0, 1, nullptr, nullptr, 0.001, 3.4028234663852886e38, nullptr, 0u, d_hits, nullptr, nullptr, nullptr, st, &g);
+    if (rc) return rc;
+    if (T.n == 0) rc = direct_nothing(d_state, d_E, (int)n, first, n_samples, d_cnt, st);
+    else {
+        const DirectView view{nullptr, true, nx, ny};
+        rc = direct_impl<R>(s, (int)n, d_hits, view, T, n_samples, first, seed, 0.0, 1, d_state, d_E, nullptr, nullptr, nullptr, d_cnt, ws_contrib, per_pass, st);
+    }
+    if (rc) return rc;
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
+    if (s->dev.has_ext) hipLaunchKernelGGL((direct_resolve_kernel<double, true>), grid, dim3(kBlock), 0, st, s->d_dev, d_hits, d_E, (int)n, s->n_mats, d_lin, d_q);
+    else hipLaunchKernelGGL((direct_resolve_kernel<R, false>), grid, dim3(kBlock), 0, st, s->d_dev, d_hits, d_E, (int)n, s->n_mats, d_lin, d_q);
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_scene_lights(rtmi_scene *s, int32_t capacity, int32_t *out_prims, int32_t *out_count) {
+    if (capacity < 0 || !out_count || (capacity > 0 && !out_prims)) return fail(RTMI_E_ARG, "bad arguments");
+    if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
+    return list_lights(kept_arrays(s), capacity, out_prims, out_count);
+}
+
+RTMI_EXPORT int rtmi_test_scene_lights(int32_t n_prims, const int32_t *prim_kind, const double *prim_geom, const int32_t *prim_mat, int32_t n_mats,
+                                       const int32_t *mat_kind, const int32_t *mat_tex, int32_t n_tex, const int32_t *tex_kind, const int32_t *prim_xform,
+                                       int32_t capacity, int32_t *out_prims, int32_t *out_count) {
+    if (capacity < 0 || !out_count || (capacity > 0 && !out_prims)) return fail(RTMI_E_ARG, "bad arguments");
+    if (n_prims < 0 || n_mats < 0 || n_tex < 0 || (n_prims > 0 && (!prim_kind || !prim_geom || !prim_mat)) || (n_mats > 0 && (!mat_kind || !mat_tex)) || (n_tex > 0 && !tex_kind))
+        return fail(RTMI_E_ARG, "a count is negative or an array is NULL");
+    const SceneArrays a{n_prims, prim_kind, prim_geom, prim_mat, n_mats, mat_kind, mat_tex, nullptr, n_tex, tex_kind, nullptr, nullptr,
+                        0, nullptr, nullptr, prim_xform, 0, nullptr, nullptr};
+    return list_lights(a, capacity, out_prims, out_count);
+}
+
+RTMI_EXPORT int rtmi_direct_irradiance_device(rtmi_scene *s, int32_t precision, int32_t n_points, const void *d_hits, const void *d_view, int32_t n_lights,
+                                              const int32_t *light_prims, int32_t n_samples, int32_t first, uint64_t seed, double time, int32_t lambert_only,
+                                              void *d_state, void *d_out_irradiance, void *d_out_contrib, void *d_out_occluded, void *d_out_rays,
+                                              void *d_out_counters, void *stream) {
+    int rc = check_direct_args(s, precision, n_points, n_points >= 0, n_samples, first, n_lights, light_prims != nullptr, d_hits, d_out_irradiance);
+    if (rc || n_points == 0) return rc;
+    LightTable T;
+    rc = make_light_table(s, n_lights, light_prims, T);
+    if (!rc) rc = check_direct_items(n_points, n_samples, T.n);
+    if (rc) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    return direct_irradiance_impl(s, precision, n_points, reinterpret_cast<const double *>(d_hits), reinterpret_cast<const double *>(d_view), T, n_samples, first,
+                                  seed, time, lambert_only, reinterpret_cast<double *>(d_state), reinterpret_cast<double *>(d_out_irradiance),
+                                  reinterpret_cast<double *>(d_out_contrib), reinterpret_cast<unsigned char *>(d_out_occluded),
+                                  reinterpret_cast<double *>(d_out_rays), reinterpret_cast<u64 *>(d_out_counters), stream_of(c, stream));
+}
+
+RTMI_EXPORT int rtmi_direct_irradiance(rtmi_scene *s, int32_t precision, int32_t n_points, const double *hits, const double *view, int32_t n_lights,
+                                       const int32_t *light_prims, int32_t n_samples, int32_t first, uint64_t seed, double time, int32_t lambert_only,
+                                       double *state, double *out_irradiance, double *out_contrib, uint8_t *out_occluded, double *out_rays,
+                                       uint64_t *out_counters) {
+    int rc = check_direct_args(s, precision, n_points, n_points >= 0, n_samples, first, n_lights, light_prims != nullptr, hits, out_irradiance);
+    if (rc || n_points == 0) return rc;
+    LightTable T;
+    rc = make_light_table(s, n_lights, light_prims, T);
+    if (!rc) rc = check_direct_items(n_points, n_samples, T.n);
+    if (rc) return rc;
+    if (state && first > 0)
+        for (int g = 0; g < n_points; ++g)
+            if (state[(size_t)g * RTMI_DIRECT_REC + 3] != (double)first)
+                return fail(RTMI_E_STATE, "point %d's record holds %g samples, first is %d", g, state[(size_t)g * RTMI_DIRECT_REC + 3], first);
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t np = (size_t)n_points, n = np * (size_t)n_samples * (size_t)T.n;
+    HostIo io(c);
+    double *d_hits, *d_view, *d_state, *d_E, *d_contrib, *d_rays;
+    unsigned char *d_occ;
+    u64 *d_cnt;
+    io.in(&d_hits, np * RTMI_HIT_REC, hits); io.in(&d_view, np * 7, view);
+    io.plane(&d_state, np * RTMI_DIRECT_REC, state != nullptr, first > 0 ? state : nullptr, state); // a first chunk (first = 0) reads no records
+    io.work(&d_E, np * 3, out_irradiance); io.out(&d_contrib, n * 3, n ? out_contrib : nullptr); io.out(&d_occ, n, n ? out_occluded : nullptr);
+    io.out(&d_rays, n * 7, n ? out_rays : nullptr); io.work(&d_cnt, 2, out_counters);
+    rc = io.stage();
+    if (rc) return rc;
+    rc = direct_irradiance_impl(s, precision, n_points, d_hits, d_view, T, n_samples, first, seed, time, lambert_only, d_state, d_E, d_contrib, d_occ, d_rays, d_cnt,
+                                c->stream);
+    return rc ? rc : io.finish();
+}
+
+RTMI_EXPORT int rtmi_render_direct_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t n_samples, int32_t first, uint64_t seed, void *d_state,
+                                          void *d_out_linear, void *d_out_rgb8, void *d_out_hits, void *d_out_counters, void *stream) {
+    int rc = check_direct_args(s, precision, (long long)nx * ny, nx >= 0 && ny >= 0, n_samples, first, 0, false, d_out_linear, d_out_linear);
+    if (rc || nx == 0 || ny == 0) return rc;
+    rc = check_direct_textures(s);
+    if (rc) return rc;
+    LightTable T;
+    rc = make_light_table(s, 0, nullptr, T);
+    if (!rc) rc = check_direct_items((long long)nx * ny, n_samples, T.n);
+    if (rc) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream_of(c, stream);
+    return with_real(precision, [&](auto r) {
+        return render_direct_impl<decltype(r)>(s, nx, ny, T, n_samples, first, seed, reinterpret_cast<double *>(d_state), reinterpret_cast<double *>(d_out_linear),
+                                               reinterpret_cast<unsigned char *>(d_out_rgb8), reinterpret_cast<double *>(d_out_hits),
+                                               reinterpret_cast<u64 *>(d_out_counters), st);
+    });
+}
+
+RTMI_EXPORT int rtmi_render_direct(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t n_samples, int32_t first, uint64_t seed, double *state,
+                                   double *out_linear, uint8_t *out_rgb8, double *out_hits, uint64_t *out_counters) {
+    int rc = check_direct_args(s, precision, (long long)nx * ny, nx >= 0 && ny >= 0, n_samples, first, 0, false, out_linear, out_linear);
+    if (rc || nx == 0 || ny == 0) return rc;
+    rc = check_direct_textures(s);
+    if (rc) return rc;
+    LightTable T;
+    rc = make_light_table(s, 0, nullptr, T);
+    if (!rc) rc = check_direct_items((long long)nx * ny, n_samples, T.n);
+    if (rc) return rc;
+    const size_t n = (size_t)nx * (size_t)ny;
+    if (state && first > 0)
+        for (size_t g = 0; g < n; ++g)
+            if (state[g * RTMI_DIRECT_REC + 3] != (double)first)
+                return fail(RTMI_E_STATE, "pixel %zu's record holds %g samples, first is %d", g, state[g * RTMI_DIRECT_REC + 3], first);
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    HostIo io(c);
+    double *d_state, *d_lin, *d_hits;
+    unsigned char *d_q;
+    u64 *d_cnt;
+    io.plane(&d_state, n * RTMI_DIRECT_REC, state != nullptr, first > 0 ? state : nullptr, state);
+    io.work(&d_lin, n * 3, out_linear); io.out(&d_q, n * 3, out_rgb8); io.out(&d_hits, n * RTMI_HIT_REC, out_hits); io.work(&d_cnt, 2, out_counters);
+    rc = io.stage();
+    if (rc) return rc;
+    rc = with_real(precision, [&](auto r) { return render_direct_impl<decltype(r)>(s, nx, ny, T, n_samples, first, seed, d_state, d_lin, d_q, d_hits, d_cnt, c->stream); });
     return rc ? rc : io.finish();
 }
