@@ -775,6 +775,58 @@ int rtmi_render_direct(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t
 int rtmi_render_direct_device(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t n_samples, int32_t first, uint64_t seed, void *d_state,
                               void *d_out_linear, void *d_out_rgb8, void *d_out_hits, void *d_out_counters, void *stream);
 
+/* ---- path tracing with next-event estimation on caller-supplied rays: rtmi_render_rays whose Lambertian vertices also sample the area lights ----
+ * rtmi_render_rays' arguments plus the lights of rtmi_direct_irradiance (n_lights, light_prims: a HOST array in both forms, each entry eligible; NULL: all
+ * eligible primitives of rtmi_scene_lights, n_lights is then not read; more than RTMI_DIRECT_MAX_LIGHTS: RTMI_E_ARG).  Groups, g_first, the RTMI_RAYS_REC
+ * state, out_mean, out_stderr and out_rays keep rtmi_render_rays' contract: any split of a group into consecutive chunks gives the bits of one call.
+ * THE NEE RULE.  The reference's Lambertian scatter p + n + b (b uniform in the unit ball) is not cosine-weighted: its directions have the density
+ * 2 cos^3 / pi about the record's normal, and the reference multiplies by the albedo and nothing else.  A light-sampled path has the expectation of
+ * rtmi_render_rays for every scene and depth only if its direct term uses that lobe (rtmi_render_direct's albedo * E / pi is another estimator and stays).
+ * One path per ray.  The path's own stream, its rays, hits, scatters and segment count are rtmi_render_rays' for the same ray, key, ctr0 and depth, bit for
+ * bit: the light samples draw from other keys.  K = the path's key, j = the 0-based index of the segment whose hit is the vertex, nl = the number of
+ * sampled lights (nl >= 1).  Every product, sum, difference and quotient is one IEEE double operation in the order written.
+ *   1. A light sample is taken at exactly the vertices where a RTMI_MAT_LAMBERTIAN scatter happens (the depth left is > 0, core.clj's (and (pos? depth)
+ *      (scatter ...))), and nowhere else.
+ *   2. The light: l = min((int)(u * nl), nl - 1), u = the FP64 uniform of draw 0 of the stream keyed rtmi_sample_key(K, j, 1).
+ *   3. The sample: steps 3 - 5 of the light rule with the stream keyed rtmi_sample_key(K, j, 0), p = the hit point, the normal THE RECORD'S AS IT IS
+ *      (normalised by step 3 of the hemisphere rule; no viewer-side flip: the reference scatters about the record's normal whatever side the ray came
+ *      from), the time the path ray's.  d, d2, cp, cl, the far-side rule, the three "no ray" conditions and the t-range (0.001, 1 - 0.001) are unchanged;
+ *      a vertex whose p or normal is not finite, or whose normal has no length, builds no ray either (step 1 of the hemisphere rule).
+ *   4. The weight: w = ((((cp*cp)*(cp*cl)) / ((d2*d2)*d2)) * area) * TWO_INV_PI, TWO_INV_PI = 0x1.45f306dc9c883p-1.
+ *   5. The any-hit search of rtmi_query_occluded runs on that ray (its stream keyed 0).  If it finds nothing, accum.c = accum.c + (double)T.c * ((Le.c * w) *
+ *      (double)nl) per channel; contributions are added in vertex order, accum starts at +0.0, T = the path's attenuation AFTER this vertex's albedo, in
+ *      the call's precision.
+ *   6. The path's closing emission (atten * emitted) is dropped when the previous vertex took a light sample (step 1) AND the emitter's primitive is one of
+ *      the sampled lights; otherwise it is kept: a primary ray, a ray after metal, glass or a vertex with depth 0, and every emitter that is not a sampled
+ *      light (a gradient dome, a triangle, an instanced lamp, an unlisted lamp).
+ *   7. radiance.c = accum.c + (double)emit.c  (emit = +0.0 where dropped).
+ * nl == 0 (an empty list, or NULL and nothing eligible): the call IS rtmi_render_rays: every emission is kept and the two shadow-ray counters are zeros.
+ * A scene that holds a ConstantMedium: RTMI_E_UNSUPPORTED, nothing is launched (no transmittance along shadow rays).  RTMI_F32: sphere worlds only, as
+ * rtmi_render_rays; shadow rays and weights are FP64 whatever the precision, as in the light rule.
+ *   out_counters (may be NULL): FOUR values {segments, rays, shadow rays built, shadow rays occluded}.
+ * Errors, in this order: rtmi_render_rays' own, in their order; n_lights < 0 or > RTMI_DIRECT_MAX_LIGHTS with a list: RTMI_E_ARG; (n_groups == 0 succeeds
+ * here); a ConstantMedium: RTMI_E_UNSUPPORTED; a listed primitive that is out of range or not eligible, more than RTMI_DIRECT_MAX_LIGHTS eligible
+ * primitives without a list: RTMI_E_ARG.  A failed call launches nothing.  Options, frames, revision and RTMI_FLAG_TIMING: as rtmi_render_rays.
+ * rtmi_probe_paths_nee: rtmi_probe_paths' sibling, one path per thread through the same device functions.  log (may be NULL): [n][max_seg][RTMI_NEE_REC]
+ *   doubles per logged vertex: [0..11] RTMI_SEG_REC's values; [12] the light-sample state: 0 none at this vertex, 1 built and unoccluded, 2 built and
+ *   occluded, 3 a light-sampled vertex that built no ray; [13] l; [14..16] d; [17] w (zeros where no ray is built); [18..20] T; [21..23] the contribution
+ *   added (zeros unless the state is 1).  out_rgb: [n][3] the radiance of step 7; out_nseg (may be NULL): the segment counts; out_dropped (may be NULL):
+ *   [n] int32, 1 where step 6 dropped the closing emission; out_nlog (may be NULL): the logged vertices per path. */
+#define RTMI_NEE_REC 24
+/* host buffers; synchronous */
+int rtmi_render_rays_nee(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first,
+                         const double *rays, const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth,
+                         int32_t n_lights, const int32_t *light_prims,
+                         double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters);
+/* every d_ pointer a device pointer (light_prims stays a host array); asynchronous on `stream` with rtmi_render_device's stream semantics */
+int rtmi_render_rays_nee_device(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first,
+                                const void *d_rays, const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth,
+                                int32_t n_lights, const int32_t *light_prims,
+                                void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream);
+int rtmi_probe_paths_nee(rtmi_scene *scene, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
+                         int32_t n_lights, const int32_t *light_prims, double *out_rgb, uint64_t *out_nseg, int32_t *out_dropped,
+                         double *log, int32_t max_seg, int32_t *out_nlog);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

@@ -261,6 +261,42 @@ def light_table(flat, prims):
     return table
 
 
+def _light_terms(px, py, pz, nx, ny, nz, rows, keys):
+    """Steps 3 - 5 of the light rule for one item per entry: the point p, the UNIT normal (nx, ny, nz), the item's light record `rows` [items, LIGHT_REC]
+    and its stream `keys` -> (dx, dy, dz, d2, cp, cl, built, area), every operation a single IEEE operation in the header's order."""
+    from . import util
+    kind = rows[:, 0].astype(np.int64)
+    sphere = kind <= 1
+    g0, g1, g2, g3, g4, area = (rows[:, c] for c in range(1, 7))
+    a = g0 + util.draw_uniforms(keys, 0) * (g2 - g0)                                    # 3. a rectangle: draws 0 and 1
+    b = g1 + util.draw_uniforms(keys, 1) * (g3 - g1)
+    x, y = np.zeros(len(keys)), np.zeros(len(keys))                                     # 4. a sphere: the first candidate inside the disk
+    pending, c = np.flatnonzero(sphere), 0
+    while len(pending):
+        cx = 2.0 * util.draw_uniforms(keys[pending], 2 * c) - 1.0
+        cy = 2.0 * util.draw_uniforms(keys[pending], 2 * c + 1) - 1.0
+        inside = ~(((cx * cx + cy * cy) + 0.0 * 0.0) >= 1.0)
+        x[pending[inside]], y[pending[inside]] = cx[inside], cy[inside]
+        pending, c = pending[~inside], c + 1
+    S = x * x + y * y
+    root = np.sqrt(1.0 - S)
+    sx = np.where(sphere, (2.0 * x) * root, np.where(kind == 5, 1.0, 0.0))
+    sy = np.where(sphere, (2.0 * y) * root, np.where(kind == 4, 1.0, 0.0))
+    sz = np.where(sphere, 1.0 - 2.0 * S, np.where(kind == 3, 1.0, 0.0))
+    qx = np.where(sphere, g0 + g3 * sx, np.where(kind == 5, g4, a))
+    qy = np.where(sphere, g1 + g3 * sy, np.where(kind == 3, b, np.where(kind == 4, g4, a)))
+    qz = np.where(sphere, g2 + g3 * sz, np.where(kind == 3, g4, b))
+    dx, dy, dz = qx - px, qy - py, qz - pz                                              # 5. the geometry term
+    d2 = (dx * dx + dy * dy) + dz * dz
+    cp = (nx * dx + ny * dy) + nz * dz
+    sd = (sx * dx + sy * dy) + sz * dz
+    cl = np.abs(sd)
+    ex, ey, ez = px - g0, py - g1, pz - g2
+    far = sphere & (((ex * ex + ey * ey) + ez * ez) > g3 * g3) & (sd > 0.0)               # the far side of a sphere seen from outside
+    built = ~far & (d2 > 0.0) & (cp > 0.0) & (cl > 0.0)
+    return dx, dy, dz, d2, cp, cl, built, area
+
+
 def light_samples(points, normals, lights, n_samples, first=0, seed=0x5EED0002, time=0.0):
     """The shadow rays and weights the device builds towards area lights (include/rtmi.h, "the light rule", steps 2 - 6), every operation a single
     IEEE operation in the header's order, so rtmi_direct_irradiance's out_rays equal these rows bit for bit.  points, normals [n, 3]: the shaded
@@ -278,41 +314,45 @@ def light_samples(points, normals, lights, n_samples, first=0, seed=0x5EED0002, 
         raise ValueError("points and normals must pair up, n_samples > 0 and first >= 0")
     g, k, l = (a.ravel() for a in np.meshgrid(np.arange(len(points)), np.arange(first, first + n_samples), np.arange(nl), indexing="ij"))
     keys = util.sample_keys(seed, g * nl + l, k)                                        # 2. the item's stream
-    kind = lights[l, 0].astype(np.int64)
-    sphere = kind <= 1
-    g0, g1, g2, g3, g4, area = (lights[l, c] for c in range(1, 7))
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         nx, ny, nz = normals[:, 0], normals[:, 1], normals[:, 2]
         length = np.sqrt((nx * nx + ny * ny) + nz * nz)                               # (step 3 of the hemisphere rule)
         nx, ny, nz = (nx / length)[g], (ny / length)[g], (nz / length)[g]
-        px, py, pz = points[g, 0], points[g, 1], points[g, 2]
-        a = g0 + util.draw_uniforms(keys, 0) * (g2 - g0)                                # 3. a rectangle: draws 0 and 1
-        b = g1 + util.draw_uniforms(keys, 1) * (g3 - g1)
-        x, y = np.zeros(len(keys)), np.zeros(len(keys))                                 # 4. a sphere: the first candidate inside the disk
-        pending, c = np.flatnonzero(sphere), 0
-        while len(pending):
-            cx = 2.0 * util.draw_uniforms(keys[pending], 2 * c) - 1.0
-            cy = 2.0 * util.draw_uniforms(keys[pending], 2 * c + 1) - 1.0
-            inside = ~(((cx * cx + cy * cy) + 0.0 * 0.0) >= 1.0)
-            x[pending[inside]], y[pending[inside]] = cx[inside], cy[inside]
-            pending, c = pending[~inside], c + 1
-        S = x * x + y * y
-        root = np.sqrt(1.0 - S)
-        sx = np.where(sphere, (2.0 * x) * root, np.where(kind == 5, 1.0, 0.0))
-        sy = np.where(sphere, (2.0 * y) * root, np.where(kind == 4, 1.0, 0.0))
-        sz = np.where(sphere, 1.0 - 2.0 * S, np.where(kind == 3, 1.0, 0.0))
-        qx = np.where(sphere, g0 + g3 * sx, np.where(kind == 5, g4, a))
-        qy = np.where(sphere, g1 + g3 * sy, np.where(kind == 3, b, np.where(kind == 4, g4, a)))
-        qz = np.where(sphere, g2 + g3 * sz, np.where(kind == 3, g4, b))
-        dx, dy, dz = qx - px, qy - py, qz - pz                                          # 5. the geometry term
-        d2 = (dx * dx + dy * dy) + dz * dz
-        cp = (nx * dx + ny * dy) + nz * dz
-        sd = (sx * dx + sy * dy) + sz * dz
-        cl = np.abs(sd)
-        ex, ey, ez = px - g0, py - g1, pz - g2
-        far = sphere & (((ex * ex + ey * ey) + ez * ez) > g3 * g3) & (sd > 0.0)           # the far side of a sphere seen from outside
-        built = ~far & (d2 > 0.0) & (cp > 0.0) & (cl > 0.0)
+        dx, dy, dz, d2, cp, cl, built, area = _light_terms(points[g, 0], points[g, 1], points[g, 2], nx, ny, nz, lights[l], keys)
         w = ((cp * cl) / (d2 * d2)) * area
     rays = _rays(points[g], np.stack([dx, dy, dz], axis=1), float(time))[0]            # 6. origin p, direction d: t = 1 is the light
     rays[~built] = 0.0
     return rays, np.where(built, w, 0.0), built
+
+
+TWO_INV_PI = float.fromhex("0x1.45f306dc9c883p-1")
+
+
+def nee_samples(points, normals, lights, keys_sample, keys_pick):
+    """The light samples of light-sampled paths (include/rtmi.h, "the NEE rule", steps 2 - 4), one per vertex, every operation a single IEEE
+    operation in the header's order, so rtmi_probe_paths_nee's log columns [13..17] equal these bit for bit.  points, normals [n, 3]: the hit
+    points and the records' normals AS THEY ARE (no viewer-side flip; the rule normalises them); lights [nl, LIGHT_REC] (light_table), nl >= 1;
+    keys_sample, keys_pick [n] uint64: sample_key(K, j, 0) and sample_key(K, j, 1) of the path keyed K at its vertex j.  The light is
+    min(int(u * nl), nl - 1) with u = draw 0 of keys_pick; the point on it comes from keys_sample as in light_samples.
+    -> (light [n] int, d [n, 3] = sampled point - p (zeros where no ray is built), w [n] = the reference's lobe 2 cos^3 / pi times the light's
+    cosine, its area and the inverse square, as ((((cp*cp)*(cp*cl)) / ((d2*d2)*d2)) * area) * TWO_INV_PI (0 where no ray is built), built [n])."""
+    from . import util
+    points, normals = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(normals, np.float64).reshape(-1, 3)
+    lights = np.asarray(lights, np.float64).reshape(-1, LIGHT_REC)
+    keys_sample, keys_pick = np.asarray(keys_sample, np.uint64).reshape(-1), np.asarray(keys_pick, np.uint64).reshape(-1)
+    nl = len(lights)
+    if not (len(points) == len(normals) == len(keys_sample) == len(keys_pick)) or nl < 1:
+        raise ValueError("points, normals and keys must pair up, and there must be a light")
+    l = np.minimum((util.draw_uniforms(keys_pick, 0) * np.float64(nl)).astype(np.int64), nl - 1)   # 2. which light
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        nx, ny, nz = normals[:, 0], normals[:, 1], normals[:, 2]
+        len2 = (nx * nx + ny * ny) + nz * nz
+        sound = np.isfinite(points).all(axis=1) & np.isfinite(normals).all(axis=1) & (len2 > 0.0)
+        length = np.sqrt(len2)                                                          # (step 3 of the hemisphere rule; no flip)
+        dx, dy, dz, d2, cp, cl, built, area = _light_terms(points[:, 0], points[:, 1], points[:, 2], nx / length, ny / length, nz / length,
+                                                           lights[l], keys_sample)
+        built = built & sound
+        w = ((((cp * cp) * (cp * cl)) / ((d2 * d2) * d2)) * area) * TWO_INV_PI        # 4. the weight
+    d = np.stack([dx, dy, dz], axis=1)
+    d[~built] = 0.0
+    return l, d, np.where(built, w, 0.0), built

@@ -625,20 +625,89 @@ class DeviceScene:
                                                  int(ctr0), int(depth), ptr(state), ptr(out_mean), ptr(out_stderr), ptr(out_rays), ptr(out_counters),
                                                  ptr(stream)))
 
-    def render_with(self, generator, nx, ny, ns, chunk, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", **generator_args):
+    def render_with(self, generator, nx, ny, ns, chunk, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", nee=False, lights=None,
+                    **generator_args):
         """An nx x ny x ns image through a ray generator of camera.py (generator(nx, ny, s_first, s_count, seed=, **generator_args) -> (rays,
         ctr0), grouped per pixel): chunks of `chunk` samples per pixel folded into one state, keys derived from (seed, pixel, sample) ->
         (linear [ny, nx, 3] = the per-pixel mean, rgb8 = the frame's 8-bit quantiser of it (Context.denoise with no pass), stderr [ny, nx], counters
-        summed over the chunks); row 0 = top.  The result does not depend on `chunk`."""
+        summed over the chunks); row 0 = top.  The result does not depend on `chunk`.  nee: the paths sample the lights (render_rays_nee with
+        `lights`; four counters)."""
         if chunk <= 0 or ns <= 0:
             raise ValueError("ns and chunk must be > 0")
         state = np.zeros((nx * ny, _ffi.RAYS_REC), np.float64)
-        total = np.zeros(2, np.uint64)
+        total = np.zeros(4 if nee else 2, np.uint64)
         k = 0
         while k < ns:
             n = min(chunk, ns - k)
             rays, ctr0 = generator(nx, ny, k, n, seed=seed, **generator_args)
-            mean, err, cnt, _ = self.render_rays(rays, group=n, seed=seed, ctr0=ctr0, depth=depth, precision=precision, first=k, state=state)
+            if nee:
+                mean, err, cnt, _ = self.render_rays_nee(rays, group=n, lights=lights, seed=seed, ctr0=ctr0, depth=depth, precision=precision, first=k,
+                                                         state=state)
+            else:
+                mean, err, cnt, _ = self.render_rays(rays, group=n, seed=seed, ctr0=ctr0, depth=depth, precision=precision, first=k, state=state)
+            total += cnt
+            k += n
+        lin = np.ascontiguousarray(mean.reshape(ny, nx, 3)[::-1])  # group j * nx + i, j = 0 at the bottom
+        return lin, self.ctx.denoise(lin, iterations=0)[1], np.ascontiguousarray(err.reshape(ny, nx)[::-1]), total
+
+    # ---- path tracing with next-event estimation: render_rays whose Lambertian vertices also sample the area lights -------------------------
+    def render_rays_nee(self, rays, group=1, lights=None, keys=None, seed=RENDER_SEED, ctr0=0, depth=DEFAULT_DEPTH, precision="f64", first=0,
+                        state=None, return_rays=False):
+        """render_rays with one shadow ray per Lambertian vertex towards a sampled point of one uniformly chosen light (lights: primitive
+        indices out of self.lights(); None: all of them) -- the NEE rule of include/rtmi.h, which camera.nee_samples restates.  The path itself
+        (stream, hits, scatters, segments) is render_rays' bit for bit and the estimate has the same expectation; on a lit scene its variance is
+        a fraction.  No lights: the call is render_rays.  A scene with a ConstantMedium is refused.  -> render_rays' tuple, the counters being
+        {segments, rays, shadow rays built, shadow rays occluded}."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+        group = int(group)
+        if group <= 0 or len(rays) % group:
+            raise ValueError("%d rays are not whole groups of %d" % (len(rays), group))
+        n_groups = len(rays) // group
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
+            if len(keys) != len(rays):
+                raise ValueError("%d keys for %d rays" % (len(keys), len(rays)))
+        if state is not None and (not isinstance(state, np.ndarray) or state.dtype != np.float64 or not state.flags.c_contiguous
+                                  or state.shape != (n_groups, _ffi.RAYS_REC)):
+            raise ValueError("state must be a C-contiguous float64 array [n_groups, %d]" % _ffi.RAYS_REC)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        mean, err, cnt = np.zeros((n_groups, 3), np.float64), np.zeros(n_groups, np.float64), np.zeros(4, np.uint64)
+        out = np.zeros((len(rays), 3), np.float64) if return_rays else None
+        check(_ffi.lib().rtmi_render_rays_nee(self.handle, _PRECISION[precision], n_groups, group, int(first), ptr(rays), ptr(keys), int(seed), int(ctr0),
+                                              int(depth), n_listed, ptr(lights), ptr(state), ptr(mean), ptr(err), ptr(out), ptr(cnt)))
+        return mean, err, cnt, out
+
+    def render_rays_nee_device(self, n_groups, group, rays, out_mean, out_stderr, lights=None, keys=None, seed=RENDER_SEED, ctr0=0,
+                               depth=DEFAULT_DEPTH, precision="f64", first=0, state=None, out_rays=None, out_counters=None, stream=None):
+        """render_rays_nee on HBM-resident buffers (lights stays a host list; out_counters: four uint64); asynchronous, render_device's stream
+        semantics.  A state's count is the caller's contract: it is not read back."""
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        check(_ffi.lib().rtmi_render_rays_nee_device(self.handle, _PRECISION[precision], int(n_groups), int(group), int(first), ptr(rays), ptr(keys),
+                                                     int(seed), int(ctr0), int(depth), n_listed, ptr(lights), ptr(state), ptr(out_mean), ptr(out_stderr),
+                                                     ptr(out_rays), ptr(out_counters), ptr(stream)))
+
+    def render_nee(self, nx, ny, ns, chunk, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", lights=None):
+        """An nx x ny x ns frame of the scene's own camera (of either kind) through light-sampled paths, folded per pixel through one state as
+        render_with folds.  Film jitter, lens draws and path streams come from three seeds derived from `seed` (sample_key(seed, 0 / 1 / 2, 0)),
+        so none of them shares draws with another: sample s of pixel g jitters with draws 0 and 1 of sample_key(film, g, s), its camera ray is
+        probe_camera's for that (u, v) with the stream sample_key(lens, g, s), and its path is keyed sample_key(paths, g, s) from draw 0.
+        -> render_with's tuple (four counters); the result does not depend on `chunk`."""
+        from . import util
+        if nx <= 0 or ny <= 0 or chunk <= 0 or ns <= 0:
+            raise ValueError("nx, ny, ns and chunk must be > 0")
+        film, lens, paths = (util.sample_key(seed, k, 0) for k in range(3))
+        state = np.zeros((nx * ny, _ffi.RAYS_REC), np.float64)
+        total = np.zeros(4, np.uint64)
+        k = 0
+        while k < ns:
+            n = min(chunk, ns - k)
+            pix, ss = (a.ravel() for a in np.meshgrid(np.arange(nx * ny), np.arange(k, k + n), indexing="ij"))
+            fk = util.sample_keys(film, pix, ss)
+            u = ((pix % nx).astype(np.float64) + util.draw_uniforms(fk, 0)) / np.float64(nx)
+            v = ((pix // nx).astype(np.float64) + util.draw_uniforms(fk, 1)) / np.float64(ny)
+            rays = self.probe_camera(np.stack([u, v], axis=1), util.sample_keys(lens, pix, ss), precision=precision)[:, :7]
+            mean, err, cnt, _ = self.render_rays_nee(rays, group=n, lights=lights, seed=paths, ctr0=0, depth=depth, precision=precision, first=k,
+                                                     state=state)
             total += cnt
             k += n
         lin = np.ascontiguousarray(mean.reshape(ny, nx, 3)[::-1])  # group j * nx + i, j = 0 at the bottom
@@ -923,6 +992,20 @@ class DeviceScene:
         check(_ffi.lib().rtmi_probe_paths(self.handle, _PRECISION[precision], n, ptr(rays), ptr(keys), ctr0, depth,
                                           ptr(rgb), ptr(nseg), ptr(log), max_seg, ptr(nlog)))
         return rgb, nseg, log, nlog
+
+    def probe_paths_nee(self, rays, keys, lights=None, depth=DEFAULT_DEPTH, ctr0=0, max_seg=0, precision="f64"):
+        """probe_paths for light-sampled paths (rtmi_probe_paths_nee) -> (rgb [n, 3], segment counts, log [n, max_seg, NEE_REC] or None, logged
+        vertices per path, dropped int32 [n] = 1 where the closing emission was dropped).  A log row: SEG_REC's twelve values, the light-sample
+        state (0 none, 1 unoccluded, 2 occluded, 3 no ray), the light, d, w, T and the contribution added."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+        keys = np.ascontiguousarray(keys, np.uint64)
+        n = len(rays)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        rgb, nseg, nlog, dropped = np.zeros((n, 3)), np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        log = np.zeros((n, max_seg, _ffi.NEE_REC)) if max_seg else None
+        check(_ffi.lib().rtmi_probe_paths_nee(self.handle, _PRECISION[precision], n, ptr(rays), ptr(keys), ctr0, depth, n_listed, ptr(lights),
+                                              ptr(rgb), ptr(nseg), ptr(dropped), ptr(log), max_seg, ptr(nlog)))
+        return rgb, nseg, log, nlog, dropped
 
     def probe_camera(self, uv, keys, precision="f64"):
         uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
@@ -1500,6 +1583,25 @@ def _direct_flags(argv):
     return rest, samples
 
 
+def _nee_flags(argv, panorama=False, orbit=False):
+    """-> (the other arguments, whether --nee was given); the modes it does not combine with are refused here, before any device work"""
+    rest = [a for a in argv if a != "--nee"]
+    given = len(rest) != len(argv)
+    for a in rest:
+        if a.startswith("--nee"):
+            raise SystemExit("--nee takes no value (got %r)" % a)
+    if given and (panorama or orbit):
+        raise SystemExit("--nee does not combine with --orbit or --panorama")
+    return rest, given
+
+
+def _nee_name(name):
+    """x.png -> x.nee.png: the light-sampled frame is written next to the frame"""
+    import os
+    root, ext = os.path.splitext(name)
+    return root + ".nee" + ext
+
+
 def _direct_name(name):
     """x.png -> x.direct.png: the directly lit view is written next to the frame"""
     import os
@@ -1570,7 +1672,9 @@ def main(argv=None):
     --ao-device N [RADIUS] writes the same kind of image through DeviceScene.ambient_occlusion_device: the rays are generated on the device (the disk
     sampler's directions, not --ao's: the same estimate from other rays).  It takes the place of --ao.
     --direct N also writes the view lit directly (DeviceScene.render_direct: N shadow rays per first hit towards every area light the scene holds,
-    sampled on the device) as name.direct.ext, beside the frame.  It does not combine with --orbit or --panorama."""
+    sampled on the device) as name.direct.ext, beside the frame.  It does not combine with --orbit or --panorama.
+    --nee also writes the frame traced by light-sampled paths (DeviceScene.render_nee: ns paths per pixel, one shadow ray per Lambertian vertex) as
+    name.nee.ext, beside the frame.  It does not combine with --orbit or --panorama, and a scene that holds a ConstantMedium is refused."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
     argv, direct = _direct_flags(argv)
@@ -1586,6 +1690,7 @@ def main(argv=None):
         raise SystemExit("--ao does not combine with --orbit or --panorama")
     if direct is not None and (panorama or orbit_views is not None):
         raise SystemExit("--direct does not combine with --orbit or --panorama")
+    argv, nee = _nee_flags(argv, panorama, orbit_views is not None)
     argv, accumulate = _accumulate_flags(argv, orbit_views)
     argv, adaptive_denoised = _adaptive_denoised_flags(argv)
     if adaptive_denoised is not None and not any(a.split("=", 1)[0] == "--denoise" for a in argv):
@@ -1605,6 +1710,8 @@ def main(argv=None):
         raise SystemExit("unknown scene %r; one of %s" % (which, ", ".join(sorted(SCENES))))
     tstart = time.time()
     sc = SCENES[which](scenes, nx, ny)
+    if nee and (fl.flatten(sc).prim_kind & 15 == fl.PRIM_MEDIUM).any():
+        raise SystemExit("--nee: scene %r holds a ConstantMedium, which the light-sampled paths do not trace" % which)
     if accumulate is not None:
         return _render_orbit_accumulated(sc, name, nx, ny, nr, orbit_views, dn_iterations, dn_samples, accumulate, tstart)
     if orbit_views is not None:
@@ -1702,6 +1809,13 @@ def main(argv=None):
         finally:
             ds.close()
         _save_image(_direct_name(name), lit)
+    if nee:
+        ds = DeviceScene(sc)
+        try:
+            lit = ds.render_nee(nx, ny, nr, min(nr, 16))[1]
+        finally:
+            ds.close()
+        _save_image(_nee_name(name), lit)
     return 0
 
 

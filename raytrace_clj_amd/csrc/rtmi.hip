@@ -1578,6 +1578,285 @@ __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WA
     }
 }
 
+// ---- path tracing with next-event estimation on caller-supplied rays (rtmi_render_rays_nee*, rtmi_probe_paths_nee) -------------------------------
+// rays_kernel's path -- the same refill, the same closest-hit trip, the same stream -- plus, at every vertex that scattered as a Lambertian, one shadow
+// ray towards a sampled point of one uniformly chosen light (THE NEE RULE of rtmi.h).  The light samples draw from keys derived from the path's key and
+// the vertex index: the path's own stream is rays_kernel's.  What crosses the any-hit search: the path (as it crosses every closest-hit search) and two
+// flags.  The pending contribution T * Le * w * nl waits in the lane's LDS slot, and the running sum `accum` lives there too: neither is a register
+// while a tree is walked.
+constexpr int kNeeSlots = 6; // doubles per lane in LDS: accum.rgb, pending.rgb; slot s of lane t at nee_lds[s * kBlock + t]
+constexpr double kTwoInvPi = 0x1.45f306dc9c883p-1;
+struct NeeLights {
+    const double *rec; // [n][kLightRec]: set_nee_lights_kernel's copy of the call's light table
+    const int *prim;   // [n]: the sampled lights' primitives (what step 6 compares a closing emitter with)
+    unsigned n;        // >= 1
+};
+
+// Is primitive `orig` one of the sampled lights?  (at most RTMI_DIRECT_MAX_LIGHTS compares, at a path's end only)
+__device__ inline bool nee_sampled_light(const NeeLights &nl, int orig) {
+    bool found = false;
+    for (unsigned l = 0; l < nl.n; ++l) found = found || nl.prim[l] == orig;
+    return found;
+}
+
+// Steps 2 - 4 of the NEE rule for the vertex j of the path keyed K: the light l, the shadow ray q[7] (zeros where none is built) and the weight w.
+// Every lane of the wave calls (the disk sampler is cooperative), the lanes whose vertex takes a light sample with `want`.  As in generate_light_ray
+// the rounds stand before the geometry (no operation changes); unlike there the normal is the record's as it is.
+__device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsigned j, double px, double py, double pz, double nx, double ny, double nz,
+                                     double time, double *q, double &w, int &l) {
+    const double big = __builtin_inf();
+    const double len2 = dot3(nx, ny, nz, nx, ny, nz);
+    bool ok = want && ::fabs(px) < big && ::fabs(py) < big && ::fabs(pz) < big && ::fabs(nx) < big && ::fabs(ny) < big && ::fabs(nz) < big && len2 > 0.0;
+    const u64 kpick = sample_key(K, (u64)j, 1ull), key = sample_key(K, (u64)j, 0ull);
+    const double up = Real<double>::uniform(mix64(kpick + RTMI_GOLD)); // draw 0 of the picking stream
+    l = min((int)(up * (double)nl.n), (int)nl.n - 1);
+    const double *L = nl.rec + (size_t)l * kLightRec;
+    const int kind = (int)L[0];
+    const bool sphere = kind == RTMI_PRIM_SPHERE || kind == RTMI_PRIM_UVSPHERE;
+    Path<double> G; // the sampler's own stream
+    seed_stream(G, key, 0u);
+    double x = 0.0, y = 0.0;
+    rand_in_unit_disk_wave<double>(G, ok && sphere, false, x, y);
+    const double u0 = Real<double>::uniform(mix64(key + RTMI_GOLD)), u1 = Real<double>::uniform(mix64(key + 2ull * RTMI_GOLD)); // draws 0 and 1
+    const double g0 = L[1], g1 = L[2], g2 = L[3], g3 = L[4], g4 = L[5], area = L[6];
+    const double len = ::sqrt(len2);
+    nx = nx / len; ny = ny / len; nz = nz / len;
+    double qx, qy, qz, sx, sy, sz;
+    if (sphere) { // Marsaglia: a uniform point of the unit disk -> a uniform point of the unit sphere
+        const double S = x * x + y * y, root = ::sqrt(1.0 - S);
+        sx = (2.0 * x) * root; sy = (2.0 * y) * root; sz = 1.0 - 2.0 * S;
+        qx = g0 + g3 * sx; qy = g1 + g3 * sy; qz = g2 + g3 * sz;
+    } else {
+        const double a = g0 + u0 * (g2 - g0), b = g1 + u1 * (g3 - g1);
+        sx = kind == RTMI_PRIM_RECT_YZ ? 1.0 : 0.0; sy = kind == RTMI_PRIM_RECT_XZ ? 1.0 : 0.0; sz = kind == RTMI_PRIM_RECT_XY ? 1.0 : 0.0;
+        if (kind == RTMI_PRIM_RECT_XY) { qx = a; qy = b; qz = g4; }
+        else if (kind == RTMI_PRIM_RECT_XZ) { qx = a; qy = g4; qz = b; }
+        else { qx = g4; qy = a; qz = b; }
+    }
+    const double dx = qx - px, dy = qy - py, dz = qz - pz;
+    const double d2 = dot3(dx, dy, dz, dx, dy, dz), cp = dot3(nx, ny, nz, dx, dy, dz), sd = dot3(sx, sy, sz, dx, dy, dz), cl = ::fabs(sd);
+    if (sphere) { // the far side of a sphere seen from outside
+        const double ex = px - g0, ey = py - g1, ez = pz - g2;
+        if (dot3(ex, ey, ez, ex, ey, ez) > g3 * g3 && sd > 0.0) ok = false;
+    }
+    ok = ok && d2 > 0.0 && cp > 0.0 && cl > 0.0;
+    w = ok ? ((((cp * cp) * (cp * cl)) / ((d2 * d2) * d2)) * area) * kTwoInvPi : 0.0; // the reference's lobe 2 cos^3 / pi, the light's cosine, the inverse square
+    q[0] = ok ? px : 0.0; q[1] = ok ? py : 0.0; q[2] = ok ? pz : 0.0;
+    q[3] = ok ? dx : 0.0; q[4] = ok ? dy : 0.0; q[5] = ok ? dz : 0.0; q[6] = ok ? time : 0.0;
+    return ok;
+}
+
+// Steps 2 - 5 of the NEE rule, for the whole wave: `lamb` lanes sit at a vertex that scattered as a Lambertian (P is already the scattered ray: its
+// origin is the hit point, its attenuation T).  slot: the lane's LDS column (accum, pending).  rec (probe only, may be null): the vertex' RTMI_NEE_REC row.
+// -> the light-sample state of the header: 0 none, 1 built and unoccluded, 2 built and occluded, 3 built no ray.
+template <typename R, int VARIANT, bool EXT>
+__device__ inline int nee_vertex(SceneRef sc, Prim4<R> *lds, const NeeLights &nl, bool lamb, u64 K, unsigned j, const Path<R> &P, double nx, double ny,
+                                 double nz, double *slot, double *rec) {
+    Path<R> S;
+    bool ok;
+    {
+        double q[7], w;
+        int l;
+        ok = nee_light_ray(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l);
+        const double *L = nl.rec + (size_t)l * kLightRec;
+        const double many = (double)nl.n;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double T = (double)(c == 0 ? P.ar : c == 1 ? P.ag : P.ab);
+            slot[(3 + c) * kBlock] = ok ? T * ((L[7 + c] * w) * many) : 0.0;
+            if (rec && lamb) rec[18 + c] = T;
+        }
+        if (rec && lamb) { rec[13] = (double)l; rec[14] = q[3]; rec[15] = q[4]; rec[16] = q[5]; rec[17] = w; }
+        load_ray<R>(q, S);
+    }
+    R best_t; int best_i;
+    intersect_world<R, true, VARIANT, EXT, false, false, 0, false, true>(sc, lds, 0, 1, S, ok, R(0.001), (R)(1.0 - 0.001), best_t, best_i);
+    const bool hit = ok && best_i >= 0;
+    if (ok && !hit) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double add = slot[(3 + c) * kBlock];
+            slot[c * kBlock] = slot[c * kBlock] + add;
+            if (rec) rec[21 + c] = add;
+        }
+    }
+    const int state = !lamb ? 0 : !ok ? 3 : hit ? 2 : 1;
+    if (rec && lamb) rec[12] = (double)state;
+    return state;
+}
+
+struct NeeParams {
+    RaysParams rp;   // rays_kernel's arguments; counters: [0] += segments, [2] += shadow rays built, [3] += shadow rays occluded
+    NeeLights lights;
+};
+
+#ifndef RTMI_NEE_MIN_WAVES
+// waves per SIMD rays_nee_kernel is compiled for.  At rays_kernel's 4 (128 VGPRs) the FP64 tree instantiations spill 36 - 68 bytes per lane around the light
+// sample; at 3 they take 131 - 141 VGPRs without scratch and measured 4 - 7 % faster (A/B: make variant NAME=nee_w4 FLAGS=-DRTMI_NEE_MIN_WAVES=4)
+#define RTMI_NEE_MIN_WAVES 3
+#endif
+template <typename R, int VARIANT, bool EXT = false>
+__global__ void __launch_bounds__(kBlock, RTMI_NEE_MIN_WAVES) rays_nee_kernel(ScenePtr scp, NeeParams np) {
+    static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the refill loop is per wave");
+    SceneRef sc = *scp;
+    __shared__ double nee_lds[kNeeSlots * kBlock];
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    Prim4<R> *lds = reinterpret_cast<Prim4<R> *>(smem);
+    double *slot = nee_lds + threadIdx.x;
+    const RaysParams &rp = np.rp;
+    const int lane = threadIdx.x & 63;
+    const unsigned total_items = rp.total_items;
+    unsigned w_cur = 0, w_end = 0; // this wave's claimed range [w_cur, w_end): wave-uniform
+    Path<R> P;
+    P.ox = P.oy = P.oz = P.dx = P.dy = P.dz = P.time = R(0);
+    P.ar = P.ag = P.ab = R(0);
+    seed_stream(P, 0ull, 0u); P.depth = 0;
+    bool alive = false;
+    bool exhausted = (total_items == 0);
+    bool sampled = false; // the path's previous vertex took a light sample
+    unsigned out_item = 0;
+    unsigned nseg = 0, seg = 0, n_built = 0, n_occ = 0; // seg: the path's segment index j
+    const R tmin = R(0.001), tmax = Real<R>::tmax();
+    for (;;) {
+        while (!exhausted) { // every lane of the wave takes part: the loop conditions are wave-uniform
+            const u64 dead = __ballot(!alive);
+            if (dead == 0) break;
+            if (w_cur == w_end) {
+                unsigned base = 0;
+                if (lane == 0) base = atomicAdd(rp.queue, rp.qblock);
+                base = __builtin_amdgcn_readfirstlane(base);
+                if (base >= total_items) { exhausted = true; break; }
+                w_cur = base;
+                w_end = min(base + rp.qblock, total_items);
+            }
+            const unsigned avail = w_end - w_cur;
+            const unsigned rank = (unsigned)__popcll(dead & ((1ull << lane) - 1ull));
+            if (!alive && rank < avail) {
+                const unsigned m = w_cur + rank; // < total_items
+                load_ray<R>(rp.rays + (size_t)m * 7, P);
+                u64 key;
+                if (rp.keys) key = rp.keys[m];
+                else { const unsigned row = rp.row0 + m, g = row / rp.group; key = sample_key(rp.seed, (u64)g, (u64)rp.g_first + (u64)(row - g * rp.group)); }
+                seed_stream(P, key, rp.ctr0); P.depth = rp.depth;
+                out_item = m;
+                alive = true;
+                sampled = false; seg = 0;
+                slot[0] = 0.0; slot[kBlock] = 0.0; slot[2 * kBlock] = 0.0; // accum starts at +0.0
+            }
+            w_cur += min((unsigned)__popcll(dead), avail);
+        }
+        if (!__any(alive ? 1 : 0)) break;
+        R best_t; int best_i;
+        intersect_world<R, true, VARIANT, EXT, false, false, 0>(sc, lds, 0, 1, P, alive, tmin, tmax, best_t, best_i);
+        bool lamb = false;
+        double nx = 0.0, ny = 0.0, nz = 0.0;
+        if (alive) {
+            ++nseg;
+            R emit[3];
+            HitRec<R> h;
+            alive = shade_segment_nee<R, EXT>(sc, P, best_t, best_i, emit, h, lamb);
+            nx = (double)h.nx; ny = (double)h.ny; nz = (double)h.nz;
+            if (!alive) { // step 6: a sampled light's emission was already counted at the previous vertex
+                const bool drop = sampled && best_i >= 0 && nee_sampled_light(np.lights, best_i);
+                double *out = rp.samples + (size_t)out_item * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) out[c] = slot[c * kBlock] + (drop ? 0.0 : (double)emit[c]);
+            }
+        }
+        if (__any(lamb ? 1 : 0)) { // wave-uniform: all 64 lanes enter the disk rounds and the any-hit search
+            const int state = nee_vertex<R, VARIANT, EXT>(sc, lds, np.lights, lamb, P.key, seg, P, nx, ny, nz, slot, nullptr);
+            n_built += state == 1 || state == 2 ? 1u : 0u;
+            n_occ += state == 2 ? 1u : 0u;
+        }
+        sampled = lamb;
+        ++seg;
+    }
+    // segments and shadow rays: wave reductions, one atomic per wave and counter
+    unsigned n = nseg, b = n_built, o = n_occ;
+    for (int off = 32; off > 0; off >>= 1) { n += __shfl_down(n, off); b += __shfl_down(b, off); o += __shfl_down(o, off); }
+    if (lane == 0) {
+        if (n) atomicAdd(rp.counters, (u64)n);
+        if (b) atomicAdd(rp.counters + 2, (u64)b);
+        if (o) atomicAdd(rp.counters + 3, (u64)o);
+    }
+}
+
+// rtmi_probe_paths_nee: one path per thread through the same device functions, each vertex logged as RTMI_NEE_REC doubles
+struct NeeProbeParams {
+    int n;
+    const double *rays;
+    const u64 *keys;
+    unsigned ctr0;
+    int depth;
+    double *out_rgb;   // [n][3]
+    u64 *out_nseg;     // [n], or null
+    int *out_dropped;  // [n], or null: 1 where the closing emission was dropped
+    double *log;       // [n][max_seg][RTMI_NEE_REC], zeroed before the launch, or null
+    int max_seg;
+    int *out_nlog;     // [n], or null
+    NeeLights lights;  // n == 0: no vertex takes a light sample
+};
+
+template <typename R, int VARIANT, bool EXT = false>
+__global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, NeeProbeParams pp) {
+    static_assert(VARIANT >= SCAN_SGPR, "the loop is per wave, as rays_nee_kernel's");
+    SceneRef sc = *scp;
+    __shared__ double nee_lds[kNeeSlots * kBlock];
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    Prim4<R> *lds = reinterpret_cast<Prim4<R> *>(smem);
+    double *slot = nee_lds + threadIdx.x;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    bool alive = k < pp.n;
+    const size_t row = (size_t)(alive ? k : 0);
+    Path<R> P;
+    load_ray<R>(pp.rays + row * 7, P);
+    seed_stream(P, alive ? pp.keys[k] : 0ull, pp.ctr0); P.depth = pp.depth;
+    double *log = pp.log ? pp.log + row * (size_t)pp.max_seg * RTMI_NEE_REC : nullptr;
+    int nlog = 0, dropped = 0;
+    u64 nseg = 0;
+    unsigned seg = 0;
+    bool sampled = false;
+    const R tmin = R(0.001), tmax = Real<R>::tmax();
+    double rgb[3] = {0.0, 0.0, 0.0};
+    slot[0] = 0.0; slot[kBlock] = 0.0; slot[2 * kBlock] = 0.0;
+    while (__any(alive ? 1 : 0)) {
+        R best_t; int best_i;
+        intersect_world<R, true, VARIANT, EXT, false, false, 0>(sc, lds, 0, 1, P, alive, tmin, tmax, best_t, best_i);
+        bool lamb = false;
+        double nx = 0.0, ny = 0.0, nz = 0.0;
+        double *rec = nullptr;
+        if (alive) {
+            ++nseg;
+            R emit[3];
+            HitRec<R> h;
+            alive = shade_segment_nee<R, EXT>(sc, P, best_t, best_i, emit, h, lamb);
+            lamb = lamb && pp.lights.n > 0;
+            nx = (double)h.nx; ny = (double)h.ny; nz = (double)h.nz;
+            if (log && best_i >= 0 && nlog < pp.max_seg) { // shade_segment's record (a miss logs none); [12..23] stay zeros unless the vertex takes a light sample
+                rec = log + (size_t)nlog * RTMI_NEE_REC;
+                rec[0] = h.orig; rec[1] = h.t; rec[2] = h.px; rec[3] = h.py; rec[4] = h.pz; rec[5] = h.nx; rec[6] = h.ny; rec[7] = h.nz;
+                rec[8] = alive ? P.dx : 0; rec[9] = alive ? P.dy : 0; rec[10] = alive ? P.dz : 0; rec[11] = alive ? 1.0 : 0.0;
+                ++nlog;
+            }
+            if (!alive) {
+                const bool drop = sampled && best_i >= 0 && nee_sampled_light(pp.lights, best_i);
+                dropped = drop ? 1 : 0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rgb[c] = slot[c * kBlock] + (drop ? 0.0 : (double)emit[c]);
+            }
+        }
+        if (__any(lamb ? 1 : 0)) nee_vertex<R, VARIANT, EXT>(sc, lds, pp.lights, lamb, P.key, seg, P, nx, ny, nz, slot, rec);
+        sampled = lamb;
+        ++seg;
+    }
+    if (k < pp.n) {
+        pp.out_rgb[3 * k] = rgb[0]; pp.out_rgb[3 * k + 1] = rgb[1]; pp.out_rgb[3 * k + 2] = rgb[2];
+        if (pp.out_nseg) pp.out_nseg[k] = nseg;
+        if (pp.out_dropped) pp.out_dropped[k] = dropped;
+        if (pp.out_nlog) pp.out_nlog[k] = nlog;
+    }
+}
+
 // ---- edge-aware denoiser (rtmi_denoise*): an a-trous wavelet filter over planar FP64 images -----------------------------------------------------
 // Planes of nx * ny doubles: colour r, g, b and the variance of the mean V (two sets: a pass reads one and writes the other), then normal xyz,
 // albedo rgb and depth (read only).  Lanes run along x: every tap of a wave is one contiguous run per plane.
@@ -1877,6 +2156,7 @@ struct rtmi_ctx {
     DevBuf dn_planes; // rtmi_denoise*: the filter's planes (two colour + variance sets, the feature planes)
     DevBuf rays_ws;   // rtmi_render_rays*: the per-ray radiance nobody asked for (one pass of it)
     DevBuf occ_ws;    // rtmi_ambient_occlusion*: the first-hit records and the per-pixel counts nobody asked for
+    DevBuf nee_ws;    // rtmi_render_rays_nee*, rtmi_probe_paths_nee: the light table and the sampled lights' primitives
     DevBuf direct_ws; // rtmi_direct_irradiance*, rtmi_render_direct*: the light table, then the records and irradiance nobody asked for, then one pass of contributions
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -2576,7 +2856,7 @@ RTMI_EXPORT int rtmi_shutdown(rtmi_ctx *c) {
 #endif
     c->samples.release(); c->accum.release(); c->tiles.release(); c->tile_ids.release(); c->counters.release(); c->io.release(); c->multi.release();
     c->prog.release();
-    c->feat_cnt.release(); c->dn_planes.release(); c->rays_ws.release(); c->occ_ws.release(); c->direct_ws.release();
+    c->feat_cnt.release(); c->dn_planes.release(); c->rays_ws.release(); c->occ_ws.release(); c->direct_ws.release(); c->nee_ws.release();
     for (hipEvent_t e : {c->ev_done, c->ev_g0, c->ev_g1}) if (e) (void)hipEventDestroy(e);
     if (c->ev_consumed) { (void)hipSetDevice(c->ev_consumed_device); (void)hipEventDestroy(c->ev_consumed); (void)hipSetDevice(c->device); }
     for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -5999,4 +6279,218 @@ RTMI_EXPORT int rtmi_render_direct(rtmi_scene *s, int32_t precision, int32_t nx,
     if (rc) return rc;
     rc = with_real(precision, [&](auto r) { return render_direct_impl<decltype(r)>(s, nx, ny, T, n_samples, first, seed, d_state, d_lin, d_q, d_hits, d_cnt, c->stream); });
     return rc ? rc : io.finish();
+}
+
+// ---- path tracing with next-event estimation (rtmi_render_rays_nee*, rtmi_probe_paths_nee) ---------------------------------------------------------
+// rtmi_render_rays' passes and fold with rays_nee_kernel in rays_kernel's place.  The light table travels as the direct-lighting calls' does -- the
+// arguments of a one-wave kernel, in stream order -- followed by the sampled lights' primitive indices, which the closing-emission rule compares with.
+namespace {
+struct NeePass {
+    static constexpr bool wave_level = true;
+    // a media scene is refused before any launch, so the media-sequence operands of the chooser all name the one kernel
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT>; }
+};
+struct ProbePathsNee {
+    static constexpr bool wave_level = true;
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT>; }
+};
+
+struct NeeLightTable { LightTable t; int prim[RTMI_DIRECT_MAX_LIGHTS]; };
+constexpr size_t kNeeLightBytes = kLightTableBytes + sizeof(int) * RTMI_DIRECT_MAX_LIGHTS;
+__global__ void __launch_bounds__(64) set_nee_lights_kernel(NeeLightTable t, double *dst, int *dst_prim) {
+    for (int i = (int)threadIdx.x; i < t.t.n * kLightRec; i += 64) dst[i] = t.t.rec[i];
+    if ((int)threadIdx.x < t.t.n) dst_prim[threadIdx.x] = t.prim[threadIdx.x];
+}
+
+// the lights of a call and their primitives: the listed ones, each eligible, or all eligible ones
+int make_nee_lights(const rtmi_scene *s, int n_lights, const int32_t *light_prims, NeeLightTable &T) {
+    int32_t all[RTMI_DIRECT_MAX_LIGHTS];
+    if (!light_prims) {
+        int32_t count = 0;
+        list_lights(kept_arrays(s), RTMI_DIRECT_MAX_LIGHTS, all, &count);
+        if (count > RTMI_DIRECT_MAX_LIGHTS) return fail(RTMI_E_ARG, "the scene holds %d eligible lights, a call samples at most %d: pass a list", count, RTMI_DIRECT_MAX_LIGHTS);
+        n_lights = count; light_prims = all;
+    }
+    const int rc = make_light_table(s, n_lights, light_prims, T.t);
+    if (rc) return rc;
+    for (int l = 0; l < RTMI_DIRECT_MAX_LIGHTS; ++l) T.prim[l] = l < n_lights ? light_prims[l] : -1;
+    return RTMI_OK;
+}
+
+// the table on the device, queued on `st` ahead of the kernels that read it
+int upload_nee_lights(rtmi_ctx *c, const NeeLightTable &T, NeeLights &L, hipStream_t st) {
+    const int rc = c->nee_ws.ensure(kNeeLightBytes);
+    if (rc) return rc;
+    L.rec = reinterpret_cast<const double *>(c->nee_ws.p);
+    L.prim = reinterpret_cast<const int *>(static_cast<const char *>(c->nee_ws.p) + kLightTableBytes);
+    L.n = (unsigned)T.t.n;
+    hipLaunchKernelGGL(set_nee_lights_kernel, dim3(1), dim3(64), 0, st, T, const_cast<double *>(L.rec), const_cast<int *>(L.prim));
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+
+// what both entries check behind rtmi_render_rays' own checks, in the header's order; *work: is there anything to trace?
+int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work) {
+    *work = false;
+    if (light_prims && (n_lights < 0 || n_lights > RTMI_DIRECT_MAX_LIGHTS)) return fail(RTMI_E_ARG, "n_lights must be in [0, %d] (got %d)", RTMI_DIRECT_MAX_LIGHTS, n_lights);
+    if (n_groups == 0) return RTMI_OK;
+    if (s->dev.n_media > 0) return fail(RTMI_E_UNSUPPORTED, "the scene holds a ConstantMedium: shadow rays through media are not built");
+    *work = true;
+    return make_nee_lights(s, n_lights, light_prims, T);
+}
+
+// render_rays_impl with the light-sampling kernel (T.t.n >= 1); counters: four values
+template <typename R>
+int render_rays_nee_impl(rtmi_scene *s, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
+                         const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
+    rtmi_ctx *c = s->ctx;
+    int rc = c->counters.ensure(8 * sizeof(u64)); // [0..3] the counters when the caller passes no buffer, [4] the work-queue head
+    if (rc) return rc;
+    if (!d_cnt) d_cnt = reinterpret_cast<u64 *>(c->counters.p);
+    int per_pass = n_groups;
+    if (!d_out_rays) {
+        const int64_t group_bytes = (int64_t)group * 3 * (int64_t)sizeof(double);
+        per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(n_groups, c->workspace_bytes / group_bytes));
+        rc = c->rays_ws.ensure((size_t)per_pass * (size_t)group_bytes);
+        if (rc) return rc;
+    }
+    NeeParams np;
+    rc = upload_nee_lights(c, T, np.lights, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, 4 * sizeof(u64), st));
+    RaysParams &rp = np.rp;
+    rp.seed = seed; rp.ctr0 = ctr0; rp.depth = depth;
+    rp.group = (unsigned)group; rp.g_first = (unsigned)g_first;
+    rp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 4);
+    rp.counters = d_cnt;
+    const u64 n_rays = (u64)n_groups * (u64)group;
+    with_probe_kernel<NeePass, R>(s, [&](auto kern, size_t lds, int, int) {
+        rc = [&]() -> int {
+            int resident = 0;
+            const int rco = resident_blocks(c, reinterpret_cast<const void *>(kern), kBlock, lds, &resident);
+            if (rco) return rco;
+            const long long persistent = (long long)c->cus * std::max(1, std::min(c->blocks_per_cu, resident));
+            for (int g0 = 0; g0 < n_groups; g0 += per_pass) {
+                const int ng = std::min(per_pass, n_groups - g0);
+                const size_t row0 = (size_t)g0 * (size_t)group;
+                const long long items = (long long)ng * group;
+                rp.rays = d_rays + row0 * 7;
+                rp.keys = d_keys ? d_keys + row0 : nullptr;
+                rp.samples = d_out_rays ? d_out_rays + row0 * 3 : reinterpret_cast<double *>(c->rays_ws.p);
+                rp.row0 = (unsigned)row0; rp.total_items = (unsigned)items;
+                { // claim size: as rays_kernel's
+                    const long long per_wave = items / std::max(1, c->cus * 16);
+                    unsigned qb = 64u;
+                    while (qb < 1024u && per_wave >= (long long)qb * 16) qb *= 2;
+                    rp.qblock = qb;
+                }
+                hipEvent_t e1 = nullptr;
+                const int rce = open_timed(c, st, &e1);
+                if (rce) return rce;
+                HIP_TRY(hipMemsetAsync(rp.queue, 0, sizeof(unsigned), st));
+                const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(persistent, (items + kBlock - 1) / kBlock));
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, s->d_dev, np);
+                HIP_TRY(hipGetLastError());
+                if (e1) HIP_TRY(hipEventRecord(e1, st));
+                hipLaunchKernelGGL((rays_fold_kernel<R>), dim3((unsigned)((ng + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rp.samples, g0, ng, group,
+                                   d_state ? g_first : 0, d_state, d_mean, d_se, d_cnt, n_rays);
+                HIP_TRY(hipGetLastError());
+                if (e1) { const int rcf = close_timed_fold(c, st); if (rcf) return rcf; }
+            }
+            return RTMI_OK;
+        }();
+    });
+    return rc;
+}
+
+// no light to sample: the call is rtmi_render_rays; its two shadow-ray counters are zeros
+template <typename R>
+int render_rays_nee_any(rtmi_scene *s, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
+                        const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
+    if (T.t.n > 0) return render_rays_nee_impl<R>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, T, d_state, d_mean, d_se, d_out_rays, d_cnt, st);
+    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt + 2, 0, 2 * sizeof(u64), st));
+    return render_rays_impl<R>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st);
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_rays_nee_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const void *d_rays,
+                                            const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
+                                            void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream) {
+    int rc = check_rays_args(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr);
+    if (rc) return rc;
+    NeeLightTable T;
+    bool work = false;
+    rc = check_nee_args(s, n_groups, n_lights, light_prims, T, &work);
+    if (rc || !work) return rc;
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream_of(c, stream);
+    return with_real(precision, [&](auto r) {
+        return render_rays_nee_any<decltype(r)>(s, n_groups, group, g_first, reinterpret_cast<const double *>(d_rays), reinterpret_cast<const u64 *>(d_keys), seed,
+                                                ctr0, depth, T, reinterpret_cast<double *>(d_state), reinterpret_cast<double *>(d_out_mean),
+                                                reinterpret_cast<double *>(d_out_stderr), reinterpret_cast<double *>(d_out_rays),
+                                                reinterpret_cast<u64 *>(d_out_counters), st);
+    });
+}
+
+RTMI_EXPORT int rtmi_render_rays_nee(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const double *rays,
+                                     const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
+                                     double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters) {
+    int rc = check_rays_args(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr);
+    if (rc) return rc;
+    NeeLightTable T;
+    bool work = false;
+    rc = check_nee_args(s, n_groups, n_lights, light_prims, T, &work);
+    if (rc || !work) return rc;
+    if (state && g_first > 0)
+        for (int g = 0; g < n_groups; ++g)
+            if (state[(size_t)g * RTMI_RAYS_REC + 9] != (double)g_first)
+                return fail(RTMI_E_STATE, "group %d's record holds %g rays, g_first is %d", g, state[(size_t)g * RTMI_RAYS_REC + 9], g_first);
+    rtmi_ctx *c = s->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)n_groups * (size_t)group, ng = (size_t)n_groups;
+    HostIo io(c);
+    double *d_rays, *d_state, *d_mean, *d_se, *d_out;
+    u64 *d_keys, *d_cnt;
+    io.in(&d_rays, 7 * n, rays); io.in(&d_keys, n, keys);
+    io.plane(&d_state, ng * RTMI_RAYS_REC, state != nullptr, g_first > 0 ? state : nullptr, state); // a first chunk (g_first = 0) reads no records
+    io.out(&d_mean, 3 * ng, out_mean); io.out(&d_se, ng, out_stderr); io.work(&d_cnt, 4, out_counters); io.out(&d_out, 3 * n, out_rays);
+    rc = io.stage();
+    if (rc) return rc;
+    rc = with_real(precision, [&](auto r) {
+        return render_rays_nee_any<decltype(r)>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, T, d_state, d_mean, d_se, d_out, d_cnt, c->stream);
+    });
+    return rc ? rc : io.finish();
+}
+
+RTMI_EXPORT int rtmi_probe_paths_nee(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
+                                     int32_t n_lights, const int32_t *light_prims, double *out_rgb, uint64_t *out_nseg, int32_t *out_dropped, double *log,
+                                     int32_t max_seg, int32_t *out_nlog) {
+    int rc = probe_begin(s, precision, n);
+    if (rc || n == 0) return rc;
+    if (!rays || !keys || !out_rgb) return fail(RTMI_E_ARG, "NULL array");
+    if (log && max_seg <= 0) return fail(RTMI_E_ARG, "log given but max_seg <= 0");
+    if (precision == RTMI_F32 && s->dev.has_ext) return fail(RTMI_E_UNSUPPORTED, "rectangles / triangles / instances are FP64 only");
+    NeeLightTable T;
+    bool work = false;
+    rc = check_nee_args(s, n, n_lights, light_prims, T, &work);
+    if (rc) return rc;
+    rtmi_ctx *c = s->ctx;
+    HostIo io(c);
+    NeeProbeParams pp{};
+    double *d_rays, *d_rgb, *d_log;
+    u64 *d_keys, *d_nseg;
+    int *d_dropped, *d_nlog;
+    const size_t log_words = log ? (size_t)n * max_seg * RTMI_NEE_REC : 0;
+    io.in(&d_rays, (size_t)n * 7, rays); io.in(&d_keys, (size_t)n, keys); io.out(&d_rgb, (size_t)n * 3, out_rgb);
+    io.out(&d_nseg, (size_t)n, out_nseg); io.out(&d_dropped, (size_t)n, out_dropped); io.out(&d_nlog, (size_t)n, out_nlog);
+    io.out(&d_log, log_words, log);
+    pp.n = n; pp.ctr0 = (unsigned)ctr0; pp.depth = depth; pp.max_seg = max_seg;
+    return probe_run(io, n, [&](hipStream_t st, dim3 grid) {
+        pp.rays = d_rays; pp.keys = d_keys; pp.out_rgb = d_rgb; pp.out_nseg = d_nseg; pp.out_dropped = d_dropped; pp.out_nlog = d_nlog; pp.log = d_log;
+        if (upload_nee_lights(c, T, pp.lights, st) != RTMI_OK) return; // (probe_run reports a launch error)
+        if (d_log && hipMemsetAsync(d_log, 0, log_words * sizeof(double), st) != hipSuccess) return;
+        auto run = [&](auto kern, size_t lds, int, int) { hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, s->d_dev, pp); };
+        with_real(precision, [&](auto r) { with_probe_kernel<ProbePathsNee, decltype(r)>(s, run); });
+    });
 }

@@ -2435,4 +2435,19 @@ __device__ inline bool shade_segment(SceneRef sc, Path<R> &P, R t, int orig, Seg
     return scat;
 }
 
+// shade_segment for the paths that sample lights (rtmi_render_rays_nee*, rtmi_probe_paths_nee): the same resolve and the same scatter_emit on the same
+// stream, so P, emit and the return value are shade_segment's bit for bit; it also hands out the record (zeros on a miss) and whether the vertex
+// scattered as RTMI_MAT_LAMBERTIAN -- scatter_emit's `live` already holds core.clj's (pos? depth).  The attenuation after the vertex is P.ar, P.ag, P.ab.
+template <typename R, bool EXT = false>
+__device__ inline bool shade_segment_nee(SceneRef sc, Path<R> &P, R t, int orig, R *emit, HitRec<R> &h, bool &lamb) {
+    emit[0] = emit[1] = emit[2] = R(0);
+    lamb = false;
+    h.px = h.py = h.pz = h.nx = h.ny = h.nz = h.u = h.v = h.t = R(0); h.mat = 0; h.orig = 0; h.kind = 0;
+    if (orig < 0) return false; // miss: (color) returns accum, core.clj:40-41
+    resolve_any<R, EXT>(sc, P, t, orig, h, false);
+    const bool scat = scatter_emit<R, EXT>(sc, P, h, nullptr, emit);
+    lamb = scat && sc.mat_kind[h.mat] == RTMI_MAT_LAMBERTIAN;
+    return scat;
+}
+
 } // namespace rtmi
