@@ -591,14 +591,9 @@ class DeviceScene:
                                                            ptr(stream)))
 
     # ---- caller-supplied rays: panoramas, orthographic views, bakers, probes ------------------------------------------------------------
-    def render_rays(self, rays, group=1, keys=None, seed=RENDER_SEED, ctr0=0, depth=DEFAULT_DEPTH, precision="f64", first=0, state=None,
-                    return_rays=False):
-        """One path per ray: rays [n_groups * group, 7] = origin, direction, time; ray r of group g is row g * group + r.  Its stream is keyed
-        keys[row], or sample_key(seed, g, first + r) without keys, and starts at draw ctr0.  -> (mean [n_groups, 3] = the group's rays folded in
-        row order as a frame folds a pixel's samples, stderr [n_groups] = render_progressive's noise estimate per group, counters {segments traced,
-        rays}, rays' radiance [n, 3] or None).  state ([n_groups, RAYS_REC] float64, updated in place; first = 0 starts it, first > 0 continues
-        it and must be the rays every group already holds): mean and stderr are then over all rays so far, and any split of a group's rays into
-        consecutive calls gives the bits of one call."""
+    @staticmethod
+    def _rays_inputs(rays, group, keys, state):
+        """render_rays' and render_rays_nee's arrays -> (rays [n, 7], group, n_groups, keys [n] or None); a state must have its layout"""
         rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
         group = int(group)
         if group <= 0 or len(rays) % group:
@@ -611,6 +606,32 @@ class DeviceScene:
         if state is not None and (not isinstance(state, np.ndarray) or state.dtype != np.float64 or not state.flags.c_contiguous
                                   or state.shape != (n_groups, _ffi.RAYS_REC)):
             raise ValueError("state must be a C-contiguous float64 array [n_groups, %d]" % _ffi.RAYS_REC)
+        return rays, group, n_groups, keys
+
+    def _fold_chunks(self, nx, ny, ns, chunk, rays_of, trace, n_counters, **trace_args):
+        """An nx x ny x ns image in chunks of `chunk` samples per pixel folded into one state: rays_of(k, n) -> (rays, ctr0) for samples
+        [k, k + n) of every pixel, grouped per pixel; trace = render_rays or render_rays_nee -> (linear, rgb8, stderr, the counters summed)"""
+        state = np.zeros((nx * ny, _ffi.RAYS_REC), np.float64)
+        total = np.zeros(n_counters, np.uint64)
+        k = 0
+        while k < ns:
+            n = min(chunk, ns - k)
+            rays, ctr0 = rays_of(k, n)
+            mean, err, cnt, _ = trace(rays, group=n, ctr0=ctr0, first=k, state=state, **trace_args)
+            total += cnt
+            k += n
+        lin = np.ascontiguousarray(mean.reshape(ny, nx, 3)[::-1])  # group j * nx + i, j = 0 at the bottom
+        return lin, self.ctx.denoise(lin, iterations=0)[1], np.ascontiguousarray(err.reshape(ny, nx)[::-1]), total
+
+    def render_rays(self, rays, group=1, keys=None, seed=RENDER_SEED, ctr0=0, depth=DEFAULT_DEPTH, precision="f64", first=0, state=None,
+                    return_rays=False):
+        """One path per ray: rays [n_groups * group, 7] = origin, direction, time; ray r of group g is row g * group + r.  Its stream is keyed
+        keys[row], or sample_key(seed, g, first + r) without keys, and starts at draw ctr0.  -> (mean [n_groups, 3] = the group's rays folded in
+        row order as a frame folds a pixel's samples, stderr [n_groups] = render_progressive's noise estimate per group, counters {segments traced,
+        rays}, rays' radiance [n, 3] or None).  state ([n_groups, RAYS_REC] float64, updated in place; first = 0 starts it, first > 0 continues
+        it and must be the rays every group already holds): mean and stderr are then over all rays so far, and any split of a group's rays into
+        consecutive calls gives the bits of one call."""
+        rays, group, n_groups, keys = self._rays_inputs(rays, group, keys, state)
         mean, err, cnt = np.zeros((n_groups, 3), np.float64), np.zeros(n_groups, np.float64), np.zeros(2, np.uint64)
         out = np.zeros((len(rays), 3), np.float64) if return_rays else None
         check(_ffi.lib().rtmi_render_rays(self.handle, _PRECISION[precision], n_groups, group, int(first), ptr(rays), ptr(keys), int(seed), int(ctr0),
@@ -634,21 +655,11 @@ class DeviceScene:
         `lights`; four counters)."""
         if chunk <= 0 or ns <= 0:
             raise ValueError("ns and chunk must be > 0")
-        state = np.zeros((nx * ny, _ffi.RAYS_REC), np.float64)
-        total = np.zeros(4 if nee else 2, np.uint64)
-        k = 0
-        while k < ns:
-            n = min(chunk, ns - k)
-            rays, ctr0 = generator(nx, ny, k, n, seed=seed, **generator_args)
-            if nee:
-                mean, err, cnt, _ = self.render_rays_nee(rays, group=n, lights=lights, seed=seed, ctr0=ctr0, depth=depth, precision=precision, first=k,
-                                                         state=state)
-            else:
-                mean, err, cnt, _ = self.render_rays(rays, group=n, seed=seed, ctr0=ctr0, depth=depth, precision=precision, first=k, state=state)
-            total += cnt
-            k += n
-        lin = np.ascontiguousarray(mean.reshape(ny, nx, 3)[::-1])  # group j * nx + i, j = 0 at the bottom
-        return lin, self.ctx.denoise(lin, iterations=0)[1], np.ascontiguousarray(err.reshape(ny, nx)[::-1]), total
+        def rays_of(k, n):
+            return generator(nx, ny, k, n, seed=seed, **generator_args)
+        if nee:
+            return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_nee, 4, lights=lights, seed=seed, depth=depth, precision=precision)
+        return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays, 2, seed=seed, depth=depth, precision=precision)
 
     # ---- path tracing with next-event estimation: render_rays whose Lambertian vertices also sample the area lights -------------------------
     def render_rays_nee(self, rays, group=1, lights=None, keys=None, seed=RENDER_SEED, ctr0=0, depth=DEFAULT_DEPTH, precision="f64", first=0,
@@ -658,18 +669,7 @@ class DeviceScene:
         (stream, hits, scatters, segments) is render_rays' bit for bit and the estimate has the same expectation; on a lit scene its variance is
         a fraction.  No lights: the call is render_rays.  A scene with a ConstantMedium is refused.  -> render_rays' tuple, the counters being
         {segments, rays, shadow rays built, shadow rays occluded}."""
-        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
-        group = int(group)
-        if group <= 0 or len(rays) % group:
-            raise ValueError("%d rays are not whole groups of %d" % (len(rays), group))
-        n_groups = len(rays) // group
-        if keys is not None:
-            keys = np.ascontiguousarray(keys, np.uint64).reshape(-1)
-            if len(keys) != len(rays):
-                raise ValueError("%d keys for %d rays" % (len(keys), len(rays)))
-        if state is not None and (not isinstance(state, np.ndarray) or state.dtype != np.float64 or not state.flags.c_contiguous
-                                  or state.shape != (n_groups, _ffi.RAYS_REC)):
-            raise ValueError("state must be a C-contiguous float64 array [n_groups, %d]" % _ffi.RAYS_REC)
+        rays, group, n_groups, keys = self._rays_inputs(rays, group, keys, state)
         lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
         mean, err, cnt = np.zeros((n_groups, 3), np.float64), np.zeros(n_groups, np.float64), np.zeros(4, np.uint64)
         out = np.zeros((len(rays), 3), np.float64) if return_rays else None
@@ -696,22 +696,14 @@ class DeviceScene:
         if nx <= 0 or ny <= 0 or chunk <= 0 or ns <= 0:
             raise ValueError("nx, ny, ns and chunk must be > 0")
         film, lens, paths = (util.sample_key(seed, k, 0) for k in range(3))
-        state = np.zeros((nx * ny, _ffi.RAYS_REC), np.float64)
-        total = np.zeros(4, np.uint64)
-        k = 0
-        while k < ns:
-            n = min(chunk, ns - k)
+
+        def rays_of(k, n):
             pix, ss = (a.ravel() for a in np.meshgrid(np.arange(nx * ny), np.arange(k, k + n), indexing="ij"))
             fk = util.sample_keys(film, pix, ss)
             u = ((pix % nx).astype(np.float64) + util.draw_uniforms(fk, 0)) / np.float64(nx)
             v = ((pix // nx).astype(np.float64) + util.draw_uniforms(fk, 1)) / np.float64(ny)
-            rays = self.probe_camera(np.stack([u, v], axis=1), util.sample_keys(lens, pix, ss), precision=precision)[:, :7]
-            mean, err, cnt, _ = self.render_rays_nee(rays, group=n, lights=lights, seed=paths, ctr0=0, depth=depth, precision=precision, first=k,
-                                                     state=state)
-            total += cnt
-            k += n
-        lin = np.ascontiguousarray(mean.reshape(ny, nx, 3)[::-1])  # group j * nx + i, j = 0 at the bottom
-        return lin, self.ctx.denoise(lin, iterations=0)[1], np.ascontiguousarray(err.reshape(ny, nx)[::-1]), total
+            return self.probe_camera(np.stack([u, v], axis=1), util.sample_keys(lens, pix, ss), precision=precision)[:, :7], 0
+        return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_nee, 4, lights=lights, seed=paths, depth=depth, precision=precision)
 
     # ---- closest-hit and any-hit queries: picking, first hits, shadow / ambient-occlusion / line-of-sight rays --------------------------------
     @staticmethod

@@ -2329,6 +2329,33 @@ int resident_blocks(rtmi_ctx *c, const void *kern, int block, size_t lds_bytes, 
     return RTMI_OK;
 }
 
+// One launch on `st` of a persistent-queue kernel (rays_kernel, rays_nee_kernel, query_kernel) over `items` work items, and its timing interval:
+// as many blocks as stay resident, none without an item, behind the zeroed queue head.  launch(grid, total_items, qblock) puts the two numbers into
+// the kernel's argument struct and starts it.  fold() starts what reduces the kernel's output, if anything does: the interval's reduce part
+// (rtmi_last_reduce_ms) ends behind it.
+struct NoFold { void operator()() const {} };
+template <typename Launch, typename Fold = NoFold>
+int queue_launch(rtmi_ctx *c, hipStream_t st, const void *kern, size_t lds, unsigned *queue, long long items, Launch launch, Fold fold = Fold{}) {
+    int resident = 0;
+    const int rc = resident_blocks(c, kern, kBlock, lds, &resident);
+    if (rc) return rc;
+    const long long persistent = (long long)c->cus * std::max(1, std::min(c->blocks_per_cu, resident));
+    // claim size: short claims on small launches (the tail matters), longer ones when a wave has many ahead of it
+    const long long per_wave = items / std::max(1, c->cus * 16);
+    unsigned qb = 64u;
+    while (qb < 1024u && per_wave >= (long long)qb * 16) qb *= 2;
+    hipEvent_t e1 = nullptr;
+    const int rce = open_timed(c, st, &e1);
+    if (rce) return rce;
+    HIP_TRY(hipMemsetAsync(queue, 0, sizeof(unsigned), st));
+    launch(dim3((unsigned)std::max<long long>(1, std::min<long long>(persistent, (items + kBlock - 1) / kBlock))), (unsigned)items, qb);
+    HIP_TRY(hipGetLastError());
+    if (e1) HIP_TRY(hipEventRecord(e1, st));
+    fold();
+    HIP_TRY(hipGetLastError());
+    return e1 ? close_timed_fold(c, st) : RTMI_OK;
+}
+
 // the stream of a call: the caller's, or the context's own
 hipStream_t stream_of(const rtmi_ctx *c, void *stream) { return stream ? reinterpret_cast<hipStream_t>(stream) : c->stream; }
 
@@ -2751,6 +2778,26 @@ struct HostIo {
     int stage() { const int rc = reserve(); if (rc) return rc; HIP_TRY(upload()); return RTMI_OK; }
     int finish() const { HIP_TRY(hipGetLastError()); HIP_TRY(download()); return RTMI_OK; }
 };
+
+// The two forms of an entry differ in where its planes lie.  What they share -- the checks, the light table, hipSetDevice -- is the family's
+// *_begin, and the launches are its *_run or *_impl, which takes device pointers and a stream.  A _device form casts the caller's pointers
+// (as<T>) and takes the caller's stream (stream_of); a host form names its planes in a HostIo and hands the launches to host_run: the inputs go
+// up, launches(stream) queues the call on the context's stream, the outputs come back.
+template <typename T, typename V> T *as(V *p) { return reinterpret_cast<T *>(p); }
+template <typename Launches> int host_run(HostIo &io, Launches launches) {
+    int rc = io.stage();
+    if (!rc) rc = launches(io.c->stream);
+    return rc ? rc : io.finish();
+}
+// A host state that continues an estimate (first > 0) holds `first` in every record's count, slot `at` of `stride` doubles; the message names
+// the records ("group") and what they count, as the header's argument is called ("rays, g_first")
+int check_state_counts(const double *state, size_t n, int stride, int at, int first, const char *noun, const char *counted) {
+    if (state && first > 0)
+        for (size_t g = 0; g < n; ++g)
+            if (state[g * stride + at] != (double)first)
+                return fail(RTMI_E_STATE, "%s %zu's record holds %g %s is %d", noun, g, state[g * stride + at], counted, first);
+    return RTMI_OK;
+}
 
 // The planes of the frame host forms, for npx pixels: linear [npx][3] doubles and rgb8 [npx][3] bytes always; stderr [npx] doubles, the two metrics
 // counters and samples [npx] ints where wanted (else null).  Each comes back to the host array the caller gave for it.  (A progressive frame keeps
@@ -5466,13 +5513,73 @@ namespace {
 // workgroup barriers and are answered with the scalar-cache scan, which finds the same hit (as the feature pass)
 struct RaysPass {
     static constexpr bool wave_level = true;
+    using Args = RaysParams; // the kernel's argument struct, and the RaysParams in it
+    static RaysParams &rays(Args &a) { return a; }
+    static constexpr int n_counters = 2;
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MSEQ>; }
 };
 
 constexpr long long kRaysMax = (1ll << 31) - 64; // rays per call: 32-bit work items, and a claim past the end must not wrap the queue head
 
-// the argument checks of both entries, in the header's order
-int check_rays_args(rtmi_scene *s, int precision, int n_groups, int group, int g_first, int depth, const void *rays, const void *mean, const void *se) {
+// The launches, all on `st`, every pointer a device pointer: passes of whole groups, each one launch of the family's kernel followed by its fold.  With
+// d_out_rays the call is one pass into it; without, a pass holds as many groups as option "workspace_bytes" allows (at least one) in c->rays_ws.
+// Family: RaysPass, or NeePass with upload_lights(args, st) queueing its table ahead of the passes.  c->counters: the family's counters when the
+// caller passes no buffer, then the work-queue head.
+struct NoLights { int operator()(RaysParams &, hipStream_t) const { return RTMI_OK; } };
+template <typename R, typename Family, typename Lights>
+int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
+                     double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st, Lights upload_lights) {
+    rtmi_ctx *c = s->ctx;
+    int rc = c->counters.ensure(8 * sizeof(u64));
+    if (rc) return rc;
+    if (!d_cnt) d_cnt = reinterpret_cast<u64 *>(c->counters.p);
+    int per_pass = n_groups;
+    if (!d_out_rays) {
+        const int64_t group_bytes = (int64_t)group * 3 * (int64_t)sizeof(double);
+        per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(n_groups, c->workspace_bytes / group_bytes));
+        rc = c->rays_ws.ensure((size_t)per_pass * (size_t)group_bytes);
+        if (rc) return rc;
+    }
+    typename Family::Args args;
+    rc = upload_lights(args, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, Family::n_counters * sizeof(u64), st));
+    RaysParams &rp = Family::rays(args);
+    rp.seed = seed; rp.ctr0 = ctr0; rp.depth = depth;
+    rp.group = (unsigned)group; rp.g_first = (unsigned)g_first;
+    rp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + Family::n_counters);
+    rp.counters = d_cnt;
+    const u64 n_rays = (u64)n_groups * (u64)group;
+    with_probe_kernel<Family, R>(s, [&](auto kern, size_t lds, int, int) {
+        for (int g0 = 0; g0 < n_groups && !rc; g0 += per_pass) {
+            const int ng = std::min(per_pass, n_groups - g0);
+            const size_t row0 = (size_t)g0 * (size_t)group;
+            rp.rays = d_rays + row0 * 7;
+            rp.keys = d_keys ? d_keys + row0 : nullptr;
+            rp.samples = d_out_rays ? d_out_rays + row0 * 3 : reinterpret_cast<double *>(c->rays_ws.p);
+            rp.row0 = (unsigned)row0;
+            rc = queue_launch(c, st, reinterpret_cast<const void *>(kern), lds, rp.queue, (long long)ng * group,
+                              [&](dim3 grid, unsigned items, unsigned qblock) {
+                                  rp.total_items = items; rp.qblock = qblock;
+                                  hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, s->d_dev, args);
+                              },
+                              [&] {
+                                  hipLaunchKernelGGL((rays_fold_kernel<R>), dim3((unsigned)((ng + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rp.samples, g0, ng,
+                                                     group, d_state ? g_first : 0, d_state, d_mean, d_se, d_cnt, n_rays);
+                              });
+        }
+    });
+    return rc;
+}
+
+// What both forms of rtmi_render_rays* and rtmi_render_rays_nee* do first: the argument checks in the header's order (with T the light-sampling
+// call's behind the plain call's: check_nee_args, beside its table below), a host form's state, then the scene's device is current.  *work
+// false: nothing to trace, the entry returns RTMI_OK at once.
+struct NeeLightTable;
+int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work);
+int rays_begin(rtmi_scene *s, int precision, int n_groups, int group, int g_first, int depth, const void *rays, const void *mean, const void *se,
+               const double *host_state, bool *work, NeeLightTable *T = nullptr, int n_lights = 0, const int32_t *light_prims = nullptr) {
+    *work = false;
     if (n_groups < 0 || group <= 0 || g_first < 0 || depth < 0)
         return fail(RTMI_E_ARG, "n_groups, g_first, depth must be >= 0 and group > 0 (got %d %d %d %d)", n_groups, g_first, depth, group);
     if ((long long)n_groups * group > kRaysMax) return fail(RTMI_E_ARG, "n_groups * group = %lld rays exceed 2^31 - 64", (long long)n_groups * group);
@@ -5484,114 +5591,50 @@ int check_rays_args(rtmi_scene *s, int precision, int n_groups, int group, int g
     if (precision == RTMI_F32 && s->dev.has_ext) return fail(RTMI_E_UNSUPPORTED, "rectangles / triangles / instances / procedural textures are traced by the FP64 kernels only");
     if (s->uses_perlin && !s->have_perlin) return fail(RTMI_E_STATE, "the scene holds a Perlin texture: call rtmi_scene_set_perlin first");
     if (s->max_image >= s->dev.n_images) return fail(RTMI_E_STATE, "the scene holds an ImageMap with index %d: call rtmi_scene_set_images first", s->max_image);
+    *work = n_groups > 0;
+    int rc = T ? check_nee_args(s, n_groups, n_lights, light_prims, *T, work) : RTMI_OK;
+    if (rc || !*work) return rc;
+    rc = check_state_counts(host_state, (size_t)n_groups, RTMI_RAYS_REC, 9, g_first, "group", "rays, g_first");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->ctx->device));
     return RTMI_OK;
 }
 
-// The launches, all on `st`, every pointer a device pointer: passes of whole groups, each one rays_kernel launch followed by its fold.  With
-// d_out_rays the call is one pass into it; without, a pass holds as many groups as option "workspace_bytes" allows (at least one) in c->rays_ws.
-template <typename R>
-int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
-                     double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
-    rtmi_ctx *c = s->ctx;
-    int rc = c->counters.ensure(8 * sizeof(u64)); // [0..1] the counters when the caller passes no buffer, [2] the work-queue head
-    if (rc) return rc;
-    if (!d_cnt) d_cnt = reinterpret_cast<u64 *>(c->counters.p);
-    int per_pass = n_groups;
-    if (!d_out_rays) {
-        const int64_t group_bytes = (int64_t)group * 3 * (int64_t)sizeof(double);
-        per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(n_groups, c->workspace_bytes / group_bytes));
-        rc = c->rays_ws.ensure((size_t)per_pass * (size_t)group_bytes);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, 2 * sizeof(u64), st));
-    RaysParams rp;
-    rp.seed = seed; rp.ctr0 = ctr0; rp.depth = depth;
-    rp.group = (unsigned)group; rp.g_first = (unsigned)g_first;
-    rp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 2);
-    rp.counters = d_cnt;
-    const u64 n_rays = (u64)n_groups * (u64)group;
-    with_probe_kernel<RaysPass, R>(s, [&](auto kern, size_t lds, int, int) {
-        rc = [&]() -> int {
-            int resident = 0;
-            const int rco = resident_blocks(c, reinterpret_cast<const void *>(kern), kBlock, lds, &resident);
-            if (rco) return rco;
-            const long long persistent = (long long)c->cus * std::max(1, std::min(c->blocks_per_cu, resident));
-            for (int g0 = 0; g0 < n_groups; g0 += per_pass) {
-                const int ng = std::min(per_pass, n_groups - g0);
-                const size_t row0 = (size_t)g0 * (size_t)group;
-                const long long items = (long long)ng * group;
-                rp.rays = d_rays + row0 * 7;
-                rp.keys = d_keys ? d_keys + row0 : nullptr;
-                rp.samples = d_out_rays ? d_out_rays + row0 * 3 : reinterpret_cast<double *>(c->rays_ws.p);
-                rp.row0 = (unsigned)row0; rp.total_items = (unsigned)items;
-                { // claim size: short claims on small launches (the tail matters), longer ones when a wave has many ahead of it
-                    const long long per_wave = items / std::max(1, c->cus * 16);
-                    unsigned qb = 64u;
-                    while (qb < 1024u && per_wave >= (long long)qb * 16) qb *= 2;
-                    rp.qblock = qb;
-                }
-                hipEvent_t e1 = nullptr;
-                const int rce = open_timed(c, st, &e1);
-                if (rce) return rce;
-                HIP_TRY(hipMemsetAsync(rp.queue, 0, sizeof(unsigned), st));
-                const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(persistent, (items + kBlock - 1) / kBlock));
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, s->d_dev, rp);
-                HIP_TRY(hipGetLastError());
-                if (e1) HIP_TRY(hipEventRecord(e1, st));
-                hipLaunchKernelGGL((rays_fold_kernel<R>), dim3((unsigned)((ng + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rp.samples, g0, ng, group,
-                                   d_state ? g_first : 0, d_state, d_mean, d_se, d_cnt, n_rays);
-                HIP_TRY(hipGetLastError());
-                if (e1) { const int rcf = close_timed_fold(c, st); if (rcf) return rcf; }
-            }
-            return RTMI_OK;
-        }();
+int rays_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
+             double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
+    return with_real(precision, [&](auto r) {
+        return render_rays_impl<decltype(r), RaysPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
+                                                       NoLights{});
     });
-    return rc;
 }
 } // namespace
 
 RTMI_EXPORT int rtmi_render_rays_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const void *d_rays,
                                         const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth, void *d_state, void *d_out_mean,
                                         void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream) {
-    int rc = check_rays_args(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr);
-    if (rc) return rc;
-    if (n_groups == 0) return RTMI_OK;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream_of(c, stream);
-    return with_real(precision, [&](auto r) {
-        return render_rays_impl<decltype(r)>(s, n_groups, group, g_first, reinterpret_cast<const double *>(d_rays), reinterpret_cast<const u64 *>(d_keys), seed,
-                                             ctr0, depth, reinterpret_cast<double *>(d_state), reinterpret_cast<double *>(d_out_mean),
-                                             reinterpret_cast<double *>(d_out_stderr), reinterpret_cast<double *>(d_out_rays),
-                                             reinterpret_cast<u64 *>(d_out_counters), st);
-    });
+    bool work = false;
+    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr, nullptr, &work);
+    if (rc || !work) return rc;
+    return rays_run(s, precision, n_groups, group, g_first, as<const double>(d_rays), as<const u64>(d_keys), seed, ctr0, depth, as<double>(d_state),
+                    as<double>(d_out_mean), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream));
 }
 
 RTMI_EXPORT int rtmi_render_rays(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const double *rays,
                                  const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth, double *state, double *out_mean, double *out_stderr,
                                  double *out_rays, uint64_t *out_counters) {
-    int rc = check_rays_args(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr);
-    if (rc) return rc;
-    if (n_groups == 0) return RTMI_OK;
-    if (state && g_first > 0)
-        for (int g = 0; g < n_groups; ++g)
-            if (state[(size_t)g * RTMI_RAYS_REC + 9] != (double)g_first)
-                return fail(RTMI_E_STATE, "group %d's record holds %g rays, g_first is %d", g, state[(size_t)g * RTMI_RAYS_REC + 9], g_first);
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
+    bool work = false;
+    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr, state, &work);
+    if (rc || !work) return rc;
     const size_t n = (size_t)n_groups * (size_t)group, ng = (size_t)n_groups;
-    HostIo io(c);
+    HostIo io(s->ctx);
     double *d_rays, *d_state, *d_mean, *d_se, *d_out;
     u64 *d_keys, *d_cnt;
     io.in(&d_rays, 7 * n, rays); io.in(&d_keys, n, keys);
     io.plane(&d_state, ng * RTMI_RAYS_REC, state != nullptr, g_first > 0 ? state : nullptr, state); // a first chunk (g_first = 0) reads no records
     io.out(&d_mean, 3 * ng, out_mean); io.out(&d_se, ng, out_stderr); io.work(&d_cnt, 2, out_counters); io.out(&d_out, 3 * n, out_rays);
-    rc = io.stage();
-    if (rc) return rc;
-    rc = with_real(precision, [&](auto r) {
-        return render_rays_impl<decltype(r)>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out, d_cnt, c->stream);
+    return host_run(io, [&](hipStream_t st) {
+        return rays_run(s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out, d_cnt, st);
     });
-    return rc ? rc : io.finish();
 }
 
 // ---- closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*) --------------------------------------------------------------------
@@ -5619,11 +5662,11 @@ int check_query_args(rtmi_scene *s, int precision, long long n, bool dims_ok, co
 }
 
 // The launch, on `st`, every pointer a device pointer: counters (and group counts) zeroed, then one query_kernel over the n rays.  gen: the src_* fields
-// and out_rays of a generated source (SRC != SRC_MEMORY, which reads no d_rays).
-template <typename R, bool ANY, int SRC = SRC_MEMORY>
+// and out_rays of a generated source (SRC != SRC_MEMORY, which reads no d_rays).  fold: what reduces the kernel's output, inside its timing interval.
+template <typename R, bool ANY, int SRC = SRC_MEMORY, typename Fold = NoFold>
 int query_impl(rtmi_scene *s, int n, int n_groups, int group, const double *d_rays, const double *d_range, double t_min, double t_max, const u64 *d_keys,
                unsigned ctr0, double *d_hits, unsigned char *d_occ, int *d_count, u64 *d_cnt, hipStream_t st, const QueryParams *gen = nullptr,
-               bool keep_counters = false) { // keep_counters: a later pass of one call adds to what its earlier passes counted
+               bool keep_counters = false, Fold fold = Fold{}) { // keep_counters: a later pass of one call adds to what its earlier passes counted
     rtmi_ctx *c = s->ctx;
     int rc = c->counters.ensure(8 * sizeof(u64)); // [0..1] the counters when the caller passes no buffer, [2] the work-queue head, [3..4] traversal counters
     if (rc) return rc;
@@ -5637,32 +5680,17 @@ int query_impl(rtmi_scene *s, int n, int n_groups, int group, const double *d_ra
     }
     QueryParams qp = gen ? *gen : QueryParams{};
     qp.rays = d_rays; qp.t_range = d_range; qp.keys = d_keys; qp.tmin = t_min; qp.tmax = t_max; qp.ctr0 = ctr0;
-    qp.group = (unsigned)std::max(1, group); qp.total_items = (unsigned)n;
+    qp.group = (unsigned)std::max(1, group);
     qp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 2);
     qp.hits = d_hits; qp.occluded = d_occ; qp.count = d_count; qp.counters = d_cnt;
     qp.trav = reinterpret_cast<u64 *>(c->counters.p) + 3;
-    { // claim size: as rays_kernel's
-        const long long per_wave = (long long)n / std::max(1, c->cus * 16);
-        unsigned qb = 64u;
-        while (qb < 1024u && per_wave >= (long long)qb * 16) qb *= 2;
-        qp.qblock = qb;
-    }
     auto run = [&](auto kern, size_t lds, int, int) {
-        rc = [&]() -> int {
-            int resident = 0;
-            const int rco = resident_blocks(c, reinterpret_cast<const void *>(kern), kBlock, lds, &resident);
-            if (rco) return rco;
-            const long long persistent = (long long)c->cus * std::max(1, std::min(c->blocks_per_cu, resident));
-            hipEvent_t e1 = nullptr;
-            const int rce = open_timed(c, st, &e1);
-            if (rce) return rce;
-            HIP_TRY(hipMemsetAsync(qp.queue, 0, sizeof(unsigned), st));
-            const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(persistent, ((long long)n + kBlock - 1) / kBlock));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, s->d_dev, qp);
-            HIP_TRY(hipGetLastError());
-            if (e1) { HIP_TRY(hipEventRecord(e1, st)); return close_timed_fold(c, st); } // (no fold follows: an empty fold interval)
-            return RTMI_OK;
-        }();
+        rc = queue_launch(c, st, reinterpret_cast<const void *>(kern), lds, qp.queue, n,
+                          [&](dim3 grid, unsigned items, unsigned qblock) {
+                              qp.total_items = items; qp.qblock = qblock;
+                              hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, s->d_dev, qp);
+                          },
+                          fold);
     };
     // a tree over a handful of mixed-kind primitives costs more than scanning them (choose_trace_kernel): the same shortcut, the same knobs
     const LaunchKnobs knobs = read_launch_knobs();
@@ -5671,78 +5699,73 @@ int query_impl(rtmi_scene *s, int n, int n_groups, int group, const double *d_ra
     else with_probe_kernel<QueryPass<ANY, false, SRC>, R>(s, run, flat);
     return rc;
 }
+
+// what both forms of the two calls do first: the checks, then (with rays to trace) the scene's device is current
+int query_begin(rtmi_scene *s, int precision, long long n, bool dims_ok, const void *rays, bool out_ok) {
+    const int rc = check_query_args(s, precision, n, dims_ok, rays, out_ok);
+    if (rc || n == 0) return rc;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    return RTMI_OK;
+}
+int query_hits_run(rtmi_scene *s, int precision, int n, const double *d_rays, const double *d_range, double t_min, double t_max, const u64 *d_keys,
+                   unsigned ctr0, double *d_hits, u64 *d_cnt, hipStream_t st) {
+    return with_real(precision, [&](auto r) {
+        return query_impl<decltype(r), false>(s, n, 0, 1, d_rays, d_range, t_min, t_max, d_keys, ctr0, d_hits, nullptr, nullptr, d_cnt, st);
+    });
+}
+int query_occluded_run(rtmi_scene *s, int precision, int n_groups, int group, const double *d_rays, const double *d_range, double t_min, double t_max,
+                       const u64 *d_keys, unsigned ctr0, unsigned char *d_occ, int *d_count, u64 *d_cnt, hipStream_t st) {
+    return with_real(precision, [&](auto r) {
+        return query_impl<decltype(r), true>(s, n_groups * group, n_groups, group, d_rays, d_range, t_min, t_max, d_keys, ctr0, nullptr, d_occ, d_count, d_cnt, st);
+    });
+}
 } // namespace
 
 RTMI_EXPORT int rtmi_query_hits_device(rtmi_scene *s, int32_t precision, int32_t n, const void *d_rays, const void *d_t_range, double t_min, double t_max,
                                        const void *d_keys, uint32_t ctr0, void *d_out_hits, void *d_out_counters, void *stream) {
-    const int rc = check_query_args(s, precision, n, n >= 0, d_rays, d_out_hits != nullptr);
+    const int rc = query_begin(s, precision, n, n >= 0, d_rays, d_out_hits != nullptr);
     if (rc || n == 0) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream_of(c, stream);
-    return with_real(precision, [&](auto r) {
-        return query_impl<decltype(r), false>(s, n, 0, 1, reinterpret_cast<const double *>(d_rays), reinterpret_cast<const double *>(d_t_range), t_min, t_max,
-                                              reinterpret_cast<const u64 *>(d_keys), ctr0, reinterpret_cast<double *>(d_out_hits), nullptr, nullptr,
-                                              reinterpret_cast<u64 *>(d_out_counters), st);
-    });
+    return query_hits_run(s, precision, n, as<const double>(d_rays), as<const double>(d_t_range), t_min, t_max, as<const u64>(d_keys), ctr0,
+                          as<double>(d_out_hits), as<u64>(d_out_counters), stream_of(s->ctx, stream));
 }
 
 RTMI_EXPORT int rtmi_query_hits(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, const double *t_range, double t_min, double t_max,
                                 const uint64_t *keys, uint32_t ctr0, double *out_hits, uint64_t *out_counters) {
-    int rc = check_query_args(s, precision, n, n >= 0, rays, out_hits != nullptr);
+    const int rc = query_begin(s, precision, n, n >= 0, rays, out_hits != nullptr);
     if (rc || n == 0) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    HostIo io(c);
+    HostIo io(s->ctx);
     double *d_rays, *d_range, *d_hits;
     u64 *d_keys, *d_cnt;
     io.in(&d_rays, (size_t)n * 7, rays); io.in(&d_range, (size_t)n * 2, t_range); io.in(&d_keys, (size_t)n, keys);
     io.out(&d_hits, (size_t)n * RTMI_HIT_REC, out_hits); io.work(&d_cnt, 2, out_counters);
-    rc = io.stage();
-    if (rc) return rc;
-    rc = with_real(precision, [&](auto r) {
-        return query_impl<decltype(r), false>(s, n, 0, 1, d_rays, d_range, t_min, t_max, d_keys, ctr0, d_hits, nullptr, nullptr, d_cnt, c->stream);
-    });
-    return rc ? rc : io.finish();
+    return host_run(io, [&](hipStream_t st) { return query_hits_run(s, precision, n, d_rays, d_range, t_min, t_max, d_keys, ctr0, d_hits, d_cnt, st); });
 }
 
 RTMI_EXPORT int rtmi_query_occluded_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, const void *d_rays, const void *d_t_range,
                                            double t_min, double t_max, const void *d_keys, uint32_t ctr0, void *d_out_occluded, void *d_out_count,
                                            void *d_out_counters, void *stream) {
-    const long long n = (long long)n_groups * group;
-    const int rc = check_query_args(s, precision, n, n_groups >= 0 && group > 0, d_rays, true);
+    const int rc = query_begin(s, precision, (long long)n_groups * group, n_groups >= 0 && group > 0, d_rays, true);
     if (rc || n_groups == 0) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream_of(c, stream);
-    return with_real(precision, [&](auto r) {
-        return query_impl<decltype(r), true>(s, (int)n, n_groups, group, reinterpret_cast<const double *>(d_rays), reinterpret_cast<const double *>(d_t_range),
-                                             t_min, t_max, reinterpret_cast<const u64 *>(d_keys), ctr0, nullptr, reinterpret_cast<unsigned char *>(d_out_occluded),
-                                             reinterpret_cast<int *>(d_out_count), reinterpret_cast<u64 *>(d_out_counters), st);
-    });
+    return query_occluded_run(s, precision, n_groups, group, as<const double>(d_rays), as<const double>(d_t_range), t_min, t_max, as<const u64>(d_keys), ctr0,
+                              as<unsigned char>(d_out_occluded), as<int>(d_out_count), as<u64>(d_out_counters), stream_of(s->ctx, stream));
 }
 
 RTMI_EXPORT int rtmi_query_occluded(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, const double *rays, const double *t_range,
                                     double t_min, double t_max, const uint64_t *keys, uint32_t ctr0, uint8_t *out_occluded, int32_t *out_count,
                                     uint64_t *out_counters) {
-    const long long n = (long long)n_groups * group;
-    int rc = check_query_args(s, precision, n, n_groups >= 0 && group > 0, rays, true);
+    const int rc = query_begin(s, precision, (long long)n_groups * group, n_groups >= 0 && group > 0, rays, true);
     if (rc || n_groups == 0) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    HostIo io(c);
+    const size_t n = (size_t)n_groups * (size_t)group;
+    HostIo io(s->ctx);
     double *d_rays, *d_range;
     u64 *d_keys, *d_cnt;
     unsigned char *d_occ;
     int *d_count;
-    io.in(&d_rays, (size_t)n * 7, rays); io.in(&d_range, (size_t)n * 2, t_range); io.in(&d_keys, (size_t)n, keys);
-    io.out(&d_occ, (size_t)n, out_occluded); io.out(&d_count, (size_t)n_groups, out_count); io.work(&d_cnt, 2, out_counters);
-    rc = io.stage();
-    if (rc) return rc;
-    rc = with_real(precision, [&](auto r) {
-        return query_impl<decltype(r), true>(s, (int)n, n_groups, group, d_rays, d_range, t_min, t_max, d_keys, ctr0, nullptr, d_occ, d_count, d_cnt, c->stream);
+    io.in(&d_rays, n * 7, rays); io.in(&d_range, n * 2, t_range); io.in(&d_keys, n, keys);
+    io.out(&d_occ, n, out_occluded); io.out(&d_count, (size_t)n_groups, out_count); io.work(&d_cnt, 2, out_counters);
+    return host_run(io, [&](hipStream_t st) {
+        return query_occluded_run(s, precision, n_groups, group, d_rays, d_range, t_min, t_max, d_keys, ctr0, d_occ, d_count, d_cnt, st);
     });
-    return rc ? rc : io.finish();
 }
 
 // ---- occlusion rays generated on the device (rtmi_occlusion_hemisphere*, rtmi_occlusion_targets*, rtmi_ambient_occlusion*) -------------------------
@@ -5756,15 +5779,16 @@ __global__ void __launch_bounds__(kBlock) ao_resolve_kernel(const double *__rest
     vis[p] = hits[(size_t)p * RTMI_HIT_REC] != 0.0 ? 1.0 - (double)count[p] / (double)n_dirs : 1.0;
 }
 
-// the argument checks of the point entries, in the header's order; per_point = n_dirs / n_targets
-int check_occlusion_args(rtmi_scene *s, int precision, int n_points, int per_point, int first, const void *hits, bool targets_ok) {
+// what both forms of the point entries do first: the argument checks, in the header's order, then (with points) the scene's device is current;
+// per_point = n_dirs / n_targets
+int occlusion_begin(rtmi_scene *s, int precision, int n_points, int per_point, int first, const void *hits, bool targets_ok) {
     if (n_points < 0 || per_point <= 0 || first < 0)
         return fail(RTMI_E_ARG, "n_points, first must be >= 0 and n_dirs / n_targets > 0 (got %d %d %d)", n_points, first, per_point);
     const long long n = (long long)n_points * per_point;
     if (n > kRaysMax) return fail(RTMI_E_ARG, "%lld rays exceed 2^31 - 64", n);
     if (n > 0 && !hits) return fail(RTMI_E_ARG, "hits is NULL");
     if (n > 0 && !targets_ok) return fail(RTMI_E_ARG, "targets is NULL");
-    return check_query_args(s, precision, 0, true, nullptr, true); // the handle, the precision, RTMI_F32 on a mixed-kind scene
+    return query_begin(s, precision, n, true, hits, true); // the handle, the precision, RTMI_F32 on a mixed-kind scene
 }
 
 template <int SRC>
@@ -5783,13 +5807,13 @@ QueryParams point_source(const double *d_hits, const double *d_view, const doubl
     return g;
 }
 
-int check_ao_args(rtmi_scene *s, int precision, int nx, int ny, int n_dirs, int first, double radius, const void *vis) {
+int ao_begin(rtmi_scene *s, int precision, int nx, int ny, int n_dirs, int first, double radius, const void *vis) {
     if (nx < 0 || ny < 0 || n_dirs <= 0 || first < 0) return fail(RTMI_E_ARG, "nx, ny, first must be >= 0 and n_dirs > 0 (got %d %d %d %d)", nx, ny, first, n_dirs);
     if (!(radius > 0.0)) return fail(RTMI_E_ARG, "radius must be > 0 (got %g)", radius);
     const long long n = (long long)nx * ny;
     if (n > kRaysMax || n * n_dirs > kRaysMax) return fail(RTMI_E_ARG, "%lld pixels x %d rays exceed 2^31 - 64", n, n_dirs);
     if (n > 0 && !vis) return fail(RTMI_E_ARG, "out_visibility is NULL");
-    return check_query_args(s, precision, 0, true, nullptr, true); // the handle, the precision, RTMI_F32 on a mixed-kind scene
+    return query_begin(s, precision, n, true, vis, true); // the handle, the precision, RTMI_F32 on a mixed-kind scene
 }
 
 // The whole pass on `st`: the first hits of the pixel-centre rays, n_dirs hemisphere rays per hit on the viewer's side (the pixel-centre ray is built
@@ -5822,104 +5846,90 @@ int ao_impl(rtmi_scene *s, int nx, int ny, int n_dirs, int first, double radius,
 RTMI_EXPORT int rtmi_occlusion_hemisphere_device(rtmi_scene *s, int32_t precision, int32_t n_points, const void *d_hits, const void *d_view, int32_t n_dirs,
                                                  int32_t first, uint64_t seed, double time, double t_min, double t_max, void *d_out_occluded,
                                                  void *d_out_count, void *d_out_rays, void *d_out_counters, void *stream) {
-    const int rc = check_occlusion_args(s, precision, n_points, n_dirs, first, d_hits, true);
+    const int rc = occlusion_begin(s, precision, n_points, n_dirs, first, d_hits, true);
     if (rc || n_points == 0) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
     return occlusion_impl<SRC_HEMISPHERE>(s, precision, n_points, n_dirs,
-                                          point_source(reinterpret_cast<const double *>(d_hits), reinterpret_cast<const double *>(d_view), nullptr, first, seed, time,
-                                                       reinterpret_cast<double *>(d_out_rays)),
-                                          t_min, t_max, reinterpret_cast<unsigned char *>(d_out_occluded), reinterpret_cast<int *>(d_out_count),
-                                          reinterpret_cast<u64 *>(d_out_counters), stream_of(c, stream));
+                                          point_source(as<const double>(d_hits), as<const double>(d_view), nullptr, first, seed, time, as<double>(d_out_rays)),
+                                          t_min, t_max, as<unsigned char>(d_out_occluded), as<int>(d_out_count), as<u64>(d_out_counters),
+                                          stream_of(s->ctx, stream));
 }
 
 RTMI_EXPORT int rtmi_occlusion_hemisphere(rtmi_scene *s, int32_t precision, int32_t n_points, const double *hits, const double *view, int32_t n_dirs,
                                           int32_t first, uint64_t seed, double time, double t_min, double t_max, uint8_t *out_occluded, int32_t *out_count,
                                           double *out_rays, uint64_t *out_counters) {
-    int rc = check_occlusion_args(s, precision, n_points, n_dirs, first, hits, true);
+    const int rc = occlusion_begin(s, precision, n_points, n_dirs, first, hits, true);
     if (rc || n_points == 0) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
     const size_t np = (size_t)n_points, n = np * (size_t)n_dirs;
-    HostIo io(c);
+    HostIo io(s->ctx);
     double *d_hits, *d_view, *d_rays;
     u64 *d_cnt;
     unsigned char *d_occ;
     int *d_count;
     io.in(&d_hits, np * RTMI_HIT_REC, hits); io.in(&d_view, np * 7, view);
     io.out(&d_occ, n, out_occluded); io.out(&d_count, np, out_count); io.out(&d_rays, n * 7, out_rays); io.work(&d_cnt, 2, out_counters);
-    rc = io.stage();
-    if (rc) return rc;
-    rc = occlusion_impl<SRC_HEMISPHERE>(s, precision, n_points, n_dirs, point_source(d_hits, d_view, nullptr, first, seed, time, d_rays), t_min, t_max, d_occ,
-                                        d_count, d_cnt, c->stream);
-    return rc ? rc : io.finish();
+    return host_run(io, [&](hipStream_t st) {
+        return occlusion_impl<SRC_HEMISPHERE>(s, precision, n_points, n_dirs, point_source(d_hits, d_view, nullptr, first, seed, time, d_rays), t_min, t_max,
+                                              d_occ, d_count, d_cnt, st);
+    });
 }
 
 RTMI_EXPORT int rtmi_occlusion_targets_device(rtmi_scene *s, int32_t precision, int32_t n_points, const void *d_hits, const void *d_view, int32_t n_targets,
                                               const void *d_targets, double time, double t_min, double t_max, void *d_out_occluded, void *d_out_count,
                                               void *d_out_rays, void *d_out_counters, void *stream) {
-    const int rc = check_occlusion_args(s, precision, n_points, n_targets, 0, d_hits, d_targets != nullptr);
+    const int rc = occlusion_begin(s, precision, n_points, n_targets, 0, d_hits, d_targets != nullptr);
     if (rc || n_points == 0) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
     return occlusion_impl<SRC_TARGETS>(s, precision, n_points, n_targets,
-                                       point_source(reinterpret_cast<const double *>(d_hits), reinterpret_cast<const double *>(d_view),
-                                                    reinterpret_cast<const double *>(d_targets), 0, 0ull, time, reinterpret_cast<double *>(d_out_rays)),
-                                       t_min, t_max, reinterpret_cast<unsigned char *>(d_out_occluded), reinterpret_cast<int *>(d_out_count),
-                                       reinterpret_cast<u64 *>(d_out_counters), stream_of(c, stream));
+                                       point_source(as<const double>(d_hits), as<const double>(d_view), as<const double>(d_targets), 0, 0ull, time,
+                                                    as<double>(d_out_rays)),
+                                       t_min, t_max, as<unsigned char>(d_out_occluded), as<int>(d_out_count), as<u64>(d_out_counters),
+                                       stream_of(s->ctx, stream));
 }
 
 RTMI_EXPORT int rtmi_occlusion_targets(rtmi_scene *s, int32_t precision, int32_t n_points, const double *hits, const double *view, int32_t n_targets,
                                        const double *targets, double time, double t_min, double t_max, uint8_t *out_occluded, int32_t *out_count,
                                        double *out_rays, uint64_t *out_counters) {
-    int rc = check_occlusion_args(s, precision, n_points, n_targets, 0, hits, targets != nullptr);
+    const int rc = occlusion_begin(s, precision, n_points, n_targets, 0, hits, targets != nullptr);
     if (rc || n_points == 0) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
     const size_t np = (size_t)n_points, n = np * (size_t)n_targets;
-    HostIo io(c);
+    HostIo io(s->ctx);
     double *d_hits, *d_view, *d_targets, *d_rays;
     u64 *d_cnt;
     unsigned char *d_occ;
     int *d_count;
     io.in(&d_hits, np * RTMI_HIT_REC, hits); io.in(&d_view, np * 7, view); io.in(&d_targets, (size_t)n_targets * 3, targets);
     io.out(&d_occ, n, out_occluded); io.out(&d_count, np, out_count); io.out(&d_rays, n * 7, out_rays); io.work(&d_cnt, 2, out_counters);
-    rc = io.stage();
-    if (rc) return rc;
-    rc = occlusion_impl<SRC_TARGETS>(s, precision, n_points, n_targets, point_source(d_hits, d_view, d_targets, 0, 0ull, time, d_rays), t_min, t_max, d_occ,
-                                     d_count, d_cnt, c->stream);
-    return rc ? rc : io.finish();
+    return host_run(io, [&](hipStream_t st) {
+        return occlusion_impl<SRC_TARGETS>(s, precision, n_points, n_targets, point_source(d_hits, d_view, d_targets, 0, 0ull, time, d_rays), t_min, t_max,
+                                           d_occ, d_count, d_cnt, st);
+    });
 }
+
+namespace { // (behind the point entries: the kernels are instantiated in the order the calls were added in)
+int ao_run(rtmi_scene *s, int precision, int nx, int ny, int n_dirs, int first, double radius, u64 seed, double *d_vis, int *d_count, double *d_hits,
+           u64 *d_cnt, hipStream_t st) {
+    return with_real(precision, [&](auto r) { return ao_impl<decltype(r)>(s, nx, ny, n_dirs, first, radius, seed, d_vis, d_count, d_hits, d_cnt, st); });
+}
+} // namespace
 
 RTMI_EXPORT int rtmi_ambient_occlusion_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t n_dirs, int32_t first, double radius,
                                               uint64_t seed, void *d_out_visibility, void *d_out_count, void *d_out_hits, void *d_out_counters, void *stream) {
-    const int rc = check_ao_args(s, precision, nx, ny, n_dirs, first, radius, d_out_visibility);
+    const int rc = ao_begin(s, precision, nx, ny, n_dirs, first, radius, d_out_visibility);
     if (rc || nx == 0 || ny == 0) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream_of(c, stream);
-    return with_real(precision, [&](auto r) {
-        return ao_impl<decltype(r)>(s, nx, ny, n_dirs, first, radius, seed, reinterpret_cast<double *>(d_out_visibility), reinterpret_cast<int *>(d_out_count),
-                                    reinterpret_cast<double *>(d_out_hits), reinterpret_cast<u64 *>(d_out_counters), st);
-    });
+    return ao_run(s, precision, nx, ny, n_dirs, first, radius, seed, as<double>(d_out_visibility), as<int>(d_out_count), as<double>(d_out_hits),
+                  as<u64>(d_out_counters), stream_of(s->ctx, stream));
 }
 
 RTMI_EXPORT int rtmi_ambient_occlusion(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t n_dirs, int32_t first, double radius, uint64_t seed,
                                        double *out_visibility, int32_t *out_count, double *out_hits, uint64_t *out_counters) {
-    int rc = check_ao_args(s, precision, nx, ny, n_dirs, first, radius, out_visibility);
+    const int rc = ao_begin(s, precision, nx, ny, n_dirs, first, radius, out_visibility);
     if (rc || nx == 0 || ny == 0) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)nx * (size_t)ny;
-    HostIo io(c);
+    HostIo io(s->ctx);
     double *d_vis, *d_hits;
     u64 *d_cnt;
     int *d_count;
     io.out(&d_vis, n, out_visibility); io.out(&d_count, n, out_count); io.out(&d_hits, n * RTMI_HIT_REC, out_hits); io.work(&d_cnt, 2, out_counters);
-    rc = io.stage();
-    if (rc) return rc;
-    rc = with_real(precision, [&](auto r) { return ao_impl<decltype(r)>(s, nx, ny, n_dirs, first, radius, seed, d_vis, d_count, d_hits, d_cnt, c->stream); });
-    return rc ? rc : io.finish();
+    return host_run(io, [&](hipStream_t st) { return ao_run(s, precision, nx, ny, n_dirs, first, radius, seed, d_vis, d_count, d_hits, d_cnt, st); });
 }
 
 // ---- direct lighting from first hits (rtmi_scene_lights, rtmi_direct_irradiance*, rtmi_render_direct*) -------------------------------------------------
@@ -6033,28 +6043,6 @@ __global__ void __launch_bounds__(kBlock) direct_resolve_kernel(ScenePtr scp, co
     }
 }
 
-// what both entries check first, in the header's order; n_points = nx * ny for the whole pass
-int check_direct_args(rtmi_scene *s, int precision, long long n_points, bool dims_ok, int n_samples, int first, int n_lights, bool listed, const void *hits,
-                      const void *out) {
-    if (!dims_ok || n_samples <= 0 || first < 0) return fail(RTMI_E_ARG, "n_points (nx, ny), first must be >= 0 and n_samples > 0 (got %lld %d %d)", n_points, first, n_samples);
-    if (listed && (n_lights < 0 || n_lights > RTMI_DIRECT_MAX_LIGHTS)) return fail(RTMI_E_ARG, "n_lights must be in [0, %d] (got %d)", RTMI_DIRECT_MAX_LIGHTS, n_lights);
-    if (n_points > kRaysMax) return fail(RTMI_E_ARG, "%lld points exceed 2^31 - 64", n_points);
-    if (n_points > 0 && !hits) return fail(RTMI_E_ARG, "hits is NULL");
-    if (n_points > 0 && !out) return fail(RTMI_E_ARG, "out_irradiance / out_linear is NULL");
-    return check_query_args(s, precision, 0, true, nullptr, true); // the handle, the precision, RTMI_F32 on a mixed-kind scene
-}
-// rtmi_render_direct*'s resolve samples textures: what rtmi_render refuses for their tables, it refuses
-int check_direct_textures(const rtmi_scene *s) {
-    if (s->uses_perlin && !s->have_perlin) return fail(RTMI_E_STATE, "the scene holds a Perlin texture: call rtmi_scene_set_perlin first");
-    if (s->max_image >= s->dev.n_images) return fail(RTMI_E_STATE, "the scene holds an ImageMap with index %d: call rtmi_scene_set_images first", s->max_image);
-    return RTMI_OK;
-}
-int check_direct_items(long long n_points, int n_samples, int n_lights) {
-    if ((long long)n_samples * n_lights > kRaysMax || n_points * n_samples * n_lights > kRaysMax)
-        return fail(RTMI_E_ARG, "%lld points x %d samples x %d lights exceed 2^31 - 64 items", n_points, n_samples, n_lights);
-    return RTMI_OK;
-}
-
 struct DirectView { const double *d_view; bool camera; int nx, ny; }; // the rays that found the points: an array, the pixel-centre rays built again, or none
 
 // bytes of c->direct_ws: the light table, then whatever the caller lets the context hold, then one pass of contributions
@@ -6083,15 +6071,12 @@ int direct_impl(rtmi_scene *s, int n_points, const double *d_hits, const DirectV
         g.src_view = view.d_view ? view.d_view + (size_t)g0 * 7 : nullptr;
         g.out_rays = d_rays ? d_rays + row0 * 7 : nullptr;
         g.contrib = d_contrib ? d_contrib + row0 * 3 : ws_contrib;
-        const int pairs_before = c->events_used; // RTMI_FLAG_TIMING: did this launch open an interval of its own? (none past the 8192nd)
-        int rc = query_impl<R, true, SRC_LIGHT>(s, ng * group, ng, group, nullptr, nullptr, 0.001, 1.0 - 0.001, nullptr, 0u, nullptr, d_occ ? d_occ + row0 : nullptr,
-                                                nullptr, d_cnt, st, &g, g0 > 0);
+        const int rc = query_impl<R, true, SRC_LIGHT>(s, ng * group, ng, group, nullptr, nullptr, 0.001, 1.0 - 0.001, nullptr, 0u, nullptr,
+                                                      d_occ ? d_occ + row0 : nullptr, nullptr, d_cnt, st, &g, g0 > 0, [&] {
+            hipLaunchKernelGGL(direct_fold_kernel, dim3((unsigned)((ng + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g.contrib, g0, ng, group,
+                               d_state ? first : 0, n_samples, d_state, d_E);
+        });
         if (rc) return rc;
-        const bool timed = c->events_used > pairs_before;
-        hipLaunchKernelGGL(direct_fold_kernel, dim3((unsigned)((ng + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g.contrib, g0, ng, group, d_state ? first : 0,
-                           n_samples, d_state, d_E);
-        HIP_TRY(hipGetLastError());
-        if (timed) { rc = close_timed_fold(c, st); if (rc) return rc; } // its fold interval ends behind the fold (query_impl closed an empty one)
     }
     return RTMI_OK;
 }
@@ -6163,6 +6148,34 @@ int render_direct_impl(rtmi_scene *s, int nx, int ny, const LightTable &T, int n
     HIP_TRY(hipGetLastError());
     return RTMI_OK;
 }
+int render_direct_run(rtmi_scene *s, int precision, int nx, int ny, const LightTable &T, int n_samples, int first, u64 seed, double *d_state, double *d_lin,
+                      unsigned char *d_q, double *d_hits, u64 *d_cnt, hipStream_t st) {
+    return with_real(precision, [&](auto r) { return render_direct_impl<decltype(r)>(s, nx, ny, T, n_samples, first, seed, d_state, d_lin, d_q, d_hits, d_cnt, st); });
+}
+
+// What both forms of the two calls do first, in the header's order: the argument checks, the lights of the call in T, a host form's state, then the
+// scene's device is current.  n_points = nx * ny for the whole pass (rtmi_render_direct*), whose resolve samples textures: what rtmi_render refuses
+// for their tables, it refuses.  n_points = 0 passes: the entry returns RTMI_OK at once.
+int direct_begin(rtmi_scene *s, int precision, long long n_points, bool dims_ok, int n_samples, int first, int n_lights, const int32_t *light_prims,
+                 bool whole_pass, const void *hits, const void *out, const double *host_state, LightTable &T) {
+    if (!dims_ok || n_samples <= 0 || first < 0) return fail(RTMI_E_ARG, "n_points (nx, ny), first must be >= 0 and n_samples > 0 (got %lld %d %d)", n_points, first, n_samples);
+    if (light_prims && (n_lights < 0 || n_lights > RTMI_DIRECT_MAX_LIGHTS)) return fail(RTMI_E_ARG, "n_lights must be in [0, %d] (got %d)", RTMI_DIRECT_MAX_LIGHTS, n_lights);
+    if (n_points > kRaysMax) return fail(RTMI_E_ARG, "%lld points exceed 2^31 - 64", n_points);
+    if (n_points > 0 && !hits) return fail(RTMI_E_ARG, "hits is NULL");
+    if (n_points > 0 && !out) return fail(RTMI_E_ARG, "out_irradiance / out_linear is NULL");
+    int rc = check_query_args(s, precision, 0, true, nullptr, true); // the handle, the precision, RTMI_F32 on a mixed-kind scene
+    if (rc || n_points == 0) return rc;
+    if (whole_pass && s->uses_perlin && !s->have_perlin) return fail(RTMI_E_STATE, "the scene holds a Perlin texture: call rtmi_scene_set_perlin first");
+    if (whole_pass && s->max_image >= s->dev.n_images) return fail(RTMI_E_STATE, "the scene holds an ImageMap with index %d: call rtmi_scene_set_images first", s->max_image);
+    rc = make_light_table(s, n_lights, light_prims, T);
+    if (rc) return rc;
+    if ((long long)n_samples * T.n > kRaysMax || n_points * n_samples * T.n > kRaysMax)
+        return fail(RTMI_E_ARG, "%lld points x %d samples x %d lights exceed 2^31 - 64 items", n_points, n_samples, T.n);
+    rc = check_state_counts(host_state, (size_t)n_points, RTMI_DIRECT_REC, 3, first, whole_pass ? "pixel" : "point", "samples, first");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    return RTMI_OK;
+}
 } // namespace
 
 RTMI_EXPORT int rtmi_scene_lights(rtmi_scene *s, int32_t capacity, int32_t *out_prims, int32_t *out_count) {
@@ -6186,38 +6199,23 @@ RTMI_EXPORT int rtmi_direct_irradiance_device(rtmi_scene *s, int32_t precision, 
                                               const int32_t *light_prims, int32_t n_samples, int32_t first, uint64_t seed, double time, int32_t lambert_only,
                                               void *d_state, void *d_out_irradiance, void *d_out_contrib, void *d_out_occluded, void *d_out_rays,
                                               void *d_out_counters, void *stream) {
-    int rc = check_direct_args(s, precision, n_points, n_points >= 0, n_samples, first, n_lights, light_prims != nullptr, d_hits, d_out_irradiance);
-    if (rc || n_points == 0) return rc;
     LightTable T;
-    rc = make_light_table(s, n_lights, light_prims, T);
-    if (!rc) rc = check_direct_items(n_points, n_samples, T.n);
-    if (rc) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    return direct_irradiance_impl(s, precision, n_points, reinterpret_cast<const double *>(d_hits), reinterpret_cast<const double *>(d_view), T, n_samples, first,
-                                  seed, time, lambert_only, reinterpret_cast<double *>(d_state), reinterpret_cast<double *>(d_out_irradiance),
-                                  reinterpret_cast<double *>(d_out_contrib), reinterpret_cast<unsigned char *>(d_out_occluded),
-                                  reinterpret_cast<double *>(d_out_rays), reinterpret_cast<u64 *>(d_out_counters), stream_of(c, stream));
+    const int rc = direct_begin(s, precision, n_points, n_points >= 0, n_samples, first, n_lights, light_prims, false, d_hits, d_out_irradiance, nullptr, T);
+    if (rc || n_points == 0) return rc;
+    return direct_irradiance_impl(s, precision, n_points, as<const double>(d_hits), as<const double>(d_view), T, n_samples, first, seed, time, lambert_only,
+                                  as<double>(d_state), as<double>(d_out_irradiance), as<double>(d_out_contrib), as<unsigned char>(d_out_occluded),
+                                  as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream));
 }
 
 RTMI_EXPORT int rtmi_direct_irradiance(rtmi_scene *s, int32_t precision, int32_t n_points, const double *hits, const double *view, int32_t n_lights,
                                        const int32_t *light_prims, int32_t n_samples, int32_t first, uint64_t seed, double time, int32_t lambert_only,
                                        double *state, double *out_irradiance, double *out_contrib, uint8_t *out_occluded, double *out_rays,
                                        uint64_t *out_counters) {
-    int rc = check_direct_args(s, precision, n_points, n_points >= 0, n_samples, first, n_lights, light_prims != nullptr, hits, out_irradiance);
-    if (rc || n_points == 0) return rc;
     LightTable T;
-    rc = make_light_table(s, n_lights, light_prims, T);
-    if (!rc) rc = check_direct_items(n_points, n_samples, T.n);
-    if (rc) return rc;
-    if (state && first > 0)
-        for (int g = 0; g < n_points; ++g)
-            if (state[(size_t)g * RTMI_DIRECT_REC + 3] != (double)first)
-                return fail(RTMI_E_STATE, "point %d's record holds %g samples, first is %d", g, state[(size_t)g * RTMI_DIRECT_REC + 3], first);
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
+    const int rc = direct_begin(s, precision, n_points, n_points >= 0, n_samples, first, n_lights, light_prims, false, hits, out_irradiance, state, T);
+    if (rc || n_points == 0) return rc;
     const size_t np = (size_t)n_points, n = np * (size_t)n_samples * (size_t)T.n;
-    HostIo io(c);
+    HostIo io(s->ctx);
     double *d_hits, *d_view, *d_state, *d_E, *d_contrib, *d_rays;
     unsigned char *d_occ;
     u64 *d_cnt;
@@ -6225,60 +6223,34 @@ RTMI_EXPORT int rtmi_direct_irradiance(rtmi_scene *s, int32_t precision, int32_t
     io.plane(&d_state, np * RTMI_DIRECT_REC, state != nullptr, first > 0 ? state : nullptr, state); // a first chunk (first = 0) reads no records
     io.work(&d_E, np * 3, out_irradiance); io.out(&d_contrib, n * 3, n ? out_contrib : nullptr); io.out(&d_occ, n, n ? out_occluded : nullptr);
     io.out(&d_rays, n * 7, n ? out_rays : nullptr); io.work(&d_cnt, 2, out_counters);
-    rc = io.stage();
-    if (rc) return rc;
-    rc = direct_irradiance_impl(s, precision, n_points, d_hits, d_view, T, n_samples, first, seed, time, lambert_only, d_state, d_E, d_contrib, d_occ, d_rays, d_cnt,
-                                c->stream);
-    return rc ? rc : io.finish();
+    return host_run(io, [&](hipStream_t st) {
+        return direct_irradiance_impl(s, precision, n_points, d_hits, d_view, T, n_samples, first, seed, time, lambert_only, d_state, d_E, d_contrib, d_occ, d_rays,
+                                      d_cnt, st);
+    });
 }
 
 RTMI_EXPORT int rtmi_render_direct_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t n_samples, int32_t first, uint64_t seed, void *d_state,
                                           void *d_out_linear, void *d_out_rgb8, void *d_out_hits, void *d_out_counters, void *stream) {
-    int rc = check_direct_args(s, precision, (long long)nx * ny, nx >= 0 && ny >= 0, n_samples, first, 0, false, d_out_linear, d_out_linear);
-    if (rc || nx == 0 || ny == 0) return rc;
-    rc = check_direct_textures(s);
-    if (rc) return rc;
     LightTable T;
-    rc = make_light_table(s, 0, nullptr, T);
-    if (!rc) rc = check_direct_items((long long)nx * ny, n_samples, T.n);
-    if (rc) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream_of(c, stream);
-    return with_real(precision, [&](auto r) {
-        return render_direct_impl<decltype(r)>(s, nx, ny, T, n_samples, first, seed, reinterpret_cast<double *>(d_state), reinterpret_cast<double *>(d_out_linear),
-                                               reinterpret_cast<unsigned char *>(d_out_rgb8), reinterpret_cast<double *>(d_out_hits),
-                                               reinterpret_cast<u64 *>(d_out_counters), st);
-    });
+    const int rc = direct_begin(s, precision, (long long)nx * ny, nx >= 0 && ny >= 0, n_samples, first, 0, nullptr, true, d_out_linear, d_out_linear, nullptr, T);
+    if (rc || nx == 0 || ny == 0) return rc;
+    return render_direct_run(s, precision, nx, ny, T, n_samples, first, seed, as<double>(d_state), as<double>(d_out_linear), as<unsigned char>(d_out_rgb8),
+                             as<double>(d_out_hits), as<u64>(d_out_counters), stream_of(s->ctx, stream));
 }
 
 RTMI_EXPORT int rtmi_render_direct(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t n_samples, int32_t first, uint64_t seed, double *state,
                                    double *out_linear, uint8_t *out_rgb8, double *out_hits, uint64_t *out_counters) {
-    int rc = check_direct_args(s, precision, (long long)nx * ny, nx >= 0 && ny >= 0, n_samples, first, 0, false, out_linear, out_linear);
-    if (rc || nx == 0 || ny == 0) return rc;
-    rc = check_direct_textures(s);
-    if (rc) return rc;
     LightTable T;
-    rc = make_light_table(s, 0, nullptr, T);
-    if (!rc) rc = check_direct_items((long long)nx * ny, n_samples, T.n);
-    if (rc) return rc;
+    const int rc = direct_begin(s, precision, (long long)nx * ny, nx >= 0 && ny >= 0, n_samples, first, 0, nullptr, true, out_linear, out_linear, state, T);
+    if (rc || nx == 0 || ny == 0) return rc;
     const size_t n = (size_t)nx * (size_t)ny;
-    if (state && first > 0)
-        for (size_t g = 0; g < n; ++g)
-            if (state[g * RTMI_DIRECT_REC + 3] != (double)first)
-                return fail(RTMI_E_STATE, "pixel %zu's record holds %g samples, first is %d", g, state[g * RTMI_DIRECT_REC + 3], first);
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    HostIo io(c);
+    HostIo io(s->ctx);
     double *d_state, *d_lin, *d_hits;
     unsigned char *d_q;
     u64 *d_cnt;
     io.plane(&d_state, n * RTMI_DIRECT_REC, state != nullptr, first > 0 ? state : nullptr, state);
     io.work(&d_lin, n * 3, out_linear); io.out(&d_q, n * 3, out_rgb8); io.out(&d_hits, n * RTMI_HIT_REC, out_hits); io.work(&d_cnt, 2, out_counters);
-    rc = io.stage();
-    if (rc) return rc;
-    rc = with_real(precision, [&](auto r) { return render_direct_impl<decltype(r)>(s, nx, ny, T, n_samples, first, seed, d_state, d_lin, d_q, d_hits, d_cnt, c->stream); });
-    return rc ? rc : io.finish();
+    return host_run(io, [&](hipStream_t st) { return render_direct_run(s, precision, nx, ny, T, n_samples, first, seed, d_state, d_lin, d_q, d_hits, d_cnt, st); });
 }
 
 // ---- path tracing with next-event estimation (rtmi_render_rays_nee*, rtmi_probe_paths_nee) ---------------------------------------------------------
@@ -6287,6 +6259,9 @@ RTMI_EXPORT int rtmi_render_direct(rtmi_scene *s, int32_t precision, int32_t nx,
 namespace {
 struct NeePass {
     static constexpr bool wave_level = true;
+    using Args = NeeParams;
+    static RaysParams &rays(Args &a) { return a.rp; }
+    static constexpr int n_counters = 4;
     // a media scene is refused before any launch, so the media-sequence operands of the chooser all name the one kernel
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT>; }
 };
@@ -6339,128 +6314,48 @@ int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *lig
     return make_nee_lights(s, n_lights, light_prims, T);
 }
 
-// render_rays_impl with the light-sampling kernel (T.t.n >= 1); counters: four values
-template <typename R>
-int render_rays_nee_impl(rtmi_scene *s, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
-                         const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
-    rtmi_ctx *c = s->ctx;
-    int rc = c->counters.ensure(8 * sizeof(u64)); // [0..3] the counters when the caller passes no buffer, [4] the work-queue head
-    if (rc) return rc;
-    if (!d_cnt) d_cnt = reinterpret_cast<u64 *>(c->counters.p);
-    int per_pass = n_groups;
-    if (!d_out_rays) {
-        const int64_t group_bytes = (int64_t)group * 3 * (int64_t)sizeof(double);
-        per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(n_groups, c->workspace_bytes / group_bytes));
-        rc = c->rays_ws.ensure((size_t)per_pass * (size_t)group_bytes);
-        if (rc) return rc;
-    }
-    NeeParams np;
-    rc = upload_nee_lights(c, T, np.lights, st);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, 4 * sizeof(u64), st));
-    RaysParams &rp = np.rp;
-    rp.seed = seed; rp.ctr0 = ctr0; rp.depth = depth;
-    rp.group = (unsigned)group; rp.g_first = (unsigned)g_first;
-    rp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + 4);
-    rp.counters = d_cnt;
-    const u64 n_rays = (u64)n_groups * (u64)group;
-    with_probe_kernel<NeePass, R>(s, [&](auto kern, size_t lds, int, int) {
-        rc = [&]() -> int {
-            int resident = 0;
-            const int rco = resident_blocks(c, reinterpret_cast<const void *>(kern), kBlock, lds, &resident);
-            if (rco) return rco;
-            const long long persistent = (long long)c->cus * std::max(1, std::min(c->blocks_per_cu, resident));
-            for (int g0 = 0; g0 < n_groups; g0 += per_pass) {
-                const int ng = std::min(per_pass, n_groups - g0);
-                const size_t row0 = (size_t)g0 * (size_t)group;
-                const long long items = (long long)ng * group;
-                rp.rays = d_rays + row0 * 7;
-                rp.keys = d_keys ? d_keys + row0 : nullptr;
-                rp.samples = d_out_rays ? d_out_rays + row0 * 3 : reinterpret_cast<double *>(c->rays_ws.p);
-                rp.row0 = (unsigned)row0; rp.total_items = (unsigned)items;
-                { // claim size: as rays_kernel's
-                    const long long per_wave = items / std::max(1, c->cus * 16);
-                    unsigned qb = 64u;
-                    while (qb < 1024u && per_wave >= (long long)qb * 16) qb *= 2;
-                    rp.qblock = qb;
-                }
-                hipEvent_t e1 = nullptr;
-                const int rce = open_timed(c, st, &e1);
-                if (rce) return rce;
-                HIP_TRY(hipMemsetAsync(rp.queue, 0, sizeof(unsigned), st));
-                const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(persistent, (items + kBlock - 1) / kBlock));
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(kBlock), lds, st, s->d_dev, np);
-                HIP_TRY(hipGetLastError());
-                if (e1) HIP_TRY(hipEventRecord(e1, st));
-                hipLaunchKernelGGL((rays_fold_kernel<R>), dim3((unsigned)((ng + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rp.samples, g0, ng, group,
-                                   d_state ? g_first : 0, d_state, d_mean, d_se, d_cnt, n_rays);
-                HIP_TRY(hipGetLastError());
-                if (e1) { const int rcf = close_timed_fold(c, st); if (rcf) return rcf; }
-            }
-            return RTMI_OK;
-        }();
+// the passes with the light-sampling kernel; no light to sample: the call is rtmi_render_rays and its two shadow-ray counters are zeros
+int nee_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
+            const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
+    return with_real(precision, [&](auto r) {
+        using R = decltype(r);
+        if (T.t.n > 0)
+            return render_rays_impl<R, NeePass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
+                                                [&](NeeParams &np, hipStream_t q) { return upload_nee_lights(s->ctx, T, np.lights, q); });
+        if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt + 2, 0, 2 * sizeof(u64), st));
+        return render_rays_impl<R, RaysPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st, NoLights{});
     });
-    return rc;
-}
-
-// no light to sample: the call is rtmi_render_rays; its two shadow-ray counters are zeros
-template <typename R>
-int render_rays_nee_any(rtmi_scene *s, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
-                        const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
-    if (T.t.n > 0) return render_rays_nee_impl<R>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, T, d_state, d_mean, d_se, d_out_rays, d_cnt, st);
-    if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt + 2, 0, 2 * sizeof(u64), st));
-    return render_rays_impl<R>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st);
 }
 } // namespace
 
 RTMI_EXPORT int rtmi_render_rays_nee_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const void *d_rays,
                                             const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
                                             void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream) {
-    int rc = check_rays_args(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr);
-    if (rc) return rc;
     NeeLightTable T;
     bool work = false;
-    rc = check_nee_args(s, n_groups, n_lights, light_prims, T, &work);
+    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr, nullptr, &work, &T, n_lights, light_prims);
     if (rc || !work) return rc;
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = stream_of(c, stream);
-    return with_real(precision, [&](auto r) {
-        return render_rays_nee_any<decltype(r)>(s, n_groups, group, g_first, reinterpret_cast<const double *>(d_rays), reinterpret_cast<const u64 *>(d_keys), seed,
-                                                ctr0, depth, T, reinterpret_cast<double *>(d_state), reinterpret_cast<double *>(d_out_mean),
-                                                reinterpret_cast<double *>(d_out_stderr), reinterpret_cast<double *>(d_out_rays),
-                                                reinterpret_cast<u64 *>(d_out_counters), st);
-    });
+    return nee_run(s, precision, n_groups, group, g_first, as<const double>(d_rays), as<const u64>(d_keys), seed, ctr0, depth, T, as<double>(d_state),
+                   as<double>(d_out_mean), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream));
 }
 
 RTMI_EXPORT int rtmi_render_rays_nee(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const double *rays,
                                      const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
                                      double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters) {
-    int rc = check_rays_args(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr);
-    if (rc) return rc;
     NeeLightTable T;
     bool work = false;
-    rc = check_nee_args(s, n_groups, n_lights, light_prims, T, &work);
+    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr, state, &work, &T, n_lights, light_prims);
     if (rc || !work) return rc;
-    if (state && g_first > 0)
-        for (int g = 0; g < n_groups; ++g)
-            if (state[(size_t)g * RTMI_RAYS_REC + 9] != (double)g_first)
-                return fail(RTMI_E_STATE, "group %d's record holds %g rays, g_first is %d", g, state[(size_t)g * RTMI_RAYS_REC + 9], g_first);
-    rtmi_ctx *c = s->ctx;
-    HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)n_groups * (size_t)group, ng = (size_t)n_groups;
-    HostIo io(c);
+    HostIo io(s->ctx);
     double *d_rays, *d_state, *d_mean, *d_se, *d_out;
     u64 *d_keys, *d_cnt;
     io.in(&d_rays, 7 * n, rays); io.in(&d_keys, n, keys);
     io.plane(&d_state, ng * RTMI_RAYS_REC, state != nullptr, g_first > 0 ? state : nullptr, state); // a first chunk (g_first = 0) reads no records
     io.out(&d_mean, 3 * ng, out_mean); io.out(&d_se, ng, out_stderr); io.work(&d_cnt, 4, out_counters); io.out(&d_out, 3 * n, out_rays);
-    rc = io.stage();
-    if (rc) return rc;
-    rc = with_real(precision, [&](auto r) {
-        return render_rays_nee_any<decltype(r)>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, T, d_state, d_mean, d_se, d_out, d_cnt, c->stream);
+    return host_run(io, [&](hipStream_t st) {
+        return nee_run(s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, T, d_state, d_mean, d_se, d_out, d_cnt, st);
     });
-    return rc ? rc : io.finish();
 }
 
 RTMI_EXPORT int rtmi_probe_paths_nee(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
