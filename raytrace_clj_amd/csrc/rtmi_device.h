@@ -428,11 +428,33 @@ template <typename R> __device__ inline void rand_in_unit_sphere(Path<R> &P, R &
 // i.e. by exactly the draws the sequential loop would have consumed; with no accepted candidate it advances by 3K and goes on.
 // kStrideMask[n] = sum over q < 64/n of 2^(q n)  (n = 1..64; scalar load, n is wave-uniform)
 __device__ __constant__ const unsigned long long kStrideMask[65] = {0ull, 0xffffffffffffffffull, 0x5555555555555555ull, 0x1249249249249249ull, 0x1111111111111111ull, 0x84210842108421ull, 0x41041041041041ull, 0x102040810204081ull, 0x101010101010101ull, 0x40201008040201ull, 0x4010040100401ull, 0x100200400801ull, 0x1001001001001ull, 0x8004002001ull, 0x40010004001ull, 0x200040008001ull, 0x1000100010001ull, 0x400020001ull, 0x1000040001ull, 0x4000080001ull, 0x10000100001ull, 0x40000200001ull, 0x400001ull, 0x800001ull, 0x1000001ull, 0x2000001ull, 0x4000001ull, 0x8000001ull, 0x10000001ull, 0x20000001ull, 0x40000001ull, 0x80000001ull, 0x100000001ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull, 0x1ull};
+// kCoopSplit[n] = M | K << 20 with K = 64 / n and M = 65536 / n + 1, so that (L M) >> 16 = L / n for L < 64: how 64 lanes split into K candidates for each of n
+// victims (n is wave-uniform: one scalar load where the compiler's own uniform divisions are ~20 vector instructions).  Both cooperative samplers split by it.
+struct CoopSplit { unsigned v[65]; };
+constexpr CoopSplit make_coop_split() {
+    CoopSplit t{};
+    for (unsigned n = 1; n <= 64; ++n) t.v[n] = (65536u / n + 1u) | ((64u / n) << 20);
+    return t;
+}
+constexpr bool coop_split_divides(const CoopSplit &t) {
+    for (unsigned n = 1; n <= 64; ++n)
+        for (unsigned L = 0; L < 64; ++L) if (((L * (t.v[n] & 0xfffffu)) >> 16) != L / n) return false;
+    return true;
+}
+static_assert(coop_split_divides(make_coop_split()), "(L M) >> 16 = L / n");
+__device__ __constant__ const CoopSplit kCoopSplit = make_coop_split();
+// ds_bpermute of a 32- or 64-bit value: lane L reads `v` of the lane whose number times 4 is `addr` (addr / 4 in 0..63)
+__device__ inline u64 bperm_lane(int addr, u64 v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(addr, (int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_ds_bpermute(addr, (int)(unsigned)(v >> 32));
+    return (u64)lo | ((u64)hi << 32);
+}
+__device__ inline double bperm_lane(int addr, double v) { return __longlong_as_double((long long)bperm_lane(addr, (u64)__double_as_longlong(v))); }
+__device__ inline float bperm_lane(int addr, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(v))); }
 #ifndef RTMI_COOP_SAMPLER
 #define RTMI_COOP_SAMPLER 1
 #endif
 #ifndef RTMI_SAMPLER_PLAIN
-#define RTMI_SAMPLER_PLAIN 2
+#define RTMI_SAMPLER_PLAIN 1 // swept 1 / 2 / 3 with the round at its present cost: 1 is best at C3 and level elsewhere
 #endif
 template <typename R> __device__ inline void rand_in_unit_sphere_wave(Path<R> &P, bool need, R &x, R &y, R &z) {
 #if RTMI_COOP_SAMPLER
@@ -450,33 +472,42 @@ template <typename R> __device__ inline void rand_in_unit_sphere_wave(Path<R> &P
             RTMI_PH(PH_SAMPLER)
         }
     }
-    u64 rem = __ballot(pending);
+    u64 rem = __builtin_amdgcn_ballot_w64(pending);
     while (rem) { // wave-uniform
-        const int n = __popcll(rem), K = 64 / n;
-        const int vrank = __popcll(rem & ((1ull << lane) - 1ull));
+        const int n = __popcll(rem);
+        const unsigned split = kCoopSplit.v[n], M = split & 0xfffffu; // scalar: n is wave-uniform
+        const int K = (int)(split >> 20);
+        const int vrank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(rem >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)rem, 0u)); // victims below this lane
         // victims to the front (by rank), everyone else behind them: a permutation of the 64 lanes; lane i < n then knows victim i
         const int dest = pending ? vrank : n + (lane - vrank);
         const int tbl = __builtin_amdgcn_ds_permute(dest << 2, lane);
-        const unsigned M = (unsigned)(65536.0f / (float)n) + 1u;          // (L * M) >> 16 = floor(L / n) for L < 64, n <= 64
-        const int c = (int)(((unsigned)lane * M) >> 16), j = lane - c * n; // this lane: candidate c of victim j
+        const int c = (int)(((unsigned)lane * M) >> 16), j = lane - c * n; // this lane: candidate c = lane / n of victim j = lane % n
         const int vic = __builtin_amdgcn_ds_bpermute(j << 2, tbl);
-        const u64 rs_c = __shfl(P.rs, vic) + RTMI_GOLD * (u64)(3 * c);
+        const u64 rs_c = bperm_lane(vic << 2, P.rs) + RTMI_GOLD * (u64)(3 * c);
         const R cx = Real<R>::symmetric(mix64(rs_c + RTMI_GOLD)), cy = Real<R>::symmetric(mix64(rs_c + 2ull * RTMI_GOLD)),
                 cz = Real<R>::symmetric(mix64(rs_c + 3ull * RTMI_GOLD));
-        const u64 acc = __ballot(c < K && !(dot3(cx, cy, cz, cx, cy, cz) >= R(1.0)));
+        // the lanes with c < K are the first K n (33..64) of the wave: a scalar mask, and the ballot is the comparison's own (the whole wave is here)
+        const u64 acc = __builtin_amdgcn_ballot_w64(!(dot3(cx, cy, cz, cx, cy, cz) >= R(1.0))) & (~0ull >> (64 - K * n));
         const u64 sm = kStrideMask[n]; // the lanes that hold one victim's candidates, relative to its rank: bits 0, n, 2n, ..., (K-1) n
-        const u64 mine = pending ? ((acc >> vrank) & sm) : 0ull;
-        const int first = mine ? __ffsll((long long)mine) - 1 : 0;
-        const int src = mine ? vrank + first : lane;
-        const R fx = __shfl(cx, src), fy = __shfl(cy, src), fz = __shfl(cz, src);
+        const u64 mine = (acc >> vrank) & sm; // means something in a victim only
+        const u64 tm = __builtin_amdgcn_ballot_w64(mine != 0ull) & rem; // the victims that take one this round: `pending` and `took` stay masks
+        const bool took = __builtin_amdgcn_inverse_ballot_w64(tm);
+        const int first = __builtin_ctzll(mine | (1ull << 63)); // its first accepted candidate sits `first` lanes above its rank (read only where took)
+        const int src = took ? vrank + first : lane;
+        const R fx = bperm_lane(src << 2, cx), fy = bperm_lane(src << 2, cy), fz = bperm_lane(src << 2, cz);
+        // one victim's candidates sit n lanes apart, so the accepted one is candidate first / n (first < 64: the table's M divides), and the
+        // sequential loop would have consumed 3 (first / n + 1) draws to reach it; without one, all 3 K.  (Written as selects over all 64
+        // lanes the round is 5 vector instructions longer -- x, y, z become six v_cndmask where the masked arm has three 64-bit moves -- and
+        // the FP32 trace kernels need 2 more VGPRs: the tail keeps its masked arms.)
         if (pending) {
-            const unsigned used = mine ? 3u * (unsigned)(__popcll(sm & ((1ull << first) - 1ull)) + 1) : 3u * (unsigned)K;
+            const unsigned used = took ? 3u * ((((unsigned)first * M) >> 16) + 1u) : 3u * (unsigned)K;
             P.rs += RTMI_GOLD * (u64)used;
             P.ctr += used;
-            if (mine) { x = fx; y = fy; z = fz; pending = false; }
+            if (took) { x = fx; y = fy; z = fz; }
         }
+        rem &= ~tm;
+        pending = __builtin_amdgcn_inverse_ballot_w64(rem);
         RTMI_PH(PH_SAMPLER) // a cooperative round: every lane evaluates a candidate
-        rem = __ballot(pending);
     }
 #else
     if (need) rand_in_unit_sphere(P, x, y, z);
@@ -497,24 +528,8 @@ template <typename R> __device__ inline void rand_in_unit_disk(Path<R> &P, R &x,
 // Here ONE ordinary round, then the n lanes still pending (~14) get K = 64/n candidates each at once: candidate c of a victim is draws
 // 2c+1, 2c+2 after its position; it takes its first accepted one and advances by exactly the draws the sequential loop would have consumed.
 // counts_only (wave-uniform): the caller needs the stream position alone (the lens radius is zero: get_ray_wave), so no value travels back.
-// The two samplers derive the lane split differently: rand_in_unit_sphere_wave keeps its arithmetic form (its schedule is not this change's to touch).
-// (The sphere sampler's (unsigned)(65536.0f / n) and 64 / n are an IEEE float division and a reciprocal sequence on the vector unit, 21 of this round's
-// 110 instructions: here both come from a table.)
-// kCoopSplit[n] = M | K << 20 with K = 64 / n and M = 65536 / n + 1, so that (L M) >> 16 = L / n for L < 64: how 64 lanes split into K candidates for each of n
-// victims (n is wave-uniform: one scalar load where the compiler's own uniform divisions are ~20 vector instructions)
-struct CoopSplit { unsigned v[65]; };
-constexpr CoopSplit make_coop_split() {
-    CoopSplit t{};
-    for (unsigned n = 1; n <= 64; ++n) t.v[n] = (65536u / n + 1u) | ((64u / n) << 20);
-    return t;
-}
-constexpr bool coop_split_divides(const CoopSplit &t) {
-    for (unsigned n = 1; n <= 64; ++n)
-        for (unsigned L = 0; L < 64; ++L) if (((L * (t.v[n] & 0xfffffu)) >> 16) != L / n) return false;
-    return true;
-}
-static_assert(coop_split_divides(make_coop_split()), "(L M) >> 16 = L / n");
-__device__ __constant__ const CoopSplit kCoopSplit = make_coop_split();
+// The lane split is the sphere sampler's: K and M from kCoopSplit[n] (written as (unsigned)(65536.0f / n) and 64 / n they are an IEEE float division and a
+// reciprocal sequence on the vector unit, 21 of this round's 110 instructions).
 #ifndef RTMI_COOP_DISK
 #define RTMI_COOP_DISK 1
 #endif
