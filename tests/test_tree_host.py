@@ -74,7 +74,7 @@ def test_chooser_thresholds_sit_where_the_recipes_straddle_them():
     # without the cap's four the tree over the 300 small spheres has 299 inner nodes: the other four shells are in it
     assert ts.HOST_TABLE["many_big(20, 300)"][0] == 299 + 4
     # twenty spheres of one size, each as large as the scene: sixteen stay out, four build a tree
-    geom = np.array([[0.1 * k, 0.0, 0.0, 50.0] for k in range(20)])
+    geom = ts.scene_sized(20)
     assert _build(geom, 1)[1][3] == 16 and _build(geom, 1)[1][0] == 3
 
 
@@ -88,8 +88,7 @@ def test_unboundable_spheres_are_kept_out_of_the_tree_and_the_build_returns():
     """non-finite coordinates and coordinates beyond 1e15 cannot be bounded: such spheres join the big primitives (exact test for every ray) while
     there is room, and the build still returns a tree over the rest"""
     base = ts.sphere_geom(ts.cloud(40, dome=False))
-    odd = np.array([[np.inf, 0, 0, 1.0], [0, -np.inf, 0, 1.0], [np.nan, 0, 0, 1.0], [0, 0, 0, np.inf], [0, 0, 0, np.nan], [1e16, 0, 0, 1.0],
-                    [0, 0, -3e15, 1.0], [0, 0, 0, 2e15], [0, 0, 0, -np.inf]])
+    odd = ts.UNBOUNDABLE
     for k in range(len(odd)):
         (_, one), (_, team) = _build(np.concatenate([base, odd[k:k + 1]]), 1), _build(np.concatenate([base, odd[k:k + 1]]), 8)
         assert one == team and one[3] == 1 and one[0] == 39 and one[1] < ts.STACK - 1, (odd[k], one)

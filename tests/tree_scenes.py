@@ -86,6 +86,16 @@ def chain_scene(items, lens=False):
     return scene(items, lens, lookfrom=CHAIN_CAMERA_AT, lookat=(4.0, 0.0, 0.0), vfov=6.0, aperture=2e-5, focus_dist=2.0)
 
 
+# spheres that cannot be bounded (non-finite coordinates, coordinates beyond 1e15), as [cx, cy, cz, r] rows: the builder keeps them out of the tree
+UNBOUNDABLE = np.array([[np.inf, 0, 0, 1.0], [0, -np.inf, 0, 1.0], [np.nan, 0, 0, 1.0], [0, 0, 0, np.inf], [0, 0, 0, np.nan], [1e16, 0, 0, 1.0],
+                        [0, 0, -3e15, 1.0], [0, 0, 0, 2e15], [0, 0, 0, -np.inf]])
+
+
+def scene_sized(n):
+    """[n, 4]: n spheres of one size, each as large as the scene -- from the seventeenth on they go into the tree (the cap on big primitives)"""
+    return np.array([[0.1 * k, 0.0, 0.0, 50.0] for k in range(n)])
+
+
 def sphere_geom(items):
     """[n, 4] cx cy cz r of a list of plain spheres: what rtmi_test_build_tree takes"""
     return np.ascontiguousarray([[it.center[0], it.center[1], it.center[2], it.radius] for it in items], np.float64)
