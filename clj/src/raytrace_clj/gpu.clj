@@ -586,6 +586,36 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn render-rays-mis
+  "render-rays-nee under multiple importance sampling (rtmi_render_rays_mis): the same paths and shadow rays, but the light sample and the path's own
+  scatter share each lamp's emission by the balance heuristic, so no contribution exceeds attenuation x emission -- no bright outliers beside a lamp.
+  `light-choice` 0 picks the light uniformly, 1 in proportion to its power.  `lights` as for render-rays-nee (required; an empty list is render-rays).
+  Returns render-rays-nee's map."
+  [scene rays n-groups group lights & {:keys [keys seed ctr0 depth device precision first-ray state light-choice]
+                                       :or {seed 0x5eed0002 ctr0 0 depth 50 device 0 precision 0 first-ray 0 light-choice 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        n    (* n-groups group)
+        rs   (double-array rays)
+        ks   (long-array (or keys (for [g (range n-groups) r (range group)] (sample-key seed g (+ first-ray r)))))
+        lp   (int-array (if (seq lights) lights [0]))
+        nl   (count lights)
+        st   (double-array (or state (* 10 n-groups)))
+        mean (double-array (* 3 n-groups))
+        err  (double-array n-groups)
+        out  (double-array (* 3 n))
+        cnt  (long-array 4)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_rays_mis" scn (int precision) (int n-groups) (int group) (int first-ray) rs ks (long seed) (int ctr0)
+                           (int depth) (int nl) lp (int light-choice) st mean err out cnt))
+          {:mean mean :stderr err :rays out :state st :segments (aget cnt 0) :total-rays (aget cnt 1)
+           :shadow-rays (aget cnt 2) :shadow-rays-occluded (aget cnt 3)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn query-hits
   "The closest hit of every caller-supplied ray of scene {:camera :world} on GPU `device` (rtmi_query_hits): `rays` holds 7 doubles per ray
   (origin, direction, time), `n` of them; the scene's camera is not read.  Every ray takes (t-min, t-max), or its own pair of `t-range`

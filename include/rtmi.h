@@ -827,6 +827,56 @@ int rtmi_probe_paths_nee(rtmi_scene *scene, int32_t precision, int32_t n, const 
                          int32_t n_lights, const int32_t *light_prims, double *out_rgb, uint64_t *out_nseg, int32_t *out_dropped,
                          double *log, int32_t max_seg, int32_t *out_nlog);
 
+/* ---- multiple importance sampling for the light-sampled paths: the light sample and the scatter share each lamp's emission ----
+ * The NEE siblings' arguments plus light_choice behind light_prims: 0 = the light is picked uniformly, 1 = by power; anything else is RTMI_E_ARG.
+ * A light sample's w carries the inverse square of area sampling and is unbounded beside a lamp; the path's own scatter finds that lamp with the
+ * density 2 cos^3 / pi, and the ratio of the two densities at one point is x = p_scatter / p_light = w * q, q = 1 / (the pick's probability).  The balance
+ * heuristic gives the light sample the share m = x / (1 + x) and the closing emission the share of the same form at the point the scatter found, so
+ * every contribution is bounded by T * Le and the expectation is rtmi_render_rays'.
+ * THE MIS RULE, operation by operation as the NEE rule: every product, sum, difference and quotient is one IEEE double operation in the order written,
+ * only + - * / sqrt occur, dot3(a, b) = (ax*bx + ay*by) + az*bz.  Where nothing else is said the NEE rule holds.
+ *   1. Vertices: light samples are taken at the NEE rule's vertices (its step 1).  The path's own stream, rays, hits, scatters and segment count stay
+ *      rtmi_render_rays' bit for bit.
+ *   2. The light.  light_choice 0: the NEE rule's step 2, and q_l = (double)nl for every light.  light_choice 1: omega_l = area_l * ((Le.r + Le.g) +
+ *      Le.b), C_l = the running sum of omega in list order (C_0 = omega_0, C_l = C_(l-1) + omega_l), W = C_(nl-1); l = the first index with u * W < C_l,
+ *      else nl - 1, with the same draw u; q_l = W / omega_l.  If W is not finite and > 0 the call behaves as light_choice 0.  A light with omega_l = 0
+ *      is never picked, and for step 7 it does not count as a sampled light: its emission is kept whole.  omega, C and q are computed on the host and
+ *      travel with the light table.
+ *   3. The sample, its ray and w: the NEE rule's steps 3 and 4, unchanged.
+ *   4. The weight: x = w * q_l, m = x / (1.0 + x); if x is +inf, m = 1.0.  (A vertex that builds no ray has w = 0: x and m are computed all the same.)
+ *   5. The contribution: if the any-hit search finds nothing, accum.c = accum.c + (double)T.c * (Le.c * m) per channel.
+ *   6. The lobe value, at the same vertex, whether or not a shadow ray was built: D = the scattered ray's direction as doubles, nn = the step-3
+ *      normalised record normal, a = dot3(nn, D), DD = dot3(D, D); g = ((a*a)*a) / ((DD*DD)*DD) if the vertex is valid (step 3's finiteness test of p and
+ *      the normal, and a normal with length), a > 0 and DD > 0; otherwise g = +0.0.
+ *   7. The closing emission is kept whole (m' = 1.0) under the conditions where the NEE rule keeps it.  Where the NEE rule drops it -- the previous
+ *      vertex took a light sample and the emitter's primitive is sampled light l' (its first index in the list) -- it is weighted instead:
+ *      s' = the emitter record's normal, normalised as step 3 of the hemisphere rule; cl' = |dot3(s', D)|, D = the arriving ray's direction as doubles;
+ *      t = the record's t as a double; x' = ((((g * cl') / (t*t)) * area_l') * TWO_INV_PI) * q_l', g = the previous vertex' lobe value;
+ *      m' = x' / (1.0 + x'), or 1.0 if x' is +inf, or +0.0 if x' is NaN.  radiance.c = accum.c + (double)emit.c * m'.
+ *      (With d = t * D the NEE weight's cp^3 cl / d2^3 equals g * cl' / t^2: x' is the same density ratio, at the point the scatter found.)
+ *   8. Unchanged from the NEE rule: nl == 0 (the call IS rtmi_render_rays), the refusal of media, the RTMI_F32 scope (weights and g are doubles whatever
+ *      the precision), the four counters, the invariance under chunks and workspace passes.
+ * Errors: the NEE calls', in their order, with light_choice other than 0 or 1 (RTMI_E_ARG) reported directly behind the list's length (n_lights), before
+ * n_groups == 0 succeeds and before the media and the list's entries are looked at.
+ * rtmi_probe_paths_mis: rtmi_probe_paths_nee's sibling.  log (may be NULL): [n][max_seg][RTMI_MIS_REC] doubles per logged vertex: [0..23] the RTMI_NEE_REC
+ *   values (with light_choice 0, l, d and w are rtmi_probe_paths_nee's bit for bit; [21..23] the contribution of step 5); [24] x, [25] m, [26] g (zeros
+ *   unless the vertex takes a light sample); [27] x' on a closing vertex whose emission step 7 weighted, else 0.  out_weight (may be NULL): [n] doubles,
+ *   m' of step 7 -- 1.0 for every path whose closing emission is kept whole or that emits nothing. */
+#define RTMI_MIS_REC 28
+/* host buffers; synchronous */
+int rtmi_render_rays_mis(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first,
+                         const double *rays, const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth,
+                         int32_t n_lights, const int32_t *light_prims, int32_t light_choice,
+                         double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters);
+/* every d_ pointer a device pointer (light_prims stays a host array); asynchronous on `stream` with rtmi_render_device's stream semantics */
+int rtmi_render_rays_mis_device(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first,
+                                const void *d_rays, const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth,
+                                int32_t n_lights, const int32_t *light_prims, int32_t light_choice,
+                                void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream);
+int rtmi_probe_paths_mis(rtmi_scene *scene, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
+                         int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *out_rgb, uint64_t *out_nseg, double *out_weight,
+                         double *log, int32_t max_seg, int32_t *out_nlog);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

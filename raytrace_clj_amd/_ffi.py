@@ -43,6 +43,7 @@ SYMBOLS = [
     "rtmi_ambient_occlusion", "rtmi_ambient_occlusion_device",
     "rtmi_scene_lights", "rtmi_test_scene_lights", "rtmi_direct_irradiance", "rtmi_direct_irradiance_device", "rtmi_render_direct", "rtmi_render_direct_device",
     "rtmi_render_rays_nee", "rtmi_render_rays_nee_device", "rtmi_probe_paths_nee",
+    "rtmi_render_rays_mis", "rtmi_render_rays_mis_device", "rtmi_probe_paths_mis",
 ]
 
 F64, F32 = 0, 1
@@ -57,6 +58,7 @@ HIT_REC = 12  # doubles per ray of rtmi_query_hits: hit?, prim, t, p xyz, normal
 RAYS_REC = 10  # doubles per group record of rtmi_render_rays: sums rgb, Welford mean rgb, Welford M2 rgb, count
 DIRECT_REC = 4  # doubles per point record of rtmi_direct_irradiance / rtmi_render_direct: sum rgb, samples
 NEE_REC = 24  # doubles per logged vertex of rtmi_probe_paths_nee: SEG_REC's twelve, state, light, d xyz, w, T rgb, contribution rgb
+MIS_REC = 28  # doubles per logged vertex of rtmi_probe_paths_mis: NEE_REC's twenty-four, x, m, g, x' (closing vertex)
 DIRECT_MAX_LIGHTS = 32  # RTMI_DIRECT_MAX_LIGHTS: lights one call samples
 EDIT_STREAM_MAX_BYTES = 32768  # RTMI_EDIT_STREAM_MAX_BYTES: changed row payload one rtmi_scene_set_materials_stream call carries
 
@@ -183,6 +185,9 @@ def lib():
     L.rtmi_render_rays_nee.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.rtmi_render_rays_nee_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.rtmi_probe_paths_nee.argtypes = [vp, i32, i32, vp, vp, u64, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    L.rtmi_render_rays_mis.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.rtmi_render_rays_mis_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.rtmi_probe_paths_mis.argtypes = [vp, i32, i32, vp, vp, u64, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

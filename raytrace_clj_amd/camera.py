@@ -328,12 +328,12 @@ def light_samples(points, normals, lights, n_samples, first=0, seed=0x5EED0002, 
 TWO_INV_PI = float.fromhex("0x1.45f306dc9c883p-1")
 
 
-def nee_samples(points, normals, lights, keys_sample, keys_pick):
+def nee_samples(points, normals, lights, keys_sample, keys_pick, light=None):
     """The light samples of light-sampled paths (include/rtmi.h, "the NEE rule", steps 2 - 4), one per vertex, every operation a single IEEE
     operation in the header's order, so rtmi_probe_paths_nee's log columns [13..17] equal these bit for bit.  points, normals [n, 3]: the hit
     points and the records' normals AS THEY ARE (no viewer-side flip; the rule normalises them); lights [nl, LIGHT_REC] (light_table), nl >= 1;
     keys_sample, keys_pick [n] uint64: sample_key(K, j, 0) and sample_key(K, j, 1) of the path keyed K at its vertex j.  The light is
-    min(int(u * nl), nl - 1) with u = draw 0 of keys_pick; the point on it comes from keys_sample as in light_samples.
+    min(int(u * nl), nl - 1) with u = draw 0 of keys_pick (or `light` [n], where given); the point on it comes from keys_sample as in light_samples.
     -> (light [n] int, d [n, 3] = sampled point - p (zeros where no ray is built), w [n] = the reference's lobe 2 cos^3 / pi times the light's
     cosine, its area and the inverse square, as ((((cp*cp)*(cp*cl)) / ((d2*d2)*d2)) * area) * TWO_INV_PI (0 where no ray is built), built [n])."""
     from . import util
@@ -344,6 +344,8 @@ def nee_samples(points, normals, lights, keys_sample, keys_pick):
     if not (len(points) == len(normals) == len(keys_sample) == len(keys_pick)) or nl < 1:
         raise ValueError("points, normals and keys must pair up, and there must be a light")
     l = np.minimum((util.draw_uniforms(keys_pick, 0) * np.float64(nl)).astype(np.int64), nl - 1)   # 2. which light
+    if light is not None:                                                               # (the MIS rule's pick, mis_pick, in its place)
+        l = np.asarray(light, np.int64).reshape(-1)
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         nx, ny, nz = normals[:, 0], normals[:, 1], normals[:, 2]
         len2 = (nx * nx + ny * ny) + nz * nz
@@ -356,3 +358,77 @@ def nee_samples(points, normals, lights, keys_sample, keys_pick):
     d = np.stack([dx, dy, dz], axis=1)
     d[~built] = 0.0
     return l, d, np.where(built, w, 0.0), built
+
+
+def mis_pick(lights, keys_pick, light_choice=0):
+    """Step 2 of the MIS rule (include/rtmi.h): which light each vertex samples, and the inverse pick probability q of every light.
+    light_choice 0: the NEE rule's uniform pick, q = nl.  light_choice 1, by power: omega_l = area_l * ((Le.r + Le.g) + Le.b), C = the running sum in
+    list order, W = C[nl - 1]; the light is the first index with u * W < C_l (else nl - 1) for the same draw u, and q_l = W / omega_l; if W is not finite
+    and > 0 the pick is the uniform one.  -> (light [n] int, q [nl], live [nl] bool: False for a light by power with omega = 0, which is never picked
+    and whose closing emission is kept whole)."""
+    from . import util
+    lights = np.asarray(lights, np.float64).reshape(-1, LIGHT_REC)
+    keys_pick = np.asarray(keys_pick, np.uint64).reshape(-1)
+    nl = len(lights)
+    if nl < 1 or light_choice not in (0, 1):
+        raise ValueError("there must be a light, and light_choice is 0 (uniform) or 1 (by power)")
+    u = util.draw_uniforms(keys_pick, 0)
+    uniform = (np.minimum((u * np.float64(nl)).astype(np.int64), nl - 1), np.full(nl, np.float64(nl)), np.ones(nl, bool))
+    if light_choice == 0:
+        return uniform
+    with np.errstate(all="ignore"):
+        omega = lights[:, 6] * ((lights[:, 7] + lights[:, 8]) + lights[:, 9])
+        C = omega.copy()
+        for k in range(1, nl):
+            C[k] = C[k - 1] + omega[k]
+        W = C[nl - 1]
+        if not (np.isfinite(W) and W > 0.0):
+            return uniform
+        below = (u * W)[:, None] < C[None, :]
+        light = np.where(below.any(axis=1), below.argmax(axis=1), nl - 1)
+        return light, W / omega, omega != 0.0
+
+
+def mis_weight(w, q):
+    """Step 4 of the MIS rule: x = w * q, the ratio p_scatter / p_light of the two strategies' densities at the sampled point, and the balance
+    heuristic's share of the light sample m = x / (1 + x), 1 where x is +inf -> (x, m).  T * Le * m is bounded by T * Le whatever w is."""
+    w, q = np.asarray(w, np.float64), np.asarray(q, np.float64)
+    with np.errstate(all="ignore"):
+        x = w * q
+        m = np.where(x == np.inf, 1.0, x / (1.0 + x))
+    return x, m
+
+
+def mis_lobe(normals, dirs, points=None):
+    """Step 6 of the MIS rule: g = ((a*a)*a) / ((DD*DD)*DD) with a = dot3(nn, D), DD = dot3(D, D), nn the normalised normal and D the scattered
+    direction (any length) -- the reference's lobe 2 cos^3 / pi less its constant; +0.0 where the normal (or the point, if given) is not finite, the
+    normal has no length, or a > 0 and DD > 0 do not both hold."""
+    normals, dirs = np.asarray(normals, np.float64).reshape(-1, 3), np.asarray(dirs, np.float64).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        nx, ny, nz = normals[:, 0], normals[:, 1], normals[:, 2]
+        len2 = (nx * nx + ny * ny) + nz * nz
+        valid = np.isfinite(normals).all(axis=1) & (len2 > 0.0)
+        if points is not None:
+            valid &= np.isfinite(np.asarray(points, np.float64).reshape(-1, 3)).all(axis=1)
+        length = np.sqrt(len2)
+        nx, ny, nz = nx / length, ny / length, nz / length
+        Dx, Dy, Dz = dirs[:, 0], dirs[:, 1], dirs[:, 2]
+        a = (nx * Dx + ny * Dy) + nz * Dz
+        DD = (Dx * Dx + Dy * Dy) + Dz * Dz
+        g = ((a * a) * a) / ((DD * DD) * DD)
+    return np.where(valid & (a > 0.0) & (DD > 0.0), g, 0.0)
+
+
+def mis_closing(g, normals, dirs, t, area, q):
+    """Step 7 of the MIS rule where the closing emission is weighted: the emitter record's normal normalised to s', cl' = |dot3(s', D)| for the arriving
+    direction D, x' = ((((g * cl') / (t*t)) * area) * TWO_INV_PI) * q and m' = x' / (1 + x'), 1 where x' is +inf, +0.0 where it is NaN -> (x', m')."""
+    normals, dirs = np.asarray(normals, np.float64).reshape(-1, 3), np.asarray(dirs, np.float64).reshape(-1, 3)
+    g, t, area, q = (np.asarray(a, np.float64) for a in (g, t, area, q))
+    with np.errstate(all="ignore"):
+        nx, ny, nz = normals[:, 0], normals[:, 1], normals[:, 2]
+        length = np.sqrt((nx * nx + ny * ny) + nz * nz)
+        nx, ny, nz = nx / length, ny / length, nz / length
+        cl = np.abs((nx * dirs[:, 0] + ny * dirs[:, 1]) + nz * dirs[:, 2])
+        x = ((((g * cl) / (t * t)) * area) * TWO_INV_PI) * q
+        m = np.where(np.isnan(x), 0.0, np.where(x == np.inf, 1.0, x / (1.0 + x)))
+    return x, m

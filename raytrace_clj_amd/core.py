@@ -646,17 +646,22 @@ class DeviceScene:
                                                  int(ctr0), int(depth), ptr(state), ptr(out_mean), ptr(out_stderr), ptr(out_rays), ptr(out_counters),
                                                  ptr(stream)))
 
-    def render_with(self, generator, nx, ny, ns, chunk, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", nee=False, lights=None,
+    def render_with(self, generator, nx, ny, ns, chunk, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", nee=False, lights=None, light_choice=0,
                     **generator_args):
         """An nx x ny x ns image through a ray generator of camera.py (generator(nx, ny, s_first, s_count, seed=, **generator_args) -> (rays,
         ctr0), grouped per pixel): chunks of `chunk` samples per pixel folded into one state, keys derived from (seed, pixel, sample) ->
         (linear [ny, nx, 3] = the per-pixel mean, rgb8 = the frame's 8-bit quantiser of it (Context.denoise with no pass), stderr [ny, nx], counters
         summed over the chunks); row 0 = top.  The result does not depend on `chunk`.  nee: the paths sample the lights (render_rays_nee with
-        `lights`; four counters)."""
+        `lights`; four counters); nee="mis": under multiple importance sampling (render_rays_mis with `lights` and `light_choice`)."""
         if chunk <= 0 or ns <= 0:
             raise ValueError("ns and chunk must be > 0")
         def rays_of(k, n):
             return generator(nx, ny, k, n, seed=seed, **generator_args)
+        if isinstance(nee, str):
+            if nee != "mis":
+                raise ValueError("nee is False, True or \"mis\" (got %r)" % nee)
+            return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_mis, 4, lights=lights, light_choice=light_choice, seed=seed, depth=depth,
+                                     precision=precision)
         if nee:
             return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_nee, 4, lights=lights, seed=seed, depth=depth, precision=precision)
         return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays, 2, seed=seed, depth=depth, precision=precision)
@@ -686,12 +691,44 @@ class DeviceScene:
                                                      int(seed), int(ctr0), int(depth), n_listed, ptr(lights), ptr(state), ptr(out_mean), ptr(out_stderr),
                                                      ptr(out_rays), ptr(out_counters), ptr(stream)))
 
-    def render_nee(self, nx, ny, ns, chunk, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", lights=None):
+    # ---- multiple importance sampling: the light sample and the scatter share each lamp's emission (THE MIS RULE of include/rtmi.h) ----------
+    @staticmethod
+    def _light_choice(light_choice):
+        """0 / "uniform", 1 / "power" -> the C entry's light_choice (anything else goes through as an integer and is refused there)"""
+        return MIS_CHOICES[light_choice] if isinstance(light_choice, str) else int(light_choice)
+
+    def render_rays_mis(self, rays, group=1, lights=None, light_choice=0, keys=None, seed=RENDER_SEED, ctr0=0, depth=DEFAULT_DEPTH, precision="f64",
+                        first=0, state=None, return_rays=False):
+        """render_rays_nee under multiple importance sampling (rtmi_render_rays_mis): the same path and the same shadow rays, but the light sample
+        counts with the balance heuristic's share m = x / (1 + x), x = p_scatter / p_light, and a closing emission on a sampled light -- which
+        render_rays_nee drops -- with the scatter's share, so every contribution is at most T * Le: no bright outliers beside a lamp.
+        light_choice: 0 / "uniform" or 1 / "power" (the light is picked in proportion to area x (Le.r + Le.g + Le.b)).  camera.mis_pick,
+        mis_weight, mis_lobe and mis_closing restate the rule.  -> render_rays_nee's tuple."""
+        rays, group, n_groups, keys = self._rays_inputs(rays, group, keys, state)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        mean, err, cnt = np.zeros((n_groups, 3), np.float64), np.zeros(n_groups, np.float64), np.zeros(4, np.uint64)
+        out = np.zeros((len(rays), 3), np.float64) if return_rays else None
+        check(_ffi.lib().rtmi_render_rays_mis(self.handle, _PRECISION[precision], n_groups, group, int(first), ptr(rays), ptr(keys), int(seed), int(ctr0),
+                                              int(depth), n_listed, ptr(lights), self._light_choice(light_choice), ptr(state), ptr(mean), ptr(err),
+                                              ptr(out), ptr(cnt)))
+        return mean, err, cnt, out
+
+    def render_rays_mis_device(self, n_groups, group, rays, out_mean, out_stderr, lights=None, light_choice=0, keys=None, seed=RENDER_SEED, ctr0=0,
+                               depth=DEFAULT_DEPTH, precision="f64", first=0, state=None, out_rays=None, out_counters=None, stream=None):
+        """render_rays_mis on HBM-resident buffers (lights stays a host list; out_counters: four uint64); asynchronous, render_device's stream
+        semantics.  A state's count is the caller's contract: it is not read back."""
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        check(_ffi.lib().rtmi_render_rays_mis_device(self.handle, _PRECISION[precision], int(n_groups), int(group), int(first), ptr(rays), ptr(keys),
+                                                     int(seed), int(ctr0), int(depth), n_listed, ptr(lights), self._light_choice(light_choice), ptr(state),
+                                                     ptr(out_mean), ptr(out_stderr), ptr(out_rays), ptr(out_counters), ptr(stream)))
+
+    def render_nee(self, nx, ny, ns, chunk, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", lights=None, mis=False, light_choice=0):
         """An nx x ny x ns frame of the scene's own camera (of either kind) through light-sampled paths, folded per pixel through one state as
         render_with folds.  Film jitter, lens draws and path streams come from three seeds derived from `seed` (sample_key(seed, 0 / 1 / 2, 0)),
         so none of them shares draws with another: sample s of pixel g jitters with draws 0 and 1 of sample_key(film, g, s), its camera ray is
         probe_camera's for that (u, v) with the stream sample_key(lens, g, s), and its path is keyed sample_key(paths, g, s) from draw 0.
-        -> render_with's tuple (four counters); the result does not depend on `chunk`."""
+        -> render_with's tuple (four counters); the result does not depend on `chunk`.  mis: the same rays and paths through render_rays_mis with
+        `light_choice`."""
         from . import util
         if nx <= 0 or ny <= 0 or chunk <= 0 or ns <= 0:
             raise ValueError("nx, ny, ns and chunk must be > 0")
@@ -703,6 +740,9 @@ class DeviceScene:
             u = ((pix % nx).astype(np.float64) + util.draw_uniforms(fk, 0)) / np.float64(nx)
             v = ((pix // nx).astype(np.float64) + util.draw_uniforms(fk, 1)) / np.float64(ny)
             return self.probe_camera(np.stack([u, v], axis=1), util.sample_keys(lens, pix, ss), precision=precision)[:, :7], 0
+        if mis:
+            return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_mis, 4, lights=lights, light_choice=light_choice, seed=paths, depth=depth,
+                                     precision=precision)
         return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_nee, 4, lights=lights, seed=paths, depth=depth, precision=precision)
 
     # ---- closest-hit and any-hit queries: picking, first hits, shadow / ambient-occlusion / line-of-sight rays --------------------------------
@@ -998,6 +1038,20 @@ class DeviceScene:
         check(_ffi.lib().rtmi_probe_paths_nee(self.handle, _PRECISION[precision], n, ptr(rays), ptr(keys), ctr0, depth, n_listed, ptr(lights),
                                               ptr(rgb), ptr(nseg), ptr(dropped), ptr(log), max_seg, ptr(nlog)))
         return rgb, nseg, log, nlog, dropped
+
+    def probe_paths_mis(self, rays, keys, lights=None, light_choice=0, depth=DEFAULT_DEPTH, ctr0=0, max_seg=0, precision="f64"):
+        """probe_paths_nee for the MIS rule (rtmi_probe_paths_mis) -> (rgb [n, 3], segment counts, log [n, max_seg, MIS_REC] or None, logged vertices
+        per path, weight float64 [n] = the factor on the closing emission, 1 where it is kept whole).  A log row: NEE_REC's twenty-four values, then
+        x, m, g of the vertex' light sample and, on a closing vertex whose emission was weighted, x'."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+        keys = np.ascontiguousarray(keys, np.uint64)
+        n = len(rays)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        rgb, nseg, nlog, weight = np.zeros((n, 3)), np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        log = np.zeros((n, max_seg, _ffi.MIS_REC)) if max_seg else None
+        check(_ffi.lib().rtmi_probe_paths_mis(self.handle, _PRECISION[precision], n, ptr(rays), ptr(keys), ctr0, depth, n_listed, ptr(lights),
+                                              self._light_choice(light_choice), ptr(rgb), ptr(nseg), ptr(weight), ptr(log), max_seg, ptr(nlog)))
+        return rgb, nseg, log, nlog, weight
 
     def probe_camera(self, uv, keys, precision="f64"):
         uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
@@ -1594,6 +1648,38 @@ def _nee_name(name):
     return root + ".nee" + ext
 
 
+MIS_CHOICES = {"uniform": 0, "power": 1}  # light_choice of the MIS calls
+
+
+def _mis_flags(argv, panorama=False, orbit=False):
+    """-> (the other arguments, None or the light choice of --mis [uniform|power], default uniform); refused where --nee is, before any device work"""
+    rest, choice, k = [], None, 0
+    while k < len(argv):
+        a = argv[k]
+        if a == "--mis":
+            if choice is not None:
+                raise SystemExit("--mis given twice")
+            choice = "uniform"
+            if k + 1 < len(argv) and argv[k + 1] in MIS_CHOICES:
+                choice = argv[k + 1]
+                k += 1
+        elif a.startswith("--mis"):
+            raise SystemExit("--mis takes uniform or power as a separate word (got %r)" % a)
+        else:
+            rest.append(a)
+        k += 1
+    if choice is not None and (panorama or orbit):
+        raise SystemExit("--mis does not combine with --orbit or --panorama")
+    return rest, choice
+
+
+def _mis_name(name):
+    """x.png -> x.mis.png: the frame of the MIS paths is written next to the frame"""
+    import os
+    root, ext = os.path.splitext(name)
+    return root + ".mis" + ext
+
+
 def _direct_name(name):
     """x.png -> x.direct.png: the directly lit view is written next to the frame"""
     import os
@@ -1666,7 +1752,10 @@ def main(argv=None):
     --direct N also writes the view lit directly (DeviceScene.render_direct: N shadow rays per first hit towards every area light the scene holds,
     sampled on the device) as name.direct.ext, beside the frame.  It does not combine with --orbit or --panorama.
     --nee also writes the frame traced by light-sampled paths (DeviceScene.render_nee: ns paths per pixel, one shadow ray per Lambertian vertex) as
-    name.nee.ext, beside the frame.  It does not combine with --orbit or --panorama, and a scene that holds a ConstantMedium is refused."""
+    name.nee.ext, beside the frame.  It does not combine with --orbit or --panorama, and a scene that holds a ConstantMedium is refused.
+    --mis [uniform|power] also writes the frame of those paths under multiple importance sampling (DeviceScene.render_nee(mis=True): the light sample
+    and the scatter share each lamp's emission by the balance heuristic; the light is picked uniformly, the default, or by power) as name.mis.ext.
+    It is refused where --nee is."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
     argv, direct = _direct_flags(argv)
@@ -1683,6 +1772,7 @@ def main(argv=None):
     if direct is not None and (panorama or orbit_views is not None):
         raise SystemExit("--direct does not combine with --orbit or --panorama")
     argv, nee = _nee_flags(argv, panorama, orbit_views is not None)
+    argv, mis = _mis_flags(argv, panorama, orbit_views is not None)
     argv, accumulate = _accumulate_flags(argv, orbit_views)
     argv, adaptive_denoised = _adaptive_denoised_flags(argv)
     if adaptive_denoised is not None and not any(a.split("=", 1)[0] == "--denoise" for a in argv):
@@ -1702,8 +1792,8 @@ def main(argv=None):
         raise SystemExit("unknown scene %r; one of %s" % (which, ", ".join(sorted(SCENES))))
     tstart = time.time()
     sc = SCENES[which](scenes, nx, ny)
-    if nee and (fl.flatten(sc).prim_kind & 15 == fl.PRIM_MEDIUM).any():
-        raise SystemExit("--nee: scene %r holds a ConstantMedium, which the light-sampled paths do not trace" % which)
+    if (nee or mis is not None) and (fl.flatten(sc).prim_kind & 15 == fl.PRIM_MEDIUM).any():
+        raise SystemExit("%s: scene %r holds a ConstantMedium, which the light-sampled paths do not trace" % ("--nee" if nee else "--mis", which))
     if accumulate is not None:
         return _render_orbit_accumulated(sc, name, nx, ny, nr, orbit_views, dn_iterations, dn_samples, accumulate, tstart)
     if orbit_views is not None:
@@ -1808,6 +1898,13 @@ def main(argv=None):
         finally:
             ds.close()
         _save_image(_nee_name(name), lit)
+    if mis is not None:
+        ds = DeviceScene(sc)
+        try:
+            lit = ds.render_nee(nx, ny, nr, min(nr, 16), mis=True, light_choice=mis)[1]
+        finally:
+            ds.close()
+        _save_image(_mis_name(name), lit)
     return 0
 
 

@@ -1585,31 +1585,53 @@ __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WA
 // flags.  The pending contribution T * Le * w * nl waits in the lane's LDS slot, and the running sum `accum` lives there too: neither is a register
 // while a tree is walked.
 constexpr int kNeeSlots = 6; // doubles per lane in LDS: accum.rgb, pending.rgb; slot s of lane t at nee_lds[s * kBlock + t]
+constexpr int kMisSlots = 7; // the MIS instantiations': the lobe value g of the path's last light-sampled vertex behind them
 constexpr double kTwoInvPi = 0x1.45f306dc9c883p-1;
 struct NeeLights {
     const double *rec; // [n][kLightRec]: set_nee_lights_kernel's copy of the call's light table
     const int *prim;   // [n]: the sampled lights' primitives (what step 6 compares a closing emitter with)
     unsigned n;        // >= 1
 };
+// The MIS instantiations' light table (set_mis_lights_kernel) carries, behind the kLightRec rows and the primitives, the pick of the MIS rule's step 2:
+// rec[kMisRows] = W (+0.0: the uniform pick), then per light {C_l, q_l} from rec[kMisRows + 2].  No other kernel reads past the primitives.
+constexpr int kMisRows = RTMI_DIRECT_MAX_LIGHTS * kLightRec + RTMI_DIRECT_MAX_LIGHTS / 2;
 
-// Is primitive `orig` one of the sampled lights?  (at most RTMI_DIRECT_MAX_LIGHTS compares, at a path's end only)
-__device__ inline bool nee_sampled_light(const NeeLights &nl, int orig) {
-    bool found = false;
-    for (unsigned l = 0; l < nl.n; ++l) found = found || nl.prim[l] == orig;
+// Which of the sampled lights is primitive `orig`: its first index in the list, -1 if none  (at most RTMI_DIRECT_MAX_LIGHTS compares, at a path's end only)
+__device__ inline int nee_sampled_light(const NeeLights &nl, int orig) {
+    int found = -1;
+    for (unsigned l = 0; l < nl.n; ++l) found = found < 0 && nl.prim[l] == orig ? (int)l : found;
     return found;
 }
 
 // Steps 2 - 4 of the NEE rule for the vertex j of the path keyed K: the light l, the shadow ray q[7] (zeros where none is built) and the weight w.
 // Every lane of the wave calls (the disk sampler is cooperative), the lanes whose vertex takes a light sample with `want`.  As in generate_light_ray
 // the rounds stand before the geometry (no operation changes); unlike there the normal is the record's as it is.
+// MIS: the light by the MIS rule's step 2, and xmg = {x, m, g} of its steps 4 and 6 for the scattered direction D.
+template <bool MIS = false>
 __device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsigned j, double px, double py, double pz, double nx, double ny, double nz,
-                                     double time, double *q, double &w, int &l) {
+                                     double time, double *q, double &w, int &l, const double *D = nullptr, double *xmg = nullptr) {
     const double big = __builtin_inf();
     const double len2 = dot3(nx, ny, nz, nx, ny, nz);
     bool ok = want && ::fabs(px) < big && ::fabs(py) < big && ::fabs(pz) < big && ::fabs(nx) < big && ::fabs(ny) < big && ::fabs(nz) < big && len2 > 0.0;
+    const bool valid = ok; // (MIS) the vertex itself is sound, whatever becomes of its light sample
     const u64 kpick = sample_key(K, (u64)j, 1ull), key = sample_key(K, (u64)j, 0ull);
     const double up = Real<double>::uniform(mix64(kpick + RTMI_GOLD)); // draw 0 of the picking stream
     l = min((int)(up * (double)nl.n), (int)nl.n - 1);
+    if constexpr (MIS) {
+        const double *M = nl.rec + kMisRows;
+        const double W = M[0];
+        if (W > 0.0) { // by power: the first light whose running sum exceeds u * W
+            const double uw = up * W;
+            int pick = (int)nl.n - 1;
+            bool found = false;
+            for (unsigned k = 0; k < nl.n; ++k) {
+                const bool here = !found && uw < M[2 + 2 * k];
+                pick = here ? (int)k : pick;
+                found = found || here;
+            }
+            l = pick;
+        }
+    }
     const double *L = nl.rec + (size_t)l * kLightRec;
     const int kind = (int)L[0];
     const bool sphere = kind == RTMI_PRIM_SPHERE || kind == RTMI_PRIM_UVSPHERE;
@@ -1621,6 +1643,10 @@ __device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsi
     const double g0 = L[1], g1 = L[2], g2 = L[3], g3 = L[4], g4 = L[5], area = L[6];
     const double len = ::sqrt(len2);
     nx = nx / len; ny = ny / len; nz = nz / len;
+    if constexpr (MIS) { // step 6: the lobe's value along the scattered ray, less its constant: cos^3 with the direction's length divided out
+        const double a = dot3(nx, ny, nz, D[0], D[1], D[2]), DD = dot3(D[0], D[1], D[2], D[0], D[1], D[2]);
+        xmg[2] = valid && a > 0.0 && DD > 0.0 ? ((a * a) * a) / ((DD * DD) * DD) : 0.0;
+    }
     double qx, qy, qz, sx, sy, sz;
     if (sphere) { // Marsaglia: a uniform point of the unit disk -> a uniform point of the unit sphere
         const double S = x * x + y * y, root = ::sqrt(1.0 - S);
@@ -1641,6 +1667,11 @@ __device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsi
     }
     ok = ok && d2 > 0.0 && cp > 0.0 && cl > 0.0;
     w = ok ? ((((cp * cp) * (cp * cl)) / ((d2 * d2) * d2)) * area) * kTwoInvPi : 0.0; // the reference's lobe 2 cos^3 / pi, the light's cosine, the inverse square
+    if constexpr (MIS) { // step 4: x = p_scatter / p_light, m = the balance heuristic's share of the light sample
+        const double xx = w * nl.rec[kMisRows + 3 + 2 * l];
+        xmg[0] = xx;
+        xmg[1] = xx == big ? 1.0 : xx / (1.0 + xx);
+    }
     q[0] = ok ? px : 0.0; q[1] = ok ? py : 0.0; q[2] = ok ? pz : 0.0;
     q[3] = ok ? dx : 0.0; q[4] = ok ? dy : 0.0; q[5] = ok ? dz : 0.0; q[6] = ok ? time : 0.0;
     return ok;
@@ -1649,7 +1680,9 @@ __device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsi
 // Steps 2 - 5 of the NEE rule, for the whole wave: `lamb` lanes sit at a vertex that scattered as a Lambertian (P is already the scattered ray: its
 // origin is the hit point, its attenuation T).  slot: the lane's LDS column (accum, pending).  rec (probe only, may be null): the vertex' RTMI_NEE_REC row.
 // -> the light-sample state of the header: 0 none, 1 built and unoccluded, 2 built and occluded, 3 built no ray.
-template <typename R, int VARIANT, bool EXT>
+// MIS (THE MIS RULE): the pending contribution is T * (Le * m), and the lobe value g of the scattered ray goes to the lane's seventh slot, where the path's
+// end finds it; rec is then an RTMI_MIS_REC row.
+template <typename R, int VARIANT, bool EXT, bool MIS = false>
 __device__ inline int nee_vertex(SceneRef sc, Prim4<R> *lds, const NeeLights &nl, bool lamb, u64 K, unsigned j, const Path<R> &P, double nx, double ny,
                                  double nz, double *slot, double *rec) {
     Path<R> S;
@@ -1657,13 +1690,20 @@ __device__ inline int nee_vertex(SceneRef sc, Prim4<R> *lds, const NeeLights &nl
     {
         double q[7], w;
         int l;
-        ok = nee_light_ray(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l);
+        double xmg[3] = {0.0, 0.0, 0.0};
+        if constexpr (MIS) {
+            const double D[3] = {(double)P.dx, (double)P.dy, (double)P.dz};
+            ok = nee_light_ray<true>(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l, D, xmg);
+            if (lamb) slot[6 * kBlock] = xmg[2];
+            if (rec && lamb) { rec[24] = xmg[0]; rec[25] = xmg[1]; rec[26] = xmg[2]; }
+        } else ok = nee_light_ray(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l);
         const double *L = nl.rec + (size_t)l * kLightRec;
         const double many = (double)nl.n;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const double T = (double)(c == 0 ? P.ar : c == 1 ? P.ag : P.ab);
-            slot[(3 + c) * kBlock] = ok ? T * ((L[7 + c] * w) * many) : 0.0;
+            if constexpr (MIS) slot[(3 + c) * kBlock] = ok ? T * (L[7 + c] * xmg[1]) : 0.0;
+            else slot[(3 + c) * kBlock] = ok ? T * ((L[7 + c] * w) * many) : 0.0;
             if (rec && lamb) rec[18 + c] = T;
         }
         if (rec && lamb) { rec[13] = (double)l; rec[14] = q[3]; rec[15] = q[4]; rec[16] = q[5]; rec[17] = w; }
@@ -1685,6 +1725,18 @@ __device__ inline int nee_vertex(SceneRef sc, Prim4<R> *lds, const NeeLights &nl
     return state;
 }
 
+// Step 7 of the MIS rule: the factor m' on the closing emission of a path that arrives along D at parameter t on sampled light lp, whose record's normal
+// is (nx, ny, nz); g = the lobe value its previous vertex left in LDS.  *xq = x', the density ratio at the point the scatter found.
+__device__ inline double mis_closing_weight(const NeeLights &nl, int lp, double g, double nx, double ny, double nz, double Dx, double Dy, double Dz, double t,
+                                            double *xq) {
+    const double len = ::sqrt(dot3(nx, ny, nz, nx, ny, nz));
+    nx = nx / len; ny = ny / len; nz = nz / len;
+    const double cl = ::fabs(dot3(nx, ny, nz, Dx, Dy, Dz));
+    const double x = ((((g * cl) / (t * t)) * nl.rec[(size_t)lp * kLightRec + 6]) * kTwoInvPi) * nl.rec[kMisRows + 3 + 2 * lp];
+    *xq = x;
+    return x != x ? 0.0 : x == __builtin_inf() ? 1.0 : x / (1.0 + x);
+}
+
 struct NeeParams {
     RaysParams rp;   // rays_kernel's arguments; counters: [0] += segments, [2] += shadow rays built, [3] += shadow rays occluded
     NeeLights lights;
@@ -1695,11 +1747,12 @@ struct NeeParams {
 // sample; at 3 they take 131 - 141 VGPRs without scratch and measured 4 - 7 % faster (A/B: make variant NAME=nee_w4 FLAGS=-DRTMI_NEE_MIN_WAVES=4)
 #define RTMI_NEE_MIN_WAVES 3
 #endif
-template <typename R, int VARIANT, bool EXT = false>
+// MIS (rtmi_render_rays_mis*): THE MIS RULE of rtmi.h -- the same path and the same shadow rays, the balance heuristic on both ends.
+template <typename R, int VARIANT, bool EXT = false, bool MIS = false>
 __global__ void __launch_bounds__(kBlock, RTMI_NEE_MIN_WAVES) rays_nee_kernel(ScenePtr scp, NeeParams np) {
     static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the refill loop is per wave");
     SceneRef sc = *scp;
-    __shared__ double nee_lds[kNeeSlots * kBlock];
+    __shared__ double nee_lds[(MIS ? kMisSlots : kNeeSlots) * kBlock];
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Prim4<R> *lds = reinterpret_cast<Prim4<R> *>(smem);
     double *slot = nee_lds + threadIdx.x;
@@ -1757,14 +1810,22 @@ __global__ void __launch_bounds__(kBlock, RTMI_NEE_MIN_WAVES) rays_nee_kernel(Sc
             alive = shade_segment_nee<R, EXT>(sc, P, best_t, best_i, emit, h, lamb);
             nx = (double)h.nx; ny = (double)h.ny; nz = (double)h.nz;
             if (!alive) { // step 6: a sampled light's emission was already counted at the previous vertex
-                const bool drop = sampled && best_i >= 0 && nee_sampled_light(np.lights, best_i);
                 double *out = rp.samples + (size_t)out_item * 3;
+                if constexpr (MIS) { // step 7 of the MIS rule: that emission is weighted, not dropped -- the scatter's share of the two strategies
+                    const int lp = sampled && best_i >= 0 ? nee_sampled_light(np.lights, best_i) : -1;
+                    double mw = 1.0, xq;
+                    if (lp >= 0) mw = mis_closing_weight(np.lights, lp, slot[6 * kBlock], nx, ny, nz, (double)P.dx, (double)P.dy, (double)P.dz, (double)h.t, &xq);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) out[c] = slot[c * kBlock] + (drop ? 0.0 : (double)emit[c]);
+                    for (int c = 0; c < 3; ++c) out[c] = slot[c * kBlock] + (double)emit[c] * mw;
+                } else {
+                    const bool drop = sampled && best_i >= 0 && nee_sampled_light(np.lights, best_i) >= 0;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) out[c] = slot[c * kBlock] + (drop ? 0.0 : (double)emit[c]);
+                }
             }
         }
         if (__any(lamb ? 1 : 0)) { // wave-uniform: all 64 lanes enter the disk rounds and the any-hit search
-            const int state = nee_vertex<R, VARIANT, EXT>(sc, lds, np.lights, lamb, P.key, seg, P, nx, ny, nz, slot, nullptr);
+            const int state = nee_vertex<R, VARIANT, EXT, MIS>(sc, lds, np.lights, lamb, P.key, seg, P, nx, ny, nz, slot, nullptr);
             n_built += state == 1 || state == 2 ? 1u : 0u;
             n_occ += state == 2 ? 1u : 0u;
         }
@@ -1790,18 +1851,18 @@ struct NeeProbeParams {
     int depth;
     double *out_rgb;   // [n][3]
     u64 *out_nseg;     // [n], or null
-    int *out_dropped;  // [n], or null: 1 where the closing emission was dropped
-    double *log;       // [n][max_seg][RTMI_NEE_REC], zeroed before the launch, or null
+    void *out_end;     // [n], or null: int32, 1 where the closing emission was dropped; MIS: doubles, the factor on the closing emission
+    double *log;       // [n][max_seg][RTMI_NEE_REC] (MIS: RTMI_MIS_REC), zeroed before the launch, or null
     int max_seg;
     int *out_nlog;     // [n], or null
     NeeLights lights;  // n == 0: no vertex takes a light sample
 };
 
-template <typename R, int VARIANT, bool EXT = false>
+template <typename R, int VARIANT, bool EXT = false, bool MIS = false>
 __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, NeeProbeParams pp) {
     static_assert(VARIANT >= SCAN_SGPR, "the loop is per wave, as rays_nee_kernel's");
     SceneRef sc = *scp;
-    __shared__ double nee_lds[kNeeSlots * kBlock];
+    __shared__ double nee_lds[(MIS ? kMisSlots : kNeeSlots) * kBlock];
     extern __shared__ __attribute__((aligned(16))) char smem[];
     Prim4<R> *lds = reinterpret_cast<Prim4<R> *>(smem);
     double *slot = nee_lds + threadIdx.x;
@@ -1811,8 +1872,10 @@ __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, N
     Path<R> P;
     load_ray<R>(pp.rays + row * 7, P);
     seed_stream(P, alive ? pp.keys[k] : 0ull, pp.ctr0); P.depth = pp.depth;
-    double *log = pp.log ? pp.log + row * (size_t)pp.max_seg * RTMI_NEE_REC : nullptr;
+    constexpr int kRec = MIS ? RTMI_MIS_REC : RTMI_NEE_REC;
+    double *log = pp.log ? pp.log + row * (size_t)pp.max_seg * kRec : nullptr;
     int nlog = 0, dropped = 0;
+    double weight = 1.0; // (MIS) the factor on the closing emission
     u64 nseg = 0;
     unsigned seg = 0;
     bool sampled = false;
@@ -1833,26 +1896,40 @@ __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, N
             lamb = lamb && pp.lights.n > 0;
             nx = (double)h.nx; ny = (double)h.ny; nz = (double)h.nz;
             if (log && best_i >= 0 && nlog < pp.max_seg) { // shade_segment's record (a miss logs none); [12..23] stay zeros unless the vertex takes a light sample
-                rec = log + (size_t)nlog * RTMI_NEE_REC;
+                rec = log + (size_t)nlog * kRec;
                 rec[0] = h.orig; rec[1] = h.t; rec[2] = h.px; rec[3] = h.py; rec[4] = h.pz; rec[5] = h.nx; rec[6] = h.ny; rec[7] = h.nz;
                 rec[8] = alive ? P.dx : 0; rec[9] = alive ? P.dy : 0; rec[10] = alive ? P.dz : 0; rec[11] = alive ? 1.0 : 0.0;
                 ++nlog;
             }
             if (!alive) {
-                const bool drop = sampled && best_i >= 0 && nee_sampled_light(pp.lights, best_i);
-                dropped = drop ? 1 : 0;
+                if constexpr (MIS) {
+                    const int lp = sampled && best_i >= 0 ? nee_sampled_light(pp.lights, best_i) : -1;
+                    if (lp >= 0) {
+                        double xq;
+                        weight = mis_closing_weight(pp.lights, lp, slot[6 * kBlock], nx, ny, nz, (double)P.dx, (double)P.dy, (double)P.dz, (double)h.t, &xq);
+                        if (rec) rec[27] = xq;
+                    }
 #pragma unroll
-                for (int c = 0; c < 3; ++c) rgb[c] = slot[c * kBlock] + (drop ? 0.0 : (double)emit[c]);
+                    for (int c = 0; c < 3; ++c) rgb[c] = slot[c * kBlock] + (double)emit[c] * weight;
+                } else {
+                    const bool drop = sampled && best_i >= 0 && nee_sampled_light(pp.lights, best_i) >= 0;
+                    dropped = drop ? 1 : 0;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) rgb[c] = slot[c * kBlock] + (drop ? 0.0 : (double)emit[c]);
+                }
             }
         }
-        if (__any(lamb ? 1 : 0)) nee_vertex<R, VARIANT, EXT>(sc, lds, pp.lights, lamb, P.key, seg, P, nx, ny, nz, slot, rec);
+        if (__any(lamb ? 1 : 0)) nee_vertex<R, VARIANT, EXT, MIS>(sc, lds, pp.lights, lamb, P.key, seg, P, nx, ny, nz, slot, rec);
         sampled = lamb;
         ++seg;
     }
     if (k < pp.n) {
         pp.out_rgb[3 * k] = rgb[0]; pp.out_rgb[3 * k + 1] = rgb[1]; pp.out_rgb[3 * k + 2] = rgb[2];
         if (pp.out_nseg) pp.out_nseg[k] = nseg;
-        if (pp.out_dropped) pp.out_dropped[k] = dropped;
+        if (pp.out_end) {
+            if constexpr (MIS) static_cast<double *>(pp.out_end)[k] = weight;
+            else static_cast<int *>(pp.out_end)[k] = dropped;
+        }
         if (pp.out_nlog) pp.out_nlog[k] = nlog;
     }
 }
@@ -5576,9 +5653,10 @@ int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const 
 // call's behind the plain call's: check_nee_args, beside its table below), a host form's state, then the scene's device is current.  *work
 // false: nothing to trace, the entry returns RTMI_OK at once.
 struct NeeLightTable;
-int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work);
+int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work, int light_choice = 0);
 int rays_begin(rtmi_scene *s, int precision, int n_groups, int group, int g_first, int depth, const void *rays, const void *mean, const void *se,
-               const double *host_state, bool *work, NeeLightTable *T = nullptr, int n_lights = 0, const int32_t *light_prims = nullptr) {
+               const double *host_state, bool *work, NeeLightTable *T = nullptr, int n_lights = 0, const int32_t *light_prims = nullptr,
+               int light_choice = 0) {
     *work = false;
     if (n_groups < 0 || group <= 0 || g_first < 0 || depth < 0)
         return fail(RTMI_E_ARG, "n_groups, g_first, depth must be >= 0 and group > 0 (got %d %d %d %d)", n_groups, g_first, depth, group);
@@ -5592,7 +5670,7 @@ int rays_begin(rtmi_scene *s, int precision, int n_groups, int group, int g_firs
     if (s->uses_perlin && !s->have_perlin) return fail(RTMI_E_STATE, "the scene holds a Perlin texture: call rtmi_scene_set_perlin first");
     if (s->max_image >= s->dev.n_images) return fail(RTMI_E_STATE, "the scene holds an ImageMap with index %d: call rtmi_scene_set_images first", s->max_image);
     *work = n_groups > 0;
-    int rc = T ? check_nee_args(s, n_groups, n_lights, light_prims, *T, work) : RTMI_OK;
+    int rc = T ? check_nee_args(s, n_groups, n_lights, light_prims, *T, work, light_choice) : RTMI_OK;
     if (rc || !*work) return rc;
     rc = check_state_counts(host_state, (size_t)n_groups, RTMI_RAYS_REC, 9, g_first, "group", "rays, g_first");
     if (rc) return rc;
@@ -6269,6 +6347,14 @@ struct ProbePathsNee {
     static constexpr bool wave_level = true;
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT>; }
 };
+// the MIS rule's instantiations of the two kernels (rtmi_render_rays_mis*, rtmi_probe_paths_mis)
+struct MisPass : NeePass {
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, true>; }
+};
+struct ProbePathsMis {
+    static constexpr bool wave_level = true;
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, true>; }
+};
 
 struct NeeLightTable { LightTable t; int prim[RTMI_DIRECT_MAX_LIGHTS]; };
 constexpr size_t kNeeLightBytes = kLightTableBytes + sizeof(int) * RTMI_DIRECT_MAX_LIGHTS;
@@ -6304,10 +6390,59 @@ int upload_nee_lights(rtmi_ctx *c, const NeeLightTable &T, NeeLights &L, hipStre
     return RTMI_OK;
 }
 
+// The MIS calls' table: the NEE table, then the pick of the MIS rule's step 2 -- {W, -, then C_l, q_l per light} -- where the MIS instantiations read it
+// (kMisRows).  It goes through a kernel of its own: what set_nee_lights_kernel stores is what it always stored.
+constexpr int kMisWords = 2 + 2 * RTMI_DIRECT_MAX_LIGHTS;
+struct MisLightTable { NeeLightTable t; double mis[kMisWords]; };
+constexpr size_t kMisLightBytes = kNeeLightBytes + sizeof(double) * kMisWords;
+static_assert(kNeeLightBytes == sizeof(double) * kMisRows, "the MIS rows start where the NEE table ends");
+__global__ void __launch_bounds__(64) set_mis_lights_kernel(MisLightTable t, double *dst) {
+    const int n = t.t.t.n;
+    for (int i = (int)threadIdx.x; i < n * kLightRec; i += 64) dst[i] = t.t.t.rec[i];
+    if ((int)threadIdx.x < n) reinterpret_cast<int *>(dst + RTMI_DIRECT_MAX_LIGHTS * kLightRec)[threadIdx.x] = t.t.prim[threadIdx.x];
+    for (int i = (int)threadIdx.x; i < 2 + 2 * n; i += 64) dst[kMisRows + i] = t.mis[i];
+}
+
+// Step 2 of the MIS rule on the host: q_l = nl and W = 0 (the uniform pick) for light_choice 0, and for light_choice 1 whose W is not finite and > 0;
+// else W, the running sums and q_l = W / omega_l.  A light by power with omega = 0 is never picked and is no sampled light for step 7: its primitive
+// leaves the list the closing emitter is compared with.
+void make_mis_rows(MisLightTable &T, int light_choice) {
+    const int n = T.t.t.n;
+    double *M = T.mis;
+    M[0] = 0.0; M[1] = 0.0;
+    for (int l = 0; l < RTMI_DIRECT_MAX_LIGHTS; ++l) { M[2 + 2 * l] = 0.0; M[3 + 2 * l] = (double)n; }
+    if (light_choice != 1 || n == 0) return;
+    double omega[RTMI_DIRECT_MAX_LIGHTS], cum[RTMI_DIRECT_MAX_LIGHTS];
+    for (int l = 0; l < n; ++l) {
+        const double *r = T.t.t.rec + (size_t)l * kLightRec;
+        omega[l] = r[6] * ((r[7] + r[8]) + r[9]);
+        cum[l] = l ? cum[l - 1] + omega[l] : omega[l];
+    }
+    const double W = cum[n - 1];
+    if (!(std::isfinite(W) && W > 0.0)) return;
+    M[0] = W;
+    for (int l = 0; l < n; ++l) {
+        M[2 + 2 * l] = cum[l]; M[3 + 2 * l] = W / omega[l];
+        if (omega[l] == 0.0) T.t.prim[l] = -1;
+    }
+}
+
+int upload_mis_lights(rtmi_ctx *c, const MisLightTable &T, NeeLights &L, hipStream_t st) {
+    const int rc = c->nee_ws.ensure(kMisLightBytes);
+    if (rc) return rc;
+    L.rec = reinterpret_cast<const double *>(c->nee_ws.p);
+    L.prim = reinterpret_cast<const int *>(static_cast<const char *>(c->nee_ws.p) + kLightTableBytes);
+    L.n = (unsigned)T.t.t.n;
+    hipLaunchKernelGGL(set_mis_lights_kernel, dim3(1), dim3(64), 0, st, T, const_cast<double *>(L.rec));
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+
 // what both entries check behind rtmi_render_rays' own checks, in the header's order; *work: is there anything to trace?
-int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work) {
+int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work, int light_choice) {
     *work = false;
     if (light_prims && (n_lights < 0 || n_lights > RTMI_DIRECT_MAX_LIGHTS)) return fail(RTMI_E_ARG, "n_lights must be in [0, %d] (got %d)", RTMI_DIRECT_MAX_LIGHTS, n_lights);
+    if (light_choice != 0 && light_choice != 1) return fail(RTMI_E_ARG, "light_choice must be 0 (uniform) or 1 (by power) (got %d)", light_choice); // (the MIS calls')
     if (n_groups == 0) return RTMI_OK;
     if (s->dev.n_media > 0) return fail(RTMI_E_UNSUPPORTED, "the scene holds a ConstantMedium: shadow rays through media are not built");
     *work = true;
@@ -6316,9 +6451,13 @@ int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *lig
 
 // the passes with the light-sampling kernel; no light to sample: the call is rtmi_render_rays and its two shadow-ray counters are zeros
 int nee_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
-            const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
+            const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st,
+            const MisLightTable *M = nullptr) { // M (then T is M->t): the MIS rule's kernels and table
     return with_real(precision, [&](auto r) {
         using R = decltype(r);
+        if (M && T.t.n > 0)
+            return render_rays_impl<R, MisPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
+                                                [&](NeeParams &np, hipStream_t q) { return upload_mis_lights(s->ctx, *M, np.lights, q); });
         if (T.t.n > 0)
             return render_rays_impl<R, NeePass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
                                                 [&](NeeParams &np, hipStream_t q) { return upload_nee_lights(s->ctx, T, np.lights, q); });
@@ -6326,26 +6465,30 @@ int nee_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, 
         return render_rays_impl<R, RaysPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st, NoLights{});
     });
 }
-} // namespace
 
-RTMI_EXPORT int rtmi_render_rays_nee_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const void *d_rays,
-                                            const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
-                                            void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream) {
-    NeeLightTable T;
+// The three entries of both families.  mis: the MIS rule with light_choice; else the NEE rule (light_choice is 0).
+int lit_rays_device(bool mis, rtmi_scene *s, int precision, int n_groups, int group, int g_first, const void *d_rays, const void *d_keys, u64 seed, unsigned ctr0,
+                    int depth, int n_lights, const int32_t *light_prims, int light_choice, void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays,
+                    void *d_out_counters, void *stream) {
+    MisLightTable M;
+    NeeLightTable &T = M.t;
     bool work = false;
-    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr, nullptr, &work, &T, n_lights, light_prims);
+    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr, nullptr, &work, &T, n_lights, light_prims, light_choice);
     if (rc || !work) return rc;
+    if (mis) make_mis_rows(M, light_choice);
     return nee_run(s, precision, n_groups, group, g_first, as<const double>(d_rays), as<const u64>(d_keys), seed, ctr0, depth, T, as<double>(d_state),
-                   as<double>(d_out_mean), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream));
+                   as<double>(d_out_mean), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream), mis ? &M : nullptr);
 }
 
-RTMI_EXPORT int rtmi_render_rays_nee(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const double *rays,
-                                     const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
-                                     double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters) {
-    NeeLightTable T;
+int lit_rays_host(bool mis, rtmi_scene *s, int precision, int n_groups, int group, int g_first, const double *rays, const uint64_t *keys, u64 seed, unsigned ctr0,
+                  int depth, int n_lights, const int32_t *light_prims, int light_choice, double *state, double *out_mean, double *out_stderr, double *out_rays,
+                  uint64_t *out_counters) {
+    MisLightTable M;
+    NeeLightTable &T = M.t;
     bool work = false;
-    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr, state, &work, &T, n_lights, light_prims);
+    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr, state, &work, &T, n_lights, light_prims, light_choice);
     if (rc || !work) return rc;
+    if (mis) make_mis_rows(M, light_choice);
     const size_t n = (size_t)n_groups * (size_t)group, ng = (size_t)n_groups;
     HostIo io(s->ctx);
     double *d_rays, *d_state, *d_mean, *d_se, *d_out;
@@ -6354,38 +6497,88 @@ RTMI_EXPORT int rtmi_render_rays_nee(rtmi_scene *s, int32_t precision, int32_t n
     io.plane(&d_state, ng * RTMI_RAYS_REC, state != nullptr, g_first > 0 ? state : nullptr, state); // a first chunk (g_first = 0) reads no records
     io.out(&d_mean, 3 * ng, out_mean); io.out(&d_se, ng, out_stderr); io.work(&d_cnt, 4, out_counters); io.out(&d_out, 3 * n, out_rays);
     return host_run(io, [&](hipStream_t st) {
-        return nee_run(s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, T, d_state, d_mean, d_se, d_out, d_cnt, st);
+        return nee_run(s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, T, d_state, d_mean, d_se, d_out, d_cnt, st, mis ? &M : nullptr);
     });
 }
 
-RTMI_EXPORT int rtmi_probe_paths_nee(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
-                                     int32_t n_lights, const int32_t *light_prims, double *out_rgb, uint64_t *out_nseg, int32_t *out_dropped, double *log,
-                                     int32_t max_seg, int32_t *out_nlog) {
+// out_dropped (the NEE probe: int32 flags) or out_weight (the MIS probe: doubles), whichever the family writes per path
+int lit_probe(bool mis, rtmi_scene *s, int precision, int n, const double *rays, const uint64_t *keys, u64 ctr0, int depth, int n_lights, const int32_t *light_prims,
+              int light_choice, double *out_rgb, uint64_t *out_nseg, int32_t *out_dropped, double *out_weight, double *log, int max_seg, int32_t *out_nlog) {
     int rc = probe_begin(s, precision, n);
     if (rc || n == 0) return rc;
     if (!rays || !keys || !out_rgb) return fail(RTMI_E_ARG, "NULL array");
     if (log && max_seg <= 0) return fail(RTMI_E_ARG, "log given but max_seg <= 0");
     if (precision == RTMI_F32 && s->dev.has_ext) return fail(RTMI_E_UNSUPPORTED, "rectangles / triangles / instances are FP64 only");
-    NeeLightTable T;
+    MisLightTable M;
+    NeeLightTable &T = M.t;
     bool work = false;
-    rc = check_nee_args(s, n, n_lights, light_prims, T, &work);
+    rc = check_nee_args(s, n, n_lights, light_prims, T, &work, light_choice);
     if (rc) return rc;
+    if (mis) make_mis_rows(M, light_choice);
     rtmi_ctx *c = s->ctx;
     HostIo io(c);
     NeeProbeParams pp{};
-    double *d_rays, *d_rgb, *d_log;
+    double *d_rays, *d_rgb, *d_log, *d_weight;
     u64 *d_keys, *d_nseg;
     int *d_dropped, *d_nlog;
-    const size_t log_words = log ? (size_t)n * max_seg * RTMI_NEE_REC : 0;
+    const size_t log_words = log ? (size_t)n * max_seg * (mis ? RTMI_MIS_REC : RTMI_NEE_REC) : 0;
     io.in(&d_rays, (size_t)n * 7, rays); io.in(&d_keys, (size_t)n, keys); io.out(&d_rgb, (size_t)n * 3, out_rgb);
-    io.out(&d_nseg, (size_t)n, out_nseg); io.out(&d_dropped, (size_t)n, out_dropped); io.out(&d_nlog, (size_t)n, out_nlog);
+    io.out(&d_nseg, (size_t)n, out_nseg); io.out(&d_dropped, (size_t)n, out_dropped); io.out(&d_weight, (size_t)n, out_weight); io.out(&d_nlog, (size_t)n, out_nlog);
     io.out(&d_log, log_words, log);
     pp.n = n; pp.ctr0 = (unsigned)ctr0; pp.depth = depth; pp.max_seg = max_seg;
     return probe_run(io, n, [&](hipStream_t st, dim3 grid) {
-        pp.rays = d_rays; pp.keys = d_keys; pp.out_rgb = d_rgb; pp.out_nseg = d_nseg; pp.out_dropped = d_dropped; pp.out_nlog = d_nlog; pp.log = d_log;
-        if (upload_nee_lights(c, T, pp.lights, st) != RTMI_OK) return; // (probe_run reports a launch error)
+        pp.rays = d_rays; pp.keys = d_keys; pp.out_rgb = d_rgb; pp.out_nseg = d_nseg; pp.out_nlog = d_nlog; pp.log = d_log;
+        pp.out_end = mis ? static_cast<void *>(d_weight) : static_cast<void *>(d_dropped);
+        if ((mis ? upload_mis_lights(c, M, pp.lights, st) : upload_nee_lights(c, T, pp.lights, st)) != RTMI_OK) return; // (probe_run reports a launch error)
         if (d_log && hipMemsetAsync(d_log, 0, log_words * sizeof(double), st) != hipSuccess) return;
         auto run = [&](auto kern, size_t lds, int, int) { hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, s->d_dev, pp); };
-        with_real(precision, [&](auto r) { with_probe_kernel<ProbePathsNee, decltype(r)>(s, run); });
+        with_real(precision, [&](auto r) {
+            if (mis) with_probe_kernel<ProbePathsMis, decltype(r)>(s, run);
+            else with_probe_kernel<ProbePathsNee, decltype(r)>(s, run);
+        });
     });
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_rays_nee_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const void *d_rays,
+                                            const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
+                                            void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream) {
+    return lit_rays_device(false, s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, n_lights, light_prims, 0, d_state, d_out_mean,
+                           d_out_stderr, d_out_rays, d_out_counters, stream);
+}
+
+RTMI_EXPORT int rtmi_render_rays_nee(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const double *rays,
+                                     const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
+                                     double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters) {
+    return lit_rays_host(false, s, precision, n_groups, group, g_first, rays, keys, seed, ctr0, depth, n_lights, light_prims, 0, state, out_mean, out_stderr,
+                         out_rays, out_counters);
+}
+
+RTMI_EXPORT int rtmi_probe_paths_nee(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
+                                     int32_t n_lights, const int32_t *light_prims, double *out_rgb, uint64_t *out_nseg, int32_t *out_dropped, double *log,
+                                     int32_t max_seg, int32_t *out_nlog) {
+    return lit_probe(false, s, precision, n, rays, keys, ctr0, depth, n_lights, light_prims, 0, out_rgb, out_nseg, out_dropped, nullptr, log, max_seg, out_nlog);
+}
+
+// ---- multiple importance sampling for the light-sampled paths (rtmi_render_rays_mis*, rtmi_probe_paths_mis): THE MIS RULE of rtmi.h ---------------------
+RTMI_EXPORT int rtmi_render_rays_mis_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const void *d_rays,
+                                            const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
+                                            int32_t light_choice, void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters,
+                                            void *stream) {
+    return lit_rays_device(true, s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, n_lights, light_prims, light_choice, d_state,
+                           d_out_mean, d_out_stderr, d_out_rays, d_out_counters, stream);
+}
+
+RTMI_EXPORT int rtmi_render_rays_mis(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const double *rays,
+                                     const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
+                                     int32_t light_choice, double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters) {
+    return lit_rays_host(true, s, precision, n_groups, group, g_first, rays, keys, seed, ctr0, depth, n_lights, light_prims, light_choice, state, out_mean,
+                         out_stderr, out_rays, out_counters);
+}
+
+RTMI_EXPORT int rtmi_probe_paths_mis(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
+                                     int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *out_rgb, uint64_t *out_nseg, double *out_weight,
+                                     double *log, int32_t max_seg, int32_t *out_nlog) {
+    return lit_probe(true, s, precision, n, rays, keys, ctr0, depth, n_lights, light_prims, light_choice, out_rgb, out_nseg, nullptr, out_weight, log, max_seg,
+                     out_nlog);
 }
