@@ -101,7 +101,12 @@ int rtmi_shutdown(rtmi_ctx *ctx);
  * parked lanes resume in the next trip; 0 = the plain loop; the image does not depend on it), "flat_below" (default 24: a scene of rectangles /
  * triangles / instances / media / f4 textures with fewer primitives than this renders through the flat scan even under RTMI_ACCEL_BVH -- same image, a
  * tree over so few primitives only costs; 0 = never; renders with "count_traversal" always walk the tree), "workspace_bytes" (sample-buffer budget, default 64 GiB, allocated as needed: a frame is rendered in as many sample passes as
- * it takes), "blocks_per_cu" (cap on resident trace workgroups per CU; the launch never exceeds what stays resident),
+ * it takes), "defer_emitters" (0/1, default 1; the image does not depend on it: in a scene of spheres whose only UVSphere light is a
+ * dome with a UVGradient that reads v alone -- the cover scene's sky --, a path that ends on that light is stored as {attenuation, normal y}
+ * and finished where the pixel's samples are summed, the same operations on the same operands (renders through the tree, "count_traversal"
+ * off; every other render is as with 0); a sample record then holds four reals, not three.  "workspace_bytes" still counts three per sample, so a call splits into the same passes either way, and the fourth is allocated on
+ * top of that budget -- within what the free-HBM clamp allows; 0: every render stores finished three-real samples; environment
+ * RTMI_DEFER_EMITTERS=0/1 overrides it), "blocks_per_cu" (cap on resident trace workgroups per CU; the launch never exceeds what stays resident),
  * "scan_variant" (flat scan: 0 LDS literal, 1 LDS pipelined, 2 scalar cache, 3 scalar cache + FP32 cull = default),
  * "lds_tile_bytes" (LDS variants), "timing" (0/1 = RTMI_FLAG_TIMING); test hooks: "test_fail_next_render" (the context's next render
  * fails before launching anything), "test_fail_allocs" (its next n sample-buffer allocations fail).
@@ -333,7 +338,7 @@ int32_t rtmi_local_tiles(int32_t nx, int32_t ny, int32_t tile_first, int32_t til
  * s_first == 0 starts a new frame (any previous one is discarded).  s_first > 0 must equal the k the context holds and the key must match,
  * else RTMI_E_STATE and rtmi_last_error names what differs.  The key: the scene's identity (a creation serial: a new scene allocated at a
  * destroyed scene's address does not match), its revision (every rtmi_scene_set_* call changes it), nx, ny, depth, seed, precision and region.
- * Options the image does not depend on ("accel", "suspend_lanes", "flat_below", "scan_variant", "workspace_bytes", "blocks_per_cu") may change
+ * Options the image does not depend on ("accel", "suspend_lanes", "flat_below", "scan_variant", "workspace_bytes", "blocks_per_cu", "defer_emitters") may change
  * between calls, and one-shot renders on the same context may come in between: the frame has buffers of its own.
  * A call that fails before it launches anything (argument checks, a mismatched key, the test_fail_next_render hook) leaves the frame as it
  * was; a call that fails after it launched anything drops it (k = 0): a later continuation is refused rather than allowed to produce a wrong
@@ -978,6 +983,8 @@ int rtmi_stream_idle(rtmi_ctx *ctx, int32_t *idle);
 /* Sample passes (trace-kernel launches) the context's most recent render took: the per-sample colour buffer is sized by option
  * "workspace_bytes", by the HBM that is free when it has to grow (at most 80 % of it) and, if the allocation still fails, by halving. */
 int rtmi_last_passes(rtmi_ctx *ctx, int32_t *passes);
+/* Reals per sample record of the context's most recent render that traced: 4 = it deferred (option "defer_emitters"), 3 = it did not; 0 before any. */
+int rtmi_last_record_reals(rtmi_ctx *ctx, int32_t *reals);
 /* RTMI_ACCEL_* the context's most recent render actually ran: option "accel" as set, except that a small mixed-kind scene (option
  * "flat_below") is scanned even when the tree was asked for.  RTMI_E_STATE before the first render. */
 int rtmi_last_accel(rtmi_ctx *ctx, int32_t *accel);

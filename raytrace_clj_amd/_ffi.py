@@ -25,7 +25,7 @@ SYMBOLS = [
     "rtmi_probe_paths", "rtmi_probe_camera", "rtmi_probe_texture", "rtmi_probe_scatter", "rtmi_probe_rng",
     "rtmi_sample_key", "rtmi_test_half_outward", "rtmi_test_camera_fixed", "rtmi_test_build_tree", "rtmi_probe_arith", "rtmi_probe_math", "rtmi_probe_math2", "rtmi_last_traversal_counters",
     "rtmi_scene_clone", "rtmi_render_multi", "rtmi_render_multi_device", "rtmi_last_gather_ms",
-    "rtmi_last_gather_path", "rtmi_rccl_probe", "rtmi_stream_idle", "rtmi_last_passes", "rtmi_last_accel",
+    "rtmi_last_gather_path", "rtmi_rccl_probe", "rtmi_stream_idle", "rtmi_last_passes", "rtmi_last_record_reals", "rtmi_last_accel",
     "rtmi_render_progressive", "rtmi_render_progressive_device", "rtmi_progressive_samples", "rtmi_progressive_release",
     "rtmi_render_adaptive", "rtmi_render_adaptive_device", "rtmi_adaptive_status", "rtmi_adaptive_active_tiles",
     "rtmi_render_features", "rtmi_render_features_device", "rtmi_denoise", "rtmi_denoise_device",
@@ -129,6 +129,7 @@ def lib():
     L.rtmi_rccl_probe.argtypes = [C.c_char_p]
     L.rtmi_stream_idle.argtypes = [vp, C.POINTER(i32)]
     L.rtmi_last_passes.argtypes = [vp, C.POINTER(i32)]
+    L.rtmi_last_record_reals.argtypes = [vp, C.POINTER(i32)]
     L.rtmi_last_accel.argtypes = [vp, C.POINTER(i32)]
     L.rtmi_render_progressive.argtypes = [vp, i32, i32, i32, i32, i32, u64, i32, i32, i32, i32, i32, vp, vp, vp, vp]
     L.rtmi_render_progressive_device.argtypes = [vp, i32, i32, i32, i32, i32, u64, i32, vp, vp, vp, vp, vp]

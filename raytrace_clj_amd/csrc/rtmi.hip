@@ -75,7 +75,7 @@ struct TraceParams {
     int n_local_tiles;
     const int *tile_ids;   // [n_local_tiles] global tile index (row-major over tiles)
     int s_begin, s_count;  // samples [s_begin, s_begin + s_count) of every pixel in this pass
-    void *samples;         // [n_local_tiles * s_count][64][3] real
+    void *samples;         // [n_local_tiles * s_count][64][3] real; [..][64][4] when the launch defers (defer_mat >= 0)
     u64 *counters;         // [0] += ray segments (metrics total-rays, core.clj:24)
     int prims_per_tile;    // static spheres per LDS tile
     int n_ptiles;          // number of LDS tiles the static spheres are cut into
@@ -89,6 +89,8 @@ struct TraceParams {
     int stash_off;         // mixed-kind kernels: word offset of the camera-ray stash in LDS (behind the stack and the parked cursors; 0 for the scan)
     double rnx, rny;       // RN(1 / nx), RN(1 / ny): the FP64 kernels divide the jittered pixel coordinates through div_const
     int fixed_rays;        // thin lens whose offset (+-0, +-0, +-0) changes no bit of a ray's origin or direction (camera_fixed_rays): the lens disk loop only counts its draws
+    int defer_mat;         // the launch defers (the kernel is a DEFER twin): paths ending on this material (DevScene::defer_mat) are stored as {atten, ny} and finished by
+                           // the fold; -1: every sample is finished here and stored as 3 reals
 };
 #ifndef RTMI_QUEUE_BLOCK
 #define RTMI_QUEUE_BLOCK 256
@@ -103,6 +105,39 @@ struct TraceParams {
 #define RTMI_STASH 1 // camera rays generated 64 at a time at full wave width into a register stash (0: per trip, for the dead lanes only)
 #endif
 constexpr unsigned kQueueBlock = RTMI_QUEUE_BLOCK; // work items a wave claims per queue access at least: 4 chunks = one tile x 4 consecutive samples
+
+// The sample record of a launch that defers: 4 reals per work item, 16-byte stores and loads (two in FP64, one in FP32); a (tile, sample) row is 64 records, contiguous
+__device__ inline void store_record4(void *samples, unsigned item, const double *rgb, double w) {
+    double2 *o = reinterpret_cast<double2 *>(samples) + (size_t)item * 2;
+    o[0] = make_double2(rgb[0], rgb[1]); o[1] = make_double2(rgb[2], w);
+}
+__device__ inline void store_record4(void *samples, unsigned item, const float *rgb, float w) {
+    reinterpret_cast<float4 *>(samples)[item] = make_float4(rgb[0], rgb[1], rgb[2], w);
+}
+__device__ inline void load_record4(const double *rec, double *rgb, double &w) {
+    const double2 a = reinterpret_cast<const double2 *>(rec)[0], b = reinterpret_cast<const double2 *>(rec)[1];
+    rgb[0] = a.x; rgb[1] = a.y; rgb[2] = b.x; w = b.y;
+}
+__device__ inline void load_record4(const float *rec, float *rgb, float &w) {
+    const float4 a = *reinterpret_cast<const float4 *>(rec);
+    rgb[0] = a.x; rgb[1] = a.y; rgb[2] = a.z; w = a.w;
+}
+// The folds of a deferring render (reduce_kernel, frame_fold_kernel: DEFER): lane l of a tile's wave owns PIXEL l, all three channels -- its record of sample s is
+// 64 (entry s_count + s) + l, a contiguous 2 KB (1 KB) per wave --, where the 3-real folds own elements l, l + 64, l + 128.  Only the thread-to-element mapping
+// differs: element e of a tile lies where it lay, and per element the additions run s = 0, 1, 2, ... as before.
+// One sample of the lane's pixel: the record, finished (finish_deferred) if the trace kernel left it to the fold.  A row without a deferred record -- a tile
+// that sees no sky -- skips that code with one wave-uniform branch.  `use`: the pixel lies inside the region (the records of the others were never written).
+template <typename R> __device__ inline void fold_record4(const R *rec, const GradientU<R> &q, bool use, R *v) {
+    R w;
+    load_record4(rec, v, w);
+    const bool deferred = use && !SampleTag<R>::is(w);
+    if (__any(deferred ? 1 : 0)) {
+        if (deferred) finish_deferred<R>(q, w, v[0], v[1], v[2]);
+    }
+}
+// element k of the lane (k = 0, 1, 2) within its tile's 192, and the pixel it belongs to
+template <bool DEFER> __device__ inline int fold_elem(int l, int k) { return DEFER ? 3 * l + k : l + 64 * k; }
+template <bool DEFER> __device__ inline int fold_pixel(int l, int k) { return DEFER ? l : (l + 64 * k) / 3; }
 
 template <typename R> __device__ inline const R *stat4_of(SceneRef sc);
 // Stage static spheres [first, first+count) into LDS as {cx, cy, cz, r*r} (hitable.clj:188: (* radius radius)).
@@ -341,7 +376,9 @@ template <typename R, bool KEEP> __device__ inline bool generate_camera_rays(Sce
 
 // SLICE: time-sliced BVH traversal (section 5.1b of DESIGN.md); the plain instantiation is kept for scenes whose tree is too small to gain
 // LST: the sphere (non-EXT) time-sliced BVH kernel with the camera-ray stash in LDS and stack columns sized by the scene's tree (launch site: when it fits)
-template <typename R, bool MULTI, int VARIANT, bool EXT = false, bool COUNT = false, bool SLICE = true, int MSEQ = 0, bool LST = false>
+// DEFER: the twin a launch that defers runs (TraceParams::defer_mat >= 0; the tree kernels of sphere-only scenes have one): paths that end on the scene's deferred
+// emitter are stored unfinished, 4 reals per record.  Every other instantiation is compiled without a trace of it
+template <typename R, bool MULTI, int VARIANT, bool EXT = false, bool COUNT = false, bool SLICE = true, int MSEQ = 0, bool LST = false, bool DEFER = false>
 // (the Hitlist-with-media (MSEQ) and the counting (COUNT) instantiations of the mixed-kind kernels need more than the 128 VGPRs of four waves per SIMD: rather
 // than spill, they are compiled for three -- rare worlds and a diagnostic; the kernels the benchmarks run keep four)
 __global__ void __launch_bounds__(kTraceBlock, EXT ? ((MSEQ != 0 || COUNT) ? 3 : RTMI_EXT_MIN_WAVES) : RTMI_MIN_WAVES) trace_kernel(ScenePtr scp, TraceParams tp) {
@@ -543,12 +580,23 @@ __global__ void __launch_bounds__(kTraceBlock, EXT ? ((MSEQ != 0 || COUNT) ? 3 :
         if (alive) {
             if (!mid) ++nrays;
             R emit[3];
-            const bool scat = shade_segment<R, EXT>(sc, P, best_t, best_i, nullptr, emit, mid); // a `mid` lane is a passenger: it changes nothing
-            if (!mid && !scat) {
-                R *out = reinterpret_cast<R *>(tp.samples) + (size_t)out_item * 3;
-                out[0] = emit[0]; out[1] = emit[1]; out[2] = emit[2];
-                alive = false;
-                RTMI_PH(PH_STORE)
+            if constexpr (!DEFER) { // (the call and the store exactly as they stood: these instantiations compile to the registers they had)
+                const bool scat = shade_segment<R, EXT>(sc, P, best_t, best_i, nullptr, emit, mid); // a `mid` lane is a passenger: it changes nothing
+                if (!mid && !scat) {
+                    R *out = reinterpret_cast<R *>(tp.samples) + (size_t)out_item * 3;
+                    out[0] = emit[0]; out[1] = emit[1]; out[2] = emit[2];
+                    alive = false;
+                    RTMI_PH(PH_STORE)
+                }
+            } else {
+                R dny;
+                bool deferred;
+                const bool scat = shade_segment<R, EXT, true>(sc, P, best_t, best_i, nullptr, emit, mid, tp.defer_mat, &deferred, &dny);
+                if (!mid && !scat) {
+                    store_record4(tp.samples, out_item, emit, deferred ? dny : SampleTag<R>::value()); // {r, g, b, SampleTag} or {ar, ag, ab, ny}
+                    alive = false;
+                    RTMI_PH(PH_STORE)
+                }
             }
         }
         }
@@ -567,11 +615,12 @@ __global__ void __launch_bounds__(kTraceBlock, EXT ? ((MSEQ != 0 || COUNT) ? 3 :
 }
 
 // core.clj:52-53: (reduce mat/add) over the samples IN ORDER, then (mul (/ 1.0 nr)) on the last pass.
-template <typename R>
+// DEFER: the samples are the 4-real records of a launch that defers and a lane owns a pixel (fold_record4); grad = mat_grad[defer_mat], the scene's record in HBM.
+template <typename R, bool DEFER = false>
 __global__ void __launch_bounds__(kBlock) reduce_kernel(const R *__restrict__ samples, R *__restrict__ accum, double *__restrict__ tiles_linear,
                                                         const int *__restrict__ tile_ids, int tiles_x, int nx, int ny, int n_local_tiles,
                                                         int s_begin, int s_count, int ns, u64 *counters, u64 n_valid_pixels,
-                                                        int rx0, int ry0, int rx1, int ry1) {
+                                                        int rx0, int ry0, int rx1, int ry1, const double *__restrict__ grad) {
     // A (tile, sample) row is 64 pixels x 3 channels = 192 consecutive values; the sum over the samples is element-wise, so lane l of the
     // tile's wave owns elements l, l + 64, l + 128 of the row (pixel j / 3, channel j % 3): every load of the wave is one contiguous
     // 64-element run (a thread per PIXEL read its 3 values at a 24-byte stride, three passes over the same cache lines).  Per element
@@ -587,20 +636,31 @@ __global__ void __launch_bounds__(kBlock) reduce_kernel(const R *__restrict__ sa
     const size_t tile_base = (size_t)tile_local * 192;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int p = (l + 64 * k) / 3; // pixel of the tile this element belongs to
+        const int p = fold_pixel<DEFER>(l, k); // pixel of the tile this element belongs to
         const int x = tx + (p & 7), y = ty + (p >> 3);
         valid[k] = x >= rx0 && x < rx1 && y >= ry0 && y < ry1;
-        acc[k] = (valid[k] && s_begin > 0) ? accum[tile_base + l + 64 * k] : R(0);
+        acc[k] = (valid[k] && s_begin > 0) ? accum[tile_base + fold_elem<DEFER>(l, k)] : R(0);
     }
+    if constexpr (DEFER) {
+        const GradientU<R> gu = gradient_rec_u<R>(grad, R(0.5)); // the lerps along u read the material only: once per thread
+        const R *rec = samples + ((size_t)tile_local * s_count * 64 + l) * 4;
+        for (int s = 0; s < s_count; ++s, rec += 256) {
+            R v[3];
+            fold_record4<R>(rec, gu, valid[0], v);
+            if (s_begin + s == 0) { acc[0] = v[0]; acc[1] = v[1]; acc[2] = v[2]; }
+            else { acc[0] = acc[0] + v[0]; acc[1] = acc[1] + v[1]; acc[2] = acc[2] + v[2]; }
+        }
+    } else {
     const R *row = samples + (size_t)tile_local * s_count * 192 + l;
     for (int s = 0; s < s_count; ++s, row += 192) {
         const R v0 = row[0], v1 = row[64], v2 = row[128];
         if (s_begin + s == 0) { acc[0] = v0; acc[1] = v1; acc[2] = v2; } // the fold starts FROM the first sample (not 0 + first)
         else { acc[0] = acc[0] + v0; acc[1] = acc[1] + v1; acc[2] = acc[2] + v2; }
     }
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const size_t o = tile_base + l + 64 * k;
+        const size_t o = tile_base + fold_elem<DEFER>(l, k);
         if (s_begin + s_count < ns) accum[o] = valid[k] ? acc[k] : R(0);
         else tiles_linear[o] = valid[k] ? (double)(acc[k] * (R(1.0) / (R)ns)) : 0.0;
     }
@@ -852,10 +912,12 @@ struct FoldRetire {
 // RETIRE = true (an adaptive call): `tiles` is the active list and the state sits at rt.act_slots[i] * 192, same element ownership, same arithmetic.
 // On the call's last pass (rt.last) the wave also decides: k = s_begin + s_count, the tile stays active (keep[i] = 1) if k < 2 or any element of a
 // valid pixel fails se <= eps, se = sqrt((M2 / (k - 1)) / k) as the resolve computes it, on the M2 in registers (a NaN fails); n_t[slot] = k.
-template <typename R, bool RETIRE>
+// DEFER: as reduce_kernel's -- 4-real records, a lane owns a pixel; the state's layout and every element's arithmetic are the same.
+template <typename R, bool RETIRE, bool DEFER = false>
 __global__ void __launch_bounds__(kBlock) frame_fold_kernel(const R *__restrict__ samples, R *__restrict__ sums, double *__restrict__ mean,
                                                             double *__restrict__ m2, const int *__restrict__ tiles, int tiles_x, int n_entries, int s_begin,
-                                                            int s_count, u64 *counters, u64 n_valid_pixels, int rx0, int ry0, int rx1, int ry1, FoldRetire rt) {
+                                                            int s_count, u64 *counters, u64 n_valid_pixels, int rx0, int ry0, int rx1, int ry1, FoldRetire rt,
+                                                            const double *__restrict__ grad) {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid == 0) counters[1] = n_valid_pixels; // metrics total-pixels, core.clj:47
     if (gid >= (long long)n_entries * 64) return; // (whole waves: kBlock is a multiple of 64)
@@ -870,18 +932,22 @@ __global__ void __launch_bounds__(kBlock) frame_fold_kernel(const R *__restrict_
     const size_t tile_base = (size_t)slot * 192;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int p = (l + 64 * k) / 3;
+        const int p = fold_pixel<DEFER>(l, k);
         const int x = tx + (p & 7), y = ty + (p >> 3);
         valid[k] = x >= rx0 && x < rx1 && y >= ry0 && y < ry1;
         const bool carry = valid[k] && s_begin > 0;
-        const size_t o = tile_base + l + 64 * k;
+        const size_t o = tile_base + fold_elem<DEFER>(l, k);
         acc[k] = carry ? sums[o] : R(0);
         mu[k] = carry ? mean[o] : 0.0;
         q[k] = carry ? m2[o] : 0.0;
     }
-    const R *row = samples + (size_t)entry * s_count * 192 + l;
-    for (int s = 0; s < s_count; ++s, row += 192) {
-        const R v[3] = {row[0], row[64], row[128]};
+    GradientU<R> gu = {};
+    if constexpr (DEFER) gu = gradient_rec_u<R>(grad, R(0.5)); // the lerps along u read the material only: once per thread
+    const R *row = DEFER ? samples + ((size_t)entry * s_count * 64 + l) * 4 : samples + (size_t)entry * s_count * 192 + l;
+    for (int s = 0; s < s_count; ++s, row += DEFER ? 256 : 192) {
+        R v[3];
+        if constexpr (DEFER) fold_record4<R>(row, gu, valid[0], v);
+        else { v[0] = row[0]; v[1] = row[64]; v[2] = row[128]; }
         if (s_begin + s == 0) { // the fold starts FROM the first sample (not 0 + first)
 #pragma unroll
             for (int k = 0; k < 3; ++k) { acc[k] = v[k]; mu[k] = (double)v[k]; q[k] = 0.0; }
@@ -898,7 +964,7 @@ __global__ void __launch_bounds__(kBlock) frame_fold_kernel(const R *__restrict_
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const size_t o = tile_base + l + 64 * k;
+        const size_t o = tile_base + fold_elem<DEFER>(l, k);
         sums[o] = valid[k] ? acc[k] : R(0);
         mean[o] = valid[k] ? mu[k] : 0.0;
         m2[o] = valid[k] ? q[k] : 0.0;
@@ -2211,10 +2277,12 @@ struct rtmi_ctx {
     hipEvent_t ev_consumed = nullptr;
     int ev_consumed_device = -1;
     bool consume_pending = false;
+    int defer_emitters = 1;    // option "defer_emitters": a scene's deferred emitter (DevScene::defer_mat) is finished by the fold; 0: every render stores 3-real samples
     int fail_next_render = 0;  // option "test_fail_next_render" (test hook): the next render on this context fails before it launches anything
     int fail_allocs = 0;       // option "test_fail_allocs" (test hook): the next n sample-buffer allocations fail as if HBM were exhausted
     int last_accel = -1;       // RTMI_ACCEL_* the most recent render ran (rtmi_last_accel): option "flat_below" can answer a request for the tree with the scan
     int last_passes = 0;       // sample passes of the most recent render (rtmi_last_passes)
+    int last_record_reals = 0; // reals per sample record of the most recent render that traced (rtmi_last_record_reals): 4 = it deferred, 3 = it did not
     int last_grid = 0; // workgroups of the last trace launch (diagnostics)
     std::map<std::pair<const void *, size_t>, int> occupancy; // resident workgroups per CU by (kernel, dynamic LDS bytes)
     std::vector<int> tile_ids_host;
@@ -2444,9 +2512,17 @@ int check_region(int nx, int ny, int x0, int y0, int x1, int y1) {
 
 // ---- which trace kernel a render launches --------------------------------------------------------------------------
 // The launch knobs, read once per render call (null: not set).  RTMI_FLAT_BELOW / RTMI_SUSPEND_LANES override the options of the same names;
-// RTMI_SPHERE_LDS_STASH=0 keeps the time-sliced sphere kernel's camera-ray stash in registers.
-struct LaunchKnobs { const char *flat_below, *suspend_lanes, *sphere_stash; };
-LaunchKnobs read_launch_knobs() { return {std::getenv("RTMI_FLAT_BELOW"), std::getenv("RTMI_SUSPEND_LANES"), std::getenv("RTMI_SPHERE_LDS_STASH")}; }
+// RTMI_SPHERE_LDS_STASH=0 keeps the time-sliced sphere kernel's camera-ray stash in registers; RTMI_DEFER_EMITTERS overrides option "defer_emitters" (A/B runs).
+struct LaunchKnobs { const char *flat_below, *suspend_lanes, *sphere_stash, *defer_emitters; };
+LaunchKnobs read_launch_knobs() {
+    return {std::getenv("RTMI_FLAT_BELOW"), std::getenv("RTMI_SUSPEND_LANES"), std::getenv("RTMI_SPHERE_LDS_STASH"), std::getenv("RTMI_DEFER_EMITTERS")};
+}
+// The material whose samples this render's fold finishes (TraceParams::defer_mat), -1: the render stores finished 3-real samples -- the scene has no
+// deferred emitter (a mixed-kind scene never has), or the option / the knob says no
+int launch_defer_mat(const rtmi_scene *s, const rtmi_ctx *c, const LaunchKnobs &k) {
+    const bool on = k.defer_emitters ? k.defer_emitters[0] != '0' : c->defer_emitters != 0;
+    return (on && !s->dev.has_ext) ? s->dev.defer_mat : -1;
+}
 
 // Dynamic LDS of a BVH kernel, per lane in words: `levels` stack columns, then `susp_words` of parked cursors (time-sliced instantiations), then
 // `stash_words` of camera-ray stash; susp_off / stash_off are where the last two begin (TraceParams)
@@ -2460,11 +2536,13 @@ struct TracePlan {
     LdsLayout lds{RTMI_BVH_STACK * RTMI_BVH_STRIDE, 0, 0}; // (the sphere kernels' stack has the compile-time RTMI_BVH_STACK levels: immediate ds_ offsets)
     int suspend_lanes = 0;
     int accel = RTMI_ACCEL_BVH; // what runs: the request for the tree may be answered with the flat scan (rtmi_last_accel)
+    bool defers = false;        // kern is a DEFER twin: the render stores 4-real records and its folds finish them
 };
 
 // The trace kernel of a render, its LDS layout and its time-slicing threshold.  multi / lds_bytes: the LDS tiling of the static spheres (lds_plan).
+// defer_mat >= 0: the render may defer (launch_defer_mat) -- it does where the kernel has a DEFER twin: the tree kernels, traversal counters aside.
 template <typename R>
-TracePlan choose_trace_kernel(const rtmi_scene *s, const rtmi_ctx *c, const LaunchKnobs &k, bool multi, size_t lds_bytes) {
+TracePlan choose_trace_kernel(const rtmi_scene *s, const rtmi_ctx *c, const LaunchKnobs &k, bool multi, size_t lds_bytes, int defer_mat) {
     const DevScene &d = s->dev;
     TracePlan p;
     int variant = c->accel == RTMI_ACCEL_BVH ? SCAN_BVH : c->scan_variant;
@@ -2506,7 +2584,13 @@ TracePlan choose_trace_kernel(const rtmi_scene *s, const rtmi_ctx *c, const Laun
         const LdsLayout stash = lds_layout(levels, RTMI_BVH_SUSPEND_WORDS, stash_words);
         if (slice) p.kern = count ? trace_kernel<R, false, SCAN_BVH, false, true> : trace_kernel<R, false, SCAN_BVH>;
         else p.kern = count ? trace_kernel<R, false, SCAN_BVH, false, true, false> : trace_kernel<R, false, SCAN_BVH, false, false, false>;
-        if (slice && !count && !(k.sphere_stash && k.sphere_stash[0] == '0') && stash.bytes <= 40 * 1024) { p.kern = trace_kernel<R, false, SCAN_BVH, false, false, true, false, true>; p.lds = stash; } // four workgroups per CU still fit
+        const bool lst = slice && !count && !(k.sphere_stash && k.sphere_stash[0] == '0') && stash.bytes <= 40 * 1024; // four workgroups per CU still fit
+        if (lst) { p.kern = trace_kernel<R, false, SCAN_BVH, false, false, true, false, true>; p.lds = stash; }
+        if (defer_mat >= 0 && !count) {
+            p.defers = true;
+            p.kern = lst ? trace_kernel<R, false, SCAN_BVH, false, false, true, 0, true, true>
+                         : slice ? trace_kernel<R, false, SCAN_BVH, false, false, true, 0, false, true> : trace_kernel<R, false, SCAN_BVH, false, false, false, 0, false, true>;
+        }
     } else if (variant == SCAN_SGPR_CULL) p.kern = trace_kernel<R, false, SCAN_SGPR_CULL>;
     else if (variant == SCAN_SGPR) p.kern = trace_kernel<R, false, SCAN_SGPR>;
     else {
@@ -2627,9 +2711,12 @@ int prepare_frame(rtmi_ctx *c, ProgFrame *prog, const AdaptiveCall *ad, int n_lo
 }
 
 // render_passes, step 2: how many of the call's ns samples of n_local tiles one pass takes, and a sample buffer that holds them.
-int size_sample_passes(rtmi_ctx *c, int n_local, int ns, size_t real_bytes, int *out_s_per_pass) {
-    const size_t per_sample = (size_t)n_local * 64 * 3 * real_bytes;
-    int s_per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(ns, c->workspace_bytes / (int64_t)per_sample));
+// record_reals: 3, or 4 for a render that defers.  The BUDGET counts 3 reals per item either way -- the split of a call into passes does not depend on
+// option "defer_emitters" --; the buffer, the free-HBM clamp and the halving retry take the record as it is, the fourth real on top of the budget.
+int size_sample_passes(rtmi_ctx *c, int n_local, int ns, size_t real_bytes, int record_reals, int *out_s_per_pass) {
+    const size_t budgeted = (size_t)n_local * 64 * 3 * real_bytes;
+    const size_t per_sample = (size_t)n_local * 64 * (size_t)record_reals * real_bytes;
+    int s_per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(ns, c->workspace_bytes / (int64_t)budgeted));
     // the work queue is indexed with 32 bits: items per pass (+ one claim per wave past the end) must stay below 2^32
     while (s_per_pass > 1 && (long long)n_local * s_per_pass * 64 >= 0xf0000000ll) s_per_pass /= 2;
     if ((long long)n_local * s_per_pass * 64 >= 0xf0000000ll) return fail(RTMI_E_ARG, "frame too large for one pass: %d tiles per rank", n_local);
@@ -2698,27 +2785,28 @@ int launch_trace_pass(rtmi_scene *s, const TracePlan &plan, TraceParams &tp, int
 // samples, the mean into d_tiles_linear; a progressive call: frame_fold_kernel into the frame; an adaptive one (ad): its retiring instantiation,
 // which decides on the pass that ends at s_end.  Timed (e1): the fold is the interval from the trace kernel's end event to one recorded here.
 template <typename R>
-int launch_fold(rtmi_ctx *c, const TraceParams &tp, int ns, int s_end, void *d_tiles_linear, bool count_pixels, ProgFrame *prog, const AdaptiveCall *ad,
-                hipEvent_t e1, hipStream_t st) {
+int launch_fold(rtmi_ctx *c, const TraceParams &tp, const double *defer_grad, int ns, int s_end, void *d_tiles_linear, bool count_pixels, ProgFrame *prog,
+                const AdaptiveCall *ad, hipEvent_t e1, hipStream_t st) {
     const long long npx = (long long)tp.n_local_tiles * 64;
     const dim3 grid((unsigned)((npx + kBlock - 1) / kBlock));
     const R *samples = reinterpret_cast<const R *>(c->samples.p);
+    const bool defer = tp.defer_mat >= 0; // the pass was traced into 4-real records: the DEFER twins
     if (ad) {
         FoldRetire rt;
         rt.act_slots = reinterpret_cast<const int *>(prog->act_slots[prog->cur].p);
         rt.last = tp.s_begin + tp.s_count == s_end ? 1 : 0; rt.eps = ad->eps;
         rt.keep = reinterpret_cast<int *>(prog->keep.p); rt.n_t = reinterpret_cast<int *>(prog->n_t.p);
-        hipLaunchKernelGGL((frame_fold_kernel<R, true>), grid, dim3(kBlock), 0, st, samples, reinterpret_cast<R *>(prog->sums.p),
+        hipLaunchKernelGGL((defer ? frame_fold_kernel<R, true, true> : frame_fold_kernel<R, true>), grid, dim3(kBlock), 0, st, samples, reinterpret_cast<R *>(prog->sums.p),
                            reinterpret_cast<double *>(prog->mean.p), reinterpret_cast<double *>(prog->m2.p), tp.tile_ids, tp.tiles_x, tp.n_local_tiles,
-                           tp.s_begin, tp.s_count, tp.counters, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1, rt);
+                           tp.s_begin, tp.s_count, tp.counters, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1, rt, defer_grad);
     } else if (prog)
-        hipLaunchKernelGGL((frame_fold_kernel<R, false>), grid, dim3(kBlock), 0, st, samples, reinterpret_cast<R *>(prog->sums.p),
+        hipLaunchKernelGGL((defer ? frame_fold_kernel<R, false, true> : frame_fold_kernel<R, false>), grid, dim3(kBlock), 0, st, samples, reinterpret_cast<R *>(prog->sums.p),
                            reinterpret_cast<double *>(prog->mean.p), reinterpret_cast<double *>(prog->m2.p), tp.tile_ids, tp.tiles_x, tp.n_local_tiles,
-                           tp.s_begin, tp.s_count, tp.counters, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1, FoldRetire{});
+                           tp.s_begin, tp.s_count, tp.counters, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1, FoldRetire{}, defer_grad);
     else
-        hipLaunchKernelGGL((reduce_kernel<R>), grid, dim3(kBlock), 0, st, samples, reinterpret_cast<R *>(c->accum.p),
+        hipLaunchKernelGGL((defer ? reduce_kernel<R, true> : reduce_kernel<R>), grid, dim3(kBlock), 0, st, samples, reinterpret_cast<R *>(c->accum.p),
                            reinterpret_cast<double *>(d_tiles_linear), tp.tile_ids, tp.tiles_x, tp.nx, tp.ny, tp.n_local_tiles, tp.s_begin, tp.s_count, ns,
-                           count_pixels ? tp.counters : nullptr, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1);
+                           count_pixels ? tp.counters : nullptr, (u64)c->tile_valid_pixels, tp.rx0, tp.ry0, tp.rx1, tp.ry1, defer_grad);
     HIP_TRY(hipGetLastError());
     return e1 ? close_timed_fold(c, st) : RTMI_OK;
 }
@@ -2755,18 +2843,21 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
 
     const int ns = s_end - s_first; // samples this call renders
     int s_per_pass = 0;
-    rc = size_sample_passes(c, n_local, ns, sizeof(R), &s_per_pass);
+    const LaunchKnobs knobs = read_launch_knobs();
+    int ppt, nptiles;
+    size_t lds_bytes;
+    lds_plan(c, s->dev.n_static, sizeof(R), &ppt, &nptiles, &lds_bytes);
+    const TracePlan plan = choose_trace_kernel<R>(s, c, knobs, nptiles > 1, lds_bytes, launch_defer_mat(s, c, knobs));
+    const int defer_mat = plan.defers ? s->dev.defer_mat : -1;
+    rc = size_sample_passes(c, n_local, ns, sizeof(R), defer_mat >= 0 ? 4 : 3, &s_per_pass);
     if (rc) return rc;
+    c->last_accel = plan.accel;
+    c->last_record_reals = defer_mat >= 0 ? 4 : 3;
     c->last_passes = (ns + s_per_pass - 1) / s_per_pass;
     if (!prog && s_per_pass < ns) {
         rc = c->accum.ensure((size_t)n_local * 64 * 3 * sizeof(R));
         if (rc) return rc;
     }
-    int ppt, nptiles;
-    size_t lds_bytes;
-    lds_plan(c, s->dev.n_static, sizeof(R), &ppt, &nptiles, &lds_bytes);
-    const TracePlan plan = choose_trace_kernel<R>(s, c, read_launch_knobs(), nptiles > 1, lds_bytes);
-    c->last_accel = plan.accel;
 
     TraceParams tp; // what every pass of the call shares; launch_trace_pass adds the pass
     tp.nx = nx; tp.ny = ny; tp.depth = depth; tp.seed = seed; tp.tiles_x = tiles_x_of(nx);
@@ -2780,10 +2871,12 @@ int render_passes(rtmi_scene *s, int nx, int ny, int s_first, int s_end, int dep
     tp.trav = reinterpret_cast<u64 *>(c->counters.p) + 3;
     tp.suspend_lanes = plan.suspend_lanes; tp.susp_off = plan.lds.susp_off; tp.stash_off = plan.lds.stash_off;
     tp.rnx = 1.0 / (double)nx; tp.rny = 1.0 / (double)ny; tp.fixed_rays = camera_fixed_rays(s->dev.cam_kind, s->dev.cam_fixed_origin, s->dev.cam);
+    tp.defer_mat = defer_mat;
+    const double *defer_grad = defer_mat >= 0 ? s->dev.mat_grad + (size_t)defer_mat * 12 : nullptr; // the DEFER folds' operand
     for (int s_begin = s_first; s_begin < s_end; s_begin += s_per_pass) {
         hipEvent_t e1 = nullptr;
         rc = launch_trace_pass(s, plan, tp, s_begin, std::min(s_per_pass, s_end - s_begin), st, &e1);
-        if (!rc) rc = launch_fold<R>(c, tp, ns, s_end, d_tiles_linear, d_counters != nullptr, prog, ad, e1, st);
+        if (!rc) rc = launch_fold<R>(c, tp, defer_grad, ns, s_end, d_tiles_linear, d_counters != nullptr, prog, ad, e1, st);
         if (rc) return rc;
     }
 #ifdef RTMI_STAMPS
@@ -3000,6 +3093,7 @@ RTMI_EXPORT int rtmi_set_option(rtmi_ctx *c, const char *name, int64_t value) {
     if (!std::strcmp(name, "timing")) { if (value) c->flags |= RTMI_FLAG_TIMING; else c->flags &= ~RTMI_FLAG_TIMING; return RTMI_OK; }
     if (!std::strcmp(name, "scan_variant")) { if (value < 0 || value > 3) return fail(RTMI_E_ARG, "scan_variant must be 0..3"); c->scan_variant = (int)value; return RTMI_OK; }
     if (!std::strcmp(name, "count_traversal")) { c->count_traversal = value ? 1 : 0; return RTMI_OK; }
+    if (!std::strcmp(name, "defer_emitters")) { if (value < 0 || value > 1) return fail(RTMI_E_ARG, "defer_emitters must be 0 or 1"); c->defer_emitters = (int)value; return RTMI_OK; }
     if (!std::strcmp(name, "test_fail_next_render")) { c->fail_next_render = value ? 1 : 0; return RTMI_OK; }
     if (!std::strcmp(name, "test_fail_allocs")) { c->fail_allocs = (int)std::max<int64_t>(0, std::min<int64_t>(value, 64)); return RTMI_OK; }
     if (!std::strcmp(name, "flat_below")) { if (value < 0 || value > (1 << 20)) return fail(RTMI_E_ARG, "flat_below must be 0..2^20"); c->flat_below = (int)value; return RTMI_OK; }
@@ -3496,7 +3590,7 @@ bool materials_fit(const rtmi_scene *s, const SceneArrays &a, const PackedMateri
 // the host's half of an edit: the mirror of the tables, the facts the render checks read, and the arguments a clone or a camera rebuild replays
 void adopt_materials(rtmi_scene *s, const SceneArrays &a, PackedMaterials *M) {
     rtmi_scene::Args &A = s->args;
-    if (M) { s->uses_perlin = M->uses_perlin; s->max_image = M->max_image; s->mat = std::move(*M); } // (a rebuild has done this itself)
+    if (M) { s->uses_perlin = M->uses_perlin; s->max_image = M->max_image; s->dev.defer_mat = M->defer_mat; s->mat = std::move(*M); } // (a rebuild has done this itself)
     if (a.prim_mat != A.prim_mat.data()) A.prim_mat.assign(a.prim_mat, a.prim_mat + a.n_prims);
     A.mat_kind.assign(a.mat_kind, a.mat_kind + a.n_mats); A.mat_tex.assign(a.mat_tex, a.mat_tex + a.n_mats); A.mat_param.assign(a.mat_param, a.mat_param + a.n_mats);
     A.tex_kind.assign(a.tex_kind, a.tex_kind + a.n_tex); A.tex_param.assign(a.tex_param, a.tex_param + (size_t)a.n_tex * RTMI_TEX_STRIDE);
@@ -3515,7 +3609,7 @@ int prepare_material_edit(rtmi_scene *s, int n_mats, const int32_t *mat_kind, co
     if (prim_mat) a.prim_mat = prim_mat;
     rc = check_material_edit(a);
     if (rc) return rc;
-    M = pack_materials(a);
+    M = pack_materials(a, s->geom_ext);
     return RTMI_OK;
 }
 } // namespace
@@ -3618,7 +3712,7 @@ RTMI_EXPORT int rtmi_test_pack_materials(int32_t n_prims, const int32_t *prim_ki
         if (!rc && (n_prims < 0 || (n_prims > 0 && (!prim_kind || !prim_mat)))) rc = fail(RTMI_E_ARG, "primitive arrays are NULL");
         if (!rc) rc = check_material_edit(a);
         if (rc) return rc;
-        M = pack_materials(a);
+        M = pack_materials(a, geometry_is_ext(a)); // (no built scene to ask: the hook reads the arrays)
     }
     uint64_t h = 1469598103934665603ull;
     DevScene none{};
@@ -5056,6 +5150,13 @@ RTMI_EXPORT int rtmi_stream_idle(rtmi_ctx *c, int32_t *idle) {
     const hipError_t e = hipStreamQuery(c->stream);
     if (e != hipSuccess && e != hipErrorNotReady) return fail(RTMI_E_DEVICE, "hipStreamQuery: %s", hipGetErrorString(e));
     if (idle) *idle = e == hipSuccess ? 1 : 0;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_last_record_reals(rtmi_ctx *c, int32_t *reals) {
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    if (!reals) return fail(RTMI_E_ARG, "reals is NULL");
+    *reals = c->last_record_reals;
     return RTMI_OK;
 }
 

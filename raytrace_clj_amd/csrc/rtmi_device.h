@@ -92,6 +92,7 @@ struct DevScene {
     const int *mat_tex;
     const double *mat_param;
     int n_tex;
+    int defer_mat;           // the scene's deferred emitter (pack_materials): the one DiffuseLight whose samples the fold may finish, -1: none.  The launches read the host's copy
     const int *tex_kind;
     const double *tex_param; // [n_tex][12]
     const int *tex_child;    // [n_tex][2]
@@ -2154,7 +2155,11 @@ struct __attribute__((aligned(16))) MatRec { int mat_kind, tex, tex_kind, pad; d
 #define RTMI_PRIM_NEEDS_U 32
 #define RTMI_PRIM_NEEDS_V 64
 #define RTMI_PRIM_NEEDS_UV (RTMI_PRIM_NEEDS_U | RTMI_PRIM_NEEDS_V)
-template <typename R> __device__ inline void resolve_hit(SceneRef sc, const Path<R> &P, R t, int orig, HitRec<R> &h, bool all_uv = true) {
+// prim_km only: a UVSphere of the scene's deferred emitter (DevScene::defer_mat).  Its texture reads v, so it carries RTMI_PRIM_NEEDS_V as well; a launch that
+// defers (`defer`: the DEFER twins of the trace kernel, a compile-time constant there) skips sphere_v for it and leaves the normal's y in h.v for the fold.  Every
+// other caller never looks at the bit: its code is what it was.
+#define RTMI_PRIM_DEFERRED 128
+template <typename R> __device__ inline void resolve_hit(SceneRef sc, const Path<R> &P, R t, int orig, HitRec<R> &h, bool all_uv = true, bool defer = false) {
     const double *g = sc.exact12 + (size_t)orig * 12;
     R cx = (R)g[0], cy = (R)g[1], cz = (R)g[2];
     h.orig = orig;
@@ -2178,9 +2183,10 @@ template <typename R> __device__ inline void resolve_hit(SceneRef sc, const Path
     if (h.kind == RTMI_PRIM_UVSPHERE && (all_uv || (kind_flags & RTMI_PRIM_NEEDS_UV))) {
         h.u = h.v = R(0.5);
         if (all_uv || (kind_flags & RTMI_PRIM_NEEDS_U)) h.u = Real<R>::sphere_u(nx, nz);
-        if (all_uv || (kind_flags & RTMI_PRIM_NEEDS_V)) h.v = Real<R>::sphere_v(ny);
+        if (all_uv || ((kind_flags & RTMI_PRIM_NEEDS_V) && !(defer && (kind_flags & RTMI_PRIM_DEFERRED)))) h.v = Real<R>::sphere_v(ny);
         RTMI_PH(PH_UV)
     }
+    if (defer && (kind_flags & RTMI_PRIM_DEFERRED)) h.v = ny; // the fold's operand travels in v, which nothing else reads on this material: no register of its own
 }
 
 // the hit record of an f3 primitive: the innermost record's {:t :p :uv :normal} in ITS frame, then every wrapper's
@@ -2292,14 +2298,53 @@ __device__ inline void resolve_hit_ext(SceneRef sc, const Path<double> &P, doubl
     }
     h.px = px; h.py = py; h.pz = pz; h.nx = nx; h.ny = ny; h.nz = nz;
 }
-template <typename R, bool EXT> __device__ inline void resolve_any(SceneRef sc, const Path<R> &P, R t, int orig, HitRec<R> &h, bool all_uv = true) { resolve_hit<R>(sc, P, t, orig, h, all_uv); }
-template <> __device__ inline void resolve_any<double, true>(SceneRef sc, const Path<double> &P, double t, int orig, HitRec<double> &h, bool all_uv) { resolve_hit_ext(sc, P, t, orig, h, all_uv); }
+template <typename R, bool EXT> __device__ inline void resolve_any(SceneRef sc, const Path<R> &P, R t, int orig, HitRec<R> &h, bool all_uv = true, bool defer = false) { resolve_hit<R>(sc, P, t, orig, h, all_uv, defer); }
+template <> __device__ inline void resolve_any<double, true>(SceneRef sc, const Path<double> &P, double t, int orig, HitRec<double> &h, bool all_uv, bool) { resolve_hit_ext(sc, P, t, orig, h, all_uv); }
+
+// The UVGradient of a material's second record (tex_kind RTMI_TEX_GRADIENT_REC), in the two steps of texture.clj:26-34: the six lerps along u, which read the
+// record and u only, then the three along v.  scatter_emit runs one after the other; the fold that finishes deferred samples runs the first once per thread.
+template <typename R> struct GradientU { R a0, a1, a2, b0, b1, b2; };
+template <typename R> __device__ inline GradientU<R> gradient_rec_u(const double *rec, R u) {
+    const double2 *gq = reinterpret_cast<const double2 *>(rec);
+    const double2 g0 = gq[0], g1 = gq[1], g2 = gq[2], g3 = gq[3], g4 = gq[4], g5 = gq[5]; // co.rg co.b|cu.r cu.gb cv.rg cv.b|cuv.r cuv.gb
+    const R omu = R(1.0) - u;
+    GradientU<R> q;
+    q.a0 = (R)g1.y * omu + (R)g0.x * u; q.a1 = (R)g2.x * omu + (R)g0.y * u; q.a2 = (R)g2.y * omu + (R)g1.x * u;
+    q.b0 = (R)g4.y * omu + (R)g3.x * u; q.b1 = (R)g5.x * omu + (R)g3.y * u; q.b2 = (R)g5.y * omu + (R)g4.x * u;
+    return q;
+}
+template <typename R> __device__ inline void gradient_rec_v(const GradientU<R> &q, R v, R &tr, R &tg, R &tb) {
+    const R omv = R(1.0) - v;
+    tr = q.b0 * omv + q.a0 * v; tg = q.b1 * omv + q.a1 * v; tb = q.b2 * omv + q.a2 * v;
+}
+
+// The fourth value of a sample record of a launch that defers (trace_kernel's store): a finished sample carries this quiet NaN -- one fixed bit pattern with a
+// payload no arithmetic produces, compared as an integer --, a deferred one the normal's y (whatever it holds: a NaN from a path that went NaN is not the tag).
+template <typename R> struct SampleTag;
+template <> struct SampleTag<double> {
+    __device__ static inline double value() { return __longlong_as_double(0x7ff8000052544d49ll); }
+    __device__ static inline bool is(double x) { return __double_as_longlong(x) == 0x7ff8000052544d49ll; }
+};
+template <> struct SampleTag<float> {
+    __device__ static inline float value() { return __uint_as_float(0x7fc0524du); }
+    __device__ static inline bool is(float x) { return __float_as_uint(x) == 0x7fc0524du; }
+};
+// What the fold does with a deferred record {ar, ag, ab, ny}: the last step of the path as scatter_emit runs it for every other launch -- v of the dome
+// (resolve_hit), the gradient at u = 1/2 (the coordinate the texture does not read), emitted added to an empty accum (core.clj:37-39).
+template <typename R> __device__ inline void finish_deferred(const GradientU<R> &q, R ny, R &r, R &g, R &b) {
+    R tr, tg, tb;
+    gradient_rec_v(q, Real<R>::sphere_v(ny), tr, tg, tb);
+    r = R(0) + r * tr; g = R(0) + g * tg; b = R(0) + b * tb;
+}
 
 // Shader.scatter + Shader.emitted for the hit record, and the atten/accum update of core.clj:27-39.
 // Returns true when the path continues (the `recur` of core.clj:30) with P holding the scattered ray.
 // `att` (optional) receives the attenuation of a successful scatter.  `emit` receives accum + atten * emitted of a path that
 // ends here (core.clj:37-39) with accum = (0 0 0): only a path's LAST segment can emit (the emitting Shader never scatters).
-template <typename R, bool F4 = false> __device__ inline bool scatter_emit(SceneRef sc, Path<R> &P, const HitRec<R> &h, R *att, R *emit, bool passenger = false) {
+// DEFER (the DEFER twins of the trace kernel only): a hit on material defer_mat skips the texture phase; emit receives the path's
+// attenuation and *out_deferred is set -- the fold finishes the sample (finish_deferred) from the normal's y, which resolve_hit left in h.v.
+template <typename R, bool F4 = false, bool DEFER = false>
+__device__ inline bool scatter_emit(SceneRef sc, Path<R> &P, const HitRec<R> &h, R *att, R *emit, bool passenger = false, int defer_mat = -1, bool *out_deferred = nullptr) {
     // The material switch is laid out in PHASES shared by the materials that need them (one rejection-sampler loop,
     // one |d| normalisation, one texture evaluation per trip) instead of one inlined copy per material: the lanes of a
     // wave hold different materials, so every copy would be executed serially.  Per lane the operations and the draw
@@ -2377,7 +2422,8 @@ template <typename R, bool F4 = false> __device__ inline bool scatter_emit(Scene
     }
     // phase 4 -- ONE texture evaluation: emitted of DiffuseLight (shader.clj:118-119) or the albedo of a successful
     // Lambertian / Metal scatter (shader.clj:34,57)
-    const bool want_tex = is_light || is_lamb || is_iso || (is_metal && scat);
+    const bool deferred = DEFER && is_light && mat == defer_mat; // (here, not with the other flags: a lane mask less across the phases above)
+    const bool want_tex = (is_light && !deferred) || is_lamb || is_iso || (is_metal && scat);
     double turb = 0.0, turb_p0 = 0.0; // F4: a material whose texture IS a Marble / PerlinTurbulence gets its turbulence from the wave (perlin_turbulence_wave)
     bool turb_done = false;
     if (F4 && sizeof(R) == sizeof(double)) { // (wave-uniform: every active lane passes here)
@@ -2407,16 +2453,15 @@ template <typename R, bool F4 = false> __device__ inline bool scatter_emit(Scene
             const bool neg = sx * sy * sz < 0;
             tr = neg ? (R)m1.y : (R)m3.y; tg = neg ? (R)m2.x : (R)m4.x; tb = neg ? (R)m2.y : (R)m4.y;
         } else if (mtk == RTMI_TEX_GRADIENT_REC) { // the operations of tex_sample's UVGradient case, operands from the material's second record
-            const double2 *gq = reinterpret_cast<const double2 *>(sc.mat_grad + (size_t)mat * 12);
-            const double2 g0 = gq[0], g1 = gq[1], g2 = gq[2], g3 = gq[3], g4 = gq[4], g5 = gq[5]; // co.rg co.b|cu.r cu.gb cv.rg cv.b|cuv.r cuv.gb
-            const R u = h.u, v = h.v, omu = R(1.0) - u, omv = R(1.0) - v;
-            const R a0 = (R)g1.y * omu + (R)g0.x * u, a1 = (R)g2.x * omu + (R)g0.y * u, a2 = (R)g2.y * omu + (R)g1.x * u;
-            const R b0 = (R)g4.y * omu + (R)g3.x * u, b1 = (R)g5.x * omu + (R)g3.y * u, b2 = (R)g5.y * omu + (R)g4.x * u;
-            tr = b0 * omv + a0 * v; tg = b1 * omv + a1 * v; tb = b2 * omv + a2 * v;
+            gradient_rec_v(gradient_rec_u<R>(sc.mat_grad + (size_t)mat * 12, h.u), h.v, tr, tg, tb);
         } else tex_sample<R, F4>(sc, mtex, h.u, h.v, px, py, pz, tr, tg, tb);
         if (is_light) { emit[0] = R(0) + P.ar * tr; emit[1] = R(0) + P.ag * tg; emit[2] = R(0) + P.ab * tb; } // core.clj:37-39: (add accum (mul atten emitted))
         else { atr = tr; atg = tg; atb = tb; }
         RTMI_PH(PH_TEXTURE)
+    }
+    if (DEFER) {
+        *out_deferred = deferred;
+        if (deferred) { emit[0] = P.ar; emit[1] = P.ag; emit[2] = P.ab; }
     }
     if (!scat) return false;
     if (att) { att[0] = atr; att[1] = atg; att[2] = atb; }
@@ -2428,19 +2473,23 @@ template <typename R, bool F4 = false> __device__ inline bool scatter_emit(Scene
 }
 
 // One iteration of `color`'s loop after hit? has returned (core.clj:25-41).
-template <typename R, bool EXT = false>
+template <typename R, bool EXT = false, bool DEFER = false>
 // passenger: a lane with no hit to shade in this trip (its segment is suspended in the tree, see trace_kernel).  It stays in the wave
 // through scatter_emit -- the cooperative rand-in-unit-sphere wants all 64 lanes -- with every material flag off: P is untouched.
-__device__ inline bool shade_segment(SceneRef sc, Path<R> &P, R t, int orig, SegLog *lg, R *emit, bool passenger = false) {
+// DEFER: scatter_emit's; the DEFER twins of the trace kernel set it and pass the launch's defer_mat.  *out_deferred: the sample is left to the fold, *out_ny its operand.
+__device__ inline bool shade_segment(SceneRef sc, Path<R> &P, R t, int orig, SegLog *lg, R *emit, bool passenger = false, int defer_mat = -1, bool *out_deferred = nullptr,
+                                     R *out_ny = nullptr) {
     emit[0] = emit[1] = emit[2] = R(0);
+    if (DEFER) { *out_deferred = false; *out_ny = R(0); }
     if (!passenger && orig < 0) return false; // miss: (color) returns accum, core.clj:40-41
     HitRec<R> h;
     h.px = h.py = h.pz = h.nx = h.ny = h.nz = h.u = h.v = h.t = R(0); h.mat = 0; h.orig = 0; h.kind = 0;
     if (!passenger) {
-        resolve_any<R, EXT>(sc, P, t, orig, h, false);
+        resolve_any<R, EXT>(sc, P, t, orig, h, false, DEFER);
         RTMI_PH(PH_HITREC)
     }
-    const bool scat = scatter_emit<R, EXT>(sc, P, h, nullptr, emit, passenger);
+    const bool scat = scatter_emit<R, EXT, DEFER>(sc, P, h, nullptr, emit, passenger, defer_mat, out_deferred);
+    if (DEFER) *out_ny = h.v;
     if (lg && lg->n < lg->max_seg) {
         double *q = lg->rec + (size_t)lg->n * RTMI_SEG_REC;
         q[0] = h.orig; q[1] = h.t; q[2] = h.px; q[3] = h.py; q[4] = h.pz; q[5] = h.nx; q[6] = h.ny; q[7] = h.nz;

@@ -669,6 +669,7 @@ struct PackedMaterials {
     bool has_ext = false; // the materials' share of DevScene::has_ext: a section 8(f4) texture, or a primitive whose material is Isotropic
     bool uses_perlin = false;
     int max_image = -1;
+    int defer_mat = -1; // DevScene::defer_mat: the scene's deferred emitter (pack_materials)
 };
 
 // What a scene uploads, as host tables (each named after its DevScene field), plus what rtmi_scene keeps on the host.
@@ -752,8 +753,19 @@ inline void camera_shutter(int cam_kind, const double *cam, double &t_lo, double
     t_hi = cam_kind == RTMI_CAM_THINLENS ? std::max(cam[22], cam[23]) : 0.0;
 }
 
+// PackedScene::geom_ext from the arrays alone, for the host-only test hook rtmi_test_pack_materials, which has no built scene to ask (creation and the live edits
+// pass the flag pack_geometry computed): a kind beyond the spheres, a medium's boundary, an instance wrapper, a flip.  prim_flip / prim_xform may be null (none)
+inline bool geometry_is_ext(const SceneArrays &a) {
+    for (int i = 0; i < a.n_prims; ++i) {
+        const int kind = a.prim_kind[i] & ~RTMI_PRIM_BOUNDARY;
+        if ((a.prim_kind[i] & RTMI_PRIM_BOUNDARY) || kind > RTMI_PRIM_MOVING || (a.prim_xform && a.prim_xform[2 * i + 1] != 0) || (a.prim_flip && a.prim_flip[i])) return true;
+    }
+    return false;
+}
+
 // The material half of pack_scene.  Of `a` it reads the primitive count, kinds and materials and the material and texture tables -- no geometry, no camera.
-PackedMaterials pack_materials(const SceneArrays &a) {
+// geom_ext: PackedScene::geom_ext of the scene these materials belong to (a mixed-kind scene has no deferred emitter).
+PackedMaterials pack_materials(const SceneArrays &a, bool geom_ext) {
     PackedMaterials M;
     const int n_prims = a.n_prims;
     for (int t = 0; t < a.n_tex; ++t) {
@@ -783,6 +795,31 @@ PackedMaterials pack_materials(const SceneArrays &a) {
     }
     M.prim_km.assign((size_t)std::max(n_prims, 1) * 2, 0);
     for (int i = 0; i < n_prims; ++i) { M.prim_km[2 * (size_t)i] = M.prim_kind[(size_t)i]; M.prim_km[2 * (size_t)i + 1] = M.prim_mat[(size_t)i]; }
+    // The deferred emitter of a sphere-only scene: the ONE material that is a DiffuseLight, whose texture is a UVGradient (evaluated from mat_grad) that reads v
+    // and not u, and that sits on UVSpheres only (on one at least).  A path that ends on it -- the cover scene's sky: nearly every path -- needs nothing of the hit
+    // but the normal's y, and nothing reads the result but the fold: a launch that defers stores {atten, ny} and the fold finishes the sample.  Its primitives carry
+    // RTMI_PRIM_DEFERRED beside RTMI_PRIM_NEEDS_V in prim_km (every kernel but the deferring twins still computes v for them; prim_kind, which the mixed-kind
+    // kernels read, keeps its bits).  Two candidates, or none: no deferred emitter, and not one byte of the tables differs from what they were.
+    if (!M.has_ext && !geom_ext) {
+        std::vector<char> on_uv((size_t)std::max(a.n_mats, 1), 0), on_other((size_t)std::max(a.n_mats, 1), 0);
+        for (int i = 0; i < n_prims; ++i) {
+            const int m = M.prim_mat[(size_t)i];
+            if (m < 0 || m >= a.n_mats) continue;
+            ((M.prim_kind[(size_t)i] & 15) == RTMI_PRIM_UVSPHERE ? on_uv : on_other)[(size_t)m] = 1;
+        }
+        int n_cand = 0, cand = -1;
+        for (int m = 0; m < a.n_mats; ++m) {
+            const int t = a.mat_tex[m];
+            if (a.mat_kind[m] != RTMI_MAT_DIFFUSE_LIGHT || t < 0 || t >= a.n_tex || a.tex_kind[t] != RTMI_TEX_UVGRADIENT || uses[(size_t)t] != 2) continue;
+            if (!on_uv[(size_t)m] || on_other[(size_t)m]) continue;
+            ++n_cand; cand = m;
+        }
+        if (n_cand == 1) {
+            M.defer_mat = cand;
+            for (int i = 0; i < n_prims; ++i)
+                if (M.prim_mat[(size_t)i] == cand) M.prim_km[2 * (size_t)i] |= RTMI_PRIM_DEFERRED;
+        }
+    }
     // MatRec (rtmi_device.h) of every material, and the four corner colours of those whose texture is a UVGradient
     M.mat_rec.assign((size_t)std::max(a.n_mats, 1) * 12, 0.0);
     M.mat_grad.assign((size_t)std::max(a.n_mats, 1) * 12, 0.0);
@@ -1034,7 +1071,6 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
     DevScene &d = P.d;
     std::memset(&d, 0, sizeof d); // (padding included: the descriptor is uploaded as bytes)
     const double *cam = a.cam;
-    P.M = pack_materials(a);
     d.n_tex = a.n_tex; d.cam_kind = a.cam_kind;
     std::memcpy(d.cam, cam, 24 * sizeof(double));
     d.cam_fixed_origin = camera_fixed_origin(a.cam_kind, cam);
@@ -1042,10 +1078,12 @@ PackedScene pack_scene(const SceneArrays &a, const BuildKnobs &K) {
     camera_shutter(a.cam_kind, cam, t_lo, t_hi);
     GeomExtras X;
     pack_geometry(a, K.box_leaf, t_lo, t_hi, P, X);
+    P.M = pack_materials(a, P.geom_ext); // (after the geometry: the deferred emitter wants a sphere-only scene)
     const int n_world = X.n_world;
     const bool has_ext = P.geom_ext || P.M.has_ext;
     build_trees(a, K, has_ext, X, P);
     d.has_ext = has_ext ? 1 : 0;
+    d.defer_mat = has_ext ? -1 : P.M.defer_mat; // (pack_materials saw the same geometry: -1 already where has_ext)
     d.small_scan = (has_ext && n_world <= RTMI_SMALL_SCAN_MAX && K.small_scan) ? 1 : 0;
     return P;
 }
