@@ -48,6 +48,10 @@ struct DevScene {
     int grid_walk;           // 1: a segment touching more cells is walked in pieces (RTMI_GRID_CHUNK); 0: it takes the whole tree, from its root (RTMI_GRID_WALK=0, or grid_kmax < 4)
     int grid_tall;           // root code of the tall primitives' tree (RTMI_BVH_EMPTY: none)
     float grid_lo_x, grid_lo_z, grid_inv_x, grid_inv_z; // cell index = floor((p - lo) * inv)
+    float grid_off_x, grid_off_z; // = -lo * inv, in float: the device takes the cell coordinate as ONE fma, p * inv + off
+    float grid_pad;          // (unused: the eight floats from here on are one 32-byte group -- with seven, one FP32 any-hit query kernel takes a VGPR more and loses a wave)
+    float grid_nf, grid_nnf, grid_gmax; // grid_n, its square and grid_n - 1 as floats: the device keeps cell numbers, and forms the index of grid_cells, in float
+    float grid_cs_x, grid_cs_z;   // the cell's size (the float next to 1 / inv): times a ray's 1 / d = its t per cell, for the end of a piece of the walk
     float grid_box[6];       // lo.xyz hi.xyz of the layer primitives' boxes (rounded outward like every node box): a ray's t range inside it
     float grid_tall_box[6];  // the same for the tall primitives: their tree is entered only by rays that meet this box
     float grid_eps;          // the cell rectangle of a segment is grown by this much (float position error, far below a cell)
@@ -128,7 +132,7 @@ __host__ __device__ inline u64 draw_bits(u64 key, u64 d) { return mix64(key + RT
 // cycles) and as lane-ticks = ticks x the lanes active AT the stamp.  A stamp therefore sits at the END of the code it names, inside
 // the divergent region if that code runs under a lane mask (a region no lane enters executes no stamp: its few scalar cycles fall to
 // the next stamp).  Accumulators live in LDS, one row per wave, updated by the wave's first active lane; flushed once per launch.
-enum { PH_LOOP = 0, PH_REFILL_GEN, PH_REFILL_DEAL, PH_BVH_SETUP, PH_BIG, PH_DESCENT, PH_LEAF, PH_BVH_POST, PH_HITREC, PH_DNORM, PH_SAMPLER, PH_DIRS, PH_TEXTURE, PH_STORE, PH_UV, PH_CAL, PH_GRID, PH_MEDIA, PH_GEN_KEY, PH_GEN_DISK, PH_GEN_CAM, PH_N }; // PH_CAL: back-to-back stamps = the cost of a stamp, subtracted per stamp on the host
+enum { PH_LOOP = 0, PH_REFILL_GEN, PH_REFILL_DEAL, PH_BVH_SETUP, PH_BIG, PH_DESCENT, PH_LEAF, PH_BVH_POST, PH_HITREC, PH_DNORM, PH_SAMPLER, PH_DIRS, PH_TEXTURE, PH_STORE, PH_UV, PH_CAL, PH_GRID, PH_MEDIA, PH_GEN_KEY, PH_GEN_DISK, PH_GEN_CAM, PH_GRID_BOX, PH_GRID_RECT, PH_GRID_PIECE, PH_N }; // PH_CAL: back-to-back stamps = the cost of a stamp, subtracted per stamp on the host
 #define PH_SLOTS 24
 __shared__ unsigned long long g_ph[4][3 * PH_SLOTS + 2]; // [wave]: ticks[PH_SLOTS], lane-ticks[PH_SLOTS], stamps[PH_SLOTS], last stamp, unused
 __device__ inline void ph_stamp(int k, unsigned lane_trips = 0, unsigned trips = 0) { // trips > 0: book lane_trips / trips lanes per tick instead of the stamp's own mask (loops that count their lanes per trip)
@@ -1340,17 +1344,44 @@ __device__ inline void bvh_traverse_fmt(SceneRef sc, const BvhRay &r, BvhCursor 
 // their inflated boxes.  A primitive two cells share is tested twice at worst (same t, same index: the any-order rule keeps one).
 // e_rel: rectangle growth relative to |o| + cbound -- RTMI_F32's float sphere test calls a hit up to 3.1e-3 (|o| + cbound) outside the sphere
 // (make_bvh_ray), so its rectangle grows by that much more.
-// Long segments (RTMI_GRID_CHUNK): a segment whose rectangle is larger is cut at t_split, the parameter up to which it stays within the 2 x 2 cells
-// around its start (1 .. 2 cells of travel along the tighter axis), and only [start, t_split] is entered now -- every primitive it can hit at a
+// Long segments (RTMI_GRID_CHUNK): a segment that leaves the 2 x 2 cells around its start is cut at t_split, the parameter up to which it stays within
+// them (1 .. 2 cells of travel along the tighter axis), and only [start, t_split] is entered now -- every primitive it can hit at a
 // t <= t_split overlaps those cells.  The caller traverses them, and if the closest hit so far is not at or before t_split it calls again with
 // t_from = t_split (first = false: the tall primitives' tree, entered with the first piece, is done): an ORDERED walk, nearest piece first, that
 // ends at the first piece holding the hit -- the mean free path of a ray inside the layer is about a cell --, where the descent from the root of
 // the whole tree spends a dozen node visits on locating the ray.  Returns t_split, +inf when this start covers all that remains of the segment.
+// ONE pass: the end of the first piece is computed for EVERY lane, without a branch, the segment is clipped to it -- te = ts if tn < ts < tf, else
+// tf -- and one rectangle is taken, from p(tn) and p(te).  (Until this form the rectangle of the whole segment came first and the lanes whose
+// rectangle was too large took a divergent arm -- piece end, second rectangle -- that 73 % of C3's trips entered with 14 lanes: DESIGN section 9.)
+//   * the bound per axis, in cells: the range may run to the far border of the two cells that hold its start and the start's margin, less 2^-8 of a
+//     cell for the rounding of this very computation and less the margin of the end point: floor(sx - ex) + (2 - 1/256) - ex along +x,
+//     floor(sx + ex) - (1 - 1/256) + ex along -x (floor clamped to the grid like every cell number).  The direction's sign is copied into the margin
+//     and into the constant -- (m + 0.5) +- (1.5 - 1/256), all three exact in float -- so both signs give the bits of the two-armed form;
+//   * the sign is d's own: cells per unit of t is d * inv with inv > 0, and a ray make_bvh_ray accepts has |d| >= 1e-12 dmax > 1e-27, so the product
+//     neither vanishes nor changes sign (a -0 product cannot arise);
+//   * t per cell is the ray's 1 / d (make_bvh_ray's v_rcp_f32) times the cell's size instead of a reciprocal of d * inv: (bound - sx) * (1 / d) * cell
+//     carries 2 + 1 + 1 half-ulps of relative error and 2 more for the cell size against its rounded inverse, the reciprocal form 1 + 2 + 1: the two
+//     differ by at most 10 x 2^-24 of a travel of at most two cells, 1.2e-6 of a cell -- 1/3000 of the 2^-8 allowance, which is there for the rounding
+//     of tn + dt and of p(ts) for origins thousands of cells away: it stays as it is;
+//   * what it cannot break: the rectangle is taken from the end points of what is entered, [tn, te], grown by the margin, as it always was, so every
+//     primitive hit at a t <= t_split overlaps the piece's cells whatever ts is -- a ts that is too long only makes the rectangle exceed 2 x 2 cells,
+//     and the lane takes the whole tree from its root (kNoSplit), as it does when ts is not inside (tn, tf) and the whole segment does not fit;
+//   * what it changes: a segment that fits un-split is now cut if its end lies beyond the bound, that is in the last 1/256 of the second cell before
+//     that cell's margin (a window of 2^-8 of a cell per axis in a span of up to two cells): the sliver [ts, tf] then becomes a piece of its own, entered
+//     only if the first holds no hit.  C3 counts 7.036 node visits per segment instead of 7.033 for it.
+// grid_walk = 0 (tests): the clip is gated off (ts is still computed: the block has no branch), the rectangle is the whole segment's, as before.
 __device__ inline float bvh_grid_entry(SceneRef sc, const BvhRay &r, float ox, float oy, float oz, float dx, float dy, float dz, float best_hi, float e_rel, BvhCursor &cur,
                                        float t_from = -__builtin_inff(), bool first = true) {
     const float kNoSplit = __builtin_inff();
     float t_split = kNoSplit;
-    const int G = sc.grid_n;
+    // the descriptor fields the block reads (scalar loads: the compiler places each group in the block of its first use and waits once per group)
+    const int tall_root = sc.grid_tall;
+    const bool walk = sc.grid_walk != 0;
+    const float gf = sc.grid_nf, gg = sc.grid_nnf, gmax = sc.grid_gmax;
+    const int kmax = sc.grid_kmax;
+    const float fam_max = kmax >= 4 ? 3.0f : kmax >= 2 ? 2.0f : 0.0f; // the largest rectangle family wi + 2 wj (0 .. 3: 1, 2, 2, 4 cells) that holds at most grid_kmax cells
+    const float ax = sc.grid_inv_x, az = sc.grid_inv_z, bx = sc.grid_off_x, bz = sc.grid_off_z, csx = sc.grid_cs_x, csz = sc.grid_cs_z, cbound = sc.bvh_cbound;
+    const int *const cells = sc.grid_cells;
     // The slab test of a node visit: per axis the {lo, hi} half pair is rotated by the ray's direction sign (entry plane first) and v_fma_mix_f32 gives
     // entry and exit distances with the ray's own conservative constants -- 3 + 6 instructions per box, where selecting float planes by sign took 18.
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -1363,51 +1394,57 @@ __device__ inline float bvh_grid_entry(SceneRef sc, const BvhRay &r, float ox, f
     float tn, tf;
     box_range(sc.grid_box_h[0], sc.grid_box_h[1], sc.grid_box_h[2], best_hi, tn, tf);
     tn = fmaxf(tn, t_from);
-    int tall = first ? sc.grid_tall : RTMI_BVH_EMPTY;
+    int tall = first ? tall_root : RTMI_BVH_EMPTY;
     if (tall != RTMI_BVH_EMPTY) { // (wave-uniform) the tall primitives' tree: only if the ray meets their box within its range
         float un, uf;
         box_range(sc.grid_tall_box_h[0], sc.grid_tall_box_h[1], sc.grid_tall_box_h[2], best_hi, un, uf);
         tall = un > uf ? RTMI_BVH_EMPTY : tall; // (a NaN keeps the tree)
     }
+    RTMI_PH(PH_GRID_BOX)
     constexpr int stride = RTMI_BVH_STRIDE;
     int node = RTMI_BVH_EMPTY, tos = cur.tos, *top = cur.top;
     if (tn <= tf) {
         const float omax = fmaxf(fmaxf(fabsf(ox), fabsf(oy)), fabsf(oz));
-        const float e = (omax + sc.bvh_cbound) * e_rel;
+        const float e = (omax + cbound) * e_rel;
         const float p0x = fmaf(tn, dx, ox), p0z = fmaf(tn, dz, oz);
-        float p1x = fmaf(tf, dx, ox), p1z = fmaf(tf, dz, oz);
-        const float gmax = (float)(G - 1);
         // cell coordinate = (p - lo) * inv as one fma (p * inv + (-lo * inv)); its rounding (a few 2^-24 of a coordinate <= grid_n) is far below
         // the margin e * inv, which is at least 2^-16 (|o| + cbound) * inv >= 2^-16 of the layer's extent in cells
-        const float ax = sc.grid_inv_x, az = sc.grid_inv_z, bx = -sc.grid_lo_x * ax, bz = -sc.grid_lo_z * az, ex = e * ax, ez = e * az;
+        const float ex = e * ax, ez = e * az;
         const float sx = fmaf(p0x, ax, bx), sz = fmaf(p0z, az, bz); // where the range starts, in cells
-        int i0, i1, j0, j1, wi, wj;
-        auto rect = [&]() { // the cells the rectangle of the range's two end points touches
-            const float qx = fmaf(p1x, ax, bx), qz = fmaf(p1z, az, bz);
-            const float fx0 = fminf(sx, qx) - ex, fx1 = fmaxf(sx, qx) + ex, fz0 = fminf(sz, qz) - ez, fz1 = fmaxf(sz, qz) + ez;
-            i0 = (int)__builtin_amdgcn_fmed3f(floorf(fx0), 0.0f, gmax); i1 = (int)__builtin_amdgcn_fmed3f(floorf(fx1), 0.0f, gmax); // (med3 of a NaN: the smaller bound)
-            j0 = (int)__builtin_amdgcn_fmed3f(floorf(fz0), 0.0f, gmax); j1 = (int)__builtin_amdgcn_fmed3f(floorf(fz1), 0.0f, gmax);
-            wi = i1 - i0; wj = j1 - j0;
-            return wi <= 1 && wj <= 1 && (wi + 1) * (wj + 1) <= sc.grid_kmax; // (a NaN: false)
-        };
-        if (!rect()) { // too many cells
+        float te = tf, ts = kNoSplit;
 #if RTMI_GRID_CHUNK
-            // the first piece: as far as the range stays inside the two cells per axis that hold its start (and the start's own margin), less 2^-8 of
-            // a cell for the rounding of this very computation -- the rectangle of the piece is then taken from its end points like any other
-            const float gx = dx * ax, gz = dz * az; // cells per unit of t
-            const float lx = gx >= 0.0f ? __builtin_amdgcn_fmed3f(floorf(sx - ex), 0.0f, gmax) + (2.0f - 1.0f / 256.0f) - ex : __builtin_amdgcn_fmed3f(floorf(sx + ex), 0.0f, gmax) - (1.0f - 1.0f / 256.0f) + ex;
-            const float lz = gz >= 0.0f ? __builtin_amdgcn_fmed3f(floorf(sz - ez), 0.0f, gmax) + (2.0f - 1.0f / 256.0f) - ez : __builtin_amdgcn_fmed3f(floorf(sz + ez), 0.0f, gmax) - (1.0f - 1.0f / 256.0f) + ez;
-            const float ts = tn + fminf((lx - sx) * __builtin_amdgcn_rcpf(gx), (lz - sz) * __builtin_amdgcn_rcpf(gz));
-            p1x = fmaf(ts, dx, ox); p1z = fmaf(ts, dz, oz);
-            if (!(ts > tn && ts < tf && sc.grid_walk && rect())) return kNoSplit; // (cannot happen for margins far below a cell; if it does: the whole tree, from its root)
-            t_split = ts;
-#else
-            return kNoSplit; // the whole tree, from its root
-#endif
+        { // the end of the piece, for every lane (see above); `walk` only gates the clip, so the block stays straight-line
+            // (the products run left to right: d's reciprocal times the cell size alone would be loop-invariant in the callers that loop over the pieces,
+            // and ride in two registers across their traversals)
+            const float mx = __builtin_copysignf(ex, dx), mz = __builtin_copysignf(ez, dz); // the margin, on the side the ray comes from
+            const float lx = __builtin_amdgcn_fmed3f(floorf(sx - mx), 0.0f, gmax) + 0.5f + __builtin_copysignf(1.5f - 1.0f / 256.0f, dx) - mx;
+            const float lz = __builtin_amdgcn_fmed3f(floorf(sz - mz), 0.0f, gmax) + 0.5f + __builtin_copysignf(1.5f - 1.0f / 256.0f, dz) - mz;
+            const float t1 = tn + fminf((lx - sx) * r.ixy.x * csx, (lz - sz) * r.izz.x * csz);
+            const bool clipped = walk & (t1 > tn) & (t1 < tf); // (a NaN: not clipped)
+            ts = clipped ? t1 : kNoSplit;
+            te = clipped ? t1 : tf;
+            RTMI_PH(PH_GRID_PIECE)
         }
+#else
+        (void)walk; (void)csx; (void)csz;
+#endif
+        const float p1x = fmaf(te, dx, ox), p1z = fmaf(te, dz, oz);
+        // the cells the rectangle of the range's two end points touches.  Cell numbers stay in float up to the index: they are integers below 2^8, the
+        // index is one below 2^18 -- exact in float, at full rate, where the integer form took four conversions and 32-bit multiply-adds at a quarter of it
+        const float qx = fmaf(p1x, ax, bx), qz = fmaf(p1z, az, bz);
+        const float fx0 = fminf(sx, qx) - ex, fx1 = fmaxf(sx, qx) + ex, fz0 = fminf(sz, qz) - ez, fz1 = fmaxf(sz, qz) + ez;
+        const float i0 = __builtin_amdgcn_fmed3f(floorf(fx0), 0.0f, gmax), i1 = __builtin_amdgcn_fmed3f(floorf(fx1), 0.0f, gmax); // (med3 of a NaN: the smaller bound)
+        const float j0 = __builtin_amdgcn_fmed3f(floorf(fz0), 0.0f, gmax), j1 = __builtin_amdgcn_fmed3f(floorf(fz1), 0.0f, gmax);
+        const float wi = i1 - i0, wj = j1 - j0, fam = fmaf(wj, 2.0f, wi);
+        // at most 2 x 2 cells and grid_kmax of them: (wi + 1)(wj + 1) is 1, 2, 2, 4 for the families 0 .. 3
+        const bool fits = (fmaxf(wi, wj) < 2.0f) & (fam <= fam_max);
+        RTMI_PH(PH_GRID_RECT)
+        if (!fits) return kNoSplit; // too many cells and no piece to cut (cannot happen to a piece for margins far below a cell; if it does: the same): the whole tree, from its root
+        t_split = ts;
         // ONE root: the host built a tree for every rectangle of cells (1 x 1, 2 x 1, 1 x 2, 2 x 2: family wi + 2 wj, indexed by the low corner) over the union
         // of the cells' primitives -- nothing to push, no root per cell to visit, and a primitive two of the cells share is tested once
-        node = sc.grid_cells[((wi + 2 * wj) * G + j0) * G + i0];
+        const unsigned cell = (unsigned)fmaf(fam, gg, fmaf(j0, gf, i0)); // (family * G + row) * G + column
+        node = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(cells) + (cell << 2)); // (a 32-bit byte offset: no 64-bit pointer sum)
     } else if (!(tn > tf)) return kNoSplit; // (a NaN cannot arise for a ray make_bvh_ray accepted; if it did: the whole tree)
     // else: the ray does not meet the layer's box within its range -- only the tall primitives remain
     if (tall != RTMI_BVH_EMPTY) { // (few lanes: the tall primitives' box is small) visited first

@@ -546,11 +546,13 @@ std::vector<float> build_bvh(DevScene &d, int n_prims, const int *prim_kind, con
             if (cell_items.empty() || B.max_depth >= RTMI_BVH_STACK - 1 || B.nodes.size() / 16 >= (1u << 25)) { // too deep for the stack: no grid (the whole tree above stays valid)
                 grid_cells.clear(); d.grid_tall = RTMI_BVH_EMPTY;
             } else {
-                d.grid_n = G;
+                d.grid_n = G; d.grid_nf = (float)G; d.grid_nnf = (float)(G * G); d.grid_gmax = (float)(G - 1);
                 d.grid_kmax = K.grid_kmax;
                 d.grid_walk = d.grid_kmax >= 4 && K.grid_walk; // (RTMI_GRID_WALK=0, tests: the same grid without the piecewise walk)
                 d.grid_lo_x = (float)lb.lo[0]; d.grid_lo_z = (float)lb.lo[2];
                 d.grid_inv_x = (float)(1.0 / csx); d.grid_inv_z = (float)(1.0 / csz);
+                d.grid_off_x = -d.grid_lo_x * d.grid_inv_x; d.grid_off_z = -d.grid_lo_z * d.grid_inv_z; // (float products: the bits the device used to compute per ray)
+                d.grid_cs_x = (float)csx; d.grid_cs_z = (float)csz;
                 for (int k = 0; k < 3; ++k) { d.grid_box[k] = f_down(lb.lo[k] - B.delta - eps); d.grid_box[3 + k] = f_up(lb.hi[k] + B.delta + eps); }
                 d.grid_eps = 0.0f;
                 BvhBox tb = box_empty();
