@@ -616,6 +616,40 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn render-lit
+  "A light-sampled nx x ny frame of scene {:camera :world} from its own camera, the camera rays built on the device (rtmi_render_lit): samples
+  [s-first, s-first + ns) of every pixel -- the keys, film jitter, lens draws and streams of `render` -- under `estimator` 0 (the plain path:
+  `render`'s frame bit for bit), 1 (the NEE rule) or 2 (the MIS rule, with `light-choice` 0 uniform / 1 by power).  `lights` as for render-rays-nee
+  (required; estimator 0 does not read them, an empty list is the plain path).  Returns {:linear double-array [ny * nx][3] (row 0 = top), :rgb8
+  byte-array, :stderr double-array [ny * nx], :rays double-array [nx * ny * ns][3] (sample s of pixel g at row (+ (* g ns) s)), :camera
+  double-array [nx * ny * ns][8] (origin, direction, time, the stream position behind the camera), :state double-array [nx * ny][10] (pass it back
+  as `state` with `s-first` = the samples every pixel holds to refine the frame), :segments, :total-rays, :shadow-rays, :shadow-rays-occluded}."
+  [scene nx ny ns lights & {:keys [estimator light-choice seed depth device precision s-first state]
+                            :or {estimator 2 light-choice 0 seed 0x5eed0002 depth 50 device 0 precision 0 s-first 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        npx  (* nx ny)
+        n    (* npx ns)
+        lp   (int-array (if (seq lights) lights [0]))
+        nl   (count lights)
+        st   (double-array (or state (* 10 npx)))
+        lin  (double-array (* 3 npx))
+        rgb8 (byte-array (* 3 npx))
+        err  (double-array npx)
+        out  (double-array (* 3 n))
+        cam  (double-array (* 8 n))
+        cnt  (long-array 4)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_lit" scn (int precision) (int nx) (int ny) (int s-first) (int ns) (int depth) (long seed) (int estimator)
+                           (int nl) lp (int light-choice) st lin rgb8 err out cam cnt))
+          {:linear lin :rgb8 rgb8 :stderr err :rays out :camera cam :state st :segments (aget cnt 0) :total-rays (aget cnt 1)
+           :shadow-rays (aget cnt 2) :shadow-rays-occluded (aget cnt 3)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn query-hits
   "The closest hit of every caller-supplied ray of scene {:camera :world} on GPU `device` (rtmi_query_hits): `rays` holds 7 doubles per ray
   (origin, direction, time), `n` of them; the scene's camera is not read.  Every ray takes (t-min, t-max), or its own pair of `t-range`

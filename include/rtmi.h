@@ -882,6 +882,48 @@ int rtmi_probe_paths_mis(rtmi_scene *scene, int32_t precision, int32_t n, const 
                          int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *out_rgb, uint64_t *out_nseg, double *out_weight,
                          double *log, int32_t max_seg, int32_t *out_nlog);
 
+/* ---- light-sampled frames from the scene's camera: the path calls above with their rays built on the device ----
+ * rtmi_render_rays / _nee / _mis over the frame rtmi_render traces: no ray and no key is uploaded, a lane builds its camera ray in registers.
+ *   n_groups = nx * ny, g_first = s_first, group = s_count; the state (may be NULL) is [nx*ny][RTMI_RAYS_REC], rtmi_render_rays' record and contract: any
+ *   split of the samples into consecutive chunks (s_first = the samples already folded) gives the bits of one call; without a state s_first only offsets
+ *   the keys and every call folds its own s_count samples.
+ * THE FRAME RULE, operation by operation in the call's precision R (core.clj:43-51 and 105, camera.clj:8-16 and 35-48: rtmi_render's start of a sample).
+ *   Row r of the call (0 <= r < nx*ny*s_count) belongs to group g = r / s_count and is sample s = s_first + (r - g * s_count).
+ *   1. The pixel: x = g % nx, y = g / nx, row 0 at the top: j = ny - 1 - y.
+ *   2. The stream: K = rtmi_sample_key(seed, j * nx + x, s), at draw 0.
+ *   3. u = ((R)(float)x + draw 0) / (R)nx, v = ((R)(float)j + draw 1) / (R)ny: uniforms of R, one IEEE addition and one IEEE division each.
+ *   4. The camera's get-ray with (u, v), from the camera the scene holds on the device, read in stream order (after rtmi_scene_set_camera / _stream: the
+ *      new view).  RTMI_CAM_PINHOLE draws nothing more and the time is 0.  RTMI_CAM_THINLENS runs the unit-disk rejection loop (two draws per round, until
+ *      x*x + y*y < 1; it runs with aperture 0 too) and then draws the time: the path starts at draw 2 + 2 * rounds + 1, a different one per sample.
+ *   5. The attenuation is (1, 1, 1), the depth is the call's, and the path goes on in the SAME stream behind the camera's last draw.
+ *   These are the operations of rtmi_render's samples: the path of row r is the path rtmi_render(nx, ny, ns > s, depth, seed, precision) traces for sample
+ *   s of pixel (x, y), segment by segment.
+ * estimator 0: the plain path of rtmi_render_rays (n_lights, light_prims and light_choice are not looked at); every scene rtmi_render_rays accepts, media
+ *   included.  out_linear, out_stderr and the segment counter are rtmi_render's and rtmi_render_progressive's for (nx, ny, s_first + s_count, depth, seed,
+ *   precision), bit for bit (with a state, or s_first = 0).
+ * estimator 1: THE NEE RULE on those paths (light_choice is not looked at).  estimator 2: THE MIS RULE with light_choice.  Both with K of step 2 as the
+ *   path's key; no light to sample: estimator 0 with the two shadow-ray counters zero.  They refuse a ConstantMedium and keep the rules' RTMI_F32 scope.
+ *   out_linear: [ny][nx][3] the fold's mean (rtmi_render_rays' out_mean); out_stderr: [ny][nx]; out_rgb8 (may be NULL): [ny][nx][3], the frame's
+ *   quantiser of out_linear, bit-equal to rtmi_denoise with zero passes; out_rays (may be NULL): [nx*ny*s_count][3], the radiance per row -- the call is
+ *   then one pass; out_camera (may be NULL): [nx*ny*s_count][8] doubles per row: origin, direction, time and the stream position behind step 4, each
+ *   widened from R; out_counters (may be NULL): FOUR values {segments, rays, shadow rays built, shadow rays occluded}.
+ * Errors, in this order: nx, ny or s_count <= 0, s_first or depth < 0: RTMI_E_ARG; nx * ny * s_count > 2^31 - 64: RTMI_E_ARG; s_first + s_count
+ * overflows int32: RTMI_E_ARG; out_linear or out_stderr NULL: RTMI_E_ARG; estimator outside 0..2: RTMI_E_ARG; then rtmi_render_rays' own from the scene
+ * handle on (RTMI_E_STATE, the precision, RTMI_F32 with mixed kinds, Perlin, images); for estimators 1 and 2 the NEE / MIS calls' behind them (n_lights,
+ * light_choice for estimator 2, the ConstantMedium, the list's entries); a host state whose counts are not s_first: RTMI_E_STATE.  A failed call
+ * launches nothing.  Option "workspace_bytes" may split the call into passes of whole pixels: no bit changes.  The call touches neither the context's
+ * progressive or adaptive frame nor the scene's revision; RTMI_FLAG_TIMING covers its passes as rtmi_render_rays'. */
+/* host buffers; synchronous */
+int rtmi_render_lit(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                    int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice,
+                    double *state, double *out_linear, uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera,
+                    uint64_t *out_counters);
+/* every d_ pointer a device pointer (light_prims stays a host array); asynchronous on `stream` with rtmi_render_device's stream semantics */
+int rtmi_render_lit_device(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                           int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice,
+                           void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera,
+                           void *d_out_counters, void *stream);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

@@ -44,6 +44,7 @@ SYMBOLS = [
     "rtmi_scene_lights", "rtmi_test_scene_lights", "rtmi_direct_irradiance", "rtmi_direct_irradiance_device", "rtmi_render_direct", "rtmi_render_direct_device",
     "rtmi_render_rays_nee", "rtmi_render_rays_nee_device", "rtmi_probe_paths_nee",
     "rtmi_render_rays_mis", "rtmi_render_rays_mis_device", "rtmi_probe_paths_mis",
+    "rtmi_render_lit", "rtmi_render_lit_device",
 ]
 
 F64, F32 = 0, 1
@@ -189,6 +190,8 @@ def lib():
     L.rtmi_render_rays_mis.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, i32, vp, i32, vp, vp, vp, vp, vp]
     L.rtmi_render_rays_mis_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]
     L.rtmi_probe_paths_mis.argtypes = [vp, i32, i32, vp, vp, u64, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]
+    L.rtmi_render_lit.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.rtmi_render_lit_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

@@ -745,6 +745,67 @@ class DeviceScene:
                                      precision=precision)
         return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_nee, 4, lights=lights, seed=paths, depth=depth, precision=precision)
 
+    # ---- light-sampled frames of the scene's own camera, the rays built on the device (THE FRAME RULE of include/rtmi.h) ----------------------
+    @staticmethod
+    def _lit_estimator(estimator):
+        """"plain" / "nee" / "mis" (or 0 / 1 / 2) -> the C entry's estimator; an unknown name is a ValueError, before any device work"""
+        if isinstance(estimator, str):
+            if estimator not in LIT_ESTIMATORS:
+                raise ValueError("estimator is one of %s (got %r)" % (", ".join(sorted(LIT_ESTIMATORS)), estimator))
+            return LIT_ESTIMATORS[estimator]
+        if isinstance(estimator, bool) or int(estimator) not in (0, 1, 2):
+            raise ValueError("estimator is 0 (plain), 1 (nee) or 2 (mis) (got %r)" % (estimator,))
+        return int(estimator)
+
+    def render_lit(self, nx, ny, ns, chunk=None, estimator="mis", lights=None, light_choice=0, depth=DEFAULT_DEPTH, seed=RENDER_SEED,
+                   precision="f64", return_rays=False, return_camera=False):
+        """An nx x ny x ns frame of the scene's own camera through rtmi_render_lit: the paths `render` traces -- the same keys, film jitter, lens
+        draws and streams, built on the device, no ray uploaded -- under the plain estimator ("plain": the frame of `render` bit for bit), the NEE
+        rule ("nee") or the MIS rule ("mis", with light_choice 0 / "uniform" or 1 / "power").  chunk: samples per call, folded through one state
+        (None: one call); the result does not depend on it.  -> (linear [ny, nx, 3], rgb8, stderr [ny, nx], counters {segments, rays, shadow rays
+        built, shadow rays occluded} summed over the calls[, rays' radiance [nx * ny, ns, 3]][, camera [nx * ny, ns, 8] = origin, direction,
+        time, the stream position behind the camera]); row 0 = top."""
+        est = self._lit_estimator(estimator)
+        nx, ny, ns = int(nx), int(ny), int(ns)
+        chunk = ns if chunk is None else int(chunk)
+        if nx <= 0 or ny <= 0 or ns <= 0 or chunk <= 0:
+            raise ValueError("nx, ny, ns and chunk must be > 0")
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        choice = self._light_choice(light_choice)
+        npx = nx * ny
+        lin, q, err = np.zeros((ny, nx, 3), np.float64), np.zeros((ny, nx, 3), np.uint8), np.zeros((ny, nx), np.float64)
+        state = np.zeros((npx, _ffi.RAYS_REC), np.float64) if chunk < ns else None
+        total = np.zeros(4, np.uint64)
+        rays = np.zeros((npx, ns, 3), np.float64) if return_rays else None
+        cam = np.zeros((npx, ns, 8), np.float64) if return_camera else None
+        k = 0
+        while k < ns:
+            n = min(chunk, ns - k)
+            cnt = np.zeros(4, np.uint64)
+            r = np.zeros((npx, n, 3), np.float64) if return_rays else None
+            c = np.zeros((npx, n, 8), np.float64) if return_camera else None
+            check(_ffi.lib().rtmi_render_lit(self.handle, _PRECISION[precision], nx, ny, k, n, int(depth), int(seed), est, n_listed, ptr(lights), choice,
+                                             ptr(state), ptr(lin), ptr(q), ptr(err), ptr(r), ptr(c), ptr(cnt)))
+            total += cnt
+            if return_rays:
+                rays[:, k:k + n] = r
+            if return_camera:
+                cam[:, k:k + n] = c
+            k += n
+        return (lin, q, err, total) + ((rays,) if return_rays else ()) + ((cam,) if return_camera else ())
+
+    def render_lit_device(self, nx, ny, s_first, s_count, out_linear, out_stderr, out_rgb8=None, estimator="mis", lights=None, light_choice=0,
+                          depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", state=None, out_rays=None, out_camera=None, out_counters=None,
+                          stream=None):
+        """rtmi_render_lit_device: samples [s_first, s_first + s_count) of every pixel on HBM-resident buffers (torch tensors or raw device pointers;
+        lights stays a host list; out_counters: four uint64); asynchronous, render_device's stream semantics.  state ([nx * ny, RAYS_REC] doubles,
+        the caller's): the frame refined over calls; its count is the caller's contract and is not read back."""
+        est = self._lit_estimator(estimator)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        check(_ffi.lib().rtmi_render_lit_device(self.handle, _PRECISION[precision], int(nx), int(ny), int(s_first), int(s_count), int(depth), int(seed), est,
+                                                n_listed, ptr(lights), self._light_choice(light_choice), ptr(state), ptr(out_linear), ptr(out_rgb8),
+                                                ptr(out_stderr), ptr(out_rays), ptr(out_camera), ptr(out_counters), ptr(stream)))
+
     # ---- closest-hit and any-hit queries: picking, first hits, shadow / ambient-occlusion / line-of-sight rays --------------------------------
     @staticmethod
     def _query_inputs(rays, t_range, keys):
@@ -1680,6 +1741,45 @@ def _mis_name(name):
     return root + ".mis" + ext
 
 
+LIT_ESTIMATORS = {"plain": 0, "nee": 1, "mis": 2}  # estimator of rtmi_render_lit
+
+
+def _lit_flags(argv, panorama=False, orbit=False, nee=False, mis=False):
+    """-> (the other arguments, None or (estimator, light choice) of --lit [plain|nee|mis[:uniform|:power]], default mis); the modes it does not
+    combine with are refused here, before any device work"""
+    rest, lit, k = [], None, 0
+    while k < len(argv):
+        a = argv[k]
+        if a == "--lit":
+            if lit is not None:
+                raise SystemExit("--lit given twice")
+            lit = ("mis", "uniform")
+            if k + 1 < len(argv):
+                est, _, choice = argv[k + 1].partition(":")
+                if est in LIT_ESTIMATORS:
+                    if choice and (est != "mis" or choice not in MIS_CHOICES):
+                        raise SystemExit("--lit takes plain, nee, mis, mis:uniform or mis:power (got %r)" % argv[k + 1])
+                    lit = (est, choice or "uniform")
+                    k += 1
+        elif a.startswith("--lit"):
+            raise SystemExit("--lit takes plain, nee or mis[:power] as a separate word (got %r)" % a)
+        else:
+            rest.append(a)
+        k += 1
+    if lit is not None and (panorama or orbit):
+        raise SystemExit("--lit does not combine with --orbit or --panorama")
+    if lit is not None and (nee or mis):
+        raise SystemExit("--lit does not combine with --nee or --mis: it is their frame through the scene's own streams")
+    return rest, lit
+
+
+def _lit_name(name):
+    """x.png -> x.lit.png: the frame of rtmi_render_lit is written next to the frame"""
+    import os
+    root, ext = os.path.splitext(name)
+    return root + ".lit" + ext
+
+
 def _direct_name(name):
     """x.png -> x.direct.png: the directly lit view is written next to the frame"""
     import os
@@ -1755,7 +1855,10 @@ def main(argv=None):
     name.nee.ext, beside the frame.  It does not combine with --orbit or --panorama, and a scene that holds a ConstantMedium is refused.
     --mis [uniform|power] also writes the frame of those paths under multiple importance sampling (DeviceScene.render_nee(mis=True): the light sample
     and the scatter share each lamp's emission by the balance heuristic; the light is picked uniformly, the default, or by power) as name.mis.ext.
-    It is refused where --nee is."""
+    It is refused where --nee is.
+    --lit [plain|nee|mis[:power]] also writes the frame of DeviceScene.render_lit (default mis): the samples the frame itself traces -- the same keys, jitter,
+    lens draws and streams, the camera rays built on the device -- under the plain estimator, the NEE rule or the MIS rule, as name.lit.ext.  With --chunk
+    K it is refined K samples at a time through one state (the same image).  It does not combine with --orbit, --panorama, --nee or --mis."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
     argv, direct = _direct_flags(argv)
@@ -1773,6 +1876,7 @@ def main(argv=None):
         raise SystemExit("--direct does not combine with --orbit or --panorama")
     argv, nee = _nee_flags(argv, panorama, orbit_views is not None)
     argv, mis = _mis_flags(argv, panorama, orbit_views is not None)
+    argv, lit_mode = _lit_flags(argv, panorama, orbit_views is not None, nee, mis is not None)
     argv, accumulate = _accumulate_flags(argv, orbit_views)
     argv, adaptive_denoised = _adaptive_denoised_flags(argv)
     if adaptive_denoised is not None and not any(a.split("=", 1)[0] == "--denoise" for a in argv):
@@ -1794,6 +1898,8 @@ def main(argv=None):
     sc = SCENES[which](scenes, nx, ny)
     if (nee or mis is not None) and (fl.flatten(sc).prim_kind & 15 == fl.PRIM_MEDIUM).any():
         raise SystemExit("%s: scene %r holds a ConstantMedium, which the light-sampled paths do not trace" % ("--nee" if nee else "--mis", which))
+    if lit_mode is not None and lit_mode[0] != "plain" and (fl.flatten(sc).prim_kind & 15 == fl.PRIM_MEDIUM).any():
+        raise SystemExit("--lit %s: scene %r holds a ConstantMedium, which the light-sampled paths do not trace" % (lit_mode[0], which))
     if accumulate is not None:
         return _render_orbit_accumulated(sc, name, nx, ny, nr, orbit_views, dn_iterations, dn_samples, accumulate, tstart)
     if orbit_views is not None:
@@ -1905,6 +2011,13 @@ def main(argv=None):
         finally:
             ds.close()
         _save_image(_mis_name(name), lit)
+    if lit_mode is not None:
+        ds = DeviceScene(sc)
+        try:
+            frame = ds.render_lit(nx, ny, nr, chunk=chunk, estimator=lit_mode[0], light_choice=lit_mode[1])[1]
+        finally:
+            ds.close()
+        _save_image(_lit_name(name), frame)
     return 0
 
 

@@ -1258,10 +1258,53 @@ struct RaysParams {
     unsigned qblock;      // items a wave claims per queue access
     unsigned *queue;      // zeroed before the launch
     u64 *counters;        // [0] += segments
+    // the frame of a generated source (SRC_CAMERA; never read by the memory source): group g is pixel (g % nx, g / nx), row 0 at the top
+    int nx, ny;
+    int fixed_rays;       // TraceParams::fixed_rays (read by the wave-wide lens sampler only: RTMI_LIT_WAVE_LENS)
+    double *out_camera;   // [total_items][8], or null: origin, direction, time, stream position behind the camera
 };
 
-template <typename R, int VARIANT, bool EXT = false, int MSEQ = 0>
+// Where a lane's ray comes from (the query kernels' sources are described at query_kernel).  SRC_CAMERA, the path kernels' (rtmi_render_lit*): row
+// row0 + m is sample g_first + r of pixel g, and the lane builds start_sample's ray in R from the camera the scene holds on the device.
+enum { SRC_MEMORY = 0, SRC_HEMISPHERE = 1, SRC_TARGETS = 2, SRC_PIXEL = 3, SRC_LIGHT = 4, SRC_CAMERA = 5 };
+
+#ifndef RTMI_LIT_WAVE_LENS
+#define RTMI_LIT_WAVE_LENS 0 // 1: the refill samples the lens with get_ray_wave, the whole wave helping (A/B; DESIGN.md section 7q: the same bits)
+#endif
+// The refill of a SRC_CAMERA lane, THE FRAME RULE of rtmi.h: start_sample's operations, so the path goes on in the stream where rtmi_render's does.
+// `has`: the lane takes item m; every lane of the wave calls (the refill loop is wave-uniform), the others leave P as it is.
+template <typename R> __device__ inline void camera_refill(SceneRef sc, const RaysParams &rp, bool has, unsigned m, Path<R> &P) {
+    const unsigned row = rp.row0 + m, g = row / rp.group, y = g / (unsigned)rp.nx;
+    const int x = (int)(g - y * (unsigned)rp.nx), j = rp.ny - 1 - (int)y, s = (int)(rp.g_first + (row - g * rp.group)); // j = ny-1-y (core.clj:105)
+    const u64 key = sample_key(rp.seed, (u64)j * (u64)rp.nx + (u64)x, (u64)s);
+#if RTMI_LIT_WAVE_LENS
+    Path<R> Q;
+    seed_stream(Q, key, 0u);
+    const R u = ((R)(float)x + next_uniform(Q)) / (R)rp.nx;
+    const R v = ((R)(float)j + next_uniform(Q)) / (R)rp.ny;
+    get_ray_wave<R>(sc, rp.fixed_rays != 0, has, u, v, Q);
+    if (has) { P.ox = Q.ox; P.oy = Q.oy; P.oz = Q.oz; P.dx = Q.dx; P.dy = Q.dy; P.dz = Q.dz; P.time = Q.time; P.key = Q.key; P.rs = Q.rs; P.ctr = Q.ctr; }
+#else
+    if (has) {
+        seed_stream(P, key, 0u);
+        const R u = ((R)(float)x + next_uniform(P)) / (R)rp.nx;
+        const R v = ((R)(float)j + next_uniform(P)) / (R)rp.ny;
+        get_ray<R>(sc, u, v, P);
+    }
+#endif
+    if (has) { P.ar = P.ag = P.ab = R(1); P.depth = rp.depth; }
+    if (rp.out_camera) { // wave-uniform
+        if (has) {
+            double *o = rp.out_camera + (size_t)m * 8;
+            o[0] = (double)P.ox; o[1] = (double)P.oy; o[2] = (double)P.oz; o[3] = (double)P.dx; o[4] = (double)P.dy; o[5] = (double)P.dz;
+            o[6] = (double)P.time; o[7] = (double)P.ctr;
+        }
+    }
+}
+
+template <typename R, int VARIANT, bool EXT = false, int MSEQ = 0, int SRC = SRC_MEMORY>
 __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WAVES) : RTMI_MIN_WAVES) rays_kernel(ScenePtr scp, RaysParams rp) {
+    static_assert(SRC == SRC_MEMORY || SRC == SRC_CAMERA, "the path kernels read their rays or build the frame's");
     static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the refill loop is per wave");
     SceneRef sc = *scp;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1292,7 +1335,12 @@ __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WA
             }
             const unsigned avail = w_end - w_cur;
             const unsigned rank = (unsigned)__popcll(dead & ((1ull << lane) - 1ull));
-            if (!alive && rank < avail) {
+            if constexpr (SRC == SRC_CAMERA) {
+                const bool has = !alive && rank < avail;
+                const unsigned m = w_cur + (has ? rank : 0u); // < total_items
+                camera_refill<R>(sc, rp, has, m, P);
+                if (has) { out_item = m; alive = true; }
+            } else if (!alive && rank < avail) {
                 const unsigned m = w_cur + rank; // < total_items
                 load_ray<R>(rp.rays + (size_t)m * 7, P);
                 u64 key;
@@ -1377,6 +1425,12 @@ __global__ void __launch_bounds__(kBlock) rays_fold_kernel(const double *__restr
     se[g] = err;
 }
 
+// rtmi_render_lit*'s 8-bit frame: the frame's quantiser on the fold's means, n = 3 * pixels values
+__global__ void __launch_bounds__(kBlock) lit_quantise_kernel(const double *__restrict__ mean, size_t n, unsigned char *__restrict__ out_rgb8) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out_rgb8[i] = quantise8(mean[i]);
+}
+
 // ---- closest-hit and any-hit queries on caller-supplied rays (rtmi_query_hits*, rtmi_query_occluded*) ------------------------------------------------
 // A work item is one ray = one hit? of the world (probe_hit_kernel's trip), so every lane is free again after every trip: persistent waves over one queue with
 // rays_kernel's claim -- qblock (a multiple of 64) consecutive items per atomic --, of which the wave takes 64 consecutive rays per trip, lane order = row order.
@@ -1423,7 +1477,7 @@ constexpr int kLightRec = 10;
 // so that numpy restates them bit for bit; the seven doubles then go through load_ray as if they had been read.
 // SRC_LIGHT: towards a sampled point of an area light, by the light rule of rtmi.h (rtmi_direct_irradiance); the lane writes the sample's
 // contribution before the search and zeroes it behind the search if the ray is occluded.
-enum { SRC_MEMORY = 0, SRC_HEMISPHERE = 1, SRC_TARGETS = 2, SRC_PIXEL = 3, SRC_LIGHT = 4 };
+// (the enum stands above RaysParams: the path kernels' SRC_CAMERA is one of its values)
 
 // pixel m of an nx x ny view, row-major from the top, through its centre from the camera the scene holds on the device (DeviceScene.pixel_centre_rays)
 __device__ inline void pixel_centre_ray(SceneRef sc, unsigned m, unsigned nx, unsigned ny, double *q) {
@@ -1814,8 +1868,9 @@ struct NeeParams {
 #define RTMI_NEE_MIN_WAVES 3
 #endif
 // MIS (rtmi_render_rays_mis*): THE MIS RULE of rtmi.h -- the same path and the same shadow rays, the balance heuristic on both ends.
-template <typename R, int VARIANT, bool EXT = false, bool MIS = false>
+template <typename R, int VARIANT, bool EXT = false, bool MIS = false, int SRC = SRC_MEMORY>
 __global__ void __launch_bounds__(kBlock, RTMI_NEE_MIN_WAVES) rays_nee_kernel(ScenePtr scp, NeeParams np) {
+    static_assert(SRC == SRC_MEMORY || SRC == SRC_CAMERA, "the path kernels read their rays or build the frame's");
     static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the refill loop is per wave");
     SceneRef sc = *scp;
     __shared__ double nee_lds[(MIS ? kMisSlots : kNeeSlots) * kBlock];
@@ -1850,7 +1905,17 @@ __global__ void __launch_bounds__(kBlock, RTMI_NEE_MIN_WAVES) rays_nee_kernel(Sc
             }
             const unsigned avail = w_end - w_cur;
             const unsigned rank = (unsigned)__popcll(dead & ((1ull << lane) - 1ull));
-            if (!alive && rank < avail) {
+            if constexpr (SRC == SRC_CAMERA) {
+                const bool has = !alive && rank < avail;
+                const unsigned m = w_cur + (has ? rank : 0u); // < total_items
+                camera_refill<R>(sc, rp, has, m, P);
+                if (has) {
+                    out_item = m;
+                    alive = true;
+                    sampled = false; seg = 0;
+                    slot[0] = 0.0; slot[kBlock] = 0.0; slot[2 * kBlock] = 0.0; // accum starts at +0.0
+                }
+            } else if (!alive && rank < avail) {
                 const unsigned m = w_cur + rank; // < total_items
                 load_ray<R>(rp.rays + (size_t)m * 7, P);
                 u64 key;
@@ -5696,6 +5761,12 @@ struct RaysPass {
     static constexpr int n_counters = 2;
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MSEQ>; }
 };
+// rtmi_render_lit*, estimator 0: the same kernel building the frame's camera rays (SRC_CAMERA)
+struct LitRaysPass : RaysPass {
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MSEQ, SRC_CAMERA>; }
+};
+// The frame of a call whose rays the kernel builds (null for the calls that read theirs): what RaysParams holds of it.  out_camera is the call's.
+struct RaysFrame { int nx, ny, fixed_rays; double *out_camera; };
 
 constexpr long long kRaysMax = (1ll << 31) - 64; // rays per call: 32-bit work items, and a claim past the end must not wrap the queue head
 
@@ -5706,7 +5777,8 @@ constexpr long long kRaysMax = (1ll << 31) - 64; // rays per call: 32-bit work i
 struct NoLights { int operator()(RaysParams &, hipStream_t) const { return RTMI_OK; } };
 template <typename R, typename Family, typename Lights>
 int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
-                     double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st, Lights upload_lights) {
+                     double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st, Lights upload_lights,
+                     const RaysFrame *frame = nullptr) { // frame: the family's kernels are the SRC_CAMERA ones, d_rays and d_keys are null
     rtmi_ctx *c = s->ctx;
     int rc = c->counters.ensure(8 * sizeof(u64));
     if (rc) return rc;
@@ -5727,13 +5799,15 @@ int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const 
     rp.group = (unsigned)group; rp.g_first = (unsigned)g_first;
     rp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + Family::n_counters);
     rp.counters = d_cnt;
+    rp.nx = frame ? frame->nx : 0; rp.ny = frame ? frame->ny : 0; rp.fixed_rays = frame ? frame->fixed_rays : 0; rp.out_camera = nullptr;
     const u64 n_rays = (u64)n_groups * (u64)group;
     with_probe_kernel<Family, R>(s, [&](auto kern, size_t lds, int, int) {
         for (int g0 = 0; g0 < n_groups && !rc; g0 += per_pass) {
             const int ng = std::min(per_pass, n_groups - g0);
             const size_t row0 = (size_t)g0 * (size_t)group;
-            rp.rays = d_rays + row0 * 7;
+            rp.rays = d_rays ? d_rays + row0 * 7 : nullptr;
             rp.keys = d_keys ? d_keys + row0 : nullptr;
+            if (frame && frame->out_camera) rp.out_camera = frame->out_camera + row0 * 8;
             rp.samples = d_out_rays ? d_out_rays + row0 * 3 : reinterpret_cast<double *>(c->rays_ws.p);
             rp.row0 = (unsigned)row0;
             rc = queue_launch(c, st, reinterpret_cast<const void *>(kern), lds, rp.queue, (long long)ng * group,
@@ -5757,13 +5831,13 @@ struct NeeLightTable;
 int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work, int light_choice = 0);
 int rays_begin(rtmi_scene *s, int precision, int n_groups, int group, int g_first, int depth, const void *rays, const void *mean, const void *se,
                const double *host_state, bool *work, NeeLightTable *T = nullptr, int n_lights = 0, const int32_t *light_prims = nullptr,
-               int light_choice = 0) {
+               int light_choice = 0, bool generated = false) { // generated: the kernel builds the rays (rtmi_render_lit*), `rays` is not looked at
     *work = false;
     if (n_groups < 0 || group <= 0 || g_first < 0 || depth < 0)
         return fail(RTMI_E_ARG, "n_groups, g_first, depth must be >= 0 and group > 0 (got %d %d %d %d)", n_groups, g_first, depth, group);
     if ((long long)n_groups * group > kRaysMax) return fail(RTMI_E_ARG, "n_groups * group = %lld rays exceed 2^31 - 64", (long long)n_groups * group);
     if ((long long)g_first + group > INT32_MAX) return fail(RTMI_E_ARG, "g_first + group = %d + %d overflows int32", g_first, group);
-    if (n_groups > 0 && !rays) return fail(RTMI_E_ARG, "rays is NULL");
+    if (n_groups > 0 && !rays && !generated) return fail(RTMI_E_ARG, "rays is NULL");
     if (n_groups > 0 && (!mean || !se)) return fail(RTMI_E_ARG, "out_mean / out_stderr is NULL");
     if (!scene_ok(s)) return fail(RTMI_E_STATE, "invalid scene handle");
     if (precision != RTMI_F64 && precision != RTMI_F32) return fail(RTMI_E_ARG, "precision must be RTMI_F64 or RTMI_F32");
@@ -6444,6 +6518,9 @@ struct NeePass {
     // a media scene is refused before any launch, so the media-sequence operands of the chooser all name the one kernel
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT>; }
 };
+struct LitNeePass : NeePass { // rtmi_render_lit*, estimator 1: the frame's camera rays (SRC_CAMERA)
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, false, SRC_CAMERA>; }
+};
 struct ProbePathsNee {
     static constexpr bool wave_level = true;
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT>; }
@@ -6451,6 +6528,9 @@ struct ProbePathsNee {
 // the MIS rule's instantiations of the two kernels (rtmi_render_rays_mis*, rtmi_probe_paths_mis)
 struct MisPass : NeePass {
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, true>; }
+};
+struct LitMisPass : NeePass { // rtmi_render_lit*, estimator 2
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, true, SRC_CAMERA>; }
 };
 struct ProbePathsMis {
     static constexpr bool wave_level = true;
@@ -6553,17 +6633,27 @@ int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *lig
 // the passes with the light-sampling kernel; no light to sample: the call is rtmi_render_rays and its two shadow-ray counters are zeros
 int nee_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
             const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st,
-            const MisLightTable *M = nullptr) { // M (then T is M->t): the MIS rule's kernels and table
+            const MisLightTable *M = nullptr, // M (then T is M->t): the MIS rule's kernels and table
+            const RaysFrame *frame = nullptr) { // frame: the SRC_CAMERA twins of the three families (rtmi_render_lit*)
     return with_real(precision, [&](auto r) {
         using R = decltype(r);
+        auto mis_lights = [&](NeeParams &np, hipStream_t q) { return upload_mis_lights(s->ctx, *M, np.lights, q); };
+        auto nee_lights = [&](NeeParams &np, hipStream_t q) { return upload_nee_lights(s->ctx, T, np.lights, q); };
         if (M && T.t.n > 0)
-            return render_rays_impl<R, MisPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
-                                                [&](NeeParams &np, hipStream_t q) { return upload_mis_lights(s->ctx, *M, np.lights, q); });
+            return frame ? render_rays_impl<R, LitMisPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt,
+                                                           st, mis_lights, frame)
+                         : render_rays_impl<R, MisPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
+                                                        mis_lights);
         if (T.t.n > 0)
-            return render_rays_impl<R, NeePass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
-                                                [&](NeeParams &np, hipStream_t q) { return upload_nee_lights(s->ctx, T, np.lights, q); });
+            return frame ? render_rays_impl<R, LitNeePass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt,
+                                                           st, nee_lights, frame)
+                         : render_rays_impl<R, NeePass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
+                                                        nee_lights);
         if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt + 2, 0, 2 * sizeof(u64), st));
-        return render_rays_impl<R, RaysPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st, NoLights{});
+        return frame ? render_rays_impl<R, LitRaysPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
+                                                        NoLights{}, frame)
+                     : render_rays_impl<R, RaysPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
+                                                     NoLights{});
     });
 }
 
@@ -6682,4 +6772,78 @@ RTMI_EXPORT int rtmi_probe_paths_mis(rtmi_scene *s, int32_t precision, int32_t n
                                      double *log, int32_t max_seg, int32_t *out_nlog) {
     return lit_probe(true, s, precision, n, rays, keys, ctr0, depth, n_lights, light_prims, light_choice, out_rgb, out_nseg, nullptr, out_weight, log, max_seg,
                      out_nlog);
+}
+
+// ---- light-sampled frames from the scene's camera (rtmi_render_lit*): THE FRAME RULE of rtmi.h -----------------------------------------------------------
+// rtmi_render_rays* / _nee* / _mis* with n_groups = nx * ny, g_first = s_first, group = s_count and the SRC_CAMERA twins of their kernels: no ray is
+// read, a refilled lane builds start_sample's.  Everything behind the checks is nee_run's.
+namespace {
+// what both forms check first, in the header's order; *M: estimators 1 and 2's light table (estimator 0: no light); *work false: nothing to do
+int lit_frame_begin(rtmi_scene *s, int precision, int nx, int ny, int s_first, int s_count, int depth, int estimator, int n_lights, const int32_t *light_prims,
+                    int light_choice, const double *host_state, const void *out_linear, const void *out_stderr, MisLightTable &M, RaysFrame &F, bool *work) {
+    *work = false;
+    if (nx <= 0 || ny <= 0 || s_count <= 0 || s_first < 0 || depth < 0)
+        return fail(RTMI_E_ARG, "nx, ny, s_count must be > 0 and s_first, depth >= 0 (got %d %d %d %d %d)", nx, ny, s_count, s_first, depth);
+    if ((long long)nx * ny > kRaysMax || (long long)nx * ny * s_count > kRaysMax)
+        return fail(RTMI_E_ARG, "nx * ny * s_count = %d * %d * %d rays exceed 2^31 - 64", nx, ny, s_count);
+    if ((long long)s_first + s_count > INT32_MAX) return fail(RTMI_E_ARG, "s_first + s_count = %d + %d overflows int32", s_first, s_count);
+    if (!out_linear || !out_stderr) return fail(RTMI_E_ARG, "out_linear / out_stderr is NULL");
+    if (estimator < 0 || estimator > 2) return fail(RTMI_E_ARG, "estimator must be 0 (plain), 1 (the NEE rule) or 2 (the MIS rule) (got %d)", estimator);
+    M.t.t.n = 0;
+    const int rc = rays_begin(s, precision, nx * ny, s_count, s_first, depth, nullptr, out_linear, out_stderr, host_state, work, estimator ? &M.t : nullptr,
+                              n_lights, light_prims, estimator == 2 ? light_choice : 0, true);
+    if (rc || !*work) return rc;
+    if (estimator == 2) make_mis_rows(M, light_choice);
+    F.nx = nx; F.ny = ny; F.fixed_rays = camera_fixed_rays(s->dev.cam_kind, s->dev.cam_fixed_origin, s->dev.cam);
+    return RTMI_OK;
+}
+
+int lit_frame_run(rtmi_scene *s, int precision, int nx, int ny, int s_first, int s_count, int depth, u64 seed, int estimator, const MisLightTable &M,
+                  const RaysFrame &F, double *d_state, double *d_lin, unsigned char *d_q, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
+    const int rc = nee_run(s, precision, nx * ny, s_count, s_first, nullptr, nullptr, seed, 0u, depth, M.t, d_state, d_lin, d_se, d_out_rays, d_cnt, st,
+                           estimator == 2 ? &M : nullptr, &F);
+    if (rc || !d_q) return rc;
+    const size_t n = (size_t)nx * (size_t)ny * 3;
+    hipLaunchKernelGGL(lit_quantise_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_lin, n, d_q);
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_lit_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                       int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, void *d_state,
+                                       void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera, void *d_out_counters,
+                                       void *stream) {
+    MisLightTable M;
+    RaysFrame F;
+    bool work = false;
+    const int rc = lit_frame_begin(s, precision, nx, ny, s_first, s_count, depth, estimator, n_lights, light_prims, light_choice, nullptr, d_out_linear,
+                                   d_out_stderr, M, F, &work);
+    if (rc || !work) return rc;
+    F.out_camera = as<double>(d_out_camera);
+    return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, as<double>(d_state), as<double>(d_out_linear),
+                         as<unsigned char>(d_out_rgb8), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream));
+}
+
+RTMI_EXPORT int rtmi_render_lit(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *state, double *out_linear,
+                                uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera, uint64_t *out_counters) {
+    MisLightTable M;
+    RaysFrame F;
+    bool work = false;
+    const int rc = lit_frame_begin(s, precision, nx, ny, s_first, s_count, depth, estimator, n_lights, light_prims, light_choice, state, out_linear, out_stderr,
+                                   M, F, &work);
+    if (rc || !work) return rc;
+    const size_t ng = (size_t)nx * (size_t)ny, n = ng * (size_t)s_count;
+    HostIo io(s->ctx);
+    double *d_state, *d_lin, *d_se, *d_out, *d_cam;
+    unsigned char *d_q;
+    u64 *d_cnt;
+    io.plane(&d_state, ng * RTMI_RAYS_REC, state != nullptr, s_first > 0 ? state : nullptr, state); // a first chunk (s_first = 0) reads no records
+    io.out(&d_lin, 3 * ng, out_linear); io.out(&d_se, ng, out_stderr); io.out(&d_q, 3 * ng, out_rgb8); io.work(&d_cnt, 4, out_counters);
+    io.out(&d_out, 3 * n, out_rays); io.out(&d_cam, 8 * n, out_camera);
+    return host_run(io, [&](hipStream_t st) {
+        F.out_camera = d_cam;
+        return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, d_state, d_lin, d_q, d_se, d_out, d_cnt, st);
+    });
 }
