@@ -2688,7 +2688,8 @@ int report_phase_stamps(rtmi_ctx *c, hipStream_t st) {
                                       "bvh: descent (node visits)", "bvh: leaf exact tests", "bvh: loop control / park", "shade: hit record", "shade: |d| normalise",
                                       "shade: rand-in-unit-sphere", "shade: material record + directions", "shade: texture", "shade: store / rest", "shade: sphere uv", "(stamp calibration)",
                                       "bvh: grid entry / next piece of the walk", "media: chords, draws, log", "generate: key, jitter, u v", "generate: lens disk rounds",
-                                      "generate: camera arithmetic", "grid entry: box ranges, ray constants", "grid entry: the rectangle", "grid entry: start cell, piece end"};
+                                      "generate: camera arithmetic", "grid entry: box ranges, ray constants", "grid entry: the rectangle", "grid entry: start cell, piece end",
+                                      "roots: second-root arm (big primitives)", "roots: second-root arm (leaf)"};
     // every interval begins with the bookkeeping of the stamp that opened it: subtract the cost of one stamp (PH_CAL: back-to-back stamps) per stamp
     const double per_stamp = h[2 * PH_SLOTS + PH_CAL] ? (double)h[PH_CAL] / (double)h[2 * PH_SLOTS + PH_CAL] : 0.0;
     double tk[PH_N], lk[PH_N], tot = 0, totl = 0, raw = 0;

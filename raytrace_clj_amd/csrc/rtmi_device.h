@@ -132,8 +132,8 @@ __host__ __device__ inline u64 draw_bits(u64 key, u64 d) { return mix64(key + RT
 // cycles) and as lane-ticks = ticks x the lanes active AT the stamp.  A stamp therefore sits at the END of the code it names, inside
 // the divergent region if that code runs under a lane mask (a region no lane enters executes no stamp: its few scalar cycles fall to
 // the next stamp).  Accumulators live in LDS, one row per wave, updated by the wave's first active lane; flushed once per launch.
-enum { PH_LOOP = 0, PH_REFILL_GEN, PH_REFILL_DEAL, PH_BVH_SETUP, PH_BIG, PH_DESCENT, PH_LEAF, PH_BVH_POST, PH_HITREC, PH_DNORM, PH_SAMPLER, PH_DIRS, PH_TEXTURE, PH_STORE, PH_UV, PH_CAL, PH_GRID, PH_MEDIA, PH_GEN_KEY, PH_GEN_DISK, PH_GEN_CAM, PH_GRID_BOX, PH_GRID_RECT, PH_GRID_PIECE, PH_N }; // PH_CAL: back-to-back stamps = the cost of a stamp, subtracted per stamp on the host
-#define PH_SLOTS 24
+enum { PH_LOOP = 0, PH_REFILL_GEN, PH_REFILL_DEAL, PH_BVH_SETUP, PH_BIG, PH_DESCENT, PH_LEAF, PH_BVH_POST, PH_HITREC, PH_DNORM, PH_SAMPLER, PH_DIRS, PH_TEXTURE, PH_STORE, PH_UV, PH_CAL, PH_GRID, PH_MEDIA, PH_GEN_KEY, PH_GEN_DISK, PH_GEN_CAM, PH_GRID_BOX, PH_GRID_RECT, PH_GRID_PIECE, PH_ROOT2_BIG, PH_ROOT2_LEAF, PH_N }; // PH_CAL: back-to-back stamps = the cost of a stamp, subtracted per stamp on the host
+#define PH_SLOTS 26
 __shared__ unsigned long long g_ph[4][3 * PH_SLOTS + 2]; // [wave]: ticks[PH_SLOTS], lane-ticks[PH_SLOTS], stamps[PH_SLOTS], last stamp, unused
 __device__ inline void ph_stamp(int k, unsigned lane_trips = 0, unsigned trips = 0) { // trips > 0: book lane_trips / trips lanes per tick instead of the stamp's own mask (loops that count their lanes per trip)
     __builtin_amdgcn_sched_barrier(0);
@@ -154,12 +154,15 @@ __device__ inline void ph_stamp(int k, unsigned lane_trips = 0, unsigned trips =
 }
 #define RTMI_PH(k) ph_stamp(k);
 #define RTMI_PH_LANES(k, lt, tr) ph_stamp(k, lt, tr);
+#define RTMI_PH_ARM(k) ph_stamp(k); // a count inside a divergent arm (how often, at how many lanes); no marker of the static analysis build
 #elif defined(RTMI_MARKERS) // static analysis build (scripts/isa_phases.py): an assembler comment at every phase boundary, no code
 #define RTMI_PH(k) asm volatile("; PHASE_END " #k);
 #define RTMI_PH_LANES(k, lt, tr) asm volatile("; PHASE_END " #k);
+#define RTMI_PH_ARM(k)
 #else
 #define RTMI_PH(k)
 #define RTMI_PH_LANES(k, lt, tr)
+#define RTMI_PH_ARM(k)
 #endif
 // FP64 square root.  The device libm's correctly rounded sqrt is v_rsq_f64 + nine fma/mul (Goldschmidt, two residual corrections)
 // wrapped in 14 more instructions: a 2^256 pre-scale for arguments below 2^-767 (whose residuals would underflow), the matching
@@ -863,17 +866,36 @@ __device__ inline void scan_static(const Prim4<R> *__restrict__ lds, int n, int 
 // Exact early-out (only used when t-min >= 0): with the origin outside the sphere (c > 0) and the centre behind
 // the ray (b' = oc.d > 0) both roots are <= 0: -b'-sq < 0, and sq = sqrt(fl(fl(b'b') - fl(ac))) <= sqrt(fl(b'b')) = b'
 // (a correctly rounded sqrt of a correctly rounded square returns |x|), so -b'+sq <= 0: `t > t-min` fails for both.
+//
+// One numerator per test (FP64 rays on the per-ray reciprocal; A = Quot<double>).  With the origin inside or on the sphere (c <= 0) the
+// first root can never pass `t > t-min`, so such a lane forms the second root directly and one quotient serves the wave:
+//   a >= 0 and c <= 0 give fl(a c) <= 0, so disc' = fl(fl(b'b') - fl(a c)) >= fl(b'b') (rounding is monotone), so sq >= RN(sqrt(fl(b'b'))),
+//   which is |b'| whenever b'b' neither underflows nor overflows: -b' - sq <= 0 and t <= 0 < t-min.  Where |b'| < 2^-500 the numerator
+//   -b' - sq <= |b'| is below 2^-500 and, with a >= 2^-200, t < 2^-300 <= t-min -- both bounds are what Quot<double>::fast certifies,
+//   which is why the selector needs `fast` and not c alone (in the underflow zone -b' - sq > 0 does occur).  Where b'b' overflows,
+//   sq = +inf and -b' - sq is -inf or NaN.  (tests/test_sphere_roots_host.py runs exactly these operations on 8 M operands.)
+// Every other lane forms the first root as before; the second root stays as the fallback arm of the lanes whose first root fails
+// `t > t-min`: a ray just outside a surface heading inwards, and the lanes on the IEEE division.  A lane whose first root passed
+// `t > t-min` but failed `t < best` does not enter it: its numerator is >= the first one's (sq >= 0), both quotient forms are monotone
+// in the numerator for a > 0, so the second root fails `t < best` as well (a NaN fails both tests either way).
+template <typename R, typename A> __device__ inline bool far_root_only(const A &, bool, R) { return false; }
+__device__ inline bool far_root_only(const Quot<double> &a, bool behind_ok, double cq) { return a.fast & behind_ok & !(cq > 0.0); }
+// far ? -b' + sq : -b' - sq as ONE addition: x - y is x + (-y) bit for bit, and the sign of sq flips in its high word
+template <typename R> __device__ inline R root_numerator(R bq, R sq, bool far) { return far ? -bq + sq : -bq - sq; }
+template <> __device__ inline double root_numerator<double>(double bq, double sq, bool far) {
+    return -bq + __hiloint2double(__double2hiint(sq) ^ (far ? 0 : (int)0x80000000), __double2loint(sq));
+}
 template <typename R, typename A>
 __device__ inline void sphere_roots(R bq, R cq, R disc, const A &a, R tmin, bool behind_ok, R &best_t, int &best_i, int idx) {
     if (behind_ok && bq > R(0) && cq > R(0)) return;
     const R sq = Real<R>::sqrt_(disc);
-    R t = quot<R>(-bq - sq, a);
-    bool ok = (t > tmin) && (t < best_t);
-    if (!ok) {
+    const bool far = far_root_only(a, behind_ok, cq);
+    R t = quot<R>(root_numerator<R>(bq, sq, far), a);
+    if (!far && !(t > tmin)) {
         t = quot<R>(-bq + sq, a);
-        ok = (t > tmin) && (t < best_t);
+        RTMI_PH_ARM(PH_ROOT2_BIG)
     }
-    if (ok) { best_t = t; best_i = idx; }
+    if ((t > tmin) && (t < best_t)) { best_t = t; best_i = idx; }
 }
 
 template <typename R> __device__ inline void sphere_test(const Prim4<R> &s, const Path<R> &P, R a, R &bq, R &cq, R &disc) {
@@ -1092,9 +1114,18 @@ template <typename R, typename A>
 __device__ inline void sphere_roots_any_order(R bq, R cq, R disc, const A &a, R tmin, bool behind_ok, R &best_t, int &best_i, int idx) {
     if (behind_ok && bq > R(0) && cq > R(0)) return;
     const R sq = Real<R>::sqrt_(disc);
-    R t = quot<R>(-bq - sq, a);
-    if (!(t > tmin)) t = quot<R>(-bq + sq, a);
-    if ((t > tmin) && ((t < best_t) || (t == best_t && idx < best_i))) { best_t = t; best_i = idx; }
+    const bool far = far_root_only(a, behind_ok, cq); // one numerator per test: see sphere_roots
+    R t = quot<R>(root_numerator<R>(bq, sq, far), a);
+    if (!far && !(t > tmin)) {
+        t = quot<R>(-bq + sq, a);
+        RTMI_PH_ARM(PH_ROOT2_LEAF)
+    }
+    // the tie rule (lowest Hitlist index among equal t) behind `t < best`: only a lane with t == best compares the indices
+    if (t > tmin) {
+        bool take = t < best_t;
+        if (__builtin_expect(!take && t == best_t, 0)) take = idx < best_i;
+        if (take) { best_t = t; best_i = idx; }
+    }
 }
 
 // exact test of the primitive of leaf code `code` (per-lane: vector loads; a static sphere needs only its first 32 bytes).
@@ -1104,7 +1135,9 @@ template <typename R, typename A>
 __device__ inline void exact_prim_test_lane(const double *exact12, int code, const Path<R> &P, const A &a, R tmin, bool behind_ok, R &best_t, int &best_i) {
     const int bits = ~code;
     const int idx = bits & 0x3fffffff;
-    const double2 *g = reinterpret_cast<const double2 *>(exact12 + (size_t)idx * 12);
+    // a 32-bit byte offset beside the scalar base (as bvh_grid_entry's node fetch), not a 64-bit address per lane: a tree holds fewer than 2^25 nodes
+    // (scene_build.h), so idx * 96 < 2^32
+    const double2 *g = reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(exact12) + (unsigned)idx * 96u);
     const double2 g0 = g[0], g1 = g[1];
     Prim4<R> s;
     s.cx = (R)g0.x; s.cy = (R)g0.y; s.cz = (R)g1.x;
