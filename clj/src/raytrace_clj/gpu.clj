@@ -650,6 +650,66 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn render-rays-vol
+  "render-rays-nee / render-rays-mis on a scene that holds a ConstantMedium (rtmi_render_rays_vol): the vertices inside a medium sample the lights
+  too, with the uniform sphere's density, and every shadow ray draws its own free-flight distances from the media it crosses, so the unoccluded flag
+  estimates the transmittance.  `estimator` 1 is the NEE rule, 2 the MIS rule (with `light-choice` 0 uniform / 1 by power).  `lights` as for
+  render-rays-nee (required; an empty list is render-rays).  On a scene without media the result is the sibling's bit for bit.  Returns
+  render-rays-nee's map."
+  [scene rays n-groups group lights & {:keys [keys seed ctr0 depth device precision first-ray state estimator light-choice]
+                                       :or {seed 0x5eed0002 ctr0 0 depth 50 device 0 precision 0 first-ray 0 estimator 2 light-choice 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        n    (* n-groups group)
+        rs   (double-array rays)
+        ks   (long-array (or keys (for [g (range n-groups) r (range group)] (sample-key seed g (+ first-ray r)))))
+        lp   (int-array (if (seq lights) lights [0]))
+        nl   (count lights)
+        st   (double-array (or state (* 10 n-groups)))
+        mean (double-array (* 3 n-groups))
+        err  (double-array n-groups)
+        out  (double-array (* 3 n))
+        cnt  (long-array 4)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_rays_vol" scn (int precision) (int n-groups) (int group) (int first-ray) rs ks (long seed) (int ctr0)
+                           (int depth) (int estimator) (int nl) lp (int light-choice) st mean err out cnt))
+          {:mean mean :stderr err :rays out :state st :segments (aget cnt 0) :total-rays (aget cnt 1)
+           :shadow-rays (aget cnt 2) :shadow-rays-occluded (aget cnt 3)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
+(defn render-lit-vol
+  "render-lit on a scene that holds a ConstantMedium (rtmi_render_lit_vol): the same frame rule, state and outputs under the volume rule, `estimator`
+  1 (the NEE rule) or 2 (the MIS rule) only.  make-final, the smoke Cornell box and make-subsurface-sphere render through it.  Returns render-lit's map."
+  [scene nx ny ns lights & {:keys [estimator light-choice seed depth device precision s-first state]
+                            :or {estimator 2 light-choice 0 seed 0x5eed0002 depth 50 device 0 precision 0 s-first 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        npx  (* nx ny)
+        n    (* npx ns)
+        lp   (int-array (if (seq lights) lights [0]))
+        nl   (count lights)
+        st   (double-array (or state (* 10 npx)))
+        lin  (double-array (* 3 npx))
+        rgb8 (byte-array (* 3 npx))
+        err  (double-array npx)
+        out  (double-array (* 3 n))
+        cam  (double-array (* 8 n))
+        cnt  (long-array 4)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_lit_vol" scn (int precision) (int nx) (int ny) (int s-first) (int ns) (int depth) (long seed) (int estimator)
+                           (int nl) lp (int light-choice) st lin rgb8 err out cam cnt))
+          {:linear lin :rgb8 rgb8 :stderr err :rays out :camera cam :state st :segments (aget cnt 0) :total-rays (aget cnt 1)
+           :shadow-rays (aget cnt 2) :shadow-rays-occluded (aget cnt 3)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn query-hits
   "The closest hit of every caller-supplied ray of scene {:camera :world} on GPU `device` (rtmi_query_hits): `rays` holds 7 doubles per ray
   (origin, direction, time), `n` of them; the scene's camera is not read.  Every ray takes (t-min, t-max), or its own pair of `t-range`

@@ -924,6 +924,69 @@ int rtmi_render_lit_device(rtmi_scene *scene, int32_t precision, int32_t nx, int
                            void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera,
                            void *d_out_counters, void *stream);
 
+/* ---- light-sampled paths and frames through participating media: the NEE and MIS rules on scenes that hold a ConstantMedium ----
+ * The calls above refuse a ConstantMedium; these take it.  The reference's medium is itself a stochastic test: hit? scatters a ray whose chord in the
+ * boundary has length L with probability 1 - exp(-density * L).  The same hit? run on a shadow ray with a draw of its own lets the ray through with
+ * probability exactly exp(-density * L), the transmittance: the unoccluded flag is an unbiased estimate of it, no exp is evaluated, and the arithmetic
+ * stays + - * / sqrt plus the medium's own log.  A medium the reference asks twice per ray is asked twice per shadow ray.  In the MIS ratio both
+ * strategies carry the same transmittance, which cancels: x = w * q stays the density ratio.
+ * THE VOLUME RULE, operation by operation as its siblings.  Where nothing is said the NEE rule (estimator 1) and the MIS rule (estimator 2) hold unchanged.
+ * K = the path's key, j = the vertex' segment index, INV_4PI = 0x1.45f306dc9c883p-4.
+ *   1. Vertices: a light sample is taken at every vertex where a RTMI_MAT_LAMBERTIAN or a RTMI_MAT_ISOTROPIC scatter happens (the depth left is > 0),
+ *      and nowhere else.
+ *   2. Light and point: the pick (stream rtmi_sample_key(K, j, 1)) and the point on the light (stream rtmi_sample_key(K, j, 0)) are unchanged, and so
+ *      are d, d2, sd, cl, the far-side rule and the ray (p, d, time) with the t-range (0.001, 1 - 0.001); the time is the scattered ray's (at an
+ *      Isotropic vertex the reference sets it to the hit's t, shader.clj:136, and every later vertex of the path inherits it).  At a Lambertian vertex
+ *      everything is the NEE rule's.  At an Isotropic vertex the record's normal is not read (the reference's medium record carries an arbitrary one):
+ *      the vertex is valid when p is finite; a ray is built when d2 > 0, cl > 0 and the far-side rule allows it; cp is not formed; p is the scatter point.
+ *   3. The weight at an Isotropic vertex -- the reference scatters a medium hit uniformly over the sphere, density 1 / 4 pi:
+ *      w = ((cl / (d2 * sqrt(d2))) * area) * INV_4PI.
+ *   4. The shadow ray's stream is keyed rtmi_sample_key(K, j, 2) and starts at draw 0: the search is rtmi_query_occluded's on that ray with that key and
+ *      ctr0 = 0.  The media are asked first, in the scene's call order; a medium that hits occludes the ray; a shadow ray that starts inside a medium is
+ *      clipped as a path ray is.  The contributions are the siblings': NEE T * ((Le * w) * nl); MIS x = w * q_l, m = x / (1 + x), T * (Le * m).
+ *   5. The MIS lobe value at an Isotropic vertex: DD = dot3(D, D); g = 0.125 / (DD * sqrt(DD)) if p is finite and DD > 0, else +0.0.  Step 7 of the MIS
+ *      rule is unchanged and reads this g.  (With d = t * D, d2 = t*t * DD and cl = t * cl' for the unit normal: the weight of step 3 at the point the
+ *      scatter found is cl' / (t*t * DD * sqrt(DD)) * area * INV_4PI = g * cl' / (t*t) * area * TWO_INV_PI with g = (INV_4PI / TWO_INV_PI) / (DD * sqrt(DD));
+ *      INV_4PI / TWO_INV_PI = 1/8, exact -- both constants are the same significand.)
+ *   6. The closing emission (NEE step 6, MIS step 7): "the previous vertex took a light sample" includes the Isotropic vertices.
+ *   7. Scope.  Media mode RTMI_MEDIA_DESCENT only (every scene function of scene.clj); a scene in RTMI_MEDIA_HITLIST or the narrowed form returns
+ *      RTMI_E_UNSUPPORTED and launches nothing (those worlds need the path kernels' media-sequence instantiations, which this family does not have).
+ *      On a scene without media every output is the NEE or MIS sibling's bit for bit: no medium ever reads the new stream.  The RTMI_F32 scope is the
+ *      siblings'.
+ * rtmi_render_rays_vol*: rtmi_render_rays_mis' arguments with estimator (1 = the NEE rule, light_choice is not looked at; 2 = the MIS rule) in front of
+ *   n_lights; the same state record, the same four counters, the same invariance under chunks and workspace passes.
+ * rtmi_probe_paths_vol: rtmi_probe_paths_mis' arguments with estimator.  log: [n][max_seg][RTMI_VOL_REC]: [0..27] the RTMI_MIS_REC values (estimator 1:
+ *   [21..23] the NEE contribution, [24..27] zeros); [28] = 1.0 where the light-sampled vertex is an Isotropic scatter.  out_weight: m'; for estimator 1,
+ *   0.0 where the closing emission is dropped and 1.0 otherwise.
+ * rtmi_render_lit_vol*: rtmi_render_lit's arguments, estimator 1 or 2 only; the same frame rule, state, out_camera, out_rays, 8-bit frame and counters.
+ * Errors, in this order: the sibling's own, in its order, up to and including the list's length (n_lights); estimator outside {1, 2}: RTMI_E_ARG;
+ * light_choice outside {0, 1} with estimator 2: RTMI_E_ARG; (n_groups == 0 succeeds here); media present and the mode not RTMI_MEDIA_DESCENT:
+ * RTMI_E_UNSUPPORTED; the list's entries.  A failed call launches nothing and writes nothing. */
+#define RTMI_VOL_REC 29
+/* host buffers; synchronous */
+int rtmi_render_rays_vol(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first,
+                         const double *rays, const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth,
+                         int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice,
+                         double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters);
+/* every d_ pointer a device pointer (light_prims stays a host array); asynchronous on `stream` with rtmi_render_device's stream semantics */
+int rtmi_render_rays_vol_device(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first,
+                                const void *d_rays, const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth,
+                                int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice,
+                                void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream);
+int rtmi_probe_paths_vol(rtmi_scene *scene, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
+                         int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *out_rgb, uint64_t *out_nseg,
+                         double *out_weight, double *log, int32_t max_seg, int32_t *out_nlog);
+/* host buffers; synchronous */
+int rtmi_render_lit_vol(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                        int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice,
+                        double *state, double *out_linear, uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera,
+                        uint64_t *out_counters);
+/* every d_ pointer a device pointer (light_prims stays a host array); asynchronous on `stream` with rtmi_render_device's stream semantics */
+int rtmi_render_lit_vol_device(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                               int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice,
+                               void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera,
+                               void *d_out_counters, void *stream);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

@@ -45,6 +45,7 @@ SYMBOLS = [
     "rtmi_render_rays_nee", "rtmi_render_rays_nee_device", "rtmi_probe_paths_nee",
     "rtmi_render_rays_mis", "rtmi_render_rays_mis_device", "rtmi_probe_paths_mis",
     "rtmi_render_lit", "rtmi_render_lit_device",
+    "rtmi_render_rays_vol", "rtmi_render_rays_vol_device", "rtmi_probe_paths_vol", "rtmi_render_lit_vol", "rtmi_render_lit_vol_device",
 ]
 
 F64, F32 = 0, 1
@@ -60,6 +61,7 @@ RAYS_REC = 10  # doubles per group record of rtmi_render_rays: sums rgb, Welford
 DIRECT_REC = 4  # doubles per point record of rtmi_direct_irradiance / rtmi_render_direct: sum rgb, samples
 NEE_REC = 24  # doubles per logged vertex of rtmi_probe_paths_nee: SEG_REC's twelve, state, light, d xyz, w, T rgb, contribution rgb
 MIS_REC = 28  # doubles per logged vertex of rtmi_probe_paths_mis: NEE_REC's twenty-four, x, m, g, x' (closing vertex)
+VOL_REC = 29  # doubles per logged vertex of rtmi_probe_paths_vol: MIS_REC's twenty-eight, then 1.0 at an Isotropic light-sampled vertex
 DIRECT_MAX_LIGHTS = 32  # RTMI_DIRECT_MAX_LIGHTS: lights one call samples
 EDIT_STREAM_MAX_BYTES = 32768  # RTMI_EDIT_STREAM_MAX_BYTES: changed row payload one rtmi_scene_set_materials_stream call carries
 
@@ -192,6 +194,11 @@ def lib():
     L.rtmi_probe_paths_mis.argtypes = [vp, i32, i32, vp, vp, u64, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]
     L.rtmi_render_lit.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.rtmi_render_lit_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rtmi_render_rays_vol.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.rtmi_render_rays_vol_device.argtypes = [vp, i32, i32, i32, i32, vp, vp, u64, C.c_uint32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.rtmi_probe_paths_vol.argtypes = [vp, i32, i32, vp, vp, u64, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]
+    L.rtmi_render_lit_vol.argtypes = L.rtmi_render_lit.argtypes
+    L.rtmi_render_lit_vol_device.argtypes = L.rtmi_render_lit_device.argtypes
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

@@ -261,9 +261,10 @@ def light_table(flat, prims):
     return table
 
 
-def _light_terms(px, py, pz, nx, ny, nz, rows, keys):
+def _light_terms(px, py, pz, nx, ny, nz, rows, keys, lobe=True):
     """Steps 3 - 5 of the light rule for one item per entry: the point p, the UNIT normal (nx, ny, nz), the item's light record `rows` [items, LIGHT_REC]
-    and its stream `keys` -> (dx, dy, dz, d2, cp, cl, built, area), every operation a single IEEE operation in the header's order."""
+    and its stream `keys` -> (dx, dy, dz, d2, cp, cl, built, area), every operation a single IEEE operation in the header's order.  lobe=False (a
+    vertex inside a medium: no normal, vol_samples): cp > 0 is not asked for."""
     from . import util
     kind = rows[:, 0].astype(np.int64)
     sphere = kind <= 1
@@ -293,7 +294,7 @@ def _light_terms(px, py, pz, nx, ny, nz, rows, keys):
     cl = np.abs(sd)
     ex, ey, ez = px - g0, py - g1, pz - g2
     far = sphere & (((ex * ex + ey * ey) + ez * ez) > g3 * g3) & (sd > 0.0)               # the far side of a sphere seen from outside
-    built = ~far & (d2 > 0.0) & (cp > 0.0) & (cl > 0.0)
+    built = ~far & (d2 > 0.0) & ((cp > 0.0) if lobe else True) & (cl > 0.0)
     return dx, dy, dz, d2, cp, cl, built, area
 
 
@@ -432,3 +433,51 @@ def mis_closing(g, normals, dirs, t, area, q):
         x = ((((g * cl) / (t * t)) * area) * TWO_INV_PI) * q
         m = np.where(np.isnan(x), 0.0, np.where(x == np.inf, 1.0, x / (1.0 + x)))
     return x, m
+
+
+INV_4PI = float.fromhex("0x1.45f306dc9c883p-4")
+
+
+def vol_samples(points, normals, iso, lights, keys_sample, keys_pick, light=None):
+    """The light samples of light-sampled paths through participating media (include/rtmi.h, "the volume rule", steps 2 and 3), one per vertex,
+    so rtmi_probe_paths_vol's log columns [13..17] equal these bit for bit.  iso [n] bool: the vertex is an Isotropic scatter inside a medium.
+    A Lambertian vertex (iso False) is nee_samples' row.  At an Isotropic vertex the normal is not read: the vertex is valid when p is finite, a ray
+    is built when d2 > 0, cl > 0 and the far-side rule allows it, and the weight carries the uniform sphere's density 1 / 4 pi in the lobe's place:
+    w = ((cl / (d2 * sqrt(d2))) * area) * INV_4PI.  The pick and the point on the light are nee_samples' (`light`: the MIS rule's pick).
+    -> nee_samples' tuple (light [n], d [n, 3], w [n], built [n])."""
+    points, normals = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(normals, np.float64).reshape(-1, 3)
+    iso = np.asarray(iso, bool).reshape(-1)
+    if len(iso) != len(points):
+        raise ValueError("iso must pair up with the points")
+    lights = np.asarray(lights, np.float64).reshape(-1, LIGHT_REC)
+    keys_sample = np.asarray(keys_sample, np.uint64).reshape(-1)
+    unit = np.where(iso[:, None], np.array([0.0, 0.0, 1.0]), normals)                   # (an Isotropic row's normal is not read: its row is replaced below)
+    l, d, w, built = nee_samples(points, unit, lights, keys_sample, keys_pick, light)
+    k = np.flatnonzero(iso)
+    if len(k):
+        zero = np.zeros(len(k))
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            dx, dy, dz, d2, _, cl, bi, area = _light_terms(points[k, 0], points[k, 1], points[k, 2], zero, zero, zero, lights[l[k]], keys_sample[k],
+                                                           lobe=False)
+            bi = bi & np.isfinite(points[k]).all(axis=1)
+            wi = ((cl / (d2 * np.sqrt(d2))) * area) * INV_4PI                           # 3. the weight at an Isotropic vertex
+        d[k] = np.where(bi[:, None], np.stack([dx, dy, dz], axis=1), 0.0)
+        w[k] = np.where(bi, wi, 0.0)
+        built[k] = bi
+    return l, d, w, built
+
+
+def vol_lobe(normals, dirs, iso, points=None):
+    """Step 5 of the volume rule: the MIS lobe value per vertex -- mis_lobe's at a Lambertian vertex; at an Isotropic one (iso True)
+    g = 0.125 / (DD * sqrt(DD)) with DD = dot3(D, D) if the point (where given) is finite and DD > 0, else +0.0.  g * cl' / t^2 * area * TWO_INV_PI
+    is then the weight of vol_samples at d = t * D (0.125 = INV_4PI / TWO_INV_PI, exact), which mis_closing forms."""
+    dirs = np.asarray(dirs, np.float64).reshape(-1, 3)
+    iso = np.asarray(iso, bool).reshape(-1)
+    g = mis_lobe(normals, dirs, points)
+    with np.errstate(all="ignore"):
+        DD = (dirs[:, 0] * dirs[:, 0] + dirs[:, 1] * dirs[:, 1]) + dirs[:, 2] * dirs[:, 2]
+        gi = 0.125 / (DD * np.sqrt(DD))
+    valid = DD > 0.0
+    if points is not None:
+        valid = valid & np.isfinite(np.asarray(points, np.float64).reshape(-1, 3)).all(axis=1)
+    return np.where(iso, np.where(valid, gi, 0.0), g)

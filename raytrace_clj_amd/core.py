@@ -657,9 +657,12 @@ class DeviceScene:
             raise ValueError("ns and chunk must be > 0")
         def rays_of(k, n):
             return generator(nx, ny, k, n, seed=seed, **generator_args)
+        if isinstance(nee, str) and nee in ("vol-nee", "vol-mis"):  # the volume rule: scenes that hold a ConstantMedium
+            return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_vol, 4, estimator=nee[4:], lights=lights, light_choice=light_choice,
+                                     seed=seed, depth=depth, precision=precision)
         if isinstance(nee, str):
             if nee != "mis":
-                raise ValueError("nee is False, True or \"mis\" (got %r)" % nee)
+                raise ValueError("nee is False, True, \"mis\", \"vol-nee\" or \"vol-mis\" (got %r)" % nee)
             return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_mis, 4, lights=lights, light_choice=light_choice, seed=seed, depth=depth,
                                      precision=precision)
         if nee:
@@ -722,6 +725,64 @@ class DeviceScene:
                                                      int(seed), int(ctr0), int(depth), n_listed, ptr(lights), self._light_choice(light_choice), ptr(state),
                                                      ptr(out_mean), ptr(out_stderr), ptr(out_rays), ptr(out_counters), ptr(stream)))
 
+    # ---- light-sampled paths through participating media (THE VOLUME RULE of include/rtmi.h) -------------------------------------------------
+    @staticmethod
+    def _vol_estimator(estimator):
+        """"nee" / "mis" (or 1 / 2) -> the C entry's estimator; an unknown name is a ValueError, before any device work (an integer goes through
+        and is refused there)"""
+        if isinstance(estimator, str):
+            if estimator not in VOL_ESTIMATORS:
+                raise ValueError("estimator is one of %s (got %r)" % (", ".join(sorted(VOL_ESTIMATORS)), estimator))
+            return VOL_ESTIMATORS[estimator]
+        return int(estimator)
+
+    def render_rays_vol(self, rays, group=1, estimator="mis", lights=None, light_choice=0, keys=None, seed=RENDER_SEED, ctr0=0, depth=DEFAULT_DEPTH,
+                        precision="f64", first=0, state=None, return_rays=False):
+        """render_rays_nee (estimator "nee" / 1) or render_rays_mis ("mis" / 2) on a scene that holds a ConstantMedium (rtmi_render_rays_vol): the
+        Isotropic scatters inside a medium sample the lights too, with the uniform sphere's density 1 / 4 pi in the lobe's place, and every shadow
+        ray draws from a stream of its own (sample_key(K, j, 2)) the free-flight distances of the media it crosses, so its unoccluded flag is an
+        unbiased estimate of the transmittance.  camera.vol_samples and vol_lobe restate the rule.  Without media the result is the sibling's bit
+        for bit.  -> render_rays_nee's tuple."""
+        est = self._vol_estimator(estimator)
+        rays, group, n_groups, keys = self._rays_inputs(rays, group, keys, state)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        mean, err, cnt = np.zeros((n_groups, 3), np.float64), np.zeros(n_groups, np.float64), np.zeros(4, np.uint64)
+        out = np.zeros((len(rays), 3), np.float64) if return_rays else None
+        check(_ffi.lib().rtmi_render_rays_vol(self.handle, _PRECISION[precision], n_groups, group, int(first), ptr(rays), ptr(keys), int(seed), int(ctr0),
+                                              int(depth), est, n_listed, ptr(lights), self._light_choice(light_choice),
+                                              ptr(state), ptr(mean), ptr(err), ptr(out), ptr(cnt)))
+        return mean, err, cnt, out
+
+    def render_rays_vol_device(self, n_groups, group, rays, out_mean, out_stderr, estimator="mis", lights=None, light_choice=0, keys=None,
+                               seed=RENDER_SEED, ctr0=0, depth=DEFAULT_DEPTH, precision="f64", first=0, state=None, out_rays=None, out_counters=None,
+                               stream=None):
+        """render_rays_vol on HBM-resident buffers (lights stays a host list; out_counters: four uint64); asynchronous, render_device's stream
+        semantics.  A state's count is the caller's contract: it is not read back."""
+        est = self._vol_estimator(estimator)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        check(_ffi.lib().rtmi_render_rays_vol_device(self.handle, _PRECISION[precision], int(n_groups), int(group), int(first), ptr(rays), ptr(keys),
+                                                     int(seed), int(ctr0), int(depth), est, n_listed, ptr(lights),
+                                                     self._light_choice(light_choice), ptr(state), ptr(out_mean), ptr(out_stderr), ptr(out_rays),
+                                                     ptr(out_counters), ptr(stream)))
+
+    def render_lit_vol(self, nx, ny, ns, chunk=None, estimator="mis", lights=None, light_choice=0, depth=DEFAULT_DEPTH, seed=RENDER_SEED,
+                       precision="f64", return_rays=False, return_camera=False):
+        """render_lit under the volume rule (rtmi_render_lit_vol; estimator "nee" or "mis" only): the frame of a scene that holds a ConstantMedium
+        -- make-final, the smoke Cornell box, make-subsurface-sphere -- through light-sampled paths.  -> render_lit's tuple."""
+        return self.render_lit(nx, ny, ns, chunk, self._vol_estimator(estimator), lights, light_choice, depth, seed, precision, return_rays,
+                               return_camera, _entry=_ffi.lib().rtmi_render_lit_vol)
+
+    def render_lit_vol_device(self, nx, ny, s_first, s_count, out_linear, out_stderr, out_rgb8=None, estimator="mis", lights=None, light_choice=0,
+                              depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", state=None, out_rays=None, out_camera=None, out_counters=None,
+                              stream=None):
+        """rtmi_render_lit_vol_device: render_lit_device under the volume rule (estimator "nee" or "mis" only)."""
+        est = self._vol_estimator(estimator)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        check(_ffi.lib().rtmi_render_lit_vol_device(self.handle, _PRECISION[precision], int(nx), int(ny), int(s_first), int(s_count), int(depth), int(seed),
+                                                    est, n_listed, ptr(lights), self._light_choice(light_choice), ptr(state),
+                                                    ptr(out_linear), ptr(out_rgb8), ptr(out_stderr), ptr(out_rays), ptr(out_camera), ptr(out_counters),
+                                                    ptr(stream)))
+
     def render_nee(self, nx, ny, ns, chunk, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", lights=None, mis=False, light_choice=0):
         """An nx x ny x ns frame of the scene's own camera (of either kind) through light-sampled paths, folded per pixel through one state as
         render_with folds.  Film jitter, lens draws and path streams come from three seeds derived from `seed` (sample_key(seed, 0 / 1 / 2, 0)),
@@ -758,14 +819,15 @@ class DeviceScene:
         return int(estimator)
 
     def render_lit(self, nx, ny, ns, chunk=None, estimator="mis", lights=None, light_choice=0, depth=DEFAULT_DEPTH, seed=RENDER_SEED,
-                   precision="f64", return_rays=False, return_camera=False):
+                   precision="f64", return_rays=False, return_camera=False, _entry=None):
         """An nx x ny x ns frame of the scene's own camera through rtmi_render_lit: the paths `render` traces -- the same keys, film jitter, lens
         draws and streams, built on the device, no ray uploaded -- under the plain estimator ("plain": the frame of `render` bit for bit), the NEE
         rule ("nee") or the MIS rule ("mis", with light_choice 0 / "uniform" or 1 / "power").  chunk: samples per call, folded through one state
         (None: one call); the result does not depend on it.  -> (linear [ny, nx, 3], rgb8, stderr [ny, nx], counters {segments, rays, shadow rays
         built, shadow rays occluded} summed over the calls[, rays' radiance [nx * ny, ns, 3]][, camera [nx * ny, ns, 8] = origin, direction,
         time, the stream position behind the camera]); row 0 = top."""
-        est = self._lit_estimator(estimator)
+        est = self._lit_estimator(estimator) if _entry is None else int(estimator)  # (_entry: render_lit_vol's C entry, the same arguments)
+        entry = _ffi.lib().rtmi_render_lit if _entry is None else _entry
         nx, ny, ns = int(nx), int(ny), int(ns)
         chunk = ns if chunk is None else int(chunk)
         if nx <= 0 or ny <= 0 or ns <= 0 or chunk <= 0:
@@ -784,8 +846,8 @@ class DeviceScene:
             cnt = np.zeros(4, np.uint64)
             r = np.zeros((npx, n, 3), np.float64) if return_rays else None
             c = np.zeros((npx, n, 8), np.float64) if return_camera else None
-            check(_ffi.lib().rtmi_render_lit(self.handle, _PRECISION[precision], nx, ny, k, n, int(depth), int(seed), est, n_listed, ptr(lights), choice,
-                                             ptr(state), ptr(lin), ptr(q), ptr(err), ptr(r), ptr(c), ptr(cnt)))
+            check(entry(self.handle, _PRECISION[precision], nx, ny, k, n, int(depth), int(seed), est, n_listed, ptr(lights), choice,
+                        ptr(state), ptr(lin), ptr(q), ptr(err), ptr(r), ptr(c), ptr(cnt)))
             total += cnt
             if return_rays:
                 rays[:, k:k + n] = r
@@ -1112,6 +1174,23 @@ class DeviceScene:
         log = np.zeros((n, max_seg, _ffi.MIS_REC)) if max_seg else None
         check(_ffi.lib().rtmi_probe_paths_mis(self.handle, _PRECISION[precision], n, ptr(rays), ptr(keys), ctr0, depth, n_listed, ptr(lights),
                                               self._light_choice(light_choice), ptr(rgb), ptr(nseg), ptr(weight), ptr(log), max_seg, ptr(nlog)))
+        return rgb, nseg, log, nlog, weight
+
+    def probe_paths_vol(self, rays, keys, estimator="mis", lights=None, light_choice=0, depth=DEFAULT_DEPTH, ctr0=0, max_seg=0, precision="f64"):
+        """probe_paths_mis for the volume rule (rtmi_probe_paths_vol; estimator "nee" / 1 or "mis" / 2) -> (rgb [n, 3], segment counts, log [n,
+        max_seg, VOL_REC] or None, logged vertices per path, weight float64 [n] = the factor on the closing emission; under the NEE rule 0 where it
+        is dropped).  A log row: MIS_REC's twenty-eight values (under the NEE rule [21..23] its contribution and [24..27] zeros), then 1.0 where the
+        light-sampled vertex is an Isotropic scatter."""
+        est = self._vol_estimator(estimator)
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+        keys = np.ascontiguousarray(keys, np.uint64)
+        n = len(rays)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        rgb, nseg, nlog, weight = np.zeros((n, 3)), np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        log = np.zeros((n, max_seg, _ffi.VOL_REC)) if max_seg else None
+        check(_ffi.lib().rtmi_probe_paths_vol(self.handle, _PRECISION[precision], n, ptr(rays), ptr(keys), ctr0, depth, est,
+                                              n_listed, ptr(lights), self._light_choice(light_choice), ptr(rgb), ptr(nseg), ptr(weight), ptr(log),
+                                              max_seg, ptr(nlog)))
         return rgb, nseg, log, nlog, weight
 
     def probe_camera(self, uv, keys, precision="f64"):
@@ -1773,6 +1852,45 @@ def _lit_flags(argv, panorama=False, orbit=False, nee=False, mis=False):
     return rest, lit
 
 
+VOL_ESTIMATORS = {"nee": 1, "mis": 2}  # estimator of the volume rule's calls
+
+
+def _lit_vol_flags(argv, panorama=False, orbit=False, nee=False, mis=False):
+    """-> (the other arguments, None or (estimator, light choice) of --lit-vol [nee|mis[:uniform|:power]], default mis); it is taken out of the
+    arguments before --lit is looked for, and the modes it does not combine with (--lit among them) are refused here, before any device work"""
+    rest, vol, k = [], None, 0
+    while k < len(argv):
+        a = argv[k]
+        if a == "--lit-vol":
+            if vol is not None:
+                raise SystemExit("--lit-vol given twice")
+            vol = ("mis", "uniform")
+            if k + 1 < len(argv):
+                est, _, choice = argv[k + 1].partition(":")
+                if est in VOL_ESTIMATORS:
+                    if choice and (est != "mis" or choice not in MIS_CHOICES):
+                        raise SystemExit("--lit-vol takes nee, mis, mis:uniform or mis:power (got %r)" % argv[k + 1])
+                    vol = (est, choice or "uniform")
+                    k += 1
+        elif a.startswith("--lit-vol"):
+            raise SystemExit("--lit-vol takes nee or mis[:power] as a separate word (got %r)" % a)
+        else:
+            rest.append(a)
+        k += 1
+    if vol is not None and (panorama or orbit):
+        raise SystemExit("--lit-vol does not combine with --orbit or --panorama")
+    if vol is not None and (nee or mis or any(a == "--lit" for a in rest)):
+        raise SystemExit("--lit-vol does not combine with --lit, --nee or --mis: it is their frame on a scene that holds a ConstantMedium")
+    return rest, vol
+
+
+def _lit_vol_name(name):
+    """x.png -> x.vol.png: the frame of rtmi_render_lit_vol is written next to the frame"""
+    import os
+    root, ext = os.path.splitext(name)
+    return root + ".vol" + ext
+
+
 def _lit_name(name):
     """x.png -> x.lit.png: the frame of rtmi_render_lit is written next to the frame"""
     import os
@@ -1858,7 +1976,11 @@ def main(argv=None):
     It is refused where --nee is.
     --lit [plain|nee|mis[:power]] also writes the frame of DeviceScene.render_lit (default mis): the samples the frame itself traces -- the same keys, jitter,
     lens draws and streams, the camera rays built on the device -- under the plain estimator, the NEE rule or the MIS rule, as name.lit.ext.  With --chunk
-    K it is refined K samples at a time through one state (the same image).  It does not combine with --orbit, --panorama, --nee or --mis."""
+    K it is refined K samples at a time through one state (the same image).  It does not combine with --orbit, --panorama, --nee or --mis.
+    --lit-vol [nee|mis[:power]] also writes the frame of DeviceScene.render_lit_vol (default mis) as name.vol.ext: --lit's frame under the volume rule,
+    for the scenes that hold a ConstantMedium (final, the smoke cornell-box, subsurface) -- the vertices inside a medium sample the lights too and the
+    shadow rays draw their own way through the media.  With --chunk K it is refined K samples at a time.  It does not combine with --lit, --nee, --mis,
+    --orbit or --panorama."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
     argv, direct = _direct_flags(argv)
@@ -1876,6 +1998,7 @@ def main(argv=None):
         raise SystemExit("--direct does not combine with --orbit or --panorama")
     argv, nee = _nee_flags(argv, panorama, orbit_views is not None)
     argv, mis = _mis_flags(argv, panorama, orbit_views is not None)
+    argv, vol_mode = _lit_vol_flags(argv, panorama, orbit_views is not None, nee, mis is not None)
     argv, lit_mode = _lit_flags(argv, panorama, orbit_views is not None, nee, mis is not None)
     argv, accumulate = _accumulate_flags(argv, orbit_views)
     argv, adaptive_denoised = _adaptive_denoised_flags(argv)
@@ -2018,6 +2141,13 @@ def main(argv=None):
         finally:
             ds.close()
         _save_image(_lit_name(name), frame)
+    if vol_mode is not None:
+        ds = DeviceScene(sc)
+        try:
+            frame = ds.render_lit_vol(nx, ny, nr, chunk=chunk, estimator=vol_mode[0], light_choice=vol_mode[1])[1]
+        finally:
+            ds.close()
+        _save_image(_lit_vol_name(name), frame)
     return 0
 
 

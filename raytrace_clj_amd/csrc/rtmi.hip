@@ -1727,12 +1727,17 @@ __device__ inline int nee_sampled_light(const NeeLights &nl, int orig) {
 // Every lane of the wave calls (the disk sampler is cooperative), the lanes whose vertex takes a light sample with `want`.  As in generate_light_ray
 // the rounds stand before the geometry (no operation changes); unlike there the normal is the record's as it is.
 // MIS: the light by the MIS rule's step 2, and xmg = {x, m, g} of its steps 4 and 6 for the scattered direction D.
-template <bool MIS = false>
+// VOL (THE VOLUME RULE): `iso` lanes sit at an Isotropic scatter -- the record's normal is not read, the lobe is the sphere's 1 / 4 pi.  Both weights and
+// both lobe values are formed by every lane and selected: no divergent path.
+constexpr double kInv4Pi = 0x1.45f306dc9c883p-4;
+template <bool MIS = false, bool VOL = false>
 __device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsigned j, double px, double py, double pz, double nx, double ny, double nz,
-                                     double time, double *q, double &w, int &l, const double *D = nullptr, double *xmg = nullptr) {
+                                     double time, double *q, double &w, int &l, const double *D = nullptr, double *xmg = nullptr, bool iso = false) {
     const double big = __builtin_inf();
     const double len2 = dot3(nx, ny, nz, nx, ny, nz);
-    bool ok = want && ::fabs(px) < big && ::fabs(py) < big && ::fabs(pz) < big && ::fabs(nx) < big && ::fabs(ny) < big && ::fabs(nz) < big && len2 > 0.0;
+    bool ok = want && ::fabs(px) < big && ::fabs(py) < big && ::fabs(pz) < big;
+    if constexpr (VOL) ok = ok && (iso || (::fabs(nx) < big && ::fabs(ny) < big && ::fabs(nz) < big && len2 > 0.0));
+    else ok = ok && ::fabs(nx) < big && ::fabs(ny) < big && ::fabs(nz) < big && len2 > 0.0;
     const bool valid = ok; // (MIS) the vertex itself is sound, whatever becomes of its light sample
     const u64 kpick = sample_key(K, (u64)j, 1ull), key = sample_key(K, (u64)j, 0ull);
     const double up = Real<double>::uniform(mix64(kpick + RTMI_GOLD)); // draw 0 of the picking stream
@@ -1766,6 +1771,10 @@ __device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsi
     if constexpr (MIS) { // step 6: the lobe's value along the scattered ray, less its constant: cos^3 with the direction's length divided out
         const double a = dot3(nx, ny, nz, D[0], D[1], D[2]), DD = dot3(D[0], D[1], D[2], D[0], D[1], D[2]);
         xmg[2] = valid && a > 0.0 && DD > 0.0 ? ((a * a) * a) / ((DD * DD) * DD) : 0.0;
+        if constexpr (VOL) { // step 5 of the volume rule: the uniform sphere's density over TWO_INV_PI, with the direction's length divided out
+            const double gi = valid && DD > 0.0 ? 0.125 / (DD * ::sqrt(DD)) : 0.0;
+            xmg[2] = iso ? gi : xmg[2];
+        }
     }
     double qx, qy, qz, sx, sy, sz;
     if (sphere) { // Marsaglia: a uniform point of the unit disk -> a uniform point of the unit sphere
@@ -1785,8 +1794,13 @@ __device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsi
         const double ex = px - g0, ey = py - g1, ez = pz - g2;
         if (dot3(ex, ey, ez, ex, ey, ez) > g3 * g3 && sd > 0.0) ok = false;
     }
-    ok = ok && d2 > 0.0 && cp > 0.0 && cl > 0.0;
+    if constexpr (VOL) ok = ok && d2 > 0.0 && (iso || cp > 0.0) && cl > 0.0;
+    else ok = ok && d2 > 0.0 && cp > 0.0 && cl > 0.0;
     w = ok ? ((((cp * cp) * (cp * cl)) / ((d2 * d2) * d2)) * area) * kTwoInvPi : 0.0; // the reference's lobe 2 cos^3 / pi, the light's cosine, the inverse square
+    if constexpr (VOL) { // step 3 of the volume rule: the medium scatters uniformly over the sphere
+        const double wi = ok ? ((cl / (d2 * ::sqrt(d2))) * area) * kInv4Pi : 0.0;
+        w = iso ? wi : w;
+    }
     if constexpr (MIS) { // step 4: x = p_scatter / p_light, m = the balance heuristic's share of the light sample
         const double xx = w * nl.rec[kMisRows + 3 + 2 * l];
         xmg[0] = xx;
@@ -1802,9 +1816,11 @@ __device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsi
 // -> the light-sample state of the header: 0 none, 1 built and unoccluded, 2 built and occluded, 3 built no ray.
 // MIS (THE MIS RULE): the pending contribution is T * (Le * m), and the lobe value g of the scattered ray goes to the lane's seventh slot, where the path's
 // end finds it; rec is then an RTMI_MIS_REC row.
-template <typename R, int VARIANT, bool EXT, bool MIS = false>
+// VOL (THE VOLUME RULE): `lamb` holds the Lambertian and the Isotropic vertices, `iso` the latter; the shadow ray carries a stream of its own, keyed
+// sample_key(K, j, 2) at draw 0, from which the media it crosses draw their free-flight distances: the unoccluded flag estimates the transmittance.
+template <typename R, int VARIANT, bool EXT, bool MIS = false, bool VOL = false>
 __device__ inline int nee_vertex(SceneRef sc, Prim4<R> *lds, const NeeLights &nl, bool lamb, u64 K, unsigned j, const Path<R> &P, double nx, double ny,
-                                 double nz, double *slot, double *rec) {
+                                 double nz, double *slot, double *rec, bool iso = false) {
     Path<R> S;
     bool ok;
     {
@@ -1813,10 +1829,10 @@ __device__ inline int nee_vertex(SceneRef sc, Prim4<R> *lds, const NeeLights &nl
         double xmg[3] = {0.0, 0.0, 0.0};
         if constexpr (MIS) {
             const double D[3] = {(double)P.dx, (double)P.dy, (double)P.dz};
-            ok = nee_light_ray<true>(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l, D, xmg);
+            ok = nee_light_ray<true, VOL>(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l, D, xmg, iso);
             if (lamb) slot[6 * kBlock] = xmg[2];
             if (rec && lamb) { rec[24] = xmg[0]; rec[25] = xmg[1]; rec[26] = xmg[2]; }
-        } else ok = nee_light_ray(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l);
+        } else ok = nee_light_ray<false, VOL>(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l, nullptr, nullptr, iso);
         const double *L = nl.rec + (size_t)l * kLightRec;
         const double many = (double)nl.n;
 #pragma unroll
@@ -1828,6 +1844,10 @@ __device__ inline int nee_vertex(SceneRef sc, Prim4<R> *lds, const NeeLights &nl
         }
         if (rec && lamb) { rec[13] = (double)l; rec[14] = q[3]; rec[15] = q[4]; rec[16] = q[5]; rec[17] = w; }
         load_ray<R>(q, S);
+        if constexpr (VOL) {
+            seed_stream(S, sample_key(K, (u64)j, 2ull), 0u);
+            if (rec && lamb) rec[28] = iso ? 1.0 : 0.0;
+        }
     }
     R best_t; int best_i;
     intersect_world<R, true, VARIANT, EXT, false, false, 0, false, true>(sc, lds, 0, 1, S, ok, R(0.001), (R)(1.0 - 0.001), best_t, best_i);
@@ -1867,9 +1887,15 @@ struct NeeParams {
 // sample; at 3 they take 131 - 141 VGPRs without scratch and measured 4 - 7 % faster (A/B: make variant NAME=nee_w4 FLAGS=-DRTMI_NEE_MIN_WAVES=4)
 #define RTMI_NEE_MIN_WAVES 3
 #endif
+#ifndef RTMI_VOL_MIN_WAVES
+// waves per SIMD of the VOL instantiations alone (A/B: make variant NAME=vol_w2 FLAGS=-DRTMI_VOL_MIN_WAVES=2)
+#define RTMI_VOL_MIN_WAVES RTMI_NEE_MIN_WAVES
+#endif
 // MIS (rtmi_render_rays_mis*): THE MIS RULE of rtmi.h -- the same path and the same shadow rays, the balance heuristic on both ends.
-template <typename R, int VARIANT, bool EXT = false, bool MIS = false, int SRC = SRC_MEMORY>
-__global__ void __launch_bounds__(kBlock, RTMI_NEE_MIN_WAVES) rays_nee_kernel(ScenePtr scp, NeeParams np) {
+// VOL (rtmi_render_rays_vol*, rtmi_render_lit_vol*): THE VOLUME RULE of rtmi.h -- Isotropic vertices sample the lights too, and every shadow ray has a
+// stream of its own for the media it crosses.  Mixed-kind FP64 instantiations only: a world of spheres holds no medium.
+template <typename R, int VARIANT, bool EXT = false, bool MIS = false, int SRC = SRC_MEMORY, bool VOL = false>
+__global__ void __launch_bounds__(kBlock, VOL ? RTMI_VOL_MIN_WAVES : RTMI_NEE_MIN_WAVES) rays_nee_kernel(ScenePtr scp, NeeParams np) {
     static_assert(SRC == SRC_MEMORY || SRC == SRC_CAMERA, "the path kernels read their rays or build the frame's");
     static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the refill loop is per wave");
     SceneRef sc = *scp;
@@ -1932,13 +1958,14 @@ __global__ void __launch_bounds__(kBlock, RTMI_NEE_MIN_WAVES) rays_nee_kernel(Sc
         if (!__any(alive ? 1 : 0)) break;
         R best_t; int best_i;
         intersect_world<R, true, VARIANT, EXT, false, false, 0>(sc, lds, 0, 1, P, alive, tmin, tmax, best_t, best_i);
-        bool lamb = false;
+        bool lamb = false, iso = false; // (VOL) lamb: the vertex takes a light sample, Lambertian or Isotropic; iso: the latter
         double nx = 0.0, ny = 0.0, nz = 0.0;
         if (alive) {
             ++nseg;
             R emit[3];
             HitRec<R> h;
-            alive = shade_segment_nee<R, EXT>(sc, P, best_t, best_i, emit, h, lamb);
+            if constexpr (VOL) { alive = shade_segment_vol<R, EXT>(sc, P, best_t, best_i, emit, h, lamb, iso); lamb = lamb || iso; }
+            else alive = shade_segment_nee<R, EXT>(sc, P, best_t, best_i, emit, h, lamb);
             nx = (double)h.nx; ny = (double)h.ny; nz = (double)h.nz;
             if (!alive) { // step 6: a sampled light's emission was already counted at the previous vertex
                 double *out = rp.samples + (size_t)out_item * 3;
@@ -1956,7 +1983,7 @@ __global__ void __launch_bounds__(kBlock, RTMI_NEE_MIN_WAVES) rays_nee_kernel(Sc
             }
         }
         if (__any(lamb ? 1 : 0)) { // wave-uniform: all 64 lanes enter the disk rounds and the any-hit search
-            const int state = nee_vertex<R, VARIANT, EXT, MIS>(sc, lds, np.lights, lamb, P.key, seg, P, nx, ny, nz, slot, nullptr);
+            const int state = nee_vertex<R, VARIANT, EXT, MIS, VOL>(sc, lds, np.lights, lamb, P.key, seg, P, nx, ny, nz, slot, nullptr, iso);
             n_built += state == 1 || state == 2 ? 1u : 0u;
             n_occ += state == 2 ? 1u : 0u;
         }
@@ -1989,7 +2016,9 @@ struct NeeProbeParams {
     NeeLights lights;  // n == 0: no vertex takes a light sample
 };
 
-template <typename R, int VARIANT, bool EXT = false, bool MIS = false>
+// VOL (rtmi_probe_paths_vol): the rows are RTMI_VOL_REC doubles and out_end is the factor on the closing emission under either rule (the NEE rule's
+// 0.0 where it is dropped)
+template <typename R, int VARIANT, bool EXT = false, bool MIS = false, bool VOL = false>
 __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, NeeProbeParams pp) {
     static_assert(VARIANT >= SCAN_SGPR, "the loop is per wave, as rays_nee_kernel's");
     SceneRef sc = *scp;
@@ -2003,7 +2032,7 @@ __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, N
     Path<R> P;
     load_ray<R>(pp.rays + row * 7, P);
     seed_stream(P, alive ? pp.keys[k] : 0ull, pp.ctr0); P.depth = pp.depth;
-    constexpr int kRec = MIS ? RTMI_MIS_REC : RTMI_NEE_REC;
+    constexpr int kRec = VOL ? RTMI_VOL_REC : MIS ? RTMI_MIS_REC : RTMI_NEE_REC;
     double *log = pp.log ? pp.log + row * (size_t)pp.max_seg * kRec : nullptr;
     int nlog = 0, dropped = 0;
     double weight = 1.0; // (MIS) the factor on the closing emission
@@ -2016,14 +2045,15 @@ __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, N
     while (__any(alive ? 1 : 0)) {
         R best_t; int best_i;
         intersect_world<R, true, VARIANT, EXT, false, false, 0>(sc, lds, 0, 1, P, alive, tmin, tmax, best_t, best_i);
-        bool lamb = false;
+        bool lamb = false, iso = false;
         double nx = 0.0, ny = 0.0, nz = 0.0;
         double *rec = nullptr;
         if (alive) {
             ++nseg;
             R emit[3];
             HitRec<R> h;
-            alive = shade_segment_nee<R, EXT>(sc, P, best_t, best_i, emit, h, lamb);
+            if constexpr (VOL) { alive = shade_segment_vol<R, EXT>(sc, P, best_t, best_i, emit, h, lamb, iso); lamb = lamb || iso; }
+            else alive = shade_segment_nee<R, EXT>(sc, P, best_t, best_i, emit, h, lamb);
             lamb = lamb && pp.lights.n > 0;
             nx = (double)h.nx; ny = (double)h.ny; nz = (double)h.nz;
             if (log && best_i >= 0 && nlog < pp.max_seg) { // shade_segment's record (a miss logs none); [12..23] stay zeros unless the vertex takes a light sample
@@ -2045,12 +2075,13 @@ __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, N
                 } else {
                     const bool drop = sampled && best_i >= 0 && nee_sampled_light(pp.lights, best_i) >= 0;
                     dropped = drop ? 1 : 0;
+                    if constexpr (VOL) weight = drop ? 0.0 : 1.0;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) rgb[c] = slot[c * kBlock] + (drop ? 0.0 : (double)emit[c]);
                 }
             }
         }
-        if (__any(lamb ? 1 : 0)) nee_vertex<R, VARIANT, EXT, MIS>(sc, lds, pp.lights, lamb, P.key, seg, P, nx, ny, nz, slot, rec);
+        if (__any(lamb ? 1 : 0)) nee_vertex<R, VARIANT, EXT, MIS, VOL>(sc, lds, pp.lights, lamb, P.key, seg, P, nx, ny, nz, slot, rec, iso);
         sampled = lamb;
         ++seg;
     }
@@ -2058,7 +2089,7 @@ __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, N
         pp.out_rgb[3 * k] = rgb[0]; pp.out_rgb[3 * k + 1] = rgb[1]; pp.out_rgb[3 * k + 2] = rgb[2];
         if (pp.out_nseg) pp.out_nseg[k] = nseg;
         if (pp.out_end) {
-            if constexpr (MIS) static_cast<double *>(pp.out_end)[k] = weight;
+            if constexpr (MIS || VOL) static_cast<double *>(pp.out_end)[k] = weight;
             else static_cast<int *>(pp.out_end)[k] = dropped;
         }
         if (pp.out_nlog) pp.out_nlog[k] = nlog;
@@ -5829,10 +5860,11 @@ int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const 
 // call's behind the plain call's: check_nee_args, beside its table below), a host form's state, then the scene's device is current.  *work
 // false: nothing to trace, the entry returns RTMI_OK at once.
 struct NeeLightTable;
-int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work, int light_choice = 0);
+int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work, int light_choice = 0, int vol = -1);
 int rays_begin(rtmi_scene *s, int precision, int n_groups, int group, int g_first, int depth, const void *rays, const void *mean, const void *se,
                const double *host_state, bool *work, NeeLightTable *T = nullptr, int n_lights = 0, const int32_t *light_prims = nullptr,
-               int light_choice = 0, bool generated = false) { // generated: the kernel builds the rays (rtmi_render_lit*), `rays` is not looked at
+               int light_choice = 0, bool generated = false, // generated: the kernel builds the rays (rtmi_render_lit*), `rays` is not looked at
+               int vol = -1) {                               // vol >= 0: a call of the volume rule, vol its estimator argument
     *work = false;
     if (n_groups < 0 || group <= 0 || g_first < 0 || depth < 0)
         return fail(RTMI_E_ARG, "n_groups, g_first, depth must be >= 0 and group > 0 (got %d %d %d %d)", n_groups, g_first, depth, group);
@@ -5846,7 +5878,7 @@ int rays_begin(rtmi_scene *s, int precision, int n_groups, int group, int g_firs
     if (s->uses_perlin && !s->have_perlin) return fail(RTMI_E_STATE, "the scene holds a Perlin texture: call rtmi_scene_set_perlin first");
     if (s->max_image >= s->dev.n_images) return fail(RTMI_E_STATE, "the scene holds an ImageMap with index %d: call rtmi_scene_set_images first", s->max_image);
     *work = n_groups > 0;
-    int rc = T ? check_nee_args(s, n_groups, n_lights, light_prims, *T, work, light_choice) : RTMI_OK;
+    int rc = T ? check_nee_args(s, n_groups, n_lights, light_prims, *T, work, light_choice, vol) : RTMI_OK;
     if (rc || !*work) return rc;
     rc = check_state_counts(host_state, (size_t)n_groups, RTMI_RAYS_REC, 9, g_first, "group", "rays, g_first");
     if (rc) return rc;
@@ -6537,6 +6569,16 @@ struct ProbePathsMis {
     static constexpr bool wave_level = true;
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, true>; }
 };
+// THE VOLUME RULE's instantiations (rtmi_render_rays_vol*, rtmi_render_lit_vol*, rtmi_probe_paths_vol): VOL with the mixed-kind FP64 kernels, the only ones
+// that trace a medium or an Isotropic scatter.  A world of spheres runs its sibling's kernel, which is then the same rule (the entries see to the probe's rows).
+// A media scene outside RTMI_MEDIA_DESCENT is refused before any launch, so the media-sequence operands of the chooser all name the one kernel.
+template <bool MIS, int SRC> struct VolPass : NeePass {
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MIS, SRC, EXT>; }
+};
+template <bool MIS> struct ProbePathsVol {
+    static constexpr bool wave_level = true;
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MIS, EXT>; }
+};
 
 struct NeeLightTable { LightTable t; int prim[RTMI_DIRECT_MAX_LIGHTS]; };
 constexpr size_t kNeeLightBytes = kLightTableBytes + sizeof(int) * RTMI_DIRECT_MAX_LIGHTS;
@@ -6621,11 +6663,16 @@ int upload_mis_lights(rtmi_ctx *c, const MisLightTable &T, NeeLights &L, hipStre
 }
 
 // what both entries check behind rtmi_render_rays' own checks, in the header's order; *work: is there anything to trace?
-int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work, int light_choice) {
+int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work, int light_choice, int vol) {
     *work = false;
     if (light_prims && (n_lights < 0 || n_lights > RTMI_DIRECT_MAX_LIGHTS)) return fail(RTMI_E_ARG, "n_lights must be in [0, %d] (got %d)", RTMI_DIRECT_MAX_LIGHTS, n_lights);
+    if (vol >= 0 && vol != 1 && vol != 2) return fail(RTMI_E_ARG, "estimator must be 1 (the NEE rule) or 2 (the MIS rule) (got %d)", vol); // (the volume calls')
     if (light_choice != 0 && light_choice != 1) return fail(RTMI_E_ARG, "light_choice must be 0 (uniform) or 1 (by power) (got %d)", light_choice); // (the MIS calls')
     if (n_groups == 0) return RTMI_OK;
+    if (vol >= 0) { // the volume rule takes the media of a RTMI_MEDIA_DESCENT world; the list forms need MSEQ kernels this family does not have
+        if (s->dev.n_media > 0 && s->dev.media_seq != 0)
+            return fail(RTMI_E_UNSUPPORTED, "the scene holds a ConstantMedium in a Hitlist (media mode %d): the volume rule covers RTMI_MEDIA_DESCENT only", s->dev.media_seq);
+    } else
     if (s->dev.n_media > 0) return fail(RTMI_E_UNSUPPORTED, "the scene holds a ConstantMedium: shadow rays through media are not built");
     *work = true;
     return make_nee_lights(s, n_lights, light_prims, T);
@@ -6635,11 +6682,22 @@ int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *lig
 int nee_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
             const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st,
             const MisLightTable *M = nullptr, // M (then T is M->t): the MIS rule's kernels and table
-            const RaysFrame *frame = nullptr) { // frame: the SRC_CAMERA twins of the three families (rtmi_render_lit*)
+            const RaysFrame *frame = nullptr, // frame: the SRC_CAMERA twins of the three families (rtmi_render_lit*)
+            bool vol = false) {               // vol: the volume rule's instantiations of the two light-sampling families
     return with_real(precision, [&](auto r) {
         using R = decltype(r);
         auto mis_lights = [&](NeeParams &np, hipStream_t q) { return upload_mis_lights(s->ctx, *M, np.lights, q); };
         auto nee_lights = [&](NeeParams &np, hipStream_t q) { return upload_nee_lights(s->ctx, T, np.lights, q); };
+        if (vol && M && T.t.n > 0)
+            return frame ? render_rays_impl<R, VolPass<true, SRC_CAMERA>>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se,
+                                                                          d_out_rays, d_cnt, st, mis_lights, frame)
+                         : render_rays_impl<R, VolPass<true, SRC_MEMORY>>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se,
+                                                                          d_out_rays, d_cnt, st, mis_lights);
+        if (vol && T.t.n > 0)
+            return frame ? render_rays_impl<R, VolPass<false, SRC_CAMERA>>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se,
+                                                                           d_out_rays, d_cnt, st, nee_lights, frame)
+                         : render_rays_impl<R, VolPass<false, SRC_MEMORY>>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se,
+                                                                           d_out_rays, d_cnt, st, nee_lights);
         if (M && T.t.n > 0)
             return frame ? render_rays_impl<R, LitMisPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt,
                                                            st, mis_lights, frame)
@@ -6658,27 +6716,31 @@ int nee_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, 
     });
 }
 
-// The three entries of both families.  mis: the MIS rule with light_choice; else the NEE rule (light_choice is 0).
+// The three entries of both families.  mis: the MIS rule with light_choice; else the NEE rule (light_choice is 0).  vol >= 0: the volume rule's entries,
+// vol their estimator argument (mis is then vol == 2).
 int lit_rays_device(bool mis, rtmi_scene *s, int precision, int n_groups, int group, int g_first, const void *d_rays, const void *d_keys, u64 seed, unsigned ctr0,
                     int depth, int n_lights, const int32_t *light_prims, int light_choice, void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays,
-                    void *d_out_counters, void *stream) {
+                    void *d_out_counters, void *stream, int vol = -1) {
     MisLightTable M;
     NeeLightTable &T = M.t;
     bool work = false;
-    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr, nullptr, &work, &T, n_lights, light_prims, light_choice);
+    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr, nullptr, &work, &T, n_lights, light_prims, light_choice,
+                              false, vol);
     if (rc || !work) return rc;
     if (mis) make_mis_rows(M, light_choice);
     return nee_run(s, precision, n_groups, group, g_first, as<const double>(d_rays), as<const u64>(d_keys), seed, ctr0, depth, T, as<double>(d_state),
-                   as<double>(d_out_mean), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream), mis ? &M : nullptr);
+                   as<double>(d_out_mean), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream), mis ? &M : nullptr,
+                   nullptr, vol >= 0);
 }
 
 int lit_rays_host(bool mis, rtmi_scene *s, int precision, int n_groups, int group, int g_first, const double *rays, const uint64_t *keys, u64 seed, unsigned ctr0,
                   int depth, int n_lights, const int32_t *light_prims, int light_choice, double *state, double *out_mean, double *out_stderr, double *out_rays,
-                  uint64_t *out_counters) {
+                  uint64_t *out_counters, int vol = -1) {
     MisLightTable M;
     NeeLightTable &T = M.t;
     bool work = false;
-    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr, state, &work, &T, n_lights, light_prims, light_choice);
+    const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr, state, &work, &T, n_lights, light_prims, light_choice, false,
+                              vol);
     if (rc || !work) return rc;
     if (mis) make_mis_rows(M, light_choice);
     const size_t n = (size_t)n_groups * (size_t)group, ng = (size_t)n_groups;
@@ -6689,13 +6751,16 @@ int lit_rays_host(bool mis, rtmi_scene *s, int precision, int n_groups, int grou
     io.plane(&d_state, ng * RTMI_RAYS_REC, state != nullptr, g_first > 0 ? state : nullptr, state); // a first chunk (g_first = 0) reads no records
     io.out(&d_mean, 3 * ng, out_mean); io.out(&d_se, ng, out_stderr); io.work(&d_cnt, 4, out_counters); io.out(&d_out, 3 * n, out_rays);
     return host_run(io, [&](hipStream_t st) {
-        return nee_run(s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, T, d_state, d_mean, d_se, d_out, d_cnt, st, mis ? &M : nullptr);
+        return nee_run(s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, T, d_state, d_mean, d_se, d_out, d_cnt, st, mis ? &M : nullptr,
+                       nullptr, vol >= 0);
     });
 }
 
-// out_dropped (the NEE probe: int32 flags) or out_weight (the MIS probe: doubles), whichever the family writes per path
+// out_dropped (the NEE probe: int32 flags) or out_weight (the MIS probe: doubles), whichever the family writes per path.  vol >= 0: rtmi_probe_paths_vol,
+// vol its estimator argument (mis is then vol == 2): RTMI_VOL_REC rows and out_weight under either rule.
 int lit_probe(bool mis, rtmi_scene *s, int precision, int n, const double *rays, const uint64_t *keys, u64 ctr0, int depth, int n_lights, const int32_t *light_prims,
-              int light_choice, double *out_rgb, uint64_t *out_nseg, int32_t *out_dropped, double *out_weight, double *log, int max_seg, int32_t *out_nlog) {
+              int light_choice, double *out_rgb, uint64_t *out_nseg, int32_t *out_dropped, double *out_weight, double *log, int max_seg, int32_t *out_nlog,
+              int vol = -1) {
     int rc = probe_begin(s, precision, n);
     if (rc || n == 0) return rc;
     if (!rays || !keys || !out_rgb) return fail(RTMI_E_ARG, "NULL array");
@@ -6704,8 +6769,20 @@ int lit_probe(bool mis, rtmi_scene *s, int precision, int n, const double *rays,
     MisLightTable M;
     NeeLightTable &T = M.t;
     bool work = false;
-    rc = check_nee_args(s, n, n_lights, light_prims, T, &work, light_choice);
+    rc = check_nee_args(s, n, n_lights, light_prims, T, &work, light_choice, vol);
     if (rc) return rc;
+    if (vol >= 0 && !s->dev.has_ext) { // a world of spheres: no medium, no Isotropic scatter -- the sibling's probe is the rule; its rows are widened here
+        const int kSib = mis ? RTMI_MIS_REC : RTMI_NEE_REC;
+        std::vector<double> rows(log ? (size_t)n * max_seg * kSib : 0);
+        std::vector<int32_t> dropped(mis || !out_weight ? 0 : (size_t)n);
+        rc = lit_probe(mis, s, precision, n, rays, keys, ctr0, depth, n_lights, light_prims, light_choice, out_rgb, out_nseg, dropped.empty() ? nullptr : dropped.data(),
+                       mis ? out_weight : nullptr, log ? rows.data() : nullptr, max_seg, out_nlog);
+        if (rc) return rc;
+        for (size_t k = 0; k < dropped.size(); ++k) out_weight[k] = dropped[k] ? 0.0 : 1.0;
+        for (size_t v = 0; log && v < (size_t)n * max_seg; ++v)
+            for (int c = 0; c < RTMI_VOL_REC; ++c) log[v * RTMI_VOL_REC + c] = c < kSib ? rows[v * kSib + c] : 0.0;
+        return RTMI_OK;
+    }
     if (mis) make_mis_rows(M, light_choice);
     rtmi_ctx *c = s->ctx;
     HostIo io(c);
@@ -6713,19 +6790,21 @@ int lit_probe(bool mis, rtmi_scene *s, int precision, int n, const double *rays,
     double *d_rays, *d_rgb, *d_log, *d_weight;
     u64 *d_keys, *d_nseg;
     int *d_dropped, *d_nlog;
-    const size_t log_words = log ? (size_t)n * max_seg * (mis ? RTMI_MIS_REC : RTMI_NEE_REC) : 0;
+    const size_t log_words = log ? (size_t)n * max_seg * (vol >= 0 ? RTMI_VOL_REC : mis ? RTMI_MIS_REC : RTMI_NEE_REC) : 0;
     io.in(&d_rays, (size_t)n * 7, rays); io.in(&d_keys, (size_t)n, keys); io.out(&d_rgb, (size_t)n * 3, out_rgb);
     io.out(&d_nseg, (size_t)n, out_nseg); io.out(&d_dropped, (size_t)n, out_dropped); io.out(&d_weight, (size_t)n, out_weight); io.out(&d_nlog, (size_t)n, out_nlog);
     io.out(&d_log, log_words, log);
     pp.n = n; pp.ctr0 = (unsigned)ctr0; pp.depth = depth; pp.max_seg = max_seg;
     return probe_run(io, n, [&](hipStream_t st, dim3 grid) {
         pp.rays = d_rays; pp.keys = d_keys; pp.out_rgb = d_rgb; pp.out_nseg = d_nseg; pp.out_nlog = d_nlog; pp.log = d_log;
-        pp.out_end = mis ? static_cast<void *>(d_weight) : static_cast<void *>(d_dropped);
+        pp.out_end = mis || vol >= 0 ? static_cast<void *>(d_weight) : static_cast<void *>(d_dropped);
         if ((mis ? upload_mis_lights(c, M, pp.lights, st) : upload_nee_lights(c, T, pp.lights, st)) != RTMI_OK) return; // (probe_run reports a launch error)
         if (d_log && hipMemsetAsync(d_log, 0, log_words * sizeof(double), st) != hipSuccess) return;
         auto run = [&](auto kern, size_t lds, int, int) { hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, s->d_dev, pp); };
         with_real(precision, [&](auto r) {
-            if (mis) with_probe_kernel<ProbePathsMis, decltype(r)>(s, run);
+            if (vol >= 0 && mis) with_probe_kernel<ProbePathsVol<true>, decltype(r)>(s, run);
+            else if (vol >= 0) with_probe_kernel<ProbePathsVol<false>, decltype(r)>(s, run);
+            else if (mis) with_probe_kernel<ProbePathsMis, decltype(r)>(s, run);
             else with_probe_kernel<ProbePathsNee, decltype(r)>(s, run);
         });
     });
@@ -6780,8 +6859,10 @@ RTMI_EXPORT int rtmi_probe_paths_mis(rtmi_scene *s, int32_t precision, int32_t n
 // read, a refilled lane builds start_sample's.  Everything behind the checks is nee_run's.
 namespace {
 // what both forms check first, in the header's order; *M: estimators 1 and 2's light table (estimator 0: no light); *work false: nothing to do
+// vol: rtmi_render_lit_vol* -- the light-sampling calls' checks run for every estimator, the volume rule's own (estimators 1 and 2 only) behind the list's length
 int lit_frame_begin(rtmi_scene *s, int precision, int nx, int ny, int s_first, int s_count, int depth, int estimator, int n_lights, const int32_t *light_prims,
-                    int light_choice, const double *host_state, const void *out_linear, const void *out_stderr, MisLightTable &M, RaysFrame &F, bool *work) {
+                    int light_choice, const double *host_state, const void *out_linear, const void *out_stderr, MisLightTable &M, RaysFrame &F, bool *work,
+                    bool vol = false) {
     *work = false;
     if (nx <= 0 || ny <= 0 || s_count <= 0 || s_first < 0 || depth < 0)
         return fail(RTMI_E_ARG, "nx, ny, s_count must be > 0 and s_first, depth >= 0 (got %d %d %d %d %d)", nx, ny, s_count, s_first, depth);
@@ -6791,8 +6872,8 @@ int lit_frame_begin(rtmi_scene *s, int precision, int nx, int ny, int s_first, i
     if (!out_linear || !out_stderr) return fail(RTMI_E_ARG, "out_linear / out_stderr is NULL");
     if (estimator < 0 || estimator > 2) return fail(RTMI_E_ARG, "estimator must be 0 (plain), 1 (the NEE rule) or 2 (the MIS rule) (got %d)", estimator);
     M.t.t.n = 0;
-    const int rc = rays_begin(s, precision, nx * ny, s_count, s_first, depth, nullptr, out_linear, out_stderr, host_state, work, estimator ? &M.t : nullptr,
-                              n_lights, light_prims, estimator == 2 ? light_choice : 0, true);
+    const int rc = rays_begin(s, precision, nx * ny, s_count, s_first, depth, nullptr, out_linear, out_stderr, host_state, work, estimator || vol ? &M.t : nullptr,
+                              n_lights, light_prims, estimator == 2 ? light_choice : 0, true, vol ? estimator : -1);
     if (rc || !*work) return rc;
     if (estimator == 2) make_mis_rows(M, light_choice);
     F.nx = nx; F.ny = ny; F.fixed_rays = camera_fixed_rays(s->dev.cam_kind, s->dev.cam_fixed_origin, s->dev.cam);
@@ -6800,9 +6881,10 @@ int lit_frame_begin(rtmi_scene *s, int precision, int nx, int ny, int s_first, i
 }
 
 int lit_frame_run(rtmi_scene *s, int precision, int nx, int ny, int s_first, int s_count, int depth, u64 seed, int estimator, const MisLightTable &M,
-                  const RaysFrame &F, double *d_state, double *d_lin, unsigned char *d_q, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st) {
+                  const RaysFrame &F, double *d_state, double *d_lin, unsigned char *d_q, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st,
+                  bool vol = false) {
     const int rc = nee_run(s, precision, nx * ny, s_count, s_first, nullptr, nullptr, seed, 0u, depth, M.t, d_state, d_lin, d_se, d_out_rays, d_cnt, st,
-                           estimator == 2 ? &M : nullptr, &F);
+                           estimator == 2 ? &M : nullptr, &F, vol);
     if (rc || !d_q) return rc;
     const size_t n = (size_t)nx * (size_t)ny * 3;
     hipLaunchKernelGGL(lit_quantise_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_lin, n, d_q);
@@ -6811,29 +6893,30 @@ int lit_frame_run(rtmi_scene *s, int precision, int nx, int ny, int s_first, int
 }
 } // namespace
 
-RTMI_EXPORT int rtmi_render_lit_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
-                                       int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, void *d_state,
-                                       void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera, void *d_out_counters,
-                                       void *stream) {
+namespace {
+// both forms of rtmi_render_lit* and, with vol, of rtmi_render_lit_vol*
+int lit_frame_device(bool vol, rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                     int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, void *d_state, void *d_out_linear, void *d_out_rgb8,
+                     void *d_out_stderr, void *d_out_rays, void *d_out_camera, void *d_out_counters, void *stream) {
     MisLightTable M;
     RaysFrame F;
     bool work = false;
     const int rc = lit_frame_begin(s, precision, nx, ny, s_first, s_count, depth, estimator, n_lights, light_prims, light_choice, nullptr, d_out_linear,
-                                   d_out_stderr, M, F, &work);
+                                   d_out_stderr, M, F, &work, vol);
     if (rc || !work) return rc;
     F.out_camera = as<double>(d_out_camera);
     return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, as<double>(d_state), as<double>(d_out_linear),
-                         as<unsigned char>(d_out_rgb8), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream));
+                         as<unsigned char>(d_out_rgb8), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream), vol);
 }
 
-RTMI_EXPORT int rtmi_render_lit(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
-                                int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *state, double *out_linear,
-                                uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera, uint64_t *out_counters) {
+int lit_frame_host(bool vol, rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                   int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *state, double *out_linear,
+                   uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera, uint64_t *out_counters) {
     MisLightTable M;
     RaysFrame F;
     bool work = false;
     const int rc = lit_frame_begin(s, precision, nx, ny, s_first, s_count, depth, estimator, n_lights, light_prims, light_choice, state, out_linear, out_stderr,
-                                   M, F, &work);
+                                   M, F, &work, vol);
     if (rc || !work) return rc;
     const size_t ng = (size_t)nx * (size_t)ny, n = ng * (size_t)s_count;
     HostIo io(s->ctx);
@@ -6845,6 +6928,62 @@ RTMI_EXPORT int rtmi_render_lit(rtmi_scene *s, int32_t precision, int32_t nx, in
     io.out(&d_out, 3 * n, out_rays); io.out(&d_cam, 8 * n, out_camera);
     return host_run(io, [&](hipStream_t st) {
         F.out_camera = d_cam;
-        return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, d_state, d_lin, d_q, d_se, d_out, d_cnt, st);
+        return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, d_state, d_lin, d_q, d_se, d_out, d_cnt, st, vol);
     });
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_lit_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                       int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, void *d_state,
+                                       void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera, void *d_out_counters,
+                                       void *stream) {
+    return lit_frame_device(false, s, precision, nx, ny, s_first, s_count, depth, seed, estimator, n_lights, light_prims, light_choice, d_state, d_out_linear,
+                            d_out_rgb8, d_out_stderr, d_out_rays, d_out_camera, d_out_counters, stream);
+}
+
+RTMI_EXPORT int rtmi_render_lit(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *state, double *out_linear,
+                                uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera, uint64_t *out_counters) {
+    return lit_frame_host(false, s, precision, nx, ny, s_first, s_count, depth, seed, estimator, n_lights, light_prims, light_choice, state, out_linear, out_rgb8,
+                          out_stderr, out_rays, out_camera, out_counters);
+}
+
+// ---- light-sampled paths and frames through participating media (rtmi_render_rays_vol*, rtmi_probe_paths_vol, rtmi_render_lit_vol*): THE VOLUME RULE ------
+// The siblings' entries with the VOL instantiations of their kernels.  estimator 1: the NEE rule (light_choice is not looked at), 2: the MIS rule.
+RTMI_EXPORT int rtmi_render_rays_vol_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const void *d_rays,
+                                            const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t estimator, int32_t n_lights,
+                                            const int32_t *light_prims, int32_t light_choice, void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays,
+                                            void *d_out_counters, void *stream) {
+    return lit_rays_device(estimator == 2, s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, n_lights, light_prims,
+                           estimator == 2 ? light_choice : 0, d_state, d_out_mean, d_out_stderr, d_out_rays, d_out_counters, stream, estimator < 0 ? 0 : estimator);
+}
+
+RTMI_EXPORT int rtmi_render_rays_vol(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const double *rays,
+                                     const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t estimator, int32_t n_lights,
+                                     const int32_t *light_prims, int32_t light_choice, double *state, double *out_mean, double *out_stderr, double *out_rays,
+                                     uint64_t *out_counters) {
+    return lit_rays_host(estimator == 2, s, precision, n_groups, group, g_first, rays, keys, seed, ctr0, depth, n_lights, light_prims,
+                         estimator == 2 ? light_choice : 0, state, out_mean, out_stderr, out_rays, out_counters, estimator < 0 ? 0 : estimator);
+}
+
+RTMI_EXPORT int rtmi_probe_paths_vol(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
+                                     int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *out_rgb, uint64_t *out_nseg,
+                                     double *out_weight, double *log, int32_t max_seg, int32_t *out_nlog) {
+    return lit_probe(estimator == 2, s, precision, n, rays, keys, ctr0, depth, n_lights, light_prims, estimator == 2 ? light_choice : 0, out_rgb, out_nseg, nullptr,
+                     out_weight, log, max_seg, out_nlog, estimator < 0 ? 0 : estimator);
+}
+
+RTMI_EXPORT int rtmi_render_lit_vol_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth,
+                                           uint64_t seed, int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, void *d_state,
+                                           void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera, void *d_out_counters,
+                                           void *stream) {
+    return lit_frame_device(true, s, precision, nx, ny, s_first, s_count, depth, seed, estimator, n_lights, light_prims, light_choice, d_state, d_out_linear,
+                            d_out_rgb8, d_out_stderr, d_out_rays, d_out_camera, d_out_counters, stream);
+}
+
+RTMI_EXPORT int rtmi_render_lit_vol(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                    int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *state, double *out_linear,
+                                    uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera, uint64_t *out_counters) {
+    return lit_frame_host(true, s, precision, nx, ny, s_first, s_count, depth, seed, estimator, n_lights, light_prims, light_choice, state, out_linear, out_rgb8,
+                          out_stderr, out_rays, out_camera, out_counters);
 }

@@ -2584,4 +2584,13 @@ __device__ inline bool shade_segment_nee(SceneRef sc, Path<R> &P, R t, int orig,
     return scat;
 }
 
+// shade_segment_nee for the paths that also sample lights inside participating media (THE VOLUME RULE): the same call, and whether the vertex scattered
+// as RTMI_MAT_ISOTROPIC -- a ConstantMedium's phase function.  P.time is then already the scattered ray's (the hit's t, shader.clj:136).
+template <typename R, bool EXT = false>
+__device__ inline bool shade_segment_vol(SceneRef sc, Path<R> &P, R t, int orig, R *emit, HitRec<R> &h, bool &lamb, bool &iso) {
+    const bool scat = shade_segment_nee<R, EXT>(sc, P, t, orig, emit, h, lamb);
+    iso = scat && sc.mat_kind[h.mat] == RTMI_MAT_ISOTROPIC;
+    return scat;
+}
+
 } // namespace rtmi
