@@ -1001,6 +1001,100 @@
     (check (.invokeInt (cfn "rtmi_adaptive_retire_device") (object-array [ctx (int nx) (int ny) d-noise (double eps) out stream])))
     (aget out 0)))
 
+(defn tiles-retire
+  "The stateless adaptive-retire (rtmi_tiles_retire): of the 8x8 tiles listed in `tiles` (global indices, row-major over the frame's tiles) those
+  with a pixel inside the image that fails noise <= eps (NaN and +inf fail), in the list's order, as a vector.  `noise` holds [ny][nx] doubles of the
+  whole frame, row 0 = top -- :stderr of render-lit-tiles or of `denoise` as it is.  No frame of context `ctx` is read or changed."
+  [ctx nx ny noise eps tiles]
+  (let [m   (double-array noise)
+        tin (int-array tiles)
+        out (int-array (max 1 (count tiles)))
+        n   (int-array 1)]
+    (check (call-int "rtmi_tiles_retire" ctx (int nx) (int ny) m (double eps) (int (count tiles)) tin out n))
+    (vec (take (aget n 0) out))))
+
+(defn render-lit-tiles
+  "render-lit / render-lit-vol over a list of 8x8 tiles (rtmi_render_lit_tiles): samples [s-first, s-first + ns) of the pixels of the tiles in
+  `tiles` (strictly ascending global tile indices, rtmi_adaptive_active_tiles' numbering) and of no other pixel.  `frame` = {:linear :rgb8 :stderr
+  :state} holds the whole frame's arrays (double-array [ny * nx][3], byte-array [ny * nx][3], double-array [ny * nx], double-array [nx * ny][10]) and
+  is written IN PLACE: the listed pixels take the fold's values, every other element keeps what it held; nil starts a frame of zeros.  :volume true
+  runs the volume rule (estimator 1 or 2).  Returns {:linear :rgb8 :stderr :state (the frame's arrays), :rays double-array [n-tiles * 64 * ns][3] and
+  :camera double-array [...][8] in THE TILE ORDER of rtmi.h (sample s of local pixel l of entry k at row (+ (* (+ (* k 64) l) ns) s); zeros where the
+  pixel lies outside the image), :segments, :total-rays, :shadow-rays, :shadow-rays-occluded} of this call alone."
+  [scene nx ny ns lights tiles frame & {:keys [estimator light-choice volume seed depth device precision s-first]
+                                        :or {estimator 2 light-choice 0 volume false seed 0x5eed0002 depth 50 device 0 precision 0 s-first 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        npx  (* nx ny)
+        nt   (count tiles)
+        n    (* nt 64 ns)
+        lp   (int-array (if (seq lights) lights [0]))
+        nl   (count lights)
+        tl   (int-array (if (seq tiles) tiles [0]))
+        st   (double-array (or (:state frame) (* 10 npx)))
+        lin  (double-array (or (:linear frame) (* 3 npx)))
+        rgb8 (byte-array (or (:rgb8 frame) (* 3 npx)))
+        err  (double-array (or (:stderr frame) npx))
+        out  (double-array (max 1 (* 3 n)))
+        cam  (double-array (max 1 (* 8 n)))
+        cnt  (long-array 4)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_lit_tiles" scn (int precision) (int nx) (int ny) (int s-first) (int ns) (int depth) (long seed) (int estimator)
+                           (int nl) lp (int light-choice) (int (if volume 1 0)) (int nt) tl st lin rgb8 err out cam cnt))
+          {:linear lin :rgb8 rgb8 :stderr err :state st :rays out :camera cam :segments (aget cnt 0) :total-rays (aget cnt 1)
+           :shadow-rays (aget cnt 2) :shadow-rays-occluded (aget cnt 3)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
+(defn render-lit-adaptive
+  "A light-sampled frame of scene {:camera :world} refined adaptively on GPU `device`: every 8x8 tile listed, then rounds of rtmi_render_lit_tiles
+  (`first-round` samples, default `chunk`, then `chunk`), each followed by rtmi_tiles_retire of the tiles whose standard error is <= eps everywhere,
+  until no tile is listed or `ns` is reached.  The list is compacted in place.  After each round (on-round m), m = {:samples k :linear :rgb8 :stderr
+  :state :rays :camera (the round's rows in THE TILE ORDER; all refilled by the next round) :active-tiles :total-tiles :segments :total-rays :shadow-rays :shadow-rays-occluded (summed over the rounds)};
+  on-round returning :stop ends the render early.  A pixel whose tile took n samples equals render-lit with ns = n there bit for bit; the samples a
+  pixel holds are slot 9 of its :state record.  Returns the last m."
+  [scene nx ny ns chunk eps lights on-round & {:keys [first-round estimator light-choice volume seed depth device precision]
+                                               :or {estimator 2 light-choice 0 volume false seed 0x5eed0002 depth 50 device 0 precision 0}}]
+  (let [f     (flatten-scene scene)
+        ctx   (PointerByReference.)
+        npx   (* nx ny)
+        total (* (quot (+ nx 7) 8) (quot (+ ny 7) 8))
+        lp    (int-array (if (seq lights) lights [0]))
+        nl    (count lights)
+        tl    (int-array (range total))
+        st    (double-array (* 10 npx))
+        lin   (double-array (* 3 npx))
+        rgb8  (byte-array (* 3 npx))
+        err   (double-array npx)
+        cnt   (long-array 4)
+        sums  (long-array 4)
+        left  (int-array 1)
+        head  (or first-round chunk)
+        rows  (* total 64 (max head chunk))
+        out   (double-array (* 3 rows))
+        cam   (double-array (* 8 rows))]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (loop [k 0 nt total]
+            (let [n (min (if (zero? k) head chunk) (- ns k))]
+              (check (call-int "rtmi_render_lit_tiles" scn (int precision) (int nx) (int ny) (int k) (int n) (int depth) (long seed) (int estimator)
+                               (int nl) lp (int light-choice) (int (if volume 1 0)) (int nt) tl st lin rgb8 err out cam cnt))
+              (check (call-int "rtmi_tiles_retire" (.getValue ctx) (int nx) (int ny) err (double eps) (int nt) tl tl left))
+              (dotimes [i 4] (aset sums i (+ (aget sums i) (aget cnt i))))
+              (let [k' (+ k n)
+                    m  {:samples k' :linear lin :rgb8 rgb8 :stderr err :state st :rays out :camera cam :active-tiles (aget left 0) :total-tiles total
+                        :segments (aget sums 0) :total-rays (aget sums 1) :shadow-rays (aget sums 2) :shadow-rays-occluded (aget sums 3)}]
+                (if (and (not= :stop (on-round m)) (< k' ns) (pos? (aget left 0)))
+                  (recur k' (aget left 0))
+                  m))))
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn render-adaptive-denoised
   "Render scene {:camera :world} adaptively on GPU `device` for a frame that is denoised anyway: the feature buffers once (:feature-samples,
   default 4), then rounds as in render-adaptive; per round rtmi_render_adaptive with the raw rule at eps 0 (only tiles whose samples are all

@@ -987,6 +987,61 @@ int rtmi_render_lit_vol_device(rtmi_scene *scene, int32_t precision, int32_t nx,
                                void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera,
                                void *d_out_counters, void *stream);
 
+/* ---- light-sampled frames over a caller's list of 8x8 tiles: the primitive of an adaptive frame whose state the caller holds ----
+ * rtmi_render_lit_tiles*: rtmi_render_lit's arguments, then volume, n_tiles and tiles in front of the state.  volume 0: rtmi_render_lit's rules, estimators
+ *   0..2; volume 1: rtmi_render_lit_vol's, estimators 1..2.  tiles: n_tiles int32 -- a host array in the host form, a device array in the device form --
+ *   of tile indices in rtmi_adaptive_active_tiles' numbering: tile t is row-major over T = ceil(nx/8) x ceil(ny/8) tiles, its local pixel l = row * 8 +
+ *   column is pixel (x, y) = ((t % ceil(nx/8)) * 8 + l % 8, (t / ceil(nx/8)) * 8 + l / 8), row 0 at the top.  The call adds samples
+ *   [s_first, s_first + s_count) to the pixels of the listed tiles and to nothing else.
+ * THE TILE ORDER.  Row r of the call (0 <= r < n_tiles * 64 * s_count) is sample s = s_first + r % s_count of local pixel l = (r / s_count) % 64 of tile
+ *   tiles[r / (64 * s_count)].  From that (x, y, s) on everything is THE FRAME RULE's steps 1 - 5 unchanged: j = ny - 1 - y, the key
+ *   rtmi_sample_key(seed, j * nx + x, s), the jitter, the lens, the stream.  A row whose pixel lies outside the image (x >= nx or y >= ny: a partial tile's)
+ *   builds no ray, traces nothing and counts nothing.
+ *   state, out_linear, out_rgb8 and out_stderr keep the whole frame's layouts -- [nx*ny][RTMI_RAYS_REC], [ny][nx][3], [ny][nx][3], [ny][nx] -- and are
+ *   in/out: the elements of the listed tiles' pixels inside the image are written with the fold's values (the state's records read first when s_first > 0,
+ *   the 8-bit values quantised from the means just written), and every other element is neither written nor read by the device (the host form stages the
+ *   whole planes both ways: those elements come back with the bits they went up with).  out_rays and out_camera (each may be NULL) are
+ *   [n_tiles*64*s_count][3] and [...][8] in THE TILE ORDER, the rows of pixels outside the image +0.0; with out_rays the call is one pass.
+ *   out_counters (may be NULL): rtmi_render_lit's four values for this call alone; rays = the listed pixels inside the image * s_count.
+ *   For every listed pixel and every estimator the mean, the 8-bit value, the standard error and the state record are bit-identical to rtmi_render_lit
+ *   (rtmi_render_lit_vol) of the whole frame with the same s_first, s_count and state; with all T tiles listed in ascending order every output and counter
+ *   of the frame call is reproduced (out_rays and out_camera row by row through THE TILE ORDER).  Under estimator 0 the segment counter over a run of
+ *   calls is rtmi_render_adaptive's over the same tiles and samples.  Option "workspace_bytes" may split the call into passes of whole tiles: no bit changes.
+ * Errors, in this order: rtmi_render_lit's argument checks up to and including the estimator's range, the ray limit taken on n_tiles * 64 * s_count (and
+ * nx * ny <= 2^31 - 64); volume outside {0, 1}: RTMI_E_ARG; n_tiles < 0, or tiles NULL with n_tiles > 0: RTMI_E_ARG; host form only: an entry outside
+ * [0, T) or a list that is not strictly ascending: RTMI_E_ARG; then the sibling's checks from the scene handle on (with volume 1 the volume rule's: the
+ * estimator in {1, 2}, the media mode) and its light checks; host form with a state and s_first > 0: a listed pixel inside the image whose count is not
+ * s_first: RTMI_E_STATE.  n_tiles == 0 succeeds behind the argument checks and launches nothing.  A failed call launches nothing and writes nothing.
+ * The device form cannot read its list back: there an entry outside [0, T) holds no pixel -- its rows build no ray and nothing of it is written, in the trace
+ * kernel and in the fold alike, out_rays and out_camera included -- and duplicates and order are the caller's contract (a duplicated tile is folded twice,
+ * in no defined order).  The call touches neither the context's progressive or adaptive frame nor the scene's revision. */
+/* host buffers; synchronous */
+int rtmi_render_lit_tiles(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                          int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice,
+                          int32_t volume, int32_t n_tiles, const int32_t *tiles,
+                          double *state, double *out_linear, uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera,
+                          uint64_t *out_counters);
+/* every d_ pointer a device pointer, d_tiles among them (light_prims stays a host array); asynchronous on `stream` with rtmi_render_device's stream semantics */
+int rtmi_render_lit_tiles_device(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                 int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice,
+                                 int32_t volume, int32_t n_tiles, const void *d_tiles,
+                                 void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera,
+                                 void *d_out_counters, void *stream);
+
+/* rtmi_tiles_retire*: the stateless rtmi_adaptive_retire -- the decision of that call on a list the caller holds; no frame of the context is read or changed.
+ *   noise: [ny][nx] doubles of the whole frame, row 0 at the top: rtmi_render_lit_tiles' out_stderr or rtmi_denoise's filtered error as it is.  A listed tile
+ *   SURVIVES if any of its pixels inside the image fails noise <= eps, the comparison written exactly so: NaN and +inf fail, -inf passes (a pixel of one
+ *   sample, whose standard error is +inf, keeps its tile).  The survivors go to tiles_out in the order of tiles_in, *out_count (a host int32 in both forms) is
+ *   their number; tiles_out holds n_tiles entries, may be tiles_in itself, and its entries from *out_count on keep what they held.
+ * Errors, all reported before the handle is examined: nx or ny <= 0, noise NULL, eps negative, NaN or infinite: RTMI_E_ARG; n_tiles < 0, tiles_in or
+ * tiles_out NULL with n_tiles > 0, out_count NULL: RTMI_E_ARG; host form only: an entry outside [0, T): RTMI_E_ARG.  Then the handle: RTMI_E_STATE.
+ * n_tiles == 0 sets *out_count = 0 and launches nothing.  The device form synchronises `stream` once, as rtmi_adaptive_retire_device does, and queues the
+ * copy of the survivors into d_tiles_out behind it, in stream order; there an entry outside [0, T) reads no element of the map outside the image. */
+int rtmi_tiles_retire(rtmi_ctx *ctx, int32_t nx, int32_t ny, const double *noise, double eps, int32_t n_tiles, const int32_t *tiles_in, int32_t *tiles_out,
+                      int32_t *out_count);
+int rtmi_tiles_retire_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, const void *d_noise, double eps, int32_t n_tiles, const void *d_tiles_in,
+                             void *d_tiles_out, int32_t *out_count, void *stream);
+
 /* After the gather: d_gathered[r][k][64][3] (r < world, k < tiles_per_rank, rank r's k-th tile is global
  * tile r + k*world) -> dense row-major frame (doubles, may be NULL) + 8-bit frame (may be NULL). */
 int rtmi_assemble_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t world, int32_t tiles_per_rank,

@@ -46,6 +46,7 @@ SYMBOLS = [
     "rtmi_render_rays_mis", "rtmi_render_rays_mis_device", "rtmi_probe_paths_mis",
     "rtmi_render_lit", "rtmi_render_lit_device",
     "rtmi_render_rays_vol", "rtmi_render_rays_vol_device", "rtmi_probe_paths_vol", "rtmi_render_lit_vol", "rtmi_render_lit_vol_device",
+    "rtmi_render_lit_tiles", "rtmi_render_lit_tiles_device", "rtmi_tiles_retire", "rtmi_tiles_retire_device",
 ]
 
 F64, F32 = 0, 1
@@ -199,6 +200,10 @@ def lib():
     L.rtmi_probe_paths_vol.argtypes = [vp, i32, i32, vp, vp, u64, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp]
     L.rtmi_render_lit_vol.argtypes = L.rtmi_render_lit.argtypes
     L.rtmi_render_lit_vol_device.argtypes = L.rtmi_render_lit_device.argtypes
+    L.rtmi_render_lit_tiles.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rtmi_render_lit_tiles_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rtmi_tiles_retire.argtypes = [vp, i32, i32, vp, dbl, i32, vp, vp, C.POINTER(i32)]
+    L.rtmi_tiles_retire_device.argtypes = [vp, i32, i32, vp, dbl, i32, vp, vp, C.POINTER(i32), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

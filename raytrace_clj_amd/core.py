@@ -133,6 +133,26 @@ class Context:
         check(_ffi.lib().rtmi_adaptive_retire_device(self.handle, nx, ny, ptr(noise), float(eps), C.byref(n), ptr(stream)))
         return n.value
 
+    def tiles_retire(self, noise, eps, tiles):
+        """The stateless adaptive_retire (rtmi_tiles_retire): of the listed 8x8 tiles (global indices, row-major over the frame's tiles) those
+        with a pixel inside the image that fails noise <= eps (NaN and +inf fail), in the list's order -> int32 array.  noise: [ny, nx] float64
+        of the whole frame -- render_lit_tiles' stderr or denoise's as it is.  No frame of the context is read or changed."""
+        m = np.ascontiguousarray(noise, np.float64)
+        if m.ndim != 2:
+            raise ValueError("noise must be [ny, nx]")
+        tiles = np.ascontiguousarray(tiles, np.int32).reshape(-1)
+        out, n = np.zeros(max(len(tiles), 1), np.int32), C.c_int32()
+        check(_ffi.lib().rtmi_tiles_retire(self.handle, m.shape[1], m.shape[0], ptr(m), float(eps), len(tiles), ptr(tiles), ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def tiles_retire_device(self, nx, ny, noise, eps, n_tiles, tiles_in, tiles_out=None, stream=None):
+        """tiles_retire on HBM-resident buffers (torch tensors or raw device pointers; render_device's stream semantics; synchronises the stream
+        once: the host reads the number of survivors) -> that number; the survivors are the first entries of tiles_out (None: of tiles_in itself)"""
+        n = C.c_int32()
+        check(_ffi.lib().rtmi_tiles_retire_device(self.handle, int(nx), int(ny), ptr(noise), float(eps), int(n_tiles), ptr(tiles_in),
+                                                  ptr(tiles_in if tiles_out is None else tiles_out), C.byref(n), ptr(stream)))
+        return n.value
+
     # ---- the edge-aware denoiser: a pure image operation (rtmi_denoise*) ---------------------------------------------------------
     def denoise(self, linear, stderr=None, features=None, iterations=DENOISE_ITERATIONS, sigma_c=DENOISE_SIGMA_C, sigma_n=DENOISE_SIGMA_N,
                 sigma_a=DENOISE_SIGMA_A, sigma_d=DENOISE_SIGMA_D):
@@ -867,6 +887,100 @@ class DeviceScene:
         check(_ffi.lib().rtmi_render_lit_device(self.handle, _PRECISION[precision], int(nx), int(ny), int(s_first), int(s_count), int(depth), int(seed), est,
                                                 n_listed, ptr(lights), self._light_choice(light_choice), ptr(state), ptr(out_linear), ptr(out_rgb8),
                                                 ptr(out_stderr), ptr(out_rays), ptr(out_camera), ptr(out_counters), ptr(stream)))
+
+    # ---- light-sampled frames over a caller's list of 8x8 tiles, and the adaptive loop on top (THE TILE ORDER of include/rtmi.h) --------------
+    def _tiles_estimator(self, estimator, volume):
+        return self._vol_estimator(estimator) if volume else self._lit_estimator(estimator)
+
+    def render_lit_tiles(self, nx, ny, s_first, s_count, tiles, linear, rgb8, stderr, state=None, estimator="mis", volume=False, lights=None,
+                         light_choice=0, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", return_rays=False, return_camera=False):
+        """rtmi_render_lit_tiles: samples [s_first, s_first + s_count) of the pixels of the listed tiles (int32, strictly ascending global tile
+        indices) folded IN PLACE into the caller's whole-frame arrays linear [ny, nx, 3] float64, rgb8 [ny, nx, 3] uint8 (or None), stderr
+        [ny, nx] float64 and state [nx * ny, RAYS_REC] (or None); no other element changes.  volume: the volume rule (render_lit_vol's).
+        -> (counters[, rays' radiance [len(tiles) * 64, s_count, 3]][, camera [len(tiles) * 64, s_count, 8]]) in THE TILE ORDER, the rows of
+        pixels outside the image zeros."""
+        tiles = np.ascontiguousarray(tiles, np.int32).reshape(-1)
+        for name, a, shape, dt in (("linear", linear, (ny, nx, 3), np.float64), ("rgb8", rgb8, (ny, nx, 3), np.uint8),
+                                   ("stderr", stderr, (ny, nx), np.float64), ("state", state, (nx * ny, _ffi.RAYS_REC), np.float64)):
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError("%s must be a contiguous %s array of shape %r: it is written in place" % (name, np.dtype(dt).name, shape))
+        est = self._tiles_estimator(estimator, volume)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        cnt = np.zeros(4, np.uint64)
+        rays = np.zeros((len(tiles) * 64, int(s_count), 3), np.float64) if return_rays else None
+        cam = np.zeros((len(tiles) * 64, int(s_count), 8), np.float64) if return_camera else None
+        check(_ffi.lib().rtmi_render_lit_tiles(self.handle, _PRECISION[precision], int(nx), int(ny), int(s_first), int(s_count), int(depth), int(seed), est,
+                                               n_listed, ptr(lights), self._light_choice(light_choice), int(bool(volume)), len(tiles), ptr(tiles),
+                                               ptr(state), ptr(linear), ptr(rgb8), ptr(stderr), ptr(rays), ptr(cam), ptr(cnt)))
+        return (cnt,) + ((rays,) if return_rays else ()) + ((cam,) if return_camera else ())
+
+    def render_lit_tiles_device(self, nx, ny, s_first, s_count, n_tiles, tiles, out_linear, out_stderr, out_rgb8=None, estimator="mis", volume=False,
+                                lights=None, light_choice=0, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", state=None, out_rays=None,
+                                out_camera=None, out_counters=None, stream=None):
+        """rtmi_render_lit_tiles_device: render_lit_device over the first n_tiles entries of an HBM-resident int32 tile list; the frame buffers
+        and the state are the whole frame's and only the listed pixels' elements are written.  An entry outside the frame holds no pixel;
+        duplicates and order are the caller's contract."""
+        est = self._tiles_estimator(estimator, volume)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        check(_ffi.lib().rtmi_render_lit_tiles_device(self.handle, _PRECISION[precision], int(nx), int(ny), int(s_first), int(s_count), int(depth),
+                                                      int(seed), est, n_listed, ptr(lights), self._light_choice(light_choice), int(bool(volume)),
+                                                      int(n_tiles), ptr(tiles), ptr(state), ptr(out_linear), ptr(out_rgb8), ptr(out_stderr),
+                                                      ptr(out_rays), ptr(out_camera), ptr(out_counters), ptr(stream)))
+
+    def refine_lit_adaptive(self, nx, ny, ns, chunk, eps, first=None, estimator="mis", volume=False, lights=None, light_choice=0, denoised=False,
+                            na=FEATURE_SAMPLES, iterations=DENOISE_ITERATIONS, sigma_c=DENOISE_SIGMA_C, sigma_n=DENOISE_SIGMA_N,
+                            sigma_a=DENOISE_SIGMA_A, sigma_d=DENOISE_SIGMA_D, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64"):
+        """A light-sampled frame refined adaptively: every 8x8 tile listed, then rounds of render_lit_tiles (`first` samples, default chunk, then
+        `chunk`) each followed by tiles_retire of the tiles whose standard error is <= eps everywhere -- with denoised=True of those whose FILTERED
+        standard error is (render_features once, denoise per round, as refine_adaptive_denoised) -- until no tile is listed or ns is reached.
+        -> (linear, rgb8, stderr, samples [ny, nx] int32, counters summed over the rounds, rounds = [(k, tiles listed after the round's
+        retirement, int32)]).  A pixel whose tile took n samples equals render_lit(ns = n) there bit for bit.  With torch the buffers and the list
+        stay in HBM across the rounds and only the number of survivors comes back per round."""
+        first = chunk if first is None else first
+        if nx <= 0 or ny <= 0 or chunk <= 0 or ns <= 0 or first <= 0:
+            raise ValueError("nx, ny, ns, chunk and first must be > 0")
+        n_all = ((nx + _ffi.TILE - 1) // _ffi.TILE) * ((ny + _ffi.TILE - 1) // _ffi.TILE)
+        kw = dict(estimator=estimator, volume=volume, lights=lights, light_choice=light_choice, depth=depth, seed=seed, precision=precision)
+        dn = (int(iterations), float(sigma_c), float(sigma_n), float(sigma_a), float(sigma_d))
+        total, rounds, k, n_tiles = np.zeros(4, np.uint64), [], 0, n_all
+        if _ffi.torch is None:  # host arrays: every round stages the frame
+            lin, q, err = np.zeros((ny, nx, 3), np.float64), np.zeros((ny, nx, 3), np.uint8), np.zeros((ny, nx), np.float64)
+            state, tiles = np.zeros((nx * ny, _ffi.RAYS_REC), np.float64), np.arange(n_all, dtype=np.int32)
+            ft = self.render_features(nx, ny, na, seed, precision)[0] if denoised else None
+            while k < ns and len(tiles):
+                n = min(first if k == 0 else chunk, ns - k)
+                total += self.render_lit_tiles(nx, ny, k, n, tiles, lin, q, err, state, **kw)[0]
+                k += n
+                tiles = self.ctx.tiles_retire(self.ctx.denoise(lin, err, ft, *dn)[2] if denoised else err, eps, tiles)
+                rounds.append((k, tiles))
+            return lin, q, err, state[:, 9].reshape(ny, nx).astype(np.int32), total, rounds
+        torch = _ffi.torch
+        dev = torch.device("cuda", self.ctx.device)
+        f64 = dict(dtype=torch.float64, device=dev)
+        side = torch.cuda.Stream(dev)  # torch's own operations and the library's calls in one order
+        stream = side.cuda_stream
+        with torch.cuda.stream(side):
+            lin, q, err = torch.zeros((ny, nx, 3), **f64), torch.zeros((ny, nx, 3), dtype=torch.uint8, device=dev), torch.zeros((ny, nx), **f64)
+            state, tiles = torch.zeros((nx * ny, _ffi.RAYS_REC), **f64), torch.arange(n_all, dtype=torch.int32, device=dev)
+            cnt, sums = torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros(4, dtype=torch.int64, device=dev)
+            ft = ferr = None
+            if denoised:
+                ft, ferr = torch.zeros((ny, nx, _ffi.FEATURES), **f64), torch.zeros((ny, nx), **f64)
+                self.render_features_device(nx, ny, na, ft, None, seed, precision, stream)
+            kept = []
+            while k < ns and n_tiles:
+                n = min(first if k == 0 else chunk, ns - k)
+                self.render_lit_tiles_device(nx, ny, k, n, n_tiles, tiles, lin, err, q, state=state, out_counters=cnt, stream=stream, **kw)
+                k += n
+                if denoised:
+                    self.ctx.denoise_device(nx, ny, lin, err, ft, None, None, ferr, *dn, stream=stream)
+                n_tiles = self.ctx.tiles_retire_device(nx, ny, ferr if denoised else err, eps, n_tiles, tiles, stream=stream)  # (synchronises)
+                sums += cnt
+                kept.append((k, tiles[:n_tiles].clone()))
+            side.synchronize()
+            rounds = [(kk, t.cpu().numpy()) for kk, t in kept]
+            return (lin.cpu().numpy(), q.cpu().numpy(), err.cpu().numpy(), state[:, 9].reshape(ny, nx).cpu().numpy().astype(np.int32),
+                    sums.cpu().numpy().astype(np.uint64), rounds)
 
     # ---- closest-hit and any-hit queries: picking, first hits, shadow / ambient-occlusion / line-of-sight rays --------------------------------
     @staticmethod
@@ -1980,7 +2094,10 @@ def main(argv=None):
     --lit-vol [nee|mis[:power]] also writes the frame of DeviceScene.render_lit_vol (default mis) as name.vol.ext: --lit's frame under the volume rule,
     for the scenes that hold a ConstantMedium (final, the smoke cornell-box, subsurface) -- the vertices inside a medium sample the lights too and the
     shadow rays draw their own way through the media.  With --chunk K it is refined K samples at a time.  It does not combine with --lit, --nee, --mis,
-    --orbit or --panorama."""
+    --orbit or --panorama.
+    --lit / --lit-vol with --adaptive EPS (or --adaptive-denoised EPS) refine their frame adaptively too (DeviceScene.refine_lit_adaptive, rounds of
+    --chunk): an 8x8 tile stops taking samples once its standard error (its filtered standard error) is <= EPS everywhere, ns is the cap, and a line
+    reports the share of the pixel-samples taken."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
     argv, direct = _direct_flags(argv)
@@ -2134,20 +2251,21 @@ def main(argv=None):
         finally:
             ds.close()
         _save_image(_mis_name(name), lit)
-    if lit_mode is not None:
+    lit_eps = adaptive if adaptive is not None else adaptive_denoised  # the frame's stopping rule is the light-sampled frame's too
+    for mode, volume, out_name in ((lit_mode, False, _lit_name(name)), (vol_mode, True, _lit_vol_name(name))):
+        if mode is None:
+            continue
         ds = DeviceScene(sc)
         try:
-            frame = ds.render_lit(nx, ny, nr, chunk=chunk, estimator=lit_mode[0], light_choice=lit_mode[1])[1]
+            if lit_eps is None:
+                frame = (ds.render_lit_vol if volume else ds.render_lit)(nx, ny, nr, chunk=chunk, estimator=mode[0], light_choice=mode[1])[1]
+            else:
+                more = {} if adaptive is not None else dict(denoised=True, na=FEATURE_SAMPLES if dn_samples is None else dn_samples, iterations=dn_iterations)
+                frame, smp = ds.refine_lit_adaptive(nx, ny, nr, chunk, lit_eps, estimator=mode[0], volume=volume, light_choice=mode[1], **more)[1:4:2]
+                print("%s: %.1f%% of the %d pixel-samples taken" % ("--lit-vol" if volume else "--lit", 100.0 * float(smp.sum()) / (nx * ny * nr), nx * ny * nr))
         finally:
             ds.close()
-        _save_image(_lit_name(name), frame)
-    if vol_mode is not None:
-        ds = DeviceScene(sc)
-        try:
-            frame = ds.render_lit_vol(nx, ny, nr, chunk=chunk, estimator=vol_mode[0], light_choice=vol_mode[1])[1]
-        finally:
-            ds.close()
-        _save_image(_lit_vol_name(name), frame)
+        _save_image(out_name, frame)
     return 0
 
 

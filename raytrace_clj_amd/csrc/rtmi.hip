@@ -1262,20 +1262,23 @@ struct RaysParams {
     int nx, ny;
     int fixed_rays;       // TraceParams::fixed_rays (read by the wave-wide lens sampler only: RTMI_LIT_WAVE_LENS)
     double *out_camera;   // [total_items][8], or null: origin, direction, time, stream position behind the camera
+    // the tile list of SRC_CAMERA_TILES (never read by another source): the pass's own entries, total_items = entries * 64 * group
+    const int *tiles;     // [entries]: global 8x8 tile indices, row-major over tiles_x x ceil(ny / 8); an entry outside [0, n_frame_tiles) holds no pixel
+    int tiles_x, n_frame_tiles;
 };
 
 // Where a lane's ray comes from (the query kernels' sources are described at query_kernel).  SRC_CAMERA, the path kernels' (rtmi_render_lit*): row
 // row0 + m is sample g_first + r of pixel g, and the lane builds start_sample's ray in R from the camera the scene holds on the device.
-enum { SRC_MEMORY = 0, SRC_HEMISPHERE = 1, SRC_TARGETS = 2, SRC_PIXEL = 3, SRC_LIGHT = 4, SRC_CAMERA = 5 };
+// SRC_CAMERA_TILES (rtmi_render_lit_tiles*): SRC_CAMERA with the pixels taken from a list of 8x8 tiles, THE TILE ORDER of rtmi.h.
+enum { SRC_MEMORY = 0, SRC_HEMISPHERE = 1, SRC_TARGETS = 2, SRC_PIXEL = 3, SRC_LIGHT = 4, SRC_CAMERA = 5, SRC_CAMERA_TILES = 6 };
 
 #ifndef RTMI_LIT_WAVE_LENS
 #define RTMI_LIT_WAVE_LENS 0 // 1: the refill samples the lens with get_ray_wave, the whole wave helping (A/B; DESIGN.md section 7q: the same bits)
 #endif
 // The refill of a SRC_CAMERA lane, THE FRAME RULE of rtmi.h: start_sample's operations, so the path goes on in the stream where rtmi_render's does.
 // `has`: the lane takes item m; every lane of the wave calls (the refill loop is wave-uniform), the others leave P as it is.
-template <typename R> __device__ inline void camera_refill(SceneRef sc, const RaysParams &rp, bool has, unsigned m, Path<R> &P) {
-    const unsigned row = rp.row0 + m, g = row / rp.group, y = g / (unsigned)rp.nx;
-    const int x = (int)(g - y * (unsigned)rp.nx), j = rp.ny - 1 - (int)y, s = (int)(rp.g_first + (row - g * rp.group)); // j = ny-1-y (core.clj:105)
+// camera_refill_at: steps 2 - 5 for sample s of pixel (x, j) as item m of the pass; camera_refill: step 1 for the frame's row-major rows in front of it.
+template <typename R> __device__ inline void camera_refill_at(SceneRef sc, const RaysParams &rp, bool has, unsigned m, int x, int j, int s, Path<R> &P) {
     const u64 key = sample_key(rp.seed, (u64)j * (u64)rp.nx + (u64)x, (u64)s);
 #if RTMI_LIT_WAVE_LENS
     Path<R> Q;
@@ -1301,10 +1304,40 @@ template <typename R> __device__ inline void camera_refill(SceneRef sc, const Ra
         }
     }
 }
+template <typename R> __device__ inline void camera_refill(SceneRef sc, const RaysParams &rp, bool has, unsigned m, Path<R> &P) {
+    const unsigned row = rp.row0 + m, g = row / rp.group, y = g / (unsigned)rp.nx;
+    const int x = (int)(g - y * (unsigned)rp.nx), j = rp.ny - 1 - (int)y, s = (int)(rp.g_first + (row - g * rp.group)); // j = ny-1-y (core.clj:105)
+    camera_refill_at<R>(sc, rp, has, m, x, j, s, P);
+}
+
+// The refill of a SRC_CAMERA_TILES lane, THE TILE ORDER of rtmi.h: item m of the pass is sample g_first + m % group of local pixel (m / group) % 64 of
+// entry m / (64 * group) of the pass's list.  The divisions and the load of the tile index happen here, once per path; the entries of a claimed block
+// differ from lane to lane unless 64 * group divides the block, so the index is a per-lane load.  -> the lane took a pixel.  An item whose pixel lies
+// outside the image (a partial tile's) leaves +0.0 in its rows of samples and out_camera and its lane dead; an entry outside [0, n_frame_tiles) -- a
+// device list is the caller's -- touches nothing at all.
+template <typename R> __device__ inline bool tile_refill(SceneRef sc, const RaysParams &rp, bool has, unsigned m, Path<R> &P) {
+    const unsigned px = m / rp.group, r = m - px * rp.group, entry = px >> 6, l = px & 63u;
+    const int t = has ? rp.tiles[entry] : -1; // entry < the pass's entries: m < total_items
+    const bool listed = (unsigned)t < (unsigned)rp.n_frame_tiles;
+    const int ty = listed ? t / rp.tiles_x : 0, tx = listed ? t - ty * rp.tiles_x : 0;
+    const int x = tx * RTMI_TILE + (int)(l & 7u), y = ty * RTMI_TILE + (int)(l >> 3);
+    const bool inside = listed && x < rp.nx && y < rp.ny;
+    if (listed && !inside) {
+        double *o = rp.samples + (size_t)m * 3;
+        o[0] = 0.0; o[1] = 0.0; o[2] = 0.0;
+        if (rp.out_camera) {
+            double *c = rp.out_camera + (size_t)m * 8;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) c[k] = 0.0;
+        }
+    }
+    camera_refill_at<R>(sc, rp, inside, m, inside ? x : 0, inside ? rp.ny - 1 - y : 0, (int)(rp.g_first + r), P);
+    return inside;
+}
 
 template <typename R, int VARIANT, bool EXT = false, int MSEQ = 0, int SRC = SRC_MEMORY>
 __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WAVES) : RTMI_MIN_WAVES) rays_kernel(ScenePtr scp, RaysParams rp) {
-    static_assert(SRC == SRC_MEMORY || SRC == SRC_CAMERA, "the path kernels read their rays or build the frame's");
+    static_assert(SRC == SRC_MEMORY || SRC == SRC_CAMERA || SRC == SRC_CAMERA_TILES, "the path kernels read their rays or build the frame's");
     static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the refill loop is per wave");
     SceneRef sc = *scp;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1340,6 +1373,10 @@ __global__ void __launch_bounds__(kBlock, EXT ? (MSEQ != 0 ? 3 : RTMI_EXT_MIN_WA
                 const unsigned m = w_cur + (has ? rank : 0u); // < total_items
                 camera_refill<R>(sc, rp, has, m, P);
                 if (has) { out_item = m; alive = true; }
+            } else if constexpr (SRC == SRC_CAMERA_TILES) { // a lane whose item holds no pixel stays dead: the next round of this loop deals it another
+                const bool has = !alive && rank < avail;
+                const unsigned m = w_cur + (has ? rank : 0u); // < total_items
+                if (tile_refill<R>(sc, rp, has, m, P)) { out_item = m; alive = true; }
             } else if (!alive && rank < avail) {
                 const unsigned m = w_cur + rank; // < total_items
                 load_ray<R>(rp.rays + (size_t)m * 7, P);
@@ -1423,6 +1460,95 @@ __global__ void __launch_bounds__(kBlock) rays_fold_kernel(const double *__restr
         }
     }
     se[g] = err;
+}
+
+// rtmi_render_lit_tiles*: rays_fold_kernel over a pass of THE TILE ORDER.  One wave per entry of the pass's list, lane l = local pixel l: group
+// entry * 64 + l of the pass folds into pixel (x, y) of the whole-frame state, mean and se, and the frame's quantiser runs on the means it wrote (rgb8
+// may be null).  A lane outside the image and every lane of an entry outside [0, n_frame_tiles) reads and writes nothing.
+template <typename R>
+__global__ void __launch_bounds__(kBlock) lit_tiles_fold_kernel(const double *__restrict__ samples, const int *__restrict__ tiles, int n_entries, int group,
+                                                                int first, int tiles_x, int n_frame_tiles, int nx, int ny, double *__restrict__ state,
+                                                                double *__restrict__ mean, double *__restrict__ se, unsigned char *__restrict__ rgb8) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)n_entries * 64) return; // (whole waves: kBlock is a multiple of 64)
+    const int entry = (int)(gid >> 6), l = (int)(gid & 63);
+    const int t = tiles[entry];
+    const bool listed = (unsigned)t < (unsigned)n_frame_tiles;
+    const int ty = listed ? t / tiles_x : 0, tx = listed ? t - ty * tiles_x : 0;
+    const int x = tx * RTMI_TILE + (l & 7), y = ty * RTMI_TILE + (l >> 3);
+    const bool inside = listed && x < nx && y < ny;
+    if (!inside) return;
+    const size_t g = (size_t)y * (size_t)nx + (size_t)x;
+    // rays_fold_kernel's body from here to se[g], expression by expression (that kernel stays as it is for its callers): the bits are its bits
+    R acc[3] = {R(0), R(0), R(0)};
+    double mu[3] = {0.0, 0.0, 0.0}, q[3] = {0.0, 0.0, 0.0};
+    double *rec = state ? state + g * RTMI_RAYS_REC : nullptr;
+    if (rec && first > 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { acc[k] = (R)rec[k]; mu[k] = rec[3 + k]; q[k] = rec[6 + k]; }
+    }
+    const double *row = samples + (size_t)gid * (size_t)group * 3;
+    for (int s = 0; s < group; ++s, row += 3) {
+        const R v[3] = {(R)row[0], (R)row[1], (R)row[2]};
+        if (first + s == 0) { // the fold starts FROM the first ray (not 0 + first)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { acc[k] = v[k]; mu[k] = (double)v[k]; q[k] = 0.0; }
+        } else {
+            const double n = (double)(first + s + 1);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                acc[k] = acc[k] + v[k];
+                const double x = (double)v[k], d = x - mu[k];
+                mu[k] = mu[k] + d / n;
+                q[k] = q[k] + d * (x - mu[k]);
+            }
+        }
+    }
+    const int count = first + group;
+    if (rec) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { rec[k] = (double)acc[k]; rec[3 + k] = mu[k]; rec[6 + k] = q[k]; }
+        rec[9] = (double)count;
+    }
+    double err = count > 1 ? 0.0 : INFINITY;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        mean[g * 3 + k] = (double)(acc[k] * (R(1.0) / (R)count));
+        if (count > 1) {
+            const double e = ::sqrt((q[k] / (double)(count - 1)) / (double)count);
+            err = e > err ? e : err;
+        }
+    }
+    se[g] = err;
+    if (rgb8) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) rgb8[g * 3 + k] = quantise8(mean[g * 3 + k]);
+    }
+}
+
+// The rays of a pass of rtmi_render_lit_tiles*: counters[1] += (the pixels of its entries inside the image) * group -- a device list cannot be counted on the
+// host, and an atomic per folded tile (32 400 of them at 1920 x 1080, all on one address) cost five times the fold.  One workgroup walks the list in
+// strides of its size, as adaptive_compact_kernel does; the passes of a call run in stream order behind the memset that zeroes the counters.
+__global__ void __launch_bounds__(kCompactBlock) lit_tiles_count_kernel(const int *__restrict__ tiles, int n_entries, int group, int tiles_x, int n_frame_tiles,
+                                                                        int nx, int ny, u64 *counters) {
+    __shared__ int wave_pixels[kCompactBlock / 64];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int pixels = 0; // <= 64 * entries / kCompactBlock per thread and <= nx * ny < 2^31 in all
+    for (int i = tid; i < n_entries; i += kCompactBlock) {
+        const int t = tiles[i];
+        if ((unsigned)t < (unsigned)n_frame_tiles) {
+            const int ty = t / tiles_x, tx = t - ty * tiles_x;
+            pixels += min(RTMI_TILE, nx - tx * RTMI_TILE) * min(RTMI_TILE, ny - ty * RTMI_TILE);
+        }
+    }
+    for (int d = 32; d > 0; d >>= 1) pixels += __shfl_down(pixels, d, 64);
+    if (lane == 0) wave_pixels[wave] = pixels;
+    __syncthreads();
+    if (tid == 0) {
+        u64 sum = 0;
+        for (int w = 0; w < kCompactBlock / 64; ++w) sum += (u64)wave_pixels[w];
+        counters[1] += sum * (u64)group;
+    }
 }
 
 // rtmi_render_lit*'s 8-bit frame: the frame's quantiser on the fold's means, n = 3 * pixels values
@@ -1896,7 +2022,7 @@ struct NeeParams {
 // stream of its own for the media it crosses.  Mixed-kind FP64 instantiations only: a world of spheres holds no medium.
 template <typename R, int VARIANT, bool EXT = false, bool MIS = false, int SRC = SRC_MEMORY, bool VOL = false>
 __global__ void __launch_bounds__(kBlock, VOL ? RTMI_VOL_MIN_WAVES : RTMI_NEE_MIN_WAVES) rays_nee_kernel(ScenePtr scp, NeeParams np) {
-    static_assert(SRC == SRC_MEMORY || SRC == SRC_CAMERA, "the path kernels read their rays or build the frame's");
+    static_assert(SRC == SRC_MEMORY || SRC == SRC_CAMERA || SRC == SRC_CAMERA_TILES, "the path kernels read their rays or build the frame's");
     static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the refill loop is per wave");
     SceneRef sc = *scp;
     __shared__ double nee_lds[(MIS ? kMisSlots : kNeeSlots) * kBlock];
@@ -1936,6 +2062,15 @@ __global__ void __launch_bounds__(kBlock, VOL ? RTMI_VOL_MIN_WAVES : RTMI_NEE_MI
                 const unsigned m = w_cur + (has ? rank : 0u); // < total_items
                 camera_refill<R>(sc, rp, has, m, P);
                 if (has) {
+                    out_item = m;
+                    alive = true;
+                    sampled = false; seg = 0;
+                    slot[0] = 0.0; slot[kBlock] = 0.0; slot[2 * kBlock] = 0.0; // accum starts at +0.0
+                }
+            } else if constexpr (SRC == SRC_CAMERA_TILES) { // a lane whose item holds no pixel stays dead: the next round of this loop deals it another
+                const bool has = !alive && rank < avail;
+                const unsigned m = w_cur + (has ? rank : 0u); // < total_items
+                if (tile_refill<R>(sc, rp, has, m, P)) {
                     out_item = m;
                     alive = true;
                     sampled = false; seg = 0;
@@ -2398,6 +2533,7 @@ struct rtmi_ctx {
     DevBuf rays_ws;   // rtmi_render_rays*: the per-ray radiance nobody asked for (one pass of it)
     DevBuf occ_ws;    // rtmi_ambient_occlusion*: the first-hit records and the per-pixel counts nobody asked for
     DevBuf nee_ws;    // rtmi_render_rays_nee*, rtmi_probe_paths_nee: the light table and the sampled lights' primitives
+    DevBuf retire_ws; // rtmi_tiles_retire*: the keep flags, the surviving tiles and their slots, the two ints of the compaction's meta
     DevBuf direct_ws; // rtmi_direct_irradiance*, rtmi_render_direct*: the light table, then the records and irradiance nobody asked for, then one pass of contributions
     // timing
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -3131,7 +3267,7 @@ RTMI_EXPORT int rtmi_test_stage_layout(int32_t n, const uint64_t *elem_bytes, co
 }
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 218; } // 218: direct lighting from the scene's area lights (rtmi_scene_lights, rtmi_direct_irradiance*, rtmi_render_direct*); 217: occlusion rays generated on the device (rtmi_occlusion_hemisphere*, rtmi_occlusion_targets*, rtmi_ambient_occlusion*); 216: closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*); 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 219; } // 219: light-sampled frames over a caller's tile list and the stateless retirement (rtmi_render_lit_tiles*, rtmi_tiles_retire*); 218: direct lighting from the scene's area lights (rtmi_scene_lights, rtmi_direct_irradiance*, rtmi_render_direct*); 217: occlusion rays generated on the device (rtmi_occlusion_hemisphere*, rtmi_occlusion_targets*, rtmi_ambient_occlusion*); 216: closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*); 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -3170,7 +3306,7 @@ RTMI_EXPORT int rtmi_shutdown(rtmi_ctx *c) {
 #endif
     c->samples.release(); c->accum.release(); c->tiles.release(); c->tile_ids.release(); c->counters.release(); c->io.release(); c->multi.release();
     c->prog.release();
-    c->feat_cnt.release(); c->dn_planes.release(); c->rays_ws.release(); c->occ_ws.release(); c->direct_ws.release(); c->nee_ws.release();
+    c->feat_cnt.release(); c->dn_planes.release(); c->rays_ws.release(); c->occ_ws.release(); c->direct_ws.release(); c->nee_ws.release(); c->retire_ws.release();
     for (hipEvent_t e : {c->ev_done, c->ev_g0, c->ev_g1}) if (e) (void)hipEventDestroy(e);
     if (c->ev_consumed) { (void)hipSetDevice(c->ev_consumed_device); (void)hipEventDestroy(c->ev_consumed); (void)hipSetDevice(c->device); }
     for (auto &e : c->events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -5797,8 +5933,13 @@ struct RaysPass {
 struct LitRaysPass : RaysPass {
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MSEQ, SRC_CAMERA>; }
 };
+struct LitTilesRaysPass : RaysPass { // rtmi_render_lit_tiles*, estimator 0: the camera rays of a list of tiles (SRC_CAMERA_TILES)
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MSEQ, SRC_CAMERA_TILES>; }
+};
 // The frame of a call whose rays the kernel builds (null for the calls that read theirs): what RaysParams holds of it.  out_camera is the call's.
-struct RaysFrame { int nx, ny, fixed_rays; double *out_camera; };
+// d_tiles (rtmi_render_lit_tiles*): the family's kernels are the SRC_CAMERA_TILES ones, the call's groups are the 64 pixel slots of each of its
+// n_tiles entries in THE TILE ORDER, and the fold writes the listed pixels of the whole-frame state, mean, se and d_rgb8 (may be null).
+struct RaysFrame { int nx, ny, fixed_rays; double *out_camera; const int *d_tiles = nullptr; int n_tiles = 0; unsigned char *d_rgb8 = nullptr; };
 
 constexpr long long kRaysMax = (1ll << 31) - 64; // rays per call: 32-bit work items, and a claim past the end must not wrap the queue head
 
@@ -5815,10 +5956,12 @@ int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const 
     int rc = c->counters.ensure(8 * sizeof(u64));
     if (rc) return rc;
     if (!d_cnt) d_cnt = reinterpret_cast<u64 *>(c->counters.p);
+    const int *d_tiles = frame ? frame->d_tiles : nullptr;
+    const int unit = d_tiles ? 64 : 1; // groups a pass is made of: a listed tile's 64 pixel slots stay together
     int per_pass = n_groups;
     if (!d_out_rays) {
         const int64_t group_bytes = (int64_t)group * 3 * (int64_t)sizeof(double);
-        per_pass = (int)std::max<int64_t>(1, std::min<int64_t>(n_groups, c->workspace_bytes / group_bytes));
+        per_pass = (int)std::max<int64_t>(unit, std::min<int64_t>(n_groups, c->workspace_bytes / group_bytes / unit * unit));
         rc = c->rays_ws.ensure((size_t)per_pass * (size_t)group_bytes);
         if (rc) return rc;
     }
@@ -5832,6 +5975,7 @@ int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const 
     rp.queue = reinterpret_cast<unsigned *>(reinterpret_cast<u64 *>(c->counters.p) + Family::n_counters);
     rp.counters = d_cnt;
     rp.nx = frame ? frame->nx : 0; rp.ny = frame ? frame->ny : 0; rp.fixed_rays = frame ? frame->fixed_rays : 0; rp.out_camera = nullptr;
+    rp.tiles = nullptr; rp.tiles_x = d_tiles ? tiles_x_of(rp.nx) : 0; rp.n_frame_tiles = d_tiles ? rp.tiles_x * tiles_x_of(rp.ny) : 0;
     const u64 n_rays = (u64)n_groups * (u64)group;
     with_probe_kernel<Family, R>(s, [&](auto kern, size_t lds, int, int) {
         for (int g0 = 0; g0 < n_groups && !rc; g0 += per_pass) {
@@ -5842,14 +5986,22 @@ int render_rays_impl(rtmi_scene *s, int n_groups, int group, int g_first, const 
             if (frame && frame->out_camera) rp.out_camera = frame->out_camera + row0 * 8;
             rp.samples = d_out_rays ? d_out_rays + row0 * 3 : reinterpret_cast<double *>(c->rays_ws.p);
             rp.row0 = (unsigned)row0;
+            if (d_tiles) rp.tiles = d_tiles + g0 / 64;
             rc = queue_launch(c, st, reinterpret_cast<const void *>(kern), lds, rp.queue, (long long)ng * group,
                               [&](dim3 grid, unsigned items, unsigned qblock) {
                                   rp.total_items = items; rp.qblock = qblock;
                                   hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, s->d_dev, args);
                               },
                               [&] {
-                                  hipLaunchKernelGGL((rays_fold_kernel<R>), dim3((unsigned)((ng + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rp.samples, g0, ng,
-                                                     group, d_state ? g_first : 0, d_state, d_mean, d_se, d_cnt, n_rays);
+                                  const dim3 fold_grid((unsigned)((ng + kBlock - 1) / kBlock));
+                                  if (d_tiles) {
+                                      hipLaunchKernelGGL((lit_tiles_fold_kernel<R>), fold_grid, dim3(kBlock), 0, st, rp.samples, rp.tiles, ng / 64, group,
+                                                         d_state ? g_first : 0, rp.tiles_x, rp.n_frame_tiles, rp.nx, rp.ny, d_state, d_mean, d_se, frame->d_rgb8);
+                                      hipLaunchKernelGGL(lit_tiles_count_kernel, dim3(1), dim3(kCompactBlock), 0, st, rp.tiles, ng / 64, group, rp.tiles_x,
+                                                         rp.n_frame_tiles, rp.nx, rp.ny, d_cnt);
+                                  } else
+                                      hipLaunchKernelGGL((rays_fold_kernel<R>), fold_grid, dim3(kBlock), 0, st, rp.samples, g0, ng, group,
+                                                         d_state ? g_first : 0, d_state, d_mean, d_se, d_cnt, n_rays);
                               });
         }
     });
@@ -6565,6 +6717,12 @@ struct MisPass : NeePass {
 struct LitMisPass : NeePass { // rtmi_render_lit*, estimator 2
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, true, SRC_CAMERA>; }
 };
+struct LitTilesNeePass : NeePass { // rtmi_render_lit_tiles*, estimators 1 and 2: the camera rays of a list of tiles (SRC_CAMERA_TILES)
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, false, SRC_CAMERA_TILES>; }
+};
+struct LitTilesMisPass : NeePass {
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, true, SRC_CAMERA_TILES>; }
+};
 struct ProbePathsMis {
     static constexpr bool wave_level = true;
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, true>; }
@@ -6682,37 +6840,26 @@ int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *lig
 int nee_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, const double *d_rays, const u64 *d_keys, u64 seed, unsigned ctr0, int depth,
             const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st,
             const MisLightTable *M = nullptr, // M (then T is M->t): the MIS rule's kernels and table
-            const RaysFrame *frame = nullptr, // frame: the SRC_CAMERA twins of the three families (rtmi_render_lit*)
+            const RaysFrame *frame = nullptr, // frame: the SRC_CAMERA twins of the three families (rtmi_render_lit*), or with a list their SRC_CAMERA_TILES twins
             bool vol = false) {               // vol: the volume rule's instantiations of the two light-sampling families
     return with_real(precision, [&](auto r) {
         using R = decltype(r);
         auto mis_lights = [&](NeeParams &np, hipStream_t q) { return upload_mis_lights(s->ctx, *M, np.lights, q); };
         auto nee_lights = [&](NeeParams &np, hipStream_t q) { return upload_nee_lights(s->ctx, T, np.lights, q); };
-        if (vol && M && T.t.n > 0)
-            return frame ? render_rays_impl<R, VolPass<true, SRC_CAMERA>>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se,
-                                                                          d_out_rays, d_cnt, st, mis_lights, frame)
-                         : render_rays_impl<R, VolPass<true, SRC_MEMORY>>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se,
-                                                                          d_out_rays, d_cnt, st, mis_lights);
-        if (vol && T.t.n > 0)
-            return frame ? render_rays_impl<R, VolPass<false, SRC_CAMERA>>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se,
-                                                                           d_out_rays, d_cnt, st, nee_lights, frame)
-                         : render_rays_impl<R, VolPass<false, SRC_MEMORY>>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se,
-                                                                           d_out_rays, d_cnt, st, nee_lights);
-        if (M && T.t.n > 0)
-            return frame ? render_rays_impl<R, LitMisPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt,
-                                                           st, mis_lights, frame)
-                         : render_rays_impl<R, MisPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
-                                                        mis_lights);
-        if (T.t.n > 0)
-            return frame ? render_rays_impl<R, LitNeePass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt,
-                                                           st, nee_lights, frame)
-                         : render_rays_impl<R, NeePass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
-                                                        nee_lights);
+        // the family's kernels by the source of the rays: the caller's array, the frame's camera rays, those of a list of tiles
+        auto run = [&](auto camera, auto memory, auto tiles, auto lights) {
+            auto go = [&](auto family) {
+                return render_rays_impl<R, decltype(family)>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt,
+                                                             st, lights, frame);
+            };
+            return frame && !frame->d_tiles ? go(camera) : !frame ? go(memory) : go(tiles);
+        };
+        if (vol && M && T.t.n > 0) return run(VolPass<true, SRC_CAMERA>{}, VolPass<true, SRC_MEMORY>{}, VolPass<true, SRC_CAMERA_TILES>{}, mis_lights);
+        if (vol && T.t.n > 0) return run(VolPass<false, SRC_CAMERA>{}, VolPass<false, SRC_MEMORY>{}, VolPass<false, SRC_CAMERA_TILES>{}, nee_lights);
+        if (M && T.t.n > 0) return run(LitMisPass{}, MisPass{}, LitTilesMisPass{}, mis_lights);
+        if (T.t.n > 0) return run(LitNeePass{}, NeePass{}, LitTilesNeePass{}, nee_lights);
         if (d_cnt) HIP_TRY(hipMemsetAsync(d_cnt + 2, 0, 2 * sizeof(u64), st));
-        return frame ? render_rays_impl<R, LitRaysPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
-                                                        NoLights{}, frame)
-                     : render_rays_impl<R, RaysPass>(s, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, d_state, d_mean, d_se, d_out_rays, d_cnt, st,
-                                                     NoLights{});
+        return run(LitRaysPass{}, RaysPass{}, LitTilesRaysPass{}, NoLights{});
     });
 }
 
@@ -6860,32 +7007,56 @@ RTMI_EXPORT int rtmi_probe_paths_mis(rtmi_scene *s, int32_t precision, int32_t n
 namespace {
 // what both forms check first, in the header's order; *M: estimators 1 and 2's light table (estimator 0: no light); *work false: nothing to do
 // vol: rtmi_render_lit_vol* -- the light-sampling calls' checks run for every estimator, the volume rule's own (estimators 1 and 2 only) behind the list's length
+// tl: rtmi_render_lit_tiles* -- the list as the caller gave it (a host form's is checked entry by entry, a device form's is the caller's contract; the
+// kernels give an entry outside the frame no pixel); the volume rule is then tl->volume, and the rows of the call are the listed tiles' 64 * s_count each
+struct LitTileArgs { int volume, n_tiles; const int32_t *host_tiles; const void *tiles; };
 int lit_frame_begin(rtmi_scene *s, int precision, int nx, int ny, int s_first, int s_count, int depth, int estimator, int n_lights, const int32_t *light_prims,
                     int light_choice, const double *host_state, const void *out_linear, const void *out_stderr, MisLightTable &M, RaysFrame &F, bool *work,
-                    bool vol = false) {
+                    bool vol = false, const LitTileArgs *tl = nullptr) {
     *work = false;
     if (nx <= 0 || ny <= 0 || s_count <= 0 || s_first < 0 || depth < 0)
         return fail(RTMI_E_ARG, "nx, ny, s_count must be > 0 and s_first, depth >= 0 (got %d %d %d %d %d)", nx, ny, s_count, s_first, depth);
-    if ((long long)nx * ny > kRaysMax || (long long)nx * ny * s_count > kRaysMax)
+    if (tl && ((long long)nx * ny > kRaysMax || (tl->n_tiles > 0 && (long long)tl->n_tiles * 64 > kRaysMax / s_count)))
+        return fail(RTMI_E_ARG, "n_tiles * 64 * s_count = %d * 64 * %d rays (or nx * ny = %d * %d pixels) exceed 2^31 - 64", tl->n_tiles, s_count, nx, ny);
+    if (!tl && ((long long)nx * ny > kRaysMax || (long long)nx * ny * s_count > kRaysMax))
         return fail(RTMI_E_ARG, "nx * ny * s_count = %d * %d * %d rays exceed 2^31 - 64", nx, ny, s_count);
     if ((long long)s_first + s_count > INT32_MAX) return fail(RTMI_E_ARG, "s_first + s_count = %d + %d overflows int32", s_first, s_count);
     if (!out_linear || !out_stderr) return fail(RTMI_E_ARG, "out_linear / out_stderr is NULL");
     if (estimator < 0 || estimator > 2) return fail(RTMI_E_ARG, "estimator must be 0 (plain), 1 (the NEE rule) or 2 (the MIS rule) (got %d)", estimator);
+    const int tiles_x = tiles_x_of(nx), n_frame_tiles = tiles_x * tiles_x_of(ny);
+    if (tl) {
+        if (tl->volume != 0 && tl->volume != 1) return fail(RTMI_E_ARG, "volume must be 0 (rtmi_render_lit's rules) or 1 (rtmi_render_lit_vol's) (got %d)", tl->volume);
+        if (tl->n_tiles < 0 || (tl->n_tiles > 0 && !tl->tiles)) return fail(RTMI_E_ARG, "n_tiles must be >= 0 and tiles not NULL (got %d)", tl->n_tiles);
+        for (int k = 0; tl->host_tiles && k < tl->n_tiles; ++k) {
+            const int t = tl->host_tiles[k];
+            if (t < 0 || t >= n_frame_tiles) return fail(RTMI_E_ARG, "tiles[%d] = %d, the frame has %d tiles", k, t, n_frame_tiles);
+            if (k && t <= tl->host_tiles[k - 1]) return fail(RTMI_E_ARG, "tiles[%d] = %d follows %d: the list must be strictly ascending", k, t, tl->host_tiles[k - 1]);
+        }
+    }
     M.t.t.n = 0;
-    const int rc = rays_begin(s, precision, nx * ny, s_count, s_first, depth, nullptr, out_linear, out_stderr, host_state, work, estimator || vol ? &M.t : nullptr,
-                              n_lights, light_prims, estimator == 2 ? light_choice : 0, true, vol ? estimator : -1);
+    const int rc = rays_begin(s, precision, tl ? tl->n_tiles * 64 : nx * ny, s_count, s_first, depth, nullptr, out_linear, out_stderr, tl ? nullptr : host_state, work,
+                              estimator || vol ? &M.t : nullptr, n_lights, light_prims, estimator == 2 ? light_choice : 0, true, vol ? estimator : -1);
     if (rc || !*work) return rc;
+    for (int k = 0; tl && tl->host_tiles && host_state && s_first > 0 && k < tl->n_tiles; ++k) { // the listed pixels' records continue at s_first
+        const int t = tl->host_tiles[k], x0 = (t % tiles_x) * RTMI_TILE, y0 = (t / tiles_x) * RTMI_TILE;
+        for (int y = y0; y < std::min(y0 + RTMI_TILE, ny); ++y)
+            for (int x = x0; x < std::min(x0 + RTMI_TILE, nx); ++x) {
+                const double held = host_state[((size_t)y * (size_t)nx + (size_t)x) * RTMI_RAYS_REC + 9];
+                if (held != (double)s_first) return fail(RTMI_E_STATE, "pixel (%d, %d) of tile %d holds %g samples, s_first is %d", x, y, t, held, s_first);
+            }
+    }
     if (estimator == 2) make_mis_rows(M, light_choice);
     F.nx = nx; F.ny = ny; F.fixed_rays = camera_fixed_rays(s->dev.cam_kind, s->dev.cam_fixed_origin, s->dev.cam);
+    F.n_tiles = tl ? tl->n_tiles : 0;
     return RTMI_OK;
 }
 
 int lit_frame_run(rtmi_scene *s, int precision, int nx, int ny, int s_first, int s_count, int depth, u64 seed, int estimator, const MisLightTable &M,
                   const RaysFrame &F, double *d_state, double *d_lin, unsigned char *d_q, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st,
                   bool vol = false) {
-    const int rc = nee_run(s, precision, nx * ny, s_count, s_first, nullptr, nullptr, seed, 0u, depth, M.t, d_state, d_lin, d_se, d_out_rays, d_cnt, st,
-                           estimator == 2 ? &M : nullptr, &F, vol);
-    if (rc || !d_q) return rc;
+    const int rc = nee_run(s, precision, F.d_tiles ? F.n_tiles * 64 : nx * ny, s_count, s_first, nullptr, nullptr, seed, 0u, depth, M.t, d_state, d_lin, d_se,
+                           d_out_rays, d_cnt, st, estimator == 2 ? &M : nullptr, &F, vol);
+    if (rc || !d_q || F.d_tiles) return rc; // (a list: the tile fold has quantised the pixels it wrote, F.d_rgb8)
     const size_t n = (size_t)nx * (size_t)ny * 3;
     hipLaunchKernelGGL(lit_quantise_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_lin, n, d_q);
     HIP_TRY(hipGetLastError());
@@ -6986,4 +7157,125 @@ RTMI_EXPORT int rtmi_render_lit_vol(rtmi_scene *s, int32_t precision, int32_t nx
                                     uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera, uint64_t *out_counters) {
     return lit_frame_host(true, s, precision, nx, ny, s_first, s_count, depth, seed, estimator, n_lights, light_prims, light_choice, state, out_linear, out_rgb8,
                           out_stderr, out_rays, out_camera, out_counters);
+}
+
+// ---- light-sampled frames over a caller's list of 8x8 tiles (rtmi_render_lit_tiles*): THE TILE ORDER of rtmi.h --------------------------------------------
+// rtmi_render_lit* / rtmi_render_lit_vol* with the SRC_CAMERA_TILES twins of their kernels and lit_tiles_fold_kernel behind each pass: the rows of the call
+// are the listed tiles' pixels, the frame planes and the state stay the whole frame's and only the listed pixels' elements are touched.
+RTMI_EXPORT int rtmi_render_lit_tiles_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth,
+                                             uint64_t seed, int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, int32_t volume,
+                                             int32_t n_tiles, const void *d_tiles, void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr,
+                                             void *d_out_rays, void *d_out_camera, void *d_out_counters, void *stream) {
+    MisLightTable M;
+    RaysFrame F;
+    bool work = false;
+    const LitTileArgs tl{volume, n_tiles, nullptr, d_tiles};
+    const int rc = lit_frame_begin(s, precision, nx, ny, s_first, s_count, depth, estimator, n_lights, light_prims, light_choice, nullptr, d_out_linear,
+                                   d_out_stderr, M, F, &work, volume == 1, &tl);
+    if (rc || !work) return rc;
+    F.out_camera = as<double>(d_out_camera); F.d_tiles = as<const int>(d_tiles); F.d_rgb8 = as<unsigned char>(d_out_rgb8);
+    return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, as<double>(d_state), as<double>(d_out_linear),
+                         as<unsigned char>(d_out_rgb8), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream),
+                         volume == 1);
+}
+
+// The host form stages the whole planes both ways: the elements outside the list come back with the bits they went up with.
+RTMI_EXPORT int rtmi_render_lit_tiles(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                      int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, int32_t volume, int32_t n_tiles,
+                                      const int32_t *tiles, double *state, double *out_linear, uint8_t *out_rgb8, double *out_stderr, double *out_rays,
+                                      double *out_camera, uint64_t *out_counters) {
+    MisLightTable M;
+    RaysFrame F;
+    bool work = false;
+    const LitTileArgs tl{volume, n_tiles, tiles, tiles};
+    const int rc = lit_frame_begin(s, precision, nx, ny, s_first, s_count, depth, estimator, n_lights, light_prims, light_choice, state, out_linear, out_stderr,
+                                   M, F, &work, volume == 1, &tl);
+    if (rc || !work) return rc;
+    const size_t ng = (size_t)nx * (size_t)ny, n = (size_t)n_tiles * 64 * (size_t)s_count;
+    HostIo io(s->ctx);
+    double *d_state, *d_lin, *d_se, *d_out, *d_cam;
+    unsigned char *d_q;
+    u64 *d_cnt;
+    int *d_tiles;
+    io.in(&d_tiles, (size_t)n_tiles, tiles);
+    io.plane(&d_state, ng * RTMI_RAYS_REC, state != nullptr, state, state);
+    io.plane(&d_lin, 3 * ng, true, out_linear, out_linear); io.plane(&d_se, ng, true, out_stderr, out_stderr);
+    io.plane(&d_q, 3 * ng, out_rgb8 != nullptr, out_rgb8, out_rgb8); io.work(&d_cnt, 4, out_counters);
+    io.out(&d_out, 3 * n, out_rays); io.out(&d_cam, 8 * n, out_camera);
+    return host_run(io, [&](hipStream_t st) {
+        F.out_camera = d_cam; F.d_tiles = d_tiles; F.d_rgb8 = d_q;
+        return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, d_state, d_lin, d_q, d_se, d_out, d_cnt, st, volume == 1);
+    });
+}
+
+// ---- retiring the tiles of a caller's list by a noise map (rtmi_tiles_retire*): the stateless rtmi_adaptive_retire ------------------------------------------
+// adaptive_retire_kernel over the caller's list with the whole image as the region, then adaptive_compact_kernel into the context's workspace (so the output
+// may be the input), whose survivors go to the caller once their number is known.
+namespace {
+int check_tiles_retire_args(int nx, int ny, const void *noise, double eps, int n_tiles, const void *tiles_in, const void *tiles_out, const int32_t *out_count) {
+    const int rc = check_retire_args(nx, ny, noise, eps);
+    if (rc) return rc;
+    if (n_tiles < 0 || (n_tiles > 0 && (!tiles_in || !tiles_out)) || !out_count)
+        return fail(RTMI_E_ARG, "n_tiles must be >= 0 and tiles_in, tiles_out, out_count not NULL (got n_tiles = %d)", n_tiles);
+    return RTMI_OK;
+}
+
+// d_noise and d_in are device pointers; the survivors lie in *d_kept behind the one synchronisation of `st`
+int tiles_retire_impl(rtmi_ctx *c, int nx, int ny, const double *d_noise, double eps, int n, const int *d_in, int **d_kept, int32_t *out_count, hipStream_t st) {
+    const int rc = c->retire_ws.ensure(((size_t)3 * (size_t)n + 2) * sizeof(int));
+    if (rc) return rc;
+    int *keep = reinterpret_cast<int *>(c->retire_ws.p), *kept = keep + n, *slots = kept + n, *d_meta = slots + n;
+    hipLaunchKernelGGL(adaptive_retire_kernel, dim3((unsigned)(((long long)n * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_noise, d_in, n, tiles_x_of(nx), nx,
+                       0, 0, nx, ny, eps, keep);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(kCompactBlock), 0, st, keep, d_in, nullptr, n, kept, slots, d_meta, -1, nullptr, tiles_x_of(nx), 0, 0,
+                       nx, ny);
+    HIP_TRY(hipGetLastError());
+    int meta[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(meta, d_meta, sizeof meta, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out_count = meta[0];
+    *d_kept = kept;
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_tiles_retire_device(rtmi_ctx *c, int32_t nx, int32_t ny, const void *d_noise, double eps, int32_t n_tiles, const void *d_tiles_in,
+                                         void *d_tiles_out, int32_t *out_count, void *stream) {
+    int rc = check_tiles_retire_args(nx, ny, d_noise, eps, n_tiles, d_tiles_in, d_tiles_out, out_count);
+    if (rc) return rc;
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    *out_count = 0;
+    if (n_tiles == 0) return RTMI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = stream_of(c, stream);
+    int *kept = nullptr;
+    rc = tiles_retire_impl(c, nx, ny, as<const double>(d_noise), eps, n_tiles, as<const int>(d_tiles_in), &kept, out_count, st);
+    if (rc || *out_count == 0) return rc;
+    HIP_TRY(hipMemcpyAsync(d_tiles_out, kept, (size_t)*out_count * sizeof(int), hipMemcpyDeviceToDevice, st)); // in stream order: ahead of the caller's next call
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_tiles_retire(rtmi_ctx *c, int32_t nx, int32_t ny, const double *noise, double eps, int32_t n_tiles, const int32_t *tiles_in,
+                                  int32_t *tiles_out, int32_t *out_count) {
+    int rc = check_tiles_retire_args(nx, ny, noise, eps, n_tiles, tiles_in, tiles_out, out_count);
+    if (rc) return rc;
+    const int n_frame_tiles = tiles_x_of(nx) * tiles_x_of(ny);
+    for (int k = 0; k < n_tiles; ++k)
+        if (tiles_in[k] < 0 || tiles_in[k] >= n_frame_tiles) return fail(RTMI_E_ARG, "tiles_in[%d] = %d, the frame has %d tiles", k, tiles_in[k], n_frame_tiles);
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    *out_count = 0;
+    if (n_tiles == 0) return RTMI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HostIo io(c);
+    double *d_noise;
+    int *d_in;
+    io.in(&d_noise, (size_t)nx * (size_t)ny, noise); io.in(&d_in, (size_t)n_tiles, tiles_in);
+    rc = io.stage();
+    if (rc) return rc;
+    int *kept = nullptr;
+    rc = tiles_retire_impl(c, nx, ny, d_noise, eps, n_tiles, d_in, &kept, out_count, c->stream);
+    if (rc || *out_count == 0) return rc;
+    HIP_TRY(hipMemcpy(tiles_out, kept, (size_t)*out_count * sizeof(int), hipMemcpyDeviceToHost));
+    return RTMI_OK;
 }
