@@ -616,6 +616,36 @@
           (finally (call-int "rtmi_scene_destroy" scn))))
       (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
 
+(defn render-rays-ris
+  "render-rays-mis whose light is chosen by looking at the vertex (rtmi_render_rays_ris, THE PROPOSAL RULE of rtmi.h): every listed light (at most
+  32) proposes one point at each Lambertian vertex, each proposal is weighed by what it would contribute if it were visible, and a one-pass weighted
+  reservoir keeps the one the shadow ray is sent to.  The path and the closing emission are render-rays-mis'; there is no light choice.  `lights` as
+  for render-rays-nee (required; an empty list is render-rays).  Returns render-rays-nee's map."
+  [scene rays n-groups group lights & {:keys [keys seed ctr0 depth device precision first-ray state]
+                                       :or {seed 0x5eed0002 ctr0 0 depth 50 device 0 precision 0 first-ray 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        n    (* n-groups group)
+        rs   (double-array rays)
+        ks   (long-array (or keys (for [g (range n-groups) r (range group)] (sample-key seed g (+ first-ray r)))))
+        lp   (int-array (if (seq lights) lights [0]))
+        nl   (count lights)
+        st   (double-array (or state (* 10 n-groups)))
+        mean (double-array (* 3 n-groups))
+        err  (double-array n-groups)
+        out  (double-array (* 3 n))
+        cnt  (long-array 4)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_rays_ris" scn (int precision) (int n-groups) (int group) (int first-ray) rs ks (long seed) (int ctr0)
+                           (int depth) (int nl) lp st mean err out cnt))
+          {:mean mean :stderr err :rays out :state st :segments (aget cnt 0) :total-rays (aget cnt 1)
+           :shadow-rays (aget cnt 2) :shadow-rays-occluded (aget cnt 3)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
 (defn render-lit
   "A light-sampled nx x ny frame of scene {:camera :world} from its own camera, the camera rays built on the device (rtmi_render_lit): samples
   [s-first, s-first + ns) of every pixel -- the keys, film jitter, lens draws and streams of `render` -- under `estimator` 0 (the plain path:
@@ -1044,6 +1074,40 @@
         (try
           (check (call-int "rtmi_render_lit_tiles" scn (int precision) (int nx) (int ny) (int s-first) (int ns) (int depth) (long seed) (int estimator)
                            (int nl) lp (int light-choice) (int (if volume 1 0)) (int nt) tl st lin rgb8 err out cam cnt))
+          {:linear lin :rgb8 rgb8 :stderr err :state st :rays out :camera cam :segments (aget cnt 0) :total-rays (aget cnt 1)
+           :shadow-rays (aget cnt 2) :shadow-rays-occluded (aget cnt 3)}
+          (finally (call-int "rtmi_scene_destroy" scn))))
+      (finally (call-int "rtmi_shutdown" (.getValue ctx))))))
+
+(defn render-lit-ris
+  "render-lit-tiles under THE PROPOSAL RULE of rtmi.h (rtmi_render_lit_ris): the frame of the scene's own camera whose every light proposes a point
+  at each Lambertian vertex, one shadow ray sent to the candidate a weighted reservoir keeps.  `tiles`: strictly ascending global tile indices, or
+  nil for every tile of the frame in ascending order, which reproduces every output of the whole-frame call.  `frame`, the in-place arrays and the
+  returned map are render-lit-tiles'; there is no estimator, light choice or volume form."
+  [scene nx ny ns lights tiles frame & {:keys [seed depth device precision s-first]
+                                        :or {seed 0x5eed0002 depth 50 device 0 precision 0 s-first 0}}]
+  (let [f    (flatten-scene scene)
+        ctx  (PointerByReference.)
+        npx  (* nx ny)
+        tiles (or tiles (range (* (quot (+ nx 7) 8) (quot (+ ny 7) 8))))
+        nt   (count tiles)
+        n    (* nt 64 ns)
+        lp   (int-array (if (seq lights) lights [0]))
+        nl   (count lights)
+        tl   (int-array (if (seq tiles) tiles [0]))
+        st   (double-array (or (:state frame) (* 10 npx)))
+        lin  (double-array (or (:linear frame) (* 3 npx)))
+        rgb8 (byte-array (or (:rgb8 frame) (* 3 npx)))
+        err  (double-array (or (:stderr frame) npx))
+        out  (double-array (max 1 (* 3 n)))
+        cam  (double-array (max 1 (* 8 n)))
+        cnt  (long-array 4)]
+    (check (call-int "rtmi_init" (int device) (int 0) ctx))
+    (try
+      (let [scn (create-scene! (.getValue ctx) f)]
+        (try
+          (check (call-int "rtmi_render_lit_ris" scn (int precision) (int nx) (int ny) (int s-first) (int ns) (int depth) (long seed)
+                           (int nl) lp (int nt) tl st lin rgb8 err out cam cnt))
           {:linear lin :rgb8 rgb8 :stderr err :state st :rays out :camera cam :segments (aget cnt 0) :total-rays (aget cnt 1)
            :shadow-rays (aget cnt 2) :shadow-rays-occluded (aget cnt 3)}
           (finally (call-int "rtmi_scene_destroy" scn))))

@@ -1028,6 +1028,73 @@ int rtmi_render_lit_tiles_device(rtmi_scene *scene, int32_t precision, int32_t n
                                  void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera,
                                  void *d_out_counters, void *stream);
 
+/* ---- light-sampled paths whose every lamp proposes a point: importance choice among the lights, one shadow ray per vertex ----
+ * The NEE and MIS calls choose their light without looking at the vertex (uniformly, or by power).  In a room with many lamps a point is lit by the one or
+ * two next to it, and a blind pick spends most shadow rays on lamps far away or facing the other way.  Here every listed light (at most
+ * RTMI_DIRECT_MAX_LIGHTS) proposes one point at every vertex, each proposal is weighed by what it would contribute if it were visible, and a one-pass
+ * weighted reservoir keeps one: the shadow ray goes where the light is.  These are new entries beside the MIS calls; the MIS siblings' arguments without
+ * light_choice.
+ * THE PROPOSAL RULE, operation by operation as its siblings: every product, sum, difference and quotient is one IEEE double operation in the order written,
+ * only + - * / sqrt occur.  Where nothing else is said THE MIS RULE holds; K, j, nl, T and rtmi_sample_key are as defined there.
+ *   1. Vertices: light samples are taken at the NEE rule's vertices (its step 1).  The path's own stream, rays, hits, scatters and segment count stay
+ *      rtmi_render_rays' bit for bit.
+ *   2. Candidates: every listed light l = 0 .. nl - 1 proposes one point, in list order: the NEE rule's steps 3 and 4 (point, d, d2, cp, cl, the far-side
+ *      rule, the "no ray" conditions, w) with the stream keyed rtmi_sample_key(K, j, 4*l) at draw 0 -- light 0 uses the MIS rule's own stream and no light
+ *      lands on streams 1 or 2.  x_l = w_l (every light proposes: the pick's inverse probability q is 1.0); m_l = x_l / (1.0 + x_l), or 1.0 if x_l is +inf.
+ *      lum_l = (Le.r + Le.g) + Le.b, computed on the host and travelling with the light table; w^_l = lum_l * m_l.  A candidate is LIVE if it built a ray
+ *      and w^_l > 0 and w^_l < +inf (a NaN fails).
+ *   3. The choice, a one-pass weighted reservoir: S starts at +0.0; for each live candidate in list order S = S + w^_l; the first live candidate is taken;
+ *      a later one replaces the chosen candidate if u_l * S < w^_l, u_l = the FP64 uniform of draw l of the stream keyed rtmi_sample_key(K, j, 1).
+ *      A vertex with no live candidate builds no ray.
+ *   4. The ray is the chosen candidate's; the any-hit search runs with the t-range (0.001, 1 - 0.001), as in the NEE rule.
+ *   5. The contribution: if the search finds nothing, r = S / w^_sel and accum.c = accum.c + (double)T.c * ((Le_sel.c * m_sel) * r) per channel.
+ *   6. The lobe value g: the MIS rule's step 6, unchanged.
+ *   7. The closing emission: the MIS rule's step 7 with q_l' = 1.0 for every light.  A light whose lum_l is not > 0 can never be chosen: for this step it
+ *      does not count as a sampled light and its emission is kept whole (as the power pick treats omega = 0; decided on the host).
+ *   8. Unchanged from the MIS rule: nl == 0 (the call IS rtmi_render_rays), a ConstantMedium (RTMI_E_UNSUPPORTED), the RTMI_F32 scope (candidates, weights
+ *      and g are doubles whatever the precision), the four counters ([2] counts the chosen candidates), the invariance under chunks and workspace passes.
+ *   Over the choice the expectation of step 5 is the sum over l of Le_l * m_l * V_l: the light strategy "one point on every light", whose density on light l
+ *   is 1 / area_l; m_l depends on the proposed point alone, and step 7 gives the scatter the complementary share at the point it found.  Every
+ *   contribution is at most T.c * (Le_sel.c / lum_sel) * (the sum of lum_k over the lights).  With one light of positive emission r is exactly 1.0 and every
+ *   output equals the MIS rule's under light_choice 0 -- except at a vertex whose ray the MIS rule builds with a share m of +0.0 (w underflowed): that
+ *   candidate is not live here, so the vertex builds no ray: state 3, zeros for l, d, w, x, m in the log, and counter [2] does not count it.  Its
+ *   contribution is +0.0 under either rule, so the radiance is the same.
+ * rtmi_probe_paths_ris: rtmi_probe_paths_mis without light_choice.  log (may be NULL): [n][max_seg][RTMI_RIS_REC] doubles per logged vertex: [0..27] the
+ *   RTMI_MIS_REC values for the chosen candidate ([12] the state, 3 = a light-sampled vertex with no live candidate: l, d, w, x, m are then zeros);
+ *   [28] S, [29] w^_sel, [30] r, [31] the number of live candidates (zeros where the vertex takes no light sample).
+ * rtmi_render_rays_ris*: rtmi_render_rays_mis* without light_choice.
+ * rtmi_render_lit_ris*: the frame of the scene's own camera: rtmi_render_lit_tiles*' arguments without estimator, light_choice and volume.  tiles NULL:
+ *   the whole frame -- n_tiles is not read, the rows, out_rays, out_camera and every layout are rtmi_render_lit's (the SRC_CAMERA kernels).  tiles not
+ *   NULL: THE TILE ORDER, the in/out whole-frame buffers and every other word of rtmi_render_lit_tiles*.  THE FRAME RULE, the RTMI_RAYS_REC state and the
+ *   counters are the siblings'.
+ * Errors: the MIS calls' (rtmi_render_lit_tiles*' for the frame with a list, rtmi_render_lit*'s without), in their order, less the checks of the removed
+ * arguments.  A failed call launches nothing and writes nothing.  Out of scope: media, more than RTMI_DIRECT_MAX_LIGHTS lights, proposals at metal or
+ * glass, reuse of candidates between pixels or frames. */
+#define RTMI_RIS_REC 32
+/* host buffers; synchronous */
+int rtmi_render_rays_ris(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first,
+                         const double *rays, const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth,
+                         int32_t n_lights, const int32_t *light_prims,
+                         double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters);
+/* every d_ pointer a device pointer (light_prims stays a host array); asynchronous on `stream` with rtmi_render_device's stream semantics */
+int rtmi_render_rays_ris_device(rtmi_scene *scene, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first,
+                                const void *d_rays, const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth,
+                                int32_t n_lights, const int32_t *light_prims,
+                                void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream);
+int rtmi_probe_paths_ris(rtmi_scene *scene, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
+                         int32_t n_lights, const int32_t *light_prims, double *out_rgb, uint64_t *out_nseg, double *out_weight,
+                         double *log, int32_t max_seg, int32_t *out_nlog);
+/* host buffers; synchronous */
+int rtmi_render_lit_ris(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                        int32_t n_lights, const int32_t *light_prims, int32_t n_tiles, const int32_t *tiles,
+                        double *state, double *out_linear, uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera,
+                        uint64_t *out_counters);
+/* every d_ pointer a device pointer, d_tiles among them (light_prims stays a host array); asynchronous on `stream` with rtmi_render_device's stream semantics */
+int rtmi_render_lit_ris_device(rtmi_scene *scene, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                               int32_t n_lights, const int32_t *light_prims, int32_t n_tiles, const void *d_tiles,
+                               void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera,
+                               void *d_out_counters, void *stream);
+
 /* rtmi_tiles_retire*: the stateless rtmi_adaptive_retire -- the decision of that call on a list the caller holds; no frame of the context is read or changed.
  *   noise: [ny][nx] doubles of the whole frame, row 0 at the top: rtmi_render_lit_tiles' out_stderr or rtmi_denoise's filtered error as it is.  A listed tile
  *   SURVIVES if any of its pixels inside the image fails noise <= eps, the comparison written exactly so: NaN and +inf fail, -inf passes (a pixel of one

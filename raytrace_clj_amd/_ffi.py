@@ -47,6 +47,7 @@ SYMBOLS = [
     "rtmi_render_lit", "rtmi_render_lit_device",
     "rtmi_render_rays_vol", "rtmi_render_rays_vol_device", "rtmi_probe_paths_vol", "rtmi_render_lit_vol", "rtmi_render_lit_vol_device",
     "rtmi_render_lit_tiles", "rtmi_render_lit_tiles_device", "rtmi_tiles_retire", "rtmi_tiles_retire_device",
+    "rtmi_render_rays_ris", "rtmi_render_rays_ris_device", "rtmi_probe_paths_ris", "rtmi_render_lit_ris", "rtmi_render_lit_ris_device",
 ]
 
 F64, F32 = 0, 1
@@ -63,6 +64,7 @@ DIRECT_REC = 4  # doubles per point record of rtmi_direct_irradiance / rtmi_rend
 NEE_REC = 24  # doubles per logged vertex of rtmi_probe_paths_nee: SEG_REC's twelve, state, light, d xyz, w, T rgb, contribution rgb
 MIS_REC = 28  # doubles per logged vertex of rtmi_probe_paths_mis: NEE_REC's twenty-four, x, m, g, x' (closing vertex)
 VOL_REC = 29  # doubles per logged vertex of rtmi_probe_paths_vol: MIS_REC's twenty-eight, then 1.0 at an Isotropic light-sampled vertex
+RIS_REC = 32  # doubles per logged vertex of rtmi_probe_paths_ris: MIS_REC's twenty-eight for the chosen candidate, then S, w^ of the chosen one, r, live candidates
 DIRECT_MAX_LIGHTS = 32  # RTMI_DIRECT_MAX_LIGHTS: lights one call samples
 EDIT_STREAM_MAX_BYTES = 32768  # RTMI_EDIT_STREAM_MAX_BYTES: changed row payload one rtmi_scene_set_materials_stream call carries
 
@@ -202,6 +204,11 @@ def lib():
     L.rtmi_render_lit_vol_device.argtypes = L.rtmi_render_lit_device.argtypes
     L.rtmi_render_lit_tiles.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rtmi_render_lit_tiles_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rtmi_render_rays_ris.argtypes = L.rtmi_render_rays_nee.argtypes
+    L.rtmi_render_rays_ris_device.argtypes = L.rtmi_render_rays_nee_device.argtypes
+    L.rtmi_probe_paths_ris.argtypes = [vp, i32, i32, vp, vp, u64, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    L.rtmi_render_lit_ris.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.rtmi_render_lit_ris_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rtmi_tiles_retire.argtypes = [vp, i32, i32, vp, dbl, i32, vp, vp, C.POINTER(i32)]
     L.rtmi_tiles_retire_device.argtypes = [vp, i32, i32, vp, dbl, i32, vp, vp, C.POINTER(i32), vp]
     for name in SYMBOLS:

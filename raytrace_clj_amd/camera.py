@@ -435,6 +435,51 @@ def mis_closing(g, normals, dirs, t, area, q):
     return x, m
 
 
+def ris_candidates(points, normals, lights, path_keys, segments):
+    """Step 2 of the proposal rule (include/rtmi.h): every light of lights [nl, LIGHT_REC] proposes one point at every vertex -- nee_samples with the
+    stream keyed sample_key(K, j, 4 * l) for light l, K = path_keys [n] and j = segments [n] -- and is weighed: x = w (q = 1: mis_weight),
+    m = x / (1 + x), lum = (Le.r + Le.g) + Le.b, what = lum * m; a candidate is live if it built a ray and 0 < what < +inf (a NaN fails).
+    -> (d [n, nl, 3], w [n, nl], m [n, nl], what [n, nl], live [n, nl] bool, lum [nl])."""
+    from . import util
+    points, normals = np.asarray(points, np.float64).reshape(-1, 3), np.asarray(normals, np.float64).reshape(-1, 3)
+    lights = np.asarray(lights, np.float64).reshape(-1, LIGHT_REC)
+    path_keys, segments = np.asarray(path_keys, np.uint64).reshape(-1), np.asarray(segments, np.uint64).reshape(-1)
+    n, nl = len(points), len(lights)
+    lum = (lights[:, 7] + lights[:, 8]) + lights[:, 9]
+    d, w, m, what, live = np.zeros((n, nl, 3)), np.zeros((n, nl)), np.zeros((n, nl)), np.zeros((n, nl)), np.zeros((n, nl), bool)
+    for l in range(nl):
+        keys = util.sample_keys(path_keys, segments, np.full(n, 4 * l, np.uint64))
+        _, d[:, l], w[:, l], built = nee_samples(points, normals, lights, keys, keys, light=np.full(n, l, np.int64))
+        _, m[:, l] = mis_weight(w[:, l], 1.0)
+        with np.errstate(all="ignore"):
+            what[:, l] = lum[l] * m[:, l]
+        live[:, l] = built & (what[:, l] > 0.0) & (what[:, l] < np.inf)
+    return d, w, m, what, live, lum
+
+
+def ris_choose(what, live, path_keys, segments):
+    """Step 3 of the proposal rule: the one-pass weighted reservoir over the candidates of ris_candidates, in list order.  S starts at +0.0 and grows
+    by what_l at every live candidate; the first live candidate is taken, a later one replaces it if u_l * S < what_l, u_l = draw l of the stream keyed
+    sample_key(K, j, 1).  -> (chosen [n] int (0 where none is live), S [n], what of the chosen [n] (0 where none), r = S / what (0 where none),
+    live count [n] int)."""
+    from . import util
+    what, live = np.asarray(what, np.float64), np.asarray(live, bool)
+    path_keys, segments = np.asarray(path_keys, np.uint64).reshape(-1), np.asarray(segments, np.uint64).reshape(-1)
+    n, nl = what.shape
+    kc = util.sample_keys(path_keys, segments, np.full(n, 1, np.uint64))
+    S, sel, sel_what, count = np.zeros(n), np.zeros(n, np.int64), np.zeros(n), np.zeros(n, np.int64)
+    for l in range(nl):
+        with np.errstate(all="ignore"):
+            S = np.where(live[:, l], S + what[:, l], S)
+            take = live[:, l] & ((count == 0) | (util.draw_uniforms(kc, l) * S < what[:, l]))
+        sel = np.where(take, l, sel)
+        sel_what = np.where(take, what[:, l], sel_what)
+        count = count + live[:, l]
+    with np.errstate(all="ignore"):
+        r = np.where(count > 0, S / sel_what, 0.0)
+    return sel, S, sel_what, r, count
+
+
 INV_4PI = float.fromhex("0x1.45f306dc9c883p-4")
 
 

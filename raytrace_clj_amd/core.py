@@ -672,7 +672,8 @@ class DeviceScene:
         ctr0), grouped per pixel): chunks of `chunk` samples per pixel folded into one state, keys derived from (seed, pixel, sample) ->
         (linear [ny, nx, 3] = the per-pixel mean, rgb8 = the frame's 8-bit quantiser of it (Context.denoise with no pass), stderr [ny, nx], counters
         summed over the chunks); row 0 = top.  The result does not depend on `chunk`.  nee: the paths sample the lights (render_rays_nee with
-        `lights`; four counters); nee="mis": under multiple importance sampling (render_rays_mis with `lights` and `light_choice`)."""
+        `lights`; four counters); nee="mis": under multiple importance sampling (render_rays_mis with `lights` and `light_choice`); nee="ris":
+        under the proposal rule (render_rays_ris with `lights`)."""
         if chunk <= 0 or ns <= 0:
             raise ValueError("ns and chunk must be > 0")
         def rays_of(k, n):
@@ -680,9 +681,11 @@ class DeviceScene:
         if isinstance(nee, str) and nee in ("vol-nee", "vol-mis"):  # the volume rule: scenes that hold a ConstantMedium
             return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_vol, 4, estimator=nee[4:], lights=lights, light_choice=light_choice,
                                      seed=seed, depth=depth, precision=precision)
+        if isinstance(nee, str) and nee == "ris":  # the proposal rule: every light proposes a point (light_choice is not looked at)
+            return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_ris, 4, lights=lights, seed=seed, depth=depth, precision=precision)
         if isinstance(nee, str):
             if nee != "mis":
-                raise ValueError("nee is False, True, \"mis\", \"vol-nee\" or \"vol-mis\" (got %r)" % nee)
+                raise ValueError("nee is False, True, \"mis\", \"ris\", \"vol-nee\" or \"vol-mis\" (got %r)" % nee)
             return self._fold_chunks(nx, ny, ns, chunk, rays_of, self.render_rays_mis, 4, lights=lights, light_choice=light_choice, seed=seed, depth=depth,
                                      precision=precision)
         if nee:
@@ -744,6 +747,89 @@ class DeviceScene:
         check(_ffi.lib().rtmi_render_rays_mis_device(self.handle, _PRECISION[precision], int(n_groups), int(group), int(first), ptr(rays), ptr(keys),
                                                      int(seed), int(ctr0), int(depth), n_listed, ptr(lights), self._light_choice(light_choice), ptr(state),
                                                      ptr(out_mean), ptr(out_stderr), ptr(out_rays), ptr(out_counters), ptr(stream)))
+
+    # ---- every lamp proposes a point, one shadow ray is sent: importance choice among the lights (THE PROPOSAL RULE of include/rtmi.h) ----------
+    def render_rays_ris(self, rays, group=1, lights=None, keys=None, seed=RENDER_SEED, ctr0=0, depth=DEFAULT_DEPTH, precision="f64", first=0,
+                        state=None, return_rays=False):
+        """render_rays_mis whose light is chosen by looking at the vertex (rtmi_render_rays_ris): every listed light (at most DIRECT_MAX_LIGHTS)
+        proposes one point, each proposal is weighed by lum * m -- what it would contribute if it were visible -- and a one-pass weighted reservoir
+        keeps one, whose shadow ray counts with S / w^ on top of the balance heuristic's share.  The path and the closing emission are
+        render_rays_mis'; with one lamp so is every bit of the result.  camera.ris_candidates and ris_choose restate the rule.
+        -> render_rays_nee's tuple."""
+        rays, group, n_groups, keys = self._rays_inputs(rays, group, keys, state)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        mean, err, cnt = np.zeros((n_groups, 3), np.float64), np.zeros(n_groups, np.float64), np.zeros(4, np.uint64)
+        out = np.zeros((len(rays), 3), np.float64) if return_rays else None
+        check(_ffi.lib().rtmi_render_rays_ris(self.handle, _PRECISION[precision], n_groups, group, int(first), ptr(rays), ptr(keys), int(seed), int(ctr0),
+                                              int(depth), n_listed, ptr(lights), ptr(state), ptr(mean), ptr(err), ptr(out), ptr(cnt)))
+        return mean, err, cnt, out
+
+    def render_rays_ris_device(self, n_groups, group, rays, out_mean, out_stderr, lights=None, keys=None, seed=RENDER_SEED, ctr0=0,
+                               depth=DEFAULT_DEPTH, precision="f64", first=0, state=None, out_rays=None, out_counters=None, stream=None):
+        """render_rays_ris on HBM-resident buffers (lights stays a host list; out_counters: four uint64); asynchronous, render_device's stream
+        semantics.  A state's count is the caller's contract: it is not read back."""
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        check(_ffi.lib().rtmi_render_rays_ris_device(self.handle, _PRECISION[precision], int(n_groups), int(group), int(first), ptr(rays), ptr(keys),
+                                                     int(seed), int(ctr0), int(depth), n_listed, ptr(lights), ptr(state), ptr(out_mean), ptr(out_stderr),
+                                                     ptr(out_rays), ptr(out_counters), ptr(stream)))
+
+    def render_lit_ris(self, nx, ny, ns, chunk=None, lights=None, depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", return_rays=False,
+                       return_camera=False, tiles=None, s_first=0, linear=None, rgb8=None, stderr=None, state=None):
+        """The frame of the scene's own camera under the proposal rule (rtmi_render_lit_ris).  tiles None: render_lit's call and tuple -- an
+        nx x ny x ns frame, `chunk` samples per call through one state.  tiles (int32, strictly ascending global tile indices): render_lit_tiles'
+        call -- samples [s_first, s_first + ns) of the listed tiles' pixels folded IN PLACE into the caller's whole-frame linear, rgb8 (or None),
+        stderr and state (or None) -> render_lit_tiles' tuple (counters[, rays][, camera]) in THE TILE ORDER."""
+        nx, ny, ns = int(nx), int(ny), int(ns)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        entry = _ffi.lib().rtmi_render_lit_ris
+        if tiles is not None:
+            tiles = np.ascontiguousarray(tiles, np.int32).reshape(-1)
+            for name, a, shape, dt in (("linear", linear, (ny, nx, 3), np.float64), ("rgb8", rgb8, (ny, nx, 3), np.uint8),
+                                       ("stderr", stderr, (ny, nx), np.float64), ("state", state, (nx * ny, _ffi.RAYS_REC), np.float64)):
+                if (a is None and name in ("linear", "stderr")) or (
+                        a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous)):
+                    raise ValueError("%s must be a contiguous %s array of shape %r: it is written in place" % (name, np.dtype(dt).name, shape))
+            cnt = np.zeros(4, np.uint64)
+            rays = np.zeros((len(tiles) * 64, ns, 3), np.float64) if return_rays else None
+            cam = np.zeros((len(tiles) * 64, ns, 8), np.float64) if return_camera else None
+            held = tiles if len(tiles) else np.zeros(1, np.int32)  # (an empty list is still a list: a pointer that is not NULL)
+            check(entry(self.handle, _PRECISION[precision], nx, ny, int(s_first), ns, int(depth), int(seed), n_listed, ptr(lights), len(tiles), ptr(held),
+                        ptr(state), ptr(linear), ptr(rgb8), ptr(stderr), ptr(rays), ptr(cam), ptr(cnt)))
+            return (cnt,) + ((rays,) if return_rays else ()) + ((cam,) if return_camera else ())
+        chunk = ns if chunk is None else int(chunk)
+        if nx <= 0 or ny <= 0 or ns <= 0 or chunk <= 0:
+            raise ValueError("nx, ny, ns and chunk must be > 0")
+        npx = nx * ny
+        lin, q, err = np.zeros((ny, nx, 3), np.float64), np.zeros((ny, nx, 3), np.uint8), np.zeros((ny, nx), np.float64)
+        state = np.zeros((npx, _ffi.RAYS_REC), np.float64) if chunk < ns else None
+        total = np.zeros(4, np.uint64)
+        rays = np.zeros((npx, ns, 3), np.float64) if return_rays else None
+        cam = np.zeros((npx, ns, 8), np.float64) if return_camera else None
+        k = 0
+        while k < ns:
+            n = min(chunk, ns - k)
+            cnt = np.zeros(4, np.uint64)
+            r = np.zeros((npx, n, 3), np.float64) if return_rays else None
+            c = np.zeros((npx, n, 8), np.float64) if return_camera else None
+            check(entry(self.handle, _PRECISION[precision], nx, ny, k, n, int(depth), int(seed), n_listed, ptr(lights), 0, None,
+                        ptr(state), ptr(lin), ptr(q), ptr(err), ptr(r), ptr(c), ptr(cnt)))
+            total += cnt
+            if return_rays:
+                rays[:, k:k + n] = r
+            if return_camera:
+                cam[:, k:k + n] = c
+            k += n
+        return (lin, q, err, total) + ((rays,) if return_rays else ()) + ((cam,) if return_camera else ())
+
+    def render_lit_ris_device(self, nx, ny, s_first, s_count, out_linear, out_stderr, out_rgb8=None, lights=None, n_tiles=0, tiles=None,
+                              depth=DEFAULT_DEPTH, seed=RENDER_SEED, precision="f64", state=None, out_rays=None, out_camera=None, out_counters=None,
+                              stream=None):
+        """rtmi_render_lit_ris_device on HBM-resident buffers: tiles None is render_lit_device's call, a device int32 list (its first n_tiles
+        entries) render_lit_tiles_device's; asynchronous, render_device's stream semantics."""
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        check(_ffi.lib().rtmi_render_lit_ris_device(self.handle, _PRECISION[precision], int(nx), int(ny), int(s_first), int(s_count), int(depth), int(seed),
+                                                    n_listed, ptr(lights), int(n_tiles), ptr(tiles), ptr(state), ptr(out_linear), ptr(out_rgb8),
+                                                    ptr(out_stderr), ptr(out_rays), ptr(out_camera), ptr(out_counters), ptr(stream)))
 
     # ---- light-sampled paths through participating media (THE VOLUME RULE of include/rtmi.h) -------------------------------------------------
     @staticmethod
@@ -933,6 +1019,7 @@ class DeviceScene:
         """A light-sampled frame refined adaptively: every 8x8 tile listed, then rounds of render_lit_tiles (`first` samples, default chunk, then
         `chunk`) each followed by tiles_retire of the tiles whose standard error is <= eps everywhere -- with denoised=True of those whose FILTERED
         standard error is (render_features once, denoise per round, as refine_adaptive_denoised) -- until no tile is listed or ns is reached.
+        estimator "ris": the rounds go through render_lit_ris (the proposal rule; volume and light_choice do not apply).
         -> (linear, rgb8, stderr, samples [ny, nx] int32, counters summed over the rounds, rounds = [(k, tiles listed after the round's
         retirement, int32)]).  A pixel whose tile took n samples equals render_lit(ns = n) there bit for bit.  With torch the buffers and the list
         stay in HBM across the rounds and only the number of survivors comes back per round."""
@@ -941,6 +1028,10 @@ class DeviceScene:
             raise ValueError("nx, ny, ns, chunk and first must be > 0")
         n_all = ((nx + _ffi.TILE - 1) // _ffi.TILE) * ((ny + _ffi.TILE - 1) // _ffi.TILE)
         kw = dict(estimator=estimator, volume=volume, lights=lights, light_choice=light_choice, depth=depth, seed=seed, precision=precision)
+        ris = isinstance(estimator, str) and estimator == "ris"  # the proposal rule's frame call: no estimator, light_choice or volume
+        if ris and volume:
+            raise ValueError("estimator \"ris\" has no volume form")
+        kr = dict(lights=lights, depth=depth, seed=seed, precision=precision)
         dn = (int(iterations), float(sigma_c), float(sigma_n), float(sigma_a), float(sigma_d))
         total, rounds, k, n_tiles = np.zeros(4, np.uint64), [], 0, n_all
         if _ffi.torch is None:  # host arrays: every round stages the frame
@@ -949,7 +1040,10 @@ class DeviceScene:
             ft = self.render_features(nx, ny, na, seed, precision)[0] if denoised else None
             while k < ns and len(tiles):
                 n = min(first if k == 0 else chunk, ns - k)
-                total += self.render_lit_tiles(nx, ny, k, n, tiles, lin, q, err, state, **kw)[0]
+                if ris:
+                    total += self.render_lit_ris(nx, ny, n, tiles=tiles, s_first=k, linear=lin, rgb8=q, stderr=err, state=state, **kr)[0]
+                else:
+                    total += self.render_lit_tiles(nx, ny, k, n, tiles, lin, q, err, state, **kw)[0]
                 k += n
                 tiles = self.ctx.tiles_retire(self.ctx.denoise(lin, err, ft, *dn)[2] if denoised else err, eps, tiles)
                 rounds.append((k, tiles))
@@ -970,7 +1064,10 @@ class DeviceScene:
             kept = []
             while k < ns and n_tiles:
                 n = min(first if k == 0 else chunk, ns - k)
-                self.render_lit_tiles_device(nx, ny, k, n, n_tiles, tiles, lin, err, q, state=state, out_counters=cnt, stream=stream, **kw)
+                if ris:
+                    self.render_lit_ris_device(nx, ny, k, n, lin, err, q, n_tiles=n_tiles, tiles=tiles, state=state, out_counters=cnt, stream=stream, **kr)
+                else:
+                    self.render_lit_tiles_device(nx, ny, k, n, n_tiles, tiles, lin, err, q, state=state, out_counters=cnt, stream=stream, **kw)
                 k += n
                 if denoised:
                     self.ctx.denoise_device(nx, ny, lin, err, ft, None, None, ferr, *dn, stream=stream)
@@ -1288,6 +1385,20 @@ class DeviceScene:
         log = np.zeros((n, max_seg, _ffi.MIS_REC)) if max_seg else None
         check(_ffi.lib().rtmi_probe_paths_mis(self.handle, _PRECISION[precision], n, ptr(rays), ptr(keys), ctr0, depth, n_listed, ptr(lights),
                                               self._light_choice(light_choice), ptr(rgb), ptr(nseg), ptr(weight), ptr(log), max_seg, ptr(nlog)))
+        return rgb, nseg, log, nlog, weight
+
+    def probe_paths_ris(self, rays, keys, lights=None, depth=DEFAULT_DEPTH, ctr0=0, max_seg=0, precision="f64"):
+        """probe_paths_mis for the proposal rule (rtmi_probe_paths_ris) -> (rgb [n, 3], segment counts, log [n, max_seg, RIS_REC] or None, logged
+        vertices per path, weight float64 [n] = the factor on the closing emission).  A log row: MIS_REC's twenty-eight values for the chosen
+        candidate, then S, w^ of the chosen candidate, r = S / w^ and the number of live candidates."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+        keys = np.ascontiguousarray(keys, np.uint64)
+        n = len(rays)
+        lights, n_listed, _ = (None, 0, 0) if lights is None else self._direct_lights(lights)
+        rgb, nseg, nlog, weight = np.zeros((n, 3)), np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        log = np.zeros((n, max_seg, _ffi.RIS_REC)) if max_seg else None
+        check(_ffi.lib().rtmi_probe_paths_ris(self.handle, _PRECISION[precision], n, ptr(rays), ptr(keys), ctr0, depth, n_listed, ptr(lights),
+                                              ptr(rgb), ptr(nseg), ptr(weight), ptr(log), max_seg, ptr(nlog)))
         return rgb, nseg, log, nlog, weight
 
     def probe_paths_vol(self, rays, keys, estimator="mis", lights=None, light_choice=0, depth=DEFAULT_DEPTH, ctr0=0, max_seg=0, precision="f64"):
@@ -1938,8 +2049,8 @@ LIT_ESTIMATORS = {"plain": 0, "nee": 1, "mis": 2}  # estimator of rtmi_render_li
 
 
 def _lit_flags(argv, panorama=False, orbit=False, nee=False, mis=False):
-    """-> (the other arguments, None or (estimator, light choice) of --lit [plain|nee|mis[:uniform|:power]], default mis); the modes it does not
-    combine with are refused here, before any device work"""
+    """-> (the other arguments, None or (estimator, light choice) of --lit [plain|nee|mis[:uniform|:power]|ris], default mis; ris: the proposal rule,
+    which has no light choice); the modes it does not combine with are refused here, before any device work"""
     rest, lit, k = [], None, 0
     while k < len(argv):
         a = argv[k]
@@ -1949,9 +2060,9 @@ def _lit_flags(argv, panorama=False, orbit=False, nee=False, mis=False):
             lit = ("mis", "uniform")
             if k + 1 < len(argv):
                 est, _, choice = argv[k + 1].partition(":")
-                if est in LIT_ESTIMATORS:
+                if est in LIT_ESTIMATORS or est == "ris":
                     if choice and (est != "mis" or choice not in MIS_CHOICES):
-                        raise SystemExit("--lit takes plain, nee, mis, mis:uniform or mis:power (got %r)" % argv[k + 1])
+                        raise SystemExit("--lit takes plain, nee, mis, mis:uniform, mis:power or ris (got %r)" % argv[k + 1])
                     lit = (est, choice or "uniform")
                     k += 1
         elif a.startswith("--lit"):
@@ -2089,7 +2200,8 @@ def main(argv=None):
     and the scatter share each lamp's emission by the balance heuristic; the light is picked uniformly, the default, or by power) as name.mis.ext.
     It is refused where --nee is.
     --lit [plain|nee|mis[:power]] also writes the frame of DeviceScene.render_lit (default mis): the samples the frame itself traces -- the same keys, jitter,
-    lens draws and streams, the camera rays built on the device -- under the plain estimator, the NEE rule or the MIS rule, as name.lit.ext.  With --chunk
+    lens draws and streams, the camera rays built on the device -- under the plain estimator, the NEE rule, the MIS rule or (--lit ris) the proposal
+    rule, where every lamp proposes a point at each vertex and one shadow ray is sent (DeviceScene.render_lit_ris), as name.lit.ext.  With --chunk
     K it is refined K samples at a time through one state (the same image).  It does not combine with --orbit, --panorama, --nee or --mis.
     --lit-vol [nee|mis[:power]] also writes the frame of DeviceScene.render_lit_vol (default mis) as name.vol.ext: --lit's frame under the volume rule,
     for the scenes that hold a ConstantMedium (final, the smoke cornell-box, subsurface) -- the vertices inside a medium sample the lights too and the
@@ -2257,7 +2369,9 @@ def main(argv=None):
             continue
         ds = DeviceScene(sc)
         try:
-            if lit_eps is None:
+            if lit_eps is None and mode[0] == "ris":
+                frame = ds.render_lit_ris(nx, ny, nr, chunk=chunk)[1]
+            elif lit_eps is None:
                 frame = (ds.render_lit_vol if volume else ds.render_lit)(nx, ny, nr, chunk=chunk, estimator=mode[0], light_choice=mode[1])[1]
             else:
                 more = {} if adaptive is not None else dict(denoised=True, na=FEATURE_SAMPLES if dn_samples is None else dn_samples, iterations=dn_iterations)

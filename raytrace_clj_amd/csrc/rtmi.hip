@@ -1856,15 +1856,88 @@ __device__ inline int nee_sampled_light(const NeeLights &nl, int orig) {
 // VOL (THE VOLUME RULE): `iso` lanes sit at an Isotropic scatter -- the record's normal is not read, the lobe is the sphere's 1 / 4 pi.  Both weights and
 // both lobe values are formed by every lane and selected: no divergent path.
 constexpr double kInv4Pi = 0x1.45f306dc9c883p-4;
-template <bool MIS = false, bool VOL = false>
+// The RIS instantiations' light table (set_ris_lights_kernel) carries, behind the MIS rows (whose q_l are all 1.0), lum_l = (Le.r + Le.g) + Le.b per light.
+constexpr int kRisRows = kMisRows + 2 + 2 * RTMI_DIRECT_MAX_LIGHTS;
+// What the choice of THE PROPOSAL RULE leaves behind the chosen candidate's ray: S, w^ and r = S / w^ of the chosen one, (Le * m) of it per channel, and
+// the number of live candidates.  All zeros where no candidate is live.
+struct RisPick { double S, what, r, pend[3]; int live; };
+// RIS (THE PROPOSAL RULE; with MIS, without VOL): every listed light proposes a point and a one-pass weighted reservoir keeps one.  The loop index is
+// wave-uniform: a light's record is read through the scalar cache, its kind decides one scalar branch for the wave, and in a sphere light's iteration all
+// 64 lanes run the disk rounds for the same light.  xmg = {x, m, g} of the chosen candidate; l, w and q are its as well.
+template <bool MIS = false, bool VOL = false, bool RIS = false>
 __device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsigned j, double px, double py, double pz, double nx, double ny, double nz,
-                                     double time, double *q, double &w, int &l, const double *D = nullptr, double *xmg = nullptr, bool iso = false) {
+                                     double time, double *q, double &w, int &l, const double *D = nullptr, double *xmg = nullptr, bool iso = false,
+                                     RisPick *pick = nullptr) {
     const double big = __builtin_inf();
     const double len2 = dot3(nx, ny, nz, nx, ny, nz);
     bool ok = want && ::fabs(px) < big && ::fabs(py) < big && ::fabs(pz) < big;
     if constexpr (VOL) ok = ok && (iso || (::fabs(nx) < big && ::fabs(ny) < big && ::fabs(nz) < big && len2 > 0.0));
     else ok = ok && ::fabs(nx) < big && ::fabs(ny) < big && ::fabs(nz) < big && len2 > 0.0;
     const bool valid = ok; // (MIS) the vertex itself is sound, whatever becomes of its light sample
+    if constexpr (RIS) {
+        static_assert(MIS && !VOL, "the proposal rule shares the MIS rule's lobe value and closing weight, and takes no medium");
+        const u64 kchoice = sample_key(K, (u64)j, 1ull);
+        const double len = ::sqrt(len2);
+        nx = nx / len; ny = ny / len; nz = nz / len;
+        { // step 6 of the MIS rule, unchanged
+            const double a = dot3(nx, ny, nz, D[0], D[1], D[2]), DD = dot3(D[0], D[1], D[2], D[0], D[1], D[2]);
+            xmg[2] = valid && a > 0.0 && DD > 0.0 ? ((a * a) * a) / ((DD * DD) * DD) : 0.0;
+        }
+        double S = 0.0, sel_what = 0.0, sel_w = 0.0, sel_m = 0.0, sel_dx = 0.0, sel_dy = 0.0, sel_dz = 0.0, pend0 = 0.0, pend1 = 0.0, pend2 = 0.0;
+        int sel = 0, live = 0;
+#pragma nounroll
+        for (unsigned k = 0; k < nl.n; ++k) { // nl.n and k are wave-uniform
+            typedef const __attribute__((address_space(4))) double *ConstRow;
+            ConstRow L = (ConstRow)(unsigned long long)(nl.rec + (size_t)k * kLightRec); // uniform data: scalar loads
+            const int kind = __builtin_amdgcn_readfirstlane((int)L[0]);
+            const double g0 = L[1], g1 = L[2], g2 = L[3], g3 = L[4], g4 = L[5], area = L[6];
+            const double lum = ((ConstRow)(unsigned long long)(nl.rec + kRisRows))[k];
+            const u64 key = sample_key(K, (u64)j, 4ull * (u64)k);
+            double qx, qy, qz, sx, sy, sz;
+            bool far = false;
+            if (kind == RTMI_PRIM_SPHERE || kind == RTMI_PRIM_UVSPHERE) { // one branch for the wave: every lane is in the disk rounds
+                Path<double> G;
+                seed_stream(G, key, 0u);
+                double x = 0.0, y = 0.0;
+                rand_in_unit_disk_wave<double>(G, valid, false, x, y);
+                const double SS = x * x + y * y, root = ::sqrt(1.0 - SS);
+                sx = (2.0 * x) * root; sy = (2.0 * y) * root; sz = 1.0 - 2.0 * SS;
+                qx = g0 + g3 * sx; qy = g1 + g3 * sy; qz = g2 + g3 * sz;
+                const double ex = px - g0, ey = py - g1, ez = pz - g2;
+                far = dot3(ex, ey, ez, ex, ey, ez) > g3 * g3; // the far side of a sphere seen from outside, once sd is known
+            } else {
+                const double u0 = Real<double>::uniform(mix64(key + RTMI_GOLD)), u1 = Real<double>::uniform(mix64(key + 2ull * RTMI_GOLD));
+                const double a = g0 + u0 * (g2 - g0), b = g1 + u1 * (g3 - g1);
+                sx = kind == RTMI_PRIM_RECT_YZ ? 1.0 : 0.0; sy = kind == RTMI_PRIM_RECT_XZ ? 1.0 : 0.0; sz = kind == RTMI_PRIM_RECT_XY ? 1.0 : 0.0;
+                if (kind == RTMI_PRIM_RECT_XY) { qx = a; qy = b; qz = g4; }
+                else if (kind == RTMI_PRIM_RECT_XZ) { qx = a; qy = g4; qz = b; }
+                else { qx = g4; qy = a; qz = b; }
+            }
+            const double dx = qx - px, dy = qy - py, dz = qz - pz;
+            const double d2 = dot3(dx, dy, dz, dx, dy, dz), cp = dot3(nx, ny, nz, dx, dy, dz), sd = dot3(sx, sy, sz, dx, dy, dz), cl = ::fabs(sd);
+            const bool built = valid && !(far && sd > 0.0) && d2 > 0.0 && cp > 0.0 && cl > 0.0;
+            const double wk = built ? ((((cp * cp) * (cp * cl)) / ((d2 * d2) * d2)) * area) * kTwoInvPi : 0.0; // x = w: every light proposes, q = 1
+            const double mk = wk == big ? 1.0 : wk / (1.0 + wk);
+            const double what = lum * mk;
+            const bool is_live = built && what > 0.0 && what < big; // (a NaN fails)
+            S = is_live ? S + what : S;
+            const double u = Real<double>::uniform(mix64(kchoice + RTMI_GOLD * (u64)(k + 1u))); // draw k of the choice's stream
+            const bool take = is_live && (live == 0 || u * S < what);
+            sel = take ? (int)k : sel;
+            sel_what = take ? what : sel_what; sel_w = take ? wk : sel_w; sel_m = take ? mk : sel_m;
+            sel_dx = take ? dx : sel_dx; sel_dy = take ? dy : sel_dy; sel_dz = take ? dz : sel_dz;
+            pend0 = take ? L[7] * mk : pend0; pend1 = take ? L[8] * mk : pend1; pend2 = take ? L[9] * mk : pend2;
+            live += is_live ? 1 : 0;
+        }
+        ok = live > 0;
+        l = sel; w = sel_w;
+        xmg[0] = sel_w; xmg[1] = sel_m;
+        pick->S = S; pick->what = sel_what; pick->r = ok ? S / sel_what : 0.0; pick->live = live;
+        pick->pend[0] = pend0; pick->pend[1] = pend1; pick->pend[2] = pend2;
+        q[0] = ok ? px : 0.0; q[1] = ok ? py : 0.0; q[2] = ok ? pz : 0.0;
+        q[3] = sel_dx; q[4] = sel_dy; q[5] = sel_dz; q[6] = ok ? time : 0.0;
+        return ok;
+    }
     const u64 kpick = sample_key(K, (u64)j, 1ull), key = sample_key(K, (u64)j, 0ull);
     const double up = Real<double>::uniform(mix64(kpick + RTMI_GOLD)); // draw 0 of the picking stream
     l = min((int)(up * (double)nl.n), (int)nl.n - 1);
@@ -1944,7 +2017,8 @@ __device__ inline bool nee_light_ray(const NeeLights &nl, bool want, u64 K, unsi
 // end finds it; rec is then an RTMI_MIS_REC row.
 // VOL (THE VOLUME RULE): `lamb` holds the Lambertian and the Isotropic vertices, `iso` the latter; the shadow ray carries a stream of its own, keyed
 // sample_key(K, j, 2) at draw 0, from which the media it crosses draw their free-flight distances: the unoccluded flag estimates the transmittance.
-template <typename R, int VARIANT, bool EXT, bool MIS = false, bool VOL = false>
+// RIS (THE PROPOSAL RULE): the pending contribution is T * ((Le * m) * r) of the chosen candidate; rec is then an RTMI_RIS_REC row.
+template <typename R, int VARIANT, bool EXT, bool MIS = false, bool VOL = false, bool RIS = false>
 __device__ inline int nee_vertex(SceneRef sc, Prim4<R> *lds, const NeeLights &nl, bool lamb, u64 K, unsigned j, const Path<R> &P, double nx, double ny,
                                  double nz, double *slot, double *rec, bool iso = false) {
     Path<R> S;
@@ -1953,20 +2027,38 @@ __device__ inline int nee_vertex(SceneRef sc, Prim4<R> *lds, const NeeLights &nl
         double q[7], w;
         int l;
         double xmg[3] = {0.0, 0.0, 0.0};
+        if constexpr (RIS) {
+            const double D[3] = {(double)P.dx, (double)P.dy, (double)P.dz};
+            RisPick pk;
+            ok = nee_light_ray<true, false, true>(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l, D, xmg, false, &pk);
+            if (lamb) slot[6 * kBlock] = xmg[2];
+            if (rec && lamb) {
+                rec[24] = xmg[0]; rec[25] = xmg[1]; rec[26] = xmg[2];
+                rec[28] = pk.S; rec[29] = pk.what; rec[30] = pk.r; rec[31] = (double)pk.live;
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double T = (double)(c == 0 ? P.ar : c == 1 ? P.ag : P.ab);
+                slot[(3 + c) * kBlock] = ok ? T * (pk.pend[c] * pk.r) : 0.0;
+                if (rec && lamb) rec[18 + c] = T;
+            }
+        } else
         if constexpr (MIS) {
             const double D[3] = {(double)P.dx, (double)P.dy, (double)P.dz};
             ok = nee_light_ray<true, VOL>(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l, D, xmg, iso);
             if (lamb) slot[6 * kBlock] = xmg[2];
             if (rec && lamb) { rec[24] = xmg[0]; rec[25] = xmg[1]; rec[26] = xmg[2]; }
         } else ok = nee_light_ray<false, VOL>(nl, lamb, K, j, (double)P.ox, (double)P.oy, (double)P.oz, nx, ny, nz, (double)P.time, q, w, l, nullptr, nullptr, iso);
-        const double *L = nl.rec + (size_t)l * kLightRec;
-        const double many = (double)nl.n;
+        if constexpr (!RIS) {
+            const double *L = nl.rec + (size_t)l * kLightRec;
+            const double many = (double)nl.n;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double T = (double)(c == 0 ? P.ar : c == 1 ? P.ag : P.ab);
-            if constexpr (MIS) slot[(3 + c) * kBlock] = ok ? T * (L[7 + c] * xmg[1]) : 0.0;
-            else slot[(3 + c) * kBlock] = ok ? T * ((L[7 + c] * w) * many) : 0.0;
-            if (rec && lamb) rec[18 + c] = T;
+            for (int c = 0; c < 3; ++c) {
+                const double T = (double)(c == 0 ? P.ar : c == 1 ? P.ag : P.ab);
+                if constexpr (MIS) slot[(3 + c) * kBlock] = ok ? T * (L[7 + c] * xmg[1]) : 0.0;
+                else slot[(3 + c) * kBlock] = ok ? T * ((L[7 + c] * w) * many) : 0.0;
+                if (rec && lamb) rec[18 + c] = T;
+            }
         }
         if (rec && lamb) { rec[13] = (double)l; rec[14] = q[3]; rec[15] = q[4]; rec[16] = q[5]; rec[17] = w; }
         load_ray<R>(q, S);
@@ -2020,7 +2112,9 @@ struct NeeParams {
 // MIS (rtmi_render_rays_mis*): THE MIS RULE of rtmi.h -- the same path and the same shadow rays, the balance heuristic on both ends.
 // VOL (rtmi_render_rays_vol*, rtmi_render_lit_vol*): THE VOLUME RULE of rtmi.h -- Isotropic vertices sample the lights too, and every shadow ray has a
 // stream of its own for the media it crosses.  Mixed-kind FP64 instantiations only: a world of spheres holds no medium.
-template <typename R, int VARIANT, bool EXT = false, bool MIS = false, int SRC = SRC_MEMORY, bool VOL = false>
+// RIS (rtmi_render_rays_ris*, rtmi_render_lit_ris*): THE PROPOSAL RULE of rtmi.h -- the MIS rule's path, lobe value and closing weight, with every listed
+// light proposing a point at each vertex and one shadow ray towards the candidate a weighted reservoir keeps.
+template <typename R, int VARIANT, bool EXT = false, bool MIS = false, int SRC = SRC_MEMORY, bool VOL = false, bool RIS = false>
 __global__ void __launch_bounds__(kBlock, VOL ? RTMI_VOL_MIN_WAVES : RTMI_NEE_MIN_WAVES) rays_nee_kernel(ScenePtr scp, NeeParams np) {
     static_assert(SRC == SRC_MEMORY || SRC == SRC_CAMERA || SRC == SRC_CAMERA_TILES, "the path kernels read their rays or build the frame's");
     static_assert(VARIANT >= SCAN_SGPR, "the LDS-staged scans need workgroup barriers: the refill loop is per wave");
@@ -2118,7 +2212,7 @@ __global__ void __launch_bounds__(kBlock, VOL ? RTMI_VOL_MIN_WAVES : RTMI_NEE_MI
             }
         }
         if (__any(lamb ? 1 : 0)) { // wave-uniform: all 64 lanes enter the disk rounds and the any-hit search
-            const int state = nee_vertex<R, VARIANT, EXT, MIS, VOL>(sc, lds, np.lights, lamb, P.key, seg, P, nx, ny, nz, slot, nullptr, iso);
+            const int state = nee_vertex<R, VARIANT, EXT, MIS, VOL, RIS>(sc, lds, np.lights, lamb, P.key, seg, P, nx, ny, nz, slot, nullptr, iso);
             n_built += state == 1 || state == 2 ? 1u : 0u;
             n_occ += state == 2 ? 1u : 0u;
         }
@@ -2153,7 +2247,8 @@ struct NeeProbeParams {
 
 // VOL (rtmi_probe_paths_vol): the rows are RTMI_VOL_REC doubles and out_end is the factor on the closing emission under either rule (the NEE rule's
 // 0.0 where it is dropped)
-template <typename R, int VARIANT, bool EXT = false, bool MIS = false, bool VOL = false>
+// RIS (rtmi_probe_paths_ris): the rows are RTMI_RIS_REC doubles
+template <typename R, int VARIANT, bool EXT = false, bool MIS = false, bool VOL = false, bool RIS = false>
 __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, NeeProbeParams pp) {
     static_assert(VARIANT >= SCAN_SGPR, "the loop is per wave, as rays_nee_kernel's");
     SceneRef sc = *scp;
@@ -2167,7 +2262,7 @@ __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, N
     Path<R> P;
     load_ray<R>(pp.rays + row * 7, P);
     seed_stream(P, alive ? pp.keys[k] : 0ull, pp.ctr0); P.depth = pp.depth;
-    constexpr int kRec = VOL ? RTMI_VOL_REC : MIS ? RTMI_MIS_REC : RTMI_NEE_REC;
+    constexpr int kRec = RIS ? RTMI_RIS_REC : VOL ? RTMI_VOL_REC : MIS ? RTMI_MIS_REC : RTMI_NEE_REC;
     double *log = pp.log ? pp.log + row * (size_t)pp.max_seg * kRec : nullptr;
     int nlog = 0, dropped = 0;
     double weight = 1.0; // (MIS) the factor on the closing emission
@@ -2216,7 +2311,7 @@ __global__ void __launch_bounds__(kBlock) probe_paths_nee_kernel(ScenePtr scp, N
                 }
             }
         }
-        if (__any(lamb ? 1 : 0)) nee_vertex<R, VARIANT, EXT, MIS, VOL>(sc, lds, pp.lights, lamb, P.key, seg, P, nx, ny, nz, slot, rec, iso);
+        if (__any(lamb ? 1 : 0)) nee_vertex<R, VARIANT, EXT, MIS, VOL, RIS>(sc, lds, pp.lights, lamb, P.key, seg, P, nx, ny, nz, slot, rec, iso);
         sampled = lamb;
         ++seg;
     }
@@ -6737,6 +6832,14 @@ template <bool MIS> struct ProbePathsVol {
     static constexpr bool wave_level = true;
     template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, MIS, EXT>; }
 };
+// THE PROPOSAL RULE's instantiations (rtmi_render_rays_ris*, rtmi_render_lit_ris*, rtmi_probe_paths_ris): RIS on top of the MIS rule's kernels
+template <int SRC> struct RisPass : NeePass {
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return rays_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, true, SRC, false, true>; }
+};
+struct ProbePathsRis {
+    static constexpr bool wave_level = true;
+    template <typename R, int V, bool EXT = false, int MSEQ = 0> static auto kernel() { return probe_paths_nee_kernel<R, (V < SCAN_SGPR ? (int)SCAN_SGPR : V), EXT, true, false, true>; }
+};
 
 struct NeeLightTable { LightTable t; int prim[RTMI_DIRECT_MAX_LIGHTS]; };
 constexpr size_t kNeeLightBytes = kLightTableBytes + sizeof(int) * RTMI_DIRECT_MAX_LIGHTS;
@@ -6820,6 +6923,45 @@ int upload_mis_lights(rtmi_ctx *c, const MisLightTable &T, NeeLights &L, hipStre
     return RTMI_OK;
 }
 
+// The RIS calls' table: the MIS table with q_l = 1.0 for every light (every light proposes: no pick), then lum_l where the RIS instantiations read it
+// (kRisRows).  It goes through a kernel of its own: what the other two set-kernels store is what they always stored.
+struct RisLightTable { MisLightTable m; double lum[RTMI_DIRECT_MAX_LIGHTS]; };
+constexpr size_t kRisLightBytes = kMisLightBytes + sizeof(double) * RTMI_DIRECT_MAX_LIGHTS;
+static_assert(kMisLightBytes == sizeof(double) * kRisRows, "the lum row starts where the MIS table ends");
+static_assert(sizeof(RisLightTable) + 2 * sizeof(void *) <= 4096, "the table travels as a kernel's arguments");
+__global__ void __launch_bounds__(64) set_ris_lights_kernel(RisLightTable t, double *dst) {
+    const int n = t.m.t.t.n;
+    for (int i = (int)threadIdx.x; i < n * kLightRec; i += 64) dst[i] = t.m.t.t.rec[i];
+    if ((int)threadIdx.x < n) reinterpret_cast<int *>(dst + RTMI_DIRECT_MAX_LIGHTS * kLightRec)[threadIdx.x] = t.m.t.prim[threadIdx.x];
+    for (int i = (int)threadIdx.x; i < 2 + 2 * n; i += 64) dst[kMisRows + i] = t.m.mis[i];
+    if ((int)threadIdx.x < n) dst[kRisRows + threadIdx.x] = t.lum[threadIdx.x];
+}
+
+// Steps 2 and 7 of the proposal rule on the host: lum_l, q_l = 1.0, and a light whose lum is not > 0 -- it can never be chosen -- leaves the list the
+// closing emitter is compared with.
+void make_ris_rows(RisLightTable &T) {
+    const int n = T.m.t.t.n;
+    double *M = T.m.mis;
+    M[0] = 0.0; M[1] = 0.0;
+    for (int l = 0; l < RTMI_DIRECT_MAX_LIGHTS; ++l) {
+        const double *r = T.m.t.t.rec + (size_t)l * kLightRec;
+        M[2 + 2 * l] = 0.0; M[3 + 2 * l] = 1.0;
+        T.lum[l] = l < n ? (r[7] + r[8]) + r[9] : 0.0;
+        if (l < n && !(T.lum[l] > 0.0)) T.m.t.prim[l] = -1;
+    }
+}
+
+int upload_ris_lights(rtmi_ctx *c, const RisLightTable &T, NeeLights &L, hipStream_t st) {
+    const int rc = c->nee_ws.ensure(kRisLightBytes);
+    if (rc) return rc;
+    L.rec = reinterpret_cast<const double *>(c->nee_ws.p);
+    L.prim = reinterpret_cast<const int *>(static_cast<const char *>(c->nee_ws.p) + kLightTableBytes);
+    L.n = (unsigned)T.m.t.t.n;
+    hipLaunchKernelGGL(set_ris_lights_kernel, dim3(1), dim3(64), 0, st, T, const_cast<double *>(L.rec));
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+
 // what both entries check behind rtmi_render_rays' own checks, in the header's order; *work: is there anything to trace?
 int check_nee_args(rtmi_scene *s, int n_groups, int n_lights, const int32_t *light_prims, NeeLightTable &T, bool *work, int light_choice, int vol) {
     *work = false;
@@ -6841,9 +6983,11 @@ int nee_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, 
             const NeeLightTable &T, double *d_state, double *d_mean, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st,
             const MisLightTable *M = nullptr, // M (then T is M->t): the MIS rule's kernels and table
             const RaysFrame *frame = nullptr, // frame: the SRC_CAMERA twins of the three families (rtmi_render_lit*), or with a list their SRC_CAMERA_TILES twins
-            bool vol = false) {               // vol: the volume rule's instantiations of the two light-sampling families
+            bool vol = false,                 // vol: the volume rule's instantiations of the two light-sampling families
+            const RisLightTable *Rs = nullptr) { // Rs (then T is Rs->m.t): the proposal rule's kernels and table
     return with_real(precision, [&](auto r) {
         using R = decltype(r);
+        auto ris_lights = [&](NeeParams &np, hipStream_t q) { return upload_ris_lights(s->ctx, *Rs, np.lights, q); };
         auto mis_lights = [&](NeeParams &np, hipStream_t q) { return upload_mis_lights(s->ctx, *M, np.lights, q); };
         auto nee_lights = [&](NeeParams &np, hipStream_t q) { return upload_nee_lights(s->ctx, T, np.lights, q); };
         // the family's kernels by the source of the rays: the caller's array, the frame's camera rays, those of a list of tiles
@@ -6854,6 +6998,7 @@ int nee_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, 
             };
             return frame && !frame->d_tiles ? go(camera) : !frame ? go(memory) : go(tiles);
         };
+        if (Rs && T.t.n > 0) return run(RisPass<SRC_CAMERA>{}, RisPass<SRC_MEMORY>{}, RisPass<SRC_CAMERA_TILES>{}, ris_lights);
         if (vol && M && T.t.n > 0) return run(VolPass<true, SRC_CAMERA>{}, VolPass<true, SRC_MEMORY>{}, VolPass<true, SRC_CAMERA_TILES>{}, mis_lights);
         if (vol && T.t.n > 0) return run(VolPass<false, SRC_CAMERA>{}, VolPass<false, SRC_MEMORY>{}, VolPass<false, SRC_CAMERA_TILES>{}, nee_lights);
         if (M && T.t.n > 0) return run(LitMisPass{}, MisPass{}, LitTilesMisPass{}, mis_lights);
@@ -6867,29 +7012,33 @@ int nee_run(rtmi_scene *s, int precision, int n_groups, int group, int g_first, 
 // vol their estimator argument (mis is then vol == 2).
 int lit_rays_device(bool mis, rtmi_scene *s, int precision, int n_groups, int group, int g_first, const void *d_rays, const void *d_keys, u64 seed, unsigned ctr0,
                     int depth, int n_lights, const int32_t *light_prims, int light_choice, void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays,
-                    void *d_out_counters, void *stream, int vol = -1) {
-    MisLightTable M;
+                    void *d_out_counters, void *stream, int vol = -1, bool ris = false) {
+    RisLightTable Rt;
+    MisLightTable &M = Rt.m;
     NeeLightTable &T = M.t;
     bool work = false;
     const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, d_rays, d_out_mean, d_out_stderr, nullptr, &work, &T, n_lights, light_prims, light_choice,
                               false, vol);
     if (rc || !work) return rc;
     if (mis) make_mis_rows(M, light_choice);
+    if (ris) make_ris_rows(Rt);
     return nee_run(s, precision, n_groups, group, g_first, as<const double>(d_rays), as<const u64>(d_keys), seed, ctr0, depth, T, as<double>(d_state),
                    as<double>(d_out_mean), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream), mis ? &M : nullptr,
-                   nullptr, vol >= 0);
+                   nullptr, vol >= 0, ris ? &Rt : nullptr);
 }
 
 int lit_rays_host(bool mis, rtmi_scene *s, int precision, int n_groups, int group, int g_first, const double *rays, const uint64_t *keys, u64 seed, unsigned ctr0,
                   int depth, int n_lights, const int32_t *light_prims, int light_choice, double *state, double *out_mean, double *out_stderr, double *out_rays,
-                  uint64_t *out_counters, int vol = -1) {
-    MisLightTable M;
+                  uint64_t *out_counters, int vol = -1, bool ris = false) {
+    RisLightTable Rt;
+    MisLightTable &M = Rt.m;
     NeeLightTable &T = M.t;
     bool work = false;
     const int rc = rays_begin(s, precision, n_groups, group, g_first, depth, rays, out_mean, out_stderr, state, &work, &T, n_lights, light_prims, light_choice, false,
                               vol);
     if (rc || !work) return rc;
     if (mis) make_mis_rows(M, light_choice);
+    if (ris) make_ris_rows(Rt);
     const size_t n = (size_t)n_groups * (size_t)group, ng = (size_t)n_groups;
     HostIo io(s->ctx);
     double *d_rays, *d_state, *d_mean, *d_se, *d_out;
@@ -6899,7 +7048,7 @@ int lit_rays_host(bool mis, rtmi_scene *s, int precision, int n_groups, int grou
     io.out(&d_mean, 3 * ng, out_mean); io.out(&d_se, ng, out_stderr); io.work(&d_cnt, 4, out_counters); io.out(&d_out, 3 * n, out_rays);
     return host_run(io, [&](hipStream_t st) {
         return nee_run(s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, T, d_state, d_mean, d_se, d_out, d_cnt, st, mis ? &M : nullptr,
-                       nullptr, vol >= 0);
+                       nullptr, vol >= 0, ris ? &Rt : nullptr);
     });
 }
 
@@ -6907,13 +7056,14 @@ int lit_rays_host(bool mis, rtmi_scene *s, int precision, int n_groups, int grou
 // vol its estimator argument (mis is then vol == 2): RTMI_VOL_REC rows and out_weight under either rule.
 int lit_probe(bool mis, rtmi_scene *s, int precision, int n, const double *rays, const uint64_t *keys, u64 ctr0, int depth, int n_lights, const int32_t *light_prims,
               int light_choice, double *out_rgb, uint64_t *out_nseg, int32_t *out_dropped, double *out_weight, double *log, int max_seg, int32_t *out_nlog,
-              int vol = -1) {
+              int vol = -1, bool ris = false) { // ris: rtmi_probe_paths_ris (mis is then true, light_choice 0): RTMI_RIS_REC rows
     int rc = probe_begin(s, precision, n);
     if (rc || n == 0) return rc;
     if (!rays || !keys || !out_rgb) return fail(RTMI_E_ARG, "NULL array");
     if (log && max_seg <= 0) return fail(RTMI_E_ARG, "log given but max_seg <= 0");
     if (precision == RTMI_F32 && s->dev.has_ext) return fail(RTMI_E_UNSUPPORTED, "rectangles / triangles / instances are FP64 only");
-    MisLightTable M;
+    RisLightTable Rt;
+    MisLightTable &M = Rt.m;
     NeeLightTable &T = M.t;
     bool work = false;
     rc = check_nee_args(s, n, n_lights, light_prims, T, &work, light_choice, vol);
@@ -6931,13 +7081,14 @@ int lit_probe(bool mis, rtmi_scene *s, int precision, int n, const double *rays,
         return RTMI_OK;
     }
     if (mis) make_mis_rows(M, light_choice);
+    if (ris) make_ris_rows(Rt);
     rtmi_ctx *c = s->ctx;
     HostIo io(c);
     NeeProbeParams pp{};
     double *d_rays, *d_rgb, *d_log, *d_weight;
     u64 *d_keys, *d_nseg;
     int *d_dropped, *d_nlog;
-    const size_t log_words = log ? (size_t)n * max_seg * (vol >= 0 ? RTMI_VOL_REC : mis ? RTMI_MIS_REC : RTMI_NEE_REC) : 0;
+    const size_t log_words = log ? (size_t)n * max_seg * (ris ? RTMI_RIS_REC : vol >= 0 ? RTMI_VOL_REC : mis ? RTMI_MIS_REC : RTMI_NEE_REC) : 0;
     io.in(&d_rays, (size_t)n * 7, rays); io.in(&d_keys, (size_t)n, keys); io.out(&d_rgb, (size_t)n * 3, out_rgb);
     io.out(&d_nseg, (size_t)n, out_nseg); io.out(&d_dropped, (size_t)n, out_dropped); io.out(&d_weight, (size_t)n, out_weight); io.out(&d_nlog, (size_t)n, out_nlog);
     io.out(&d_log, log_words, log);
@@ -6945,11 +7096,12 @@ int lit_probe(bool mis, rtmi_scene *s, int precision, int n, const double *rays,
     return probe_run(io, n, [&](hipStream_t st, dim3 grid) {
         pp.rays = d_rays; pp.keys = d_keys; pp.out_rgb = d_rgb; pp.out_nseg = d_nseg; pp.out_nlog = d_nlog; pp.log = d_log;
         pp.out_end = mis || vol >= 0 ? static_cast<void *>(d_weight) : static_cast<void *>(d_dropped);
-        if ((mis ? upload_mis_lights(c, M, pp.lights, st) : upload_nee_lights(c, T, pp.lights, st)) != RTMI_OK) return; // (probe_run reports a launch error)
+        if ((ris ? upload_ris_lights(c, Rt, pp.lights, st) : mis ? upload_mis_lights(c, M, pp.lights, st) : upload_nee_lights(c, T, pp.lights, st)) != RTMI_OK) return; // (probe_run reports a launch error)
         if (d_log && hipMemsetAsync(d_log, 0, log_words * sizeof(double), st) != hipSuccess) return;
         auto run = [&](auto kern, size_t lds, int, int) { hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, st, s->d_dev, pp); };
         with_real(precision, [&](auto r) {
-            if (vol >= 0 && mis) with_probe_kernel<ProbePathsVol<true>, decltype(r)>(s, run);
+            if (ris) with_probe_kernel<ProbePathsRis, decltype(r)>(s, run);
+            else if (vol >= 0 && mis) with_probe_kernel<ProbePathsVol<true>, decltype(r)>(s, run);
             else if (vol >= 0) with_probe_kernel<ProbePathsVol<false>, decltype(r)>(s, run);
             else if (mis) with_probe_kernel<ProbePathsMis, decltype(r)>(s, run);
             else with_probe_kernel<ProbePathsNee, decltype(r)>(s, run);
@@ -7053,9 +7205,9 @@ int lit_frame_begin(rtmi_scene *s, int precision, int nx, int ny, int s_first, i
 
 int lit_frame_run(rtmi_scene *s, int precision, int nx, int ny, int s_first, int s_count, int depth, u64 seed, int estimator, const MisLightTable &M,
                   const RaysFrame &F, double *d_state, double *d_lin, unsigned char *d_q, double *d_se, double *d_out_rays, u64 *d_cnt, hipStream_t st,
-                  bool vol = false) {
+                  bool vol = false, const RisLightTable *Rs = nullptr) { // Rs (then M is Rs->m): the proposal rule
     const int rc = nee_run(s, precision, F.d_tiles ? F.n_tiles * 64 : nx * ny, s_count, s_first, nullptr, nullptr, seed, 0u, depth, M.t, d_state, d_lin, d_se,
-                           d_out_rays, d_cnt, st, estimator == 2 ? &M : nullptr, &F, vol);
+                           d_out_rays, d_cnt, st, estimator == 2 ? &M : nullptr, &F, vol, Rs);
     if (rc || !d_q || F.d_tiles) return rc; // (a list: the tile fold has quantised the pixels it wrote, F.d_rgb8)
     const size_t n = (size_t)nx * (size_t)ny * 3;
     hipLaunchKernelGGL(lit_quantise_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_lin, n, d_q);
@@ -7065,30 +7217,35 @@ int lit_frame_run(rtmi_scene *s, int precision, int nx, int ny, int s_first, int
 } // namespace
 
 namespace {
-// both forms of rtmi_render_lit* and, with vol, of rtmi_render_lit_vol*
+// both forms of rtmi_render_lit* and, with vol, of rtmi_render_lit_vol*; ris: rtmi_render_lit_ris* without a list (the MIS rule's checks, light_choice 0)
 int lit_frame_device(bool vol, rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
                      int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, void *d_state, void *d_out_linear, void *d_out_rgb8,
-                     void *d_out_stderr, void *d_out_rays, void *d_out_camera, void *d_out_counters, void *stream) {
-    MisLightTable M;
+                     void *d_out_stderr, void *d_out_rays, void *d_out_camera, void *d_out_counters, void *stream, bool ris = false) {
+    RisLightTable Rt;
+    MisLightTable &M = Rt.m;
     RaysFrame F;
     bool work = false;
     const int rc = lit_frame_begin(s, precision, nx, ny, s_first, s_count, depth, estimator, n_lights, light_prims, light_choice, nullptr, d_out_linear,
                                    d_out_stderr, M, F, &work, vol);
     if (rc || !work) return rc;
+    if (ris) make_ris_rows(Rt);
     F.out_camera = as<double>(d_out_camera);
     return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, as<double>(d_state), as<double>(d_out_linear),
-                         as<unsigned char>(d_out_rgb8), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream), vol);
+                         as<unsigned char>(d_out_rgb8), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream), vol,
+                         ris ? &Rt : nullptr);
 }
 
 int lit_frame_host(bool vol, rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
                    int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, double *state, double *out_linear,
-                   uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera, uint64_t *out_counters) {
-    MisLightTable M;
+                   uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera, uint64_t *out_counters, bool ris = false) {
+    RisLightTable Rt;
+    MisLightTable &M = Rt.m;
     RaysFrame F;
     bool work = false;
     const int rc = lit_frame_begin(s, precision, nx, ny, s_first, s_count, depth, estimator, n_lights, light_prims, light_choice, state, out_linear, out_stderr,
                                    M, F, &work, vol);
     if (rc || !work) return rc;
+    if (ris) make_ris_rows(Rt);
     const size_t ng = (size_t)nx * (size_t)ny, n = ng * (size_t)s_count;
     HostIo io(s->ctx);
     double *d_state, *d_lin, *d_se, *d_out, *d_cam;
@@ -7099,7 +7256,8 @@ int lit_frame_host(bool vol, rtmi_scene *s, int32_t precision, int32_t nx, int32
     io.out(&d_out, 3 * n, out_rays); io.out(&d_cam, 8 * n, out_camera);
     return host_run(io, [&](hipStream_t st) {
         F.out_camera = d_cam;
-        return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, d_state, d_lin, d_q, d_se, d_out, d_cnt, st, vol);
+        return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, d_state, d_lin, d_q, d_se, d_out, d_cnt, st, vol,
+                             ris ? &Rt : nullptr);
     });
 }
 } // namespace
@@ -7162,35 +7320,41 @@ RTMI_EXPORT int rtmi_render_lit_vol(rtmi_scene *s, int32_t precision, int32_t nx
 // ---- light-sampled frames over a caller's list of 8x8 tiles (rtmi_render_lit_tiles*): THE TILE ORDER of rtmi.h --------------------------------------------
 // rtmi_render_lit* / rtmi_render_lit_vol* with the SRC_CAMERA_TILES twins of their kernels and lit_tiles_fold_kernel behind each pass: the rows of the call
 // are the listed tiles' pixels, the frame planes and the state stay the whole frame's and only the listed pixels' elements are touched.
-RTMI_EXPORT int rtmi_render_lit_tiles_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth,
-                                             uint64_t seed, int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, int32_t volume,
-                                             int32_t n_tiles, const void *d_tiles, void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr,
-                                             void *d_out_rays, void *d_out_camera, void *d_out_counters, void *stream) {
-    MisLightTable M;
+namespace {
+// both forms of rtmi_render_lit_tiles*; ris: rtmi_render_lit_ris* with a list (the MIS rule's checks, light_choice 0, volume 0)
+int lit_tiles_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth,
+                     uint64_t seed, int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, int32_t volume,
+                     int32_t n_tiles, const void *d_tiles, void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr,
+                     void *d_out_rays, void *d_out_camera, void *d_out_counters, void *stream, bool ris = false) {
+    RisLightTable Rt;
+    MisLightTable &M = Rt.m;
     RaysFrame F;
     bool work = false;
     const LitTileArgs tl{volume, n_tiles, nullptr, d_tiles};
     const int rc = lit_frame_begin(s, precision, nx, ny, s_first, s_count, depth, estimator, n_lights, light_prims, light_choice, nullptr, d_out_linear,
                                    d_out_stderr, M, F, &work, volume == 1, &tl);
     if (rc || !work) return rc;
+    if (ris) make_ris_rows(Rt);
     F.out_camera = as<double>(d_out_camera); F.d_tiles = as<const int>(d_tiles); F.d_rgb8 = as<unsigned char>(d_out_rgb8);
     return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, as<double>(d_state), as<double>(d_out_linear),
                          as<unsigned char>(d_out_rgb8), as<double>(d_out_stderr), as<double>(d_out_rays), as<u64>(d_out_counters), stream_of(s->ctx, stream),
-                         volume == 1);
+                         volume == 1, ris ? &Rt : nullptr);
 }
 
 // The host form stages the whole planes both ways: the elements outside the list come back with the bits they went up with.
-RTMI_EXPORT int rtmi_render_lit_tiles(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
-                                      int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, int32_t volume, int32_t n_tiles,
-                                      const int32_t *tiles, double *state, double *out_linear, uint8_t *out_rgb8, double *out_stderr, double *out_rays,
-                                      double *out_camera, uint64_t *out_counters) {
-    MisLightTable M;
+int lit_tiles_host(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                   int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, int32_t volume, int32_t n_tiles,
+                   const int32_t *tiles, double *state, double *out_linear, uint8_t *out_rgb8, double *out_stderr, double *out_rays,
+                   double *out_camera, uint64_t *out_counters, bool ris = false) {
+    RisLightTable Rt;
+    MisLightTable &M = Rt.m;
     RaysFrame F;
     bool work = false;
     const LitTileArgs tl{volume, n_tiles, tiles, tiles};
     const int rc = lit_frame_begin(s, precision, nx, ny, s_first, s_count, depth, estimator, n_lights, light_prims, light_choice, state, out_linear, out_stderr,
                                    M, F, &work, volume == 1, &tl);
     if (rc || !work) return rc;
+    if (ris) make_ris_rows(Rt);
     const size_t ng = (size_t)nx * (size_t)ny, n = (size_t)n_tiles * 64 * (size_t)s_count;
     HostIo io(s->ctx);
     double *d_state, *d_lin, *d_se, *d_out, *d_cam;
@@ -7204,8 +7368,69 @@ RTMI_EXPORT int rtmi_render_lit_tiles(rtmi_scene *s, int32_t precision, int32_t 
     io.out(&d_out, 3 * n, out_rays); io.out(&d_cam, 8 * n, out_camera);
     return host_run(io, [&](hipStream_t st) {
         F.out_camera = d_cam; F.d_tiles = d_tiles; F.d_rgb8 = d_q;
-        return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, d_state, d_lin, d_q, d_se, d_out, d_cnt, st, volume == 1);
+        return lit_frame_run(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, M, F, d_state, d_lin, d_q, d_se, d_out, d_cnt, st, volume == 1,
+                             ris ? &Rt : nullptr);
     });
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_render_lit_tiles_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth,
+                                             uint64_t seed, int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, int32_t volume,
+                                             int32_t n_tiles, const void *d_tiles, void *d_state, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr,
+                                             void *d_out_rays, void *d_out_camera, void *d_out_counters, void *stream) {
+    return lit_tiles_device(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, n_lights, light_prims, light_choice, volume, n_tiles, d_tiles, d_state,
+                            d_out_linear, d_out_rgb8, d_out_stderr, d_out_rays, d_out_camera, d_out_counters, stream);
+}
+
+RTMI_EXPORT int rtmi_render_lit_tiles(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                      int32_t estimator, int32_t n_lights, const int32_t *light_prims, int32_t light_choice, int32_t volume, int32_t n_tiles,
+                                      const int32_t *tiles, double *state, double *out_linear, uint8_t *out_rgb8, double *out_stderr, double *out_rays,
+                                      double *out_camera, uint64_t *out_counters) {
+    return lit_tiles_host(s, precision, nx, ny, s_first, s_count, depth, seed, estimator, n_lights, light_prims, light_choice, volume, n_tiles, tiles, state,
+                          out_linear, out_rgb8, out_stderr, out_rays, out_camera, out_counters);
+}
+
+// ---- light-sampled paths whose every lamp proposes a point (rtmi_render_rays_ris*, rtmi_probe_paths_ris, rtmi_render_lit_ris*): THE PROPOSAL RULE -------
+// The MIS siblings' entries with the RIS instantiations of their kernels: the MIS rule's checks with light_choice 0, then the table with q = 1 and lum.
+// The frame call without a list runs the SRC_CAMERA kernels (rtmi_render_lit's rows and layouts), with a list the SRC_CAMERA_TILES ones.
+RTMI_EXPORT int rtmi_render_rays_ris_device(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const void *d_rays,
+                                            const void *d_keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
+                                            void *d_state, void *d_out_mean, void *d_out_stderr, void *d_out_rays, void *d_out_counters, void *stream) {
+    return lit_rays_device(true, s, precision, n_groups, group, g_first, d_rays, d_keys, seed, ctr0, depth, n_lights, light_prims, 0, d_state, d_out_mean,
+                           d_out_stderr, d_out_rays, d_out_counters, stream, -1, true);
+}
+
+RTMI_EXPORT int rtmi_render_rays_ris(rtmi_scene *s, int32_t precision, int32_t n_groups, int32_t group, int32_t g_first, const double *rays,
+                                     const uint64_t *keys, uint64_t seed, uint32_t ctr0, int32_t depth, int32_t n_lights, const int32_t *light_prims,
+                                     double *state, double *out_mean, double *out_stderr, double *out_rays, uint64_t *out_counters) {
+    return lit_rays_host(true, s, precision, n_groups, group, g_first, rays, keys, seed, ctr0, depth, n_lights, light_prims, 0, state, out_mean, out_stderr,
+                         out_rays, out_counters, -1, true);
+}
+
+RTMI_EXPORT int rtmi_probe_paths_ris(rtmi_scene *s, int32_t precision, int32_t n, const double *rays, const uint64_t *keys, uint64_t ctr0, int32_t depth,
+                                     int32_t n_lights, const int32_t *light_prims, double *out_rgb, uint64_t *out_nseg, double *out_weight, double *log,
+                                     int32_t max_seg, int32_t *out_nlog) {
+    return lit_probe(true, s, precision, n, rays, keys, ctr0, depth, n_lights, light_prims, 0, out_rgb, out_nseg, nullptr, out_weight, log, max_seg, out_nlog,
+                     -1, true);
+}
+
+RTMI_EXPORT int rtmi_render_lit_ris_device(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth,
+                                           uint64_t seed, int32_t n_lights, const int32_t *light_prims, int32_t n_tiles, const void *d_tiles, void *d_state,
+                                           void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_rays, void *d_out_camera,
+                                           void *d_out_counters, void *stream) {
+    if (!d_tiles) return lit_frame_device(false, s, precision, nx, ny, s_first, s_count, depth, seed, 2, n_lights, light_prims, 0, d_state, d_out_linear,
+                                          d_out_rgb8, d_out_stderr, d_out_rays, d_out_camera, d_out_counters, stream, true);
+    return lit_tiles_device(s, precision, nx, ny, s_first, s_count, depth, seed, 2, n_lights, light_prims, 0, 0, n_tiles, d_tiles, d_state, d_out_linear,
+                            d_out_rgb8, d_out_stderr, d_out_rays, d_out_camera, d_out_counters, stream, true);
+}
+
+RTMI_EXPORT int rtmi_render_lit_ris(rtmi_scene *s, int32_t precision, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count, int32_t depth, uint64_t seed,
+                                    int32_t n_lights, const int32_t *light_prims, int32_t n_tiles, const int32_t *tiles, double *state, double *out_linear,
+                                    uint8_t *out_rgb8, double *out_stderr, double *out_rays, double *out_camera, uint64_t *out_counters) {
+    if (!tiles) return lit_frame_host(false, s, precision, nx, ny, s_first, s_count, depth, seed, 2, n_lights, light_prims, 0, state, out_linear, out_rgb8,
+                                      out_stderr, out_rays, out_camera, out_counters, true);
+    return lit_tiles_host(s, precision, nx, ny, s_first, s_count, depth, seed, 2, n_lights, light_prims, 0, 0, n_tiles, tiles, state, out_linear, out_rgb8,
+                          out_stderr, out_rays, out_camera, out_counters, true);
 }
 
 // ---- retiring the tiles of a caller's list by a noise map (rtmi_tiles_retire*): the stateless rtmi_adaptive_retire ------------------------------------------
