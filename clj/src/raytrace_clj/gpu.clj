@@ -1277,6 +1277,101 @@
           (finally (doseq [s scenes] (call-int "rtmi_scene_destroy" s)))))
       (finally (doseq [c ctxs] (call-int "rtmi_shutdown" c))))))
 
+(defn render-multi-lit
+  "render-lit (estimator 0 plain, 1 the NEE rule, 2 the MIS rule; :volume true the volume rule; estimator 3 the proposal rule of render-lit-ris) on
+  every GPU in `devices` from this one JVM (rtmi_multi_lit_render): contexts and scene replicas as in render-multi, the 8x8 tiles of the ONE frame
+  dealt round-robin, `chunk` samples per call (default: one call), one gather of the tile records per call, assembled on the first device.
+  Returns {:linear :rgb8 :stderr :pixel-samples :segments :total-rays :shadow-rays :shadow-rays-occluded (summed over the calls and devices)}.
+  Every array is bit-identical to the single-device call's."
+  [scene nx ny ns lights & {:keys [chunk estimator light-choice volume seed depth devices precision]
+                            :or {estimator 2 light-choice 0 volume false seed 0x5eed0002 depth 50 devices [0] precision 0}}]
+  (let [f     (flatten-scene scene)
+        fh    (long-array 1)
+        npx   (* nx ny)
+        lp    (int-array (if (seq lights) lights [0]))
+        nl    (count lights)
+        lin   (double-array (* 3 npx))
+        rgb   (byte-array (* 3 npx))
+        err   (double-array npx)
+        smp   (int-array npx)
+        cnt   (long-array 4)
+        sums  (long-array 4)
+        step  (or chunk ns)
+        ctxs  (mapv (fn [d] (let [ctx (PointerByReference.)] (check (call-int "rtmi_init" (int d) (int 0) ctx)) (.getValue ctx))) devices)]
+    (try
+      (let [scn0   (create-scene! (first ctxs) f)
+            clones (mapv (fn [c] (let [scn (PointerByReference.)] (check (call-int "rtmi_scene_clone" scn0 c scn)) (.getValue scn)))
+                         (rest ctxs))
+            scenes (into [scn0] clones)
+            handles (into-array com.sun.jna.Pointer scenes)]
+        (try
+          (check (call-int "rtmi_multi_lit_create" (int (count scenes)) handles (int nx) (int ny) fh))
+          (try
+            (loop [k 0]
+              (let [n (min step (- ns k))]
+                (check (call-int "rtmi_multi_lit_render" (long (aget fh 0)) (int precision) (int n) (int depth) (long seed) (int estimator) (int nl) lp
+                                 (int light-choice) (int (if volume 1 0)) lin rgb err smp cnt))
+                (dotimes [i 4] (aset sums i (+ (aget sums i) (aget cnt i))))
+                (if (< (+ k n) ns)
+                  (recur (+ k n))
+                  {:linear lin :rgb8 rgb :stderr err :pixel-samples smp :segments (aget sums 0) :total-rays (aget sums 1)
+                   :shadow-rays (aget sums 2) :shadow-rays-occluded (aget sums 3)})))
+            (finally (call-int "rtmi_multi_lit_destroy" (long (aget fh 0)))))
+          (finally (doseq [s scenes] (call-int "rtmi_scene_destroy" s)))))
+      (finally (doseq [c ctxs] (call-int "rtmi_shutdown" c))))))
+
+(defn render-multi-lit-adaptive
+  "render-lit-adaptive on every GPU in `devices` from this one JVM: rounds of rtmi_multi_lit_render (`first-round` samples, default `chunk`, then
+  `chunk`) each followed by rtmi_multi_lit_retire by the assembled frame's standard error -- on a replica's own tiles that is the replica's own
+  plane, bit for bit; a NULL map would spare the upload of 8 bytes per pixel per round, but every array argument of this file is a typed primitive
+  array, which is what its conformance reader checks call site by call site -- until no tile is listed or `ns` is reached.  After each round (on-round m), m = {:samples k :linear :rgb8 :stderr
+  :pixel-samples :active-tiles :total-tiles :segments :total-rays :shadow-rays :shadow-rays-occluded (summed over the rounds and devices)}; on-round
+  returning :stop ends the render early.  Every array and every round's list are bit-identical to render-lit-adaptive's on one GPU.  Returns the last m."
+  [scene nx ny ns chunk eps lights on-round & {:keys [first-round estimator light-choice volume seed depth devices precision]
+                                               :or {estimator 2 light-choice 0 volume false seed 0x5eed0002 depth 50 devices [0] precision 0}}]
+  (let [f     (flatten-scene scene)
+        fh    (long-array 1)
+        npx   (* nx ny)
+        total (* (quot (+ nx 7) 8) (quot (+ ny 7) 8))
+        lp    (int-array (if (seq lights) lights [0]))
+        nl    (count lights)
+        lin   (double-array (* 3 npx))
+        rgb   (byte-array (* 3 npx))
+        err   (double-array npx)
+        smp   (int-array npx)
+        cnt   (long-array 4)
+        sums  (long-array 4)
+        left  (int-array 1)
+        held  (int-array 1)
+        head  (or first-round chunk)
+        ctxs  (mapv (fn [d] (let [ctx (PointerByReference.)] (check (call-int "rtmi_init" (int d) (int 0) ctx)) (.getValue ctx))) devices)]
+    (try
+      (let [scn0   (create-scene! (first ctxs) f)
+            clones (mapv (fn [c] (let [scn (PointerByReference.)] (check (call-int "rtmi_scene_clone" scn0 c scn)) (.getValue scn)))
+                         (rest ctxs))
+            scenes (into [scn0] clones)
+            handles (into-array com.sun.jna.Pointer scenes)]
+        (try
+          (check (call-int "rtmi_multi_lit_create" (int (count scenes)) handles (int nx) (int ny) fh))
+          (try
+            (loop []
+              (check (call-int "rtmi_multi_lit_status" (long (aget fh 0)) held left))
+              (let [k (aget held 0)
+                    n (min (if (zero? k) head chunk) (- ns k))]
+                (check (call-int "rtmi_multi_lit_render" (long (aget fh 0)) (int precision) (int n) (int depth) (long seed) (int estimator) (int nl) lp
+                                 (int light-choice) (int (if volume 1 0)) lin rgb err smp cnt))
+                (check (call-int "rtmi_multi_lit_retire" (long (aget fh 0)) err (double eps) left))
+                (dotimes [i 4] (aset sums i (+ (aget sums i) (aget cnt i))))
+                (let [k' (+ k n)
+                      m  {:samples k' :linear lin :rgb8 rgb :stderr err :pixel-samples smp :active-tiles (aget left 0) :total-tiles total
+                          :segments (aget sums 0) :total-rays (aget sums 1) :shadow-rays (aget sums 2) :shadow-rays-occluded (aget sums 3)}]
+                  (if (and (not= :stop (on-round m)) (< k' ns) (pos? (aget left 0)))
+                    (recur)
+                    m))))
+            (finally (call-int "rtmi_multi_lit_destroy" (long (aget fh 0)))))
+          (finally (doseq [s scenes] (call-int "rtmi_scene_destroy" s)))))
+      (finally (doseq [c ctxs] (call-int "rtmi_shutdown" c))))))
+
 (defn save-ppm
   "imagez `save` (core.clj:112) has no PPM writer; binary P6 written here"
   [filename ^bytes rgb8 nx ny]

@@ -1194,6 +1194,75 @@ int rtmi_render_multi_adaptive(int32_t n, rtmi_scene *const *scenes, int32_t nx,
 int rtmi_render_multi_adaptive_device(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t ny, int32_t s_first, int32_t s_count,
                                       int32_t retire, double eps, int32_t depth, uint64_t seed, int32_t precision,
                                       void *d_out_linear, void *d_out_rgb8, void *d_out_stderr, void *d_out_samples, void *d_out_counters);
+/* ---- light-sampled frames on several GPUs: THE DEALT LIT FRAME ----
+ * One light-sampled frame -- uniform or adaptive, under the plain estimator, the NEE rule, the MIS rule (with or without the volume rule) or the
+ * proposal rule -- refined on n replicas of a scene.  What rtmi_render_multi_adaptive is to rtmi_render_adaptive these entries are to
+ * rtmi_render_lit_tiles / rtmi_render_lit_ris with a list and rtmi_tiles_retire: the sample path and the decision are those calls' own, keyed by
+ * (seed, global pixel, sample) and taken per tile from that tile's pixels alone, so nothing in them knows who owns a tile.
+ *   THE RECORD.  rtmi_lit_tiles_records_device packs dealt tiles out of a replica's WHOLE-FRAME buffers into the record of the dealt progressive
+ *   frames above: d_out_rec[n_slots][64][RTMI_PROG_REC] doubles, slot k = global tile tile_first + k * tile_stride, local pixel l = row * 8 + column
+ *   (THE TILE ORDER's numbering).  Values 0-2 are the pixel's three doubles of d_linear [ny][nx][3] and value 3 its double of d_stderr [ny][nx], copied
+ *   as they are (rtmi_render_lit_tiles' out_linear and out_stderr); value 4 is word [9], the sample count, of the pixel's record in d_state
+ *   [nx * ny][RTMI_RAYS_REC].  A pixel outside the image holds five zeros, and so does every pixel of a slot whose tile is at or past
+ *   T = ceil(nx/8) * ceil(ny/8): those slots are the padding of a gathered record, so a gather never moves uninitialised memory.  No tile list is
+ *   read.  rtmi_assemble_progressive_device assembles the gathered records unchanged; its quantiser and rtmi_render_lit_tiles' are one function
+ *   (sqrt, x 255.99, min, truncation, NaN -> 0 on the double mean), so the 8-bit frame is the single context's too.
+ *   Errors, all reported before the handle is examined: nx or ny <= 0 or more than 2^30 pixels, tile_first < 0, tile_stride <= 0, n_slots < 0 or
+ *   > 2^24, a NULL buffer with n_slots > 0: RTMI_E_ARG.  Then the handle: RTMI_E_STATE.  n_slots == 0 launches nothing.  Asynchronous on `stream`. */
+int rtmi_lit_tiles_records_device(rtmi_ctx *ctx, int32_t nx, int32_t ny, int32_t tile_first, int32_t tile_stride, int32_t n_slots, const void *d_state,
+                                  const void *d_linear, const void *d_stderr, void *d_out_rec, void *stream);
+/*   THE FRAME is an object the library owns, named by a 64-bit handle that is never 0 (a JNA host holds a long).  rtmi_multi_lit_create takes
+ *   n = 1 .. RTMI_MULTI_LIT_MAX replicas of one scene, each on its own context, as rtmi_render_multi takes them (replaces the caller's buffers of
+ *   rtmi_render_lit_tiles_device, per device).  Per replica the frame holds the whole-frame state (RTMI_RAYS_REC doubles = 80 bytes per pixel), the
+ *   linear and stderr planes, the replica's tile list and its record; on replica 0's device the gathered records.  Whole-frame buffers on every
+ *   replica cost n times the memory a compact layout would -- 166 MB of state per device at 1920 x 1080, 232 MB with the planes -- because the
+ *   sample path indexes its state by the global pixel; a compact layout would mean editing those kernels.
+ *   THE DEALING is round-robin: replica r owns tiles r, r + n, ... and starts with all of them listed, ascending.  A replica that owns no tile
+ *   (n > T) is legal and launches no trace.  Every replica's record holds per = ceil(T / n) slots.
+ *   rtmi_multi_lit_destroy frees the buffers (after every replica's stream is idle); destroy the frame before its scenes. */
+#define RTMI_MULTI_LIT_MAX 8
+int rtmi_multi_lit_create(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t ny, uint64_t *out_frame);
+int rtmi_multi_lit_destroy(uint64_t frame);
+/*   THE CALL ORDER.  rtmi_multi_lit_render adds samples [k, k + s_count) to every listed tile, k being the frame's own count (the samples its active
+ *   tiles hold; 0 after create and reset): on every replica, on its own context stream, rtmi_render_lit_tiles_device's work on the replica's list with
+ *   `estimator` 0, 1, 2 and `volume` 0 or 1 -- estimator 3 is the proposal rule, rtmi_render_lit_ris_device's work with a list, which has no volume
+ *   form -- then the record of its dealt tiles and the call's four counters behind them; all replicas are enqueued before any is waited for.  ONE
+ *   gather -- rtmi_render_multi's paths and RTMI_MULTI_GATHER values: same-device copies, peer copies, the grouped ncclGather; rtmi_last_gather_path
+ *   and rtmi_last_gather_ms on replica 0's context report it; n = 1 moves nothing -- brings per * 320 + 4 eight-byte words per replica to replica 0's
+ *   device, which assembles the frame and sums the counters (replaces rtmi_render_lit_tiles / rtmi_render_lit_ris on one context).
+ *   Outputs, each may be NULL, host arrays in the first form and buffers on replica 0's device in the second: linear [ny][nx][3] doubles, rgb8
+ *   [ny][nx][3], stderr [ny][nx] doubles, samples [ny][nx] int32, counters[4] = rtmi_render_lit_tiles' four of THIS call summed over the replicas.
+ *   For every n, either gather path, every estimator, F64 and F32, any sequence of chunk sizes and any "workspace_bytes" split they are BIT-IDENTICAL
+ *   to what one context holds after the same rtmi_render_lit_tiles / rtmi_tiles_retire calls on one list.  Both forms return with every replica's
+ *   stream synchronised.
+ *   rtmi_multi_lit_retire: every replica runs rtmi_tiles_retire_device on its own list (replaces rtmi_tiles_retire on one list).  noise NULL: each
+ *   replica tests its own stderr plane, which is valid on exactly its own tiles -- all the decision reads.  Otherwise noise is a whole-frame map
+ *   [ny][nx], on the host (first form) or on replica 0's device and complete on its context stream (second form) -- the denoiser's filtered error --
+ *   and is sent to every replica first.  *out_count = the tiles still listed, summed over the replicas.
+ *   rtmi_multi_lit_status: *out_k = k, *out_active = the listed tiles of all replicas (either may be NULL).  rtmi_multi_lit_active_tiles: the
+ *   replicas' lists merged in ascending order into out_tiles[capacity]; *out_count is their number, and a capacity below it is RTMI_E_ARG with
+ *   *out_count set.  rtmi_multi_lit_reset: k = 0 and every tile listed again; no buffer is freed.
+ *   THE KEY.  The first render after create or reset fixes precision, depth, seed, estimator, volume, light_choice (where the estimator reads it), the
+ *   light list and the revisions of the replicas' scenes.  A later render under another key is RTMI_E_STATE and rtmi_last_error gives both keys.  A
+ *   camera, material or geometry edit of a scene changes its revision: a frame is not continued across an edit, it is reset.
+ *   Errors of a render, in this order: frame 0, s_count <= 0, depth < 0, estimator outside 0..3, volume outside {0, 1}, estimator 3 with volume 1, an
+ *   unknown precision: RTMI_E_ARG, before the handle is examined; a handle that names no frame: RTMI_E_STATE; n_lights outside the sibling's range, a
+ *   light_choice the MIS rule does not know: RTMI_E_ARG; the key: RTMI_E_STATE; then, replica by replica, the sibling's own checks in its order (the
+ *   scene's tables, an ineligible listed light: RTMI_E_ARG, the media mode: RTMI_E_UNSUPPORTED; the text names the replica) and the gather policy.
+ *   Every check of every replica runs before the first launch: a refusal leaves the frame exactly as it was.  A failure after a launch resets the
+ *   frame on every replica once every touched stream is idle.  rtmi_multi_lit_retire: frame 0, an eps that is negative, NaN or infinite, out_count
+ *   NULL: RTMI_E_ARG; a bad handle or a frame without samples: RTMI_E_STATE. */
+int rtmi_multi_lit_render(uint64_t frame, int32_t precision, int32_t s_count, int32_t depth, uint64_t seed, int32_t estimator, int32_t n_lights,
+                          const int32_t *light_prims, int32_t light_choice, int32_t volume, double *out_linear, uint8_t *out_rgb8, double *out_stderr,
+                          int32_t *out_samples, uint64_t *out_counters);
+int rtmi_multi_lit_render_device(uint64_t frame, int32_t precision, int32_t s_count, int32_t depth, uint64_t seed, int32_t estimator, int32_t n_lights,
+                                 const int32_t *light_prims, int32_t light_choice, int32_t volume, void *d_out_linear, void *d_out_rgb8, void *d_out_stderr,
+                                 void *d_out_samples, void *d_out_counters);
+int rtmi_multi_lit_retire(uint64_t frame, const double *noise, double eps, int32_t *out_count);
+int rtmi_multi_lit_retire_device(uint64_t frame, const void *d_noise, double eps, int32_t *out_count);
+int rtmi_multi_lit_status(uint64_t frame, int32_t *out_k, int32_t *out_active);
+int rtmi_multi_lit_active_tiles(uint64_t frame, int32_t capacity, int32_t *out_tiles, int32_t *out_count);
+int rtmi_multi_lit_reset(uint64_t frame);
 /* How the last rtmi_render_multi* on replica 0's context moved the replicas' records to replica 0's device. */
 enum { RTMI_GATHER_NONE = 0,        /* one replica: nothing to move */
        RTMI_GATHER_SAME_DEVICE = 1, /* replicas share replica 0's device (rehearsal on a one-GPU host): device-to-device copies */

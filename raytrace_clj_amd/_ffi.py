@@ -48,6 +48,8 @@ SYMBOLS = [
     "rtmi_render_rays_vol", "rtmi_render_rays_vol_device", "rtmi_probe_paths_vol", "rtmi_render_lit_vol", "rtmi_render_lit_vol_device",
     "rtmi_render_lit_tiles", "rtmi_render_lit_tiles_device", "rtmi_tiles_retire", "rtmi_tiles_retire_device",
     "rtmi_render_rays_ris", "rtmi_render_rays_ris_device", "rtmi_probe_paths_ris", "rtmi_render_lit_ris", "rtmi_render_lit_ris_device",
+    "rtmi_lit_tiles_records_device", "rtmi_multi_lit_create", "rtmi_multi_lit_destroy", "rtmi_multi_lit_render", "rtmi_multi_lit_render_device",
+    "rtmi_multi_lit_retire", "rtmi_multi_lit_retire_device", "rtmi_multi_lit_status", "rtmi_multi_lit_active_tiles", "rtmi_multi_lit_reset",
 ]
 
 F64, F32 = 0, 1
@@ -211,6 +213,16 @@ def lib():
     L.rtmi_render_lit_ris_device.argtypes = [vp, i32, i32, i32, i32, i32, i32, u64, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rtmi_tiles_retire.argtypes = [vp, i32, i32, vp, dbl, i32, vp, vp, C.POINTER(i32)]
     L.rtmi_tiles_retire_device.argtypes = [vp, i32, i32, vp, dbl, i32, vp, vp, C.POINTER(i32), vp]
+    L.rtmi_lit_tiles_records_device.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.rtmi_multi_lit_create.argtypes = [i32, C.POINTER(vp), i32, i32, C.POINTER(u64)]
+    L.rtmi_multi_lit_destroy.argtypes = [u64]
+    L.rtmi_multi_lit_render.argtypes = [u64, i32, i32, i32, u64, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.rtmi_multi_lit_render_device.argtypes = L.rtmi_multi_lit_render.argtypes
+    L.rtmi_multi_lit_retire.argtypes = [u64, vp, dbl, C.POINTER(i32)]
+    L.rtmi_multi_lit_retire_device.argtypes = L.rtmi_multi_lit_retire.argtypes
+    L.rtmi_multi_lit_status.argtypes = [u64, C.POINTER(i32), C.POINTER(i32)]
+    L.rtmi_multi_lit_active_tiles.argtypes = [u64, i32, vp, C.POINTER(i32)]
+    L.rtmi_multi_lit_reset.argtypes = [u64]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("rtmi_version",):

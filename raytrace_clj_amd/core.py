@@ -153,6 +153,14 @@ class Context:
                                                   ptr(tiles_in if tiles_out is None else tiles_out), C.byref(n), ptr(stream)))
         return n.value
 
+    def lit_tiles_records_device(self, nx, ny, tile_first, tile_stride, n_slots, state, linear, stderr, out_rec, stream=None):
+        """rtmi_lit_tiles_records_device: the dealt tiles tile_first, tile_first + tile_stride, ... out of render_lit_tiles_device's whole-frame
+        buffers (state [nx * ny, RAYS_REC], linear [ny, nx, 3], stderr [ny, nx]) into out_rec [n_slots, 64, PROG_REC] -- mean, stderr, samples per
+        pixel, the record assemble_progressive_device takes; pixels outside the image and slots past the last tile are zeros.  HBM-resident
+        buffers; asynchronous, render_device's stream semantics."""
+        check(_ffi.lib().rtmi_lit_tiles_records_device(self.handle, int(nx), int(ny), int(tile_first), int(tile_stride), int(n_slots), ptr(state),
+                                                       ptr(linear), ptr(stderr), ptr(out_rec), ptr(stream)))
+
     # ---- the edge-aware denoiser: a pure image operation (rtmi_denoise*) ---------------------------------------------------------
     def denoise(self, linear, stderr=None, features=None, iterations=DENOISE_ITERATIONS, sigma_c=DENOISE_SIGMA_C, sigma_n=DENOISE_SIGMA_N,
                 sigma_a=DENOISE_SIGMA_A, sigma_d=DENOISE_SIGMA_D):
@@ -2080,6 +2088,32 @@ def _lit_flags(argv, panorama=False, orbit=False, nee=False, mis=False):
 VOL_ESTIMATORS = {"nee": 1, "mis": 2}  # estimator of the volume rule's calls
 
 
+def _devices_flags(argv, lit=False):
+    """-> (the other arguments, None or the device ordinals of --devices 0,1,...: the light-sampled frame is refined on one replica per listed device
+    (dist.MultiDevice; an ordinal may repeat, to rehearse on one GPU)); accepted only together with --lit or --lit-vol"""
+    rest, devices, k = [], None, 0
+    while k < len(argv):
+        a = argv[k]
+        if a == "--devices":
+            if devices is not None:
+                raise SystemExit("--devices given twice")
+            words = argv[k + 1].split(",") if k + 1 < len(argv) else []
+            if not words or not all(w.isdigit() for w in words):
+                raise SystemExit("--devices takes device ordinals separated by commas, as in --devices 0,1 (got %r)" % (argv[k + 1] if k + 1 < len(argv) else ""))
+            devices = [int(w) for w in words]
+            if len(devices) > 8:
+                raise SystemExit("--devices takes at most 8 devices (got %d)" % len(devices))
+            k += 1
+        elif a.startswith("--devices"):
+            raise SystemExit("--devices takes its list as a separate word (got %r)" % a)
+        else:
+            rest.append(a)
+        k += 1
+    if devices is not None and not lit:
+        raise SystemExit("--devices goes with --lit or --lit-vol: it spreads the light-sampled frame over the listed devices")
+    return rest, devices
+
+
 def _lit_vol_flags(argv, panorama=False, orbit=False, nee=False, mis=False):
     """-> (the other arguments, None or (estimator, light choice) of --lit-vol [nee|mis[:uniform|:power]], default mis); it is taken out of the
     arguments before --lit is looked for, and the modes it does not combine with (--lit among them) are refused here, before any device work"""
@@ -2209,7 +2243,10 @@ def main(argv=None):
     --orbit or --panorama.
     --lit / --lit-vol with --adaptive EPS (or --adaptive-denoised EPS) refine their frame adaptively too (DeviceScene.refine_lit_adaptive, rounds of
     --chunk): an 8x8 tile stops taking samples once its standard error (its filtered standard error) is <= EPS everywhere, ns is the cap, and a line
-    reports the share of the pixel-samples taken."""
+    reports the share of the pixel-samples taken.
+    --devices 0,1,... refines the frame of --lit / --lit-vol on one replica per listed device (dist.MultiDevice.render_lit / refine_lit_adaptive: the
+    8x8 tiles dealt round-robin, one gather per chunk), with or without --chunk, --adaptive or --adaptive-denoised: the same image, bit for bit.  It
+    is refused without --lit or --lit-vol."""
     from . import scene as scenes
     argv = list(sys.argv[1:] if argv is None else argv)
     argv, direct = _direct_flags(argv)
@@ -2229,6 +2266,7 @@ def main(argv=None):
     argv, mis = _mis_flags(argv, panorama, orbit_views is not None)
     argv, vol_mode = _lit_vol_flags(argv, panorama, orbit_views is not None, nee, mis is not None)
     argv, lit_mode = _lit_flags(argv, panorama, orbit_views is not None, nee, mis is not None)
+    argv, devices = _devices_flags(argv, lit_mode is not None or vol_mode is not None)
     argv, accumulate = _accumulate_flags(argv, orbit_views)
     argv, adaptive_denoised = _adaptive_denoised_flags(argv)
     if adaptive_denoised is not None and not any(a.split("=", 1)[0] == "--denoise" for a in argv):
@@ -2366,6 +2404,21 @@ def main(argv=None):
     lit_eps = adaptive if adaptive is not None else adaptive_denoised  # the frame's stopping rule is the light-sampled frame's too
     for mode, volume, out_name in ((lit_mode, False, _lit_name(name)), (vol_mode, True, _lit_vol_name(name))):
         if mode is None:
+            continue
+        if devices is not None:  # one replica per listed device: the same frame, bit for bit
+            from . import dist
+            md = dist.MultiDevice(sc, devices)
+            try:
+                kw = dict(estimator=mode[0], volume=volume, light_choice=mode[1])
+                if lit_eps is None:
+                    frame = md.render_lit(nx, ny, nr, chunk=chunk, **kw)[1]
+                else:
+                    more = {} if adaptive is not None else dict(denoised=True, na=FEATURE_SAMPLES if dn_samples is None else dn_samples, iterations=dn_iterations)
+                    frame, smp = md.refine_lit_adaptive(nx, ny, nr, chunk, lit_eps, **kw, **more)[1:4:2]
+                    print("%s: %.1f%% of the %d pixel-samples taken" % ("--lit-vol" if volume else "--lit", 100.0 * float(smp.sum()) / (nx * ny * nr), nx * ny * nr))
+            finally:
+                md.close()
+            _save_image(out_name, frame)
             continue
         ds = DeviceScene(sc)
         try:

@@ -27,6 +27,7 @@
 #include <cstring>
 #include <array>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -1555,6 +1556,34 @@ __global__ void __launch_bounds__(kCompactBlock) lit_tiles_count_kernel(const in
 __global__ void __launch_bounds__(kBlock) lit_quantise_kernel(const double *__restrict__ mean, size_t n, unsigned char *__restrict__ out_rgb8) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out_rgb8[i] = quantise8(mean[i]);
+}
+
+// rtmi_lit_tiles_records_device: a replica's dealt tiles out of its WHOLE-FRAME planes into progressive_record_kernel's layout, rec[n_slots][64][RTMI_PROG_REC]:
+// slot t is global tile first + t * stride, lane l = local pixel l.  The mean and the error are the planes' values as they are, the samples word [9] of the
+// pixel's RTMI_RAYS_REC record.  One thread per record pixel, so a wave writes one contiguous 64 * 40 = 2560-byte run; a slot whose tile lies at or past the
+// frame's last (the padding of a gathered record) and a pixel outside the image read nothing and hold five zeros.  No tile list is read.
+__global__ void __launch_bounds__(kBlock) lit_tiles_record_kernel(const double *__restrict__ state, const double *__restrict__ mean, const double *__restrict__ se,
+                                                                  int first, int stride, int tiles_x, int n_frame_tiles, int nx, int ny, int n_slots,
+                                                                  double *__restrict__ rec) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)n_slots * 64) return;
+    const int t = (int)(gid >> 6), l = (int)(gid & 63);
+    const long long gtile = (long long)first + (long long)t * stride;
+    double v[RTMI_PROG_REC] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (gtile < (long long)n_frame_tiles) {
+        const int ty = (int)(gtile / tiles_x), tx = (int)(gtile - (long long)ty * tiles_x);
+        const int x = tx * RTMI_TILE + (l & 7), y = ty * RTMI_TILE + (l >> 3);
+        if (x < nx && y < ny) {
+            const size_t g = (size_t)y * (size_t)nx + (size_t)x;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = mean[g * 3 + c];
+            v[3] = se[g];
+            v[4] = state[g * RTMI_RAYS_REC + 9];
+        }
+    }
+    double *o = rec + (size_t)gid * RTMI_PROG_REC;
+#pragma unroll
+    for (int c = 0; c < RTMI_PROG_REC; ++c) o[c] = v[c];
 }
 
 // ---- closest-hit and any-hit queries on caller-supplied rays (rtmi_query_hits*, rtmi_query_occluded*) ------------------------------------------------
@@ -3362,7 +3391,7 @@ RTMI_EXPORT int rtmi_test_stage_layout(int32_t n, const uint64_t *elem_bytes, co
 }
 RTMI_EXPORT const char *rtmi_last_error(void) { return g_err.c_str(); }
 RTMI_EXPORT const char *rtmi_backend_name(void) { return "hip-gfx950"; }
-RTMI_EXPORT int rtmi_version(void) { return 219; } // 219: light-sampled frames over a caller's tile list and the stateless retirement (rtmi_render_lit_tiles*, rtmi_tiles_retire*); 218: direct lighting from the scene's area lights (rtmi_scene_lights, rtmi_direct_irradiance*, rtmi_render_direct*); 217: occlusion rays generated on the device (rtmi_occlusion_hemisphere*, rtmi_occlusion_targets*, rtmi_ambient_occlusion*); 216: closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*); 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
+RTMI_EXPORT int rtmi_version(void) { return 220; } // 220: light-sampled frames on several GPUs (rtmi_lit_tiles_records_device, rtmi_multi_lit_*); 219: light-sampled frames over a caller's tile list and the stateless retirement (rtmi_render_lit_tiles*, rtmi_tiles_retire*); 218: direct lighting from the scene's area lights (rtmi_scene_lights, rtmi_direct_irradiance*, rtmi_render_direct*); 217: occlusion rays generated on the device (rtmi_occlusion_hemisphere*, rtmi_occlusion_targets*, rtmi_ambient_occlusion*); 216: closest-hit and any-hit queries (rtmi_query_hits*, rtmi_query_occluded*); 215: caller-supplied rays (rtmi_render_rays*); 214: the geometry of a live scene (rtmi_scene_set_geometry: the trees refit on the device); 213: the materials of a live scene (rtmi_scene_set_materials, rtmi_scene_set_materials_stream); 212: rtmi_scene_tree_info; 211: rtmi_reproject* (temporal accumulation); 210: the camera of a live scene (rtmi_scene_set_camera, rtmi_scene_set_camera_stream, rtmi_scene_camera); 209: progressive / adaptive frames on dealt tiles and several devices (rtmi_render_adaptive_tiles_device, rtmi_assemble_progressive_device, rtmi_render_multi_adaptive*); 208: tiles retired by a caller's noise map (rtmi_adaptive_retire*); 207: first-hit feature buffers and the edge-aware denoiser (rtmi_render_features*, rtmi_denoise*); 206: adaptive sampling (rtmi_render_adaptive*, rtmi_adaptive_status, rtmi_adaptive_active_tiles); 205: progressive rendering (rtmi_render_progressive*, rtmi_progressive_samples / _release); 204: rtmi_probe_math2
 RTMI_EXPORT uint64_t rtmi_sample_key(uint64_t seed, uint64_t pixel, uint64_t sample) { return sample_key(seed, pixel, sample); }
 
 RTMI_EXPORT int rtmi_init(int device, uint32_t flags, rtmi_ctx **out_ctx) {
@@ -7503,4 +7532,456 @@ RTMI_EXPORT int rtmi_tiles_retire(rtmi_ctx *c, int32_t nx, int32_t ny, const dou
     if (rc || *out_count == 0) return rc;
     HIP_TRY(hipMemcpy(tiles_out, kept, (size_t)*out_count * sizeof(int), hipMemcpyDeviceToHost));
     return RTMI_OK;
+}
+
+// ---- light-sampled frames on several GPUs (rtmi_lit_tiles_records_device, rtmi_multi_lit_*): THE DEALT LIT FRAME of rtmi.h ---------------------------------
+// The sample path is rtmi_render_lit_tiles_device's (rtmi_render_lit_ris_device's for the proposal rule) on every replica's own list, the decision
+// rtmi_tiles_retire_device's; lit_tiles_record_kernel packs a replica's dealt tiles into the record of the dealt progressive frames, and the gather, the
+// assemble and the counter sums behind it are those frames' (enqueue_gather, assemble_progressive_kernel, sum_counters_kernel).
+RTMI_EXPORT int rtmi_lit_tiles_records_device(rtmi_ctx *c, int32_t nx, int32_t ny, int32_t tile_first, int32_t tile_stride, int32_t n_slots, const void *d_state,
+                                              const void *d_linear, const void *d_stderr, void *d_out_rec, void *stream) {
+    if (nx <= 0 || ny <= 0 || (long long)nx * ny > (1ll << 30)) return fail(RTMI_E_ARG, "nx, ny must be > 0 and the frame at most 2^30 pixels (got %d %d)", nx, ny);
+    if (tile_first < 0 || tile_stride <= 0) return fail(RTMI_E_ARG, "tile_first must be >= 0 and tile_stride > 0 (got %d, %d)", tile_first, tile_stride);
+    if (n_slots < 0 || n_slots > (1 << 24)) return fail(RTMI_E_ARG, "n_slots must be in [0, 2^24] (got %d)", n_slots);
+    if (n_slots > 0 && (!d_state || !d_linear || !d_stderr || !d_out_rec)) return fail(RTMI_E_ARG, "d_state, d_linear, d_stderr or d_out_rec is NULL");
+    if (!ctx_ok(c)) return fail(RTMI_E_STATE, "invalid context handle");
+    if (n_slots == 0) return RTMI_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const long long npx = (long long)n_slots * 64;
+    hipLaunchKernelGGL(lit_tiles_record_kernel, dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream_of(c, stream), as<const double>(d_state),
+                       as<const double>(d_linear), as<const double>(d_stderr), tile_first, tile_stride, tiles_x_of(nx), tiles_x_of(nx) * tiles_y_of(ny), nx, ny,
+                       n_slots, as<double>(d_out_rec));
+    HIP_TRY(hipGetLastError());
+    return RTMI_OK;
+}
+
+namespace {
+// What the first render after create / reset fixes: a later render continues the frame only under the same key.
+struct LitKey {
+    int precision = 0, depth = 0, estimator = 0, volume = 0, light_choice = 0, n_lights = -1; // n_lights -1: no list (the scene's eligible lights)
+    uint64_t seed = 0;
+    std::vector<int32_t> lights;
+    std::vector<uint64_t> revisions; // of the replicas' scenes
+    bool operator==(const LitKey &o) const {
+        return precision == o.precision && depth == o.depth && estimator == o.estimator && volume == o.volume && light_choice == o.light_choice &&
+               n_lights == o.n_lights && seed == o.seed && lights == o.lights && revisions == o.revisions;
+    }
+    std::string text() const {
+        char b[192];
+        snprintf(b, sizeof b, "precision %d, depth %d, seed %llu, estimator %d, volume %d, light_choice %d, lights ", precision, depth, (unsigned long long)seed,
+                 estimator, volume, light_choice);
+        std::string s = b;
+        if (n_lights < 0) s += "NULL";
+        else { s += "["; for (size_t i = 0; i < lights.size(); ++i) s += (i ? " " : "") + std::to_string(lights[i]); s += "]"; }
+        s += ", scene revisions [";
+        for (size_t i = 0; i < revisions.size(); ++i) s += (i ? " " : "") + std::to_string((unsigned long long)revisions[i]);
+        return s + "]";
+    }
+};
+
+struct MultiLitReplica {
+    DevBuf state, lin, se, tiles, rec, noise; // whole-frame state and planes, the active list, the record (replicas > 0), a caller's map (replicas > 0)
+    std::vector<int32_t> owned;               // the dealing: tiles r, r + n, ..., ascending
+    int n_active = 0;
+};
+
+struct MultiLitFrame {
+    int n = 0, nx = 0, ny = 0, n_tiles = 0, per = 0, k = 0;
+    bool keyed = false;
+    LitKey key;
+    std::vector<rtmi_scene *> scenes;
+    std::vector<MultiLitReplica> rep;
+    DevBuf gathered; // on replica 0's device: the records of all replicas, replica 0's in place
+    size_t tile_words() const { return (size_t)per * 64 * RTMI_PROG_REC; }
+    size_t rec_words() const { return tile_words() + 4; } // the tiles, then the call's four counters
+};
+
+std::map<uint64_t, std::unique_ptr<MultiLitFrame>> g_lit_frames; // by handle (never 0); under g_multi_mu
+uint64_t g_lit_next = 1;
+
+int lit_frame_of(uint64_t handle, MultiLitFrame **f) {
+    if (handle == 0) return fail(RTMI_E_ARG, "frame is NULL");
+    const auto it = g_lit_frames.find(handle);
+    if (it == g_lit_frames.end()) return fail(RTMI_E_STATE, "invalid frame handle (destroyed, or never created)");
+    *f = it->second.get();
+    for (int r = 0; r < (*f)->n; ++r)
+        if (!scene_ok((*f)->scenes[(size_t)r])) return fail(RTMI_E_STATE, "replica %d's scene was destroyed under the frame", r);
+    return RTMI_OK;
+}
+
+void multi_lit_free(MultiLitFrame &f) {
+    for (int r = 0; r < f.n; ++r) {
+        MultiLitReplica &p = f.rep[(size_t)r];
+        if (scene_ok(f.scenes[(size_t)r])) { (void)hipSetDevice(f.scenes[(size_t)r]->ctx->device); (void)hipStreamSynchronize(f.scenes[(size_t)r]->ctx->stream); }
+        p.state.release(); p.lin.release(); p.se.release(); p.tiles.release(); p.rec.release(); p.noise.release();
+        if (r == 0) f.gathered.release();
+    }
+}
+
+// k = 0, every tile listed on its owner, the state's counts zero; waits for every replica's stream first
+int multi_lit_reset(MultiLitFrame &f) {
+    for (int r = 0; r < f.n; ++r) {
+        MultiLitReplica &p = f.rep[(size_t)r];
+        rtmi_ctx *c = f.scenes[(size_t)r]->ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (!p.owned.empty()) HIP_TRY(hipMemcpy(p.tiles.p, p.owned.data(), p.owned.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemsetAsync(p.state.p, 0, p.state.bytes, c->stream)); // (the context's stream is not ordered with the null stream)
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        p.n_active = (int)p.owned.size();
+        c->consume_pending = false;
+    }
+    f.k = 0; f.keyed = false;
+    return RTMI_OK;
+}
+
+// the argument checks of a render that need no frame, in the header's order
+int check_multi_lit_args(int precision, int s_count, int depth, int estimator, int light_choice, int volume) {
+    if (s_count <= 0 || depth < 0) return fail(RTMI_E_ARG, "s_count must be > 0 and depth >= 0 (got %d, %d)", s_count, depth);
+    if (estimator < 0 || estimator > 3) return fail(RTMI_E_ARG, "estimator must be 0 (plain), 1 (the NEE rule), 2 (the MIS rule) or 3 (the proposal rule) (got %d)", estimator);
+    if (volume != 0 && volume != 1) return fail(RTMI_E_ARG, "volume must be 0 or 1 (got %d)", volume);
+    if (estimator == 3 && volume == 1) return fail(RTMI_E_ARG, "estimator 3 (the proposal rule) has no volume form");
+    if (precision != RTMI_F64 && precision != RTMI_F32) return fail(RTMI_E_ARG, "precision must be RTMI_F64 or RTMI_F32");
+    return RTMI_OK;
+}
+
+struct LitPrep { RisLightTable Rt; RaysFrame F; bool work = false; };
+
+// d_out_*: on replica 0's device, each may be null.  Returns with every replica's stream synchronised.
+int multi_lit_render_impl(MultiLitFrame &f, int precision, int s_count, int depth, uint64_t seed, int estimator, int n_lights, const int32_t *light_prims,
+                          int light_choice, int volume, double *d_lin, unsigned char *d_q, double *d_se, int *d_smp, u64 *d_cnt) {
+    const int n = f.n;
+    const bool ris = estimator == 3;
+    const int est = ris ? 2 : estimator, choice = estimator == 2 ? light_choice : 0;
+    if (light_prims && (n_lights < 0 || n_lights > RTMI_DIRECT_MAX_LIGHTS)) return fail(RTMI_E_ARG, "n_lights must be in [0, %d] (got %d)", RTMI_DIRECT_MAX_LIGHTS, n_lights);
+    if (estimator == 2 && light_choice != 0 && light_choice != 1) return fail(RTMI_E_ARG, "light_choice must be 0 (uniform) or 1 (by power) (got %d)", light_choice);
+    // the key
+    LitKey key;
+    key.precision = precision; key.depth = depth; key.estimator = estimator; key.volume = volume; key.light_choice = choice; key.seed = seed;
+    key.n_lights = light_prims ? n_lights : -1;
+    if (light_prims) key.lights.assign(light_prims, light_prims + n_lights);
+    for (int r = 0; r < n; ++r) key.revisions.push_back(f.scenes[(size_t)r]->revision);
+    if (f.keyed && !(key == f.key))
+        return fail(RTMI_E_STATE, "the frame holds %d samples under {%s}; this call's key is {%s}: rtmi_multi_lit_reset starts another frame", f.k, f.key.text().c_str(),
+                    key.text().c_str());
+    if ((long long)f.k + s_count > INT32_MAX) return fail(RTMI_E_ARG, "k + s_count = %d + %d overflows int32", f.k, s_count);
+    // the sibling's checks on every replica, before the first launch
+    std::vector<LitPrep> prep((size_t)n);
+    for (int r = 0; r < n; ++r) {
+        MultiLitReplica &p = f.rep[(size_t)r];
+        LitPrep &q = prep[(size_t)r];
+        const LitTileArgs tl{volume, p.n_active, nullptr, p.tiles.p};
+        const int rc = lit_frame_begin(f.scenes[(size_t)r], precision, f.nx, f.ny, f.k, s_count, depth, est, n_lights, light_prims, choice, nullptr, p.lin.p, p.se.p,
+                                       q.Rt.m, q.F, &q.work, volume == 1, &tl);
+        if (rc) { const std::string why = g_err; return fail(rc, "replica %d: %s", r, why.c_str()); }
+        if (q.work && ris) make_ris_rows(q.Rt);
+    }
+    GatherPlan plan;
+    int rc = plan_gather(n, f.scenes.data(), plan);
+    if (rc) return rc;
+    rtmi_ctx *c0 = f.scenes[0]->ctx;
+    char *gathered = reinterpret_cast<char *>(f.gathered.p);
+    const size_t rec = f.rec_words(), tile_words = f.tile_words();
+    // A failure from here on resets the frame on every replica once every touched stream is idle (some replicas hold the new samples, some do not).
+    int launched = 0;
+    auto bail = [&](int code) {
+        const std::string keep = g_err;
+        for (int r = 0; r < launched; ++r) { (void)hipSetDevice(f.scenes[(size_t)r]->ctx->device); (void)hipStreamSynchronize(f.scenes[(size_t)r]->ctx->stream); }
+        (void)hipSetDevice(c0->device); (void)hipStreamSynchronize(c0->stream);
+        (void)multi_lit_reset(f);
+        g_err = keep;
+        return code;
+    };
+#define HIP_BAIL(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return bail(fail(RTMI_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_))); } while (0)
+    // 1. every replica, on its own context stream: the trace and the fold of its listed tiles, the record of its dealt tiles, the call's counters
+    std::vector<char *> recs((size_t)n);
+    for (int r = 0; r < n; ++r) {
+        MultiLitReplica &p = f.rep[(size_t)r];
+        LitPrep &q = prep[(size_t)r];
+        rtmi_scene *s = f.scenes[(size_t)r];
+        rtmi_ctx *cr = s->ctx;
+        launched = r + 1;
+        HIP_BAIL(hipSetDevice(cr->device));
+        char *buf = recs[(size_t)r] = r == 0 ? gathered : reinterpret_cast<char *>(p.rec.p);
+        if (cr->consume_pending) { // the previous call's copy out of this record (on replica 0's stream) must have read it
+            HIP_BAIL(hipStreamWaitEvent(cr->stream, cr->ev_consumed, 0));
+            cr->consume_pending = false;
+        }
+        u64 *cnt = reinterpret_cast<u64 *>(buf) + tile_words;
+        if (q.work) {
+            q.F.out_camera = nullptr; q.F.d_tiles = as<const int>(p.tiles.p); q.F.d_rgb8 = nullptr;
+            rc = lit_frame_run(s, precision, f.nx, f.ny, f.k, s_count, depth, seed, est, q.Rt.m, q.F, as<double>(p.state.p), as<double>(p.lin.p), nullptr,
+                               as<double>(p.se.p), nullptr, cnt, cr->stream, volume == 1, ris ? &q.Rt : nullptr);
+            if (rc) return bail(rc);
+        } else
+            HIP_BAIL(hipMemsetAsync(cnt, 0, 4 * sizeof(u64), cr->stream)); // no tile listed here: nothing traced
+        const long long npx = (long long)f.per * 64;
+        hipLaunchKernelGGL(lit_tiles_record_kernel, dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, cr->stream, as<const double>(p.state.p),
+                           as<const double>(p.lin.p), as<const double>(p.se.p), r, n, tiles_x_of(f.nx), f.n_tiles, f.nx, f.ny, f.per, reinterpret_cast<double *>(buf));
+        HIP_BAIL(hipGetLastError());
+        if (!plan.use_rccl && r > 0) { rc = ensure_event(&cr->ev_done); if (rc) return bail(rc); HIP_BAIL(hipEventRecord(cr->ev_done, cr->stream)); }
+    }
+    // 2. ONE gather to replica 0's device (n = 1 without RTMI_MULTI_GATHER=rccl: nothing to move)
+    rc = enqueue_gather(n, f.scenes.data(), plan, recs, gathered, rec);
+    if (rc) return bail(rc);
+    // 3. replica 0 un-tiles, quantises and sums the counters
+    HIP_BAIL(hipSetDevice(c0->device));
+    if (d_lin || d_q || d_se || d_smp) {
+        const long long npx = (long long)f.nx * f.ny;
+        hipLaunchKernelGGL(assemble_progressive_kernel, dim3((unsigned)((npx + kBlock - 1) / kBlock)), dim3(kBlock), 0, c0->stream,
+                           reinterpret_cast<const double *>(gathered), n, rec, tiles_x_of(f.nx), f.nx, f.ny, d_lin, d_q, d_se, d_smp);
+        HIP_BAIL(hipGetLastError());
+    }
+    if (d_cnt) { // the record ends with four counters: sum_counters_kernel sums two
+        for (int h = 0; h < 2; ++h)
+            hipLaunchKernelGGL(sum_counters_kernel, dim3(1), dim3(64), 0, c0->stream, reinterpret_cast<const u64 *>(gathered), n, rec, tile_words + 2 * (size_t)h,
+                               d_cnt + 2 * h);
+        HIP_BAIL(hipGetLastError());
+    }
+    // 4. every stream idle; replica 0 last: its stream carries the gather and the assemble
+    for (int r = n - 1; r >= 0; --r) {
+        rtmi_ctx *cr = f.scenes[(size_t)r]->ctx;
+        HIP_BAIL(hipSetDevice(cr->device));
+        HIP_BAIL(hipStreamSynchronize(cr->stream));
+    }
+#undef HIP_BAIL
+    for (int r = 1; r < n; ++r) f.scenes[(size_t)r]->ctx->consume_pending = false; // replica 0's stream is idle: the copies out of the records are done
+    if (!f.keyed) { f.key = key; f.keyed = true; }
+    f.k += s_count;
+    return RTMI_OK;
+}
+
+// d_noise: null (every replica's own stderr plane) or a whole-frame map on replica 0's device, complete on replica 0's context stream
+int multi_lit_retire_impl(MultiLitFrame &f, const double *d_noise, const double *host_noise, double eps, int32_t *out_count) {
+    const int n = f.n;
+    const size_t map_bytes = (size_t)f.nx * (size_t)f.ny * sizeof(double);
+    rtmi_ctx *c0 = f.scenes[0]->ctx;
+    int total = 0, touched = 0;
+    auto bail = [&](int code) {
+        const std::string keep = g_err;
+        for (int r = 0; r < touched; ++r) { (void)hipSetDevice(f.scenes[(size_t)r]->ctx->device); (void)hipStreamSynchronize(f.scenes[(size_t)r]->ctx->stream); }
+        (void)multi_lit_reset(f);
+        g_err = keep;
+        return code;
+    };
+#define HIP_BAIL(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return bail(fail(RTMI_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_))); } while (0)
+    if (d_noise || host_noise) { // the map goes to every replica first: every copy is enqueued on the stream that replica's decision runs on
+        if (d_noise && n > 1) { // a caller's device map is complete on replica 0's stream: the other streams wait for that point of it
+            HIP_TRY(hipSetDevice(c0->device));
+            const int rc = ensure_event(&c0->ev_done); // (the gather records ev_done on replicas > 0 only)
+            if (rc) return rc;
+            HIP_TRY(hipEventRecord(c0->ev_done, c0->stream));
+        }
+        for (int r = 0; r < n; ++r) {
+            MultiLitReplica &p = f.rep[(size_t)r];
+            rtmi_ctx *cr = f.scenes[(size_t)r]->ctx;
+            if (p.n_active == 0 || (d_noise && r == 0)) continue; // (replica 0 reads a device map where it lies, on the stream it is complete on)
+            HIP_TRY(hipSetDevice(cr->device));
+            const int rc = p.noise.ensure(map_bytes);
+            if (rc) return rc;
+            if (host_noise) HIP_TRY(hipMemcpyAsync(p.noise.p, host_noise, map_bytes, hipMemcpyHostToDevice, cr->stream)); // (the decision below waits for the stream)
+            else {
+                HIP_TRY(hipStreamWaitEvent(cr->stream, c0->ev_done, 0));
+                if (cr->device == c0->device) HIP_TRY(hipMemcpyAsync(p.noise.p, d_noise, map_bytes, hipMemcpyDeviceToDevice, cr->stream));
+                else HIP_TRY(hipMemcpyPeerAsync(p.noise.p, cr->device, d_noise, c0->device, map_bytes, cr->stream));
+            }
+        }
+    }
+    for (int r = 0; r < n; ++r) {
+        MultiLitReplica &p = f.rep[(size_t)r];
+        rtmi_ctx *cr = f.scenes[(size_t)r]->ctx;
+        if (p.n_active == 0) continue;
+        touched = r + 1;
+        HIP_BAIL(hipSetDevice(cr->device));
+        const double *map = !d_noise && !host_noise ? as<const double>(p.se.p) : (d_noise && r == 0) ? d_noise : as<const double>(p.noise.p);
+        int *kept = nullptr;
+        int32_t count = 0;
+        const int rc = tiles_retire_impl(cr, f.nx, f.ny, map, eps, p.n_active, as<const int>(p.tiles.p), &kept, &count, cr->stream);
+        if (rc) return bail(rc);
+        if (count > 0) HIP_BAIL(hipMemcpyAsync(p.tiles.p, kept, (size_t)count * sizeof(int), hipMemcpyDeviceToDevice, cr->stream)); // ahead of the next render
+        p.n_active = count;
+        total += count;
+    }
+#undef HIP_BAIL
+    *out_count = total;
+    return RTMI_OK;
+}
+
+int check_multi_lit_retire(MultiLitFrame &f) {
+    if (f.k == 0) return fail(RTMI_E_STATE, "the frame holds no samples to retire tiles by (rtmi_multi_lit_render first)");
+    return RTMI_OK;
+}
+} // namespace
+
+RTMI_EXPORT int rtmi_multi_lit_create(int32_t n, rtmi_scene *const *scenes, int32_t nx, int32_t ny, uint64_t *out_frame) {
+    if (n < 1 || n > RTMI_MULTI_LIT_MAX || !scenes) return fail(RTMI_E_ARG, "n must be 1..%d and scenes non-NULL (got %d)", RTMI_MULTI_LIT_MAX, n);
+    if (nx <= 0 || ny <= 0 || (long long)nx * ny > (1ll << 30)) return fail(RTMI_E_ARG, "nx, ny must be > 0 and the frame at most 2^30 pixels (got %d %d)", nx, ny);
+    if (!out_frame) return fail(RTMI_E_ARG, "out_frame is NULL");
+    for (int r = 0; r < n; ++r) {
+        if (!scene_ok(scenes[r])) return fail(RTMI_E_STATE, "replica %d: invalid scene handle", r);
+        for (int q = 0; q < r; ++q)
+            if (scenes[q]->ctx == scenes[r]->ctx) return fail(RTMI_E_ARG, "replicas %d and %d share a context (a context is not re-entrant: one per replica)", q, r);
+        if (scenes[r]->n_prims != scenes[0]->n_prims) return fail(RTMI_E_ARG, "replica %d is not a clone of replica 0", r);
+    }
+    std::lock_guard<std::mutex> lock(g_multi_mu);
+    DeviceGuard guard;
+    std::unique_ptr<MultiLitFrame> f(new MultiLitFrame);
+    f->n = n; f->nx = nx; f->ny = ny;
+    f->n_tiles = tiles_x_of(nx) * tiles_y_of(ny);
+    f->per = (f->n_tiles + n - 1) / n; // every replica's record is padded to this many tiles
+    f->scenes.assign(scenes, scenes + n);
+    f->rep.resize((size_t)n);
+    const size_t npx = (size_t)nx * (size_t)ny;
+    int rc = RTMI_OK;
+    for (int r = 0; r < n && !rc; ++r) {
+        MultiLitReplica &p = f->rep[(size_t)r];
+        for (int t = r; t < f->n_tiles; t += n) p.owned.push_back(t);
+        if (hipSetDevice(scenes[r]->ctx->device) != hipSuccess) { rc = fail(RTMI_E_DEVICE, "hipSetDevice(%d) failed", scenes[r]->ctx->device); break; }
+        rc = p.state.ensure(npx * RTMI_RAYS_REC * sizeof(double));
+        if (!rc) rc = p.lin.ensure(npx * 3 * sizeof(double));
+        if (!rc) rc = p.se.ensure(npx * sizeof(double));
+        if (!rc) rc = p.tiles.ensure(std::max<size_t>(1, p.owned.size()) * sizeof(int32_t));
+        if (!rc) rc = r == 0 ? f->gathered.ensure((size_t)n * f->rec_words() * 8) : p.rec.ensure(f->rec_words() * 8);
+        hipStream_t st = scenes[r]->ctx->stream; // (reset below waits for it)
+        if (!rc && (hipMemsetAsync(p.lin.p, 0, p.lin.bytes, st) != hipSuccess || hipMemsetAsync(p.se.p, 0, p.se.bytes, st) != hipSuccess))
+            rc = fail(RTMI_E_DEVICE, "hipMemset of replica %d's planes failed", r);
+    }
+    if (!rc) rc = multi_lit_reset(*f);
+    if (rc) { const std::string keep = g_err; multi_lit_free(*f); g_err = keep; return rc; }
+    *out_frame = g_lit_next++;
+    g_lit_frames[*out_frame] = std::move(f);
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_multi_lit_destroy(uint64_t frame) {
+    std::lock_guard<std::mutex> lock(g_multi_mu);
+    if (frame == 0) return fail(RTMI_E_ARG, "frame is NULL");
+    const auto it = g_lit_frames.find(frame);
+    if (it == g_lit_frames.end()) return fail(RTMI_E_STATE, "invalid frame handle (destroyed, or never created)");
+    DeviceGuard guard;
+    multi_lit_free(*it->second);
+    g_lit_frames.erase(it);
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_multi_lit_render_device(uint64_t frame, int32_t precision, int32_t s_count, int32_t depth, uint64_t seed, int32_t estimator, int32_t n_lights,
+                                             const int32_t *light_prims, int32_t light_choice, int32_t volume, void *d_out_linear, void *d_out_rgb8,
+                                             void *d_out_stderr, void *d_out_samples, void *d_out_counters) {
+    if (frame == 0) return fail(RTMI_E_ARG, "frame is NULL");
+    int rc = check_multi_lit_args(precision, s_count, depth, estimator, light_choice, volume);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(g_multi_mu);
+    MultiLitFrame *f = nullptr;
+    rc = lit_frame_of(frame, &f);
+    if (rc) return rc;
+    DeviceGuard guard;
+    return multi_lit_render_impl(*f, precision, s_count, depth, seed, estimator, n_lights, light_prims, light_choice, volume, as<double>(d_out_linear),
+                                 as<unsigned char>(d_out_rgb8), as<double>(d_out_stderr), as<int>(d_out_samples), as<u64>(d_out_counters));
+}
+
+RTMI_EXPORT int rtmi_multi_lit_render(uint64_t frame, int32_t precision, int32_t s_count, int32_t depth, uint64_t seed, int32_t estimator, int32_t n_lights,
+                                      const int32_t *light_prims, int32_t light_choice, int32_t volume, double *out_linear, uint8_t *out_rgb8,
+                                      double *out_stderr, int32_t *out_samples, uint64_t *out_counters) {
+    if (frame == 0) return fail(RTMI_E_ARG, "frame is NULL");
+    int rc = check_multi_lit_args(precision, s_count, depth, estimator, light_choice, volume);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(g_multi_mu);
+    MultiLitFrame *f = nullptr;
+    rc = lit_frame_of(frame, &f);
+    if (rc) return rc;
+    DeviceGuard guard;
+    rtmi_ctx *c0 = f->scenes[0]->ctx;
+    HIP_TRY(hipSetDevice(c0->device));
+    const size_t npx = (size_t)f->nx * (size_t)f->ny;
+    HostIo io(c0);
+    double *d_lin, *d_se;
+    unsigned char *d_q;
+    int *d_smp;
+    u64 *d_cnt;
+    io.out(&d_lin, npx * 3, out_linear); io.out(&d_se, npx, out_stderr); io.out(&d_smp, npx, out_samples); io.out(&d_cnt, 4, out_counters);
+    io.out(&d_q, npx * 3, out_rgb8);
+    rc = io.reserve();
+    if (rc) return rc;
+    rc = multi_lit_render_impl(*f, precision, s_count, depth, seed, estimator, n_lights, light_prims, light_choice, volume, d_lin, d_q, d_se, d_smp, d_cnt);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c0->device)); // (every replica's stream is synchronised)
+    const hipError_t e = io.download();
+    if (e != hipSuccess) {
+        (void)multi_lit_reset(*f);
+        return fail(RTMI_E_DEVICE, "multi-device lit render: %s", hipGetErrorString(e));
+    }
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_multi_lit_retire_device(uint64_t frame, const void *d_noise, double eps, int32_t *out_count) {
+    if (frame == 0) return fail(RTMI_E_ARG, "frame is NULL");
+    if (!(eps >= 0.0) || std::isinf(eps)) return fail(RTMI_E_ARG, "eps must be a finite number >= 0 (got %g)", eps);
+    if (!out_count) return fail(RTMI_E_ARG, "out_count is NULL");
+    std::lock_guard<std::mutex> lock(g_multi_mu);
+    MultiLitFrame *f = nullptr;
+    int rc = lit_frame_of(frame, &f);
+    if (!rc) rc = check_multi_lit_retire(*f);
+    if (rc) return rc;
+    DeviceGuard guard;
+    return multi_lit_retire_impl(*f, as<const double>(d_noise), nullptr, eps, out_count);
+}
+
+RTMI_EXPORT int rtmi_multi_lit_retire(uint64_t frame, const double *noise, double eps, int32_t *out_count) {
+    if (frame == 0) return fail(RTMI_E_ARG, "frame is NULL");
+    if (!(eps >= 0.0) || std::isinf(eps)) return fail(RTMI_E_ARG, "eps must be a finite number >= 0 (got %g)", eps);
+    if (!out_count) return fail(RTMI_E_ARG, "out_count is NULL");
+    std::lock_guard<std::mutex> lock(g_multi_mu);
+    MultiLitFrame *f = nullptr;
+    int rc = lit_frame_of(frame, &f);
+    if (!rc) rc = check_multi_lit_retire(*f);
+    if (rc) return rc;
+    DeviceGuard guard;
+    return multi_lit_retire_impl(*f, nullptr, noise, eps, out_count);
+}
+
+RTMI_EXPORT int rtmi_multi_lit_status(uint64_t frame, int32_t *out_k, int32_t *out_active) {
+    std::lock_guard<std::mutex> lock(g_multi_mu);
+    MultiLitFrame *f = nullptr;
+    const int rc = lit_frame_of(frame, &f);
+    if (rc) return rc;
+    int active = 0;
+    for (const MultiLitReplica &p : f->rep) active += p.n_active;
+    if (out_k) *out_k = f->k;
+    if (out_active) *out_active = active;
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_multi_lit_active_tiles(uint64_t frame, int32_t capacity, int32_t *out_tiles, int32_t *out_count) {
+    if (frame == 0) return fail(RTMI_E_ARG, "frame is NULL");
+    if (capacity < 0 || (capacity > 0 && !out_tiles) || !out_count) return fail(RTMI_E_ARG, "capacity must be >= 0 and out_tiles, out_count not NULL (got %d)", capacity);
+    std::lock_guard<std::mutex> lock(g_multi_mu);
+    MultiLitFrame *f = nullptr;
+    const int rc = lit_frame_of(frame, &f);
+    if (rc) return rc;
+    DeviceGuard guard;
+    std::vector<int32_t> all;
+    for (int r = 0; r < f->n; ++r) {
+        const MultiLitReplica &p = f->rep[(size_t)r];
+        if (p.n_active == 0) continue;
+        rtmi_ctx *c = f->scenes[(size_t)r]->ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        const size_t at = all.size();
+        all.resize(at + (size_t)p.n_active);
+        HIP_TRY(hipMemcpy(all.data() + at, p.tiles.p, (size_t)p.n_active * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    std::sort(all.begin(), all.end()); // the replicas' lists are ascending and disjoint: the merge
+    *out_count = (int32_t)all.size();
+    if ((size_t)capacity < all.size()) return fail(RTMI_E_ARG, "capacity %d, the frame lists %zu tiles (*out_count holds the number)", capacity, all.size());
+    std::copy(all.begin(), all.end(), out_tiles);
+    return RTMI_OK;
+}
+
+RTMI_EXPORT int rtmi_multi_lit_reset(uint64_t frame) {
+    std::lock_guard<std::mutex> lock(g_multi_mu);
+    MultiLitFrame *f = nullptr;
+    const int rc = lit_frame_of(frame, &f);
+    if (rc) return rc;
+    DeviceGuard guard;
+    return multi_lit_reset(*f);
 }

@@ -126,6 +126,64 @@ class TileRenderer:
             self.ds.ctx.assemble_progressive_device(self.nx, self.ny, self.world, self.per, gathered, self.linear, self.rgb8, self.stderr,
                                                     self.samples, stream)
 
+    def step_lit(self, s_first, s_count, estimator="mis", volume=False, lights=None, light_choice=0, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED,
+                 precision="f64"):
+        """One refinement of the light-sampled frame dealt over the ranks (the one-process-per-GPU form of MultiDevice.lit_render): samples
+        [s_first, s_first + s_count) into this rank's listed tiles (render_lit_tiles_device, or render_lit_ris_device for estimator "ris", on
+        whole-frame buffers the rank holds) -> the records of its dealt tiles (lit_tiles_records_device) -> gather -> (rank 0) assemble into
+        self.linear, self.rgb8, self.stderr, self.samples.  self.lit_counters holds the call's four counters of this rank.  The rank's list is
+        self.lit_tiles[:self.lit_active], all its dealt tiles at first; retire_lit shortens it.  Ordered with torch's current stream as step() is."""
+        if getattr(self, "lit_state", None) is None:
+            f64 = dict(dtype=torch.float64, device=self.dev)
+            own = local_tile_ids(self.nx, self.ny, self.rank, self.world)
+            self.lit_state = torch.zeros((self.nx * self.ny, _ffi.RAYS_REC), **f64)
+            self.lit_linear, self.lit_stderr = torch.zeros((self.ny, self.nx, 3), **f64), torch.zeros((self.ny, self.nx), **f64)
+            self.lit_tiles = torch.tensor(own if own else [0], dtype=torch.int32, device=self.dev)
+            self.lit_active = len(own)
+            self.lit_counters = torch.zeros(4, dtype=torch.int64, device=self.dev)
+            self.lit_rec = torch.zeros((self.per, 64, _ffi.PROG_REC), **f64)
+            if self.rank == 0 and getattr(self, "stderr", None) is None:
+                self.stderr = torch.zeros((self.ny, self.nx), **f64)
+                self.samples = torch.zeros((self.ny, self.nx), dtype=torch.int32, device=self.dev)
+        args = (s_first, s_count, estimator, volume, lights, light_choice, depth, seed, precision)
+        cur = torch.cuda.current_stream(self.dev)
+        if cur.cuda_stream != 0:
+            return self._step_lit(cur.cuda_stream, *args)
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.dev)
+        self._side.wait_stream(cur)
+        with torch.cuda.stream(self._side):
+            self._step_lit(self._side.cuda_stream, *args)
+        cur.wait_stream(self._side)
+
+    def _step_lit(self, stream, s_first, s_count, estimator, volume, lights, light_choice, depth, seed, precision):
+        kw = dict(lights=lights, depth=depth, seed=seed, precision=precision, state=self.lit_state, out_counters=self.lit_counters, stream=stream)
+        if self.lit_active == 0:
+            self.lit_counters.zero_()  # (a call without a tile traces nothing and writes no counter)
+        if isinstance(estimator, str) and estimator == "ris":
+            if volume:
+                raise ValueError("estimator \"ris\" has no volume form")
+            self.ds.render_lit_ris_device(self.nx, self.ny, s_first, s_count, self.lit_linear, self.lit_stderr, None, n_tiles=self.lit_active,
+                                          tiles=self.lit_tiles, **kw)
+        else:
+            self.ds.render_lit_tiles_device(self.nx, self.ny, s_first, s_count, self.lit_active, self.lit_tiles, self.lit_linear, self.lit_stderr, None,
+                                            estimator=estimator, volume=volume, light_choice=light_choice, **kw)
+        self.ds.ctx.lit_tiles_records_device(self.nx, self.ny, self.rank, self.world, self.per, self.lit_state, self.lit_linear, self.lit_stderr,
+                                             self.lit_rec, stream)
+        gathered = gather_tiles(self.lit_rec, self.world, self.rank)
+        if self.rank == 0:
+            self.ds.ctx.assemble_progressive_device(self.nx, self.ny, self.world, self.per, gathered, self.linear, self.rgb8, self.stderr,
+                                                    self.samples, stream)
+
+    def retire_lit(self, eps, noise=None):
+        """tiles_retire_device on this rank's list (noise None: the rank's own stderr plane, valid on exactly its own tiles; else a whole-frame
+        [ny, nx] map on this rank's device) -> tiles still listed on this rank.  Synchronises the current stream once."""
+        cur = torch.cuda.current_stream(self.dev)
+        cur.synchronize()
+        self.lit_active = self.ds.ctx.tiles_retire_device(self.nx, self.ny, self.lit_stderr if noise is None else noise, eps, self.lit_active,
+                                                          self.lit_tiles)
+        torch.cuda.synchronize(self.dev)
+        return self.lit_active
 
     def last_gather_ms(self):
         """milliseconds the last step's gather took on this rank's stream (the transfer plus the wait for the slowest rank)"""
@@ -151,6 +209,7 @@ class MultiDevice:
             self.scenes.append(DeviceScene(flat_scene, ctx=ctx) if not self.scenes else self.scenes[0].clone(ctx))
         self._arr = (C.c_void_p * len(self.scenes))(*[s.handle for s in self.scenes])
         self.n = len(self.scenes)
+        self._lit_frames = {}  # (nx, ny) -> the library's light-sampled frame object (rtmi_multi_lit_create), made on first use
 
     def set_option(self, name, value):
         for ctx in self.ctxs:
@@ -302,6 +361,123 @@ class MultiDevice:
             if active == 0:
                 break
 
+    # ---- one light-sampled frame refined on all replicas (rtmi_multi_lit_*): DeviceScene's lit drivers, same defaults, same shapes ------------------
+    def _lit_frame(self, nx, ny):
+        """the library's frame object for nx x ny, created on first use and kept until close()"""
+        key = (int(nx), int(ny))
+        if key not in self._lit_frames:
+            h = C.c_uint64(0)
+            check(_ffi.lib().rtmi_multi_lit_create(self.n, self._arr, key[0], key[1], C.byref(h)))
+            self._lit_frames[key] = h.value
+        return self._lit_frames[key]
+
+    def _lit_args(self, estimator, volume, lights, light_choice, depth, seed, precision):
+        """-> the arguments of rtmi_multi_lit_render between s_count and the outputs, and what keeps the light list alive"""
+        ds = self.scenes[0]
+        if isinstance(estimator, str) and estimator == "ris":
+            if volume:
+                raise ValueError("estimator \"ris\" has no volume form")
+            est = 3
+        else:
+            est = ds._tiles_estimator(estimator, volume)
+        held, n_listed, _ = (None, 0, 0) if lights is None else ds._direct_lights(lights)
+        return (int(depth), int(seed), est, n_listed, _ffi.ptr(held), ds._light_choice(light_choice), int(bool(volume))), held, {"f64": 0, "f32": 1}[precision]
+
+    def lit_render(self, nx, ny, s_count, estimator="mis", volume=False, lights=None, light_choice=0, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED,
+                   precision="f64"):
+        """rtmi_multi_lit_render: s_count more samples into every listed tile of the nx x ny frame -> (linear, rgb8, stderr [ny, nx], samples int32
+        [ny, nx], the call's four counters summed over the replicas), host arrays, bit for bit one context's"""
+        args, held, prec = self._lit_args(estimator, volume, lights, light_choice, depth, seed, precision)  # held: keeps the light list alive over the call
+        lin, q = np.zeros((ny, nx, 3)), np.zeros((ny, nx, 3), np.uint8)
+        err, smp, cnt = np.zeros((ny, nx)), np.zeros((ny, nx), np.int32), np.zeros(4, np.uint64)
+        check(_ffi.lib().rtmi_multi_lit_render(self._lit_frame(nx, ny), prec, int(s_count), *args, _ffi.ptr(lin), _ffi.ptr(q), _ffi.ptr(err), _ffi.ptr(smp),
+                                               _ffi.ptr(cnt)))
+        return lin, q, err, smp, cnt
+
+    def lit_render_device(self, nx, ny, s_count, out_linear=None, out_rgb8=None, out_stderr=None, out_samples=None, out_counters=None, estimator="mis",
+                          volume=False, lights=None, light_choice=0, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED, precision="f64"):
+        """the same with the outputs resident on devices[0] (rtmi_multi_lit_render_device); returns with every replica's stream synchronised"""
+        args, held, prec = self._lit_args(estimator, volume, lights, light_choice, depth, seed, precision)  # held: keeps the light list alive over the call
+        check(_ffi.lib().rtmi_multi_lit_render_device(self._lit_frame(nx, ny), prec, int(s_count), *args, _ffi.ptr(out_linear), _ffi.ptr(out_rgb8),
+                                                      _ffi.ptr(out_stderr), _ffi.ptr(out_samples), _ffi.ptr(out_counters)))
+
+    def lit_retire(self, nx, ny, eps, noise=None):
+        """rtmi_multi_lit_retire: every replica retires the tiles of its list whose pixels all pass noise <= eps (noise None: its own standard error;
+        else a whole-frame [ny, nx] map -- a host array, or a torch tensor on devices[0]) -> tiles still listed on all replicas"""
+        n = C.c_int32(0)
+        if noise is None or isinstance(noise, np.ndarray):
+            held = None if noise is None else np.ascontiguousarray(noise, np.float64)
+            if held is not None and held.shape != (ny, nx):
+                raise ValueError("noise must have shape (%d, %d)" % (ny, nx))
+            check(_ffi.lib().rtmi_multi_lit_retire(self._lit_frame(nx, ny), _ffi.ptr(held), float(eps), C.byref(n)))
+        else:
+            check(_ffi.lib().rtmi_multi_lit_retire_device(self._lit_frame(nx, ny), _ffi.ptr(noise), float(eps), C.byref(n)))
+        return n.value
+
+    def lit_status(self, nx, ny):
+        """(k = samples the frame's active tiles hold, tiles still listed on all replicas)"""
+        k, a = C.c_int32(0), C.c_int32(0)
+        check(_ffi.lib().rtmi_multi_lit_status(self._lit_frame(nx, ny), C.byref(k), C.byref(a)))
+        return k.value, a.value
+
+    def lit_active_tiles(self, nx, ny):
+        """global tile indices still listed on any replica, int32, ascending"""
+        out, n = np.zeros(max(1, n_tiles(nx, ny)), np.int32), C.c_int32(0)
+        check(_ffi.lib().rtmi_multi_lit_active_tiles(self._lit_frame(nx, ny), len(out), _ffi.ptr(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def lit_reset(self, nx, ny):
+        """k = 0 and every tile listed again (after a camera, material or geometry edit, or to start another frame)"""
+        check(_ffi.lib().rtmi_multi_lit_reset(self._lit_frame(nx, ny)))
+
+    def refine_lit(self, nx, ny, ns, chunk, estimator="mis", volume=False, lights=None, light_choice=0, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED,
+                   precision="f64"):
+        """A fresh light-sampled frame refined uniformly on all replicas: yields (k, linear, rgb8, stderr, counters summed so far) after every chunk"""
+        nx, ny, ns, chunk = int(nx), int(ny), int(ns), int(chunk)
+        if nx <= 0 or ny <= 0 or ns <= 0 or chunk <= 0:
+            raise ValueError("nx, ny, ns and chunk must be > 0")
+        self.lit_reset(nx, ny)
+        total, k = np.zeros(4, np.uint64), 0
+        while k < ns:
+            n = min(chunk, ns - k)
+            lin, q, err, _, cnt = self.lit_render(nx, ny, n, estimator, volume, lights, light_choice, depth, seed, precision)
+            total += cnt
+            k += n
+            yield k, lin, q, err, total.copy()
+
+    def render_lit(self, nx, ny, ns, chunk=None, estimator="mis", volume=False, lights=None, light_choice=0, depth=core.DEFAULT_DEPTH,
+                   seed=core.RENDER_SEED, precision="f64"):
+        """DeviceScene.render_lit / render_lit_vol (volume=True) / render_lit_ris (estimator "ris") for the whole frame, its tiles dealt over the
+        replicas -> (linear, rgb8, stderr, counters summed over the chunks), bit for bit the single context's"""
+        out = None
+        for out in self.refine_lit(nx, ny, ns, ns if chunk is None else chunk, estimator, volume, lights, light_choice, depth, seed, precision):
+            pass
+        return out[1:]
+
+    def refine_lit_adaptive(self, nx, ny, ns, chunk, eps, first=None, estimator="mis", volume=False, lights=None, light_choice=0, denoised=False,
+                            na=core.FEATURE_SAMPLES, iterations=core.DENOISE_ITERATIONS, sigma_c=core.DENOISE_SIGMA_C, sigma_n=core.DENOISE_SIGMA_N,
+                            sigma_a=core.DENOISE_SIGMA_A, sigma_d=core.DENOISE_SIGMA_D, depth=core.DEFAULT_DEPTH, seed=core.RENDER_SEED, precision="f64"):
+        """DeviceScene.refine_lit_adaptive on all replicas: every tile listed on its owner, then rounds of lit_render (`first` samples, default chunk,
+        then `chunk`) each followed by lit_retire -- with denoised=True replica 0 renders the features once, filters the assembled frame each round
+        and its filtered error is the map every replica retires by -- until no tile is listed or ns is reached.  -> (linear, rgb8, stderr, samples,
+        counters summed over the rounds, rounds = [(k, tiles listed after the round's retirement, int32)]), bit for bit the single context's."""
+        first = chunk if first is None else first
+        if nx <= 0 or ny <= 0 or chunk <= 0 or ns <= 0 or first <= 0:
+            raise ValueError("nx, ny, ns, chunk and first must be > 0")
+        dn = (int(iterations), float(sigma_c), float(sigma_n), float(sigma_a), float(sigma_d))
+        self.lit_reset(nx, ny)
+        ft = self.scenes[0].render_features(nx, ny, na, seed, precision)[0] if denoised else None
+        total, rounds, k, active = np.zeros(4, np.uint64), [], 0, n_tiles(nx, ny)
+        lin = q = err = smp = None
+        while k < ns and active:
+            n = min(first if k == 0 else chunk, ns - k)
+            lin, q, err, smp, cnt = self.lit_render(nx, ny, n, estimator, volume, lights, light_choice, depth, seed, precision)
+            total += cnt
+            k += n
+            active = self.lit_retire(nx, ny, eps, self.ctxs[0].denoise(lin, err, ft, *dn)[2] if denoised else None)
+            rounds.append((k, self.lit_active_tiles(nx, ny)))
+        return lin, q, err, smp, total, rounds
+
     def sync(self):
         """wait for every replica (a multi render is complete when replica 0's stream is; the others finished before the gather)"""
         for ctx in self.ctxs:
@@ -323,6 +499,9 @@ class MultiDevice:
         return [ctx.last_trace_ms() for ctx in self.ctxs]
 
     def close(self):
+        for h in self._lit_frames.values():  # the frames go before their scenes
+            _ffi.lib().rtmi_multi_lit_destroy(h)
+        self._lit_frames = {}
         for s in self.scenes:
             s.close()
         for c in self.ctxs:
